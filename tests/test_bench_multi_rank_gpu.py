@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 def test_two_ranks_decode_disjoint_gops_with_matching_checksums():
     env = dict(os.environ, LEON_BENCH_BACKEND="gloo", LEON_BENCH_ONE_DEVICE="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--gops", "4", "--unique", "2", "--steps", "2",
-                          "--warmup", "1", "--no-cpu-baseline", "--no-second-recipe", "--e2e-window", "8", "--e2e-loop", "4"],
+                          "--warmup", "1", "--full", "--no-cpu-baseline", "--no-second-recipe", "--e2e-window", "8", "--e2e-loop", "4"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

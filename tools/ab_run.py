@@ -21,7 +21,7 @@ for spec in args:
     for e in envs:
         k, v = e.split("=", 1)
         env[k] = v
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-second-recipe", "--steps", "20"] + extra,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-second-recipe", "--steps", "20"] + extra,
                          env=env, capture_output=True, text=True)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -31,6 +31,6 @@ tail -n 2 $out/gpu_tests.log
 timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/driver.log 2> $out/driver.err &&
 grep -h "^{" $out/driver.log | tail -n 1 > $out/summary/${tag}_bench_line_driver_command.json &&
 OUT=$out TAG=$tag bash tools/probe/trace_only.sh &&
-timeout -k 10 400 python bench.py > $out/default.log 2> $out/default.err &&
+timeout -k 10 400 python bench.py --full > $out/default.log 2> $out/default.err &&
 grep -h "^{" $out/default.log | tail -n 1 > $out/summary/${tag}_bench_line.json
 ls $out/summary

@@ -8,6 +8,6 @@ OUT=$out TAG=$tag bash tools/probe/trace_only.sh &&
 bash tools/probe/valu_pass.sh $out/valu > $out/summary/${tag}_valu_per_wave.txt 2>&1 &&
 timeout -k 10 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/driver.log 2> $out/driver.err &&
 grep -h "^{" $out/driver.log | tail -1 > $out/summary/${tag}_bench_line_driver_command.json &&
-timeout -k 10 500 python bench.py > $out/default.log 2> $out/default.err &&
+timeout -k 10 500 python bench.py --full > $out/default.log 2> $out/default.err &&
 grep -h "^{" $out/default.log | tail -1 > $out/summary/${tag}_bench_line.json
 ls $out/summary

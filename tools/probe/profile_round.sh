@@ -7,7 +7,7 @@ out=${1:-gpurun_out/prof}
 mkdir -p $out
 # (--no-placement: the start-up step that draws every region twice launches the same kernels on the draws it rejects; the trace
 #  and the counters are to show the launches of the steps)
-B="python3 bench.py --no-cpu-baseline --no-second-recipe --no-end-to-end --no-placement"
+B="python3 bench.py --full --no-cpu-baseline --no-second-recipe --no-end-to-end --no-placement"
 S="$B --steps 2 --warmup 1"
 echo "== trace";  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/kt --output-format csv -- $B > $out/kt.log 2>&1 || echo "trace failed"
 echo "== fetch";  timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d $out/pf --output-format csv -- $S > $out/pf.log 2>&1 || echo "fetch failed"
@@ -32,5 +32,5 @@ echo "== calibration"; ./tools/probe/fetch_calib.bin > $out/calib_plain.json
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d $out/cal_fetch --output-format csv -- ./tools/probe/fetch_calib.bin > $out/cal_fetch.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_BUBBLE_sum -d $out/cal_raw --output-format csv -- ./tools/probe/fetch_calib.bin > $out/cal_raw.log 2>&1
 fi
-timeout -k 10 400 python bench.py > $out/summary/${tag}_bench_line.json 2> $out/bench.err; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full > $out/summary/${tag}_bench_line.json 2> $out/bench.err; echo "bench rc=$?"
 echo done

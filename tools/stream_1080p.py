@@ -3,7 +3,7 @@
 2 closed GOPs (24 pictures, 0.82 Mbit each), written by tools/jsv_writer.py from the seeded recipe of synth.py (seed
 0x4C454F4E, the recipe of SURVEY.md 8d config 4).  Deterministic: the bytes are pinned by their SHA-256 below.  The file
 (tools/probe/stream_1080p_2gop.bin, 2.4 MB) is git-ignored; `ensure()` writes it when it is absent -- 30 s of pure
-Python -- so a clean clone has it after __graft_entry__.build(), and the GPU box gets it with the tree.
+Python -- so the first user in a clean clone (a test, bench.py --full) writes it and later ones read it.
 
   python tools/stream_1080p.py            # write it if it is not there, print its path"""
 import hashlib
