@@ -48,9 +48,7 @@ typedef struct leon_pipeline_config {
      * the stream's own index, decoders/jsv.js:264-350).  shard_count <= 1: everything. */
     int32_t shard_index, shard_count;
     /* = jsv.prototype.seek (decoders/jsv.js:1618-1648) at start-up: begin with the key-map entry at or before this
-     * time (seconds) instead of the first one; 0 = from the start.  (A running pipeline is not repositioned: a
-     * host seeks by destroying it and creating one at the new time, as the reference frees all its output
-     * buffers on a seek, jsv.js:1623.) */
+     * time (seconds) instead of the first one; 0 = from the start.  A running pipeline moves with leon_pipeline_seek. */
     double start_seconds;
     /* Where the slice layer is decoded (everything below a slice start code: macroblock headers, vectors, coefficients
      * -- decodeSlice .. decodeBlockGL, decoders/jsv.js:683-1525):
@@ -133,6 +131,24 @@ int leon_pipeline_release_window(leon_pipeline* p, int64_t window);
  * first error.  Not to be called from inside the callback. */
 int leon_pipeline_wait(leon_pipeline* p);
 int leon_pipeline_get_stats(leon_pipeline* p, leon_pipeline_stats* out);
+
+/* Repositioning a running pipeline = jsv.prototype.seek (decoders/jsv.js:1618-1648), without the allocations of create:
+ *   LEON_PIPELINE_SEEK_KEY    from the key-map entry start_seconds = `seconds` would start with: the frames from
+ *                             *first_window on are those of a pipeline created with that start_seconds (shards honoured)
+ *   LEON_PIPELINE_SEEK_EXACT  from the same entry, but the first frame delivered is the one on screen at `seconds` (the
+ *                             largest ts_ms <= seconds * 1000 of that GOP, or its first frame): earlier I and P pictures
+ *                             are reconstructed for what predicts from them but not delivered, earlier B pictures are not
+ *                             decoded.  With shard_count > 1 only the shard that owns the entry trims.
+ * *first_window = the id of the first window of the new position (window ids count on across seeks).  Once seek returns
+ * no callback starts for a window below it (a callback under way has returned); windows submitted for the old position
+ * are drained and never delivered; windows delivered and not released stay valid until released.  After 'ended' a seek
+ * starts a new run with its own 'ended'; leon_pipeline_wait waits for the current run; stats accumulate.  A partial
+ * stream may be seeked past what has arrived.  Refused (LEON_ERR_INVALID, nothing changes): loop > 1, a failed
+ * pipeline, a call from inside the callback, another mode, a non-finite time.  Any host thread but the callback's,
+ * not concurrently with leon_pipeline_destroy. */
+#define LEON_PIPELINE_SEEK_KEY   0
+#define LEON_PIPELINE_SEEK_EXACT 1
+int leon_pipeline_seek(leon_pipeline* p, double seconds, int32_t mode, int64_t* first_window);
 /* copy one frame of a delivered, not yet released window to host memory (tests, thumbnails) */
 int leon_pipeline_read_frame(leon_pipeline* p, const leon_pipeline_frame* f, uint8_t* rgba_host);
 const char* leon_pipeline_error(leon_pipeline* p);

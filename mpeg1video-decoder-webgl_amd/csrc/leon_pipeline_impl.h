@@ -9,7 +9,9 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <cmath>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -23,6 +25,7 @@ struct PipePic {                 // one parsed picture: offsets of its arrays in
     double ts_ms;
     size_t grp_off, entries, qscale, intra, repadd, mb_dir, mv_fwd, mv_bwd;   // (size_t)-1: absent
     int32_t qm = -1;             // index into its GOP's `qms` (matrices of the sequence header in force), -1: the stream's first
+    bool shown = true;           // false: reconstructed for the pictures that predict from it, not converted nor delivered (trim_to_target)
 };
 
 struct Arena {                   // pinned host buffer + its device twin, one GOP at a time
@@ -32,7 +35,18 @@ struct Arena {                   // pinned host buffer + its device twin, one GO
     bool host_owned = true, dev_owned = true;    // false: a piece of the pipeline's slabs (gpu_parser), not to be freed
 };
 
+// One position of the pipeline: the one leon_pipeline_create starts at, then one per leon_pipeline_seek.  The parser and
+// submit threads work for the current run (leon_pipeline::run) only; what they hold of an earlier one is dropped.
+struct PipeRun {
+    std::vector<uint32_t> mine;  // key-map ids the run decodes, in order (this shard's, from the entry it starts with)
+    uint32_t first_key = 0;      // the key-map entry it starts with
+    uint64_t total_gops = 0;     // mine.size() * loop
+    int64_t total_windows = 0;
+    double exact_ms = -1;        // LEON_PIPELINE_SEEK_EXACT: the first GOP's frames start at the one on screen at this time; < 0: all
+};
+
 struct GopJob {
+    std::shared_ptr<const PipeRun> run;      // the run it was parsed for
     bool open_gop = false;       // its GOP header says closed_gop = 0
     uint64_t gop = 0;            // running index among the GOPs of this pipeline
     uint64_t key_gop = 0;        // GOP id in the stream (key-map index, counting on across loops)
@@ -53,6 +67,7 @@ struct GopJob {
 };
 
 struct PipeWindow {
+    std::shared_ptr<const PipeRun> run;
     int64_t id = 0;
     int ring = 0;
     std::vector<GopJob*> jobs;
@@ -85,8 +100,8 @@ struct leon_pipeline {
     void* user = nullptr;
     leon_vlc_info vinfo{};
     std::vector<uint64_t> shard_begin, shard_end;     // byte ranges of the GOP shards
-    std::vector<uint32_t> mine;                       // key-map ids this pipeline decodes (all, or g % shard_count == shard_index)
-    uint64_t total_gops = 0;                          // gops * loop
+    std::vector<uint32_t> shard_gops;                 // key-map ids this pipeline may decode (all, or g % shard_count == shard_index)
+    bool has_keymap = false;
     int W = 32, R = 2, K = 1, max_pics = 16;
     std::vector<double> st_window_done;                      // LEON_DEBUG_PIPE_TIMING: when each window completed (seconds from the start)
     uint64_t st_wait_ring_ns = 0, st_wait_scan_ns = 0;       // submit thread: waiting for a ring entry / for the window's GOPs to be parsed
@@ -112,13 +127,19 @@ struct leon_pipeline {
 
     std::mutex mu;
     std::condition_variable cv;
-    std::atomic<uint64_t> next_gop{0};
-    std::map<uint64_t, GopJob*> parsed;               // waiting for the submit thread
+    // the current run and how far it is; a seek replaces the run and starts these over (under mu)
+    std::shared_ptr<const PipeRun> run, ended_run;    // ended_run: the last run whose 'ended' callback has returned
+    uint64_t next_gop = 0;                            // next GOP of the run for a parser thread
+    int64_t run_submitted = 0, run_done = 0;          // windows of the run submitted / delivered
+    bool run_ended = false;                           // its 'ended' callback is out
+    int64_t next_window = 0;                          // window ids count on across runs
+    bool in_callback = false;                         // the notify thread is inside the callback
+    std::map<uint64_t, GopJob*> parsed;               // waiting for the submit thread (GOP of the current run -> job)
     std::deque<Arena*> free_arenas;
     std::deque<PipeWindow*> to_notify;
     std::vector<int64_t> ring_owner;                  // window id holding a ring entry, -1 free
     std::map<int64_t, PipeWindow*> delivered;         // waiting for release
-    int64_t windows_submitted = 0, windows_done = 0, total_windows = 0;
+    int64_t windows_submitted = 0, windows_done = 0;      // over all runs
     bool stop = false, finished = false, quiet = false, submit_exited = false;
     int status = LEON_OK;
     std::string err;
@@ -326,8 +347,9 @@ void scan_gop_for_gpu(leon_pipeline* p, GopJob* job, leon_vlc_stream* st, const 
 void parse_gop(leon_pipeline* p, GopJob* job)
 {
     // job->gop counts the GOPs this pipeline decodes; which key-map entry that is:
-    const uint64_t g = p->mine[job->gop % p->mine.size()];
-    job->key_gop = (job->gop / p->mine.size()) * p->shard_begin.size() + g;      // id in the whole (looped) stream
+    const std::vector<uint32_t>& mine = job->run->mine;
+    const uint64_t g = mine[job->gop % mine.size()];
+    job->key_gop = (job->gop / mine.size()) * p->shard_begin.size() + g;      // id in the whole (looped) stream
     const uint8_t* b = p->stream + p->shard_begin[g];
     const size_t n = (size_t)(p->shard_end[g] - p->shard_begin[g]);
     leon_vlc_stream* st = nullptr;
@@ -404,46 +426,96 @@ void parse_gop(leon_pipeline* p, GopJob* job)
     }
 }
 
+// LEON_PIPELINE_SEEK_EXACT: the first GOP of the run delivers its frames from the one on screen at t_ms on (the largest
+// ts_ms <= t_ms; none: the GOP's first frame, i.e. all of them).  B pictures before it are dropped -- neither parsed on the
+// GPU nor launched --, I and P pictures before it are still reconstructed (later pictures predict from them) but not
+// converted to RGBA and not delivered.
+void trim_to_target(leon_pipeline* p, GopJob* job, double t_ms)
+{
+    const double rate = p->vinfo.picture_rate > 0 ? p->vinfo.picture_rate : 25.0;
+    int target = -1;                 // same arithmetic as the frames' ts_ms (submit_window)
+    for (const PipePic& m : job->pics)
+        if (job->gop_ts_ms + 1000.0 * (double)m.tref / rate <= t_ms) target = std::max(target, m.tref);
+    if (target < 0) return;
+    std::vector<PipePic> pics;
+    std::vector<leon::VlcPic> vpics;
+    std::vector<int> renum(job->pics.size(), -1);
+    for (size_t k = 0; k < job->pics.size(); k++) {
+        PipePic m = job->pics[k];
+        if (m.tref < target) {
+            if (m.type == LEON_PIC_B) continue;
+            m.shown = false;
+        }
+        renum[k] = (int)pics.size();
+        pics.push_back(m);
+        if (k < job->vpics.size()) vpics.push_back(job->vpics[k]);
+    }
+    std::vector<leon::VlcSlice> slices;       // (in picture order, as launch_gpu_parser walks them)
+    for (leon::VlcSlice sl : job->slices)
+        if (renum[sl.pic] >= 0) {
+            sl.pic = (uint32_t)renum[sl.pic];
+            slices.push_back(sl);
+        }
+    job->pics.swap(pics);
+    job->vpics.swap(vpics);
+    job->slices.swap(slices);
+}
+
 void parser_main(leon_pipeline* p)
 {
     hipSetDevice(p->cfg.device_id);
     for (;;) {
         Arena* a = nullptr;
         uint64_t g;
+        std::shared_ptr<const PipeRun> run;
         {
             std::unique_lock<std::mutex> lk(p->mu);
-            // an arena is the ticket to parse ahead: there are W * (R + 1) of them
-            p->cv.wait(lk, [&] { return p->stop || !p->free_arenas.empty(); });
+            // an arena is the ticket to parse ahead: there are W * (R + 1) of them; once every GOP of the run is taken
+            // the thread waits for a seek
+            p->cv.wait(lk, [&] { return p->stop || (!p->free_arenas.empty() && p->next_gop < p->run->total_gops); });
             if (p->stop) return;
-            g = p->next_gop.load();
-            if (g >= p->total_gops) return;
-            p->next_gop = g + 1;
+            run = p->run;
+            g = p->next_gop++;
             a = p->free_arenas.front();
             p->free_arenas.pop_front();
         }
         GopJob* job = new GopJob();
+        job->run = run;
         job->gop = g;
         job->arena = a;
+        const uint32_t key = run->mine[g % run->mine.size()];
+        bool dropped = false;
         {   // a stream that is still arriving (leon_pipeline_create_partial): the GOP's bytes must be there -- the
             // decoder of the reference stalls the same way when its buffer runs dry (features/bitreader.js:135-189)
-            const uint64_t need = p->shard_end[p->mine[g % p->mine.size()]];
+            const uint64_t need = p->shard_end[key];
             std::unique_lock<std::mutex> lk(p->mu);
-            p->cv.wait(lk, [&] { return p->stop || p->valid >= need; });
+            p->cv.wait(lk, [&] { return p->stop || p->valid >= need || p->run != run; });
             if (p->stop) { p->free_arenas.push_back(a); delete job; return; }
+            if (p->run != run) {         // seeked away from while waiting
+                p->free_arenas.push_back(a);
+                delete job;
+                dropped = true;
+            }
         }
+        if (dropped) { p->cv.notify_all(); continue; }
         {
-            const uint8_t* b = p->stream + p->shard_begin[p->mine[g % p->mine.size()]];
+            const uint8_t* b = p->stream + p->shard_begin[key];
             if (b[0] != 0 || b[1] != 0 || b[2] != 1) {
                 job->status = LEON_ERR_INVALID;
-                job->err = "key map entry " + std::to_string(p->mine[g % p->mine.size()]) + " does not point at a start code";
+                job->err = "key map entry " + std::to_string(key) + " does not point at a start code";
             }
         }
         const auto t = Clock::now();
         if (job->status == LEON_OK) parse_gop(p, job);
+        if (job->status == LEON_OK && g == 0 && run->exact_ms >= 0) trim_to_target(p, job, run->exact_ms);
         p->st_parse_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t).count();
         {
             std::lock_guard<std::mutex> lk(p->mu);
-            p->parsed[g] = job;
+            if (p->run == run) p->parsed[g] = job;
+            else {                       // a GOP of a run seeked away from
+                p->free_arenas.push_back(job->arena);
+                delete job;
+            }
         }
         p->cv.notify_all();
     }
@@ -688,7 +760,7 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
             sp.mb_dir = (const uint8_t*)ptr(m.mb_dir);
             sp.mv_fwd = (const int16_t*)ptr(m.mv_fwd);
             sp.mv_bwd = (const int16_t*)ptr(m.mv_bwd);
-            sp.rgba_out = p->unfused ? nullptr : ring + ((size_t)it.lane * p->max_pics + (size_t)m.tref) * p->frame_bytes;
+            sp.rgba_out = p->unfused || !m.shown ? nullptr : ring + ((size_t)it.lane * p->max_pics + (size_t)m.tref) * p->frame_bytes;
             sp.no_planes = !p->unfused && m.type == LEON_PIC_B;
             sp.qm_set = m.qm >= 0 ? qset[it.lane][(size_t)m.qm] : 0;
             batch.push_back(sp);
@@ -698,6 +770,7 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
         if (rc != LEON_OK) return rc;
         if (p->unfused)
             for (const Item& it : lvl) {
+                if (!it.pic->shown) continue;
                 rc = leon_convert_rgba(d, it.out, ring + ((size_t)it.lane * p->max_pics + (size_t)it.pic->tref) * p->frame_bytes, LEON_MEM_DEVICE, p->flavour);
                 if (rc != LEON_OK) return rc;
             }
@@ -730,7 +803,7 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
         std::vector<const PipePic*> by_disp((size_t)p->max_pics, nullptr);
         for (const PipePic& m : job->pics) by_disp[(size_t)m.tref] = &m;
         for (size_t k = 0; k < by_disp.size(); k++) {
-            if (!by_disp[k]) continue;
+            if (!by_disp[k] || !by_disp[k]->shown) continue;
             leon_pipeline_frame f{};
             f.gop = job->key_gop;
             f.display_index = (int32_t)k;
@@ -759,36 +832,48 @@ void submit_main(leon_pipeline* p)
 
 void submit_loop(leon_pipeline* p)
 {
-    for (int64_t wid = 0; wid < p->total_windows; wid++) {
+    for (;;) {
         PipeWindow* w = new PipeWindow();
-        w->id = wid;
         const auto t_begin = Clock::now();
         auto t_ring = t_begin, t_scanned = t_begin;
-        const uint64_t g0 = (uint64_t)wid * p->W, g1 = std::min<uint64_t>(g0 + p->W, p->total_gops);
         {
             std::unique_lock<std::mutex> lk(p->mu);
-            // a free entry of the RGBA ring, then every GOP of the window parsed
-            p->cv.wait(lk, [&] {
-                if (p->stop) return true;
+            // a window of the current run to submit (once the run is all submitted the thread waits for a seek), a free entry
+            // of the RGBA ring, then every GOP of the window parsed.  A seek in between: the ring entry goes back, and the
+            // window is taken from the new run.
+            for (;;) {
+                p->cv.wait(lk, [&] {
+                    if (p->stop) return true;
+                    if (p->run_submitted >= p->run->total_windows) return false;
+                    for (int r = 0; r < p->R; r++)
+                        if (p->ring_owner[r] < 0) return true;
+                    return false;
+                });
+                if (p->stop) { delete w; return; }
+                t_ring = Clock::now();
+                w->run = p->run;
+                w->id = p->next_window++;
                 for (int r = 0; r < p->R; r++)
-                    if (p->ring_owner[r] < 0) return true;
-                return false;
-            });
-            if (p->stop) { delete w; return; }
-            t_ring = Clock::now();
-            for (int r = 0; r < p->R; r++)
-                if (p->ring_owner[r] < 0) { w->ring = r; p->ring_owner[r] = wid; break; }
-            p->cv.wait(lk, [&] {
-                if (p->stop) return true;
-                for (uint64_t g = g0; g < g1; g++)
-                    if (!p->parsed.count(g)) return false;
-                return true;
-            });
-            if (p->stop) { delete w; return; }
-            t_scanned = Clock::now();
-            for (uint64_t g = g0; g < g1; g++) {
-                w->jobs.push_back(p->parsed[g]);
-                p->parsed.erase(g);
+                    if (p->ring_owner[r] < 0) { w->ring = r; p->ring_owner[r] = w->id; break; }
+                const uint64_t g0 = (uint64_t)p->run_submitted * p->W, g1 = std::min<uint64_t>(g0 + p->W, w->run->total_gops);
+                p->cv.wait(lk, [&] {
+                    if (p->stop || p->run != w->run) return true;
+                    for (uint64_t g = g0; g < g1; g++)
+                        if (!p->parsed.count(g)) return false;
+                    return true;
+                });
+                if (p->stop) { delete w; return; }
+                if (p->run != w->run) {
+                    p->ring_owner[w->ring] = -1;
+                    continue;
+                }
+                t_scanned = Clock::now();
+                for (uint64_t g = g0; g < g1; g++) {
+                    w->jobs.push_back(p->parsed[g]);
+                    p->parsed.erase(g);
+                }
+                p->run_submitted++;
+                break;
             }
         }
         int rc = LEON_OK;
@@ -811,7 +896,7 @@ void submit_loop(leon_pipeline* p)
             p->st_wait_scan_ns += ns(t_ring, t_scanned);
         }
         if (rc != LEON_OK) pipe_fail(p, rc, msg);
-        {
+        {   // (a window of a run seeked away from meanwhile goes the same way: the notify thread drains it)
             std::lock_guard<std::mutex> lk(p->mu);
             p->to_notify.push_back(w);
             p->windows_submitted++;
@@ -837,17 +922,49 @@ void notify_main(leon_pipeline* p)
     hipSetDevice(p->cfg.device_id);
     for (;;) {
         PipeWindow* w = nullptr;
+        std::shared_ptr<const PipeRun> ended;
+        bool quiet;
         {
             std::unique_lock<std::mutex> lk(p->mu);
-            p->cv.wait(lk, [&] { return !p->to_notify.empty() || p->windows_done == p->total_windows || p->submit_exited; });
-            if (p->to_notify.empty()) break;
-            w = p->to_notify.front();
-            p->to_notify.pop_front();
+            p->cv.wait(lk, [&] {
+                return !p->to_notify.empty() || p->submit_exited ||
+                       (!p->stop && !p->run_ended && p->run_done == p->run->total_windows);
+            });
+            if (!p->to_notify.empty()) {
+                w = p->to_notify.front();
+                p->to_notify.pop_front();
+            } else if (p->submit_exited) break;
+            else {      // every window of the run delivered: its 'ended'; the thread stays for the next seek
+                p->run_ended = true;
+                p->in_callback = true;
+                ended = p->run;
+            }
+            quiet = p->quiet;
+        }
+        if (ended) {
+            if (p->cb && !quiet) p->cb(p->user, -1, nullptr, 0, LEON_OK);
+            {
+                std::lock_guard<std::mutex> lk(p->mu);
+                p->in_callback = false;
+                p->ended_run = ended;
+            }
+            p->cv.notify_all();
+            continue;
         }
         if (w->status == LEON_OK && hipEventSynchronize(w->done) != hipSuccess) {
             w->status = LEON_ERR_HIP;
             pipe_fail(p, LEON_ERR_HIP, std::string("window ") + std::to_string(w->id) + ": " + hipGetErrorString(hipGetLastError()));
         }
+        {   // a window of a run seeked away from: drained -- its launches have finished (the event above), its ring entry,
+            // arenas and descriptor ring entry go back -- and never delivered.  Once a window is past this point a seek
+            // waits for its callback to return (in_callback).
+            std::lock_guard<std::mutex> lk(p->mu);
+            if (w->run != p->run && w->status == LEON_OK) {
+                release_window_locked(p, w);
+                w = nullptr;
+            } else p->in_callback = true;
+        }
+        if (!w) { p->cv.notify_all(); continue; }
         if (w->status == LEON_OK && p->gpu_parser && w->n_vpics) {          // the GPU parser's verdict on every picture of the window
             const uint32_t* e = p->vlc_ring[(size_t)w->ring].h_err;
             for (uint32_t k = 0; k < w->n_vpics; k++)
@@ -865,7 +982,7 @@ void notify_main(leon_pipeline* p)
         }
         const int64_t id = w->id;
         const int st = w->status;
-        bool quiet;
+        const std::shared_ptr<const PipeRun> run = w->run;
         {
             std::lock_guard<std::mutex> lk(p->mu);
             p->delivered[id] = w;
@@ -879,6 +996,8 @@ void notify_main(leon_pipeline* p)
         {
             std::lock_guard<std::mutex> lk(p->mu);
             p->windows_done++;
+            if (run == p->run) p->run_done++;
+            p->in_callback = false;
         }
         p->cv.notify_all();
     }
@@ -895,6 +1014,24 @@ void notify_main(leon_pipeline* p)
         p->finished = true;
     }
     p->cv.notify_all();
+}
+
+// The run that starts at `seconds`: the key-map entry the front end's own seek finds (leon_vlc_seek, decoders/jsv.js
+// :327-350), then this shard's entries from it on.  leon_pipeline_create (start_seconds) and leon_pipeline_seek both
+// ask here; `st` is a stream opened on the pipeline's bytes (its container header and key map).
+std::shared_ptr<PipeRun> make_run(const leon_pipeline* p, leon_vlc_stream* st, double seconds, int loops)
+{
+    auto run = std::make_shared<PipeRun>();
+    if (p->has_keymap && seconds > 0) {
+        uint64_t off = 0;
+        if (leon_vlc_seek(st, seconds, &off) == LEON_VLC_OK)
+            for (size_t g = 0; g < p->shard_begin.size(); g++)
+                if (p->shard_begin[g] == off) run->first_key = (uint32_t)g;
+    }
+    for (uint32_t g : p->shard_gops)
+        if (g >= run->first_key) run->mine.push_back(g);
+    run->total_gops = (uint64_t)run->mine.size() * (uint64_t)loops;
+    return run;
 }
 
 }  // namespace
@@ -934,14 +1071,6 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     const int n_keys = leon_vlc_get_keymap(st, nullptr, nullptr, 0);
     std::vector<uint32_t> offs((size_t)std::max(n_keys, 0));
     if (n_keys > 0) leon_vlc_get_keymap(st, offs.data(), nullptr, (uint32_t)n_keys);
-    uint32_t first_gop = 0;
-    if (n_keys > 0 && cfg->start_seconds > 0) {       // the front end's own seek finds the entry (decoders/jsv.js:327-350)
-        uint64_t off = 0;
-        if (leon_vlc_seek(st, cfg->start_seconds, &off) == LEON_VLC_OK)
-            for (int g = 0; g < n_keys; g++)
-                if (offs[(size_t)g] == off) first_gop = (uint32_t)g;
-    }
-    leon_vlc_close(st);
     p->cfg = *cfg;
     p->stream = stream;
     p->bytes = bytes;
@@ -954,6 +1083,7 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
             const uint64_t b = offs[(size_t)g], e = g + 1 < n_keys ? offs[(size_t)g + 1] : bytes;
             // (an entry behind what has arrived of a partial stream is looked at when its bytes are there: parser_main)
             if (b >= e || e > bytes || b + 4 > bytes || (b + 4 <= valid_bytes && (stream[b] != 0 || stream[b + 1] != 0 || stream[b + 2] != 1))) {
+                leon_vlc_close(st);
                 delete p;
                 return fail(LEON_ERR_INVALID, "key map entry %d does not point at a start code", g);
             }
@@ -969,20 +1099,23 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     }
     const int loops = cfg->loop > 0 ? cfg->loop : 1;
     const uint32_t sc = cfg->shard_count > 1 ? (uint32_t)cfg->shard_count : 1u, si = sc > 1 ? (uint32_t)cfg->shard_index : 0u;
-    if (si >= sc) { delete p; return fail(LEON_ERR_INVALID, "shard_index %d of %d", cfg->shard_index, cfg->shard_count); }
-    for (uint32_t g = si; g < p->shard_begin.size(); g += sc)
-        if (g >= first_gop) p->mine.push_back(g);
-    p->info.first_gop = first_gop;
-    if (p->mine.empty()) { delete p; return fail(LEON_ERR_INVALID, "shard %u of %u gets no GOP: the stream has %zu", si, sc, p->shard_begin.size()); }
-    p->total_gops = (uint64_t)p->mine.size() * (uint64_t)loops;
+    if (si >= sc) { leon_vlc_close(st); delete p; return fail(LEON_ERR_INVALID, "shard_index %d of %d", cfg->shard_index, cfg->shard_count); }
+    p->has_keymap = n_keys > 0;
+    for (uint32_t g = si; g < p->shard_begin.size(); g += sc) p->shard_gops.push_back(g);
+    const std::shared_ptr<PipeRun> run0 = make_run(p, st, cfg->start_seconds, loops);
+    leon_vlc_close(st);
+    p->run = run0;
+    const PipeRun& run = *run0;
+    p->info.first_gop = run.first_key;
+    if (run.mine.empty()) { delete p; return fail(LEON_ERR_INVALID, "shard %u of %u gets no GOP: the stream has %zu", si, sc, p->shard_begin.size()); }
     p->W = cfg->gops_per_window > 0 ? cfg->gops_per_window : 32;
-    if ((uint64_t)p->W > p->total_gops) p->W = (int)p->total_gops;
+    if ((uint64_t)p->W > run.total_gops) p->W = (int)run.total_gops;
     p->gpu_parser = cfg->gpu_parser >= 0;          // 0 = default: the GPU (a pipeline has a device by construction); < 0: the parser threads
     if (cfg->gpu_parser == LEON_PIPELINE_PARSER_DEFAULT) {
         // a caller who did not ASK for the GPU parser is not refused for its limits: a picture whose group counters do not fit
         // k_vlc_index's LDS, or a GOP shard of 2^28 bytes and more (the kernels count bits in 32), goes to the parser threads
         bool fits = ((size_t)p->vinfo.n_groups + leon::kVlcIndexThreads) * 4 <= (size_t)160 * 1024 - 512;
-        for (uint32_t g : p->mine) fits = fits && p->shard_end[g] - p->shard_begin[g] < ((uint64_t)1 << 28);
+        for (uint32_t g : p->shard_gops) fits = fits && p->shard_end[g] - p->shard_begin[g] < ((uint64_t)1 << 28);
         if (getenv("LEON_DEBUG_GPU_PARSER_LIMIT") && p->vinfo.n_groups > atoi(getenv("LEON_DEBUG_GPU_PARSER_LIMIT"))) fits = false;      // tests: a mocked n_groups limit
         if (!fits) p->gpu_parser = false;
     }
@@ -993,9 +1126,10 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     else {
         // the frames a GOP can fill in a window's ring entry: the longest GOP of this pipeline's shards, from the picture
         // start codes (00 00 01 00 -- the syntax keeps that pattern out of everything else); a fixed 16 would reserve a
-        // third more than IBBP-12 streams use
+        // third more than IBBP-12 streams use.  (Every GOP of the shard, not only those from start_seconds on: a seek may
+        // go back to them.)
         size_t longest = 1;
-        for (uint64_t g : p->mine) {
+        for (uint64_t g : p->shard_gops) {
             const uint8_t* b = stream + p->shard_begin[g];
             const uint8_t* const e = stream + p->shard_end[g];
             size_t n = 0;
@@ -1011,13 +1145,13 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     int k = cfg->parser_threads;
     if (k <= 0) { k = (int)std::thread::hardware_concurrency(); if (k < 1) k = 1; if (k > 16) k = 16; }
     p->K = k;
-    p->total_windows = (int64_t)((p->total_gops + p->W - 1) / p->W);
+    run0->total_windows = (int64_t)((run.total_gops + p->W - 1) / p->W);
     p->frame_bytes = (size_t)p->vinfo.frame_width * p->vinfo.frame_height * 4;
     p->info.coded_width = p->vinfo.coded_width; p->info.coded_height = p->vinfo.coded_height;
     p->info.frame_width = p->vinfo.frame_width; p->info.frame_height = p->vinfo.frame_height;
     p->info.picture_rate = p->vinfo.picture_rate; p->info.duration = p->vinfo.duration;
     p->info.gops = (uint32_t)p->shard_begin.size();
-    p->info.shard_gops = (uint32_t)p->mine.size();
+    p->info.shard_gops = (uint32_t)run.mine.size();
     p->info.parser_threads = p->K; p->info.gops_per_window = p->W;
     // the fused display conversion writes eight pixels per lane: it needs frame_width % 8 == 0.  The reference crops to
     // any width (player/easybits.player.js:2818): such a stream takes the slow road -- every picture (B pictures too)
@@ -1162,7 +1296,7 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
         // a 1080p run took 35-40 ms each instead of 8.6.  A GOP that still does not fit gets an allocation of its own
         // (arena_reserve); without the memory for the slabs everything does.
         size_t largest = 0;
-        for (uint64_t g : p->mine) largest = std::max(largest, (size_t)(p->shard_end[g] - p->shard_begin[g]));
+        for (uint64_t g : p->shard_gops) largest = std::max(largest, (size_t)(p->shard_end[g] - p->shard_begin[g]));
         const size_t mbs = (size_t)p->vinfo.mb_width * p->vinfo.mb_height;
         const size_t per_pic = pad256(mbs * leon::kVlcMbRecBytes) + 4 * pad256(mbs) + 2 * pad256(mbs * 4) + pad256(((size_t)p->vinfo.n_groups + 1) * 4) + 1024 +
                                pad256(mbs * (size_t)leon::vlc_blocks_per_mb(p->vinfo.has_alpha == 1) * leon::kVlcRecWords * 4) +
@@ -1196,6 +1330,7 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
 int leon_pipeline_get_info(leon_pipeline* p, leon_pipeline_info* out)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(p->mu);
     *out = p->info;
     return LEON_OK;
 }
@@ -1218,8 +1353,50 @@ int leon_pipeline_wait(leon_pipeline* p)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
     std::unique_lock<std::mutex> lk(p->mu);
-    p->cv.wait(lk, [&] { return p->finished; });
+    p->cv.wait(lk, [&] { return p->finished || p->ended_run == p->run; });      // the current run
     if (p->status != LEON_OK) return fail(p->status, "%s", p->err.c_str());
+    return LEON_OK;
+}
+
+int leon_pipeline_seek(leon_pipeline* p, double seconds, int32_t mode, int64_t* first_window)
+{
+    if (!p || !first_window) return fail(LEON_ERR_INVALID, "null argument");
+    if (mode != LEON_PIPELINE_SEEK_KEY && mode != LEON_PIPELINE_SEEK_EXACT) return fail(LEON_ERR_INVALID, "seek mode %d", mode);
+    if (!std::isfinite(seconds)) return fail(LEON_ERR_INVALID, "seek to a time that is not finite");
+    if (p->cfg.loop > 1) return fail(LEON_ERR_INVALID, "a pipeline that loops over the stream (loop = %d, benchmarking) does not seek", p->cfg.loop);
+    if (std::this_thread::get_id() == p->notifier.get_id()) return fail(LEON_ERR_INVALID, "leon_pipeline_seek from inside the pipeline's callback");
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->status != LEON_OK) return fail(LEON_ERR_INVALID, "the pipeline has failed: %s", p->err.c_str());
+    }
+    // the key map through a view of the pipeline's own bytes: nothing is copied, and a partial stream may be seeked
+    // past what has arrived (the parser threads wait for leon_pipeline_feed, as after create)
+    leon_vlc_stream* st = nullptr;
+    if (p->has_keymap && seconds > 0 && leon_vlc_open_scan(p->stream, p->bytes - 16, p->bytes, p->vinfo.has_alpha, &st) != LEON_VLC_OK)
+        return fail(LEON_ERR_INVALID, "stream: %s", leon_vlc_last_error());
+    const std::shared_ptr<PipeRun> run = make_run(p, st, seconds, 1);
+    if (st) leon_vlc_close(st);
+    run->total_windows = (int64_t)((run->total_gops + p->W - 1) / p->W);
+    // EXACT: the shard that owns the entry trims its first GOP (trim_to_target); the others decode from their next GOP on
+    if (mode == LEON_PIPELINE_SEEK_EXACT && !run->mine.empty() && run->mine[0] == run->first_key) run->exact_ms = std::max(seconds, 0.0) * 1000.0;
+    std::unique_lock<std::mutex> lk(p->mu);
+    if (p->status != LEON_OK) return fail(LEON_ERR_INVALID, "the pipeline has failed: %s", p->err.c_str());
+    p->run = run;
+    p->next_gop = 0;
+    p->run_submitted = p->run_done = 0;
+    p->run_ended = false;
+    *first_window = p->next_window;
+    // what was parsed for the old position goes back; GOPs still on the parser threads are dropped when they are done,
+    // windows submitted and not delivered are drained by the notify thread (notify_main), held windows stay held
+    for (auto& kv : p->parsed) {
+        p->free_arenas.push_back(kv.second->arena);
+        delete kv.second;
+    }
+    p->parsed.clear();
+    p->info.first_gop = run->first_key;
+    p->info.shard_gops = (uint32_t)run->mine.size();
+    p->cv.notify_all();
+    p->cv.wait(lk, [&] { return !p->in_callback; });      // a callback under way returns first
     return LEON_OK;
 }
 

@@ -15,6 +15,10 @@
  *   p.on('frames', (window, frames) => ...)   // one call per window; keep it with {autoRelease: false}
  *   p.on('ended', () => ...)       // decoders/jsv.js:437
  *   p.on('error', (err) => ...)
+ *   p.seek(seconds, {exact}) -> first window id of the new position (leon_pipeline_seek; jsv.prototype.seek,
+ *                                  decoders/jsv.js:1618-1648): nothing is recreated; windows of the old position
+ *                                  never arrive, 'seeked' (frame) comes with the first frame of the new one, and
+ *                                  after 'ended' a seek starts a new run with its own 'ended'
  *   p.readFrame(window, index) -> Uint8Array RGBA (copies to the host: tests, thumbnails)
  *   p.releaseWindow(window); p.stats(); p.destroy();
  */
@@ -45,6 +49,10 @@ class LeonPipeline extends EventEmitter {
       return;
     }
     frames.forEach((f, i) => { f.window = window; f.index = i; });
+    if (this._seekFirst !== undefined && window >= this._seekFirst) {
+      this._seekFirst = undefined;
+      this.emit('seeked', frames[0]);
+    }
     this.emit('frames', window, frames);
     for (const f of frames) this.emit('frame', f);
     if (this.autoRelease) this._p.releaseWindow(window);
@@ -53,6 +61,13 @@ class LeonPipeline extends EventEmitter {
   // a stream that is still arriving (opts.validBytes at construction; the Buffer has the file's final size): the loader
   // writes the next chunk into the same Buffer and reports how far it is valid now -- features/bitreader.js:332 addBuffer
   feed(validBytes) { this._p.feed(validBytes); }
+  // (the addon gives back what the notify thread had queued for the old position: no stale window reaches _deliver)
+  seek(seconds, opts) {
+    const first = this._p.seek(seconds, !!(opts && opts.exact));
+    this.ended = false;
+    this._seekFirst = first;
+    return first;
+  }
   readFrame(window, index) { return this._p.readFrame(window, index); }
   releaseWindow(window) { this._p.releaseWindow(window); }
   stats() { return this._p.stats(); }

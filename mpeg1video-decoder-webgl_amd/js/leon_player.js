@@ -18,7 +18,8 @@
  * opts.pipeline = true puts the native pipeline (leon_pipeline.js, include/leon_pipeline.h) under the same surface:
  * parsing, reconstruction and display conversion run in native threads, whole GOPs arrive as 'frames' events in
  * display order, the JavaScript thread only paces and hands frames out.  The queue bound is then the pipeline's:
- * one GOP per window, two windows in flight.  Seeking recreates the pipeline at the key-map entry for the time.
+ * one GOP per window, two windows in flight.  Seeking moves the running pipeline (leon_pipeline_seek) to the key-map entry
+ * for the time -- or, with opts.accurateSeek, to the frame on screen at it.
  */
 const fs = require('fs');
 const { EventEmitter } = require('events');
@@ -37,7 +38,8 @@ class LeonPlayer extends EventEmitter {
    * opts.nativeParser  true: parse with libleon_vlc on worker threads and hand pictures over as sparse
    *                    group lists (native_decoder.js) instead of the JavaScript bitstream layer
    * opts.pipeline      true: the native pipeline does everything below this class (needs frame width % 8 == 0);
-   *                    opts.parserThreads (default 4)
+   *                    opts.parserThreads (default 4); opts.accurateSeek: currentTime= shows the frame at that
+   *                    time first instead of its GOP's first frame (default off: the reference's GOP granularity)
    */
   constructor(opts) {
     super();
@@ -244,7 +246,12 @@ class LeonPlayer extends EventEmitter {
       this._streamEnded = false;
       this.ended = false;
       this._currentTime = t;
-      this._startPipeline(t);                       // 'seeked' when its first frames arrive
+      if (this._pipe) {
+        // the running pipeline moves -- no destroy and create: the windows queued for display go back first
+        for (const w of this._windowLeft.keys()) this._pipe.releaseWindow(w);
+        this._windowLeft.clear();
+        this._pipe.seek(t, { exact: !!this.opts.accurateSeek });      // 'seeked' when its first frames arrive
+      } else this._startPipeline(t);
       return;
     }
     if (!this._decoder) return;

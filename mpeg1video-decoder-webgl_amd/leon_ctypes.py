@@ -33,8 +33,9 @@ ABI_VERSION = 3        # LEON_ABI_VERSION of include/leon.h
 # include/leon_pipeline.h (same library)
 PIPELINE_SYMBOLS = [
     "leon_pipeline_create", "leon_pipeline_create_partial", "leon_pipeline_feed", "leon_pipeline_get_info", "leon_pipeline_release_window", "leon_pipeline_wait",
-    "leon_pipeline_get_stats", "leon_pipeline_read_frame", "leon_pipeline_error", "leon_pipeline_destroy",
+    "leon_pipeline_get_stats", "leon_pipeline_read_frame", "leon_pipeline_error", "leon_pipeline_destroy", "leon_pipeline_seek",
 ]
+PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 
 
 class LeonError(RuntimeError):
@@ -177,6 +178,7 @@ def load():
     lib.leon_pipeline_read_frame.argtypes = [C.c_void_p, C.POINTER(PipelineFrame), C.c_void_p]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
+    lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
     lib.leon_pipeline_destroy.argtypes = [C.c_void_p]
     lib.leon_pipeline_destroy.restype = None
     _lib = lib
@@ -445,6 +447,7 @@ class Pipeline:
         self.windows = 0
         self.frames = 0
         self.ended = False
+        self.ends = 0              # 'ended' callbacks so far (one per run: create's, then one per seek that runs to the end)
         self.error = None
 
         import threading
@@ -459,6 +462,7 @@ class Pipeline:
             try:
                 ready.wait()
                 if window < 0:
+                    self.ends += 1
                     self.ended = True
                     return
                 if status != OK:          # a failed window is delivered too and must be given back like any other
@@ -514,6 +518,25 @@ class Pipeline:
 
     def release_window(self, window):
         _chk(self.lib.leon_pipeline_release_window(self.h, window))
+
+    def seek(self, seconds, exact=False, mode=None):
+        """leon_pipeline_seek: move the running pipeline to `seconds` (the key-map entry at or before it; exact: from
+        the frame on screen at it).  Returns the id of the new position's first window: no callback starts for a
+        window below it once this returns.  Restarts a run that has ended; `ended` / wait() describe the new run.
+        `mode` overrides `exact` with a raw mode value.  Raises LeonError when the pipeline refuses."""
+        if mode is None:
+            mode = PIPELINE_SEEK_EXACT if exact else PIPELINE_SEEK_KEY
+        first = C.c_int64()
+        was = self.ended
+        self.ended = False
+        rc = self.lib.leon_pipeline_seek(self.h, float(seconds), int(mode), C.byref(first))
+        if rc != OK:
+            self.ended = was
+            raise LeonError(rc, self.lib.leon_last_error().decode())
+        info = PipelineInfo()
+        _chk(self.lib.leon_pipeline_get_info(self.h, C.byref(info)))      # first_gop / shard_gops of the new position
+        self.info = info
+        return first.value
 
     def wait(self):
         _chk(self.lib.leon_pipeline_wait(self.h))

@@ -367,10 +367,13 @@ napi_value Create(napi_env env, napi_callback_info info)
 //   frames: [{gop, displayIndex, type, ts}] in display order; window < 0 = 'ended' (decoders/jsv.js:437).
 //   p.readFrame(window, i) -> Uint8Array (copies one frame to the host: tests, thumbnails),
 //   p.releaseWindow(window), p.stats(), p.info(), p.destroy().
+//   p.seek(seconds, exact) -> firstWindow (leon_pipeline_seek): windows the notify thread queued for the old position and
+//   its 'ended' reach no JavaScript callback -- they are released here; a seek after 'ended' starts a new run.
 // The callback arrives on the JavaScript thread through a napi_threadsafe_function: the pipeline's notify
 // thread waits on the HIP event, nothing ever blocks the event loop (SURVEY.md 8b "Threading").
 struct PipeMsg {
     int64_t window;
+    int64_t last_window;        // 'ended': the last window delivered before it (which position it ends)
     int32_t status;
     std::vector<leon_pipeline_frame> frames;
 };
@@ -382,6 +385,9 @@ struct PipeHandle {
     std::mutex mu;
     std::map<int64_t, std::vector<leon_pipeline_frame>> out;   // delivered, not yet released
     leon_pipeline_info info{};
+    int64_t last_window = -1;               // notify thread, under mu
+    int64_t floor = 0;                      // JavaScript thread: the first window of the latest seek
+    bool seeked = false;
 };
 
 void pipe_native_cb(void* user, int64_t window, const leon_pipeline_frame* frames, int32_t n, int32_t status)
@@ -391,9 +397,13 @@ void pipe_native_cb(void* user, int64_t window, const leon_pipeline_frame* frame
     m->window = window;
     m->status = status;
     if (frames && n > 0) m->frames.assign(frames, frames + n);
-    if (window >= 0) {
+    {
         std::lock_guard<std::mutex> lk(h->mu);
-        h->out[window] = m->frames;
+        if (window >= 0) {
+            h->out[window] = m->frames;
+            h->last_window = std::max(h->last_window, window);
+        }
+        m->last_window = h->last_window;
     }
     napi_call_threadsafe_function(h->tsfn, m, napi_tsfn_blocking);
 }
@@ -402,6 +412,23 @@ void pipe_call_js(napi_env env, napi_value js_cb, void* ctx, void* data)
 {
     PipeHandle* h = (PipeHandle*)ctx;
     PipeMsg* m = (PipeMsg*)data;
+    // queued for a position seeked away from (the seek ran on this thread in between): a window is given back, an 'ended'
+    // dropped.  (Window ids count on across seeks; the windows of the new position start at `floor`.)
+    const bool stale = h->seeked && (m->window >= 0 ? m->window < h->floor : m->last_window < h->floor);
+    if (stale) {
+        if (m->window >= 0 && h->p) {
+            {
+                std::lock_guard<std::mutex> lk(h->mu);
+                h->out.erase(m->window);
+            }
+            leon_pipeline_release_window(h->p, m->window);
+        }
+        delete m;
+        return;
+    }
+    // 'ended': nothing more will come unless a seek restarts the run -- let the event loop end.  Before the call: a seek
+    // from the handler refs it again (PipeSeek).
+    if (m->window < 0 && h->tsfn && env) napi_unref_threadsafe_function(env, h->tsfn);
     if (env && js_cb) {
         napi_value argv[3], undef, ret;
         napi_create_int64(env, m->window, &argv[0]);
@@ -419,18 +446,14 @@ void pipe_call_js(napi_env env, napi_value js_cb, void* ctx, void* data)
         napi_get_undefined(env, &undef);
         napi_call_function(env, undef, js_cb, 3, argv, &ret);
     }
-    const bool ended = m->window < 0;
     delete m;
-    if (ended && h->tsfn) {          // nothing more will come: let the event loop end
-        napi_release_threadsafe_function(h->tsfn, napi_tsfn_release);
-        h->tsfn = nullptr;
-    }
 }
 
 void pipe_finalize(napi_env env, void* data, void*)
 {
     PipeHandle* h = (PipeHandle*)data;
     if (h->p) leon_pipeline_destroy(h->p);
+    if (h->tsfn) napi_release_threadsafe_function(h->tsfn, napi_tsfn_abort);
     if (h->stream_ref) napi_delete_reference(env, h->stream_ref);
     delete h;
 }
@@ -537,6 +560,29 @@ napi_value PipeDestroy(napi_env env, napi_callback_info info)
     return nullptr;
 }
 
+// seek(seconds, exact) -> firstWindow
+napi_value PipeSeek(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    double t = 0;
+    bool exact = false;
+    if (argc < 1 || napi_get_value_double(env, argv[0], &t) != napi_ok) { napi_throw_type_error(env, nullptr, "seek(seconds, exact)"); return nullptr; }
+    if (argc >= 2) napi_get_value_bool(env, argv[1], &exact);
+    int64_t first = -1;
+    const int rc = leon_pipeline_seek(h->p, t, exact ? LEON_PIPELINE_SEEK_EXACT : LEON_PIPELINE_SEEK_KEY, &first);
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    h->floor = first;
+    h->seeked = true;
+    leon_pipeline_get_info(h->p, &h->info);
+    if (h->tsfn) napi_ref_threadsafe_function(env, h->tsfn);      // (unref'd by an 'ended' before): the run goes on
+    napi_value v;
+    NAPI_OK(napi_create_int64(env, first, &v));
+    return v;
+}
+
 // feed(validBytes): more of the stream has arrived in the Buffer the pipeline was created on
 napi_value PipeFeed(napi_env env, napi_callback_info info)
 {
@@ -632,7 +678,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));
