@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <array>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -40,6 +41,15 @@ int fail(int code, const char* fmt, ...)
         hipError_t e_ = (expr);                                                            \
         if (e_ != hipSuccess) return fail(LEON_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// An integer debugging knob from the environment: `d` when the variable is unset or not a whole integer.
+int env_int(const char* name, int d)
+{
+    const char* v = getenv(name);
+    char* end = nullptr;
+    const long x = v && *v ? strtol(v, &end, 10) : 0;      // (out of range: LONG_MIN / LONG_MAX, outside int's range as well)
+    return end && *end == '\0' && x >= INT_MIN && x <= INT_MAX ? (int)x : d;
+}
 
 // decoders/jsv.js:1777-1806 default tables (same data as the oracle's, stated here
 // because the product never links the oracle)
@@ -131,7 +141,6 @@ struct leon_decoder {
     size_t plane_bytes = 0;      // cw*ch*3/2
     size_t slot_stride = 0;      // padded
     uint8_t* d_slots = nullptr;
-    void* d_slots_alloc = nullptr;     // what big_alloc returned (d_slots may start inside it: LEON_SLOT_ALIGN / LEON_SLOT_SKEW)
     std::vector<uint8_t> inuse;
     // batch independence check (check_batch): which picture of the current batch writes a slot
     std::vector<uint32_t> writer_epoch;
@@ -225,9 +234,8 @@ void upload_tables(leon_decoder* d)
     memcpy(d->h_tables.rgba_lut, kLeonRgbaLut, sizeof(kLeonRgbaLut));
 }
 
-inline bool alpha_geom(const leon_decoder* d) { return d->geom.alpha != 0; }
 // Occupancy of the fused display kernels, set through extra dynamic LDS per workgroup (0 = what registers and LDS allow: 8 workgroups
-// of 4 waves per CU, 7 for B).  Round 4, one box, per type (tools/ab_run.py tree@LEON_LDS_PAD_I=...): the I and the P launches are
+// of 4 waves per CU, 7 for B).  Round 4, one box, per type (tools/ab_run.py, a pad per type): the I and the P launches are
 // FASTER with fewer waves in flight -- I 0.477 ms at 8 workgroups per CU, 0.465 at 6, 0.458 at 5 and at 4, 0.630 at 3; P 0.581 /
 // 0.572 / 0.557 / 0.557 / 0.737 -- they wait for the memory pipe, not for instructions, and 32 waves per CU streaming through ~12 regions
 // each get in each other's way in L2 (dense boundary; the SPARSE kernels keep their occupancy: in the pipeline they share the CUs with
@@ -235,8 +243,10 @@ inline bool alpha_geom(const leon_decoder* d) { return d->geom.alpha != 0; }
 // ms) and lose 7 % at 5.  So: I and P at 5 workgroups per CU (20 KB + 11.5 KB of LDS per workgroup), B as the registers allow.
 // Measured again at the end of round 4, when a workgroup no longer began with a round trip to memory for its tables:
 // the I launch 0.382-0.384 ms at 5 workgroups per CU, **0.352 at 6**, 0.359 at 7
-// -- 6 it is (20 KB + 6 KB).  P (the two-tile kernel: launch_recon_type's own pad) is the same at 5 and 6.
+// -- 6 it is (20 KB + 6 KB).  P (the two-tile kernel: kOccupancyPadPairP) is the same at 5 and 6.
 constexpr size_t kOccupancyPadI = 6144, kOccupancyPadP = 11776, kOccupancyPadB = 0;
+// the two-tile kernels (dense P / B display, 26.25 KB per workgroup = six per CU): P back to five, B as the registers allow
+constexpr size_t kOccupancyPadPairP = 1024;
 
 int n_groups_of(const Geom& G) { return 2 * G.tasksY + 2 * G.tasksC + (G.alpha ? 2 * G.tasksY : 0); }
 
@@ -352,18 +362,14 @@ int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, 
     Geom G = d->geom;
     G.n_pics = n;
     const bool alpha = d->geom.alpha != 0;
-    const bool pair = LEON_PAIR_LUMA && LEON_CARRY && display && !sparse && !alpha && type != LEON_PIC_I;      // k_recon_display: recon_luma_pair, two tiles
-    // waves per workgroup: 4 -- but 6 for the dense B display kernel, whose two tiles per wave would leave room for 5 workgroups of 4
-    // per CU (20 waves: it loses 7 % there) and leave room for 4 of 6 (24 waves, what its registers allow anyway); LEON_WAVES_B (experiments)
-    static const int waves_b = getenv("LEON_WAVES_B") ? atoi(getenv("LEON_WAVES_B")) : kWavesPerWGPairB;      // (6 measured: +5 % on the B launches; 4 it is)
-    const int wpw = pair && type == LEON_PIC_B && waves_b >= 1 && waves_b * 64 <= kReconMaxThreads ? waves_b : kWavesPerWG;
+    const bool pair = display && !sparse && !alpha && type != LEON_PIC_I;      // k_recon_display: recon_luma_pair, two tiles
     if (display) {   // one task = one chroma group with everything above it (k_recon_display)
         G.tasks_per_pic = G.tasksC;
-        G.wg_per_pic = (G.tasks_per_pic + wpw - 1) / wpw;
+        G.wg_per_pic = (G.tasks_per_pic + kWavesPerWG - 1) / kWavesPerWG;
         G.inv_wg_per_pic = G.wg_per_pic == 1 ? 0u : (uint32_t)(((1ull << 32) + G.wg_per_pic - 1) / G.wg_per_pic);
     }
     // B launches: the workgroups of two consecutive pictures alternate (pic_of_wg), an odd last picture leaves its partner's idle
-    long long wgs = (long long)(type == LEON_PIC_B && LEON_PAIR_B ? (n + 1) / 2 * 2 : n) * G.wg_per_pic;
+    long long wgs = (long long)(type == LEON_PIC_B ? (n + 1) / 2 * 2 : n) * G.wg_per_pic;
     // the kernel divides by multiply-high: exact while n_wg * wg_per_pic < 2^32
     if (wgs > 0x7fffffffLL || wgs * G.wg_per_pic >= (1LL << 32))
         return fail(LEON_ERR_INVALID, "batch of %d pictures is too large for one launch; split it", n);
@@ -379,19 +385,12 @@ int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, 
             tl.bytes += 4.0 * (double)entries + 4.0 * (double)(n_groups_of(d->geom) + 1) * n - 768.0 * (double)tl.mbs;
         HIP_TRY(hipEventRecord(tl.a, d->stream));
     }
-    static_assert(64 * kWavesPerWG <= kReconMaxThreads && 64 * kWavesPerWGPairB <= kReconMaxThreads, "k_recon is launched with more threads than its __launch_bounds__");
-    const dim3 grid(G.n_wg), block(64 * wpw);
-    // LEON_DEBUG_LDS_PAD (bytes): extra dynamic LDS per workgroup = an occupancy throttle for experiments
-    static const size_t lds_pad_all = getenv("LEON_DEBUG_LDS_PAD") ? (size_t)atol(getenv("LEON_DEBUG_LDS_PAD")) : 0;
-    // per picture type (experiments): LEON_LDS_PAD_I / _P / _B
-    static const size_t lds_pad_t[3] = {getenv("LEON_LDS_PAD_I") ? (size_t)atol(getenv("LEON_LDS_PAD_I")) : kOccupancyPadI,
-                                        getenv("LEON_LDS_PAD_P") ? (size_t)atol(getenv("LEON_LDS_PAD_P")) : kOccupancyPadP,
-                                        getenv("LEON_LDS_PAD_B") ? (size_t)atol(getenv("LEON_LDS_PAD_B")) : kOccupancyPadB};
-    const size_t lds_pad = lds_pad_all + (display && !sparse && !alpha_geom(d) ? lds_pad_t[type - 1] : 0);
-    // the two-tile kernels (26.25 KB per workgroup = six per CU): P back to five (LEON_LDS_PAD_PP / _BP: experiments)
-    static const size_t lds_pad_ppair = getenv("LEON_LDS_PAD_PP") ? (size_t)atol(getenv("LEON_LDS_PAD_PP")) : 1024;
-    static const size_t lds_pad_bpair = getenv("LEON_LDS_PAD_BP") ? (size_t)atol(getenv("LEON_LDS_PAD_BP")) : 0;
-    const size_t lds = (size_t)wpw * (display ? (alpha ? kLdsPerWaveDisplayAlpha : (pair ? kLdsPerWaveDisplayPair : kLdsPerWaveDisplay)) : kLdsPerWave) + (pair ? lds_pad_all + (type == LEON_PIC_P ? lds_pad_ppair : lds_pad_bpair) : lds_pad);      // display kernels: + kLdsLut of static LDS (the conversion tables)
+    static_assert(64 * kWavesPerWG <= kReconMaxThreads, "k_recon is launched with more threads than its __launch_bounds__");
+    const dim3 grid(G.n_wg), block(64 * kWavesPerWG);
+    // extra dynamic LDS per workgroup = the occupancy of the fused display kernels
+    const size_t lds_pad = pair ? (type == LEON_PIC_P ? kOccupancyPadPairP : 0)
+                                : display && !sparse && !alpha ? (type == LEON_PIC_I ? kOccupancyPadI : type == LEON_PIC_P ? kOccupancyPadP : kOccupancyPadB) : 0;
+    const size_t lds = (size_t)kWavesPerWG * (display ? (alpha ? kLdsPerWaveDisplayAlpha : (pair ? kLdsPerWaveDisplayPair : kLdsPerWaveDisplay)) : kLdsPerWave) + lds_pad;      // display kernels: + kLdsLut of static LDS (the conversion tables)
     if (display && alpha) {          // yuva: the A parts ride in the same task (k_recon_display<.., .., true>)
         if (!sparse) {
             if (type == LEON_PIC_I) hipLaunchKernelGGL((k_recon_display<1, false, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
@@ -553,9 +552,9 @@ ContigPool& contig_pool()
 
 hipError_t big_alloc(void** ptr, size_t bytes, int kind, bool* contiguous = nullptr, bool asked = false)
 {
-    static const int mask = getenv("LEON_CONTIGUOUS") ? atoi(getenv("LEON_CONTIGUOUS")) : kBigCaller;
+    static const int mask = env_int("LEON_CONTIGUOUS", kBigCaller);
     // LEON_DEBUG_ZERO_ALLOC = a mask of kBig*: such buffers start as zeros (hunting reads of memory nobody wrote)
-    static const int zero = getenv("LEON_DEBUG_ZERO_ALLOC") ? atoi(getenv("LEON_DEBUG_ZERO_ALLOC")) : 0;
+    static const int zero = env_int("LEON_DEBUG_ZERO_ALLOC", 0);
     if (contiguous) *contiguous = false;
     hipError_t e = hipErrorOutOfMemory;
     if (((mask & kind) || asked) && bytes >= ((size_t)1 << 20)) {
@@ -709,13 +708,7 @@ int leon_create(const leon_config* cfg, leon_decoder** out)
         leon_destroy(d);
         return fail(LEON_ERR_NOMEM, "%s", msg.c_str());
     };
-    // LEON_SLOT_ALIGN / LEON_SLOT_SKEW (bytes; placement experiments, tools/probe/placement_probe.py): the ring starts at a multiple
-    // of ALIGN plus SKEW inside a larger allocation
-    const size_t s_align = getenv("LEON_SLOT_ALIGN") ? (size_t)atoll(getenv("LEON_SLOT_ALIGN")) : 0, s_skew = getenv("LEON_SLOT_SKEW") ? (size_t)atoll(getenv("LEON_SLOT_SKEW")) : 0;
-    if (big_alloc((void**)&d->d_slots_alloc, d->slot_stride * (size_t)cfg->n_slots + 256 + s_align + s_skew, kBigSlots, nullptr, cfg->contiguous_slots == 1) != hipSuccess) return bail("slot ring");
-    d->d_slots = (uint8_t*)d->d_slots_alloc;
-    if (s_align) d->d_slots = (uint8_t*)(((uintptr_t)d->d_slots + s_align - 1) / s_align * s_align);
-    d->d_slots += s_skew;
+    if (big_alloc((void**)&d->d_slots, d->slot_stride * (size_t)cfg->n_slots + 256, kBigSlots, nullptr, cfg->contiguous_slots == 1) != hipSuccess) return bail("slot ring");
     if (hipMemsetAsync(d->d_slots, 0, d->slot_stride * (size_t)cfg->n_slots + 256, d->stream) != hipSuccess) return bail("slot memset");
     if (hipMalloc(&d->d_tables, sizeof(Tables)) != hipSuccess) return bail("tables");
     memcpy(d->qm, kDefaultIntra, 64);
@@ -755,7 +748,7 @@ void leon_destroy(leon_decoder* d)
         if (s.host) hipHostFree(s.host);
         if (s.done) hipEventDestroy(s.done);
     }
-    if (d->d_slots_alloc) big_free(d->d_slots_alloc);          // a contiguous ring goes back to the process's pool, never to the driver (big_alloc)
+    if (d->d_slots) big_free(d->d_slots);          // a contiguous ring goes back to the process's pool, never to the driver (big_alloc)
     if (d->d_tables) hipFree(d->d_tables);
     if (d->d_qsets) hipFree(d->d_qsets);
     if (d->h_qsets) hipHostFree(d->h_qsets);
@@ -797,9 +790,13 @@ int leon_add_quant_matrices(leon_decoder* d, const uint8_t* intra64, const uint8
     if (non_intra64) memcpy(m.data() + 64, non_intra64, 64); else memset(m.data() + 64, 16, 64);
     for (size_t i = 1; i < d->qsets.size(); i++)
         if (d->qsets[i] == m) { *set = (int32_t)i; return LEON_OK; }
-    if (!d->d_qsets) {
-        HIP_TRY(hipMalloc(&d->d_qsets, sizeof(QTables) * leon_decoder::kMaxQSets));
-        HIP_TRY(hipHostMalloc((void**)&d->h_qsets, sizeof(QTables) * leon_decoder::kMaxQSets));
+    if (!d->d_qsets) {       // both buffers or neither: a decoder never holds d_qsets without h_qsets
+        QTables *dq = nullptr, *hq = nullptr;
+        HIP_TRY(hipMalloc(&dq, sizeof(QTables) * leon_decoder::kMaxQSets));
+        const hipError_t e = hipHostMalloc((void**)&hq, sizeof(QTables) * leon_decoder::kMaxQSets);
+        if (e != hipSuccess) { hipFree(dq); return fail(LEON_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)); }
+        d->d_qsets = dq;
+        d->h_qsets = hq;
         d->qsets.assign(1, std::array<uint8_t, 128>{});
     }
     if ((int)d->qsets.size() >= leon_decoder::kMaxQSets)

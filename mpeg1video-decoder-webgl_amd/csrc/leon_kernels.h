@@ -38,12 +38,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#ifndef LEON_CARRY
-#define LEON_CARRY 1
-#endif
-#ifndef LEON_PAIR_B
-#define LEON_PAIR_B 1
-#endif
 
 namespace leon {
 
@@ -99,7 +93,6 @@ static constexpr int kWavesPerWG = 4;
 // more threads than the bound fails at launch time ("unspecified launch failure" from
 // hipGetLastError -- what a 512-thread block-size sweep of the RGBA kernels ran into in round 1).
 static constexpr int kReconMaxThreads = 384;
-static constexpr int kWavesPerWGPairB = 4;       // (6 waves per workgroup for the dense B display kernel were tried: launch_recon_type)
 static constexpr int kRgbaBlock = 256;
 // A wave's LDS strip.  The tile holds BOTH block groups of a task, [half][row][block][column] int16, and is
 // worked on in place: coefficients -> (column pass) the int16 hand-off values w -> (row pass reads them).
@@ -137,37 +130,10 @@ template <> struct Lay<1> { static constexpr int carry = kLdsTile, slots = kLdsT
                             static constexpr bool tables_in_lds = false, park_in_tile = true; };
 static constexpr int kLdsPerWaveDisplayPair = Lay<1>::tile_r + kLdsTile;      // 5440
 static constexpr int kOffTileR = Lay<1>::tile_r;
-#ifndef LEON_PAIR_LUMA
-#define LEON_PAIR_LUMA 1
-#endif
-#ifndef LEON_NINTH_FROM_BELOW
-#define LEON_NINTH_FROM_BELOW 1
-#endif
-#ifndef LEON_PRIO
-#define LEON_PRIO 0        // experiment (round 4): wave priority by progress through a display task, all picture types (1: rising, 2: falling)
-#endif
-#ifndef LEON_PRIO_B
-#define LEON_PRIO_B 3      // B display tasks: a wave starts at priority 3 and drops to 0 (2: after its chroma part, 3: when the luma parts' coefficient
-                          // loads are out, 4: after their column pass, 5: before the second luma part) -- young waves first: their loads are on the way
-                          // while the older ones compute.  One box, alternating, ms per mixed B launch: 1.027-1.031 without, 0.992-0.993 with 3 (4: the
-                          // same, 5: 1.018, 2: 0.998-1.004); the step 5.83-5.85 -> 5.73-5.75 ms.  For ALL types (LEON_PRIO=2) I and P got slower.
-#endif
-#ifndef LEON_PRIO_P
-#define LEON_PRIO_P 0
-#endif
-#define LEON_PRIO_OF(TYPE) (LEON_PRIO ? LEON_PRIO : ((TYPE) == 3 ? LEON_PRIO_B : (TYPE) == 2 ? LEON_PRIO_P : 0))      // (recon_luma_pair is the dense, non-alpha path only)
-#ifndef LEON_RGBA_AUX
-#define LEON_RGBA_AUX 2    // cache policy bits of the frames' stores (1 sc0, 2 nt, 16 sc1).  nt: the GPU never reads a frame again, and written
-                          // through the caches like everything else it pushes the reference planes out -- round 4, one box, alternating: 5.944 ->
-                          // 5.818 ms per step (I -5 %, P -3.6 %, mixed B -1.2 %); sc0 / sc1: nothing.  (Round 2 measured nt on ALL stores: -4 %,
-                          // the planes are read again.)
-#endif
-#ifndef LEON_ABL
-#define LEON_ABL 0      // ablation builds (tools/ab_build.sh x -DLEON_ABL=n): 1 no reference loads, 2 no RGBA stores, 4 no display conversion at all; WRONG output, timing only
-#endif
-#ifndef LEON_NO_PLANES_BRANCH
-#define LEON_NO_PLANES_BRANCH 1
-#endif
+// cache policy bits of the frames' stores (1 sc0, 2 nt, 16 sc1).  nt: the GPU never reads a frame again, and written through the
+// caches like everything else it pushes the reference planes out -- round 4, one box, alternating: 5.944 -> 5.818 ms per step (I -5 %,
+// P -3.6 %, mixed B -1.2 %); sc0 / sc1: nothing.  (Round 2 measured nt on ALL stores: -4 %, the planes are read again.)
+static constexpr int kAuxFrameStore = 2;
 
 // ---- small helpers -----------------------------------------------------------
 
@@ -533,8 +499,8 @@ __device__ __forceinline__ RefRows fetch_rows(const LEON_GLOBAL uint8_t* ref, in
         uint32_t xo = (uint32_t)px & ~3u;
         // buffer loads: wave-uniform descriptor in SGPRs + 32-bit offset, no 64-bit address math
         const __amdgpu_buffer_rsrc_t rs = buf_rsrc((const void*)ref);
-        const v3u a = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)(use && !(LEON_ABL & 1) ? r0 + xo : kOobBit), 0, 0);
-        const v3u c = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)(use && last_row && ov && !(LEON_ABL & 1) ? r1 + xo : kOobBit), 0, 0);
+        const v3u a = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)(use ? r0 + xo : kOobBit), 0, 0);
+        const v3u c = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)(use && last_row && ov ? r1 + xo : kOobBit), 0, 0);
         R.l0 = a.x; R.l1 = a.y; R.l2 = a.z;
         R.m0 = c.x; R.m1 = c.y; R.m2 = c.z;
     } else {                                         // vector leaves the picture (rare)
@@ -708,10 +674,9 @@ __device__ __forceinline__ void display_half(const PicDesc& pd, const Geom& G, c
     const uint32_t row_off = __umul24((uint32_t)yrow, (uint32_t)G.fw) + (uint32_t)xa;     // both < 4096
     const bool in_a = yrow < G.fh && xa < G.fw, in_b = yrow + 1 < G.fh && xa < G.fw;
     const v4u pa = rgba_row4<AMODE == 2>(dsp.lut, ya, c0, c1, aa, two, k21);
-    if (!(LEON_ABL & 2)) __builtin_amdgcn_raw_buffer_store_b128(pa, rrs, (int)((row_off * 4u) | (in_a ? 0u : kOobBit)), 0, LEON_RGBA_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(pa, rrs, (int)((row_off * 4u) | (in_a ? 0u : kOobBit)), 0, kAuxFrameStore);
     const v4u pb = rgba_row4<AMODE == 2>(dsp.lut, yb, c0, c1, ab, two, k21);
-    if (!(LEON_ABL & 2)) __builtin_amdgcn_raw_buffer_store_b128(pb, rrs, (int)(((row_off + (uint32_t)G.fw) * 4u) | (in_b ? 0u : kOobBit)), 0, LEON_RGBA_AUX);
-    if (LEON_ABL & 2) asm volatile("" :: "v"(pa.x ^ pa.y ^ pa.z ^ pa.w ^ pb.x ^ pb.y ^ pb.z ^ pb.w));      // keep the conversion alive
+    __builtin_amdgcn_raw_buffer_store_b128(pb, rrs, (int)(((row_off + (uint32_t)G.fw) * 4u) | (in_b ? 0u : kOobBit)), 0, kAuxFrameStore);
 }
 
 // ---- stage 2 as functions: the liveness scan of a tile and the column pass over a list of live columns ------------------------
@@ -973,7 +938,7 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
             const int Rh = CHROMA ? Rt : 2 * Rt + h;
             const uint32_t po = CHROMA ? (h == 0 ? ysz : ysz + (ysz >> 2)) : a_off;
             // (luma, upper half: no ninth row of its own -- finish_rows takes it from the lower half)
-            const bool ninth = hi3 == 7 && (CHROMA || h == 1 || !LEON_NINTH_FROM_BELOW);
+            const bool ninth = hi3 == 7 && (CHROMA || h == 1);
             if (any_f) rfh[h] = fetch_rows(gptr(pd.ref_fwd) + po, W, H, 8 * Rh + hi3, pxA, ayA, ohA, ovA, inA, ninth, useA);
             if (TYPE == 3 && any_b) rbh[h] = fetch_rows(gptr(pd.ref_bwd) + po, W, H, 8 * Rh + hi3, pxB, ayB, ohB, ovB, inB, ninth, useB);
         }
@@ -1070,13 +1035,13 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
         if (TYPE != 1) {
             v2u pred = {0u, 0u};
             if (any_f) {
-                finish_rows(rf, ovA, hi3 == 7, lane, !CHROMA && half == 0 && LEON_NINTH_FROM_BELOW ? &rfh[1] : nullptr);
+                finish_rows(rf, ovA, hi3 == 7, lane, !CHROMA && half == 0 ? &rfh[1] : nullptr);
                 pred = predict8(rf);
             }
             if (TYPE == 3) {
                 v2u pb = {0u, 0u};
                 if (any_b) {
-                    finish_rows(rb, ovB, hi3 == 7, lane, !CHROMA && half == 0 && LEON_NINTH_FROM_BELOW ? &rbh[1] : nullptr);
+                    finish_rows(rb, ovB, hi3 == 7, lane, !CHROMA && half == 0 ? &rbh[1] : nullptr);
                     pb = predict8(rb);
                 }
                 v2u pf = usef ? pred : pb;
@@ -1104,13 +1069,7 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
             // planes only for pictures that will be predicted from.  A scalar branch (the flag is the picture's): until round 4 the
             // store was issued into a resource without records, which drops it -- after the texture path has processed it; a B task
             // issued six such stores among its 54 memory instructions
-#if LEON_NO_PLANES_BRANCH
             if (!pd.no_planes) __builtin_amdgcn_raw_buffer_store_b64(o, buf_rsrc(pd.out + plane_off), (int)out_voff, (int)(half ? half_step : 0u), 0);
-#else
-            const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)(pd.out + plane_off), 0, pd.no_planes ? 0 : 0x7fffffff, 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b64(o, prs, (int)out_voff, (int)(half ? half_step : 0u), 0);
-#endif
             if constexpr (CHROMA) {
                 // park the samples for the luma parts: [plane = half][row hi3][8 bytes of macroblock lo3]
                 *reinterpret_cast<v2u*>(dsp.stash + half * 512 + hi3 * 64 + lo3 * 8) = o;
@@ -1130,161 +1089,12 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (!(LEON_ABL & 4)) display_half<AMODE>(pd, G, dsp, Lay<LAYOUT>::park_in_tile ? tile + half * kLdsHalf : lds + kOffYpark, half, Rt, g, hi3, lo3);
+            display_half<AMODE>(pd, G, dsp, Lay<LAYOUT>::park_in_tile ? tile + half * kLdsHalf : lds + kOffYpark, half, Rt, g, hi3, lo3);
             // the next half parks its rows in the same place
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-    }
-}
-
-// ---- the back half of a luma part of recon_luma_pair as two functions (LEON_EARLY_RIGHT) -----------------------------------------
-// What recon_task<TYPE, false, false, true, 0, 2, true, 1> does, cut in two at the point where the reference rows have been requested:
-// luma_back_fetch (the macroblock's flags and vectors from the chroma part's lanes, window geometry, the requests) and luma_back_rest
-// (row passes, prediction, stores, conversion).  Between a wave's request for reference rows and its first use of them lay one row
-// pass (~170 vector instructions); with the cut, the RIGHT part's rows are requested while the left part still has its last half to
-// convert and store (`hook`, called when the left part's own reference rows are dead: the registers are free), so they fly behind
-// ~310 instructions and two store instructions more.
-#ifndef LEON_EARLY_RIGHT
-#define LEON_EARLY_RIGHT 0
-#endif
-struct NoHook { __device__ __forceinline__ void operator()() const {} };
-struct LumaBack {
-    uint32_t out_voff;
-    int ovA, ovB;
-    bool nopred, usef, useb, any_f, any_b;
-    RefRows rfh[2], rbh[2];
-};
-
-template <int TYPE>
-__device__ __forceinline__ void luma_back_fetch(LumaBack& S, const PicDesc& pd, const Geom& G, int Rt, int g, const char* lds, int lane, int side,
-                                                const MbCarry& carry)
-{
-    const int W = G.cw, H = G.ch, bw = W >> 3;
-    const int hi3 = lane >> 3, lo3 = lane & 7;
-    const int Qb = g * 8 + lo3;
-    const bool valid = Qb < bw;
-    const int Qs = valid ? Qb : bw - 1;
-    // this lane's macroblock is number 4 * side + (block >> 1) of the task: its chroma-part lane holds it
-    const int src = (4 * side + (lo3 >> 1)) << 2;
-    const uint32_t flags = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)carry.flags);
-    uint32_t mf = *reinterpret_cast<const uint32_t*>(lds + Lay<1>::carry + src), mk = 0;
-    if (TYPE == 3) mk = *reinterpret_cast<const uint32_t*>(lds + Lay<1>::carry + 32 + src);
-    const int x0 = 8 * Qs;
-    bool nopred = (flags & 512u) != 0u, usef = true, useb = true;
-    if (TYPE == 3) {
-        const int dir = (int)(flags >> 10) & 3;
-        usef = (dir & 1) != 0;
-        useb = (dir & 2) != 0;
-        nopred = nopred || dir == 0;
-        if (!usef) mf = 0;
-        if (!useb) mk = 0;
-    }
-    const int fh = (int)(short)(mf & 0xffff), fv = (int)mf >> 16;
-    const int bh = (int)(short)(mk & 0xffff), bv = (int)mk >> 16;
-    const int pxA = x0 + (fh >> 1), ohA = fh & 1, ayA = fv >> 1, ovA = fv & 1;
-    bool inA = (uint32_t)pxA < (uint32_t)(W - 7 - ohA), inB = true;
-    int pxB = 0, ohB = 0, ayB = 0, ovB = 0;
-    if (TYPE == 3) {
-        pxB = x0 + (bh >> 1); ohB = bh & 1; ayB = bv >> 1; ovB = bv & 1;
-        inB = (uint32_t)pxB < (uint32_t)(W - 7 - ohB);
-    }
-    const bool useA = usef && !nopred, useB = useb && !nopred;
-    inA = inA || !useA;
-    inB = inB || !useB;
-    S.out_voff = ((uint32_t)__mul24(16 * Rt + hi3, W) + (uint32_t)x0) | (valid ? 0u : kOobBit);
-    S.ovA = ovA; S.ovB = ovB; S.nopred = nopred; S.usef = usef; S.useb = useb;
-    S.any_f = TYPE != 3 || __builtin_amdgcn_ballot_w64(useA) != 0;
-    S.any_b = TYPE == 3 && __builtin_amdgcn_ballot_w64(useB) != 0;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const bool ninth = hi3 == 7 && (h == 1 || !LEON_NINTH_FROM_BELOW);
-        if (S.any_f) S.rfh[h] = fetch_rows(gptr(pd.ref_fwd), W, H, 8 * (2 * Rt + h) + hi3, pxA, ayA, ohA, ovA, inA, ninth, useA);
-        if (TYPE == 3 && S.any_b) S.rbh[h] = fetch_rows(gptr(pd.ref_bwd), W, H, 8 * (2 * Rt + h) + hi3, pxB, ayB, ohB, ovB, inB, ninth, useB);
-    }
-}
-
-template <int TYPE, typename HOOK>
-__device__ __forceinline__ void luma_back_rest(LumaBack& S, const PicDesc& pd, const Geom& G, int Rt, int g, int lane, const Display& dsp, char* tile,
-                                               uint64_t live0, uint64_t live1, HOOK hook)
-{
-    const int hi3 = lane >> 3, lo3 = lane & 7;
-    const uint32_t half_step = 8u * (uint32_t)G.cw;
-    const uint64_t live[2] = {live0, live1};
-#pragma unroll
-    for (int half = 0; half < 2; half++) {
-        int t[8];
-        const uint64_t colbits = live[half];
-        if (colbits == 0) {
-#pragma unroll
-            for (int m = 0; m < 8; m++) t[m] = 128;
-        } else {
-            // stage 3, the row pass (recon_task)
-            const int cols_live = 8 - (__builtin_clzll(colbits | 1ull) >> 3);
-            const v4u wv = *reinterpret_cast<const v4u*>(tile + half * kLdsHalf + hi3 * 128 + lo3 * 16);
-            const v2f k25 = {2.5f, 2.5f};
-            const v2f a = v2f{(float)(short)(wv.x & 0xffffu), (float)((int)wv.x >> 16)} * k25;
-            const int Y0 = (int)a.x + 128, Y1 = (int)a.y;
-            if (cols_live <= 2) {
-                butterfly8_lo2(Y0, Y1, t);
-            } else {
-                const v2f bb = v2f{(float)(short)(wv.y & 0xffffu), (float)((int)wv.y >> 16)} * k25;
-                if (cols_live <= 4) {
-                    butterfly8_lo4(Y0, Y1, (int)bb.x, (int)bb.y, t);
-                } else {
-                    const v2f cc = v2f{(float)(short)(wv.z & 0xffffu), (float)((int)wv.z >> 16)} * k25;
-                    const v2f dd = v2f{(float)(short)(wv.w & 0xffffu), (float)((int)wv.w >> 16)} * k25;
-                    const int Y[8] = {Y0, Y1, (int)bb.x, (int)bb.y, (int)cc.x, (int)cc.y, (int)dd.x, (int)dd.y};
-                    butterfly8(Y, t);
-                }
-            }
-#pragma unroll
-            for (int m = 0; m < 8; m++) t[m] += (t[m] >> 31) & 255;
-        }
-        // stage 4: prediction, add, clamp, store
-        v2u pred = {0u, 0u};
-        if (S.any_f) {
-            finish_rows(S.rfh[half], S.ovA, hi3 == 7, lane, half == 0 && LEON_NINTH_FROM_BELOW ? &S.rfh[1] : nullptr);
-            pred = predict8(S.rfh[half]);
-        }
-        if (TYPE == 3) {
-            v2u pb = {0u, 0u};
-            if (S.any_b) {
-                finish_rows(S.rbh[half], S.ovB, hi3 == 7, lane, half == 0 && LEON_NINTH_FROM_BELOW ? &S.rbh[1] : nullptr);
-                pb = predict8(S.rbh[half]);
-            }
-            const v2u pf = S.usef ? pred : pb;
-            pb = S.useb ? pb : pred;
-            pred.x = __builtin_amdgcn_lerp(pf.x, pb.x, 0x01010101u);
-            pred.y = __builtin_amdgcn_lerp(pf.y, pb.y, 0x01010101u);
-        }
-        if (S.nopred) pred = v2u{0u, 0u};
-        t[0] += pred_x256<0>(pred.x);
-        t[1] += pred_x256<1>(pred.x);
-        t[2] += pred_x256<2>(pred.x);
-        t[3] += pred_x256<3>(pred.x);
-        t[4] += pred_x256<0>(pred.y);
-        t[5] += pred_x256<1>(pred.y);
-        t[6] += pred_x256<2>(pred.y);
-        t[7] += pred_x256<3>(pred.y);
-        v2u o;
-        o.x = sat_pk4<8>(t[0], t[1], t[2], t[3]);
-        o.y = sat_pk4<8>(t[4], t[5], t[6], t[7]);
-        // the part's own reference rows are dead: the next part's may be requested
-        if (half == 1) hook();
-        if (!pd.no_planes) __builtin_amdgcn_raw_buffer_store_b64(o, buf_rsrc(pd.out), (int)S.out_voff, (int)(half ? half_step : 0u), 0);
-        // the tile half is read out (stage 3): every lane's read has completed; the rows change lanes through it
-        wait_lds_all();
-        __builtin_amdgcn_wave_barrier();
-        *reinterpret_cast<v2u*>(tile + half * kLdsHalf + hi3 * 64 + lo3 * 8) = o;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (!(LEON_ABL & 4)) display_half<0>(pd, G, dsp, tile + half * kLdsHalf, half, Rt, g, hi3, lo3);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 }
 
@@ -1315,16 +1125,10 @@ __device__ __forceinline__ void recon_luma_pair(const PicDesc& pd, const Geom& G
         coef_rows_to_lds(pd.coef[0], tileR, voff, 0u);
         coef_rows_to_lds(pd.coef[0], tileR + kLdsHalf, voff, 16u * (uint32_t)W);
     }
-#if LEON_EARLY_RIGHT
-    // P pictures (52 registers, five waves per SIMD by LDS: room for 96): the reference rows of BOTH parts are requested right behind
-    // the coefficient rows -- one trip to memory for everything the luma parts read
-    constexpr bool kRefsUpFront = LEON_EARLY_RIGHT >= 2 && TYPE == 2;
-    constexpr bool kLeftUpFront = kRefsUpFront || (LEON_EARLY_RIGHT == 4 && TYPE == 3);     // (B: the left part's only; 71 registers)
-    LumaBack backL, backR;
-    if (kLeftUpFront) luma_back_fetch<TYPE>(backL, pd, G, Rt, 2 * gc, lds, lane, 0, carry);
-    if (kRefsUpFront && has_right) luma_back_fetch<TYPE>(backR, pd, G, Rt, 2 * gc + 1, lds, lane, 1, carry);
-#endif
-    if (LEON_PRIO_OF(TYPE) == 3) __builtin_amdgcn_s_setprio(0);
+    // B: the wave started at priority 3 (k_recon_display) and drops to 0 now that its luma coefficient loads are out -- young waves
+    // first: their loads are on the way while the older ones compute.  One box, alternating, ms per mixed B launch: 1.027-1.031
+    // without, 0.992-0.993 with; the step 5.83-5.85 -> 5.73-5.75 ms.  Other drop points and other picture types: no better or slower.
+    if (TYPE == 3) __builtin_amdgcn_s_setprio(0);
     // quantiser scale | intra << 8 of the macroblock of block b of either part, in lane b (the chroma part's lanes hold the task's
     // eight macroblocks: lane m, macroblock m)
     const int qiaL = __builtin_amdgcn_ds_bpermute((lo3 >> 1) << 2, (int)carry.flags) & 0x11f;
@@ -1333,12 +1137,6 @@ __device__ __forceinline__ void recon_luma_pair(const PicDesc& pd, const Geom& G
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#if LEON_EARLY_RIGHT
-    // B pictures (70 registers of 72): the LEFT part's reference rows are requested as soon as the coefficient rows are in (a full
-    // wait in front of them would wait for these too) -- the scan and the column pass run while they fly
-    constexpr bool kLeftBeforeScan = LEON_EARLY_RIGHT == 3 && TYPE == 3;
-    if (kLeftBeforeScan) luma_back_fetch<TYPE>(backL, pd, G, Rt, 2 * gc, lds, lane, 0, carry);
-#endif
     uint64_t liveL[2], liveR[2] = {0, 0};
     uint32_t n_cols = scan_tile(lds, lds + Lay<1>::slots, lane, 0u, 0u, liveL);
     if (has_right) n_cols = scan_tile(tileR, lds + Lay<1>::slots, lane, 128u, n_cols, liveR);
@@ -1346,27 +1144,12 @@ __device__ __forceinline__ void recon_luma_pair(const PicDesc& pd, const Geom& G
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     column_pass<true, false>(lds, (uint32_t)kOffTileR, lds + Lay<1>::slots, nullptr, n_cols, qiaL, qiaR, lane, qreg);
-    if (LEON_PRIO_OF(TYPE) == 4) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     dsp.side = 0;
-#if LEON_EARLY_RIGHT
-    {
-        if (!kLeftUpFront && !kLeftBeforeScan) luma_back_fetch<TYPE>(backL, pd, G, Rt, 2 * gc, lds, lane, 0, carry);
-        luma_back_rest<TYPE>(backL, pd, G, Rt, 2 * gc, lane, dsp, lds, liveL[0], liveL[1],
-                             [&]() { if (!kRefsUpFront && has_right) luma_back_fetch<TYPE>(backR, pd, G, Rt, 2 * gc + 1, lds, lane, 1, carry); });
-        if (has_right) {
-            dsp.side = 1;
-            luma_back_rest<TYPE>(backR, pd, G, Rt, 2 * gc + 1, lane, dsp, tileR, liveR[0], liveR[1], NoHook{});
-        }
-        return;
-    }
-#endif
     recon_task<TYPE, false, false, true, 0, 2, true, 1>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, false, lds, liveL[0], liveL[1]);
     if (has_right) {
-        if (LEON_PRIO_OF(TYPE) == 1) __builtin_amdgcn_s_setprio(3);
-        if (LEON_PRIO_OF(TYPE) == 5) __builtin_amdgcn_s_setprio(0);
         dsp.side = 1;
         recon_task<TYPE, false, false, true, 0, 2, true, 1>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, false, tileR, liveR[0], liveR[1]);
     }
@@ -1402,7 +1185,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int n)
 template <int TYPE>
 __device__ __forceinline__ void pic_of_wg(const Geom& G, int wg, int& pic, int& twg)
 {
-    if (TYPE == 3 && LEON_PAIR_B) {
+    if (TYPE == 3) {
         const int half = wg >> 1;
         const int pair = div_inv(half, G.inv_wg_per_pic);
         twg = half - pair * G.wg_per_pic;
@@ -1463,7 +1246,7 @@ __global__ __launch_bounds__(kReconMaxThreads) void k_recon(const PicDesc* __res
 template <int TYPE, bool SPARSE, bool ALPHA>
 __device__ __forceinline__ bool display_task(const PicDesc* __restrict__ descs, const Geom& G, int pic, int t, char* lds, int lane, const char* lut, bool first)
 {
-    constexpr bool kPair = LEON_PAIR_LUMA && LEON_CARRY && !SPARSE && !ALPHA && TYPE != 1;      // recon_luma_pair
+    constexpr bool kPair = !SPARSE && !ALPHA && TYPE != 1;      // recon_luma_pair
     const bool live = t < G.tasks_per_pic && pic < G.n_pics;
     const PicDesc& pd = descs[live ? pic : 0];
     const int Rt = div_inv(t, G.inv_gC), gc = t - Rt * G.gC;
@@ -1477,14 +1260,12 @@ __device__ __forceinline__ bool display_task(const PicDesc* __restrict__ descs, 
     // in lane i (column_pass takes what it needs by ds_bpermute); requested first, landed with the macroblock maps
     uint32_t qreg = 0u;
     if constexpr (kPair) qreg = ldg<uint32_t>(gptr(pd.qt), (uint32_t)lane * 4u);
-    if (live) recon_task<TYPE, true, SPARSE, true, 0, LEON_CARRY ? 1 : 0, false, kPair ? 1 : 0>(pd, G, Rt, gc, lds, lane, dsp, carry, false, nullptr, 0, 0, qreg);
+    if (live) recon_task<TYPE, true, SPARSE, true, 0, 1, false, kPair ? 1 : 0>(pd, G, Rt, gc, lds, lane, dsp, carry, false, nullptr, 0, 0, qreg);
     if (first) {
         if (!live) wait_vmem_all();      // (a wave with a task has waited for memory behind its chroma part's loads: its chunks of the tables are in)
         __syncthreads();                 // the conversion tables have landed: every wave's chunks
     }
     if (!live) return false;
-    if (kPair && LEON_PRIO_OF(TYPE) == 1) __builtin_amdgcn_s_setprio(1);
-    if (kPair && LEON_PRIO_OF(TYPE) == 2) __builtin_amdgcn_s_setprio(0);
     // the two luma parts as two calls, not a loop: the loop form keeps 15 more registers live (B path: 93).
     // yuva: the A part of the same four macroblocks first (AMODE 1), then the Y part that displays them (AMODE 2).
     if constexpr (kPair) {
@@ -1493,32 +1274,32 @@ __device__ __forceinline__ bool display_task(const PicDesc* __restrict__ descs, 
     }
     dsp.side = 0;
     if constexpr (ALPHA) {
-        recon_task<TYPE, false, SPARSE, true, 1, LEON_CARRY ? 2 : 0>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, true);
-        recon_task<TYPE, false, SPARSE, true, 2, LEON_CARRY ? 2 : 0>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
+        recon_task<TYPE, false, SPARSE, true, 1, 2>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, true);
+        recon_task<TYPE, false, SPARSE, true, 2, 2>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
     } else {
-        recon_task<TYPE, false, SPARSE, true, 0, LEON_CARRY ? 2 : 0>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
+        recon_task<TYPE, false, SPARSE, true, 0, 2>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
     }
     if (2 * gc + 1 < G.gY) {
         dsp.side = 1;
         if constexpr (ALPHA) {
-            recon_task<TYPE, false, SPARSE, true, 1, LEON_CARRY ? 2 : 0>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, true);
-            recon_task<TYPE, false, SPARSE, true, 2, LEON_CARRY ? 2 : 0>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
+            recon_task<TYPE, false, SPARSE, true, 1, 2>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, true);
+            recon_task<TYPE, false, SPARSE, true, 2, 2>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
         } else {
-            recon_task<TYPE, false, SPARSE, true, 0, LEON_CARRY ? 2 : 0>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
+            recon_task<TYPE, false, SPARSE, true, 0, 2>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
         }
     }
     return true;
 }
 
 template <int TYPE, bool SPARSE, bool ALPHA = false>
-__global__ __launch_bounds__(kReconMaxThreads) __attribute__((amdgpu_waves_per_eu(TYPE == 3 && !ALPHA && (SPARSE || LEON_CARRY) ? 7 : 4)))
+__global__ __launch_bounds__(kReconMaxThreads) __attribute__((amdgpu_waves_per_eu(TYPE == 3 && !ALPHA ? 7 : 4)))
 void k_recon_display(const PicDesc* __restrict__ descs, Geom G,
                                                                     const Tables* __restrict__ T)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // (the dense, non-alpha kernels only: in the pipeline's sparse launches a raised priority takes issue slots from the parser
-    // kernels beside them -- 175-177 k against 181-182 k pictures/s end to end)
-    if ((LEON_PAIR_LUMA && LEON_CARRY && !SPARSE && !ALPHA && TYPE != 1) && LEON_PRIO_OF(TYPE) >= 2) __builtin_amdgcn_s_setprio(3);
+    // B waves start at priority 3 and drop to 0 in recon_luma_pair.  (The dense, non-alpha kernel only: in the pipeline's sparse
+    // launches a raised priority takes issue slots from the parser kernels beside them -- 175-177 k against 181-182 k pictures/s end to end)
+    if (TYPE == 3 && !SPARSE && !ALPHA) __builtin_amdgcn_s_setprio(3);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane0 = threadIdx.x & 63;
     const int wg = xcd_remap(blockIdx.x, G.n_wg);
@@ -1542,7 +1323,7 @@ void k_recon_display(const PicDesc* __restrict__ descs, Geom G,
             __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lut_s) + c * 1024), 16,
                                                      (int)(lane0 * 16u), c * 1024, 0, 0);
     }
-    constexpr bool kPair = LEON_PAIR_LUMA && LEON_CARRY && !SPARSE && !ALPHA && TYPE != 1;
+    constexpr bool kPair = !SPARSE && !ALPHA && TYPE != 1;
     char* lds = smem + wave * (ALPHA ? kLdsPerWaveDisplayAlpha : (kPair ? kLdsPerWaveDisplayPair : kLdsPerWaveDisplay));
     // (Round 4 tried a wave running two to five tasks one after the other, so that the frames' stores of a task drain while the wave
     // works on the next: 5.89-5.92 ms per step with two against 5.90-5.95 with one, worse with three and five, and 10-20 registers more

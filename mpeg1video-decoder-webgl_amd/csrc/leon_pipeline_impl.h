@@ -522,12 +522,8 @@ void parser_main(leon_pipeline* p)
 }
 
 
-// which of the two parser streams a window's parser kernels run on (LEON_VLC_STREAMS=1: all on one, for A/B runs)
-inline size_t vlc_stream_of(int64_t window)
-{
-    static const bool one = getenv("LEON_VLC_STREAMS") && atoi(getenv("LEON_VLC_STREAMS")) == 1;
-    return one ? 0 : (size_t)(window & 1);
-}
+// which of the two parser streams a window's parser kernels run on: they alternate
+inline size_t vlc_stream_of(int64_t window) { return (size_t)(window & 1); }
 
 // gpu_parser: the slices of the whole window in one launch each of k_vlc_parse / k_vlc_index / k_vlc_blocks
 // (leon_vlc_gpu.h), on a parser stream, in front of the reconstruction launches that read their output
@@ -607,9 +603,7 @@ int launch_gpu_parser(leon_pipeline* p, PipeWindow* w)
     const leon::VlcSlice* ds = (const leon::VlcSlice*)R.d;
     const leon::VlcPic* dp = (const leon::VlcPic*)(R.d + pad256(n_slices * sizeof(leon::VlcSlice)));
     const int blocks = (int)((n_slices + 255) / 256);
-    // LEON_DEBUG_VLC_LDS_PAD (bytes): more dynamic LDS for the slice loop's workgroups than they use -- what the reconstruction beside them loses to the parser's LDS
-    static const size_t vlc_lds_pad = getenv("LEON_DEBUG_VLC_LDS_PAD") ? (size_t)atol(getenv("LEON_DEBUG_VLC_LDS_PAD")) : 0;
-    hipLaunchKernelGGL(leon::k_vlc_parse, dim3(blocks), dim3(256), 4 * leon::kVlcRingDwords * 64 * 4 + vlc_lds_pad, vs, ds, d_words, (int)n_slices, dp, d_err, p->vgeom, p->d_vlc_tables);
+    hipLaunchKernelGGL(leon::k_vlc_parse, dim3(blocks), dim3(256), 4 * leon::kVlcRingDwords * 64 * 4, vs, ds, d_words, (int)n_slices, dp, d_err, p->vgeom, p->d_vlc_tables);
     hipLaunchKernelGGL(leon::k_vlc_index, dim3((unsigned)n_pics), dim3(leon::kVlcIndexThreads), p->vlc_index_lds, vs, ds, d_words, dp, d_err, p->vgeom);
     hipLaunchKernelGGL(leon::k_vlc_blocks, dim3((unsigned)((n_slices + 3) / 4)), dim3(256), 0, vs, ds, d_words, (int)n_slices, dp, d_err, p->vgeom, p->d_vlc_tables);
     HIP_TRY(hipGetLastError());
@@ -648,7 +642,7 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
         // LEON_DEBUG_POISON=1: everything of the arena that the kernels are expected to write before they read it starts
         // as 0xCD bytes -- a read of something nobody wrote then shows in every run, not only when the memory's history
         // happens to differ from zero
-        static const bool poison = getenv("LEON_DEBUG_POISON") && atoi(getenv("LEON_DEBUG_POISON")) == 1;
+        static const bool poison = env_int("LEON_DEBUG_POISON", 0) == 1;
         if (poison && p->gpu_parser && job->arena->used > up) HIP_TRY(hipMemsetAsync(job->arena->dev + up, 0xCD, job->arena->used - up, p->copy_stream));
         if (up) {
             HIP_TRY(hipMemcpyAsync(job->arena->dev, job->arena->host, up, hipMemcpyHostToDevice, p->copy_stream));
@@ -700,7 +694,7 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
     HIP_TRY(hipEventRecord(copied, p->copy_stream));
     // LEON_DEBUG_SERIAL=1: the host waits behind every stage (uploads, parser kernels, reconstruction) -- takes every
     // cross-stream dependency out of the picture when a wrong frame is being hunted
-    static const bool serial = getenv("LEON_DEBUG_SERIAL") && atoi(getenv("LEON_DEBUG_SERIAL")) == 1;
+    static const bool serial = env_int("LEON_DEBUG_SERIAL", 0) == 1;
     if (serial) HIP_TRY(hipStreamSynchronize(p->copy_stream));
     if (p->gpu_parser) {
         // upload -> parser kernels (their own stream) -> reconstruction (the decoder's stream)
@@ -1116,7 +1110,7 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
         // k_vlc_index's LDS, or a GOP shard of 2^28 bytes and more (the kernels count bits in 32), goes to the parser threads
         bool fits = ((size_t)p->vinfo.n_groups + leon::kVlcIndexThreads) * 4 <= (size_t)160 * 1024 - 512;
         for (uint32_t g : p->shard_gops) fits = fits && p->shard_end[g] - p->shard_begin[g] < ((uint64_t)1 << 28);
-        if (getenv("LEON_DEBUG_GPU_PARSER_LIMIT") && p->vinfo.n_groups > atoi(getenv("LEON_DEBUG_GPU_PARSER_LIMIT"))) fits = false;      // tests: a mocked n_groups limit
+        if (p->vinfo.n_groups > env_int("LEON_DEBUG_GPU_PARSER_LIMIT", INT_MAX)) fits = false;      // tests: a mocked n_groups limit
         if (!fits) p->gpu_parser = false;
     }
     p->info.gpu_parser = p->gpu_parser ? 1 : 0;
@@ -1238,23 +1232,11 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
         }
         // The parser kernels want little of the chip (a quarter of the issue slots of the SIMDs they sit on) but all of it
         // for as long as their longest slice takes; the reconstruction launches beside them fill every CU.  Highest
-        // stream priority: a freed slot goes to a waiting parser workgroup first.  (LEON_VLC_PRIO=0: default priority.)
+        // stream priority: a freed slot goes to a waiting parser workgroup first.
         int prio_lo = 0, prio_hi = 0;
         hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        const bool high = !(getenv("LEON_VLC_PRIO") && atoi(getenv("LEON_VLC_PRIO")) == 0);
-        // LEON_VLC_CUS=K: the parser streams may use K compute units only (hipExtStreamCreateWithCUMask; the first K bits of
-        // the mask).  Packed four waves to a SIMD on a part of the chip, the parser leaves the rest to the reconstruction
-        // launches at their full occupancy instead of thinning them out everywhere.
-        const int cus = getenv("LEON_VLC_CUS") ? atoi(getenv("LEON_VLC_CUS")) : 0;
-        for (hipStream_t& vs : p->vlc_stream) {
-            hipError_t e;
-            if (cus > 0) {
-                uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (int i = 0; i < cus && i < 256; i++) mask[i >> 5] |= 1u << (i & 31);
-                e = hipExtStreamCreateWithCUMask(&vs, 8, mask);
-            } else e = hipStreamCreateWithPriority(&vs, hipStreamNonBlocking, high ? prio_hi : prio_lo);
-            if (e != hipSuccess) return bail(LEON_ERR_HIP, "parser stream");
-        }
+        for (hipStream_t& vs : p->vlc_stream)
+            if (hipStreamCreateWithPriority(&vs, hipStreamNonBlocking, prio_hi) != hipSuccess) return bail(LEON_ERR_HIP, "parser stream");
         if (hipMalloc((void**)&p->d_vlc_tables, sizeof(leon::VlcTables)) != hipSuccess) return bail(LEON_ERR_NOMEM, "GPU parser tables");
         if (hipMemcpy(p->d_vlc_tables, t.data(), sizeof(leon::VlcTables), hipMemcpyHostToDevice) != hipSuccess) return bail(LEON_ERR_HIP, "GPU parser tables");
         p->vgeom.mbw = p->vinfo.mb_width; p->vgeom.mbh = p->vinfo.mb_height;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of kernel variants on ONE box: runs bench.py once per variant built by tools/ab_build.sh (or the in-tree
 library for the name `tree`), optionally with environment settings (name@VAR=VALUE), and prints one line each.
-    python tools/ab_run.py base lut base@LEON_DEBUG_LDS_PAD=5120 [-- extra bench.py flags]"""
+    python tools/ab_run.py base lut base@LEON_CONTIGUOUS=0 [-- extra bench.py flags]"""
 import json
 import os
 import subprocess

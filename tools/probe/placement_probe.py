@@ -106,8 +106,6 @@ measure("start")
 if "--many-rings" in sys.argv:
     # ring after ring, every one HELD (so every one is a new range): step time against the ring's address
     held = []
-    os.environ.pop("LEON_SLOT_ALIGN", None)
-    os.environ.pop("LEON_SLOT_SKEW", None)
     for k in range(7):
         old = wl.dec
         for b in wl.batches:
@@ -123,14 +121,6 @@ if "--many-rings" in sys.argv:
     wl.dec = held[0]
     wl.batches = [wl.build_level(li) for li in range(len(wl.levels))]
     measure("ring 0 again")
-    rounds = 0
-if "--slot-skews" in sys.argv:
-    # the slot ring at chosen positions relative to a 64 MiB boundary, everything else held where it is
-    for skew in [0, 2, 8, 10, 16, 32, 0, 10, 34, 1, 0]:
-        os.environ["LEON_SLOT_ALIGN"] = str(64 << 20)
-        os.environ["LEON_SLOT_SKEW"] = str(skew << 20)
-        redraw_slots()
-        measure("slots at 64 MiB + %d MiB" % skew)
     rounds = 0
 for r in range(rounds):
     for tag, fn in (("rgba", redraw_rgba), ("coef", redraw_coef), ("slots", redraw_slots)):
