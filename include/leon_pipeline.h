@@ -35,6 +35,10 @@ typedef struct leon_pipeline leon_pipeline;
 #define LEON_PIPELINE_PARSER_GPU 1
 #define LEON_PIPELINE_PARSER_HOST (-1)
 
+/* leon_pipeline_config.output: a bit set; 0 = RGBA */
+#define LEON_PIPELINE_OUTPUT_RGBA  1
+#define LEON_PIPELINE_OUTPUT_YCBCR 2
+
 typedef struct leon_pipeline_config {
     int32_t device_id;
     int32_t parser_threads;     /* K; <= 0: one per hardware thread, at most 16 */
@@ -71,15 +75,30 @@ typedef struct leon_pipeline_config {
      *     wants the pixels the page shows (within 1 LSB of the executed reference's canvas, tests/test_pipeline_gl_flavour_gpu.py).
      *     Takes the unfused road: every picture writes its planes, one k_rgba_gl launch per picture.  Not with yuva streams. */
     int32_t display_flavour;
+    /* What a frame carries, a bit set (0 = LEON_PIPELINE_OUTPUT_RGBA, what every caller got before the field existed; other bits
+     * are refused at create):
+     *   LEON_PIPELINE_OUTPUT_RGBA   frame.rgba, RGBA8 in the display flavour above
+     *   LEON_PIPELINE_OUTPUT_YCBCR  frame.y / cb / cr (+ a for yuva streams): the decoded YCbCr 4:2:0 planes, cropped to the frame --
+     *                               the reference's own frame event, this['go']('frame', {'ybr': [Y, Cb, Cr], 'ts': ts})
+     *                               (decoders/jsv.js:600, :673; a yuva stream's fourth plane as in its 4-plane ring, :59-73), which its
+     *                               display converts in a shader (renderFrameGL, player/easybits.player.js:2787-2858).  The planes do
+     *                               not depend on display_flavour; with YCBCR alone no RGBA is written nor allocated.
+     * Plane layout in device memory (leon_pipeline_info reports it): Y and A frame_width x frame_height, Cb and Cr
+     * ((frame_width + 1) / 2) x ((frame_height + 1) / 2); a row takes its plane's width rounded up to 64 bytes (luma_stride,
+     * chroma_stride; the bytes behind the width are unspecified), every plane starts on a 256-byte boundary; rows past the plane
+     * height are not written.  leon_pipeline_read_frame_planes copies them packed. */
+    int32_t output;
 } leon_pipeline_config;
 
-/* One decoded picture.  rgba stays valid until leon_pipeline_release_window(window) */
+/* One decoded picture.  rgba and the planes stay valid until leon_pipeline_release_window(window); a pointer whose output
+ * was not asked for (leon_pipeline_config.output) is NULL, and so is `a` but for yuva streams */
 typedef struct leon_pipeline_frame {
     uint64_t gop;               /* GOP id (key-map index, counting on across loops) */
     int32_t  display_index;     /* temporal reference inside its GOP */
     int32_t  type;              /* LEON_PIC_I / _P / _B */
     double   ts_ms;             /* presentation time: GOP time code + display_index / picture rate */
     void*    rgba;              /* DEVICE pointer: frame_width * frame_height * 4 bytes */
+    void    *y, *cb, *cr, *a;   /* DEVICE pointers to the frame's planes (LEON_PIPELINE_OUTPUT_YCBCR; layout: leon_pipeline_config.output) */
 } leon_pipeline_frame;
 
 /* Called on the pipeline's notify thread once per window, frames in display order (GOP-major).
@@ -101,6 +120,9 @@ typedef struct leon_pipeline_info {
     int32_t parser_threads, gops_per_window;
     int32_t gpu_parser;         /* 1: the slice layer is decoded on the GPU, 0: on the parser threads (what LEON_PIPELINE_PARSER_DEFAULT chose) */
     int32_t display_flavour;    /* LEON_RGB_CPU_TWIN / LEON_RGB_GL, as configured */
+    int32_t output;             /* LEON_PIPELINE_OUTPUT_* bits in force (0 configured = RGBA) */
+    int32_t chroma_width, chroma_height;   /* of Cb and Cr: (frame_width + 1) / 2, (frame_height + 1) / 2 */
+    int32_t luma_stride, chroma_stride;    /* bytes per row of Y (and A), of Cb and Cr: the plane width rounded up to 64 */
 } leon_pipeline_info;
 
 typedef struct leon_pipeline_stats {
@@ -125,7 +147,7 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
                                  leon_pipeline_callback cb, void* user, leon_pipeline** out);
 int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes);
 int leon_pipeline_get_info(leon_pipeline* p, leon_pipeline_info* out);
-/* the consumer is done with a window's frames: its RGBA ring entry and staging may be reused */
+/* the consumer is done with a window's frames: its ring entries (RGBA, planes) and staging may be reused */
 int leon_pipeline_release_window(leon_pipeline* p, int64_t window);
 /* blocks until every window has been delivered and the final callback (window -1) has returned; returns the
  * first error.  Not to be called from inside the callback. */
@@ -149,8 +171,12 @@ int leon_pipeline_get_stats(leon_pipeline* p, leon_pipeline_stats* out);
 #define LEON_PIPELINE_SEEK_KEY   0
 #define LEON_PIPELINE_SEEK_EXACT 1
 int leon_pipeline_seek(leon_pipeline* p, double seconds, int32_t mode, int64_t* first_window);
-/* copy one frame of a delivered, not yet released window to host memory (tests, thumbnails) */
+/* copy one frame of a delivered, not yet released window to host memory (tests, thumbnails); LEON_ERR_INVALID for a frame
+ * without RGBA */
 int leon_pipeline_read_frame(leon_pipeline* p, const leon_pipeline_frame* f, uint8_t* rgba_host);
+/* the same for its planes, packed (row stride = plane width): y frame_width x frame_height, cb and cr chroma_width x chroma_height,
+ * a (may be NULL; yuva streams) like y.  LEON_ERR_INVALID for a frame without planes */
+int leon_pipeline_read_frame_planes(leon_pipeline* p, const leon_pipeline_frame* f, uint8_t* y, uint8_t* cb, uint8_t* cr, uint8_t* a);
 const char* leon_pipeline_error(leon_pipeline* p);
 void leon_pipeline_destroy(leon_pipeline* p);
 

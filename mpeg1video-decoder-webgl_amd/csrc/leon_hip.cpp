@@ -80,6 +80,23 @@ struct TimedLaunch {
 const double kBytesI = 1154.0, kBytesPBase = 1158.0, kBytesBBase = 1162.0, kBytesRef = 384.0;
 const double kRgbaBytesPerMb = 1408.0;
 
+// The frame-planes layout of include/leon_pipeline.h: Y (and A) frame_width x frame_height, Cb and Cr ((w + 1) / 2) x ((h + 1) / 2),
+// rows padded to 64 bytes, each plane on a 256-byte boundary, [Y | Cb | Cr | A]; *record_bytes: one frame's record without A
+FrameOut planes_layout(int fw, int fh, size_t* record_bytes)
+{
+    auto up = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
+    FrameOut fo{};
+    fo.luma_stride = (uint32_t)up((size_t)fw, 64);
+    fo.chroma_stride = (uint32_t)up((size_t)(fw + 1) / 2, 64);
+    fo.chroma_height = (fh + 1) / 2;
+    const size_t ybytes = up((size_t)fo.luma_stride * fh, 256), cbytes = up((size_t)fo.chroma_stride * fo.chroma_height, 256);
+    fo.cb_off = (uint32_t)ybytes;
+    fo.cr_off = (uint32_t)(ybytes + cbytes);
+    fo.a_off = (uint32_t)(ybytes + 2 * cbytes);
+    if (record_bytes) *record_bytes = ybytes + 2 * cbytes;
+    return fo;
+}
+
 // dense or sparse picture as the internals see it
 struct AnyPic {
     leon_picture p{};            // coef_* unused when sparse
@@ -87,6 +104,7 @@ struct AnyPic {
     const uint32_t* entries = nullptr;
     uint32_t n_entries = 0;
     bool sparse = false;
+    uint8_t* planes_out = nullptr;   // pipeline only (leon_pipeline.h output YCbCr): the frame's planes record (FrameOut), device memory
 };
 AnyPic any_of(const leon_picture& p)
 {
@@ -106,6 +124,10 @@ AnyPic any_of(const leon_sparse_picture& q)
     return a;
 }
 
+// launch class of a picture = 3 * output + type - 1, output 0: planes only (k_recon), 1: RGBA (k_recon_display), 2: the frame's
+// YCbCr planes, 3: both (k_recon_display_out)
+constexpr int kClasses = 12;
+
 struct Staging {                 // device copy of one host-submitted picture
     char* base = nullptr;
     char* host = nullptr;        // pinned mirror: the caller's arrays are gathered here, then ONE async copy
@@ -116,14 +138,14 @@ struct Staging {                 // device copy of one host-submitted picture
 }  // namespace
 
 struct leon_batch {
-    // descriptors sorted by launch class: class = type - 1 (planes only) or 3 + type - 1 (fused display conversion)
+    // descriptors sorted by launch class (class_of); a batch of leon_picture holds classes 0 .. 5 only
     PicDesc* d_descs = nullptr;
     int n = 0;
-    int count[6] = {0, 0, 0, 0, 0, 0};
+    int count[kClasses] = {};
     std::vector<int32_t> out_slots;
     bool sparse = false;
-    uint64_t entries_of_type[6] = {0, 0, 0, 0, 0, 0};   // sparse: list lengths per class (algorithmic bytes)
-    double bytes_of_type[6] = {0, 0, 0, 0, 0, 0};       // dense-boundary algorithmic bytes per class, from the pictures' own maps
+    uint64_t entries_of_type[kClasses] = {};   // sparse: list lengths per class (algorithmic bytes)
+    double bytes_of_type[kClasses] = {};       // dense-boundary algorithmic bytes per class, from the pictures' own maps
 };
 
 struct leon_decoder {
@@ -162,6 +184,17 @@ struct leon_decoder {
     int next_stage = 0;
     PicDesc* d_desc_ring = nullptr;   // kDescRing descriptors for ad-hoc submits
     PicDesc* h_desc_pinned = nullptr;
+    // beside each descriptor of the ring: the frame-planes record of a picture with YCbCr output (FrameOut::frames); allocated
+    // with the first such batch
+    uint8_t** d_frames_ring = nullptr;
+    uint8_t** h_frames_pinned = nullptr;
+    FrameOut frame_out{};             // the frames' plane layout (frames = null), planes_layout()
+    // k_planes_crop: the batch's source slots and destinations
+    int32_t* d_crop_slots = nullptr;
+    int32_t* h_crop_slots = nullptr;
+    uint8_t** d_crop_frames = nullptr;
+    uint8_t** h_crop_frames = nullptr;
+    int crop_head = 0;
     // A lap of the ring is 65536 pictures; a range is reused only after the launches that read it have finished -- not by
     // waiting for the STREAM at the wrap (the pipeline lost five windows' time, 45 ms, every 65536 pictures that way) but
     // for the event recorded behind the last launch of that range, a lap ago: long since signalled.
@@ -288,7 +321,8 @@ int check_pic(const leon_decoder* d, const AnyPic& a)
 {
     const leon_picture& p = a.p;
     if (p.type < LEON_PIC_I || p.type > LEON_PIC_B) return fail(LEON_ERR_INVALID, "picture type %d", p.type);
-    const bool writes_planes = !(p.rgba_out && p.no_planes);
+    const bool display = p.rgba_out || a.planes_out;
+    const bool writes_planes = !(display && p.no_planes);
     if (writes_planes ? (p.out_slot < 0 || p.out_slot >= d->cfg.n_slots) : (p.out_slot < -1 || p.out_slot >= d->cfg.n_slots))
         return fail(LEON_ERR_INVALID, "out_slot %d", p.out_slot);
     if (a.sparse) {
@@ -309,9 +343,10 @@ int check_pic(const leon_decoder* d, const AnyPic& a)
     }
     if (p.qm_set < 0 || p.qm_set > (int32_t)d->qsets.size() - 1 + (d->qsets.empty() ? 1 : 0))
         return fail(LEON_ERR_INVALID, "qm_set %d: the decoder has %zu matrix sets beside set 0 (leon_add_quant_matrices)", p.qm_set, d->qsets.empty() ? (size_t)0 : d->qsets.size() - 1);
-    if (p.rgba_out) {
+    if (display) {
         if (d->cfg.frame_width & 7) return fail(LEON_ERR_INVALID, "fused display conversion needs frame_width %% 8 == 0 (it is %d)", d->cfg.frame_width);
         if ((size_t)p.rgba_out & 15) return fail(LEON_ERR_INVALID, "rgba_out must be 16-byte aligned");
+        if ((size_t)a.planes_out & 255) return fail(LEON_ERR_INVALID, "frame planes must be 256-byte aligned");
     } else if (p.no_planes) return fail(LEON_ERR_INVALID, "no_planes without rgba_out: the picture would leave nothing behind");
     return LEON_OK;
 }
@@ -337,7 +372,7 @@ void fill_desc(const leon_decoder* d, const AnyPic& a, PicDesc& o)
     o.ref_bwd = p.type == LEON_PIC_B ? d->d_slots + (size_t)p.ref_bwd_slot * d->slot_stride : nullptr;
     o.type = p.type;
     o.rgba = (uint8_t*)p.rgba_out;
-    o.no_planes = p.rgba_out ? p.no_planes : 0;
+    o.no_planes = p.rgba_out || a.planes_out ? p.no_planes : 0;
     o.pad_ = 0;
     o.qt = p.qm_set > 0 ? d->d_qsets + p.qm_set : &d->d_tables->q;
 }
@@ -356,9 +391,11 @@ int guard_pending_conversions(leon_decoder* d, const int32_t* out_slots, int n)
 }
 
 // one launch of the type-specialised kernel over n pictures of that type
+// out: 0 planes only, 1 RGBA, 2 the frames' YCbCr planes (frames[i]: picture i's record), 3 both (class_of)
 int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, double dense_bytes, bool sparse = false, uint64_t entries = 0,
-                      bool display = false)
+                      int out = 0, uint8_t* const* frames = nullptr)
 {
+    const bool display = out != 0;
     Geom G = d->geom;
     G.n_pics = n;
     const bool alpha = d->geom.alpha != 0;
@@ -391,7 +428,29 @@ int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, 
     const size_t lds_pad = pair ? (type == LEON_PIC_P ? kOccupancyPadPairP : 0)
                                 : display && !sparse && !alpha ? (type == LEON_PIC_I ? kOccupancyPadI : type == LEON_PIC_P ? kOccupancyPadP : kOccupancyPadB) : 0;
     const size_t lds = (size_t)kWavesPerWG * (display ? (alpha ? kLdsPerWaveDisplayAlpha : (pair ? kLdsPerWaveDisplayPair : kLdsPerWaveDisplay)) : kLdsPerWave) + lds_pad;      // display kernels: + kLdsLut of static LDS (the conversion tables)
-    if (display && alpha) {          // yuva: the A parts ride in the same task (k_recon_display<.., .., true>)
+    if (out >= 2) {                  // k_recon_display_out: the same tasks, LDS and occupancy as k_recon_display
+        // (the pipeline's boundary only: the frames' planes are a pipeline output, and the pipeline submits group lists)
+        if (!sparse) return fail(LEON_ERR_INVALID, "frame planes output needs the sparse boundary");
+        FrameOut fo = d->frame_out;
+        fo.frames = frames;
+        const int k = (type - 1) * 4 + (alpha ? 2 : 0) + (out == 3 ? 1 : 0);
+#define LEON_OUT_LAUNCH(T, A, O) hipLaunchKernelGGL((k_recon_display_out<T, true, A, O>), grid, block, lds, d->stream, d_descs, G, d->d_tables, fo)
+        switch (k) {
+        case 0: LEON_OUT_LAUNCH(1, false, kOutYcbcr); break;
+        case 1: LEON_OUT_LAUNCH(1, false, kOutBoth); break;
+        case 2: LEON_OUT_LAUNCH(1, true, kOutYcbcr); break;
+        case 3: LEON_OUT_LAUNCH(1, true, kOutBoth); break;
+        case 4: LEON_OUT_LAUNCH(2, false, kOutYcbcr); break;
+        case 5: LEON_OUT_LAUNCH(2, false, kOutBoth); break;
+        case 6: LEON_OUT_LAUNCH(2, true, kOutYcbcr); break;
+        case 7: LEON_OUT_LAUNCH(2, true, kOutBoth); break;
+        case 8: LEON_OUT_LAUNCH(3, false, kOutYcbcr); break;
+        case 9: LEON_OUT_LAUNCH(3, false, kOutBoth); break;
+        case 10: LEON_OUT_LAUNCH(3, true, kOutYcbcr); break;
+        default: LEON_OUT_LAUNCH(3, true, kOutBoth); break;
+        }
+#undef LEON_OUT_LAUNCH
+    } else if (display && alpha) {          // yuva: the A parts ride in the same task (k_recon_display<.., .., true>)
         if (!sparse) {
             if (type == LEON_PIC_I) hipLaunchKernelGGL((k_recon_display<1, false, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
             else if (type == LEON_PIC_P) hipLaunchKernelGGL((k_recon_display<2, false, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
@@ -428,21 +487,22 @@ int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, 
     return LEON_OK;
 }
 
-// launch class of a picture: its type, and whether the display conversion is fused in
-inline int class_of(const leon_picture& p) { return (p.rgba_out ? 3 : 0) + p.type - 1; }
+// launch class of a picture: its type, and what its launch writes besides the slot (kClasses)
+inline int class_of(const AnyPic& a) { return 3 * (a.planes_out ? (a.p.rgba_out ? 3 : 2) : (a.p.rgba_out ? 1 : 0)) + a.p.type - 1; }
 
-// descriptors sorted by class; one launch per class present
-int launch_recon(leon_decoder* d, const PicDesc* d_descs, const int count[6], const double bytes[6], bool sparse = false, const uint64_t* entries = nullptr)
+// descriptors sorted by class; one launch per class present.  frames: the frame-planes records beside the descriptors (classes 6 .. 11)
+int launch_recon(leon_decoder* d, const PicDesc* d_descs, const int count[kClasses], const double bytes[kClasses], bool sparse = false, const uint64_t* entries = nullptr,
+                 uint8_t* const* frames = nullptr)
 {
     // B pictures first, anchors last: what the NEXT batch will read as references (I and P planes)
     // is then the most recently written data and still sits in the 256 MB Infinity Cache / L2,
     // instead of being pushed out by B planes nobody reads again.
-    int at[6];
-    for (int k = 0, a = 0; k < 6; k++) { at[k] = a; a += count[k]; }
-    static const int order[6] = {5, 2, 4, 1, 3, 0};
+    int at[kClasses];
+    for (int k = 0, a = 0; k < kClasses; k++) { at[k] = a; a += count[k]; }
+    static const int order[kClasses] = {11, 8, 5, 2, 10, 7, 4, 1, 9, 6, 3, 0};
     for (int k : order) {
         if (count[k] > 0) {
-            int rc = launch_recon_type(d, k % 3 + 1, d_descs + at[k], count[k], bytes[k], sparse, entries ? entries[k] : 0, k >= 3);
+            int rc = launch_recon_type(d, k % 3 + 1, d_descs + at[k], count[k], bytes[k], sparse, entries ? entries[k] : 0, k / 3, frames ? frames + at[k] : nullptr);
             if (rc != LEON_OK) return rc;
         }
     }
@@ -450,16 +510,21 @@ int launch_recon(leon_decoder* d, const PicDesc* d_descs, const int count[6], co
 }
 
 // fill `out` with the descriptors of pics sorted by class, and the per-class counts
-void sorted_descs(const leon_decoder* d, const AnyPic* pics, int n, PicDesc* out, int count[6], uint64_t entries[6])
+// (frames: the frame-planes record of each descriptor, in the same order; may be null when no picture has one)
+void sorted_descs(const leon_decoder* d, const AnyPic* pics, int n, PicDesc* out, int count[kClasses], uint64_t entries[kClasses], uint8_t** frames = nullptr)
 {
-    for (int k = 0; k < 6; k++) { count[k] = 0; entries[k] = 0; }
+    for (int k = 0; k < kClasses; k++) { count[k] = 0; entries[k] = 0; }
     for (int i = 0; i < n; i++) {
-        count[class_of(pics[i].p)]++;
-        entries[class_of(pics[i].p)] += pics[i].n_entries;
+        count[class_of(pics[i])]++;
+        entries[class_of(pics[i])] += pics[i].n_entries;
     }
-    int at[6];
-    for (int k = 0, a = 0; k < 6; k++) { at[k] = a; a += count[k]; }
-    for (int i = 0; i < n; i++) fill_desc(d, pics[i], out[at[class_of(pics[i].p)]++]);
+    int at[kClasses];
+    for (int k = 0, a = 0; k < kClasses; k++) { at[k] = a; a += count[k]; }
+    for (int i = 0; i < n; i++) {
+        const int j = at[class_of(pics[i])]++;
+        fill_desc(d, pics[i], out[j]);
+        if (frames) frames[j] = pics[i].planes_out;
+    }
 }
 
 // Large buffers: physically contiguous when the device grants it (include/leon.h leon_device_malloc) -- by default ONLY
@@ -702,6 +767,7 @@ int leon_create(const leon_config* cfg, leon_decoder** out)
     G.fh = cfg->frame_height;
     d->plane_bytes = (size_t)G.cw * G.ch * (G.alpha ? 5 : 3) / 2;
     d->slot_stride = (d->plane_bytes + 255) / 256 * 256 + 256;   // tail pad: the 12-byte MC window may over-read 3 bytes
+    d->frame_out = planes_layout(cfg->frame_width, cfg->frame_height, nullptr);
     d->inuse.assign(cfg->n_slots, 0);
     auto bail = [&](const char* what) {
         std::string msg = std::string(what) + ": " + hipGetErrorString(hipGetLastError());
@@ -754,6 +820,12 @@ void leon_destroy(leon_decoder* d)
     if (d->h_qsets) hipHostFree(d->h_qsets);
     if (d->d_desc_ring) hipFree(d->d_desc_ring);
     if (d->h_desc_pinned) hipHostFree(d->h_desc_pinned);
+    if (d->d_frames_ring) hipFree(d->d_frames_ring);
+    if (d->h_frames_pinned) hipHostFree(d->h_frames_pinned);
+    if (d->d_crop_slots) hipFree(d->d_crop_slots);
+    if (d->h_crop_slots) hipHostFree(d->h_crop_slots);
+    if (d->d_crop_frames) hipFree(d->d_crop_frames);
+    if (d->h_crop_frames) hipHostFree(d->h_crop_frames);
     if (d->d_slot_ids) hipFree(d->d_slot_ids);
     if (d->h_slot_ids) hipHostFree(d->h_slot_ids);
     if (d->d_rgba_tmp) hipFree(d->d_rgba_tmp);
@@ -938,7 +1010,7 @@ int check_batch(leon_decoder* d, const AnyPic* pics, int n)
         d->epoch = 1;
     }
     for (int i = 0; i < n; i++) {
-        if (pics[i].p.rgba_out && pics[i].p.no_planes) continue;       // writes no slot
+        if ((pics[i].p.rgba_out || pics[i].planes_out) && pics[i].p.no_planes) continue;       // writes no slot (out_slot may be -1)
         const int s = pics[i].p.out_slot;
         if (d->writer_epoch[s] == d->epoch)
             return fail(LEON_ERR_INVALID, "pictures %d and %d of one batch depend on each other (both write slot %d)", d->writer_of[s], i, s);
@@ -961,6 +1033,14 @@ int submit_batch_any(leon_decoder* d, const AnyPic* pics, int n, int mem)
     HIP_TRY(hipSetDevice(d->dev));
     int rc = check_batch(d, pics, n);
     if (rc != LEON_OK) return rc;
+    bool any_frames = false;
+    for (int i = 0; i < n; i++) any_frames = any_frames || pics[i].planes_out;
+    if (any_frames && mem != LEON_MEM_DEVICE) return fail(LEON_ERR_INVALID, "frame planes output needs device-resident pictures");
+    if (any_frames && !d->d_frames_ring) {
+        if (hipMalloc(&d->d_frames_ring, sizeof(uint8_t*) * leon_decoder::kDescRing) != hipSuccess ||
+            hipHostMalloc((void**)&d->h_frames_pinned, sizeof(uint8_t*) * leon_decoder::kDescRing) != hipSuccess)
+            return fail(LEON_ERR_NOMEM, "frame-planes descriptor ring");
+    }
     if (mem == LEON_MEM_HOST) {
         for (int i = 0; i < n; i++) {
             rc = submit_picture_any(d, pics[i]);
@@ -977,19 +1057,20 @@ int submit_batch_any(leon_decoder* d, const AnyPic* pics, int n, int mem)
         rc = guard_pending_conversions(d, outs.data(), n);
         if (rc != LEON_OK) return rc;
     }
-    int count[6];
-    uint64_t entries[6];
-    sorted_descs(d, pics, n, d->h_desc_pinned + at, count, entries);
-    double bytes[6] = {0, 0, 0, 0, 0, 0};
+    int count[kClasses];
+    uint64_t entries[kClasses];
+    sorted_descs(d, pics, n, d->h_desc_pinned + at, count, entries, any_frames ? d->h_frames_pinned + at : nullptr);
+    double bytes[kClasses] = {};
     if (d->timing)   // a measurement mode: the maps are read back to price the launches
         for (int i = 0; i < n; i++) {
             double b = 0;
             rc = algo_bytes_of(d, pics[i].p, true, b);
             if (rc != LEON_OK) return rc;
-            bytes[class_of(pics[i].p)] += b;
+            bytes[class_of(pics[i])] += b;
         }
     HIP_TRY(hipMemcpyAsync(d->d_desc_ring + at, d->h_desc_pinned + at, sizeof(PicDesc) * n, hipMemcpyHostToDevice, d->stream));
-    rc = launch_recon(d, d->d_desc_ring + at, count, bytes, pics[0].sparse, entries);
+    if (any_frames) HIP_TRY(hipMemcpyAsync(d->d_frames_ring + at, d->h_frames_pinned + at, sizeof(uint8_t*) * n, hipMemcpyHostToDevice, d->stream));
+    rc = launch_recon(d, d->d_desc_ring + at, count, bytes, pics[0].sparse, entries, any_frames ? d->d_frames_ring + at : nullptr);
     if (rc != LEON_OK) return rc;
     return commit_descs(d, at, n);
 }
@@ -1013,7 +1094,7 @@ int batch_create_any(leon_decoder* d, const AnyPic* pics, int n, leon_batch** ou
             delete b;
             return rc;
         }
-        b->bytes_of_type[class_of(pics[i].p)] += pb;
+        b->bytes_of_type[class_of(pics[i])] += pb;
     }
     b->out_slots.resize(n);
     for (int i = 0; i < n; i++) b->out_slots[i] = pics[i].p.out_slot;
@@ -1028,6 +1109,49 @@ int batch_create_any(leon_decoder* d, const AnyPic* pics, int n, leon_batch** ou
         return fail(LEON_ERR_HIP, "descriptor upload: %s", hipGetErrorString(e));
     }
     *out = b;
+    return LEON_OK;
+}
+
+// the unfused road's frame planes: slot planes of n pictures -> their frames' planes records, one k_planes_crop launch
+int crop_planes_batch(leon_decoder* d, const int32_t* slots, uint8_t* const* frames, int n)
+{
+    constexpr int kRing = leon_decoder::kSlotIdRing;
+    if (n <= 0) return LEON_OK;
+    if (n > kRing) return fail(LEON_ERR_INVALID, "more than %d frames in one planes crop", kRing);
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= d->cfg.n_slots) return fail(LEON_ERR_INVALID, "slot %d", slots[i]);
+        if (!frames[i] || ((size_t)frames[i] & 255)) return fail(LEON_ERR_INVALID, "frame planes must be 256-byte aligned");
+    }
+    if (!d->d_crop_slots) {
+        if (hipMalloc(&d->d_crop_slots, sizeof(int32_t) * kRing) != hipSuccess || hipHostMalloc((void**)&d->h_crop_slots, sizeof(int32_t) * kRing) != hipSuccess ||
+            hipMalloc(&d->d_crop_frames, sizeof(uint8_t*) * kRing) != hipSuccess || hipHostMalloc((void**)&d->h_crop_frames, sizeof(uint8_t*) * kRing) != hipSuccess)
+            return fail(LEON_ERR_NOMEM, "planes crop ring");
+    }
+    if (d->crop_head + n > kRing) {                 // a lap: what the ring's launches read has been read
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        d->crop_head = 0;
+    }
+    const int at = d->crop_head;
+    d->crop_head += n;
+    memcpy(d->h_crop_slots + at, slots, sizeof(int32_t) * n);
+    memcpy(d->h_crop_frames + at, frames, sizeof(uint8_t*) * n);
+    HIP_TRY(hipMemcpyAsync(d->d_crop_slots + at, d->h_crop_slots + at, sizeof(int32_t) * n, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->d_crop_frames + at, d->h_crop_frames + at, sizeof(uint8_t*) * n, hipMemcpyHostToDevice, d->stream));
+    FrameOut fo = d->frame_out;
+    fo.frames = d->d_crop_frames + at;
+    CropGeom G{};
+    G.cw = d->cfg.coded_width; G.ch = d->cfg.coded_height;
+    G.fw = d->cfg.frame_width; G.fh = d->cfg.frame_height;
+    G.cwid = (G.fw + 1) / 2;
+    G.slot_stride_lo = (uint32_t)(d->slot_stride & 0xffffffffu);
+    G.slot_stride_hi = (uint32_t)(d->slot_stride >> 32);
+    G.alpha = d->geom.alpha;
+    // the plane with the most pieces: Y, (fw + 15) / 16 per row, or a chroma plane, (cwid + 7) / 8 per row
+    const size_t pieces = std::max((size_t)(G.fw + 15) / 16 * (size_t)G.fh, (size_t)(G.cwid + 7) / 8 * (size_t)fo.chroma_height);
+    if (pieces == 0) return LEON_OK;
+    hipLaunchKernelGGL(k_planes_crop, dim3((unsigned)((pieces + kRgbaBlock - 1) / kRgbaBlock), G.alpha ? 4 : 3, n), dim3(kRgbaBlock), 0, d->stream,
+                       d->d_slots, d->d_crop_slots + at, fo, G);
+    HIP_TRY(hipGetLastError());
     return LEON_OK;
 }
 

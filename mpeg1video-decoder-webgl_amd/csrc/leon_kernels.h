@@ -88,6 +88,18 @@ struct Tables {                  // per decoder
     int32_t rgba_lut[1280];      // fused display conversion: fixed-point terms of YCbCrToRGBA (leon_rgba_lut.h)
 };
 
+// Output of a display task (k_recon_display_out): RGBA (what k_recon_display writes), the cropped YCbCr 4:2:0 planes of the frame
+// (include/leon_pipeline.h: rows padded to 64 bytes, planes on 256-byte boundaries), or both.  Pictures with planes output find
+// their frame's planes in FrameOut::frames[picture of the launch]: PicDesc keeps its 152 bytes, so the code of the RGBA kernels,
+// which index it, stays as it is.
+static constexpr int kOutRgba = 0, kOutYcbcr = 1, kOutBoth = 2;
+struct FrameOut {
+    uint8_t* const* frames;      // per picture of the launch: its frame's planes record [Y | Cb | Cr (| A)]
+    uint32_t luma_stride, chroma_stride;   // bytes per row: the plane width rounded up to 64
+    uint32_t cb_off, cr_off, a_off;        // byte offsets of the planes in the record (multiples of 256)
+    int32_t chroma_height;       // (frame_height + 1) / 2; Y and A have frame_height rows (Geom::fh)
+};
+
 static constexpr int kWavesPerWG = 4;
 // Launch block sizes and the kernels' __launch_bounds__ come from the same constants: a launch with
 // more threads than the bound fails at launch time ("unspecified launch failure" from
@@ -583,6 +595,8 @@ struct Display {
     int side;                    // luma parts: 0 / 1 = left / right four macroblocks of the chroma group
     char* apark;                 // yuva: the A samples of the four macroblocks, [half][8 rows][64 bytes]
     const char* lut;             // LDS copy of Tables::rgba_lut (the workgroup's)
+    uint8_t* planes;             // OUT != kOutRgba: the picture's frame planes (FrameOut), else null
+    const struct FrameOut* fo;
 };
 // AMODE of recon_task in a yuva display task: the A part runs before the Y part of the same four macroblocks
 // and parks its samples (1); the Y part's conversion takes its alpha bytes from there (2); 0 otherwise.
@@ -798,7 +812,7 @@ struct MbCarry { uint32_t flags; };       // q | intra << 8 | repadd >= 128 << 9
 
 // BACK (dense display tasks whose two luma parts share their front, recon_luma_pair): the part's coefficients are in `tile` and have
 // been through the column pass already; `live_in` says which of its columns were live
-template <int TYPE, bool CHROMA, bool SPARSE, bool DISPLAY, int AMODE = 0, int CARRY = 0, bool BACK = false, int LAYOUT = 0>
+template <int TYPE, bool CHROMA, bool SPARSE, bool DISPLAY, int AMODE = 0, int CARRY = 0, bool BACK = false, int LAYOUT = 0, int OUT = kOutRgba>
 __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int Rt, int g, char* lds, int lane, Display dsp, MbCarry& carry, bool alpha = false,
                                            char* tile_in = nullptr, uint64_t live_in0 = 0, uint64_t live_in1 = 0, uint32_t qreg = 0u)
 {
@@ -1070,7 +1084,20 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
             // store was issued into a resource without records, which drops it -- after the texture path has processed it; a B task
             // issued six such stores among its 54 memory instructions
             if (!pd.no_planes) __builtin_amdgcn_raw_buffer_store_b64(o, buf_rsrc(pd.out + plane_off), (int)out_voff, (int)(half ? half_step : 0u), 0);
-            if constexpr (CHROMA) {
+            if constexpr (OUT != kOutRgba) {
+                // the frame's cropped plane: the same 8 samples, row y of Y / A (luma: half = the next block row) or of Cb / Cr
+                // (chroma: half = the plane).  Every 8-byte chunk of the coded width lies inside the 64-byte row stride, so only
+                // rows past the plane height are dropped -- by the offset select, like every other store here.
+                const FrameOut& fo = *dsp.fo;
+                const int y = CHROMA ? 8 * Rt + hi3 : 8 * (2 * Rt + half) + hi3;
+                const bool in = valid && y < (CHROMA ? fo.chroma_height : G.fh);
+                const uint32_t po = CHROMA ? (half ? fo.cr_off : fo.cb_off) : (AMODE == 1 ? fo.a_off : 0u);
+                const uint32_t fvoff = (__umul24((uint32_t)y, CHROMA ? fo.chroma_stride : fo.luma_stride) + (uint32_t)x0) | (in ? 0u : kOobBit);
+                __builtin_amdgcn_raw_buffer_store_b64(o, buf_rsrc(dsp.planes + po), (int)fvoff, 0, kAuxFrameStore);
+            }
+            if constexpr (OUT == kOutYcbcr) {
+                // no display stage: nothing is parked for a conversion
+            } else if constexpr (CHROMA) {
                 // park the samples for the luma parts: [plane = half][row hi3][8 bytes of macroblock lo3]
                 *reinterpret_cast<v2u*>(dsp.stash + half * 512 + hi3 * 64 + lo3 * 8) = o;
             } else if constexpr (AMODE == 1) {
@@ -1085,7 +1112,7 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
                 *reinterpret_cast<v2u*>((Lay<LAYOUT>::park_in_tile ? tile + half * kLdsHalf : lds + kOffYpark) + hi3 * 64 + lo3 * 8) = o;
             }
         }
-        if constexpr (DISPLAY && !CHROMA && AMODE != 1) {
+        if constexpr (DISPLAY && !CHROMA && AMODE != 1 && OUT != kOutYcbcr) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1103,7 +1130,7 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
 // has about a dozen live columns of 128, and a pass costs ~140 instructions however few of its 64 lanes have a column -- and then each
 // part runs its back half (maps from the chroma part, reference fetches, row passes, prediction, stores, conversion) as before.
 // I pictures keep a front per part: with ~40 live columns per part the shared pass would run twice anyway.
-template <int TYPE>
+template <int TYPE, int OUT = kOutRgba>
 __device__ __forceinline__ void recon_luma_pair(const PicDesc& pd, const Geom& G, int Rt, int gc, char* lds, int lane, Display dsp, MbCarry& carry, bool has_right,
                                                 uint32_t qreg)
 {
@@ -1148,10 +1175,10 @@ __device__ __forceinline__ void recon_luma_pair(const PicDesc& pd, const Geom& G
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     dsp.side = 0;
-    recon_task<TYPE, false, false, true, 0, 2, true, 1>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, false, lds, liveL[0], liveL[1]);
+    recon_task<TYPE, false, false, true, 0, 2, true, 1, OUT>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, false, lds, liveL[0], liveL[1]);
     if (has_right) {
         dsp.side = 1;
-        recon_task<TYPE, false, false, true, 0, 2, true, 1>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, false, tileR, liveR[0], liveR[1]);
+        recon_task<TYPE, false, false, true, 0, 2, true, 1, OUT>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, false, tileR, liveR[0], liveR[1]);
     }
 }
 
@@ -1243,14 +1270,18 @@ __global__ __launch_bounds__(kReconMaxThreads) void k_recon(const PicDesc* __res
 // spilled dwords (8 bytes of scratch per lane) cost less than the wave brings: +1..2 % end to end, three pairs on one box.
 // one display task of a wave: the chroma part, the workgroup's barrier in front of the first table lookup (`first`: every wave of the
 // workgroup comes by here exactly once), the luma parts.  false: the wave has no task (and none behind this one).
-template <int TYPE, bool SPARSE, bool ALPHA>
-__device__ __forceinline__ bool display_task(const PicDesc* __restrict__ descs, const Geom& G, int pic, int t, char* lds, int lane, const char* lut, bool first)
+// OUT (kOutYcbcr / kOutBoth): the task also stores the frame's planes (FrameOut); kOutYcbcr converts nothing, so it neither waits
+// for the conversion tables nor meets the other waves at the barrier.
+template <int TYPE, bool SPARSE, bool ALPHA, int OUT = kOutRgba>
+__device__ __forceinline__ bool display_task(const PicDesc* __restrict__ descs, const Geom& G, int pic, int t, char* lds, int lane, const char* lut, bool first,
+                                             const FrameOut* fo = nullptr)
 {
     constexpr bool kPair = !SPARSE && !ALPHA && TYPE != 1;      // recon_luma_pair
     const bool live = t < G.tasks_per_pic && pic < G.n_pics;
     const PicDesc& pd = descs[live ? pic : 0];
     const int Rt = div_inv(t, G.inv_gC), gc = t - Rt * G.gC;
-    Display dsp{lds + (kPair ? Lay<1>::stash : Lay<0>::stash), 0, lds + kLdsPerWaveDisplay, lut};
+    Display dsp{lds + (kPair ? Lay<1>::stash : Lay<0>::stash), 0, lds + kLdsPerWaveDisplay, lut, nullptr, fo};
+    if constexpr (OUT != kOutRgba) dsp.planes = fo->frames[live ? pic : 0];
     if constexpr (!kPair) {
         if (!first) { wait_lds_all(); __builtin_amdgcn_wave_barrier(); }      // the column pass of the task before has read its tables
         stage_tables(pd.qt, lds, lane);
@@ -1260,32 +1291,32 @@ __device__ __forceinline__ bool display_task(const PicDesc* __restrict__ descs, 
     // in lane i (column_pass takes what it needs by ds_bpermute); requested first, landed with the macroblock maps
     uint32_t qreg = 0u;
     if constexpr (kPair) qreg = ldg<uint32_t>(gptr(pd.qt), (uint32_t)lane * 4u);
-    if (live) recon_task<TYPE, true, SPARSE, true, 0, 1, false, kPair ? 1 : 0>(pd, G, Rt, gc, lds, lane, dsp, carry, false, nullptr, 0, 0, qreg);
+    if (live) recon_task<TYPE, true, SPARSE, true, 0, 1, false, kPair ? 1 : 0, OUT>(pd, G, Rt, gc, lds, lane, dsp, carry, false, nullptr, 0, 0, qreg);
     if (first) {
         if (!live) wait_vmem_all();      // (a wave with a task has waited for memory behind its chroma part's loads: its chunks of the tables are in)
-        __syncthreads();                 // the conversion tables have landed: every wave's chunks
+        if constexpr (OUT != kOutYcbcr) __syncthreads();      // the conversion tables have landed: every wave's chunks
     }
     if (!live) return false;
     // the two luma parts as two calls, not a loop: the loop form keeps 15 more registers live (B path: 93).
     // yuva: the A part of the same four macroblocks first (AMODE 1), then the Y part that displays them (AMODE 2).
     if constexpr (kPair) {
-        recon_luma_pair<TYPE>(pd, G, Rt, gc, lds, lane, dsp, carry, 2 * gc + 1 < G.gY, qreg);
+        recon_luma_pair<TYPE, OUT>(pd, G, Rt, gc, lds, lane, dsp, carry, 2 * gc + 1 < G.gY, qreg);
         return true;
     }
     dsp.side = 0;
     if constexpr (ALPHA) {
-        recon_task<TYPE, false, SPARSE, true, 1, 2>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, true);
-        recon_task<TYPE, false, SPARSE, true, 2, 2>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
+        recon_task<TYPE, false, SPARSE, true, 1, 2, false, 0, OUT>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, true);
+        recon_task<TYPE, false, SPARSE, true, 2, 2, false, 0, OUT>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
     } else {
-        recon_task<TYPE, false, SPARSE, true, 0, 2>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
+        recon_task<TYPE, false, SPARSE, true, 0, 2, false, 0, OUT>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
     }
     if (2 * gc + 1 < G.gY) {
         dsp.side = 1;
         if constexpr (ALPHA) {
-            recon_task<TYPE, false, SPARSE, true, 1, 2>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, true);
-            recon_task<TYPE, false, SPARSE, true, 2, 2>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
+            recon_task<TYPE, false, SPARSE, true, 1, 2, false, 0, OUT>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, true);
+            recon_task<TYPE, false, SPARSE, true, 2, 2, false, 0, OUT>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
         } else {
-            recon_task<TYPE, false, SPARSE, true, 0, 2>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
+            recon_task<TYPE, false, SPARSE, true, 0, 2, false, 0, OUT>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
         }
     }
     return true;
@@ -1329,6 +1360,71 @@ void k_recon_display(const PicDesc* __restrict__ descs, Geom G,
     // works on the next: 5.89-5.92 ms per step with two against 5.90-5.95 with one, worse with three and five, and 10-20 registers more
     // for the loop -- not kept.)
     display_task<TYPE, SPARSE, ALPHA>(descs, G, pic, twg * wpw + wave, lds, lane0, reinterpret_cast<const char*>(lut_s), true);
+}
+
+
+// The same launch with the frame's YCbCr planes as output (OUT = kOutYcbcr: planes only, no conversion; kOutBoth: planes and
+// RGBA).  I and P pictures still write their slots (motion compensation reads the coded-size planes), B pictures (no_planes) only
+// the frame's planes.  The strip layout and the launch geometry are k_recon_display's; kOutYcbcr leaves the strip's stash and park
+// unused and loads no conversion tables.  A kernel of its own rather than a parameter of k_recon_display: a fourth argument would
+// move the implicit arguments the RGBA kernels read.  Each instantiation keeps at least its RGBA twin's waves per SIMD: the yuva P kernel
+// with both outputs wants 104 scalar registers (7 waves) and is held to the twin's 8.
+template <int TYPE, bool SPARSE, bool ALPHA, int OUT>
+__global__ __launch_bounds__(kReconMaxThreads) __attribute__((amdgpu_waves_per_eu(TYPE == 3 && !ALPHA ? 7 : (TYPE == 2 && ALPHA && OUT == kOutBoth ? 8 : 4))))
+void k_recon_display_out(const PicDesc* __restrict__ descs, Geom G, const Tables* __restrict__ T, FrameOut fo)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (TYPE == 3 && !SPARSE && !ALPHA) __builtin_amdgcn_s_setprio(3);      // as k_recon_display
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane0 = threadIdx.x & 63;
+    const int wg = xcd_remap(blockIdx.x, G.n_wg);
+    int pic, twg;
+    pic_of_wg<TYPE>(G, wg, pic, twg);
+    const int wpw = (int)(blockDim.x >> 6);
+    // the conversion tables (kOutBoth only), as k_recon_display loads them
+    __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
+    if constexpr (OUT == kOutBoth) {
+        const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc((void*)T->rgba_lut, 0, kLdsLut, 0x00020000);
+        const int n_waves = (int)(blockDim.x >> 6);
+        for (int c = wave; c < kLdsLut / 1024; c += n_waves)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lut_s) + c * 1024), 16,
+                                                     (int)(lane0 * 16u), c * 1024, 0, 0);
+    }
+    constexpr bool kPair = !SPARSE && !ALPHA && TYPE != 1;
+    char* lds = smem + wave * (ALPHA ? kLdsPerWaveDisplayAlpha : (kPair ? kLdsPerWaveDisplayPair : kLdsPerWaveDisplay));
+    display_task<TYPE, SPARSE, ALPHA, OUT>(descs, G, pic, twg * wpw + wave, lds, lane0, OUT == kOutBoth ? reinterpret_cast<const char*>(lut_s) : nullptr, true, &fo);
+}
+
+// ---- the frames' planes on the unfused road: slot planes -> cropped frame planes (FrameOut layout) ------------------------
+// One launch per batch: blockIdx.z = picture (src_slots[z] -> FrameOut::frames[z]), blockIdx.y = plane (Y, Cb, Cr, A), a lane = one
+// piece of one row: 16 bytes of Y / A (the slot's luma rows are coded_width apart, a multiple of 16), 8 bytes of Cb / Cr (their rows
+// are coded_width / 2 apart, a multiple of 8 only).  A piece never reaches past the coded row nor past the 64-byte destination stride.
+struct CropGeom {
+    int32_t cw, ch, fw, fh;
+    int32_t cwid;                // (fw + 1) / 2
+    uint32_t slot_stride_lo, slot_stride_hi;
+    int32_t alpha;
+};
+__global__ __launch_bounds__(kRgbaBlock) void k_planes_crop(const uint8_t* __restrict__ slots, const int32_t* __restrict__ src_slots, FrameOut fo, CropGeom G)
+{
+    const int plane = blockIdx.y;
+    if (plane == 3 && !G.alpha) return;
+    const bool luma = plane == 0 || plane == 3;
+    const uint32_t piece = luma ? 16u : 8u;
+    const uint32_t pw = (uint32_t)(luma ? G.fw : G.cwid), ph = (uint32_t)(luma ? G.fh : fo.chroma_height);
+    const uint32_t per_row = (pw + piece - 1) / piece;
+    const uint32_t idx = blockIdx.x * (uint32_t)blockDim.x + threadIdx.x;
+    if (idx >= per_row * ph) return;
+    const uint32_t y = idx / per_row, x = (idx - y * per_row) * piece;
+    const uint32_t ysz = (uint32_t)G.cw * (uint32_t)G.ch;
+    const uint32_t src_w = luma ? (uint32_t)G.cw : (uint32_t)G.cw >> 1;
+    const uint32_t src_plane = plane == 0 ? 0u : plane == 1 ? ysz : plane == 2 ? ysz + (ysz >> 2) : ysz + (ysz >> 1);
+    const size_t stride = ((size_t)G.slot_stride_hi << 32) | G.slot_stride_lo;
+    const uint8_t* src = slots + (size_t)src_slots[blockIdx.z] * stride + src_plane + (size_t)y * src_w + x;
+    uint8_t* dst = fo.frames[blockIdx.z] + (plane == 0 ? 0u : plane == 1 ? fo.cb_off : plane == 2 ? fo.cr_off : fo.a_off)
+                 + (size_t)y * (luma ? fo.luma_stride : fo.chroma_stride) + x;
+    if (luma) *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
+    else *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(src);
 }
 
 // ---- K3: YCbCr 4:2:0 -> RGBA8 ------------------------------------------------------

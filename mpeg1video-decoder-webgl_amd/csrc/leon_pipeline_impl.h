@@ -108,11 +108,15 @@ struct leon_pipeline {
     std::string capture_dir;     // LEON_DEBUG_CAPTURE=<dir> at create: everything a window's launches read and wrote goes to files (capture_*)
     bool unfused = false;        // frame_width % 8 != 0, or the GL flavour: planes for every picture, one display conversion launch per picture
     int flavour = LEON_RGB_CPU_TWIN;      // leon_pipeline_config.display_flavour
-    size_t frame_bytes = 0;
+    size_t frame_bytes = 0;      // RGBA bytes of a frame
+    int output = LEON_PIPELINE_OUTPUT_RGBA;           // leon_pipeline_config.output, 0 resolved
+    FrameOut planes_geom{};      // the frames' plane layout (planes_layout)
+    size_t planes_bytes = 0;     // one frame's planes record [Y | Cb | Cr (| A)], a multiple of 256
 
     leon_decoder* dec = nullptr;
     hipStream_t copy_stream = nullptr;
-    uint8_t* d_rgba = nullptr;                        // R ring entries of W * max_pics frames
+    uint8_t* d_rgba = nullptr;                        // R ring entries of W * max_pics frames (output RGBA)
+    uint8_t* d_planes = nullptr;                      // the same for the frames' planes records (output YCbCr)
     bool gpu_parser = false;
     // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
     // window n + 2, on a second stream: a parse launch lasts as long as its longest slice (one lane, symbol after symbol) and
@@ -633,7 +637,11 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
     const size_t lanes = w->jobs.size();
     struct Item { size_t lane; const PipePic* pic; int fwd, bwd, out; };
     std::vector<std::vector<Item>> levels;
-    uint8_t* ring = p->d_rgba + (size_t)w->ring * p->W * p->max_pics * p->frame_bytes;
+    const bool want_rgba = (p->output & LEON_PIPELINE_OUTPUT_RGBA) != 0, want_planes = (p->output & LEON_PIPELINE_OUTPUT_YCBCR) != 0;
+    uint8_t* ring = want_rgba ? p->d_rgba + (size_t)w->ring * p->W * p->max_pics * p->frame_bytes : nullptr;
+    uint8_t* pring = want_planes ? p->d_planes + (size_t)w->ring * p->W * p->max_pics * p->planes_bytes : nullptr;
+    auto rgba_of = [&](size_t lane, size_t tref) { return ring ? ring + (lane * p->max_pics + tref) * p->frame_bytes : nullptr; };
+    auto planes_of = [&](size_t lane, size_t tref) { return pring ? pring + (lane * p->max_pics + tref) * p->planes_bytes : nullptr; };
     w->frames.clear();
     for (size_t j = 0; j < lanes; j++) {
         GopJob* job = w->jobs[j];
@@ -734,8 +742,12 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
     }
     size_t lvl_no = 0;
     std::vector<leon_sparse_picture> batch;
+    std::vector<uint8_t*> batch_planes;
+    std::vector<int32_t> crop_slots;
+    std::vector<uint8_t*> crop_frames;
     for (auto& lvl : levels) {
         batch.clear();
+        batch_planes.clear();
         for (const Item& it : lvl) {
             const char* base = w->jobs[it.lane]->arena->dev;
             const PipePic& m = *it.pic;
@@ -754,20 +766,36 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
             sp.mb_dir = (const uint8_t*)ptr(m.mb_dir);
             sp.mv_fwd = (const int16_t*)ptr(m.mv_fwd);
             sp.mv_bwd = (const int16_t*)ptr(m.mv_bwd);
-            sp.rgba_out = p->unfused || !m.shown ? nullptr : ring + ((size_t)it.lane * p->max_pics + (size_t)m.tref) * p->frame_bytes;
+            // fused road: a shown picture's launch writes its frame (RGBA and / or planes), B pictures nothing else
+            sp.rgba_out = p->unfused || !m.shown ? nullptr : rgba_of(it.lane, (size_t)m.tref);
             sp.no_planes = !p->unfused && m.type == LEON_PIC_B;
             sp.qm_set = m.qm >= 0 ? qset[it.lane][(size_t)m.qm] : 0;
             batch.push_back(sp);
+            batch_planes.push_back(p->unfused || !m.shown ? nullptr : planes_of(it.lane, (size_t)m.tref));
         }
         if (batch.empty()) continue;
-        int rc = submit_batch_any(d, wrap(batch.data(), (int)batch.size()).data(), (int)batch.size(), LEON_MEM_DEVICE);
+        std::vector<AnyPic> apics = wrap(batch.data(), (int)batch.size());
+        for (size_t i = 0; i < apics.size(); i++) apics[i].planes_out = batch_planes[i];
+        int rc = submit_batch_any(d, apics.data(), (int)apics.size(), LEON_MEM_DEVICE);
         if (rc != LEON_OK) return rc;
-        if (p->unfused)
+        if (p->unfused) {
+            crop_slots.clear();
+            crop_frames.clear();
             for (const Item& it : lvl) {
                 if (!it.pic->shown) continue;
-                rc = leon_convert_rgba(d, it.out, ring + ((size_t)it.lane * p->max_pics + (size_t)it.pic->tref) * p->frame_bytes, LEON_MEM_DEVICE, p->flavour);
-                if (rc != LEON_OK) return rc;
+                if (want_rgba) {
+                    rc = leon_convert_rgba(d, it.out, rgba_of(it.lane, (size_t)it.pic->tref), LEON_MEM_DEVICE, p->flavour);
+                    if (rc != LEON_OK) return rc;
+                }
+                if (want_planes) {
+                    crop_slots.push_back(it.out);
+                    crop_frames.push_back(planes_of(it.lane, (size_t)it.pic->tref));
+                }
             }
+            // the level's shown pictures' planes, one launch (k_planes_crop)
+            rc = crop_planes_batch(d, crop_slots.data(), crop_frames.data(), (int)crop_slots.size());
+            if (rc != LEON_OK) return rc;
+        }
         if (capture) {
             HIP_TRY(hipStreamSynchronize(d->stream));
             for (const Item& it : lvl) {
@@ -803,7 +831,13 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
             f.display_index = (int32_t)k;
             f.type = by_disp[k]->type;
             f.ts_ms = job->gop_ts_ms + 1000.0 * (double)k / rate;
-            f.rgba = ring + ((size_t)j * p->max_pics + k) * p->frame_bytes;
+            f.rgba = rgba_of(j, k);
+            if (uint8_t* pl = planes_of(j, k)) {
+                f.y = pl;
+                f.cb = pl + p->planes_geom.cb_off;
+                f.cr = pl + p->planes_geom.cr_off;
+                f.a = p->vinfo.has_alpha == 1 ? pl + p->planes_geom.a_off : nullptr;
+            }
             w->frames.push_back(f);
         }
         p->st_pictures += job->pics.size();
@@ -1152,6 +1186,16 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     // writes its planes, and one leon_convert_rgba per picture (the generic k_rgba_twin) fills the window's frames.
     // The GL flavour (the reference's live display arithmetic, fp32) exists as a launch of its own only: the same road.
     if (cfg->display_flavour != LEON_RGB_CPU_TWIN && cfg->display_flavour != LEON_RGB_GL) { delete p; return fail(LEON_ERR_INVALID, "display_flavour %d", cfg->display_flavour); }
+    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR)) { delete p; return fail(LEON_ERR_INVALID, "output %d", cfg->output); }
+    // the frames' planes (output YCbCr): the layout of include/leon_pipeline.h, one record per frame, A behind Cr for yuva
+    p->output = cfg->output ? cfg->output : LEON_PIPELINE_OUTPUT_RGBA;
+    p->planes_geom = planes_layout(p->vinfo.frame_width, p->vinfo.frame_height, &p->planes_bytes);
+    if (p->vinfo.has_alpha == 1) p->planes_bytes = p->planes_geom.a_off + ((size_t)p->planes_geom.luma_stride * p->vinfo.frame_height + 255) / 256 * 256;
+    p->info.output = p->output;
+    p->info.chroma_width = (p->vinfo.frame_width + 1) / 2;
+    p->info.chroma_height = p->planes_geom.chroma_height;
+    p->info.luma_stride = (int32_t)p->planes_geom.luma_stride;
+    p->info.chroma_stride = (int32_t)p->planes_geom.chroma_stride;
     p->flavour = cfg->display_flavour;
     p->info.display_flavour = p->flavour;
     p->unfused = (p->vinfo.frame_width & 7) != 0 || p->flavour == LEON_RGB_GL;
@@ -1176,7 +1220,13 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     };
     if (rc != LEON_OK) { leon_pipeline_destroy(p); return rc; }
     if (hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking) != hipSuccess) return bail(LEON_ERR_HIP, "copy stream");
-    if (big_alloc((void**)&p->d_rgba, (size_t)p->R * p->W * p->max_pics * p->frame_bytes, kBigRgbaRing) != hipSuccess) {
+    if ((p->output & LEON_PIPELINE_OUTPUT_YCBCR) && big_alloc((void**)&p->d_planes, (size_t)p->R * p->W * p->max_pics * p->planes_bytes, kBigRgbaRing) != hipSuccess) {
+        const std::string what = "planes ring of " + std::to_string((size_t)p->R * p->W * p->max_pics * p->planes_bytes >> 20) + " MiB (windows_in_flight " +
+                                 std::to_string(p->R) + " x gops_per_window " + std::to_string(p->W) + " x max_gop_pictures " + std::to_string(p->max_pics) +
+                                 " x " + std::to_string(p->planes_bytes) + " bytes per frame)";
+        return bail(LEON_ERR_NOMEM, what.c_str());
+    }
+    if ((p->output & LEON_PIPELINE_OUTPUT_RGBA) && big_alloc((void**)&p->d_rgba, (size_t)p->R * p->W * p->max_pics * p->frame_bytes, kBigRgbaRing) != hipSuccess) {
         const std::string what = "RGBA ring of " + std::to_string((size_t)p->R * p->W * p->max_pics * p->frame_bytes >> 20) + " MiB (windows_in_flight " +
                                  std::to_string(p->R) + " x gops_per_window " + std::to_string(p->W) + " x max_gop_pictures " + std::to_string(p->max_pics) +
                                  " x " + std::to_string(p->frame_bytes) + " bytes per frame)";
@@ -1399,9 +1449,25 @@ int leon_pipeline_get_stats(leon_pipeline* p, leon_pipeline_stats* out)
 
 int leon_pipeline_read_frame(leon_pipeline* p, const leon_pipeline_frame* f, uint8_t* rgba_host)
 {
-    if (!p || !f || !f->rgba || !rgba_host) return fail(LEON_ERR_INVALID, "null argument");
+    if (!p || !f || !rgba_host) return fail(LEON_ERR_INVALID, "null argument");
+    if (!f->rgba) return fail(LEON_ERR_INVALID, "the frame has no RGBA (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_RGBA)");
     HIP_TRY(hipSetDevice(p->cfg.device_id));
     HIP_TRY(hipMemcpy(rgba_host, f->rgba, p->frame_bytes, hipMemcpyDeviceToHost));
+    return LEON_OK;
+}
+
+int leon_pipeline_read_frame_planes(leon_pipeline* p, const leon_pipeline_frame* f, uint8_t* y, uint8_t* cb, uint8_t* cr, uint8_t* a)
+{
+    if (!p || !f || !y || !cb || !cr) return fail(LEON_ERR_INVALID, "null argument");
+    if (!f->y || !f->cb || !f->cr) return fail(LEON_ERR_INVALID, "the frame has no planes (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_YCBCR)");
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    const size_t fw = (size_t)p->info.frame_width, fh = (size_t)p->info.frame_height;
+    const size_t cw = (size_t)p->info.chroma_width, chh = (size_t)p->info.chroma_height;
+    const size_t ls = p->planes_geom.luma_stride, cs = p->planes_geom.chroma_stride;
+    HIP_TRY(hipMemcpy2D(y, fw, f->y, ls, fw, fh, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(cb, cw, f->cb, cs, cw, chh, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(cr, cw, f->cr, cs, cw, chh, hipMemcpyDeviceToHost));
+    if (a && f->a) HIP_TRY(hipMemcpy2D(a, fw, f->a, ls, fw, fh, hipMemcpyDeviceToHost));
     return LEON_OK;
 }
 
@@ -1465,6 +1531,7 @@ void leon_pipeline_destroy(leon_pipeline* p)
     for (hipStream_t vs : p->vlc_stream)
         if (vs) hipStreamDestroy(vs);
     if (p->d_rgba) big_free(p->d_rgba);
+    if (p->d_planes) big_free(p->d_planes);
     if (p->copy_stream) hipStreamDestroy(p->copy_stream);
     if (p->dec) leon_destroy(p->dec);
     delete p;

@@ -20,6 +20,9 @@
  *                                  never arrive, 'seeked' (frame) comes with the first frame of the new one, and
  *                                  after 'ended' a seek starts a new run with its own 'ended'
  *   p.readFrame(window, index) -> Uint8Array RGBA (copies to the host: tests, thumbnails)
+ *   p.readPlanes(window, index) -> {y, cb, cr[, a]} packed Uint8Arrays: the frame's YCbCr 4:2:0 planes, with
+ *                                  opts.output 'ycbcr' (no RGBA at all) or 'both' -- the reference's frame payload
+ *                                  {ybr: [Y, Cb, Cr]} (decoders/jsv.js:600, :673); default 'rgba'
  *   p.releaseWindow(window); p.stats(); p.destroy();
  */
 const path = require('path');
@@ -33,7 +36,13 @@ class LeonPipeline extends EventEmitter {
     if (!Buffer.isBuffer(stream)) stream = Buffer.from(stream.buffer, stream.byteOffset, stream.byteLength);
     this.autoRelease = opts.autoRelease !== false;
     this.ended = false;
-    this._p = addon.createPipeline(stream, opts, (w, frames, status) => this._deliver(w, frames, status));
+    const outputs = { rgba: 1, ycbcr: 2, both: 3 };
+    let output = opts.output === undefined ? 0 : opts.output;
+    if (typeof output === 'string') {
+      if (!(output in outputs)) throw new TypeError("output: 'rgba', 'ycbcr' or 'both'");
+      output = outputs[output];
+    }
+    this._p = addon.createPipeline(stream, Object.assign({}, opts, { output }), (w, frames, status) => this._deliver(w, frames, status));
   }
 
   _deliver(window, frames, status) {
@@ -69,6 +78,7 @@ class LeonPipeline extends EventEmitter {
     return first;
   }
   readFrame(window, index) { return this._p.readFrame(window, index); }
+  readPlanes(window, index) { return this._p.readPlanes(window, index); }
   releaseWindow(window) { this._p.releaseWindow(window); }
   stats() { return this._p.stats(); }
   destroy() { if (this._p) { this._p.destroy(); this._p = null; } }

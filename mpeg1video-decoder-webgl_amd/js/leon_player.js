@@ -34,7 +34,8 @@ class LeonPlayer extends EventEmitter {
   /*
    * opts.backend   the N-API addon module (required to decode pixels; null = bitstream only)
    * opts.realtime  true: one frame per frame duration on a timer (default); false: as fast as possible
-   * opts.render    (rgba: Uint8Array, frame) => void, called for every displayed frame when a backend is present
+   * opts.render    (rgba: Uint8Array, frame) => void, called for every displayed frame when a backend is present;
+   *                in pipeline mode with opts.output = 'ycbcr': ({ybr: [Y, Cb, Cr], ts, width, height}, frame) instead
    * opts.nativeParser  true: parse with libleon_vlc on worker threads and hand pictures over as sparse
    *                    group lists (native_decoder.js) instead of the JavaScript bitstream layer
    * opts.pipeline      true: the native pipeline does everything below this class (needs frame width % 8 == 0);
@@ -124,7 +125,8 @@ class LeonPlayer extends EventEmitter {
     const p = this._pipe = new LeonPipeline(Buffer.from(this._bytes.buffer, this._bytes.byteOffset, this._bytes.byteLength),
       { backend: this.opts.backend, parserThreads: this.opts.parserThreads, gopsPerWindow: 1, windowsInFlight: 2, autoRelease: false, startSeconds,
         gpuParser: this.opts.gpuParser === undefined ? 0 : (this.opts.gpuParser ? 1 : -1),       // opts.gpuParser: the slice layer on the GPU (include/leon_pipeline.h)
-        displayFlavour: this.opts.displayFlavour | 0 });      // 1: the fp32 arithmetic of the page's renderFrameGL (player/parts/end.js:77-156)
+        displayFlavour: this.opts.displayFlavour | 0,      // 1: the fp32 arithmetic of the page's renderFrameGL (player/parts/end.js:77-156)
+        output: this.opts.output === 'ycbcr' ? 'ycbcr' : 'rgba' });
     const s = p.stats();
     this.videoWidth = s.frameWidth; this.videoHeight = s.frameHeight; this.frameDuration = 1000 / (s.pictureRate || 25);
     if (s.duration) this.duration = s.duration;
@@ -222,8 +224,17 @@ class LeonPlayer extends EventEmitter {
     }
     if (f.ts) this._currentTime = f.ts / 1000; else this._currentTime += (this.frameDuration || 40) / 1000;
     if (this._pipe) {
-      // = renderFrameGL: the frame is RGBA in device memory already; a renderer gets a host copy
-      if (this.opts.render) this.opts.render(this._pipe.readFrame(f.window, f.index), f);
+      // = renderFrameGL: the frame is RGBA in device memory already; a renderer gets a host copy.  opts.output = 'ycbcr': the
+      // planes instead (1.5 bytes per pixel), shaped like the reference decoder's frame payload {ybr: [Y, Cb, Cr], ts}
+      // (decoders/jsv.js:600, :673) for a host that converts them itself
+      if (this.opts.render) {
+        if (this.opts.output === 'ycbcr') {
+          const pl = this._pipe.readPlanes(f.window, f.index);
+          this.opts.render({ ybr: pl.a ? [pl.y, pl.cb, pl.cr, pl.a] : [pl.y, pl.cb, pl.cr], ts: f.ts, width: this.videoWidth, height: this.videoHeight }, f);
+        } else {
+          this.opts.render(this._pipe.readFrame(f.window, f.index), f);
+        }
+      }
       const left = this._windowLeft.get(f.window) - 1;
       if (left > 0) this._windowLeft.set(f.window, left);
       else { this._windowLeft.delete(f.window); this._pipe.releaseWindow(f.window); }     // = texture.inuse = false for the GOP

@@ -34,8 +34,23 @@ ABI_VERSION = 3        # LEON_ABI_VERSION of include/leon.h
 PIPELINE_SYMBOLS = [
     "leon_pipeline_create", "leon_pipeline_create_partial", "leon_pipeline_feed", "leon_pipeline_get_info", "leon_pipeline_release_window", "leon_pipeline_wait",
     "leon_pipeline_get_stats", "leon_pipeline_read_frame", "leon_pipeline_error", "leon_pipeline_destroy", "leon_pipeline_seek",
+    "leon_pipeline_read_frame_planes",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
+PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
+PIPELINE_OUTPUTS = {"rgba": PIPELINE_OUTPUT_RGBA, "ycbcr": PIPELINE_OUTPUT_YCBCR, "both": PIPELINE_OUTPUT_RGBA | PIPELINE_OUTPUT_YCBCR}
+
+
+def planes_layout(frame_width, frame_height, alpha=False):
+    """the device layout of a frame's planes (include/leon_pipeline.h, leon_pipeline_config.output): rows padded to 64 bytes,
+    planes on 256-byte boundaries, [Y | Cb | Cr (| A)].  Offsets are from the Y pointer; `bytes` is one frame's record."""
+    up = lambda v, a: (v + a - 1) // a * a
+    cw, ch = (frame_width + 1) // 2, (frame_height + 1) // 2
+    ls, cs = up(frame_width, 64), up(cw, 64)
+    yb, cb = up(ls * frame_height, 256), up(cs * ch, 256)
+    return {"luma_stride": ls, "chroma_stride": cs, "chroma_width": cw, "chroma_height": ch,
+            "cb_offset": yb, "cr_offset": yb + cb, "a_offset": yb + 2 * cb,
+            "bytes": yb + 2 * cb + (up(ls * frame_height, 256) if alpha else 0)}
 
 
 class LeonError(RuntimeError):
@@ -88,19 +103,20 @@ class PipelineConfig(C.Structure):
     _fields_ = [("device_id", C.c_int32), ("parser_threads", C.c_int32), ("gops_per_window", C.c_int32),
                 ("windows_in_flight", C.c_int32), ("max_gop_pictures", C.c_int32), ("loop", C.c_int32),
                 ("shard_index", C.c_int32), ("shard_count", C.c_int32), ("start_seconds", C.c_double),
-                ("gpu_parser", C.c_int32), ("display_flavour", C.c_int32)]
+                ("gpu_parser", C.c_int32), ("display_flavour", C.c_int32), ("output", C.c_int32)]
 
 
 class PipelineFrame(C.Structure):
     _fields_ = [("gop", C.c_uint64), ("display_index", C.c_int32), ("type", C.c_int32), ("ts_ms", C.c_double),
-                ("rgba", C.c_void_p)]
+                ("rgba", C.c_void_p), ("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("a", C.c_void_p)]
 
 
 class PipelineInfo(C.Structure):
     _fields_ = [("coded_width", C.c_int32), ("coded_height", C.c_int32), ("frame_width", C.c_int32), ("frame_height", C.c_int32),
                 ("picture_rate", C.c_double), ("duration", C.c_double), ("gops", C.c_uint32), ("shard_gops", C.c_uint32),
                 ("first_gop", C.c_uint32), ("parser_threads", C.c_int32), ("gops_per_window", C.c_int32),
-                ("gpu_parser", C.c_int32), ("display_flavour", C.c_int32)]
+                ("gpu_parser", C.c_int32), ("display_flavour", C.c_int32), ("output", C.c_int32),
+                ("chroma_width", C.c_int32), ("chroma_height", C.c_int32), ("luma_stride", C.c_int32), ("chroma_stride", C.c_int32)]
 
 
 class PipelineStats(C.Structure):
@@ -176,6 +192,7 @@ def load():
     lib.leon_pipeline_wait.argtypes = [C.c_void_p]
     lib.leon_pipeline_get_stats.argtypes = [C.c_void_p, C.POINTER(PipelineStats)]
     lib.leon_pipeline_read_frame.argtypes = [C.c_void_p, C.POINTER(PipelineFrame), C.c_void_p]
+    lib.leon_pipeline_read_frame_planes.argtypes = [C.c_void_p, C.POINTER(PipelineFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -427,7 +444,7 @@ class _Frames:
             raise IndexError(i)
         f = self._f[i]
         return {"gop": int(f.gop), "display_index": f.display_index, "type": f.type, "ts_ms": f.ts_ms, "rgba": f.rgba,
-                "_i": i, "_frames": self._f, "_pipe": self._pipe}
+                "y": f.y, "cb": f.cb, "cr": f.cr, "a": f.a, "_i": i, "_frames": self._f, "_pipe": self._pipe}
 
     def __iter__(self):
         return (self[i] for i in range(self._n))
@@ -437,11 +454,17 @@ class Pipeline:
     """leon_pipeline_* (include/leon_pipeline.h): stream bytes in, RGBA frames in device memory out.
     on_window(window_id, frames) runs on the pipeline's notify thread with a list of dicts
     (gop, display_index, type, ts_ms, rgba = device address); unless it returns False the window is
-    released right after.  read_frame(frame) works until the frame's window is released."""
+    released right after.  read_frame(frame) works until the frame's window is released.
+    output="ycbcr" / "both": the frames carry their YCbCr 4:2:0 planes too (y, cb, cr, a = device addresses, a for yuva
+    streams only; rgba is None with "ycbcr"): read_planes(frame) copies them to the host, plane_views(frame) wraps them."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
-                 loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0):
+                 loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
+                 output="rgba"):
         self.lib = load()
+        self.device_id = device_id
+        # a name of PIPELINE_OUTPUTS, or the raw bit set (anything the library does not know is refused by create)
+        out_bits = PIPELINE_OUTPUTS[output] if isinstance(output, str) else int(output)
         self._data = (C.c_uint8 * len(data)).from_buffer_copy(data)      # must outlive the pipeline
         self._on_window = on_window
         self.windows = 0
@@ -484,7 +507,8 @@ class Pipeline:
         self._cb = PIPELINE_CB(_cb)
         self._ready = ready
         cfg = PipelineConfig(device_id, parser_threads, gops_per_window, windows_in_flight, max_gop_pictures, loop,
-                             shard_index, shard_count, float(start_seconds), 0 if gpu_parser is None else (1 if gpu_parser else -1), int(display_flavour))      # None: the library's default (the GPU)
+                             shard_index, shard_count, float(start_seconds), 0 if gpu_parser is None else (1 if gpu_parser else -1), int(display_flavour),      # None: the library's default (the GPU)
+                             out_bits)
         h = C.c_void_p()
         self.h = None
         # valid_bytes: the stream is still arriving (leon_pipeline_create_partial); feed() reports progress
@@ -504,6 +528,29 @@ class Pipeline:
         out = np.empty((self.info.frame_height, self.info.frame_width, 4), dtype=np.uint8)
         _chk(self.lib.leon_pipeline_read_frame(self.h, C.byref(frame["_frames"][frame["_i"]]), out.ctypes.data))
         return out
+
+    def read_planes(self, frame):
+        """the frame's planes as packed host arrays: (y, cb, cr), and a for a yuva stream"""
+        i = self.info
+        y = np.empty((i.frame_height, i.frame_width), dtype=np.uint8)
+        cb = np.empty((i.chroma_height, i.chroma_width), dtype=np.uint8)
+        cr = np.empty_like(cb)
+        a = np.empty_like(y) if frame["a"] else None
+        _chk(self.lib.leon_pipeline_read_frame_planes(self.h, C.byref(frame["_frames"][frame["_i"]]), y.ctypes.data, cb.ctypes.data,
+                                                      cr.ctypes.data, None if a is None else a.ctypes.data))
+        return (y, cb, cr) if a is None else (y, cb, cr, a)
+
+    def plane_views(self, frame, device_id=None):
+        """the frame's planes where they lie, as torch uint8 tensors (height x width, row stride = the plane's padded stride),
+        without copying: valid until the frame's window is released"""
+        i = self.info
+        dev = self.device_id if device_id is None else device_id
+        views = [plane_view(frame["y"], i.frame_height, i.frame_width, i.luma_stride, dev),
+                 plane_view(frame["cb"], i.chroma_height, i.chroma_width, i.chroma_stride, dev),
+                 plane_view(frame["cr"], i.chroma_height, i.chroma_width, i.chroma_stride, dev)]
+        if frame["a"]:
+            views.append(plane_view(frame["a"], i.frame_height, i.frame_width, i.luma_stride, dev))
+        return tuple(views)
 
     def feed(self, valid_bytes, chunk=None, offset=None):
         """more of the stream has arrived: optionally copy `chunk` to `offset` of the pipeline's buffer first"""
@@ -577,6 +624,21 @@ def device_view(ptr, nbytes, device_id=0):
         pass
     v = _View()
     v.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+    return torch.as_tensor(v, device="cuda:%d" % device_id)
+
+
+def plane_view(ptr, height, width, stride, device_id=0):
+    """a height x width uint8 plane with rows `stride` bytes apart at device address `ptr`, as a torch tensor without copying"""
+    import torch
+
+    if not ptr:
+        raise ValueError("the frame has no such plane (Pipeline output)")
+
+    class _View:
+        pass
+    v = _View()
+    v.__cuda_array_interface__ = {"shape": (int(height), int(width)), "typestr": "|u1", "data": (int(ptr), False),
+                                  "strides": (int(stride), 1), "version": 2}
     return torch.as_tensor(v, device="cuda:%d" % device_id)
 
 

@@ -366,6 +366,7 @@ napi_value Create(napi_env env, napi_callback_info info)
 //   one Node process per GPU is the JavaScript host's form of the frame-parallel partition.
 //   frames: [{gop, displayIndex, type, ts}] in display order; window < 0 = 'ended' (decoders/jsv.js:437).
 //   p.readFrame(window, i) -> Uint8Array (copies one frame to the host: tests, thumbnails),
+//   p.readPlanes(window, i) -> {y, cb, cr[, a]} packed Uint8Arrays (options.output 2 / 3: the frames' YCbCr planes),
 //   p.releaseWindow(window), p.stats(), p.info(), p.destroy().
 //   p.seek(seconds, exact) -> firstWindow (leon_pipeline_seek): windows the notify thread queued for the old position and
 //   its 'ended' reach no JavaScript callback -- they are released here; a seek after 'ended' starts a new run.
@@ -520,6 +521,44 @@ napi_value PipeReadFrame(napi_env env, napi_callback_info info)
     return rc == LEON_OK ? ta : throw_leon(env, rc);
 }
 
+// p.readPlanes(window, i) -> {y, cb, cr[, a]}: packed Uint8Arrays of one frame's YCbCr planes (output 'ycbcr' / 'both')
+napi_value PipeReadPlanes(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    int32_t i = -1;
+    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "readPlanes(window, index)");
+        return nullptr;
+    }
+    leon_pipeline_frame f{};
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        auto it = h->out.find(w);
+        if (it == h->out.end() || i < 0 || (size_t)i >= it->second.size()) {
+            napi_throw_range_error(env, nullptr, "readPlanes: no such frame (window released?)");
+            return nullptr;
+        }
+        f = it->second[(size_t)i];
+    }
+    const size_t ybytes = (size_t)h->info.frame_width * h->info.frame_height, cbytes = (size_t)h->info.chroma_width * h->info.chroma_height;
+    const char* names[4] = {"y", "cb", "cr", "a"};
+    const size_t sizes[4] = {ybytes, cbytes, cbytes, ybytes};
+    void* data[4] = {nullptr, nullptr, nullptr, nullptr};
+    napi_value o, ab, ta;
+    NAPI_OK(napi_create_object(env, &o));
+    for (int k = 0; k < (f.a ? 4 : 3); k++) {
+        NAPI_OK(napi_create_arraybuffer(env, sizes[k], &data[k], &ab));
+        NAPI_OK(napi_create_typedarray(env, napi_uint8_array, sizes[k], ab, 0, &ta));
+        NAPI_OK(napi_set_named_property(env, o, names[k], ta));
+    }
+    int rc = leon_pipeline_read_frame_planes(h->p, &f, (uint8_t*)data[0], (uint8_t*)data[1], (uint8_t*)data[2], (uint8_t*)data[3]);
+    return rc == LEON_OK ? o : throw_leon(env, rc);
+}
+
 napi_value PipeStats(napi_env env, napi_callback_info info)
 {
     size_t argc = 0;
@@ -535,7 +574,8 @@ napi_value PipeStats(napi_env env, napi_callback_info info)
         {"frameWidth", (double)h->info.frame_width}, {"frameHeight", (double)h->info.frame_height},
         {"codedWidth", (double)h->info.coded_width}, {"codedHeight", (double)h->info.coded_height},
         {"pictureRate", h->info.picture_rate}, {"keyMapGops", (double)h->info.gops}, {"shardGops", (double)h->info.shard_gops}, {"firstGop", (double)h->info.first_gop}, {"duration", h->info.duration}, {"parserThreads", (double)h->info.parser_threads},
-        {"gopsPerWindow", (double)h->info.gops_per_window}};
+        {"gopsPerWindow", (double)h->info.gops_per_window}, {"output", (double)h->info.output},
+        {"chromaWidth", (double)h->info.chroma_width}, {"chromaHeight", (double)h->info.chroma_height}};
     for (auto& e : kv) {
         NAPI_OK(napi_create_double(env, e.val, &v));
         NAPI_OK(napi_set_named_property(env, o, e.k, v));
@@ -619,7 +659,8 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
               get_i32(env, argv[1], "gopsPerWindow", &cfg.gops_per_window, 0) && get_i32(env, argv[1], "windowsInFlight", &cfg.windows_in_flight, 0) &&
               get_i32(env, argv[1], "maxGopPictures", &cfg.max_gop_pictures, 0) && get_i32(env, argv[1], "loop", &cfg.loop, 0) &&
               get_i32(env, argv[1], "shardIndex", &cfg.shard_index, 0) && get_i32(env, argv[1], "shardCount", &cfg.shard_count, 0) &&
-              get_i32(env, argv[1], "gpuParser", &cfg.gpu_parser, 0) && get_i32(env, argv[1], "displayFlavour", &cfg.display_flavour, 0);
+              get_i32(env, argv[1], "gpuParser", &cfg.gpu_parser, 0) && get_i32(env, argv[1], "displayFlavour", &cfg.display_flavour, 0) &&
+              get_i32(env, argv[1], "output", &cfg.output, 0);      // LEON_PIPELINE_OUTPUT_* bits (js/leon_pipeline.js maps the names)
     {   // startSeconds: begin at the key-map entry at or before this time
         napi_value v;
         bool has = false;
@@ -678,7 +719,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));

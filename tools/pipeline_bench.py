@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--window", type=int, default=32)
     ap.add_argument("--inflight", type=int, default=2)
     ap.add_argument("--gpu-parser", action="store_true", help="decode the slice layer on the GPU (leon_pipeline_config.gpu_parser)")
+    ap.add_argument("--output", choices=["rgba", "ycbcr", "both"], default="rgba",
+                    help="what the frames carry (leon_pipeline_config.output): RGBA, the YCbCr planes, or both")
     ap.add_argument("--varied", action="store_true", help="the 16-GOP stream with 16 different contents (tools/stream_1080p.py) instead of --gops GOPs")
     a = ap.parse_args()
     cached = os.path.join(ROOT, "tools", "probe", "stream_1080p_%dgop.bin" % a.gops)
@@ -51,7 +53,8 @@ def main():
         return f.value if hip.hipMemGetInfo(ctypes.byref(f), ctypes.byref(t)) == 0 else None
     free0 = free_device_bytes()
     t0 = time.perf_counter()
-    pipe = L.Pipeline(data, parser_threads=a.threads, gops_per_window=a.window, windows_in_flight=a.inflight, loop=a.loop, gpu_parser=a.gpu_parser)
+    pipe = L.Pipeline(data, parser_threads=a.threads, gops_per_window=a.window, windows_in_flight=a.inflight, loop=a.loop, gpu_parser=a.gpu_parser,
+                      output=a.output)
     free1 = free_device_bytes()
     pipe.wait()
     wall = time.perf_counter() - t0
@@ -59,8 +62,9 @@ def main():
     pipe.close()
     mbs = (pipe.info.coded_width // 16) * (pipe.info.coded_height // 16)
     print(json.dumps({
-        "metric": "end-to-end %dx%d pictures/s (parse + PCIe + reconstruct + RGBA in device memory), native pipeline, one GPU"
-                  % (pipe.info.frame_width, pipe.info.frame_height),
+        "metric": "end-to-end %dx%d pictures/s (parse + PCIe + reconstruct + %s in device memory), native pipeline, one GPU"
+                  % (pipe.info.frame_width, pipe.info.frame_height, {"rgba": "RGBA", "ycbcr": "YCbCr planes", "both": "RGBA + YCbCr planes"}[a.output]),
+        "output": a.output,
         "value": s["pictures"] / s["seconds"], "macroblocks_per_s": s["pictures"] * mbs / s["seconds"],
         "pictures": s["pictures"], "seconds": s["seconds"], "wall_seconds_incl_setup": wall, "windows": s["windows"],
         "slice_layer": "GPU (csrc/leon_vlc_gpu.h)" if a.gpu_parser else "host threads (libleon_vlc.so)",
