@@ -97,6 +97,21 @@ FrameOut planes_layout(int fw, int fh, size_t* record_bytes)
     return fo;
 }
 
+inline size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
+
+// A picture's maps as every buffer that holds them lays them out (submit_picture_any's staging, the pipeline's arenas,
+// the GPU parser's VlcGeom): [qscale | intra | repadd | mb_dir | mv_fwd | mv_bwd], a byte per macroblock (mpad) or four
+// (vpad), each padded to 256 bytes; beside them the group offsets (gpad) and the entry list (entries_pad).  off() is a
+// map's offset with every map present; the host parser's arenas leave a picture's absent maps out.
+struct MapLayout {
+    enum { QSCALE, INTRA, REPADD, MB_DIR, MV_FWD, MV_BWD };
+    size_t mbs, mpad, vpad, gpad;
+    size_t off(int map) const { return map <= MV_FWD ? map * mpad : 4 * mpad + vpad; }
+    size_t bytes() const { return 4 * mpad + 2 * vpad; }      // the six
+    static size_t entries_pad(size_t n_entries) { return pad256(n_entries * 4 + 4); }
+};
+MapLayout map_layout(size_t mbs, size_t n_groups) { return MapLayout{mbs, pad256(mbs), pad256(mbs * 4), pad256((n_groups + 1) * 4)}; }
+
 // dense or sparse picture as the internals see it
 struct AnyPic {
     leon_picture p{};            // coef_* unused when sparse
@@ -786,9 +801,10 @@ int leon_create(const leon_config* cfg, leon_decoder** out)
     if (hipMalloc(&d->d_slot_ids, sizeof(int32_t) * leon_decoder::kSlotIdRing) != hipSuccess) return bail("slot id ring");
     if (hipHostMalloc((void**)&d->h_slot_ids, sizeof(int32_t) * leon_decoder::kSlotIdRing) != hipSuccess) return bail("pinned slot ids");
     // staging for host-memory pictures: coef planes (2 bytes/sample) + 5 byte maps + 2 vector maps
-    size_t mbs = (size_t)G.mbw * G.mbh;
+    const size_t n_groups = (size_t)n_groups_of(d->geom);
     // coefficients: dense planes (2 B each) or, at worst, one 4-byte entry each plus the group offsets
-    d->stage_bytes = d->plane_bytes * 4 + (G.alpha ? (size_t)G.cw * G.ch * 2 : 0) + ((size_t)n_groups_of(d->geom) + 1) * 4 + 1024 + 4 * ((mbs + 255) / 256 * 256) + 2 * ((mbs * 4 + 255) / 256 * 256) + 1024;
+    d->stage_bytes = d->plane_bytes * 4 + (G.alpha ? (size_t)G.cw * G.ch * 2 : 0) + (n_groups + 1) * 4 + 1024 +
+                     map_layout((size_t)G.mbw * G.mbh, n_groups).bytes() + 1024;
     if (hipStreamSynchronize(d->stream) != hipSuccess) return bail("create sync");
     *out = d;
     return LEON_OK;
@@ -937,8 +953,8 @@ int submit_picture_any(leon_decoder* d, const AnyPic& pic)
         HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     }
     if (s.busy) HIP_TRY(hipEventSynchronize(s.done));
-    size_t ny = (size_t)G.cw * G.ch, nc = ny >> 2, mbs = (size_t)G.mbw * G.mbh;
-    size_t mpad = (mbs + 255) / 256 * 256, vpad = (mbs * 4 + 255) / 256 * 256;
+    const size_t ny = (size_t)G.cw * G.ch, nc = ny >> 2, mbs = (size_t)G.mbw * G.mbh;
+    const MapLayout M = map_layout(mbs, n_groups);
     char* p = s.base;
     AnyPic dp = pic;
     // The pieces are gathered into the pinned mirror with plain memcpy and cross PCIe in one
@@ -950,11 +966,10 @@ int submit_picture_any(leon_decoder* d, const AnyPic& pic)
         if (src && bytes) memcpy(s.host + (at - s.base), src, bytes);
         return src ? at : nullptr;
     };
-    auto pad256 = [](size_t v) { return (v + 255) / 256 * 256; };
     if (pic.sparse) {
-        dp.grp_off = (const uint32_t*)put(pic.grp_off, (n_groups + 1) * 4, pad256((n_groups + 1) * 4));
+        dp.grp_off = (const uint32_t*)put(pic.grp_off, (n_groups + 1) * 4, M.gpad);
         dp.entries = (const uint32_t*)put(pic.entries ? (const void*)pic.entries : (const void*)pic.grp_off,
-                                          (size_t)pic.n_entries * 4, pad256((size_t)pic.n_entries * 4 + 4));
+                                          (size_t)pic.n_entries * 4, MapLayout::entries_pad(pic.n_entries));
     } else {
         dp.p.coef_y = (const int16_t*)put(pic.p.coef_y, ny * 2, ny * 2);
         dp.p.coef_cb = (const int16_t*)put(pic.p.coef_cb, nc * 2, nc * 2);
@@ -962,12 +977,12 @@ int submit_picture_any(leon_decoder* d, const AnyPic& pic)
         dp.p.coef_a = (const int16_t*)put(G.alpha ? pic.p.coef_a : nullptr, ny * 2, G.alpha ? ny * 2 : 0);
     }
     const int type = pic.p.type;
-    dp.p.qscale = (const uint8_t*)put(pic.p.qscale, mbs, mpad);
-    dp.p.intra = (const uint8_t*)put(pic.p.intra, mbs, mpad);
-    dp.p.repadd = (const uint8_t*)put(type != LEON_PIC_I ? pic.p.repadd : nullptr, mbs, mpad);
-    dp.p.mb_dir = (const uint8_t*)put(type == LEON_PIC_B ? pic.p.mb_dir : nullptr, mbs, mpad);
-    dp.p.mv_fwd = (const int16_t*)put(type != LEON_PIC_I ? pic.p.mv_fwd : nullptr, mbs * 4, vpad);
-    dp.p.mv_bwd = (const int16_t*)put(type == LEON_PIC_B ? pic.p.mv_bwd : nullptr, mbs * 4, vpad);
+    dp.p.qscale = (const uint8_t*)put(pic.p.qscale, mbs, M.mpad);
+    dp.p.intra = (const uint8_t*)put(pic.p.intra, mbs, M.mpad);
+    dp.p.repadd = (const uint8_t*)put(type != LEON_PIC_I ? pic.p.repadd : nullptr, mbs, M.mpad);
+    dp.p.mb_dir = (const uint8_t*)put(type == LEON_PIC_B ? pic.p.mb_dir : nullptr, mbs, M.mpad);
+    dp.p.mv_fwd = (const int16_t*)put(type != LEON_PIC_I ? pic.p.mv_fwd : nullptr, mbs * 4, M.vpad);
+    dp.p.mv_bwd = (const int16_t*)put(type == LEON_PIC_B ? pic.p.mv_bwd : nullptr, mbs * 4, M.vpad);
     HIP_TRY(hipMemcpyAsync(s.base, s.host, (size_t)(p - s.base), hipMemcpyHostToDevice, d->stream));
     int at = 0;
     rc = reserve_descs(d, 1, at);

@@ -86,7 +86,6 @@ struct VlcRing {                 // gpu_parser: per ring entry, the window's sli
 };
 
 constexpr size_t kNone = (size_t)-1;
-inline size_t pad256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -111,6 +110,7 @@ struct leon_pipeline {
     size_t frame_bytes = 0;      // RGBA bytes of a frame
     int output = LEON_PIPELINE_OUTPUT_RGBA;           // leon_pipeline_config.output, 0 resolved
     FrameOut planes_geom{};      // the frames' plane layout (planes_layout)
+    MapLayout maps{};            // a picture's maps in the arenas (map_layout)
     size_t planes_bytes = 0;     // one frame's planes record [Y | Cb | Cr (| A)], a multiple of 256
 
     leon_decoder* dec = nullptr;
@@ -154,7 +154,7 @@ struct leon_pipeline {
 
     // stats
     Clock::time_point t0;
-    std::atomic<uint64_t> st_pictures{0}, st_gops{0}, st_entries{0}, st_parse_ns{0}, st_upload{0}, st_submit_ns{0}, st_submit_wait_ns{0};
+    std::atomic<uint64_t> st_pictures{0}, st_gops{0}, st_entries{0}, st_parse_ns{0}, st_upload{0}, st_submit_ns{0};
     double st_seconds = 0;
 };
 
@@ -173,9 +173,8 @@ void pipe_fail(leon_pipeline* p, int code, const std::string& msg)
 
 // host_need bytes of pinned memory and dev_need bytes of its device twin (equal for a GOP parsed on the host: the
 // arena is copied as it is; the GPU parser uploads the stream bytes only and keeps everything else on the device)
-bool arena_reserve(leon_pipeline* p, Arena* a, size_t host_need, size_t dev_need)
+bool arena_reserve(Arena* a, size_t host_need, size_t dev_need)
 {
-    (void)p;
     if (host_need > a->host_cap) {
         const size_t cap = std::max(host_need + host_need / 2, (size_t)4 << 20);
         char* h = nullptr;
@@ -197,8 +196,6 @@ bool arena_reserve(leon_pipeline* p, Arena* a, size_t host_need, size_t dev_need
     }
     return true;
 }
-
-inline Arena* a_of(GopJob* job) { return job->arena; }
 
 // The pipeline takes the picture size from the stream's FIRST sequence header (leon_create).  Every key-map entry starts
 // with a sequence header of its own and the reference re-initialises at each (decoders/jsv.js:491-561): a shard whose
@@ -228,6 +225,28 @@ int sequence_in_force(leon_pipeline* p, GopJob* job, leon_vlc_stream* st, uint64
     return (int)job->qms.size() - 1;
 }
 
+// gpu_parser: the entry list a picture reserves for a slice of `bytes` stream bytes.  An entry is a coefficient symbol, and n
+// of them in a block take 3 n + 1 bits at least: the shortest code is '11s' (three bits; '1s', two, in first position only),
+// and the end-of-block code (or an intra block's DC size code) another two -- entries <= bits / 3.  (Round 3 reserved a
+// dword per two bits.)  The kernels keep inside the bound whatever the stream says (k_vlc_blocks, and the reconstruction
+// reads the list through a buffer resource of exactly this length).  The bound of a whole GOP shard covers the sum over its
+// slices: each slice has a 4-byte start code of its own outside every slice's bytes, worth ten entries of the bound -- more
+// than the two a slice adds.
+inline size_t vlc_entry_bound(size_t bytes) { return (8 * bytes) / 3 + 2; }
+constexpr size_t kVlcMinEntries = 64;       // the least a picture's entry list reserves
+
+// gpu_parser: what a picture takes of its GOP's arena besides its entry list: the macroblock records (mb_recs), the block
+// records of all its slices (blk_recs: leon_vlc_gpu.h VlcSliceOut, a record per block at most), the maps, the group offsets
+struct VlcPicBytes { size_t mb_recs, blk_recs, total; };
+VlcPicBytes vlc_pic_bytes(const leon_pipeline* p)
+{
+    VlcPicBytes b;
+    b.mb_recs = pad256(p->maps.mbs * leon::kVlcMbRecBytes);
+    b.blk_recs = pad256(p->maps.mbs * (size_t)leon::vlc_blocks_per_mb(p->vinfo.has_alpha == 1) * leon::kVlcRecWords * 4);
+    b.total = b.mb_recs + b.blk_recs + p->maps.bytes() + p->maps.gpad;
+    return b;
+}
+
 // gpu_parser: the host reads the picture layer only (leon_vlc_scan_picture) and lays the GOP's arena out for the
 // device kernels of leon_vlc_gpu.h:
 //   [stream bytes, zero padded]                                            uploaded
@@ -255,47 +274,32 @@ void scan_gop_for_gpu(leon_pipeline* p, GopJob* job, leon_vlc_stream* st, const 
         x.pos.assign(sc.slice_bit_pos, sc.slice_bit_pos + sc.n_slices);
         scans.push_back(std::move(x));
     }
-    if ((int)scans.size() > p->max_pics) {
-        job->status = LEON_ERR_INVALID;
-        job->err = "a GOP has " + std::to_string(scans.size()) + " pictures; raise max_gop_pictures (" + std::to_string(p->max_pics) + ")";
-        return;
-    }
     if (n >= ((size_t)1 << 28)) { job->status = LEON_ERR_INVALID; job->err = "GOP shard too large for the GPU parser"; return; }
-    const size_t mbs = (size_t)p->vinfo.mb_width * p->vinfo.mb_height;
-    const size_t mpad = pad256(mbs), vpad = pad256(mbs * 4), gpad = pad256(((size_t)p->vinfo.n_groups + 1) * 4);
-    const size_t rpad = pad256(mbs * leon::kVlcMbRecBytes);
-    // the block records of a picture: one array for all its slices (leon_vlc_gpu.h VlcSliceOut), a record per block at most
-    const size_t recpad = pad256(mbs * (size_t)leon::vlc_blocks_per_mb(p->vinfo.has_alpha == 1) * leon::kVlcRecWords * 4);
+    const MapLayout& M = p->maps;
+    const VlcPicBytes pb = vlc_pic_bytes(p);
     const size_t max_entries = (size_t)p->vinfo.coded_width * p->vinfo.coded_height * (p->vinfo.has_alpha == 1 ? 5 : 3) / 2;
     const size_t stream_pad = pad256(n + 16);
     // sizes first: the arena may move when it grows
-    const size_t maps_per_pic = 4 * mpad + 2 * vpad;
-    size_t need = stream_pad + scans.size() * (rpad + recpad + maps_per_pic);
+    size_t need = stream_pad;
     std::vector<size_t> ecap(scans.size());
     for (size_t k = 0; k < scans.size(); k++) {
         const Scan& x = scans[k];
         size_t pic_words = 0;
         for (size_t j = 0; j < x.code.size(); j++) {
             const uint64_t begin = x.pos[j] >> 3, end = j + 1 < x.code.size() ? (x.pos[j + 1] >> 3) - 4 : x.s.end_byte;
-            const size_t nb = end > begin ? (size_t)(end - begin) : 0;
-            // An entry is a coefficient symbol, and n of them in a block take 3 n + 1 bits at least: the shortest code is
-            // '11s' (three bits; '1s', two, in first position only), and the end-of-block code (or an intra block's DC size
-            // code) another two -- entries <= bits / 3.  (Round 3 reserved a dword per two bits.)  The kernels keep inside
-            // the bound whatever the stream says (k_vlc_blocks, and the reconstruction reads the list through a buffer
-            // resource of exactly this length).
-            pic_words += (8 * nb) / 3 + 2;
+            pic_words += vlc_entry_bound(end > begin ? (size_t)(end - begin) : 0);
         }
-        ecap[k] = std::min(std::max(pic_words, (size_t)64), max_entries);
-        need += gpad + pad256(ecap[k] * 4 + 4);
+        ecap[k] = std::min(std::max(pic_words, kVlcMinEntries), max_entries);
+        need += pb.total + MapLayout::entries_pad(ecap[k]);
     }
-    if (!arena_reserve(p, a_of(job), stream_pad, need)) { job->status = LEON_ERR_NOMEM; job->err = "staging allocation failed"; return; }
+    if (!arena_reserve(job->arena, stream_pad, need)) { job->status = LEON_ERR_NOMEM; job->err = "staging allocation failed"; return; }
     Arena* a = job->arena;
     memcpy(a->host, bytes, n);
     memset(a->host + n, 0, stream_pad - n);
     job->upload_bytes = stream_pad;
     size_t at = stream_pad;
     job->zero_begin = at;                                // the macroblock records of all its pictures, side by side
-    job->zero_bytes = scans.size() * rpad;
+    job->zero_bytes = scans.size() * pb.mb_recs;
     char* dev = a->dev;
     auto take = [&](size_t bytes_) { const size_t o = at; at += bytes_; return o; };
     for (size_t k = 0; k < scans.size(); k++) {
@@ -309,7 +313,7 @@ void scan_gop_for_gpu(leon_pipeline* p, GopJob* job, leon_vlc_stream* st, const 
         v.type = x.s.type;
         v.full_pel_fwd = x.s.full_pel_fwd; v.fwd_rsize = x.s.fwd_rsize;
         v.full_pel_bwd = x.s.full_pel_bwd; v.bwd_rsize = x.s.bwd_rsize;
-        v.zbase = dev + take(rpad);
+        v.zbase = dev + take(pb.mb_recs);
         job->pics.push_back(m);
         job->vpics.push_back(v);
     }
@@ -317,20 +321,21 @@ void scan_gop_for_gpu(leon_pipeline* p, GopJob* job, leon_vlc_stream* st, const 
         const Scan& x = scans[k];
         PipePic& m = job->pics[k];
         leon::VlcPic& v = job->vpics[k];
-        v.maps = dev + at;                               // [qscale | intra | repadd | mb_dir | mv_fwd | mv_bwd]: VlcGeom's offsets
-        m.qscale = take(mpad); m.intra = take(mpad);
-        const size_t ra = take(mpad), md = take(mpad), mf = take(vpad), mk = take(vpad);
-        m.repadd = x.s.type != LEON_PIC_I ? ra : kNone;
-        m.mb_dir = x.s.type == LEON_PIC_B ? md : kNone;
-        m.mv_fwd = x.s.type != LEON_PIC_I ? mf : kNone;
-        m.mv_bwd = x.s.type == LEON_PIC_B ? mk : kNone;
-        m.grp_off = take(gpad);
-        m.entries = take(pad256(ecap[k] * 4 + 4));
+        const size_t maps = take(M.bytes());             // all six: the kernels write them at VlcGeom's offsets (M's)
+        v.maps = dev + maps;
+        m.qscale = maps + M.off(M.QSCALE);
+        m.intra = maps + M.off(M.INTRA);
+        m.repadd = x.s.type != LEON_PIC_I ? maps + M.off(M.REPADD) : kNone;
+        m.mb_dir = x.s.type == LEON_PIC_B ? maps + M.off(M.MB_DIR) : kNone;
+        m.mv_fwd = x.s.type != LEON_PIC_I ? maps + M.off(M.MV_FWD) : kNone;
+        m.mv_bwd = x.s.type == LEON_PIC_B ? maps + M.off(M.MV_BWD) : kNone;
+        m.grp_off = take(M.gpad);
+        m.entries = take(MapLayout::entries_pad(ecap[k]));
         m.n_entries = (uint32_t)ecap[k];                 // the bound of the device lists (the kernels keep inside it)
         v.grp_off = (uint32_t*)(dev + m.grp_off);
         v.entries = (uint32_t*)(dev + m.entries);
         v.entries_cap = (uint32_t)ecap[k];
-        v.recs = (uint32_t*)(dev + take(recpad));
+        v.recs = (uint32_t*)(dev + take(pb.blk_recs));
         for (size_t j = 0; j < x.code.size(); j++) {
             leon::VlcSlice sl{};
             sl.bytes = (const uint32_t*)dev;
@@ -371,8 +376,6 @@ void parse_gop(leon_pipeline* p, GopJob* job)
         leon_vlc_close(st);
         return;
     }
-    const size_t mbs = (size_t)p->vinfo.mb_width * p->vinfo.mb_height;
-    const size_t mpad = pad256(mbs), vpad = pad256(mbs * 4), gpad = pad256(((size_t)p->vinfo.n_groups + 1) * 4);
     Arena* a = job->arena;
     a->used = 0;
     if (p->gpu_parser) {
@@ -391,9 +394,10 @@ void parse_gop(leon_pipeline* p, GopJob* job)
         }
         if (pic.new_sequence && (qm_now = sequence_in_force(p, job, st, g)) == -2) break;
         if (pic.open_gop) job->open_gop = true;
-        const size_t epad = pad256((size_t)pic.n_entries * 4 + 4);
-        const size_t need = a->used + gpad + epad + 4 * mpad + 2 * vpad;
-        if (!arena_reserve(p, a, need, need)) {
+        const MapLayout& M = p->maps;
+        const size_t epad = MapLayout::entries_pad(pic.n_entries), mbs = M.mbs;
+        const size_t need = a->used + M.gpad + epad + M.bytes();      // (absent maps are left out: no more than this)
+        if (!arena_reserve(a, need, need)) {
             job->status = LEON_ERR_NOMEM;
             job->err = "pinned staging allocation failed";
             break;
@@ -411,23 +415,35 @@ void parse_gop(leon_pipeline* p, GopJob* job)
             a->used += reserve;
             return at;
         };
-        m.grp_off = put(pic.grp_off, ((size_t)pic.n_groups + 1) * 4, gpad);
+        m.grp_off = put(pic.grp_off, ((size_t)pic.n_groups + 1) * 4, M.gpad);
         m.entries = put(pic.entries ? (const void*)pic.entries : (const void*)pic.grp_off, (size_t)pic.n_entries * 4, epad);
-        m.qscale = put(pic.qscale, mbs, mpad);
-        m.intra = put(pic.intra, mbs, mpad);
-        m.repadd = put(pic.type != LEON_PIC_I ? pic.repadd : nullptr, mbs, mpad);
-        m.mb_dir = put(pic.type == LEON_PIC_B ? pic.mb_dir : nullptr, mbs, mpad);
-        m.mv_fwd = put(pic.type != LEON_PIC_I ? pic.mv_fwd : nullptr, mbs * 4, vpad);
-        m.mv_bwd = put(pic.type == LEON_PIC_B ? pic.mv_bwd : nullptr, mbs * 4, vpad);
+        m.qscale = put(pic.qscale, mbs, M.mpad);
+        m.intra = put(pic.intra, mbs, M.mpad);
+        m.repadd = put(pic.type != LEON_PIC_I ? pic.repadd : nullptr, mbs, M.mpad);
+        m.mb_dir = put(pic.type == LEON_PIC_B ? pic.mb_dir : nullptr, mbs, M.mpad);
+        m.mv_fwd = put(pic.type != LEON_PIC_I ? pic.mv_fwd : nullptr, mbs * 4, M.vpad);
+        m.mv_bwd = put(pic.type == LEON_PIC_B ? pic.mv_bwd : nullptr, mbs * 4, M.vpad);
         if (job->pics.empty()) job->gop_ts_ms = pic.ts_ms;
         job->pics.push_back(m);
         p->st_entries += pic.n_entries;
     }
     leon_vlc_close(st);
-    if (job->status == LEON_OK && (int)job->pics.size() > p->max_pics) {
-        job->status = LEON_ERR_INVALID;
-        job->err = "a GOP has " + std::to_string(job->pics.size()) + " pictures; raise max_gop_pictures (" + std::to_string(p->max_pics) + ")";
-    }
+}
+
+// a frame's presentation time: its GOP's time code + its display index at the picture rate (25 when the stream names none)
+double frame_ts_ms(const leon_pipeline* p, const GopJob* job, int display_index)
+{
+    const double rate = p->vinfo.picture_rate > 0 ? p->vinfo.picture_rate : 25.0;
+    return job->gop_ts_ms + 1000.0 * (double)display_index / rate;
+}
+
+// a frame's RGBA and planes record in the output rings (null: that output is off): ring entry, lane (GOP of the window),
+// display index
+struct FrameAddr { uint8_t* rgba; uint8_t* planes; };
+FrameAddr frame_addr(const leon_pipeline* p, int ring, size_t lane, size_t k)
+{
+    const size_t i = ((size_t)ring * p->W + lane) * p->max_pics + k;
+    return {p->d_rgba ? p->d_rgba + i * p->frame_bytes : nullptr, p->d_planes ? p->d_planes + i * p->planes_bytes : nullptr};
 }
 
 // LEON_PIPELINE_SEEK_EXACT: the first GOP of the run delivers its frames from the one on screen at t_ms on (the largest
@@ -436,10 +452,9 @@ void parse_gop(leon_pipeline* p, GopJob* job)
 // converted to RGBA and not delivered.
 void trim_to_target(leon_pipeline* p, GopJob* job, double t_ms)
 {
-    const double rate = p->vinfo.picture_rate > 0 ? p->vinfo.picture_rate : 25.0;
-    int target = -1;                 // same arithmetic as the frames' ts_ms (submit_window)
+    int target = -1;
     for (const PipePic& m : job->pics)
-        if (job->gop_ts_ms + 1000.0 * (double)m.tref / rate <= t_ms) target = std::max(target, m.tref);
+        if (frame_ts_ms(p, job, m.tref) <= t_ms) target = std::max(target, m.tref);
     if (target < 0) return;
     std::vector<PipePic> pics;
     std::vector<leon::VlcPic> vpics;
@@ -511,6 +526,10 @@ void parser_main(leon_pipeline* p)
         }
         const auto t = Clock::now();
         if (job->status == LEON_OK) parse_gop(p, job);
+        if (job->status == LEON_OK && (int)job->pics.size() > p->max_pics) {        // (either parser)
+            job->status = LEON_ERR_INVALID;
+            job->err = "a GOP has " + std::to_string(job->pics.size()) + " pictures; raise max_gop_pictures (" + std::to_string(p->max_pics) + ")";
+        }
         if (job->status == LEON_OK && g == 0 && run->exact_ms >= 0) trim_to_target(p, job, run->exact_ms);
         p->st_parse_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t).count();
         {
@@ -629,38 +648,44 @@ void capture_file(const std::string& path, const void* dev, size_t bytes)
     if (FILE* f = fopen(path.c_str(), "wb")) { fwrite(h.data(), 1, bytes, f); fclose(f); }
 }
 
-// the pictures of one window as launches: per GOP the anchors rotate through three slots; a picture's
-// level is one more than the deepest picture it predicts from, and a level is one batch
-int submit_window(leon_pipeline* p, PipeWindow* w)
+// a picture of a level: the lane of its GOP in the window, the slots it writes and predicts from
+struct LevelPic { size_t lane; const PipePic* pic; int fwd, bwd, out; };
+
+// after a level, the decoder's stream idle: the planes its pictures wrote and predicted from, a line each in the index
+// (the first level begins the index with the geometry)
+int capture_level(const leon_pipeline* p, const PipeWindow* w, const std::string& dir, const std::vector<LevelPic>& lvl, size_t lvl_no)
 {
-    leon_decoder* d = p->dec;
-    const size_t lanes = w->jobs.size();
-    struct Item { size_t lane; const PipePic* pic; int fwd, bwd, out; };
-    std::vector<std::vector<Item>> levels;
-    const bool want_rgba = (p->output & LEON_PIPELINE_OUTPUT_RGBA) != 0, want_planes = (p->output & LEON_PIPELINE_OUTPUT_YCBCR) != 0;
-    uint8_t* ring = want_rgba ? p->d_rgba + (size_t)w->ring * p->W * p->max_pics * p->frame_bytes : nullptr;
-    uint8_t* pring = want_planes ? p->d_planes + (size_t)w->ring * p->W * p->max_pics * p->planes_bytes : nullptr;
-    auto rgba_of = [&](size_t lane, size_t tref) { return ring ? ring + (lane * p->max_pics + tref) * p->frame_bytes : nullptr; };
-    auto planes_of = [&](size_t lane, size_t tref) { return pring ? pring + (lane * p->max_pics + tref) * p->planes_bytes : nullptr; };
-    w->frames.clear();
-    for (size_t j = 0; j < lanes; j++) {
-        GopJob* job = w->jobs[j];
-        // upload the GOP's arena; everything of this window is copied before its first launch
-        const size_t up = p->gpu_parser ? job->upload_bytes : job->arena->used;
-        // LEON_DEBUG_POISON=1: everything of the arena that the kernels are expected to write before they read it starts
-        // as 0xCD bytes -- a read of something nobody wrote then shows in every run, not only when the memory's history
-        // happens to differ from zero
-        static const bool poison = env_int("LEON_DEBUG_POISON", 0) == 1;
-        if (poison && p->gpu_parser && job->arena->used > up) HIP_TRY(hipMemsetAsync(job->arena->dev + up, 0xCD, job->arena->used - up, p->copy_stream));
-        if (up) {
-            HIP_TRY(hipMemcpyAsync(job->arena->dev, job->arena->host, up, hipMemcpyHostToDevice, p->copy_stream));
-            p->st_upload += up;
-        }
+    const leon_decoder* d = p->dec;
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    FILE* idx = fopen((dir + "/index.txt").c_str(), lvl_no ? "a" : "w");
+    if (idx && !lvl_no)
+        fprintf(idx, "geom coded=%dx%d frame=%dx%d mbs=%d n_groups=%d gpu_parser=%d unfused=%d slot_bytes=%zu\n", p->vinfo.coded_width, p->vinfo.coded_height,
+                p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width * p->vinfo.mb_height, p->vinfo.n_groups, (int)p->gpu_parser, (int)p->unfused, d->plane_bytes);
+    for (const LevelPic& it : lvl) {
+        const PipePic& m = *it.pic;
+        const std::string stem = dir + "/L" + std::to_string(lvl_no) + "_g" + std::to_string(it.lane) + "_t" + std::to_string(m.tref);
+        if (it.out >= 0) capture_file(stem + "_out.planes", d->d_slots + (size_t)it.out * d->slot_stride, d->plane_bytes);
+        if (it.fwd >= 0) capture_file(stem + "_fwd.planes", d->d_slots + (size_t)it.fwd * d->slot_stride, d->plane_bytes);
+        if (it.bwd >= 0) capture_file(stem + "_bwd.planes", d->d_slots + (size_t)it.bwd * d->slot_stride, d->plane_bytes);
+        if (idx) fprintf(idx, "pic lane=%zu gop=%llu tref=%d type=%d level=%zu out=%d fwd=%d bwd=%d n_entries=%u qm=%d grp_off=%zd entries=%zd qscale=%zd intra=%zd repadd=%zd "
+                              "mb_dir=%zd mv_fwd=%zd mv_bwd=%zd\n", it.lane, (unsigned long long)w->jobs[it.lane]->key_gop, m.tref, m.type, lvl_no, it.out, it.fwd, it.bwd,
+                         m.n_entries, m.qm, (ssize_t)m.grp_off, (ssize_t)m.entries, (ssize_t)m.qscale, (ssize_t)m.intra, (ssize_t)m.repadd, (ssize_t)m.mb_dir, (ssize_t)m.mv_fwd, (ssize_t)m.mv_bwd);
+    }
+    if (idx) fclose(idx);
+    return LEON_OK;
+}
+
+// The pictures of one window as levels of launches: per GOP the anchors rotate through three slots (on the unfused road a B
+// picture has one of its own until it is converted); a picture's level is one more than the deepest picture it predicts from.
+int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::vector<LevelPic>>& levels)
+{
+    const int per_lane = 3 + (p->unfused ? p->max_pics : 0);
+    for (size_t j = 0; j < w->jobs.size(); j++) {
+        const GopJob* job = w->jobs[j];
         int older = -1, newer = -1, lv_older = -1, lv_newer = -1, n_anchor = 0;      // anchor slots (0..2 of the lane) and their levels
-        const int per_lane = 3 + (p->unfused ? p->max_pics : 0);
         int n_b = 0;
         for (const PipePic& m : job->pics) {
-            Item it{j, &m, -1, -1, -1};
+            LevelPic it{j, &m, -1, -1, -1};
             int lv = 0;
             if (m.type == LEON_PIC_I) {
                 it.out = (int)(per_lane * j) + n_anchor % 3;
@@ -679,7 +704,7 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
                 it.bwd = newer;
                 it.fwd = older >= 0 ? older : newer;
                 lv = std::max(lv_newer, lv_older) + 1;
-                if (p->unfused) it.out = (int)(per_lane * j) + 3 + n_b++ % p->max_pics;      // a slot of its own until it is converted
+                if (p->unfused) it.out = (int)(per_lane * j) + 3 + n_b++ % p->max_pics;
             }
             if (m.type != LEON_PIC_B) {
                 older = newer; lv_older = lv_newer;
@@ -697,165 +722,170 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
             seen[(size_t)m.tref] = 1;
         }
     }
-    hipEvent_t copied = get_event(d);
-    if (!copied) return LEON_ERR_HIP;
-    HIP_TRY(hipEventRecord(copied, p->copy_stream));
-    // LEON_DEBUG_SERIAL=1: the host waits behind every stage (uploads, parser kernels, reconstruction) -- takes every
-    // cross-stream dependency out of the picture when a wrong frame is being hunted
-    static const bool serial = env_int("LEON_DEBUG_SERIAL", 0) == 1;
+    return LEON_OK;
+}
+
+// Every GOP's arena goes up on the copy stream before the window's first launch; then the chain copy stream -> (gpu_parser:
+// the parser kernels, on a parser stream ->) the decoder's stream.
+int upload_and_chain(leon_pipeline* p, PipeWindow* w, bool serial, bool poison)
+{
+    leon_decoder* d = p->dec;
+    for (GopJob* job : w->jobs) {
+        const size_t up = p->gpu_parser ? job->upload_bytes : job->arena->used;
+        if (poison && p->gpu_parser && job->arena->used > up) HIP_TRY(hipMemsetAsync(job->arena->dev + up, 0xCD, job->arena->used - up, p->copy_stream));
+        if (up) {
+            HIP_TRY(hipMemcpyAsync(job->arena->dev, job->arena->host, up, hipMemcpyHostToDevice, p->copy_stream));
+            p->st_upload += up;
+        }
+    }
+    hipEvent_t ready = get_event(d);            // what the decoder's stream waits for: the upload, or the parser kernels
+    if (!ready) return LEON_ERR_HIP;
+    HIP_TRY(hipEventRecord(ready, p->copy_stream));
     if (serial) HIP_TRY(hipStreamSynchronize(p->copy_stream));
     if (p->gpu_parser) {
-        // upload -> parser kernels (their own stream) -> reconstruction (the decoder's stream)
-        HIP_TRY(hipStreamWaitEvent(p->vlc_stream[vlc_stream_of(w->id)], copied, 0));
-        d->ev_pool.push_back(copied);
+        hipStream_t vs = p->vlc_stream[vlc_stream_of(w->id)];
+        HIP_TRY(hipStreamWaitEvent(vs, ready, 0));
+        d->ev_pool.push_back(ready);
         const int rc = launch_gpu_parser(p, w);
         if (rc != LEON_OK) return rc;
-        if (serial) HIP_TRY(hipStreamSynchronize(p->vlc_stream[vlc_stream_of(w->id)]));
-        hipEvent_t parsed = get_event(d);
-        if (!parsed) return LEON_ERR_HIP;
-        HIP_TRY(hipEventRecord(parsed, p->vlc_stream[vlc_stream_of(w->id)]));
-        HIP_TRY(hipStreamWaitEvent(d->stream, parsed, 0));
-        d->ev_pool.push_back(parsed);
-    } else {
-        HIP_TRY(hipStreamWaitEvent(d->stream, copied, 0));
-        d->ev_pool.push_back(copied);
+        if (serial) HIP_TRY(hipStreamSynchronize(vs));
+        if (!(ready = get_event(d))) return LEON_ERR_HIP;
+        HIP_TRY(hipEventRecord(ready, vs));
     }
-    // the matrix sets of shards whose sequence headers carry other matrices than the stream's first: registered with the
-    // decoder here, on the one thread that drives it (the upload is ordered in front of the launches by the stream)
-    std::vector<std::vector<int32_t>> qset(lanes);
-    for (size_t j = 0; j < lanes; j++)
+    HIP_TRY(hipStreamWaitEvent(d->stream, ready, 0));
+    d->ev_pool.push_back(ready);
+    return LEON_OK;
+}
+
+// the matrix sets of shards whose sequence headers carry other matrices than the stream's first: registered with the
+// decoder here, on the one thread that drives it (the upload is ordered in front of the launches by the stream)
+int register_qsets(leon_pipeline* p, const PipeWindow* w, std::vector<std::vector<int32_t>>& qset)
+{
+    for (size_t j = 0; j < w->jobs.size(); j++)
         for (const auto& m : w->jobs[j]->qms) {
             int32_t id = 0;
-            const int rc = leon_add_quant_matrices(d, m.data(), m.data() + 64, &id);
+            const int rc = leon_add_quant_matrices(p->dec, m.data(), m.data() + 64, &id);
             if (rc != LEON_OK) return rc;
             qset[j].push_back(id);
         }
-    const bool capture = !p->capture_dir.empty();
-    const std::string cdir = capture ? p->capture_dir + "/w" + std::to_string(w->id) : std::string();
-    FILE* cidx = nullptr;
-    if (capture) {
-        (void)mkdir(p->capture_dir.c_str(), 0777);          // (both may exist)
-        (void)mkdir(cdir.c_str(), 0777);
-        cidx = fopen((cdir + "/index.txt").c_str(), "w");
-        if (cidx) fprintf(cidx, "geom coded=%dx%d frame=%dx%d mbs=%d n_groups=%d gpu_parser=%d unfused=%d slot_bytes=%zu\n", p->vinfo.coded_width, p->vinfo.coded_height,
-                          p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width * p->vinfo.mb_height, p->vinfo.n_groups, (int)p->gpu_parser, (int)p->unfused, d->plane_bytes);
+    return LEON_OK;
+}
+
+// One level, one batch.  Fused road: a shown picture's launch writes its frame (RGBA and / or planes), B pictures nothing
+// else.  Unfused road: every picture writes its planes, then each shown one is converted (leon_convert_rgba) and the level's
+// shown pictures are cropped into their frames' planes (k_planes_crop, one launch).
+int launch_level(leon_pipeline* p, const PipeWindow* w, const std::vector<LevelPic>& lvl, const std::vector<std::vector<int32_t>>& qset)
+{
+    leon_decoder* d = p->dec;
+    std::vector<AnyPic> batch;
+    for (const LevelPic& it : lvl) {
+        const char* base = w->jobs[it.lane]->arena->dev;
+        const PipePic& m = *it.pic;
+        auto ptr = [&](size_t off) -> const void* { return off == kNone ? nullptr : (const void*)(base + off); };
+        const bool writes_frame = !p->unfused && m.shown;
+        const FrameAddr f = frame_addr(p, w->ring, it.lane, (size_t)m.tref);
+        AnyPic a;
+        a.sparse = true;
+        a.p.type = m.type;
+        a.p.out_slot = it.out;
+        a.p.ref_fwd_slot = it.fwd;
+        a.p.ref_bwd_slot = it.bwd;
+        a.grp_off = (const uint32_t*)ptr(m.grp_off);
+        a.entries = (const uint32_t*)ptr(m.entries);
+        a.n_entries = m.n_entries;
+        a.p.qscale = (const uint8_t*)ptr(m.qscale);
+        a.p.intra = (const uint8_t*)ptr(m.intra);
+        a.p.repadd = (const uint8_t*)ptr(m.repadd);
+        a.p.mb_dir = (const uint8_t*)ptr(m.mb_dir);
+        a.p.mv_fwd = (const int16_t*)ptr(m.mv_fwd);
+        a.p.mv_bwd = (const int16_t*)ptr(m.mv_bwd);
+        a.p.rgba_out = writes_frame ? f.rgba : nullptr;
+        a.planes_out = writes_frame ? f.planes : nullptr;
+        a.p.no_planes = !p->unfused && m.type == LEON_PIC_B;
+        a.p.qm_set = m.qm >= 0 ? qset[it.lane][(size_t)m.qm] : 0;
+        batch.push_back(a);
     }
-    size_t lvl_no = 0;
-    std::vector<leon_sparse_picture> batch;
-    std::vector<uint8_t*> batch_planes;
+    int rc = submit_batch_any(d, batch.data(), (int)batch.size(), LEON_MEM_DEVICE);
+    if (rc != LEON_OK || !p->unfused) return rc;
     std::vector<int32_t> crop_slots;
     std::vector<uint8_t*> crop_frames;
-    for (auto& lvl : levels) {
-        batch.clear();
-        batch_planes.clear();
-        for (const Item& it : lvl) {
-            const char* base = w->jobs[it.lane]->arena->dev;
-            const PipePic& m = *it.pic;
-            auto ptr = [&](size_t off) -> const void* { return off == kNone ? nullptr : (const void*)(base + off); };
-            leon_sparse_picture sp{};
-            sp.type = m.type;
-            sp.out_slot = it.out;
-            sp.ref_fwd_slot = it.fwd;
-            sp.ref_bwd_slot = it.bwd;
-            sp.grp_off = (const uint32_t*)ptr(m.grp_off);
-            sp.entries = (const uint32_t*)ptr(m.entries);
-            sp.n_entries = m.n_entries;
-            sp.qscale = (const uint8_t*)ptr(m.qscale);
-            sp.intra = (const uint8_t*)ptr(m.intra);
-            sp.repadd = (const uint8_t*)ptr(m.repadd);
-            sp.mb_dir = (const uint8_t*)ptr(m.mb_dir);
-            sp.mv_fwd = (const int16_t*)ptr(m.mv_fwd);
-            sp.mv_bwd = (const int16_t*)ptr(m.mv_bwd);
-            // fused road: a shown picture's launch writes its frame (RGBA and / or planes), B pictures nothing else
-            sp.rgba_out = p->unfused || !m.shown ? nullptr : rgba_of(it.lane, (size_t)m.tref);
-            sp.no_planes = !p->unfused && m.type == LEON_PIC_B;
-            sp.qm_set = m.qm >= 0 ? qset[it.lane][(size_t)m.qm] : 0;
-            batch.push_back(sp);
-            batch_planes.push_back(p->unfused || !m.shown ? nullptr : planes_of(it.lane, (size_t)m.tref));
+    for (const LevelPic& it : lvl) {
+        if (!it.pic->shown) continue;
+        const FrameAddr f = frame_addr(p, w->ring, it.lane, (size_t)it.pic->tref);
+        if (f.rgba && (rc = leon_convert_rgba(d, it.out, f.rgba, LEON_MEM_DEVICE, p->flavour)) != LEON_OK) return rc;
+        if (f.planes) {
+            crop_slots.push_back(it.out);
+            crop_frames.push_back(f.planes);
         }
-        if (batch.empty()) continue;
-        std::vector<AnyPic> apics = wrap(batch.data(), (int)batch.size());
-        for (size_t i = 0; i < apics.size(); i++) apics[i].planes_out = batch_planes[i];
-        int rc = submit_batch_any(d, apics.data(), (int)apics.size(), LEON_MEM_DEVICE);
-        if (rc != LEON_OK) return rc;
-        if (p->unfused) {
-            crop_slots.clear();
-            crop_frames.clear();
-            for (const Item& it : lvl) {
-                if (!it.pic->shown) continue;
-                if (want_rgba) {
-                    rc = leon_convert_rgba(d, it.out, rgba_of(it.lane, (size_t)it.pic->tref), LEON_MEM_DEVICE, p->flavour);
-                    if (rc != LEON_OK) return rc;
-                }
-                if (want_planes) {
-                    crop_slots.push_back(it.out);
-                    crop_frames.push_back(planes_of(it.lane, (size_t)it.pic->tref));
-                }
-            }
-            // the level's shown pictures' planes, one launch (k_planes_crop)
-            rc = crop_planes_batch(d, crop_slots.data(), crop_frames.data(), (int)crop_slots.size());
-            if (rc != LEON_OK) return rc;
-        }
-        if (capture) {
-            HIP_TRY(hipStreamSynchronize(d->stream));
-            for (const Item& it : lvl) {
-                const PipePic& m = *it.pic;
-                const std::string stem = cdir + "/L" + std::to_string(lvl_no) + "_g" + std::to_string(it.lane) + "_t" + std::to_string(m.tref);
-                if (it.out >= 0) capture_file(stem + "_out.planes", d->d_slots + (size_t)it.out * d->slot_stride, d->plane_bytes);
-                if (it.fwd >= 0) capture_file(stem + "_fwd.planes", d->d_slots + (size_t)it.fwd * d->slot_stride, d->plane_bytes);
-                if (it.bwd >= 0) capture_file(stem + "_bwd.planes", d->d_slots + (size_t)it.bwd * d->slot_stride, d->plane_bytes);
-                if (cidx) fprintf(cidx, "pic lane=%zu gop=%llu tref=%d type=%d level=%zu out=%d fwd=%d bwd=%d n_entries=%u qm=%d grp_off=%zd entries=%zd qscale=%zd intra=%zd repadd=%zd "
-                                        "mb_dir=%zd mv_fwd=%zd mv_bwd=%zd\n", it.lane, (unsigned long long)w->jobs[it.lane]->key_gop, m.tref, m.type, lvl_no, it.out, it.fwd, it.bwd,
-                                  m.n_entries, m.qm, (ssize_t)m.grp_off, (ssize_t)m.entries, (ssize_t)m.qscale, (ssize_t)m.intra, (ssize_t)m.repadd, (ssize_t)m.mb_dir, (ssize_t)m.mv_fwd, (ssize_t)m.mv_bwd);
-            }
-        }
-        lvl_no++;
     }
-    if (capture) {
-        for (size_t j = 0; j < lanes; j++) capture_file(cdir + "/arena_" + std::to_string(j) + ".bin", w->jobs[j]->arena->dev, w->jobs[j]->arena->used);
-        if (cidx) fclose(cidx);
-    }
-    if (serial) HIP_TRY(hipStreamSynchronize(d->stream));
-    HIP_TRY(hipEventRecord(w->done, d->stream));
-    // frames in display order, GOP-major
-    const double rate = p->vinfo.picture_rate > 0 ? p->vinfo.picture_rate : 25.0;
-    for (size_t j = 0; j < lanes; j++) {
-        GopJob* job = w->jobs[j];
+    return crop_planes_batch(d, crop_slots.data(), crop_frames.data(), (int)crop_slots.size());
+}
+
+// the window's frames in display order, GOP-major
+void list_frames(leon_pipeline* p, PipeWindow* w)
+{
+    w->frames.clear();
+    for (size_t j = 0; j < w->jobs.size(); j++) {
+        const GopJob* job = w->jobs[j];
         // by temporal reference: a GOP cut short by the encoder may skip display positions
         std::vector<const PipePic*> by_disp((size_t)p->max_pics, nullptr);
         for (const PipePic& m : job->pics) by_disp[(size_t)m.tref] = &m;
         for (size_t k = 0; k < by_disp.size(); k++) {
             if (!by_disp[k] || !by_disp[k]->shown) continue;
+            const FrameAddr a = frame_addr(p, w->ring, j, k);
             leon_pipeline_frame f{};
             f.gop = job->key_gop;
             f.display_index = (int32_t)k;
             f.type = by_disp[k]->type;
-            f.ts_ms = job->gop_ts_ms + 1000.0 * (double)k / rate;
-            f.rgba = rgba_of(j, k);
-            if (uint8_t* pl = planes_of(j, k)) {
-                f.y = pl;
-                f.cb = pl + p->planes_geom.cb_off;
-                f.cr = pl + p->planes_geom.cr_off;
-                f.a = p->vinfo.has_alpha == 1 ? pl + p->planes_geom.a_off : nullptr;
+            f.ts_ms = frame_ts_ms(p, job, (int)k);
+            f.rgba = a.rgba;
+            if (a.planes) {
+                f.y = a.planes;
+                f.cb = a.planes + p->planes_geom.cb_off;
+                f.cr = a.planes + p->planes_geom.cr_off;
+                f.a = p->vinfo.has_alpha == 1 ? a.planes + p->planes_geom.a_off : nullptr;
             }
             w->frames.push_back(f);
         }
         p->st_pictures += job->pics.size();
     }
-    p->st_gops += lanes;
-    return LEON_OK;
+    p->st_gops += w->jobs.size();
 }
 
-void submit_loop(leon_pipeline* p);
-void submit_main(leon_pipeline* p)
+// one window: its levels planned, its arenas uploaded (and parsed on the GPU), its levels launched, its frames listed
+int submit_window(leon_pipeline* p, PipeWindow* w)
 {
-    hipSetDevice(p->cfg.device_id);
-    submit_loop(p);
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        p->submit_exited = true;
+    // LEON_DEBUG_SERIAL=1: the host waits behind every stage (uploads, parser kernels, reconstruction) -- takes every
+    // cross-stream dependency out of the picture when a wrong frame is being hunted
+    static const bool serial = env_int("LEON_DEBUG_SERIAL", 0) == 1;
+    // LEON_DEBUG_POISON=1: everything of the arena that the kernels are expected to write before they read it starts
+    // as 0xCD bytes -- a read of something nobody wrote then shows in every run, not only when the memory's history
+    // happens to differ from zero
+    static const bool poison = env_int("LEON_DEBUG_POISON", 0) == 1;
+    std::vector<std::vector<LevelPic>> levels;
+    std::vector<std::vector<int32_t>> qset(w->jobs.size());
+    int rc = plan_levels(p, w, levels);
+    if (rc == LEON_OK) rc = upload_and_chain(p, w, serial, poison);
+    if (rc == LEON_OK) rc = register_qsets(p, w, qset);
+    if (rc != LEON_OK) return rc;
+    const std::string cdir = p->capture_dir.empty() ? "" : p->capture_dir + "/w" + std::to_string(w->id);
+    if (!cdir.empty()) {
+        (void)mkdir(p->capture_dir.c_str(), 0777);          // (both may exist)
+        (void)mkdir(cdir.c_str(), 0777);
     }
-    p->cv.notify_all();
+    size_t lvl_no = 0;
+    for (const auto& lvl : levels) {
+        if (lvl.empty()) continue;
+        if ((rc = launch_level(p, w, lvl, qset)) != LEON_OK) return rc;
+        if (!cdir.empty() && (rc = capture_level(p, w, cdir, lvl, lvl_no)) != LEON_OK) return rc;
+        lvl_no++;
+    }
+    if (!cdir.empty())
+        for (size_t j = 0; j < w->jobs.size(); j++) capture_file(cdir + "/arena_" + std::to_string(j) + ".bin", w->jobs[j]->arena->dev, w->jobs[j]->arena->used);
+    if (serial) HIP_TRY(hipStreamSynchronize(p->dec->stream));
+    HIP_TRY(hipEventRecord(w->done, p->dec->stream));
+    list_frames(p, w);
+    return LEON_OK;
 }
 
 void submit_loop(leon_pipeline* p)
@@ -932,6 +962,17 @@ void submit_loop(leon_pipeline* p)
         p->cv.notify_all();
         if (rc != LEON_OK) return;
     }
+}
+
+void submit_main(leon_pipeline* p)
+{
+    hipSetDevice(p->cfg.device_id);
+    submit_loop(p);
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        p->submit_exited = true;
+    }
+    p->cv.notify_all();
 }
 
 void release_window_locked(leon_pipeline* p, PipeWindow* w)
@@ -1045,8 +1086,8 @@ void notify_main(leon_pipeline* p)
 }
 
 // The run that starts at `seconds`: the key-map entry the front end's own seek finds (leon_vlc_seek, decoders/jsv.js
-// :327-350), then this shard's entries from it on.  leon_pipeline_create (start_seconds) and leon_pipeline_seek both
-// ask here; `st` is a stream opened on the pipeline's bytes (its container header and key map).
+// :327-350), then this shard's entries from it on, in windows of p->W GOPs.  leon_pipeline_create (start_seconds) and
+// leon_pipeline_seek both ask here; `st` is a stream opened on the pipeline's bytes (its container header and key map).
 std::shared_ptr<PipeRun> make_run(const leon_pipeline* p, leon_vlc_stream* st, double seconds, int loops)
 {
     auto run = std::make_shared<PipeRun>();
@@ -1059,42 +1100,21 @@ std::shared_ptr<PipeRun> make_run(const leon_pipeline* p, leon_vlc_stream* st, d
     for (uint32_t g : p->shard_gops)
         if (g >= run->first_key) run->mine.push_back(g);
     run->total_gops = (uint64_t)run->mine.size() * (uint64_t)loops;
+    run->total_windows = (int64_t)((run->total_gops + p->W - 1) / p->W);
     return run;
 }
 
-}  // namespace
+// k_vlc_index counts a picture's groups in LDS (one workgroup may have all 160 KiB of a CU)
+constexpr size_t kMaxVlcIndexLds = 160 * 1024 - 512;
 
-extern "C" {
-
-int leon_pipeline_create(const leon_pipeline_config* cfg, const uint8_t* stream, size_t bytes,
-                         leon_pipeline_callback cb, void* user, leon_pipeline** out)
+// Create, stage 1: what the config and the stream decide -- the shards, the run, W / R / K, the longest GOP, the front
+// end, the output and its roads, info.  No HIP call and no allocation: a refused config leaves nothing to free but p.
+int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const uint8_t* stream, size_t bytes, size_t valid_bytes)
 {
-    return leon_pipeline_create_partial(cfg, stream, bytes, bytes, cb, user, out);
-}
-
-int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes)
-{
-    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
-    if (valid_bytes > p->bytes) return fail(LEON_ERR_INVALID, "%zu bytes fed, the stream has %zu", valid_bytes, p->bytes);
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (valid_bytes > p->valid) p->valid = valid_bytes;
-    }
-    p->cv.notify_all();
-    return LEON_OK;
-}
-
-int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t* stream, size_t bytes, size_t valid_bytes,
-                                 leon_pipeline_callback cb, void* user, leon_pipeline** out)
-{
-    if (!cfg || !stream || bytes < 16 || !out) return fail(LEON_ERR_INVALID, "null argument");
-    if (valid_bytes > bytes) return fail(LEON_ERR_INVALID, "%zu valid bytes of a stream of %zu", valid_bytes, bytes);
-    *out = nullptr;
     leon_vlc_stream* st = nullptr;
     // the container header, the key map and the first sequence header must have arrived
     if (leon_vlc_open(stream, valid_bytes, 1, &st) != LEON_VLC_OK) return fail(LEON_ERR_INVALID, "stream: %s", leon_vlc_last_error());
-    leon_pipeline* p = new (std::nothrow) leon_pipeline();
-    if (!p) { leon_vlc_close(st); return fail(LEON_ERR_NOMEM, "out of host memory"); }
+    const std::unique_ptr<leon_vlc_stream, decltype(&leon_vlc_close)> st_owner(st, &leon_vlc_close);
     leon_vlc_get_info(st, &p->vinfo);
     const int n_keys = leon_vlc_get_keymap(st, nullptr, nullptr, 0);
     std::vector<uint32_t> offs((size_t)std::max(n_keys, 0));
@@ -1103,18 +1123,13 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     p->stream = stream;
     p->bytes = bytes;
     p->valid = valid_bytes;
-    p->cb = cb;
-    p->user = user;
     if (const char* cd = getenv("LEON_DEBUG_CAPTURE")) p->capture_dir = cd;
     if (n_keys > 0) {
         for (int g = 0; g < n_keys; g++) {
             const uint64_t b = offs[(size_t)g], e = g + 1 < n_keys ? offs[(size_t)g + 1] : bytes;
             // (an entry behind what has arrived of a partial stream is looked at when its bytes are there: parser_main)
-            if (b >= e || e > bytes || b + 4 > bytes || (b + 4 <= valid_bytes && (stream[b] != 0 || stream[b + 1] != 0 || stream[b + 2] != 1))) {
-                leon_vlc_close(st);
-                delete p;
+            if (b >= e || e > bytes || b + 4 > bytes || (b + 4 <= valid_bytes && (stream[b] != 0 || stream[b + 1] != 0 || stream[b + 2] != 1)))
                 return fail(LEON_ERR_INVALID, "key map entry %d does not point at a start code", g);
-            }
             p->shard_begin.push_back(b);
             // the shard takes the start code PREFIX of what follows along (00 00 01, not the code byte): its last slice
             // then ends exactly as it does in the whole stream.  Cut at the key-map offset, a last macroblock coded in
@@ -1127,22 +1142,21 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     }
     const int loops = cfg->loop > 0 ? cfg->loop : 1;
     const uint32_t sc = cfg->shard_count > 1 ? (uint32_t)cfg->shard_count : 1u, si = sc > 1 ? (uint32_t)cfg->shard_index : 0u;
-    if (si >= sc) { leon_vlc_close(st); delete p; return fail(LEON_ERR_INVALID, "shard_index %d of %d", cfg->shard_index, cfg->shard_count); }
+    if (si >= sc) return fail(LEON_ERR_INVALID, "shard_index %d of %d", cfg->shard_index, cfg->shard_count);
     p->has_keymap = n_keys > 0;
     for (uint32_t g = si; g < p->shard_begin.size(); g += sc) p->shard_gops.push_back(g);
-    const std::shared_ptr<PipeRun> run0 = make_run(p, st, cfg->start_seconds, loops);
-    leon_vlc_close(st);
-    p->run = run0;
-    const PipeRun& run = *run0;
-    p->info.first_gop = run.first_key;
-    if (run.mine.empty()) { delete p; return fail(LEON_ERR_INVALID, "shard %u of %u gets no GOP: the stream has %zu", si, sc, p->shard_begin.size()); }
     p->W = cfg->gops_per_window > 0 ? cfg->gops_per_window : 32;
-    if ((uint64_t)p->W > run.total_gops) p->W = (int)run.total_gops;
+    p->run = make_run(p, st, cfg->start_seconds, loops);
+    const PipeRun& run = *p->run;
+    p->info.first_gop = run.first_key;
+    if (run.mine.empty()) return fail(LEON_ERR_INVALID, "shard %u of %u gets no GOP: the stream has %zu", si, sc, p->shard_begin.size());
+    if ((uint64_t)p->W > run.total_gops) p->W = (int)run.total_gops;      // (one window either way: run.total_windows stands)
     p->gpu_parser = cfg->gpu_parser >= 0;          // 0 = default: the GPU (a pipeline has a device by construction); < 0: the parser threads
+    p->vlc_index_lds = ((size_t)p->vinfo.n_groups + leon::kVlcIndexThreads) * 4;      // the group counters of one picture + its scan
     if (cfg->gpu_parser == LEON_PIPELINE_PARSER_DEFAULT) {
         // a caller who did not ASK for the GPU parser is not refused for its limits: a picture whose group counters do not fit
         // k_vlc_index's LDS, or a GOP shard of 2^28 bytes and more (the kernels count bits in 32), goes to the parser threads
-        bool fits = ((size_t)p->vinfo.n_groups + leon::kVlcIndexThreads) * 4 <= (size_t)160 * 1024 - 512;
+        bool fits = p->vlc_index_lds <= kMaxVlcIndexLds;
         for (uint32_t g : p->shard_gops) fits = fits && p->shard_end[g] - p->shard_begin[g] < ((uint64_t)1 << 28);
         if (p->vinfo.n_groups > env_int("LEON_DEBUG_GPU_PARSER_LIMIT", INT_MAX)) fits = false;      // tests: a mocked n_groups limit
         if (!fits) p->gpu_parser = false;
@@ -1173,7 +1187,6 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     int k = cfg->parser_threads;
     if (k <= 0) { k = (int)std::thread::hardware_concurrency(); if (k < 1) k = 1; if (k > 16) k = 16; }
     p->K = k;
-    run0->total_windows = (int64_t)((run.total_gops + p->W - 1) / p->W);
     p->frame_bytes = (size_t)p->vinfo.frame_width * p->vinfo.frame_height * 4;
     p->info.coded_width = p->vinfo.coded_width; p->info.coded_height = p->vinfo.coded_height;
     p->info.frame_width = p->vinfo.frame_width; p->info.frame_height = p->vinfo.frame_height;
@@ -1185,8 +1198,8 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     // any width (player/easybits.player.js:2818): such a stream takes the slow road -- every picture (B pictures too)
     // writes its planes, and one leon_convert_rgba per picture (the generic k_rgba_twin) fills the window's frames.
     // The GL flavour (the reference's live display arithmetic, fp32) exists as a launch of its own only: the same road.
-    if (cfg->display_flavour != LEON_RGB_CPU_TWIN && cfg->display_flavour != LEON_RGB_GL) { delete p; return fail(LEON_ERR_INVALID, "display_flavour %d", cfg->display_flavour); }
-    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR)) { delete p; return fail(LEON_ERR_INVALID, "output %d", cfg->output); }
+    if (cfg->display_flavour != LEON_RGB_CPU_TWIN && cfg->display_flavour != LEON_RGB_GL) return fail(LEON_ERR_INVALID, "display_flavour %d", cfg->display_flavour);
+    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR)) return fail(LEON_ERR_INVALID, "output %d", cfg->output);
     // the frames' planes (output YCbCr): the layout of include/leon_pipeline.h, one record per frame, A behind Cr for yuva
     p->output = cfg->output ? cfg->output : LEON_PIPELINE_OUTPUT_RGBA;
     p->planes_geom = planes_layout(p->vinfo.frame_width, p->vinfo.frame_height, &p->planes_bytes);
@@ -1199,118 +1212,127 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     p->flavour = cfg->display_flavour;
     p->info.display_flavour = p->flavour;
     p->unfused = (p->vinfo.frame_width & 7) != 0 || p->flavour == LEON_RGB_GL;
-    if (p->unfused && p->vinfo.has_alpha == 1) {
-        delete p;
+    if (p->unfused && p->vinfo.has_alpha == 1)
         return fail(LEON_ERR_INVALID, "a yuva stream needs frame_width %% 8 == 0 (it is %d) and the CPU-twin display flavour in the pipeline", p->vinfo.frame_width);
-    }
+    p->maps = map_layout((size_t)p->vinfo.mb_width * p->vinfo.mb_height, (size_t)p->vinfo.n_groups);
+    // the GPU parser's geometry; it writes a picture's maps at the offsets of the layout the arenas give them
+    p->vgeom.mbw = p->vinfo.mb_width; p->vgeom.mbh = p->vinfo.mb_height;
+    p->vgeom.gy = p->vinfo.groups_y; p->vgeom.gc = p->vinfo.groups_c;
+    p->vgeom.n_y = 2 * p->vinfo.mb_height * p->vinfo.groups_y;
+    p->vgeom.n_c = p->vinfo.mb_height * p->vinfo.groups_c;
+    p->vgeom.n_groups = p->vinfo.n_groups;
+    p->vgeom.alpha = p->vinfo.has_alpha == 1;
+    const MapLayout& M = p->maps;
+    p->vgeom.off_qscale = (uint32_t)M.off(M.QSCALE);
+    p->vgeom.off_intra = (uint32_t)M.off(M.INTRA);
+    p->vgeom.off_repadd = (uint32_t)M.off(M.REPADD);
+    p->vgeom.off_mb_dir = (uint32_t)M.off(M.MB_DIR);
+    p->vgeom.off_mv_fwd = (uint32_t)M.off(M.MV_FWD);
+    p->vgeom.off_mv_bwd = (uint32_t)M.off(M.MV_BWD);
+    return LEON_OK;
+}
 
+// The front end's tables as the GPU parser's kernels copy them to LDS (leon_vlc_gpu.h), 16 bits per entry.  Returns what
+// does not fit, "" when everything does.
+std::string pack_vlc_tables(const leon_vlc_gpu_tables& src, leon::VlcTables& t)
+{
+    // fast12 as {length:4, end of block:1, run:5, level:6}, the others as (length << 8) | value
+    for (int i = 0; i < 4096; i++) {
+        const uint32_t f = src.fast12[i];
+        const int len = (int)(f & 0x7f), run = (int)((f >> 8) & 0xff), level = (int)(int16_t)(f >> 16);
+        if (len > 15 || run > 31 || level < -32 || level > 31) return "coefficient table does not fit 16 bits";
+        t.fast12[i] = (uint16_t)(len | ((f & 0x80u) ? 0x10 : 0) | (run << 5) | ((level & 63) << 10));
+    }
+    // multi12: every symbol that lies complete in the next 12 bits, taken together (a prefix code is decided by its own
+    // bits: the entry of the pattern shifted up, whatever follows, names the symbol if its length fits what is left)
+    for (int i = 0; i < leon::kVlcMulti; i++) {
+        const int B = leon::kVlcMultiBits;
+        int pos = 0, nsym = 0, adv = 0, eob = 0;
+        while (pos < B) {
+            // the 12 bits from `pos` on, zeros behind the pattern's end
+            const uint32_t f = src.fast12[(((uint32_t)i << pos) & (uint32_t)(leon::kVlcMulti - 1)) << 12 >> B];
+            const int len = (int)(f & 0x7f);
+            if (len == 0 || len > B - pos) break;
+            pos += len;
+            if (f & 0x80u) { eob = 1; break; }
+            nsym++;
+            adv += (int)((f >> 8) & 0xff) + 1;
+        }
+        if (pos > 15 || nsym > 7 || adv > 255) return "multi-symbol table does not fit 16 bits";
+        t.multi12[i] = (uint16_t)(pos | (nsym << 4) | (eob << 7) | (adv << 8));
+    }
+    auto pack = [](int32_t e) { return (uint16_t)(((e >> 16) << 8) | (e & 0xff)); };
+    for (int i = 0; i < 2048; i++) { t.motion_s[i] = pack(src.motion_s[i]); t.mba[i] = pack(src.mba[i]); }
+    for (int i = 0; i < 512; i++) t.cbp[i] = pack(src.cbp[i]);
+    for (int k = 0; k < 4; k++) for (int i = 0; i < 64; i++) t.mbtype[k][i] = pack(src.mbtype[k][i]);
+    for (int i = 0; i < 128; i++) t.dc_lum[i] = pack(src.dc_lum[i]);
+    for (int i = 0; i < 256; i++) t.dc_chr[i] = pack(src.dc_chr[i]);
+    for (int i = 0; i < 64; i++) t.zz_off[i] = src.zz_off[i];
+    // the codes of 12 .. 16 bits start with seven zeros: by the nine bits behind them (= the first 512 entries of the
+    // 16-bit table)
+    for (int i = 0; i < 512; i++) {
+        const int32_t e = src.coef16[i];
+        const int len = e >> 16, cf = e & 0xffff, run = cf >> 8, level = cf & 0xff;
+        if (e == 0) { t.long9[i] = 0; continue; }
+        if (cf == 0xffff || len < 8 || len > 16 || run > 31 || level > 63 || level == 0) return "long coefficient code does not fit 16 bits";
+        t.long9[i] = (uint16_t)(len | (run << 5) | (level << 10));
+    }
+    return "";
+}
+
+// "<what>: <the runtime's last error>"
+int hip_fail(int code, const std::string& what)
+{
+    return fail(code, "%s: %s", what.c_str(), hipGetErrorString(hipGetLastError()));
+}
+
+// one output ring: R entries of W * max_pics frames of `frame` bytes
+int alloc_ring(leon_pipeline* p, uint8_t** ring, size_t frame, const char* name)
+{
+    const size_t bytes = (size_t)p->R * p->W * p->max_pics * frame;
+    if (big_alloc((void**)ring, bytes, kBigRgbaRing) == hipSuccess) return LEON_OK;
+    return hip_fail(LEON_ERR_NOMEM, std::string(name) + " ring of " + std::to_string(bytes >> 20) + " MiB (windows_in_flight " + std::to_string(p->R) +
+                                        " x gops_per_window " + std::to_string(p->W) + " x max_gop_pictures " + std::to_string(p->max_pics) + " x " +
+                                        std::to_string(frame) + " bytes per frame)");
+}
+
+// Create, stage 2: the decoder, the copy stream, the output rings, the GPU parser's tables and streams, the arenas and
+// their slabs.  A failure returns its code with the message set and leaves what it allocated to leon_pipeline_destroy.
+int allocate_pipeline(leon_pipeline* p)
+{
     leon_config dc{};
     dc.coded_width = p->vinfo.coded_width; dc.coded_height = p->vinfo.coded_height;
     dc.frame_width = p->vinfo.frame_width; dc.frame_height = p->vinfo.frame_height;
     dc.n_slots = (3 + (p->unfused ? p->max_pics : 0)) * p->W;      // three rotating anchors per GOP of a window (+ its B pictures)
     dc.alpha = p->vinfo.has_alpha == 1;        // yuva: the frames' A bytes come from the stream's fourth component
-    dc.device_id = cfg->device_id;
+    dc.device_id = p->cfg.device_id;
     int rc = leon_create(&dc, &p->dec);
-    if (rc != LEON_OK) { delete p; return rc; }
-    rc = leon_set_quant_matrices(p->dec, p->vinfo.intra_qm, p->vinfo.non_intra_qm);
-    auto bail = [&](int code, const char* what) {
-        std::string m = std::string(what) + ": " + hipGetErrorString(hipGetLastError());
-        leon_pipeline_destroy(p);
-        return fail(code, "%s", m.c_str());
-    };
-    if (rc != LEON_OK) { leon_pipeline_destroy(p); return rc; }
-    if (hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking) != hipSuccess) return bail(LEON_ERR_HIP, "copy stream");
-    if ((p->output & LEON_PIPELINE_OUTPUT_YCBCR) && big_alloc((void**)&p->d_planes, (size_t)p->R * p->W * p->max_pics * p->planes_bytes, kBigRgbaRing) != hipSuccess) {
-        const std::string what = "planes ring of " + std::to_string((size_t)p->R * p->W * p->max_pics * p->planes_bytes >> 20) + " MiB (windows_in_flight " +
-                                 std::to_string(p->R) + " x gops_per_window " + std::to_string(p->W) + " x max_gop_pictures " + std::to_string(p->max_pics) +
-                                 " x " + std::to_string(p->planes_bytes) + " bytes per frame)";
-        return bail(LEON_ERR_NOMEM, what.c_str());
-    }
-    if ((p->output & LEON_PIPELINE_OUTPUT_RGBA) && big_alloc((void**)&p->d_rgba, (size_t)p->R * p->W * p->max_pics * p->frame_bytes, kBigRgbaRing) != hipSuccess) {
-        const std::string what = "RGBA ring of " + std::to_string((size_t)p->R * p->W * p->max_pics * p->frame_bytes >> 20) + " MiB (windows_in_flight " +
-                                 std::to_string(p->R) + " x gops_per_window " + std::to_string(p->W) + " x max_gop_pictures " + std::to_string(p->max_pics) +
-                                 " x " + std::to_string(p->frame_bytes) + " bytes per frame)";
-        return bail(LEON_ERR_NOMEM, what.c_str());
-    }
+    if (rc == LEON_OK) rc = leon_set_quant_matrices(p->dec, p->vinfo.intra_qm, p->vinfo.non_intra_qm);
+    if (rc != LEON_OK) return rc;
+    if (hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking) != hipSuccess) return hip_fail(LEON_ERR_HIP, "copy stream");
+    if ((p->output & LEON_PIPELINE_OUTPUT_YCBCR) && (rc = alloc_ring(p, &p->d_planes, p->planes_bytes, "planes")) != LEON_OK) return rc;
+    if ((p->output & LEON_PIPELINE_OUTPUT_RGBA) && (rc = alloc_ring(p, &p->d_rgba, p->frame_bytes, "RGBA")) != LEON_OK) return rc;
     p->ring_owner.assign((size_t)p->R, -1);
     if (p->gpu_parser) {
-        // the front end's tables in the order the kernels copy them to LDS (leon_vlc_gpu.h)
         std::vector<leon_vlc_gpu_tables> src(1);
         std::vector<leon::VlcTables> t(1);
         leon_vlc_get_gpu_tables(src.data());
-        // 16 bits per entry for the part that lives in LDS: fast12 as {length:4, end of block:1, run:5, level:6},
-        // the others as (length << 8) | value
-        for (int i = 0; i < 4096; i++) {
-            const uint32_t f = src[0].fast12[i];
-            const int len = (int)(f & 0x7f), run = (int)((f >> 8) & 0xff), level = (int)(int16_t)(f >> 16);
-            if (len > 15 || run > 31 || level < -32 || level > 31) { leon_pipeline_destroy(p); return fail(LEON_ERR_INVALID, "coefficient table does not fit 16 bits"); }
-            t[0].fast12[i] = (uint16_t)(len | ((f & 0x80u) ? 0x10 : 0) | (run << 5) | ((level & 63) << 10));
-        }
-        // multi12: every symbol that lies complete in the next 12 bits, taken together (a prefix code is decided by its own
-        // bits: the entry of the pattern shifted up, whatever follows, names the symbol if its length fits what is left)
-        for (int i = 0; i < leon::kVlcMulti; i++) {
-            const int B = leon::kVlcMultiBits;
-            int pos = 0, nsym = 0, adv = 0, eob = 0;
-            while (pos < B) {
-                // the 12 bits from `pos` on, zeros behind the pattern's end
-                const uint32_t f = src[0].fast12[(((uint32_t)i << pos) & (uint32_t)(leon::kVlcMulti - 1)) << 12 >> B];
-                const int len = (int)(f & 0x7f);
-                if (len == 0 || len > B - pos) break;
-                pos += len;
-                if (f & 0x80u) { eob = 1; break; }
-                nsym++;
-                adv += (int)((f >> 8) & 0xff) + 1;
-            }
-            if (pos > 15 || nsym > 7 || adv > 255) { leon_pipeline_destroy(p); return fail(LEON_ERR_INVALID, "multi-symbol table does not fit 16 bits"); }
-            t[0].multi12[i] = (uint16_t)(pos | (nsym << 4) | (eob << 7) | (adv << 8));
-        }
-        auto pack = [](int32_t e) { return (uint16_t)(((e >> 16) << 8) | (e & 0xff)); };
-        for (int i = 0; i < 2048; i++) { t[0].motion_s[i] = pack(src[0].motion_s[i]); t[0].mba[i] = pack(src[0].mba[i]); }
-        for (int i = 0; i < 512; i++) t[0].cbp[i] = pack(src[0].cbp[i]);
-        for (int k = 0; k < 4; k++) for (int i = 0; i < 64; i++) t[0].mbtype[k][i] = pack(src[0].mbtype[k][i]);
-        for (int i = 0; i < 128; i++) t[0].dc_lum[i] = pack(src[0].dc_lum[i]);
-        for (int i = 0; i < 256; i++) t[0].dc_chr[i] = pack(src[0].dc_chr[i]);
-        for (int i = 0; i < 64; i++) t[0].zz_off[i] = src[0].zz_off[i];
-        // the codes of 12 .. 16 bits start with seven zeros: by the nine bits behind them (= the first 512 entries of the
-        // 16-bit table)
-        for (int i = 0; i < 512; i++) {
-            const int32_t e = src[0].coef16[i];
-            const int len = e >> 16, cf = e & 0xffff, run = cf >> 8, level = cf & 0xff;
-            if (e == 0) { t[0].long9[i] = 0; continue; }
-            if (cf == 0xffff || len < 8 || len > 16 || run > 31 || level > 63 || level == 0) { leon_pipeline_destroy(p); return fail(LEON_ERR_INVALID, "long coefficient code does not fit 16 bits"); }
-            t[0].long9[i] = (uint16_t)(len | (run << 5) | (level << 10));
-        }
+        const std::string bad = pack_vlc_tables(src[0], t[0]);
+        if (!bad.empty()) return fail(LEON_ERR_INVALID, "%s", bad.c_str());
         // The parser kernels want little of the chip (a quarter of the issue slots of the SIMDs they sit on) but all of it
         // for as long as their longest slice takes; the reconstruction launches beside them fill every CU.  Highest
         // stream priority: a freed slot goes to a waiting parser workgroup first.
         int prio_lo = 0, prio_hi = 0;
         hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
         for (hipStream_t& vs : p->vlc_stream)
-            if (hipStreamCreateWithPriority(&vs, hipStreamNonBlocking, prio_hi) != hipSuccess) return bail(LEON_ERR_HIP, "parser stream");
-        if (hipMalloc((void**)&p->d_vlc_tables, sizeof(leon::VlcTables)) != hipSuccess) return bail(LEON_ERR_NOMEM, "GPU parser tables");
-        if (hipMemcpy(p->d_vlc_tables, t.data(), sizeof(leon::VlcTables), hipMemcpyHostToDevice) != hipSuccess) return bail(LEON_ERR_HIP, "GPU parser tables");
-        p->vgeom.mbw = p->vinfo.mb_width; p->vgeom.mbh = p->vinfo.mb_height;
-        p->vgeom.gy = p->vinfo.groups_y; p->vgeom.gc = p->vinfo.groups_c;
-        p->vgeom.n_y = 2 * p->vinfo.mb_height * p->vinfo.groups_y;
-        p->vgeom.n_c = p->vinfo.mb_height * p->vinfo.groups_c;
-        p->vgeom.n_groups = p->vinfo.n_groups;
-        p->vgeom.alpha = p->vinfo.has_alpha == 1;
-        {   // a picture's maps, in the order scan_gop_for_gpu lays them out
-            const size_t mbs = (size_t)p->vinfo.mb_width * p->vinfo.mb_height;
-            const size_t mpad = pad256(mbs), vpad = pad256(mbs * 4);
-            p->vgeom.off_qscale = 0;
-            p->vgeom.off_intra = (uint32_t)mpad;
-            p->vgeom.off_repadd = (uint32_t)(2 * mpad);
-            p->vgeom.off_mb_dir = (uint32_t)(3 * mpad);
-            p->vgeom.off_mv_fwd = (uint32_t)(4 * mpad);
-            p->vgeom.off_mv_bwd = (uint32_t)(4 * mpad + vpad);
-        }
-        // k_vlc_index counts a picture's groups in LDS (one workgroup may have all 160 KiB of a CU)
-        p->vlc_index_lds = ((size_t)p->vinfo.n_groups + leon::kVlcIndexThreads) * 4;
-        if (p->vlc_index_lds > 160 * 1024 - 512) return bail(LEON_ERR_INVALID, "picture too large for the GPU parser (its group counters do not fit in LDS): use LEON_PIPELINE_PARSER_HOST or LEON_PIPELINE_PARSER_DEFAULT");
+            if (hipStreamCreateWithPriority(&vs, hipStreamNonBlocking, prio_hi) != hipSuccess) return hip_fail(LEON_ERR_HIP, "parser stream");
+        if (hipMalloc((void**)&p->d_vlc_tables, sizeof(leon::VlcTables)) != hipSuccess) return hip_fail(LEON_ERR_NOMEM, "GPU parser tables");
+        if (hipMemcpy(p->d_vlc_tables, t.data(), sizeof(leon::VlcTables), hipMemcpyHostToDevice) != hipSuccess) return hip_fail(LEON_ERR_HIP, "GPU parser tables");
+        if (p->vlc_index_lds > kMaxVlcIndexLds)
+            return hip_fail(LEON_ERR_INVALID, "picture too large for the GPU parser (its group counters do not fit in LDS): use LEON_PIPELINE_PARSER_HOST or LEON_PIPELINE_PARSER_DEFAULT");
         if (p->vlc_index_lds > 48 * 1024 &&
             hipFuncSetAttribute((const void*)leon::k_vlc_index, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->vlc_index_lds) != hipSuccess)
-            return bail(LEON_ERR_HIP, "LDS of the GPU parser's index kernel");
+            return hip_fail(LEON_ERR_HIP, "LDS of the GPU parser's index kernel");
         p->vlc_ring.resize((size_t)p->R);
     }
     const int n_arenas = p->W * (p->R + 1);
@@ -1321,20 +1343,17 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
     }
     if (p->gpu_parser) {
         // The arenas of the GPU parser come out of two slabs allocated HERE, sized for the largest GOP shard of the key
-        // map (what scan_gop_for_gpu will ask for, from its own bounds: 32 / 3 bytes of entry list per stream byte -- an entry
-        // takes three bits at least --, the maps, macroblock records and block records of max_gop_pictures pictures; round 3
-        // asked for 48 bytes per stream byte, 35 GB at W = 128 in 1080p, round 4's bounds come to 15 GB): allocated one by one at
-        // their first use -- and again when a larger GOP came by, hipFree waits for the device -- the first four windows of
-        // a 1080p run took 35-40 ms each instead of 8.6.  A GOP that still does not fit gets an allocation of its own
-        // (arena_reserve); without the memory for the slabs everything does.
+        // map by the bounds scan_gop_for_gpu sizes a GOP's arena with: vlc_entry_bound over the whole shard (32 / 3 bytes of
+        // entry list per stream byte -- an entry takes three bits at least), vlc_pic_bytes and the least entry list of
+        // max_gop_pictures pictures.  (Round 3 asked for 48 bytes per stream byte, 35 GB at W = 128 in 1080p.)  Allocated one
+        // by one at their first use -- and again when a larger GOP came by, hipFree waits for the device -- the first four
+        // windows of a 1080p run took 35-40 ms each instead of 8.6.  A GOP that does not fit all the same gets an allocation
+        // of its own (arena_reserve); without the memory for the slabs everything does.
         size_t largest = 0;
         for (uint64_t g : p->shard_gops) largest = std::max(largest, (size_t)(p->shard_end[g] - p->shard_begin[g]));
-        const size_t mbs = (size_t)p->vinfo.mb_width * p->vinfo.mb_height;
-        const size_t per_pic = pad256(mbs * leon::kVlcMbRecBytes) + 4 * pad256(mbs) + 2 * pad256(mbs * 4) + pad256(((size_t)p->vinfo.n_groups + 1) * 4) + 1024 +
-                               pad256(mbs * (size_t)leon::vlc_blocks_per_mb(p->vinfo.has_alpha == 1) * leon::kVlcRecWords * 4) +
-                               8 * (size_t)p->vinfo.mb_height * 4;      // (+ 2 entries per slice: one slice per macroblock row is the common case, more find room in the lists' slack)
         const size_t host_each = pad256(largest + 16) + 4096;
-        const size_t dev_each = (pad256(largest + 16) + 11 * largest + (size_t)p->max_pics * per_pic + 65535) / 65536 * 65536;
+        const size_t dev_each = (pad256(largest + 16) + 4 * vlc_entry_bound(largest) +
+                                 (size_t)p->max_pics * (vlc_pic_bytes(p).total + MapLayout::entries_pad(kVlcMinEntries)) + 65535) / 65536 * 65536;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)n_arenas * dev_each < free_b / 2 && !getenv("LEON_DEBUG_NO_SLABS")) {
             if (big_alloc((void**)&p->slab_dev, (size_t)n_arenas * dev_each, kBigArenas) == hipSuccess &&
@@ -1351,6 +1370,50 @@ int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t*
             }
         }
     }
+    return LEON_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int leon_pipeline_create(const leon_pipeline_config* cfg, const uint8_t* stream, size_t bytes,
+                         leon_pipeline_callback cb, void* user, leon_pipeline** out)
+{
+    return leon_pipeline_create_partial(cfg, stream, bytes, bytes, cb, user, out);
+}
+
+int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    if (valid_bytes > p->bytes) return fail(LEON_ERR_INVALID, "%zu bytes fed, the stream has %zu", valid_bytes, p->bytes);
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (valid_bytes > p->valid) p->valid = valid_bytes;
+    }
+    p->cv.notify_all();
+    return LEON_OK;
+}
+
+int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t* stream, size_t bytes, size_t valid_bytes,
+                                 leon_pipeline_callback cb, void* user, leon_pipeline** out)
+{
+    if (!cfg || !stream || bytes < 16 || !out) return fail(LEON_ERR_INVALID, "null argument");
+    if (valid_bytes > bytes) return fail(LEON_ERR_INVALID, "%zu valid bytes of a stream of %zu", valid_bytes, bytes);
+    *out = nullptr;
+    leon_pipeline* p = new (std::nothrow) leon_pipeline();
+    if (!p) return fail(LEON_ERR_NOMEM, "out of host memory");
+    int rc = plan_pipeline(p, cfg, stream, bytes, valid_bytes);
+    if (rc != LEON_OK) { delete p; return rc; }
+    p->cb = cb;
+    p->user = user;
+    rc = allocate_pipeline(p);
+    if (rc != LEON_OK) {          // (the message survives the teardown)
+        const std::string msg = g_err;
+        leon_pipeline_destroy(p);
+        return fail(rc, "%s", msg.c_str());
+    }
+    // stage 3: the threads
     p->t0 = Clock::now();
     for (int i = 0; i < p->K; i++) p->parsers.emplace_back(parser_main, p);
     p->submitter = std::thread(submit_main, p);
@@ -1408,7 +1471,6 @@ int leon_pipeline_seek(leon_pipeline* p, double seconds, int32_t mode, int64_t* 
         return fail(LEON_ERR_INVALID, "stream: %s", leon_vlc_last_error());
     const std::shared_ptr<PipeRun> run = make_run(p, st, seconds, 1);
     if (st) leon_vlc_close(st);
-    run->total_windows = (int64_t)((run->total_gops + p->W - 1) / p->W);
     // EXACT: the shard that owns the entry trims its first GOP (trim_to_target); the others decode from their next GOP on
     if (mode == LEON_PIPELINE_SEEK_EXACT && !run->mine.empty() && run->mine[0] == run->first_key) run->exact_ms = std::max(seconds, 0.0) * 1000.0;
     std::unique_lock<std::mutex> lk(p->mu);
