@@ -38,6 +38,14 @@ typedef struct leon_pipeline leon_pipeline;
 /* leon_pipeline_config.output: a bit set; 0 = RGBA */
 #define LEON_PIPELINE_OUTPUT_RGBA  1
 #define LEON_PIPELINE_OUTPUT_YCBCR 2
+/* Bit 4, not 2 or 3: create goes on refusing output = 4 and 8 (tests/test_pipeline_planes_gpu.py::test_refusals).  Written as a
+ * shift: the decimal defines of this family are the RGBA / YCBCR pair tests/test_pipeline_planes_abi.py compares with its binding. */
+#define LEON_PIPELINE_OUTPUT_TENSOR (1 << 4)
+
+/* element type of the tensor output (leon_pipeline_tensor_config.dtype) */
+#define LEON_TENSOR_F16  1
+#define LEON_TENSOR_BF16 2
+#define LEON_TENSOR_F32  3
 
 typedef struct leon_pipeline_config {
     int32_t device_id;
@@ -109,6 +117,26 @@ typedef struct leon_pipeline_frame {
  * kept); the device memory `rgba` points to stays valid until leon_pipeline_release_window(window).  A window
  * delivered with status != 0 (n_frames may be 0) holds its ring entry and staging like any other and must be
  * released too. */
+/* LEON_PIPELINE_OUTPUT_TENSOR: a frame as [3][frame_height][frame_width] elements -- planar R, G, B, dense (row stride = frame_width
+ * elements), fp16 / bf16 / fp32, each element a per-channel affine function of the 8-bit colour value:
+ *     tensor[c][y][x] = T[c][ rgba[y][x][c] ]        c = 0, 1, 2; rgba = the bytes an RGBA pipeline with display_flavour
+ *                                                    LEON_RGB_CPU_TWIN delivers for the frame (the A byte is not used)
+ *     T[c][v] = to_dtype( (float) ( (double)v * (double)scale[c] + (double)bias[c] ) )        v = 0 .. 255
+ * -- the double expression rounded once to binary32 (to nearest even), that value once to the element type (to nearest even;
+ * identity for fp32).  T is built on the host at create (leon_pipeline_tensor_table gives the same 768 values without a device)
+ * and looked up by one kernel per window (k_tensor) that reads the frame's YCbCr planes.  The tensor never depends on
+ * display_flavour (that field governs frame.rgba only); a yuva stream's alpha is not in it (ask for YCBCR beside it); an odd
+ * frame height leaves the last row at the CPU twin's fill value, T[c][255]; an odd frame width is refused at create.
+ * dtype: 0 = LEON_TENSOR_F16; scale and bias all zero = scale 1/255, bias 0 (values in [0, 1]).  Refused: another dtype, a
+ * non-finite scale or bias, a table entry that is not finite in the element type, a config with a dtype and without the bit.
+ * leon_pipeline_config and leon_pipeline_frame keep their layout (existing hosts and tests pin it): the tensor's settings travel in
+ * this struct of their own through leon_pipeline_create_tensor, the frames' tensor pointers through leon_pipeline_window_tensors.
+ * leon_pipeline_create / _create_partial with the TENSOR bit set take the defaults (fp16, [0, 1]). */
+typedef struct leon_pipeline_tensor_config {
+    int32_t dtype;              /* LEON_TENSOR_*; 0 = F16 */
+    float   scale[3], bias[3];  /* per channel R, G, B */
+} leon_pipeline_tensor_config;
+
 typedef void (*leon_pipeline_callback)(void* user, int64_t window, const leon_pipeline_frame* frames, int32_t n_frames, int32_t status);
 
 typedef struct leon_pipeline_info {
@@ -123,6 +151,11 @@ typedef struct leon_pipeline_info {
     int32_t output;             /* LEON_PIPELINE_OUTPUT_* bits in force (0 configured = RGBA) */
     int32_t chroma_width, chroma_height;   /* of Cb and Cr: (frame_width + 1) / 2, (frame_height + 1) / 2 */
     int32_t luma_stride, chroma_stride;    /* bytes per row of Y (and A), of Cb and Cr: the plane width rounded up to 64 */
+    /* LEON_PIPELINE_OUTPUT_TENSOR (all 0 without it): element type and size, 3 * frame_height * frame_width * element size, and the
+     * bytes between the tensors of consecutive display positions of one GOP and ring entry (= tensor_frame_bytes rounded up to 256)
+     * and between the GOP lanes of a window: a window whose GOPs are equally long is one strided [gops, pictures, 3, H, W] view */
+    int32_t tensor_dtype, tensor_element_bytes;
+    uint64_t tensor_frame_bytes, tensor_frame_pitch, tensor_gop_pitch;
 } leon_pipeline_info;
 
 typedef struct leon_pipeline_stats {
@@ -145,9 +178,15 @@ int leon_pipeline_create(const leon_pipeline_config* cfg, const uint8_t* stream,
  * arrived, windows are delivered as they complete.  With max_gop_pictures <= 0 a partial stream reserves 16 frames per GOP. */
 int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t* stream, size_t bytes, size_t valid_bytes,
                                  leon_pipeline_callback cb, void* user, leon_pipeline** out);
+/* leon_pipeline_create_partial with the tensor output's settings (valid_bytes = bytes: a complete stream); `tensor` NULL = the defaults */
+int leon_pipeline_create_tensor(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const uint8_t* stream, size_t bytes,
+                                size_t valid_bytes, leon_pipeline_callback cb, void* user, leon_pipeline** out);
+/* the table T (3 x 256 elements of the element type, [channel][value]) a pipeline created with these settings looks up: computed on
+ * the host, no device touched -- and refused as create refuses (cfg->output must have the TENSOR bit) */
+int leon_pipeline_tensor_table(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, void* out768);
 int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes);
 int leon_pipeline_get_info(leon_pipeline* p, leon_pipeline_info* out);
-/* the consumer is done with a window's frames: its ring entries (RGBA, planes) and staging may be reused */
+/* the consumer is done with a window's frames: its ring entries (RGBA, planes, tensors) and staging may be reused */
 int leon_pipeline_release_window(leon_pipeline* p, int64_t window);
 /* blocks until every window has been delivered and the final callback (window -1) has returned; returns the
  * first error.  Not to be called from inside the callback. */
@@ -177,6 +216,12 @@ int leon_pipeline_read_frame(leon_pipeline* p, const leon_pipeline_frame* f, uin
 /* the same for its planes, packed (row stride = plane width): y frame_width x frame_height, cb and cr chroma_width x chroma_height,
  * a (may be NULL; yuva streams) like y.  LEON_ERR_INVALID for a frame without planes */
 int leon_pipeline_read_frame_planes(leon_pipeline* p, const leon_pipeline_frame* f, uint8_t* y, uint8_t* cb, uint8_t* cr, uint8_t* a);
+/* the tensors of a delivered, not yet released window: out[i] = DEVICE pointer of frames[i]'s tensor (256-byte aligned, valid until the
+ * window is released, like rgba), n = the window's n_frames.  May be called from inside the callback.  LEON_ERR_INVALID for a
+ * pipeline without tensor output, a window that is not out for delivery, another n */
+int leon_pipeline_window_tensors(leon_pipeline* p, int64_t window, void** out, int32_t n);
+/* copy the tensor of frame `index` of such a window to host memory, packed (tensor_frame_bytes) */
+int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, void* host);
 const char* leon_pipeline_error(leon_pipeline* p);
 void leon_pipeline_destroy(leon_pipeline* p);
 

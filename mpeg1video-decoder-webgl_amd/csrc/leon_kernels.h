@@ -1588,6 +1588,152 @@ __global__ __launch_bounds__(kRgbaBlock) void k_rgba_gl(const uint8_t* __restric
     *reinterpret_cast<uint32_t*>(rgba + ((size_t)f * G.fw * G.fh + (size_t)yy * G.fw + x) * 4) = o;
 }
 
+// ---- the frames as planar float tensors (leon_pipeline.h, LEON_PIPELINE_OUTPUT_TENSOR) ------------------------
+// frame planes record (FrameOut layout) -> [3][fh][fw] elements R, G, B, dense: element = table[c][8-bit colour value], the colour
+// value from the fused display's integer tables (chroma_terms / rgba_px above -- the arithmetic is not restated), the table
+// (3 x 256 elements, built by the host: tensor_table_build) in LDS beside them.  One launch per window, blockIdx.z = frame:
+// frame_ids[z] is the frame's index in both rings.  Threads are numbered linearly through the frame (k_rgba_twin4: a row-shaped grid
+// leaves every eighth wave of a 1920-wide row half empty).  Fast path (fw % 8 == 0): a lane takes 8 pixels x 2 rows of 16-bit elements
+// -- one 8-byte Y load per row, 4 Cb + 4 Cr bytes for both -- or 4 pixels x 2 rows of fp32 (k_rgba_twin4's shape), so that per
+// channel and row a wave stores 64 x 16 B = 1 KB contiguous with ONE instruction.  (fp32 with 8 pixels per lane, two 16-byte stores
+// 32 bytes apart, every instruction writing half of each line it touches: 18.5 ms per 1536 1080p frames, 2.3 TB/s -- measured,
+// dropped.)  Other even widths: a lane takes one 2 x 2 quad, element stores.  The planes are read once
+// and the tensor is never read again here: both non-temporal.  An odd frame height leaves the last row at the CPU twin's fill
+// value 255 (its quad loop covers fh >> 1 row pairs): table[c][255].
+static constexpr int kTensorF16 = 1, kTensorBf16 = 2, kTensorF32 = 3;      // = LEON_TENSOR_*
+struct TensorGeom {
+    int32_t fw, fh;
+    uint32_t per_row, n_items;           // lanes per row pair (tensor_lane_px pixels each), lanes per frame ((fh + 1) / 2 row pairs)
+    uint32_t luma_stride, chroma_stride, cb_off, cr_off;      // FrameOut
+    uint32_t planes_pitch_lo, planes_pitch_hi, tensor_pitch_lo, tensor_pitch_hi;      // bytes between ring frames
+    int32_t fast;                        // fw % 8 == 0
+};
+template <int DTYPE> struct TensorElem { typedef uint16_t type; };
+template <> struct TensorElem<kTensorF32> { typedef uint32_t type; };
+// pixels per lane and row on the fast path: 16 bytes of elements
+constexpr int tensor_lane_px(int dtype) { return dtype == kTensorF32 ? 4 : 8; }
+
+// 8 pixels of one row: Y samples y8, the four chroma pairs' terms; `off` = the row's first element in a channel plane
+// the fp32 form: 4 pixels of one row, Y samples y4, two chroma pairs
+__device__ __forceinline__ void tensor_row4_f32(const char* lut, const uint32_t* tab, uint32_t y4, const ChromaTerms& c0, const ChromaTerms& c1, bool fill,
+                                                __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_elems, bool in, uint32_t two)
+{
+    const int opaque = 255 << kLutShift;
+    uint32_t px[4] = {rgba_px<0>(lut, y4, c0, opaque, two), rgba_px<1>(lut, y4, c0, opaque, two),
+                      rgba_px<2>(lut, y4, c1, opaque, two), rgba_px<3>(lut, y4, c1, opaque, two)};
+    if (fill) px[0] = px[1] = px[2] = px[3] = 0xffffffffu;
+    const uint32_t oob = in ? 0u : kOobBit;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        const v4u e = {tab[ch * 256 + ((px[0] >> (8 * ch)) & 255u)], tab[ch * 256 + ((px[1] >> (8 * ch)) & 255u)],
+                       tab[ch * 256 + ((px[2] >> (8 * ch)) & 255u)], tab[ch * 256 + ((px[3] >> (8 * ch)) & 255u)]};
+        __builtin_amdgcn_raw_buffer_store_b128(e, rs, (int)((((uint32_t)ch * plane_elems + off) * 4u) | oob), 0, kAuxFrameStore);
+    }
+}
+
+template <int DTYPE>
+__device__ __forceinline__ void tensor_row8(const char* lut, const typename TensorElem<DTYPE>::type* tab, v2u y8, const ChromaTerms (&c)[4], bool fill,
+                                            __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_elems, bool in, uint32_t two)
+{
+    const int opaque = 255 << kLutShift;
+    uint32_t px[8] = {rgba_px<0>(lut, y8.x, c[0], opaque, two), rgba_px<1>(lut, y8.x, c[0], opaque, two),
+                      rgba_px<2>(lut, y8.x, c[1], opaque, two), rgba_px<3>(lut, y8.x, c[1], opaque, two),
+                      rgba_px<0>(lut, y8.y, c[2], opaque, two), rgba_px<1>(lut, y8.y, c[2], opaque, two),
+                      rgba_px<2>(lut, y8.y, c[3], opaque, two), rgba_px<3>(lut, y8.y, c[3], opaque, two)};
+    if (fill) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) px[k] = 0xffffffffu;
+    }
+    const uint32_t oob = in ? 0u : kOobBit;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        uint32_t e[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) e[k] = tab[ch * 256 + ((px[k] >> (8 * ch)) & 255u)];
+        const uint32_t at = (uint32_t)ch * plane_elems + off;
+        __builtin_amdgcn_raw_buffer_store_b128(v4u{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)}, rs,
+                                               (int)((at * 2u) | oob), 0, kAuxFrameStore);
+    }
+}
+
+template <int DTYPE>
+__global__ __launch_bounds__(kRgbaBlock) void k_tensor(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
+                                                       const uint32_t* __restrict__ table, const Tables* __restrict__ T, TensorGeom G)
+{
+    typedef typename TensorElem<DTYPE>::type Elem;
+    __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
+    __shared__ __attribute__((aligned(16))) Elem tab_s[3 * 256];
+    {   // the conversion tables as k_recon_display loads them (1 KB chunks straight into LDS), the element table through registers
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const int lane0 = threadIdx.x & 63;
+        const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc((void*)T->rgba_lut, 0, kLdsLut, 0x00020000);
+        for (int c = wave; c < kLdsLut / 1024; c += kRgbaBlock / 64)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lut_s) + c * 1024), 16,
+                                                     (int)(lane0 * 16u), c * 1024, 0, 0);
+        constexpr int kDwords = 3 * 256 * (int)sizeof(Elem) / 4;
+        for (int i = threadIdx.x; i < kDwords; i += kRgbaBlock) reinterpret_cast<uint32_t*>(tab_s)[i] = table[i];
+        wait_vmem_all();
+        __syncthreads();
+    }
+    const uint32_t idx = blockIdx.x * (uint32_t)kRgbaBlock + threadIdx.x;
+    if (idx >= G.n_items) return;
+    const char* lut = reinterpret_cast<const char*>(lut_s);
+    const uint32_t pair = idx / G.per_row, col = idx - pair * G.per_row;
+    const uint32_t fid = frame_ids[blockIdx.z];
+    const uint8_t* src = planes_ring + (size_t)fid * (((size_t)G.planes_pitch_hi << 32) | G.planes_pitch_lo);
+    uint8_t* dst = tensor_ring + (size_t)fid * (((size_t)G.tensor_pitch_hi << 32) | G.tensor_pitch_lo);
+    const uint32_t r0 = 2u * pair, fw = (uint32_t)G.fw, fh = (uint32_t)G.fh;
+    const bool has_r1 = r0 + 1u < fh;                    // false: the last row of an odd height, left at 255 by the twin
+    const uint32_t plane_elems = fw * fh;
+    uint32_t two = 2u, three = 3u;                       // SDWA shift counts live in registers (display_half)
+    asm("" : "+v"(two), "+v"(three));
+    const uint8_t* yrow = src + (size_t)r0 * G.luma_stride;
+    const uint8_t* cbrow = src + G.cb_off + (size_t)pair * G.chroma_stride;
+    const uint8_t* crrow = src + G.cr_off + (size_t)pair * G.chroma_stride;
+    if (G.fast) {
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(dst);
+        if constexpr (DTYPE == kTensorF32) {
+            const uint32_t y0 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(yrow + 4u * col));
+            const uint32_t y1 = has_r1 ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(yrow + G.luma_stride + 4u * col)) : 0u;
+            const uint32_t cb2 = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(cbrow + 2u * col));
+            const uint32_t cr2 = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(crrow + 2u * col));
+            const ChromaTerms c0 = chroma_terms<0>(lut, cb2, cr2, three), c1 = chroma_terms<1>(lut, cb2, cr2, three);
+            const uint32_t off = r0 * fw + 4u * col;
+            tensor_row4_f32(lut, tab_s, y0, c0, c1, !has_r1, rs, off, plane_elems, true, two);
+            tensor_row4_f32(lut, tab_s, y1, c0, c1, false, rs, off + fw, plane_elems, has_r1, two);
+        } else {
+            const v2u y0 = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(yrow + 8u * col));
+            const v2u y1 = has_r1 ? __builtin_nontemporal_load(reinterpret_cast<const v2u*>(yrow + G.luma_stride + 8u * col)) : v2u{0u, 0u};
+            const uint32_t cb4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(cbrow + 4u * col));
+            const uint32_t cr4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(crrow + 4u * col));
+            const ChromaTerms c[4] = {chroma_terms<0>(lut, cb4, cr4, three), chroma_terms<1>(lut, cb4, cr4, three),
+                                      chroma_terms<2>(lut, cb4, cr4, three), chroma_terms<3>(lut, cb4, cr4, three)};
+            const uint32_t off = r0 * fw + 8u * col;
+            tensor_row8<DTYPE>(lut, tab_s, y0, c, !has_r1, rs, off, plane_elems, true, two);
+            tensor_row8<DTYPE>(lut, tab_s, y1, c, false, rs, off + fw, plane_elems, has_r1, two);
+        }
+    } else {
+        const uint32_t y0 = *reinterpret_cast<const uint16_t*>(yrow + 2u * col);
+        const uint32_t y1 = has_r1 ? *reinterpret_cast<const uint16_t*>(yrow + G.luma_stride + 2u * col) : 0u;
+        const ChromaTerms c0 = chroma_terms<0>(lut, (uint32_t)cbrow[col], (uint32_t)crrow[col], three);
+        const int opaque = 255 << kLutShift;
+        uint32_t px[4] = {rgba_px<0>(lut, y0, c0, opaque, two), rgba_px<1>(lut, y0, c0, opaque, two),
+                          rgba_px<0>(lut, y1, c0, opaque, two), rgba_px<1>(lut, y1, c0, opaque, two)};
+        if (!has_r1) px[0] = px[1] = 0xffffffffu;
+        Elem* out = reinterpret_cast<Elem*>(dst);
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            Elem* o = out + (size_t)ch * plane_elems + (size_t)r0 * fw + 2u * col;
+            __builtin_nontemporal_store(tab_s[ch * 256 + ((px[0] >> (8 * ch)) & 255u)], o);
+            __builtin_nontemporal_store(tab_s[ch * 256 + ((px[1] >> (8 * ch)) & 255u)], o + 1);
+            if (has_r1) {
+                __builtin_nontemporal_store(tab_s[ch * 256 + ((px[2] >> (8 * ch)) & 255u)], o + fw);
+                __builtin_nontemporal_store(tab_s[ch * 256 + ((px[3] >> (8 * ch)) & 255u)], o + fw + 1);
+            }
+        }
+    }
+}
+
 // ---- measured HBM roofline -----------------------------------------------------------
 // One 16-byte element per thread, no loop: the fastest of the copy shapes probed on MI355X
 // (tools/probe/bw_probe.cpp: 6.3 TB/s vs 4.8-5.9 TB/s for grid-stride forms).

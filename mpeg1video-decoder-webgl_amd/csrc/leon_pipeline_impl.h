@@ -72,6 +72,8 @@ struct PipeWindow {
     int ring = 0;
     std::vector<GopJob*> jobs;
     std::vector<leon_pipeline_frame> frames;
+    std::vector<uint8_t*> tensors;       // output TENSOR: frames[i]'s tensor
+    std::vector<uint32_t> frame_ids;     // ... and its index in the ring entry's lanes (what k_tensor finds planes and tensor by)
     hipEvent_t done = nullptr;
     int status = LEON_OK;
     uint32_t n_vpics = 0;        // gpu_parser: error words of the window's pictures are in the ring entry's h_err
@@ -116,7 +118,16 @@ struct leon_pipeline {
     leon_decoder* dec = nullptr;
     hipStream_t copy_stream = nullptr;
     uint8_t* d_rgba = nullptr;                        // R ring entries of W * max_pics frames (output RGBA)
-    uint8_t* d_planes = nullptr;                      // the same for the frames' planes records (output YCbCr)
+    uint8_t* d_planes = nullptr;                      // the same for the frames' planes records (output YCbCr, and what the tensors are made from)
+    // output TENSOR: the ring of [3][fh][fw] tensors (tensor_pitch apart), the element table T (host, device), and per ring entry
+    // the frame indices of its window for k_tensor (pinned, device)
+    uint8_t* d_tensor = nullptr;
+    int tensor_dtype = 0;
+    size_t tensor_elem = 0, tensor_bytes = 0, tensor_pitch = 0;
+    std::vector<uint8_t> tensor_table;
+    uint32_t* d_tensor_table = nullptr;
+    uint32_t* h_tensor_ids = nullptr;
+    uint32_t* d_tensor_ids = nullptr;
     bool gpu_parser = false;
     // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
     // window n + 2, on a second stream: a parse launch lasts as long as its longest slice (one lane, symbol after symbol) and
@@ -439,11 +450,76 @@ double frame_ts_ms(const leon_pipeline* p, const GopJob* job, int display_index)
 
 // a frame's RGBA and planes record in the output rings (null: that output is off): ring entry, lane (GOP of the window),
 // display index
-struct FrameAddr { uint8_t* rgba; uint8_t* planes; };
+struct FrameAddr { uint8_t* rgba; uint8_t* planes; uint8_t* tensor; size_t index; };
 FrameAddr frame_addr(const leon_pipeline* p, int ring, size_t lane, size_t k)
 {
     const size_t i = ((size_t)ring * p->W + lane) * p->max_pics + k;
-    return {p->d_rgba ? p->d_rgba + i * p->frame_bytes : nullptr, p->d_planes ? p->d_planes + i * p->planes_bytes : nullptr};
+    return {p->d_rgba ? p->d_rgba + i * p->frame_bytes : nullptr, p->d_planes ? p->d_planes + i * p->planes_bytes : nullptr,
+            p->d_tensor ? p->d_tensor + i * p->tensor_pitch : nullptr, i};
+}
+
+// ---- output TENSOR: the element table (the definition of include/leon_pipeline.h) ------------------------
+
+// binary32 -> binary16 / bfloat16 bits, round to nearest even (finite input)
+uint16_t f32_to_f16_bits(float f)
+{
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7fffffffu;
+    if (x >= 0x47800000u) return (uint16_t)(sign | 0x7c00u);          // 65536 and beyond (65520 .. 65536 round up below)
+    if (x < 0x38800000u) {                                             // below 2^-14: a subnormal half -- the adder rounds at 2^-24
+        float a;
+        memcpy(&a, &x, 4);
+        a += 0.5f;
+        uint32_t y;
+        memcpy(&y, &a, 4);
+        return (uint16_t)(sign | (y - 0x3f000000u));
+    }
+    const uint32_t r = x - 0x38000000u;                                // exponent rebased from 127 to 15
+    return (uint16_t)(sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13));
+}
+uint16_t f32_to_bf16_bits(float f)
+{
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    return (uint16_t)((x + 0x7fffu + ((x >> 16) & 1u)) >> 16);
+}
+
+// What create and leon_pipeline_tensor_table make of the settings: the element type, scale and bias with the defaults resolved,
+// and T itself (3 x 256 elements) into `out` (may be null).  Every refusal of the header is here.
+int tensor_table_build(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tc, int* dtype_out, void* out)
+{
+    const bool bit = (cfg->output & LEON_PIPELINE_OUTPUT_TENSOR) != 0;
+    if (!bit) return fail(LEON_ERR_INVALID, "tensor settings (dtype %d) without LEON_PIPELINE_OUTPUT_TENSOR in output %d", tc ? tc->dtype : 0, cfg->output);
+    const int dtype = tc && tc->dtype ? tc->dtype : LEON_TENSOR_F16;
+    if (dtype != LEON_TENSOR_F16 && dtype != LEON_TENSOR_BF16 && dtype != LEON_TENSOR_F32) return fail(LEON_ERR_INVALID, "tensor dtype %d", dtype);
+    float scale[3] = {0, 0, 0}, bias[3] = {0, 0, 0};
+    bool all_zero = true;
+    for (int c = 0; c < 3 && tc; c++) {
+        scale[c] = tc->scale[c];
+        bias[c] = tc->bias[c];
+        if (!std::isfinite(scale[c]) || !std::isfinite(bias[c])) return fail(LEON_ERR_INVALID, "tensor scale / bias of channel %d is not finite", c);
+        all_zero = all_zero && scale[c] == 0.0f && bias[c] == 0.0f;
+    }
+    if (all_zero)
+        for (int c = 0; c < 3; c++) scale[c] = (float)(1.0 / 255.0);
+    for (int c = 0; c < 3; c++)
+        for (int v = 0; v < 256; v++) {
+            const float f = (float)((double)v * (double)scale[c] + (double)bias[c]);
+            const int i = c * 256 + v;
+            bool finite = std::isfinite(f);
+            if (dtype == LEON_TENSOR_F32) {
+                if (out) memcpy((char*)out + 4 * i, &f, 4);
+            } else if (finite) {
+                const uint16_t h = dtype == LEON_TENSOR_F16 ? f32_to_f16_bits(f) : f32_to_bf16_bits(f);
+                finite = dtype == LEON_TENSOR_F16 ? (h & 0x7c00u) != 0x7c00u : (h & 0x7f80u) != 0x7f80u;
+                if (out) memcpy((char*)out + 2 * i, &h, 2);
+            }
+            if (!finite) return fail(LEON_ERR_INVALID, "tensor table: value %d of channel %d is not finite in the element type (dtype %d)", v, c, dtype);
+        }
+    if (dtype_out) *dtype_out = dtype;
+    return LEON_OK;
 }
 
 // LEON_PIPELINE_SEEK_EXACT: the first GOP of the run delivers its frames from the one on screen at t_ms on (the largest
@@ -825,6 +901,8 @@ int launch_level(leon_pipeline* p, const PipeWindow* w, const std::vector<LevelP
 void list_frames(leon_pipeline* p, PipeWindow* w)
 {
     w->frames.clear();
+    w->tensors.clear();
+    w->frame_ids.clear();
     for (size_t j = 0; j < w->jobs.size(); j++) {
         const GopJob* job = w->jobs[j];
         // by temporal reference: a GOP cut short by the encoder may skip display positions
@@ -839,7 +917,11 @@ void list_frames(leon_pipeline* p, PipeWindow* w)
             f.type = by_disp[k]->type;
             f.ts_ms = frame_ts_ms(p, job, (int)k);
             f.rgba = a.rgba;
-            if (a.planes) {
+            if (a.tensor) {
+                w->tensors.push_back(a.tensor);
+                w->frame_ids.push_back((uint32_t)(a.index - (size_t)w->ring * p->W * p->max_pics));
+            }
+            if (a.planes && (p->output & LEON_PIPELINE_OUTPUT_YCBCR)) {
                 f.y = a.planes;
                 f.cb = a.planes + p->planes_geom.cb_off;
                 f.cr = a.planes + p->planes_geom.cr_off;
@@ -850,6 +932,43 @@ void list_frames(leon_pipeline* p, PipeWindow* w)
         p->st_pictures += job->pics.size();
     }
     p->st_gops += w->jobs.size();
+}
+
+// output TENSOR: the window's frames -> their tensors, one k_tensor launch on the decoder's stream behind the last level (at most
+// 65535 frames per launch: blockIdx.z).  Pictures decoded for prediction only (EXACT seek) are not among the frames.
+template <int DTYPE>
+void launch_k_tensor(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::TensorGeom& G)
+{
+    hipLaunchKernelGGL(leon::k_tensor<DTYPE>, dim3((G.n_items + leon::kRgbaBlock - 1) / leon::kRgbaBlock, 1, n), dim3(leon::kRgbaBlock), 0, p->dec->stream,
+                       (const uint8_t*)p->d_planes, p->d_tensor, ids, (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, G);
+}
+int launch_tensors(leon_pipeline* p, const PipeWindow* w)
+{
+    const size_t n = w->frame_ids.size();
+    if (!p->d_tensor || !n) return LEON_OK;
+    const size_t entry = (size_t)p->W * p->max_pics;
+    uint32_t* h = p->h_tensor_ids + (size_t)w->ring * entry;       // the ring entry is this window's: its previous launch has finished
+    uint32_t* dv = p->d_tensor_ids + (size_t)w->ring * entry;
+    for (size_t i = 0; i < n; i++) h[i] = (uint32_t)((size_t)w->ring * entry) + w->frame_ids[i];
+    HIP_TRY(hipMemcpyAsync(dv, h, n * 4, hipMemcpyHostToDevice, p->dec->stream));
+    leon::TensorGeom G{};
+    G.fw = p->vinfo.frame_width; G.fh = p->vinfo.frame_height;
+    G.fast = (G.fw & 7) == 0;
+    G.per_row = (uint32_t)(G.fast ? G.fw / leon::tensor_lane_px(p->tensor_dtype) : G.fw / 2);
+    G.n_items = G.per_row * (uint32_t)((G.fh + 1) / 2);
+    G.luma_stride = p->planes_geom.luma_stride; G.chroma_stride = p->planes_geom.chroma_stride;
+    G.cb_off = p->planes_geom.cb_off; G.cr_off = p->planes_geom.cr_off;
+    G.planes_pitch_lo = (uint32_t)(p->planes_bytes & 0xffffffffu); G.planes_pitch_hi = (uint32_t)((uint64_t)p->planes_bytes >> 32);
+    G.tensor_pitch_lo = (uint32_t)(p->tensor_pitch & 0xffffffffu); G.tensor_pitch_hi = (uint32_t)((uint64_t)p->tensor_pitch >> 32);
+    if (!G.n_items) return LEON_OK;
+    for (size_t at = 0; at < n; at += 65535) {
+        const unsigned m = (unsigned)std::min<size_t>(65535, n - at);
+        if (p->tensor_dtype == LEON_TENSOR_F16) launch_k_tensor<leon::kTensorF16>(p, dv + at, m, G);
+        else if (p->tensor_dtype == LEON_TENSOR_BF16) launch_k_tensor<leon::kTensorBf16>(p, dv + at, m, G);
+        else launch_k_tensor<leon::kTensorF32>(p, dv + at, m, G);
+    }
+    HIP_TRY(hipGetLastError());
+    return LEON_OK;
 }
 
 // one window: its levels planned, its arenas uploaded (and parsed on the GPU), its levels launched, its frames listed
@@ -882,9 +1001,10 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
     }
     if (!cdir.empty())
         for (size_t j = 0; j < w->jobs.size(); j++) capture_file(cdir + "/arena_" + std::to_string(j) + ".bin", w->jobs[j]->arena->dev, w->jobs[j]->arena->used);
+    list_frames(p, w);
+    if ((rc = launch_tensors(p, w)) != LEON_OK) return rc;
     if (serial) HIP_TRY(hipStreamSynchronize(p->dec->stream));
     HIP_TRY(hipEventRecord(w->done, p->dec->stream));
-    list_frames(p, w);
     return LEON_OK;
 }
 
@@ -1109,7 +1229,7 @@ constexpr size_t kMaxVlcIndexLds = 160 * 1024 - 512;
 
 // Create, stage 1: what the config and the stream decide -- the shards, the run, W / R / K, the longest GOP, the front
 // end, the output and its roads, info.  No HIP call and no allocation: a refused config leaves nothing to free but p.
-int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const uint8_t* stream, size_t bytes, size_t valid_bytes)
+int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tcfg, const uint8_t* stream, size_t bytes, size_t valid_bytes)
 {
     leon_vlc_stream* st = nullptr;
     // the container header, the key map and the first sequence header must have arrived
@@ -1199,7 +1319,23 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const uint8
     // writes its planes, and one leon_convert_rgba per picture (the generic k_rgba_twin) fills the window's frames.
     // The GL flavour (the reference's live display arithmetic, fp32) exists as a launch of its own only: the same road.
     if (cfg->display_flavour != LEON_RGB_CPU_TWIN && cfg->display_flavour != LEON_RGB_GL) return fail(LEON_ERR_INVALID, "display_flavour %d", cfg->display_flavour);
-    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR)) return fail(LEON_ERR_INVALID, "output %d", cfg->output);
+    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR)) return fail(LEON_ERR_INVALID, "output %d", cfg->output);
+    if (cfg->output & LEON_PIPELINE_OUTPUT_TENSOR) {
+        // the tensor is defined through the CPU twin's RGBA, whose index drifts over an odd width (k_rgba_twin): refused, as yuva is
+        if (p->vinfo.frame_width & 1) return fail(LEON_ERR_INVALID, "the tensor output needs an even frame_width (it is %d)", p->vinfo.frame_width);
+        p->tensor_table.resize(3 * 256 * 4);
+        const int rc = tensor_table_build(cfg, tcfg, &p->tensor_dtype, p->tensor_table.data());
+        if (rc != LEON_OK) return rc;
+        p->tensor_elem = p->tensor_dtype == LEON_TENSOR_F32 ? 4 : 2;
+        p->tensor_table.resize(3 * 256 * p->tensor_elem);
+        p->tensor_bytes = (size_t)3 * p->vinfo.frame_height * p->vinfo.frame_width * p->tensor_elem;
+        p->tensor_pitch = pad256(p->tensor_bytes);
+        p->info.tensor_dtype = p->tensor_dtype;
+        p->info.tensor_element_bytes = (int32_t)p->tensor_elem;
+        p->info.tensor_frame_bytes = p->tensor_bytes;
+        p->info.tensor_frame_pitch = p->tensor_pitch;
+        p->info.tensor_gop_pitch = (uint64_t)p->tensor_pitch * (uint64_t)p->max_pics;
+    } else if (tcfg && tcfg->dtype) return fail(LEON_ERR_INVALID, "tensor dtype %d without LEON_PIPELINE_OUTPUT_TENSOR in output", tcfg->dtype);
     // the frames' planes (output YCbCr): the layout of include/leon_pipeline.h, one record per frame, A behind Cr for yuva
     p->output = cfg->output ? cfg->output : LEON_PIPELINE_OUTPUT_RGBA;
     p->planes_geom = planes_layout(p->vinfo.frame_width, p->vinfo.frame_height, &p->planes_bytes);
@@ -1310,7 +1446,16 @@ int allocate_pipeline(leon_pipeline* p)
     if (rc == LEON_OK) rc = leon_set_quant_matrices(p->dec, p->vinfo.intra_qm, p->vinfo.non_intra_qm);
     if (rc != LEON_OK) return rc;
     if (hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking) != hipSuccess) return hip_fail(LEON_ERR_HIP, "copy stream");
-    if ((p->output & LEON_PIPELINE_OUTPUT_YCBCR) && (rc = alloc_ring(p, &p->d_planes, p->planes_bytes, "planes")) != LEON_OK) return rc;
+    // (the tensors are made from the frames' planes: TENSOR runs the YCbCr road inside whether or not the planes are handed out)
+    if ((p->output & (LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR)) && (rc = alloc_ring(p, &p->d_planes, p->planes_bytes, "planes")) != LEON_OK) return rc;
+    if (p->output & LEON_PIPELINE_OUTPUT_TENSOR) {
+        if ((rc = alloc_ring(p, &p->d_tensor, p->tensor_pitch, "tensor")) != LEON_OK) return rc;
+        const size_t ids = (size_t)p->R * p->W * p->max_pics * 4;
+        if (hipMalloc((void**)&p->d_tensor_table, p->tensor_table.size()) != hipSuccess || hipMalloc((void**)&p->d_tensor_ids, ids) != hipSuccess ||
+            hipHostMalloc((void**)&p->h_tensor_ids, ids, hipHostMallocDefault) != hipSuccess)
+            return hip_fail(LEON_ERR_NOMEM, "tensor table and frame index ring");
+        if (hipMemcpy(p->d_tensor_table, p->tensor_table.data(), p->tensor_table.size(), hipMemcpyHostToDevice) != hipSuccess) return hip_fail(LEON_ERR_HIP, "tensor table");
+    }
     if ((p->output & LEON_PIPELINE_OUTPUT_RGBA) && (rc = alloc_ring(p, &p->d_rgba, p->frame_bytes, "RGBA")) != LEON_OK) return rc;
     p->ring_owner.assign((size_t)p->R, -1);
     if (p->gpu_parser) {
@@ -1380,7 +1525,19 @@ extern "C" {
 int leon_pipeline_create(const leon_pipeline_config* cfg, const uint8_t* stream, size_t bytes,
                          leon_pipeline_callback cb, void* user, leon_pipeline** out)
 {
-    return leon_pipeline_create_partial(cfg, stream, bytes, bytes, cb, user, out);
+    return leon_pipeline_create_tensor(cfg, nullptr, stream, bytes, bytes, cb, user, out);
+}
+
+int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t* stream, size_t bytes, size_t valid_bytes,
+                                 leon_pipeline_callback cb, void* user, leon_pipeline** out)
+{
+    return leon_pipeline_create_tensor(cfg, nullptr, stream, bytes, valid_bytes, cb, user, out);
+}
+
+int leon_pipeline_tensor_table(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, void* out768)
+{
+    if (!cfg || !out768) return fail(LEON_ERR_INVALID, "null argument");
+    return tensor_table_build(cfg, tensor, nullptr, out768);
 }
 
 int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes)
@@ -1395,15 +1552,15 @@ int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes)
     return LEON_OK;
 }
 
-int leon_pipeline_create_partial(const leon_pipeline_config* cfg, const uint8_t* stream, size_t bytes, size_t valid_bytes,
-                                 leon_pipeline_callback cb, void* user, leon_pipeline** out)
+int leon_pipeline_create_tensor(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const uint8_t* stream, size_t bytes,
+                                size_t valid_bytes, leon_pipeline_callback cb, void* user, leon_pipeline** out)
 {
     if (!cfg || !stream || bytes < 16 || !out) return fail(LEON_ERR_INVALID, "null argument");
     if (valid_bytes > bytes) return fail(LEON_ERR_INVALID, "%zu valid bytes of a stream of %zu", valid_bytes, bytes);
     *out = nullptr;
     leon_pipeline* p = new (std::nothrow) leon_pipeline();
     if (!p) return fail(LEON_ERR_NOMEM, "out of host memory");
-    int rc = plan_pipeline(p, cfg, stream, bytes, valid_bytes);
+    int rc = plan_pipeline(p, cfg, tensor, stream, bytes, valid_bytes);
     if (rc != LEON_OK) { delete p; return rc; }
     p->cb = cb;
     p->user = user;
@@ -1533,6 +1690,36 @@ int leon_pipeline_read_frame_planes(leon_pipeline* p, const leon_pipeline_frame*
     return LEON_OK;
 }
 
+int leon_pipeline_window_tensors(leon_pipeline* p, int64_t window, void** out, int32_t n)
+{
+    if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    if (!p->d_tensor) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    std::lock_guard<std::mutex> lk(p->mu);
+    auto it = p->delivered.find(window);
+    if (it == p->delivered.end()) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    const PipeWindow* w = it->second;
+    if (n < 0 || (size_t)n != w->tensors.size()) return fail(LEON_ERR_INVALID, "window %lld has %zu tensors, not %d", (long long)window, w->tensors.size(), n);
+    for (size_t i = 0; i < w->tensors.size(); i++) out[i] = w->tensors[i];
+    return LEON_OK;
+}
+
+int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, void* host)
+{
+    if (!p || !host) return fail(LEON_ERR_INVALID, "null argument");
+    if (!p->d_tensor) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    const uint8_t* src = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        auto it = p->delivered.find(window);
+        if (it == p->delivered.end()) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+        if (index < 0 || (size_t)index >= it->second->tensors.size()) return fail(LEON_ERR_INVALID, "window %lld has no frame %d", (long long)window, index);
+        src = it->second->tensors[(size_t)index];
+    }
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    HIP_TRY(hipMemcpy(host, src, p->tensor_bytes, hipMemcpyDeviceToHost));
+    return LEON_OK;
+}
+
 const char* leon_pipeline_error(leon_pipeline* p)
 {
     if (!p) return "";
@@ -1594,6 +1781,10 @@ void leon_pipeline_destroy(leon_pipeline* p)
         if (vs) hipStreamDestroy(vs);
     if (p->d_rgba) big_free(p->d_rgba);
     if (p->d_planes) big_free(p->d_planes);
+    if (p->d_tensor) big_free(p->d_tensor);
+    if (p->d_tensor_table) hipFree(p->d_tensor_table);
+    if (p->d_tensor_ids) hipFree(p->d_tensor_ids);
+    if (p->h_tensor_ids) hipHostFree(p->h_tensor_ids);
     if (p->copy_stream) hipStreamDestroy(p->copy_stream);
     if (p->dec) leon_destroy(p->dec);
     delete p;

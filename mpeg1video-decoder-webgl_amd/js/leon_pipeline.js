@@ -23,6 +23,12 @@
  *   p.readPlanes(window, index) -> {y, cb, cr[, a]} packed Uint8Arrays: the frame's YCbCr 4:2:0 planes, with
  *                                  opts.output 'ycbcr' (no RGBA at all) or 'both' -- the reference's frame payload
  *                                  {ybr: [Y, Cb, Cr]} (decoders/jsv.js:600, :673); default 'rgba'
+ *   p.readTensor(window, index) -> Uint16Array (fp16 / bf16 bit patterns) or Float32Array, [3][H][W] packed: the frame as a planar,
+ *                                  normalised R, G, B tensor for a model, with opts.output 'tensor' (no RGBA at all),
+ *                                  'rgba+tensor', 'ycbcr+tensor' or 'all'; opts.tensorDtype 'float16' (default) / 'bfloat16' /
+ *                                  'float32', opts.tensorScale / tensorBias [r, g, b] (default 1/255 and 0: values in [0, 1]);
+ *                                  element = to_dtype(float32(v * scale[c] + bias[c])) of the CPU-twin colour value v;
+ *                                  stats() reports tensorDtype, tensorElementBytes, tensorFrameBytes, tensorFramePitch, tensorGopPitch
  *   p.releaseWindow(window); p.stats(); p.destroy();
  */
 const path = require('path');
@@ -36,13 +42,19 @@ class LeonPipeline extends EventEmitter {
     if (!Buffer.isBuffer(stream)) stream = Buffer.from(stream.buffer, stream.byteOffset, stream.byteLength);
     this.autoRelease = opts.autoRelease !== false;
     this.ended = false;
-    const outputs = { rgba: 1, ycbcr: 2, both: 3 };
+    const outputs = { rgba: 1, ycbcr: 2, both: 3, tensor: 16, 'rgba+tensor': 17, 'ycbcr+tensor': 18, all: 19 };
+    const dtypes = { float16: 1, bfloat16: 2, float32: 3 };
     let output = opts.output === undefined ? 0 : opts.output;
     if (typeof output === 'string') {
-      if (!(output in outputs)) throw new TypeError("output: 'rgba', 'ycbcr' or 'both'");
+      if (!(output in outputs)) throw new TypeError("output: 'rgba', 'ycbcr', 'both', 'tensor', 'rgba+tensor', 'ycbcr+tensor' or 'all'");
       output = outputs[output];
     }
-    this._p = addon.createPipeline(stream, Object.assign({}, opts, { output }), (w, frames, status) => this._deliver(w, frames, status));
+    let tensorDtype = opts.tensorDtype === undefined ? 0 : opts.tensorDtype;
+    if (typeof tensorDtype === 'string') {
+      if (!(tensorDtype in dtypes)) throw new TypeError("tensorDtype: 'float16', 'bfloat16' or 'float32'");
+      tensorDtype = dtypes[tensorDtype];
+    }
+    this._p = addon.createPipeline(stream, Object.assign({}, opts, { output, tensorDtype }), (w, frames, status) => this._deliver(w, frames, status));
   }
 
   _deliver(window, frames, status) {
@@ -79,6 +91,7 @@ class LeonPipeline extends EventEmitter {
   }
   readFrame(window, index) { return this._p.readFrame(window, index); }
   readPlanes(window, index) { return this._p.readPlanes(window, index); }
+  readTensor(window, index) { return this._p.readTensor(window, index); }
   releaseWindow(window) { this._p.releaseWindow(window); }
   stats() { return this._p.stats(); }
   destroy() { if (this._p) { this._p.destroy(); this._p = null; } }

@@ -35,10 +35,44 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_create", "leon_pipeline_create_partial", "leon_pipeline_feed", "leon_pipeline_get_info", "leon_pipeline_release_window", "leon_pipeline_wait",
     "leon_pipeline_get_stats", "leon_pipeline_read_frame", "leon_pipeline_error", "leon_pipeline_destroy", "leon_pipeline_seek",
     "leon_pipeline_read_frame_planes",
+    "leon_pipeline_create_tensor", "leon_pipeline_tensor_table", "leon_pipeline_window_tensors", "leon_pipeline_read_tensor",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
 PIPELINE_OUTPUTS = {"rgba": PIPELINE_OUTPUT_RGBA, "ycbcr": PIPELINE_OUTPUT_YCBCR, "both": PIPELINE_OUTPUT_RGBA | PIPELINE_OUTPUT_YCBCR}
+# the tensor output (LEON_PIPELINE_OUTPUT_TENSOR) and its combinations: names Pipeline(output=...) takes beside the ones above
+PIPELINE_OUTPUT_TENSOR = 16
+PIPELINE_TENSOR_OUTPUTS = {"tensor": PIPELINE_OUTPUT_TENSOR, "rgba+tensor": PIPELINE_OUTPUT_RGBA | PIPELINE_OUTPUT_TENSOR,
+                           "ycbcr+tensor": PIPELINE_OUTPUT_YCBCR | PIPELINE_OUTPUT_TENSOR,
+                           "all": PIPELINE_OUTPUT_RGBA | PIPELINE_OUTPUT_YCBCR | PIPELINE_OUTPUT_TENSOR}
+TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 1, 2, 3       # LEON_TENSOR_*
+TENSOR_DTYPES = {"float16": TENSOR_F16, "bfloat16": TENSOR_BF16, "float32": TENSOR_F32}
+
+
+def _tensor_dtype_code(dtype):
+    return TENSOR_DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+
+
+def tensor_table(dtype="float16", scale=None, bias=None):
+    """The table T of the tensor output (include/leon_pipeline.h), in numpy and independent of the C code: [3, 256],
+    T[c][v] = to_dtype(float32(float64(v) * float64(scale[c]) + float64(bias[c]))); scale and bias default to 1/255 and 0.
+    float16 / float32 arrays; bfloat16 as uint16 bit patterns (round to nearest even of the float32 value)."""
+    code = _tensor_dtype_code(dtype)
+    sc = np.asarray([0, 0, 0] if scale is None else scale, dtype=np.float32).reshape(3)
+    bi = np.asarray([0, 0, 0] if bias is None else bias, dtype=np.float32).reshape(3)
+    if not sc.any() and not bi.any():
+        sc = np.full(3, np.float32(1.0 / 255.0), dtype=np.float32)
+    v = np.arange(256, dtype=np.float64)[None, :]
+    with np.errstate(over="ignore", invalid="ignore"):
+        f32 = (v * sc.astype(np.float64)[:, None] + bi.astype(np.float64)[:, None]).astype(np.float32)
+        if code == TENSOR_F32:
+            return f32
+        if code == TENSOR_F16:
+            return f32.astype(np.float16)
+    if code != TENSOR_BF16:
+        raise ValueError("tensor dtype %r" % (dtype,))
+    x = f32.view(np.uint32).astype(np.uint64)
+    return ((x + 0x7fff + ((x >> 16) & 1)) >> 16).astype(np.uint16)
 
 
 def planes_layout(frame_width, frame_height, alpha=False):
@@ -106,6 +140,10 @@ class PipelineConfig(C.Structure):
                 ("gpu_parser", C.c_int32), ("display_flavour", C.c_int32), ("output", C.c_int32)]
 
 
+class PipelineTensorConfig(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
 class PipelineFrame(C.Structure):
     _fields_ = [("gop", C.c_uint64), ("display_index", C.c_int32), ("type", C.c_int32), ("ts_ms", C.c_double),
                 ("rgba", C.c_void_p), ("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("a", C.c_void_p)]
@@ -116,7 +154,9 @@ class PipelineInfo(C.Structure):
                 ("picture_rate", C.c_double), ("duration", C.c_double), ("gops", C.c_uint32), ("shard_gops", C.c_uint32),
                 ("first_gop", C.c_uint32), ("parser_threads", C.c_int32), ("gops_per_window", C.c_int32),
                 ("gpu_parser", C.c_int32), ("display_flavour", C.c_int32), ("output", C.c_int32),
-                ("chroma_width", C.c_int32), ("chroma_height", C.c_int32), ("luma_stride", C.c_int32), ("chroma_stride", C.c_int32)]
+                ("chroma_width", C.c_int32), ("chroma_height", C.c_int32), ("luma_stride", C.c_int32), ("chroma_stride", C.c_int32),
+                ("tensor_dtype", C.c_int32), ("tensor_element_bytes", C.c_int32), ("tensor_frame_bytes", C.c_uint64),
+                ("tensor_frame_pitch", C.c_uint64), ("tensor_gop_pitch", C.c_uint64)]
 
 
 class PipelineStats(C.Structure):
@@ -193,6 +233,11 @@ def load():
     lib.leon_pipeline_get_stats.argtypes = [C.c_void_p, C.POINTER(PipelineStats)]
     lib.leon_pipeline_read_frame.argtypes = [C.c_void_p, C.POINTER(PipelineFrame), C.c_void_p]
     lib.leon_pipeline_read_frame_planes.argtypes = [C.c_void_p, C.POINTER(PipelineFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.leon_pipeline_create_tensor.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.c_void_p, C.c_size_t, C.c_size_t, PIPELINE_CB,
+                                                C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.leon_pipeline_tensor_table.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.c_void_p]
+    lib.leon_pipeline_window_tensors.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int32]
+    lib.leon_pipeline_read_tensor.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -429,8 +474,8 @@ class _Frames:
     """the frames of a delivered window as a read-only sequence of dicts, made when asked for (a 128-GOP window has 1536 of
     them; a callback that looks at a dozen should not pay for the rest on the pipeline's notify thread)"""
 
-    def __init__(self, frames, n, pipe):
-        self._f, self._n, self._pipe = frames, n, pipe
+    def __init__(self, frames, n, pipe, window=-1, tensors=None):
+        self._f, self._n, self._pipe, self._window, self._tensors = frames, n, pipe, window, tensors
 
     def __len__(self):
         return self._n
@@ -444,7 +489,8 @@ class _Frames:
             raise IndexError(i)
         f = self._f[i]
         return {"gop": int(f.gop), "display_index": f.display_index, "type": f.type, "ts_ms": f.ts_ms, "rgba": f.rgba,
-                "y": f.y, "cb": f.cb, "cr": f.cr, "a": f.a, "_i": i, "_frames": self._f, "_pipe": self._pipe}
+                "y": f.y, "cb": f.cb, "cr": f.cr, "a": f.a, "tensor": self._tensors[i] if self._tensors is not None else None,
+                "_i": i, "_window": self._window, "_frames": self._f, "_pipe": self._pipe}
 
     def __iter__(self):
         return (self[i] for i in range(self._n))
@@ -456,15 +502,23 @@ class Pipeline:
     (gop, display_index, type, ts_ms, rgba = device address); unless it returns False the window is
     released right after.  read_frame(frame) works until the frame's window is released.
     output="ycbcr" / "both": the frames carry their YCbCr 4:2:0 planes too (y, cb, cr, a = device addresses, a for yuva
-    streams only; rgba is None with "ycbcr"): read_planes(frame) copies them to the host, plane_views(frame) wraps them."""
+    streams only; rgba is None with "ycbcr"): read_planes(frame) copies them to the host, plane_views(frame) wraps them.
+    output="tensor" / "rgba+tensor" / "ycbcr+tensor" / "all" (PIPELINE_TENSOR_OUTPUTS): the frames carry a planar [3, H, W] tensor
+    (tensor = device address) of tensor_dtype "float16" / "bfloat16" / "float32", element = tensor_table(dtype, scale, bias)[c][colour
+    value]; tensor_scale / tensor_bias: three floats each (None: 1/255 and 0).  read_tensor(frame) copies it to the host,
+    tensor_view(frame) and window_tensor(frames) wrap it in place as torch tensors."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
-                 output="rgba"):
+                 output="rgba", tensor_dtype="float16", tensor_scale=None, tensor_bias=None):
         self.lib = load()
         self.device_id = device_id
         # a name of PIPELINE_OUTPUTS, or the raw bit set (anything the library does not know is refused by create)
-        out_bits = PIPELINE_OUTPUTS[output] if isinstance(output, str) else int(output)
+        out_bits = (PIPELINE_OUTPUTS.get(output) or PIPELINE_TENSOR_OUTPUTS[output]) if isinstance(output, str) else int(output)
+        tcfg = None
+        if out_bits > 0 and out_bits & PIPELINE_OUTPUT_TENSOR:
+            tcfg = PipelineTensorConfig(_tensor_dtype_code(tensor_dtype), (C.c_float * 3)(*([0, 0, 0] if tensor_scale is None else tensor_scale)),
+                                        (C.c_float * 3)(*([0, 0, 0] if tensor_bias is None else tensor_bias)))
         self._data = (C.c_uint8 * len(data)).from_buffer_copy(data)      # must outlive the pipeline
         self._on_window = on_window
         self.windows = 0
@@ -498,7 +552,12 @@ class Pipeline:
                 if self._on_window is not None:
                     # `_pipe`: a callback may read frames through the dicts alone (read_frame(f) below), without the
                     # variable its caller assigns the pipeline to -- which does not exist yet while the constructor runs
-                    fl = _Frames(frames, n, self)
+                    tensors = None
+                    if self.info.tensor_dtype and n:          # the window's tensor pointers, one call
+                        tensors = (C.c_void_p * n)()
+                        if self.lib.leon_pipeline_window_tensors(self.h, window, tensors, n) != OK:
+                            raise LeonError(ERR_INVALID, self.lib.leon_last_error().decode())
+                    fl = _Frames(frames, n, self, window, tensors)
                     keep = self._on_window(window, fl)
                 if keep is not False:
                     _release(window)
@@ -512,7 +571,10 @@ class Pipeline:
         h = C.c_void_p()
         self.h = None
         # valid_bytes: the stream is still arriving (leon_pipeline_create_partial); feed() reports progress
-        if valid_bytes is None:
+        if tcfg is not None:
+            rc = self.lib.leon_pipeline_create_tensor(C.byref(cfg), C.byref(tcfg), self._data, len(data), len(data) if valid_bytes is None else int(valid_bytes),
+                                                      self._cb, None, C.byref(h))
+        elif valid_bytes is None:
             rc = self.lib.leon_pipeline_create(C.byref(cfg), self._data, len(data), self._cb, None, C.byref(h))
         else:
             rc = self.lib.leon_pipeline_create_partial(C.byref(cfg), self._data, len(data), int(valid_bytes), self._cb, None, C.byref(h))
@@ -539,6 +601,51 @@ class Pipeline:
         _chk(self.lib.leon_pipeline_read_frame_planes(self.h, C.byref(frame["_frames"][frame["_i"]]), y.ctypes.data, cb.ctypes.data,
                                                       cr.ctypes.data, None if a is None else a.ctypes.data))
         return (y, cb, cr) if a is None else (y, cb, cr, a)
+
+    def _tensor_np_dtype(self):
+        return {TENSOR_F16: np.float16, TENSOR_BF16: np.uint16, TENSOR_F32: np.float32}[self.info.tensor_dtype]
+
+    def read_tensor(self, frame):
+        """the frame's tensor as a host array [3, frame_height, frame_width]: float16 / float32, bfloat16 as uint16 bit patterns"""
+        if not frame.get("tensor"):
+            raise LeonError(ERR_INVALID, "the frame has no tensor (Pipeline output)")
+        out = np.empty((3, self.info.frame_height, self.info.frame_width), dtype=self._tensor_np_dtype())
+        _chk(self.lib.leon_pipeline_read_tensor(self.h, frame["_window"], frame["_i"], out.ctypes.data))
+        return out
+
+    def _tensor_at(self, ptr, shape, strides, device_id=None):
+        import torch
+        dt = self.info.tensor_dtype
+
+        class _View:
+            pass
+        v = _View()
+        v.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4" if dt == TENSOR_F32 else ("<f2" if dt == TENSOR_F16 else "<i2"),
+                                      "data": (int(ptr), False), "strides": tuple(int(x) for x in strides), "version": 2}
+        t = torch.as_tensor(v, device="cuda:%d" % (self.device_id if device_id is None else device_id))
+        return t.view(torch.bfloat16) if dt == TENSOR_BF16 else t
+
+    def tensor_view(self, frame, device_id=None):
+        """the frame's tensor where it lies, as a torch [3, H, W] tensor of the pipeline's element type, without copying: valid until
+        the frame's window is released"""
+        if not frame.get("tensor"):
+            raise ValueError("the frame has no tensor (Pipeline output)")
+        i = self.info
+        e, h, w = i.tensor_element_bytes, i.frame_height, i.frame_width
+        return self._tensor_at(frame["tensor"], (3, h, w), (h * w * e, w * e, e), device_id)
+
+    def window_tensor(self, frames, device_id=None):
+        """frames of one window (in order) as ONE strided torch view [N, 3, H, W] when their tensors are evenly spaced in the
+        ring -- consecutive display positions of a GOP are tensor_frame_pitch apart --, else None"""
+        ptrs = [f.get("tensor") for f in frames]
+        if not ptrs or not all(ptrs):
+            return None
+        step = ptrs[1] - ptrs[0] if len(ptrs) > 1 else self.info.tensor_frame_pitch
+        i = self.info
+        e, h, w = i.tensor_element_bytes, i.frame_height, i.frame_width
+        if step <= 0 or step % e or step < i.tensor_frame_bytes or any(b - a != step for a, b in zip(ptrs, ptrs[1:])):
+            return None
+        return self._tensor_at(ptrs[0], (len(ptrs), 3, h, w), (step, h * w * e, w * e, e), device_id)
 
     def plane_views(self, frame, device_id=None):
         """the frame's planes where they lie, as torch uint8 tensors (height x width, row stride = the plane's padded stride),

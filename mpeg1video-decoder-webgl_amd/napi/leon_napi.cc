@@ -559,6 +559,52 @@ napi_value PipeReadPlanes(napi_env env, napi_callback_info info)
     return rc == LEON_OK ? o : throw_leon(env, rc);
 }
 
+// p.readTensor(window, i) -> Uint16Array (fp16 / bf16 bit patterns) or Float32Array, [3][frameHeight][frameWidth] packed: one frame's
+// tensor (output 'tensor' ...)
+napi_value PipeReadTensor(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    int32_t i = -1;
+    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "readTensor(window, index)");
+        return nullptr;
+    }
+    if (!h->info.tensor_dtype) {
+        napi_throw_error(env, nullptr, "readTensor: the pipeline has no tensor output (opts.output)");
+        return nullptr;
+    }
+    const size_t bytes = (size_t)h->info.tensor_frame_bytes, eb = (size_t)h->info.tensor_element_bytes;
+    napi_value ab, ta;
+    void* data = nullptr;
+    NAPI_OK(napi_create_arraybuffer(env, bytes, &data, &ab));
+    NAPI_OK(napi_create_typedarray(env, eb == 4 ? napi_float32_array : napi_uint16_array, bytes / eb, ab, 0, &ta));
+    int rc = leon_pipeline_read_tensor(h->p, w, i, data);
+    return rc == LEON_OK ? ta : throw_leon(env, rc);
+}
+
+// opts[name] as three floats (an array of numbers); absent: zeros
+bool get_f32x3(napi_env env, napi_value opts, const char* name, float* out)
+{
+    napi_value v, e;
+    bool has = false, is_arr = false;
+    if (napi_has_named_property(env, opts, name, &has) != napi_ok || !has) return true;
+    if (napi_get_named_property(env, opts, name, &v) != napi_ok) return false;
+    napi_valuetype t;
+    if (napi_typeof(env, v, &t) == napi_ok && (t == napi_undefined || t == napi_null)) return true;
+    uint32_t n = 0;
+    if (napi_is_array(env, v, &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, v, &n) != napi_ok || n != 3) return false;
+    for (uint32_t k = 0; k < 3; k++) {
+        double d = 0;
+        if (napi_get_element(env, v, k, &e) != napi_ok || napi_get_value_double(env, e, &d) != napi_ok) return false;
+        out[k] = (float)d;
+    }
+    return true;
+}
+
 napi_value PipeStats(napi_env env, napi_callback_info info)
 {
     size_t argc = 0;
@@ -575,7 +621,10 @@ napi_value PipeStats(napi_env env, napi_callback_info info)
         {"codedWidth", (double)h->info.coded_width}, {"codedHeight", (double)h->info.coded_height},
         {"pictureRate", h->info.picture_rate}, {"keyMapGops", (double)h->info.gops}, {"shardGops", (double)h->info.shard_gops}, {"firstGop", (double)h->info.first_gop}, {"duration", h->info.duration}, {"parserThreads", (double)h->info.parser_threads},
         {"gopsPerWindow", (double)h->info.gops_per_window}, {"output", (double)h->info.output},
-        {"chromaWidth", (double)h->info.chroma_width}, {"chromaHeight", (double)h->info.chroma_height}};
+        {"chromaWidth", (double)h->info.chroma_width}, {"chromaHeight", (double)h->info.chroma_height},
+        {"tensorDtype", (double)h->info.tensor_dtype}, {"tensorElementBytes", (double)h->info.tensor_element_bytes},
+        {"tensorFrameBytes", (double)h->info.tensor_frame_bytes}, {"tensorFramePitch", (double)h->info.tensor_frame_pitch},
+        {"tensorGopPitch", (double)h->info.tensor_gop_pitch}};
     for (auto& e : kv) {
         NAPI_OK(napi_create_double(env, e.val, &v));
         NAPI_OK(napi_set_named_property(env, o, e.k, v));
@@ -671,10 +720,20 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
             if (t == napi_number) napi_get_value_double(env, v, &cfg.start_seconds);
         }
     }
+    // the tensor output's settings (leon_pipeline_tensor_config): tensorDtype LEON_TENSOR_* (js/leon_pipeline.js maps the names),
+    // tensorScale / tensorBias [r, g, b]
+    leon_pipeline_tensor_config tcfg;
+    memset(&tcfg, 0, sizeof tcfg);
+    ok = ok && get_i32(env, argv[1], "tensorDtype", &tcfg.dtype, 0);
     if (!ok) {
         napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
         return nullptr;
     }
+    if (!get_f32x3(env, argv[1], "tensorScale", tcfg.scale) || !get_f32x3(env, argv[1], "tensorBias", tcfg.bias)) {
+        napi_throw_type_error(env, nullptr, "createPipeline: tensorScale / tensorBias must be arrays of three numbers");
+        return nullptr;
+    }
+    const bool tensor = (cfg.output & LEON_PIPELINE_OUTPUT_TENSOR) != 0 || tcfg.dtype != 0;
     PipeHandle* h = new PipeHandle();
     napi_value name;
     NAPI_OK(napi_create_string_utf8(env, "leon pipeline frames", NAPI_AUTO_LENGTH, &name));
@@ -706,7 +765,8 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
             }
         }
     }
-    int rc = partial ? leon_pipeline_create_partial(&cfg, (const uint8_t*)data, len, (size_t)valid, pipe_native_cb, h, &h->p)
+    int rc = tensor ? leon_pipeline_create_tensor(&cfg, &tcfg, (const uint8_t*)data, len, partial ? (size_t)valid : len, pipe_native_cb, h, &h->p)
+           : partial ? leon_pipeline_create_partial(&cfg, (const uint8_t*)data, len, (size_t)valid, pipe_native_cb, h, &h->p)
                      : leon_pipeline_create(&cfg, (const uint8_t*)data, len, pipe_native_cb, h, &h->p);
     if (rc != LEON_OK) {
         napi_release_threadsafe_function(h->tsfn, napi_tsfn_abort);
@@ -719,7 +779,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));

@@ -29,8 +29,9 @@ def main():
     ap.add_argument("--window", type=int, default=32)
     ap.add_argument("--inflight", type=int, default=2)
     ap.add_argument("--gpu-parser", action="store_true", help="decode the slice layer on the GPU (leon_pipeline_config.gpu_parser)")
-    ap.add_argument("--output", choices=["rgba", "ycbcr", "both"], default="rgba",
-                    help="what the frames carry (leon_pipeline_config.output): RGBA, the YCbCr planes, or both")
+    ap.add_argument("--output", choices=["rgba", "ycbcr", "both", "tensor", "rgba+tensor", "ycbcr+tensor", "all"], default="rgba",
+                    help="what the frames carry (leon_pipeline_config.output): RGBA, the YCbCr planes, planar float tensors, or a combination")
+    ap.add_argument("--tensor-dtype", choices=["float16", "bfloat16", "float32"], default="float16", help="element type of --output tensor")
     ap.add_argument("--varied", action="store_true", help="the 16-GOP stream with 16 different contents (tools/stream_1080p.py) instead of --gops GOPs")
     a = ap.parse_args()
     cached = os.path.join(ROOT, "tools", "probe", "stream_1080p_%dgop.bin" % a.gops)
@@ -54,7 +55,7 @@ def main():
     free0 = free_device_bytes()
     t0 = time.perf_counter()
     pipe = L.Pipeline(data, parser_threads=a.threads, gops_per_window=a.window, windows_in_flight=a.inflight, loop=a.loop, gpu_parser=a.gpu_parser,
-                      output=a.output)
+                      output=a.output, tensor_dtype=a.tensor_dtype)
     free1 = free_device_bytes()
     pipe.wait()
     wall = time.perf_counter() - t0
@@ -63,8 +64,10 @@ def main():
     mbs = (pipe.info.coded_width // 16) * (pipe.info.coded_height // 16)
     print(json.dumps({
         "metric": "end-to-end %dx%d pictures/s (parse + PCIe + reconstruct + %s in device memory), native pipeline, one GPU"
-                  % (pipe.info.frame_width, pipe.info.frame_height, {"rgba": "RGBA", "ycbcr": "YCbCr planes", "both": "RGBA + YCbCr planes"}[a.output]),
-        "output": a.output,
+                  % (pipe.info.frame_width, pipe.info.frame_height, {"rgba": "RGBA", "ycbcr": "YCbCr planes", "both": "RGBA + YCbCr planes", "tensor": "tensors", "rgba+tensor": "RGBA + tensors",
+                     "ycbcr+tensor": "YCbCr planes + tensors", "all": "RGBA + YCbCr planes + tensors"}[a.output]),
+        "output": a.output, "tensor_dtype": a.tensor_dtype if pipe.info.tensor_dtype else None,
+        "tensor_frame_bytes": pipe.info.tensor_frame_bytes, "windows_in_flight": a.inflight,
         "value": s["pictures"] / s["seconds"], "macroblocks_per_s": s["pictures"] * mbs / s["seconds"],
         "pictures": s["pictures"], "seconds": s["seconds"], "wall_seconds_incl_setup": wall, "windows": s["windows"],
         "slice_layer": "GPU (csrc/leon_vlc_gpu.h)" if a.gpu_parser else "host threads (libleon_vlc.so)",
