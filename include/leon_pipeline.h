@@ -137,6 +137,40 @@ typedef struct leon_pipeline_tensor_config {
     float   scale[3], bias[3];  /* per channel R, G, B */
 } leon_pipeline_tensor_config;
 
+/* The tensor at a model's input size: a crop box of the frame resampled to out_width x out_height on the device, from the frame's
+ * planes straight to the small tensor (one kernel per window, k_resample; the full-size tensor is never written).  The definition is
+ * integer and built from host tables, P = 22:
+ *     one axis (in_size = the FRAME's size, in0 = crop start, in1 = crop start + crop size):
+ *         scale = (in1 - in0) / out_size (double); fscale = support = max(scale, 1.0)
+ *         center = in0 + (o + 0.5) * scale; first = max(0, (int)(center - support + 0.5)); end = min(in_size, (int)(center + support + 0.5))
+ *         w[k] = max(0, 1 - |(first + k - center + 0.5) / fscale|), k = 0 .. end - first - 1; w[k] /= sum(w) (index order, doubles)
+ *         W[o][k] = (int)(0.5 + w[k] * 2^P)                                  -- leon_pipeline_resize_weights gives first, count, W
+ *     h[y][o][c]  = min(255, (2^(P-1) + sum_k Wx[o][k] * rgb[y][first_x[o] + k][c]) >> P)         horizontal pass first, 8-bit result
+ *     r[oy][o][c] = min(255, (2^(P-1) + sum_k Wy[oy][k] * h[first_y[oy] + k][o][c]) >> P)         then vertical
+ *     tensor[c][oy][ox] = T[c][ r[oy][ox][c] ]                                                    T: the table above
+ * with rgb = the bytes an RGBA pipeline with LEON_RGB_CPU_TWIN delivers (the row of 255 in the last row of an odd frame height
+ * included).  Taps may reach outside the crop box, never outside the frame.  This is the arithmetic of an 8-bit antialiased
+ * triangle ("bilinear") resize: a triangle filter widened by the ratio when reducing, plain bilinear when enlarging.
+ * All fields zero (or no struct) = the full-size tensor above; a crop box of all zeros = the whole frame.  Refused at create:
+ * out_width / out_height outside 1 .. 4096, an empty crop box or one that leaves the frame, crop / out > 16 on an axis, another
+ * filter, resize settings without the TENSOR bit. */
+#define LEON_RESIZE_TRIANGLE 0
+#define LEON_RESIZE_MAX_TAPS 33      /* count <= 2 * 16 + 1 */
+typedef struct leon_pipeline_tensor_resize {
+    int32_t crop_x, crop_y, crop_width, crop_height;    /* frame pixels */
+    int32_t out_width, out_height;
+    int32_t filter;                                     /* LEON_RESIZE_TRIANGLE */
+} leon_pipeline_tensor_resize;
+
+/* what a pipeline's tensors are (leon_pipeline_get_tensor_geometry): width and height of the tensor, the crop box in force, the
+ * largest tap count of an output column / row (1 and 1 without resize settings), resized = 1 when k_resample makes them */
+typedef struct leon_pipeline_tensor_geometry {
+    int32_t width, height;
+    int32_t crop_x, crop_y, crop_width, crop_height;
+    int32_t taps_x, taps_y;
+    int32_t resized;
+} leon_pipeline_tensor_geometry;
+
 typedef void (*leon_pipeline_callback)(void* user, int64_t window, const leon_pipeline_frame* frames, int32_t n_frames, int32_t status);
 
 typedef struct leon_pipeline_info {
@@ -151,7 +185,8 @@ typedef struct leon_pipeline_info {
     int32_t output;             /* LEON_PIPELINE_OUTPUT_* bits in force (0 configured = RGBA) */
     int32_t chroma_width, chroma_height;   /* of Cb and Cr: (frame_width + 1) / 2, (frame_height + 1) / 2 */
     int32_t luma_stride, chroma_stride;    /* bytes per row of Y (and A), of Cb and Cr: the plane width rounded up to 64 */
-    /* LEON_PIPELINE_OUTPUT_TENSOR (all 0 without it): element type and size, 3 * frame_height * frame_width * element size, and the
+    /* LEON_PIPELINE_OUTPUT_TENSOR (all 0 without it): element type and size, 3 * height * width * element size (the frame's, or
+     * out_height and out_width of leon_pipeline_tensor_resize), and the
      * bytes between the tensors of consecutive display positions of one GOP and ring entry (= tensor_frame_bytes rounded up to 256)
      * and between the GOP lanes of a window: a window whose GOPs are equally long is one strided [gops, pictures, 3, H, W] view */
     int32_t tensor_dtype, tensor_element_bytes;
@@ -184,6 +219,14 @@ int leon_pipeline_create_tensor(const leon_pipeline_config* cfg, const leon_pipe
 /* the table T (3 x 256 elements of the element type, [channel][value]) a pipeline created with these settings looks up: computed on
  * the host, no device touched -- and refused as create refuses (cfg->output must have the TENSOR bit) */
 int leon_pipeline_tensor_table(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, void* out768);
+/* leon_pipeline_create_tensor with the tensors resampled to a model's input size; `resize` NULL (or all zero) = leon_pipeline_create_tensor */
+int leon_pipeline_create_tensor_resized(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const leon_pipeline_tensor_resize* resize,
+                                        const uint8_t* stream, size_t bytes, size_t valid_bytes, leon_pipeline_callback cb, void* user, leon_pipeline** out);
+/* the tables of one axis of that resampling: first[o], count[o] and weights[o * max_taps + k] (k >= count[o]: 0) for o = 0 .. out_size - 1.
+ * Computed on the host, no device touched, refused as create refuses (and when a count exceeds max_taps; LEON_RESIZE_MAX_TAPS always fits) */
+int leon_pipeline_resize_weights(int32_t in_size, int32_t crop_start, int32_t crop_size, int32_t out_size, int32_t filter,
+                                 int32_t* first, int32_t* count, int32_t* weights, int32_t max_taps);
+int leon_pipeline_get_tensor_geometry(leon_pipeline* p, leon_pipeline_tensor_geometry* out);
 int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes);
 int leon_pipeline_get_info(leon_pipeline* p, leon_pipeline_info* out);
 /* the consumer is done with a window's frames: its ring entries (RGBA, planes, tensors) and staging may be reused */
@@ -220,7 +263,7 @@ int leon_pipeline_read_frame_planes(leon_pipeline* p, const leon_pipeline_frame*
  * window is released, like rgba), n = the window's n_frames.  May be called from inside the callback.  LEON_ERR_INVALID for a
  * pipeline without tensor output, a window that is not out for delivery, another n */
 int leon_pipeline_window_tensors(leon_pipeline* p, int64_t window, void** out, int32_t n);
-/* copy the tensor of frame `index` of such a window to host memory, packed (tensor_frame_bytes) */
+/* copy the tensor of frame `index` of such a window to host memory, packed (tensor_frame_bytes: [3][height][width] of the geometry) */
 int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, void* host);
 const char* leon_pipeline_error(leon_pipeline* p);
 void leon_pipeline_destroy(leon_pipeline* p);

@@ -1734,6 +1734,181 @@ __global__ __launch_bounds__(kRgbaBlock) void k_tensor(const uint8_t* __restrict
     }
 }
 
+// ---- the frames as tensors at a model's input size (leon_pipeline.h, leon_pipeline_tensor_resize) -----------------------
+// frame planes record -> [3][oh][ow] elements: a crop box of the frame resampled with the host's integer tables (per axis first[o],
+// count[o], weights[o][taps], 22 fractional bits: leon_pipeline_resize_weights is the definition), horizontal pass first with an
+// 8-bit result, then vertical, then the element table of k_tensor.  One launch per window, blockIdx.z = frame as in k_tensor.
+// A workgroup owns kResTileX x kResTileY output pixels.  Their source footprint -- columns first_x[tile's first] (rounded down to
+// 8) .. end_x[tile's last], rows first_y .. end_y -- is walked in chunks of whole source rows that fit the staging buffer (a
+// footprint that does not fit is split, never refused: ratio 16 stages 6 rows of 544 pixels at a time).  Per chunk: (1) every
+// source sample is loaded once (non-temporal: 8 Y bytes per row and 4 Cb + 4 Cr bytes for a row pair per lane, k_tensor's shape)
+// and converted once with chroma_terms / rgba_px into RGBX dwords in LDS; (2) the horizontal pass, a lane per (output column, row
+// pair), writes packed 8-bit results to the tile's h rows in LDS -- two rows per lane share every weight read.  After the last
+// chunk (3) the vertical pass, a lane per output pixel, reads h, looks the three elements up and stores them.  Products are
+// v_mad_u32_u24 (weights <= 2^22, samples < 2^8; the sums stay below 2^31).  Rows at and beyond the frame height are never loaded
+// (kOobBit) and never tapped; the last row of an odd height is the CPU twin's fill row, 255.
+static constexpr int kResTileX = 32, kResTileY = 8;          // kResTileX * kResTileY = kRgbaBlock: the vertical pass is one pixel per lane
+static constexpr int kResMaxTaps = 33;                       // = LEON_RESIZE_MAX_TAPS: 2 * 16 + 1
+static constexpr int kResStagePx = 4096;                     // staging dwords: 6 rows of the widest footprint (31 * 16 + 33 + 14 <= 544 columns, 578 dwords padded)
+static constexpr int kResHRows = 160;                        // h rows of a tile: <= 7 * 16 + 33 + 2 = 147, and one spare for the odd tail
+static constexpr int kResWeightShift = 22;
+struct ResampleGeom {
+    int32_t fw, fh, ow, oh;
+    int32_t taps_x, taps_y;              // row length of the weight tables
+    uint32_t off_cx, off_wx, off_fy, off_cy, off_wy;          // int32 offsets in the table buffer (first_x at 0)
+    uint32_t luma_stride, chroma_stride, cb_off, cr_off;      // FrameOut
+    uint32_t planes_pitch_lo, planes_pitch_hi, tensor_pitch_lo, tensor_pitch_hi;      // bytes between ring frames
+};
+
+// Column c of a staged row lies at dword c + (c >> 4): the horizontal pass's lanes are the tile's output columns and read columns
+// about `ratio` apart -- at a ratio of 16 or 8 unpadded rows would put all of them on two or four LDS banks; one pad dword per 16
+// turns those strides into 17 and 8.5.
+__host__ __device__ constexpr int resample_col(int c) { return c + (c >> 4); }
+__device__ __forceinline__ uint32_t resample_px(uint32_t ar, uint32_t ag, uint32_t ab)
+{
+    return min(ar >> kResWeightShift, 255u) | (min(ag >> kResWeightShift, 255u) << 8) | (min(ab >> kResWeightShift, 255u) << 16);
+}
+
+template <int DTYPE>
+__global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
+                                                         const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
+                                                         ResampleGeom G)
+{
+    typedef typename TensorElem<DTYPE>::type Elem;
+    static_assert(kResTileX * kResTileY == kRgbaBlock && kResTileX == 32, "lane = (tid & 31, tid >> 5)");
+    __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
+    __shared__ __attribute__((aligned(16))) Elem tab_s[3 * 256];
+    __shared__ __attribute__((aligned(16))) uint32_t stage_s[kResStagePx];
+    __shared__ uint32_t h_s[kResHRows * kResTileX];
+    __shared__ int32_t wx_s[kResTileX * kResMaxTaps], wy_s[kResTileY * kResMaxTaps];
+    __shared__ int32_t fx_s[kResTileX], nx_s[kResTileX], fy_s[kResTileY], ny_s[kResTileY];
+    const int tid = threadIdx.x;
+    const int ox0 = blockIdx.x * kResTileX, oy0 = blockIdx.y * kResTileY;
+    const int nox = min(kResTileX, G.ow - ox0), noy = min(kResTileY, G.oh - oy0);
+    const int32_t* first_x = rt;
+    const int32_t* count_x = rt + G.off_cx;
+    const int32_t* first_y = rt + G.off_fy;
+    const int32_t* count_y = rt + G.off_cy;
+    {   // the conversion tables and the element table as k_tensor loads them, then the tile's slices of the resampling tables
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const int lane0 = tid & 63;
+        const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc((void*)T->rgba_lut, 0, kLdsLut, 0x00020000);
+        for (int c = wave; c < kLdsLut / 1024; c += kRgbaBlock / 64)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lut_s) + c * 1024), 16,
+                                                     (int)(lane0 * 16u), c * 1024, 0, 0);
+        constexpr int kDwords = 3 * 256 * (int)sizeof(Elem) / 4;
+        for (int i = tid; i < kDwords; i += kRgbaBlock) reinterpret_cast<uint32_t*>(tab_s)[i] = table[i];
+        const int32_t* wxg = rt + G.off_wx + (size_t)ox0 * G.taps_x;
+        for (int i = tid; i < nox * G.taps_x; i += kRgbaBlock) wx_s[i] = wxg[i];
+        const int32_t* wyg = rt + G.off_wy + (size_t)oy0 * G.taps_y;
+        for (int i = tid; i < noy * G.taps_y; i += kRgbaBlock) wy_s[i] = wyg[i];
+        if (tid < nox) { fx_s[tid] = first_x[ox0 + tid]; nx_s[tid] = count_x[ox0 + tid]; }
+        if (tid < noy) { fy_s[tid] = first_y[oy0 + tid]; ny_s[tid] = count_y[oy0 + tid]; }
+        wait_vmem_all();
+        __syncthreads();
+    }
+    // the tile's source footprint (first and end are monotone in o)
+    const int cx0 = first_x[ox0] & ~7;
+    const int sw = (first_x[ox0 + nox - 1] + count_x[ox0 + nox - 1] - cx0 + 7) & ~7;      // staged columns: whole 8-pixel groups, inside luma_stride
+    const int ry0 = first_y[oy0] & ~1;                                                    // even: a row pair shares its chroma row
+    const int ry1 = first_y[oy0 + noy - 1] + count_y[oy0 + noy - 1];                      // <= fh
+    const int sw8 = sw >> 3;
+    const int swp = resample_col(sw);                                                     // dwords of a staged row
+    const int rc = (kResStagePx / swp) & ~1;                                              // rows per chunk
+    const int pair_t = tid / sw8, col_t = tid - pair_t * sw8;                             // this lane's first item of a chunk ...
+    const int pair_step = kRgbaBlock / sw8, col_step = kRgbaBlock - pair_step * sw8;      // ... and the way to its next
+
+    const char* lut = reinterpret_cast<const char*>(lut_s);
+    const uint32_t fid = frame_ids[blockIdx.z];
+    const uint8_t* src = planes_ring + (size_t)fid * (((size_t)G.planes_pitch_hi << 32) | G.planes_pitch_lo);
+    uint8_t* dst = tensor_ring + (size_t)fid * (((size_t)G.tensor_pitch_hi << 32) | G.tensor_pitch_lo);
+    const __amdgpu_buffer_rsrc_t prs = buf_rsrc(src);
+    uint32_t two = 2u, three = 3u;                       // SDWA shift counts live in registers (display_half)
+    asm("" : "+v"(two), "+v"(three));
+    const int opaque = 255 << kLutShift;
+    const int o = tid & 31, sub = tid >> 5;
+
+    for (int r = ry0; r < ry1; r += rc) {
+        const int rows = min(rc, ry1 - r);
+        // (1) rows r .. r + rows - 1 (whole pairs), columns cx0 .. cx0 + sw - 1 -> RGBX in stage_s[row][swp]
+        const int n_pairs = (rows + 1) >> 1;
+        for (int pair = pair_t, col = col_t; pair < n_pairs;) {
+            const int row = r + 2 * pair;
+            const bool in0 = row < G.fh, in1 = row + 1 < G.fh;
+            const uint32_t yo = (uint32_t)row * G.luma_stride + (uint32_t)(cx0 + 8 * col);
+            const uint32_t co = (uint32_t)(row >> 1) * G.chroma_stride + (uint32_t)((cx0 >> 1) + 4 * col);
+            const v2u y0 = __builtin_amdgcn_raw_buffer_load_b64(prs, (int)(in0 ? yo : kOobBit), 0, kAuxStreamOnce);
+            const v2u y1 = __builtin_amdgcn_raw_buffer_load_b64(prs, (int)(in1 ? yo + G.luma_stride : kOobBit), 0, kAuxStreamOnce);
+            const uint32_t cb4 = __builtin_amdgcn_raw_buffer_load_b32(prs, (int)(in0 ? G.cb_off + co : kOobBit), 0, kAuxStreamOnce);
+            const uint32_t cr4 = __builtin_amdgcn_raw_buffer_load_b32(prs, (int)(in0 ? G.cr_off + co : kOobBit), 0, kAuxStreamOnce);
+            const ChromaTerms c[4] = {chroma_terms<0>(lut, cb4, cr4, three), chroma_terms<1>(lut, cb4, cr4, three),
+                                      chroma_terms<2>(lut, cb4, cr4, three), chroma_terms<3>(lut, cb4, cr4, three)};
+            uint32_t a[8] = {rgba_px<0>(lut, y0.x, c[0], opaque, two), rgba_px<1>(lut, y0.x, c[0], opaque, two),
+                             rgba_px<2>(lut, y0.x, c[1], opaque, two), rgba_px<3>(lut, y0.x, c[1], opaque, two),
+                             rgba_px<0>(lut, y0.y, c[2], opaque, two), rgba_px<1>(lut, y0.y, c[2], opaque, two),
+                             rgba_px<2>(lut, y0.y, c[3], opaque, two), rgba_px<3>(lut, y0.y, c[3], opaque, two)};
+            const uint32_t b[8] = {rgba_px<0>(lut, y1.x, c[0], opaque, two), rgba_px<1>(lut, y1.x, c[0], opaque, two),
+                                   rgba_px<2>(lut, y1.x, c[1], opaque, two), rgba_px<3>(lut, y1.x, c[1], opaque, two),
+                                   rgba_px<0>(lut, y1.y, c[2], opaque, two), rgba_px<1>(lut, y1.y, c[2], opaque, two),
+                                   rgba_px<2>(lut, y1.y, c[3], opaque, two), rgba_px<3>(lut, y1.y, c[3], opaque, two)};
+            if (!in1) {                                  // the last row of an odd height: left at 255 by the twin
+#pragma unroll
+                for (int k = 0; k < 8; k++) a[k] = 0xffffffffu;
+            }
+            uint32_t* s0 = stage_s + (2 * pair) * swp + resample_col(8 * col);            // (8 columns of one group of 16: contiguous)
+#pragma unroll
+            for (int k = 0; k < 8; k++) { s0[k] = a[k]; s0[swp + k] = b[k]; }
+            pair += pair_step; col += col_step;
+            if (col >= sw8) { col -= sw8; pair++; }
+        }
+        __syncthreads();
+        // (2) horizontal pass: output column o of the tile, staged rows 2 * sub, 2 * sub + 1, then 16 rows on
+        if (o < nox) {
+            const int n = nx_s[o];
+            const int32_t* w = wx_s + o * G.taps_x;
+            for (int rr = 2 * sub; rr < rows; rr += 2 * (kRgbaBlock / 32)) {
+                const uint32_t* s = stage_s + rr * swp;
+                const int c0 = fx_s[o] - cx0;
+                uint32_t ar = 1u << (kResWeightShift - 1), ag = ar, ab = ar, br = ar, bg = ar, bb = ar;
+                for (int k = 0; k < n; k++) {
+                    const int at = resample_col(c0 + k);
+                    const uint32_t wk = (uint32_t)w[k], pa = s[at], pb = s[at + swp];
+                    ar = __umul24(wk, pa & 255u) + ar; ag = __umul24(wk, (pa >> 8) & 255u) + ag; ab = __umul24(wk, (pa >> 16) & 255u) + ab;
+                    br = __umul24(wk, pb & 255u) + br; bg = __umul24(wk, (pb >> 8) & 255u) + bg; bb = __umul24(wk, (pb >> 16) & 255u) + bb;
+                }
+                uint32_t* hrow = h_s + (r - ry0 + rr) * kResTileX + o;       // (the second row of an odd tail lands in the spare row)
+                hrow[0] = resample_px(ar, ag, ab);
+                hrow[kResTileX] = resample_px(br, bg, bb);
+            }
+        }
+        __syncthreads();
+    }
+    // (3) vertical pass: output pixel (ox0 + o, oy0 + sub)
+    const bool valid = o < nox && sub < noy;
+    uint32_t ar = 1u << (kResWeightShift - 1), ag = ar, ab = ar;
+    if (valid) {
+        const int n = ny_s[sub];
+        const int32_t* w = wy_s + sub * G.taps_y;
+        const uint32_t* hcol = h_s + (fy_s[sub] - ry0) * kResTileX + o;
+        for (int k = 0; k < n; k++) {
+            const uint32_t wk = (uint32_t)w[k], pa = hcol[k * kResTileX];
+            ar = __umul24(wk, pa & 255u) + ar; ag = __umul24(wk, (pa >> 8) & 255u) + ag; ab = __umul24(wk, (pa >> 16) & 255u) + ab;
+        }
+    }
+    const uint32_t px = resample_px(ar, ag, ab);
+    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(dst);
+    const uint32_t plane_elems = (uint32_t)G.ow * (uint32_t)G.oh;
+    const uint32_t at = (uint32_t)(oy0 + sub) * (uint32_t)G.ow + (uint32_t)(ox0 + o);
+    const uint32_t oob = valid ? 0u : kOobBit;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        const Elem e = tab_s[ch * 256 + ((px >> (8 * ch)) & 255u)];
+        const uint32_t voff = (((uint32_t)ch * plane_elems + at) * (uint32_t)sizeof(Elem)) | oob;
+        if constexpr (sizeof(Elem) == 4) __builtin_amdgcn_raw_buffer_store_b32(e, rs, (int)voff, 0, kAuxFrameStore);
+        else __builtin_amdgcn_raw_buffer_store_b16(e, rs, (int)voff, 0, kAuxFrameStore);
+    }
+}
+
 // ---- measured HBM roofline -----------------------------------------------------------
 // One 16-byte element per thread, no loop: the fastest of the copy shapes probed on MI355X
 // (tools/probe/bw_probe.cpp: 6.3 TB/s vs 4.8-5.9 TB/s for grid-stride forms).

@@ -128,6 +128,12 @@ struct leon_pipeline {
     uint32_t* d_tensor_table = nullptr;
     uint32_t* h_tensor_ids = nullptr;
     uint32_t* d_tensor_ids = nullptr;
+    // ... resampled to a model's input size (leon_pipeline_tensor_resize; geom.resized = 0: the full-size tensor, k_tensor): the
+    // tables of both axes as k_resample reads them -- first_x, count_x, Wx, first_y, count_y, Wy in one int32 buffer
+    leon_pipeline_tensor_geometry tensor_geom{};
+    std::vector<int32_t> resize_tabs;
+    leon::ResampleGeom resample_geom{};
+    int32_t* d_resize_tabs = nullptr;
     bool gpu_parser = false;
     // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
     // window n + 2, on a second stream: a parse launch lasts as long as its longest slice (one lane, symbol after symbol) and
@@ -519,6 +525,103 @@ int tensor_table_build(const leon_pipeline_config* cfg, const leon_pipeline_tens
             if (!finite) return fail(LEON_ERR_INVALID, "tensor table: value %d of channel %d is not finite in the element type (dtype %d)", v, c, dtype);
         }
     if (dtype_out) *dtype_out = dtype;
+    return LEON_OK;
+}
+
+// ---- output TENSOR at a model's input size: the tables of one axis (the definition of include/leon_pipeline.h) --------
+
+// first[o], count[o], weights[o * max_taps + k] (zero behind count[o]); *taps = the largest count.  Every refusal of one axis is here.
+// Doubles, evaluated as written (the library is compiled with -ffp-contract=off; the pragma holds it for other builds).
+int resize_axis_build(const char* axis, int32_t in_size, int32_t crop_start, int32_t crop_size, int32_t out_size, int32_t filter,
+                      int32_t* first, int32_t* count, int32_t* weights, int32_t max_taps, int32_t* taps)
+{
+#pragma clang fp contract(off)
+    if (filter != LEON_RESIZE_TRIANGLE) return fail(LEON_ERR_INVALID, "resize filter %d (LEON_RESIZE_TRIANGLE is the only one)", filter);
+    if (out_size < 1 || out_size > 4096) return fail(LEON_ERR_INVALID, "resize: output %s %d is outside 1 .. 4096", axis, out_size);
+    if (in_size < 1 || crop_size < 1 || crop_start < 0 || crop_start > in_size || crop_size > in_size - crop_start)
+        return fail(LEON_ERR_INVALID, "resize: the crop box (%s: start %d, size %d) is empty or leaves the frame (%d)", axis, crop_start, crop_size, in_size);
+    if ((int64_t)crop_size > 16 * (int64_t)out_size) return fail(LEON_ERR_INVALID, "resize: %s %d -> %d reduces by more than 16", axis, crop_size, out_size);
+    if (max_taps < 1) return fail(LEON_ERR_INVALID, "resize: max_taps %d", max_taps);
+    const double scale = (double)crop_size / (double)out_size;
+    const double fscale = scale < 1.0 ? 1.0 : scale, support = fscale;
+    int32_t most = 0;
+    double w[LEON_RESIZE_MAX_TAPS + 2];
+    for (int32_t o = 0; o < out_size; o++) {
+        const double center = (double)crop_start + ((double)o + 0.5) * scale;
+        int32_t lo = (int32_t)(center - support + 0.5), hi = (int32_t)(center + support + 0.5);
+        if (lo < 0) lo = 0;
+        if (hi > in_size) hi = in_size;
+        const int32_t n = hi - lo;
+        if (n < 1 || n > LEON_RESIZE_MAX_TAPS) return fail(LEON_ERR_INVALID, "resize: %s output %d has %d taps", axis, o, n);
+        if (n > max_taps) return fail(LEON_ERR_INVALID, "resize: %s output %d has %d taps, max_taps is %d", axis, o, n, max_taps);
+        double sum = 0.0;
+        for (int32_t k = 0; k < n; k++) {
+            const double x = ((double)(lo + k) - center + 0.5) / fscale;
+            const double t = 1.0 - std::fabs(x);
+            w[k] = t > 0.0 ? t : 0.0;
+            sum += w[k];
+        }
+        if (!(sum > 0.0)) return fail(LEON_ERR_INVALID, "resize: %s output %d has no weight", axis, o);
+        if (first) first[o] = lo;
+        if (count) count[o] = n;
+        if (weights)
+            for (int32_t k = 0; k < max_taps; k++) weights[(size_t)o * max_taps + k] = k < n ? (int32_t)(0.5 + (w[k] / sum) * 4194304.0) : 0;
+        if (n > most) most = n;
+    }
+    if (taps) *taps = most;
+    return LEON_OK;
+}
+
+bool resize_asked(const leon_pipeline_tensor_resize* rz)
+{
+    return rz && (rz->crop_x | rz->crop_y | rz->crop_width | rz->crop_height | rz->out_width | rz->out_height | rz->filter) != 0;
+}
+
+// What create makes of the resize settings: the geometry in force, the table buffer and k_resample's constants
+int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
+{
+    const int32_t fw = p->vinfo.frame_width, fh = p->vinfo.frame_height;
+    leon_pipeline_tensor_geometry& g = p->tensor_geom;
+    g = leon_pipeline_tensor_geometry{fw, fh, 0, 0, fw, fh, 1, 1, 0};
+    if (!resize_asked(rz)) return LEON_OK;
+    g.resized = 1;
+    g.width = rz->out_width;
+    g.height = rz->out_height;
+    if (rz->crop_x | rz->crop_y | rz->crop_width | rz->crop_height) {
+        g.crop_x = rz->crop_x; g.crop_y = rz->crop_y; g.crop_width = rz->crop_width; g.crop_height = rz->crop_height;
+    }
+    int rc;
+    // once for the refusals and the tap counts, then into the buffer with rows of exactly that length
+    if ((rc = resize_axis_build("width", fw, g.crop_x, g.crop_width, g.width, rz->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS, &g.taps_x)) != LEON_OK) return rc;
+    if ((rc = resize_axis_build("height", fh, g.crop_y, g.crop_height, g.height, rz->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS, &g.taps_y)) != LEON_OK) return rc;
+    leon::ResampleGeom& G = p->resample_geom;
+    G = leon::ResampleGeom{};
+    G.fw = fw; G.fh = fh; G.ow = g.width; G.oh = g.height;
+    // rows of Wx are an odd number of entries long (zero behind count[o]): the horizontal pass's lanes are output columns and read
+    // Wx[o][k] for one k together -- 32 entries a row (ratio 16) would put them all on one LDS bank, 18 (1080p -> 224) on every other
+    G.taps_x = g.taps_x | 1; G.taps_y = g.taps_y;
+    G.off_cx = (uint32_t)g.width;
+    G.off_wx = G.off_cx + (uint32_t)g.width;
+    G.off_fy = G.off_wx + (uint32_t)g.width * (uint32_t)G.taps_x;
+    G.off_cy = G.off_fy + (uint32_t)g.height;
+    G.off_wy = G.off_cy + (uint32_t)g.height;
+    p->resize_tabs.assign((size_t)G.off_wy + (size_t)g.height * g.taps_y, 0);
+    int32_t* t = p->resize_tabs.data();
+    if ((rc = resize_axis_build("width", fw, g.crop_x, g.crop_width, g.width, rz->filter, t, t + G.off_cx, t + G.off_wx, G.taps_x, nullptr)) != LEON_OK) return rc;
+    if ((rc = resize_axis_build("height", fh, g.crop_y, g.crop_height, g.height, rz->filter, t + G.off_fy, t + G.off_cy, t + G.off_wy, g.taps_y, nullptr)) != LEON_OK) return rc;
+    // What k_resample's LDS is sized for.  Within the limits above neither check can fail (at most 544 columns and 147 rows:
+    // leon_kernels.h has the arithmetic); they stand guard for the kernel's chunk loop, which needs at least one row pair per chunk
+    // (rc >= 2) to advance, should a limit ever be widened without the kernel.
+    for (int32_t o = 0; o < g.width; o += leon::kResTileX) {
+        const int32_t l = std::min(o + leon::kResTileX, g.width) - 1;
+        const int32_t sw = (t[l] + t[G.off_cx + l] - (t[o] & ~7) + 7) & ~7;
+        if (leon::resample_col(sw) * 2 > leon::kResStagePx) return fail(LEON_ERR_INVALID, "resize: a tile's source footprint of %d columns does not fit the staging buffer", sw);
+    }
+    for (int32_t o = 0; o < g.height; o += leon::kResTileY) {
+        const int32_t l = std::min(o + leon::kResTileY, g.height) - 1;
+        const int32_t rows = t[G.off_fy + l] + t[G.off_cy + l] - (t[G.off_fy + o] & ~1);
+        if (rows + 1 > leon::kResHRows) return fail(LEON_ERR_INVALID, "resize: a tile's source footprint of %d rows does not fit", rows);
+    }
     return LEON_OK;
 }
 
@@ -942,6 +1045,14 @@ void launch_k_tensor(const leon_pipeline* p, const uint32_t* ids, unsigned n, co
     hipLaunchKernelGGL(leon::k_tensor<DTYPE>, dim3((G.n_items + leon::kRgbaBlock - 1) / leon::kRgbaBlock, 1, n), dim3(leon::kRgbaBlock), 0, p->dec->stream,
                        (const uint8_t*)p->d_planes, p->d_tensor, ids, (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, G);
 }
+// ... at a model's input size: k_resample in k_tensor's place, a workgroup per tile of kResTileX x kResTileY output pixels
+template <int DTYPE>
+void launch_k_resample(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::ResampleGeom& G)
+{
+    const dim3 grid((unsigned)((G.ow + leon::kResTileX - 1) / leon::kResTileX), (unsigned)((G.oh + leon::kResTileY - 1) / leon::kResTileY), n);
+    hipLaunchKernelGGL(leon::k_resample<DTYPE>, grid, dim3(leon::kRgbaBlock), 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, ids,
+                       (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, G);
+}
 int launch_tensors(leon_pipeline* p, const PipeWindow* w)
 {
     const size_t n = w->frame_ids.size();
@@ -951,6 +1062,21 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
     uint32_t* dv = p->d_tensor_ids + (size_t)w->ring * entry;
     for (size_t i = 0; i < n; i++) h[i] = (uint32_t)((size_t)w->ring * entry) + w->frame_ids[i];
     HIP_TRY(hipMemcpyAsync(dv, h, n * 4, hipMemcpyHostToDevice, p->dec->stream));
+    if (p->tensor_geom.resized) {
+        leon::ResampleGeom R = p->resample_geom;
+        R.luma_stride = p->planes_geom.luma_stride; R.chroma_stride = p->planes_geom.chroma_stride;
+        R.cb_off = p->planes_geom.cb_off; R.cr_off = p->planes_geom.cr_off;
+        R.planes_pitch_lo = (uint32_t)(p->planes_bytes & 0xffffffffu); R.planes_pitch_hi = (uint32_t)((uint64_t)p->planes_bytes >> 32);
+        R.tensor_pitch_lo = (uint32_t)(p->tensor_pitch & 0xffffffffu); R.tensor_pitch_hi = (uint32_t)((uint64_t)p->tensor_pitch >> 32);
+        for (size_t at = 0; at < n; at += 65535) {
+            const unsigned m = (unsigned)std::min<size_t>(65535, n - at);
+            if (p->tensor_dtype == LEON_TENSOR_F16) launch_k_resample<leon::kTensorF16>(p, dv + at, m, R);
+            else if (p->tensor_dtype == LEON_TENSOR_BF16) launch_k_resample<leon::kTensorBf16>(p, dv + at, m, R);
+            else launch_k_resample<leon::kTensorF32>(p, dv + at, m, R);
+        }
+        HIP_TRY(hipGetLastError());
+        return LEON_OK;
+    }
     leon::TensorGeom G{};
     G.fw = p->vinfo.frame_width; G.fh = p->vinfo.frame_height;
     G.fast = (G.fw & 7) == 0;
@@ -1229,7 +1355,7 @@ constexpr size_t kMaxVlcIndexLds = 160 * 1024 - 512;
 
 // Create, stage 1: what the config and the stream decide -- the shards, the run, W / R / K, the longest GOP, the front
 // end, the output and its roads, info.  No HIP call and no allocation: a refused config leaves nothing to free but p.
-int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tcfg, const uint8_t* stream, size_t bytes, size_t valid_bytes)
+int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tcfg, const leon_pipeline_tensor_resize* rz, const uint8_t* stream, size_t bytes, size_t valid_bytes)
 {
     leon_vlc_stream* st = nullptr;
     // the container header, the key map and the first sequence header must have arrived
@@ -1328,7 +1454,9 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
         if (rc != LEON_OK) return rc;
         p->tensor_elem = p->tensor_dtype == LEON_TENSOR_F32 ? 4 : 2;
         p->tensor_table.resize(3 * 256 * p->tensor_elem);
-        p->tensor_bytes = (size_t)3 * p->vinfo.frame_height * p->vinfo.frame_width * p->tensor_elem;
+        const int rrc = plan_resize(p, rz);
+        if (rrc != LEON_OK) return rrc;
+        p->tensor_bytes = (size_t)3 * p->tensor_geom.height * p->tensor_geom.width * p->tensor_elem;
         p->tensor_pitch = pad256(p->tensor_bytes);
         p->info.tensor_dtype = p->tensor_dtype;
         p->info.tensor_element_bytes = (int32_t)p->tensor_elem;
@@ -1336,6 +1464,7 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
         p->info.tensor_frame_pitch = p->tensor_pitch;
         p->info.tensor_gop_pitch = (uint64_t)p->tensor_pitch * (uint64_t)p->max_pics;
     } else if (tcfg && tcfg->dtype) return fail(LEON_ERR_INVALID, "tensor dtype %d without LEON_PIPELINE_OUTPUT_TENSOR in output", tcfg->dtype);
+    else if (resize_asked(rz)) return fail(LEON_ERR_INVALID, "resize settings (%d x %d) without LEON_PIPELINE_OUTPUT_TENSOR in output %d", rz->out_width, rz->out_height, cfg->output);
     // the frames' planes (output YCbCr): the layout of include/leon_pipeline.h, one record per frame, A behind Cr for yuva
     p->output = cfg->output ? cfg->output : LEON_PIPELINE_OUTPUT_RGBA;
     p->planes_geom = planes_layout(p->vinfo.frame_width, p->vinfo.frame_height, &p->planes_bytes);
@@ -1455,6 +1584,11 @@ int allocate_pipeline(leon_pipeline* p)
             hipHostMalloc((void**)&p->h_tensor_ids, ids, hipHostMallocDefault) != hipSuccess)
             return hip_fail(LEON_ERR_NOMEM, "tensor table and frame index ring");
         if (hipMemcpy(p->d_tensor_table, p->tensor_table.data(), p->tensor_table.size(), hipMemcpyHostToDevice) != hipSuccess) return hip_fail(LEON_ERR_HIP, "tensor table");
+        if (p->tensor_geom.resized) {
+            const size_t tb = p->resize_tabs.size() * 4;
+            if (hipMalloc((void**)&p->d_resize_tabs, tb) != hipSuccess) return hip_fail(LEON_ERR_NOMEM, "resize tables");
+            if (hipMemcpy(p->d_resize_tabs, p->resize_tabs.data(), tb, hipMemcpyHostToDevice) != hipSuccess) return hip_fail(LEON_ERR_HIP, "resize tables");
+        }
     }
     if ((p->output & LEON_PIPELINE_OUTPUT_RGBA) && (rc = alloc_ring(p, &p->d_rgba, p->frame_bytes, "RGBA")) != LEON_OK) return rc;
     p->ring_owner.assign((size_t)p->R, -1);
@@ -1555,12 +1689,33 @@ int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes)
 int leon_pipeline_create_tensor(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const uint8_t* stream, size_t bytes,
                                 size_t valid_bytes, leon_pipeline_callback cb, void* user, leon_pipeline** out)
 {
+    return leon_pipeline_create_tensor_resized(cfg, tensor, nullptr, stream, bytes, valid_bytes, cb, user, out);
+}
+
+int leon_pipeline_resize_weights(int32_t in_size, int32_t crop_start, int32_t crop_size, int32_t out_size, int32_t filter,
+                                 int32_t* first, int32_t* count, int32_t* weights, int32_t max_taps)
+{
+    if (!first || !count || !weights) return fail(LEON_ERR_INVALID, "null argument");
+    return resize_axis_build("axis", in_size, crop_start, crop_size, out_size, filter, first, count, weights, max_taps, nullptr);
+}
+
+int leon_pipeline_get_tensor_geometry(leon_pipeline* p, leon_pipeline_tensor_geometry* out)
+{
+    if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR)) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    *out = p->tensor_geom;
+    return LEON_OK;
+}
+
+int leon_pipeline_create_tensor_resized(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const leon_pipeline_tensor_resize* resize,
+                                        const uint8_t* stream, size_t bytes, size_t valid_bytes, leon_pipeline_callback cb, void* user, leon_pipeline** out)
+{
     if (!cfg || !stream || bytes < 16 || !out) return fail(LEON_ERR_INVALID, "null argument");
     if (valid_bytes > bytes) return fail(LEON_ERR_INVALID, "%zu valid bytes of a stream of %zu", valid_bytes, bytes);
     *out = nullptr;
     leon_pipeline* p = new (std::nothrow) leon_pipeline();
     if (!p) return fail(LEON_ERR_NOMEM, "out of host memory");
-    int rc = plan_pipeline(p, cfg, tensor, stream, bytes, valid_bytes);
+    int rc = plan_pipeline(p, cfg, tensor, resize, stream, bytes, valid_bytes);
     if (rc != LEON_OK) { delete p; return rc; }
     p->cb = cb;
     p->user = user;
@@ -1784,6 +1939,7 @@ void leon_pipeline_destroy(leon_pipeline* p)
     if (p->d_tensor) big_free(p->d_tensor);
     if (p->d_tensor_table) hipFree(p->d_tensor_table);
     if (p->d_tensor_ids) hipFree(p->d_tensor_ids);
+    if (p->d_resize_tabs) hipFree(p->d_resize_tabs);
     if (p->h_tensor_ids) hipHostFree(p->h_tensor_ids);
     if (p->copy_stream) hipStreamDestroy(p->copy_stream);
     if (p->dec) leon_destroy(p->dec);

@@ -29,6 +29,9 @@
  *                                  'float32', opts.tensorScale / tensorBias [r, g, b] (default 1/255 and 0: values in [0, 1]);
  *                                  element = to_dtype(float32(v * scale[c] + bias[c])) of the CPU-twin colour value v;
  *                                  stats() reports tensorDtype, tensorElementBytes, tensorFrameBytes, tensorFramePitch, tensorGopPitch
+ *                                  opts.tensorSize [h, w] (and opts.tensorCrop [x, y, w, h], frame pixels; default the whole frame):
+ *                                  that crop box resampled on the device to h x w (antialiased triangle filter, include/leon_pipeline.h)
+ *                                  -- readTensor then returns [3][h][w]; stats() reports tensorWidth, tensorHeight
  *   p.releaseWindow(window); p.stats(); p.destroy();
  */
 const path = require('path');
@@ -54,7 +57,16 @@ class LeonPipeline extends EventEmitter {
       if (!(tensorDtype in dtypes)) throw new TypeError("tensorDtype: 'float16', 'bfloat16' or 'float32'");
       tensorDtype = dtypes[tensorDtype];
     }
-    this._p = addon.createPipeline(stream, Object.assign({}, opts, { output, tensorDtype }), (w, frames, status) => this._deliver(w, frames, status));
+    // tensorSize [h, w] (, tensorCrop [x, y, w, h] in frame pixels): the tensors resampled on the device to a model's input size
+    const ints = (v, n, what) => {
+      if (v === undefined || v === null) return new Array(n).fill(0);
+      if (!Array.isArray(v) || v.length !== n || !v.every(Number.isInteger)) throw new TypeError(what);
+      return v;
+    };
+    const [tensorOutHeight, tensorOutWidth] = ints(opts.tensorSize, 2, 'tensorSize: [height, width]');
+    const [tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight] = ints(opts.tensorCrop, 4, 'tensorCrop: [x, y, width, height]');
+    const resize = { tensorOutHeight, tensorOutWidth, tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight };
+    this._p = addon.createPipeline(stream, Object.assign({}, opts, { output, tensorDtype }, resize), (w, frames, status) => this._deliver(w, frames, status));
   }
 
   _deliver(window, frames, status) {

@@ -36,6 +36,7 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_get_stats", "leon_pipeline_read_frame", "leon_pipeline_error", "leon_pipeline_destroy", "leon_pipeline_seek",
     "leon_pipeline_read_frame_planes",
     "leon_pipeline_create_tensor", "leon_pipeline_tensor_table", "leon_pipeline_window_tensors", "leon_pipeline_read_tensor",
+    "leon_pipeline_create_tensor_resized", "leon_pipeline_resize_weights", "leon_pipeline_get_tensor_geometry",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -73,6 +74,70 @@ def tensor_table(dtype="float16", scale=None, bias=None):
         raise ValueError("tensor dtype %r" % (dtype,))
     x = f32.view(np.uint32).astype(np.uint64)
     return ((x + 0x7fff + ((x >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+RESIZE_TRIANGLE = 0          # LEON_RESIZE_TRIANGLE, the only filter
+RESIZE_MAX_TAPS = 33         # LEON_RESIZE_MAX_TAPS
+RESIZE_PRECISION = 22
+
+
+def resize_weights(in_size, crop_start, crop_size, out_size):
+    """The tables of one axis of the resized tensor output (include/leon_pipeline.h), in numpy / Python floats and independent of
+    the C code: (first[out], count[out], weights[out, taps]) with taps = the largest count, weights int32 with 22 fractional bits
+    and zero behind count[o].  An antialiased triangle filter over crop_start .. crop_start + crop_size of an axis of in_size
+    samples: taps may leave the crop box, never the axis.  ValueError where the library refuses."""
+    in_size, in0, crop_size, out_size = int(in_size), int(crop_start), int(crop_size), int(out_size)
+    if not 1 <= out_size <= 4096:
+        raise ValueError("output size %d is outside 1 .. 4096" % out_size)
+    if in_size < 1 or crop_size < 1 or in0 < 0 or in0 + crop_size > in_size:
+        raise ValueError("the crop (%d, %d) is empty or leaves the axis (%d)" % (in0, crop_size, in_size))
+    if crop_size > 16 * out_size:
+        raise ValueError("%d -> %d reduces by more than 16" % (crop_size, out_size))
+    scale = float(crop_size) / float(out_size)
+    fscale = max(scale, 1.0)
+    support = fscale
+    first, rows = [], []
+    for o in range(out_size):
+        center = in0 + (o + 0.5) * scale
+        lo = max(0, int(center - support + 0.5))
+        hi = min(in_size, int(center + support + 0.5))
+        w = [max(0.0, 1.0 - abs((lo + k - center + 0.5) / fscale)) for k in range(hi - lo)]
+        total = 0.0
+        for v in w:
+            total += v
+        first.append(lo)
+        rows.append([int(0.5 + (v / total) * float(1 << RESIZE_PRECISION)) for v in w])
+    count = np.asarray([len(r) for r in rows], dtype=np.int32)
+    weights = np.zeros((out_size, int(count.max())), dtype=np.int32)
+    for o, r in enumerate(rows):
+        weights[o, :len(r)] = r
+    return np.asarray(first, dtype=np.int32), count, weights
+
+
+def _resize_pass(img, first, count, weights):
+    """one pass along axis 1 of img [rows, in, channels] uint8 -> [rows, out, channels] uint8"""
+    out = np.empty((img.shape[0], len(first), img.shape[2]), dtype=np.uint8)
+    src = img.astype(np.int64)
+    for o in range(len(first)):
+        n = int(count[o])
+        acc = np.tensordot(src[:, first[o]:first[o] + n, :], weights[o, :n].astype(np.int64), axes=([1], [0]))
+        out[:, o, :] = np.clip((acc + (1 << (RESIZE_PRECISION - 1))) >> RESIZE_PRECISION, 0, 255)
+    return out
+
+
+def resize_rgb(rgb, crop, size):
+    """The resized tensor output's 8-bit colour values, in numpy: rgb [H, W, C] uint8 (the frame), crop = (x, y, width, height) in
+    frame pixels (None: the whole frame), size = (out_height, out_width) -> [out_height, out_width, C] uint8.  Horizontal pass first
+    with an 8-bit result, then vertical (include/leon_pipeline.h has the definition)."""
+    rgb = np.asarray(rgb, dtype=np.uint8)
+    fh, fw = rgb.shape[:2]
+    x, y, w, h = (0, 0, fw, fh) if crop is None or not any(crop) else crop
+    oh, ow = size
+    fx, nx, wx = resize_weights(fw, x, w, ow)
+    fy, ny, wy = resize_weights(fh, y, h, oh)
+    lo, hi = int(fy.min()), int((fy + ny).max())          # the rows the vertical pass taps
+    hz = _resize_pass(rgb[lo:hi], fx, nx, wx)
+    return _resize_pass(hz.transpose(1, 0, 2), fy - lo, ny, wy).transpose(1, 0, 2).copy()
 
 
 def planes_layout(frame_width, frame_height, alpha=False):
@@ -142,6 +207,16 @@ class PipelineConfig(C.Structure):
 
 class PipelineTensorConfig(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+class PipelineTensorResize(C.Structure):
+    _fields_ = [("crop_x", C.c_int32), ("crop_y", C.c_int32), ("crop_width", C.c_int32), ("crop_height", C.c_int32),
+                ("out_width", C.c_int32), ("out_height", C.c_int32), ("filter", C.c_int32)]
+
+
+class PipelineTensorGeometry(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("crop_width", C.c_int32),
+                ("crop_height", C.c_int32), ("taps_x", C.c_int32), ("taps_y", C.c_int32), ("resized", C.c_int32)]
 
 
 class PipelineFrame(C.Structure):
@@ -235,6 +310,10 @@ def load():
     lib.leon_pipeline_read_frame_planes.argtypes = [C.c_void_p, C.POINTER(PipelineFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.leon_pipeline_create_tensor.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.c_void_p, C.c_size_t, C.c_size_t, PIPELINE_CB,
                                                 C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.leon_pipeline_create_tensor_resized.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.POINTER(PipelineTensorResize), C.c_void_p,
+                                                        C.c_size_t, C.c_size_t, PIPELINE_CB, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.leon_pipeline_resize_weights.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.leon_pipeline_get_tensor_geometry.argtypes = [C.c_void_p, C.POINTER(PipelineTensorGeometry)]
     lib.leon_pipeline_tensor_table.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.c_void_p]
     lib.leon_pipeline_window_tensors.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int32]
     lib.leon_pipeline_read_tensor.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
@@ -506,11 +585,14 @@ class Pipeline:
     output="tensor" / "rgba+tensor" / "ycbcr+tensor" / "all" (PIPELINE_TENSOR_OUTPUTS): the frames carry a planar [3, H, W] tensor
     (tensor = device address) of tensor_dtype "float16" / "bfloat16" / "float32", element = tensor_table(dtype, scale, bias)[c][colour
     value]; tensor_scale / tensor_bias: three floats each (None: 1/255 and 0).  read_tensor(frame) copies it to the host,
-    tensor_view(frame) and window_tensor(frames) wrap it in place as torch tensors."""
+    tensor_view(frame) and window_tensor(frames) wrap it in place as torch tensors.
+    tensor_size=(out_h, out_w) [, tensor_crop=(x, y, w, h) in frame pixels]: the tensors are that crop box (default: the whole frame)
+    resampled on the device to a model's input size -- element = table[c][resize_rgb(rgb, crop, size)] --, and every tensor shape
+    above is [3, out_h, out_w] (tensor_geometry has the values in force)."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
-                 output="rgba", tensor_dtype="float16", tensor_scale=None, tensor_bias=None):
+                 output="rgba", tensor_dtype="float16", tensor_scale=None, tensor_bias=None, tensor_size=None, tensor_crop=None, tensor_filter=RESIZE_TRIANGLE):
         self.lib = load()
         self.device_id = device_id
         # a name of PIPELINE_OUTPUTS, or the raw bit set (anything the library does not know is refused by create)
@@ -519,6 +601,11 @@ class Pipeline:
         if out_bits > 0 and out_bits & PIPELINE_OUTPUT_TENSOR:
             tcfg = PipelineTensorConfig(_tensor_dtype_code(tensor_dtype), (C.c_float * 3)(*([0, 0, 0] if tensor_scale is None else tensor_scale)),
                                         (C.c_float * 3)(*([0, 0, 0] if tensor_bias is None else tensor_bias)))
+        rcfg = None
+        if tensor_size is not None or tensor_crop is not None or tensor_filter:      # (the library refuses what does not go together)
+            oh, ow = (0, 0) if tensor_size is None else tensor_size
+            cx, cy, cw, ch = (0, 0, 0, 0) if tensor_crop is None else tensor_crop
+            rcfg = PipelineTensorResize(int(cx), int(cy), int(cw), int(ch), int(ow), int(oh), int(tensor_filter))
         self._data = (C.c_uint8 * len(data)).from_buffer_copy(data)      # must outlive the pipeline
         self._on_window = on_window
         self.windows = 0
@@ -571,7 +658,10 @@ class Pipeline:
         h = C.c_void_p()
         self.h = None
         # valid_bytes: the stream is still arriving (leon_pipeline_create_partial); feed() reports progress
-        if tcfg is not None:
+        if rcfg is not None:
+            rc = self.lib.leon_pipeline_create_tensor_resized(C.byref(cfg), None if tcfg is None else C.byref(tcfg), C.byref(rcfg), self._data, len(data),
+                                                              len(data) if valid_bytes is None else int(valid_bytes), self._cb, None, C.byref(h))
+        elif tcfg is not None:
             rc = self.lib.leon_pipeline_create_tensor(C.byref(cfg), C.byref(tcfg), self._data, len(data), len(data) if valid_bytes is None else int(valid_bytes),
                                                       self._cb, None, C.byref(h))
         elif valid_bytes is None:
@@ -583,6 +673,12 @@ class Pipeline:
         info = PipelineInfo()
         rc = self.lib.leon_pipeline_get_info(self.h, C.byref(info))
         self.info = info
+        # the tensors' shape: the frame's, or tensor_size (None without tensor output)
+        self.tensor_geometry = None
+        if rc == OK and info.tensor_dtype:
+            geom = PipelineTensorGeometry()
+            rc = self.lib.leon_pipeline_get_tensor_geometry(self.h, C.byref(geom))
+            self.tensor_geometry = geom
         ready.set()
         _chk(rc)
 
@@ -606,10 +702,11 @@ class Pipeline:
         return {TENSOR_F16: np.float16, TENSOR_BF16: np.uint16, TENSOR_F32: np.float32}[self.info.tensor_dtype]
 
     def read_tensor(self, frame):
-        """the frame's tensor as a host array [3, frame_height, frame_width]: float16 / float32, bfloat16 as uint16 bit patterns"""
+        """the frame's tensor as a host array [3, height, width] (tensor_geometry: the frame's size, or tensor_size): float16 / float32,
+        bfloat16 as uint16 bit patterns"""
         if not frame.get("tensor"):
             raise LeonError(ERR_INVALID, "the frame has no tensor (Pipeline output)")
-        out = np.empty((3, self.info.frame_height, self.info.frame_width), dtype=self._tensor_np_dtype())
+        out = np.empty((3, self.tensor_geometry.height, self.tensor_geometry.width), dtype=self._tensor_np_dtype())
         _chk(self.lib.leon_pipeline_read_tensor(self.h, frame["_window"], frame["_i"], out.ctypes.data))
         return out
 
@@ -631,7 +728,7 @@ class Pipeline:
         if not frame.get("tensor"):
             raise ValueError("the frame has no tensor (Pipeline output)")
         i = self.info
-        e, h, w = i.tensor_element_bytes, i.frame_height, i.frame_width
+        e, h, w = i.tensor_element_bytes, self.tensor_geometry.height, self.tensor_geometry.width
         return self._tensor_at(frame["tensor"], (3, h, w), (h * w * e, w * e, e), device_id)
 
     def window_tensor(self, frames, device_id=None):
@@ -642,7 +739,7 @@ class Pipeline:
             return None
         step = ptrs[1] - ptrs[0] if len(ptrs) > 1 else self.info.tensor_frame_pitch
         i = self.info
-        e, h, w = i.tensor_element_bytes, i.frame_height, i.frame_width
+        e, h, w = i.tensor_element_bytes, self.tensor_geometry.height, self.tensor_geometry.width
         if step <= 0 or step % e or step < i.tensor_frame_bytes or any(b - a != step for a, b in zip(ptrs, ptrs[1:])):
             return None
         return self._tensor_at(ptrs[0], (len(ptrs), 3, h, w), (step, h * w * e, w * e, e), device_id)

@@ -386,6 +386,7 @@ struct PipeHandle {
     std::mutex mu;
     std::map<int64_t, std::vector<leon_pipeline_frame>> out;   // delivered, not yet released
     leon_pipeline_info info{};
+    leon_pipeline_tensor_geometry tensor_geom{};      // all 0 without tensor output
     int64_t last_window = -1;               // notify thread, under mu
     int64_t floor = 0;                      // JavaScript thread: the first window of the latest seek
     bool seeked = false;
@@ -559,8 +560,8 @@ napi_value PipeReadPlanes(napi_env env, napi_callback_info info)
     return rc == LEON_OK ? o : throw_leon(env, rc);
 }
 
-// p.readTensor(window, i) -> Uint16Array (fp16 / bf16 bit patterns) or Float32Array, [3][frameHeight][frameWidth] packed: one frame's
-// tensor (output 'tensor' ...)
+// p.readTensor(window, i) -> Uint16Array (fp16 / bf16 bit patterns) or Float32Array, [3][tensorHeight][tensorWidth] packed (the frame's
+// size, or opts.tensorSize): one frame's tensor (output 'tensor' ...)
 napi_value PipeReadTensor(napi_env env, napi_callback_info info)
 {
     size_t argc = 2;
@@ -624,7 +625,7 @@ napi_value PipeStats(napi_env env, napi_callback_info info)
         {"chromaWidth", (double)h->info.chroma_width}, {"chromaHeight", (double)h->info.chroma_height},
         {"tensorDtype", (double)h->info.tensor_dtype}, {"tensorElementBytes", (double)h->info.tensor_element_bytes},
         {"tensorFrameBytes", (double)h->info.tensor_frame_bytes}, {"tensorFramePitch", (double)h->info.tensor_frame_pitch},
-        {"tensorGopPitch", (double)h->info.tensor_gop_pitch}};
+        {"tensorGopPitch", (double)h->info.tensor_gop_pitch}, {"tensorWidth", (double)h->tensor_geom.width}, {"tensorHeight", (double)h->tensor_geom.height}};
     for (auto& e : kv) {
         NAPI_OK(napi_create_double(env, e.val, &v));
         NAPI_OK(napi_set_named_property(env, o, e.k, v));
@@ -733,7 +734,17 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
         napi_throw_type_error(env, nullptr, "createPipeline: tensorScale / tensorBias must be arrays of three numbers");
         return nullptr;
     }
-    const bool tensor = (cfg.output & LEON_PIPELINE_OUTPUT_TENSOR) != 0 || tcfg.dtype != 0;
+    // ... resampled to a model's input size (leon_pipeline_tensor_resize; js/leon_pipeline.js spreads tensorSize / tensorCrop into these)
+    leon_pipeline_tensor_resize rcfg;
+    memset(&rcfg, 0, sizeof rcfg);
+    if (!(get_i32(env, argv[1], "tensorOutWidth", &rcfg.out_width, 0) && get_i32(env, argv[1], "tensorOutHeight", &rcfg.out_height, 0) &&
+          get_i32(env, argv[1], "tensorCropX", &rcfg.crop_x, 0) && get_i32(env, argv[1], "tensorCropY", &rcfg.crop_y, 0) &&
+          get_i32(env, argv[1], "tensorCropWidth", &rcfg.crop_width, 0) && get_i32(env, argv[1], "tensorCropHeight", &rcfg.crop_height, 0))) {
+        napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
+        return nullptr;
+    }
+    const bool resized = (rcfg.out_width | rcfg.out_height | rcfg.crop_x | rcfg.crop_y | rcfg.crop_width | rcfg.crop_height) != 0;
+    const bool tensor = (cfg.output & LEON_PIPELINE_OUTPUT_TENSOR) != 0 || tcfg.dtype != 0 || resized;
     PipeHandle* h = new PipeHandle();
     napi_value name;
     NAPI_OK(napi_create_string_utf8(env, "leon pipeline frames", NAPI_AUTO_LENGTH, &name));
@@ -765,7 +776,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
             }
         }
     }
-    int rc = tensor ? leon_pipeline_create_tensor(&cfg, &tcfg, (const uint8_t*)data, len, partial ? (size_t)valid : len, pipe_native_cb, h, &h->p)
+    int rc = tensor ? leon_pipeline_create_tensor_resized(&cfg, &tcfg, resized ? &rcfg : nullptr, (const uint8_t*)data, len, partial ? (size_t)valid : len, pipe_native_cb, h, &h->p)
            : partial ? leon_pipeline_create_partial(&cfg, (const uint8_t*)data, len, (size_t)valid, pipe_native_cb, h, &h->p)
                      : leon_pipeline_create(&cfg, (const uint8_t*)data, len, pipe_native_cb, h, &h->p);
     if (rc != LEON_OK) {
@@ -775,6 +786,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
         return throw_leon(env, rc);
     }
     leon_pipeline_get_info(h->p, &h->info);
+    if (h->info.tensor_dtype) leon_pipeline_get_tensor_geometry(h->p, &h->tensor_geom);
     napi_value obj;
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));

@@ -32,6 +32,12 @@ def main():
     ap.add_argument("--output", choices=["rgba", "ycbcr", "both", "tensor", "rgba+tensor", "ycbcr+tensor", "all"], default="rgba",
                     help="what the frames carry (leon_pipeline_config.output): RGBA, the YCbCr planes, planar float tensors, or a combination")
     ap.add_argument("--tensor-dtype", choices=["float16", "bfloat16", "float32"], default="float16", help="element type of --output tensor")
+    ap.add_argument("--tensor-size", type=int, nargs=2, metavar=("H", "W"), help="tensors resampled on the device to H x W (leon_pipeline_tensor_resize)")
+    ap.add_argument("--tensor-crop", type=int, nargs=4, metavar=("X", "Y", "W", "H"), help="the crop box --tensor-size resamples (frame pixels; default: the whole frame)")
+    ap.add_argument("--host-resize", type=int, nargs=2, metavar=("H", "W"),
+                    help="the route without --tensor-size, for comparison: full-size tensors, and the callback resizes every window's window_tensor view "
+                         "with torch.nn.functional.interpolate(mode='bilinear', antialias=True)")
+    ap.add_argument("--copy-rate", action="store_true", help="measure leon_measure_copy_bandwidth in this process first (the yardstick of a launch's rate)")
     ap.add_argument("--varied", action="store_true", help="the 16-GOP stream with 16 different contents (tools/stream_1080p.py) instead of --gops GOPs")
     a = ap.parse_args()
     cached = os.path.join(ROOT, "tools", "probe", "stream_1080p_%dgop.bin" % a.gops)
@@ -52,11 +58,29 @@ def main():
         hip = ctypes.CDLL("libamdhip64.so")
         f, t = ctypes.c_size_t(), ctypes.c_size_t()
         return f.value if hip.hipMemGetInfo(ctypes.byref(f), ctypes.byref(t)) == 0 else None
+    copy_gbps = None
+    if a.copy_rate:
+        dec = L.Decoder(96, 64, n_slots=3, device_id=0)
+        copy_gbps = dec.measure_copy_bandwidth()
+        dec.close()
+    on_window = None
+    if a.host_resize:
+        import torch
+
+        def on_window(window, frames):
+            fl = list(frames)
+            p = fl[0]["_pipe"]
+            t = p.window_tensor(fl)
+            parts = [t] if t is not None else [p.tensor_view(f)[None] for f in fl]
+            for x in parts:
+                torch.nn.functional.interpolate(x, size=tuple(a.host_resize), mode="bilinear", antialias=True, align_corners=False)
+            torch.cuda.synchronize()          # the window is released on return: the resize must have read it
     free0 = free_device_bytes()
     t0 = time.perf_counter()
     pipe = L.Pipeline(data, parser_threads=a.threads, gops_per_window=a.window, windows_in_flight=a.inflight, loop=a.loop, gpu_parser=a.gpu_parser,
-                      output=a.output, tensor_dtype=a.tensor_dtype)
+                      output=a.output, tensor_dtype=a.tensor_dtype, tensor_size=a.tensor_size, tensor_crop=a.tensor_crop, on_window=on_window)
     free1 = free_device_bytes()
+    pool = L.pool_stats()
     pipe.wait()
     wall = time.perf_counter() - t0
     s = pipe.stats()
@@ -67,11 +91,12 @@ def main():
                   % (pipe.info.frame_width, pipe.info.frame_height, {"rgba": "RGBA", "ycbcr": "YCbCr planes", "both": "RGBA + YCbCr planes", "tensor": "tensors", "rgba+tensor": "RGBA + tensors",
                      "ycbcr+tensor": "YCbCr planes + tensors", "all": "RGBA + YCbCr planes + tensors"}[a.output]),
         "output": a.output, "tensor_dtype": a.tensor_dtype if pipe.info.tensor_dtype else None,
-        "tensor_frame_bytes": pipe.info.tensor_frame_bytes, "windows_in_flight": a.inflight,
+        "tensor_frame_bytes": pipe.info.tensor_frame_bytes, "tensor_size": a.tensor_size, "tensor_crop": a.tensor_crop, "host_resize": a.host_resize, "windows_in_flight": a.inflight,
         "value": s["pictures"] / s["seconds"], "macroblocks_per_s": s["pictures"] * mbs / s["seconds"],
         "pictures": s["pictures"], "seconds": s["seconds"], "wall_seconds_incl_setup": wall, "windows": s["windows"],
         "slice_layer": "GPU (csrc/leon_vlc_gpu.h)" if a.gpu_parser else "host threads (libleon_vlc.so)",
         "device_gb_held_by_the_pipeline": (free0 - free1) / 1e9 if free0 is not None and free1 is not None else None,
+        "pool_held_gb": pool["held_bytes"] / 1e9, "pool_in_use_gb": pool["in_use_bytes"] / 1e9, "copy_gbps_same_process": copy_gbps,
         "parser_threads": pipe.info.parser_threads, "gops_per_window": pipe.info.gops_per_window,
         "parse_seconds_summed_over_threads": s["parse_seconds_sum"],
         "parser_pictures_per_s_per_thread": s["pictures"] / s["parse_seconds_sum"] if s["parse_seconds_sum"] else None,
