@@ -139,8 +139,8 @@ AnyPic any_of(const leon_sparse_picture& q)
     return a;
 }
 
-// launch class of a picture = 3 * output + type - 1, output 0: planes only (k_recon), 1: RGBA (k_recon_display), 2: the frame's
-// YCbCr planes, 3: both (k_recon_display_out)
+// launch class of a picture = 3 * (output - kOutSlots) + type - 1, output = what its launch writes besides the slot (leon_kernels.h):
+// kOutSlots nothing (k_recon), kOutRgba (k_recon_display), kOutYcbcr the frame's planes, kOutBoth (k_recon_display_out)
 constexpr int kClasses = 12;
 
 struct Staging {                 // device copy of one host-submitted picture
@@ -405,17 +405,55 @@ int guard_pending_conversions(leon_decoder* d, const int32_t* out_slots, int n)
     return LEON_OK;
 }
 
-// one launch of the type-specialised kernel over n pictures of that type
-// out: 0 planes only, 1 RGBA, 2 the frames' YCbCr planes (frames[i]: picture i's record), 3 both (class_of)
-int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, double dense_bytes, bool sparse = false, uint64_t entries = 0,
-                      int out = 0, uint8_t* const* frames = nullptr)
+// The reconstruction kernels by what the launch writes, picture type, boundary and alpha: kReconKernels[out - kOutSlots].t[type - 1]
+// .e[sparse][alpha].  Two signatures: `frames` for the launches that write frame planes (FrameOut), `plain` for the others.  (k_recon
+// runs a yuva picture's A plane as tasks of the same kernel; frame planes need the sparse boundary: no dense entry.)
+struct ReconEntry {
+    void (*plain)(const PicDesc*, Geom, const Tables*);
+    void (*frames)(const PicDesc*, Geom, const Tables*, FrameOut);
+};
+template <int OUT, int TYPE, bool SPARSE, bool ALPHA>
+constexpr ReconEntry recon_entry()
 {
-    const bool display = out != 0;
+    if constexpr (OUT == kOutSlots) return {k_recon<TYPE, SPARSE>, nullptr};
+    else if constexpr (OUT == kOutRgba) return {k_recon_display<TYPE, SPARSE, ALPHA>, nullptr};
+    else if constexpr (SPARSE) return {nullptr, k_recon_display_out<TYPE, true, ALPHA, OUT>};
+    else return {nullptr, nullptr};
+}
+struct ReconEntriesOfType { ReconEntry e[2][2]; };
+struct ReconEntriesOfOut { ReconEntriesOfType t[3]; };
+template <int OUT, int TYPE> constexpr ReconEntriesOfType kReconEntriesOfType = {
+    {{recon_entry<OUT, TYPE, false, false>(), recon_entry<OUT, TYPE, false, true>()}, {recon_entry<OUT, TYPE, true, false>(), recon_entry<OUT, TYPE, true, true>()}}};
+template <int OUT> constexpr ReconEntriesOfOut kReconEntriesOfOut = {{kReconEntriesOfType<OUT, 1>, kReconEntriesOfType<OUT, 2>, kReconEntriesOfType<OUT, 3>}};
+static_assert(kOutSlots + 1 == kOutRgba && kOutRgba + 1 == kOutYcbcr && kOutYcbcr + 1 == kOutBoth, "kReconKernels and the launch classes are indexed by out - kOutSlots");
+constexpr ReconEntriesOfOut kReconKernels[4] = {kReconEntriesOfOut<kOutSlots>, kReconEntriesOfOut<kOutRgba>, kReconEntriesOfOut<kOutYcbcr>, kReconEntriesOfOut<kOutBoth>};
+
+// dynamic LDS of a launch: the waves' strips (leon_kernels.h) + the extra that sets the occupancy of the fused display kernels
+// (display kernels: + kLdsLut of static LDS, the conversion tables)
+constexpr size_t recon_lds_bytes(int out, int type, bool sparse, bool alpha)
+{
+    if (out == kOutSlots) return (size_t)kWavesPerWG * kLdsPerWave;
+    const size_t pad = pair_task(type, sparse, alpha) ? (type == LEON_PIC_P ? kOccupancyPadPairP : 0)
+                     : !sparse && !alpha ? (type == LEON_PIC_I ? kOccupancyPadI : type == LEON_PIC_P ? kOccupancyPadP : kOccupancyPadB) : 0;
+    return (size_t)kWavesPerWG * display_strip_bytes(type, sparse, alpha) + pad;
+}
+// what every launch asked for before these sizes had one definition: a slip here changes the occupancy, or lets a kernel walk off its LDS
+static_assert(recon_lds_bytes(kOutSlots, 1, false, false) == 9728 && recon_lds_bytes(kOutSlots, 3, true, true) == 9728, "k_recon");
+static_assert(recon_lds_bytes(kOutRgba, 1, false, false) == 21504 && recon_lds_bytes(kOutRgba, 1, true, false) == 15360, "I display");
+static_assert(recon_lds_bytes(kOutRgba, 2, false, false) == 22784 && recon_lds_bytes(kOutRgba, 2, true, false) == 15360, "P display");
+static_assert(recon_lds_bytes(kOutRgba, 3, false, false) == 21760 && recon_lds_bytes(kOutRgba, 3, true, false) == 15360, "B display");
+static_assert(recon_lds_bytes(kOutRgba, 1, false, true) == 19456 && recon_lds_bytes(kOutRgba, 1, true, true) == 19456 && recon_lds_bytes(kOutRgba, 2, false, true) == 19456
+              && recon_lds_bytes(kOutRgba, 2, true, true) == 19456 && recon_lds_bytes(kOutRgba, 3, false, true) == 19456 && recon_lds_bytes(kOutRgba, 3, true, true) == 19456, "yuva display");
+static_assert(recon_lds_bytes(kOutBoth, 3, true, false) == recon_lds_bytes(kOutRgba, 3, true, false), "k_recon_display_out: as k_recon_display");
+
+// one launch of the type-specialised kernel over n pictures of that type
+// out: what the launch writes besides the slot, kOutSlots .. kOutBoth (frames[i]: picture i's frame planes record)
+int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, double dense_bytes, bool sparse = false, uint64_t entries = 0,
+                      int out = kOutSlots, uint8_t* const* frames = nullptr)
+{
     Geom G = d->geom;
     G.n_pics = n;
-    const bool alpha = d->geom.alpha != 0;
-    const bool pair = display && !sparse && !alpha && type != LEON_PIC_I;      // k_recon_display: recon_luma_pair, two tiles
-    if (display) {   // one task = one chroma group with everything above it (k_recon_display)
+    if (out != kOutSlots) {   // one task = one chroma group with everything above it (k_recon_display)
         G.tasks_per_pic = G.tasksC;
         G.wg_per_pic = (G.tasks_per_pic + kWavesPerWG - 1) / kWavesPerWG;
         G.inv_wg_per_pic = G.wg_per_pic == 1 ? 0u : (uint32_t)(((1ull << 32) + G.wg_per_pic - 1) / G.wg_per_pic);
@@ -439,60 +477,16 @@ int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, 
     }
     static_assert(64 * kWavesPerWG <= kReconMaxThreads, "k_recon is launched with more threads than its __launch_bounds__");
     const dim3 grid(G.n_wg), block(64 * kWavesPerWG);
-    // extra dynamic LDS per workgroup = the occupancy of the fused display kernels
-    const size_t lds_pad = pair ? (type == LEON_PIC_P ? kOccupancyPadPairP : 0)
-                                : display && !sparse && !alpha ? (type == LEON_PIC_I ? kOccupancyPadI : type == LEON_PIC_P ? kOccupancyPadP : kOccupancyPadB) : 0;
-    const size_t lds = (size_t)kWavesPerWG * (display ? (alpha ? kLdsPerWaveDisplayAlpha : (pair ? kLdsPerWaveDisplayPair : kLdsPerWaveDisplay)) : kLdsPerWave) + lds_pad;      // display kernels: + kLdsLut of static LDS (the conversion tables)
-    if (out >= 2) {                  // k_recon_display_out: the same tasks, LDS and occupancy as k_recon_display
+    const size_t lds = recon_lds_bytes(out, type, sparse, d->geom.alpha != 0);
+    const ReconEntry& k = kReconKernels[out - kOutSlots].t[type - 1].e[sparse][d->geom.alpha != 0];
+    if (out == kOutYcbcr || out == kOutBoth) {      // k_recon_display_out: the same tasks, LDS and occupancy as k_recon_display
         // (the pipeline's boundary only: the frames' planes are a pipeline output, and the pipeline submits group lists)
         if (!sparse) return fail(LEON_ERR_INVALID, "frame planes output needs the sparse boundary");
         FrameOut fo = d->frame_out;
         fo.frames = frames;
-        const int k = (type - 1) * 4 + (alpha ? 2 : 0) + (out == 3 ? 1 : 0);
-#define LEON_OUT_LAUNCH(T, A, O) hipLaunchKernelGGL((k_recon_display_out<T, true, A, O>), grid, block, lds, d->stream, d_descs, G, d->d_tables, fo)
-        switch (k) {
-        case 0: LEON_OUT_LAUNCH(1, false, kOutYcbcr); break;
-        case 1: LEON_OUT_LAUNCH(1, false, kOutBoth); break;
-        case 2: LEON_OUT_LAUNCH(1, true, kOutYcbcr); break;
-        case 3: LEON_OUT_LAUNCH(1, true, kOutBoth); break;
-        case 4: LEON_OUT_LAUNCH(2, false, kOutYcbcr); break;
-        case 5: LEON_OUT_LAUNCH(2, false, kOutBoth); break;
-        case 6: LEON_OUT_LAUNCH(2, true, kOutYcbcr); break;
-        case 7: LEON_OUT_LAUNCH(2, true, kOutBoth); break;
-        case 8: LEON_OUT_LAUNCH(3, false, kOutYcbcr); break;
-        case 9: LEON_OUT_LAUNCH(3, false, kOutBoth); break;
-        case 10: LEON_OUT_LAUNCH(3, true, kOutYcbcr); break;
-        default: LEON_OUT_LAUNCH(3, true, kOutBoth); break;
-        }
-#undef LEON_OUT_LAUNCH
-    } else if (display && alpha) {          // yuva: the A parts ride in the same task (k_recon_display<.., .., true>)
-        if (!sparse) {
-            if (type == LEON_PIC_I) hipLaunchKernelGGL((k_recon_display<1, false, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-            else if (type == LEON_PIC_P) hipLaunchKernelGGL((k_recon_display<2, false, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-            else hipLaunchKernelGGL((k_recon_display<3, false, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-        } else {
-            if (type == LEON_PIC_I) hipLaunchKernelGGL((k_recon_display<1, true, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-            else if (type == LEON_PIC_P) hipLaunchKernelGGL((k_recon_display<2, true, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-            else hipLaunchKernelGGL((k_recon_display<3, true, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-        }
-    } else if (display) {
-        if (!sparse) {
-            if (type == LEON_PIC_I) hipLaunchKernelGGL((k_recon_display<1, false>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-            else if (type == LEON_PIC_P) hipLaunchKernelGGL((k_recon_display<2, false>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-            else hipLaunchKernelGGL((k_recon_display<3, false>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-        } else {
-            if (type == LEON_PIC_I) hipLaunchKernelGGL((k_recon_display<1, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-            else if (type == LEON_PIC_P) hipLaunchKernelGGL((k_recon_display<2, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-            else hipLaunchKernelGGL((k_recon_display<3, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-        }
-    } else if (!sparse) {
-        if (type == LEON_PIC_I) hipLaunchKernelGGL((k_recon<1, false>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-        else if (type == LEON_PIC_P) hipLaunchKernelGGL((k_recon<2, false>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-        else hipLaunchKernelGGL((k_recon<3, false>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
+        hipLaunchKernelGGL(k.frames, grid, block, lds, d->stream, d_descs, G, d->d_tables, fo);
     } else {
-        if (type == LEON_PIC_I) hipLaunchKernelGGL((k_recon<1, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-        else if (type == LEON_PIC_P) hipLaunchKernelGGL((k_recon<2, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
-        else hipLaunchKernelGGL((k_recon<3, true>), grid, block, lds, d->stream, d_descs, G, d->d_tables);
+        hipLaunchKernelGGL(k.plain, grid, block, lds, d->stream, d_descs, G, d->d_tables);
     }
     HIP_TRY(hipGetLastError());
     if (d->timing) {
@@ -503,7 +497,7 @@ int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, 
 }
 
 // launch class of a picture: its type, and what its launch writes besides the slot (kClasses)
-inline int class_of(const AnyPic& a) { return 3 * (a.planes_out ? (a.p.rgba_out ? 3 : 2) : (a.p.rgba_out ? 1 : 0)) + a.p.type - 1; }
+inline int class_of(const AnyPic& a) { return 3 * ((a.planes_out ? (a.p.rgba_out ? kOutBoth : kOutYcbcr) : (a.p.rgba_out ? kOutRgba : kOutSlots)) - kOutSlots) + a.p.type - 1; }
 
 // descriptors sorted by class; one launch per class present.  frames: the frame-planes records beside the descriptors (classes 6 .. 11)
 int launch_recon(leon_decoder* d, const PicDesc* d_descs, const int count[kClasses], const double bytes[kClasses], bool sparse = false, const uint64_t* entries = nullptr,
@@ -517,7 +511,7 @@ int launch_recon(leon_decoder* d, const PicDesc* d_descs, const int count[kClass
     static const int order[kClasses] = {11, 8, 5, 2, 10, 7, 4, 1, 9, 6, 3, 0};
     for (int k : order) {
         if (count[k] > 0) {
-            int rc = launch_recon_type(d, k % 3 + 1, d_descs + at[k], count[k], bytes[k], sparse, entries ? entries[k] : 0, k / 3, frames ? frames + at[k] : nullptr);
+            int rc = launch_recon_type(d, k % 3 + 1, d_descs + at[k], count[k], bytes[k], sparse, entries ? entries[k] : 0, k / 3 + kOutSlots, frames ? frames + at[k] : nullptr);
             if (rc != LEON_OK) return rc;
         }
     }
@@ -996,7 +990,7 @@ int submit_picture_any(leon_decoder* d, const AnyPic& pic)
         rc = algo_bytes_of(d, pic.p, false, bytes);
         if (rc != LEON_OK) return rc;
     }
-    rc = launch_recon_type(d, type, d->d_desc_ring + at, 1, bytes, pic.sparse, pic.n_entries, pic.p.rgba_out != nullptr);
+    rc = launch_recon_type(d, type, d->d_desc_ring + at, 1, bytes, pic.sparse, pic.n_entries, pic.p.rgba_out ? kOutRgba : kOutSlots);
     if (rc != LEON_OK) return rc;
     rc = commit_descs(d, at, 1);
     if (rc != LEON_OK) return rc;

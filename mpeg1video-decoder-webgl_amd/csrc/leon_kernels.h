@@ -92,7 +92,9 @@ struct Tables {                  // per decoder
 // (include/leon_pipeline.h: rows padded to 64 bytes, planes on 256-byte boundaries), or both.  Pictures with planes output find
 // their frame's planes in FrameOut::frames[picture of the launch]: PicDesc keeps its 152 bytes, so the code of the RGBA kernels,
 // which index it, stays as it is.
-static constexpr int kOutRgba = 0, kOutYcbcr = 1, kOutBoth = 2;
+// What a launch writes besides the slot planes, from the host's launch classes down to the kernels' OUT: nothing (kOutSlots: k_recon),
+// RGBA (k_recon_display), the frame's planes, both (k_recon_display_out).
+static constexpr int kOutSlots = -1, kOutRgba = 0, kOutYcbcr = 1, kOutBoth = 2;
 struct FrameOut {
     uint8_t* const* frames;      // per picture of the launch: its frame's planes record [Y | Cb | Cr (| A)]
     uint32_t luma_stride, chroma_stride;   // bytes per row: the plane width rounded up to 64
@@ -142,6 +144,10 @@ template <> struct Lay<1> { static constexpr int carry = kLdsTile, slots = kLdsT
                             static constexpr bool tables_in_lds = false, park_in_tile = true; };
 static constexpr int kLdsPerWaveDisplayPair = Lay<1>::tile_r + kLdsTile;      // 5440
 static constexpr int kOffTileR = Lay<1>::tile_r;
+// the two luma parts of a display task share one front (recon_luma_pair) on layout 1: dense P and B pictures without alpha
+constexpr bool pair_task(int type, bool sparse, bool alpha) { return !sparse && !alpha && type != 1; }
+// a display wave's strip in bytes: what the kernels step by and what the host launches with
+constexpr int display_strip_bytes(int type, bool sparse, bool alpha) { return alpha ? kLdsPerWaveDisplayAlpha : (pair_task(type, sparse, alpha) ? kLdsPerWaveDisplayPair : kLdsPerWaveDisplay); }
 // cache policy bits of the frames' stores (1 sc0, 2 nt, 16 sc1).  nt: the GPU never reads a frame again, and written through the
 // caches like everything else it pushes the reference planes out -- round 4, one box, alternating: 5.944 -> 5.818 ms per step (I -5 %,
 // P -3.6 %, mixed B -1.2 %); sc0 / sc1: nothing.  (Round 2 measured nt on ALL stores: -4 %, the planes are read again.)
@@ -211,6 +217,15 @@ __device__ __forceinline__ void coef_rows_to_lds(const void* plane, char* tile, 
 // every vector memory operation of this wave has completed (loads, LDS-direct loads, stores)
 __device__ __forceinline__ void wait_vmem_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void wait_lds_all() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// what the wave's lanes wrote to LDS before is what every lane of the wave reads behind (waves never talk to each other)
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// a 64-bit field that a geometry struct carries as two dwords (the struct keeps 4-byte alignment)
+__host__ __device__ constexpr size_t join64(uint32_t lo, uint32_t hi) { return ((size_t)hi << 32) | lo; }
 
 // lanes whose value is non-zero, as a scalar mask: ONE v_cmp (the ballot builtin on a
 // 16-bit-derived compare costs three vector instructions with this compiler)
@@ -599,7 +614,8 @@ struct Display {
     const struct FrameOut* fo;
 };
 // AMODE of recon_task in a yuva display task: the A part runs before the Y part of the same four macroblocks
-// and parks its samples (1); the Y part's conversion takes its alpha bytes from there (2); 0 otherwise.
+// and parks its samples (kAlphaPark); the Y part's conversion takes its alpha bytes from there (kAlphaTake); kAlphaNone otherwise.
+static constexpr int kAlphaNone = 0, kAlphaPark = 1, kAlphaTake = 2;
 
 // byte i of a packed dword, times 2^sh: one v_lshlrev_b32_sdwa (table addresses from packed samples)
 template <int I>
@@ -670,7 +686,7 @@ __device__ __forceinline__ void display_half(const PicDesc& pd, const Geom& G, c
     const __amdgpu_buffer_rsrc_t rrs = buf_rsrc(pd.rgba);
     uint32_t two = 2u, three = 3u, k21 = (uint32_t)kLutShift;  // SDWA shift counts live in registers
     asm("" : "+v"(two), "+v"(three));
-    if constexpr (AMODE == 2) asm("" : "+v"(k21));
+    if constexpr (AMODE == kAlphaTake) asm("" : "+v"(k21));
     const int yrow = 8 * (2 * Rt + half) + 2 * pr;
     // chroma: row y>>1 = stash row 4*half + p; the quad's two chroma samples are bytes 32*side + 2j, + 1
     const char* yp = ypark + pr * 128 + jq * 4;
@@ -678,7 +694,7 @@ __device__ __forceinline__ void display_half(const PicDesc& pd, const Geom& G, c
     const uint32_t ya = *reinterpret_cast<const uint32_t*>(yp), yb = *reinterpret_cast<const uint32_t*>(yp + 64);
     const uint32_t cb2 = *reinterpret_cast<const uint16_t*>(sp), cr2 = *reinterpret_cast<const uint16_t*>(sp + 512);
     uint32_t aa = 0u, ab = 0u;                             // yuva: the pixels' A samples, parked by the A part
-    if constexpr (AMODE == 2) {
+    if constexpr (AMODE == kAlphaTake) {
         const char* ap = dsp.apark + half * 512 + pr * 128 + jq * 4;
         aa = *reinterpret_cast<const uint32_t*>(ap);
         ab = *reinterpret_cast<const uint32_t*>(ap + 64);
@@ -687,9 +703,9 @@ __device__ __forceinline__ void display_half(const PicDesc& pd, const Geom& G, c
     // the frame is the top-left crop of the coded picture; its width is a multiple of 8 (host check)
     const uint32_t row_off = __umul24((uint32_t)yrow, (uint32_t)G.fw) + (uint32_t)xa;     // both < 4096
     const bool in_a = yrow < G.fh && xa < G.fw, in_b = yrow + 1 < G.fh && xa < G.fw;
-    const v4u pa = rgba_row4<AMODE == 2>(dsp.lut, ya, c0, c1, aa, two, k21);
+    const v4u pa = rgba_row4<AMODE == kAlphaTake>(dsp.lut, ya, c0, c1, aa, two, k21);
     __builtin_amdgcn_raw_buffer_store_b128(pa, rrs, (int)((row_off * 4u) | (in_a ? 0u : kOobBit)), 0, kAuxFrameStore);
-    const v4u pb = rgba_row4<AMODE == 2>(dsp.lut, yb, c0, c1, ab, two, k21);
+    const v4u pb = rgba_row4<AMODE == kAlphaTake>(dsp.lut, yb, c0, c1, ab, two, k21);
     __builtin_amdgcn_raw_buffer_store_b128(pb, rrs, (int)(((row_off + (uint32_t)G.fw) * 4u) | (in_b ? 0u : kOobBit)), 0, kAuxFrameStore);
 }
 
@@ -801,22 +817,65 @@ __device__ __forceinline__ void column_pass(char* tile0, uint32_t tile_step, con
     }
 }
 
-// `alpha` (wave-uniform, luma-shaped tasks only): the task reconstructs the A plane of a yuva picture --
-// the same code path as luma with its own coefficient plane, the plane behind Cr in every slot, and the
-// alpha groups of the sparse lists.
 // CARRY (display tasks): the eight macroblocks of a task are looked up in the maps ONCE, by its chroma part (1: lane
 // (., m) loads macroblock m's quantiser scale, flags and vectors as always and leaves them in `carry`); the luma and
 // alpha parts (2) take theirs from the lane of their macroblock by ds_bpermute -- no loads, no second wait for memory
 // in front of their reference fetches.  0: a task on its own loads what it needs.
 struct MbCarry { uint32_t flags; };       // q | intra << 8 | repadd >= 128 << 9 | direction << 10 (the vectors: LDS, kOffCarry)
+static constexpr int kCarryNone = 0, kCarryLeave = 1, kCarryTake = 2;
 
-// BACK (dense display tasks whose two luma parts share their front, recon_luma_pair): the part's coefficients are in `tile` and have
-// been through the column pass already; `live_in` says which of its columns were live
-template <int TYPE, bool CHROMA, bool SPARSE, bool DISPLAY, int AMODE = 0, int CARRY = 0, bool BACK = false, int LAYOUT = 0, int OUT = kOutRgba>
-__device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int Rt, int g, char* lds, int lane, Display dsp, MbCarry& carry, bool alpha = false,
-                                           char* tile_in = nullptr, uint64_t live_in0 = 0, uint64_t live_in1 = 0, uint32_t qreg = 0u)
+// What a recon_task instantiation is: a variant type with these constants.  BACK (dense display tasks whose two luma parts share
+// their front, recon_luma_pair): the part's coefficients are in TaskArgs::tile and have been through the column pass already;
+// TaskArgs::live says which of its columns were live.
+template <int TYPE_, bool SPARSE_> struct PlainLuma {               // a task of k_recon, on its own: luma, or the A plane of a yuva picture (TaskArgs{true})
+    static constexpr int TYPE = TYPE_, AMODE = kAlphaNone, CARRY = kCarryNone, LAYOUT = 0, OUT = kOutRgba; static constexpr bool SPARSE = SPARSE_, CHROMA = false, DISPLAY = false, BACK = false;
+};
+template <int TYPE, bool SPARSE> struct PlainChroma : PlainLuma<TYPE, SPARSE> { static constexpr bool CHROMA = true; };
+// the parts of a display task (display_task), in the order they run
+template <int TYPE, bool SPARSE, int LAYOUT_, int OUT_> struct DisplayChroma : PlainChroma<TYPE, SPARSE> {         // looks the task's macroblocks up and leaves them to the others
+    static constexpr int CARRY = kCarryLeave, LAYOUT = LAYOUT_, OUT = OUT_; static constexpr bool DISPLAY = true;
+};
+template <int TYPE, bool SPARSE, int OUT_> struct DisplayLuma : PlainLuma<TYPE, SPARSE> {             // four macroblocks' Y, converted right away
+    static constexpr int CARRY = kCarryTake, OUT = OUT_; static constexpr bool DISPLAY = true;
+};
+template <int TYPE, bool SPARSE, int OUT> struct YuvaAPart : DisplayLuma<TYPE, SPARSE, OUT> { static constexpr int AMODE = kAlphaPark; };
+template <int TYPE, bool SPARSE, int OUT> struct YuvaYPart : DisplayLuma<TYPE, SPARSE, OUT> { static constexpr int AMODE = kAlphaTake; };
+template <int TYPE, int OUT> struct PairBackHalf : DisplayLuma<TYPE, false, OUT> { static constexpr int LAYOUT = 1; static constexpr bool BACK = true; };
+
+struct TaskArgs {                // what only a few callers of recon_task set
+    // a luma-shaped task of k_recon reconstructs the A plane of a yuva picture (wave-uniform; a display task's A part is one by
+    // its variant) -- the same code path as luma with its own coefficient plane, the plane behind Cr in every slot, and the alpha
+    // groups of the sparse lists
+    bool alpha = false;
+    char* tile = nullptr;        // BACK: the part's tile
+    uint64_t live[2] = {0, 0};   // BACK: its live columns, per half
+    uint32_t qreg = 0u;          // layout 1: the quantiser tables, dword i in lane i (column_pass)
+};
+
+// stage 2: column pass over the LIVE columns of both halves
+// A column (half, block, c) without a coefficient gives eight zeros, and zeros are what it holds already.
+// Quantised video leaves few columns alive (one in ten in P and B pictures, a third in I pictures), so
+// the lanes first find the live ones -- lane (c = hi3, b = lo3) looks at its own column of each half --
+// and the wave then runs the pass on them alone, usually in one go for both halves instead of one go
+// per half with most lanes computing zeros.  The results replace the coefficients in place.
+template <int LAYOUT>
+__device__ __forceinline__ void column_front(const PicDesc& pd, char* lds, char* tile, int lane, int qia, uint32_t qreg, uint64_t (&live)[2])
 {
-    char* const tile = BACK ? tile_in : lds;
+    const uint32_t n_cols = scan_tile(tile, lds + Lay<LAYOUT>::slots, lane, 0u, 0u, live);
+    wave_sync();
+    column_pass<false, Lay<LAYOUT>::tables_in_lds>(tile, 0u, lds + Lay<LAYOUT>::slots, Lay<LAYOUT>::tables_in_lds ? lds + kOffQtab : reinterpret_cast<const char*>(pd.qt),
+                                                   n_cols, qia, qia, lane, qreg);
+    wave_sync();
+}
+
+template <typename V>
+__device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int Rt, int g, char* lds, int lane, Display dsp, MbCarry& carry, const TaskArgs& args = TaskArgs())
+{
+    constexpr int TYPE = V::TYPE, AMODE = V::AMODE, CARRY = V::CARRY, LAYOUT = V::LAYOUT, OUT = V::OUT;
+    constexpr bool CHROMA = V::CHROMA, SPARSE = V::SPARSE, DISPLAY = V::DISPLAY, BACK = V::BACK;
+    static_assert(!BACK || (LAYOUT == 1 && CARRY == kCarryTake), "a back half runs on the two-tile layout behind the chroma part");
+    const bool alpha = AMODE == kAlphaPark || args.alpha;
+    char* const tile = BACK ? args.tile : lds;
     const int W = CHROMA ? G.cw >> 1 : G.cw;
     const int H = CHROMA ? G.ch >> 1 : G.ch;
     const int bw = W >> 3;
@@ -870,7 +929,7 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
     }
     const uint32_t mb = (uint32_t)(CHROMA ? Rt * G.mbw + Qs : Rt * G.mbw + (Qs >> 1));
     uint32_t mf = 0, mk = 0, flags;
-    if constexpr (CARRY == 2) {
+    if constexpr (CARRY == kCarryTake) {
         // this lane's macroblock is number 4 * side + (block >> 1) of the task: its chroma-part lane holds it
         const int src = (4 * dsp.side + (lo3 >> 1)) << 2;
         flags = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)carry.flags);
@@ -888,7 +947,7 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
             mk = ldg<uint32_t>(gptr(pd.mv_bwd), mb * 4);
             flags |= (uint32_t)(ldg<uint8_t>(gptr(pd.mb_dir), mb) & 3) << 10;
         }
-        if constexpr (CARRY == 1) {       // lane i < 8 holds macroblock i of the task (and so does every lane i + 8 k)
+        if constexpr (CARRY == kCarryLeave) {       // lane i < 8 holds macroblock i of the task (and so does every lane i + 8 k)
             carry.flags = flags;
             if (TYPE != 1) *reinterpret_cast<uint32_t*>(lds + Lay<LAYOUT>::carry + ((lane & 7) << 2)) = mf;
             if (TYPE == 3) *reinterpret_cast<uint32_t*>(lds + Lay<LAYOUT>::carry + 32 + ((lane & 7) << 2)) = mk;
@@ -963,9 +1022,7 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
     if constexpr (SPARSE) {
         *reinterpret_cast<v4i*>(lds + lane * 16) = v4i{0, 0, 0, 0};
         *reinterpret_cast<v4i*>(lds + kLdsHalf + lane * 16) = v4i{0, 0, 0, 0};
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             // scatter the group's entries into the cleared tile; the offset is masked to the tile
@@ -980,28 +1037,10 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
 
-    // ---- stage 2: column pass over the LIVE columns of both halves ----------------------------------
-    // A column (half, block, c) without a coefficient gives eight zeros, and zeros are what it holds already.
-    // Quantised video leaves few columns alive (one in ten in P and B pictures, a third in I pictures), so
-    // the lanes first find the live ones -- lane (c = hi3, b = lo3) looks at its own column of each half --
-    // and the wave then runs the pass on them alone, usually in one go for both halves instead of one go
-    // per half with most lanes computing zeros.  The results replace the coefficients in place.
-    uint64_t live[2] = {live_in0, live_in1};
-    if constexpr (!BACK) {
-        const uint32_t n_cols = scan_tile(tile, lds + Lay<LAYOUT>::slots, lane, 0u, 0u, live);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        column_pass<false, Lay<LAYOUT>::tables_in_lds>(tile, 0u, lds + Lay<LAYOUT>::slots, Lay<LAYOUT>::tables_in_lds ? lds + kOffQtab : reinterpret_cast<const char*>(pd.qt),
-                                                       n_cols, qia, qia, lane, qreg);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
+    uint64_t live[2] = {args.live[0], args.live[1]};
+    if constexpr (!BACK) column_front<LAYOUT>(pd, lds, tile, lane, qia, args.qreg, live);
 
 #pragma unroll
     for (int half = 0; half < 2; half++) {
@@ -1091,7 +1130,7 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
                 const FrameOut& fo = *dsp.fo;
                 const int y = CHROMA ? 8 * Rt + hi3 : 8 * (2 * Rt + half) + hi3;
                 const bool in = valid && y < (CHROMA ? fo.chroma_height : G.fh);
-                const uint32_t po = CHROMA ? (half ? fo.cr_off : fo.cb_off) : (AMODE == 1 ? fo.a_off : 0u);
+                const uint32_t po = CHROMA ? (half ? fo.cr_off : fo.cb_off) : (AMODE == kAlphaPark ? fo.a_off : 0u);
                 const uint32_t fvoff = (__umul24((uint32_t)y, CHROMA ? fo.chroma_stride : fo.luma_stride) + (uint32_t)x0) | (in ? 0u : kOobBit);
                 __builtin_amdgcn_raw_buffer_store_b64(o, buf_rsrc(dsp.planes + po), (int)fvoff, 0, kAuxFrameStore);
             }
@@ -1100,7 +1139,7 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
             } else if constexpr (CHROMA) {
                 // park the samples for the luma parts: [plane = half][row hi3][8 bytes of macroblock lo3]
                 *reinterpret_cast<v2u*>(dsp.stash + half * 512 + hi3 * 64 + lo3 * 8) = o;
-            } else if constexpr (AMODE == 1) {
+            } else if constexpr (AMODE == kAlphaPark) {
                 // yuva, A part: the samples wait for the Y part of the same macroblocks
                 *reinterpret_cast<v2u*>(dsp.apark + half * 512 + hi3 * 64 + lo3 * 8) = o;
             } else {
@@ -1112,15 +1151,11 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
                 *reinterpret_cast<v2u*>((Lay<LAYOUT>::park_in_tile ? tile + half * kLdsHalf : lds + kOffYpark) + hi3 * 64 + lo3 * 8) = o;
             }
         }
-        if constexpr (DISPLAY && !CHROMA && AMODE != 1 && OUT != kOutYcbcr) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if constexpr (DISPLAY && !CHROMA && AMODE != kAlphaPark && OUT != kOutYcbcr) {
+            wave_sync();
             display_half<AMODE>(pd, G, dsp, Lay<LAYOUT>::park_in_tile ? tile + half * kLdsHalf : lds + kOffYpark, half, Rt, g, hi3, lo3);
             // the next half parks its rows in the same place
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
         }
     }
 }
@@ -1161,24 +1196,18 @@ __device__ __forceinline__ void recon_luma_pair(const PicDesc& pd, const Geom& G
     const int qiaL = __builtin_amdgcn_ds_bpermute((lo3 >> 1) << 2, (int)carry.flags) & 0x11f;
     const int qiaR = __builtin_amdgcn_ds_bpermute((4 + (lo3 >> 1)) << 2, (int)carry.flags) & 0x11f;
     wait_vmem_all();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    uint64_t liveL[2], liveR[2] = {0, 0};
-    uint32_t n_cols = scan_tile(lds, lds + Lay<1>::slots, lane, 0u, 0u, liveL);
-    if (has_right) n_cols = scan_tile(tileR, lds + Lay<1>::slots, lane, 128u, n_cols, liveR);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
+    TaskArgs left{false, lds}, right{false, tileR};
+    uint32_t n_cols = scan_tile(lds, lds + Lay<1>::slots, lane, 0u, 0u, left.live);
+    if (has_right) n_cols = scan_tile(tileR, lds + Lay<1>::slots, lane, 128u, n_cols, right.live);
+    wave_sync();
     column_pass<true, false>(lds, (uint32_t)kOffTileR, lds + Lay<1>::slots, nullptr, n_cols, qiaL, qiaR, lane, qreg);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     dsp.side = 0;
-    recon_task<TYPE, false, false, true, 0, 2, true, 1, OUT>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, false, lds, liveL[0], liveL[1]);
+    recon_task<PairBackHalf<TYPE, OUT>>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, left);
     if (has_right) {
         dsp.side = 1;
-        recon_task<TYPE, false, false, true, 0, 2, true, 1, OUT>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, false, tileR, liveR[0], liveR[1]);
+        recon_task<PairBackHalf<TYPE, OUT>>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, right);
     }
 }
 
@@ -1230,15 +1259,15 @@ __device__ __forceinline__ void recon_dispatch(const PicDesc& pd, const Geom& G,
     MbCarry own{};
     if (t < G.tasksY) {
         int Rt = div_inv(t, G.inv_gY), g = t - Rt * G.gY;
-        recon_task<TYPE, false, SPARSE, false>(pd, G, Rt, g, lds, lane, none, own);
+        recon_task<PlainLuma<TYPE, SPARSE>>(pd, G, Rt, g, lds, lane, none, own);
     } else if (t < G.tasksY + G.tasksC) {
         t -= G.tasksY;
         int Rt = div_inv(t, G.inv_gC), g = t - Rt * G.gC;
-        recon_task<TYPE, true, SPARSE, false>(pd, G, Rt, g, lds, lane, none, own);
+        recon_task<PlainChroma<TYPE, SPARSE>>(pd, G, Rt, g, lds, lane, none, own);
     } else {                                   // yuva: the A plane, luma-shaped
         t -= G.tasksY + G.tasksC;
         int Rt = div_inv(t, G.inv_gY), g = t - Rt * G.gY;
-        recon_task<TYPE, false, SPARSE, false>(pd, G, Rt, g, lds, lane, none, own, true);
+        recon_task<PlainLuma<TYPE, SPARSE>>(pd, G, Rt, g, lds, lane, none, own, TaskArgs{true});
     }
 }
 
@@ -1276,7 +1305,7 @@ template <int TYPE, bool SPARSE, bool ALPHA, int OUT = kOutRgba>
 __device__ __forceinline__ bool display_task(const PicDesc* __restrict__ descs, const Geom& G, int pic, int t, char* lds, int lane, const char* lut, bool first,
                                              const FrameOut* fo = nullptr)
 {
-    constexpr bool kPair = !SPARSE && !ALPHA && TYPE != 1;      // recon_luma_pair
+    constexpr bool kPair = pair_task(TYPE, SPARSE, ALPHA);      // recon_luma_pair
     const bool live = t < G.tasks_per_pic && pic < G.n_pics;
     const PicDesc& pd = descs[live ? pic : 0];
     const int Rt = div_inv(t, G.inv_gC), gc = t - Rt * G.gC;
@@ -1291,7 +1320,8 @@ __device__ __forceinline__ bool display_task(const PicDesc* __restrict__ descs, 
     // in lane i (column_pass takes what it needs by ds_bpermute); requested first, landed with the macroblock maps
     uint32_t qreg = 0u;
     if constexpr (kPair) qreg = ldg<uint32_t>(gptr(pd.qt), (uint32_t)lane * 4u);
-    if (live) recon_task<TYPE, true, SPARSE, true, 0, 1, false, kPair ? 1 : 0, OUT>(pd, G, Rt, gc, lds, lane, dsp, carry, false, nullptr, 0, 0, qreg);
+    const TaskArgs tables{false, nullptr, {0, 0}, qreg};
+    if (live) recon_task<DisplayChroma<TYPE, SPARSE, kPair ? 1 : 0, OUT>>(pd, G, Rt, gc, lds, lane, dsp, carry, tables);
     if (first) {
         if (!live) wait_vmem_all();      // (a wave with a task has waited for memory behind its chroma part's loads: its chunks of the tables are in)
         if constexpr (OUT != kOutYcbcr) __syncthreads();      // the conversion tables have landed: every wave's chunks
@@ -1305,18 +1335,18 @@ __device__ __forceinline__ bool display_task(const PicDesc* __restrict__ descs, 
     }
     dsp.side = 0;
     if constexpr (ALPHA) {
-        recon_task<TYPE, false, SPARSE, true, 1, 2, false, 0, OUT>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, true);
-        recon_task<TYPE, false, SPARSE, true, 2, 2, false, 0, OUT>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
+        recon_task<YuvaAPart<TYPE, SPARSE, OUT>>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
+        recon_task<YuvaYPart<TYPE, SPARSE, OUT>>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
     } else {
-        recon_task<TYPE, false, SPARSE, true, 0, 2, false, 0, OUT>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
+        recon_task<DisplayLuma<TYPE, SPARSE, OUT>>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry);
     }
     if (2 * gc + 1 < G.gY) {
         dsp.side = 1;
         if constexpr (ALPHA) {
-            recon_task<TYPE, false, SPARSE, true, 1, 2, false, 0, OUT>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, true);
-            recon_task<TYPE, false, SPARSE, true, 2, 2, false, 0, OUT>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
+            recon_task<YuvaAPart<TYPE, SPARSE, OUT>>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
+            recon_task<YuvaYPart<TYPE, SPARSE, OUT>>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
         } else {
-            recon_task<TYPE, false, SPARSE, true, 0, 2, false, 0, OUT>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
+            recon_task<DisplayLuma<TYPE, SPARSE, OUT>>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry);
         }
     }
     return true;
@@ -1346,16 +1376,12 @@ void k_recon_display(const PicDesc* __restrict__ descs, Geom G,
     // (sparse; loads return in order) -- a wave without a task waits in display_task -- and the barrier there makes every
     // wave's chunks everybody's.
     __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];      // static: its LDS address is a compile-time constant
-    {
-        static_assert(kLdsLut % 1024 == 0, "whole chunks");
-        const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc((void*)T->rgba_lut, 0, kLdsLut, 0x00020000);
-        const int n_waves = (int)(blockDim.x >> 6);
-        for (int c = wave; c < kLdsLut / 1024; c += n_waves)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lut_s) + c * 1024), 16,
-                                                     (int)(lane0 * 16u), c * 1024, 0, 0);
-    }
-    constexpr bool kPair = !SPARSE && !ALPHA && TYPE != 1;
-    char* lds = smem + wave * (ALPHA ? kLdsPerWaveDisplayAlpha : (kPair ? kLdsPerWaveDisplayPair : kLdsPerWaveDisplay));
+    static_assert(kLdsLut % 1024 == 0, "whole chunks");
+    const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc((void*)T->rgba_lut, 0, kLdsLut, 0x00020000);
+    for (int c = wave; c < kLdsLut / 1024; c += wpw)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lut_s) + c * 1024), 16,
+                                                 (int)(lane0 * 16u), c * 1024, 0, 0);
+    char* lds = smem + wave * display_strip_bytes(TYPE, SPARSE, ALPHA);
     // (Round 4 tried a wave running two to five tasks one after the other, so that the frames' stores of a task drain while the wave
     // works on the next: 5.89-5.92 ms per step with two against 5.90-5.95 with one, worse with three and five, and 10-20 registers more
     // for the loop -- not kept.)
@@ -1385,13 +1411,11 @@ void k_recon_display_out(const PicDesc* __restrict__ descs, Geom G, const Tables
     __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
     if constexpr (OUT == kOutBoth) {
         const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc((void*)T->rgba_lut, 0, kLdsLut, 0x00020000);
-        const int n_waves = (int)(blockDim.x >> 6);
-        for (int c = wave; c < kLdsLut / 1024; c += n_waves)
+        for (int c = wave; c < kLdsLut / 1024; c += wpw)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lut_s) + c * 1024), 16,
                                                      (int)(lane0 * 16u), c * 1024, 0, 0);
     }
-    constexpr bool kPair = !SPARSE && !ALPHA && TYPE != 1;
-    char* lds = smem + wave * (ALPHA ? kLdsPerWaveDisplayAlpha : (kPair ? kLdsPerWaveDisplayPair : kLdsPerWaveDisplay));
+    char* lds = smem + wave * display_strip_bytes(TYPE, SPARSE, ALPHA);
     display_task<TYPE, SPARSE, ALPHA, OUT>(descs, G, pic, twg * wpw + wave, lds, lane0, OUT == kOutBoth ? reinterpret_cast<const char*>(lut_s) : nullptr, true, &fo);
 }
 
@@ -1419,7 +1443,7 @@ __global__ __launch_bounds__(kRgbaBlock) void k_planes_crop(const uint8_t* __res
     const uint32_t ysz = (uint32_t)G.cw * (uint32_t)G.ch;
     const uint32_t src_w = luma ? (uint32_t)G.cw : (uint32_t)G.cw >> 1;
     const uint32_t src_plane = plane == 0 ? 0u : plane == 1 ? ysz : plane == 2 ? ysz + (ysz >> 2) : ysz + (ysz >> 1);
-    const size_t stride = ((size_t)G.slot_stride_hi << 32) | G.slot_stride_lo;
+    const size_t stride = join64(G.slot_stride_lo, G.slot_stride_hi);
     const uint8_t* src = slots + (size_t)src_slots[blockIdx.z] * stride + src_plane + (size_t)y * src_w + x;
     uint8_t* dst = fo.frames[blockIdx.z] + (plane == 0 ? 0u : plane == 1 ? fo.cb_off : plane == 2 ? fo.cr_off : fo.a_off)
                  + (size_t)y * (luma ? fo.luma_stride : fo.chroma_stride) + x;
@@ -1456,7 +1480,7 @@ __global__ __launch_bounds__(kRgbaBlock) void k_rgba_twin(const uint8_t* __restr
     const int row = blockIdx.y;
     const int f = blockIdx.z;
     if (col >= G.cols) return;
-    const size_t stride = ((size_t)G.slot_stride_hi << 32) | G.slot_stride_lo;
+    const size_t stride = join64(G.slot_stride_lo, G.slot_stride_hi);
     const uint8_t* Y = slots + (size_t)slot_ids[f] * stride;
     const uint8_t* Cb = Y + (size_t)G.cw * G.ch;
     const uint8_t* Cr = Cb + ((size_t)G.cw * G.ch >> 2);
@@ -1500,7 +1524,7 @@ __global__ __launch_bounds__(kRgbaBlock) void k_rgba_twin4(const uint8_t* __rest
     const int row = (int)(G.inv_cols4 ? __umulhi(idx, G.inv_cols4) : idx);   // exact: idx * cols4 < 2^32
     const int col4 = (int)(idx - (uint32_t)row * cols4);
     const int f = blockIdx.z;
-    const size_t stride = ((size_t)G.slot_stride_hi << 32) | G.slot_stride_lo;
+    const size_t stride = join64(G.slot_stride_lo, G.slot_stride_hi);
     const uint8_t* Y = slots + (size_t)slot_ids[f] * stride;
     const uint8_t* Cb = Y + (size_t)G.cw * G.ch;
     const uint8_t* Cr = Cb + ((size_t)G.cw * G.ch >> 2);
@@ -1541,7 +1565,7 @@ __global__ __launch_bounds__(kRgbaBlock) void k_rgba_alpha(const uint8_t* __rest
     const int yy = blockIdx.y;
     const int f = blockIdx.z;
     if (x >= cover_w || yy >= cover_h) return;
-    const size_t stride = ((size_t)G.slot_stride_hi << 32) | G.slot_stride_lo;
+    const size_t stride = join64(G.slot_stride_lo, G.slot_stride_hi);
     const size_t ysz = (size_t)G.cw * G.ch;
     const uint8_t* A = slots + (size_t)slot_ids[f] * stride + ysz + (ysz >> 1);
     uint8_t* dst = rgba + ((size_t)f * G.fw * G.fh + (size_t)yy * G.fw + x) * 4;
@@ -1564,7 +1588,7 @@ __global__ __launch_bounds__(kRgbaBlock) void k_rgba_gl(const uint8_t* __restric
     const int yy = blockIdx.y;
     const int f = blockIdx.z;
     if (x >= G.fw) return;
-    const size_t stride = ((size_t)G.slot_stride_hi << 32) | G.slot_stride_lo;
+    const size_t stride = join64(G.slot_stride_lo, G.slot_stride_hi);
     const uint8_t* Y = slots + (size_t)slot_ids[f] * stride;
     const uint8_t* Cb = Y + (size_t)G.cw * G.ch;
     const uint8_t* Cr = Cb + ((size_t)G.cw * G.ch >> 2);
@@ -1680,8 +1704,8 @@ __global__ __launch_bounds__(kRgbaBlock) void k_tensor(const uint8_t* __restrict
     const char* lut = reinterpret_cast<const char*>(lut_s);
     const uint32_t pair = idx / G.per_row, col = idx - pair * G.per_row;
     const uint32_t fid = frame_ids[blockIdx.z];
-    const uint8_t* src = planes_ring + (size_t)fid * (((size_t)G.planes_pitch_hi << 32) | G.planes_pitch_lo);
-    uint8_t* dst = tensor_ring + (size_t)fid * (((size_t)G.tensor_pitch_hi << 32) | G.tensor_pitch_lo);
+    const uint8_t* src = planes_ring + (size_t)fid * join64(G.planes_pitch_lo, G.planes_pitch_hi);
+    uint8_t* dst = tensor_ring + (size_t)fid * join64(G.tensor_pitch_lo, G.tensor_pitch_hi);
     const uint32_t r0 = 2u * pair, fw = (uint32_t)G.fw, fh = (uint32_t)G.fh;
     const bool has_r1 = r0 + 1u < fh;                    // false: the last row of an odd height, left at 255 by the twin
     const uint32_t plane_elems = fw * fh;
@@ -1820,8 +1844,8 @@ __global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restri
 
     const char* lut = reinterpret_cast<const char*>(lut_s);
     const uint32_t fid = frame_ids[blockIdx.z];
-    const uint8_t* src = planes_ring + (size_t)fid * (((size_t)G.planes_pitch_hi << 32) | G.planes_pitch_lo);
-    uint8_t* dst = tensor_ring + (size_t)fid * (((size_t)G.tensor_pitch_hi << 32) | G.tensor_pitch_lo);
+    const uint8_t* src = planes_ring + (size_t)fid * join64(G.planes_pitch_lo, G.planes_pitch_hi);
+    uint8_t* dst = tensor_ring + (size_t)fid * join64(G.tensor_pitch_lo, G.tensor_pitch_hi);
     const __amdgpu_buffer_rsrc_t prs = buf_rsrc(src);
     uint32_t two = 2u, three = 3u;                       // SDWA shift counts live in registers (display_half)
     asm("" : "+v"(two), "+v"(three));

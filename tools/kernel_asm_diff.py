@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Which kernels of libleon_hip's device code changed between two trees: compiles leon_hip.cpp of each with hipcc -S
---cuda-device-only for gfx950 (no GPU needed) and compares the instructions kernel by kernel, block labels normalised.
-    python tools/kernel_asm_diff.py OTHER_TREE [THIS_TREE]        e.g. OTHER_TREE = a `git worktree` of the parent commit
-Prints the kernels that are identical, differ, are new and are gone; exit status 1 when a kernel both trees have differs."""
+--cuda-device-only for gfx950 (no GPU needed) and compares kernel by kernel the instructions (block labels normalised) and,
+separately, the kernel descriptor (the .amdhsa_* lines: static LDS, kernarg size, register counts, ...).
+    python tools/kernel_asm_diff.py OTHER_TREE [THIS_TREE] [--show KERNEL]     e.g. OTHER_TREE = a `git worktree` of the parent commit
+Prints the kernels that are identical, differ, are new and are gone; --show prints a unified diff of the normalised instructions
+and descriptors of every kernel whose name contains KERNEL.  Exit status 1 when a kernel both trees have differs in either."""
+import argparse
+import difflib
 import os
 import re
 import subprocess
@@ -12,33 +16,66 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def parse(lines):
+    """{kernel: (instructions, descriptor lines)} of an assembly listing"""
+    ins, desc, cur, hsa = {}, {}, None, None
+    for line in lines:
+        m = re.match(r"^(_Z\w+):", line)
+        text = re.sub(r";.*", "", re.sub(r"\.LBB\d+_", ".LBB_", line)).strip()
+        if m and "k_" in m.group(1):
+            cur = m.group(1)
+            ins[cur] = []
+        elif text.startswith(".amdhsa_kernel "):
+            hsa = text.split()[1]
+            desc[hsa] = []
+        elif text == ".end_amdhsa_kernel":
+            hsa = None
+        elif hsa is not None:
+            if text.startswith(".amdhsa_"):
+                desc[hsa].append(text)
+        elif cur is not None:
+            if line.startswith(".Lfunc_end"):
+                cur = None
+            elif text and not text.startswith("."):
+                ins[cur].append(text)
+    return {k: (ins[k], desc.get(k, [])) for k in ins}
+
+
 def kernels(tree):
     src = os.path.join(tree, "mpeg1video-decoder-webgl_amd", "csrc", "leon_hip.cpp")
     with tempfile.NamedTemporaryFile(suffix=".s") as f:
         subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S",
                         "--cuda-device-only", "-o", f.name, src], check=True, capture_output=True, timeout=900)
-        out, cur = {}, None
-        for line in open(f.name):
-            m = re.match(r"^(_Z\w+):", line)
-            if m and "k_" in m.group(1):
-                cur = m.group(1)
-                out[cur] = []
-            elif cur is not None:
-                if line.startswith(".Lfunc_end"):
-                    cur = None
-                    continue
-                ins = re.sub(r";.*", "", re.sub(r"\.LBB\d+_", ".LBB_", line)).strip()
-                if ins and not ins.startswith("."):
-                    out[cur].append(ins)
-    return out
+        with open(f.name) as s:
+            return parse(s)
+
+
+def main(argv):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("other_tree")
+    ap.add_argument("this_tree", nargs="?", default=ROOT)
+    ap.add_argument("--show", metavar="KERNEL", help="print the diffs of the kernels whose name contains KERNEL")
+    args = ap.parse_args(argv)
+    show = args.show
+    a, b = kernels(args.other_tree), kernels(args.this_tree)
+    both = sorted(k for k in a if k in b)
+    differ = [k for k in both if a[k][0] != b[k][0]]
+    desc_differ = [k for k in both if a[k][1] != b[k][1]]
+    print("%d kernels there, %d here: %d identical, %d differ, %d descriptor differs, %d new, %d gone" % (
+        len(a), len(b), sum(1 for k in both if a[k] == b[k]), len(differ), len(desc_differ), len(set(b) - set(a)), len(set(a) - set(b))))
+    for what, names in (("differs", differ), ("descriptor differs", desc_differ), ("new", sorted(set(b) - set(a))), ("gone", sorted(set(a) - set(b)))):
+        for k in names:
+            print("  %s: %s" % (what, k))
+    if show is not None:
+        if not any(show in k for k in both):
+            print("--show: no kernel of both trees has %r in its name" % show)
+        for k in both:
+            if show in k:
+                for part, what in ((0, "instructions"), (1, "descriptor")):
+                    sys.stdout.writelines(l + "\n" for l in difflib.unified_diff(a[k][part], b[k][part], "there/%s %s" % (k, what),
+                                                                                "here/%s %s" % (k, what), lineterm=""))
+    return 1 if differ or desc_differ else 0
 
 
 if __name__ == "__main__":
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2] if len(sys.argv) > 2 else ROOT)
-    differ = sorted(k for k in a if k in b and a[k] != b[k])
-    print("%d kernels there, %d here: %d identical, %d differ, %d new, %d gone" % (
-        len(a), len(b), sum(1 for k in a if b.get(k) == a[k]), len(differ), len(set(b) - set(a)), len(set(a) - set(b))))
-    for what, names in (("differs", differ), ("new", sorted(set(b) - set(a))), ("gone", sorted(set(a) - set(b)))):
-        for k in names:
-            print("  %s: %s" % (what, k))
-    sys.exit(1 if differ else 0)
+    sys.exit(main(sys.argv[1:]))
