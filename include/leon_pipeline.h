@@ -46,6 +46,13 @@ typedef struct leon_pipeline leon_pipeline;
 #define LEON_TENSOR_F16  1
 #define LEON_TENSOR_BF16 2
 #define LEON_TENSOR_F32  3
+/* 8, not 4: create and leon_pipeline_tensor_table go on refusing dtype 4 (tests/test_pipeline_tensor_abi.py::test_refusals,
+ * tests/test_pipeline_tensor_gpu.py::test_refusals); 4 .. 7 and everything above 8 stay refused */
+#define LEON_TENSOR_U8   8
+
+/* order of a tensor's elements in memory (leon_pipeline_tensor_format.layout) */
+#define LEON_TENSOR_LAYOUT_CHW 0
+#define LEON_TENSOR_LAYOUT_HWC 1
 
 typedef struct leon_pipeline_config {
     int32_t device_id;
@@ -118,7 +125,7 @@ typedef struct leon_pipeline_frame {
  * delivered with status != 0 (n_frames may be 0) holds its ring entry and staging like any other and must be
  * released too. */
 /* LEON_PIPELINE_OUTPUT_TENSOR: a frame as [3][frame_height][frame_width] elements -- planar R, G, B, dense (row stride = frame_width
- * elements), fp16 / bf16 / fp32, each element a per-channel affine function of the 8-bit colour value:
+ * elements), fp16 / bf16 / fp32 (8-bit elements and the channels-last layout: leon_pipeline_tensor_format below), each element a per-channel affine function of the 8-bit colour value:
  *     tensor[c][y][x] = T[c][ rgba[y][x][c] ]        c = 0, 1, 2; rgba = the bytes an RGBA pipeline with display_flavour
  *                                                    LEON_RGB_CPU_TWIN delivers for the frame (the A byte is not used)
  *     T[c][v] = to_dtype( (float) ( (double)v * (double)scale[c] + (double)bias[c] ) )        v = 0 .. 255
@@ -170,6 +177,34 @@ typedef struct leon_pipeline_tensor_geometry {
     int32_t taps_x, taps_y;
     int32_t resized;
 } leon_pipeline_tensor_geometry;
+
+/* 8-bit elements and the channels-last layout.
+ * LEON_TENSOR_U8: the element IS the 8-bit colour value -- T[c][v] = v, one byte; scale and bias must all be zero (anything else is
+ * refused at create and by leon_pipeline_tensor_table, which writes the 768-byte identity table).  Everything else of the
+ * definitions above holds: the CPU twin's bytes, the resize arithmetic, the row of 255 in the last row of an odd frame height.
+ * layout (leon_pipeline_create_tensor_format), for all four element types, with and without resize settings:
+ *   LEON_TENSOR_LAYOUT_CHW (0)  tensor[c][y][x], planar, as above
+ *   LEON_TENSOR_LAYOUT_HWC (1)  tensor[y][x][c], dense: pixel stride 3 elements, row stride 3 * width elements -- the same values,
+ *                               only the addressing differs (a packed uint8 HWC frame is the RGBA frame without its A bytes)
+ * The frame's bytes (tensor_frame_bytes = 3 * height * width * element size) and the ring pitches do not depend on the layout; a
+ * window of equally long GOPs is one strided [gops, pictures, H, W, 3] view.  A yuva stream's alpha is in neither layout.
+ * Float CHW tensors are written by k_tensor / k_resample, every other combination by k_image / k_image_scaled.
+ * Refused at create: a format without the TENSOR bit, another layout, a non-zero reserved word. */
+typedef struct leon_pipeline_tensor_format {
+    int32_t layout;             /* LEON_TENSOR_LAYOUT_* */
+    int32_t reserved[7];        /* must be 0: room for the next tensor setting */
+} leon_pipeline_tensor_format;  /* 32 bytes */
+
+/* what a pipeline's tensors look like in memory (leon_pipeline_get_tensor_shape; leon_pipeline_info and
+ * leon_pipeline_tensor_geometry keep their sizes): element type and size, layout, and for the logical index [c][y][x] the
+ * strides IN ELEMENTS -- CHW: {height * width, width, 1}, HWC: {1, 3 * width, 3} */
+typedef struct leon_pipeline_tensor_shape {
+    int32_t dtype, element_bytes;
+    int32_t layout;
+    int32_t channels;           /* 3 */
+    int32_t height, width;
+    int64_t stride_c, stride_y, stride_x;
+} leon_pipeline_tensor_shape;
 
 typedef void (*leon_pipeline_callback)(void* user, int64_t window, const leon_pipeline_frame* frames, int32_t n_frames, int32_t status);
 
@@ -227,6 +262,12 @@ int leon_pipeline_create_tensor_resized(const leon_pipeline_config* cfg, const l
 int leon_pipeline_resize_weights(int32_t in_size, int32_t crop_start, int32_t crop_size, int32_t out_size, int32_t filter,
                                  int32_t* first, int32_t* count, int32_t* weights, int32_t max_taps);
 int leon_pipeline_get_tensor_geometry(leon_pipeline* p, leon_pipeline_tensor_geometry* out);
+/* leon_pipeline_create_tensor_resized with the tensors' layout; `format` NULL (or all zero) = leon_pipeline_create_tensor_resized */
+int leon_pipeline_create_tensor_format(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const leon_pipeline_tensor_resize* resize,
+                                       const leon_pipeline_tensor_format* format, const uint8_t* stream, size_t bytes, size_t valid_bytes,
+                                       leon_pipeline_callback cb, void* user, leon_pipeline** out);
+/* LEON_ERR_INVALID for a pipeline without tensor output, as leon_pipeline_get_tensor_geometry */
+int leon_pipeline_get_tensor_shape(leon_pipeline* p, leon_pipeline_tensor_shape* out);
 int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes);
 int leon_pipeline_get_info(leon_pipeline* p, leon_pipeline_info* out);
 /* the consumer is done with a window's frames: its ring entries (RGBA, planes, tensors) and staging may be reused */
@@ -263,7 +304,8 @@ int leon_pipeline_read_frame_planes(leon_pipeline* p, const leon_pipeline_frame*
  * window is released, like rgba), n = the window's n_frames.  May be called from inside the callback.  LEON_ERR_INVALID for a
  * pipeline without tensor output, a window that is not out for delivery, another n */
 int leon_pipeline_window_tensors(leon_pipeline* p, int64_t window, void** out, int32_t n);
-/* copy the tensor of frame `index` of such a window to host memory, packed (tensor_frame_bytes: [3][height][width] of the geometry) */
+/* copy the tensor of frame `index` of such a window to host memory, packed (tensor_frame_bytes: [3][height][width] of the geometry, or
+ * [height][width][3] with LEON_TENSOR_LAYOUT_HWC) */
 int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, void* host);
 const char* leon_pipeline_error(leon_pipeline* p);
 void leon_pipeline_destroy(leon_pipeline* p);

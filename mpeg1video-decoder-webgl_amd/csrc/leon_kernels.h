@@ -1637,15 +1637,45 @@ template <> struct TensorElem<kTensorF32> { typedef uint32_t type; };
 // pixels per lane and row on the fast path: 16 bytes of elements
 constexpr int tensor_lane_px(int dtype) { return dtype == kTensorF32 ? 4 : 8; }
 
-// 8 pixels of one row: Y samples y8, the four chroma pairs' terms; `off` = the row's first element in a channel plane
-// the fp32 form: 4 pixels of one row, Y samples y4, two chroma pairs
+// The conversion tables into LDS as k_recon_display loads them (1 KB chunks straight into LDS); the caller waits (wait_vmem_all) and syncs
+__device__ __forceinline__ void display_lut_to_lds(int32_t* lut_s, const Tables* T)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane0 = threadIdx.x & 63;
+    const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc((void*)T->rgba_lut, 0, kLdsLut, 0x00020000);
+    for (int c = wave; c < kLdsLut / 1024; c += kRgbaBlock / 64)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lut_s) + c * 1024), 16,
+                                                 (int)(lane0 * 16u), c * 1024, 0, 0);
+}
+// The CPU twin's RGBA dwords (A = 255) of 4 pixels of one row: Y samples y4, two chroma pairs; fill: the twin's fill row, 255
+__device__ __forceinline__ void tensor_px4(const char* lut, uint32_t y4, const ChromaTerms& c0, const ChromaTerms& c1, bool fill, uint32_t two, uint32_t (&px)[4])
+{
+    const int opaque = 255 << kLutShift;
+    px[0] = rgba_px<0>(lut, y4, c0, opaque, two); px[1] = rgba_px<1>(lut, y4, c0, opaque, two);
+    px[2] = rgba_px<2>(lut, y4, c1, opaque, two); px[3] = rgba_px<3>(lut, y4, c1, opaque, two);
+    if (fill) px[0] = px[1] = px[2] = px[3] = 0xffffffffu;
+}
+// ... of 8 pixels: Y samples y8, the four chroma pairs' terms
+__device__ __forceinline__ void tensor_px8(const char* lut, v2u y8, const ChromaTerms (&c)[4], bool fill, uint32_t two, uint32_t (&px)[8])
+{
+    const int opaque = 255 << kLutShift;
+    px[0] = rgba_px<0>(lut, y8.x, c[0], opaque, two); px[1] = rgba_px<1>(lut, y8.x, c[0], opaque, two);
+    px[2] = rgba_px<2>(lut, y8.x, c[1], opaque, two); px[3] = rgba_px<3>(lut, y8.x, c[1], opaque, two);
+    px[4] = rgba_px<0>(lut, y8.y, c[2], opaque, two); px[5] = rgba_px<1>(lut, y8.y, c[2], opaque, two);
+    px[6] = rgba_px<2>(lut, y8.y, c[3], opaque, two); px[7] = rgba_px<3>(lut, y8.y, c[3], opaque, two);
+    if (fill) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) px[k] = 0xffffffffu;
+    }
+}
+
+// `off` = the row's first element in a channel plane
+// the fp32 form: 4 pixels of one row
 __device__ __forceinline__ void tensor_row4_f32(const char* lut, const uint32_t* tab, uint32_t y4, const ChromaTerms& c0, const ChromaTerms& c1, bool fill,
                                                 __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_elems, bool in, uint32_t two)
 {
-    const int opaque = 255 << kLutShift;
-    uint32_t px[4] = {rgba_px<0>(lut, y4, c0, opaque, two), rgba_px<1>(lut, y4, c0, opaque, two),
-                      rgba_px<2>(lut, y4, c1, opaque, two), rgba_px<3>(lut, y4, c1, opaque, two)};
-    if (fill) px[0] = px[1] = px[2] = px[3] = 0xffffffffu;
+    uint32_t px[4];
+    tensor_px4(lut, y4, c0, c1, fill, two, px);
     const uint32_t oob = in ? 0u : kOobBit;
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {
@@ -1659,15 +1689,8 @@ template <int DTYPE>
 __device__ __forceinline__ void tensor_row8(const char* lut, const typename TensorElem<DTYPE>::type* tab, v2u y8, const ChromaTerms (&c)[4], bool fill,
                                             __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_elems, bool in, uint32_t two)
 {
-    const int opaque = 255 << kLutShift;
-    uint32_t px[8] = {rgba_px<0>(lut, y8.x, c[0], opaque, two), rgba_px<1>(lut, y8.x, c[0], opaque, two),
-                      rgba_px<2>(lut, y8.x, c[1], opaque, two), rgba_px<3>(lut, y8.x, c[1], opaque, two),
-                      rgba_px<0>(lut, y8.y, c[2], opaque, two), rgba_px<1>(lut, y8.y, c[2], opaque, two),
-                      rgba_px<2>(lut, y8.y, c[3], opaque, two), rgba_px<3>(lut, y8.y, c[3], opaque, two)};
-    if (fill) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) px[k] = 0xffffffffu;
-    }
+    uint32_t px[8];
+    tensor_px8(lut, y8, c, fill, two, px);
     const uint32_t oob = in ? 0u : kOobBit;
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {
@@ -1687,13 +1710,8 @@ __global__ __launch_bounds__(kRgbaBlock) void k_tensor(const uint8_t* __restrict
     typedef typename TensorElem<DTYPE>::type Elem;
     __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
     __shared__ __attribute__((aligned(16))) Elem tab_s[3 * 256];
-    {   // the conversion tables as k_recon_display loads them (1 KB chunks straight into LDS), the element table through registers
-        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        const int lane0 = threadIdx.x & 63;
-        const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc((void*)T->rgba_lut, 0, kLdsLut, 0x00020000);
-        for (int c = wave; c < kLdsLut / 1024; c += kRgbaBlock / 64)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lut_s) + c * 1024), 16,
-                                                     (int)(lane0 * 16u), c * 1024, 0, 0);
+    {   // the conversion tables, the element table through registers
+        display_lut_to_lds(lut_s, T);
         constexpr int kDwords = 3 * 256 * (int)sizeof(Elem) / 4;
         for (int i = threadIdx.x; i < kDwords; i += kRgbaBlock) reinterpret_cast<uint32_t*>(tab_s)[i] = table[i];
         wait_vmem_all();
@@ -1758,6 +1776,193 @@ __global__ __launch_bounds__(kRgbaBlock) void k_tensor(const uint8_t* __restrict
     }
 }
 
+// ---- 8-bit elements and the channels-last layout (leon_pipeline.h, leon_pipeline_tensor_format) ---------------------------
+// Every tensor that is not float CHW: uint8 [3][fh][fw], and [fh][fw][3] of 1-, 2- and 4-byte elements.  k_tensor's launch shape,
+// loads and conversion (tensor_px8 / tensor_px4); the element is the colour value itself (1 byte: no table, none in LDS) or the
+// host's table entry (fp16 and bf16 differ in the table only: the kernels are made per element SIZE).  What is new is the store side.
+// Fast path (fw % 8 == 0), a lane holds 8 pixels x 2 rows (4 x 2 of 4-byte elements):
+//   uint8 CHW: 8 bytes per channel and row -- one b64 store, a wave writes 512 contiguous bytes per instruction.
+//   HWC: a lane's row piece is 24 / 48 / 48 contiguous bytes (1- / 2- / 4-byte elements).  Stored from the lane that made it that is
+//     three instructions whose lanes lie 24 or 48 bytes apart, each writing a third of every line it touches (the shape k_tensor's
+//     comment records as measured and dropped for fp32).  So the wave's 64 pieces (1536 B / 3 KB / 3 KB, contiguous in the frame but
+//     for the seam where the wave crosses into the next row pair) change lanes through the wave's LDS strip: written at lane * piece,
+//     read back at (j * 64 + lane) * third-of-a-piece, j = 0 .. 2 -- so store instruction j writes the thirds 64 j .. 64 j + 63 in
+//     order, 64 x 16 B = 1 KB contiguous (64 x 8 B = 512 B for uint8: a third of 24 bytes).  A third never straddles two pieces, so
+//     its address is its source lane's row offset (ds_bpermute) plus 0, 1 or 2 thirds.  LDS banks: pieces of 12 dwords written as
+//     b128 by groups of 8 lanes land on 32 different banks (12 l mod 32, l = 0 .. 7: 0 12 24 4 16 28 8 20, 4 dwords each), pieces of
+//     6 dwords written as b64 by groups of 16 lanes too (6 l mod 32 covers every even bank once); the reads are contiguous.
+//   Rows go one after the other through the same strip (both at once would put the 2- and 4-byte kernels over 20 KB).
+// Other even widths: a lane takes one 2 x 2 quad, element stores (k_tensor's generic path).
+// The tensor's buffer resource ends with the frame: the second row of a lane in the fill row pair of an odd height, and anything a
+// wrong offset would reach behind the frame, is dropped by the bounds check.
+static constexpr int kLayoutChw = 0, kLayoutHwc = 1;          // = LEON_TENSOR_LAYOUT_*
+template <int EB> struct ImageElem { typedef uint8_t type; };
+template <> struct ImageElem<2> { typedef uint16_t type; };
+template <> struct ImageElem<4> { typedef uint32_t type; };
+// pixels per lane and row on the fast path
+constexpr int image_lane_px(int eb) { return eb == 4 ? 4 : 8; }
+// bytes of a lane's row piece in the HWC layout, and of the wave's exchange strip
+constexpr int image_piece_bytes(int eb) { return image_lane_px(eb) * 3 * eb; }
+constexpr int image_strip_bytes(int eb, int layout) { return layout == kLayoutHwc ? 64 * image_piece_bytes(eb) : 0; }
+
+template <int EB>
+__device__ __forceinline__ uint32_t image_elem(const typename ImageElem<EB>::type* tab, uint32_t px, int ch)
+{
+    const uint32_t v = (px >> (8 * ch)) & 255u;
+    if constexpr (EB == 1) return v;
+    else return tab[ch * 256 + v];
+}
+
+// One row piece of a lane, HWC: NPX pixels -> the wave's strip -> three store instructions of contiguous thirds.  `rowoff`: byte offset
+// of this lane's piece in the frame (kOobBit: none); strip: the wave's; lane: 0 .. 63.  All 64 lanes take part.
+template <int EB, int NPX>
+__device__ __forceinline__ void image_row_hwc(const typename ImageElem<EB>::type* tab, const uint32_t (&px)[NPX], char* strip, int lane,
+                                              __amdgpu_buffer_rsrc_t rs, uint32_t rowoff)
+{
+    constexpr int kPiece = NPX * 3 * EB, kThird = kPiece / 3;
+    static_assert(kPiece == image_piece_bytes(EB) && (kThird == 8 || kThird == 16), "a third is one b64 or b128 store");
+    uint32_t d[kPiece / 4];
+    if constexpr (EB == 1) {
+#pragma unroll
+        for (int g = 0; g < NPX / 4; g++) {          // 4 pixels: R G B R | G B R G | B R G B
+            const uint32_t p0 = px[4 * g] & 0xffffffu, p1 = px[4 * g + 1] & 0xffffffu, p2 = px[4 * g + 2] & 0xffffffu, p3 = px[4 * g + 3] & 0xffffffu;
+            d[3 * g] = p0 | (p1 << 24);
+            d[3 * g + 1] = (p1 >> 8) | (p2 << 16);
+            d[3 * g + 2] = (p2 >> 16) | (p3 << 8);
+        }
+    } else if constexpr (EB == 2) {
+#pragma unroll
+        for (int i = 0; i < kPiece / 4; i++)
+            d[i] = image_elem<EB>(tab, px[(2 * i) / 3], (2 * i) % 3) | (image_elem<EB>(tab, px[(2 * i + 1) / 3], (2 * i + 1) % 3) << 16);
+    } else {
+#pragma unroll
+        for (int i = 0; i < kPiece / 4; i++) d[i] = image_elem<EB>(tab, px[i / 3], i % 3);
+    }
+    char* mine = strip + lane * kPiece;
+    if constexpr (kThird == 8) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) *reinterpret_cast<v2u*>(mine + 8 * j) = v2u{d[2 * j], d[2 * j + 1]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 3; j++) *reinterpret_cast<v4u*>(mine + 16 * j) = v4u{d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3]};
+    }
+    wave_sync();
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const int k = j * 64 + lane;          // the wave's third k: piece k / 3, part k % 3
+        const int from = k / 3, part = k - 3 * from;
+        const uint32_t at = (uint32_t)__builtin_amdgcn_ds_bpermute(from * 4, (int)rowoff) + (uint32_t)(part * kThird);
+        if constexpr (kThird == 8) __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<const v2u*>(strip + k * 8), rs, (int)at, 0, kAuxFrameStore);
+        else __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const v4u*>(strip + k * 16), rs, (int)at, 0, kAuxFrameStore);
+    }
+    wave_sync();          // the strip is free for the next row
+}
+
+// One row of a lane, uint8 CHW: 8 pixels -> 8 bytes per channel
+__device__ __forceinline__ void image_row_chw_u8(const uint32_t (&px)[8], __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_bytes)
+{
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        const int sh = 8 * ch;
+        const uint32_t lo = ((px[0] >> sh) & 255u) | (((px[1] >> sh) & 255u) << 8) | (((px[2] >> sh) & 255u) << 16) | (((px[3] >> sh) & 255u) << 24);
+        const uint32_t hi = ((px[4] >> sh) & 255u) | (((px[5] >> sh) & 255u) << 8) | (((px[6] >> sh) & 255u) << 16) | (((px[7] >> sh) & 255u) << 24);
+        __builtin_amdgcn_raw_buffer_store_b64(v2u{lo, hi}, rs, (int)((uint32_t)ch * plane_bytes + off), 0, kAuxFrameStore);
+    }
+}
+
+template <int EB, int LAYOUT>
+__global__ __launch_bounds__(kRgbaBlock) void k_image(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
+                                                      const uint32_t* __restrict__ table, const Tables* __restrict__ T, TensorGeom G)
+{
+    typedef typename ImageElem<EB>::type Elem;
+    constexpr int kNpx = image_lane_px(EB);
+    constexpr int kStrip = image_strip_bytes(EB, LAYOUT);
+    static_assert(LAYOUT == kLayoutHwc || EB == 1, "float CHW is k_tensor's");
+    __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
+    __shared__ __attribute__((aligned(16))) Elem tab_s[EB == 1 ? 16 : 3 * 256];
+    __shared__ __attribute__((aligned(16))) char strip_s[kStrip ? (kRgbaBlock / 64) * kStrip : 16];
+    {
+        display_lut_to_lds(lut_s, T);
+        if constexpr (EB != 1) {
+            constexpr int kDwords = 3 * 256 * EB / 4;
+            for (int i = threadIdx.x; i < kDwords; i += kRgbaBlock) reinterpret_cast<uint32_t*>(tab_s)[i] = table[i];
+        }
+        wait_vmem_all();
+        __syncthreads();
+    }
+    const uint32_t idx_raw = blockIdx.x * (uint32_t)kRgbaBlock + threadIdx.x;
+    const bool valid = idx_raw < G.n_items;
+    const uint32_t idx = valid ? idx_raw : 0u;          // lanes behind the frame load what lane 0 loads and store nothing
+    const char* lut = reinterpret_cast<const char*>(lut_s);
+    const uint32_t pair = idx / G.per_row, col = idx - pair * G.per_row;
+    const uint32_t fid = frame_ids[blockIdx.z];
+    const uint8_t* src = planes_ring + (size_t)fid * join64(G.planes_pitch_lo, G.planes_pitch_hi);
+    uint8_t* dst = tensor_ring + (size_t)fid * join64(G.tensor_pitch_lo, G.tensor_pitch_hi);
+    const uint32_t r0 = 2u * pair, fw = (uint32_t)G.fw, fh = (uint32_t)G.fh;
+    const bool has_r1 = r0 + 1u < fh;                    // false: the last row of an odd height, left at 255 by the twin
+    const uint32_t plane_elems = fw * fh;
+    uint32_t two = 2u, three = 3u;                       // SDWA shift counts live in registers (display_half)
+    asm("" : "+v"(two), "+v"(three));
+    const uint8_t* yrow = src + (size_t)r0 * G.luma_stride;
+    const uint8_t* cbrow = src + G.cb_off + (size_t)pair * G.chroma_stride;
+    const uint8_t* crrow = src + G.cr_off + (size_t)pair * G.chroma_stride;
+    if (G.fast) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, (int)(3u * plane_elems * EB), 0x00020000);
+        const uint32_t oob = valid ? 0u : kOobBit;
+        uint32_t pa[kNpx], pb[kNpx];
+        if constexpr (kNpx == 4) {
+            const uint32_t y0 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(yrow + 4u * col));
+            const uint32_t y1 = has_r1 ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(yrow + G.luma_stride + 4u * col)) : 0u;
+            const uint32_t cb2 = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(cbrow + 2u * col));
+            const uint32_t cr2 = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(crrow + 2u * col));
+            const ChromaTerms c0 = chroma_terms<0>(lut, cb2, cr2, three), c1 = chroma_terms<1>(lut, cb2, cr2, three);
+            tensor_px4(lut, y0, c0, c1, !has_r1, two, pa);
+            tensor_px4(lut, y1, c0, c1, false, two, pb);
+        } else {
+            const v2u y0 = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(yrow + 8u * col));
+            const v2u y1 = has_r1 ? __builtin_nontemporal_load(reinterpret_cast<const v2u*>(yrow + G.luma_stride + 8u * col)) : v2u{0u, 0u};
+            const uint32_t cb4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(cbrow + 4u * col));
+            const uint32_t cr4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(crrow + 4u * col));
+            const ChromaTerms c[4] = {chroma_terms<0>(lut, cb4, cr4, three), chroma_terms<1>(lut, cb4, cr4, three),
+                                      chroma_terms<2>(lut, cb4, cr4, three), chroma_terms<3>(lut, cb4, cr4, three)};
+            tensor_px8(lut, y0, c, !has_r1, two, pa);
+            tensor_px8(lut, y1, c, false, two, pb);
+        }
+        const uint32_t off = r0 * fw + (uint32_t)kNpx * col;          // the lane's first pixel
+        if constexpr (LAYOUT == kLayoutHwc) {
+            char* strip = strip_s + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kStrip;
+            const int lane = threadIdx.x & 63;
+            const uint32_t rowoff = (off * 3u * EB) | oob;
+            image_row_hwc<EB, kNpx>(tab_s, pa, strip, lane, rs, rowoff);
+            image_row_hwc<EB, kNpx>(tab_s, pb, strip, lane, rs, rowoff + fw * 3u * EB);          // (behind the frame without a second row)
+        } else {
+            image_row_chw_u8(pa, rs, off | oob, plane_elems);
+            image_row_chw_u8(pb, rs, (off + fw) | (valid && has_r1 ? 0u : kOobBit), plane_elems);
+        }
+    } else if (valid) {
+        const uint32_t y0 = *reinterpret_cast<const uint16_t*>(yrow + 2u * col);
+        const uint32_t y1 = has_r1 ? *reinterpret_cast<const uint16_t*>(yrow + G.luma_stride + 2u * col) : 0u;
+        const ChromaTerms c0 = chroma_terms<0>(lut, (uint32_t)cbrow[col], (uint32_t)crrow[col], three);
+        const int opaque = 255 << kLutShift;
+        uint32_t px[4] = {rgba_px<0>(lut, y0, c0, opaque, two), rgba_px<1>(lut, y0, c0, opaque, two),
+                          rgba_px<0>(lut, y1, c0, opaque, two), rgba_px<1>(lut, y1, c0, opaque, two)};
+        if (!has_r1) px[0] = px[1] = 0xffffffffu;
+        Elem* out = reinterpret_cast<Elem*>(dst);
+        // element strides of a channel, a pixel and a row
+        const size_t sc = LAYOUT == kLayoutHwc ? 1 : plane_elems, sx = LAYOUT == kLayoutHwc ? 3 : 1, sy = (size_t)fw * sx;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            Elem* o = out + (size_t)ch * sc + (size_t)r0 * sy + (size_t)(2u * col) * sx;
+            __builtin_nontemporal_store((Elem)image_elem<EB>(tab_s, px[0], ch), o);
+            __builtin_nontemporal_store((Elem)image_elem<EB>(tab_s, px[1], ch), o + sx);
+            if (has_r1) {
+                __builtin_nontemporal_store((Elem)image_elem<EB>(tab_s, px[2], ch), o + sy);
+                __builtin_nontemporal_store((Elem)image_elem<EB>(tab_s, px[3], ch), o + sy + sx);
+            }
+        }
+    }
+}
+
 // ---- the frames as tensors at a model's input size (leon_pipeline.h, leon_pipeline_tensor_resize) -----------------------
 // frame planes record -> [3][oh][ow] elements: a crop box of the frame resampled with the host's integer tables (per axis first[o],
 // count[o], weights[o][taps], 22 fractional bits: leon_pipeline_resize_weights is the definition), horizontal pass first with an
@@ -1793,17 +1998,23 @@ __device__ __forceinline__ uint32_t resample_px(uint32_t ar, uint32_t ag, uint32
     return min(ar >> kResWeightShift, 255u) | (min(ag >> kResWeightShift, 255u) << 8) | (min(ab >> kResWeightShift, 255u) << 16);
 }
 
-template <int DTYPE>
-__global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
-                                                         const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
-                                                         ResampleGeom G)
+// The whole of a workgroup's work, for k_resample (EB = 2 or 4, CHW: one element store per lane and channel) and for k_image_scaled
+// (8-bit elements, the channels-last layout).  The latter's tile leaves through LDS: once the vertical pass has read them the h rows
+// are dead, and the tile's elements are packed there in memory order -- HWC: the 8 tile rows, 96 elements each; uint8 CHW: 3 x 8
+// channel rows of 32 bytes -- every row at the offset its first byte has in its 16-byte line of the frame (the tensor starts on a
+// 256-byte boundary).  A lane then takes one aligned 16-byte line of one row: inside the row it is ONE b128 store, at the row's two
+// ends its elements go one by one (a row's start is aligned to nothing: out_width is any number).
+template <int EB, int LAYOUT>
+__device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
+                                              const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
+                                              const ResampleGeom& G)
 {
-    typedef typename TensorElem<DTYPE>::type Elem;
+    typedef typename ImageElem<EB>::type Elem;
     static_assert(kResTileX * kResTileY == kRgbaBlock && kResTileX == 32, "lane = (tid & 31, tid >> 5)");
     __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
-    __shared__ __attribute__((aligned(16))) Elem tab_s[3 * 256];
+    __shared__ __attribute__((aligned(16))) Elem tab_s[EB == 1 ? 16 : 3 * 256];
     __shared__ __attribute__((aligned(16))) uint32_t stage_s[kResStagePx];
-    __shared__ uint32_t h_s[kResHRows * kResTileX];
+    __shared__ __attribute__((aligned(16))) uint32_t h_s[kResHRows * kResTileX];
     __shared__ int32_t wx_s[kResTileX * kResMaxTaps], wy_s[kResTileY * kResMaxTaps];
     __shared__ int32_t fx_s[kResTileX], nx_s[kResTileX], fy_s[kResTileY], ny_s[kResTileY];
     const int tid = threadIdx.x;
@@ -1814,14 +2025,11 @@ __global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restri
     const int32_t* first_y = rt + G.off_fy;
     const int32_t* count_y = rt + G.off_cy;
     {   // the conversion tables and the element table as k_tensor loads them, then the tile's slices of the resampling tables
-        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const int lane0 = tid & 63;
-        const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc((void*)T->rgba_lut, 0, kLdsLut, 0x00020000);
-        for (int c = wave; c < kLdsLut / 1024; c += kRgbaBlock / 64)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(reinterpret_cast<char*>(lut_s) + c * 1024), 16,
-                                                     (int)(lane0 * 16u), c * 1024, 0, 0);
-        constexpr int kDwords = 3 * 256 * (int)sizeof(Elem) / 4;
-        for (int i = tid; i < kDwords; i += kRgbaBlock) reinterpret_cast<uint32_t*>(tab_s)[i] = table[i];
+        display_lut_to_lds(lut_s, T);
+        if constexpr (EB != 1) {
+            constexpr int kDwords = 3 * 256 * EB / 4;
+            for (int i = tid; i < kDwords; i += kRgbaBlock) reinterpret_cast<uint32_t*>(tab_s)[i] = table[i];
+        }
         const int32_t* wxg = rt + G.off_wx + (size_t)ox0 * G.taps_x;
         for (int i = tid; i < nox * G.taps_x; i += kRgbaBlock) wx_s[i] = wxg[i];
         const int32_t* wyg = rt + G.off_wy + (size_t)oy0 * G.taps_y;
@@ -1920,17 +2128,80 @@ __global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restri
         }
     }
     const uint32_t px = resample_px(ar, ag, ab);
-    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(dst);
     const uint32_t plane_elems = (uint32_t)G.ow * (uint32_t)G.oh;
-    const uint32_t at = (uint32_t)(oy0 + sub) * (uint32_t)G.ow + (uint32_t)(ox0 + o);
-    const uint32_t oob = valid ? 0u : kOobBit;
+    if constexpr (LAYOUT == kLayoutChw && EB != 1) {
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(dst);
+        const uint32_t at = (uint32_t)(oy0 + sub) * (uint32_t)G.ow + (uint32_t)(ox0 + o);
+        const uint32_t oob = valid ? 0u : kOobBit;
 #pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        const Elem e = tab_s[ch * 256 + ((px >> (8 * ch)) & 255u)];
-        const uint32_t voff = (((uint32_t)ch * plane_elems + at) * (uint32_t)sizeof(Elem)) | oob;
-        if constexpr (sizeof(Elem) == 4) __builtin_amdgcn_raw_buffer_store_b32(e, rs, (int)voff, 0, kAuxFrameStore);
-        else __builtin_amdgcn_raw_buffer_store_b16(e, rs, (int)voff, 0, kAuxFrameStore);
+        for (int ch = 0; ch < 3; ch++) {
+            const Elem e = tab_s[ch * 256 + ((px >> (8 * ch)) & 255u)];
+            const uint32_t voff = (((uint32_t)ch * plane_elems + at) * (uint32_t)sizeof(Elem)) | oob;
+            if constexpr (sizeof(Elem) == 4) __builtin_amdgcn_raw_buffer_store_b32(e, rs, (int)voff, 0, kAuxFrameStore);
+            else __builtin_amdgcn_raw_buffer_store_b16(e, rs, (int)voff, 0, kAuxFrameStore);
+        }
+    } else {
+        // rows of the tile in memory order: HWC 8 of 96 elements, uint8 CHW 3 x 8 of 32 bytes; 16 spare bytes for the row's place in its line
+        constexpr bool kHwc = LAYOUT == kLayoutHwc;
+        constexpr int kRowElems = kHwc ? 3 * kResTileX : kResTileX, kRowStride = kRowElems * EB + 16;
+        constexpr int kRows = kHwc ? kResTileY : 3 * kResTileY, kLines = (kRowElems * EB + 15) / 16 + 1;
+        constexpr int kLinesP2 = kLines <= 4 ? 4 : 32;          // work items of a row: a power of two of lanes
+        static_assert(kRows * kRowStride <= (int)sizeof(h_s) && kLines <= kLinesP2 && kRows * kLinesP2 <= kRgbaBlock, "the packed tile fits the h rows, a lane per line");
+        // byte offset in the frame of row `row` of the tile's rows (row = tile row, or channel * 8 + tile row)
+        auto row_start = [&](int row) -> uint32_t {
+            if constexpr (kHwc) return ((uint32_t)(oy0 + row) * (uint32_t)G.ow + (uint32_t)ox0) * 3u * EB;
+            else return ((uint32_t)(row >> 3) * plane_elems + (uint32_t)(oy0 + (row & 7)) * (uint32_t)G.ow + (uint32_t)ox0) * EB;
+        };
+        char* pack = reinterpret_cast<char*>(h_s);
+        __syncthreads();          // every lane has read its h column
+        if (valid) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                const int row = kHwc ? sub : ch * kResTileY + sub;
+                const int at = (int)(row_start(row) & 15u) + (kHwc ? (o * 3 + ch) * EB : o * EB);
+                *reinterpret_cast<Elem*>(pack + row * kRowStride + at) = (Elem)image_elem<EB>(tab_s, px, ch);
+            }
+        }
+        __syncthreads();
+        const int row = tid / kLinesP2, line = tid & (kLinesP2 - 1);
+        if (row < kRows && (kHwc ? row : (row & 7)) < noy) {
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, (int)(3u * plane_elems * EB), 0x00020000);
+            const uint32_t g0 = row_start(row), g1 = g0 + (uint32_t)(nox * (kHwc ? 3 : 1) * EB);      // the row's bytes in the frame
+            const uint32_t a0 = (g0 & ~15u) + 16u * (uint32_t)line;                                   // this lane's line
+            const char* from = pack + row * kRowStride + 16 * line;
+            if (a0 >= g0 && a0 + 16u <= g1) __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const v4u*>(from), rs, (int)a0, 0, kAuxFrameStore);
+            else if (a0 + 16u > g0 && a0 < g1) {
+                // a line at an end of the row: the tile beside this one (and the row above or below) owns the line's other bytes and
+                // writes them itself, so only the elements inside [g0, g1) may be stored -- one by one
+                for (int e = 0; e < 16 / EB; e++) {
+                    const uint32_t a = a0 + (uint32_t)(e * EB);
+                    if (a < g0 || a >= g1) continue;
+                    const Elem v = *reinterpret_cast<const Elem*>(from + e * EB);
+                    if constexpr (EB == 4) __builtin_amdgcn_raw_buffer_store_b32(v, rs, (int)a, 0, kAuxFrameStore);
+                    else if constexpr (EB == 2) __builtin_amdgcn_raw_buffer_store_b16(v, rs, (int)a, 0, kAuxFrameStore);
+                    else __builtin_amdgcn_raw_buffer_store_b8(v, rs, (int)a, 0, kAuxFrameStore);
+                }
+            }
+        }
     }
+}
+
+template <int DTYPE>
+__global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
+                                                         const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
+                                                         ResampleGeom G)
+{
+    resample_body<(int)sizeof(typename TensorElem<DTYPE>::type), kLayoutChw>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
+}
+
+// 8-bit elements and / or the channels-last layout at a model's input size (leon_pipeline_tensor_format with leon_pipeline_tensor_resize)
+template <int EB, int LAYOUT>
+__global__ __launch_bounds__(kRgbaBlock) void k_image_scaled(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
+                                                             const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
+                                                             ResampleGeom G)
+{
+    static_assert(LAYOUT == kLayoutHwc || EB == 1, "float CHW is k_resample's");
+    resample_body<EB, LAYOUT>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

@@ -122,7 +122,7 @@ struct leon_pipeline {
     // output TENSOR: the ring of [3][fh][fw] tensors (tensor_pitch apart), the element table T (host, device), and per ring entry
     // the frame indices of its window for k_tensor (pinned, device)
     uint8_t* d_tensor = nullptr;
-    int tensor_dtype = 0;
+    int tensor_dtype = 0, tensor_layout = 0;          // LEON_TENSOR_*, LEON_TENSOR_LAYOUT_* (float CHW: k_tensor / k_resample; the rest: k_image / k_image_scaled)
     size_t tensor_elem = 0, tensor_bytes = 0, tensor_pitch = 0;
     std::vector<uint8_t> tensor_table;
     uint32_t* d_tensor_table = nullptr;
@@ -499,7 +499,14 @@ int tensor_table_build(const leon_pipeline_config* cfg, const leon_pipeline_tens
     const bool bit = (cfg->output & LEON_PIPELINE_OUTPUT_TENSOR) != 0;
     if (!bit) return fail(LEON_ERR_INVALID, "tensor settings (dtype %d) without LEON_PIPELINE_OUTPUT_TENSOR in output %d", tc ? tc->dtype : 0, cfg->output);
     const int dtype = tc && tc->dtype ? tc->dtype : LEON_TENSOR_F16;
-    if (dtype != LEON_TENSOR_F16 && dtype != LEON_TENSOR_BF16 && dtype != LEON_TENSOR_F32) return fail(LEON_ERR_INVALID, "tensor dtype %d", dtype);
+    if (dtype != LEON_TENSOR_F16 && dtype != LEON_TENSOR_BF16 && dtype != LEON_TENSOR_F32 && dtype != LEON_TENSOR_U8) return fail(LEON_ERR_INVALID, "tensor dtype %d", dtype);
+    if (dtype == LEON_TENSOR_U8) {          // the element is the colour value itself: nothing to scale
+        for (int c = 0; c < 3 && tc; c++)
+            if (tc->scale[c] != 0.0f || tc->bias[c] != 0.0f) return fail(LEON_ERR_INVALID, "tensor dtype %d (LEON_TENSOR_U8) takes no scale / bias (channel %d: they must be 0)", dtype, c);
+        for (int i = 0; i < 3 * 256 && out; i++) ((uint8_t*)out)[i] = (uint8_t)(i & 255);
+        if (dtype_out) *dtype_out = dtype;
+        return LEON_OK;
+    }
     float scale[3] = {0, 0, 0}, bias[3] = {0, 0, 0};
     bool all_zero = true;
     for (int c = 0; c < 3 && tc; c++) {
@@ -569,6 +576,24 @@ int resize_axis_build(const char* axis, int32_t in_size, int32_t crop_start, int
         if (n > most) most = n;
     }
     if (taps) *taps = most;
+    return LEON_OK;
+}
+
+// Every refusal of the format settings is here
+int tensor_format_check(const leon_pipeline_config* cfg, const leon_pipeline_tensor_format* fm, int* layout_out)
+{
+    int32_t any = 0;
+    if (fm) {
+        any = fm->layout;
+        for (int i = 0; i < 7; i++) any |= fm->reserved[i];
+    }
+    if (layout_out) *layout_out = LEON_TENSOR_LAYOUT_CHW;
+    if (!any) return LEON_OK;
+    if (!(cfg->output & LEON_PIPELINE_OUTPUT_TENSOR)) return fail(LEON_ERR_INVALID, "tensor format settings (layout %d) without LEON_PIPELINE_OUTPUT_TENSOR in output %d", fm->layout, cfg->output);
+    for (int i = 0; i < 7; i++)
+        if (fm->reserved[i]) return fail(LEON_ERR_INVALID, "tensor format: reserved word %d is %d, not 0", i, fm->reserved[i]);
+    if (fm->layout != LEON_TENSOR_LAYOUT_CHW && fm->layout != LEON_TENSOR_LAYOUT_HWC) return fail(LEON_ERR_INVALID, "tensor format: layout %d", fm->layout);
+    if (layout_out) *layout_out = fm->layout;
     return LEON_OK;
 }
 
@@ -1053,6 +1078,20 @@ void launch_k_resample(const leon_pipeline* p, const uint32_t* ids, unsigned n, 
     hipLaunchKernelGGL(leon::k_resample<DTYPE>, grid, dim3(leon::kRgbaBlock), 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, ids,
                        (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, G);
 }
+// ... every combination but float CHW: 8-bit elements and / or the channels-last layout (k_image, k_image_scaled)
+template <int EB, int LAYOUT>
+void launch_k_image(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::TensorGeom& G)
+{
+    hipLaunchKernelGGL((leon::k_image<EB, LAYOUT>), dim3((G.n_items + leon::kRgbaBlock - 1) / leon::kRgbaBlock, 1, n), dim3(leon::kRgbaBlock), 0, p->dec->stream,
+                       (const uint8_t*)p->d_planes, p->d_tensor, ids, (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, G);
+}
+template <int EB, int LAYOUT>
+void launch_k_image_scaled(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::ResampleGeom& G)
+{
+    const dim3 grid((unsigned)((G.ow + leon::kResTileX - 1) / leon::kResTileX), (unsigned)((G.oh + leon::kResTileY - 1) / leon::kResTileY), n);
+    hipLaunchKernelGGL((leon::k_image_scaled<EB, LAYOUT>), grid, dim3(leon::kRgbaBlock), 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, ids,
+                       (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, G);
+}
 int launch_tensors(leon_pipeline* p, const PipeWindow* w)
 {
     const size_t n = w->frame_ids.size();
@@ -1062,6 +1101,8 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
     uint32_t* dv = p->d_tensor_ids + (size_t)w->ring * entry;
     for (size_t i = 0; i < n; i++) h[i] = (uint32_t)((size_t)w->ring * entry) + w->frame_ids[i];
     HIP_TRY(hipMemcpyAsync(dv, h, n * 4, hipMemcpyHostToDevice, p->dec->stream));
+    const bool hwc = p->tensor_layout == LEON_TENSOR_LAYOUT_HWC;
+    const bool image = hwc || p->tensor_dtype == LEON_TENSOR_U8;          // not k_tensor's / k_resample's
     if (p->tensor_geom.resized) {
         leon::ResampleGeom R = p->resample_geom;
         R.luma_stride = p->planes_geom.luma_stride; R.chroma_stride = p->planes_geom.chroma_stride;
@@ -1070,7 +1111,12 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
         R.tensor_pitch_lo = (uint32_t)(p->tensor_pitch & 0xffffffffu); R.tensor_pitch_hi = (uint32_t)((uint64_t)p->tensor_pitch >> 32);
         for (size_t at = 0; at < n; at += 65535) {
             const unsigned m = (unsigned)std::min<size_t>(65535, n - at);
-            if (p->tensor_dtype == LEON_TENSOR_F16) launch_k_resample<leon::kTensorF16>(p, dv + at, m, R);
+            if (image) {
+                if (p->tensor_elem == 1 && !hwc) launch_k_image_scaled<1, leon::kLayoutChw>(p, dv + at, m, R);
+                else if (p->tensor_elem == 1) launch_k_image_scaled<1, leon::kLayoutHwc>(p, dv + at, m, R);
+                else if (p->tensor_elem == 2) launch_k_image_scaled<2, leon::kLayoutHwc>(p, dv + at, m, R);
+                else launch_k_image_scaled<4, leon::kLayoutHwc>(p, dv + at, m, R);
+            } else if (p->tensor_dtype == LEON_TENSOR_F16) launch_k_resample<leon::kTensorF16>(p, dv + at, m, R);
             else if (p->tensor_dtype == LEON_TENSOR_BF16) launch_k_resample<leon::kTensorBf16>(p, dv + at, m, R);
             else launch_k_resample<leon::kTensorF32>(p, dv + at, m, R);
         }
@@ -1080,7 +1126,7 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
     leon::TensorGeom G{};
     G.fw = p->vinfo.frame_width; G.fh = p->vinfo.frame_height;
     G.fast = (G.fw & 7) == 0;
-    G.per_row = (uint32_t)(G.fast ? G.fw / leon::tensor_lane_px(p->tensor_dtype) : G.fw / 2);
+    G.per_row = (uint32_t)(G.fast ? G.fw / (image ? leon::image_lane_px((int)p->tensor_elem) : leon::tensor_lane_px(p->tensor_dtype)) : G.fw / 2);
     G.n_items = G.per_row * (uint32_t)((G.fh + 1) / 2);
     G.luma_stride = p->planes_geom.luma_stride; G.chroma_stride = p->planes_geom.chroma_stride;
     G.cb_off = p->planes_geom.cb_off; G.cr_off = p->planes_geom.cr_off;
@@ -1089,7 +1135,12 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
     if (!G.n_items) return LEON_OK;
     for (size_t at = 0; at < n; at += 65535) {
         const unsigned m = (unsigned)std::min<size_t>(65535, n - at);
-        if (p->tensor_dtype == LEON_TENSOR_F16) launch_k_tensor<leon::kTensorF16>(p, dv + at, m, G);
+        if (image) {
+            if (p->tensor_elem == 1 && !hwc) launch_k_image<1, leon::kLayoutChw>(p, dv + at, m, G);
+            else if (p->tensor_elem == 1) launch_k_image<1, leon::kLayoutHwc>(p, dv + at, m, G);
+            else if (p->tensor_elem == 2) launch_k_image<2, leon::kLayoutHwc>(p, dv + at, m, G);
+            else launch_k_image<4, leon::kLayoutHwc>(p, dv + at, m, G);
+        } else if (p->tensor_dtype == LEON_TENSOR_F16) launch_k_tensor<leon::kTensorF16>(p, dv + at, m, G);
         else if (p->tensor_dtype == LEON_TENSOR_BF16) launch_k_tensor<leon::kTensorBf16>(p, dv + at, m, G);
         else launch_k_tensor<leon::kTensorF32>(p, dv + at, m, G);
     }
@@ -1355,7 +1406,8 @@ constexpr size_t kMaxVlcIndexLds = 160 * 1024 - 512;
 
 // Create, stage 1: what the config and the stream decide -- the shards, the run, W / R / K, the longest GOP, the front
 // end, the output and its roads, info.  No HIP call and no allocation: a refused config leaves nothing to free but p.
-int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tcfg, const leon_pipeline_tensor_resize* rz, const uint8_t* stream, size_t bytes, size_t valid_bytes)
+int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tcfg, const leon_pipeline_tensor_resize* rz,
+                  const leon_pipeline_tensor_format* fm, const uint8_t* stream, size_t bytes, size_t valid_bytes)
 {
     leon_vlc_stream* st = nullptr;
     // the container header, the key map and the first sequence header must have arrived
@@ -1452,7 +1504,9 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
         p->tensor_table.resize(3 * 256 * 4);
         const int rc = tensor_table_build(cfg, tcfg, &p->tensor_dtype, p->tensor_table.data());
         if (rc != LEON_OK) return rc;
-        p->tensor_elem = p->tensor_dtype == LEON_TENSOR_F32 ? 4 : 2;
+        p->tensor_elem = p->tensor_dtype == LEON_TENSOR_F32 ? 4 : (p->tensor_dtype == LEON_TENSOR_U8 ? 1 : 2);
+        const int frc = tensor_format_check(cfg, fm, &p->tensor_layout);
+        if (frc != LEON_OK) return frc;
         p->tensor_table.resize(3 * 256 * p->tensor_elem);
         const int rrc = plan_resize(p, rz);
         if (rrc != LEON_OK) return rrc;
@@ -1465,6 +1519,7 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
         p->info.tensor_gop_pitch = (uint64_t)p->tensor_pitch * (uint64_t)p->max_pics;
     } else if (tcfg && tcfg->dtype) return fail(LEON_ERR_INVALID, "tensor dtype %d without LEON_PIPELINE_OUTPUT_TENSOR in output", tcfg->dtype);
     else if (resize_asked(rz)) return fail(LEON_ERR_INVALID, "resize settings (%d x %d) without LEON_PIPELINE_OUTPUT_TENSOR in output %d", rz->out_width, rz->out_height, cfg->output);
+    else if (const int frc = tensor_format_check(cfg, fm, nullptr)) return frc;
     // the frames' planes (output YCbCr): the layout of include/leon_pipeline.h, one record per frame, A behind Cr for yuva
     p->output = cfg->output ? cfg->output : LEON_PIPELINE_OUTPUT_RGBA;
     p->planes_geom = planes_layout(p->vinfo.frame_width, p->vinfo.frame_height, &p->planes_bytes);
@@ -1710,12 +1765,29 @@ int leon_pipeline_get_tensor_geometry(leon_pipeline* p, leon_pipeline_tensor_geo
 int leon_pipeline_create_tensor_resized(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const leon_pipeline_tensor_resize* resize,
                                         const uint8_t* stream, size_t bytes, size_t valid_bytes, leon_pipeline_callback cb, void* user, leon_pipeline** out)
 {
+    return leon_pipeline_create_tensor_format(cfg, tensor, resize, nullptr, stream, bytes, valid_bytes, cb, user, out);
+}
+
+int leon_pipeline_get_tensor_shape(leon_pipeline* p, leon_pipeline_tensor_shape* out)
+{
+    if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR)) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    const int64_t h = p->tensor_geom.height, w = p->tensor_geom.width;
+    const bool hwc = p->tensor_layout == LEON_TENSOR_LAYOUT_HWC;
+    *out = leon_pipeline_tensor_shape{p->tensor_dtype, (int32_t)p->tensor_elem, p->tensor_layout, 3, (int32_t)h, (int32_t)w, hwc ? 1 : h * w, hwc ? 3 * w : w, hwc ? 3 : 1};
+    return LEON_OK;
+}
+
+int leon_pipeline_create_tensor_format(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const leon_pipeline_tensor_resize* resize,
+                                       const leon_pipeline_tensor_format* format, const uint8_t* stream, size_t bytes, size_t valid_bytes,
+                                       leon_pipeline_callback cb, void* user, leon_pipeline** out)
+{
     if (!cfg || !stream || bytes < 16 || !out) return fail(LEON_ERR_INVALID, "null argument");
     if (valid_bytes > bytes) return fail(LEON_ERR_INVALID, "%zu valid bytes of a stream of %zu", valid_bytes, bytes);
     *out = nullptr;
     leon_pipeline* p = new (std::nothrow) leon_pipeline();
     if (!p) return fail(LEON_ERR_NOMEM, "out of host memory");
-    int rc = plan_pipeline(p, cfg, tensor, resize, stream, bytes, valid_bytes);
+    int rc = plan_pipeline(p, cfg, tensor, resize, format, stream, bytes, valid_bytes);
     if (rc != LEON_OK) { delete p; return rc; }
     p->cb = cb;
     p->user = user;

@@ -23,7 +23,7 @@
  *   p.readPlanes(window, index) -> {y, cb, cr[, a]} packed Uint8Arrays: the frame's YCbCr 4:2:0 planes, with
  *                                  opts.output 'ycbcr' (no RGBA at all) or 'both' -- the reference's frame payload
  *                                  {ybr: [Y, Cb, Cr]} (decoders/jsv.js:600, :673); default 'rgba'
- *   p.readTensor(window, index) -> Uint16Array (fp16 / bf16 bit patterns) or Float32Array, [3][H][W] packed: the frame as a planar,
+ *   p.readTensor(window, index) -> Uint16Array (fp16 / bf16 bit patterns), Float32Array or Uint8Array, [3][H][W] packed: the frame as a planar,
  *                                  normalised R, G, B tensor for a model, with opts.output 'tensor' (no RGBA at all),
  *                                  'rgba+tensor', 'ycbcr+tensor' or 'all'; opts.tensorDtype 'float16' (default) / 'bfloat16' /
  *                                  'float32', opts.tensorScale / tensorBias [r, g, b] (default 1/255 and 0: values in [0, 1]);
@@ -32,6 +32,9 @@
  *                                  opts.tensorSize [h, w] (and opts.tensorCrop [x, y, w, h], frame pixels; default the whole frame):
  *                                  that crop box resampled on the device to h x w (antialiased triangle filter, include/leon_pipeline.h)
  *                                  -- readTensor then returns [3][h][w]; stats() reports tensorWidth, tensorHeight
+ *                                  opts.tensorDtype 'uint8': the elements are the 8-bit colour values themselves (no tensorScale /
+ *                                  tensorBias), readTensor returns a Uint8Array; opts.tensorLayout 'chw' (default) or 'hwc': channels
+ *                                  last, [H][W][3] -- uint8 hwc is the packed RGB frame, 3 bytes per pixel; stats() reports tensorLayout
  *   p.releaseWindow(window); p.stats(); p.destroy();
  */
 const path = require('path');
@@ -46,7 +49,8 @@ class LeonPipeline extends EventEmitter {
     this.autoRelease = opts.autoRelease !== false;
     this.ended = false;
     const outputs = { rgba: 1, ycbcr: 2, both: 3, tensor: 16, 'rgba+tensor': 17, 'ycbcr+tensor': 18, all: 19 };
-    const dtypes = { float16: 1, bfloat16: 2, float32: 3 };
+    const dtypes = { float16: 1, bfloat16: 2, float32: 3, uint8: 8 };
+    const layouts = { chw: 0, hwc: 1 };
     let output = opts.output === undefined ? 0 : opts.output;
     if (typeof output === 'string') {
       if (!(output in outputs)) throw new TypeError("output: 'rgba', 'ycbcr', 'both', 'tensor', 'rgba+tensor', 'ycbcr+tensor' or 'all'");
@@ -54,8 +58,13 @@ class LeonPipeline extends EventEmitter {
     }
     let tensorDtype = opts.tensorDtype === undefined ? 0 : opts.tensorDtype;
     if (typeof tensorDtype === 'string') {
-      if (!(tensorDtype in dtypes)) throw new TypeError("tensorDtype: 'float16', 'bfloat16' or 'float32'");
+      if (!(tensorDtype in dtypes)) throw new TypeError("tensorDtype: 'float16', 'bfloat16', 'float32' or 'uint8'");
       tensorDtype = dtypes[tensorDtype];
+    }
+    let tensorLayout = opts.tensorLayout === undefined ? 0 : opts.tensorLayout;
+    if (typeof tensorLayout === 'string') {
+      if (!(tensorLayout in layouts)) throw new TypeError("tensorLayout: 'chw' or 'hwc'");
+      tensorLayout = layouts[tensorLayout];
     }
     // tensorSize [h, w] (, tensorCrop [x, y, w, h] in frame pixels): the tensors resampled on the device to a model's input size
     const ints = (v, n, what) => {
@@ -66,7 +75,7 @@ class LeonPipeline extends EventEmitter {
     const [tensorOutHeight, tensorOutWidth] = ints(opts.tensorSize, 2, 'tensorSize: [height, width]');
     const [tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight] = ints(opts.tensorCrop, 4, 'tensorCrop: [x, y, width, height]');
     const resize = { tensorOutHeight, tensorOutWidth, tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight };
-    this._p = addon.createPipeline(stream, Object.assign({}, opts, { output, tensorDtype }, resize), (w, frames, status) => this._deliver(w, frames, status));
+    this._p = addon.createPipeline(stream, Object.assign({}, opts, { output, tensorDtype, tensorLayout }, resize), (w, frames, status) => this._deliver(w, frames, status));
   }
 
   _deliver(window, frames, status) {

@@ -37,6 +37,7 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_read_frame_planes",
     "leon_pipeline_create_tensor", "leon_pipeline_tensor_table", "leon_pipeline_window_tensors", "leon_pipeline_read_tensor",
     "leon_pipeline_create_tensor_resized", "leon_pipeline_resize_weights", "leon_pipeline_get_tensor_geometry",
+    "leon_pipeline_create_tensor_format", "leon_pipeline_get_tensor_shape",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -48,19 +49,33 @@ PIPELINE_TENSOR_OUTPUTS = {"tensor": PIPELINE_OUTPUT_TENSOR, "rgba+tensor": PIPE
                            "all": PIPELINE_OUTPUT_RGBA | PIPELINE_OUTPUT_YCBCR | PIPELINE_OUTPUT_TENSOR}
 TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 1, 2, 3       # LEON_TENSOR_*
 TENSOR_DTYPES = {"float16": TENSOR_F16, "bfloat16": TENSOR_BF16, "float32": TENSOR_F32}
+TENSOR_U8 = 8                                       # LEON_TENSOR_U8 ("uint8"): the element is the 8-bit colour value
+TENSOR_LAYOUT_CHW, TENSOR_LAYOUT_HWC = 0, 1         # LEON_TENSOR_LAYOUT_*
+TENSOR_LAYOUTS = {"chw": TENSOR_LAYOUT_CHW, "hwc": TENSOR_LAYOUT_HWC}
 
 
 def _tensor_dtype_code(dtype):
+    if dtype == "uint8":
+        return TENSOR_U8
     return TENSOR_DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+
+
+def _tensor_layout_code(layout):
+    return TENSOR_LAYOUTS[layout] if isinstance(layout, str) else int(layout)
 
 
 def tensor_table(dtype="float16", scale=None, bias=None):
     """The table T of the tensor output (include/leon_pipeline.h), in numpy and independent of the C code: [3, 256],
     T[c][v] = to_dtype(float32(float64(v) * float64(scale[c]) + float64(bias[c]))); scale and bias default to 1/255 and 0.
-    float16 / float32 arrays; bfloat16 as uint16 bit patterns (round to nearest even of the float32 value)."""
+    float16 / float32 arrays; bfloat16 as uint16 bit patterns (round to nearest even of the float32 value); "uint8": the identity
+    table, T[c][v] = v (a scale or bias other than zero: ValueError)."""
     code = _tensor_dtype_code(dtype)
     sc = np.asarray([0, 0, 0] if scale is None else scale, dtype=np.float32).reshape(3)
     bi = np.asarray([0, 0, 0] if bias is None else bias, dtype=np.float32).reshape(3)
+    if code == TENSOR_U8:
+        if sc.any() or bi.any():
+            raise ValueError("tensor dtype uint8 takes no scale / bias")
+        return np.tile(np.arange(256, dtype=np.uint8), (3, 1))
     if not sc.any() and not bi.any():
         sc = np.full(3, np.float32(1.0 / 255.0), dtype=np.float32)
     v = np.arange(256, dtype=np.float64)[None, :]
@@ -219,6 +234,15 @@ class PipelineTensorGeometry(C.Structure):
                 ("crop_height", C.c_int32), ("taps_x", C.c_int32), ("taps_y", C.c_int32), ("resized", C.c_int32)]
 
 
+class PipelineTensorFormat(C.Structure):
+    _fields_ = [("layout", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class PipelineTensorShape(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("element_bytes", C.c_int32), ("layout", C.c_int32), ("channels", C.c_int32), ("height", C.c_int32),
+                ("width", C.c_int32), ("stride_c", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64)]
+
+
 class PipelineFrame(C.Structure):
     _fields_ = [("gop", C.c_uint64), ("display_index", C.c_int32), ("type", C.c_int32), ("ts_ms", C.c_double),
                 ("rgba", C.c_void_p), ("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("a", C.c_void_p)]
@@ -314,6 +338,9 @@ def load():
                                                         C.c_size_t, C.c_size_t, PIPELINE_CB, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.leon_pipeline_resize_weights.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.leon_pipeline_get_tensor_geometry.argtypes = [C.c_void_p, C.POINTER(PipelineTensorGeometry)]
+    lib.leon_pipeline_create_tensor_format.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.POINTER(PipelineTensorResize),
+                                                       C.POINTER(PipelineTensorFormat), C.c_void_p, C.c_size_t, C.c_size_t, PIPELINE_CB, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.leon_pipeline_get_tensor_shape.argtypes = [C.c_void_p, C.POINTER(PipelineTensorShape)]
     lib.leon_pipeline_tensor_table.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.c_void_p]
     lib.leon_pipeline_window_tensors.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int32]
     lib.leon_pipeline_read_tensor.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
@@ -588,11 +615,15 @@ class Pipeline:
     tensor_view(frame) and window_tensor(frames) wrap it in place as torch tensors.
     tensor_size=(out_h, out_w) [, tensor_crop=(x, y, w, h) in frame pixels]: the tensors are that crop box (default: the whole frame)
     resampled on the device to a model's input size -- element = table[c][resize_rgb(rgb, crop, size)] --, and every tensor shape
-    above is [3, out_h, out_w] (tensor_geometry has the values in force)."""
+    above is [3, out_h, out_w] (tensor_geometry has the values in force).
+    tensor_dtype="uint8": the elements are the 8-bit colour values themselves (no scale / bias).  tensor_layout="hwc": channels last
+    -- every shape above is [H, W, 3] ([N, H, W, 3] for window_tensor), a packed uint8 HWC frame is 3 bytes per pixel; tensor_shape
+    (PipelineTensorShape) has the element type, the layout and the strides in elements."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
-                 output="rgba", tensor_dtype="float16", tensor_scale=None, tensor_bias=None, tensor_size=None, tensor_crop=None, tensor_filter=RESIZE_TRIANGLE):
+                 output="rgba", tensor_dtype="float16", tensor_scale=None, tensor_bias=None, tensor_size=None, tensor_crop=None, tensor_filter=RESIZE_TRIANGLE,
+                 tensor_layout="chw"):
         self.lib = load()
         self.device_id = device_id
         # a name of PIPELINE_OUTPUTS, or the raw bit set (anything the library does not know is refused by create)
@@ -606,6 +637,9 @@ class Pipeline:
             oh, ow = (0, 0) if tensor_size is None else tensor_size
             cx, cy, cw, ch = (0, 0, 0, 0) if tensor_crop is None else tensor_crop
             rcfg = PipelineTensorResize(int(cx), int(cy), int(cw), int(ch), int(ow), int(oh), int(tensor_filter))
+        fcfg = None
+        if _tensor_layout_code(tensor_layout) != TENSOR_LAYOUT_CHW:      # only a non-default format goes through leon_pipeline_create_tensor_format
+            fcfg = PipelineTensorFormat(_tensor_layout_code(tensor_layout))
         self._data = (C.c_uint8 * len(data)).from_buffer_copy(data)      # must outlive the pipeline
         self._on_window = on_window
         self.windows = 0
@@ -658,7 +692,10 @@ class Pipeline:
         h = C.c_void_p()
         self.h = None
         # valid_bytes: the stream is still arriving (leon_pipeline_create_partial); feed() reports progress
-        if rcfg is not None:
+        if fcfg is not None:
+            rc = self.lib.leon_pipeline_create_tensor_format(C.byref(cfg), None if tcfg is None else C.byref(tcfg), None if rcfg is None else C.byref(rcfg), C.byref(fcfg),
+                                                             self._data, len(data), len(data) if valid_bytes is None else int(valid_bytes), self._cb, None, C.byref(h))
+        elif rcfg is not None:
             rc = self.lib.leon_pipeline_create_tensor_resized(C.byref(cfg), None if tcfg is None else C.byref(tcfg), C.byref(rcfg), self._data, len(data),
                                                               len(data) if valid_bytes is None else int(valid_bytes), self._cb, None, C.byref(h))
         elif tcfg is not None:
@@ -675,10 +712,15 @@ class Pipeline:
         self.info = info
         # the tensors' shape: the frame's, or tensor_size (None without tensor output)
         self.tensor_geometry = None
+        self.tensor_shape = None
         if rc == OK and info.tensor_dtype:
             geom = PipelineTensorGeometry()
             rc = self.lib.leon_pipeline_get_tensor_geometry(self.h, C.byref(geom))
             self.tensor_geometry = geom
+        if rc == OK and info.tensor_dtype:
+            shape = PipelineTensorShape()
+            rc = self.lib.leon_pipeline_get_tensor_shape(self.h, C.byref(shape))
+            self.tensor_shape = shape
         ready.set()
         _chk(rc)
 
@@ -699,14 +741,22 @@ class Pipeline:
         return (y, cb, cr) if a is None else (y, cb, cr, a)
 
     def _tensor_np_dtype(self):
-        return {TENSOR_F16: np.float16, TENSOR_BF16: np.uint16, TENSOR_F32: np.float32}[self.info.tensor_dtype]
+        return {TENSOR_F16: np.float16, TENSOR_BF16: np.uint16, TENSOR_F32: np.float32, TENSOR_U8: np.uint8}[self.info.tensor_dtype]
+
+    def _tensor_dims(self):
+        """(shape, strides in bytes) of one tensor in the pipeline's layout: [3, H, W] or [H, W, 3]"""
+        t = self.tensor_shape
+        e = t.element_bytes
+        if t.layout == TENSOR_LAYOUT_HWC:
+            return (t.height, t.width, t.channels), (t.stride_y * e, t.stride_x * e, t.stride_c * e)
+        return (t.channels, t.height, t.width), (t.stride_c * e, t.stride_y * e, t.stride_x * e)
 
     def read_tensor(self, frame):
-        """the frame's tensor as a host array [3, height, width] (tensor_geometry: the frame's size, or tensor_size): float16 / float32,
-        bfloat16 as uint16 bit patterns"""
+        """the frame's tensor as a host array [3, height, width] ([height, width, 3] with tensor_layout "hwc"; tensor_geometry: the
+        frame's size, or tensor_size): float16 / float32 / uint8, bfloat16 as uint16 bit patterns"""
         if not frame.get("tensor"):
             raise LeonError(ERR_INVALID, "the frame has no tensor (Pipeline output)")
-        out = np.empty((3, self.tensor_geometry.height, self.tensor_geometry.width), dtype=self._tensor_np_dtype())
+        out = np.empty(self._tensor_dims()[0], dtype=self._tensor_np_dtype())
         _chk(self.lib.leon_pipeline_read_tensor(self.h, frame["_window"], frame["_i"], out.ctypes.data))
         return out
 
@@ -717,32 +767,32 @@ class Pipeline:
         class _View:
             pass
         v = _View()
-        v.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4" if dt == TENSOR_F32 else ("<f2" if dt == TENSOR_F16 else "<i2"),
+        v.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": {TENSOR_F32: "<f4", TENSOR_F16: "<f2", TENSOR_BF16: "<i2", TENSOR_U8: "|u1"}[dt],
                                       "data": (int(ptr), False), "strides": tuple(int(x) for x in strides), "version": 2}
         t = torch.as_tensor(v, device="cuda:%d" % (self.device_id if device_id is None else device_id))
         return t.view(torch.bfloat16) if dt == TENSOR_BF16 else t
 
     def tensor_view(self, frame, device_id=None):
-        """the frame's tensor where it lies, as a torch [3, H, W] tensor of the pipeline's element type, without copying: valid until
-        the frame's window is released"""
+        """the frame's tensor where it lies, as a torch [3, H, W] ("hwc": [H, W, 3]) tensor of the pipeline's element type, without
+        copying: valid until the frame's window is released"""
         if not frame.get("tensor"):
             raise ValueError("the frame has no tensor (Pipeline output)")
-        i = self.info
-        e, h, w = i.tensor_element_bytes, self.tensor_geometry.height, self.tensor_geometry.width
-        return self._tensor_at(frame["tensor"], (3, h, w), (h * w * e, w * e, e), device_id)
+        shape, strides = self._tensor_dims()
+        return self._tensor_at(frame["tensor"], shape, strides, device_id)
 
     def window_tensor(self, frames, device_id=None):
-        """frames of one window (in order) as ONE strided torch view [N, 3, H, W] when their tensors are evenly spaced in the
+        """frames of one window (in order) as ONE strided torch view [N, 3, H, W] ("hwc": [N, H, W, 3]) when their tensors are evenly spaced in the
         ring -- consecutive display positions of a GOP are tensor_frame_pitch apart --, else None"""
         ptrs = [f.get("tensor") for f in frames]
         if not ptrs or not all(ptrs):
             return None
         step = ptrs[1] - ptrs[0] if len(ptrs) > 1 else self.info.tensor_frame_pitch
         i = self.info
-        e, h, w = i.tensor_element_bytes, self.tensor_geometry.height, self.tensor_geometry.width
+        e = i.tensor_element_bytes
         if step <= 0 or step % e or step < i.tensor_frame_bytes or any(b - a != step for a, b in zip(ptrs, ptrs[1:])):
             return None
-        return self._tensor_at(ptrs[0], (len(ptrs), 3, h, w), (step, h * w * e, w * e, e), device_id)
+        shape, strides = self._tensor_dims()
+        return self._tensor_at(ptrs[0], (len(ptrs),) + shape, (step,) + strides, device_id)
 
     def plane_views(self, frame, device_id=None):
         """the frame's planes where they lie, as torch uint8 tensors (height x width, row stride = the plane's padded stride),

@@ -387,6 +387,7 @@ struct PipeHandle {
     std::map<int64_t, std::vector<leon_pipeline_frame>> out;   // delivered, not yet released
     leon_pipeline_info info{};
     leon_pipeline_tensor_geometry tensor_geom{};      // all 0 without tensor output
+    leon_pipeline_tensor_shape tensor_shape{};        // the same
     int64_t last_window = -1;               // notify thread, under mu
     int64_t floor = 0;                      // JavaScript thread: the first window of the latest seek
     bool seeked = false;
@@ -560,8 +561,9 @@ napi_value PipeReadPlanes(napi_env env, napi_callback_info info)
     return rc == LEON_OK ? o : throw_leon(env, rc);
 }
 
-// p.readTensor(window, i) -> Uint16Array (fp16 / bf16 bit patterns) or Float32Array, [3][tensorHeight][tensorWidth] packed (the frame's
-// size, or opts.tensorSize): one frame's tensor (output 'tensor' ...)
+// p.readTensor(window, i) -> Uint16Array (fp16 / bf16 bit patterns), Float32Array or Uint8Array (tensorDtype 'uint8'),
+// [3][tensorHeight][tensorWidth] packed (the frame's size, or opts.tensorSize; [tensorHeight][tensorWidth][3] with tensorLayout 'hwc'):
+// one frame's tensor (output 'tensor' ...)
 napi_value PipeReadTensor(napi_env env, napi_callback_info info)
 {
     size_t argc = 2;
@@ -582,7 +584,7 @@ napi_value PipeReadTensor(napi_env env, napi_callback_info info)
     napi_value ab, ta;
     void* data = nullptr;
     NAPI_OK(napi_create_arraybuffer(env, bytes, &data, &ab));
-    NAPI_OK(napi_create_typedarray(env, eb == 4 ? napi_float32_array : napi_uint16_array, bytes / eb, ab, 0, &ta));
+    NAPI_OK(napi_create_typedarray(env, eb == 4 ? napi_float32_array : (eb == 1 ? napi_uint8_array : napi_uint16_array), bytes / eb, ab, 0, &ta));
     int rc = leon_pipeline_read_tensor(h->p, w, i, data);
     return rc == LEON_OK ? ta : throw_leon(env, rc);
 }
@@ -629,6 +631,10 @@ napi_value PipeStats(napi_env env, napi_callback_info info)
     for (auto& e : kv) {
         NAPI_OK(napi_create_double(env, e.val, &v));
         NAPI_OK(napi_set_named_property(env, o, e.k, v));
+    }
+    if (h->info.tensor_dtype) {          // the tensors' layout by its option name
+        NAPI_OK(napi_create_string_utf8(env, h->tensor_shape.layout == LEON_TENSOR_LAYOUT_HWC ? "hwc" : "chw", NAPI_AUTO_LENGTH, &v));
+        NAPI_OK(napi_set_named_property(env, o, "tensorLayout", v));
     }
     return o;
 }
@@ -743,8 +749,15 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
         napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
         return nullptr;
     }
+    // ... and their layout (leon_pipeline_tensor_format; js/leon_pipeline.js maps 'chw' / 'hwc' to LEON_TENSOR_LAYOUT_*)
+    leon_pipeline_tensor_format fcfg;
+    memset(&fcfg, 0, sizeof fcfg);
+    if (!get_i32(env, argv[1], "tensorLayout", &fcfg.layout, 0)) {
+        napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
+        return nullptr;
+    }
     const bool resized = (rcfg.out_width | rcfg.out_height | rcfg.crop_x | rcfg.crop_y | rcfg.crop_width | rcfg.crop_height) != 0;
-    const bool tensor = (cfg.output & LEON_PIPELINE_OUTPUT_TENSOR) != 0 || tcfg.dtype != 0 || resized;
+    const bool tensor = (cfg.output & LEON_PIPELINE_OUTPUT_TENSOR) != 0 || tcfg.dtype != 0 || resized || fcfg.layout != 0;
     PipeHandle* h = new PipeHandle();
     napi_value name;
     NAPI_OK(napi_create_string_utf8(env, "leon pipeline frames", NAPI_AUTO_LENGTH, &name));
@@ -776,7 +789,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
             }
         }
     }
-    int rc = tensor ? leon_pipeline_create_tensor_resized(&cfg, &tcfg, resized ? &rcfg : nullptr, (const uint8_t*)data, len, partial ? (size_t)valid : len, pipe_native_cb, h, &h->p)
+    int rc = tensor ? leon_pipeline_create_tensor_format(&cfg, &tcfg, resized ? &rcfg : nullptr, fcfg.layout ? &fcfg : nullptr, (const uint8_t*)data, len, partial ? (size_t)valid : len, pipe_native_cb, h, &h->p)
            : partial ? leon_pipeline_create_partial(&cfg, (const uint8_t*)data, len, (size_t)valid, pipe_native_cb, h, &h->p)
                      : leon_pipeline_create(&cfg, (const uint8_t*)data, len, pipe_native_cb, h, &h->p);
     if (rc != LEON_OK) {
@@ -786,7 +799,10 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
         return throw_leon(env, rc);
     }
     leon_pipeline_get_info(h->p, &h->info);
-    if (h->info.tensor_dtype) leon_pipeline_get_tensor_geometry(h->p, &h->tensor_geom);
+    if (h->info.tensor_dtype) {
+        leon_pipeline_get_tensor_geometry(h->p, &h->tensor_geom);
+        leon_pipeline_get_tensor_shape(h->p, &h->tensor_shape);
+    }
     napi_value obj;
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));

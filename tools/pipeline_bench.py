@@ -31,7 +31,8 @@ def main():
     ap.add_argument("--gpu-parser", action="store_true", help="decode the slice layer on the GPU (leon_pipeline_config.gpu_parser)")
     ap.add_argument("--output", choices=["rgba", "ycbcr", "both", "tensor", "rgba+tensor", "ycbcr+tensor", "all"], default="rgba",
                     help="what the frames carry (leon_pipeline_config.output): RGBA, the YCbCr planes, planar float tensors, or a combination")
-    ap.add_argument("--tensor-dtype", choices=["float16", "bfloat16", "float32"], default="float16", help="element type of --output tensor")
+    ap.add_argument("--tensor-dtype", choices=["float16", "bfloat16", "float32", "uint8"], default="float16", help="element type of --output tensor")
+    ap.add_argument("--tensor-layout", choices=["chw", "hwc"], default="chw", help="planar [3, H, W] or channels-last [H, W, 3] tensors (leon_pipeline_tensor_format)")
     ap.add_argument("--tensor-size", type=int, nargs=2, metavar=("H", "W"), help="tensors resampled on the device to H x W (leon_pipeline_tensor_resize)")
     ap.add_argument("--tensor-crop", type=int, nargs=4, metavar=("X", "Y", "W", "H"), help="the crop box --tensor-size resamples (frame pixels; default: the whole frame)")
     ap.add_argument("--host-resize", type=int, nargs=2, metavar=("H", "W"),
@@ -78,7 +79,8 @@ def main():
     free0 = free_device_bytes()
     t0 = time.perf_counter()
     pipe = L.Pipeline(data, parser_threads=a.threads, gops_per_window=a.window, windows_in_flight=a.inflight, loop=a.loop, gpu_parser=a.gpu_parser,
-                      output=a.output, tensor_dtype=a.tensor_dtype, tensor_size=a.tensor_size, tensor_crop=a.tensor_crop, on_window=on_window)
+                      output=a.output, tensor_dtype=a.tensor_dtype, tensor_size=a.tensor_size, tensor_crop=a.tensor_crop, tensor_layout=a.tensor_layout,
+                      on_window=on_window)
     free1 = free_device_bytes()
     pool = L.pool_stats()
     pipe.wait()
@@ -90,7 +92,7 @@ def main():
         "metric": "end-to-end %dx%d pictures/s (parse + PCIe + reconstruct + %s in device memory), native pipeline, one GPU"
                   % (pipe.info.frame_width, pipe.info.frame_height, {"rgba": "RGBA", "ycbcr": "YCbCr planes", "both": "RGBA + YCbCr planes", "tensor": "tensors", "rgba+tensor": "RGBA + tensors",
                      "ycbcr+tensor": "YCbCr planes + tensors", "all": "RGBA + YCbCr planes + tensors"}[a.output]),
-        "output": a.output, "tensor_dtype": a.tensor_dtype if pipe.info.tensor_dtype else None,
+        "output": a.output, "tensor_dtype": a.tensor_dtype if pipe.info.tensor_dtype else None, "tensor_layout": a.tensor_layout if pipe.info.tensor_dtype else None,
         "tensor_frame_bytes": pipe.info.tensor_frame_bytes, "tensor_size": a.tensor_size, "tensor_crop": a.tensor_crop, "host_resize": a.host_resize, "windows_in_flight": a.inflight,
         "value": s["pictures"] / s["seconds"], "macroblocks_per_s": s["pictures"] * mbs / s["seconds"],
         "pictures": s["pictures"], "seconds": s["seconds"], "wall_seconds_incl_setup": wall, "windows": s["windows"],
