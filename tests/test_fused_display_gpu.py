@@ -59,6 +59,32 @@ def test_fused_gop_equals_oracle(L, O, S, size, sparse):
     gop = S.gop_ibbp(9 if cw < 1000 else 6)
     rng = np.random.default_rng(cw * 7 + sparse)
     tens = _gop(S, rng, cw, ch, gop, in_picture=cw < 1000)        # small sizes: vectors may leave the picture
+    _check_fused_gop(L, O, S, size, sparse, gop, tens)
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=["dense", "sparse"])
+@pytest.mark.parametrize("case", ["f_code7_48x32", "full_pel_f_code7_176x144"])
+def test_fused_gop_with_the_vectors_of_f_code_7_and_full_pel(L, O, S, case, sparse):
+    """the fused display kernels (B pictures write no planes) at the vectors forward_f_code 7 reaches, +-1023 half-pel at
+    48x32, and full_pel on top of it, even vectors to +-2046 at 176x144: the random cases of tests/test_parity_gpu.py
+    (test_ibbp_vectors_of_f_code_7, test_ibbp_vectors_of_full_pel_f_code_7) on this road"""
+    cw, ch, n, twice = (48, 32, 9, False) if case == "f_code7_48x32" else (176, 144, 6, True)
+    gop = S.gop_ibbp(n)
+    rng = np.random.default_rng(cw * 7 + sparse)
+    tens = _gop(S, rng, cw, ch, gop, in_picture=False, mv_range=1023)
+    if twice:
+        for t in tens.values():
+            for k in ("mv_fwd", "mv_bwd"):
+                if k in t:
+                    t[k] = (t[k].astype(np.int32) * 2).astype(np.int16)
+    assert max(int(np.abs(t["mv_fwd"]).max()) for t in tens.values() if "mv_fwd" in t) > (1900 if twice else 950)
+    _check_fused_gop(L, O, S, (cw, ch, cw, ch), sparse, gop, tens)
+
+
+def _check_fused_gop(L, O, S, size, sparse, gop, tens):
+    import torch
+    import leon_vlc_ctypes as V
+    cw, ch, fw, fh = size
     exp = _decode_oracle(O, cw, ch, gop, tens)
     n = len(gop)
     dec = L.Decoder(cw, ch, fw, fh, n_slots=n + 1)

@@ -133,6 +133,50 @@ def test_all_half_pel_phases_and_edges(L, O, S):
     _run_sequence(L, O, cw, ch, pics, n_slots=slot, refs={0: ref})
 
 
+def test_ibbp_vectors_of_f_code_7(L, O, S):
+    """+-1023 half-pel, the range of forward_f_code 7: every window lies far outside a 48x32 picture or straddles its
+    edge (the clamped fetch: fetch_rows, gather9_slow, ref_px_clamped and the r1 row rule of leon_kernels.h)"""
+    rng = np.random.default_rng(41)
+    _run_sequence(L, O, 48, 32, _chain(S, rng, 48, 32, S.gop_ibbp(9), in_picture=False, mv_range=1023), n_slots=13)
+
+
+def test_ibbp_vectors_of_full_pel_f_code_7(L, O, S):
+    """even vectors up to +-2046 half-pel: full_pel with f_code 7 (and within it f_code 6: +-1022)"""
+    rng = np.random.default_rng(42)
+    pics = _chain(S, rng, 176, 144, S.gop_ibbp(6), in_picture=False, mv_range=1023)
+    for t in pics:
+        for k in ("mv_fwd", "mv_bwd"):
+            if k in t:
+                t[k] = (t[k].astype(np.int32) * 2).astype(np.int16)
+    assert max(int(np.abs(t["mv_fwd"]).max()) for t in pics if "mv_fwd" in t) > 1900
+    _run_sequence(L, O, 176, 144, pics, n_slots=13)
+
+
+def test_vectors_at_and_beyond_the_picture_size(L, O, S):
+    """One vector for all macroblocks, zero residual: the vector just inside, at and just beyond the picture's width
+    (height) in half-pel, and the ends of the ranges of f_code 7 without and with full_pel -- horizontally, vertically
+    and both at once, in P pictures and in bidirectional B pictures."""
+    cw, ch = 64, 48
+    mbw, mbh = 4, 3
+    rng = np.random.default_rng(43)
+    refs = {0: rng.integers(0, 256, size=cw * ch * 3 // 2).astype(np.uint8),
+            1: rng.integers(0, 256, size=cw * ch * 3 // 2).astype(np.uint8)}
+    ends = lambda n: [2 * n - 1, -(2 * n - 1), 2 * n, -2 * n, 2 * n + 1, -(2 * n + 1), 1023, -1023, 2046, -2046, -2048]
+    hs, vs = ends(cw), ends(ch)
+    vectors = [(h, 0) for h in hs] + [(0, v) for v in vs] + list(zip(hs, vs))
+    zeros = lambda: {"coef_y": np.zeros((ch, cw), np.int16), "coef_cb": np.zeros((ch // 2, cw // 2), np.int16),
+                     "coef_cr": np.zeros((ch // 2, cw // 2), np.int16), "qscale": np.full(mbw * mbh, 8, np.uint8),
+                     "intra": np.zeros(mbw * mbh, np.uint8), "repadd": np.zeros(mbw * mbh, np.uint8)}
+    pics, slot = [], 2
+    for i, (h, v) in enumerate(vectors):
+        pics.append(dict(zeros(), type=2, slot=slot, ref_fwd=0, ref_bwd=None, mv_fwd=np.tile(np.array([h, v], np.int16), mbw * mbh)))
+        bh, bv = vectors[-1 - i]                                # the backward vector: another of the set
+        pics.append(dict(zeros(), type=3, slot=slot + 1, ref_fwd=0, ref_bwd=1, mb_dir=np.full(mbw * mbh, 3, np.uint8),
+                         mv_fwd=np.tile(np.array([h, v], np.int16), mbw * mbh), mv_bwd=np.tile(np.array([bh, bv], np.int16), mbw * mbh)))
+        slot += 2
+    _run_sequence(L, O, cw, ch, pics, n_slots=slot, refs=refs)
+
+
 def test_custom_quant_matrices_and_zero_quirk(L, O, S):
     """Small custom matrix entries reach floor(.)==0 -> +1 (mpeg1video.js:22)."""
     rng = np.random.default_rng(6)

@@ -21,7 +21,11 @@ from helpers import ROOT, load_golden
 import leon_vlc_ctypes as V
 
 STREAMS = os.path.join(ROOT, "tests", "golden", "streams")
-NAMES = ["tiny_ip_32x32", "leon_synth_352x240", "ibbp_96x64", "slices5_ip_96x64"]
+NAMES = ["tiny_ip_32x32", "leon_synth_352x240", "ibbp_96x64", "slices5_ip_96x64",
+         # tools/syntax_streams.py FIXTURES: f_code 1, 5 + full_pel, 7, stuffing, address escapes, long escapes, dct_dc_size 8
+         "syntax_f1_ip_96x64", "syntax_f5_fullpel_ip_96x64", "syntax_f7_one_slice_ip_96x64", "syntax_escape_ip_592x32",
+         # ... and X.QUIRK_CASES: slices whose last macroblock the reference never reads (tests/test_vlc_syntax.py)
+         "syntax_lastmb_ip_96x64"]
 sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 

@@ -115,10 +115,28 @@ class BitWriter:
         return len(self.buf)
 
 
-def _put_mba(bw, incr):
+def new_stats():
+    """Counters of what a stream was written with (write_stream(stats=...) fills them in): the tests that exist for one
+    syntax element assert from these that the element is in the stream they parse."""
+    return {"stuffing": 0, "mba_escape": 0, "p_skips": 0, "b_skips": 0, "extra_slice_bytes": 0,
+            "escape_short": 0, "escape_long_pos": 0, "escape_long_neg": 0, "escape_run_gt31": 0, "codes_ge12": 0,
+            "dc_size_lum": [0] * 9, "dc_size_chr": [0] * 9, "quant_changes": {PIC_I: 0, PIC_P: 0, PIC_B: 0},
+            "wrapped": 0, "wrapped_by_code": {}, "f_codes": set(), "kept_last_mb": 0, "kept_last_mb_by_type": {PIC_P: 0, PIC_B: 0}}
+
+
+_NO_STATS = new_stats()      # where the counts of a caller that wants none go
+
+
+def _put_mba(bw, incr, stuffing=0, stats=None):
+    for _ in range(stuffing):
+        bw.vlc(MBA_STUFFING)
+    if stats is not None:
+        stats["stuffing"] += stuffing
     while incr > 33:
         bw.vlc(MBA_ESCAPE)
         incr -= 33
+        if stats is not None:
+            stats["mba_escape"] += 1
     bw.vlc(MBA[incr - 1])
 
 
@@ -136,6 +154,13 @@ def _put_motion(bw, delta, f_code):
         bw.put(resid, f_code - 1)
 
 
+def _motion_bits(delta, f_code):
+    """length of what _put_motion writes"""
+    if delta == 0:
+        return 1
+    return MOTION[(abs(delta) + (1 << (f_code - 1)) - 1) >> (f_code - 1)][1] + 1 + (f_code - 1)
+
+
 def _wrap(delta, f_code):
     r = 16 << (f_code - 1)
     if delta < -r:
@@ -145,14 +170,16 @@ def _wrap(delta, f_code):
     return delta
 
 
-def _put_block(bw, levels_zz, intra, is_chroma, dc_pred):
+def _put_block(bw, levels_zz, intra, is_chroma, dc_pred, stats=None):
     """levels_zz: 64 levels in zig-zag scan order.  Returns the new DC predictor (intra)."""
+    st = stats if stats is not None else _NO_STATS
     start = 0
     if intra:
         dc = int(levels_zz[0])
         diff = dc - dc_pred
         size = 0 if diff == 0 else abs(diff).bit_length()
         bw.vlc((DC_CHR if is_chroma else DC_LUM)[size])
+        st["dc_size_chr" if is_chroma else "dc_size_lum"][size] += 1
         if size:
             bw.put(diff if diff > 0 else diff + (1 << size) - 1, size)
         dc_pred = dc
@@ -170,17 +197,22 @@ def _put_block(bw, levels_zz, intra, is_chroma, dc_pred):
         elif (run, a) in COEF:
             bw.vlc(COEF[(run, a)])
             bw.put(1 if lv < 0 else 0, 1)
+            st["codes_ge12"] += COEF[(run, a)][1] >= 12
         else:
             bw.vlc(COEF_ESCAPE)
             bw.put(run, 6)
+            st["escape_run_gt31"] += run > 31
             if -127 <= lv <= 127:
                 bw.put(lv & 0xff, 8)
+                st["escape_short"] += 1
             elif lv > 0:
                 bw.put(0x00, 8)
                 bw.put(lv, 8)                              # 128..255
+                st["escape_long_pos"] += 1
             else:
                 bw.put(0x80, 8)
                 bw.put(lv + 256, 8)                        # -255..-128
+                st["escape_long_neg"] += 1
         first = False
         run = 0
     bw.vlc(COEF_EOB)
@@ -203,9 +235,25 @@ def _mb_blocks(t, mbx, mby):
     return out
 
 
-def write_picture(bw, t, cw, ch, temporal_ref, f_code=(2, 2), full_pel=(0, 0), slice_mbs=None):
+def write_picture(bw, t, cw, ch, temporal_ref, f_code=(2, 2), full_pel=(0, 0), slice_mbs=None, stuffing=None,
+                  extra_slice=None, b_skip=False, keep_last_mb=False, stats=None):
     """One picture.  slice_mbs None: one slice per macroblock row; else a new slice every slice_mbs
     macroblocks in raster order (slices then start mid-row and may span rows, as MPEG-1 allows).
+    t["f_code"] / t["full_pel"] (pairs forward, backward), when present, are this picture's instead of the arguments.
+    A full_pel vector is written as its half (the tensors carry half-pel units, so it has to be even).
+    stuffing / extra_slice: numpy Generators (or None) -- 0..3 macroblock_stuffing codes in front of every
+    macroblock_address_increment, the first of a slice included; 1..2 bytes of extra_information_slice in every slice.
+    stats: a new_stats() dict that counts what is written.
+    keep_last_mb: the reference ends a slice when the bytes from the next byte boundary on are a start code
+    (nextBytesAreStartCode, decoders/jsv.js:1710-1760, called after every macroblock) -- not, as 11172-2 has it, when the
+    next 23 BITS are zero.  A last macroblock of a slice that fits into what is left of the byte its predecessor ended in
+    (vectors only: 6 bits in P, 7 in B) is therefore never read.  With this option one macroblock_stuffing code goes in
+    front of such a macroblock, which carries it over the byte boundary; without it the stream is written as before.
+
+    b_skip, B pictures: a macroblock is skipped when it is non-intra, carries no coefficients (and no alpha blocks), has the
+    direction and both vectors of the macroblock before it, that one being non-intra and itself either coded or skipped
+    the same way (so all of a run repeats the last coded macroblock), and is neither first nor last of its slice.  As
+    in P pictures a skip resets the DC predictors; the motion predictors stay (ISO/IEC 11172-2 2.4.4.3).
 
     yuva ("coef_a" in t; container flag `a`, decoders/jsv.js:256-259).  The reference defines no syntax
     for the fourth component (its slice loop reads six blocks, jsv.js:817-828), so this is the repo's:
@@ -217,6 +265,25 @@ def write_picture(bw, t, cw, ch, temporal_ref, f_code=(2, 2), full_pel=(0, 0), s
     ptype = t["type"]
     alpha = "coef_a" in t
     mbw, mbh = cw // 16, ch // 16
+    f_code = tuple(t.get("f_code", f_code))
+    full_pel = tuple(t.get("full_pel", full_pel))
+    st = stats if stats is not None else _NO_STATS
+    if ptype != PIC_I:
+        st["f_codes"].add((f_code[0], full_pel[0]))
+    if ptype == PIC_B:
+        st["f_codes"].add((f_code[1], full_pel[1]))
+
+    def put_vector(mv, pmv, fc, fp):
+        for k in range(2):
+            assert not (fp and mv[k] & 1), "a full_pel vector is even in half-pel units"
+            v = mv[k] >> 1 if fp else mv[k]
+            assert -(16 << (fc - 1)) <= v <= (16 << (fc - 1)) - 1, (v, fc)
+            d = _wrap(v - pmv[k], fc)
+            if d != v - pmv[k]:                          # counted per (f_code, full_pel) too: every code has its own bound
+                st["wrapped"] += 1
+                st["wrapped_by_code"][(fc, fp)] = st["wrapped_by_code"].get((fc, fp), 0) + 1
+            _put_motion(bw, d, fc)
+            pmv[k] = v
     bw.start_code(START_PICTURE)
     bw.put(temporal_ref & 1023, 10)
     bw.put(ptype, 3)
@@ -237,12 +304,18 @@ def write_picture(bw, t, cw, ch, temporal_ref, f_code=(2, 2), full_pel=(0, 0), s
         if qcur < 1:
             qcur = 1
         bw.put(qcur, 5)
+        if extra_slice is not None:
+            for _ in range(int(extra_slice.integers(1, 3))):
+                bw.put(1, 1)                               # extra_bit_slice + extra_information_slice
+                bw.put(int(extra_slice.integers(0, 256)), 8)
+                st["extra_slice_bytes"] += 1
         bw.put(0, 1)                                       # extra_bit_slice
         dc_pred = [128, 128, 128, 128]
         pmv_f = [0, 0]
         pmv_b = [0, 0]
         last_coded = first - (first % mbw) - 1            # the slice's address origin: row start - 1
         prev_intra = False
+        prev_b = None                                      # B: (direction, vectors) of the macroblock before, None = intra / slice start
         for mb in range(first, last + 1):
             mbx, mby = mb % mbw, mb // mbw
             intra = bool(t["intra"][mb])
@@ -264,7 +337,13 @@ def write_picture(bw, t, cw, ch, temporal_ref, f_code=(2, 2), full_pel=(0, 0), s
             # a P macroblock without coefficients and with a zero vector may be skipped, but never
             # the first or last one of a slice
             if ptype == PIC_P and not intra and cbp == 0 and apat == 0 and mvf == [0, 0] and first < mb < last:
+                st["p_skips"] += 1
                 continue
+            if ptype == PIC_B:
+                if b_skip and not intra and cbp == 0 and apat == 0 and prev_b == (d, mvf, mvb) and first < mb < last:
+                    st["b_skips"] += 1
+                    continue
+                prev_b = None if intra else (d, mvf, mvb)
             flags = 0
             if intra:
                 flags = 0x01
@@ -290,11 +369,23 @@ def write_picture(bw, t, cw, ch, temporal_ref, f_code=(2, 2), full_pel=(0, 0), s
                 pmv_f = [0, 0]                             # skipped P macroblocks reset the predictor
             if skipped and mb != first:
                 dc_pred = [128, 128, 128, 128]
-            _put_mba(bw, skipped + 1)
+            n_stuff = 0 if stuffing is None else int(stuffing.integers(0, 4))
+            if keep_last_mb and mb == last and mb != first and not (intra or cbp or apat or n_stuff) and bw.n and skipped < 33:
+                nbits = MBA[skipped][1] + types[flags][1] + (4 if alpha else 0)
+                for on, mv, pmv, fc, fp in ((flags & 0x08, mvf, pmv_f, f_code[0], full_pel[0]),
+                                            (flags & 0x04, mvb, pmv_b, f_code[1], full_pel[1])):
+                    for k in range(2 if on else 0):
+                        nbits += _motion_bits(_wrap((mv[k] >> 1 if fp else mv[k]) - pmv[k], fc), fc)
+                if bw.n + nbits <= 8:
+                    n_stuff = 1
+                    st["kept_last_mb"] += 1
+                    st["kept_last_mb_by_type"][ptype] += 1
+            _put_mba(bw, skipped + 1, n_stuff, st)
             bw.vlc(types[flags])
             if flags & 0x10:
                 bw.put(q, 5)
                 qcur = q
+                st["quant_changes"][ptype] += 1
             if not intra and (prev_intra or True):
                 dc_pred = [128, 128, 128, 128]             # a non-intra macroblock resets the DC predictors
             if ptype == PIC_P and not intra and not (flags & 0x08):
@@ -304,15 +395,9 @@ def write_picture(bw, t, cw, ch, temporal_ref, f_code=(2, 2), full_pel=(0, 0), s
                 pmv_f = [0, 0]
                 pmv_b = [0, 0]
             if flags & 0x08:
-                for k in range(2):
-                    v = mvf[k] >> 1 if full_pel[0] else mvf[k]
-                    _put_motion(bw, _wrap(v - pmv_f[k], f_code[0]), f_code[0])
-                    pmv_f[k] = v
+                put_vector(mvf, pmv_f, f_code[0], full_pel[0])
             if flags & 0x04:
-                for k in range(2):
-                    v = mvb[k] >> 1 if full_pel[1] else mvb[k]
-                    _put_motion(bw, _wrap(v - pmv_b[k], f_code[1]), f_code[1])
-                    pmv_b[k] = v
+                put_vector(mvb, pmv_b, f_code[1], full_pel[1])
             if (flags & 0x02) and not intra:
                 bw.vlc(CBP[cbp])
             if alpha and not intra:
@@ -320,21 +405,28 @@ def write_picture(bw, t, cw, ch, temporal_ref, f_code=(2, 2), full_pel=(0, 0), s
             for b in range(6):
                 if cbp & (1 << (5 - b)):
                     comp = 0 if b < 4 else b - 3
-                    dc_pred[comp] = _put_block(bw, blocks[b], intra, b >= 4, dc_pred[comp])
+                    dc_pred[comp] = _put_block(bw, blocks[b], intra, b >= 4, dc_pred[comp], st)
             for b in range(4):
                 if apat & (1 << (3 - b)):
-                    dc_pred[3] = _put_block(bw, blocks[6 + b], intra, False, dc_pred[3])
+                    dc_pred[3] = _put_block(bw, blocks[6 + b], intra, False, dc_pred[3], st)
             last_coded = mb
             prev_intra = intra
 
 
 def write_stream(pictures, cw, ch, frame_w=None, frame_h=None, rate_idx=3, gop_starts=None,
-                 qm_intra=None, qm_non_intra=None, key_map=True, f_code=(2, 2), slice_mbs=None, alpha=None, gop_qm=None):
+                 qm_intra=None, qm_non_intra=None, key_map=True, f_code=(2, 2), slice_mbs=None, alpha=None, gop_qm=None,
+                 full_pel=(0, 0), stuffing=None, extra_slice=None, b_skip=False, keep_last_mb=False, stats=None):
     """pictures: tensors dicts in CODED order, each with 'display' (temporal reference inside
     its GOP).  gop_starts: indices into `pictures` where a sequence header + GOP header go.
     gop_qm: {index into `pictures`: (qm_intra, qm_non_intra)} -- matrices of that GOP's own sequence header
     instead of the stream's (a sequence header may reload them, decoders/jsv.js:540-558).
-    Returns bytes."""
+    f_code / full_pel: (forward, backward) of every picture that has no "f_code" / "full_pel" key of its own.
+    stuffing / extra_slice: a seed each (None: off) for macroblock_stuffing codes and extra_information_slice bytes,
+    see write_picture.  b_skip: skip the B macroblocks that may be skipped (off: every B macroblock is coded, as the
+    streams written before this option are).  keep_last_mb: see write_picture.  stats: a new_stats() dict to count into.
+    Returns (bytes, key-map offsets)."""
+    stuffing = None if stuffing is None else np.random.default_rng(stuffing)
+    extra_slice = None if extra_slice is None else np.random.default_rng(extra_slice)
     frame_w, frame_h = frame_w or cw, frame_h or ch
     gop_starts = sorted(set(gop_starts or [0]))
     body = BitWriter()
@@ -371,7 +463,8 @@ def write_stream(pictures, cw, ch, frame_w=None, frame_h=None, rate_idx=3, gop_s
             body.put(int(frame_no - sec * rate) & 63, 6)
             body.put(1, 1)                                 # closed_gop
             body.put(0, 1)                                 # broken_link
-        write_picture(body, t, cw, ch, t.get("display", 0), f_code=f_code, slice_mbs=slice_mbs)
+        write_picture(body, t, cw, ch, t.get("display", 0), f_code=f_code, full_pel=full_pel, slice_mbs=slice_mbs,
+                      stuffing=stuffing, extra_slice=extra_slice, b_skip=b_skip, keep_last_mb=keep_last_mb, stats=stats)
         frame_no += 1
     body.start_code(START_END)
     body.buf += bytes(8)                                   # tail so the last start-code scan terminates

@@ -45,3 +45,13 @@ if __name__ == "__main__":
     build("custom_intra_ip_48x32", 48, 32, 48, 32, [S.gop_ippp(4)], 99, qm_intra=CUSTOM_INTRA.reshape(8, 8))
     # yuva: container flag `a` + four alpha blocks per macroblock (the repo's syntax, tools/jsv_writer.py); product parsers only
     build("yuva_ibbp_96x64", 96, 64, 96, 64, [S.gop_ibbp(9), S.gop_ippp(4)], 404, alpha=True)
+    # the rest of the slice-layer syntax (f_code 1 .. 7, full_pel, stuffing, address escapes, long escapes, dct_dc_size 8,
+    # extra_information_slice), I + P only so that the reference parser reads every picture: tools/syntax_streams.py
+    import syntax_streams as X
+    # ... and one stream written WITHOUT the writer's guard for a slice's last macroblock (X.QUIRK_CASES): what the reference
+    # reads from it pins its byte-granular end-of-slice test
+    for case in X.FIXTURES + list(X.QUIRK_CASES):
+        pics, data, stats = X.build_case(X.CASES.get(case) or X.QUIRK_CASES[case])
+        with open(os.path.join(ROOT, "tests", "golden", "streams", X.fixture_name(case) + ".jsv"), "wb") as f:
+            f.write(data)
+        print(X.fixture_name(case), len(data), "bytes,", len(pics), "pictures")
