@@ -158,15 +158,26 @@ typedef struct leon_pipeline_tensor_config {
  * with rgb = the bytes an RGBA pipeline with LEON_RGB_CPU_TWIN delivers (the row of 255 in the last row of an odd frame height
  * included).  Taps may reach outside the crop box, never outside the frame.  This is the arithmetic of an 8-bit antialiased
  * triangle ("bilinear") resize: a triangle filter widened by the ratio when reducing, plain bilinear when enlarging.
+ * filter = LEON_RESIZE_BICUBIC is the same definition with another filter function f and support S (triangle: f(x) = max(0, 1 - |x|),
+ * S = 1) -- the 8-bit bicubic resize of the published CLIP / SigLIP / DINOv2 preprocessing:
+ *         support = S * fscale; w[k] = f((first + k - center + 0.5) / fscale); w[k] /= sum(w)
+ *         W[o][k] = w[k] < 0 ? (int)(-0.5 + w[k] * 2^P) : (int)(0.5 + w[k] * 2^P)
+ *         bicubic: a = -0.5, S = 2;  f(x) = ((a + 2)|x| - (a + 3)) x^2 + 1           for |x| < 1
+ *                                         = (((|x| - 5)|x| + 8)|x| - 4) a             for 1 <= |x| < 2,   0 otherwise
+ *     h and r = clamp((2^(P-1) + sum) >> P, 0, 255) with an arithmetic shift (floor): weights are negative too, so the sums overshoot on
+ *     both sides.  count <= LEON_RESIZE_MAX_TAPS_BICUBIC.  Per row of a table 2^(P-1) + 255 * (sum of the positive W) and 255 * (sum of
+ *     |negative W|) stay below 2^31 and every |W| below 2^23 (checked when the tables are built; with these filters it always holds).
  * All fields zero (or no struct) = the full-size tensor above; a crop box of all zeros = the whole frame.  Refused at create:
  * out_width / out_height outside 1 .. 4096, an empty crop box or one that leaves the frame, crop / out > 16 on an axis, another
- * filter, resize settings without the TENSOR bit. */
+ * filter (1, 2 and everything above 3), resize settings without the TENSOR bit. */
 #define LEON_RESIZE_TRIANGLE 0
-#define LEON_RESIZE_MAX_TAPS 33      /* count <= 2 * 16 + 1 */
+#define LEON_RESIZE_BICUBIC 3                /* (the number image libraries give this filter) */
+#define LEON_RESIZE_MAX_TAPS 33              /* triangle: count <= 2 * 16 + 1 */
+#define LEON_RESIZE_MAX_TAPS_BICUBIC 65      /* bicubic: count <= 4 * 16 + 1 */
 typedef struct leon_pipeline_tensor_resize {
     int32_t crop_x, crop_y, crop_width, crop_height;    /* frame pixels */
     int32_t out_width, out_height;
-    int32_t filter;                                     /* LEON_RESIZE_TRIANGLE */
+    int32_t filter;                                     /* LEON_RESIZE_TRIANGLE or LEON_RESIZE_BICUBIC */
 } leon_pipeline_tensor_resize;
 
 /* what a pipeline's tensors are (leon_pipeline_get_tensor_geometry): width and height of the tensor, the crop box in force, the
@@ -188,7 +199,8 @@ typedef struct leon_pipeline_tensor_geometry {
  *                               only the addressing differs (a packed uint8 HWC frame is the RGBA frame without its A bytes)
  * The frame's bytes (tensor_frame_bytes = 3 * height * width * element size) and the ring pitches do not depend on the layout; a
  * window of equally long GOPs is one strided [gops, pictures, H, W, 3] view.  A yuva stream's alpha is in neither layout.
- * Float CHW tensors are written by k_tensor / k_resample, every other combination by k_image / k_image_scaled.
+ * Float CHW tensors are written by k_tensor / k_resample, every other combination by k_image / k_image_scaled (bicubic: k_cubic /
+ * k_cubic_packed).
  * Refused at create: a format without the TENSOR bit, another layout, a non-zero reserved word. */
 typedef struct leon_pipeline_tensor_format {
     int32_t layout;             /* LEON_TENSOR_LAYOUT_* */
@@ -258,7 +270,8 @@ int leon_pipeline_tensor_table(const leon_pipeline_config* cfg, const leon_pipel
 int leon_pipeline_create_tensor_resized(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const leon_pipeline_tensor_resize* resize,
                                         const uint8_t* stream, size_t bytes, size_t valid_bytes, leon_pipeline_callback cb, void* user, leon_pipeline** out);
 /* the tables of one axis of that resampling: first[o], count[o] and weights[o * max_taps + k] (k >= count[o]: 0) for o = 0 .. out_size - 1.
- * Computed on the host, no device touched, refused as create refuses (and when a count exceeds max_taps; LEON_RESIZE_MAX_TAPS always fits) */
+ * Computed on the host, no device touched, refused as create refuses (and when a count exceeds max_taps; LEON_RESIZE_MAX_TAPS always fits the
+ * triangle filter, LEON_RESIZE_MAX_TAPS_BICUBIC both) */
 int leon_pipeline_resize_weights(int32_t in_size, int32_t crop_start, int32_t crop_size, int32_t out_size, int32_t filter,
                                  int32_t* first, int32_t* count, int32_t* weights, int32_t max_taps);
 int leon_pipeline_get_tensor_geometry(leon_pipeline* p, leon_pipeline_tensor_geometry* out);

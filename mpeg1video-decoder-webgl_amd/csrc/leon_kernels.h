@@ -1974,13 +1974,28 @@ __global__ __launch_bounds__(kRgbaBlock) void k_image(const uint8_t* __restrict_
 // and converted once with chroma_terms / rgba_px into RGBX dwords in LDS; (2) the horizontal pass, a lane per (output column, row
 // pair), writes packed 8-bit results to the tile's h rows in LDS -- two rows per lane share every weight read.  After the last
 // chunk (3) the vertical pass, a lane per output pixel, reads h, looks the three elements up and stores them.  Products are
-// v_mad_u32_u24 (weights <= 2^22, samples < 2^8; the sums stay below 2^31).  Rows at and beyond the frame height are never loaded
+// v_mad_u32_u24 (triangle: weights <= 2^22, samples < 2^8; the sums stay below 2^31).  Rows at and beyond the frame height are never loaded
 // (kOobBit) and never tapped; the last row of an odd height is the CPU twin's fill row, 255.
+// The filter (LEON_RESIZE_*) is a traits struct: what the LDS is sized for and the sign of the arithmetic.  Triangle weights are
+// never negative; bicubic ones are (down to about -0.074 * 2^22), so its sums are signed -- v_mad_i32_i24, an arithmetic shift and
+// a clamp on both sides (v_med3_i32) -- and its support of 2 doubles the taps: k_cubic / k_cubic_packed are instantiations of their
+// own, and the triangle kernels are compiled exactly as they were.
 static constexpr int kResTileX = 32, kResTileY = 8;          // kResTileX * kResTileY = kRgbaBlock: the vertical pass is one pixel per lane
-static constexpr int kResMaxTaps = 33;                       // = LEON_RESIZE_MAX_TAPS: 2 * 16 + 1
-static constexpr int kResStagePx = 4096;                     // staging dwords: 6 rows of the widest footprint (31 * 16 + 33 + 14 <= 544 columns, 578 dwords padded)
-static constexpr int kResHRows = 160;                        // h rows of a tile: <= 7 * 16 + 33 + 2 = 147, and one spare for the odd tail
+static constexpr int kResStagePx = 4096;                     // staging dwords: 6 rows of the widest footprint (triangle: 31 * 16 + 33 + 14 <= 544 columns, 578 dwords
+                                                             // padded; bicubic: 31 * 16 + 65 + 14 <= 576 columns, 612 dwords padded)
 static constexpr int kResWeightShift = 22;
+struct ResTriangle {
+    static constexpr int kMaxTaps = 33;                      // = LEON_RESIZE_MAX_TAPS: 2 * 16 + 1
+    static constexpr int kHRows = 160;                       // h rows of a tile: <= 7 * 16 + 33 + 2 = 147, and one spare for the odd tail
+    static constexpr bool kSigned = false;
+    typedef uint32_t Acc;
+};
+struct ResCubic {
+    static constexpr int kMaxTaps = 65;                      // = LEON_RESIZE_MAX_TAPS_BICUBIC: 4 * 16 + 1
+    static constexpr int kHRows = 192;                       // <= 7 * 16 + 65 + 2 = 179, and the spare row
+    static constexpr bool kSigned = true;
+    typedef int32_t Acc;
+};
 struct ResampleGeom {
     int32_t fw, fh, ow, oh;
     int32_t taps_x, taps_y;              // row length of the weight tables
@@ -1997,6 +2012,15 @@ __device__ __forceinline__ uint32_t resample_px(uint32_t ar, uint32_t ag, uint32
 {
     return min(ar >> kResWeightShift, 255u) | (min(ag >> kResWeightShift, 255u) << 8) | (min(ab >> kResWeightShift, 255u) << 16);
 }
+// signed sums: floor (arithmetic shift), then clamped on both sides
+__device__ __forceinline__ uint32_t resample_px(int32_t ar, int32_t ag, int32_t ab)
+{
+    const int32_t r = min(max(ar >> kResWeightShift, 0), 255), g = min(max(ag >> kResWeightShift, 0), 255), b = min(max(ab >> kResWeightShift, 0), 255);
+    return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
+}
+// acc + weight * sample, sample < 2^8: |weight| < 2^23 and the sums inside 32 bits are the table builder's promise (resize_axis_build)
+__device__ __forceinline__ uint32_t resample_mad(int32_t w, uint32_t sample, uint32_t acc) { return __umul24((uint32_t)w, sample) + acc; }
+__device__ __forceinline__ int32_t resample_mad(int32_t w, uint32_t sample, int32_t acc) { return __mul24(w, (int32_t)sample) + acc; }
 
 // The whole of a workgroup's work, for k_resample (EB = 2 or 4, CHW: one element store per lane and channel) and for k_image_scaled
 // (8-bit elements, the channels-last layout).  The latter's tile leaves through LDS: once the vertical pass has read them the h rows
@@ -2004,18 +2028,19 @@ __device__ __forceinline__ uint32_t resample_px(uint32_t ar, uint32_t ag, uint32
 // channel rows of 32 bytes -- every row at the offset its first byte has in its 16-byte line of the frame (the tensor starts on a
 // 256-byte boundary).  A lane then takes one aligned 16-byte line of one row: inside the row it is ONE b128 store, at the row's two
 // ends its elements go one by one (a row's start is aligned to nothing: out_width is any number).
-template <int EB, int LAYOUT>
+template <int EB, int LAYOUT, class F>
 __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
                                               const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
                                               const ResampleGeom& G)
 {
     typedef typename ImageElem<EB>::type Elem;
+    typedef typename F::Acc Acc;
     static_assert(kResTileX * kResTileY == kRgbaBlock && kResTileX == 32, "lane = (tid & 31, tid >> 5)");
     __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
     __shared__ __attribute__((aligned(16))) Elem tab_s[EB == 1 ? 16 : 3 * 256];
     __shared__ __attribute__((aligned(16))) uint32_t stage_s[kResStagePx];
-    __shared__ __attribute__((aligned(16))) uint32_t h_s[kResHRows * kResTileX];
-    __shared__ int32_t wx_s[kResTileX * kResMaxTaps], wy_s[kResTileY * kResMaxTaps];
+    __shared__ __attribute__((aligned(16))) uint32_t h_s[F::kHRows * kResTileX];
+    __shared__ int32_t wx_s[kResTileX * F::kMaxTaps], wy_s[kResTileY * F::kMaxTaps];
     __shared__ int32_t fx_s[kResTileX], nx_s[kResTileX], fy_s[kResTileY], ny_s[kResTileY];
     const int tid = threadIdx.x;
     const int ox0 = blockIdx.x * kResTileX, oy0 = blockIdx.y * kResTileY;
@@ -2101,12 +2126,13 @@ __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes
             for (int rr = 2 * sub; rr < rows; rr += 2 * (kRgbaBlock / 32)) {
                 const uint32_t* s = stage_s + rr * swp;
                 const int c0 = fx_s[o] - cx0;
-                uint32_t ar = 1u << (kResWeightShift - 1), ag = ar, ab = ar, br = ar, bg = ar, bb = ar;
+                Acc ar = (Acc)1 << (kResWeightShift - 1), ag = ar, ab = ar, br = ar, bg = ar, bb = ar;
                 for (int k = 0; k < n; k++) {
                     const int at = resample_col(c0 + k);
-                    const uint32_t wk = (uint32_t)w[k], pa = s[at], pb = s[at + swp];
-                    ar = __umul24(wk, pa & 255u) + ar; ag = __umul24(wk, (pa >> 8) & 255u) + ag; ab = __umul24(wk, (pa >> 16) & 255u) + ab;
-                    br = __umul24(wk, pb & 255u) + br; bg = __umul24(wk, (pb >> 8) & 255u) + bg; bb = __umul24(wk, (pb >> 16) & 255u) + bb;
+                    const int32_t wk = w[k];
+                    const uint32_t pa = s[at], pb = s[at + swp];
+                    ar = resample_mad(wk, pa & 255u, ar); ag = resample_mad(wk, (pa >> 8) & 255u, ag); ab = resample_mad(wk, (pa >> 16) & 255u, ab);
+                    br = resample_mad(wk, pb & 255u, br); bg = resample_mad(wk, (pb >> 8) & 255u, bg); bb = resample_mad(wk, (pb >> 16) & 255u, bb);
                 }
                 uint32_t* hrow = h_s + (r - ry0 + rr) * kResTileX + o;       // (the second row of an odd tail lands in the spare row)
                 hrow[0] = resample_px(ar, ag, ab);
@@ -2117,14 +2143,15 @@ __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes
     }
     // (3) vertical pass: output pixel (ox0 + o, oy0 + sub)
     const bool valid = o < nox && sub < noy;
-    uint32_t ar = 1u << (kResWeightShift - 1), ag = ar, ab = ar;
+    Acc ar = (Acc)1 << (kResWeightShift - 1), ag = ar, ab = ar;
     if (valid) {
         const int n = ny_s[sub];
         const int32_t* w = wy_s + sub * G.taps_y;
         const uint32_t* hcol = h_s + (fy_s[sub] - ry0) * kResTileX + o;
         for (int k = 0; k < n; k++) {
-            const uint32_t wk = (uint32_t)w[k], pa = hcol[k * kResTileX];
-            ar = __umul24(wk, pa & 255u) + ar; ag = __umul24(wk, (pa >> 8) & 255u) + ag; ab = __umul24(wk, (pa >> 16) & 255u) + ab;
+            const int32_t wk = w[k];
+            const uint32_t pa = hcol[k * kResTileX];
+            ar = resample_mad(wk, pa & 255u, ar); ag = resample_mad(wk, (pa >> 8) & 255u, ag); ab = resample_mad(wk, (pa >> 16) & 255u, ab);
         }
     }
     const uint32_t px = resample_px(ar, ag, ab);
@@ -2191,7 +2218,7 @@ __global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restri
                                                          const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
                                                          ResampleGeom G)
 {
-    resample_body<(int)sizeof(typename TensorElem<DTYPE>::type), kLayoutChw>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
+    resample_body<(int)sizeof(typename TensorElem<DTYPE>::type), kLayoutChw, ResTriangle>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
 }
 
 // 8-bit elements and / or the channels-last layout at a model's input size (leon_pipeline_tensor_format with leon_pipeline_tensor_resize)
@@ -2201,7 +2228,24 @@ __global__ __launch_bounds__(kRgbaBlock) void k_image_scaled(const uint8_t* __re
                                                              ResampleGeom G)
 {
     static_assert(LAYOUT == kLayoutHwc || EB == 1, "float CHW is k_resample's");
-    resample_body<EB, LAYOUT>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
+    resample_body<EB, LAYOUT, ResTriangle>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
+}
+
+// The same two kernels with the bicubic filter (LEON_RESIZE_BICUBIC): up to 65 signed taps an axis
+template <int DTYPE>
+__global__ __launch_bounds__(kRgbaBlock) void k_cubic(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
+                                                      const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
+                                                      ResampleGeom G)
+{
+    resample_body<(int)sizeof(typename TensorElem<DTYPE>::type), kLayoutChw, ResCubic>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
+}
+template <int EB, int LAYOUT>
+__global__ __launch_bounds__(kRgbaBlock) void k_cubic_packed(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
+                                                             const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
+                                                             ResampleGeom G)
+{
+    static_assert(LAYOUT == kLayoutHwc || EB == 1, "float CHW is k_cubic's");
+    resample_body<EB, LAYOUT, ResCubic>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

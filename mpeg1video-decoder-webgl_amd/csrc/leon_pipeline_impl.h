@@ -133,6 +133,7 @@ struct leon_pipeline {
     leon_pipeline_tensor_geometry tensor_geom{};
     std::vector<int32_t> resize_tabs;
     leon::ResampleGeom resample_geom{};
+    int32_t resize_filter = LEON_RESIZE_TRIANGLE;      // which kernels: k_resample / k_image_scaled, or k_cubic / k_cubic_packed
     int32_t* d_resize_tabs = nullptr;
     bool gpu_parser = false;
     // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
@@ -539,40 +540,71 @@ int tensor_table_build(const leon_pipeline_config* cfg, const leon_pipeline_tens
 
 // first[o], count[o], weights[o * max_taps + k] (zero behind count[o]); *taps = the largest count.  Every refusal of one axis is here.
 // Doubles, evaluated as written (the library is compiled with -ffp-contract=off; the pragma holds it for other builds).
+double resize_filter_triangle(double x)
+{
+    const double t = 1.0 - std::fabs(x);
+    return t > 0.0 ? t : 0.0;
+}
+double resize_filter_bicubic(double x)          // Keys' cubic, a = -0.5
+{
+#pragma clang fp contract(off)
+    const double a = -0.5;
+    x = std::fabs(x);
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
+    if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * a;
+    return 0.0;
+}
+// the most taps an output sample of `filter` has at the largest ratio (0: no such filter)
+int32_t resize_filter_max_taps(int32_t filter)
+{
+    return filter == LEON_RESIZE_TRIANGLE ? LEON_RESIZE_MAX_TAPS : filter == LEON_RESIZE_BICUBIC ? LEON_RESIZE_MAX_TAPS_BICUBIC : 0;
+}
 int resize_axis_build(const char* axis, int32_t in_size, int32_t crop_start, int32_t crop_size, int32_t out_size, int32_t filter,
                       int32_t* first, int32_t* count, int32_t* weights, int32_t max_taps, int32_t* taps)
 {
 #pragma clang fp contract(off)
-    if (filter != LEON_RESIZE_TRIANGLE) return fail(LEON_ERR_INVALID, "resize filter %d (LEON_RESIZE_TRIANGLE is the only one)", filter);
+    const int32_t filter_taps = resize_filter_max_taps(filter);
+    if (!filter_taps) return fail(LEON_ERR_INVALID, "resize filter %d (LEON_RESIZE_TRIANGLE and LEON_RESIZE_BICUBIC are the filters)", filter);
+    const bool cubic = filter == LEON_RESIZE_BICUBIC;
     if (out_size < 1 || out_size > 4096) return fail(LEON_ERR_INVALID, "resize: output %s %d is outside 1 .. 4096", axis, out_size);
     if (in_size < 1 || crop_size < 1 || crop_start < 0 || crop_start > in_size || crop_size > in_size - crop_start)
         return fail(LEON_ERR_INVALID, "resize: the crop box (%s: start %d, size %d) is empty or leaves the frame (%d)", axis, crop_start, crop_size, in_size);
     if ((int64_t)crop_size > 16 * (int64_t)out_size) return fail(LEON_ERR_INVALID, "resize: %s %d -> %d reduces by more than 16", axis, crop_size, out_size);
     if (max_taps < 1) return fail(LEON_ERR_INVALID, "resize: max_taps %d", max_taps);
     const double scale = (double)crop_size / (double)out_size;
-    const double fscale = scale < 1.0 ? 1.0 : scale, support = fscale;
+    const double fscale = scale < 1.0 ? 1.0 : scale, support = (cubic ? 2.0 : 1.0) * fscale;
     int32_t most = 0;
-    double w[LEON_RESIZE_MAX_TAPS + 2];
+    double w[LEON_RESIZE_MAX_TAPS_BICUBIC + 2];
     for (int32_t o = 0; o < out_size; o++) {
         const double center = (double)crop_start + ((double)o + 0.5) * scale;
         int32_t lo = (int32_t)(center - support + 0.5), hi = (int32_t)(center + support + 0.5);
         if (lo < 0) lo = 0;
         if (hi > in_size) hi = in_size;
         const int32_t n = hi - lo;
-        if (n < 1 || n > LEON_RESIZE_MAX_TAPS) return fail(LEON_ERR_INVALID, "resize: %s output %d has %d taps", axis, o, n);
+        if (n < 1 || n > filter_taps) return fail(LEON_ERR_INVALID, "resize: %s output %d has %d taps", axis, o, n);
         if (n > max_taps) return fail(LEON_ERR_INVALID, "resize: %s output %d has %d taps, max_taps is %d", axis, o, n, max_taps);
         double sum = 0.0;
         for (int32_t k = 0; k < n; k++) {
             const double x = ((double)(lo + k) - center + 0.5) / fscale;
-            const double t = 1.0 - std::fabs(x);
-            w[k] = t > 0.0 ? t : 0.0;
+            w[k] = cubic ? resize_filter_bicubic(x) : resize_filter_triangle(x);
             sum += w[k];
         }
         if (!(sum > 0.0)) return fail(LEON_ERR_INVALID, "resize: %s output %d has no weight", axis, o);
+        // what the kernels' 24-bit multiplies and 32-bit sums rest on: every |W| < 2^23, and neither the positive nor the negative
+        // part of a row can carry a sum of 8-bit samples out of 31 bits (with these filters it never happens)
+        int64_t pos = 0, neg = 0;
+        for (int32_t k = 0; k < n; k++) {
+            const double v = (w[k] / sum) * 4194304.0;
+            const int32_t W = v < 0.0 ? (int32_t)(-0.5 + v) : (int32_t)(0.5 + v);
+            if (W <= -(1 << 23) || W >= (1 << 23)) return fail(LEON_ERR_INVALID, "resize: %s output %d has a weight of %d", axis, o, W);
+            if (W < 0) neg -= W; else pos += W;
+            if (weights) weights[(size_t)o * max_taps + k] = W;
+        }
+        if ((1 << 21) + 255 * pos >= ((int64_t)1 << 31) || 255 * neg >= ((int64_t)1 << 31)) return fail(LEON_ERR_INVALID, "resize: the weights of %s output %d overflow 32 bits", axis, o);
         if (first) first[o] = lo;
         if (count) count[o] = n;
         if (weights)
-            for (int32_t k = 0; k < max_taps; k++) weights[(size_t)o * max_taps + k] = k < n ? (int32_t)(0.5 + (w[k] / sum) * 4194304.0) : 0;
+            for (int32_t k = n; k < max_taps; k++) weights[(size_t)o * max_taps + k] = 0;
         if (n > most) most = n;
     }
     if (taps) *taps = most;
@@ -610,6 +642,7 @@ int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
     g = leon_pipeline_tensor_geometry{fw, fh, 0, 0, fw, fh, 1, 1, 0};
     if (!resize_asked(rz)) return LEON_OK;
     g.resized = 1;
+    p->resize_filter = rz->filter;
     g.width = rz->out_width;
     g.height = rz->out_height;
     if (rz->crop_x | rz->crop_y | rz->crop_width | rz->crop_height) {
@@ -617,13 +650,14 @@ int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
     }
     int rc;
     // once for the refusals and the tap counts, then into the buffer with rows of exactly that length
-    if ((rc = resize_axis_build("width", fw, g.crop_x, g.crop_width, g.width, rz->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS, &g.taps_x)) != LEON_OK) return rc;
-    if ((rc = resize_axis_build("height", fh, g.crop_y, g.crop_height, g.height, rz->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS, &g.taps_y)) != LEON_OK) return rc;
+    if ((rc = resize_axis_build("width", fw, g.crop_x, g.crop_width, g.width, rz->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS_BICUBIC, &g.taps_x)) != LEON_OK) return rc;
+    if ((rc = resize_axis_build("height", fh, g.crop_y, g.crop_height, g.height, rz->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS_BICUBIC, &g.taps_y)) != LEON_OK) return rc;
     leon::ResampleGeom& G = p->resample_geom;
     G = leon::ResampleGeom{};
     G.fw = fw; G.fh = fh; G.ow = g.width; G.oh = g.height;
     // rows of Wx are an odd number of entries long (zero behind count[o]): the horizontal pass's lanes are output columns and read
     // Wx[o][k] for one k together -- 32 entries a row (ratio 16) would put them all on one LDS bank, 18 (1080p -> 224) on every other
+    // (bicubic: up to 65, odd as well)
     G.taps_x = g.taps_x | 1; G.taps_y = g.taps_y;
     G.off_cx = (uint32_t)g.width;
     G.off_wx = G.off_cx + (uint32_t)g.width;
@@ -634,8 +668,8 @@ int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
     int32_t* t = p->resize_tabs.data();
     if ((rc = resize_axis_build("width", fw, g.crop_x, g.crop_width, g.width, rz->filter, t, t + G.off_cx, t + G.off_wx, G.taps_x, nullptr)) != LEON_OK) return rc;
     if ((rc = resize_axis_build("height", fh, g.crop_y, g.crop_height, g.height, rz->filter, t + G.off_fy, t + G.off_cy, t + G.off_wy, g.taps_y, nullptr)) != LEON_OK) return rc;
-    // What k_resample's LDS is sized for.  Within the limits above neither check can fail (at most 544 columns and 147 rows:
-    // leon_kernels.h has the arithmetic); they stand guard for the kernel's chunk loop, which needs at least one row pair per chunk
+    // What the kernel's LDS is sized for (k_resample's, or k_cubic's for the bicubic filter).  Within the limits above neither check can
+    // fail (at most 544 columns and 147 rows, bicubic 576 and 179: leon_kernels.h has the arithmetic); they stand guard for the kernel's chunk loop, which needs at least one row pair per chunk
     // (rc >= 2) to advance, should a limit ever be widened without the kernel.
     for (int32_t o = 0; o < g.width; o += leon::kResTileX) {
         const int32_t l = std::min(o + leon::kResTileX, g.width) - 1;
@@ -645,7 +679,7 @@ int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
     for (int32_t o = 0; o < g.height; o += leon::kResTileY) {
         const int32_t l = std::min(o + leon::kResTileY, g.height) - 1;
         const int32_t rows = t[G.off_fy + l] + t[G.off_cy + l] - (t[G.off_fy + o] & ~1);
-        if (rows + 1 > leon::kResHRows) return fail(LEON_ERR_INVALID, "resize: a tile's source footprint of %d rows does not fit", rows);
+        if (rows + 1 > (rz->filter == LEON_RESIZE_BICUBIC ? leon::ResCubic::kHRows : leon::ResTriangle::kHRows)) return fail(LEON_ERR_INVALID, "resize: a tile's source footprint of %d rows does not fit", rows);
     }
     return LEON_OK;
 }
@@ -1092,6 +1126,21 @@ void launch_k_image_scaled(const leon_pipeline* p, const uint32_t* ids, unsigned
     hipLaunchKernelGGL((leon::k_image_scaled<EB, LAYOUT>), grid, dim3(leon::kRgbaBlock), 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, ids,
                        (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, G);
 }
+// ... and the bicubic filter's instantiations of both (k_cubic, k_cubic_packed)
+template <int DTYPE>
+void launch_k_cubic(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::ResampleGeom& G)
+{
+    const dim3 grid((unsigned)((G.ow + leon::kResTileX - 1) / leon::kResTileX), (unsigned)((G.oh + leon::kResTileY - 1) / leon::kResTileY), n);
+    hipLaunchKernelGGL(leon::k_cubic<DTYPE>, grid, dim3(leon::kRgbaBlock), 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, ids,
+                       (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, G);
+}
+template <int EB, int LAYOUT>
+void launch_k_cubic_packed(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::ResampleGeom& G)
+{
+    const dim3 grid((unsigned)((G.ow + leon::kResTileX - 1) / leon::kResTileX), (unsigned)((G.oh + leon::kResTileY - 1) / leon::kResTileY), n);
+    hipLaunchKernelGGL((leon::k_cubic_packed<EB, LAYOUT>), grid, dim3(leon::kRgbaBlock), 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, ids,
+                       (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, G);
+}
 int launch_tensors(leon_pipeline* p, const PipeWindow* w)
 {
     const size_t n = w->frame_ids.size();
@@ -1111,7 +1160,16 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
         R.tensor_pitch_lo = (uint32_t)(p->tensor_pitch & 0xffffffffu); R.tensor_pitch_hi = (uint32_t)((uint64_t)p->tensor_pitch >> 32);
         for (size_t at = 0; at < n; at += 65535) {
             const unsigned m = (unsigned)std::min<size_t>(65535, n - at);
-            if (image) {
+            if (p->resize_filter == LEON_RESIZE_BICUBIC) {
+                if (image) {
+                    if (p->tensor_elem == 1 && !hwc) launch_k_cubic_packed<1, leon::kLayoutChw>(p, dv + at, m, R);
+                    else if (p->tensor_elem == 1) launch_k_cubic_packed<1, leon::kLayoutHwc>(p, dv + at, m, R);
+                    else if (p->tensor_elem == 2) launch_k_cubic_packed<2, leon::kLayoutHwc>(p, dv + at, m, R);
+                    else launch_k_cubic_packed<4, leon::kLayoutHwc>(p, dv + at, m, R);
+                } else if (p->tensor_dtype == LEON_TENSOR_F16) launch_k_cubic<leon::kTensorF16>(p, dv + at, m, R);
+                else if (p->tensor_dtype == LEON_TENSOR_BF16) launch_k_cubic<leon::kTensorBf16>(p, dv + at, m, R);
+                else launch_k_cubic<leon::kTensorF32>(p, dv + at, m, R);
+            } else if (image) {
                 if (p->tensor_elem == 1 && !hwc) launch_k_image_scaled<1, leon::kLayoutChw>(p, dv + at, m, R);
                 else if (p->tensor_elem == 1) launch_k_image_scaled<1, leon::kLayoutHwc>(p, dv + at, m, R);
                 else if (p->tensor_elem == 2) launch_k_image_scaled<2, leon::kLayoutHwc>(p, dv + at, m, R);

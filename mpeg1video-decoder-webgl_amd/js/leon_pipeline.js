@@ -31,7 +31,8 @@
  *                                  stats() reports tensorDtype, tensorElementBytes, tensorFrameBytes, tensorFramePitch, tensorGopPitch
  *                                  opts.tensorSize [h, w] (and opts.tensorCrop [x, y, w, h], frame pixels; default the whole frame):
  *                                  that crop box resampled on the device to h x w (antialiased triangle filter, include/leon_pipeline.h)
- *                                  -- readTensor then returns [3][h][w]; stats() reports tensorWidth, tensorHeight
+ *                                  -- readTensor then returns [3][h][w]; stats() reports tensorWidth, tensorHeight;
+ *                                  opts.tensorFilter 'triangle' (default) or 'bicubic' (LEON_RESIZE_BICUBIC: signed taps, clamped on both sides)
  *                                  opts.tensorDtype 'uint8': the elements are the 8-bit colour values themselves (no tensorScale /
  *                                  tensorBias), readTensor returns a Uint8Array; opts.tensorLayout 'chw' (default) or 'hwc': channels
  *                                  last, [H][W][3] -- uint8 hwc is the packed RGB frame, 3 bytes per pixel; stats() reports tensorLayout
@@ -51,6 +52,7 @@ class LeonPipeline extends EventEmitter {
     const outputs = { rgba: 1, ycbcr: 2, both: 3, tensor: 16, 'rgba+tensor': 17, 'ycbcr+tensor': 18, all: 19 };
     const dtypes = { float16: 1, bfloat16: 2, float32: 3, uint8: 8 };
     const layouts = { chw: 0, hwc: 1 };
+    const filters = { triangle: 0, bicubic: 3 };
     let output = opts.output === undefined ? 0 : opts.output;
     if (typeof output === 'string') {
       if (!(output in outputs)) throw new TypeError("output: 'rgba', 'ycbcr', 'both', 'tensor', 'rgba+tensor', 'ycbcr+tensor' or 'all'");
@@ -66,6 +68,11 @@ class LeonPipeline extends EventEmitter {
       if (!(tensorLayout in layouts)) throw new TypeError("tensorLayout: 'chw' or 'hwc'");
       tensorLayout = layouts[tensorLayout];
     }
+    let tensorFilter = opts.tensorFilter === undefined ? 0 : opts.tensorFilter;
+    if (typeof tensorFilter === 'string') {
+      if (!(tensorFilter in filters)) throw new TypeError("tensorFilter: 'triangle' or 'bicubic'");
+      tensorFilter = filters[tensorFilter];
+    }
     // tensorSize [h, w] (, tensorCrop [x, y, w, h] in frame pixels): the tensors resampled on the device to a model's input size
     const ints = (v, n, what) => {
       if (v === undefined || v === null) return new Array(n).fill(0);
@@ -74,7 +81,7 @@ class LeonPipeline extends EventEmitter {
     };
     const [tensorOutHeight, tensorOutWidth] = ints(opts.tensorSize, 2, 'tensorSize: [height, width]');
     const [tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight] = ints(opts.tensorCrop, 4, 'tensorCrop: [x, y, width, height]');
-    const resize = { tensorOutHeight, tensorOutWidth, tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight };
+    const resize = { tensorOutHeight, tensorOutWidth, tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight, tensorFilter };
     this._p = addon.createPipeline(stream, Object.assign({}, opts, { output, tensorDtype, tensorLayout }, resize), (w, frames, status) => this._deliver(w, frames, status));
   }
 

@@ -91,16 +91,43 @@ def tensor_table(dtype="float16", scale=None, bias=None):
     return ((x + 0x7fff + ((x >> 16) & 1)) >> 16).astype(np.uint16)
 
 
-RESIZE_TRIANGLE = 0          # LEON_RESIZE_TRIANGLE, the only filter
+RESIZE_TRIANGLE = 0          # LEON_RESIZE_TRIANGLE
+RESIZE_BICUBIC = 3           # LEON_RESIZE_BICUBIC
 RESIZE_MAX_TAPS = 33         # LEON_RESIZE_MAX_TAPS
+RESIZE_MAX_TAPS_BICUBIC = 65         # LEON_RESIZE_MAX_TAPS_BICUBIC
 RESIZE_PRECISION = 22
+RESIZE_FILTERS = {"triangle": RESIZE_TRIANGLE, "bicubic": RESIZE_BICUBIC}
 
 
-def resize_weights(in_size, crop_start, crop_size, out_size):
+def _resize_filter_code(filter):
+    """a name of RESIZE_FILTERS or the raw code (what the library does not know it refuses)"""
+    return RESIZE_FILTERS[filter] if isinstance(filter, str) else int(filter)
+
+
+def _triangle(x):
+    return max(0.0, 1.0 - abs(x))
+
+
+def _bicubic(x):
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0
+    if x < 2.0:
+        return (((x - 5.0) * x + 8.0) * x - 4.0) * a
+    return 0.0
+
+
+def resize_weights(in_size, crop_start, crop_size, out_size, filter=RESIZE_TRIANGLE):
     """The tables of one axis of the resized tensor output (include/leon_pipeline.h), in numpy / Python floats and independent of
     the C code: (first[out], count[out], weights[out, taps]) with taps = the largest count, weights int32 with 22 fractional bits
-    and zero behind count[o].  An antialiased triangle filter over crop_start .. crop_start + crop_size of an axis of in_size
-    samples: taps may leave the crop box, never the axis.  ValueError where the library refuses."""
+    and zero behind count[o].  An antialiased triangle filter (filter=RESIZE_BICUBIC: Keys' cubic with a = -0.5, support 2, signed
+    weights) over crop_start .. crop_start + crop_size of an axis of in_size samples: taps may leave the crop box, never the axis.
+    ValueError where the library refuses."""
+    filter = _resize_filter_code(filter)
+    if filter not in (RESIZE_TRIANGLE, RESIZE_BICUBIC):
+        raise ValueError("resize filter %d" % filter)
+    f, reach = (_bicubic, 2.0) if filter == RESIZE_BICUBIC else (_triangle, 1.0)
     in_size, in0, crop_size, out_size = int(in_size), int(crop_start), int(crop_size), int(out_size)
     if not 1 <= out_size <= 4096:
         raise ValueError("output size %d is outside 1 .. 4096" % out_size)
@@ -110,18 +137,19 @@ def resize_weights(in_size, crop_start, crop_size, out_size):
         raise ValueError("%d -> %d reduces by more than 16" % (crop_size, out_size))
     scale = float(crop_size) / float(out_size)
     fscale = max(scale, 1.0)
-    support = fscale
+    support = reach * fscale
     first, rows = [], []
     for o in range(out_size):
         center = in0 + (o + 0.5) * scale
         lo = max(0, int(center - support + 0.5))
         hi = min(in_size, int(center + support + 0.5))
-        w = [max(0.0, 1.0 - abs((lo + k - center + 0.5) / fscale)) for k in range(hi - lo)]
+        w = [f((lo + k - center + 0.5) / fscale) for k in range(hi - lo)]
         total = 0.0
         for v in w:
             total += v
         first.append(lo)
-        rows.append([int(0.5 + (v / total) * float(1 << RESIZE_PRECISION)) for v in w])
+        q = [(v / total) * float(1 << RESIZE_PRECISION) for v in w]
+        rows.append([int(-0.5 + v) if v < 0.0 else int(0.5 + v) for v in q])
     count = np.asarray([len(r) for r in rows], dtype=np.int32)
     weights = np.zeros((out_size, int(count.max())), dtype=np.int32)
     for o, r in enumerate(rows):
@@ -140,16 +168,17 @@ def _resize_pass(img, first, count, weights):
     return out
 
 
-def resize_rgb(rgb, crop, size):
+def resize_rgb(rgb, crop, size, filter=RESIZE_TRIANGLE):
     """The resized tensor output's 8-bit colour values, in numpy: rgb [H, W, C] uint8 (the frame), crop = (x, y, width, height) in
     frame pixels (None: the whole frame), size = (out_height, out_width) -> [out_height, out_width, C] uint8.  Horizontal pass first
-    with an 8-bit result, then vertical (include/leon_pipeline.h has the definition)."""
+    with an 8-bit result, then vertical, each clamped to 0 .. 255 (include/leon_pipeline.h has the definition; filter: RESIZE_TRIANGLE or
+    RESIZE_BICUBIC)."""
     rgb = np.asarray(rgb, dtype=np.uint8)
     fh, fw = rgb.shape[:2]
     x, y, w, h = (0, 0, fw, fh) if crop is None or not any(crop) else crop
     oh, ow = size
-    fx, nx, wx = resize_weights(fw, x, w, ow)
-    fy, ny, wy = resize_weights(fh, y, h, oh)
+    fx, nx, wx = resize_weights(fw, x, w, ow, filter)
+    fy, ny, wy = resize_weights(fh, y, h, oh, filter)
     lo, hi = int(fy.min()), int((fy + ny).max())          # the rows the vertical pass taps
     hz = _resize_pass(rgb[lo:hi], fx, nx, wx)
     return _resize_pass(hz.transpose(1, 0, 2), fy - lo, ny, wy).transpose(1, 0, 2).copy()
@@ -614,8 +643,9 @@ class Pipeline:
     value]; tensor_scale / tensor_bias: three floats each (None: 1/255 and 0).  read_tensor(frame) copies it to the host,
     tensor_view(frame) and window_tensor(frames) wrap it in place as torch tensors.
     tensor_size=(out_h, out_w) [, tensor_crop=(x, y, w, h) in frame pixels]: the tensors are that crop box (default: the whole frame)
-    resampled on the device to a model's input size -- element = table[c][resize_rgb(rgb, crop, size)] --, and every tensor shape
-    above is [3, out_h, out_w] (tensor_geometry has the values in force).
+    resampled on the device to a model's input size -- element = table[c][resize_rgb(rgb, crop, size, filter)] --, and every tensor shape
+    above is [3, out_h, out_w] (tensor_geometry has the values in force); tensor_filter="triangle" (the default, antialiased bilinear) or
+    "bicubic" (or the RESIZE_* integers).
     tensor_dtype="uint8": the elements are the 8-bit colour values themselves (no scale / bias).  tensor_layout="hwc": channels last
     -- every shape above is [H, W, 3] ([N, H, W, 3] for window_tensor), a packed uint8 HWC frame is 3 bytes per pixel; tensor_shape
     (PipelineTensorShape) has the element type, the layout and the strides in elements."""
@@ -633,6 +663,7 @@ class Pipeline:
             tcfg = PipelineTensorConfig(_tensor_dtype_code(tensor_dtype), (C.c_float * 3)(*([0, 0, 0] if tensor_scale is None else tensor_scale)),
                                         (C.c_float * 3)(*([0, 0, 0] if tensor_bias is None else tensor_bias)))
         rcfg = None
+        tensor_filter = _resize_filter_code(tensor_filter)
         if tensor_size is not None or tensor_crop is not None or tensor_filter:      # (the library refuses what does not go together)
             oh, ow = (0, 0) if tensor_size is None else tensor_size
             cx, cy, cw, ch = (0, 0, 0, 0) if tensor_crop is None else tensor_crop

@@ -740,12 +740,13 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
         napi_throw_type_error(env, nullptr, "createPipeline: tensorScale / tensorBias must be arrays of three numbers");
         return nullptr;
     }
-    // ... resampled to a model's input size (leon_pipeline_tensor_resize; js/leon_pipeline.js spreads tensorSize / tensorCrop into these)
+    // ... resampled to a model's input size (leon_pipeline_tensor_resize; js/leon_pipeline.js spreads tensorSize / tensorCrop into these and maps tensorFilter's names to LEON_RESIZE_*)
     leon_pipeline_tensor_resize rcfg;
     memset(&rcfg, 0, sizeof rcfg);
     if (!(get_i32(env, argv[1], "tensorOutWidth", &rcfg.out_width, 0) && get_i32(env, argv[1], "tensorOutHeight", &rcfg.out_height, 0) &&
           get_i32(env, argv[1], "tensorCropX", &rcfg.crop_x, 0) && get_i32(env, argv[1], "tensorCropY", &rcfg.crop_y, 0) &&
-          get_i32(env, argv[1], "tensorCropWidth", &rcfg.crop_width, 0) && get_i32(env, argv[1], "tensorCropHeight", &rcfg.crop_height, 0))) {
+          get_i32(env, argv[1], "tensorCropWidth", &rcfg.crop_width, 0) && get_i32(env, argv[1], "tensorCropHeight", &rcfg.crop_height, 0) &&
+          get_i32(env, argv[1], "tensorFilter", &rcfg.filter, 0))) {
         napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
         return nullptr;
     }
@@ -756,7 +757,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
         napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
         return nullptr;
     }
-    const bool resized = (rcfg.out_width | rcfg.out_height | rcfg.crop_x | rcfg.crop_y | rcfg.crop_width | rcfg.crop_height) != 0;
+    const bool resized = (rcfg.out_width | rcfg.out_height | rcfg.crop_x | rcfg.crop_y | rcfg.crop_width | rcfg.crop_height | rcfg.filter) != 0;
     const bool tensor = (cfg.output & LEON_PIPELINE_OUTPUT_TENSOR) != 0 || tcfg.dtype != 0 || resized || fcfg.layout != 0;
     PipeHandle* h = new PipeHandle();
     napi_value name;
