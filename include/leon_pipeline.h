@@ -199,8 +199,8 @@ typedef struct leon_pipeline_tensor_geometry {
  *                               only the addressing differs (a packed uint8 HWC frame is the RGBA frame without its A bytes)
  * The frame's bytes (tensor_frame_bytes = 3 * height * width * element size) and the ring pitches do not depend on the layout; a
  * window of equally long GOPs is one strided [gops, pictures, H, W, 3] view.  A yuva stream's alpha is in neither layout.
- * Float CHW tensors are written by k_tensor / k_resample, every other combination by k_image / k_image_scaled (bicubic: k_cubic /
- * k_cubic_packed).
+ * Every combination is written by k_tensor<element bytes, layout> at the frame's size and by k_resample<element bytes, layout, filter> at
+ * a model's input size.
  * Refused at create: a format without the TENSOR bit, another layout, a non-zero reserved word. */
 typedef struct leon_pipeline_tensor_format {
     int32_t layout;             /* LEON_TENSOR_LAYOUT_* */

@@ -1612,30 +1612,53 @@ __global__ __launch_bounds__(kRgbaBlock) void k_rgba_gl(const uint8_t* __restric
     *reinterpret_cast<uint32_t*>(rgba + ((size_t)f * G.fw * G.fh + (size_t)yy * G.fw + x) * 4) = o;
 }
 
-// ---- the frames as planar float tensors (leon_pipeline.h, LEON_PIPELINE_OUTPUT_TENSOR) ------------------------
-// frame planes record (FrameOut layout) -> [3][fh][fw] elements R, G, B, dense: element = table[c][8-bit colour value], the colour
-// value from the fused display's integer tables (chroma_terms / rgba_px above -- the arithmetic is not restated), the table
-// (3 x 256 elements, built by the host: tensor_table_build) in LDS beside them.  One launch per window, blockIdx.z = frame:
-// frame_ids[z] is the frame's index in both rings.  Threads are numbered linearly through the frame (k_rgba_twin4: a row-shaped grid
-// leaves every eighth wave of a 1920-wide row half empty).  Fast path (fw % 8 == 0): a lane takes 8 pixels x 2 rows of 16-bit elements
-// -- one 8-byte Y load per row, 4 Cb + 4 Cr bytes for both -- or 4 pixels x 2 rows of fp32 (k_rgba_twin4's shape), so that per
-// channel and row a wave stores 64 x 16 B = 1 KB contiguous with ONE instruction.  (fp32 with 8 pixels per lane, two 16-byte stores
-// 32 bytes apart, every instruction writing half of each line it touches: 18.5 ms per 1536 1080p frames, 2.3 TB/s -- measured,
-// dropped.)  Other even widths: a lane takes one 2 x 2 quad, element stores.  The planes are read once
-// and the tensor is never read again here: both non-temporal.  An odd frame height leaves the last row at the CPU twin's fill
-// value 255 (its quad loop covers fh >> 1 row pairs): table[c][255].
-static constexpr int kTensorF16 = 1, kTensorBf16 = 2, kTensorF32 = 3;      // = LEON_TENSOR_*
-struct TensorGeom {
-    int32_t fw, fh;
-    uint32_t per_row, n_items;           // lanes per row pair (tensor_lane_px pixels each), lanes per frame ((fh + 1) / 2 row pairs)
+// ---- the frames as tensors (leon_pipeline.h, LEON_PIPELINE_OUTPUT_TENSOR, leon_pipeline_tensor_format) ----------------------------
+// frame planes record (FrameOut layout) -> elements R, G, B, dense: [3][fh][fw] (CHW) or [fh][fw][3] (HWC, channels last) of 1-, 2- or
+// 4-byte elements.  The colour value comes from the fused display's integer tables (chroma_terms / rgba_px above -- the arithmetic is
+// not restated); the element is the colour value itself (1 byte: no table, none in LDS) or table[c][colour value] (3 x 256 elements,
+// built by the host: tensor_table_build, in LDS beside the conversion tables -- fp16 and bf16 differ in the table only: the kernels
+// are made per element SIZE).  One launch per window, blockIdx.z = frame: frame_ids[z] is the frame's index in both rings.  Threads
+// are numbered linearly through the frame (k_rgba_twin4: a row-shaped grid leaves every eighth wave of a 1920-wide row half empty).
+// Fast path (fw % 8 == 0): a lane takes 8 pixels x 2 rows -- one 8-byte Y load per row, 4 Cb + 4 Cr bytes for both -- or 4 pixels x
+// 2 rows of 4-byte elements (k_rgba_twin4's shape).  The store side is what differs:
+//   float CHW: 16 bytes per channel and row, so that a wave stores 64 x 16 B = 1 KB contiguous with ONE instruction.  (fp32 with 8
+//     pixels per lane, two 16-byte stores 32 bytes apart, every instruction writing half of each line it touches: 18.5 ms per 1536
+//     1080p frames, 2.3 TB/s -- measured, dropped.)
+//   uint8 CHW: 8 bytes per channel and row -- one b64 store, a wave writes 512 contiguous bytes per instruction.
+//   HWC: a lane's row piece is 24 / 48 / 48 contiguous bytes (1- / 2- / 4-byte elements).  Stored from the lane that made it that is
+//     three instructions whose lanes lie 24 or 48 bytes apart, each writing a third of every line it touches (the shape recorded
+//     above as measured and dropped for fp32).  So the wave's 64 pieces (1536 B / 3 KB / 3 KB, contiguous in the frame but
+//     for the seam where the wave crosses into the next row pair) change lanes through the wave's LDS strip: written at lane * piece,
+//     read back at (j * 64 + lane) * third-of-a-piece, j = 0 .. 2 -- so store instruction j writes the thirds 64 j .. 64 j + 63 in
+//     order, 64 x 16 B = 1 KB contiguous (64 x 8 B = 512 B for uint8: a third of 24 bytes).  A third never straddles two pieces, so
+//     its address is its source lane's row offset (ds_bpermute) plus 0, 1 or 2 thirds.  LDS banks: pieces of 12 dwords written as
+//     b128 by groups of 8 lanes land on 32 different banks (12 l mod 32, l = 0 .. 7: 0 12 24 4 16 28 8 20, 4 dwords each), pieces of
+//     6 dwords written as b64 by groups of 16 lanes too (6 l mod 32 covers every even bank once); the reads are contiguous.
+//     Rows go one after the other through the same strip (both at once would put the 2- and 4-byte kernels over 20 KB).
+// Other even widths: a lane takes one 2 x 2 quad, element stores.  The planes are read once and the tensor is never read again here:
+// both non-temporal.  An odd frame height leaves the last row at the CPU twin's fill value 255 (its quad loop covers fh >> 1 row
+// pairs): table[c][255].  The tensor's buffer resource ends with the frame: the second row of an HWC lane in the fill row pair, and
+// anything a wrong offset would reach behind the frame, is dropped by the bounds check.
+static constexpr int kLayoutChw = 0, kLayoutHwc = 1;          // = LEON_TENSOR_LAYOUT_*
+// what both tensor kernels find a frame's planes and its tensor by
+struct RingGeom {
     uint32_t luma_stride, chroma_stride, cb_off, cr_off;      // FrameOut
     uint32_t planes_pitch_lo, planes_pitch_hi, tensor_pitch_lo, tensor_pitch_hi;      // bytes between ring frames
+};
+struct TensorGeom {
+    int32_t fw, fh;
+    uint32_t per_row, n_items;           // lanes per row pair (lane_px pixels each), lanes per frame ((fh + 1) / 2 row pairs)
+    RingGeom ring;
     int32_t fast;                        // fw % 8 == 0
 };
-template <int DTYPE> struct TensorElem { typedef uint16_t type; };
-template <> struct TensorElem<kTensorF32> { typedef uint32_t type; };
-// pixels per lane and row on the fast path: 16 bytes of elements
-constexpr int tensor_lane_px(int dtype) { return dtype == kTensorF32 ? 4 : 8; }
+template <int EB> struct ElemOf { typedef uint8_t type; };
+template <> struct ElemOf<2> { typedef uint16_t type; };
+template <> struct ElemOf<4> { typedef uint32_t type; };
+// pixels per lane and row on the fast path
+constexpr int lane_px(int eb) { return eb == 4 ? 4 : 8; }
+// bytes of a lane's row piece in the HWC layout, and of the wave's exchange strip
+constexpr int image_piece_bytes(int eb) { return lane_px(eb) * 3 * eb; }
+constexpr int image_strip_bytes(int eb, int layout) { return layout == kLayoutHwc ? 64 * image_piece_bytes(eb) : 0; }
 
 // The conversion tables into LDS as k_recon_display loads them (1 KB chunks straight into LDS); the caller waits (wait_vmem_all) and syncs
 __device__ __forceinline__ void display_lut_to_lds(int32_t* lut_s, const Tables* T)
@@ -1669,154 +1692,54 @@ __device__ __forceinline__ void tensor_px8(const char* lut, v2u y8, const Chroma
     }
 }
 
-// `off` = the row's first element in a channel plane
-// the fp32 form: 4 pixels of one row
-__device__ __forceinline__ void tensor_row4_f32(const char* lut, const uint32_t* tab, uint32_t y4, const ChromaTerms& c0, const ChromaTerms& c1, bool fill,
-                                                __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_elems, bool in, uint32_t two)
-{
-    uint32_t px[4];
-    tensor_px4(lut, y4, c0, c1, fill, two, px);
-    const uint32_t oob = in ? 0u : kOobBit;
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        const v4u e = {tab[ch * 256 + ((px[0] >> (8 * ch)) & 255u)], tab[ch * 256 + ((px[1] >> (8 * ch)) & 255u)],
-                       tab[ch * 256 + ((px[2] >> (8 * ch)) & 255u)], tab[ch * 256 + ((px[3] >> (8 * ch)) & 255u)]};
-        __builtin_amdgcn_raw_buffer_store_b128(e, rs, (int)((((uint32_t)ch * plane_elems + off) * 4u) | oob), 0, kAuxFrameStore);
-    }
-}
-
-template <int DTYPE>
-__device__ __forceinline__ void tensor_row8(const char* lut, const typename TensorElem<DTYPE>::type* tab, v2u y8, const ChromaTerms (&c)[4], bool fill,
-                                            __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_elems, bool in, uint32_t two)
-{
-    uint32_t px[8];
-    tensor_px8(lut, y8, c, fill, two, px);
-    const uint32_t oob = in ? 0u : kOobBit;
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        uint32_t e[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) e[k] = tab[ch * 256 + ((px[k] >> (8 * ch)) & 255u)];
-        const uint32_t at = (uint32_t)ch * plane_elems + off;
-        __builtin_amdgcn_raw_buffer_store_b128(v4u{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)}, rs,
-                                               (int)((at * 2u) | oob), 0, kAuxFrameStore);
-    }
-}
-
-template <int DTYPE>
-__global__ __launch_bounds__(kRgbaBlock) void k_tensor(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
-                                                       const uint32_t* __restrict__ table, const Tables* __restrict__ T, TensorGeom G)
-{
-    typedef typename TensorElem<DTYPE>::type Elem;
-    __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
-    __shared__ __attribute__((aligned(16))) Elem tab_s[3 * 256];
-    {   // the conversion tables, the element table through registers
-        display_lut_to_lds(lut_s, T);
-        constexpr int kDwords = 3 * 256 * (int)sizeof(Elem) / 4;
-        for (int i = threadIdx.x; i < kDwords; i += kRgbaBlock) reinterpret_cast<uint32_t*>(tab_s)[i] = table[i];
-        wait_vmem_all();
-        __syncthreads();
-    }
-    const uint32_t idx = blockIdx.x * (uint32_t)kRgbaBlock + threadIdx.x;
-    if (idx >= G.n_items) return;
-    const char* lut = reinterpret_cast<const char*>(lut_s);
-    const uint32_t pair = idx / G.per_row, col = idx - pair * G.per_row;
-    const uint32_t fid = frame_ids[blockIdx.z];
-    const uint8_t* src = planes_ring + (size_t)fid * join64(G.planes_pitch_lo, G.planes_pitch_hi);
-    uint8_t* dst = tensor_ring + (size_t)fid * join64(G.tensor_pitch_lo, G.tensor_pitch_hi);
-    const uint32_t r0 = 2u * pair, fw = (uint32_t)G.fw, fh = (uint32_t)G.fh;
-    const bool has_r1 = r0 + 1u < fh;                    // false: the last row of an odd height, left at 255 by the twin
-    const uint32_t plane_elems = fw * fh;
-    uint32_t two = 2u, three = 3u;                       // SDWA shift counts live in registers (display_half)
-    asm("" : "+v"(two), "+v"(three));
-    const uint8_t* yrow = src + (size_t)r0 * G.luma_stride;
-    const uint8_t* cbrow = src + G.cb_off + (size_t)pair * G.chroma_stride;
-    const uint8_t* crrow = src + G.cr_off + (size_t)pair * G.chroma_stride;
-    if (G.fast) {
-        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(dst);
-        if constexpr (DTYPE == kTensorF32) {
-            const uint32_t y0 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(yrow + 4u * col));
-            const uint32_t y1 = has_r1 ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(yrow + G.luma_stride + 4u * col)) : 0u;
-            const uint32_t cb2 = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(cbrow + 2u * col));
-            const uint32_t cr2 = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(crrow + 2u * col));
-            const ChromaTerms c0 = chroma_terms<0>(lut, cb2, cr2, three), c1 = chroma_terms<1>(lut, cb2, cr2, three);
-            const uint32_t off = r0 * fw + 4u * col;
-            tensor_row4_f32(lut, tab_s, y0, c0, c1, !has_r1, rs, off, plane_elems, true, two);
-            tensor_row4_f32(lut, tab_s, y1, c0, c1, false, rs, off + fw, plane_elems, has_r1, two);
-        } else {
-            const v2u y0 = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(yrow + 8u * col));
-            const v2u y1 = has_r1 ? __builtin_nontemporal_load(reinterpret_cast<const v2u*>(yrow + G.luma_stride + 8u * col)) : v2u{0u, 0u};
-            const uint32_t cb4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(cbrow + 4u * col));
-            const uint32_t cr4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(crrow + 4u * col));
-            const ChromaTerms c[4] = {chroma_terms<0>(lut, cb4, cr4, three), chroma_terms<1>(lut, cb4, cr4, three),
-                                      chroma_terms<2>(lut, cb4, cr4, three), chroma_terms<3>(lut, cb4, cr4, three)};
-            const uint32_t off = r0 * fw + 8u * col;
-            tensor_row8<DTYPE>(lut, tab_s, y0, c, !has_r1, rs, off, plane_elems, true, two);
-            tensor_row8<DTYPE>(lut, tab_s, y1, c, false, rs, off + fw, plane_elems, has_r1, two);
-        }
-    } else {
-        const uint32_t y0 = *reinterpret_cast<const uint16_t*>(yrow + 2u * col);
-        const uint32_t y1 = has_r1 ? *reinterpret_cast<const uint16_t*>(yrow + G.luma_stride + 2u * col) : 0u;
-        const ChromaTerms c0 = chroma_terms<0>(lut, (uint32_t)cbrow[col], (uint32_t)crrow[col], three);
-        const int opaque = 255 << kLutShift;
-        uint32_t px[4] = {rgba_px<0>(lut, y0, c0, opaque, two), rgba_px<1>(lut, y0, c0, opaque, two),
-                          rgba_px<0>(lut, y1, c0, opaque, two), rgba_px<1>(lut, y1, c0, opaque, two)};
-        if (!has_r1) px[0] = px[1] = 0xffffffffu;
-        Elem* out = reinterpret_cast<Elem*>(dst);
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            Elem* o = out + (size_t)ch * plane_elems + (size_t)r0 * fw + 2u * col;
-            __builtin_nontemporal_store(tab_s[ch * 256 + ((px[0] >> (8 * ch)) & 255u)], o);
-            __builtin_nontemporal_store(tab_s[ch * 256 + ((px[1] >> (8 * ch)) & 255u)], o + 1);
-            if (has_r1) {
-                __builtin_nontemporal_store(tab_s[ch * 256 + ((px[2] >> (8 * ch)) & 255u)], o + fw);
-                __builtin_nontemporal_store(tab_s[ch * 256 + ((px[3] >> (8 * ch)) & 255u)], o + fw + 1);
-            }
-        }
-    }
-}
-
-// ---- 8-bit elements and the channels-last layout (leon_pipeline.h, leon_pipeline_tensor_format) ---------------------------
-// Every tensor that is not float CHW: uint8 [3][fh][fw], and [fh][fw][3] of 1-, 2- and 4-byte elements.  k_tensor's launch shape,
-// loads and conversion (tensor_px8 / tensor_px4); the element is the colour value itself (1 byte: no table, none in LDS) or the
-// host's table entry (fp16 and bf16 differ in the table only: the kernels are made per element SIZE).  What is new is the store side.
-// Fast path (fw % 8 == 0), a lane holds 8 pixels x 2 rows (4 x 2 of 4-byte elements):
-//   uint8 CHW: 8 bytes per channel and row -- one b64 store, a wave writes 512 contiguous bytes per instruction.
-//   HWC: a lane's row piece is 24 / 48 / 48 contiguous bytes (1- / 2- / 4-byte elements).  Stored from the lane that made it that is
-//     three instructions whose lanes lie 24 or 48 bytes apart, each writing a third of every line it touches (the shape k_tensor's
-//     comment records as measured and dropped for fp32).  So the wave's 64 pieces (1536 B / 3 KB / 3 KB, contiguous in the frame but
-//     for the seam where the wave crosses into the next row pair) change lanes through the wave's LDS strip: written at lane * piece,
-//     read back at (j * 64 + lane) * third-of-a-piece, j = 0 .. 2 -- so store instruction j writes the thirds 64 j .. 64 j + 63 in
-//     order, 64 x 16 B = 1 KB contiguous (64 x 8 B = 512 B for uint8: a third of 24 bytes).  A third never straddles two pieces, so
-//     its address is its source lane's row offset (ds_bpermute) plus 0, 1 or 2 thirds.  LDS banks: pieces of 12 dwords written as
-//     b128 by groups of 8 lanes land on 32 different banks (12 l mod 32, l = 0 .. 7: 0 12 24 4 16 28 8 20, 4 dwords each), pieces of
-//     6 dwords written as b64 by groups of 16 lanes too (6 l mod 32 covers every even bank once); the reads are contiguous.
-//   Rows go one after the other through the same strip (both at once would put the 2- and 4-byte kernels over 20 KB).
-// Other even widths: a lane takes one 2 x 2 quad, element stores (k_tensor's generic path).
-// The tensor's buffer resource ends with the frame: the second row of a lane in the fill row pair of an odd height, and anything a
-// wrong offset would reach behind the frame, is dropped by the bounds check.
-static constexpr int kLayoutChw = 0, kLayoutHwc = 1;          // = LEON_TENSOR_LAYOUT_*
-template <int EB> struct ImageElem { typedef uint8_t type; };
-template <> struct ImageElem<2> { typedef uint16_t type; };
-template <> struct ImageElem<4> { typedef uint32_t type; };
-// pixels per lane and row on the fast path
-constexpr int image_lane_px(int eb) { return eb == 4 ? 4 : 8; }
-// bytes of a lane's row piece in the HWC layout, and of the wave's exchange strip
-constexpr int image_piece_bytes(int eb) { return image_lane_px(eb) * 3 * eb; }
-constexpr int image_strip_bytes(int eb, int layout) { return layout == kLayoutHwc ? 64 * image_piece_bytes(eb) : 0; }
-
 template <int EB>
-__device__ __forceinline__ uint32_t image_elem(const typename ImageElem<EB>::type* tab, uint32_t px, int ch)
+__device__ __forceinline__ uint32_t image_elem(const typename ElemOf<EB>::type* tab, uint32_t px, int ch)
 {
     const uint32_t v = (px >> (8 * ch)) & 255u;
     if constexpr (EB == 1) return v;
     else return tab[ch * 256 + v];
 }
 
+// One row of a lane, CHW: `off` = its first element in a channel plane; in: false stores nothing
+// fp32: 4 pixels -> 16 bytes per channel
+__device__ __forceinline__ void tensor_row4_f32(const uint32_t* tab, const uint32_t (&px)[4], __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_elems, bool in)
+{
+    const uint32_t oob = in ? 0u : kOobBit;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        const v4u e = {image_elem<4>(tab, px[0], ch), image_elem<4>(tab, px[1], ch), image_elem<4>(tab, px[2], ch), image_elem<4>(tab, px[3], ch)};
+        __builtin_amdgcn_raw_buffer_store_b128(e, rs, (int)((((uint32_t)ch * plane_elems + off) * 4u) | oob), 0, kAuxFrameStore);
+    }
+}
+// 16-bit elements: 8 pixels -> 16 bytes per channel
+__device__ __forceinline__ void tensor_row8(const uint16_t* tab, const uint32_t (&px)[8], __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_elems, bool in)
+{
+    const uint32_t oob = in ? 0u : kOobBit;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        uint32_t e[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) e[k] = image_elem<2>(tab, px[k], ch);
+        __builtin_amdgcn_raw_buffer_store_b128(v4u{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)}, rs,
+                                               (int)((((uint32_t)ch * plane_elems + off) * 2u) | oob), 0, kAuxFrameStore);
+    }
+}
+// uint8: 8 pixels -> 8 bytes per channel (`off` may carry kOobBit)
+__device__ __forceinline__ void image_row_chw_u8(const uint32_t (&px)[8], __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_bytes)
+{
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        const int sh = 8 * ch;
+        const uint32_t lo = ((px[0] >> sh) & 255u) | (((px[1] >> sh) & 255u) << 8) | (((px[2] >> sh) & 255u) << 16) | (((px[3] >> sh) & 255u) << 24);
+        const uint32_t hi = ((px[4] >> sh) & 255u) | (((px[5] >> sh) & 255u) << 8) | (((px[6] >> sh) & 255u) << 16) | (((px[7] >> sh) & 255u) << 24);
+        __builtin_amdgcn_raw_buffer_store_b64(v2u{lo, hi}, rs, (int)((uint32_t)ch * plane_bytes + off), 0, kAuxFrameStore);
+    }
+}
+
 // One row piece of a lane, HWC: NPX pixels -> the wave's strip -> three store instructions of contiguous thirds.  `rowoff`: byte offset
 // of this lane's piece in the frame (kOobBit: none); strip: the wave's; lane: 0 .. 63.  All 64 lanes take part.
 template <int EB, int NPX>
-__device__ __forceinline__ void image_row_hwc(const typename ImageElem<EB>::type* tab, const uint32_t (&px)[NPX], char* strip, int lane,
+__device__ __forceinline__ void image_row_hwc(const typename ElemOf<EB>::type* tab, const uint32_t (&px)[NPX], char* strip, int lane,
                                               __amdgpu_buffer_rsrc_t rs, uint32_t rowoff)
 {
     constexpr int kPiece = NPX * 3 * EB, kThird = kPiece / 3;
@@ -1858,30 +1781,17 @@ __device__ __forceinline__ void image_row_hwc(const typename ImageElem<EB>::type
     wave_sync();          // the strip is free for the next row
 }
 
-// One row of a lane, uint8 CHW: 8 pixels -> 8 bytes per channel
-__device__ __forceinline__ void image_row_chw_u8(const uint32_t (&px)[8], __amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t plane_bytes)
-{
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        const int sh = 8 * ch;
-        const uint32_t lo = ((px[0] >> sh) & 255u) | (((px[1] >> sh) & 255u) << 8) | (((px[2] >> sh) & 255u) << 16) | (((px[3] >> sh) & 255u) << 24);
-        const uint32_t hi = ((px[4] >> sh) & 255u) | (((px[5] >> sh) & 255u) << 8) | (((px[6] >> sh) & 255u) << 16) | (((px[7] >> sh) & 255u) << 24);
-        __builtin_amdgcn_raw_buffer_store_b64(v2u{lo, hi}, rs, (int)((uint32_t)ch * plane_bytes + off), 0, kAuxFrameStore);
-    }
-}
-
 template <int EB, int LAYOUT>
-__global__ __launch_bounds__(kRgbaBlock) void k_image(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
-                                                      const uint32_t* __restrict__ table, const Tables* __restrict__ T, TensorGeom G)
+__global__ __launch_bounds__(kRgbaBlock) void k_tensor(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
+                                                       const uint32_t* __restrict__ table, const Tables* __restrict__ T, TensorGeom G)
 {
-    typedef typename ImageElem<EB>::type Elem;
-    constexpr int kNpx = image_lane_px(EB);
+    typedef typename ElemOf<EB>::type Elem;
+    constexpr int kNpx = lane_px(EB);
     constexpr int kStrip = image_strip_bytes(EB, LAYOUT);
-    static_assert(LAYOUT == kLayoutHwc || EB == 1, "float CHW is k_tensor's");
     __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
     __shared__ __attribute__((aligned(16))) Elem tab_s[EB == 1 ? 16 : 3 * 256];
     __shared__ __attribute__((aligned(16))) char strip_s[kStrip ? (kRgbaBlock / 64) * kStrip : 16];
-    {
+    {   // the conversion tables, the element table through registers
         display_lut_to_lds(lut_s, T);
         if constexpr (EB != 1) {
             constexpr int kDwords = 3 * 256 * EB / 4;
@@ -1892,27 +1802,30 @@ __global__ __launch_bounds__(kRgbaBlock) void k_image(const uint8_t* __restrict_
     }
     const uint32_t idx_raw = blockIdx.x * (uint32_t)kRgbaBlock + threadIdx.x;
     const bool valid = idx_raw < G.n_items;
-    const uint32_t idx = valid ? idx_raw : 0u;          // lanes behind the frame load what lane 0 loads and store nothing
+    if constexpr (LAYOUT == kLayoutChw) {
+        if (!valid) return;          // cheaper for the CHW stores: with it `valid` below is a constant
+    }
+    const uint32_t idx = valid ? idx_raw : 0u;          // HWC (the exchange needs all 64 lanes of a wave): lanes behind the frame load what lane 0 loads and store nothing
     const char* lut = reinterpret_cast<const char*>(lut_s);
     const uint32_t pair = idx / G.per_row, col = idx - pair * G.per_row;
     const uint32_t fid = frame_ids[blockIdx.z];
-    const uint8_t* src = planes_ring + (size_t)fid * join64(G.planes_pitch_lo, G.planes_pitch_hi);
-    uint8_t* dst = tensor_ring + (size_t)fid * join64(G.tensor_pitch_lo, G.tensor_pitch_hi);
+    const uint8_t* src = planes_ring + (size_t)fid * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi);
+    uint8_t* dst = tensor_ring + (size_t)fid * join64(G.ring.tensor_pitch_lo, G.ring.tensor_pitch_hi);
     const uint32_t r0 = 2u * pair, fw = (uint32_t)G.fw, fh = (uint32_t)G.fh;
     const bool has_r1 = r0 + 1u < fh;                    // false: the last row of an odd height, left at 255 by the twin
     const uint32_t plane_elems = fw * fh;
     uint32_t two = 2u, three = 3u;                       // SDWA shift counts live in registers (display_half)
     asm("" : "+v"(two), "+v"(three));
-    const uint8_t* yrow = src + (size_t)r0 * G.luma_stride;
-    const uint8_t* cbrow = src + G.cb_off + (size_t)pair * G.chroma_stride;
-    const uint8_t* crrow = src + G.cr_off + (size_t)pair * G.chroma_stride;
+    const uint8_t* yrow = src + (size_t)r0 * G.ring.luma_stride;
+    const uint8_t* cbrow = src + G.ring.cb_off + (size_t)pair * G.ring.chroma_stride;
+    const uint8_t* crrow = src + G.ring.cr_off + (size_t)pair * G.ring.chroma_stride;
     if (G.fast) {
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, (int)(3u * plane_elems * EB), 0x00020000);
         const uint32_t oob = valid ? 0u : kOobBit;
         uint32_t pa[kNpx], pb[kNpx];
         if constexpr (kNpx == 4) {
             const uint32_t y0 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(yrow + 4u * col));
-            const uint32_t y1 = has_r1 ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(yrow + G.luma_stride + 4u * col)) : 0u;
+            const uint32_t y1 = has_r1 ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(yrow + G.ring.luma_stride + 4u * col)) : 0u;
             const uint32_t cb2 = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(cbrow + 2u * col));
             const uint32_t cr2 = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(crrow + 2u * col));
             const ChromaTerms c0 = chroma_terms<0>(lut, cb2, cr2, three), c1 = chroma_terms<1>(lut, cb2, cr2, three);
@@ -1920,7 +1833,7 @@ __global__ __launch_bounds__(kRgbaBlock) void k_image(const uint8_t* __restrict_
             tensor_px4(lut, y1, c0, c1, false, two, pb);
         } else {
             const v2u y0 = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(yrow + 8u * col));
-            const v2u y1 = has_r1 ? __builtin_nontemporal_load(reinterpret_cast<const v2u*>(yrow + G.luma_stride + 8u * col)) : v2u{0u, 0u};
+            const v2u y1 = has_r1 ? __builtin_nontemporal_load(reinterpret_cast<const v2u*>(yrow + G.ring.luma_stride + 8u * col)) : v2u{0u, 0u};
             const uint32_t cb4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(cbrow + 4u * col));
             const uint32_t cr4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(crrow + 4u * col));
             const ChromaTerms c[4] = {chroma_terms<0>(lut, cb4, cr4, three), chroma_terms<1>(lut, cb4, cr4, three),
@@ -1935,13 +1848,19 @@ __global__ __launch_bounds__(kRgbaBlock) void k_image(const uint8_t* __restrict_
             const uint32_t rowoff = (off * 3u * EB) | oob;
             image_row_hwc<EB, kNpx>(tab_s, pa, strip, lane, rs, rowoff);
             image_row_hwc<EB, kNpx>(tab_s, pb, strip, lane, rs, rowoff + fw * 3u * EB);          // (behind the frame without a second row)
+        } else if constexpr (EB == 4) {
+            tensor_row4_f32(tab_s, pa, rs, off, plane_elems, valid);
+            tensor_row4_f32(tab_s, pb, rs, off + fw, plane_elems, valid && has_r1);
+        } else if constexpr (EB == 2) {
+            tensor_row8(tab_s, pa, rs, off, plane_elems, valid);
+            tensor_row8(tab_s, pb, rs, off + fw, plane_elems, valid && has_r1);
         } else {
             image_row_chw_u8(pa, rs, off | oob, plane_elems);
             image_row_chw_u8(pb, rs, (off + fw) | (valid && has_r1 ? 0u : kOobBit), plane_elems);
         }
     } else if (valid) {
         const uint32_t y0 = *reinterpret_cast<const uint16_t*>(yrow + 2u * col);
-        const uint32_t y1 = has_r1 ? *reinterpret_cast<const uint16_t*>(yrow + G.luma_stride + 2u * col) : 0u;
+        const uint32_t y1 = has_r1 ? *reinterpret_cast<const uint16_t*>(yrow + G.ring.luma_stride + 2u * col) : 0u;
         const ChromaTerms c0 = chroma_terms<0>(lut, (uint32_t)cbrow[col], (uint32_t)crrow[col], three);
         const int opaque = 255 << kLutShift;
         uint32_t px[4] = {rgba_px<0>(lut, y0, c0, opaque, two), rgba_px<1>(lut, y0, c0, opaque, two),
@@ -1978,8 +1897,8 @@ __global__ __launch_bounds__(kRgbaBlock) void k_image(const uint8_t* __restrict_
 // (kOobBit) and never tapped; the last row of an odd height is the CPU twin's fill row, 255.
 // The filter (LEON_RESIZE_*) is a traits struct: what the LDS is sized for and the sign of the arithmetic.  Triangle weights are
 // never negative; bicubic ones are (down to about -0.074 * 2^22), so its sums are signed -- v_mad_i32_i24, an arithmetic shift and
-// a clamp on both sides (v_med3_i32) -- and its support of 2 doubles the taps: k_cubic / k_cubic_packed are instantiations of their
-// own, and the triangle kernels are compiled exactly as they were.
+// a clamp on both sides (v_med3_i32) -- and its support of 2 doubles the taps: k_resample<EB, LAYOUT, F> is instantiated per filter,
+// and the triangle kernels are compiled exactly as they were before there was a second one.
 static constexpr int kResTileX = 32, kResTileY = 8;          // kResTileX * kResTileY = kRgbaBlock: the vertical pass is one pixel per lane
 static constexpr int kResStagePx = 4096;                     // staging dwords: 6 rows of the widest footprint (triangle: 31 * 16 + 33 + 14 <= 544 columns, 578 dwords
                                                              // padded; bicubic: 31 * 16 + 65 + 14 <= 576 columns, 612 dwords padded)
@@ -2000,8 +1919,7 @@ struct ResampleGeom {
     int32_t fw, fh, ow, oh;
     int32_t taps_x, taps_y;              // row length of the weight tables
     uint32_t off_cx, off_wx, off_fy, off_cy, off_wy;          // int32 offsets in the table buffer (first_x at 0)
-    uint32_t luma_stride, chroma_stride, cb_off, cr_off;      // FrameOut
-    uint32_t planes_pitch_lo, planes_pitch_hi, tensor_pitch_lo, tensor_pitch_hi;      // bytes between ring frames
+    RingGeom ring;
 };
 
 // Column c of a staged row lies at dword c + (c >> 4): the horizontal pass's lanes are the tile's output columns and read columns
@@ -2022,8 +1940,8 @@ __device__ __forceinline__ uint32_t resample_px(int32_t ar, int32_t ag, int32_t 
 __device__ __forceinline__ uint32_t resample_mad(int32_t w, uint32_t sample, uint32_t acc) { return __umul24((uint32_t)w, sample) + acc; }
 __device__ __forceinline__ int32_t resample_mad(int32_t w, uint32_t sample, int32_t acc) { return __mul24(w, (int32_t)sample) + acc; }
 
-// The whole of a workgroup's work, for k_resample (EB = 2 or 4, CHW: one element store per lane and channel) and for k_image_scaled
-// (8-bit elements, the channels-last layout).  The latter's tile leaves through LDS: once the vertical pass has read them the h rows
+// Two store forms.  Float CHW (EB = 2 or 4): one element store per lane and channel.  8-bit elements and the channels-last layout
+// (leon_pipeline_tensor_format with leon_pipeline_tensor_resize): the tile leaves through LDS: once the vertical pass has read them the h rows
 // are dead, and the tile's elements are packed there in memory order -- HWC: the 8 tile rows, 96 elements each; uint8 CHW: 3 x 8
 // channel rows of 32 bytes -- every row at the offset its first byte has in its 16-byte line of the frame (the tensor starts on a
 // 256-byte boundary).  A lane then takes one aligned 16-byte line of one row: inside the row it is ONE b128 store, at the row's two
@@ -2033,7 +1951,7 @@ __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes
                                               const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
                                               const ResampleGeom& G)
 {
-    typedef typename ImageElem<EB>::type Elem;
+    typedef typename ElemOf<EB>::type Elem;
     typedef typename F::Acc Acc;
     static_assert(kResTileX * kResTileY == kRgbaBlock && kResTileX == 32, "lane = (tid & 31, tid >> 5)");
     __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
@@ -2077,12 +1995,11 @@ __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes
 
     const char* lut = reinterpret_cast<const char*>(lut_s);
     const uint32_t fid = frame_ids[blockIdx.z];
-    const uint8_t* src = planes_ring + (size_t)fid * join64(G.planes_pitch_lo, G.planes_pitch_hi);
-    uint8_t* dst = tensor_ring + (size_t)fid * join64(G.tensor_pitch_lo, G.tensor_pitch_hi);
+    const uint8_t* src = planes_ring + (size_t)fid * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi);
+    uint8_t* dst = tensor_ring + (size_t)fid * join64(G.ring.tensor_pitch_lo, G.ring.tensor_pitch_hi);
     const __amdgpu_buffer_rsrc_t prs = buf_rsrc(src);
     uint32_t two = 2u, three = 3u;                       // SDWA shift counts live in registers (display_half)
     asm("" : "+v"(two), "+v"(three));
-    const int opaque = 255 << kLutShift;
     const int o = tid & 31, sub = tid >> 5;
 
     for (int r = ry0; r < ry1; r += rc) {
@@ -2092,26 +2009,17 @@ __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes
         for (int pair = pair_t, col = col_t; pair < n_pairs;) {
             const int row = r + 2 * pair;
             const bool in0 = row < G.fh, in1 = row + 1 < G.fh;
-            const uint32_t yo = (uint32_t)row * G.luma_stride + (uint32_t)(cx0 + 8 * col);
-            const uint32_t co = (uint32_t)(row >> 1) * G.chroma_stride + (uint32_t)((cx0 >> 1) + 4 * col);
+            const uint32_t yo = (uint32_t)row * G.ring.luma_stride + (uint32_t)(cx0 + 8 * col);
+            const uint32_t co = (uint32_t)(row >> 1) * G.ring.chroma_stride + (uint32_t)((cx0 >> 1) + 4 * col);
             const v2u y0 = __builtin_amdgcn_raw_buffer_load_b64(prs, (int)(in0 ? yo : kOobBit), 0, kAuxStreamOnce);
-            const v2u y1 = __builtin_amdgcn_raw_buffer_load_b64(prs, (int)(in1 ? yo + G.luma_stride : kOobBit), 0, kAuxStreamOnce);
-            const uint32_t cb4 = __builtin_amdgcn_raw_buffer_load_b32(prs, (int)(in0 ? G.cb_off + co : kOobBit), 0, kAuxStreamOnce);
-            const uint32_t cr4 = __builtin_amdgcn_raw_buffer_load_b32(prs, (int)(in0 ? G.cr_off + co : kOobBit), 0, kAuxStreamOnce);
+            const v2u y1 = __builtin_amdgcn_raw_buffer_load_b64(prs, (int)(in1 ? yo + G.ring.luma_stride : kOobBit), 0, kAuxStreamOnce);
+            const uint32_t cb4 = __builtin_amdgcn_raw_buffer_load_b32(prs, (int)(in0 ? G.ring.cb_off + co : kOobBit), 0, kAuxStreamOnce);
+            const uint32_t cr4 = __builtin_amdgcn_raw_buffer_load_b32(prs, (int)(in0 ? G.ring.cr_off + co : kOobBit), 0, kAuxStreamOnce);
             const ChromaTerms c[4] = {chroma_terms<0>(lut, cb4, cr4, three), chroma_terms<1>(lut, cb4, cr4, three),
                                       chroma_terms<2>(lut, cb4, cr4, three), chroma_terms<3>(lut, cb4, cr4, three)};
-            uint32_t a[8] = {rgba_px<0>(lut, y0.x, c[0], opaque, two), rgba_px<1>(lut, y0.x, c[0], opaque, two),
-                             rgba_px<2>(lut, y0.x, c[1], opaque, two), rgba_px<3>(lut, y0.x, c[1], opaque, two),
-                             rgba_px<0>(lut, y0.y, c[2], opaque, two), rgba_px<1>(lut, y0.y, c[2], opaque, two),
-                             rgba_px<2>(lut, y0.y, c[3], opaque, two), rgba_px<3>(lut, y0.y, c[3], opaque, two)};
-            const uint32_t b[8] = {rgba_px<0>(lut, y1.x, c[0], opaque, two), rgba_px<1>(lut, y1.x, c[0], opaque, two),
-                                   rgba_px<2>(lut, y1.x, c[1], opaque, two), rgba_px<3>(lut, y1.x, c[1], opaque, two),
-                                   rgba_px<0>(lut, y1.y, c[2], opaque, two), rgba_px<1>(lut, y1.y, c[2], opaque, two),
-                                   rgba_px<2>(lut, y1.y, c[3], opaque, two), rgba_px<3>(lut, y1.y, c[3], opaque, two)};
-            if (!in1) {                                  // the last row of an odd height: left at 255 by the twin
-#pragma unroll
-                for (int k = 0; k < 8; k++) a[k] = 0xffffffffu;
-            }
+            uint32_t a[8], b[8];
+            tensor_px8(lut, y0, c, !in1, two, a);        // (!in1: the last row of an odd height, left at 255 by the twin)
+            tensor_px8(lut, y1, c, false, two, b);
             uint32_t* s0 = stage_s + (2 * pair) * swp + resample_col(8 * col);            // (8 columns of one group of 16: contiguous)
 #pragma unroll
             for (int k = 0; k < 8; k++) { s0[k] = a[k]; s0[swp + k] = b[k]; }
@@ -2213,39 +2121,13 @@ __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes
     }
 }
 
-template <int DTYPE>
+
+template <int EB, int LAYOUT, class F>
 __global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
                                                          const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
                                                          ResampleGeom G)
 {
-    resample_body<(int)sizeof(typename TensorElem<DTYPE>::type), kLayoutChw, ResTriangle>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
-}
-
-// 8-bit elements and / or the channels-last layout at a model's input size (leon_pipeline_tensor_format with leon_pipeline_tensor_resize)
-template <int EB, int LAYOUT>
-__global__ __launch_bounds__(kRgbaBlock) void k_image_scaled(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
-                                                             const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
-                                                             ResampleGeom G)
-{
-    static_assert(LAYOUT == kLayoutHwc || EB == 1, "float CHW is k_resample's");
-    resample_body<EB, LAYOUT, ResTriangle>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
-}
-
-// The same two kernels with the bicubic filter (LEON_RESIZE_BICUBIC): up to 65 signed taps an axis
-template <int DTYPE>
-__global__ __launch_bounds__(kRgbaBlock) void k_cubic(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
-                                                      const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
-                                                      ResampleGeom G)
-{
-    resample_body<(int)sizeof(typename TensorElem<DTYPE>::type), kLayoutChw, ResCubic>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
-}
-template <int EB, int LAYOUT>
-__global__ __launch_bounds__(kRgbaBlock) void k_cubic_packed(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
-                                                             const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
-                                                             ResampleGeom G)
-{
-    static_assert(LAYOUT == kLayoutHwc || EB == 1, "float CHW is k_cubic's");
-    resample_body<EB, LAYOUT, ResCubic>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
+    resample_body<EB, LAYOUT, F>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

@@ -122,7 +122,7 @@ struct leon_pipeline {
     // output TENSOR: the ring of [3][fh][fw] tensors (tensor_pitch apart), the element table T (host, device), and per ring entry
     // the frame indices of its window for k_tensor (pinned, device)
     uint8_t* d_tensor = nullptr;
-    int tensor_dtype = 0, tensor_layout = 0;          // LEON_TENSOR_*, LEON_TENSOR_LAYOUT_* (float CHW: k_tensor / k_resample; the rest: k_image / k_image_scaled)
+    int tensor_dtype = 0, tensor_layout = 0;          // LEON_TENSOR_*, LEON_TENSOR_LAYOUT_* (which k_tensor / k_resample: by element bytes and layout)
     size_t tensor_elem = 0, tensor_bytes = 0, tensor_pitch = 0;
     std::vector<uint8_t> tensor_table;
     uint32_t* d_tensor_table = nullptr;
@@ -133,7 +133,7 @@ struct leon_pipeline {
     leon_pipeline_tensor_geometry tensor_geom{};
     std::vector<int32_t> resize_tabs;
     leon::ResampleGeom resample_geom{};
-    int32_t resize_filter = LEON_RESIZE_TRIANGLE;      // which kernels: k_resample / k_image_scaled, or k_cubic / k_cubic_packed
+    int32_t resize_filter = LEON_RESIZE_TRIANGLE;      // LEON_RESIZE_*: which k_resample
     int32_t* d_resize_tabs = nullptr;
     bool gpu_parser = false;
     // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
@@ -668,7 +668,7 @@ int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
     int32_t* t = p->resize_tabs.data();
     if ((rc = resize_axis_build("width", fw, g.crop_x, g.crop_width, g.width, rz->filter, t, t + G.off_cx, t + G.off_wx, G.taps_x, nullptr)) != LEON_OK) return rc;
     if ((rc = resize_axis_build("height", fh, g.crop_y, g.crop_height, g.height, rz->filter, t + G.off_fy, t + G.off_cy, t + G.off_wy, g.taps_y, nullptr)) != LEON_OK) return rc;
-    // What the kernel's LDS is sized for (k_resample's, or k_cubic's for the bicubic filter).  Within the limits above neither check can
+    // What the kernel's LDS is sized for (by filter: ResTriangle, ResCubic).  Within the limits above neither check can
     // fail (at most 544 columns and 147 rows, bicubic 576 and 179: leon_kernels.h has the arithmetic); they stand guard for the kernel's chunk loop, which needs at least one row pair per chunk
     // (rc >= 2) to advance, should a limit ever be widened without the kernel.
     for (int32_t o = 0; o < g.width; o += leon::kResTileX) {
@@ -1096,51 +1096,34 @@ void list_frames(leon_pipeline* p, PipeWindow* w)
     p->st_gops += w->jobs.size();
 }
 
-// output TENSOR: the window's frames -> their tensors, one k_tensor launch on the decoder's stream behind the last level (at most
-// 65535 frames per launch: blockIdx.z).  Pictures decoded for prediction only (EXACT seek) are not among the frames.
-template <int DTYPE>
-void launch_k_tensor(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::TensorGeom& G)
+// output TENSOR: the window's frames -> their tensors, one launch on the decoder's stream behind the last level (at most 65535 frames
+// per launch: blockIdx.z).  Pictures decoded for prediction only (EXACT seek) are not among the frames.
+// The kernels by element bytes (1, 2, 4 -> 0, 1, 2) and layout: k_tensor at the frame's size, k_resample at a model's input size, by
+// filter as well (no entry: no such filter -- create refuses it).
+typedef void (*TensorKernel)(const uint8_t*, uint8_t*, const uint32_t*, const uint32_t*, const leon::Tables*, leon::TensorGeom);
+typedef void (*ResampleKernel)(const uint8_t*, uint8_t*, const uint32_t*, const uint32_t*, const leon::Tables*, const int32_t*, leon::ResampleGeom);
+static_assert(leon::kLayoutChw == LEON_TENSOR_LAYOUT_CHW && leon::kLayoutHwc == LEON_TENSOR_LAYOUT_HWC, "the tables' layout index is LEON_TENSOR_LAYOUT_*");
+static_assert(LEON_RESIZE_TRIANGLE == 0 && LEON_RESIZE_BICUBIC == 3, "kResampleKernels is indexed by LEON_RESIZE_*");
+constexpr TensorKernel kTensorKernels[3][2] = {{leon::k_tensor<1, leon::kLayoutChw>, leon::k_tensor<1, leon::kLayoutHwc>},
+                                               {leon::k_tensor<2, leon::kLayoutChw>, leon::k_tensor<2, leon::kLayoutHwc>},
+                                               {leon::k_tensor<4, leon::kLayoutChw>, leon::k_tensor<4, leon::kLayoutHwc>}};
+struct ResampleKernelsOfFilter { ResampleKernel k[3][2]; };
+template <class F> constexpr ResampleKernelsOfFilter kResampleKernelsOf = {{{leon::k_resample<1, leon::kLayoutChw, F>, leon::k_resample<1, leon::kLayoutHwc, F>},
+                                                                            {leon::k_resample<2, leon::kLayoutChw, F>, leon::k_resample<2, leon::kLayoutHwc, F>},
+                                                                            {leon::k_resample<4, leon::kLayoutChw, F>, leon::k_resample<4, leon::kLayoutHwc, F>}}};
+constexpr ResampleKernelsOfFilter kResampleKernels[4] = {kResampleKernelsOf<leon::ResTriangle>, {}, {}, kResampleKernelsOf<leon::ResCubic>};
+
+// where the kernels find a frame's planes and its tensor
+leon::RingGeom ring_geom(const leon_pipeline* p)
 {
-    hipLaunchKernelGGL(leon::k_tensor<DTYPE>, dim3((G.n_items + leon::kRgbaBlock - 1) / leon::kRgbaBlock, 1, n), dim3(leon::kRgbaBlock), 0, p->dec->stream,
-                       (const uint8_t*)p->d_planes, p->d_tensor, ids, (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, G);
+    leon::RingGeom g{};
+    g.luma_stride = p->planes_geom.luma_stride; g.chroma_stride = p->planes_geom.chroma_stride;
+    g.cb_off = p->planes_geom.cb_off; g.cr_off = p->planes_geom.cr_off;
+    g.planes_pitch_lo = (uint32_t)(p->planes_bytes & 0xffffffffu); g.planes_pitch_hi = (uint32_t)((uint64_t)p->planes_bytes >> 32);
+    g.tensor_pitch_lo = (uint32_t)(p->tensor_pitch & 0xffffffffu); g.tensor_pitch_hi = (uint32_t)((uint64_t)p->tensor_pitch >> 32);
+    return g;
 }
-// ... at a model's input size: k_resample in k_tensor's place, a workgroup per tile of kResTileX x kResTileY output pixels
-template <int DTYPE>
-void launch_k_resample(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::ResampleGeom& G)
-{
-    const dim3 grid((unsigned)((G.ow + leon::kResTileX - 1) / leon::kResTileX), (unsigned)((G.oh + leon::kResTileY - 1) / leon::kResTileY), n);
-    hipLaunchKernelGGL(leon::k_resample<DTYPE>, grid, dim3(leon::kRgbaBlock), 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, ids,
-                       (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, G);
-}
-// ... every combination but float CHW: 8-bit elements and / or the channels-last layout (k_image, k_image_scaled)
-template <int EB, int LAYOUT>
-void launch_k_image(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::TensorGeom& G)
-{
-    hipLaunchKernelGGL((leon::k_image<EB, LAYOUT>), dim3((G.n_items + leon::kRgbaBlock - 1) / leon::kRgbaBlock, 1, n), dim3(leon::kRgbaBlock), 0, p->dec->stream,
-                       (const uint8_t*)p->d_planes, p->d_tensor, ids, (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, G);
-}
-template <int EB, int LAYOUT>
-void launch_k_image_scaled(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::ResampleGeom& G)
-{
-    const dim3 grid((unsigned)((G.ow + leon::kResTileX - 1) / leon::kResTileX), (unsigned)((G.oh + leon::kResTileY - 1) / leon::kResTileY), n);
-    hipLaunchKernelGGL((leon::k_image_scaled<EB, LAYOUT>), grid, dim3(leon::kRgbaBlock), 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, ids,
-                       (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, G);
-}
-// ... and the bicubic filter's instantiations of both (k_cubic, k_cubic_packed)
-template <int DTYPE>
-void launch_k_cubic(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::ResampleGeom& G)
-{
-    const dim3 grid((unsigned)((G.ow + leon::kResTileX - 1) / leon::kResTileX), (unsigned)((G.oh + leon::kResTileY - 1) / leon::kResTileY), n);
-    hipLaunchKernelGGL(leon::k_cubic<DTYPE>, grid, dim3(leon::kRgbaBlock), 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, ids,
-                       (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, G);
-}
-template <int EB, int LAYOUT>
-void launch_k_cubic_packed(const leon_pipeline* p, const uint32_t* ids, unsigned n, const leon::ResampleGeom& G)
-{
-    const dim3 grid((unsigned)((G.ow + leon::kResTileX - 1) / leon::kResTileX), (unsigned)((G.oh + leon::kResTileY - 1) / leon::kResTileY), n);
-    hipLaunchKernelGGL((leon::k_cubic_packed<EB, LAYOUT>), grid, dim3(leon::kRgbaBlock), 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, ids,
-                       (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, G);
-}
+
 int launch_tensors(leon_pipeline* p, const PipeWindow* w)
 {
     const size_t n = w->frame_ids.size();
@@ -1150,57 +1133,34 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
     uint32_t* dv = p->d_tensor_ids + (size_t)w->ring * entry;
     for (size_t i = 0; i < n; i++) h[i] = (uint32_t)((size_t)w->ring * entry) + w->frame_ids[i];
     HIP_TRY(hipMemcpyAsync(dv, h, n * 4, hipMemcpyHostToDevice, p->dec->stream));
-    const bool hwc = p->tensor_layout == LEON_TENSOR_LAYOUT_HWC;
-    const bool image = hwc || p->tensor_dtype == LEON_TENSOR_U8;          // not k_tensor's / k_resample's
-    if (p->tensor_geom.resized) {
-        leon::ResampleGeom R = p->resample_geom;
-        R.luma_stride = p->planes_geom.luma_stride; R.chroma_stride = p->planes_geom.chroma_stride;
-        R.cb_off = p->planes_geom.cb_off; R.cr_off = p->planes_geom.cr_off;
-        R.planes_pitch_lo = (uint32_t)(p->planes_bytes & 0xffffffffu); R.planes_pitch_hi = (uint32_t)((uint64_t)p->planes_bytes >> 32);
-        R.tensor_pitch_lo = (uint32_t)(p->tensor_pitch & 0xffffffffu); R.tensor_pitch_hi = (uint32_t)((uint64_t)p->tensor_pitch >> 32);
-        for (size_t at = 0; at < n; at += 65535) {
-            const unsigned m = (unsigned)std::min<size_t>(65535, n - at);
-            if (p->resize_filter == LEON_RESIZE_BICUBIC) {
-                if (image) {
-                    if (p->tensor_elem == 1 && !hwc) launch_k_cubic_packed<1, leon::kLayoutChw>(p, dv + at, m, R);
-                    else if (p->tensor_elem == 1) launch_k_cubic_packed<1, leon::kLayoutHwc>(p, dv + at, m, R);
-                    else if (p->tensor_elem == 2) launch_k_cubic_packed<2, leon::kLayoutHwc>(p, dv + at, m, R);
-                    else launch_k_cubic_packed<4, leon::kLayoutHwc>(p, dv + at, m, R);
-                } else if (p->tensor_dtype == LEON_TENSOR_F16) launch_k_cubic<leon::kTensorF16>(p, dv + at, m, R);
-                else if (p->tensor_dtype == LEON_TENSOR_BF16) launch_k_cubic<leon::kTensorBf16>(p, dv + at, m, R);
-                else launch_k_cubic<leon::kTensorF32>(p, dv + at, m, R);
-            } else if (image) {
-                if (p->tensor_elem == 1 && !hwc) launch_k_image_scaled<1, leon::kLayoutChw>(p, dv + at, m, R);
-                else if (p->tensor_elem == 1) launch_k_image_scaled<1, leon::kLayoutHwc>(p, dv + at, m, R);
-                else if (p->tensor_elem == 2) launch_k_image_scaled<2, leon::kLayoutHwc>(p, dv + at, m, R);
-                else launch_k_image_scaled<4, leon::kLayoutHwc>(p, dv + at, m, R);
-            } else if (p->tensor_dtype == LEON_TENSOR_F16) launch_k_resample<leon::kTensorF16>(p, dv + at, m, R);
-            else if (p->tensor_dtype == LEON_TENSOR_BF16) launch_k_resample<leon::kTensorBf16>(p, dv + at, m, R);
-            else launch_k_resample<leon::kTensorF32>(p, dv + at, m, R);
-        }
-        HIP_TRY(hipGetLastError());
-        return LEON_OK;
-    }
+    const bool resized = p->tensor_geom.resized != 0;
+    const int eb = (int)p->tensor_elem, layout = p->tensor_layout, filter = p->resize_filter;
     leon::TensorGeom G{};
-    G.fw = p->vinfo.frame_width; G.fh = p->vinfo.frame_height;
-    G.fast = (G.fw & 7) == 0;
-    G.per_row = (uint32_t)(G.fast ? G.fw / (image ? leon::image_lane_px((int)p->tensor_elem) : leon::tensor_lane_px(p->tensor_dtype)) : G.fw / 2);
-    G.n_items = G.per_row * (uint32_t)((G.fh + 1) / 2);
-    G.luma_stride = p->planes_geom.luma_stride; G.chroma_stride = p->planes_geom.chroma_stride;
-    G.cb_off = p->planes_geom.cb_off; G.cr_off = p->planes_geom.cr_off;
-    G.planes_pitch_lo = (uint32_t)(p->planes_bytes & 0xffffffffu); G.planes_pitch_hi = (uint32_t)((uint64_t)p->planes_bytes >> 32);
-    G.tensor_pitch_lo = (uint32_t)(p->tensor_pitch & 0xffffffffu); G.tensor_pitch_hi = (uint32_t)((uint64_t)p->tensor_pitch >> 32);
-    if (!G.n_items) return LEON_OK;
+    leon::ResampleGeom R = p->resample_geom;
+    unsigned gx, gy = 1;
+    if (resized) {          // a workgroup per tile of kResTileX x kResTileY output pixels
+        R.ring = ring_geom(p);
+        gx = (unsigned)((R.ow + leon::kResTileX - 1) / leon::kResTileX);
+        gy = (unsigned)((R.oh + leon::kResTileY - 1) / leon::kResTileY);
+    } else {                // lanes numbered linearly through the frame
+        G.fw = p->vinfo.frame_width; G.fh = p->vinfo.frame_height;
+        G.fast = (G.fw & 7) == 0;
+        G.per_row = (uint32_t)(G.fast ? G.fw / leon::lane_px(eb) : G.fw / 2);
+        G.n_items = G.per_row * (uint32_t)((G.fh + 1) / 2);
+        G.ring = ring_geom(p);
+        if (!G.n_items) return LEON_OK;
+        gx = (G.n_items + leon::kRgbaBlock - 1) / leon::kRgbaBlock;
+    }
+    const bool listed = (eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc) && filter >= 0 && filter < 4;
+    const TensorKernel kt = listed && !resized ? kTensorKernels[eb >> 1][layout] : nullptr;
+    const ResampleKernel kr = listed && resized ? kResampleKernels[filter].k[eb >> 1][layout] : nullptr;
+    if (!kt && !kr) return fail(LEON_ERR_INVALID, "tensor: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
     for (size_t at = 0; at < n; at += 65535) {
-        const unsigned m = (unsigned)std::min<size_t>(65535, n - at);
-        if (image) {
-            if (p->tensor_elem == 1 && !hwc) launch_k_image<1, leon::kLayoutChw>(p, dv + at, m, G);
-            else if (p->tensor_elem == 1) launch_k_image<1, leon::kLayoutHwc>(p, dv + at, m, G);
-            else if (p->tensor_elem == 2) launch_k_image<2, leon::kLayoutHwc>(p, dv + at, m, G);
-            else launch_k_image<4, leon::kLayoutHwc>(p, dv + at, m, G);
-        } else if (p->tensor_dtype == LEON_TENSOR_F16) launch_k_tensor<leon::kTensorF16>(p, dv + at, m, G);
-        else if (p->tensor_dtype == LEON_TENSOR_BF16) launch_k_tensor<leon::kTensorBf16>(p, dv + at, m, G);
-        else launch_k_tensor<leon::kTensorF32>(p, dv + at, m, G);
+        const dim3 grid(gx, gy, (unsigned)std::min<size_t>(65535, n - at)), block(leon::kRgbaBlock);
+        if (resized) hipLaunchKernelGGL(kr, grid, block, 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, (const uint32_t*)(dv + at),
+                                        (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, R);
+        else hipLaunchKernelGGL(kt, grid, block, 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, (const uint32_t*)(dv + at),
+                                (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, G);
     }
     HIP_TRY(hipGetLastError());
     return LEON_OK;

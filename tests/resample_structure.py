@@ -1,6 +1,6 @@
 """The structure of resample_body (csrc/leon_kernels.h) and plan_resize (csrc/leon_pipeline_impl.h), stated on the CPU: what a 32 x 8
 tile derives from the tables of leon_ctypes.resize_weights -- staged footprint, chunks, seams, the fill row -- and what the packed store
-of k_image_scaled / k_cubic_packed makes of a tile row: its start class, its bytes, the 16-byte lines that leave as one b128 store and
+of k_resample makes of a tile row: its start class, its bytes, the 16-byte lines that leave as one b128 store and
 those that leave element by element.  The expressions are the kernel's, line for line; nothing here touches a device.
 
 CASES is the list of geometries tests/test_resample_structure.py (the facts) and tests/test_resample_structure_gpu.py (the kernels) share:
@@ -25,7 +25,7 @@ STREAMS = {
     "608x57": (608, 64, [3, 6], 60857, (608, 57)),
     "100x57": (112, 64, [3, 6], 10057, (100, 57)),
 }
-# (element bytes, layout) of the packed store: k_image_scaled / k_cubic_packed <1, chw>, <1, hwc>, <2, hwc>, <4, hwc>
+# (element bytes, layout) of the packed store: k_resample<1, chw>, <1, hwc>, <2, hwc>, <4, hwc>, either filter
 PACKED = [(1, "chw"), (1, "hwc"), (2, "hwc"), (4, "hwc")]
 
 

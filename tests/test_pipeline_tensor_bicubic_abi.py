@@ -2,18 +2,15 @@
 an axis computed on the host: leon_pipeline_resize_weights(filter 3) must equal leon_ctypes.resize_weights(filter=3), the Python
 statement of the same definition, entry for entry, and the triangle tables must be what they were.  Where Pillow is installed it is an
 independent witness: leon_ctypes.resize_rgb(filter=3) equals Image.resize(size, BICUBIC, box, reducing_gap=None) and filter 0 equals
-BILINEAR, 0 differing bytes.  The seven bicubic kernels exist, spill nothing and leave room for two workgroups per CU."""
+BILINEAR, 0 differing bytes.  (The bicubic kernels' resources: test_tensor_kernel_resources.py.)"""
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from helpers import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # (in_size, crop_start, crop_size, out_size)
 AXES = [(96, 0, 96, 40), (96, 3, 80, 7), (352, 0, 352, 22), (96, 0, 96, 150), (30, 0, 30, 30)]
@@ -156,18 +153,6 @@ def test_resize_rgb_equals_pillow(L, geometry, filt):
         assert int((got != ref).sum()) == 0, "%d bytes differ from Pillow %s" % (int((got != ref).sum()), PIL.__version__)
         if filt == 0:
             assert np.array_equal(got, L.resize_rgb(img, crop, (oh, ow)))
-
-
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
-def test_bicubic_kernels_exist_spill_nothing_and_fit_two_per_cu():
-    import kernel_resources
-    rep = kernel_resources.report()
-    ks = {n: v for n, v in rep.items() if "k_cubic" in n}
-    assert len(ks) == 7, sorted(ks)          # k_cubic: fp16, bf16, fp32; k_cubic_packed: uint8 CHW, HWC of 1, 2 and 4 bytes
-    assert len([n for n in ks if "k_cubic_packed" in n]) == 4
-    for name, v in ks.items():
-        assert v["scratch"] == 0, "%s spills %d bytes per lane" % (name, v["scratch"])
-        assert 0 < v["lds"] <= 80 * 1024, "%s: %d bytes of LDS" % (name, v["lds"])
 
 
 def test_tile_footprint_stays_inside_the_lds_at_ratio_16(L):

@@ -1,5 +1,5 @@
-"""GPU: the resized tensor output with the bicubic filter (LEON_RESIZE_BICUBIC, include/leon_pipeline.h) -- k_cubic for float CHW
-tensors, k_cubic_packed for 8-bit elements and the channels-last layout: up to 65 signed taps an axis, both 8-bit results clamped to
+"""GPU: the resized tensor output with the bicubic filter (LEON_RESIZE_BICUBIC, include/leon_pipeline.h) -- k_resample<..., ResCubic>, for float CHW
+tensors and for 8-bit elements and the channels-last layout: up to 65 signed taps an axis, both 8-bit results clamped to
 0 .. 255.  Expected = T[c][resize_rgb(ORACLE RGBA, crop, size, filter=3)]: the oracle's RGBA through the numpy statement of the two
 integer passes and the element table; compared as bit patterns, no tolerance."""
 import numpy as np

@@ -1,5 +1,5 @@
 """GPU: 8-bit tensor elements and the channels-last layout (include/leon_pipeline.h, LEON_TENSOR_U8 / leon_pipeline_tensor_format) --
-k_image at frame size, k_image_scaled at a model's input size.  Expected values come from the ORACLE's RGBA alone: uint8 tensors are
+k_tensor<element bytes, layout> at frame size, k_resample<element bytes, layout, filter> at a model's input size.  Expected values come from the ORACLE's RGBA alone: uint8 tensors are
 its bytes [..., :3] (moved to [3, H, W] for CHW), float HWC tensors the table T (leon_ctypes.tensor_table) looked up with them, resized
 ones leon_ctypes.resize_rgb of them first.  Compared as bit patterns, no tolerance."""
 import os
@@ -14,7 +14,7 @@ from test_pipeline_planes_gpu import FIXTURES, assert_planes, oracle_planes
 pytestmark = pytest.mark.gpu
 
 PARSERS = pytest.mark.parametrize("gpu_parser", [True, False], ids=["gpu-parser", "host-parser"])
-# the combinations k_tensor / k_resample do not serve
+# every combination but float CHW (test_pipeline_tensor_gpu.py, test_pipeline_tensor_resize_gpu.py)
 FORMATS = [("uint8", "chw"), ("uint8", "hwc"), ("float16", "hwc"), ("bfloat16", "hwc"), ("float32", "hwc")]
 FORMAT = pytest.mark.parametrize("dtype,layout", FORMATS, ids=["%s-%s" % f for f in FORMATS])
 

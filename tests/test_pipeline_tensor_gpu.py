@@ -111,11 +111,13 @@ def test_fixture_streams_all(L, name, gpu_parser):
 
 @DTYPES
 @PARSERS
-@pytest.mark.parametrize("case", ["360x199", "100x60"])
+@pytest.mark.parametrize("case", ["360x199", "100x60", "200x64"])
 def test_layout_edges(L, case, gpu_parser, dtype):
     """360 x 199: the fused road and an odd height -- the last row is the twin's fill value, T[c][255].
-    100 x 60: the unfused road (k_planes_crop), width % 8 = 4: k_tensor's per-quad path"""
-    fw, fh = (360, 199) if case == "360x199" else (100, 60)
+    100 x 60: the unfused road (k_planes_crop), width % 8 = 4: k_tensor's per-quad path.
+    200 x 64: a multiple of 8 whose row pair (25 lanes of 8 pixels, 50 of 4) never ends with a wave, and whose last workgroup ends
+    inside one: float CHW shares the kernel in which the lanes behind the frame matter (the HWC exchange)"""
+    fw, fh = {"360x199": (360, 199), "100x60": (100, 60), "200x64": (200, 64)}[case]
     data = ibbp_stream((fw + 15) // 16 * 16, (fh + 15) // 16 * 16, [6, 9], seed=fw + fh, frame=(fw, fh))
     rgba = oracle_frames(data)
     want = expected(L, rgba, dtype)

@@ -1,4 +1,4 @@
-"""GPU: the fourteen resize kernels (k_resample, k_image_scaled, k_cubic, k_cubic_packed: one device function, resample_body) at the
+"""GPU: the twelve resize kernels (k_resample<element bytes, layout, filter>: one device function, resample_body) at the
 geometries of tests/resample_structure.py -- every tile, chunk and store-line edge that tests/test_resample_structure.py shows them to
 reach, on three small streams whose two unequal GOPs share a window.  Expected = T[c][resize_rgb(ORACLE RGB, crop, size, filter)], the
 expectation of the existing tensor tests; compared as bit patterns, every frame of every window, no tolerance."""

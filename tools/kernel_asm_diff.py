@@ -2,9 +2,13 @@
 """Which kernels of libleon_hip's device code changed between two trees: compiles leon_hip.cpp of each with hipcc -S
 --cuda-device-only for gfx950 (no GPU needed) and compares kernel by kernel the instructions (block labels normalised) and,
 separately, the kernel descriptor (the .amdhsa_* lines: static LDS, kernarg size, register counts, ...).
-    python tools/kernel_asm_diff.py OTHER_TREE [THIS_TREE] [--show KERNEL]     e.g. OTHER_TREE = a `git worktree` of the parent commit
+    python tools/kernel_asm_diff.py OTHER_TREE [THIS_TREE] [--show KERNEL] [--rename OLD=NEW ...]
+e.g. OTHER_TREE = a `git worktree` of the parent commit.
 Prints the kernels that are identical, differ, are new and are gone; --show prints a unified diff of the normalised instructions
-and descriptors of every kernel whose name contains KERNEL.  Exit status 1 when a kernel both trees have differs in either."""
+and descriptors of every kernel whose name contains KERNEL.  --rename pairs a kernel that was renamed, or whose template arguments
+changed: OLD is its (mangled) name in OTHER_TREE, NEW its name here, both spelled out by the user (`c++filt` shows what a
+name says); it is then compared with its predecessor instead of showing as gone + new.  Exit status 1 when a kernel both trees
+have differs in either."""
 import argparse
 import difflib
 import os
@@ -55,9 +59,12 @@ def main(argv):
     ap.add_argument("other_tree")
     ap.add_argument("this_tree", nargs="?", default=ROOT)
     ap.add_argument("--show", metavar="KERNEL", help="print the diffs of the kernels whose name contains KERNEL")
+    ap.add_argument("--rename", metavar="OLD=NEW", action="append", default=[], help="compare OTHER_TREE's kernel OLD with this tree's NEW")
     args = ap.parse_args(argv)
     show = args.show
+    renamed = dict(r.split("=", 1) for r in args.rename)
     a, b = kernels(args.other_tree), kernels(args.this_tree)
+    a = {renamed.get(k, k): v for k, v in a.items()}
     both = sorted(k for k in a if k in b)
     differ = [k for k in both if a[k][0] != b[k][0]]
     desc_differ = [k for k in both if a[k][1] != b[k][1]]
