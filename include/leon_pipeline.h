@@ -6,7 +6,8 @@
  * (decoders/jsv.js:426-469, :1593-1599, :1177-1336; player/easybits.player.js:2310-2324, :2543-2617).
  * Here the same stream bytes go through
  *     K parser threads   one libleon_vlc stream per GOP shard (cut at the key map, decoders/jsv.js:264-350;
- *                        closed GOPs share nothing), lists and maps written straight into pinned memory
+ *                        GOPs share nothing but an open GOP's forward reference, see below), lists and maps written
+ *                        straight into pinned memory
  *     one submit thread  a window of W consecutive GOPs at a time: one asynchronous upload per GOP, then ONE
  *                        kernel launch per picture type and dependency level ACROSS the window's GOPs, the
  *                        display conversion fused in (leon_picture.rgba_out); B pictures write no planes
@@ -16,10 +17,29 @@
  * (mpeg1video-decoder-webgl_amd/napi/leon_napi.cc), the MI355X-side of the reference's 'frame' event
  * (decoders/jsv.js:673).
  *
- * Requirements on the stream: JSV with a key map (or a raw elementary stream: one shard), closed GOPs, ONE picture size
+ * Requirements on the stream: JSV with a key map (or a raw elementary stream: one shard), ONE picture size
  * (a sequence header that changes the size ends the run with an error; one that changes the quantiser matrices -- the
  * reference reloads them at every header, decoders/jsv.js:540-558 -- is honoured per picture, round 4).  Any frame width:
  * widths that are no multiple of 8 take an unfused road inside (planes + one conversion launch per picture).
+ *
+ * Open GOPs.  A B picture in front of its GOP's second anchor (coded order) is a LEADING B picture.
+ *   - In a GOP whose header says closed_gop = 1 both its references are the GOP's I picture (it predicts backward only).
+ *   - In an open GOP (closed_gop = 0) its forward reference is the last anchor, in coded order, of the key-map GOP directly
+ *     before it; its backward reference is its own GOP's I picture.
+ *   - A GOP HAS ITS PREDECESSOR when the run decodes the key-map entry directly before it, in the same pass of `loop`, and
+ *     the GOP's header does not set broken_link.  It has not when it is the first GOP of a run (the stream's start,
+ *     start_seconds, the target of a KEY or EXACT seek), the first GOP of each further pass of `loop`, or a GOP with
+ *     broken_link = 1.
+ *   - The leading B pictures of an open GOP without its predecessor are NOT DECODED AND NOT DELIVERED: never launched, and
+ *     with the GPU parser not parsed either (the host parser has read them with the rest of the GOP by then; what it
+ *     wrote is uploaded with the GOP and not used).  The GOP's frames start at its I picture's display_index.  ISO 11172-2 prescribes that for broken_link,
+ *     and it is what a player does after random access.  The host sees missing display positions, as with a GOP the
+ *     encoder cut short; leon_pipeline_stats.pictures counts what was decoded.  LEON_PIPELINE_SEEK_EXACT drops them first
+ *     and trims then: a target time on a dropped frame delivers from the I picture.
+ *   - shard_count > 1: a shard never holds a GOP's neighbour, so an open GOP WITH leading B pictures ends the run with an
+ *     error ("GOP shards must be closed"); nothing is dropped silently there.  Open GOPs without leading B pictures, and
+ *     closed streams, shard as before.
+ * (The reference ignores closed_gop and drops every B picture.)
  */
 #ifndef LEON_PIPELINE_H
 #define LEON_PIPELINE_H
@@ -64,7 +84,8 @@ typedef struct leon_pipeline_config {
     /* Frame-parallel GOP shards across the GPUs of a node: this pipeline decodes the key-map GOPs
      * g with g % shard_count == shard_index only -- one process (or pipeline) per GPU, each with its device_id,
      * all given the same stream; nothing is exchanged between them (closed GOPs share nothing, the key map is
-     * the stream's own index, decoders/jsv.js:264-350).  shard_count <= 1: everything. */
+     * the stream's own index, decoders/jsv.js:264-350; an open GOP with leading B pictures is refused, see "Open GOPs"
+     * above).  shard_count <= 1: everything. */
     int32_t shard_index, shard_count;
     /* = jsv.prototype.seek (decoders/jsv.js:1618-1648) at start-up: begin with the key-map entry at or before this
      * time (seconds) instead of the first one; 0 = from the start.  A running pipeline moves with leon_pipeline_seek. */

@@ -55,6 +55,14 @@ enum {
     LEON_VLC_ERR_NOMEM = -3
 };
 
+/* leon_vlc_picture.open_gop / leon_vlc_picture_scan.open_gop: what the GOP header in front of the picture says (0: no GOP
+ * header in front of it, or a closed GOP -- whatever its broken_link bit says) */
+enum {
+    LEON_VLC_GOP_OPEN = 1,           /* closed_gop = 0 */
+    LEON_VLC_GOP_BROKEN_LINK = 2     /* broken_link = 1: the GOP before this one is not the one it was coded behind (an editor cut
+                                        there); reported only together with LEON_VLC_GOP_OPEN */
+};
+
 typedef struct leon_vlc_stream leon_vlc_stream;
 
 typedef struct leon_vlc_info {
@@ -86,8 +94,9 @@ typedef struct leon_vlc_picture {
     const int16_t* mv_bwd;        /* B */
     const uint8_t* mb_dir;        /* B */
     uint32_t n_slices;
-    int32_t open_gop;             /* 1: the first picture behind a GOP header whose closed_gop bit is 0 -- B pictures in
-                                     front of the GOP's second anchor may predict from the GOP before it */
+    int32_t open_gop;             /* LEON_VLC_GOP_* bits.  Bit 0: the first picture behind a GOP header whose closed_gop bit is 0 --
+                                     B pictures in front of the GOP's second anchor may predict from the GOP before it.  Bit 1
+                                     (only with bit 0): that header's broken_link is 1 -- those B pictures cannot be decoded */
 } leon_vlc_picture;
 
 int leon_vlc_abi_version(void);

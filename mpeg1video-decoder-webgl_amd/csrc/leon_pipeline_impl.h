@@ -38,6 +38,7 @@ struct Arena {                   // pinned host buffer + its device twin, one GO
 // One position of the pipeline: the one leon_pipeline_create starts at, then one per leon_pipeline_seek.  The parser and
 // submit threads work for the current run (leon_pipeline::run) only; what they hold of an earlier one is dropped.
 struct PipeRun {
+    uint64_t id = 0;             // counts the runs of the process (make_run): what was remembered of a run is recognised by it
     std::vector<uint32_t> mine;  // key-map ids the run decodes, in order (this shard's, from the entry it starts with)
     uint32_t first_key = 0;      // the key-map entry it starts with
     uint64_t total_gops = 0;     // mine.size() * loop
@@ -48,6 +49,11 @@ struct PipeRun {
 struct GopJob {
     std::shared_ptr<const PipeRun> run;      // the run it was parsed for
     bool open_gop = false;       // its GOP header says closed_gop = 0
+    bool broken_link = false;    // ... and broken_link = 1
+    // an open GOP's leading B pictures (in front of its second anchor) predict forward from the last anchor of the key-map entry
+    // before it.  true: this run decodes that entry, directly before this GOP and in the same pass of `loop`, and the header does
+    // not say broken_link (parser_main).  false: the leading B pictures of an open GOP are dropped (drop_leading_b)
+    bool has_pred = false;
     uint64_t gop = 0;            // running index among the GOPs of this pipeline
     uint64_t key_gop = 0;        // GOP id in the stream (key-map index, counting on across loops)
     Arena* arena = nullptr;
@@ -116,6 +122,14 @@ struct leon_pipeline {
     size_t planes_bytes = 0;     // one frame's planes record [Y | Cb | Cr (| A)], a multiple of 256
 
     leon_decoder* dec = nullptr;
+    // Open GOPs across windows (submit thread only).  The leading B pictures of a window's first GOP predict from the last anchor
+    // of the window before, whose slot this window's own anchors overwrite: submit_window copies it to the carry slot first.
+    // What is remembered belongs to a run and a GOP of it: a window of another run, or one that does not follow directly, never
+    // matches.  Behind the carry slot: one hold slot per lane (plan_levels).
+    int carry_slot = -1;
+    uint64_t last_run = 0;       // PipeRun::id, 0: nothing remembered
+    uint64_t last_gop = 0;       // the run's GOP the remembered anchor closes
+    int last_anchor = -1;        // its slot, -1: none
     hipStream_t copy_stream = nullptr;
     uint8_t* d_rgba = nullptr;                        // R ring entries of W * max_pics frames (output RGBA)
     uint8_t* d_planes = nullptr;                      // the same for the frames' planes records (output YCbCr, and what the tensors are made from)
@@ -284,7 +298,8 @@ void scan_gop_for_gpu(leon_pipeline* p, GopJob* job, leon_vlc_stream* st, const 
             return;
         }
         if (sc.new_sequence && (qm_now = sequence_in_force(p, job, st, g)) == -2) return;
-        if (sc.open_gop) job->open_gop = true;
+        if (sc.open_gop & LEON_VLC_GOP_OPEN) job->open_gop = true;
+        if (sc.open_gop & LEON_VLC_GOP_BROKEN_LINK) job->broken_link = true;
         Scan x;
         x.s = sc;
         x.qm = qm_now;
@@ -411,7 +426,8 @@ void parse_gop(leon_pipeline* p, GopJob* job)
             break;
         }
         if (pic.new_sequence && (qm_now = sequence_in_force(p, job, st, g)) == -2) break;
-        if (pic.open_gop) job->open_gop = true;
+        if (pic.open_gop & LEON_VLC_GOP_OPEN) job->open_gop = true;
+        if (pic.open_gop & LEON_VLC_GOP_BROKEN_LINK) job->broken_link = true;
         const MapLayout& M = p->maps;
         const size_t epad = MapLayout::entries_pad(pic.n_entries), mbs = M.mbs;
         const size_t need = a->used + M.gpad + epad + M.bytes();      // (absent maps are left out: no more than this)
@@ -684,27 +700,16 @@ int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
     return LEON_OK;
 }
 
-// LEON_PIPELINE_SEEK_EXACT: the first GOP of the run delivers its frames from the one on screen at t_ms on (the largest
-// ts_ms <= t_ms; none: the GOP's first frame, i.e. all of them).  B pictures before it are dropped -- neither parsed on the
-// GPU nor launched --, I and P pictures before it are still reconstructed (later pictures predict from them) but not
-// converted to RGBA and not delivered.
-void trim_to_target(leon_pipeline* p, GopJob* job, double t_ms)
+// the GOP without the pictures whose `keep` is 0: they leave pics, and vpics / slices (gpu_parser) with them
+void keep_pictures(GopJob* job, const std::vector<uint8_t>& keep)
 {
-    int target = -1;
-    for (const PipePic& m : job->pics)
-        if (frame_ts_ms(p, job, m.tref) <= t_ms) target = std::max(target, m.tref);
-    if (target < 0) return;
     std::vector<PipePic> pics;
     std::vector<leon::VlcPic> vpics;
     std::vector<int> renum(job->pics.size(), -1);
     for (size_t k = 0; k < job->pics.size(); k++) {
-        PipePic m = job->pics[k];
-        if (m.tref < target) {
-            if (m.type == LEON_PIC_B) continue;
-            m.shown = false;
-        }
+        if (!keep[k]) continue;
         renum[k] = (int)pics.size();
-        pics.push_back(m);
+        pics.push_back(job->pics[k]);
         if (k < job->vpics.size()) vpics.push_back(job->vpics[k]);
     }
     std::vector<leon::VlcSlice> slices;       // (in picture order, as launch_gpu_parser walks them)
@@ -716,6 +721,43 @@ void trim_to_target(leon_pipeline* p, GopJob* job, double t_ms)
     job->pics.swap(pics);
     job->vpics.swap(vpics);
     job->slices.swap(slices);
+}
+
+// LEON_PIPELINE_SEEK_EXACT: the first GOP of the run delivers its frames from the one on screen at t_ms on (the largest
+// ts_ms <= t_ms; none: the GOP's first frame, i.e. all of them).  B pictures before it are dropped -- neither parsed on the
+// GPU nor launched --, I and P pictures before it are still reconstructed (later pictures predict from them) but not
+// converted to RGBA and not delivered.  (After drop_leading_b: a target on a dropped frame finds no picture at or before it and
+// the GOP delivers from its I picture.)
+void trim_to_target(leon_pipeline* p, GopJob* job, double t_ms)
+{
+    int target = -1;
+    for (const PipePic& m : job->pics)
+        if (frame_ts_ms(p, job, m.tref) <= t_ms) target = std::max(target, m.tref);
+    if (target < 0) return;
+    std::vector<uint8_t> keep(job->pics.size(), 1);
+    for (size_t k = 0; k < job->pics.size(); k++) {
+        PipePic& m = job->pics[k];
+        if (m.tref >= target) continue;
+        if (m.type == LEON_PIC_B) keep[k] = 0;
+        else m.shown = false;
+    }
+    keep_pictures(job, keep);
+}
+
+// A GOP that is open (closed_gop = 0) and does not have its predecessor (GopJob::has_pred): its leading B pictures -- those in
+// front of its second anchor in coded order -- would predict from pictures that are not there, or, behind a broken_link, from the
+// wrong ones.  They are dropped as trim_to_target drops pictures: neither parsed on the GPU nor launched nor delivered.  The GOP's
+// frames then start at its I picture's display index (ISO 11172-2 2.4.3.4: broken_link; what a player does after random access).
+void drop_leading_b(GopJob* job)
+{
+    std::vector<uint8_t> keep(job->pics.size(), 1);
+    int n_anchor = 0;
+    bool any = false;
+    for (size_t k = 0; k < job->pics.size(); k++) {
+        if (job->pics[k].type != LEON_PIC_B) n_anchor++;
+        else if (n_anchor == 1) { keep[k] = 0; any = true; }
+    }
+    if (any) keep_pictures(job, keep);
 }
 
 void parser_main(leon_pipeline* p)
@@ -767,6 +809,11 @@ void parser_main(leon_pipeline* p)
         if (job->status == LEON_OK && (int)job->pics.size() > p->max_pics) {        // (either parser)
             job->status = LEON_ERR_INVALID;
             job->err = "a GOP has " + std::to_string(job->pics.size()) + " pictures; raise max_gop_pictures (" + std::to_string(p->max_pics) + ")";
+        }
+        if (job->status == LEON_OK && job->open_gop && p->cfg.shard_count <= 1) {
+            // (a shard never holds a GOP's neighbour: there plan_levels refuses the GOP)
+            job->has_pred = g % run->mine.size() != 0 && !job->broken_link;
+            if (!job->has_pred) drop_leading_b(job);
         }
         if (job->status == LEON_OK && g == 0 && run->exact_ms >= 0) trim_to_target(p, job, run->exact_ms);
         p->st_parse_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t).count();
@@ -915,9 +962,21 @@ int capture_level(const leon_pipeline* p, const PipeWindow* w, const std::string
 
 // The pictures of one window as levels of launches: per GOP the anchors rotate through three slots (on the unfused road a B
 // picture has one of its own until it is converted); a picture's level is one more than the deepest picture it predicts from.
-int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::vector<LevelPic>>& levels)
+// The leading B pictures of an open GOP that has its predecessor predict forward from that GOP's last anchor: the lane before
+// owns its slots, so the slot is final once that anchor has run; for the window's first GOP it is `carry`, the slot
+// submit_window copies the window before's last anchor to in front of the first level (-1: nothing to copy, *uses_carry tells
+// whether it is needed).  *last_anchor: the slot of the last GOP's last anchor, -1 without one.
+// Invariant: a slot is not written again before the last picture that reads it has run.  Three rotating slots keep it for a GOP
+// on its own -- anchor k + 3 (level k + 3) replaces anchor k, whose last readers are the B pictures in front of anchor k + 1
+// (level k + 2) -- and for leading B pictures at level 1 (closed GOPs, and lane 0 with the carry slot).  In lane j > 0 the leading
+// B pictures of an open GOP wait for the lane before's last anchor, level 4 behind an IBBP-12, while the lane's own fourth anchor
+// would replace the I picture, their backward reference, at level 3.  So the I picture of such a GOP is written to the lane's HOLD
+// slot (behind the carry slot, one per lane), which nothing else of the window writes; its other anchors rotate as before.
+int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::vector<LevelPic>>& levels, int carry, bool* uses_carry, int* last_anchor)
 {
     const int per_lane = 3 + (p->unfused ? p->max_pics : 0);
+    int prev_last = -1, lv_prev_last = -1;       // the lane before's last anchor and its level
+    *uses_carry = false;
     for (size_t j = 0; j < w->jobs.size(); j++) {
         const GopJob* job = w->jobs[j];
         int older = -1, newer = -1, lv_older = -1, lv_newer = -1, n_anchor = 0;      // anchor slots (0..2 of the lane) and their levels
@@ -926,7 +985,7 @@ int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::ve
             LevelPic it{j, &m, -1, -1, -1};
             int lv = 0;
             if (m.type == LEON_PIC_I) {
-                it.out = (int)(per_lane * j) + n_anchor % 3;
+                it.out = j && n_anchor == 0 && job->open_gop && job->has_pred ? p->carry_slot + 1 + (int)j : (int)(per_lane * j) + n_anchor % 3;
             } else if (m.type == LEON_PIC_P) {
                 if (newer < 0) return fail(LEON_ERR_INVALID, "GOP %llu: a P picture without a preceding anchor", (unsigned long long)job->gop);
                 it.fwd = newer;
@@ -936,12 +995,19 @@ int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::ve
                 if (newer < 0) return fail(LEON_ERR_INVALID, "GOP %llu: a B picture without an anchor (open GOPs cannot be sharded)", (unsigned long long)job->key_gop);
                 // the leading B pictures of a CLOSED GOP predict backward only (both references = the I picture); in an
                 // open GOP (closed_gop = 0) they may predict from the GOP before, which a shard does not have
-                if (older < 0 && job->open_gop)
+                if (older < 0 && job->open_gop && !job->has_pred)
                     return fail(LEON_ERR_INVALID, "GOP %llu is open (closed_gop = 0) and its leading B pictures may predict from the GOP before it: "
                                                   "GOP shards must be closed", (unsigned long long)job->key_gop);
                 it.bwd = newer;
-                it.fwd = older >= 0 ? older : newer;
-                lv = std::max(lv_newer, lv_older) + 1;
+                if (older >= 0 || !job->open_gop) {
+                    it.fwd = older >= 0 ? older : newer;
+                    lv = std::max(lv_newer, lv_older) + 1;
+                } else {
+                    it.fwd = j ? prev_last : carry;
+                    if (it.fwd < 0) return fail(LEON_ERR_INVALID, "GOP %llu is open and the last anchor of the GOP before it is not at hand", (unsigned long long)job->key_gop);
+                    if (!j) *uses_carry = true;
+                    lv = std::max(lv_newer, j ? lv_prev_last : -1) + 1;
+                }
                 if (p->unfused) it.out = (int)(per_lane * j) + 3 + n_b++ % p->max_pics;
             }
             if (m.type != LEON_PIC_B) {
@@ -959,7 +1025,9 @@ int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::ve
             if (seen[(size_t)m.tref]) return fail(LEON_ERR_INVALID, "GOP %llu: two pictures with temporal reference %d", (unsigned long long)job->key_gop, m.tref);
             seen[(size_t)m.tref] = 1;
         }
+        prev_last = newer; lv_prev_last = lv_newer;
     }
+    *last_anchor = prev_last;
     return LEON_OK;
 }
 
@@ -1178,10 +1246,22 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
     static const bool poison = env_int("LEON_DEBUG_POISON", 0) == 1;
     std::vector<std::vector<LevelPic>> levels;
     std::vector<std::vector<int32_t>> qset(w->jobs.size());
-    int rc = plan_levels(p, w, levels);
+    // the window before's last anchor, if this window follows it directly in one run
+    const bool follows = p->last_anchor >= 0 && p->last_run == w->run->id && !w->jobs.empty() && p->last_gop + 1 == w->jobs[0]->gop;
+    bool uses_carry = false;
+    int last_anchor = -1;
+    int rc = plan_levels(p, w, levels, follows ? p->carry_slot : -1, &uses_carry, &last_anchor);
     if (rc == LEON_OK) rc = upload_and_chain(p, w, serial, poison);
     if (rc == LEON_OK) rc = register_qsets(p, w, qset);
     if (rc != LEON_OK) return rc;
+    if (uses_carry) {
+        // Every reconstruction launch of every window goes through the decoder's stream in submit order (submit_batch_any,
+        // leon_convert_rgba, crop_planes_batch): the copy runs behind the window before's last launch and in front of this
+        // window's first, which may overwrite the source; the carry slot's readers of the window before have run as well.
+        const leon_decoder* d = p->dec;
+        HIP_TRY(hipMemcpyAsync(d->d_slots + (size_t)p->carry_slot * d->slot_stride, d->d_slots + (size_t)p->last_anchor * d->slot_stride, d->plane_bytes,
+                               hipMemcpyDeviceToDevice, d->stream));
+    }
     const std::string cdir = p->capture_dir.empty() ? "" : p->capture_dir + "/w" + std::to_string(w->id);
     if (!cdir.empty()) {
         (void)mkdir(p->capture_dir.c_str(), 0777);          // (both may exist)
@@ -1196,6 +1276,9 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
     }
     if (!cdir.empty())
         for (size_t j = 0; j < w->jobs.size(); j++) capture_file(cdir + "/arena_" + std::to_string(j) + ".bin", w->jobs[j]->arena->dev, w->jobs[j]->arena->used);
+    p->last_run = w->run->id;
+    p->last_gop = w->jobs.empty() ? 0 : w->jobs.back()->gop;
+    p->last_anchor = last_anchor;
     list_frames(p, w);
     if ((rc = launch_tensors(p, w)) != LEON_OK) return rc;
     if (serial) HIP_TRY(hipStreamSynchronize(p->dec->stream));
@@ -1405,7 +1488,9 @@ void notify_main(leon_pipeline* p)
 // leon_pipeline_seek both ask here; `st` is a stream opened on the pipeline's bytes (its container header and key map).
 std::shared_ptr<PipeRun> make_run(const leon_pipeline* p, leon_vlc_stream* st, double seconds, int loops)
 {
+    static std::atomic<uint64_t> next_id{1};
     auto run = std::make_shared<PipeRun>();
+    run->id = next_id++;
     if (p->has_keymap && seconds > 0) {
         uint64_t off = 0;
         if (leon_vlc_seek(st, seconds, &off) == LEON_VLC_OK)
@@ -1641,7 +1726,10 @@ int allocate_pipeline(leon_pipeline* p)
     leon_config dc{};
     dc.coded_width = p->vinfo.coded_width; dc.coded_height = p->vinfo.coded_height;
     dc.frame_width = p->vinfo.frame_width; dc.frame_height = p->vinfo.frame_height;
-    dc.n_slots = (3 + (p->unfused ? p->max_pics : 0)) * p->W;      // three rotating anchors per GOP of a window (+ its B pictures)
+    // three rotating anchors per GOP of a window (+ its B pictures); behind them the carry slot (open GOPs across windows) and
+    // a hold slot per lane (the I picture of an open GOP whose leading B pictures wait for the lane before: plan_levels)
+    p->carry_slot = (3 + (p->unfused ? p->max_pics : 0)) * p->W;
+    dc.n_slots = p->carry_slot + 1 + p->W;
     dc.alpha = p->vinfo.has_alpha == 1;        // yuva: the frames' A bytes come from the stream's fourth component
     dc.device_id = p->cfg.device_id;
     int rc = leon_create(&dc, &p->dec);

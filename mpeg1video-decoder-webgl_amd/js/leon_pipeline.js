@@ -37,6 +37,8 @@
  *                                  tensorBias), readTensor returns a Uint8Array; opts.tensorLayout 'chw' (default) or 'hwc': channels
  *                                  last, [H][W][3] -- uint8 hwc is the packed RGB frame, 3 bytes per pixel; stats() reports tensorLayout
  *   p.releaseWindow(window); p.stats(); p.destroy();
+ * Open GOPs (closed_gop = 0) need no option: their leading B pictures predict from the GOP before; where that GOP is not decoded (start,
+ * seek target, broken_link) they are not delivered and the GOP's frames start at its I picture's displayIndex (include/leon_pipeline.h).
  */
 const path = require('path');
 const EventEmitter = require('events');

@@ -636,6 +636,9 @@ class Pipeline:
     on_window(window_id, frames) runs on the pipeline's notify thread with a list of dicts
     (gop, display_index, type, ts_ms, rgba = device address); unless it returns False the window is
     released right after.  read_frame(frame) works until the frame's window is released.
+    Open GOPs (closed_gop = 0) are decoded, no option needed: their leading B pictures predict from the GOP before; an open GOP
+    without its predecessor (first of a run or of a loop pass, the target of seek(), broken_link) delivers from its I picture on,
+    so its first display positions are missing from `frames`.  Only with shard_count > 1 such a GOP makes wait() raise.
     output="ycbcr" / "both": the frames carry their YCbCr 4:2:0 planes too (y, cb, cr, a = device addresses, a for yuva
     streams only; rgba is None with "ycbcr"): read_planes(frame) copies them to the host, plane_views(frame) wraps them.
     output="tensor" / "rgba+tensor" / "ycbcr+tensor" / "all" (PIPELINE_TENSOR_OUTPUTS): the frames carry a planar [3, H, W] tensor

@@ -127,7 +127,7 @@ class Stream:
         I = self.refresh_info()
         nmb = I.mb_width * I.mb_height
         out = {"type": p.type, "temporal_reference": p.temporal_reference, "ts": p.ts_ms, "new_sequence": bool(p.new_sequence),
-               "n_slices": p.n_slices, "open_gop": bool(p.open_gop),
+               "n_slices": p.n_slices, "open_gop": bool(p.open_gop & 1), "broken_link": bool(p.open_gop & 2),
                "grp_off": _arr(p.grp_off, p.n_groups + 1, np.uint32), "entries": _arr(p.entries, p.n_entries, np.uint32),
                "qscale": _arr(p.qscale, nmb, np.uint8), "intra": _arr(p.intra, nmb, np.uint8),
                "repadd": _arr(p.repadd, nmb, np.uint8), "mv_fwd": _arr(p.mv_fwd, 2 * nmb, np.int16),
@@ -160,7 +160,8 @@ class Stream:
         return {"type": p.type, "temporal_reference": p.temporal_reference, "ts": p.ts_ms, "new_sequence": bool(p.new_sequence),
                 "full_pel_fwd": p.full_pel_fwd, "fwd_rsize": p.fwd_rsize, "full_pel_bwd": p.full_pel_bwd, "bwd_rsize": p.bwd_rsize,
                 "slice_code": [int(p.slice_code[i]) for i in range(p.n_slices)],
-                "slice_bit_pos": [int(p.slice_bit_pos[i]) for i in range(p.n_slices)], "end_byte": int(p.end_byte)}
+                "slice_bit_pos": [int(p.slice_bit_pos[i]) for i in range(p.n_slices)], "end_byte": int(p.end_byte),
+                "open_gop": bool(p.open_gop & 1), "broken_link": bool(p.open_gop & 2)}
 
     def keymap(self):
         """byte offsets of the GOP shards (leon_vlc_get_keymap)"""

@@ -364,7 +364,9 @@ napi_value Create(napi_env env, napi_callback_info info)
 //                                                maxGopPictures, loop, shardIndex, shardCount}, (window, frames, status) => {...});
 //   shardIndex / shardCount: this pipeline decodes the key-map GOPs g = shardIndex (mod shardCount) on deviceId --
 //   one Node process per GPU is the JavaScript host's form of the frame-parallel partition.
-//   frames: [{gop, displayIndex, type, ts}] in display order; window < 0 = 'ended' (decoders/jsv.js:437).
+//   frames: [{gop, displayIndex, type, ts}] in display order; window < 0 = 'ended' (decoders/jsv.js:437).  An open GOP
+//   (closed_gop = 0) without its predecessor -- first of a run, seek target, broken_link -- comes without its leading B
+//   pictures: its first displayIndex is its I picture's (include/leon_pipeline.h "Open GOPs"; no option).
 //   p.readFrame(window, i) -> Uint8Array (copies one frame to the host: tests, thumbnails),
 //   p.readPlanes(window, i) -> {y, cb, cr[, a]} packed Uint8Arrays (options.output 2 / 3: the frames' YCbCr planes),
 //   p.releaseWindow(window), p.stats(), p.info(), p.destroy().

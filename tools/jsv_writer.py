@@ -415,7 +415,8 @@ def write_picture(bw, t, cw, ch, temporal_ref, f_code=(2, 2), full_pel=(0, 0), s
 
 def write_stream(pictures, cw, ch, frame_w=None, frame_h=None, rate_idx=3, gop_starts=None,
                  qm_intra=None, qm_non_intra=None, key_map=True, f_code=(2, 2), slice_mbs=None, alpha=None, gop_qm=None,
-                 full_pel=(0, 0), stuffing=None, extra_slice=None, b_skip=False, keep_last_mb=False, stats=None):
+                 full_pel=(0, 0), stuffing=None, extra_slice=None, b_skip=False, keep_last_mb=False, stats=None,
+                 closed_gop=True, broken_link=()):
     """pictures: tensors dicts in CODED order, each with 'display' (temporal reference inside
     its GOP).  gop_starts: indices into `pictures` where a sequence header + GOP header go.
     gop_qm: {index into `pictures`: (qm_intra, qm_non_intra)} -- matrices of that GOP's own sequence header
@@ -424,6 +425,9 @@ def write_stream(pictures, cw, ch, frame_w=None, frame_h=None, rate_idx=3, gop_s
     stuffing / extra_slice: a seed each (None: off) for macroblock_stuffing codes and extra_information_slice bytes,
     see write_picture.  b_skip: skip the B macroblocks that may be skipped (off: every B macroblock is coded, as the
     streams written before this option are).  keep_last_mb: see write_picture.  stats: a new_stats() dict to count into.
+    closed_gop: True / False for every GOP header's closed_gop bit, or a collection of the GOP numbers (0 = the first GOP
+    of the stream) that are OPEN (closed_gop = 0) -- the others are closed.  broken_link: the GOP numbers whose header sets
+    broken_link.  The flags only: whether a GOP's leading B pictures predict forward is up to the tensors.
     Returns (bytes, key-map offsets)."""
     stuffing = None if stuffing is None else np.random.default_rng(stuffing)
     extra_slice = None if extra_slice is None else np.random.default_rng(extra_slice)
@@ -433,8 +437,11 @@ def write_stream(pictures, cw, ch, frame_w=None, frame_h=None, rate_idx=3, gop_s
     offsets = []
     rate = [0, 23.976, 24, 25, 29.97, 30, 50, 59.94, 60][rate_idx]
     frame_no = 0
+    is_open = (lambda g: not closed_gop) if isinstance(closed_gop, (bool, np.bool_)) else (lambda g, o=frozenset(closed_gop): g in o)
+    broken_link = frozenset(broken_link)
     for i, t in enumerate(pictures):
         if i in gop_starts:
+            gop_no = len(offsets)
             offsets.append((body.tell() if body.n == 0 else None, frame_no))
             body.start_code(START_SEQUENCE)
             offsets[-1] = (len(body.buf) - 4, frame_no)
@@ -461,8 +468,8 @@ def write_stream(pictures, cw, ch, frame_w=None, frame_h=None, rate_idx=3, gop_s
             body.put(1, 1)
             body.put(sec % 60, 6)
             body.put(int(frame_no - sec * rate) & 63, 6)
-            body.put(1, 1)                                 # closed_gop
-            body.put(0, 1)                                 # broken_link
+            body.put(0 if is_open(gop_no) else 1, 1)       # closed_gop
+            body.put(1 if gop_no in broken_link else 0, 1) # broken_link
         write_picture(body, t, cw, ch, t.get("display", 0), f_code=f_code, full_pel=full_pel, slice_mbs=slice_mbs,
                       stuffing=stuffing, extra_slice=extra_slice, b_skip=b_skip, keep_last_mb=keep_last_mb, stats=stats)
         frame_no += 1
@@ -512,8 +519,8 @@ def merge_gops(streams, frame_w, frame_h, rate_idx=3, alpha=False):
         if g < 0:
             raise ValueError("stream %d: no GOP header behind the sequence header" % i)
         sec = int(frame_no / rate)
-        tc = ((sec // 3600) << 26) | (((sec // 60) % 60) << 20) | (1 << 19) | ((sec % 60) << 13) | ((int(frame_no - sec * rate) & 63) << 7) | (1 << 6)
-        body[g + 4:g + 8] = tc.to_bytes(4, "big")             # time code, closed_gop = 1, broken_link = 0, padding
+        tc = ((sec // 3600) << 26) | (((sec // 60) % 60) << 20) | (1 << 19) | ((sec % 60) << 13) | ((int(frame_no - sec * rate) & 63) << 7) | (body[g + 7] & 0x60)
+        body[g + 4:g + 8] = tc.to_bytes(4, "big")             # time code; closed_gop and broken_link as the body's own header has them; padding
         offsets.append((at, frame_no))
         at += len(body)
         bodies.append(bytes(body))

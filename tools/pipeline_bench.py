@@ -41,11 +41,15 @@ def main():
                          "with torch.nn.functional.interpolate(mode='bilinear', antialias=True)")
     ap.add_argument("--copy-rate", action="store_true", help="measure leon_measure_copy_bandwidth in this process first (the yardstick of a launch's rate)")
     ap.add_argument("--varied", action="store_true", help="the 16-GOP stream with 16 different contents (tools/stream_1080p.py) instead of --gops GOPs")
+    ap.add_argument("--open-gops", action="store_true", help="with --varied: the same recipe written with open GOPs (closed_gop = 0), the leading B pictures "
+                                                             "predicting forward (from the GOP before) and bidirectionally")
     a = ap.parse_args()
+    if a.open_gops and not a.varied:
+        ap.error("--open-gops goes with --varied")
     cached = os.path.join(ROOT, "tools", "probe", "stream_1080p_%dgop.bin" % a.gops)
     if a.varied:
         import stream_1080p
-        data = stream_1080p.load_varied()
+        data = stream_1080p.load_varied(open_gops=a.open_gops)
         a.gops = stream_1080p.VARIED_GOPS
     elif os.path.exists(cached):
         data = open(cached, "rb").read()
@@ -106,7 +110,7 @@ def main():
         "upload_gb": s["upload_bytes"] / 1e9, "upload_gbps": s["upload_bytes"] / 1e9 / s["seconds"],
         "entries_per_picture": s["entries"] / max(1, s["pictures"]), "stream_bytes": s["stream_bytes"],
         "stream_megabit_per_picture": s["stream_bytes"] * 8 / 1e6 / (12 * a.gops), "host_threads": os.cpu_count(),
-        "stream": "%d different GOPs, looped %d times" % (a.gops, a.loop)}))
+        "stream": "%d different %sGOPs, looped %d times" % (a.gops, "open " if a.open_gops else "", a.loop)}))
 
 
 if __name__ == "__main__":

@@ -6,6 +6,7 @@
 Python -- so the first user in a clean clone (a test, bench.py --full) writes it and later ones read it.
 
   python tools/stream_1080p.py            # write it if it is not there, print its path"""
+import functools
 import hashlib
 import os
 import sys
@@ -42,9 +43,10 @@ def load():
 # ---- the varied stream: N different GOPs, written by parallel processes and merged (jsv_writer.merge_gops) -------------
 VARIED_GOPS = 16
 VARIED_PATH = os.path.join(ROOT, "tools", "probe", "stream_1080p_%dgop_varied.bin" % VARIED_GOPS)
+VARIED_OPEN_PATH = os.path.join(ROOT, "tools", "probe", "stream_1080p_%dgop_varied_open.bin" % VARIED_GOPS)
 
 
-def _one_gop(g):
+def _one_gop(g, open_gop=False):
     for p in (os.path.join(ROOT, "mpeg1video-decoder-webgl_amd"), os.path.join(ROOT, "tools")):
         if p not in sys.path:
             sys.path.insert(0, p)
@@ -54,16 +56,20 @@ def _one_gop(g):
     rng = np.random.default_rng([0x4C454F4E, 1080, g])
     pics = []
     for ptype, disp, f, b in S.gop_ibbp(12):
-        t = S.make_picture(rng, 1920, 1088, ptype, force_dir=2 if (ptype == S.PIC_B and f is None) else None)
+        # (an open GOP's leading B pictures predict forward and bidirectionally, from the GOP before as well)
+        t = S.make_picture(rng, 1920, 1088, ptype, force_dir=2 if (ptype == S.PIC_B and f is None and not open_gop) else None)
         t["display"] = disp
         pics.append(t)
-    return W.write_stream(pics, 1920, 1088, 1920, 1080, gop_starts=[0])[0]
+    return W.write_stream(pics, 1920, 1088, 1920, 1080, gop_starts=[0], closed_gop=not open_gop)[0]
 
 
-def ensure_varied(path=VARIED_PATH, n_gops=VARIED_GOPS, workers=None):
-    """N closed IBBP GOPs with N different contents (GOP g is seeded by (0x4C454F4E, 1080, g)): what the end-to-end figures
+def ensure_varied(path=None, n_gops=VARIED_GOPS, workers=None, open_gops=False):
+    """N IBBP GOPs (closed; open_gops: open) with N different contents (GOP g is seeded by (0x4C454F4E, 1080, g)): what the end-to-end figures
     should be quoted on -- on the 2-GOP stream looped, a launch of the GPU parser holds every slice dozens of times, and
-    lanes with identical slices do not diverge.  Written by `workers` processes (one GOP each, 15 s per GOP)."""
+    lanes with identical slices do not diverge.  Written by `workers` processes (one GOP each, 15 s per GOP).
+    open_gops: the same recipe with every GOP header open (closed_gop = 0) and the leading B pictures left to predict in both
+    directions -- a file of its own (VARIED_OPEN_PATH)."""
+    path = path or (VARIED_OPEN_PATH if open_gops else VARIED_PATH)
     if os.path.exists(path) and os.path.getsize(path) > n_gops * 1000000:
         return path
     import multiprocessing as mp
@@ -74,7 +80,7 @@ def ensure_varied(path=VARIED_PATH, n_gops=VARIED_GOPS, workers=None):
     ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
     workers = max(1, min(workers or ncpu, n_gops))
     with mp.get_context("spawn").Pool(workers) as pool:
-        gops = pool.map(_one_gop, range(n_gops))
+        gops = pool.map(functools.partial(_one_gop, open_gop=open_gops), range(n_gops))
     data, _ = W.merge_gops(gops, 1920, 1080)
     tmp = path + ".tmp%d" % os.getpid()
     open(tmp, "wb").write(data)
@@ -82,11 +88,13 @@ def ensure_varied(path=VARIED_PATH, n_gops=VARIED_GOPS, workers=None):
     return path
 
 
-def load_varied():
-    return open(ensure_varied(), "rb").read()
+def load_varied(open_gops=False):
+    return open(ensure_varied(open_gops=open_gops), "rb").read()
 
 
 if __name__ == "__main__":
     print(ensure())
     if "--varied" in sys.argv:
         print(ensure_varied())
+    if "--varied-open" in sys.argv:
+        print(ensure_varied(open_gops=True))
