@@ -239,6 +239,33 @@ typedef struct leon_pipeline_tensor_shape {
     int64_t stride_c, stride_y, stride_x;
 } leon_pipeline_tensor_shape;
 
+/* The resampled image in a padded canvas: detection, segmentation and pose models, and any batch with a fixed input shape, take the
+ * frame resized with its aspect ratio kept and padded to a fixed size (1920 x 1080 -> 640 x 360, centred in 640 x 640 of grey).
+ * With r[oy][ox][c] the 8-bit result of the resize definition above for `resize` (either filter, unchanged; out_height x out_width)
+ * and T the element table, the tensor is width x height:
+ *     tensor[c][Y][X] = T[c][ r[Y - y][X - x][c] ]      for x <= X < x + out_width and y <= Y < y + out_height
+ *                     = T[c][ pad[c] ]                   everywhere else
+ * laid out as CHW or HWC exactly as above with width and height in place of out_width and out_height: tensor_frame_bytes, the ring
+ * pitches, leon_pipeline_tensor_shape, leon_pipeline_tensor_geometry.width / height and leon_pipeline_read_tensor are the canvas's; the
+ * geometry's crop and tap fields still describe the resampling; leon_pipeline_get_tensor_canvas reports the image rectangle.
+ * Every element of a frame's tensor is written by its window's launch, every window.  Pad elements are not written once at create
+ * and then relied upon: a consumer may overwrite a delivered tensor in place until it releases the window, and the next window that
+ * reuses the ring entry is whole again.  It is still one launch per window (k_letterbox<element bytes, layout, filter>: the image's
+ * tiles as k_resample's, further workgroups of the same launch for the pad).
+ * A canvas equal to the image (x = y = 0, same size) gives exactly the tensors of the same pipeline without a canvas; an identity resize
+ * (out size = crop size, triangle filter) with a larger canvas is the padded full frame.  All fields zero (or no struct) =
+ * leon_pipeline_create_tensor_format.
+ * Refused at create (LEON_ERR_INVALID, no device touched): a canvas without the TENSOR bit, a canvas without resize settings (no
+ * out_width / out_height), width or height outside 1 .. 4096, a negative x or y, x + out_width > width or y + out_height > height, a
+ * pad value outside 0 .. 255, image_width / image_height non-zero and different from the out size, a non-zero reserved word. */
+typedef struct leon_pipeline_tensor_canvas {
+    int32_t width, height;               /* the TENSOR's size; 1 .. 4096 each */
+    int32_t x, y;                        /* where the resampled image's top-left element lies in it; >= 0 */
+    int32_t pad[3];                      /* 8-bit R, G, B of every element outside the image; 0 .. 255 */
+    int32_t image_width, image_height;   /* create: 0, or equal to resize->out_width / out_height; get: the values in force */
+    int32_t reserved[7];                 /* must be 0 */
+} leon_pipeline_tensor_canvas;           /* 64 bytes */
+
 typedef void (*leon_pipeline_callback)(void* user, int64_t window, const leon_pipeline_frame* frames, int32_t n_frames, int32_t status);
 
 typedef struct leon_pipeline_info {
@@ -302,6 +329,25 @@ int leon_pipeline_create_tensor_format(const leon_pipeline_config* cfg, const le
                                        leon_pipeline_callback cb, void* user, leon_pipeline** out);
 /* LEON_ERR_INVALID for a pipeline without tensor output, as leon_pipeline_get_tensor_geometry */
 int leon_pipeline_get_tensor_shape(leon_pipeline* p, leon_pipeline_tensor_shape* out);
+/* leon_pipeline_create_tensor_format with the image placed in a padded canvas; `canvas` NULL (or all zero) = leon_pipeline_create_tensor_format */
+int leon_pipeline_create_tensor_canvas(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const leon_pipeline_tensor_resize* resize,
+                                       const leon_pipeline_tensor_format* format, const leon_pipeline_tensor_canvas* canvas, const uint8_t* stream,
+                                       size_t bytes, size_t valid_bytes, leon_pipeline_callback cb, void* user, leon_pipeline** out);
+/* the canvas in force: its size, the image rectangle (x, y, image_width, image_height) and the pad values; without canvas settings the
+ * tensor itself (x = y = 0, image = tensor, pad 0).  LEON_ERR_INVALID for a pipeline without tensor output */
+int leon_pipeline_get_tensor_canvas(leon_pipeline* p, leon_pipeline_tensor_canvas* out);
+/* The usual placement: a source of src_width x src_height scaled to fit canvas_width x canvas_height with its aspect ratio kept, and
+ * centred.  Host only, no device; 64-bit integers only, so that every binding agrees on every input:
+ *     canvas_width * src_height <= canvas_height * src_width:
+ *         out_width = canvas_width,   out_height = max(1, (2 * src_height * canvas_width + src_width) / (2 * src_width))
+ *     otherwise:
+ *         out_height = canvas_height, out_width = max(1, (2 * src_width * canvas_height + src_height) / (2 * src_height))
+ *     x = (canvas_width - out_width) / 2, y = (canvas_height - out_height) / 2          (the odd pixel goes right or below)
+ * Fills resize->out_width / out_height (crop and filter are left alone) and canvas->width / height / x / y (pad, image_* and reserved are
+ * left alone); src_* is the crop box's size, or the frame's.  1920 x 1080 into 640 x 640 is 640 x 360 at (0, 140).  Refuses a size below 1;
+ * the ratio limit of 16 is create's to judge. */
+int leon_pipeline_letterbox(int32_t src_width, int32_t src_height, int32_t canvas_width, int32_t canvas_height,
+                            leon_pipeline_tensor_resize* resize, leon_pipeline_tensor_canvas* canvas);
 int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes);
 int leon_pipeline_get_info(leon_pipeline* p, leon_pipeline_info* out);
 /* the consumer is done with a window's frames: its ring entries (RGBA, planes, tensors) and staging may be reused */

@@ -1921,6 +1921,27 @@ struct ResampleGeom {
     uint32_t off_cx, off_wx, off_fy, off_cy, off_wy;          // int32 offsets in the table buffer (first_x at 0)
     RingGeom ring;
 };
+// Where the resampled image lies in its tensor (leon_pipeline_tensor_canvas): only the store addresses of resample_body ask.
+// ImageIsTensor: the tensor IS the image (k_resample) -- its overloads below are constants and fields of ResampleGeom, and those
+// kernels come out instruction for instruction as before there was a canvas.  CanvasGeom: the image at (x, y) in a width x height tensor (k_letterbox).
+struct ImageIsTensor {
+};
+struct CanvasGeom {
+    int32_t cw, ch, x, y;
+    uint32_t pad;                        // the pad pixel's 8-bit R, G, B in bits 0, 8, 16
+};
+__device__ __forceinline__ uint32_t tensor_plane_elems(const ResampleGeom& G, const ImageIsTensor&) { return (uint32_t)G.ow * (uint32_t)G.oh; }
+__device__ __forceinline__ uint32_t tensor_plane_elems(const ResampleGeom&, const CanvasGeom& c) { return (uint32_t)c.cw * (uint32_t)c.ch; }
+__device__ __forceinline__ int tensor_width(const ResampleGeom& G, const ImageIsTensor&) { return G.ow; }
+__device__ __forceinline__ int tensor_width(const ResampleGeom&, const CanvasGeom& c) { return c.cw; }
+__device__ __forceinline__ int tensor_left(const ImageIsTensor&) { return 0; }
+__device__ __forceinline__ int tensor_left(const CanvasGeom& c) { return c.x; }
+__device__ __forceinline__ int tensor_top(const ImageIsTensor&) { return 0; }
+__device__ __forceinline__ int tensor_top(const CanvasGeom& c) { return c.y; }
+struct LetterboxGeom {
+    ResampleGeom image;
+    CanvasGeom canvas;
+};
 
 // Column c of a staged row lies at dword c + (c >> 4): the horizontal pass's lanes are the tile's output columns and read columns
 // about `ratio` apart -- at a ratio of 16 or 8 unpadded rows would put all of them on two or four LDS banks; one pad dword per 16
@@ -1946,10 +1967,12 @@ __device__ __forceinline__ int32_t resample_mad(int32_t w, uint32_t sample, int3
 // channel rows of 32 bytes -- every row at the offset its first byte has in its 16-byte line of the frame (the tensor starts on a
 // 256-byte boundary).  A lane then takes one aligned 16-byte line of one row: inside the row it is ONE b128 store, at the row's two
 // ends its elements go one by one (a row's start is aligned to nothing: out_width is any number).
-template <int EB, int LAYOUT, class F>
+// In a canvas (`C`: ImageIsTensor or CanvasGeom) only the store addresses move: the tiles are numbered from the image's origin, a
+// tile row still stores the bytes of [g0, g1) and nothing else, its row stride and plane size are the canvas's.
+template <int EB, int LAYOUT, class F, class C>
 __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
                                               const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
-                                              const ResampleGeom& G)
+                                              const ResampleGeom& G, const C& place)
 {
     typedef typename ElemOf<EB>::type Elem;
     typedef typename F::Acc Acc;
@@ -2063,10 +2086,11 @@ __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes
         }
     }
     const uint32_t px = resample_px(ar, ag, ab);
-    const uint32_t plane_elems = (uint32_t)G.ow * (uint32_t)G.oh;
+    // the tensor's row stride and plane, the tile's origin in the tensor
+    const uint32_t plane_elems = tensor_plane_elems(G, place);
     if constexpr (LAYOUT == kLayoutChw && EB != 1) {
         const __amdgpu_buffer_rsrc_t rs = buf_rsrc(dst);
-        const uint32_t at = (uint32_t)(oy0 + sub) * (uint32_t)G.ow + (uint32_t)(ox0 + o);
+        const uint32_t at = (uint32_t)(oy0 + sub + tensor_top(place)) * (uint32_t)tensor_width(G, place) + (uint32_t)(ox0 + o + tensor_left(place));
         const uint32_t oob = valid ? 0u : kOobBit;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
@@ -2084,8 +2108,8 @@ __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes
         static_assert(kRows * kRowStride <= (int)sizeof(h_s) && kLines <= kLinesP2 && kRows * kLinesP2 <= kRgbaBlock, "the packed tile fits the h rows, a lane per line");
         // byte offset in the frame of row `row` of the tile's rows (row = tile row, or channel * 8 + tile row)
         auto row_start = [&](int row) -> uint32_t {
-            if constexpr (kHwc) return ((uint32_t)(oy0 + row) * (uint32_t)G.ow + (uint32_t)ox0) * 3u * EB;
-            else return ((uint32_t)(row >> 3) * plane_elems + (uint32_t)(oy0 + (row & 7)) * (uint32_t)G.ow + (uint32_t)ox0) * EB;
+            if constexpr (kHwc) return ((uint32_t)(oy0 + row + tensor_top(place)) * (uint32_t)tensor_width(G, place) + (uint32_t)(ox0 + tensor_left(place))) * 3u * EB;
+            else return ((uint32_t)(row >> 3) * plane_elems + (uint32_t)(oy0 + (row & 7) + tensor_top(place)) * (uint32_t)tensor_width(G, place) + (uint32_t)(ox0 + tensor_left(place))) * EB;
         };
         char* pack = reinterpret_cast<char*>(h_s);
         __syncthreads();          // every lane has read its h column
@@ -2127,7 +2151,137 @@ __global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restri
                                                          const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
                                                          ResampleGeom G)
 {
-    resample_body<EB, LAYOUT, F>(planes_ring, tensor_ring, frame_ids, table, T, rt, G);
+    resample_body<EB, LAYOUT, F>(planes_ring, tensor_ring, frame_ids, table, T, rt, G, ImageIsTensor{});
+}
+
+// ---- the resampled image in a padded canvas (leon_pipeline.h, leon_pipeline_tensor_canvas) ------------------------------
+// One launch writes every element of every frame's tensor.  blockIdx.y below the image's tile rows: resample_body, its stores moved
+// to (x, y) of the canvas.  blockIdx.y from there on: pad workgroups, numbered (blockIdx.y - tile rows) * gridDim.x + blockIdx.x;
+// they leave before any table load or staging and use no LDS.
+// A pad workgroup owns kPadLinesPerGroup consecutive 16-byte lines of the tensor (which starts on a 256-byte boundary), a lane one
+// line per step: consecutive lanes, consecutive lines.  In memory order the tensor is a sequence of rows -- HWC: `height` rows of
+// 3 * width elements, the image in elements [3x, 3(x + ow)) of rows y .. y + oh - 1; CHW: 3 * height rows of `width` elements, the
+// image in [x, x + ow) of rows y .. y + oh - 1 of each plane -- and the pad is what lies between: byte runs that start behind one
+// row's image and end in front of the next one's (or at the tensor's ends, or run from plane to plane).  A line wholly inside a run
+// is ONE b128 store of the pad pattern, built from the line's address (HWC: period 3 elements; CHW: the plane's element); a line
+// wholly inside an image row is not touched (its tile stores it); a line shared with image elements or cut by the tensor's end
+// leaves element by element, its pad elements only.  The image tiles store exactly the image's bytes, the pad workgroups exactly
+// the others: no byte twice, none left out, no order between workgroups.
+static constexpr int kPadLinesPerLane = 4, kPadLinesPerGroup = kPadLinesPerLane * kRgbaBlock;
+template <int EB>
+__device__ __forceinline__ void pad_store_elem(uint32_t v, __amdgpu_buffer_rsrc_t rs, uint32_t at)
+{
+    typedef typename ElemOf<EB>::type Elem;
+    if constexpr (EB == 4) __builtin_amdgcn_raw_buffer_store_b32(v, rs, (int)at, 0, kAuxFrameStore);
+    else if constexpr (EB == 2) __builtin_amdgcn_raw_buffer_store_b16((Elem)v, rs, (int)at, 0, kAuxFrameStore);
+    else __builtin_amdgcn_raw_buffer_store_b8((Elem)v, rs, (int)at, 0, kAuxFrameStore);
+}
+template <int EB, int LAYOUT>
+__device__ __forceinline__ void pad_body(uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids, const uint32_t* __restrict__ table,
+                                         const LetterboxGeom& G, uint32_t group)
+{
+    typedef typename ElemOf<EB>::type Elem;
+    constexpr bool kHwc = LAYOUT == kLayoutHwc;
+    constexpr int kLineElems = 16 / EB;
+    const CanvasGeom& C = G.canvas;
+    const uint32_t cw = (uint32_t)C.cw, ch = (uint32_t)C.ch;
+    const uint32_t row_elems = kHwc ? 3u * cw : cw;                                      // a row of the tensor in memory order
+    const uint32_t total = 3u * cw * ch;                                                 // elements of the tensor (< 2^26)
+    const uint32_t ix0 = (kHwc ? 3u : 1u) * (uint32_t)C.x, ix1 = ix0 + (kHwc ? 3u : 1u) * (uint32_t)G.image.ow;      // the image's elements in its rows
+    const uint32_t iy0 = (uint32_t)C.y, iy1 = iy0 + (uint32_t)G.image.oh;
+    // the pad elements T[c][pad[c]] (uint8: the value itself)
+    uint32_t pe[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const uint32_t v = (C.pad >> (8 * c)) & 255u;
+        if constexpr (EB == 1) pe[c] = v;
+        else pe[c] = reinterpret_cast<const Elem*>(table)[c * 256 + v];
+    }
+    uint8_t* dst = tensor_ring + (size_t)frame_ids[blockIdx.z] * join64(G.image.ring.tensor_pitch_lo, G.image.ring.tensor_pitch_hi);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, (int)(total * EB), 0x00020000);
+    const uint32_t n_lines = (total * EB + 15u) / 16u;
+#pragma unroll 1
+    for (int step = 0; step < kPadLinesPerLane; step++) {
+        const uint32_t line = group * (uint32_t)kPadLinesPerGroup + (uint32_t)(step * kRgbaBlock) + threadIdx.x;
+        if (line >= n_lines) break;
+        const uint32_t e0 = line * (uint32_t)kLineElems;                                 // the line's first element ...
+        const uint32_t row = e0 / row_elems, q = e0 - row * row_elems;                   // ... lies in this row at this element
+        const uint32_t plane = kHwc ? 0u : row / ch, yrow = kHwc ? row : row - plane * ch;          // CHW: the row's channel, its row in the plane
+        const bool whole = e0 + (uint32_t)kLineElems <= total;
+        if (whole && q + (uint32_t)kLineElems <= row_elems) {                            // the line lies in one row
+            const bool image_row = yrow >= iy0 && yrow < iy1;
+            if (image_row && q >= ix0 && q + (uint32_t)kLineElems <= ix1) continue;      // image: its tile stores it
+            if (!image_row || q + (uint32_t)kLineElems <= ix0 || q >= ix1) {             // inside a pad run: one store
+                v4u v;
+                if constexpr (kHwc) {
+                    // dword j starts at channel (q + j * (4 / EB)) % 3
+                    const uint32_t ph = q % 3u;
+                    uint32_t d[3];
+#pragma unroll
+                    for (int s = 0; s < 3; s++) {
+                        if constexpr (EB == 4) d[s] = pe[s];
+                        else if constexpr (EB == 2) d[s] = pe[s] | (pe[(s + 1) % 3] << 16);
+                        else d[s] = pe[s] | (pe[(s + 1) % 3] << 8) | (pe[(s + 2) % 3] << 16) | (pe[s] << 24);
+                    }
+                    constexpr uint32_t kStep = (4 / EB) % 3;                             // channels a dword advances by
+                    const uint32_t p1 = (ph + kStep) % 3u, p2 = (ph + 2u * kStep) % 3u, p3 = (ph + 3u * kStep) % 3u;
+                    auto pick = [&](uint32_t p) { return p == 0u ? d[0] : (p == 1u ? d[1] : d[2]); };
+                    v = v4u{pick(ph), pick(p1), pick(p2), pick(p3)};
+                } else {
+                    const uint32_t e = plane == 0u ? pe[0] : (plane == 1u ? pe[1] : pe[2]);
+                    const uint32_t dw = EB == 4 ? e : (EB == 2 ? e * 0x00010001u : e * 0x01010101u);
+                    v = v4u{dw, dw, dw, dw};
+                }
+                __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)(line * 16u), 0, kAuxFrameStore);
+                continue;
+            }
+        }
+        // a line over a row's end, shared with the image or cut by the tensor's end: walk its elements
+        uint32_t ev[kLineElems];
+        uint32_t image_mask = 0u;
+        {
+            uint32_t r = row, qq = q, pl = plane, yy = yrow;
+#pragma unroll
+            for (int k = 0; k < kLineElems; k++) {
+                const bool in = e0 + (uint32_t)k < total;
+                const uint32_t c = kHwc ? qq % 3u : pl;
+                ev[k] = c == 0u ? pe[0] : (c == 1u ? pe[1] : pe[2]);
+                if (!in || (yy >= iy0 && yy < iy1 && qq >= ix0 && qq < ix1)) image_mask |= 1u << k;      // not this line's to store
+                if (++qq == row_elems) {
+                    qq = 0u; r++; yy++;
+                    if (!kHwc && yy == ch) { yy = 0u; pl++; }
+                }
+            }
+            (void)r;
+        }
+        if (image_mask == 0u) {          // over a row's end, yet wholly inside a run
+            uint32_t d[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if constexpr (EB == 4) d[j] = ev[j];
+                else if constexpr (EB == 2) d[j] = ev[2 * j] | (ev[2 * j + 1] << 16);
+                else d[j] = ev[4 * j] | (ev[4 * j + 1] << 8) | (ev[4 * j + 2] << 16) | (ev[4 * j + 3] << 24);
+            }
+            __builtin_amdgcn_raw_buffer_store_b128(v4u{d[0], d[1], d[2], d[3]}, rs, (int)(line * 16u), 0, kAuxFrameStore);
+        } else {
+#pragma unroll
+            for (int k = 0; k < kLineElems; k++)
+                if (!((image_mask >> k) & 1u)) pad_store_elem<EB>(ev[k], rs, line * 16u + (uint32_t)(k * EB));
+        }
+    }
+}
+
+template <int EB, int LAYOUT, class F>
+__global__ __launch_bounds__(kRgbaBlock) void k_letterbox(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
+                                                          const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
+                                                          LetterboxGeom G)
+{
+    const uint32_t tile_rows = (uint32_t)(G.image.oh + kResTileY - 1) / (uint32_t)kResTileY;
+    if (blockIdx.y >= tile_rows) {
+        pad_body<EB, LAYOUT>(tensor_ring, frame_ids, table, G, (blockIdx.y - tile_rows) * gridDim.x + blockIdx.x);
+        return;
+    }
+    resample_body<EB, LAYOUT, F>(planes_ring, tensor_ring, frame_ids, table, T, rt, G.image, G.canvas);
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

@@ -149,6 +149,11 @@ struct leon_pipeline {
     leon::ResampleGeom resample_geom{};
     int32_t resize_filter = LEON_RESIZE_TRIANGLE;      // LEON_RESIZE_*: which k_resample
     int32_t* d_resize_tabs = nullptr;
+    // ... placed in a padded canvas (leon_pipeline_tensor_canvas; canvas_on = 0: the tensor is the image): what get_tensor_canvas
+    // reports and k_letterbox's constants.  tensor_geom.width / height are the canvas's then, resample_geom.ow / oh the image's.
+    leon_pipeline_tensor_canvas tensor_canvas{};
+    leon::CanvasGeom canvas_geom{};
+    int canvas_on = 0;
     bool gpu_parser = false;
     // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
     // window n + 2, on a second stream: a parse launch lasts as long as its longest slice (one lane, symbol after symbol) and
@@ -643,6 +648,50 @@ int tensor_format_check(const leon_pipeline_config* cfg, const leon_pipeline_ten
     if (fm->layout != LEON_TENSOR_LAYOUT_CHW && fm->layout != LEON_TENSOR_LAYOUT_HWC) return fail(LEON_ERR_INVALID, "tensor format: layout %d", fm->layout);
     if (layout_out) *layout_out = fm->layout;
     return LEON_OK;
+}
+
+bool canvas_asked(const leon_pipeline_tensor_canvas* cv)
+{
+    if (!cv) return false;
+    int32_t any = cv->width | cv->height | cv->x | cv->y | cv->pad[0] | cv->pad[1] | cv->pad[2] | cv->image_width | cv->image_height;
+    for (int i = 0; i < 7; i++) any |= cv->reserved[i];
+    return any != 0;
+}
+
+// Every refusal of the canvas settings is here (the resize settings' own are resize_axis_build's)
+int tensor_canvas_check(const leon_pipeline_config* cfg, const leon_pipeline_tensor_resize* rz, const leon_pipeline_tensor_canvas* cv)
+{
+    if (!canvas_asked(cv)) return LEON_OK;
+    if (!(cfg->output & LEON_PIPELINE_OUTPUT_TENSOR)) return fail(LEON_ERR_INVALID, "tensor canvas settings (width %d, height %d) without LEON_PIPELINE_OUTPUT_TENSOR in output %d", cv->width, cv->height, cfg->output);
+    for (int i = 0; i < 7; i++)
+        if (cv->reserved[i]) return fail(LEON_ERR_INVALID, "tensor canvas: reserved word %d is %d, not 0", i, cv->reserved[i]);
+    if (!rz || rz->out_width < 1 || rz->out_height < 1) return fail(LEON_ERR_INVALID, "tensor canvas: no resize settings (out_width %d, out_height %d): the canvas places the resampled image", rz ? rz->out_width : 0, rz ? rz->out_height : 0);
+    if (cv->width < 1 || cv->width > 4096) return fail(LEON_ERR_INVALID, "tensor canvas: width %d is outside 1 .. 4096", cv->width);
+    if (cv->height < 1 || cv->height > 4096) return fail(LEON_ERR_INVALID, "tensor canvas: height %d is outside 1 .. 4096", cv->height);
+    if (cv->x < 0) return fail(LEON_ERR_INVALID, "tensor canvas: x %d is negative", cv->x);
+    if (cv->y < 0) return fail(LEON_ERR_INVALID, "tensor canvas: y %d is negative", cv->y);
+    if ((int64_t)cv->x + rz->out_width > cv->width) return fail(LEON_ERR_INVALID, "tensor canvas: x %d + out_width %d leaves the width %d", cv->x, rz->out_width, cv->width);
+    if ((int64_t)cv->y + rz->out_height > cv->height) return fail(LEON_ERR_INVALID, "tensor canvas: y %d + out_height %d leaves the height %d", cv->y, rz->out_height, cv->height);
+    for (int c = 0; c < 3; c++)
+        if (cv->pad[c] < 0 || cv->pad[c] > 255) return fail(LEON_ERR_INVALID, "tensor canvas: pad[%d] %d is outside 0 .. 255", c, cv->pad[c]);
+    if (cv->image_width && cv->image_width != rz->out_width) return fail(LEON_ERR_INVALID, "tensor canvas: image_width %d is not out_width %d", cv->image_width, rz->out_width);
+    if (cv->image_height && cv->image_height != rz->out_height) return fail(LEON_ERR_INVALID, "tensor canvas: image_height %d is not out_height %d", cv->image_height, rz->out_height);
+    return LEON_OK;
+}
+
+// What create makes of the canvas settings, behind plan_resize: the tensor takes the canvas's size, the image keeps resample_geom's
+void plan_canvas(leon_pipeline* p, const leon_pipeline_tensor_canvas* cv)
+{
+    leon_pipeline_tensor_geometry& g = p->tensor_geom;
+    leon_pipeline_tensor_canvas& c = p->tensor_canvas;
+    c = leon_pipeline_tensor_canvas{};
+    c.width = g.width; c.height = g.height; c.image_width = g.width; c.image_height = g.height;
+    if (!canvas_asked(cv)) return;
+    c.width = cv->width; c.height = cv->height; c.x = cv->x; c.y = cv->y;
+    for (int i = 0; i < 3; i++) c.pad[i] = cv->pad[i];
+    g.width = c.width; g.height = c.height;
+    p->canvas_on = 1;
+    p->canvas_geom = leon::CanvasGeom{c.width, c.height, c.x, c.y, (uint32_t)c.pad[0] | ((uint32_t)c.pad[1] << 8) | ((uint32_t)c.pad[2] << 16)};
 }
 
 bool resize_asked(const leon_pipeline_tensor_resize* rz)
@@ -1180,6 +1229,13 @@ template <class F> constexpr ResampleKernelsOfFilter kResampleKernelsOf = {{{leo
                                                                             {leon::k_resample<2, leon::kLayoutChw, F>, leon::k_resample<2, leon::kLayoutHwc, F>},
                                                                             {leon::k_resample<4, leon::kLayoutChw, F>, leon::k_resample<4, leon::kLayoutHwc, F>}}};
 constexpr ResampleKernelsOfFilter kResampleKernels[4] = {kResampleKernelsOf<leon::ResTriangle>, {}, {}, kResampleKernelsOf<leon::ResCubic>};
+// ... and k_letterbox where the resampled image lies in a padded canvas
+typedef void (*LetterboxKernel)(const uint8_t*, uint8_t*, const uint32_t*, const uint32_t*, const leon::Tables*, const int32_t*, leon::LetterboxGeom);
+struct LetterboxKernelsOfFilter { LetterboxKernel k[3][2]; };
+template <class F> constexpr LetterboxKernelsOfFilter kLetterboxKernelsOf = {{{leon::k_letterbox<1, leon::kLayoutChw, F>, leon::k_letterbox<1, leon::kLayoutHwc, F>},
+                                                                              {leon::k_letterbox<2, leon::kLayoutChw, F>, leon::k_letterbox<2, leon::kLayoutHwc, F>},
+                                                                              {leon::k_letterbox<4, leon::kLayoutChw, F>, leon::k_letterbox<4, leon::kLayoutHwc, F>}}};
+constexpr LetterboxKernelsOfFilter kLetterboxKernels[4] = {kLetterboxKernelsOf<leon::ResTriangle>, {}, {}, kLetterboxKernelsOf<leon::ResCubic>};
 
 // where the kernels find a frame's planes and its tensor
 leon::RingGeom ring_geom(const leon_pipeline* p)
@@ -1221,11 +1277,24 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
     }
     const bool listed = (eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc) && filter >= 0 && filter < 4;
     const TensorKernel kt = listed && !resized ? kTensorKernels[eb >> 1][layout] : nullptr;
-    const ResampleKernel kr = listed && resized ? kResampleKernels[filter].k[eb >> 1][layout] : nullptr;
-    if (!kt && !kr) return fail(LEON_ERR_INVALID, "tensor: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
+    const bool canvas = resized && p->canvas_on;
+    const ResampleKernel kr = listed && resized && !canvas ? kResampleKernels[filter].k[eb >> 1][layout] : nullptr;
+    const LetterboxKernel kl = listed && canvas ? kLetterboxKernels[filter].k[eb >> 1][layout] : nullptr;
+    leon::LetterboxGeom L{R, p->canvas_geom};
+    if (canvas) {
+        // the pad's workgroups behind the image's tile rows: whole rows of gx workgroups that cover every 16-byte line of the tensor,
+        // kPadLinesPerGroup each (the last ones may find nothing); none when the image fills the canvas
+        const bool pad = L.canvas.cw != R.ow || L.canvas.ch != R.oh;
+        const size_t lines = (p->tensor_bytes + 15) / 16, groups = pad ? (lines + leon::kPadLinesPerGroup - 1) / leon::kPadLinesPerGroup : 0;
+        gy += (unsigned)((groups + gx - 1) / gx);
+        if (gy > 65535u) return fail(LEON_ERR_INVALID, "tensor canvas: %u workgroup rows", gy);
+    }
+    if (!kt && !kr && !kl) return fail(LEON_ERR_INVALID, "tensor: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
     for (size_t at = 0; at < n; at += 65535) {
         const dim3 grid(gx, gy, (unsigned)std::min<size_t>(65535, n - at)), block(leon::kRgbaBlock);
-        if (resized) hipLaunchKernelGGL(kr, grid, block, 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, (const uint32_t*)(dv + at),
+        if (canvas) hipLaunchKernelGGL(kl, grid, block, 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, (const uint32_t*)(dv + at),
+                                       (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, L);
+        else if (resized) hipLaunchKernelGGL(kr, grid, block, 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, (const uint32_t*)(dv + at),
                                         (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)p->d_resize_tabs, R);
         else hipLaunchKernelGGL(kt, grid, block, 0, p->dec->stream, (const uint8_t*)p->d_planes, p->d_tensor, (const uint32_t*)(dv + at),
                                 (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, G);
@@ -1510,7 +1579,7 @@ constexpr size_t kMaxVlcIndexLds = 160 * 1024 - 512;
 // Create, stage 1: what the config and the stream decide -- the shards, the run, W / R / K, the longest GOP, the front
 // end, the output and its roads, info.  No HIP call and no allocation: a refused config leaves nothing to free but p.
 int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tcfg, const leon_pipeline_tensor_resize* rz,
-                  const leon_pipeline_tensor_format* fm, const uint8_t* stream, size_t bytes, size_t valid_bytes)
+                  const leon_pipeline_tensor_format* fm, const leon_pipeline_tensor_canvas* cv, const uint8_t* stream, size_t bytes, size_t valid_bytes)
 {
     leon_vlc_stream* st = nullptr;
     // the container header, the key map and the first sequence header must have arrived
@@ -1613,6 +1682,9 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
         p->tensor_table.resize(3 * 256 * p->tensor_elem);
         const int rrc = plan_resize(p, rz);
         if (rrc != LEON_OK) return rrc;
+        const int crc = tensor_canvas_check(cfg, rz, cv);
+        if (crc != LEON_OK) return crc;
+        plan_canvas(p, cv);
         p->tensor_bytes = (size_t)3 * p->tensor_geom.height * p->tensor_geom.width * p->tensor_elem;
         p->tensor_pitch = pad256(p->tensor_bytes);
         p->info.tensor_dtype = p->tensor_dtype;
@@ -1623,6 +1695,7 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
     } else if (tcfg && tcfg->dtype) return fail(LEON_ERR_INVALID, "tensor dtype %d without LEON_PIPELINE_OUTPUT_TENSOR in output", tcfg->dtype);
     else if (resize_asked(rz)) return fail(LEON_ERR_INVALID, "resize settings (%d x %d) without LEON_PIPELINE_OUTPUT_TENSOR in output %d", rz->out_width, rz->out_height, cfg->output);
     else if (const int frc = tensor_format_check(cfg, fm, nullptr)) return frc;
+    else if (const int crc = tensor_canvas_check(cfg, rz, cv)) return crc;
     // the frames' planes (output YCbCr): the layout of include/leon_pipeline.h, one record per frame, A behind Cr for yuva
     p->output = cfg->output ? cfg->output : LEON_PIPELINE_OUTPUT_RGBA;
     p->planes_geom = planes_layout(p->vinfo.frame_width, p->vinfo.frame_height, &p->planes_bytes);
@@ -1888,12 +1961,43 @@ int leon_pipeline_create_tensor_format(const leon_pipeline_config* cfg, const le
                                        const leon_pipeline_tensor_format* format, const uint8_t* stream, size_t bytes, size_t valid_bytes,
                                        leon_pipeline_callback cb, void* user, leon_pipeline** out)
 {
+    return leon_pipeline_create_tensor_canvas(cfg, tensor, resize, format, nullptr, stream, bytes, valid_bytes, cb, user, out);
+}
+
+int leon_pipeline_get_tensor_canvas(leon_pipeline* p, leon_pipeline_tensor_canvas* out)
+{
+    if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR)) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    *out = p->tensor_canvas;
+    return LEON_OK;
+}
+
+int leon_pipeline_letterbox(int32_t src_width, int32_t src_height, int32_t canvas_width, int32_t canvas_height,
+                            leon_pipeline_tensor_resize* resize, leon_pipeline_tensor_canvas* canvas)
+{
+    if (!resize || !canvas) return fail(LEON_ERR_INVALID, "null argument");
+    if (src_width < 1 || src_height < 1) return fail(LEON_ERR_INVALID, "letterbox: source %d x %d", src_width, src_height);
+    if (canvas_width < 1 || canvas_height < 1) return fail(LEON_ERR_INVALID, "letterbox: canvas %d x %d", canvas_width, canvas_height);
+    const int64_t sw = src_width, sh = src_height, cw = canvas_width, ch = canvas_height;
+    int64_t ow, oh;
+    if (cw * sh <= ch * sw) { ow = cw; oh = std::max<int64_t>(1, (2 * sh * cw + sw) / (2 * sw)); }
+    else { oh = ch; ow = std::max<int64_t>(1, (2 * sw * ch + sh) / (2 * sh)); }
+    resize->out_width = (int32_t)ow; resize->out_height = (int32_t)oh;
+    canvas->width = canvas_width; canvas->height = canvas_height;
+    canvas->x = (int32_t)((cw - ow) / 2); canvas->y = (int32_t)((ch - oh) / 2);
+    return LEON_OK;
+}
+
+int leon_pipeline_create_tensor_canvas(const leon_pipeline_config* cfg, const leon_pipeline_tensor_config* tensor, const leon_pipeline_tensor_resize* resize,
+                                       const leon_pipeline_tensor_format* format, const leon_pipeline_tensor_canvas* canvas, const uint8_t* stream,
+                                       size_t bytes, size_t valid_bytes, leon_pipeline_callback cb, void* user, leon_pipeline** out)
+{
     if (!cfg || !stream || bytes < 16 || !out) return fail(LEON_ERR_INVALID, "null argument");
     if (valid_bytes > bytes) return fail(LEON_ERR_INVALID, "%zu valid bytes of a stream of %zu", valid_bytes, bytes);
     *out = nullptr;
     leon_pipeline* p = new (std::nothrow) leon_pipeline();
     if (!p) return fail(LEON_ERR_NOMEM, "out of host memory");
-    int rc = plan_pipeline(p, cfg, tensor, resize, format, stream, bytes, valid_bytes);
+    int rc = plan_pipeline(p, cfg, tensor, resize, format, canvas, stream, bytes, valid_bytes);
     if (rc != LEON_OK) { delete p; return rc; }
     p->cb = cb;
     p->user = user;

@@ -36,6 +36,13 @@
  *                                  opts.tensorDtype 'uint8': the elements are the 8-bit colour values themselves (no tensorScale /
  *                                  tensorBias), readTensor returns a Uint8Array; opts.tensorLayout 'chw' (default) or 'hwc': channels
  *                                  last, [H][W][3] -- uint8 hwc is the packed RGB frame, 3 bytes per pixel; stats() reports tensorLayout
+ *                                  opts.tensorCanvas [h, w] (with tensorSize): the resampled image lies in an h x w tensor, its top-left
+ *                                  element at opts.tensorOrigin [x, y] (default: centred), every other element at opts.tensorPadValue
+ *                                  [r, g, b] (8-bit colour values through the element table; default 0) -- every element is written every
+ *                                  window; readTensor returns the canvas; stats() reports tensorWidth / tensorHeight (the canvas's) and the
+ *                                  image rectangle tensorImageX, tensorImageY, tensorImageWidth, tensorImageHeight.
+ *                                  opts.tensorLetterbox [h, w]: tensorSize, tensorCanvas and tensorOrigin derived from the crop box or the
+ *                                  frame with the aspect ratio kept (LeonPipeline.letterbox = leon_pipeline_letterbox)
  *   p.releaseWindow(window); p.stats(); p.destroy();
  * Open GOPs (closed_gop = 0) need no option: their leading B pictures predict from the GOP before; where that GOP is not decoded (start,
  * seek target, broken_link) they are not delivered and the GOP's frames start at its I picture's displayIndex (include/leon_pipeline.h).
@@ -84,6 +91,14 @@ class LeonPipeline extends EventEmitter {
     const [tensorOutHeight, tensorOutWidth] = ints(opts.tensorSize, 2, 'tensorSize: [height, width]');
     const [tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight] = ints(opts.tensorCrop, 4, 'tensorCrop: [x, y, width, height]');
     const resize = { tensorOutHeight, tensorOutWidth, tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight, tensorFilter };
+    // tensorCanvas [h, w], tensorOrigin [x, y], tensorPadValue [r, g, b]: the image in a padded canvas; tensorLetterbox [h, w] derives them
+    const [tensorCanvasHeight, tensorCanvasWidth] = ints(opts.tensorCanvas, 2, 'tensorCanvas: [height, width]');
+    const [tensorOriginX, tensorOriginY] = ints(opts.tensorOrigin, 2, 'tensorOrigin: [x, y]');
+    const [tensorPadR, tensorPadG, tensorPadB] = ints(opts.tensorPadValue, 3, 'tensorPadValue: [r, g, b]');
+    const [tensorLetterboxHeight, tensorLetterboxWidth] = ints(opts.tensorLetterbox, 2, 'tensorLetterbox: [height, width]');
+    const tensorOriginSet = opts.tensorOrigin === undefined || opts.tensorOrigin === null ? 0 : 1;
+    Object.assign(resize, { tensorCanvasHeight, tensorCanvasWidth, tensorOriginX, tensorOriginY, tensorOriginSet, tensorPadR, tensorPadG, tensorPadB,
+      tensorLetterboxHeight, tensorLetterboxWidth });
     this._p = addon.createPipeline(stream, Object.assign({}, opts, { output, tensorDtype, tensorLayout }, resize), (w, frames, status) => this._deliver(w, frames, status));
   }
 
@@ -126,5 +141,9 @@ class LeonPipeline extends EventEmitter {
   stats() { return this._p.stats(); }
   destroy() { if (this._p) { this._p.destroy(); this._p = null; } }
 }
+
+// letterbox(srcWidth, srcHeight, canvasWidth, canvasHeight) -> [outWidth, outHeight, x, y]: leon_pipeline_letterbox (no device)
+LeonPipeline.letterbox = (srcWidth, srcHeight, canvasWidth, canvasHeight, backend) =>
+  (backend || require(path.join(__dirname, '..', 'napi', 'leon_napi.node'))).letterbox(srcWidth, srcHeight, canvasWidth, canvasHeight);
 
 module.exports = { LeonPipeline };

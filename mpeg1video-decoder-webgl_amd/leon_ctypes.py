@@ -38,6 +38,7 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_create_tensor", "leon_pipeline_tensor_table", "leon_pipeline_window_tensors", "leon_pipeline_read_tensor",
     "leon_pipeline_create_tensor_resized", "leon_pipeline_resize_weights", "leon_pipeline_get_tensor_geometry",
     "leon_pipeline_create_tensor_format", "leon_pipeline_get_tensor_shape",
+    "leon_pipeline_create_tensor_canvas", "leon_pipeline_get_tensor_canvas", "leon_pipeline_letterbox",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -184,6 +185,28 @@ def resize_rgb(rgb, crop, size, filter=RESIZE_TRIANGLE):
     return _resize_pass(hz.transpose(1, 0, 2), fy - lo, ny, wy).transpose(1, 0, 2).copy()
 
 
+def letterbox(src_width, src_height, canvas_width, canvas_height):
+    """leon_pipeline_letterbox: the source scaled to fit the canvas with its aspect ratio kept, and centred ->
+    (out_width, out_height, x, y).  The library's integers (no device touched)."""
+    rz, cv = PipelineTensorResize(), PipelineTensorCanvas()
+    _chk(load().leon_pipeline_letterbox(int(src_width), int(src_height), int(canvas_width), int(canvas_height), C.byref(rz), C.byref(cv)))
+    return rz.out_width, rz.out_height, cv.x, cv.y
+
+
+def canvas_rgb(rgb, crop, size, canvas, origin, pad=(0, 0, 0), filter=RESIZE_TRIANGLE):
+    """The canvas tensor output's 8-bit colour values, in numpy: resize_rgb(rgb, crop, size, filter) with its top-left pixel at
+    origin = (x, y) of a canvas = (height, width) array whose other pixels are pad = (r, g, b) -> [height, width, 3] uint8
+    (include/leon_pipeline.h, leon_pipeline_tensor_canvas)."""
+    image = resize_rgb(np.asarray(rgb)[..., :3], crop, size, filter)
+    (ch, cw), (x, y), (oh, ow) = canvas, origin, size
+    if x < 0 or y < 0 or x + ow > cw or y + oh > ch:
+        raise ValueError("the image %d x %d at (%d, %d) leaves the canvas %d x %d" % (ow, oh, x, y, cw, ch))
+    out = np.empty((ch, cw, 3), dtype=np.uint8)
+    out[:] = np.asarray(pad, dtype=np.uint8)
+    out[y:y + oh, x:x + ow] = image
+    return out
+
+
 def planes_layout(frame_width, frame_height, alpha=False):
     """the device layout of a frame's planes (include/leon_pipeline.h, leon_pipeline_config.output): rows padded to 64 bytes,
     planes on 256-byte boundaries, [Y | Cb | Cr (| A)].  Offsets are from the Y pointer; `bytes` is one frame's record."""
@@ -265,6 +288,11 @@ class PipelineTensorGeometry(C.Structure):
 
 class PipelineTensorFormat(C.Structure):
     _fields_ = [("layout", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class PipelineTensorCanvas(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("pad", C.c_int32 * 3),
+                ("image_width", C.c_int32), ("image_height", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class PipelineTensorShape(C.Structure):
@@ -370,6 +398,11 @@ def load():
     lib.leon_pipeline_create_tensor_format.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.POINTER(PipelineTensorResize),
                                                        C.POINTER(PipelineTensorFormat), C.c_void_p, C.c_size_t, C.c_size_t, PIPELINE_CB, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.leon_pipeline_get_tensor_shape.argtypes = [C.c_void_p, C.POINTER(PipelineTensorShape)]
+    lib.leon_pipeline_create_tensor_canvas.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.POINTER(PipelineTensorResize),
+                                                       C.POINTER(PipelineTensorFormat), C.POINTER(PipelineTensorCanvas), C.c_void_p, C.c_size_t, C.c_size_t,
+                                                       PIPELINE_CB, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.leon_pipeline_get_tensor_canvas.argtypes = [C.c_void_p, C.POINTER(PipelineTensorCanvas)]
+    lib.leon_pipeline_letterbox.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineTensorResize), C.POINTER(PipelineTensorCanvas)]
     lib.leon_pipeline_tensor_table.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.c_void_p]
     lib.leon_pipeline_window_tensors.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int32]
     lib.leon_pipeline_read_tensor.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
@@ -651,13 +684,31 @@ class Pipeline:
     "bicubic" (or the RESIZE_* integers).
     tensor_dtype="uint8": the elements are the 8-bit colour values themselves (no scale / bias).  tensor_layout="hwc": channels last
     -- every shape above is [H, W, 3] ([N, H, W, 3] for window_tensor), a packed uint8 HWC frame is 3 bytes per pixel; tensor_shape
-    (PipelineTensorShape) has the element type, the layout and the strides in elements."""
+    (PipelineTensorShape) has the element type, the layout and the strides in elements.
+    tensor_canvas=(H, W) (with tensor_size): the resampled image lies in an H x W tensor, its top-left element at tensor_origin=(x, y)
+    (None: centred, the odd pixel right or below), every other element at tensor_pad_value=(r, g, b), 8-bit colour values that go through
+    the element table like the image's -- element = table[c][canvas_rgb(rgb, crop, size, canvas, origin, pad, filter)]; every tensor shape
+    above is the canvas's, tensor_canvas_geometry (PipelineTensorCanvas) has the image rectangle.  Every element is written every window.
+    tensor_letterbox=(H, W): tensor_size, tensor_canvas and tensor_origin derived with letterbox() from the crop box, or the frame:
+    the aspect ratio kept, the image centred."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
                  output="rgba", tensor_dtype="float16", tensor_scale=None, tensor_bias=None, tensor_size=None, tensor_crop=None, tensor_filter=RESIZE_TRIANGLE,
-                 tensor_layout="chw"):
+                 tensor_layout="chw", tensor_canvas=None, tensor_origin=None, tensor_pad_value=None, tensor_letterbox=None):
         self.lib = load()
+        if tensor_letterbox is not None:
+            if tensor_size is not None or tensor_canvas is not None or tensor_origin is not None:
+                raise ValueError("tensor_letterbox derives tensor_size, tensor_canvas and tensor_origin: give it alone")
+            if tensor_crop is not None and any(tensor_crop):
+                src_w, src_h = tensor_crop[2], tensor_crop[3]
+            else:          # the frame's size, from the stream's first sequence header
+                import leon_vlc_ctypes as V
+                st = V.Stream(bytes(data) if valid_bytes is None else bytes(data[:int(valid_bytes)]), threads=1)
+                src_w, src_h = st.info.frame_width, st.info.frame_height
+                st.close()
+            ow, oh, x, y = letterbox(src_w, src_h, tensor_letterbox[1], tensor_letterbox[0])
+            tensor_size, tensor_canvas, tensor_origin = (oh, ow), tuple(tensor_letterbox), (x, y)
         self.device_id = device_id
         # a name of PIPELINE_OUTPUTS, or the raw bit set (anything the library does not know is refused by create)
         out_bits = (PIPELINE_OUTPUTS.get(output) or PIPELINE_TENSOR_OUTPUTS[output]) if isinstance(output, str) else int(output)
@@ -674,6 +725,14 @@ class Pipeline:
         fcfg = None
         if _tensor_layout_code(tensor_layout) != TENSOR_LAYOUT_CHW:      # only a non-default format goes through leon_pipeline_create_tensor_format
             fcfg = PipelineTensorFormat(_tensor_layout_code(tensor_layout))
+        ccfg = None
+        if tensor_canvas is not None or tensor_origin is not None or tensor_pad_value is not None:      # (the library refuses what does not go together)
+            ch_, cw_ = (0, 0) if tensor_canvas is None else tensor_canvas
+            if tensor_origin is None:          # centred, as leon_pipeline_letterbox centres
+                oh_, ow_ = (0, 0) if tensor_size is None else tensor_size
+                tensor_origin = ((int(cw_) - int(ow_)) // 2, (int(ch_) - int(oh_)) // 2) if int(cw_) >= int(ow_) and int(ch_) >= int(oh_) else (0, 0)
+            pr, pg, pb = (0, 0, 0) if tensor_pad_value is None else tensor_pad_value
+            ccfg = PipelineTensorCanvas(int(cw_), int(ch_), int(tensor_origin[0]), int(tensor_origin[1]), (C.c_int32 * 3)(int(pr), int(pg), int(pb)))
         self._data = (C.c_uint8 * len(data)).from_buffer_copy(data)      # must outlive the pipeline
         self._on_window = on_window
         self.windows = 0
@@ -726,7 +785,11 @@ class Pipeline:
         h = C.c_void_p()
         self.h = None
         # valid_bytes: the stream is still arriving (leon_pipeline_create_partial); feed() reports progress
-        if fcfg is not None:
+        if ccfg is not None:
+            rc = self.lib.leon_pipeline_create_tensor_canvas(C.byref(cfg), None if tcfg is None else C.byref(tcfg), None if rcfg is None else C.byref(rcfg),
+                                                             None if fcfg is None else C.byref(fcfg), C.byref(ccfg), self._data, len(data),
+                                                             len(data) if valid_bytes is None else int(valid_bytes), self._cb, None, C.byref(h))
+        elif fcfg is not None:
             rc = self.lib.leon_pipeline_create_tensor_format(C.byref(cfg), None if tcfg is None else C.byref(tcfg), None if rcfg is None else C.byref(rcfg), C.byref(fcfg),
                                                              self._data, len(data), len(data) if valid_bytes is None else int(valid_bytes), self._cb, None, C.byref(h))
         elif rcfg is not None:
@@ -755,6 +818,12 @@ class Pipeline:
             shape = PipelineTensorShape()
             rc = self.lib.leon_pipeline_get_tensor_shape(self.h, C.byref(shape))
             self.tensor_shape = shape
+        # where the image lies in the tensor (without canvas settings: all of it)
+        self.tensor_canvas_geometry = None
+        if rc == OK and info.tensor_dtype:
+            canvas = PipelineTensorCanvas()
+            rc = self.lib.leon_pipeline_get_tensor_canvas(self.h, C.byref(canvas))
+            self.tensor_canvas_geometry = canvas
         ready.set()
         _chk(rc)
 

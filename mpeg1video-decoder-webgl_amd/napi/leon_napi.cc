@@ -17,6 +17,7 @@
 #include <cstring>
 #include "../../include/leon.h"
 #include "../../include/leon_pipeline.h"
+#include "../../include/leon_vlc.h"
 #include <map>
 #include <mutex>
 #include <vector>
@@ -390,6 +391,7 @@ struct PipeHandle {
     leon_pipeline_info info{};
     leon_pipeline_tensor_geometry tensor_geom{};      // all 0 without tensor output
     leon_pipeline_tensor_shape tensor_shape{};        // the same
+    leon_pipeline_tensor_canvas tensor_canvas{};      // the same
     int64_t last_window = -1;               // notify thread, under mu
     int64_t floor = 0;                      // JavaScript thread: the first window of the latest seek
     bool seeked = false;
@@ -629,7 +631,10 @@ napi_value PipeStats(napi_env env, napi_callback_info info)
         {"chromaWidth", (double)h->info.chroma_width}, {"chromaHeight", (double)h->info.chroma_height},
         {"tensorDtype", (double)h->info.tensor_dtype}, {"tensorElementBytes", (double)h->info.tensor_element_bytes},
         {"tensorFrameBytes", (double)h->info.tensor_frame_bytes}, {"tensorFramePitch", (double)h->info.tensor_frame_pitch},
-        {"tensorGopPitch", (double)h->info.tensor_gop_pitch}, {"tensorWidth", (double)h->tensor_geom.width}, {"tensorHeight", (double)h->tensor_geom.height}};
+        {"tensorGopPitch", (double)h->info.tensor_gop_pitch}, {"tensorWidth", (double)h->tensor_geom.width}, {"tensorHeight", (double)h->tensor_geom.height},
+        // where the resampled image lies in the tensor (leon_pipeline_tensor_canvas; without a canvas: all of it)
+        {"tensorImageX", (double)h->tensor_canvas.x}, {"tensorImageY", (double)h->tensor_canvas.y},
+        {"tensorImageWidth", (double)h->tensor_canvas.image_width}, {"tensorImageHeight", (double)h->tensor_canvas.image_height}};
     for (auto& e : kv) {
         NAPI_OK(napi_create_double(env, e.val, &v));
         NAPI_OK(napi_set_named_property(env, o, e.k, v));
@@ -759,8 +764,45 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
         napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
         return nullptr;
     }
+    // ... placed in a padded canvas (leon_pipeline_tensor_canvas; js/leon_pipeline.js spreads tensorCanvas / tensorOrigin / tensorPadValue /
+    // tensorLetterbox into these).  tensorLetterbox: out size, canvas and origin from leon_pipeline_letterbox of the crop box, or of the
+    // frame (the stream's first sequence header)
+    leon_pipeline_tensor_canvas ccfg;
+    memset(&ccfg, 0, sizeof ccfg);
+    int32_t lb_w = 0, lb_h = 0, origin_set = 0;
+    if (!(get_i32(env, argv[1], "tensorCanvasWidth", &ccfg.width, 0) && get_i32(env, argv[1], "tensorCanvasHeight", &ccfg.height, 0) &&
+          get_i32(env, argv[1], "tensorOriginX", &ccfg.x, 0) && get_i32(env, argv[1], "tensorOriginY", &ccfg.y, 0) && get_i32(env, argv[1], "tensorOriginSet", &origin_set, 0) &&
+          get_i32(env, argv[1], "tensorPadR", &ccfg.pad[0], 0) && get_i32(env, argv[1], "tensorPadG", &ccfg.pad[1], 0) && get_i32(env, argv[1], "tensorPadB", &ccfg.pad[2], 0) &&
+          get_i32(env, argv[1], "tensorLetterboxWidth", &lb_w, 0) && get_i32(env, argv[1], "tensorLetterboxHeight", &lb_h, 0))) {
+        napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
+        return nullptr;
+    }
+    if (lb_w || lb_h) {
+        if (rcfg.out_width || rcfg.out_height || ccfg.width || ccfg.height || origin_set) {
+            napi_throw_type_error(env, nullptr, "createPipeline: tensorLetterbox derives tensorSize, tensorCanvas and tensorOrigin: give it alone");
+            return nullptr;
+        }
+        int32_t sw = rcfg.crop_width, sh = rcfg.crop_height;
+        if (!(rcfg.crop_x | rcfg.crop_y | rcfg.crop_width | rcfg.crop_height)) {
+            leon_vlc_stream* st = nullptr;
+            leon_vlc_info vi;
+            if (leon_vlc_open((const uint8_t*)data, len, 1, &st) != LEON_VLC_OK) {
+                napi_throw_error(env, nullptr, leon_vlc_last_error());
+                return nullptr;
+            }
+            leon_vlc_get_info(st, &vi);
+            leon_vlc_close(st);
+            sw = vi.frame_width; sh = vi.frame_height;
+        }
+        const int lrc = leon_pipeline_letterbox(sw, sh, lb_w, lb_h, &rcfg, &ccfg);
+        if (lrc != LEON_OK) return throw_leon(env, lrc);
+    } else if ((ccfg.width || ccfg.height) && !origin_set) {          // centred, as leon_pipeline_letterbox centres (what does not fit is create's to refuse)
+        ccfg.x = ccfg.width >= rcfg.out_width ? (ccfg.width - rcfg.out_width) / 2 : 0;
+        ccfg.y = ccfg.height >= rcfg.out_height ? (ccfg.height - rcfg.out_height) / 2 : 0;
+    }
+    const bool canvas = (ccfg.width | ccfg.height | ccfg.x | ccfg.y | ccfg.pad[0] | ccfg.pad[1] | ccfg.pad[2]) != 0;
     const bool resized = (rcfg.out_width | rcfg.out_height | rcfg.crop_x | rcfg.crop_y | rcfg.crop_width | rcfg.crop_height | rcfg.filter) != 0;
-    const bool tensor = (cfg.output & LEON_PIPELINE_OUTPUT_TENSOR) != 0 || tcfg.dtype != 0 || resized || fcfg.layout != 0;
+    const bool tensor = (cfg.output & LEON_PIPELINE_OUTPUT_TENSOR) != 0 || tcfg.dtype != 0 || resized || fcfg.layout != 0 || canvas;
     PipeHandle* h = new PipeHandle();
     napi_value name;
     NAPI_OK(napi_create_string_utf8(env, "leon pipeline frames", NAPI_AUTO_LENGTH, &name));
@@ -792,7 +834,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
             }
         }
     }
-    int rc = tensor ? leon_pipeline_create_tensor_format(&cfg, &tcfg, resized ? &rcfg : nullptr, fcfg.layout ? &fcfg : nullptr, (const uint8_t*)data, len, partial ? (size_t)valid : len, pipe_native_cb, h, &h->p)
+    int rc = tensor ? leon_pipeline_create_tensor_canvas(&cfg, &tcfg, resized ? &rcfg : nullptr, fcfg.layout ? &fcfg : nullptr, canvas ? &ccfg : nullptr, (const uint8_t*)data, len, partial ? (size_t)valid : len, pipe_native_cb, h, &h->p)
            : partial ? leon_pipeline_create_partial(&cfg, (const uint8_t*)data, len, (size_t)valid, pipe_native_cb, h, &h->p)
                      : leon_pipeline_create(&cfg, (const uint8_t*)data, len, pipe_native_cb, h, &h->p);
     if (rc != LEON_OK) {
@@ -805,6 +847,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     if (h->info.tensor_dtype) {
         leon_pipeline_get_tensor_geometry(h->p, &h->tensor_geom);
         leon_pipeline_get_tensor_shape(h->p, &h->tensor_shape);
+        leon_pipeline_get_tensor_canvas(h->p, &h->tensor_canvas);
     }
     napi_value obj;
     NAPI_OK(napi_create_object(env, &obj));
@@ -817,6 +860,34 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
         NAPI_OK(napi_set_named_property(env, obj, m.name, fn));
     }
     return obj;
+}
+
+// letterbox(srcWidth, srcHeight, canvasWidth, canvasHeight) -> [outWidth, outHeight, x, y]: leon_pipeline_letterbox, no device
+napi_value Letterbox(napi_env env, napi_callback_info info)
+{
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    int32_t a[4] = {0, 0, 0, 0};
+    for (size_t k = 0; k < 4; k++)
+        if (argc < 4 || napi_get_value_int32(env, argv[k], &a[k]) != napi_ok) {
+            napi_throw_type_error(env, nullptr, "letterbox(srcWidth, srcHeight, canvasWidth, canvasHeight)");
+            return nullptr;
+        }
+    leon_pipeline_tensor_resize rz;
+    leon_pipeline_tensor_canvas cv;
+    memset(&rz, 0, sizeof rz);
+    memset(&cv, 0, sizeof cv);
+    const int rc = leon_pipeline_letterbox(a[0], a[1], a[2], a[3], &rz, &cv);
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    const int32_t r[4] = {rz.out_width, rz.out_height, cv.x, cv.y};
+    napi_value arr, v;
+    NAPI_OK(napi_create_array_with_length(env, 4, &arr));
+    for (uint32_t k = 0; k < 4; k++) {
+        NAPI_OK(napi_create_int32(env, r[k], &v));
+        NAPI_OK(napi_set_element(env, arr, k, v));
+    }
+    return arr;
 }
 
 napi_value AbiVersion(napi_env env, napi_callback_info)
@@ -837,6 +908,8 @@ napi_value Init(napi_env env, napi_value exports)
     NAPI_OK(napi_set_named_property(env, exports, "create", fn));
     NAPI_OK(napi_create_function(env, "createPipeline", NAPI_AUTO_LENGTH, CreatePipeline, nullptr, &fn));
     NAPI_OK(napi_set_named_property(env, exports, "createPipeline", fn));
+    NAPI_OK(napi_create_function(env, "letterbox", NAPI_AUTO_LENGTH, Letterbox, nullptr, &fn));
+    NAPI_OK(napi_set_named_property(env, exports, "letterbox", fn));
     NAPI_OK(napi_create_function(env, "abiVersion", NAPI_AUTO_LENGTH, AbiVersion, nullptr, &fn));
     NAPI_OK(napi_set_named_property(env, exports, "abiVersion", fn));
     return exports;

@@ -36,6 +36,10 @@ def main():
     ap.add_argument("--tensor-size", type=int, nargs=2, metavar=("H", "W"), help="tensors resampled on the device to H x W (leon_pipeline_tensor_resize)")
     ap.add_argument("--tensor-crop", type=int, nargs=4, metavar=("X", "Y", "W", "H"), help="the crop box --tensor-size resamples (frame pixels; default: the whole frame)")
     ap.add_argument("--tensor-filter", choices=["triangle", "bicubic"], default="triangle", help="the filter of --tensor-size (leon_pipeline_tensor_resize.filter)")
+    ap.add_argument("--tensor-canvas", type=int, nargs=2, metavar=("H", "W"), help="with --tensor-size: the resampled image centred in an H x W tensor (leon_pipeline_tensor_canvas)")
+    ap.add_argument("--tensor-letterbox", type=int, nargs=2, metavar=("H", "W"),
+                    help="the crop box (or the frame) resampled with its aspect ratio kept and centred in an H x W tensor (leon_pipeline_letterbox): instead of --tensor-size")
+    ap.add_argument("--tensor-pad-value", type=int, nargs=3, metavar=("R", "G", "B"), help="the 8-bit colour value of the canvas outside the image (default 0 0 0)")
     ap.add_argument("--host-resize", type=int, nargs=2, metavar=("H", "W"),
                     help="the route without --tensor-size, for comparison: full-size tensors, and the callback resizes every window's window_tensor view "
                          "with torch.nn.functional.interpolate(mode='bilinear', antialias=True)")
@@ -85,12 +89,13 @@ def main():
     t0 = time.perf_counter()
     pipe = L.Pipeline(data, parser_threads=a.threads, gops_per_window=a.window, windows_in_flight=a.inflight, loop=a.loop, gpu_parser=a.gpu_parser,
                       output=a.output, tensor_dtype=a.tensor_dtype, tensor_size=a.tensor_size, tensor_crop=a.tensor_crop, tensor_layout=a.tensor_layout, tensor_filter=a.tensor_filter,
-                      on_window=on_window)
+                      tensor_canvas=a.tensor_canvas, tensor_letterbox=a.tensor_letterbox, tensor_pad_value=a.tensor_pad_value, on_window=on_window)
     free1 = free_device_bytes()
     pool = L.pool_stats()
     pipe.wait()
     wall = time.perf_counter() - t0
     s = pipe.stats()
+    canvas = pipe.tensor_canvas_geometry if (a.tensor_canvas or a.tensor_letterbox) else None
     pipe.close()
     mbs = (pipe.info.coded_width // 16) * (pipe.info.coded_height // 16)
     print(json.dumps({
@@ -98,7 +103,9 @@ def main():
                   % (pipe.info.frame_width, pipe.info.frame_height, {"rgba": "RGBA", "ycbcr": "YCbCr planes", "both": "RGBA + YCbCr planes", "tensor": "tensors", "rgba+tensor": "RGBA + tensors",
                      "ycbcr+tensor": "YCbCr planes + tensors", "all": "RGBA + YCbCr planes + tensors"}[a.output]),
         "output": a.output, "tensor_dtype": a.tensor_dtype if pipe.info.tensor_dtype else None, "tensor_layout": a.tensor_layout if pipe.info.tensor_dtype else None,
-        "tensor_frame_bytes": pipe.info.tensor_frame_bytes, "tensor_size": a.tensor_size, "tensor_crop": a.tensor_crop, "tensor_filter": a.tensor_filter if a.tensor_size else None, "host_resize": a.host_resize, "windows_in_flight": a.inflight,
+        "tensor_frame_bytes": pipe.info.tensor_frame_bytes, "tensor_size": a.tensor_size, "tensor_crop": a.tensor_crop, "tensor_filter": a.tensor_filter if (a.tensor_size or a.tensor_letterbox) else None,
+        "tensor_canvas": [canvas.height, canvas.width] if canvas else None, "tensor_image": [canvas.x, canvas.y, canvas.image_width, canvas.image_height] if canvas else None,
+        "tensor_pad_value": list(canvas.pad) if canvas else None, "host_resize": a.host_resize, "windows_in_flight": a.inflight,
         "value": s["pictures"] / s["seconds"], "macroblocks_per_s": s["pictures"] * mbs / s["seconds"],
         "pictures": s["pictures"], "seconds": s["seconds"], "wall_seconds_incl_setup": wall, "windows": s["windows"],
         "slice_layer": "GPU (csrc/leon_vlc_gpu.h)" if a.gpu_parser else "host threads (libleon_vlc.so)",
