@@ -387,6 +387,53 @@ int leon_pipeline_window_tensors(leon_pipeline* p, int64_t window, void** out, i
 /* copy the tensor of frame `index` of such a window to host memory, packed (tensor_frame_bytes: [3][height][width] of the geometry, or
  * [height][width][3] with LEON_TENSOR_LAYOUT_HWC) */
 int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, void* host);
+
+/* Regions of delivered frames as a tensor batch: what runs behind a detector.  The detector's boxes are cut out of the FULL-RESOLUTION
+ * frames of a delivered window and resampled to a second-stage model's input size, any number of them in one call, into memory of the
+ * caller's -- from the frames' planes, which a pipeline with LEON_PIPELINE_OUTPUT_TENSOR keeps in its ring until the window is released
+ * (no second, full-size tensor output is needed for it).
+ * Region i is r of the resize definition above (leon_pipeline_tensor_resize) with crop = (x, y, width, height) of frames[frame],
+ * in_size the frame's size and out = the config's out_width x out_height; its tensor is T[c][ r[oy][ox][c] ] with the PIPELINE's
+ * element table, element type and layout (CHW or HWC), at device_out + i * out_pitch_bytes.  The pipeline's own resize, crop and
+ * canvas settings play no part.  The fill row of 255 of an odd frame height is in the source as before; taps may leave the box, never
+ * the frame; a yuva stream's alpha is not in it.  It equals, bit for bit, what a pipeline created with crop = the box, out size and
+ * filter = the config's delivers for that frame.
+ * Placement: region_bytes = 3 * out_height * out_width * element bytes; out_pitch_bytes = 0 means region_bytes rounded up to 256,
+ * otherwise it must be a multiple of 256 and >= region_bytes; device_out must be 256-byte aligned.  Exactly the region_bytes of each
+ * region are written: the bytes between region_bytes and the pitch are not touched, nor is anything behind region n - 1.
+ * The call is synchronous: when it returns LEON_OK the tensors are complete in device memory.  It runs on a non-blocking stream of the
+ * pipeline's own (created at first use), not on the decoder's: a window in flight is not ordered behind it.  It may be called from any
+ * host thread, from inside the callback too, any number of times on a window that is out for delivery and not released; concurrent
+ * calls are serialised.  Releasing the window, or destroying the pipeline, while a call on it is in flight is the caller's error.  A
+ * window delivered before a seek and still held stays usable.  One kernel launch per call (k_regions<element bytes, layout, filter>:
+ * blockIdx.z = the region); every region has tables of its own, built on the host per call and uploaded with the regions'
+ * descriptors; the scratch for them grows to its high-water mark and stays with the pipeline.
+ * Refused (LEON_ERR_INVALID, nothing launched, nothing written; the message names the region): a pipeline without the TENSOR bit, a
+ * window that is not out for delivery or was delivered with an error, n outside 1 .. 65535, a frame outside the window's frames, an
+ * empty box or one that leaves the frame, width / out_width or height / out_height above 16, an out size outside 1 .. 4096, another
+ * filter, a non-zero reserved word, a null or misaligned device_out, a bad pitch. */
+typedef struct leon_pipeline_region {
+    int32_t frame;                 /* index into the window's frames[] as delivered to the callback */
+    int32_t x, y, width, height;   /* the box, frame pixels; non-empty, inside the frame */
+    int32_t reserved[3];           /* must be 0 */
+} leon_pipeline_region;            /* 32 bytes */
+
+typedef struct leon_pipeline_regions_config {
+    int32_t out_width, out_height; /* 1 .. 4096, the same for every region of a call */
+    int32_t filter;                /* LEON_RESIZE_TRIANGLE or LEON_RESIZE_BICUBIC */
+    int32_t reserved[5];           /* must be 0 */
+} leon_pipeline_regions_config;    /* 32 bytes */
+
+/* host only, no device: what resample_regions would refuse of a window of n_frames frames of frame_width x frame_height;
+ * *bad (may be NULL) = index of the first offending region (-1: the config, or n) */
+int leon_pipeline_regions_check(int32_t frame_width, int32_t frame_height, int32_t n_frames,
+                                const leon_pipeline_region* regions, int32_t n,
+                                const leon_pipeline_regions_config* cfg, int32_t* bad);
+int leon_pipeline_resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n,
+                                   const leon_pipeline_regions_config* cfg, void* device_out, uint64_t out_pitch_bytes);
+/* the same into pooled device scratch, then copied to the host packed (n * region_bytes): tests, Node, thumbnails */
+int leon_pipeline_read_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n,
+                               const leon_pipeline_regions_config* cfg, void* host);
 const char* leon_pipeline_error(leon_pipeline* p);
 void leon_pipeline_destroy(leon_pipeline* p);
 

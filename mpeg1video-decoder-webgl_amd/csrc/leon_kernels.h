@@ -1969,9 +1969,29 @@ __device__ __forceinline__ int32_t resample_mad(int32_t w, uint32_t sample, int3
 // ends its elements go one by one (a row's start is aligned to nothing: out_width is any number).
 // In a canvas (`C`: ImageIsTensor or CanvasGeom) only the store addresses move: the tiles are numbered from the image's origin, a
 // tile row still stores the bytes of [g0, g1) and nothing else, its row stride and plane size are the canvas's.
-template <int EB, int LAYOUT, class F, class C>
-__device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids,
-                                              const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
+// Where a workgroup's frame and tensor lie (`W`) is asked once, behind the table loads.  RingFrame: frame_ids[blockIdx.z] of the
+// pipeline's rings (k_resample, k_letterbox).  RegionFrame: the two addresses k_regions has read from its region's descriptor.
+struct FramePair {
+    const uint8_t* src;
+    uint8_t* dst;
+};
+struct RingFrame {
+    const uint8_t* __restrict__ planes_ring;
+    uint8_t* __restrict__ tensor_ring;
+    const uint32_t* __restrict__ frame_ids;
+    __device__ __forceinline__ FramePair locate(const ResampleGeom& G) const
+    {
+        const uint32_t fid = frame_ids[blockIdx.z];
+        return FramePair{planes_ring + (size_t)fid * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi),
+                         tensor_ring + (size_t)fid * join64(G.ring.tensor_pitch_lo, G.ring.tensor_pitch_hi)};
+    }
+};
+struct RegionFrame {
+    FramePair at;
+    __device__ __forceinline__ FramePair locate(const ResampleGeom&) const { return at; }
+};
+template <int EB, int LAYOUT, class F, class C, class W>
+__device__ __forceinline__ void resample_body(const W& where, const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
                                               const ResampleGeom& G, const C& place)
 {
     typedef typename ElemOf<EB>::type Elem;
@@ -2017,9 +2037,9 @@ __device__ __forceinline__ void resample_body(const uint8_t* __restrict__ planes
     const int pair_step = kRgbaBlock / sw8, col_step = kRgbaBlock - pair_step * sw8;      // ... and the way to its next
 
     const char* lut = reinterpret_cast<const char*>(lut_s);
-    const uint32_t fid = frame_ids[blockIdx.z];
-    const uint8_t* src = planes_ring + (size_t)fid * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi);
-    uint8_t* dst = tensor_ring + (size_t)fid * join64(G.ring.tensor_pitch_lo, G.ring.tensor_pitch_hi);
+    const FramePair frame = where.locate(G);
+    const uint8_t* src = frame.src;
+    uint8_t* dst = frame.dst;
     const __amdgpu_buffer_rsrc_t prs = buf_rsrc(src);
     uint32_t two = 2u, three = 3u;                       // SDWA shift counts live in registers (display_half)
     asm("" : "+v"(two), "+v"(three));
@@ -2151,7 +2171,32 @@ __global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restri
                                                          const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ rt,
                                                          ResampleGeom G)
 {
-    resample_body<EB, LAYOUT, F>(planes_ring, tensor_ring, frame_ids, table, T, rt, G, ImageIsTensor{});
+    resample_body<EB, LAYOUT, F>(RingFrame{planes_ring, tensor_ring, frame_ids}, table, T, rt, G, ImageIsTensor{});
+}
+
+// ---- regions of delivered frames as a tensor batch (leon_pipeline.h, leon_pipeline_resample_regions) ---------------------
+// blockIdx.z is the region, blockIdx.x / y the tiles of the out size all regions of a call share.  What k_resample has as launch
+// constants a region has of its own -- the source frame, the destination, the tables of its box with their row lengths -- and a
+// workgroup reads it from the region's descriptor (one address per workgroup: scalar loads), then runs resample_body.  Each region's
+// tables are laid out as plan_resize lays out a pipeline's, `rt_base` int32 words into the call's table buffer.
+struct RegionDesc {
+    uint32_t frame_id;                   // index into the planes ring
+    uint32_t rt_base;                    // int32 offset of the region's first_x in the table buffer
+    uint32_t off_cx, off_wx, off_fy, off_cy, off_wy;          // as ResampleGeom's, from rt_base
+    int32_t taps_x, taps_y;              // row lengths of this region's weight tables (taps_x odd)
+    uint32_t dst_lo, dst_hi;             // byte offset of the region's tensor in the caller's buffer: index * pitch
+    uint32_t pad[5];
+};                                       // 64 bytes
+template <int EB, int LAYOUT, class F>
+__global__ __launch_bounds__(kRgbaBlock) void k_regions(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ out, const RegionDesc* __restrict__ descs,
+                                                        const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ tabs,
+                                                        ResampleGeom G)
+{
+    const RegionDesc& d = descs[blockIdx.z];
+    G.taps_x = d.taps_x; G.taps_y = d.taps_y;
+    G.off_cx = d.off_cx; G.off_wx = d.off_wx; G.off_fy = d.off_fy; G.off_cy = d.off_cy; G.off_wy = d.off_wy;
+    const RegionFrame where{FramePair{planes_ring + (size_t)d.frame_id * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi), out + join64(d.dst_lo, d.dst_hi)}};
+    resample_body<EB, LAYOUT, F>(where, table, T, tabs + d.rt_base, G, ImageIsTensor{});
 }
 
 // ---- the resampled image in a padded canvas (leon_pipeline.h, leon_pipeline_tensor_canvas) ------------------------------
@@ -2281,7 +2326,7 @@ __global__ __launch_bounds__(kRgbaBlock) void k_letterbox(const uint8_t* __restr
         pad_body<EB, LAYOUT>(tensor_ring, frame_ids, table, G, (blockIdx.y - tile_rows) * gridDim.x + blockIdx.x);
         return;
     }
-    resample_body<EB, LAYOUT, F>(planes_ring, tensor_ring, frame_ids, table, T, rt, G.image, G.canvas);
+    resample_body<EB, LAYOUT, F>(RingFrame{planes_ring, tensor_ring, frame_ids}, table, T, rt, G.image, G.canvas);
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

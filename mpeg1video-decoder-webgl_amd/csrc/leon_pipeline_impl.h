@@ -154,6 +154,14 @@ struct leon_pipeline {
     leon_pipeline_tensor_canvas tensor_canvas{};
     leon::CanvasGeom canvas_geom{};
     int canvas_on = 0;
+    // leon_pipeline_resample_regions: a stream of its own (non-blocking, made at first use) and the scratch of a call -- pinned staging
+    // and its device twin for [descriptors | tables], read_regions' device tensors -- grown to the high-water mark, all under regions_mu
+    std::mutex regions_mu;
+    hipStream_t regions_stream = nullptr;
+    char* regions_host = nullptr;
+    char* regions_dev = nullptr;
+    uint8_t* regions_out = nullptr;
+    size_t regions_host_cap = 0, regions_dev_cap = 0, regions_out_cap = 0;
     bool gpu_parser = false;
     // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
     // window n + 2, on a second stream: a parse launch lasts as long as its longest slice (one lane, symbol after symbol) and
@@ -632,6 +640,29 @@ int resize_axis_build(const char* axis, int32_t in_size, int32_t crop_start, int
     return LEON_OK;
 }
 
+// The largest count of resize_axis_build for arguments it accepts, without the weights: the same window expressions, no filter
+// evaluated.  0: arguments it refuses (the caller asks resize_axis_build itself for the message).  A caller that sizes table rows by it
+// and builds them with max_taps = this value is told by resize_axis_build should the two ever disagree ("max_taps is").
+int32_t resize_axis_taps(int32_t in_size, int32_t crop_start, int32_t crop_size, int32_t out_size, int32_t filter)
+{
+#pragma clang fp contract(off)
+    const int32_t filter_taps = resize_filter_max_taps(filter);
+    if (!filter_taps || out_size < 1 || out_size > 4096 || in_size < 1 || crop_size < 1 || crop_start < 0 || crop_start > in_size || crop_size > in_size - crop_start ||
+        (int64_t)crop_size > 16 * (int64_t)out_size) return 0;
+    const double scale = (double)crop_size / (double)out_size;
+    const double fscale = scale < 1.0 ? 1.0 : scale, support = (filter == LEON_RESIZE_BICUBIC ? 2.0 : 1.0) * fscale;
+    int32_t most = 0;
+    for (int32_t o = 0; o < out_size; o++) {
+        const double center = (double)crop_start + ((double)o + 0.5) * scale;
+        int32_t lo = (int32_t)(center - support + 0.5), hi = (int32_t)(center + support + 0.5);
+        if (lo < 0) lo = 0;
+        if (hi > in_size) hi = in_size;
+        if (hi - lo < 1 || hi - lo > filter_taps) return 0;
+        if (hi - lo > most) most = hi - lo;
+    }
+    return most;
+}
+
 // Every refusal of the format settings is here
 int tensor_format_check(const leon_pipeline_config* cfg, const leon_pipeline_tensor_format* fm, int* layout_out)
 {
@@ -699,6 +730,25 @@ bool resize_asked(const leon_pipeline_tensor_resize* rz)
     return rz && (rz->crop_x | rz->crop_y | rz->crop_width | rz->crop_height | rz->out_width | rz->out_height | rz->filter) != 0;
 }
 
+// What the kernel's LDS is sized for (by filter: ResTriangle, ResCubic), of the tables `t` laid out by G.  Within the limits of
+// resize_axis_build neither check can fail (at most 544 columns and 147 rows, bicubic 576 and 179: leon_kernels.h has the arithmetic);
+// they stand guard for the kernel's chunk loop, which needs at least one row pair per chunk (rc >= 2) to advance, should a limit ever
+// be widened without the kernel.
+int resize_footprint_check(const int32_t* t, const leon::ResampleGeom& G, int32_t filter)
+{
+    for (int32_t o = 0; o < G.ow; o += leon::kResTileX) {
+        const int32_t l = std::min(o + leon::kResTileX, G.ow) - 1;
+        const int32_t sw = (t[l] + t[G.off_cx + l] - (t[o] & ~7) + 7) & ~7;
+        if (leon::resample_col(sw) * 2 > leon::kResStagePx) return fail(LEON_ERR_INVALID, "resize: a tile's source footprint of %d columns does not fit the staging buffer", sw);
+    }
+    for (int32_t o = 0; o < G.oh; o += leon::kResTileY) {
+        const int32_t l = std::min(o + leon::kResTileY, G.oh) - 1;
+        const int32_t rows = t[G.off_fy + l] + t[G.off_cy + l] - (t[G.off_fy + o] & ~1);
+        if (rows + 1 > (filter == LEON_RESIZE_BICUBIC ? leon::ResCubic::kHRows : leon::ResTriangle::kHRows)) return fail(LEON_ERR_INVALID, "resize: a tile's source footprint of %d rows does not fit", rows);
+    }
+    return LEON_OK;
+}
+
 // What create makes of the resize settings: the geometry in force, the table buffer and k_resample's constants
 int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
 {
@@ -733,20 +783,7 @@ int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
     int32_t* t = p->resize_tabs.data();
     if ((rc = resize_axis_build("width", fw, g.crop_x, g.crop_width, g.width, rz->filter, t, t + G.off_cx, t + G.off_wx, G.taps_x, nullptr)) != LEON_OK) return rc;
     if ((rc = resize_axis_build("height", fh, g.crop_y, g.crop_height, g.height, rz->filter, t + G.off_fy, t + G.off_cy, t + G.off_wy, g.taps_y, nullptr)) != LEON_OK) return rc;
-    // What the kernel's LDS is sized for (by filter: ResTriangle, ResCubic).  Within the limits above neither check can
-    // fail (at most 544 columns and 147 rows, bicubic 576 and 179: leon_kernels.h has the arithmetic); they stand guard for the kernel's chunk loop, which needs at least one row pair per chunk
-    // (rc >= 2) to advance, should a limit ever be widened without the kernel.
-    for (int32_t o = 0; o < g.width; o += leon::kResTileX) {
-        const int32_t l = std::min(o + leon::kResTileX, g.width) - 1;
-        const int32_t sw = (t[l] + t[G.off_cx + l] - (t[o] & ~7) + 7) & ~7;
-        if (leon::resample_col(sw) * 2 > leon::kResStagePx) return fail(LEON_ERR_INVALID, "resize: a tile's source footprint of %d columns does not fit the staging buffer", sw);
-    }
-    for (int32_t o = 0; o < g.height; o += leon::kResTileY) {
-        const int32_t l = std::min(o + leon::kResTileY, g.height) - 1;
-        const int32_t rows = t[G.off_fy + l] + t[G.off_cy + l] - (t[G.off_fy + o] & ~1);
-        if (rows + 1 > (rz->filter == LEON_RESIZE_BICUBIC ? leon::ResCubic::kHRows : leon::ResTriangle::kHRows)) return fail(LEON_ERR_INVALID, "resize: a tile's source footprint of %d rows does not fit", rows);
-    }
-    return LEON_OK;
+    return resize_footprint_check(t, G, rz->filter);
 }
 
 // the GOP without the pictures whose `keep` is 0: they leave pics, and vpics / slices (gpu_parser) with them
@@ -1300,6 +1337,183 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
                                 (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, G);
     }
     HIP_TRY(hipGetLastError());
+    return LEON_OK;
+}
+
+// ---- regions of delivered frames as a tensor batch (leon_pipeline_resample_regions) ------------------------------------
+typedef void (*RegionsKernel)(const uint8_t*, uint8_t*, const leon::RegionDesc*, const uint32_t*, const leon::Tables*, const int32_t*, leon::ResampleGeom);
+struct RegionsKernelsOfFilter { RegionsKernel k[3][2]; };
+template <class F> constexpr RegionsKernelsOfFilter kRegionsKernelsOf = {{{leon::k_regions<1, leon::kLayoutChw, F>, leon::k_regions<1, leon::kLayoutHwc, F>},
+                                                                          {leon::k_regions<2, leon::kLayoutChw, F>, leon::k_regions<2, leon::kLayoutHwc, F>},
+                                                                          {leon::k_regions<4, leon::kLayoutChw, F>, leon::k_regions<4, leon::kLayoutHwc, F>}}};
+constexpr RegionsKernelsOfFilter kRegionsKernels[4] = {kRegionsKernelsOf<leon::ResTriangle>, {}, {}, kRegionsKernelsOf<leon::ResCubic>};
+static_assert(sizeof(leon::RegionDesc) == 64, "a descriptor is 16 dwords");
+static_assert(sizeof(leon_pipeline_region) == 32 && sizeof(leon_pipeline_regions_config) == 32, "include/leon_pipeline.h states the sizes");
+
+struct RegionTaps { int32_t x, y; };       // the largest tap count of a region's columns and rows
+
+// Every refusal that needs no device is here (leon_pipeline_regions_check is this function); taps: per region, for the table layout
+int regions_check(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
+                  int32_t* bad, std::vector<RegionTaps>* taps)
+{
+    if (bad) *bad = -1;
+    if (!regions || !cfg) return fail(LEON_ERR_INVALID, "null argument");
+    for (int i = 0; i < 5; i++)
+        if (cfg->reserved[i]) return fail(LEON_ERR_INVALID, "regions config: reserved word %d is %d, not 0", i, cfg->reserved[i]);
+    if (cfg->out_width < 1 || cfg->out_width > 4096) return fail(LEON_ERR_INVALID, "regions config: out_width %d is outside 1 .. 4096", cfg->out_width);
+    if (cfg->out_height < 1 || cfg->out_height > 4096) return fail(LEON_ERR_INVALID, "regions config: out_height %d is outside 1 .. 4096", cfg->out_height);
+    if (!resize_filter_max_taps(cfg->filter)) return fail(LEON_ERR_INVALID, "regions config: filter %d (LEON_RESIZE_TRIANGLE and LEON_RESIZE_BICUBIC are the filters)", cfg->filter);
+    if (fw < 1 || fh < 1 || n_frames < 0) return fail(LEON_ERR_INVALID, "regions: %d frames of %d x %d", n_frames, fw, fh);
+    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "regions: %d regions (a call takes 1 .. 65535)", n);
+    if (taps) taps->resize((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        const leon_pipeline_region& r = regions[i];
+        if (bad) *bad = i;
+        for (int k = 0; k < 3; k++)
+            if (r.reserved[k]) return fail(LEON_ERR_INVALID, "region %d: reserved word %d is %d, not 0", i, k, r.reserved[k]);
+        if (r.frame < 0 || r.frame >= n_frames) return fail(LEON_ERR_INVALID, "region %d: frame %d is outside the window's %d frames", i, r.frame, n_frames);
+        // a call that goes on to build the tables (taps != NULL) needs the row lengths only: the weights are judged when they are built
+        RegionTaps t{};
+        if (taps) {
+            t.x = resize_axis_taps(fw, r.x, r.width, cfg->out_width, cfg->filter);
+            t.y = resize_axis_taps(fh, r.y, r.height, cfg->out_height, cfg->filter);
+        }
+        int rc = LEON_OK;
+        if ((!t.x && (rc = resize_axis_build("width", fw, r.x, r.width, cfg->out_width, cfg->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS_BICUBIC, &t.x)) != LEON_OK) ||
+            (!t.y && (rc = resize_axis_build("height", fh, r.y, r.height, cfg->out_height, cfg->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS_BICUBIC, &t.y)) != LEON_OK)) {
+            const std::string why = g_err;
+            return fail(rc, "region %d: %s", i, why.c_str());
+        }
+        if (taps) (*taps)[(size_t)i] = t;
+    }
+    if (bad) *bad = -1;
+    return LEON_OK;
+}
+
+// the call's scratch, grown and never shrunk (regions_mu held; the regions stream is idle between calls)
+int regions_reserve(leon_pipeline* p, size_t upload_bytes, size_t out_bytes)
+{
+    if (upload_bytes > p->regions_host_cap) {
+        const size_t cap = std::max(upload_bytes + upload_bytes / 2, (size_t)1 << 20);
+        char* h = nullptr;
+        if (hipHostMalloc((void**)&h, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of pinned staging", cap); }
+        if (p->regions_host) hipHostFree(p->regions_host);
+        p->regions_host = h;
+        p->regions_host_cap = cap;
+    }
+    if (upload_bytes > p->regions_dev_cap) {
+        const size_t cap = std::max(upload_bytes + upload_bytes / 2, (size_t)1 << 20);
+        char* dv = nullptr;
+        if (big_alloc((void**)&dv, cap, kBigCaller) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of device scratch", cap); }
+        if (p->regions_dev) big_free(p->regions_dev);
+        p->regions_dev = dv;
+        p->regions_dev_cap = cap;
+    }
+    if (out_bytes > p->regions_out_cap) {
+        const size_t cap = std::max(out_bytes + out_bytes / 2, (size_t)1 << 20);
+        uint8_t* dv = nullptr;
+        if (big_alloc((void**)&dv, cap, kBigCaller) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes for the tensors", cap); }
+        if (p->regions_out) big_free(p->regions_out);
+        p->regions_out = dv;
+        p->regions_out_cap = cap;
+    }
+    return LEON_OK;
+}
+
+// One call: refusals, the regions' descriptors and tables into pinned staging, one upload, one launch, the wait -- all on the
+// pipeline's regions stream.  device_out NULL with `host`: into the pooled scratch at the default pitch, then packed to the host.
+int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
+                     void* device_out, uint64_t out_pitch, void* host)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR) || !p->d_tensor || !p->d_planes)
+        return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    std::lock_guard<std::mutex> call(p->regions_mu);
+    // the window's ring ids: p->mu is held for the look-up and the copy only (the notify thread and release_window need it)
+    std::vector<uint32_t> ids;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        auto it = p->delivered.find(window);
+        if (it == p->delivered.end()) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+        const PipeWindow* w = it->second;
+        if (w->status != LEON_OK) return fail(LEON_ERR_INVALID, "window %lld was delivered with an error (status %d)", (long long)window, w->status);
+        const uint32_t base = (uint32_t)((size_t)w->ring * p->W * p->max_pics);
+        ids.reserve(w->frame_ids.size());
+        for (uint32_t id : w->frame_ids) ids.push_back(base + id);
+    }
+    std::vector<RegionTaps> taps;
+    const int32_t fw = p->vinfo.frame_width, fh = p->vinfo.frame_height;
+    int rc = regions_check(fw, fh, (int32_t)ids.size(), regions, n, cfg, nullptr, &taps);
+    if (rc != LEON_OK) return rc;
+    const int32_t ow = cfg->out_width, oh = cfg->out_height, filter = cfg->filter;
+    const size_t region_bytes = (size_t)3 * oh * ow * p->tensor_elem;
+    if (host) { device_out = nullptr; out_pitch = 0; }
+    else {
+        if (!device_out) return fail(LEON_ERR_INVALID, "regions: null device_out");
+        if ((uintptr_t)device_out & 255u) return fail(LEON_ERR_INVALID, "regions: device_out %p is not 256-byte aligned", device_out);
+    }
+    if (out_pitch && (out_pitch % 256 || out_pitch < region_bytes))
+        return fail(LEON_ERR_INVALID, "regions: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", (unsigned long long)out_pitch, region_bytes);
+    const size_t pitch = out_pitch ? (size_t)out_pitch : pad256(region_bytes);
+    const int eb = (int)p->tensor_elem, layout = p->tensor_layout;
+    const bool listed = (eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc);
+    const RegionsKernel kr = listed ? kRegionsKernels[filter].k[eb >> 1][layout] : nullptr;
+    if (!kr) return fail(LEON_ERR_INVALID, "regions: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
+
+    // [descriptors | tables]: a region's tables as plan_resize lays out a pipeline's, rows of its own tap counts
+    const size_t desc_bytes = pad256((size_t)n * sizeof(leon::RegionDesc));
+    size_t words = 0;
+    for (int32_t i = 0; i < n; i++) words += 2 * (size_t)ow + (size_t)ow * (size_t)(taps[(size_t)i].x | 1) + 2 * (size_t)oh + (size_t)oh * (size_t)taps[(size_t)i].y;
+    if (words >= ((size_t)1 << 32)) return fail(LEON_ERR_INVALID, "regions: the tables of %d regions take %zu bytes (4 GiB a call at most)", n, words * 4);
+    const size_t upload_bytes = desc_bytes + words * 4;
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    if (!p->regions_stream) HIP_TRY(hipStreamCreateWithFlags(&p->regions_stream, hipStreamNonBlocking));
+    if ((rc = regions_reserve(p, upload_bytes, host ? (size_t)n * pitch : 0)) != LEON_OK) return rc;
+    leon::RegionDesc* descs = reinterpret_cast<leon::RegionDesc*>(p->regions_host);
+    int32_t* tabs = reinterpret_cast<int32_t*>(p->regions_host + desc_bytes);
+    leon::ResampleGeom G{};
+    G.fw = fw; G.fh = fh; G.ow = ow; G.oh = oh;
+    size_t at = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const leon_pipeline_region& r = regions[i];
+        leon::ResampleGeom R = G;
+        R.taps_x = taps[(size_t)i].x | 1; R.taps_y = taps[(size_t)i].y;          // (odd rows of Wx: plan_resize says why)
+        R.off_cx = (uint32_t)ow;
+        R.off_wx = R.off_cx + (uint32_t)ow;
+        R.off_fy = R.off_wx + (uint32_t)ow * (uint32_t)R.taps_x;
+        R.off_cy = R.off_fy + (uint32_t)oh;
+        R.off_wy = R.off_cy + (uint32_t)oh;
+        int32_t* t = tabs + at;
+        if ((rc = resize_axis_build("width", fw, r.x, r.width, ow, filter, t, t + R.off_cx, t + R.off_wx, R.taps_x, nullptr)) != LEON_OK ||
+            (rc = resize_axis_build("height", fh, r.y, r.height, oh, filter, t + R.off_fy, t + R.off_cy, t + R.off_wy, R.taps_y, nullptr)) != LEON_OK ||
+            (rc = resize_footprint_check(t, R, filter)) != LEON_OK) {
+            const std::string why = g_err;
+            return fail(rc, "region %d: %s", i, why.c_str());
+        }
+        leon::RegionDesc d{};
+        d.frame_id = ids[(size_t)r.frame];
+        d.rt_base = (uint32_t)at;
+        d.off_cx = R.off_cx; d.off_wx = R.off_wx; d.off_fy = R.off_fy; d.off_cy = R.off_cy; d.off_wy = R.off_wy;
+        d.taps_x = R.taps_x; d.taps_y = R.taps_y;
+        const uint64_t dst = (uint64_t)i * pitch;
+        d.dst_lo = (uint32_t)(dst & 0xffffffffu); d.dst_hi = (uint32_t)(dst >> 32);
+        descs[i] = d;
+        at += (size_t)R.off_wy + (size_t)oh * (size_t)R.taps_y;
+    }
+    uint8_t* out = host ? p->regions_out : static_cast<uint8_t*>(device_out);
+    hipStream_t st = p->regions_stream;
+    HIP_TRY(hipMemcpyAsync(p->regions_dev, p->regions_host, upload_bytes, hipMemcpyHostToDevice, st));
+    G.ring = ring_geom(p);
+    const unsigned gx = (unsigned)((ow + leon::kResTileX - 1) / leon::kResTileX), gy = (unsigned)((oh + leon::kResTileY - 1) / leon::kResTileY);
+    const leon::RegionDesc* d_descs = reinterpret_cast<const leon::RegionDesc*>(p->regions_dev);
+    for (size_t first = 0; first < (size_t)n; first += 65535) {          // (blockIdx.z; one launch: n <= 65535)
+        const dim3 grid(gx, gy, (unsigned)std::min<size_t>(65535, (size_t)n - first)), block(leon::kRgbaBlock);
+        hipLaunchKernelGGL(kr, grid, block, 0, st, (const uint8_t*)p->d_planes, out, d_descs + first, (const uint32_t*)p->d_tensor_table,
+                           (const leon::Tables*)p->dec->d_tables, reinterpret_cast<const int32_t*>(p->regions_dev + desc_bytes), G);
+    }
+    HIP_TRY(hipGetLastError());
+    if (host) HIP_TRY(hipMemcpy2DAsync(host, region_bytes, out, pitch, region_bytes, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return LEON_OK;
 }
 
@@ -2157,6 +2371,25 @@ int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, v
     return LEON_OK;
 }
 
+int leon_pipeline_regions_check(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* regions, int32_t n,
+                                const leon_pipeline_regions_config* cfg, int32_t* bad)
+{
+    return regions_check(frame_width, frame_height, n_frames, regions, n, cfg, bad, nullptr);
+}
+
+int leon_pipeline_resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n,
+                                   const leon_pipeline_regions_config* cfg, void* device_out, uint64_t out_pitch_bytes)
+{
+    return resample_regions(p, window, regions, n, cfg, device_out, out_pitch_bytes, nullptr);
+}
+
+int leon_pipeline_read_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n,
+                               const leon_pipeline_regions_config* cfg, void* host)
+{
+    if (!host) return fail(LEON_ERR_INVALID, "null argument");
+    return resample_regions(p, window, regions, n, cfg, nullptr, 0, host);
+}
+
 const char* leon_pipeline_error(leon_pipeline* p)
 {
     if (!p) return "";
@@ -2180,6 +2413,7 @@ void leon_pipeline_destroy(leon_pipeline* p)
     // every stream of the pipeline is idle before any of its memory is freed (a submit interrupted by `stop` may have
     // left uploads or parser kernels behind that no window's event covers)
     if (p->copy_stream) hipStreamSynchronize(p->copy_stream);
+    if (p->regions_stream) hipStreamSynchronize(p->regions_stream);
     for (hipStream_t vs : p->vlc_stream)
         if (vs) hipStreamSynchronize(vs);
     if (p->dec) leon_sync(p->dec);
@@ -2223,6 +2457,10 @@ void leon_pipeline_destroy(leon_pipeline* p)
     if (p->d_tensor_ids) hipFree(p->d_tensor_ids);
     if (p->d_resize_tabs) hipFree(p->d_resize_tabs);
     if (p->h_tensor_ids) hipHostFree(p->h_tensor_ids);
+    if (p->regions_host) hipHostFree(p->regions_host);
+    if (p->regions_dev) big_free(p->regions_dev);
+    if (p->regions_out) big_free(p->regions_out);
+    if (p->regions_stream) hipStreamDestroy(p->regions_stream);
     if (p->copy_stream) hipStreamDestroy(p->copy_stream);
     if (p->dec) leon_destroy(p->dec);
     delete p;

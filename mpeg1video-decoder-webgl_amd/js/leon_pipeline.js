@@ -43,6 +43,11 @@
  *                                  image rectangle tensorImageX, tensorImageY, tensorImageWidth, tensorImageHeight.
  *                                  opts.tensorLetterbox [h, w]: tensorSize, tensorCanvas and tensorOrigin derived from the crop box or the
  *                                  frame with the aspect ratio kept (LeonPipeline.letterbox = leon_pipeline_letterbox)
+ *   p.readRegions(window, regions, {size: [h, w], filter}) -> Buffer of n * 3 * h * w elements, packed: regions = [[frameIndex, x, y,
+ *                                  width, height], ...], boxes of the window's FULL-RESOLUTION frames (a detector's boxes) each resampled to
+ *                                  h x w with the pipeline's element type, table and layout (leon_pipeline_read_regions) -- any tensor
+ *                                  output, whatever its tensorSize / tensorCanvas; until the window is released; filter 'triangle'
+ *                                  (default) or 'bicubic'
  *   p.releaseWindow(window); p.stats(); p.destroy();
  * Open GOPs (closed_gop = 0) need no option: their leading B pictures predict from the GOP before; where that GOP is not decoded (start,
  * seek target, broken_link) they are not delivered and the GOP's frames start at its I picture's displayIndex (include/leon_pipeline.h).
@@ -137,6 +142,22 @@ class LeonPipeline extends EventEmitter {
   readFrame(window, index) { return this._p.readFrame(window, index); }
   readPlanes(window, index) { return this._p.readPlanes(window, index); }
   readTensor(window, index) { return this._p.readTensor(window, index); }
+  // regions: [[frameIndex, x, y, width, height], ...] of a delivered window's full-resolution frames, resampled to opts.size [h, w]
+  readRegions(window, regions, opts) {
+    opts = opts || {};
+    const filters = { triangle: 0, bicubic: 3 };
+    let filter = opts.filter === undefined ? 0 : opts.filter;
+    if (typeof filter === 'string') {
+      if (!(filter in filters)) throw new TypeError("filter: 'triangle' or 'bicubic'");
+      filter = filters[filter];
+    }
+    const size = opts.size;
+    if (!Array.isArray(size) || size.length !== 2 || !size.every(Number.isInteger)) throw new TypeError('size: [height, width]');
+    if (!Array.isArray(regions) || !regions.every((r) => Array.isArray(r) && r.length === 5 && r.every(Number.isInteger))) {
+      throw new TypeError('regions: [[frameIndex, x, y, width, height], ...]');
+    }
+    return this._p.readRegions(window, Int32Array.from(regions.flat()), size[0], size[1], filter);
+  }
   releaseWindow(window) { this._p.releaseWindow(window); }
   stats() { return this._p.stats(); }
   destroy() { if (this._p) { this._p.destroy(); this._p = null; } }

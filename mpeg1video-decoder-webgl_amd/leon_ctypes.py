@@ -39,6 +39,7 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_create_tensor_resized", "leon_pipeline_resize_weights", "leon_pipeline_get_tensor_geometry",
     "leon_pipeline_create_tensor_format", "leon_pipeline_get_tensor_shape",
     "leon_pipeline_create_tensor_canvas", "leon_pipeline_get_tensor_canvas", "leon_pipeline_letterbox",
+    "leon_pipeline_regions_check", "leon_pipeline_resample_regions", "leon_pipeline_read_regions",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -295,6 +296,14 @@ class PipelineTensorCanvas(C.Structure):
                 ("image_width", C.c_int32), ("image_height", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
+class PipelineRegion(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class PipelineRegionsConfig(C.Structure):
+    _fields_ = [("out_width", C.c_int32), ("out_height", C.c_int32), ("filter", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 class PipelineTensorShape(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("element_bytes", C.c_int32), ("layout", C.c_int32), ("channels", C.c_int32), ("height", C.c_int32),
                 ("width", C.c_int32), ("stride_c", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64)]
@@ -406,6 +415,10 @@ def load():
     lib.leon_pipeline_tensor_table.argtypes = [C.POINTER(PipelineConfig), C.POINTER(PipelineTensorConfig), C.c_void_p]
     lib.leon_pipeline_window_tensors.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int32]
     lib.leon_pipeline_read_tensor.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_regions_check"):          # (an older build under LEON_DEBUG_LIB, A/B runs against a parent commit, has none of the three)
+        lib.leon_pipeline_regions_check.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineRegion), C.c_int32, C.POINTER(PipelineRegionsConfig), C.POINTER(C.c_int32)]
+        lib.leon_pipeline_resample_regions.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineRegion), C.c_int32, C.POINTER(PipelineRegionsConfig), C.c_void_p, C.c_uint64]
+        lib.leon_pipeline_read_regions.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineRegion), C.c_int32, C.POINTER(PipelineRegionsConfig), C.c_void_p]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -418,6 +431,37 @@ def load():
 def _chk(rc):
     if rc != OK:
         raise LeonError(rc, load().leon_last_error().decode("utf-8", "replace"))
+
+
+def _regions_args(regions, size, filter):
+    """(PipelineRegion array, n, PipelineRegionsConfig) of a list of (frame_index, x, y, w, h) -- or PipelineRegion structs, or one
+    integer array [n, 5] -- and
+    size = (out_height, out_width) -- or a PipelineRegionsConfig"""
+    if isinstance(regions, np.ndarray):          # [n, 5] integers: no Python loop over the regions
+        full = np.zeros((len(regions), 8), dtype=np.int32)
+        full[:, :5] = regions
+        arr = (PipelineRegion * max(1, len(full))).from_buffer_copy(full.tobytes() or bytes(32))
+        cfg = size if isinstance(size, PipelineRegionsConfig) else PipelineRegionsConfig(int(size[1]), int(size[0]), _resize_filter_code(filter))
+        return arr, len(full), cfg
+    regions = list(regions)
+    arr = (PipelineRegion * max(1, len(regions)))()
+    for i, r in enumerate(regions):
+        arr[i] = r if isinstance(r, PipelineRegion) else PipelineRegion(*[int(v) for v in r])
+    cfg = size if isinstance(size, PipelineRegionsConfig) else PipelineRegionsConfig(int(size[1]), int(size[0]), _resize_filter_code(filter))
+    return arr, len(regions), cfg
+
+
+def regions_check(frame_width, frame_height, n_frames, regions, size, filter="triangle"):
+    """leon_pipeline_regions_check: what Pipeline.resample_regions would refuse of these regions (a list of (frame_index, x, y, w, h))
+    for a window of n_frames frames of frame_width x frame_height, without a device.  Returns None when they are accepted; raises
+    LeonError otherwise, its `bad` the index of the first offending region (-1: size, filter or the number of regions)."""
+    arr, n, cfg = _regions_args(regions, size, filter)
+    bad = C.c_int32(-2)
+    rc = load().leon_pipeline_regions_check(int(frame_width), int(frame_height), int(n_frames), arr, n, C.byref(cfg), C.byref(bad))
+    if rc != OK:
+        e = LeonError(rc, load().leon_last_error().decode("utf-8", "replace"))
+        e.bad = bad.value
+        raise e
 
 
 def _hostptr(a, dtype, keep):
@@ -690,7 +734,12 @@ class Pipeline:
     the element table like the image's -- element = table[c][canvas_rgb(rgb, crop, size, canvas, origin, pad, filter)]; every tensor shape
     above is the canvas's, tensor_canvas_geometry (PipelineTensorCanvas) has the image rectangle.  Every element is written every window.
     tensor_letterbox=(H, W): tensor_size, tensor_canvas and tensor_origin derived with letterbox() from the crop box, or the frame:
-    the aspect ratio kept, the image centred."""
+    the aspect ratio kept, the image centred.
+    Regions (any tensor output): resample_regions(window, regions, size, filter) resamples boxes of the window's full-resolution frames
+    -- regions = [(frame["_i"], x, y, w, h), ...], a detector's boxes -- to size = (h, w) into one [N, 3, h, w] ("hwc": [N, h, w, 3])
+    device batch of the pipeline's element type and table, element = table[c][resize_rgb(rgb of that frame, (x, y, w, h), size, filter)];
+    the pipeline's own tensor_size / crop / canvas play no part.  Until the window is released, from the callback or (for a window held
+    by returning False) from any thread; read_regions(...) gives the same as a host array."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
@@ -863,13 +912,60 @@ class Pipeline:
         _chk(self.lib.leon_pipeline_read_tensor(self.h, frame["_window"], frame["_i"], out.ctypes.data))
         return out
 
-    def _tensor_at(self, ptr, shape, strides, device_id=None):
+    def region_bytes(self, size):
+        """(bytes of one region's tensor, the default pitch between regions: the bytes rounded up to 256)"""
+        n = 3 * int(size[0]) * int(size[1]) * self.info.tensor_element_bytes
+        return n, (n + 255) // 256 * 256
+
+    def _region_dims(self, size):
+        """(shape, strides in bytes) of one region's tensor in the pipeline's layout"""
+        h, w, e = int(size[0]), int(size[1]), self.info.tensor_element_bytes
+        if self.tensor_shape.layout == TENSOR_LAYOUT_HWC:
+            return (h, w, 3), (3 * w * e, 3 * e, e)
+        return (3, h, w), (h * w * e, w * e, e)
+
+    def resample_regions(self, window, regions, size, filter="triangle", out=None, pitch=None, device_id=None):
+        """leon_pipeline_resample_regions: regions = [(frame_index, x, y, w, h), ...] of the delivered, not yet released `window`
+        (frame["_i"] is the index) resampled to size = (h, w) -> a torch view [N, 3, h, w] ("hwc": [N, h, w, 3]) of the pipeline's
+        element type, regions `pitch` bytes apart (None: the region's bytes rounded up to 256 -- dense when they are a multiple of
+        256, as 224 x 224 is in every element type).  The view lies over a uint8 buffer the method allocates, or over `out`: a torch
+        uint8 tensor on the device, 256-byte aligned, of at least (N - 1) * pitch + the region's bytes.  Synchronous: the batch is
+        complete when the method returns.  Raises LeonError where the library refuses; nothing is written then."""
+        import torch
+        if not self.info.tensor_dtype:
+            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        arr, n, cfg = _regions_args(regions, size, filter)
+        nbytes, dflt = self.region_bytes(size)
+        step = dflt if pitch is None else int(pitch)
+        dev = self.device_id if device_id is None else device_id
+        if out is None:
+            out = torch.empty(max(1, n) * max(step, 1), dtype=torch.uint8, device="cuda:%d" % dev)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < (n - 1) * step + nbytes:
+            raise ValueError("out: a contiguous uint8 tensor of at least %d bytes" % ((n - 1) * step + nbytes))
+        # the library writes on a stream of its own: what torch has queued for this memory (a fill, an earlier owner's kernels) goes first
+        torch.cuda.current_stream(dev).synchronize()
+        _chk(self.lib.leon_pipeline_resample_regions(self.h, int(window), arr, n, C.byref(cfg), out.data_ptr(), 0 if pitch is None else step))
+        shape, strides = self._region_dims(size)
+        return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out)
+
+    def read_regions(self, window, regions, size, filter="triangle"):
+        """leon_pipeline_read_regions: the same regions as a host array [N, 3, h, w] ("hwc": [N, h, w, 3]), packed: float16 / float32 /
+        uint8, bfloat16 as uint16 bit patterns like read_tensor"""
+        if not self.info.tensor_dtype:
+            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        arr, n, cfg = _regions_args(regions, size, filter)
+        out = np.empty((max(1, n),) + self._region_dims(size)[0], dtype=self._tensor_np_dtype())
+        _chk(self.lib.leon_pipeline_read_regions(self.h, int(window), arr, n, C.byref(cfg), out.ctypes.data))
+        return out[:n]
+
+    def _tensor_at(self, ptr, shape, strides, device_id=None, owner=None):
         import torch
         dt = self.info.tensor_dtype
 
         class _View:
             pass
         v = _View()
+        v.owner = owner          # torch.as_tensor keeps this object alive, and with it the memory's owner
         v.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": {TENSOR_F32: "<f4", TENSOR_F16: "<f2", TENSOR_BF16: "<i2", TENSOR_U8: "|u1"}[dt],
                                       "data": (int(ptr), False), "strides": tuple(int(x) for x in strides), "version": 2}
         t = torch.as_tensor(v, device="cuda:%d" % (self.device_id if device_id is None else device_id))

@@ -18,6 +18,7 @@
 #include "../../include/leon.h"
 #include "../../include/leon_pipeline.h"
 #include "../../include/leon_vlc.h"
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -593,6 +594,46 @@ napi_value PipeReadTensor(napi_env env, napi_callback_info info)
     return rc == LEON_OK ? ta : throw_leon(env, rc);
 }
 
+// p.readRegions(window, boxes, outHeight, outWidth, filter) -> Buffer of n * region bytes (3 * outHeight * outWidth elements of the
+// pipeline's element type and layout each, packed): leon_pipeline_read_regions.  boxes: an Int32Array of n x [frame index, x, y, width, height]
+napi_value PipeReadRegions(napi_env env, napi_callback_info info)
+{
+    size_t argc = 5;
+    napi_value argv[5];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    int32_t oh = 0, ow = 0, filter = 0;
+    napi_typedarray_type tt;
+    size_t len = 0, off = 0;
+    void* boxes = nullptr;
+    napi_value ab;
+    bool is_ta = false;
+    if (argc < 5 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta ||
+        napi_get_typedarray_info(env, argv[1], &tt, &len, &boxes, &ab, &off) != napi_ok || tt != napi_int32_array || len % 5 != 0 ||
+        napi_get_value_int32(env, argv[2], &oh) != napi_ok || napi_get_value_int32(env, argv[3], &ow) != napi_ok || napi_get_value_int32(env, argv[4], &filter) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "readRegions(window, Int32Array of [frame, x, y, width, height] per region, outHeight, outWidth, filter)");
+        return nullptr;
+    }
+    if (!h->info.tensor_dtype) {
+        napi_throw_error(env, nullptr, "readRegions: the pipeline has no tensor output (opts.output)");
+        return nullptr;
+    }
+    const size_t n = len / 5;
+    std::vector<leon_pipeline_region> regions(n ? n : 1);
+    const int32_t* b = static_cast<const int32_t*>(boxes);
+    for (size_t i = 0; i < n; i++) regions[i] = leon_pipeline_region{b[5 * i], b[5 * i + 1], b[5 * i + 2], b[5 * i + 3], b[5 * i + 4], {0, 0, 0}};
+    const leon_pipeline_regions_config cfg{ow, oh, filter, {0, 0, 0, 0, 0}};
+    // (a size the library refuses allocates nothing here)
+    const bool sized = oh >= 1 && oh <= 4096 && ow >= 1 && ow <= 4096 && n >= 1 && n <= 65535;
+    const size_t bytes = sized ? n * 3 * (size_t)oh * (size_t)ow * (size_t)h->info.tensor_element_bytes : 0;
+    napi_value buf;
+    void* data = nullptr;
+    NAPI_OK(napi_create_buffer(env, bytes ? bytes : 1, &data, &buf));
+    int rc = leon_pipeline_read_regions(h->p, w, regions.data(), (int32_t)std::min<size_t>(n, 65536), &cfg, data);
+    return rc == LEON_OK ? buf : throw_leon(env, rc);
+}
+
 // opts[name] as three floats (an array of numbers); absent: zeros
 bool get_f32x3(napi_env env, napi_value opts, const char* name, float* out)
 {
@@ -853,7 +894,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readRegions", PipeReadRegions}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));

@@ -43,6 +43,10 @@ def main():
     ap.add_argument("--host-resize", type=int, nargs=2, metavar=("H", "W"),
                     help="the route without --tensor-size, for comparison: full-size tensors, and the callback resizes every window's window_tensor view "
                          "with torch.nn.functional.interpolate(mode='bilinear', antialias=True)")
+    ap.add_argument("--regions", type=int, nargs=3, metavar=("N", "H", "W"),
+                    help="with a tensor output: after each window is delivered and before it is released, N seeded random boxes per frame (ratio <= 16) of the "
+                         "full-resolution frames resampled to H x W in one call (leon_pipeline_resample_regions); reports regions/s and the mean time per call")
+    ap.add_argument("--regions-filter", choices=["triangle", "bicubic"], default="triangle", help="the filter of --regions")
     ap.add_argument("--copy-rate", action="store_true", help="measure leon_measure_copy_bandwidth in this process first (the yardstick of a launch's rate)")
     ap.add_argument("--varied", action="store_true", help="the 16-GOP stream with 16 different contents (tools/stream_1080p.py) instead of --gops GOPs")
     ap.add_argument("--open-gops", action="store_true", help="with --varied: the same recipe written with open GOPs (closed_gop = 0), the leading B pictures "
@@ -85,6 +89,33 @@ def main():
             for x in parts:
                 torch.nn.functional.interpolate(x, size=tuple(a.host_resize), mode="bilinear", antialias=True, align_corners=False)
             torch.cuda.synchronize()          # the window is released on return: the resize must have read it
+    regions_stat = {"calls": 0, "regions": 0, "seconds": 0.0, "out": None}
+    if a.regions:
+        if a.host_resize:
+            ap.error("--regions and --host-resize are two runs")
+        import numpy as np
+        import torch
+        rn, rh, rw = a.regions
+
+        def on_window(window, frames):
+            p = frames[0]["_pipe"]
+            n_frames, fw, fh = len(frames), p.info.frame_width, p.info.frame_height
+            rng = np.random.default_rng(1000 + window)
+            n = n_frames * rn
+            # boxes of ratio <= 16 inside the frame: sizes first, then an origin that keeps them inside
+            w = rng.integers(1, min(fw, 16 * rw) + 1, n)
+            h = rng.integers(1, min(fh, 16 * rh) + 1, n)
+            x = (rng.random(n) * (fw - w + 1)).astype(np.int64)
+            y = (rng.random(n) * (fh - h + 1)).astype(np.int64)
+            boxes = np.stack([np.repeat(np.arange(n_frames), rn), x, y, w, h], axis=1)
+            nbytes, pitch = p.region_bytes((rh, rw))
+            if regions_stat["out"] is None or regions_stat["out"].numel() < n * pitch:          # the caller's batch buffer, allocated once
+                regions_stat["out"] = torch.empty(n * pitch, dtype=torch.uint8, device="cuda:0")
+            t = time.perf_counter()
+            p.resample_regions(window, boxes, (rh, rw), a.regions_filter, out=regions_stat["out"])
+            regions_stat["seconds"] += time.perf_counter() - t
+            regions_stat["calls"] += 1
+            regions_stat["regions"] += n
     free0 = free_device_bytes()
     t0 = time.perf_counter()
     pipe = L.Pipeline(data, parser_threads=a.threads, gops_per_window=a.window, windows_in_flight=a.inflight, loop=a.loop, gpu_parser=a.gpu_parser,
@@ -107,6 +138,10 @@ def main():
         "tensor_canvas": [canvas.height, canvas.width] if canvas else None, "tensor_image": [canvas.x, canvas.y, canvas.image_width, canvas.image_height] if canvas else None,
         "tensor_pad_value": list(canvas.pad) if canvas else None, "host_resize": a.host_resize, "windows_in_flight": a.inflight,
         "value": s["pictures"] / s["seconds"], "macroblocks_per_s": s["pictures"] * mbs / s["seconds"],
+        "regions": a.regions, "regions_filter": a.regions_filter if a.regions else None, "regions_calls": regions_stat["calls"] if a.regions else None,
+        "regions_per_s": regions_stat["regions"] / s["seconds"] if a.regions else None,
+        "regions_ms_per_call": 1e3 * regions_stat["seconds"] / regions_stat["calls"] if regions_stat["calls"] else None,
+        "regions_per_call": regions_stat["regions"] / regions_stat["calls"] if regions_stat["calls"] else None,
         "pictures": s["pictures"], "seconds": s["seconds"], "wall_seconds_incl_setup": wall, "windows": s["windows"],
         "slice_layer": "GPU (csrc/leon_vlc_gpu.h)" if a.gpu_parser else "host threads (libleon_vlc.so)",
         "device_gb_held_by_the_pipeline": (free0 - free1) / 1e9 if free0 is not None and free1 is not None else None,

@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""leon_pipeline_resample_regions alone: one window of 1080p frames held, then --calls calls of --regions seeded random boxes (ratio
+1 .. --max-ratio on both axes, clipped to the frame, frames drawn at random) resampled to --size, into one caller-owned buffer.
+Reports the wall time of a call (it is synchronous: tables built on the host, one upload, one launch, the wait), the host part that
+can be timed without a device (leon_pipeline_regions_check: one of the two passes over the tables), the bytes a call requests (the
+boxes' Y, Cb and Cr samples) and writes, and the copy rate of the same process.  The kernel's own time comes from running this under
+`rocprofv3 --kernel-trace --stats -- python tools/regions_bench.py ...` (k_regions, and k_resample of the pipeline's own --tensor-size
+tensors for comparison: one launch per window of --window GOPs).
+
+  python tools/regions_bench.py [--regions 4096] [--size 224 224] [--calls 5] [--window 128] [--filter triangle]"""
+import argparse
+import json
+import os
+import sys
+import threading
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "mpeg1video-decoder-webgl_amd"), os.path.join(ROOT, "tools")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--regions", type=int, default=4096)
+    ap.add_argument("--size", type=int, nargs=2, default=[224, 224], metavar=("H", "W"))
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--window", type=int, default=128, help="GOPs of the held window (12 pictures each)")
+    ap.add_argument("--windows", type=int, default=4, help="windows decoded (each one launch of the pipeline's own resize kernel)")
+    ap.add_argument("--max-ratio", type=float, default=8.0)
+    ap.add_argument("--filter", choices=["triangle", "bicubic"], default="triangle")
+    ap.add_argument("--tensor-dtype", choices=["float16", "bfloat16", "float32", "uint8"], default="float16")
+    ap.add_argument("--tensor-layout", choices=["chw", "hwc"], default="chw")
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    import leon_ctypes as L
+    import stream_1080p
+    data = stream_1080p.load()          # two GOPs of 12 pictures
+    L.load()
+    dec = L.Decoder(96, 64, n_slots=3, device_id=0)
+    copy_gbps = dec.measure_copy_bandwidth()
+    dec.close()
+    oh, ow = a.size
+    out, lock = {}, threading.Lock()
+
+    def on_window(window, frames):
+        if out:
+            return None
+        p = frames[0]["_pipe"]
+        n_frames, fw, fh = len(frames), p.info.frame_width, p.info.frame_height
+        rng = np.random.default_rng(4096)
+        r = 1.0 + rng.random(a.regions) * (a.max_ratio - 1.0)
+        w = np.minimum(fw, np.rint(ow * r)).astype(np.int64)
+        h = np.minimum(fh, np.rint(oh * r)).astype(np.int64)
+        x = (rng.random(a.regions) * (fw - w + 1)).astype(np.int64)
+        y = (rng.random(a.regions) * (fh - h + 1)).astype(np.int64)
+        boxes = np.stack([rng.integers(0, n_frames, a.regions), x, y, w, h], axis=1)
+        nbytes, pitch = p.region_bytes((oh, ow))
+        buf = torch.empty(a.regions * pitch, dtype=torch.uint8, device="cuda:0")
+        t = time.perf_counter()
+        L.regions_check(fw, fh, n_frames, boxes, (oh, ow), a.filter)
+        check_ms = 1e3 * (time.perf_counter() - t)
+        p.resample_regions(window, boxes, (oh, ow), a.filter, out=buf)          # scratch reaches its high-water mark
+        times = []
+        for _ in range(a.calls):
+            t = time.perf_counter()
+            p.resample_regions(window, boxes, (oh, ow), a.filter, out=buf)
+            times.append(1e3 * (time.perf_counter() - t))
+        requested = int((w * h).sum() * 3 // 2)
+        with lock:
+            out.update(frames=n_frames, call_ms=times, regions_check_ms=check_ms, requested_bytes=requested, written_bytes=a.regions * nbytes,
+                       mean_ratio_x=float((w / ow).mean()), mean_ratio_y=float((h / oh).mean()))
+    pipe = L.Pipeline(data, parser_threads=16, gops_per_window=a.window, windows_in_flight=2, loop=a.window * a.windows // 2, gpu_parser=True, output="tensor",
+                      tensor_dtype=a.tensor_dtype, tensor_layout=a.tensor_layout, tensor_size=(oh, ow), tensor_filter=a.filter, on_window=on_window)
+    try:
+        pipe.wait()
+        if pipe.error is not None:
+            raise SystemExit("pipeline: %r" % (pipe.error,))
+    finally:
+        pipe.close()
+    mean = sum(out["call_ms"]) / len(out["call_ms"])
+    print(json.dumps(dict(out, metric="leon_pipeline_resample_regions: %d regions of a window of %d 1080p frames -> %d x %d %s %s, %s" % (
+        a.regions, out["frames"], oh, ow, a.tensor_dtype, a.tensor_layout, a.filter), regions=a.regions, call_ms_mean=mean, regions_per_s=a.regions / (mean * 1e-3),
+        call_gbps_requested_plus_written=(out["requested_bytes"] + out["written_bytes"]) / (mean * 1e-3) / 1e9, copy_gbps_same_process=copy_gbps,
+        windows=pipe.windows, frames_per_window=out["frames"])))
+
+
+if __name__ == "__main__":
+    main()
