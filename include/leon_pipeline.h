@@ -434,6 +434,71 @@ int leon_pipeline_resample_regions(leon_pipeline* p, int64_t window, const leon_
 /* the same into pooled device scratch, then copied to the host packed (n * region_bytes): tests, Node, thumbnails */
 int leon_pipeline_read_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n,
                                const leon_pipeline_regions_config* cfg, void* host);
+/* Regions whose boxes lie in DEVICE memory: the detector ran on the GPU, its boxes never visit the host, and the crops are queued on the
+ * caller's stream behind the detector and in front of the second-stage model.  The tensors are those of leon_pipeline_resample_regions,
+ * bit for bit (same definition, same placement rules, same kernels behind a status test); what differs is who judges a region and when.
+ * The host knows nothing about a box any more, so the regions' tables are built on the device (k_box_tables: the row expressions of
+ * leon_pipeline_tensor_resize in IEEE binary64, the same operations in the same order as the host's builder -- one text compiled for both)
+ * and a region's faults are not an error of the call: region i gets a status word,
+ *     0 (LEON_REGION_OK)      exactly when leon_pipeline_regions_check accepts the region alone in that window,
+ *     otherwise the first failing check in regions_check's order: LEON_REGION_RESERVED (a reserved word), LEON_REGION_FRAME (the frame
+ *     index), then for x and after it for y: LEON_REGION_BOX (empty, or leaves the frame), LEON_REGION_RATIO_X / _Y (above 16),
+ *     LEON_REGION_TAPS (a row's tap count outside 1 .. the filter's maximum; unreachable inside the other limits)
+ * written to device_status[i] when that is given.  A region with a non-zero status is skipped: not one byte of its tensor is written.
+ * leon_pipeline_region_status is the same judgement on the host, no device involved (tests; hosts that want to name a fault).
+ * Ordering.  With `stream` given the call ONLY ENQUEUES and returns LEON_OK once the work is queued there: what wrote the boxes earlier
+ * on that stream has run before they are read, what is queued on it later sees the tensors and the status words, and the host learns
+ * nothing until it synchronises that stream itself.  With stream NULL the work runs on the pipeline's regions stream and the call waits
+ * for it (the boxes must be complete in memory when it is made).  Either way the window must stay unreleased, the pipeline alive and
+ * `regions`, `device_out` and `device_status` valid until the work has run: that is the caller's duty, as the host call's.
+ * Scratch.  The regions are taken in chunks of as many as fit scratch_limit_bytes -- per region a 64-byte descriptor and a table slot
+ * of the filter's worst case for the out size, 4 * (2 * ow + ow * T + 2 * oh + oh * T) bytes with T = 33 (triangle) or 65 (bicubic);
+ * the limit bounds a chunk's descriptors and slots, beside which the allocation holds the window's frame ids (4 bytes a frame), each of
+ * the three parts rounded up to 256 bytes, and is never smaller than 1 MiB --
+ * one k_box_tables and one k_boxes<element bytes, layout, filter> launch per chunk, in stream order over the same memory: the scratch is
+ * bounded whatever n is (no 4 GiB rule here).  It belongs to the pipeline and grows to its high-water mark.  Every call records an event
+ * behind its last launch and the next call's stream waits for that event on the device before its first, so calls on different
+ * streams never share the scratch at once; growing it, and leon_pipeline_destroy, wait for the event on the host.  Concurrent calls are
+ * serialised while they enqueue.  Any host thread, inside the callback too.
+ * Refused (LEON_ERR_INVALID, nothing enqueued, nothing written): what leon_pipeline_regions_check says about the config and n, a pipeline
+ * without the TENSOR bit, a window that is not out for delivery or was delivered with an error, a null call, `regions` or `device_out`,
+ * `regions` (or device_status) not 4-byte aligned, device_out not 256-byte aligned, a bad pitch, a scratch limit below one region's slot
+ * and descriptor, a non-zero reserved word. */
+#define LEON_REGION_OK       0
+#define LEON_REGION_RESERVED 1
+#define LEON_REGION_FRAME    2
+#define LEON_REGION_BOX      3
+#define LEON_REGION_RATIO_X  4
+#define LEON_REGION_RATIO_Y  5
+#define LEON_REGION_TAPS     6
+#define LEON_REGIONS_SCRATCH_DEFAULT ((uint64_t)256 << 20)   /* scratch_limit_bytes = 0 */
+typedef struct leon_pipeline_regions_device {
+    const leon_pipeline_region* regions;   /* DEVICE memory, n records, 4-byte aligned */
+    int32_t  n;                            /* 1 .. 65535 */
+    int32_t  reserved0;                    /* must be 0 */
+    void*    device_out;                   /* 256-byte aligned */
+    uint64_t out_pitch_bytes;              /* as resample_regions */
+    int32_t* device_status;                /* DEVICE memory, n words, may be NULL */
+    void*    stream;                       /* hipStream_t of the caller's; NULL: the pipeline's regions stream, and the call waits */
+    uint64_t scratch_limit_bytes;          /* 0: LEON_REGIONS_SCRATCH_DEFAULT; otherwise >= one region's slot + descriptor */
+    uint64_t reserved[1];                  /* must be 0 */
+} leon_pipeline_regions_device;            /* 64 bytes */
+int leon_pipeline_resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg,
+                                          const leon_pipeline_regions_device* call);
+/* host only, no device: the status word the device writes for this one region (cfg as judged by leon_pipeline_regions_check; a null
+ * argument or a config that check refuses: LEON_ERR_INVALID, which is negative and no status) */
+int32_t leon_pipeline_region_status(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* region,
+                                    const leon_pipeline_regions_config* cfg);
+/* A diagnostic: the DEVICE's evaluation of the tables of n_axes single axes, copied back, to be compared word for word with
+ * leon_pipeline_resize_weights (pixels would hide a weight that is one unit off).  axes = n_axes x {in_size, crop_start, crop_size,
+ * out_size}; with max_out the largest out_size of the batch, axis a's tables lie at a fixed pitch: first[a * max_out + o],
+ * count[a * max_out + o] and weights[(a * max_out + o) * max_taps + k] (k >= count: 0) for o < its out_size -- the caller provides
+ * n_axes * max_out words for first and count, n_axes * max_out * max_taps for weights, n_axes for status; what lies behind an axis's
+ * out_size, and everything of an axis whose status is not 0, is left as it was.  status[a]: 0, LEON_REGION_BOX, LEON_REGION_RATIO_X
+ * (there is one axis), LEON_REGION_TAPS (also: a count above max_taps).  Synchronous, on device_id's null stream, memory of its own.
+ * Refused (LEON_ERR_INVALID): a null pointer, n_axes < 1, max_taps < 1, another filter, an in_size or out_size outside 1 .. 4096. */
+int leon_pipeline_resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps,
+                                        int32_t* first, int32_t* count, int32_t* weights, int32_t* status);
 const char* leon_pipeline_error(leon_pipeline* p);
 void leon_pipeline_destroy(leon_pipeline* p);
 

@@ -37,6 +37,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "leon_resize_row.h"
 
 
 namespace leon {
@@ -2185,7 +2186,8 @@ struct RegionDesc {
     uint32_t off_cx, off_wx, off_fy, off_cy, off_wy;          // as ResampleGeom's, from rt_base
     int32_t taps_x, taps_y;              // row lengths of this region's weight tables (taps_x odd)
     uint32_t dst_lo, dst_hi;             // byte offset of the region's tensor in the caller's buffer: index * pitch
-    uint32_t pad[5];
+    int32_t status;                      // 0 on the host path; k_box_tables: kRegion* (non-zero: k_boxes leaves the region alone)
+    uint32_t pad[4];
 };                                       // 64 bytes
 template <int EB, int LAYOUT, class F>
 __global__ __launch_bounds__(kRgbaBlock) void k_regions(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ out, const RegionDesc* __restrict__ descs,
@@ -2193,6 +2195,142 @@ __global__ __launch_bounds__(kRgbaBlock) void k_regions(const uint8_t* __restric
                                                         ResampleGeom G)
 {
     const RegionDesc& d = descs[blockIdx.z];
+    G.taps_x = d.taps_x; G.taps_y = d.taps_y;
+    G.off_cx = d.off_cx; G.off_wx = d.off_wx; G.off_fy = d.off_fy; G.off_cy = d.off_cy; G.off_wy = d.off_wy;
+    const RegionFrame where{FramePair{planes_ring + (size_t)d.frame_id * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi), out + join64(d.dst_lo, d.dst_hi)}};
+    resample_body<EB, LAYOUT, F>(where, table, T, tabs + d.rt_base, G, ImageIsTensor{});
+}
+
+// ---- regions whose boxes lie in device memory (leon_pipeline.h, leon_pipeline_resample_regions_device) -------------------
+// Behind a detector that ran on the GPU nothing about a box is known on the host.  Per chunk of regions two launches in stream order
+// over one scratch: k_box_tables judges each region and writes its descriptor and tables, k_boxes<EB, LAYOUT, F> is k_regions behind
+// the descriptor's status word.
+// k_box_tables: one workgroup per region.  The region's record is one address per workgroup (scalar loads); its status is
+// region_axis_status and the rows' tap counts, which the workgroup reduces first (a lane takes every 256th output sample of both
+// axes; two LDS words) -- the row length of a table is the largest count of its rows and has to be known before a weight is stored.
+// A valid region's tables then lie as plan_resize lays out a pipeline's -- first_x | count_x | Wx | first_y | count_y | Wy, rows of
+// taps_x | 1 and taps_y words, zero behind count[o] -- in the region's fixed slot of the scratch (slot_words: the filter's worst case
+// for the out size, so no prefix sum and nothing read back).  A lane builds whole rows: the sum in index order first, then the
+// weights from the same expressions once more (leon_resize_row.h; no array of doubles per lane).  fp64 throughout, a division per tap
+// and another per weight, a row's words stored by one lane: measured, 4096 regions of 224 x 224 (triangle, ratio 1 .. 8) take 0.09 -
+// 0.16 ms, a hundredth of the k_boxes launch behind it.
+struct BoxRecord {                       // = leon_pipeline_region
+    int32_t frame, x, y, width, height, reserved[3];
+};
+struct BoxCall {
+    int32_t fw, fh, ow, oh;
+    int32_t n_frames, cubic;
+    uint32_t slot_words;                 // int32 words of a region's slot in the table buffer
+    uint32_t first;                      // the chunk's first region in the call: region i of the launch is written to (first + i) * pitch
+    uint32_t pitch_lo, pitch_hi;
+};
+// this lane's share of an axis's rows: the largest count, INT32_MAX when resize_axis_build refuses one
+__device__ __forceinline__ int32_t box_axis_most(const ResizeAxis& A, int32_t out_size)
+{
+    int32_t most = 0;
+    for (int32_t o = (int32_t)threadIdx.x; o < out_size; o += kRgbaBlock) {
+        const int32_t n = resize_row_window(A, o).n;
+        most = max(most, resize_row_count_ok(n, A.cubic) ? n : INT32_MAX);
+    }
+    return most;
+}
+// row o of an axis: first, count and the `row_len` words at `row` (count <= row_len: the caller reduced the counts)
+__device__ __forceinline__ void box_axis_row(const ResizeAxis& A, int32_t o, int32_t* __restrict__ first, int32_t* __restrict__ count, int32_t* __restrict__ row,
+                                             int32_t row_len)
+{
+    const ResizeWindow R = resize_row_window(A, o);
+    const double sum = resize_row_sum(A, R);
+    first[o] = R.lo;
+    count[o] = R.n;
+    for (int32_t k = 0; k < R.n; k++) row[k] = resize_row_weight(resize_row_tap(A, R, k), sum);
+    for (int32_t k = R.n; k < row_len; k++) row[k] = 0;
+}
+__global__ __launch_bounds__(kRgbaBlock) void k_box_tables(const BoxRecord* __restrict__ boxes, const uint32_t* __restrict__ frame_ids, RegionDesc* __restrict__ descs,
+                                                           int32_t* __restrict__ tabs, int32_t* __restrict__ status_out, BoxCall c)
+{
+    __shared__ int32_t most_s[2];
+    const uint32_t i = blockIdx.x;
+    const BoxRecord r = boxes[i];
+    const bool cubic = c.cubic != 0;
+    int32_t status = kRegionOk, sx = kRegionOk, sy = kRegionOk;
+    if (r.reserved[0] | r.reserved[1] | r.reserved[2]) status = kRegionReserved;
+    else if (r.frame < 0 || r.frame >= c.n_frames) status = kRegionFrame;
+    else {
+        sx = region_axis_status(c.fw, r.x, r.width, c.ow, kRegionRatioX);
+        sy = region_axis_status(c.fh, r.y, r.height, c.oh, kRegionRatioY);
+    }
+    // (the axes of a box that is refused are never evaluated: resize_axis stands on region_axis_status)
+    const bool do_x = status == kRegionOk && sx == kRegionOk, do_y = status == kRegionOk && sy == kRegionOk;
+    ResizeAxis X{}, Y{};
+    if (do_x) X = resize_axis(c.fw, r.x, r.width, c.ow, cubic);
+    if (do_y) Y = resize_axis(c.fh, r.y, r.height, c.oh, cubic);
+    if (threadIdx.x < 2) most_s[threadIdx.x] = 0;
+    __syncthreads();
+    if (do_x) atomicMax(&most_s[0], box_axis_most(X, c.ow));
+    if (do_y) atomicMax(&most_s[1], box_axis_most(Y, c.oh));
+    __syncthreads();
+    const int32_t most_x = most_s[0], most_y = most_s[1];
+    if (status == kRegionOk)
+        status = sx != kRegionOk ? sx : most_x == INT32_MAX ? kRegionTaps : sy != kRegionOk ? sy : most_y == INT32_MAX ? kRegionTaps : kRegionOk;
+    RegionDesc d{};
+    d.status = status;
+    if (status == kRegionOk) {
+        d.frame_id = frame_ids[r.frame];
+        d.rt_base = i * c.slot_words;
+        d.taps_x = most_x | 1; d.taps_y = most_y;
+        d.off_cx = (uint32_t)c.ow;
+        d.off_wx = d.off_cx + (uint32_t)c.ow;
+        d.off_fy = d.off_wx + (uint32_t)c.ow * (uint32_t)d.taps_x;
+        d.off_cy = d.off_fy + (uint32_t)c.oh;
+        d.off_wy = d.off_cy + (uint32_t)c.oh;
+        const uint64_t dst = (uint64_t)(c.first + i) * join64(c.pitch_lo, c.pitch_hi);
+        d.dst_lo = (uint32_t)(dst & 0xffffffffu); d.dst_hi = (uint32_t)(dst >> 32);
+    }
+    if (threadIdx.x == 0) {
+        descs[i] = d;
+        if (status_out) status_out[i] = status;
+    }
+    if (status != kRegionOk) return;
+    int32_t* __restrict__ t = tabs + (size_t)d.rt_base;
+    for (int32_t row = (int32_t)threadIdx.x; row < c.ow + c.oh; row += kRgbaBlock) {
+        if (row < c.ow) box_axis_row(X, row, t, t + d.off_cx, t + d.off_wx + (size_t)row * (size_t)d.taps_x, d.taps_x);
+        else box_axis_row(Y, row - c.ow, t + d.off_fy, t + d.off_cy, t + d.off_wy + (size_t)(row - c.ow) * (size_t)d.taps_y, d.taps_y);
+    }
+}
+// The same rows for a batch of single axes at a fixed pitch (leon_pipeline_resize_weights_device, a diagnostic: the doubles' outcome
+// compared word for word with the host's): one workgroup per axis, `max_out` rows of `max_taps` words each.  status: kRegionBox, kRegionRatioX
+// (either axis: there is one), kRegionTaps (also a count above max_taps); nothing of a refused axis is written.
+struct AxisRecord {
+    int32_t in_size, crop_start, crop_size, out_size;
+};
+__global__ __launch_bounds__(kRgbaBlock) void k_axis_tables(const AxisRecord* __restrict__ axes, int32_t* __restrict__ first, int32_t* __restrict__ count,
+                                                            int32_t* __restrict__ weights, int32_t* __restrict__ status_out, int32_t cubic, int32_t max_taps, int32_t max_out)
+{
+    __shared__ int32_t most_s;
+    const uint32_t i = blockIdx.x;
+    const AxisRecord a = axes[i];
+    int32_t status = region_axis_status(a.in_size, a.crop_start, a.crop_size, a.out_size, kRegionRatioX);
+    ResizeAxis A{};
+    if (status == kRegionOk) A = resize_axis(a.in_size, a.crop_start, a.crop_size, a.out_size, cubic != 0);
+    if (threadIdx.x == 0) most_s = 0;
+    __syncthreads();
+    if (status == kRegionOk) atomicMax(&most_s, box_axis_most(A, a.out_size));
+    __syncthreads();
+    if (status == kRegionOk && most_s > max_taps) status = kRegionTaps;
+    if (threadIdx.x == 0) status_out[i] = status;
+    if (status != kRegionOk) return;
+    const size_t at = (size_t)i * (size_t)max_out;
+    for (int32_t o = (int32_t)threadIdx.x; o < a.out_size; o += kRgbaBlock)
+        box_axis_row(A, o, first + at, count + at, weights + (at + (size_t)o) * (size_t)max_taps, max_taps);
+}
+// k_regions behind the status test: a refused region stores nothing anywhere
+template <int EB, int LAYOUT, class F>
+__global__ __launch_bounds__(kRgbaBlock) void k_boxes(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ out, const RegionDesc* __restrict__ descs,
+                                                      const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ tabs,
+                                                      ResampleGeom G)
+{
+    const RegionDesc& d = descs[blockIdx.z];
+    if (d.status != kRegionOk) return;
     G.taps_x = d.taps_x; G.taps_y = d.taps_y;
     G.off_cx = d.off_cx; G.off_wx = d.off_wx; G.off_fy = d.off_fy; G.off_cy = d.off_cy; G.off_wy = d.off_wy;
     const RegionFrame where{FramePair{planes_ring + (size_t)d.frame_id * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi), out + join64(d.dst_lo, d.dst_hi)}};

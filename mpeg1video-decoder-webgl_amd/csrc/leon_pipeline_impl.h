@@ -162,6 +162,19 @@ struct leon_pipeline {
     char* regions_dev = nullptr;
     uint8_t* regions_out = nullptr;
     size_t regions_host_cap = 0, regions_dev_cap = 0, regions_out_cap = 0;
+    // leon_pipeline_resample_regions_device (regions_mu too): the scratch of a chunk [frame ids | descriptors | table slots], the event
+    // behind the last call's last launch -- the next call's stream waits for it on the device, growing the scratch and destroy on the
+    // host -- and a small ring of pinned staging for the frame ids, each entry with the event behind its upload
+    static constexpr int kBoxesStaging = 4;
+    char* boxes_dev = nullptr;
+    size_t boxes_dev_cap = 0;
+    hipEvent_t boxes_done = nullptr;
+    bool boxes_busy = false;
+    uint32_t* boxes_ids_host[kBoxesStaging] = {};
+    size_t boxes_ids_cap[kBoxesStaging] = {};
+    hipEvent_t boxes_ids_done[kBoxesStaging] = {};
+    bool boxes_ids_busy[kBoxesStaging] = {};
+    unsigned boxes_ids_next = 0;
     bool gpu_parser = false;
     // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
     // window n + 2, on a second stream: a parse launch lasts as long as its longest slice (one lane, symbol after symbol) and
@@ -568,21 +581,10 @@ int tensor_table_build(const leon_pipeline_config* cfg, const leon_pipeline_tens
 // ---- output TENSOR at a model's input size: the tables of one axis (the definition of include/leon_pipeline.h) --------
 
 // first[o], count[o], weights[o * max_taps + k] (zero behind count[o]); *taps = the largest count.  Every refusal of one axis is here.
-// Doubles, evaluated as written (the library is compiled with -ffp-contract=off; the pragma holds it for other builds).
-double resize_filter_triangle(double x)
-{
-    const double t = 1.0 - std::fabs(x);
-    return t > 0.0 ? t : 0.0;
-}
-double resize_filter_bicubic(double x)          // Keys' cubic, a = -0.5
-{
-#pragma clang fp contract(off)
-    const double a = -0.5;
-    x = std::fabs(x);
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
-    if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * a;
-    return 0.0;
-}
+// Doubles, evaluated as written (the library is compiled with -ffp-contract=off; the pragma holds it for other builds).  What one
+// output sample's row is -- the window, the filter functions, the sum in index order, the normalisation and the rounding -- is
+// leon_resize_row.h, the text the device evaluates too (k_box_tables).
+
 // the most taps an output sample of `filter` has at the largest ratio (0: no such filter)
 int32_t resize_filter_max_taps(int32_t filter)
 {
@@ -600,22 +602,17 @@ int resize_axis_build(const char* axis, int32_t in_size, int32_t crop_start, int
         return fail(LEON_ERR_INVALID, "resize: the crop box (%s: start %d, size %d) is empty or leaves the frame (%d)", axis, crop_start, crop_size, in_size);
     if ((int64_t)crop_size > 16 * (int64_t)out_size) return fail(LEON_ERR_INVALID, "resize: %s %d -> %d reduces by more than 16", axis, crop_size, out_size);
     if (max_taps < 1) return fail(LEON_ERR_INVALID, "resize: max_taps %d", max_taps);
-    const double scale = (double)crop_size / (double)out_size;
-    const double fscale = scale < 1.0 ? 1.0 : scale, support = (cubic ? 2.0 : 1.0) * fscale;
+    const leon::ResizeAxis A = leon::resize_axis(in_size, crop_start, crop_size, out_size, cubic);
     int32_t most = 0;
     double w[LEON_RESIZE_MAX_TAPS_BICUBIC + 2];
     for (int32_t o = 0; o < out_size; o++) {
-        const double center = (double)crop_start + ((double)o + 0.5) * scale;
-        int32_t lo = (int32_t)(center - support + 0.5), hi = (int32_t)(center + support + 0.5);
-        if (lo < 0) lo = 0;
-        if (hi > in_size) hi = in_size;
-        const int32_t n = hi - lo;
+        const leon::ResizeWindow R = leon::resize_row_window(A, o);
+        const int32_t lo = R.lo, n = R.n;
         if (n < 1 || n > filter_taps) return fail(LEON_ERR_INVALID, "resize: %s output %d has %d taps", axis, o, n);
         if (n > max_taps) return fail(LEON_ERR_INVALID, "resize: %s output %d has %d taps, max_taps is %d", axis, o, n, max_taps);
         double sum = 0.0;
         for (int32_t k = 0; k < n; k++) {
-            const double x = ((double)(lo + k) - center + 0.5) / fscale;
-            w[k] = cubic ? resize_filter_bicubic(x) : resize_filter_triangle(x);
+            w[k] = leon::resize_row_tap(A, R, k);
             sum += w[k];
         }
         if (!(sum > 0.0)) return fail(LEON_ERR_INVALID, "resize: %s output %d has no weight", axis, o);
@@ -623,8 +620,7 @@ int resize_axis_build(const char* axis, int32_t in_size, int32_t crop_start, int
         // part of a row can carry a sum of 8-bit samples out of 31 bits (with these filters it never happens)
         int64_t pos = 0, neg = 0;
         for (int32_t k = 0; k < n; k++) {
-            const double v = (w[k] / sum) * 4194304.0;
-            const int32_t W = v < 0.0 ? (int32_t)(-0.5 + v) : (int32_t)(0.5 + v);
+            const int32_t W = leon::resize_row_weight(w[k], sum);
             if (W <= -(1 << 23) || W >= (1 << 23)) return fail(LEON_ERR_INVALID, "resize: %s output %d has a weight of %d", axis, o, W);
             if (W < 0) neg -= W; else pos += W;
             if (weights) weights[(size_t)o * max_taps + k] = W;
@@ -649,16 +645,12 @@ int32_t resize_axis_taps(int32_t in_size, int32_t crop_start, int32_t crop_size,
     const int32_t filter_taps = resize_filter_max_taps(filter);
     if (!filter_taps || out_size < 1 || out_size > 4096 || in_size < 1 || crop_size < 1 || crop_start < 0 || crop_start > in_size || crop_size > in_size - crop_start ||
         (int64_t)crop_size > 16 * (int64_t)out_size) return 0;
-    const double scale = (double)crop_size / (double)out_size;
-    const double fscale = scale < 1.0 ? 1.0 : scale, support = (filter == LEON_RESIZE_BICUBIC ? 2.0 : 1.0) * fscale;
+    const leon::ResizeAxis A = leon::resize_axis(in_size, crop_start, crop_size, out_size, filter == LEON_RESIZE_BICUBIC);
     int32_t most = 0;
     for (int32_t o = 0; o < out_size; o++) {
-        const double center = (double)crop_start + ((double)o + 0.5) * scale;
-        int32_t lo = (int32_t)(center - support + 0.5), hi = (int32_t)(center + support + 0.5);
-        if (lo < 0) lo = 0;
-        if (hi > in_size) hi = in_size;
-        if (hi - lo < 1 || hi - lo > filter_taps) return 0;
-        if (hi - lo > most) most = hi - lo;
+        const int32_t n = leon::resize_row_window(A, o).n;
+        if (n < 1 || n > filter_taps) return 0;
+        if (n > most) most = n;
     }
     return most;
 }
@@ -1352,12 +1344,9 @@ static_assert(sizeof(leon_pipeline_region) == 32 && sizeof(leon_pipeline_regions
 
 struct RegionTaps { int32_t x, y; };       // the largest tap count of a region's columns and rows
 
-// Every refusal that needs no device is here (leon_pipeline_regions_check is this function); taps: per region, for the table layout
-int regions_check(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
-                  int32_t* bad, std::vector<RegionTaps>* taps)
+// what a call's config, window and n can be refused for, whichever memory the regions lie in
+int regions_config_check(int32_t fw, int32_t fh, int32_t n_frames, int32_t n, const leon_pipeline_regions_config* cfg)
 {
-    if (bad) *bad = -1;
-    if (!regions || !cfg) return fail(LEON_ERR_INVALID, "null argument");
     for (int i = 0; i < 5; i++)
         if (cfg->reserved[i]) return fail(LEON_ERR_INVALID, "regions config: reserved word %d is %d, not 0", i, cfg->reserved[i]);
     if (cfg->out_width < 1 || cfg->out_width > 4096) return fail(LEON_ERR_INVALID, "regions config: out_width %d is outside 1 .. 4096", cfg->out_width);
@@ -1365,6 +1354,17 @@ int regions_check(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_
     if (!resize_filter_max_taps(cfg->filter)) return fail(LEON_ERR_INVALID, "regions config: filter %d (LEON_RESIZE_TRIANGLE and LEON_RESIZE_BICUBIC are the filters)", cfg->filter);
     if (fw < 1 || fh < 1 || n_frames < 0) return fail(LEON_ERR_INVALID, "regions: %d frames of %d x %d", n_frames, fw, fh);
     if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "regions: %d regions (a call takes 1 .. 65535)", n);
+    return LEON_OK;
+}
+
+// Every refusal that needs no device is here (leon_pipeline_regions_check is this function); taps: per region, for the table layout
+int regions_check(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
+                  int32_t* bad, std::vector<RegionTaps>* taps)
+{
+    if (bad) *bad = -1;
+    if (!regions || !cfg) return fail(LEON_ERR_INVALID, "null argument");
+    const int crc = regions_config_check(fw, fh, n_frames, n, cfg);
+    if (crc != LEON_OK) return crc;
     if (taps) taps->resize((size_t)n);
     for (int32_t i = 0; i < n; i++) {
         const leon_pipeline_region& r = regions[i];
@@ -1420,6 +1420,20 @@ int regions_reserve(leon_pipeline* p, size_t upload_bytes, size_t out_bytes)
     return LEON_OK;
 }
 
+// the ring ids of a delivered window's frames: p->mu is held for the look-up and the copy only (the notify thread and release_window need it)
+int regions_window_ids(leon_pipeline* p, int64_t window, std::vector<uint32_t>* ids)
+{
+    std::lock_guard<std::mutex> lk(p->mu);
+    auto it = p->delivered.find(window);
+    if (it == p->delivered.end()) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    const PipeWindow* w = it->second;
+    if (w->status != LEON_OK) return fail(LEON_ERR_INVALID, "window %lld was delivered with an error (status %d)", (long long)window, w->status);
+    const uint32_t base = (uint32_t)((size_t)w->ring * p->W * p->max_pics);
+    ids->reserve(w->frame_ids.size());
+    for (uint32_t id : w->frame_ids) ids->push_back(base + id);
+    return LEON_OK;
+}
+
 // One call: refusals, the regions' descriptors and tables into pinned staging, one upload, one launch, the wait -- all on the
 // pipeline's regions stream.  device_out NULL with `host`: into the pooled scratch at the default pitch, then packed to the host.
 int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
@@ -1429,21 +1443,12 @@ int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_regio
     if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR) || !p->d_tensor || !p->d_planes)
         return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
     std::lock_guard<std::mutex> call(p->regions_mu);
-    // the window's ring ids: p->mu is held for the look-up and the copy only (the notify thread and release_window need it)
     std::vector<uint32_t> ids;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        auto it = p->delivered.find(window);
-        if (it == p->delivered.end()) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-        const PipeWindow* w = it->second;
-        if (w->status != LEON_OK) return fail(LEON_ERR_INVALID, "window %lld was delivered with an error (status %d)", (long long)window, w->status);
-        const uint32_t base = (uint32_t)((size_t)w->ring * p->W * p->max_pics);
-        ids.reserve(w->frame_ids.size());
-        for (uint32_t id : w->frame_ids) ids.push_back(base + id);
-    }
+    int rc = regions_window_ids(p, window, &ids);
+    if (rc != LEON_OK) return rc;
     std::vector<RegionTaps> taps;
     const int32_t fw = p->vinfo.frame_width, fh = p->vinfo.frame_height;
-    int rc = regions_check(fw, fh, (int32_t)ids.size(), regions, n, cfg, nullptr, &taps);
+    rc = regions_check(fw, fh, (int32_t)ids.size(), regions, n, cfg, nullptr, &taps);
     if (rc != LEON_OK) return rc;
     const int32_t ow = cfg->out_width, oh = cfg->out_height, filter = cfg->filter;
     const size_t region_bytes = (size_t)3 * oh * ow * p->tensor_elem;
@@ -1514,6 +1519,185 @@ int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_regio
     HIP_TRY(hipGetLastError());
     if (host) HIP_TRY(hipMemcpy2DAsync(host, region_bytes, out, pitch, region_bytes, (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return LEON_OK;
+}
+
+// ---- regions whose boxes lie in device memory (leon_pipeline_resample_regions_device) -----------------------------------
+template <class F> constexpr RegionsKernelsOfFilter kBoxesKernelsOfFilter = {{{leon::k_boxes<1, leon::kLayoutChw, F>, leon::k_boxes<1, leon::kLayoutHwc, F>},
+                                                                              {leon::k_boxes<2, leon::kLayoutChw, F>, leon::k_boxes<2, leon::kLayoutHwc, F>},
+                                                                              {leon::k_boxes<4, leon::kLayoutChw, F>, leon::k_boxes<4, leon::kLayoutHwc, F>}}};
+constexpr RegionsKernelsOfFilter kBoxesKernels[4] = {kBoxesKernelsOfFilter<leon::ResTriangle>, {}, {}, kBoxesKernelsOfFilter<leon::ResCubic>};
+static_assert(sizeof(leon::BoxRecord) == sizeof(leon_pipeline_region) && sizeof(leon_pipeline_regions_device) == 64, "include/leon_pipeline.h states the sizes");
+static_assert(leon::kRegionOk == LEON_REGION_OK && leon::kRegionReserved == LEON_REGION_RESERVED && leon::kRegionFrame == LEON_REGION_FRAME &&
+              leon::kRegionBox == LEON_REGION_BOX && leon::kRegionRatioX == LEON_REGION_RATIO_X && leon::kRegionRatioY == LEON_REGION_RATIO_Y &&
+              leon::kRegionTaps == LEON_REGION_TAPS, "the kernels' codes are the header's");
+static_assert(leon::kResizeMaxTapsTriangle == LEON_RESIZE_MAX_TAPS && leon::kResizeMaxTapsCubic == LEON_RESIZE_MAX_TAPS_BICUBIC, "one limit");
+
+// int32 words of a region's table slot: the filter's worst case for the out size (rows of Wx are an odd number of words: both maxima are odd)
+size_t boxes_slot_words(int32_t ow, int32_t oh, int32_t filter)
+{
+    const size_t t = (size_t)resize_filter_max_taps(filter);
+    return 2 * (size_t)ow + (size_t)ow * t + 2 * (size_t)oh + (size_t)oh * t;
+}
+
+// The CPU twin of k_box_tables' judgement: the same functions of leon_resize_row.h in the same order
+int32_t region_status(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_region& r, const leon_pipeline_regions_config& cfg)
+{
+    if (r.reserved[0] | r.reserved[1] | r.reserved[2]) return LEON_REGION_RESERVED;
+    if (r.frame < 0 || r.frame >= n_frames) return LEON_REGION_FRAME;
+    const bool cubic = cfg.filter == LEON_RESIZE_BICUBIC;
+    const int32_t in[2] = {fw, fh}, start[2] = {r.x, r.y}, size[2] = {r.width, r.height}, out[2] = {cfg.out_width, cfg.out_height};
+    const int32_t ratio[2] = {LEON_REGION_RATIO_X, LEON_REGION_RATIO_Y};
+    for (int a = 0; a < 2; a++) {
+        const int32_t s = leon::region_axis_status(in[a], start[a], size[a], out[a], ratio[a]);
+        if (s) return s;
+        const leon::ResizeAxis A = leon::resize_axis(in[a], start[a], size[a], out[a], cubic);
+        for (int32_t o = 0; o < out[a]; o++)
+            if (!leon::resize_row_count_ok(leon::resize_row_window(A, o).n, cubic)) return LEON_REGION_TAPS;
+    }
+    return LEON_REGION_OK;
+}
+
+// the chunk's scratch, grown and never shrunk (regions_mu held): nothing of an earlier call may still run in the old one
+int boxes_reserve(leon_pipeline* p, size_t bytes)
+{
+    if (bytes <= p->boxes_dev_cap) return LEON_OK;
+    if (p->boxes_busy) { HIP_TRY(hipEventSynchronize(p->boxes_done)); p->boxes_busy = false; }
+    const size_t cap = std::max(bytes, (size_t)1 << 20);
+    char* dv = nullptr;
+    if (big_alloc((void**)&dv, cap, kBigCaller) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of device scratch", cap); }
+    if (p->boxes_dev) big_free(p->boxes_dev);
+    p->boxes_dev = dv;
+    p->boxes_dev_cap = cap;
+    return LEON_OK;
+}
+
+// One call: the host's refusals, the window's frame ids uploaded, then per chunk k_box_tables and k_boxes on the caller's stream (or the
+// pipeline's regions stream and a wait).  regions_mu is held while enqueuing only.
+int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_device* c)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    if (!cfg || !c) return fail(LEON_ERR_INVALID, "null argument");
+    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR) || !p->d_tensor || !p->d_planes)
+        return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    std::unique_lock<std::mutex> call(p->regions_mu);
+    std::vector<uint32_t> ids;
+    int rc = regions_window_ids(p, window, &ids);
+    if (rc != LEON_OK) return rc;
+    const int32_t fw = p->vinfo.frame_width, fh = p->vinfo.frame_height, n = c->n;
+    if ((rc = regions_config_check(fw, fh, (int32_t)ids.size(), n, cfg)) != LEON_OK) return rc;
+    if (c->reserved0 || c->reserved[0]) return fail(LEON_ERR_INVALID, "regions: a reserved word of the call is not 0");
+    if (!c->regions) return fail(LEON_ERR_INVALID, "regions: null regions");
+    if ((uintptr_t)c->regions & 3u) return fail(LEON_ERR_INVALID, "regions: regions %p is not 4-byte aligned", (const void*)c->regions);
+    if ((uintptr_t)c->device_status & 3u) return fail(LEON_ERR_INVALID, "regions: device_status %p is not 4-byte aligned", (void*)c->device_status);
+    if (!c->device_out) return fail(LEON_ERR_INVALID, "regions: null device_out");
+    if ((uintptr_t)c->device_out & 255u) return fail(LEON_ERR_INVALID, "regions: device_out %p is not 256-byte aligned", c->device_out);
+    const int32_t ow = cfg->out_width, oh = cfg->out_height, filter = cfg->filter;
+    const size_t region_bytes = (size_t)3 * oh * ow * p->tensor_elem;
+    if (c->out_pitch_bytes && (c->out_pitch_bytes % 256 || c->out_pitch_bytes < region_bytes))
+        return fail(LEON_ERR_INVALID, "regions: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", (unsigned long long)c->out_pitch_bytes, region_bytes);
+    const uint64_t pitch = c->out_pitch_bytes ? c->out_pitch_bytes : (uint64_t)pad256(region_bytes);
+    const int eb = (int)p->tensor_elem, layout = p->tensor_layout;
+    const bool listed = (eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc);
+    const RegionsKernel kb = listed ? kBoxesKernels[filter].k[eb >> 1][layout] : nullptr;
+    if (!kb) return fail(LEON_ERR_INVALID, "regions: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
+    // as many regions a chunk as fit the limit (and 32 bits of table words, which rt_base counts)
+    const size_t slot_words = boxes_slot_words(ow, oh, filter), per_region = slot_words * 4 + sizeof(leon::RegionDesc);
+    const uint64_t limit = c->scratch_limit_bytes ? c->scratch_limit_bytes : LEON_REGIONS_SCRATCH_DEFAULT;
+    if (limit < per_region) return fail(LEON_ERR_INVALID, "regions: scratch_limit_bytes %llu is below one region's %zu bytes", (unsigned long long)limit, per_region);
+    const size_t chunk = (size_t)std::min<uint64_t>({(uint64_t)n, limit / per_region, (((uint64_t)1 << 32) - 1) / slot_words});
+    const size_t ids_bytes = pad256(ids.size() * 4), desc_bytes = pad256(chunk * sizeof(leon::RegionDesc));
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    hipStream_t st = static_cast<hipStream_t>(c->stream);
+    if (!st) {
+        if (!p->regions_stream) HIP_TRY(hipStreamCreateWithFlags(&p->regions_stream, hipStreamNonBlocking));
+        st = p->regions_stream;
+    }
+    if (!p->boxes_done) HIP_TRY(hipEventCreateWithFlags(&p->boxes_done, hipEventDisableTiming));
+    if ((rc = boxes_reserve(p, ids_bytes + desc_bytes + chunk * slot_words * 4)) != LEON_OK) return rc;
+    // the frame ids through a staging entry whose last upload has run (four calls back: as good as always)
+    const unsigned e = p->boxes_ids_next++ % leon_pipeline::kBoxesStaging;
+    if (p->boxes_ids_busy[e]) { HIP_TRY(hipEventSynchronize(p->boxes_ids_done[e])); p->boxes_ids_busy[e] = false; }
+    if (!p->boxes_ids_done[e]) HIP_TRY(hipEventCreateWithFlags(&p->boxes_ids_done[e], hipEventDisableTiming));
+    if (ids.size() > p->boxes_ids_cap[e]) {
+        const size_t cap = std::max(ids.size() * 2, (size_t)1024);
+        uint32_t* h = nullptr;
+        if (hipHostMalloc((void**)&h, cap * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of pinned staging", cap * 4); }
+        if (p->boxes_ids_host[e]) hipHostFree(p->boxes_ids_host[e]);
+        p->boxes_ids_host[e] = h;
+        p->boxes_ids_cap[e] = cap;
+    }
+    std::copy(ids.begin(), ids.end(), p->boxes_ids_host[e]);
+    // from here on the stream holds work: the event is recorded whatever happens, so that the scratch stays covered
+    if (p->boxes_busy) HIP_TRY(hipStreamWaitEvent(st, p->boxes_done, 0));
+    uint32_t* d_ids = reinterpret_cast<uint32_t*>(p->boxes_dev);
+    leon::RegionDesc* d_descs = reinterpret_cast<leon::RegionDesc*>(p->boxes_dev + ids_bytes);
+    int32_t* d_tabs = reinterpret_cast<int32_t*>(p->boxes_dev + ids_bytes + desc_bytes);
+    hipError_t he = hipMemcpyAsync(d_ids, p->boxes_ids_host[e], ids.size() * 4, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && (he = hipEventRecord(p->boxes_ids_done[e], st)) == hipSuccess) p->boxes_ids_busy[e] = true;
+    leon::ResampleGeom G{};
+    G.fw = fw; G.fh = fh; G.ow = ow; G.oh = oh;
+    G.ring = ring_geom(p);
+    leon::BoxCall B{};
+    B.fw = fw; B.fh = fh; B.ow = ow; B.oh = oh;
+    B.n_frames = (int32_t)ids.size(); B.cubic = filter == LEON_RESIZE_BICUBIC;
+    B.slot_words = (uint32_t)slot_words;
+    B.pitch_lo = (uint32_t)(pitch & 0xffffffffu); B.pitch_hi = (uint32_t)(pitch >> 32);
+    const unsigned gx = (unsigned)((ow + leon::kResTileX - 1) / leon::kResTileX), gy = (unsigned)((oh + leon::kResTileY - 1) / leon::kResTileY);
+    const leon::BoxRecord* boxes = reinterpret_cast<const leon::BoxRecord*>(c->regions);
+    for (size_t first = 0; he == hipSuccess && first < (size_t)n; first += chunk) {
+        const unsigned m = (unsigned)std::min(chunk, (size_t)n - first);          // (blockIdx.z of k_boxes: m <= n <= 65535)
+        B.first = (uint32_t)first;
+        hipLaunchKernelGGL(leon::k_box_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, (const uint32_t*)d_ids, d_descs, d_tabs,
+                           c->device_status ? c->device_status + first : nullptr, B);
+        hipLaunchKernelGGL(kb, dim3(gx, gy, m), dim3(leon::kRgbaBlock), 0, st, (const uint8_t*)p->d_planes, static_cast<uint8_t*>(c->device_out), (const leon::RegionDesc*)d_descs,
+                           (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)d_tabs, G);
+        he = hipGetLastError();
+    }
+    if (hipEventRecord(p->boxes_done, st) == hipSuccess) p->boxes_busy = true;
+    else if (he == hipSuccess) he = hipGetLastError();
+    call.unlock();
+    HIP_TRY(he);
+    if (!c->stream) HIP_TRY(hipStreamSynchronize(st));
+    return LEON_OK;
+}
+
+// The device's rows of a batch of single axes, copied back (leon_pipeline_resize_weights_device): memory of its own, the null stream
+int resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,
+                          int32_t* weights, int32_t* status)
+{
+    if (!axes || !first || !count || !weights || !status) return fail(LEON_ERR_INVALID, "null argument");
+    if (n_axes < 1) return fail(LEON_ERR_INVALID, "resize: %d axes", n_axes);
+    if (max_taps < 1) return fail(LEON_ERR_INVALID, "resize: max_taps %d", max_taps);
+    if (!resize_filter_max_taps(filter)) return fail(LEON_ERR_INVALID, "resize filter %d (LEON_RESIZE_TRIANGLE and LEON_RESIZE_BICUBIC are the filters)", filter);
+    int32_t max_out = 0;
+    for (int32_t a = 0; a < n_axes; a++) {
+        if (axes[4 * a] < 1 || axes[4 * a] > 4096) return fail(LEON_ERR_INVALID, "resize: axis %d: in_size %d is outside 1 .. 4096", a, axes[4 * a]);
+        if (axes[4 * a + 3] < 1 || axes[4 * a + 3] > 4096) return fail(LEON_ERR_INVALID, "resize: axis %d: output %d is outside 1 .. 4096", a, axes[4 * a + 3]);
+        max_out = std::max(max_out, axes[4 * a + 3]);
+    }
+    static_assert(sizeof(leon::AxisRecord) == 16, "four words an axis");
+    const size_t rows = (size_t)n_axes * (size_t)max_out, words = (size_t)n_axes * 4 + 2 * rows + rows * (size_t)max_taps + (size_t)n_axes;
+    HIP_TRY(hipSetDevice(device_id));
+    int32_t* d = nullptr;
+    if (hipMalloc((void**)&d, words * 4) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "resize: %zu bytes of device memory", words * 4); }
+    int32_t *d_first = d + (size_t)n_axes * 4, *d_count = d_first + rows, *d_weights = d_count + rows, *d_status = d_weights + rows * (size_t)max_taps;
+    // the caller's arrays go up and come back whole: what the kernel does not write stays as the caller had it
+    hipError_t he = hipMemcpy(d, axes, (size_t)n_axes * 16, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d_first, first, rows * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d_count, count, rows * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(d_weights, weights, rows * (size_t)max_taps * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(leon::k_axis_tables, dim3((unsigned)n_axes), dim3(leon::kRgbaBlock), 0, nullptr, reinterpret_cast<const leon::AxisRecord*>(d), d_first, d_count,
+                           d_weights, d_status, filter == LEON_RESIZE_BICUBIC ? 1 : 0, max_taps, max_out);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipMemcpy(first, d_first, rows * 4, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(count, d_count, rows * 4, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(weights, d_weights, rows * (size_t)max_taps * 4, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(status, d_status, (size_t)n_axes * 4, hipMemcpyDeviceToHost);
+    hipFree(d);
+    HIP_TRY(he);
     return LEON_OK;
 }
 
@@ -2390,6 +2574,25 @@ int leon_pipeline_read_regions(leon_pipeline* p, int64_t window, const leon_pipe
     return resample_regions(p, window, regions, n, cfg, nullptr, 0, host);
 }
 
+int leon_pipeline_resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_device* call)
+{
+    return resample_regions_device(p, window, cfg, call);
+}
+
+int32_t leon_pipeline_region_status(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* region,
+                                    const leon_pipeline_regions_config* cfg)
+{
+    if (!region || !cfg) return fail(LEON_ERR_INVALID, "null argument");
+    const int rc = regions_config_check(frame_width, frame_height, n_frames, 1, cfg);
+    return rc != LEON_OK ? rc : region_status(frame_width, frame_height, n_frames, *region, *cfg);
+}
+
+int leon_pipeline_resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,
+                                        int32_t* weights, int32_t* status)
+{
+    return resize_weights_device(device_id, n_axes, axes, filter, max_taps, first, count, weights, status);
+}
+
 const char* leon_pipeline_error(leon_pipeline* p)
 {
     if (!p) return "";
@@ -2414,6 +2617,7 @@ void leon_pipeline_destroy(leon_pipeline* p)
     // left uploads or parser kernels behind that no window's event covers)
     if (p->copy_stream) hipStreamSynchronize(p->copy_stream);
     if (p->regions_stream) hipStreamSynchronize(p->regions_stream);
+    if (p->boxes_busy) hipEventSynchronize(p->boxes_done);          // (a caller's stream may still run the last call's launches)
     for (hipStream_t vs : p->vlc_stream)
         if (vs) hipStreamSynchronize(vs);
     if (p->dec) leon_sync(p->dec);
@@ -2460,6 +2664,12 @@ void leon_pipeline_destroy(leon_pipeline* p)
     if (p->regions_host) hipHostFree(p->regions_host);
     if (p->regions_dev) big_free(p->regions_dev);
     if (p->regions_out) big_free(p->regions_out);
+    if (p->boxes_dev) big_free(p->boxes_dev);
+    if (p->boxes_done) hipEventDestroy(p->boxes_done);
+    for (int e = 0; e < leon_pipeline::kBoxesStaging; e++) {
+        if (p->boxes_ids_host[e]) hipHostFree(p->boxes_ids_host[e]);
+        if (p->boxes_ids_done[e]) hipEventDestroy(p->boxes_ids_done[e]);
+    }
     if (p->regions_stream) hipStreamDestroy(p->regions_stream);
     if (p->copy_stream) hipStreamDestroy(p->copy_stream);
     if (p->dec) leon_destroy(p->dec);

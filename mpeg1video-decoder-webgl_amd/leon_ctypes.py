@@ -40,6 +40,7 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_create_tensor_format", "leon_pipeline_get_tensor_shape",
     "leon_pipeline_create_tensor_canvas", "leon_pipeline_get_tensor_canvas", "leon_pipeline_letterbox",
     "leon_pipeline_regions_check", "leon_pipeline_resample_regions", "leon_pipeline_read_regions",
+    "leon_pipeline_resample_regions_device", "leon_pipeline_region_status", "leon_pipeline_resize_weights_device",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -304,6 +305,16 @@ class PipelineRegionsConfig(C.Structure):
     _fields_ = [("out_width", C.c_int32), ("out_height", C.c_int32), ("filter", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class PipelineRegionsDevice(C.Structure):
+    _fields_ = [("regions", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("device_out", C.c_void_p), ("out_pitch_bytes", C.c_uint64),
+                ("device_status", C.c_void_p), ("stream", C.c_void_p), ("scratch_limit_bytes", C.c_uint64), ("reserved", C.c_uint64 * 1)]
+
+
+# LEON_REGION_*: the status word of a region whose box lies in device memory (0: resampled; otherwise skipped, and why)
+REGION_OK, REGION_RESERVED, REGION_FRAME, REGION_BOX, REGION_RATIO_X, REGION_RATIO_Y, REGION_TAPS = range(7)
+REGIONS_SCRATCH_DEFAULT = 256 << 20          # LEON_REGIONS_SCRATCH_DEFAULT
+
+
 class PipelineTensorShape(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("element_bytes", C.c_int32), ("layout", C.c_int32), ("channels", C.c_int32), ("height", C.c_int32),
                 ("width", C.c_int32), ("stride_c", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64)]
@@ -419,6 +430,11 @@ def load():
         lib.leon_pipeline_regions_check.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineRegion), C.c_int32, C.POINTER(PipelineRegionsConfig), C.POINTER(C.c_int32)]
         lib.leon_pipeline_resample_regions.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineRegion), C.c_int32, C.POINTER(PipelineRegionsConfig), C.c_void_p, C.c_uint64]
         lib.leon_pipeline_read_regions.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineRegion), C.c_int32, C.POINTER(PipelineRegionsConfig), C.c_void_p]
+    if hasattr(lib, "leon_pipeline_resample_regions_device"):
+        lib.leon_pipeline_resample_regions_device.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineRegionsConfig), C.POINTER(PipelineRegionsDevice)]
+        lib.leon_pipeline_region_status.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineRegion), C.POINTER(PipelineRegionsConfig)]
+        lib.leon_pipeline_region_status.restype = C.c_int32
+        lib.leon_pipeline_resize_weights_device.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -462,6 +478,37 @@ def regions_check(frame_width, frame_height, n_frames, regions, size, filter="tr
         e = LeonError(rc, load().leon_last_error().decode("utf-8", "replace"))
         e.bad = bad.value
         raise e
+
+
+def region_status(frame_width, frame_height, n_frames, region, size, filter="triangle"):
+    """leon_pipeline_region_status: the REGION_* word Pipeline.resample_regions_device writes for region = (frame_index, x, y, w, h) (or a
+    PipelineRegion) in a window of n_frames frames of frame_width x frame_height -- 0 exactly where regions_check accepts the region alone.
+    No device.  LeonError for a size or filter the library refuses."""
+    arr, _, cfg = _regions_args([region], size, filter)
+    st = load().leon_pipeline_region_status(int(frame_width), int(frame_height), int(n_frames), arr, C.byref(cfg))
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return st
+
+
+def resize_weights_device(axes, filter=RESIZE_TRIANGLE, max_taps=None, device_id=0, fill=-1):
+    """leon_pipeline_resize_weights_device: the DEVICE's evaluation of the tables of a batch of axes = [(in_size, crop_start, crop_size,
+    out_size), ...], copied back: (first[n, max_out], count[n, max_out], weights[n, max_out, max_taps], status[n]) with max_out the
+    largest out_size; rows behind an axis's out_size, and all rows of an axis whose status is not 0, hold `fill`.  To be compared word
+    for word with resize_weights / leon_pipeline_resize_weights."""
+    filter = _resize_filter_code(filter)
+    ax = np.ascontiguousarray(np.asarray(axes, dtype=np.int32).reshape(-1, 4))
+    n = len(ax)
+    if max_taps is None:
+        max_taps = RESIZE_MAX_TAPS_BICUBIC if filter == RESIZE_BICUBIC else RESIZE_MAX_TAPS
+    max_out = int(ax[:, 3].max()) if n and 1 <= int(ax[:, 3].max()) <= 4096 else 1
+    first = np.full((max(n, 1), max_out), fill, dtype=np.int32)
+    count = np.full((max(n, 1), max_out), fill, dtype=np.int32)
+    weights = np.full((max(n, 1), max_out, max(1, int(max_taps))), fill, dtype=np.int32)
+    status = np.full(max(n, 1), fill, dtype=np.int32)
+    _chk(load().leon_pipeline_resize_weights_device(int(device_id), n, ax.ctypes.data, filter, int(max_taps), first.ctypes.data, count.ctypes.data,
+                                                    weights.ctypes.data, status.ctypes.data))
+    return first, count, weights, status
 
 
 def _hostptr(a, dtype, keep):
@@ -739,7 +786,8 @@ class Pipeline:
     -- regions = [(frame["_i"], x, y, w, h), ...], a detector's boxes -- to size = (h, w) into one [N, 3, h, w] ("hwc": [N, h, w, 3])
     device batch of the pipeline's element type and table, element = table[c][resize_rgb(rgb of that frame, (x, y, w, h), size, filter)];
     the pipeline's own tensor_size / crop / canvas play no part.  Until the window is released, from the callback or (for a window held
-    by returning False) from any thread; read_regions(...) gives the same as a host array."""
+    by returning False) from any thread; read_regions(...) gives the same as a host array.  resample_regions_device(window, boxes, ...)
+    takes the boxes from a CUDA tensor and only enqueues, on torch's current stream: no host wait between a detector and its classifier."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
@@ -947,6 +995,52 @@ class Pipeline:
         _chk(self.lib.leon_pipeline_resample_regions(self.h, int(window), arr, n, C.byref(cfg), out.data_ptr(), 0 if pitch is None else step))
         shape, strides = self._region_dims(size)
         return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out)
+
+    def resample_regions_device(self, window, boxes, size, filter="triangle", out=None, pitch=None, status=None, stream=None, scratch_limit=None):
+        """leon_pipeline_resample_regions_device: the same batch from boxes that lie in DEVICE memory -- a CUDA int32 torch tensor,
+        [N, 8] contiguous (leon_pipeline_region records) or [N, 5] (frame_index, x, y, w, h; padded to records on the device) -- queued on
+        `stream` (a torch.cuda.Stream; None: torch's current stream of the pipeline's device, where boxes, out and status must lie) behind whatever made the boxes there and in front of
+        whatever reads the result there: NO host synchronisation, the batch and the status words are complete when the stream gets
+        there.  Returns (the batch view as resample_regions builds it, status): status an int32 tensor [N] on the device (`status`, or
+        one the method allocates), REGION_* per box -- 0: resampled; otherwise the region was skipped and its bytes of `out` are
+        untouched (the method's own buffer is not initialised).  The window must stay unreleased and the pipeline open until the
+        stream has run the work.  scratch_limit: bytes of table scratch a chunk of regions may take (None: 256 MiB).  torch's legacy
+        default stream has no handle the library could queue on: there the method waits for the stream, and the call for its work."""
+        import torch
+        if not self.info.tensor_dtype:
+            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        dev = self.device_id
+        if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda and boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] in (5, 8)):
+            raise ValueError("boxes: a CUDA int32 tensor [N, 8] (records) or [N, 5] (frame, x, y, w, h)")
+        for name, t in (("boxes", boxes), ("out", out), ("status", status)):
+            if t is not None and (not t.is_cuda or t.device.index != dev):
+                raise ValueError("%s: on %s, the pipeline's device is cuda:%d" % (name, t.device, dev))
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        n = int(boxes.shape[0])
+        cfg = size if isinstance(size, PipelineRegionsConfig) else PipelineRegionsConfig(int(size[1]), int(size[0]), _resize_filter_code(filter))
+        nbytes, dflt = self.region_bytes((cfg.out_height, cfg.out_width))
+        step = dflt if pitch is None else int(pitch)
+        with torch.cuda.stream(stream):
+            if boxes.shape[1] == 5:
+                boxes = torch.nn.functional.pad(boxes, (0, 3))
+            elif not boxes.is_contiguous():
+                raise ValueError("boxes: [N, 8] records must be contiguous")
+            if out is None:
+                out = torch.empty(max(1, n) * max(step, 1), dtype=torch.uint8, device="cuda:%d" % dev)
+            elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < (n - 1) * step + nbytes:
+                raise ValueError("out: a contiguous uint8 tensor of at least %d bytes" % ((n - 1) * step + nbytes))
+            if status is None:
+                status = torch.empty(max(1, n), dtype=torch.int32, device="cuda:%d" % dev)
+            elif status.dtype != torch.int32 or not status.is_contiguous() or status.numel() < n:
+                raise ValueError("status: a contiguous int32 tensor of at least %d words" % n)
+        handle = int(stream.cuda_stream)
+        if not handle:
+            stream.synchronize()
+        call = PipelineRegionsDevice(boxes.data_ptr() if n else None, n, 0, out.data_ptr(), 0 if pitch is None else step, status.data_ptr(), handle or None,
+                                     0 if scratch_limit is None else int(scratch_limit))
+        _chk(self.lib.leon_pipeline_resample_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        shape, strides = self._region_dims((cfg.out_height, cfg.out_width))
+        return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out), status[:n]
 
     def read_regions(self, window, regions, size, filter="triangle"):
         """leon_pipeline_read_regions: the same regions as a host array [N, 3, h, w] ("hwc": [N, h, w, 3]), packed: float16 / float32 /

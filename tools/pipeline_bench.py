@@ -47,11 +47,16 @@ def main():
                     help="with a tensor output: after each window is delivered and before it is released, N seeded random boxes per frame (ratio <= 16) of the "
                          "full-resolution frames resampled to H x W in one call (leon_pipeline_resample_regions); reports regions/s and the mean time per call")
     ap.add_argument("--regions-filter", choices=["triangle", "bicubic"], default="triangle", help="the filter of --regions")
+    ap.add_argument("--device-boxes", action="store_true",
+                    help="with --regions: the boxes are uploaded as a CUDA tensor and the call is leon_pipeline_resample_regions_device, enqueued on a torch side "
+                         "stream (tables built on the device); the callback waits for that stream before it returns, since the window is released then")
     ap.add_argument("--copy-rate", action="store_true", help="measure leon_measure_copy_bandwidth in this process first (the yardstick of a launch's rate)")
     ap.add_argument("--varied", action="store_true", help="the 16-GOP stream with 16 different contents (tools/stream_1080p.py) instead of --gops GOPs")
     ap.add_argument("--open-gops", action="store_true", help="with --varied: the same recipe written with open GOPs (closed_gop = 0), the leading B pictures "
                                                              "predicting forward (from the GOP before) and bidirectionally")
     a = ap.parse_args()
+    if a.device_boxes and not a.regions:
+        ap.error("--device-boxes goes with --regions")
     if a.open_gops and not a.varied:
         ap.error("--open-gops goes with --varied")
     cached = os.path.join(ROOT, "tools", "probe", "stream_1080p_%dgop.bin" % a.gops)
@@ -111,8 +116,16 @@ def main():
             nbytes, pitch = p.region_bytes((rh, rw))
             if regions_stat["out"] is None or regions_stat["out"].numel() < n * pitch:          # the caller's batch buffer, allocated once
                 regions_stat["out"] = torch.empty(n * pitch, dtype=torch.uint8, device="cuda:0")
+                regions_stat["status"] = torch.empty(n, dtype=torch.int32, device="cuda:0")
             t = time.perf_counter()
-            p.resample_regions(window, boxes, (rh, rw), a.regions_filter, out=regions_stat["out"])
+            if a.device_boxes:
+                st = regions_stat.setdefault("stream", torch.cuda.Stream())
+                with torch.cuda.stream(st):
+                    dev = torch.from_numpy(boxes.astype(np.int32)).to("cuda:0", non_blocking=True)
+                    p.resample_regions_device(window, dev, (rh, rw), a.regions_filter, out=regions_stat["out"], status=regions_stat.get("status"))
+                st.synchronize()
+            else:
+                p.resample_regions(window, boxes, (rh, rw), a.regions_filter, out=regions_stat["out"])
             regions_stat["seconds"] += time.perf_counter() - t
             regions_stat["calls"] += 1
             regions_stat["regions"] += n
@@ -138,7 +151,7 @@ def main():
         "tensor_canvas": [canvas.height, canvas.width] if canvas else None, "tensor_image": [canvas.x, canvas.y, canvas.image_width, canvas.image_height] if canvas else None,
         "tensor_pad_value": list(canvas.pad) if canvas else None, "host_resize": a.host_resize, "windows_in_flight": a.inflight,
         "value": s["pictures"] / s["seconds"], "macroblocks_per_s": s["pictures"] * mbs / s["seconds"],
-        "regions": a.regions, "regions_filter": a.regions_filter if a.regions else None, "regions_calls": regions_stat["calls"] if a.regions else None,
+        "regions": a.regions, "device_boxes": bool(a.regions and a.device_boxes), "regions_filter": a.regions_filter if a.regions else None, "regions_calls": regions_stat["calls"] if a.regions else None,
         "regions_per_s": regions_stat["regions"] / s["seconds"] if a.regions else None,
         "regions_ms_per_call": 1e3 * regions_stat["seconds"] / regions_stat["calls"] if regions_stat["calls"] else None,
         "regions_per_call": regions_stat["regions"] / regions_stat["calls"] if regions_stat["calls"] else None,

@@ -5,9 +5,11 @@ Reports the wall time of a call (it is synchronous: tables built on the host, on
 can be timed without a device (leon_pipeline_regions_check: one of the two passes over the tables), the bytes a call requests (the
 boxes' Y, Cb and Cr samples) and writes, and the copy rate of the same process.  The kernel's own time comes from running this under
 `rocprofv3 --kernel-trace --stats -- python tools/regions_bench.py ...` (k_regions, and k_resample of the pipeline's own --tensor-size
-tensors for comparison: one launch per window of --window GOPs).
+tensors for comparison: one launch per window of --window GOPs).  --device-boxes times the same boxes through
+leon_pipeline_resample_regions_device too (k_box_tables + k_boxes per chunk; enqueue -> stream synchronisation) and checks that both
+paths wrote the same bytes.
 
-  python tools/regions_bench.py [--regions 4096] [--size 224 224] [--calls 5] [--window 128] [--filter triangle]"""
+  python tools/regions_bench.py [--regions 4096] [--size 224 224] [--calls 5] [--window 128] [--filter triangle] [--device-boxes]"""
 import argparse
 import json
 import os
@@ -30,6 +32,9 @@ def main():
     ap.add_argument("--filter", choices=["triangle", "bicubic"], default="triangle")
     ap.add_argument("--tensor-dtype", choices=["float16", "bfloat16", "float32", "uint8"], default="float16")
     ap.add_argument("--tensor-layout", choices=["chw", "hwc"], default="chw")
+    ap.add_argument("--device-boxes", action="store_true",
+                    help="also time leon_pipeline_resample_regions_device: the same boxes uploaded once as a CUDA tensor, the call enqueued on a torch side "
+                         "stream; its time runs from the enqueue to that stream's synchronisation")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -66,10 +71,28 @@ def main():
             t = time.perf_counter()
             p.resample_regions(window, boxes, (oh, ow), a.filter, out=buf)
             times.append(1e3 * (time.perf_counter() - t))
+        dev_times, dev_enqueue, same = None, None, None
+        if a.device_boxes:
+            st = torch.cuda.Stream()
+            with torch.cuda.stream(st):
+                dev_boxes = torch.from_numpy(boxes.astype(np.int32)).cuda()
+                buf2 = torch.empty_like(buf)
+                status = torch.empty(a.regions, dtype=torch.int32, device="cuda:0")
+                p.resample_regions_device(window, dev_boxes, (oh, ow), a.filter, out=buf2, status=status)          # scratch reaches its high-water mark
+            st.synchronize()
+            same = bool(torch.equal(buf, buf2)) and not bool(status.any())
+            dev_times, dev_enqueue = [], []
+            for _ in range(a.calls):
+                t = time.perf_counter()
+                p.resample_regions_device(window, dev_boxes, (oh, ow), a.filter, out=buf2, status=status, stream=st)
+                dev_enqueue.append(1e3 * (time.perf_counter() - t))
+                st.synchronize()
+                dev_times.append(1e3 * (time.perf_counter() - t))
         requested = int((w * h).sum() * 3 // 2)
         with lock:
             out.update(frames=n_frames, call_ms=times, regions_check_ms=check_ms, requested_bytes=requested, written_bytes=a.regions * nbytes,
-                       mean_ratio_x=float((w / ow).mean()), mean_ratio_y=float((h / oh).mean()))
+                       mean_ratio_x=float((w / ow).mean()), mean_ratio_y=float((h / oh).mean()), device_call_ms=dev_times, device_enqueue_ms=dev_enqueue,
+                       device_equals_host=same)
     pipe = L.Pipeline(data, parser_threads=16, gops_per_window=a.window, windows_in_flight=2, loop=a.window * a.windows // 2, gpu_parser=True, output="tensor",
                       tensor_dtype=a.tensor_dtype, tensor_layout=a.tensor_layout, tensor_size=(oh, ow), tensor_filter=a.filter, on_window=on_window)
     try:
@@ -81,6 +104,7 @@ def main():
     mean = sum(out["call_ms"]) / len(out["call_ms"])
     print(json.dumps(dict(out, metric="leon_pipeline_resample_regions: %d regions of a window of %d 1080p frames -> %d x %d %s %s, %s" % (
         a.regions, out["frames"], oh, ow, a.tensor_dtype, a.tensor_layout, a.filter), regions=a.regions, call_ms_mean=mean, regions_per_s=a.regions / (mean * 1e-3),
+        device_call_ms_mean=sum(out["device_call_ms"]) / len(out["device_call_ms"]) if out["device_call_ms"] else None,
         call_gbps_requested_plus_written=(out["requested_bytes"] + out["written_bytes"]) / (mean * 1e-3) / 1e9, copy_gbps_same_process=copy_gbps,
         windows=pipe.windows, frames_per_window=out["frames"])))
 
