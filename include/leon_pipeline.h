@@ -489,6 +489,62 @@ int leon_pipeline_resample_regions_device(leon_pipeline* p, int64_t window, cons
  * argument or a config that check refuses: LEON_ERR_INVALID, which is negative and no status) */
 int32_t leon_pipeline_region_status(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* region,
                                     const leon_pipeline_regions_config* cfg);
+/* Regions letterboxed into the batch's input size: what top-down pose, re-identification, text recognition and most classifiers take
+ * behind a detector -- the box with its ASPECT RATIO KEPT, padded to the model's fixed input, instead of stretched to it.  A call
+ * with a fit whose mode is LEON_REGIONS_FIT_LETTERBOX reads cfg->out_width x out_height as the size of every region's TENSOR, the
+ * canvas cw x ch; region_bytes, the pitch rules and the alignment rules are resample_regions', word for word.  Region i with box
+ * (x, y, w, h) gets
+ *     (ow_i, oh_i, X_i, Y_i) = the integers of leon_pipeline_letterbox(w, h, cw, ch), the same 64-bit expressions; with
+ *                              LEON_REGIONS_ANCHOR_TOP_LEFT X_i = Y_i = 0 (text lines, tiles: padded to the right and below),
+ *     r_i                    = the 8-bit result of the resize definition (leon_pipeline_tensor_resize) for crop = the box,
+ *                              out = ow_i x oh_i, the config's filter,
+ *     tensor                 = T[c][ r_i[Y - Y_i][X - X_i][c] ] inside the rectangle, T[c][pad[c]] everywhere else, CHW or HWC as the
+ *                              pipeline's: leon_pipeline_tensor_canvas's definition with a rectangle per region.
+ * Every one of a valid region's region_bytes is written by the call, and nothing behind them.  It equals, bit for bit, what a
+ * pipeline created with crop = the box, that out size and filter, and a canvas of cw x ch with the image at (X_i, Y_i) delivers.
+ * The ratio limit of 16 and the tap limits are judged on w / ow_i and h / oh_i, so a box may pass stretched and fail letterboxed
+ * (608 x 57 frame, 592 x 52 into 37 x 13: the image is 37 x 3, 52 / 3 > 16); never the other way round, since ow_i <= cw and
+ * oh_i <= ch.  The checks, their order and the status words are leon_pipeline_regions_check's and LEON_REGION_*; a box without a width or a height has
+ * no letterbox and is judged against the canvas (LEON_REGION_BOX on the axis that has none).  On the device path a refused region
+ * has not one byte written, pad included.
+ * One launch per call (chunk): k_fitted<element bytes, layout, filter>, blockIdx.z = the region, x / y = the tiles of the canvas --
+ * of which a region runs its own image's -- and behind them the pad workgroups; tables per region for ow_i x oh_i, built on the host,
+ * or by k_fit_tables on the device in slots of the unchanged worst-case size for out = the canvas (scratch_limit_bytes means what it
+ * meant).
+ * Refused with LEON_ERR_INVALID: another mode or anchor, a pad value outside 0 .. 255, a non-zero reserved word, a non-zero anchor or
+ * pad under LEON_REGIONS_FIT_STRETCH.  fit NULL or all zero is the call without a fit: the same tensors from the same kernels
+ * (k_regions / k_boxes), the rectangle of every region (0, 0, cw, ch). */
+#define LEON_REGIONS_FIT_STRETCH      0
+#define LEON_REGIONS_FIT_LETTERBOX    1
+#define LEON_REGIONS_ANCHOR_CENTRE    0
+#define LEON_REGIONS_ANCHOR_TOP_LEFT  1
+typedef struct leon_pipeline_regions_fit {
+    int32_t mode;                  /* LEON_REGIONS_FIT_* */
+    int32_t anchor;                /* LEON_REGIONS_ANCHOR_* */
+    int32_t pad[3];                /* the 8-bit R, G, B of every element outside the image, 0 .. 255 */
+    int32_t reserved[3];           /* must be 0 */
+} leon_pipeline_regions_fit;       /* 32 bytes */
+/* host only, no device: rect = (X, Y, ow, oh), where the image of a box of box_width x box_height lies in its tensor -- what maps a
+ * keypoint back to the frame.  Refuses what regions_check refuses of the config, a bad fit, a box size below 1. */
+int leon_pipeline_region_fit_rect(int32_t box_width, int32_t box_height, const leon_pipeline_regions_config* cfg,
+                                  const leon_pipeline_regions_fit* fit, int32_t rect[4]);
+/* leon_pipeline_regions_check and leon_pipeline_region_status with the fit */
+int leon_pipeline_regions_fit_check(int32_t frame_width, int32_t frame_height, int32_t n_frames,
+                                    const leon_pipeline_region* regions, int32_t n,
+                                    const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit, int32_t* bad);
+int32_t leon_pipeline_region_fit_status(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* region,
+                                        const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit);
+/* leon_pipeline_resample_regions / read_regions / resample_regions_device with the fit.  device_rects (may be NULL; letterbox only):
+ * DEVICE memory, n x 4 words (X, Y, ow, oh), 4-byte aligned, written for the regions whose status is 0 and left alone for the others,
+ * in stream order with the status words. */
+int leon_pipeline_resample_regions_fit(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n,
+                                       const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit,
+                                       void* device_out, uint64_t out_pitch_bytes);
+int leon_pipeline_read_regions_fit(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n,
+                                   const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit, void* host);
+int leon_pipeline_resample_regions_device_fit(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg,
+                                              const leon_pipeline_regions_fit* fit, const leon_pipeline_regions_device* call,
+                                              int32_t* device_rects);
 /* A diagnostic: the DEVICE's evaluation of the tables of n_axes single axes, copied back, to be compared word for word with
  * leon_pipeline_resize_weights (pixels would hide a weight that is one unit off).  axes = n_axes x {in_size, crop_start, crop_size,
  * out_size}; with max_out the largest out_size of the batch, axis a's tables lie at a fixed pitch: first[a * max_out + o],

@@ -2187,7 +2187,7 @@ struct RegionDesc {
     int32_t taps_x, taps_y;              // row lengths of this region's weight tables (taps_x odd)
     uint32_t dst_lo, dst_hi;             // byte offset of the region's tensor in the caller's buffer: index * pitch
     int32_t status;                      // 0 on the host path; k_box_tables: kRegion* (non-zero: k_boxes leaves the region alone)
-    uint32_t pad[4];
+    int32_t iw, ih, ix, iy;              // k_fitted only: the region's image, iw x ih at (ix, iy) of its tensor (0 where the image is the tensor)
 };                                       // 64 bytes
 template <int EB, int LAYOUT, class F>
 __global__ __launch_bounds__(kRgbaBlock) void k_regions(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ out, const RegionDesc* __restrict__ descs,
@@ -2245,29 +2245,50 @@ __device__ __forceinline__ void box_axis_row(const ResizeAxis& A, int32_t o, int
     for (int32_t k = 0; k < R.n; k++) row[k] = resize_row_weight(resize_row_tap(A, R, k), sum);
     for (int32_t k = R.n; k < row_len; k++) row[k] = 0;
 }
-__global__ __launch_bounds__(kRgbaBlock) void k_box_tables(const BoxRecord* __restrict__ boxes, const uint32_t* __restrict__ frame_ids, RegionDesc* __restrict__ descs,
-                                                           int32_t* __restrict__ tabs, int32_t* __restrict__ status_out, BoxCall c)
+// What the tables of a region are built for (`FIT`).  BoxStretch: the call's out size, every region's (k_box_tables).  BoxLetterbox: the
+// region's own image, the letterbox of its box in the call's out size -- the canvas (k_fit_tables); the rectangle goes into the
+// descriptor's spare words and, for a region that is valid, to the caller's `rects`.  The slot of a region is sized for the canvas,
+// which no image exceeds on either axis.
+struct BoxStretch {
+    __device__ __forceinline__ FitRect rect(const BoxRecord&, const BoxCall& c) const { return FitRect{c.ow, c.oh, 0, 0}; }
+    __device__ __forceinline__ void place(RegionDesc&, const FitRect&, uint32_t) const {}
+};
+struct BoxLetterbox {
+    int32_t* __restrict__ rects;         // n x 4 words (x, y, width, height) from the chunk's first region on, or NULL
+    int32_t top_left;
+    __device__ __forceinline__ FitRect rect(const BoxRecord& r, const BoxCall& c) const { return region_fit_rect(r.width, r.height, c.ow, c.oh, top_left != 0); }
+    __device__ __forceinline__ void place(RegionDesc& d, const FitRect& f, uint32_t i) const
+    {
+        d.iw = f.ow; d.ih = f.oh; d.ix = f.x; d.iy = f.y;
+        if (rects && threadIdx.x < 4) rects[(size_t)i * 4 + threadIdx.x] = threadIdx.x == 0 ? f.x : threadIdx.x == 1 ? f.y : threadIdx.x == 2 ? f.ow : f.oh;
+    }
+};
+template <class FIT>
+__device__ __forceinline__ void box_tables_body(const BoxRecord* __restrict__ boxes, const uint32_t* __restrict__ frame_ids, RegionDesc* __restrict__ descs,
+                                                int32_t* __restrict__ tabs, int32_t* __restrict__ status_out, const BoxCall& c, const FIT& fit)
 {
     __shared__ int32_t most_s[2];
     const uint32_t i = blockIdx.x;
     const BoxRecord r = boxes[i];
     const bool cubic = c.cubic != 0;
+    const FitRect image = fit.rect(r, c);
+    const int32_t ow = image.ow, oh = image.oh;
     int32_t status = kRegionOk, sx = kRegionOk, sy = kRegionOk;
     if (r.reserved[0] | r.reserved[1] | r.reserved[2]) status = kRegionReserved;
     else if (r.frame < 0 || r.frame >= c.n_frames) status = kRegionFrame;
     else {
-        sx = region_axis_status(c.fw, r.x, r.width, c.ow, kRegionRatioX);
-        sy = region_axis_status(c.fh, r.y, r.height, c.oh, kRegionRatioY);
+        sx = region_axis_status(c.fw, r.x, r.width, ow, kRegionRatioX);
+        sy = region_axis_status(c.fh, r.y, r.height, oh, kRegionRatioY);
     }
     // (the axes of a box that is refused are never evaluated: resize_axis stands on region_axis_status)
     const bool do_x = status == kRegionOk && sx == kRegionOk, do_y = status == kRegionOk && sy == kRegionOk;
     ResizeAxis X{}, Y{};
-    if (do_x) X = resize_axis(c.fw, r.x, r.width, c.ow, cubic);
-    if (do_y) Y = resize_axis(c.fh, r.y, r.height, c.oh, cubic);
+    if (do_x) X = resize_axis(c.fw, r.x, r.width, ow, cubic);
+    if (do_y) Y = resize_axis(c.fh, r.y, r.height, oh, cubic);
     if (threadIdx.x < 2) most_s[threadIdx.x] = 0;
     __syncthreads();
-    if (do_x) atomicMax(&most_s[0], box_axis_most(X, c.ow));
-    if (do_y) atomicMax(&most_s[1], box_axis_most(Y, c.oh));
+    if (do_x) atomicMax(&most_s[0], box_axis_most(X, ow));
+    if (do_y) atomicMax(&most_s[1], box_axis_most(Y, oh));
     __syncthreads();
     const int32_t most_x = most_s[0], most_y = most_s[1];
     if (status == kRegionOk)
@@ -2278,13 +2299,14 @@ __global__ __launch_bounds__(kRgbaBlock) void k_box_tables(const BoxRecord* __re
         d.frame_id = frame_ids[r.frame];
         d.rt_base = i * c.slot_words;
         d.taps_x = most_x | 1; d.taps_y = most_y;
-        d.off_cx = (uint32_t)c.ow;
-        d.off_wx = d.off_cx + (uint32_t)c.ow;
-        d.off_fy = d.off_wx + (uint32_t)c.ow * (uint32_t)d.taps_x;
-        d.off_cy = d.off_fy + (uint32_t)c.oh;
-        d.off_wy = d.off_cy + (uint32_t)c.oh;
+        d.off_cx = (uint32_t)ow;
+        d.off_wx = d.off_cx + (uint32_t)ow;
+        d.off_fy = d.off_wx + (uint32_t)ow * (uint32_t)d.taps_x;
+        d.off_cy = d.off_fy + (uint32_t)oh;
+        d.off_wy = d.off_cy + (uint32_t)oh;
         const uint64_t dst = (uint64_t)(c.first + i) * join64(c.pitch_lo, c.pitch_hi);
         d.dst_lo = (uint32_t)(dst & 0xffffffffu); d.dst_hi = (uint32_t)(dst >> 32);
+        fit.place(d, image, i);
     }
     if (threadIdx.x == 0) {
         descs[i] = d;
@@ -2292,10 +2314,22 @@ __global__ __launch_bounds__(kRgbaBlock) void k_box_tables(const BoxRecord* __re
     }
     if (status != kRegionOk) return;
     int32_t* __restrict__ t = tabs + (size_t)d.rt_base;
-    for (int32_t row = (int32_t)threadIdx.x; row < c.ow + c.oh; row += kRgbaBlock) {
-        if (row < c.ow) box_axis_row(X, row, t, t + d.off_cx, t + d.off_wx + (size_t)row * (size_t)d.taps_x, d.taps_x);
-        else box_axis_row(Y, row - c.ow, t + d.off_fy, t + d.off_cy, t + d.off_wy + (size_t)(row - c.ow) * (size_t)d.taps_y, d.taps_y);
+    for (int32_t row = (int32_t)threadIdx.x; row < ow + oh; row += kRgbaBlock) {
+        if (row < ow) box_axis_row(X, row, t, t + d.off_cx, t + d.off_wx + (size_t)row * (size_t)d.taps_x, d.taps_x);
+        else box_axis_row(Y, row - ow, t + d.off_fy, t + d.off_cy, t + d.off_wy + (size_t)(row - ow) * (size_t)d.taps_y, d.taps_y);
     }
+}
+__global__ __launch_bounds__(kRgbaBlock) void k_box_tables(const BoxRecord* __restrict__ boxes, const uint32_t* __restrict__ frame_ids, RegionDesc* __restrict__ descs,
+                                                           int32_t* __restrict__ tabs, int32_t* __restrict__ status_out, BoxCall c)
+{
+    box_tables_body(boxes, frame_ids, descs, tabs, status_out, c, BoxStretch{});
+}
+// (the name carries no other kernel family's: the resource tests count families by substring)
+__global__ __launch_bounds__(kRgbaBlock) void k_fit_tables(const BoxRecord* __restrict__ boxes, const uint32_t* __restrict__ frame_ids, RegionDesc* __restrict__ descs,
+                                                           int32_t* __restrict__ tabs, int32_t* __restrict__ status_out, int32_t* __restrict__ rects, int32_t top_left,
+                                                           BoxCall c)
+{
+    box_tables_body(boxes, frame_ids, descs, tabs, status_out, c, BoxLetterbox{rects, top_left});
 }
 // The same rows for a batch of single axes at a fixed pitch (leon_pipeline_resize_weights_device, a diagnostic: the doubles' outcome
 // compared word for word with the host's): one workgroup per axis, `max_out` rows of `max_taps` words each.  status: kRegionBox, kRegionRatioX
@@ -2359,19 +2393,39 @@ __device__ __forceinline__ void pad_store_elem(uint32_t v, __amdgpu_buffer_rsrc_
     else if constexpr (EB == 2) __builtin_amdgcn_raw_buffer_store_b16((Elem)v, rs, (int)at, 0, kAuxFrameStore);
     else __builtin_amdgcn_raw_buffer_store_b8((Elem)v, rs, (int)at, 0, kAuxFrameStore);
 }
-template <int EB, int LAYOUT>
-__device__ __forceinline__ void pad_body(uint8_t* __restrict__ tensor_ring, const uint32_t* __restrict__ frame_ids, const uint32_t* __restrict__ table,
-                                         const LetterboxGeom& G, uint32_t group)
+// Which tensor a pad workgroup works on and where its image lies (`P`), asked as resample_body asks its `W`.  RingPad: frame
+// blockIdx.z of the pipeline's tensor ring, the launch's one rectangle (k_letterbox).  RegionPad: what k_fitted has read from its
+// region's descriptor.
+struct RingPad {
+    uint8_t* __restrict__ tensor_ring;
+    const uint32_t* __restrict__ frame_ids;
+    const LetterboxGeom& G;
+    __device__ __forceinline__ const CanvasGeom& canvas() const { return G.canvas; }
+    __device__ __forceinline__ int32_t image_width() const { return G.image.ow; }
+    __device__ __forceinline__ int32_t image_height() const { return G.image.oh; }
+    __device__ __forceinline__ uint8_t* tensor() const { return tensor_ring + (size_t)frame_ids[blockIdx.z] * join64(G.image.ring.tensor_pitch_lo, G.image.ring.tensor_pitch_hi); }
+};
+struct RegionPad {
+    uint8_t* at;
+    CanvasGeom C;
+    int32_t iw, ih;
+    __device__ __forceinline__ const CanvasGeom& canvas() const { return C; }
+    __device__ __forceinline__ int32_t image_width() const { return iw; }
+    __device__ __forceinline__ int32_t image_height() const { return ih; }
+    __device__ __forceinline__ uint8_t* tensor() const { return at; }
+};
+template <int EB, int LAYOUT, class P>
+__device__ __forceinline__ void pad_body(const P& where, const uint32_t* __restrict__ table, uint32_t group)
 {
     typedef typename ElemOf<EB>::type Elem;
     constexpr bool kHwc = LAYOUT == kLayoutHwc;
     constexpr int kLineElems = 16 / EB;
-    const CanvasGeom& C = G.canvas;
+    const CanvasGeom& C = where.canvas();
     const uint32_t cw = (uint32_t)C.cw, ch = (uint32_t)C.ch;
     const uint32_t row_elems = kHwc ? 3u * cw : cw;                                      // a row of the tensor in memory order
     const uint32_t total = 3u * cw * ch;                                                 // elements of the tensor (< 2^26)
-    const uint32_t ix0 = (kHwc ? 3u : 1u) * (uint32_t)C.x, ix1 = ix0 + (kHwc ? 3u : 1u) * (uint32_t)G.image.ow;      // the image's elements in its rows
-    const uint32_t iy0 = (uint32_t)C.y, iy1 = iy0 + (uint32_t)G.image.oh;
+    const uint32_t ix0 = (kHwc ? 3u : 1u) * (uint32_t)C.x, ix1 = ix0 + (kHwc ? 3u : 1u) * (uint32_t)where.image_width();      // the image's elements in its rows
+    const uint32_t iy0 = (uint32_t)C.y, iy1 = iy0 + (uint32_t)where.image_height();
     // the pad elements T[c][pad[c]] (uint8: the value itself)
     uint32_t pe[3];
 #pragma unroll
@@ -2380,7 +2434,7 @@ __device__ __forceinline__ void pad_body(uint8_t* __restrict__ tensor_ring, cons
         if constexpr (EB == 1) pe[c] = v;
         else pe[c] = reinterpret_cast<const Elem*>(table)[c * 256 + v];
     }
-    uint8_t* dst = tensor_ring + (size_t)frame_ids[blockIdx.z] * join64(G.image.ring.tensor_pitch_lo, G.image.ring.tensor_pitch_hi);
+    uint8_t* dst = where.tensor();
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, (int)(total * EB), 0x00020000);
     const uint32_t n_lines = (total * EB + 15u) / 16u;
 #pragma unroll 1
@@ -2461,10 +2515,42 @@ __global__ __launch_bounds__(kRgbaBlock) void k_letterbox(const uint8_t* __restr
 {
     const uint32_t tile_rows = (uint32_t)(G.image.oh + kResTileY - 1) / (uint32_t)kResTileY;
     if (blockIdx.y >= tile_rows) {
-        pad_body<EB, LAYOUT>(tensor_ring, frame_ids, table, G, (blockIdx.y - tile_rows) * gridDim.x + blockIdx.x);
+        pad_body<EB, LAYOUT>(RingPad{tensor_ring, frame_ids, G}, table, (blockIdx.y - tile_rows) * gridDim.x + blockIdx.x);
         return;
     }
     resample_body<EB, LAYOUT, F>(RingFrame{planes_ring, tensor_ring, frame_ids}, table, T, rt, G.image, G.canvas);
+}
+
+// ---- regions letterboxed into the batch's tensor size (leon_pipeline.h, leon_pipeline_regions_fit) ------------------------------
+// k_letterbox with a rectangle per region: every region of a call has the canvas's size cw x ch (G.ow x G.oh of the launch) and an
+// image of its own in it, iw x ih at (ix, iy) of its descriptor -- the letterbox of its box -- with tables built for iw x ih.  One
+// family for both roads: the host path's descriptors carry status 0, the device path's come from k_fit_tables.
+// Grid: x = the canvas's tile columns, y = its tile rows and behind them the pad workgroup rows of a cw x ch tensor, z = the region.
+// A workgroup reads its region's descriptor (one address per workgroup: scalar loads) and decides, before any table load or LDS use
+// and the same for all its lanes: a refused region -- leave, not one byte of it is written, pad included; a tile row of the canvas --
+// resample_body with the region's own image size and origin if the tile is one of the image's ceil(iw / 32) x ceil(ih / 8), else
+// leave (the image's tiles are numbered from ITS origin, so these are the first columns and rows of the grid); behind the canvas's
+// tile rows -- pad_body on the region's tensor, which stores every byte outside the image's rectangle and none inside.
+template <int EB, int LAYOUT, class F>
+__global__ __launch_bounds__(kRgbaBlock) void k_fitted(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ out, const RegionDesc* __restrict__ descs,
+                                                       const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ tabs,
+                                                       ResampleGeom G, uint32_t pad)
+{
+    const RegionDesc& d = descs[blockIdx.z];
+    if (d.status != kRegionOk) return;
+    const CanvasGeom C{G.ow, G.oh, d.ix, d.iy, pad};
+    uint8_t* dst = out + join64(d.dst_lo, d.dst_hi);
+    const uint32_t tile_rows = (uint32_t)(G.oh + kResTileY - 1) / (uint32_t)kResTileY;
+    if (blockIdx.y >= tile_rows) {
+        pad_body<EB, LAYOUT>(RegionPad{dst, C, d.iw, d.ih}, table, (blockIdx.y - tile_rows) * gridDim.x + blockIdx.x);
+        return;
+    }
+    if (blockIdx.x * (uint32_t)kResTileX >= (uint32_t)d.iw || blockIdx.y * (uint32_t)kResTileY >= (uint32_t)d.ih) return;
+    G.ow = d.iw; G.oh = d.ih;
+    G.taps_x = d.taps_x; G.taps_y = d.taps_y;
+    G.off_cx = d.off_cx; G.off_wx = d.off_wx; G.off_fy = d.off_fy; G.off_cy = d.off_cy; G.off_wy = d.off_wy;
+    const RegionFrame where{FramePair{planes_ring + (size_t)d.frame_id * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi), dst}};
+    resample_body<EB, LAYOUT, F>(where, table, T, tabs + d.rt_base, G, C);
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

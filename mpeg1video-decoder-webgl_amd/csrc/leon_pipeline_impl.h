@@ -1342,6 +1342,21 @@ constexpr RegionsKernelsOfFilter kRegionsKernels[4] = {kRegionsKernelsOf<leon::R
 static_assert(sizeof(leon::RegionDesc) == 64, "a descriptor is 16 dwords");
 static_assert(sizeof(leon_pipeline_region) == 32 && sizeof(leon_pipeline_regions_config) == 32, "include/leon_pipeline.h states the sizes");
 
+// ... and k_fitted where every region is letterboxed into the call's out size (leon_pipeline_regions_fit), on both roads
+typedef void (*FittedKernel)(const uint8_t*, uint8_t*, const leon::RegionDesc*, const uint32_t*, const leon::Tables*, const int32_t*, leon::ResampleGeom, uint32_t);
+struct FittedKernelsOfFilter { FittedKernel k[3][2]; };
+template <class F> constexpr FittedKernelsOfFilter kFittedKernelsOf = {{{leon::k_fitted<1, leon::kLayoutChw, F>, leon::k_fitted<1, leon::kLayoutHwc, F>},
+                                                                        {leon::k_fitted<2, leon::kLayoutChw, F>, leon::k_fitted<2, leon::kLayoutHwc, F>},
+                                                                        {leon::k_fitted<4, leon::kLayoutChw, F>, leon::k_fitted<4, leon::kLayoutHwc, F>}}};
+constexpr FittedKernelsOfFilter kFittedKernels[4] = {kFittedKernelsOf<leon::ResTriangle>, {}, {}, kFittedKernelsOf<leon::ResCubic>};
+// the pad's workgroup rows behind the canvas's tile rows: whole rows of gx workgroups that cover every 16-byte line of a region's
+// tensor, kPadLinesPerGroup each (launch_tensors' rule; here always, since a call's regions differ in what they pad)
+unsigned fitted_pad_rows(size_t region_bytes, unsigned gx)
+{
+    const size_t lines = (region_bytes + 15) / 16, groups = (lines + leon::kPadLinesPerGroup - 1) / leon::kPadLinesPerGroup;
+    return (unsigned)((groups + gx - 1) / gx);
+}
+
 struct RegionTaps { int32_t x, y; };       // the largest tap count of a region's columns and rows
 
 // what a call's config, window and n can be refused for, whichever memory the regions lie in
@@ -1357,9 +1372,39 @@ int regions_config_check(int32_t fw, int32_t fh, int32_t n_frames, int32_t n, co
     return LEON_OK;
 }
 
+// The fit of a call as the kernels take it (leon_pipeline_regions_fit); every refusal of the settings is in regions_fit_check
+struct RegionsFit {
+    bool letterbox = false, top_left = false;
+    uint32_t pad = 0;                    // R, G, B in bits 0, 8, 16 (CanvasGeom::pad)
+};
+static_assert(sizeof(leon_pipeline_regions_fit) == 32, "include/leon_pipeline.h states the size");
+int regions_fit_check(const leon_pipeline_regions_fit* f, RegionsFit* out)
+{
+    *out = RegionsFit{};
+    if (!f) return LEON_OK;
+    for (int i = 0; i < 3; i++)
+        if (f->reserved[i]) return fail(LEON_ERR_INVALID, "regions fit: reserved word %d is %d, not 0", i, f->reserved[i]);
+    if (f->mode != LEON_REGIONS_FIT_STRETCH && f->mode != LEON_REGIONS_FIT_LETTERBOX) return fail(LEON_ERR_INVALID, "regions fit: mode %d", f->mode);
+    if (f->anchor != LEON_REGIONS_ANCHOR_CENTRE && f->anchor != LEON_REGIONS_ANCHOR_TOP_LEFT) return fail(LEON_ERR_INVALID, "regions fit: anchor %d", f->anchor);
+    for (int i = 0; i < 3; i++)
+        if (f->pad[i] < 0 || f->pad[i] > 255) return fail(LEON_ERR_INVALID, "regions fit: pad value %d is %d, outside 0 .. 255", i, f->pad[i]);
+    if (f->mode == LEON_REGIONS_FIT_STRETCH && (f->anchor | f->pad[0] | f->pad[1] | f->pad[2]))
+        return fail(LEON_ERR_INVALID, "regions fit: an anchor or a pad value with LEON_REGIONS_FIT_STRETCH, which has neither");
+    out->letterbox = f->mode == LEON_REGIONS_FIT_LETTERBOX;
+    out->top_left = f->anchor == LEON_REGIONS_ANCHOR_TOP_LEFT;
+    out->pad = (uint32_t)f->pad[0] | ((uint32_t)f->pad[1] << 8) | ((uint32_t)f->pad[2] << 16);
+    return LEON_OK;
+}
+// a region's image in its tensor: the tensor itself when stretched, else the letterbox of its box (leon_resize_row.h, the device's text too)
+leon::FitRect region_image(const leon_pipeline_region& r, const leon_pipeline_regions_config& cfg, const RegionsFit& fit)
+{
+    if (!fit.letterbox) return leon::FitRect{cfg.out_width, cfg.out_height, 0, 0};
+    return leon::region_fit_rect(r.width, r.height, cfg.out_width, cfg.out_height, fit.top_left);
+}
+
 // Every refusal that needs no device is here (leon_pipeline_regions_check is this function); taps: per region, for the table layout
 int regions_check(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
-                  int32_t* bad, std::vector<RegionTaps>* taps)
+                  const RegionsFit& fit, int32_t* bad, std::vector<RegionTaps>* taps)
 {
     if (bad) *bad = -1;
     if (!regions || !cfg) return fail(LEON_ERR_INVALID, "null argument");
@@ -1374,13 +1419,14 @@ int regions_check(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_
         if (r.frame < 0 || r.frame >= n_frames) return fail(LEON_ERR_INVALID, "region %d: frame %d is outside the window's %d frames", i, r.frame, n_frames);
         // a call that goes on to build the tables (taps != NULL) needs the row lengths only: the weights are judged when they are built
         RegionTaps t{};
+        const leon::FitRect image = region_image(r, *cfg, fit);          // (the limits are judged on the region's own out size)
         if (taps) {
-            t.x = resize_axis_taps(fw, r.x, r.width, cfg->out_width, cfg->filter);
-            t.y = resize_axis_taps(fh, r.y, r.height, cfg->out_height, cfg->filter);
+            t.x = resize_axis_taps(fw, r.x, r.width, image.ow, cfg->filter);
+            t.y = resize_axis_taps(fh, r.y, r.height, image.oh, cfg->filter);
         }
         int rc = LEON_OK;
-        if ((!t.x && (rc = resize_axis_build("width", fw, r.x, r.width, cfg->out_width, cfg->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS_BICUBIC, &t.x)) != LEON_OK) ||
-            (!t.y && (rc = resize_axis_build("height", fh, r.y, r.height, cfg->out_height, cfg->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS_BICUBIC, &t.y)) != LEON_OK)) {
+        if ((!t.x && (rc = resize_axis_build("width", fw, r.x, r.width, image.ow, cfg->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS_BICUBIC, &t.x)) != LEON_OK) ||
+            (!t.y && (rc = resize_axis_build("height", fh, r.y, r.height, image.oh, cfg->filter, nullptr, nullptr, nullptr, LEON_RESIZE_MAX_TAPS_BICUBIC, &t.y)) != LEON_OK)) {
             const std::string why = g_err;
             return fail(rc, "region %d: %s", i, why.c_str());
         }
@@ -1437,9 +1483,12 @@ int regions_window_ids(leon_pipeline* p, int64_t window, std::vector<uint32_t>* 
 // One call: refusals, the regions' descriptors and tables into pinned staging, one upload, one launch, the wait -- all on the
 // pipeline's regions stream.  device_out NULL with `host`: into the pooled scratch at the default pitch, then packed to the host.
 int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
-                     void* device_out, uint64_t out_pitch, void* host)
+                     const leon_pipeline_regions_fit* fit_settings, void* device_out, uint64_t out_pitch, void* host)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    RegionsFit fit;
+    int frc = regions_fit_check(fit_settings, &fit);
+    if (frc != LEON_OK) return frc;
     if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR) || !p->d_tensor || !p->d_planes)
         return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
     std::lock_guard<std::mutex> call(p->regions_mu);
@@ -1448,7 +1497,7 @@ int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_regio
     if (rc != LEON_OK) return rc;
     std::vector<RegionTaps> taps;
     const int32_t fw = p->vinfo.frame_width, fh = p->vinfo.frame_height;
-    rc = regions_check(fw, fh, (int32_t)ids.size(), regions, n, cfg, nullptr, &taps);
+    rc = regions_check(fw, fh, (int32_t)ids.size(), regions, n, cfg, fit, nullptr, &taps);
     if (rc != LEON_OK) return rc;
     const int32_t ow = cfg->out_width, oh = cfg->out_height, filter = cfg->filter;
     const size_t region_bytes = (size_t)3 * oh * ow * p->tensor_elem;
@@ -1463,12 +1512,17 @@ int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_regio
     const int eb = (int)p->tensor_elem, layout = p->tensor_layout;
     const bool listed = (eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc);
     const RegionsKernel kr = listed ? kRegionsKernels[filter].k[eb >> 1][layout] : nullptr;
-    if (!kr) return fail(LEON_ERR_INVALID, "regions: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
+    const FittedKernel kf = listed ? kFittedKernels[filter].k[eb >> 1][layout] : nullptr;
+    if (!kr || !kf) return fail(LEON_ERR_INVALID, "regions: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
 
-    // [descriptors | tables]: a region's tables as plan_resize lays out a pipeline's, rows of its own tap counts
+    // [descriptors | tables]: a region's tables as plan_resize lays out a pipeline's, rows of its own tap counts -- and, letterboxed,
+    // of its own image size
     const size_t desc_bytes = pad256((size_t)n * sizeof(leon::RegionDesc));
     size_t words = 0;
-    for (int32_t i = 0; i < n; i++) words += 2 * (size_t)ow + (size_t)ow * (size_t)(taps[(size_t)i].x | 1) + 2 * (size_t)oh + (size_t)oh * (size_t)taps[(size_t)i].y;
+    for (int32_t i = 0; i < n; i++) {
+        const leon::FitRect image = region_image(regions[i], *cfg, fit);
+        words += 2 * (size_t)image.ow + (size_t)image.ow * (size_t)(taps[(size_t)i].x | 1) + 2 * (size_t)image.oh + (size_t)image.oh * (size_t)taps[(size_t)i].y;
+    }
     if (words >= ((size_t)1 << 32)) return fail(LEON_ERR_INVALID, "regions: the tables of %d regions take %zu bytes (4 GiB a call at most)", n, words * 4);
     const size_t upload_bytes = desc_bytes + words * 4;
     HIP_TRY(hipSetDevice(p->cfg.device_id));
@@ -1481,16 +1535,19 @@ int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_regio
     size_t at = 0;
     for (int32_t i = 0; i < n; i++) {
         const leon_pipeline_region& r = regions[i];
+        const leon::FitRect image = region_image(r, *cfg, fit);
+        const int32_t iw = image.ow, ih = image.oh;
         leon::ResampleGeom R = G;
+        R.ow = iw; R.oh = ih;
         R.taps_x = taps[(size_t)i].x | 1; R.taps_y = taps[(size_t)i].y;          // (odd rows of Wx: plan_resize says why)
-        R.off_cx = (uint32_t)ow;
-        R.off_wx = R.off_cx + (uint32_t)ow;
-        R.off_fy = R.off_wx + (uint32_t)ow * (uint32_t)R.taps_x;
-        R.off_cy = R.off_fy + (uint32_t)oh;
-        R.off_wy = R.off_cy + (uint32_t)oh;
+        R.off_cx = (uint32_t)iw;
+        R.off_wx = R.off_cx + (uint32_t)iw;
+        R.off_fy = R.off_wx + (uint32_t)iw * (uint32_t)R.taps_x;
+        R.off_cy = R.off_fy + (uint32_t)ih;
+        R.off_wy = R.off_cy + (uint32_t)ih;
         int32_t* t = tabs + at;
-        if ((rc = resize_axis_build("width", fw, r.x, r.width, ow, filter, t, t + R.off_cx, t + R.off_wx, R.taps_x, nullptr)) != LEON_OK ||
-            (rc = resize_axis_build("height", fh, r.y, r.height, oh, filter, t + R.off_fy, t + R.off_cy, t + R.off_wy, R.taps_y, nullptr)) != LEON_OK ||
+        if ((rc = resize_axis_build("width", fw, r.x, r.width, iw, filter, t, t + R.off_cx, t + R.off_wx, R.taps_x, nullptr)) != LEON_OK ||
+            (rc = resize_axis_build("height", fh, r.y, r.height, ih, filter, t + R.off_fy, t + R.off_cy, t + R.off_wy, R.taps_y, nullptr)) != LEON_OK ||
             (rc = resize_footprint_check(t, R, filter)) != LEON_OK) {
             const std::string why = g_err;
             return fail(rc, "region %d: %s", i, why.c_str());
@@ -1502,19 +1559,26 @@ int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_regio
         d.taps_x = R.taps_x; d.taps_y = R.taps_y;
         const uint64_t dst = (uint64_t)i * pitch;
         d.dst_lo = (uint32_t)(dst & 0xffffffffu); d.dst_hi = (uint32_t)(dst >> 32);
+        if (fit.letterbox) { d.iw = iw; d.ih = ih; d.ix = image.x; d.iy = image.y; }
         descs[i] = d;
-        at += (size_t)R.off_wy + (size_t)oh * (size_t)R.taps_y;
+        at += (size_t)R.off_wy + (size_t)ih * (size_t)R.taps_y;
     }
     uint8_t* out = host ? p->regions_out : static_cast<uint8_t*>(device_out);
     hipStream_t st = p->regions_stream;
     HIP_TRY(hipMemcpyAsync(p->regions_dev, p->regions_host, upload_bytes, hipMemcpyHostToDevice, st));
     G.ring = ring_geom(p);
     const unsigned gx = (unsigned)((ow + leon::kResTileX - 1) / leon::kResTileX), gy = (unsigned)((oh + leon::kResTileY - 1) / leon::kResTileY);
+    const unsigned gy_fit = gy + fitted_pad_rows(region_bytes, gx);
+    if (fit.letterbox && gy_fit > 65535u) return fail(LEON_ERR_INVALID, "regions fit: %u workgroup rows", gy_fit);
     const leon::RegionDesc* d_descs = reinterpret_cast<const leon::RegionDesc*>(p->regions_dev);
     for (size_t first = 0; first < (size_t)n; first += 65535) {          // (blockIdx.z; one launch: n <= 65535)
-        const dim3 grid(gx, gy, (unsigned)std::min<size_t>(65535, (size_t)n - first)), block(leon::kRgbaBlock);
-        hipLaunchKernelGGL(kr, grid, block, 0, st, (const uint8_t*)p->d_planes, out, d_descs + first, (const uint32_t*)p->d_tensor_table,
-                           (const leon::Tables*)p->dec->d_tables, reinterpret_cast<const int32_t*>(p->regions_dev + desc_bytes), G);
+        const dim3 grid(gx, fit.letterbox ? gy_fit : gy, (unsigned)std::min<size_t>(65535, (size_t)n - first)), block(leon::kRgbaBlock);
+        if (fit.letterbox)
+            hipLaunchKernelGGL(kf, grid, block, 0, st, (const uint8_t*)p->d_planes, out, d_descs + first, (const uint32_t*)p->d_tensor_table,
+                               (const leon::Tables*)p->dec->d_tables, reinterpret_cast<const int32_t*>(p->regions_dev + desc_bytes), G, fit.pad);
+        else
+            hipLaunchKernelGGL(kr, grid, block, 0, st, (const uint8_t*)p->d_planes, out, d_descs + first, (const uint32_t*)p->d_tensor_table,
+                               (const leon::Tables*)p->dec->d_tables, reinterpret_cast<const int32_t*>(p->regions_dev + desc_bytes), G);
     }
     HIP_TRY(hipGetLastError());
     if (host) HIP_TRY(hipMemcpy2DAsync(host, region_bytes, out, pitch, region_bytes, (size_t)n, hipMemcpyDeviceToHost, st));
@@ -1541,12 +1605,13 @@ size_t boxes_slot_words(int32_t ow, int32_t oh, int32_t filter)
 }
 
 // The CPU twin of k_box_tables' judgement: the same functions of leon_resize_row.h in the same order
-int32_t region_status(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_region& r, const leon_pipeline_regions_config& cfg)
+int32_t region_status(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_region& r, const leon_pipeline_regions_config& cfg, const RegionsFit& fit)
 {
     if (r.reserved[0] | r.reserved[1] | r.reserved[2]) return LEON_REGION_RESERVED;
     if (r.frame < 0 || r.frame >= n_frames) return LEON_REGION_FRAME;
     const bool cubic = cfg.filter == LEON_RESIZE_BICUBIC;
-    const int32_t in[2] = {fw, fh}, start[2] = {r.x, r.y}, size[2] = {r.width, r.height}, out[2] = {cfg.out_width, cfg.out_height};
+    const leon::FitRect image = region_image(r, cfg, fit);
+    const int32_t in[2] = {fw, fh}, start[2] = {r.x, r.y}, size[2] = {r.width, r.height}, out[2] = {image.ow, image.oh};
     const int32_t ratio[2] = {LEON_REGION_RATIO_X, LEON_REGION_RATIO_Y};
     for (int a = 0; a < 2; a++) {
         const int32_t s = leon::region_axis_status(in[a], start[a], size[a], out[a], ratio[a]);
@@ -1574,10 +1639,16 @@ int boxes_reserve(leon_pipeline* p, size_t bytes)
 
 // One call: the host's refusals, the window's frame ids uploaded, then per chunk k_box_tables and k_boxes on the caller's stream (or the
 // pipeline's regions stream and a wait).  regions_mu is held while enqueuing only.
-int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_device* c)
+int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit_settings,
+                            const leon_pipeline_regions_device* c, int32_t* device_rects)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
     if (!cfg || !c) return fail(LEON_ERR_INVALID, "null argument");
+    RegionsFit fit;
+    const int frc = regions_fit_check(fit_settings, &fit);
+    if (frc != LEON_OK) return frc;
+    if (device_rects && !fit.letterbox) return fail(LEON_ERR_INVALID, "regions: device_rects without LEON_REGIONS_FIT_LETTERBOX (every region's rectangle is its tensor)");
+    if ((uintptr_t)device_rects & 3u) return fail(LEON_ERR_INVALID, "regions: device_rects %p is not 4-byte aligned", (void*)device_rects);
     if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR) || !p->d_tensor || !p->d_planes)
         return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
     std::unique_lock<std::mutex> call(p->regions_mu);
@@ -1600,7 +1671,8 @@ int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipelin
     const int eb = (int)p->tensor_elem, layout = p->tensor_layout;
     const bool listed = (eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc);
     const RegionsKernel kb = listed ? kBoxesKernels[filter].k[eb >> 1][layout] : nullptr;
-    if (!kb) return fail(LEON_ERR_INVALID, "regions: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
+    const FittedKernel kf = listed ? kFittedKernels[filter].k[eb >> 1][layout] : nullptr;
+    if (!kb || !kf) return fail(LEON_ERR_INVALID, "regions: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
     // as many regions a chunk as fit the limit (and 32 bits of table words, which rt_base counts)
     const size_t slot_words = boxes_slot_words(ow, oh, filter), per_region = slot_words * 4 + sizeof(leon::RegionDesc);
     const uint64_t limit = c->scratch_limit_bytes ? c->scratch_limit_bytes : LEON_REGIONS_SCRATCH_DEFAULT;
@@ -1644,14 +1716,22 @@ int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipelin
     B.slot_words = (uint32_t)slot_words;
     B.pitch_lo = (uint32_t)(pitch & 0xffffffffu); B.pitch_hi = (uint32_t)(pitch >> 32);
     const unsigned gx = (unsigned)((ow + leon::kResTileX - 1) / leon::kResTileX), gy = (unsigned)((oh + leon::kResTileY - 1) / leon::kResTileY);
+    const unsigned gy_fit = gy + fitted_pad_rows(region_bytes, gx);          // (at most 512 tile rows and 96 pad rows: inside 65535)
     const leon::BoxRecord* boxes = reinterpret_cast<const leon::BoxRecord*>(c->regions);
     for (size_t first = 0; he == hipSuccess && first < (size_t)n; first += chunk) {
         const unsigned m = (unsigned)std::min(chunk, (size_t)n - first);          // (blockIdx.z of k_boxes: m <= n <= 65535)
         B.first = (uint32_t)first;
-        hipLaunchKernelGGL(leon::k_box_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, (const uint32_t*)d_ids, d_descs, d_tabs,
-                           c->device_status ? c->device_status + first : nullptr, B);
-        hipLaunchKernelGGL(kb, dim3(gx, gy, m), dim3(leon::kRgbaBlock), 0, st, (const uint8_t*)p->d_planes, static_cast<uint8_t*>(c->device_out), (const leon::RegionDesc*)d_descs,
-                           (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)d_tabs, G);
+        int32_t* status = c->device_status ? c->device_status + first : nullptr;
+        if (fit.letterbox) {
+            hipLaunchKernelGGL(leon::k_fit_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, (const uint32_t*)d_ids, d_descs, d_tabs, status,
+                               device_rects ? device_rects + first * 4 : nullptr, fit.top_left ? 1 : 0, B);
+            hipLaunchKernelGGL(kf, dim3(gx, gy_fit, m), dim3(leon::kRgbaBlock), 0, st, (const uint8_t*)p->d_planes, static_cast<uint8_t*>(c->device_out), (const leon::RegionDesc*)d_descs,
+                               (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)d_tabs, G, fit.pad);
+        } else {
+            hipLaunchKernelGGL(leon::k_box_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, (const uint32_t*)d_ids, d_descs, d_tabs, status, B);
+            hipLaunchKernelGGL(kb, dim3(gx, gy, m), dim3(leon::kRgbaBlock), 0, st, (const uint8_t*)p->d_planes, static_cast<uint8_t*>(c->device_out), (const leon::RegionDesc*)d_descs,
+                               (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)d_tabs, G);
+        }
         he = hipGetLastError();
     }
     if (hipEventRecord(p->boxes_done, st) == hipSuccess) p->boxes_busy = true;
@@ -2376,13 +2456,10 @@ int leon_pipeline_letterbox(int32_t src_width, int32_t src_height, int32_t canva
     if (!resize || !canvas) return fail(LEON_ERR_INVALID, "null argument");
     if (src_width < 1 || src_height < 1) return fail(LEON_ERR_INVALID, "letterbox: source %d x %d", src_width, src_height);
     if (canvas_width < 1 || canvas_height < 1) return fail(LEON_ERR_INVALID, "letterbox: canvas %d x %d", canvas_width, canvas_height);
-    const int64_t sw = src_width, sh = src_height, cw = canvas_width, ch = canvas_height;
-    int64_t ow, oh;
-    if (cw * sh <= ch * sw) { ow = cw; oh = std::max<int64_t>(1, (2 * sh * cw + sw) / (2 * sw)); }
-    else { oh = ch; ow = std::max<int64_t>(1, (2 * sw * ch + sh) / (2 * sh)); }
-    resize->out_width = (int32_t)ow; resize->out_height = (int32_t)oh;
+    const leon::FitRect r = leon::letterbox_rect(src_width, src_height, canvas_width, canvas_height);          // (leon_resize_row.h: the device's text too)
+    resize->out_width = r.ow; resize->out_height = r.oh;
     canvas->width = canvas_width; canvas->height = canvas_height;
-    canvas->x = (int32_t)((cw - ow) / 2); canvas->y = (int32_t)((ch - oh) / 2);
+    canvas->x = r.x; canvas->y = r.y;
     return LEON_OK;
 }
 
@@ -2558,25 +2635,25 @@ int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, v
 int leon_pipeline_regions_check(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* regions, int32_t n,
                                 const leon_pipeline_regions_config* cfg, int32_t* bad)
 {
-    return regions_check(frame_width, frame_height, n_frames, regions, n, cfg, bad, nullptr);
+    return regions_check(frame_width, frame_height, n_frames, regions, n, cfg, RegionsFit{}, bad, nullptr);
 }
 
 int leon_pipeline_resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n,
                                    const leon_pipeline_regions_config* cfg, void* device_out, uint64_t out_pitch_bytes)
 {
-    return resample_regions(p, window, regions, n, cfg, device_out, out_pitch_bytes, nullptr);
+    return resample_regions(p, window, regions, n, cfg, nullptr, device_out, out_pitch_bytes, nullptr);
 }
 
 int leon_pipeline_read_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n,
                                const leon_pipeline_regions_config* cfg, void* host)
 {
     if (!host) return fail(LEON_ERR_INVALID, "null argument");
-    return resample_regions(p, window, regions, n, cfg, nullptr, 0, host);
+    return resample_regions(p, window, regions, n, cfg, nullptr, nullptr, 0, host);
 }
 
 int leon_pipeline_resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_device* call)
 {
-    return resample_regions_device(p, window, cfg, call);
+    return resample_regions_device(p, window, cfg, nullptr, call, nullptr);
 }
 
 int32_t leon_pipeline_region_status(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* region,
@@ -2584,7 +2661,60 @@ int32_t leon_pipeline_region_status(int32_t frame_width, int32_t frame_height, i
 {
     if (!region || !cfg) return fail(LEON_ERR_INVALID, "null argument");
     const int rc = regions_config_check(frame_width, frame_height, n_frames, 1, cfg);
-    return rc != LEON_OK ? rc : region_status(frame_width, frame_height, n_frames, *region, *cfg);
+    return rc != LEON_OK ? rc : region_status(frame_width, frame_height, n_frames, *region, *cfg, RegionsFit{});
+}
+
+int leon_pipeline_region_fit_rect(int32_t box_width, int32_t box_height, const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit_settings,
+                                  int32_t rect[4])
+{
+    if (!cfg || !rect) return fail(LEON_ERR_INVALID, "null argument");
+    int rc = regions_config_check(1, 1, 0, 1, cfg);
+    RegionsFit fit;
+    if (rc != LEON_OK || (rc = regions_fit_check(fit_settings, &fit)) != LEON_OK) return rc;
+    if (box_width < 1 || box_height < 1) return fail(LEON_ERR_INVALID, "regions fit: a box of %d x %d", box_width, box_height);
+    leon_pipeline_region r{};
+    r.width = box_width; r.height = box_height;
+    const leon::FitRect image = region_image(r, *cfg, fit);
+    rect[0] = image.x; rect[1] = image.y; rect[2] = image.ow; rect[3] = image.oh;
+    return LEON_OK;
+}
+
+int leon_pipeline_regions_fit_check(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* regions, int32_t n,
+                                    const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit_settings, int32_t* bad)
+{
+    if (bad) *bad = -1;
+    RegionsFit fit;
+    const int rc = regions_fit_check(fit_settings, &fit);
+    return rc != LEON_OK ? rc : regions_check(frame_width, frame_height, n_frames, regions, n, cfg, fit, bad, nullptr);
+}
+
+int32_t leon_pipeline_region_fit_status(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* region,
+                                        const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit_settings)
+{
+    if (!region || !cfg) return fail(LEON_ERR_INVALID, "null argument");
+    RegionsFit fit;
+    int rc = regions_config_check(frame_width, frame_height, n_frames, 1, cfg);
+    if (rc == LEON_OK) rc = regions_fit_check(fit_settings, &fit);
+    return rc != LEON_OK ? rc : region_status(frame_width, frame_height, n_frames, *region, *cfg, fit);
+}
+
+int leon_pipeline_resample_regions_fit(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
+                                       const leon_pipeline_regions_fit* fit, void* device_out, uint64_t out_pitch_bytes)
+{
+    return resample_regions(p, window, regions, n, cfg, fit, device_out, out_pitch_bytes, nullptr);
+}
+
+int leon_pipeline_read_regions_fit(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
+                                   const leon_pipeline_regions_fit* fit, void* host)
+{
+    if (!host) return fail(LEON_ERR_INVALID, "null argument");
+    return resample_regions(p, window, regions, n, cfg, fit, nullptr, 0, host);
+}
+
+int leon_pipeline_resample_regions_device_fit(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit,
+                                              const leon_pipeline_regions_device* call, int32_t* device_rects)
+{
+    return resample_regions_device(p, window, cfg, fit, call, device_rects);
 }
 
 int leon_pipeline_resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,

@@ -115,5 +115,38 @@ LEON_HD inline int32_t region_axis_status(int32_t in_size, int32_t start, int32_
 // a row's tap count as resize_axis_build judges it
 LEON_HD inline bool resize_row_count_ok(int32_t n, bool cubic) { return n >= 1 && n <= (cubic ? kResizeMaxTapsCubic : kResizeMaxTapsTriangle); }
 
+// ---- the letterbox integers (leon_pipeline_letterbox of include/leon_pipeline.h) --------------------------------------------------
+// A source of sw x sh scaled to fit cw x ch with its aspect ratio kept, and centred: 64-bit integers only.  One text for the host
+// (leon_pipeline_letterbox, the fit of leon_pipeline_resample_regions_fit) and the device (k_fit_tables), so that a region's image
+// rectangle is the same four words wherever it is worked out.  All four sizes are >= 1: the caller has judged them.
+struct FitRect {
+    int32_t ow, oh, x, y;
+};
+LEON_HD inline FitRect letterbox_rect(int32_t src_w, int32_t src_h, int32_t canvas_w, int32_t canvas_h)
+{
+    const int64_t sw = src_w, sh = src_h, cw = canvas_w, ch = canvas_h;
+    int64_t ow, oh;
+    if (cw * sh <= ch * sw) {
+        ow = cw;
+        oh = (2 * sh * cw + sw) / (2 * sw);
+        if (oh < 1) oh = 1;
+    } else {
+        oh = ch;
+        ow = (2 * sw * ch + sh) / (2 * sh);
+        if (ow < 1) ow = 1;
+    }
+    return FitRect{(int32_t)ow, (int32_t)oh, (int32_t)((cw - ow) / 2), (int32_t)((ch - oh) / 2)};
+}
+// The image rectangle of one region of a letterboxed call (leon_pipeline_regions_fit): the letterbox of the box in the canvas, at
+// (0, 0) with the top-left anchor.  A box without a size has no letterbox: it gets the canvas itself, and region_axis_status then
+// names the box (kRegionBox) on the axis that has none, in regions_check's order.
+LEON_HD inline FitRect region_fit_rect(int32_t box_w, int32_t box_h, int32_t canvas_w, int32_t canvas_h, bool top_left)
+{
+    if (box_w < 1 || box_h < 1) return FitRect{canvas_w, canvas_h, 0, 0};
+    FitRect r = letterbox_rect(box_w, box_h, canvas_w, canvas_h);
+    if (top_left) r.x = r.y = 0;
+    return r;
+}
+
 }  // namespace leon
 #endif

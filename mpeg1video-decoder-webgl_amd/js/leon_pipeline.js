@@ -47,7 +47,9 @@
  *                                  width, height], ...], boxes of the window's FULL-RESOLUTION frames (a detector's boxes) each resampled to
  *                                  h x w with the pipeline's element type, table and layout (leon_pipeline_read_regions) -- any tensor
  *                                  output, whatever its tensorSize / tensorCanvas; until the window is released; filter 'triangle'
- *                                  (default) or 'bicubic'
+ *                                  (default) or 'bicubic'.  fit: 'letterbox' keeps every box's aspect ratio inside h x w -- centred, or
+ *                                  with anchor: 'top_left' at the top left -- and fills the rest with padValue [r, g, b] through the
+ *                                  element table (leon_pipeline_read_regions_fit); without fit, anchor and padValue the boxes are stretched
  *   p.releaseWindow(window); p.stats(); p.destroy();
  * Open GOPs (closed_gop = 0) need no option: their leading B pictures predict from the GOP before; where that GOP is not decoded (start,
  * seek target, broken_link) they are not delivered and the GOP's frames start at its I picture's displayIndex (include/leon_pipeline.h).
@@ -156,7 +158,22 @@ class LeonPipeline extends EventEmitter {
     if (!Array.isArray(regions) || !regions.every((r) => Array.isArray(r) && r.length === 5 && r.every(Number.isInteger))) {
       throw new TypeError('regions: [[frameIndex, x, y, width, height], ...]');
     }
-    return this._p.readRegions(window, Int32Array.from(regions.flat()), size[0], size[1], filter);
+    const boxes = Int32Array.from(regions.flat());
+    if (opts.fit === undefined && opts.anchor === undefined && opts.padValue === undefined) return this._p.readRegions(window, boxes, size[0], size[1], filter);
+    const fits = { stretch: 0, letterbox: 1 }, anchors = { centre: 0, center: 0, top_left: 1 };
+    let fit = opts.fit === undefined ? 0 : opts.fit, anchor = opts.anchor === undefined ? 0 : opts.anchor;
+    if (typeof fit === 'string') {
+      if (!(fit in fits)) throw new TypeError("fit: 'stretch' or 'letterbox'");
+      fit = fits[fit];
+    }
+    if (typeof anchor === 'string') {
+      if (!(anchor in anchors)) throw new TypeError("anchor: 'centre' or 'top_left'");
+      anchor = anchors[anchor];
+    }
+    const pad = opts.padValue === undefined ? [0, 0, 0] : opts.padValue;
+    if (!Array.isArray(pad) || pad.length !== 3 || !pad.every(Number.isInteger)) throw new TypeError('padValue: [r, g, b]');
+    if (!Number.isInteger(fit) || !Number.isInteger(anchor)) throw new TypeError('fit, anchor: a name or an integer');
+    return this._p.readRegions(window, boxes, size[0], size[1], filter, fit, anchor, pad[0], pad[1], pad[2]);
   }
   releaseWindow(window) { this._p.releaseWindow(window); }
   stats() { return this._p.stats(); }

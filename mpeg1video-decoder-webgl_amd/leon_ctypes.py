@@ -41,6 +41,8 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_create_tensor_canvas", "leon_pipeline_get_tensor_canvas", "leon_pipeline_letterbox",
     "leon_pipeline_regions_check", "leon_pipeline_resample_regions", "leon_pipeline_read_regions",
     "leon_pipeline_resample_regions_device", "leon_pipeline_region_status", "leon_pipeline_resize_weights_device",
+    "leon_pipeline_region_fit_rect", "leon_pipeline_regions_fit_check", "leon_pipeline_region_fit_status",
+    "leon_pipeline_resample_regions_fit", "leon_pipeline_read_regions_fit", "leon_pipeline_resample_regions_device_fit",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -310,6 +312,33 @@ class PipelineRegionsDevice(C.Structure):
                 ("device_status", C.c_void_p), ("stream", C.c_void_p), ("scratch_limit_bytes", C.c_uint64), ("reserved", C.c_uint64 * 1)]
 
 
+class PipelineRegionsFit(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("anchor", C.c_int32), ("pad", C.c_int32 * 3), ("reserved", C.c_int32 * 3)]
+
+
+REGIONS_FIT_STRETCH, REGIONS_FIT_LETTERBOX = 0, 1           # LEON_REGIONS_FIT_*
+REGIONS_ANCHOR_CENTRE, REGIONS_ANCHOR_TOP_LEFT = 0, 1       # LEON_REGIONS_ANCHOR_*
+REGIONS_FITS = {"stretch": REGIONS_FIT_STRETCH, "letterbox": REGIONS_FIT_LETTERBOX}
+REGIONS_ANCHORS = {"centre": REGIONS_ANCHOR_CENTRE, "center": REGIONS_ANCHOR_CENTRE, "top_left": REGIONS_ANCHOR_TOP_LEFT}
+
+
+def _regions_fit(fit, anchor, pad_value):
+    """The PipelineRegionsFit of the fit keywords -- fit None / "stretch" / "letterbox" (or a PipelineRegionsFit), anchor "centre" /
+    "top_left", pad_value (r, g, b) -- or None when none of them is set: the call without a fit.  What the settings may not be is the
+    library's to refuse."""
+    if isinstance(fit, PipelineRegionsFit):
+        return fit
+    if fit is None and anchor is None and pad_value is None:
+        return None
+    f = PipelineRegionsFit()
+    f.mode = REGIONS_FITS[fit] if isinstance(fit, str) else int(fit or 0)
+    f.anchor = REGIONS_ANCHORS[anchor] if isinstance(anchor, str) else int(anchor or 0)
+    if pad_value is not None:
+        r, g, b = pad_value
+        f.pad[0], f.pad[1], f.pad[2] = int(r), int(g), int(b)
+    return f
+
+
 # LEON_REGION_*: the status word of a region whose box lies in device memory (0: resampled; otherwise skipped, and why)
 REGION_OK, REGION_RESERVED, REGION_FRAME, REGION_BOX, REGION_RATIO_X, REGION_RATIO_Y, REGION_TAPS = range(7)
 REGIONS_SCRATCH_DEFAULT = 256 << 20          # LEON_REGIONS_SCRATCH_DEFAULT
@@ -430,6 +459,17 @@ def load():
         lib.leon_pipeline_regions_check.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineRegion), C.c_int32, C.POINTER(PipelineRegionsConfig), C.POINTER(C.c_int32)]
         lib.leon_pipeline_resample_regions.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineRegion), C.c_int32, C.POINTER(PipelineRegionsConfig), C.c_void_p, C.c_uint64]
         lib.leon_pipeline_read_regions.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineRegion), C.c_int32, C.POINTER(PipelineRegionsConfig), C.c_void_p]
+    if hasattr(lib, "leon_pipeline_resample_regions_fit"):
+        P = C.POINTER
+        lib.leon_pipeline_region_fit_rect.argtypes = [C.c_int32, C.c_int32, P(PipelineRegionsConfig), P(PipelineRegionsFit), P(C.c_int32)]
+        lib.leon_pipeline_regions_fit_check.argtypes = [C.c_int32, C.c_int32, C.c_int32, P(PipelineRegion), C.c_int32, P(PipelineRegionsConfig), P(PipelineRegionsFit),
+                                                        P(C.c_int32)]
+        lib.leon_pipeline_region_fit_status.argtypes = [C.c_int32, C.c_int32, C.c_int32, P(PipelineRegion), P(PipelineRegionsConfig), P(PipelineRegionsFit)]
+        lib.leon_pipeline_region_fit_status.restype = C.c_int32
+        lib.leon_pipeline_resample_regions_fit.argtypes = [C.c_void_p, C.c_int64, P(PipelineRegion), C.c_int32, P(PipelineRegionsConfig), P(PipelineRegionsFit), C.c_void_p,
+                                                           C.c_uint64]
+        lib.leon_pipeline_read_regions_fit.argtypes = [C.c_void_p, C.c_int64, P(PipelineRegion), C.c_int32, P(PipelineRegionsConfig), P(PipelineRegionsFit), C.c_void_p]
+        lib.leon_pipeline_resample_regions_device_fit.argtypes = [C.c_void_p, C.c_int64, P(PipelineRegionsConfig), P(PipelineRegionsFit), P(PipelineRegionsDevice), C.c_void_p]
     if hasattr(lib, "leon_pipeline_resample_regions_device"):
         lib.leon_pipeline_resample_regions_device.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineRegionsConfig), C.POINTER(PipelineRegionsDevice)]
         lib.leon_pipeline_region_status.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineRegion), C.POINTER(PipelineRegionsConfig)]
@@ -486,6 +526,40 @@ def region_status(frame_width, frame_height, n_frames, region, size, filter="tri
     No device.  LeonError for a size or filter the library refuses."""
     arr, _, cfg = _regions_args([region], size, filter)
     st = load().leon_pipeline_region_status(int(frame_width), int(frame_height), int(n_frames), arr, C.byref(cfg))
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return st
+
+
+def _fit_ref(f):
+    return C.byref(f) if f is not None else None
+
+
+def region_fit_rect(box_width, box_height, size, fit="letterbox", anchor=None, pad_value=None):
+    """leon_pipeline_region_fit_rect: (x, y, width, height) of the image of a box of box_width x box_height in its tensor of
+    size = (height, width) -- the letterbox integers, at (0, 0) with anchor "top_left"; the tensor itself when stretched.  No device."""
+    cfg = size if isinstance(size, PipelineRegionsConfig) else PipelineRegionsConfig(int(size[1]), int(size[0]), RESIZE_TRIANGLE)
+    rect = (C.c_int32 * 4)()
+    _chk(load().leon_pipeline_region_fit_rect(int(box_width), int(box_height), C.byref(cfg), _fit_ref(_regions_fit(fit, anchor, pad_value)), rect))
+    return tuple(rect)
+
+
+def regions_fit_check(frame_width, frame_height, n_frames, regions, size, filter="triangle", fit="letterbox", anchor=None, pad_value=None):
+    """leon_pipeline_regions_fit_check: regions_check with the fit keywords of Pipeline.resample_regions"""
+    arr, n, cfg = _regions_args(regions, size, filter)
+    bad = C.c_int32(-2)
+    rc = load().leon_pipeline_regions_fit_check(int(frame_width), int(frame_height), int(n_frames), arr, n, C.byref(cfg),
+                                                _fit_ref(_regions_fit(fit, anchor, pad_value)), C.byref(bad))
+    if rc != OK:
+        e = LeonError(rc, load().leon_last_error().decode("utf-8", "replace"))
+        e.bad = bad.value
+        raise e
+
+
+def region_fit_status(frame_width, frame_height, n_frames, region, size, filter="triangle", fit="letterbox", anchor=None, pad_value=None):
+    """leon_pipeline_region_fit_status: region_status with the fit keywords of Pipeline.resample_regions_device"""
+    arr, _, cfg = _regions_args([region], size, filter)
+    st = load().leon_pipeline_region_fit_status(int(frame_width), int(frame_height), int(n_frames), arr, C.byref(cfg), _fit_ref(_regions_fit(fit, anchor, pad_value)))
     if st < 0:
         raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
     return st
@@ -972,13 +1046,16 @@ class Pipeline:
             return (h, w, 3), (3 * w * e, 3 * e, e)
         return (3, h, w), (h * w * e, w * e, e)
 
-    def resample_regions(self, window, regions, size, filter="triangle", out=None, pitch=None, device_id=None):
+    def resample_regions(self, window, regions, size, filter="triangle", out=None, pitch=None, device_id=None, fit=None, anchor=None, pad_value=None):
         """leon_pipeline_resample_regions: regions = [(frame_index, x, y, w, h), ...] of the delivered, not yet released `window`
         (frame["_i"] is the index) resampled to size = (h, w) -> a torch view [N, 3, h, w] ("hwc": [N, h, w, 3]) of the pipeline's
         element type, regions `pitch` bytes apart (None: the region's bytes rounded up to 256 -- dense when they are a multiple of
         256, as 224 x 224 is in every element type).  The view lies over a uint8 buffer the method allocates, or over `out`: a torch
         uint8 tensor on the device, 256-byte aligned, of at least (N - 1) * pitch + the region's bytes.  Synchronous: the batch is
-        complete when the method returns.  Raises LeonError where the library refuses; nothing is written then."""
+        complete when the method returns.  Raises LeonError where the library refuses; nothing is written then.
+        fit="letterbox": every box keeps its aspect ratio inside the (h, w) tensor -- centred, or at the top left with
+        anchor="top_left" -- and the rest is pad_value = (r, g, b) through the element table (leon_pipeline_regions_fit;
+        region_fit_rect says where the image lies).  Without the three keywords the call is the one it always was."""
         import torch
         if not self.info.tensor_dtype:
             raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
@@ -992,11 +1069,16 @@ class Pipeline:
             raise ValueError("out: a contiguous uint8 tensor of at least %d bytes" % ((n - 1) * step + nbytes))
         # the library writes on a stream of its own: what torch has queued for this memory (a fill, an earlier owner's kernels) goes first
         torch.cuda.current_stream(dev).synchronize()
-        _chk(self.lib.leon_pipeline_resample_regions(self.h, int(window), arr, n, C.byref(cfg), out.data_ptr(), 0 if pitch is None else step))
+        f = _regions_fit(fit, anchor, pad_value)
+        if f is None:
+            _chk(self.lib.leon_pipeline_resample_regions(self.h, int(window), arr, n, C.byref(cfg), out.data_ptr(), 0 if pitch is None else step))
+        else:
+            _chk(self.lib.leon_pipeline_resample_regions_fit(self.h, int(window), arr, n, C.byref(cfg), C.byref(f), out.data_ptr(), 0 if pitch is None else step))
         shape, strides = self._region_dims(size)
         return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out)
 
-    def resample_regions_device(self, window, boxes, size, filter="triangle", out=None, pitch=None, status=None, stream=None, scratch_limit=None):
+    def resample_regions_device(self, window, boxes, size, filter="triangle", out=None, pitch=None, status=None, stream=None, scratch_limit=None,
+                                fit=None, anchor=None, pad_value=None, rects=None):
         """leon_pipeline_resample_regions_device: the same batch from boxes that lie in DEVICE memory -- a CUDA int32 torch tensor,
         [N, 8] contiguous (leon_pipeline_region records) or [N, 5] (frame_index, x, y, w, h; padded to records on the device) -- queued on
         `stream` (a torch.cuda.Stream; None: torch's current stream of the pipeline's device, where boxes, out and status must lie) behind whatever made the boxes there and in front of
@@ -1005,14 +1087,21 @@ class Pipeline:
         one the method allocates), REGION_* per box -- 0: resampled; otherwise the region was skipped and its bytes of `out` are
         untouched (the method's own buffer is not initialised).  The window must stay unreleased and the pipeline open until the
         stream has run the work.  scratch_limit: bytes of table scratch a chunk of regions may take (None: 256 MiB).  torch's legacy
-        default stream has no handle the library could queue on: there the method waits for the stream, and the call for its work."""
+        default stream has no handle the library could queue on: there the method waits for the stream, and the call for its work.
+        fit / anchor / pad_value: as resample_regions; a box that is refused letterboxed has nothing written, pad included.  rects
+        (letterbox only): an int32 tensor of at least [N, 4] words on the device, or True for one the method allocates -- the call
+        then returns (batch, status, rects), rects[i] = (x, y, width, height) of region i's image for every status-0 region, the
+        others' words untouched."""
         import torch
         if not self.info.tensor_dtype:
             raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
         dev = self.device_id
         if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda and boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] in (5, 8)):
             raise ValueError("boxes: a CUDA int32 tensor [N, 8] (records) or [N, 5] (frame, x, y, w, h)")
-        for name, t in (("boxes", boxes), ("out", out), ("status", status)):
+        want_rects = rects is not None and rects is not False
+        if rects is True:
+            rects = None
+        for name, t in (("boxes", boxes), ("out", out), ("status", status), ("rects", rects)):
             if t is not None and (not t.is_cuda or t.device.index != dev):
                 raise ValueError("%s: on %s, the pipeline's device is cuda:%d" % (name, t.device, dev))
         stream = torch.cuda.current_stream(dev) if stream is None else stream
@@ -1033,23 +1122,36 @@ class Pipeline:
                 status = torch.empty(max(1, n), dtype=torch.int32, device="cuda:%d" % dev)
             elif status.dtype != torch.int32 or not status.is_contiguous() or status.numel() < n:
                 raise ValueError("status: a contiguous int32 tensor of at least %d words" % n)
+            if want_rects and rects is None:
+                rects = torch.empty((max(1, n), 4), dtype=torch.int32, device="cuda:%d" % dev)
+            elif want_rects and (rects.dtype != torch.int32 or not rects.is_contiguous() or rects.numel() < 4 * n):
+                raise ValueError("rects: a contiguous int32 tensor of at least %d words" % (4 * n))
         handle = int(stream.cuda_stream)
         if not handle:
             stream.synchronize()
         call = PipelineRegionsDevice(boxes.data_ptr() if n else None, n, 0, out.data_ptr(), 0 if pitch is None else step, status.data_ptr(), handle or None,
                                      0 if scratch_limit is None else int(scratch_limit))
-        _chk(self.lib.leon_pipeline_resample_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        f = _regions_fit(fit, anchor, pad_value)
+        if f is None and not want_rects:
+            _chk(self.lib.leon_pipeline_resample_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        else:
+            _chk(self.lib.leon_pipeline_resample_regions_device_fit(self.h, int(window), C.byref(cfg), _fit_ref(f), C.byref(call), rects.data_ptr() if want_rects else None))
         shape, strides = self._region_dims((cfg.out_height, cfg.out_width))
-        return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out), status[:n]
+        batch = self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out)
+        return (batch, status[:n], rects.view(-1)[:4 * n].view(n, 4)) if want_rects else (batch, status[:n])
 
-    def read_regions(self, window, regions, size, filter="triangle"):
+    def read_regions(self, window, regions, size, filter="triangle", fit=None, anchor=None, pad_value=None):
         """leon_pipeline_read_regions: the same regions as a host array [N, 3, h, w] ("hwc": [N, h, w, 3]), packed: float16 / float32 /
-        uint8, bfloat16 as uint16 bit patterns like read_tensor"""
+        uint8, bfloat16 as uint16 bit patterns like read_tensor; fit, anchor, pad_value as resample_regions"""
         if not self.info.tensor_dtype:
             raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
         arr, n, cfg = _regions_args(regions, size, filter)
         out = np.empty((max(1, n),) + self._region_dims(size)[0], dtype=self._tensor_np_dtype())
-        _chk(self.lib.leon_pipeline_read_regions(self.h, int(window), arr, n, C.byref(cfg), out.ctypes.data))
+        f = _regions_fit(fit, anchor, pad_value)
+        if f is None:
+            _chk(self.lib.leon_pipeline_read_regions(self.h, int(window), arr, n, C.byref(cfg), out.ctypes.data))
+        else:
+            _chk(self.lib.leon_pipeline_read_regions_fit(self.h, int(window), arr, n, C.byref(cfg), C.byref(f), out.ctypes.data))
         return out[:n]
 
     def _tensor_at(self, ptr, shape, strides, device_id=None, owner=None):

@@ -595,11 +595,12 @@ napi_value PipeReadTensor(napi_env env, napi_callback_info info)
 }
 
 // p.readRegions(window, boxes, outHeight, outWidth, filter) -> Buffer of n * region bytes (3 * outHeight * outWidth elements of the
-// pipeline's element type and layout each, packed): leon_pipeline_read_regions.  boxes: an Int32Array of n x [frame index, x, y, width, height]
+// pipeline's element type and layout each, packed): leon_pipeline_read_regions.  boxes: an Int32Array of n x [frame index, x, y, width, height].
+// Five numbers more -- fit mode, anchor, pad r, g, b (leon_pipeline_regions_fit) -- make it leon_pipeline_read_regions_fit.
 napi_value PipeReadRegions(napi_env env, napi_callback_info info)
 {
-    size_t argc = 5;
-    napi_value argv[5];
+    size_t argc = 10;
+    napi_value argv[10];
     PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
     if (!h) return nullptr;
     int64_t w = -1;
@@ -613,6 +614,14 @@ napi_value PipeReadRegions(napi_env env, napi_callback_info info)
         napi_get_typedarray_info(env, argv[1], &tt, &len, &boxes, &ab, &off) != napi_ok || tt != napi_int32_array || len % 5 != 0 ||
         napi_get_value_int32(env, argv[2], &oh) != napi_ok || napi_get_value_int32(env, argv[3], &ow) != napi_ok || napi_get_value_int32(env, argv[4], &filter) != napi_ok) {
         napi_throw_type_error(env, nullptr, "readRegions(window, Int32Array of [frame, x, y, width, height] per region, outHeight, outWidth, filter)");
+        return nullptr;
+    }
+    const bool fitted = argc > 5;
+    leon_pipeline_regions_fit fit{};
+    if (fitted && (argc < 10 || napi_get_value_int32(env, argv[5], &fit.mode) != napi_ok || napi_get_value_int32(env, argv[6], &fit.anchor) != napi_ok ||
+                   napi_get_value_int32(env, argv[7], &fit.pad[0]) != napi_ok || napi_get_value_int32(env, argv[8], &fit.pad[1]) != napi_ok ||
+                   napi_get_value_int32(env, argv[9], &fit.pad[2]) != napi_ok)) {
+        napi_throw_type_error(env, nullptr, "readRegions(..., filter, fitMode, anchor, padR, padG, padB)");
         return nullptr;
     }
     if (!h->info.tensor_dtype) {
@@ -630,7 +639,8 @@ napi_value PipeReadRegions(napi_env env, napi_callback_info info)
     napi_value buf;
     void* data = nullptr;
     NAPI_OK(napi_create_buffer(env, bytes ? bytes : 1, &data, &buf));
-    int rc = leon_pipeline_read_regions(h->p, w, regions.data(), (int32_t)std::min<size_t>(n, 65536), &cfg, data);
+    const int32_t count = (int32_t)std::min<size_t>(n, 65536);
+    int rc = fitted ? leon_pipeline_read_regions_fit(h->p, w, regions.data(), count, &cfg, &fit, data) : leon_pipeline_read_regions(h->p, w, regions.data(), count, &cfg, data);
     return rc == LEON_OK ? buf : throw_leon(env, rc);
 }
 

@@ -47,6 +47,8 @@ def main():
                     help="with a tensor output: after each window is delivered and before it is released, N seeded random boxes per frame (ratio <= 16) of the "
                          "full-resolution frames resampled to H x W in one call (leon_pipeline_resample_regions); reports regions/s and the mean time per call")
     ap.add_argument("--regions-filter", choices=["triangle", "bicubic"], default="triangle", help="the filter of --regions")
+    ap.add_argument("--regions-fit", choices=["stretch", "letterbox"], default="stretch",
+                    help="with --regions: letterbox keeps every box's aspect ratio inside H x W, centred, the rest grey (leon_pipeline_regions_fit)")
     ap.add_argument("--device-boxes", action="store_true",
                     help="with --regions: the boxes are uploaded as a CUDA tensor and the call is leon_pipeline_resample_regions_device, enqueued on a torch side "
                          "stream (tables built on the device); the callback waits for that stream before it returns, since the window is released then")
@@ -57,6 +59,9 @@ def main():
     a = ap.parse_args()
     if a.device_boxes and not a.regions:
         ap.error("--device-boxes goes with --regions")
+    if a.regions_fit != "stretch" and not a.regions:
+        ap.error("--regions-fit goes with --regions")
+    regions_fit = dict(fit="letterbox", pad_value=(114, 114, 114)) if a.regions_fit == "letterbox" else {}
     if a.open_gops and not a.varied:
         ap.error("--open-gops goes with --varied")
     cached = os.path.join(ROOT, "tools", "probe", "stream_1080p_%dgop.bin" % a.gops)
@@ -122,10 +127,10 @@ def main():
                 st = regions_stat.setdefault("stream", torch.cuda.Stream())
                 with torch.cuda.stream(st):
                     dev = torch.from_numpy(boxes.astype(np.int32)).to("cuda:0", non_blocking=True)
-                    p.resample_regions_device(window, dev, (rh, rw), a.regions_filter, out=regions_stat["out"], status=regions_stat.get("status"))
+                    p.resample_regions_device(window, dev, (rh, rw), a.regions_filter, out=regions_stat["out"], status=regions_stat.get("status"), **regions_fit)
                 st.synchronize()
             else:
-                p.resample_regions(window, boxes, (rh, rw), a.regions_filter, out=regions_stat["out"])
+                p.resample_regions(window, boxes, (rh, rw), a.regions_filter, out=regions_stat["out"], **regions_fit)
             regions_stat["seconds"] += time.perf_counter() - t
             regions_stat["calls"] += 1
             regions_stat["regions"] += n
@@ -151,7 +156,7 @@ def main():
         "tensor_canvas": [canvas.height, canvas.width] if canvas else None, "tensor_image": [canvas.x, canvas.y, canvas.image_width, canvas.image_height] if canvas else None,
         "tensor_pad_value": list(canvas.pad) if canvas else None, "host_resize": a.host_resize, "windows_in_flight": a.inflight,
         "value": s["pictures"] / s["seconds"], "macroblocks_per_s": s["pictures"] * mbs / s["seconds"],
-        "regions": a.regions, "device_boxes": bool(a.regions and a.device_boxes), "regions_filter": a.regions_filter if a.regions else None, "regions_calls": regions_stat["calls"] if a.regions else None,
+        "regions": a.regions, "device_boxes": bool(a.regions and a.device_boxes), "regions_filter": a.regions_filter if a.regions else None, "regions_fit": a.regions_fit if a.regions else None, "regions_calls": regions_stat["calls"] if a.regions else None,
         "regions_per_s": regions_stat["regions"] / s["seconds"] if a.regions else None,
         "regions_ms_per_call": 1e3 * regions_stat["seconds"] / regions_stat["calls"] if regions_stat["calls"] else None,
         "regions_per_call": regions_stat["regions"] / regions_stat["calls"] if regions_stat["calls"] else None,

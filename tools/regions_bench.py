@@ -7,9 +7,12 @@ boxes' Y, Cb and Cr samples) and writes, and the copy rate of the same process. 
 `rocprofv3 --kernel-trace --stats -- python tools/regions_bench.py ...` (k_regions, and k_resample of the pipeline's own --tensor-size
 tensors for comparison: one launch per window of --window GOPs).  --device-boxes times the same boxes through
 leon_pipeline_resample_regions_device too (k_box_tables + k_boxes per chunk; enqueue -> stream synchronisation) and checks that both
-paths wrote the same bytes.
+paths wrote the same bytes.  --fit letterbox times the SAME seeded boxes letterboxed into --size as well (leon_pipeline_regions_fit:
+k_fitted, and k_fit_tables on the device path), in the same process, a stretched and a letterboxed call alternating; the boxes whose
+height the frame clips are the ones that get pad.  With --device-boxes it also checks that both paths wrote the same letterboxed bytes.
 
-  python tools/regions_bench.py [--regions 4096] [--size 224 224] [--calls 5] [--window 128] [--filter triangle] [--device-boxes]"""
+  python tools/regions_bench.py [--regions 4096] [--size 224 224] [--calls 5] [--window 128] [--filter triangle] [--device-boxes]
+                                [--fit letterbox [--anchor centre|top_left] [--pad-value R G B]]"""
 import argparse
 import json
 import os
@@ -35,7 +38,11 @@ def main():
     ap.add_argument("--device-boxes", action="store_true",
                     help="also time leon_pipeline_resample_regions_device: the same boxes uploaded once as a CUDA tensor, the call enqueued on a torch side "
                          "stream; its time runs from the enqueue to that stream's synchronisation")
+    ap.add_argument("--fit", choices=["stretch", "letterbox"], default="stretch", help="letterbox: the same boxes letterboxed too, alternating with the stretched calls")
+    ap.add_argument("--anchor", choices=["centre", "top_left"], default="centre")
+    ap.add_argument("--pad-value", type=int, nargs=3, default=[114, 114, 114], metavar=("R", "G", "B"))
     a = ap.parse_args()
+    fit = dict(fit="letterbox", anchor=a.anchor, pad_value=tuple(a.pad_value)) if a.fit == "letterbox" else None
     import numpy as np
     import torch
     import leon_ctypes as L
@@ -66,12 +73,20 @@ def main():
         L.regions_check(fw, fh, n_frames, boxes, (oh, ow), a.filter)
         check_ms = 1e3 * (time.perf_counter() - t)
         p.resample_regions(window, boxes, (oh, ow), a.filter, out=buf)          # scratch reaches its high-water mark
-        times = []
+        fbuf = torch.empty_like(buf) if fit else None
+        if fit:
+            p.resample_regions(window, boxes, (oh, ow), a.filter, out=fbuf, **fit)
+        times, fit_times = [], []
         for _ in range(a.calls):
             t = time.perf_counter()
             p.resample_regions(window, boxes, (oh, ow), a.filter, out=buf)
             times.append(1e3 * (time.perf_counter() - t))
+            if fit:
+                t = time.perf_counter()
+                p.resample_regions(window, boxes, (oh, ow), a.filter, out=fbuf, **fit)
+                fit_times.append(1e3 * (time.perf_counter() - t))
         dev_times, dev_enqueue, same = None, None, None
+        fit_dev_times, fit_same, padded = None, None, None
         if a.device_boxes:
             st = torch.cuda.Stream()
             with torch.cuda.stream(st):
@@ -81,18 +96,31 @@ def main():
                 p.resample_regions_device(window, dev_boxes, (oh, ow), a.filter, out=buf2, status=status)          # scratch reaches its high-water mark
             st.synchronize()
             same = bool(torch.equal(buf, buf2)) and not bool(status.any())
-            dev_times, dev_enqueue = [], []
+            if fit:
+                with torch.cuda.stream(st):
+                    fbuf2 = torch.empty_like(buf)
+                    _, fstatus, rects = p.resample_regions_device(window, dev_boxes, (oh, ow), a.filter, out=fbuf2, rects=True, **fit)
+                st.synchronize()
+                fit_same = bool(torch.equal(fbuf, fbuf2)) and not bool(fstatus.any())
+                padded = int(((rects[:, 2] < ow) | (rects[:, 3] < oh)).sum())
+            dev_times, dev_enqueue, fit_dev_times = [], [], []
             for _ in range(a.calls):
                 t = time.perf_counter()
                 p.resample_regions_device(window, dev_boxes, (oh, ow), a.filter, out=buf2, status=status, stream=st)
                 dev_enqueue.append(1e3 * (time.perf_counter() - t))
                 st.synchronize()
                 dev_times.append(1e3 * (time.perf_counter() - t))
+                if fit:
+                    t = time.perf_counter()
+                    p.resample_regions_device(window, dev_boxes, (oh, ow), a.filter, out=fbuf2, status=status, stream=st, **fit)
+                    st.synchronize()
+                    fit_dev_times.append(1e3 * (time.perf_counter() - t))
         requested = int((w * h).sum() * 3 // 2)
         with lock:
             out.update(frames=n_frames, call_ms=times, regions_check_ms=check_ms, requested_bytes=requested, written_bytes=a.regions * nbytes,
                        mean_ratio_x=float((w / ow).mean()), mean_ratio_y=float((h / oh).mean()), device_call_ms=dev_times, device_enqueue_ms=dev_enqueue,
-                       device_equals_host=same)
+                       device_equals_host=same, fit=a.fit, fit_call_ms=fit_times or None, fit_device_call_ms=fit_dev_times or None,
+                       fit_device_equals_host=fit_same, fit_regions_with_pad=padded)
     pipe = L.Pipeline(data, parser_threads=16, gops_per_window=a.window, windows_in_flight=2, loop=a.window * a.windows // 2, gpu_parser=True, output="tensor",
                       tensor_dtype=a.tensor_dtype, tensor_layout=a.tensor_layout, tensor_size=(oh, ow), tensor_filter=a.filter, on_window=on_window)
     try:
@@ -105,6 +133,8 @@ def main():
     print(json.dumps(dict(out, metric="leon_pipeline_resample_regions: %d regions of a window of %d 1080p frames -> %d x %d %s %s, %s" % (
         a.regions, out["frames"], oh, ow, a.tensor_dtype, a.tensor_layout, a.filter), regions=a.regions, call_ms_mean=mean, regions_per_s=a.regions / (mean * 1e-3),
         device_call_ms_mean=sum(out["device_call_ms"]) / len(out["device_call_ms"]) if out["device_call_ms"] else None,
+        fit_call_ms_mean=sum(out["fit_call_ms"]) / len(out["fit_call_ms"]) if out["fit_call_ms"] else None,
+        fit_device_call_ms_mean=sum(out["fit_device_call_ms"]) / len(out["fit_device_call_ms"]) if out["fit_device_call_ms"] else None,
         call_gbps_requested_plus_written=(out["requested_bytes"] + out["written_bytes"]) / (mean * 1e-3) / 1e9, copy_gbps_same_process=copy_gbps,
         windows=pipe.windows, frames_per_window=out["frames"])))
 
