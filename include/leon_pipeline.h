@@ -471,6 +471,8 @@ int leon_pipeline_read_regions(leon_pipeline* p, int64_t window, const leon_pipe
 #define LEON_REGION_RATIO_X  4
 #define LEON_REGION_RATIO_Y  5
 #define LEON_REGION_TAPS     6
+#define LEON_REGION_SCALE    7   /* warp regions only (leon_pipeline_warp_regions below): the matrix reduces by more than 4 */
+#define LEON_REGION_OFFSET   8   /* warp regions only: |tx| or |ty| above 2^29 */
 #define LEON_REGIONS_SCRATCH_DEFAULT ((uint64_t)256 << 20)   /* scratch_limit_bytes = 0 */
 typedef struct leon_pipeline_regions_device {
     const leon_pipeline_region* regions;   /* DEVICE memory, n records, 4-byte aligned */
@@ -545,6 +547,79 @@ int leon_pipeline_read_regions_fit(leon_pipeline* p, int64_t window, const leon_
 int leon_pipeline_resample_regions_device_fit(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg,
                                               const leon_pipeline_regions_fit* fit, const leon_pipeline_regions_device* call,
                                               int32_t* device_rects);
+/* Rotated boxes and affine crops of delivered frames as a tensor batch: what OCR on oriented text lines, face recognition after
+ * landmark alignment, top-down pose on a rotated person box and oriented-object detectors take behind their first stage.  A family of
+ * its own beside the regions calls above, which keep their kernels and their bytes: those resample separably, one table per axis, and
+ * cannot express a rotation.  All arithmetic below is integer, so that every binding and the device agree on every byte.
+ * A warp region is a frame index and six words m = (a00, a01, tx, a10, a11, ty) in Q16: the map
+ *     X = a00 * u + a01 * v + tx,   Y = a10 * u + a11 * v + ty
+ * takes continuous OUTPUT coordinates (u, v) to continuous FRAME coordinates; pixel (ox, oy) has its centre at (ox + 0.5, oy + 0.5) on
+ * both sides.  Supersampling: s2 = max(a00^2 + a10^2, a01^2 + a11^2) in 64 bits; g = 0 if s2 <= (2^16 + 1)^2, 1 if s2 <= (2^17 + 1)^2,
+ * 2 if s2 <= (2^18 + 1)^2, anything above is refused; S = 1 << g, and an output pixel is the mean of S x S bilinear samples, which keeps
+ * a reduction of up to 4 from aliasing (the + 1 is slack for the quantiser: a rotation at exactly scale 1, 2 or 4 gets S = 1, 2, 4).
+ * Sub-sample (i, j), i, j < S, of pixel (ox, oy):
+ *     NX = a00 * (2S * ox + 2i + 1) + a01 * (2S * oy + 2j + 1) + 2S * (tx - 32768)          (int64; NY with a10, a11, ty)
+ *     qx = ((NX >> (g + 1)) + 128) >> 8          (arithmetic shifts),          x0 = qx >> 8, fx = qx & 255          (the same for y)
+ *     acc[c] += (256 - fx)(256 - fy) p(x0, y0) + fx (256 - fy) p(x0 + 1, y0) + (256 - fx) fy p(x0, y0 + 1) + fx fy p(x0 + 1, y0 + 1)
+ * and r[c] = (acc[c] + (1 << (15 + 2g))) >> (16 + 2g): one rounding, acc < 2^28.  p(x, y) is the CPU twin's 8-bit colour of the frame,
+ * the fill row of 255 of an odd height included; for every position outside the frame p(x, y) = pad[c], so a region may lie partly or
+ * wholly outside the frame and is then part or all pad.  The element is T[c][r[c]] with the pipeline's table, element type and layout;
+ * region_bytes, the pitch rules and the alignment rules are resample_regions', word for word, and exactly the region_bytes of each
+ * region are written.  The identity map is the crop byte for byte, rotations by multiples of 90 degrees are its rotations, a = 2 and
+ * a = 4 at integer offsets are the 2 x 2 and 4 x 4 box means (sum + 2) >> 2 and (sum + 8) >> 4; with S = 1 a pixel lies within
+ * 255 * 2 * 2^-9 + 0.5 = 1.5 of the float64 bilinear value at the same Q16 coordinates.
+ * A record is judged in this order (one text for host and device, csrc/leon_warp.h): LEON_REGION_RESERVED (the reserved word),
+ * LEON_REGION_FRAME (the frame index), LEON_REGION_SCALE (s2 above the last threshold), LEON_REGION_OFFSET (|tx| or |ty| above 2^29).
+ * leon_pipeline_warp_regions is synchronous on the pipeline's regions stream and refuses the whole call with LEON_ERR_INVALID, naming
+ * the region, as resample_regions does (nothing launched, nothing written); the refusals of the window, the pipeline, n, device_out
+ * and the pitch are resample_regions'.  leon_pipeline_warp_regions_device takes the records from DEVICE memory and ONLY ENQUEUES on
+ * the caller's stream (stream NULL: the regions stream, and the call waits), with resample_regions_device's ordering rules and its
+ * scratch event; region i gets its status word in device_status[i] when that is given, and a region whose status is not 0 has not one
+ * byte written, pad included.  One launch per call, k_warp<element bytes, layout>: blockIdx.z = the region, x / y = 32 x 8 output
+ * tiles.  There are no tables, hence no pre-pass kernel and no chunking: the kernel judges its own record, and the scratch holds the
+ * window's frame ids (on the host path also the uploaded records). */
+typedef struct leon_pipeline_warp_region {
+    int32_t frame;                 /* index into the window's frames[] as delivered to the callback */
+    int32_t m[6];                  /* a00, a01, tx, a10, a11, ty in Q16: output coordinates -> frame coordinates */
+    int32_t reserved;              /* must be 0 */
+} leon_pipeline_warp_region;       /* 32 bytes */
+typedef struct leon_pipeline_warp_config {
+    int32_t out_width, out_height; /* 1 .. 4096, the same for every region of a call */
+    int32_t pad[3];                /* the 8-bit R, G, B of every position outside the frame, 0 .. 255 */
+    int32_t reserved[3];           /* must be 0 */
+} leon_pipeline_warp_config;       /* 32 bytes */
+typedef struct leon_pipeline_warp_regions_call {
+    const leon_pipeline_warp_region* regions;   /* DEVICE memory, n records, 4-byte aligned */
+    int32_t  n;                            /* 1 .. 65535 */
+    int32_t  reserved0;                    /* must be 0 */
+    void*    device_out;                   /* 256-byte aligned */
+    uint64_t out_pitch_bytes;              /* as resample_regions */
+    int32_t* device_status;                /* DEVICE memory, n words, may be NULL */
+    void*    stream;                       /* hipStream_t of the caller's; NULL: the pipeline's regions stream, and the call waits */
+    uint64_t reserved[2];                  /* must be 0 */
+} leon_pipeline_warp_regions_call;         /* 64 bytes */
+/* host only, no device: what warp_regions would refuse of a window of n_frames frames; *bad (may be NULL) = index of the first
+ * offending region (-1: the config, or n) */
+int leon_pipeline_warp_regions_check(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_warp_region* regions,
+                                     int32_t n, const leon_pipeline_warp_config* cfg, int32_t* bad);
+/* host only: the status word the device writes for this one region (a null argument or a config that check refuses: LEON_ERR_INVALID,
+ * which is negative and no status) */
+int32_t leon_pipeline_warp_region_status(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_warp_region* region,
+                                         const leon_pipeline_warp_config* cfg);
+/* host only: m[k] = floor(A[k] * 65536 + 0.5) for A = (a00, a01, tx, a10, a11, ty); refuses non-finite values and values outside int32 */
+int leon_pipeline_warp_from_matrix(const double A[6], int32_t m[6]);
+/* host only: the box of w x h frame pixels centred at (cx, cy) and rotated by angle_degrees (clockwise on the screen: y points down),
+ * filling out_width x out_height: a00 = w / ow * cos, a01 = -h / oh * sin, a10 = w / ow * sin, a11 = h / oh * cos,
+ * t = centre - A * (ow / 2, oh / 2); quantised as leon_pipeline_warp_from_matrix does */
+int leon_pipeline_warp_from_rotated_box(double cx, double cy, double w, double h, double angle_degrees, int32_t out_width, int32_t out_height,
+                                        int32_t m[6]);
+int leon_pipeline_warp_regions(leon_pipeline* p, int64_t window, const leon_pipeline_warp_region* regions, int32_t n,
+                               const leon_pipeline_warp_config* cfg, void* device_out, uint64_t out_pitch_bytes);
+/* the same into pooled device scratch, then copied to the host packed (n * region_bytes): tests, Node, thumbnails */
+int leon_pipeline_read_warp_regions(leon_pipeline* p, int64_t window, const leon_pipeline_warp_region* regions, int32_t n,
+                                    const leon_pipeline_warp_config* cfg, void* host);
+int leon_pipeline_warp_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_warp_config* cfg,
+                                      const leon_pipeline_warp_regions_call* call);
 /* A diagnostic: the DEVICE's evaluation of the tables of n_axes single axes, copied back, to be compared word for word with
  * leon_pipeline_resize_weights (pixels would hide a weight that is one unit off).  axes = n_axes x {in_size, crop_start, crop_size,
  * out_size}; with max_out the largest out_size of the batch, axis a's tables lie at a fixed pitch: first[a * max_out + o],

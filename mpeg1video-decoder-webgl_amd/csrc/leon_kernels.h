@@ -38,6 +38,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "leon_resize_row.h"
+#include "leon_warp.h"
 
 
 namespace leon {
@@ -2551,6 +2552,199 @@ __global__ __launch_bounds__(kRgbaBlock) void k_fitted(const uint8_t* __restrict
     G.off_cx = d.off_cx; G.off_wx = d.off_wx; G.off_fy = d.off_fy; G.off_cy = d.off_cy; G.off_wy = d.off_wy;
     const RegionFrame where{FramePair{planes_ring + (size_t)d.frame_id * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi), dst}};
     resample_body<EB, LAYOUT, F>(where, table, T, tabs + d.rt_base, G, C);
+}
+
+// ---- rotated boxes and affine crops of delivered frames (leon_pipeline.h, leon_pipeline_warp_regions) ---------------------------
+// blockIdx.z is the region, blockIdx.x / y the 32 x 8 tiles of the out size, a lane one output pixel as in resample_body's vertical
+// pass.  There are no tables: a workgroup reads its region's record (one address per workgroup: scalar loads), judges it with the
+// host's text (leon_warp.h) -- a refused region is left before any LDS use, not one byte of it written -- and one workgroup of the
+// region writes the status word.  The map is affine, so the source footprint of a rectangle of output pixels is the bounding box of
+// its four corner samples and their bilinear neighbours.  The tile is walked in pieces (leon_warp.h: warp_level) whose footprint,
+// aligned to 8 columns and even rows, fits the stage; per piece (1) the footprint is loaded and converted ONCE into RGBX dwords in
+// LDS with resample_body's loads and conversion (8 Y bytes a row and 4 + 4 chroma bytes a row pair per lane, chroma_terms /
+// tensor_px8, the fill row of an odd height) -- what lies outside the frame is staged as the pad pixel and never loaded, so the taps
+// select nothing; a piece wholly outside stages nothing at all; (2) the piece's lanes accumulate their S x S x 4 taps from LDS.
+// Sample positions: the definition's 64-bit numerator once per piece and axis, minus the stage's origin (scalar); what a lane adds
+// to it stays inside 2^28, so its arithmetic is 32 bits.  After the last piece the pixel leaves through resample_body's store forms.
+struct WarpCall {
+    int32_t fw, fh, ow, oh;
+    int32_t n_frames;
+    uint32_t pad;                        // the pad pixel's 8-bit R, G, B in bits 0, 8, 16
+    uint32_t pitch_lo, pitch_hi;         // bytes between the regions' tensors
+    RingGeom ring;
+};
+// A tile's pixels to the tensor at `dst` (the image is the tensor): resample_body's two store forms, which see its comment.  `pack`:
+// LDS nobody reads any more, kRows * kRowStride bytes.
+template <int EB, int LAYOUT>
+__device__ __forceinline__ void warp_store(uint32_t px, bool valid, const typename ElemOf<EB>::type* tab_s, char* pack, uint8_t* dst, int ox0, int oy0, int nox, int noy,
+                                           int o, int sub, uint32_t width, uint32_t plane_elems)
+{
+    typedef typename ElemOf<EB>::type Elem;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, (int)(3u * plane_elems * EB), 0x00020000);
+    if constexpr (LAYOUT == kLayoutChw && EB != 1) {
+        const uint32_t at = (uint32_t)(oy0 + sub) * width + (uint32_t)(ox0 + o);
+        const uint32_t oob = valid ? 0u : kOobBit;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            const Elem e = tab_s[ch * 256 + ((px >> (8 * ch)) & 255u)];
+            const uint32_t voff = (((uint32_t)ch * plane_elems + at) * (uint32_t)sizeof(Elem)) | oob;
+            if constexpr (sizeof(Elem) == 4) __builtin_amdgcn_raw_buffer_store_b32(e, rs, (int)voff, 0, kAuxFrameStore);
+            else __builtin_amdgcn_raw_buffer_store_b16(e, rs, (int)voff, 0, kAuxFrameStore);
+        }
+    } else {
+        constexpr bool kHwc = LAYOUT == kLayoutHwc;
+        constexpr int kRowElems = kHwc ? 3 * kResTileX : kResTileX, kRowStride = kRowElems * EB + 16;
+        constexpr int kRows = kHwc ? kResTileY : 3 * kResTileY, kLines = (kRowElems * EB + 15) / 16 + 1;
+        constexpr int kLinesP2 = kLines <= 4 ? 4 : 32;
+        static_assert(kRows * kRowStride <= kWarpStagePx * 4 && kLines <= kLinesP2 && kRows * kLinesP2 <= kRgbaBlock, "the packed tile fits the stage, a lane per line");
+        auto row_start = [&](int row) -> uint32_t {
+            if constexpr (kHwc) return ((uint32_t)(oy0 + row) * width + (uint32_t)ox0) * 3u * EB;
+            else return ((uint32_t)(row >> 3) * plane_elems + (uint32_t)(oy0 + (row & 7)) * width + (uint32_t)ox0) * EB;
+        };
+        if (valid) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                const int row = kHwc ? sub : ch * kResTileY + sub;
+                const int at = (int)(row_start(row) & 15u) + (kHwc ? (o * 3 + ch) * EB : o * EB);
+                *reinterpret_cast<Elem*>(pack + row * kRowStride + at) = (Elem)image_elem<EB>(tab_s, px, ch);
+            }
+        }
+        __syncthreads();
+        const int tid = threadIdx.x;
+        const int row = tid / kLinesP2, line = tid & (kLinesP2 - 1);
+        if (row < kRows && (kHwc ? row : (row & 7)) < noy) {
+            const uint32_t g0 = row_start(row), g1 = g0 + (uint32_t)(nox * (kHwc ? 3 : 1) * EB);      // the row's bytes in the tensor
+            const uint32_t a0 = (g0 & ~15u) + 16u * (uint32_t)line;                                   // this lane's line
+            const char* from = pack + row * kRowStride + 16 * line;
+            if (a0 >= g0 && a0 + 16u <= g1) __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const v4u*>(from), rs, (int)a0, 0, kAuxFrameStore);
+            else if (a0 + 16u > g0 && a0 < g1) {
+                for (int e = 0; e < 16 / EB; e++) {          // a line at an end of the row: only the elements inside [g0, g1), one by one
+                    const uint32_t a = a0 + (uint32_t)(e * EB);
+                    if (a < g0 || a >= g1) continue;
+                    pad_store_elem<EB>(*reinterpret_cast<const Elem*>(from + e * EB), rs, a);
+                }
+            }
+        }
+    }
+}
+template <int EB, int LAYOUT>
+__global__ __launch_bounds__(kRgbaBlock) void k_warp(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ out, const WarpRecord* __restrict__ recs,
+                                                     const uint32_t* __restrict__ frame_ids, int32_t* __restrict__ status_out, const uint32_t* __restrict__ table,
+                                                     const Tables* __restrict__ T, WarpCall c)
+{
+    typedef typename ElemOf<EB>::type Elem;
+    static_assert(kResTileX * kResTileY == kRgbaBlock && kResTileX == 32, "lane = (tid & 31, tid >> 5)");
+    __shared__ __attribute__((aligned(16))) int32_t lut_s[kLdsLut / 4];
+    __shared__ __attribute__((aligned(16))) Elem tab_s[EB == 1 ? 16 : 3 * 256];
+    __shared__ __attribute__((aligned(16))) uint32_t stage_s[kWarpStagePx];
+    const WarpRecord r = recs[blockIdx.z];
+    int32_t g;
+    const int32_t status = warp_record_status(r, c.n_frames, &g);
+    if (status_out && (blockIdx.x | blockIdx.y) == 0 && threadIdx.x == 0) status_out[blockIdx.z] = status;
+    if (status != kRegionOk) return;
+    const int tid = threadIdx.x;
+    {   // the conversion tables and the element table as k_tensor loads them
+        display_lut_to_lds(lut_s, T);
+        if constexpr (EB != 1) {
+            constexpr int kDwords = 3 * 256 * EB / 4;
+            for (int i = tid; i < kDwords; i += kRgbaBlock) reinterpret_cast<uint32_t*>(tab_s)[i] = table[i];
+        }
+        wait_vmem_all();
+        __syncthreads();
+    }
+    const int ox0 = blockIdx.x * kResTileX, oy0 = blockIdx.y * kResTileY;
+    const int nox = min(kResTileX, c.ow - ox0), noy = min(kResTileY, c.oh - oy0);
+    const int o = tid & 31, sub = tid >> 5;
+    const int32_t a00 = r.m[0], a01 = r.m[1], tx = r.m[2], a10 = r.m[3], a11 = r.m[4], ty = r.m[5];
+    const int S = 1 << g, S2 = 2 << g;
+    const int level = warp_level(r.m, g);
+    const int pw = warp_piece_w(level), ph = warp_piece_h(level);
+    const uint64_t planes_pitch = join64(c.ring.planes_pitch_lo, c.ring.planes_pitch_hi);
+    const uint8_t* src = planes_ring + (size_t)frame_ids[r.frame] * planes_pitch;
+    // (the frame's planes end where the ring's next frame starts: a wrong offset reads 0 and faults nothing)
+    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (int)min(planes_pitch, (uint64_t)0x7fffffff), 0x00020000);
+    const char* lut = reinterpret_cast<const char*>(lut_s);
+    uint32_t two = 2u, three = 3u;                       // SDWA shift counts live in registers (display_half)
+    asm("" : "+v"(two), "+v"(three));
+    uint32_t px = 0u;
+    for (int py = 0; py < noy; py += ph) {
+        for (int pxo = 0; pxo < nox; pxo += pw) {
+            const int qw = min(pw, nox - pxo), qh = min(ph, noy - py);
+            const int fx_o = ox0 + pxo, fy_o = oy0 + py;          // the piece's first pixel, and its last:
+            const int lx_o = fx_o + qw - 1, ly_o = fy_o + qh - 1;
+            // the four corner samples: the piece's extremes on both axes (the numerators are affine in the pixel and the sub-sample)
+            const int64_t nx00 = warp_numerator(a00, a01, tx, g, fx_o, fy_o, 0, 0), nx10 = warp_numerator(a00, a01, tx, g, lx_o, fy_o, S - 1, 0);
+            const int64_t nx01 = warp_numerator(a00, a01, tx, g, fx_o, ly_o, 0, S - 1), nx11 = warp_numerator(a00, a01, tx, g, lx_o, ly_o, S - 1, S - 1);
+            const int64_t ny00 = warp_numerator(a10, a11, ty, g, fx_o, fy_o, 0, 0), ny10 = warp_numerator(a10, a11, ty, g, lx_o, fy_o, S - 1, 0);
+            const int64_t ny01 = warp_numerator(a10, a11, ty, g, fx_o, ly_o, 0, S - 1), ny11 = warp_numerator(a10, a11, ty, g, lx_o, ly_o, S - 1, S - 1);
+            const int x_lo = warp_q(min(min(nx00, nx10), min(nx01, nx11)), g) >> 8, x_hi = (warp_q(max(max(nx00, nx10), max(nx01, nx11)), g) >> 8) + 1;
+            const int y_lo = warp_q(min(min(ny00, ny10), min(ny01, ny11)), g) >> 8, y_hi = (warp_q(max(max(ny00, ny10), max(ny01, ny11)), g) >> 8) + 1;
+            const int sx0 = x_lo & ~7, sx1 = (x_hi + 8) & ~7, sy0 = y_lo & ~1, sy1 = (y_hi + 2) & ~1;      // [sx0, sx1) x [sy0, sy1)
+            const bool mine = o >= pxo && o < pxo + qw && sub >= py && sub < py + qh;
+            if (sx1 <= 0 || sx0 >= c.fw || sy1 <= 0 || sy0 >= c.fh) {          // nothing of the frame: every tap reads the pad
+                if (mine) px = c.pad;
+                continue;
+            }
+            const int sw8 = (sx1 - sx0) >> 3, n_pairs = (sy1 - sy0) >> 1;
+            const int pitch = sx1 - sx0 + 1;                                  // odd (leon_warp.h)
+            // (1) rows sy0 .. sy1 - 1 (whole pairs), columns sx0 .. sx1 - 1 -> RGBX in stage_s[row][pitch]; outside the frame: the pad
+            const int pair_t = tid / sw8, col_t = tid - pair_t * sw8;
+            const int pair_step = kRgbaBlock / sw8, col_step = kRgbaBlock - pair_step * sw8;
+            for (int pair = pair_t, col = col_t; pair < n_pairs;) {
+                const int row = sy0 + 2 * pair, x = sx0 + 8 * col;          // (row is even: row >= 0 is row + 1 >= 0 too)
+                const bool inx = x >= 0 && x < c.fw;
+                const bool in0 = inx && row >= 0 && row < c.fh, in1 = inx && row >= 0 && row + 1 < c.fh;
+                const uint32_t yo = (uint32_t)row * c.ring.luma_stride + (uint32_t)x;
+                const uint32_t co = (uint32_t)(row >> 1) * c.ring.chroma_stride + (uint32_t)(x >> 1);
+                const v2u y0 = __builtin_amdgcn_raw_buffer_load_b64(prs, (int)(in0 ? yo : kOobBit), 0, kAuxStreamOnce);
+                const v2u y1 = __builtin_amdgcn_raw_buffer_load_b64(prs, (int)(in1 ? yo + c.ring.luma_stride : kOobBit), 0, kAuxStreamOnce);
+                const uint32_t cb4 = __builtin_amdgcn_raw_buffer_load_b32(prs, (int)(in0 ? c.ring.cb_off + co : kOobBit), 0, kAuxStreamOnce);
+                const uint32_t cr4 = __builtin_amdgcn_raw_buffer_load_b32(prs, (int)(in0 ? c.ring.cr_off + co : kOobBit), 0, kAuxStreamOnce);
+                const ChromaTerms ct[4] = {chroma_terms<0>(lut, cb4, cr4, three), chroma_terms<1>(lut, cb4, cr4, three),
+                                           chroma_terms<2>(lut, cb4, cr4, three), chroma_terms<3>(lut, cb4, cr4, three)};
+                uint32_t a[8], b[8];
+                tensor_px8(lut, y0, ct, !in1, two, a);       // (!in1: the last row of an odd height, left at 255 by the twin)
+                tensor_px8(lut, y1, ct, false, two, b);
+                const int n_in = c.fw - x;                   // columns of the group inside the frame (a width that is no multiple of 8)
+                uint32_t* s0 = stage_s + (2 * pair) * pitch + 8 * col;
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    s0[k] = in0 && k < n_in ? a[k] : c.pad;
+                    s0[pitch + k] = in1 && k < n_in ? b[k] : c.pad;
+                }
+                pair += pair_step; col += col_step;
+                if (col >= sw8) { col -= sw8; pair++; }
+            }
+            __syncthreads();
+            // (2) the piece's pixels: S x S bilinear samples each, positions relative to the stage's origin
+            if (mine) {
+                const int32_t bx = (int32_t)(nx00 - ((int64_t)sx0 << (17 + g))), by = (int32_t)(ny00 - ((int64_t)sy0 << (17 + g)));
+                const int32_t dx = S2 * (o - pxo), dy = S2 * (sub - py);
+                const int32_t nx0 = bx + a00 * dx + a01 * dy, ny0 = by + a10 * dx + a11 * dy;
+                uint32_t ar = 0u, ag = 0u, ab = 0u;
+                for (int j = 0; j < S; j++) {
+                    for (int i = 0; i < S; i++) {
+                        const int32_t nx = nx0 + 2 * (a00 * i + a01 * j), ny = ny0 + 2 * (a10 * i + a11 * j);
+                        const int32_t qx = ((nx >> (g + 1)) + 128) >> 8, qy = ((ny >> (g + 1)) + 128) >> 8;
+                        const uint32_t fx = (uint32_t)qx & 255u, fy = (uint32_t)qy & 255u;
+                        const uint32_t* s = stage_s + (qy >> 8) * pitch + (qx >> 8);
+                        const uint32_t p00 = s[0], p01 = s[1], p10 = s[pitch], p11 = s[pitch + 1];
+                        const uint32_t w00 = (256u - fx) * (256u - fy), w01 = fx * (256u - fy), w10 = (256u - fx) * fy, w11 = fx * fy;
+                        ar += __umul24(w00, p00 & 255u) + __umul24(w01, p01 & 255u) + __umul24(w10, p10 & 255u) + __umul24(w11, p11 & 255u);
+                        ag += __umul24(w00, (p00 >> 8) & 255u) + __umul24(w01, (p01 >> 8) & 255u) + __umul24(w10, (p10 >> 8) & 255u) + __umul24(w11, (p11 >> 8) & 255u);
+                        ab += __umul24(w00, (p00 >> 16) & 255u) + __umul24(w01, (p01 >> 16) & 255u) + __umul24(w10, (p10 >> 16) & 255u) + __umul24(w11, (p11 >> 16) & 255u);
+                    }
+                }
+                const uint32_t half = 1u << (15 + 2 * g);
+                const int sh = 16 + 2 * g;
+                px = ((ar + half) >> sh) | (((ag + half) >> sh) << 8) | (((ab + half) >> sh) << 16);          // (the weights sum to 2^sh: at most 255 each)
+            }
+            __syncthreads();          // the stage is free for the next piece, or for the store
+        }
+    }
+    const uint64_t dst_off = (uint64_t)blockIdx.z * join64(c.pitch_lo, c.pitch_hi);
+    warp_store<EB, LAYOUT>(px, o < nox && sub < noy, tab_s, reinterpret_cast<char*>(stage_s), out + dst_off, ox0, oy0, nox, noy, o, sub, (uint32_t)c.ow,
+                           (uint32_t)c.ow * (uint32_t)c.oh);
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

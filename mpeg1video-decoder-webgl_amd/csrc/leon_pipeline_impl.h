@@ -1637,6 +1637,26 @@ int boxes_reserve(leon_pipeline* p, size_t bytes)
     return LEON_OK;
 }
 
+// the window's frame ids into a pinned staging entry whose last upload has run (four calls back: as good as always); regions_mu held.
+// The entry is (boxes_ids_next - 1) % kBoxesStaging afterwards: the caller records its event behind the upload.
+int boxes_ids_stage(leon_pipeline* p, const std::vector<uint32_t>& ids, uint32_t** host)
+{
+    const unsigned e = p->boxes_ids_next++ % leon_pipeline::kBoxesStaging;
+    if (p->boxes_ids_busy[e]) { HIP_TRY(hipEventSynchronize(p->boxes_ids_done[e])); p->boxes_ids_busy[e] = false; }
+    if (!p->boxes_ids_done[e]) HIP_TRY(hipEventCreateWithFlags(&p->boxes_ids_done[e], hipEventDisableTiming));
+    if (ids.size() > p->boxes_ids_cap[e]) {
+        const size_t cap = std::max(ids.size() * 2, (size_t)1024);
+        uint32_t* h = nullptr;
+        if (hipHostMalloc((void**)&h, cap * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of pinned staging", cap * 4); }
+        if (p->boxes_ids_host[e]) hipHostFree(p->boxes_ids_host[e]);
+        p->boxes_ids_host[e] = h;
+        p->boxes_ids_cap[e] = cap;
+    }
+    std::copy(ids.begin(), ids.end(), p->boxes_ids_host[e]);
+    *host = p->boxes_ids_host[e];
+    return LEON_OK;
+}
+
 // One call: the host's refusals, the window's frame ids uploaded, then per chunk k_box_tables and k_boxes on the caller's stream (or the
 // pipeline's regions stream and a wait).  regions_mu is held while enqueuing only.
 int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit_settings,
@@ -1687,25 +1707,15 @@ int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipelin
     }
     if (!p->boxes_done) HIP_TRY(hipEventCreateWithFlags(&p->boxes_done, hipEventDisableTiming));
     if ((rc = boxes_reserve(p, ids_bytes + desc_bytes + chunk * slot_words * 4)) != LEON_OK) return rc;
-    // the frame ids through a staging entry whose last upload has run (four calls back: as good as always)
-    const unsigned e = p->boxes_ids_next++ % leon_pipeline::kBoxesStaging;
-    if (p->boxes_ids_busy[e]) { HIP_TRY(hipEventSynchronize(p->boxes_ids_done[e])); p->boxes_ids_busy[e] = false; }
-    if (!p->boxes_ids_done[e]) HIP_TRY(hipEventCreateWithFlags(&p->boxes_ids_done[e], hipEventDisableTiming));
-    if (ids.size() > p->boxes_ids_cap[e]) {
-        const size_t cap = std::max(ids.size() * 2, (size_t)1024);
-        uint32_t* h = nullptr;
-        if (hipHostMalloc((void**)&h, cap * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of pinned staging", cap * 4); }
-        if (p->boxes_ids_host[e]) hipHostFree(p->boxes_ids_host[e]);
-        p->boxes_ids_host[e] = h;
-        p->boxes_ids_cap[e] = cap;
-    }
-    std::copy(ids.begin(), ids.end(), p->boxes_ids_host[e]);
+    uint32_t* ids_host = nullptr;
+    if ((rc = boxes_ids_stage(p, ids, &ids_host)) != LEON_OK) return rc;
+    const unsigned e = (p->boxes_ids_next - 1) % leon_pipeline::kBoxesStaging;
     // from here on the stream holds work: the event is recorded whatever happens, so that the scratch stays covered
     if (p->boxes_busy) HIP_TRY(hipStreamWaitEvent(st, p->boxes_done, 0));
     uint32_t* d_ids = reinterpret_cast<uint32_t*>(p->boxes_dev);
     leon::RegionDesc* d_descs = reinterpret_cast<leon::RegionDesc*>(p->boxes_dev + ids_bytes);
     int32_t* d_tabs = reinterpret_cast<int32_t*>(p->boxes_dev + ids_bytes + desc_bytes);
-    hipError_t he = hipMemcpyAsync(d_ids, p->boxes_ids_host[e], ids.size() * 4, hipMemcpyHostToDevice, st);
+    hipError_t he = hipMemcpyAsync(d_ids, ids_host, ids.size() * 4, hipMemcpyHostToDevice, st);
     if (he == hipSuccess && (he = hipEventRecord(p->boxes_ids_done[e], st)) == hipSuccess) p->boxes_ids_busy[e] = true;
     leon::ResampleGeom G{};
     G.fw = fw; G.fh = fh; G.ow = ow; G.oh = oh;
@@ -1732,6 +1742,186 @@ int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipelin
             hipLaunchKernelGGL(kb, dim3(gx, gy, m), dim3(leon::kRgbaBlock), 0, st, (const uint8_t*)p->d_planes, static_cast<uint8_t*>(c->device_out), (const leon::RegionDesc*)d_descs,
                                (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)d_tabs, G);
         }
+        he = hipGetLastError();
+    }
+    if (hipEventRecord(p->boxes_done, st) == hipSuccess) p->boxes_busy = true;
+    else if (he == hipSuccess) he = hipGetLastError();
+    call.unlock();
+    HIP_TRY(he);
+    if (!c->stream) HIP_TRY(hipStreamSynchronize(st));
+    return LEON_OK;
+}
+
+// ---- rotated boxes and affine crops (leon_pipeline_warp_regions) ---------------------------------------------------------------
+typedef void (*WarpKernel)(const uint8_t*, uint8_t*, const leon::WarpRecord*, const uint32_t*, int32_t*, const uint32_t*, const leon::Tables*, leon::WarpCall);
+constexpr WarpKernel kWarpKernels[3][2] = {{leon::k_warp<1, leon::kLayoutChw>, leon::k_warp<1, leon::kLayoutHwc>},
+                                           {leon::k_warp<2, leon::kLayoutChw>, leon::k_warp<2, leon::kLayoutHwc>},
+                                           {leon::k_warp<4, leon::kLayoutChw>, leon::k_warp<4, leon::kLayoutHwc>}};
+static_assert(sizeof(leon_pipeline_warp_region) == 32 && sizeof(leon_pipeline_warp_config) == 32 && sizeof(leon_pipeline_warp_regions_call) == 64 &&
+              sizeof(leon::WarpRecord) == sizeof(leon_pipeline_warp_region), "include/leon_pipeline.h states the sizes");
+static_assert(leon::kRegionScale == LEON_REGION_SCALE && leon::kRegionOffset == LEON_REGION_OFFSET, "the kernels' codes are the header's");
+
+// what a call's config, window and n can be refused for, whichever memory the records lie in; *pad: the pad pixel as the kernel takes it
+int warp_config_check(int32_t fw, int32_t fh, int32_t n_frames, int32_t n, const leon_pipeline_warp_config* cfg, uint32_t* pad)
+{
+    if (!cfg) return fail(LEON_ERR_INVALID, "null argument");
+    for (int i = 0; i < 3; i++)
+        if (cfg->reserved[i]) return fail(LEON_ERR_INVALID, "warp config: reserved word %d is %d, not 0", i, cfg->reserved[i]);
+    if (cfg->out_width < 1 || cfg->out_width > 4096) return fail(LEON_ERR_INVALID, "warp config: out_width %d is outside 1 .. 4096", cfg->out_width);
+    if (cfg->out_height < 1 || cfg->out_height > 4096) return fail(LEON_ERR_INVALID, "warp config: out_height %d is outside 1 .. 4096", cfg->out_height);
+    for (int i = 0; i < 3; i++)
+        if (cfg->pad[i] < 0 || cfg->pad[i] > 255) return fail(LEON_ERR_INVALID, "warp config: pad value %d is %d, outside 0 .. 255", i, cfg->pad[i]);
+    if (fw < 1 || fh < 1 || n_frames < 0) return fail(LEON_ERR_INVALID, "warp regions: %d frames of %d x %d", n_frames, fw, fh);
+    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "warp regions: %d regions (a call takes 1 .. 65535)", n);
+    if (pad) *pad = (uint32_t)cfg->pad[0] | ((uint32_t)cfg->pad[1] << 8) | ((uint32_t)cfg->pad[2] << 16);
+    return LEON_OK;
+}
+
+inline const leon::WarpRecord& warp_record(const leon_pipeline_warp_region& r) { return reinterpret_cast<const leon::WarpRecord&>(r); }
+
+// Every refusal that needs no device (leon_pipeline_warp_regions_check is this function): the kernel's judgement, named
+int warp_regions_check(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_warp_region* regions, int32_t n, const leon_pipeline_warp_config* cfg,
+                       int32_t* bad, uint32_t* pad)
+{
+    if (bad) *bad = -1;
+    if (!regions || !cfg) return fail(LEON_ERR_INVALID, "null argument");
+    const int crc = warp_config_check(fw, fh, n_frames, n, cfg, pad);
+    if (crc != LEON_OK) return crc;
+    for (int32_t i = 0; i < n; i++) {
+        const leon_pipeline_warp_region& r = regions[i];
+        int32_t g;
+        const int32_t status = leon::warp_record_status(warp_record(r), n_frames, &g);
+        if (status == LEON_REGION_OK) continue;
+        if (bad) *bad = i;
+        switch (status) {
+        case LEON_REGION_RESERVED: return fail(LEON_ERR_INVALID, "region %d: the reserved word is %d, not 0", i, r.reserved);
+        case LEON_REGION_FRAME: return fail(LEON_ERR_INVALID, "region %d: frame %d is outside the window's %d frames", i, r.frame, n_frames);
+        case LEON_REGION_SCALE: return fail(LEON_ERR_INVALID, "region %d: the matrix (%d %d / %d %d, Q16) reduces by more than 4", i, r.m[0], r.m[1], r.m[3], r.m[4]);
+        default: return fail(LEON_ERR_INVALID, "region %d: offset (%d, %d) is outside +-2^29 (Q16)", i, r.m[2], r.m[5]);
+        }
+    }
+    return LEON_OK;
+}
+
+int warp_quantise(const double* A, int32_t* m)
+{
+    if (!A || !m) return fail(LEON_ERR_INVALID, "null argument");
+    int32_t q[6];
+    for (int k = 0; k < 6; k++) {
+        if (!std::isfinite(A[k])) return fail(LEON_ERR_INVALID, "warp matrix: entry %d is not finite", k);
+        const double v = std::floor(A[k] * 65536.0 + 0.5);
+        if (v < -2147483648.0 || v > 2147483647.0) return fail(LEON_ERR_INVALID, "warp matrix: entry %d (%g) is outside Q16 in 32 bits", k, A[k]);
+        q[k] = (int32_t)v;
+    }
+    for (int k = 0; k < 6; k++) m[k] = q[k];
+    return LEON_OK;
+}
+
+// the launch both roads share: records and frame ids in device memory
+void warp_launch(leon_pipeline* p, hipStream_t st, const leon::WarpRecord* d_recs, const uint32_t* d_ids, int32_t n_frames, int32_t n, const leon_pipeline_warp_config& cfg,
+                 uint32_t pad, uint8_t* out, uint64_t pitch, int32_t* d_status)
+{
+    leon::WarpCall C{};
+    C.fw = p->vinfo.frame_width; C.fh = p->vinfo.frame_height; C.ow = cfg.out_width; C.oh = cfg.out_height;
+    C.n_frames = n_frames;
+    C.pad = pad;
+    C.pitch_lo = (uint32_t)(pitch & 0xffffffffu); C.pitch_hi = (uint32_t)(pitch >> 32);
+    C.ring = ring_geom(p);
+    const unsigned gx = (unsigned)((cfg.out_width + leon::kResTileX - 1) / leon::kResTileX), gy = (unsigned)((cfg.out_height + leon::kResTileY - 1) / leon::kResTileY);
+    hipLaunchKernelGGL(kWarpKernels[p->tensor_elem >> 1][p->tensor_layout], dim3(gx, gy, (unsigned)n), dim3(leon::kRgbaBlock), 0, st, (const uint8_t*)p->d_planes, out, d_recs,
+                       d_ids, d_status, (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, C);
+}
+int warp_pipeline_check(const leon_pipeline* p)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR) || !p->d_tensor || !p->d_planes)
+        return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    const int eb = (int)p->tensor_elem, layout = p->tensor_layout;
+    if (!((eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc)))
+        return fail(LEON_ERR_INVALID, "warp regions: no kernel for %d-byte elements, layout %d", eb, layout);
+    return LEON_OK;
+}
+
+// One call of the host road: refusals, [frame ids | records] through the regions staging, one upload, one launch, the wait
+int warp_regions(leon_pipeline* p, int64_t window, const leon_pipeline_warp_region* regions, int32_t n, const leon_pipeline_warp_config* cfg, void* device_out,
+                 uint64_t out_pitch, void* host)
+{
+    int rc = warp_pipeline_check(p);
+    if (rc != LEON_OK) return rc;
+    std::lock_guard<std::mutex> call(p->regions_mu);
+    std::vector<uint32_t> ids;
+    if ((rc = regions_window_ids(p, window, &ids)) != LEON_OK) return rc;
+    uint32_t pad = 0;
+    if ((rc = warp_regions_check(p->vinfo.frame_width, p->vinfo.frame_height, (int32_t)ids.size(), regions, n, cfg, nullptr, &pad)) != LEON_OK) return rc;
+    const size_t region_bytes = (size_t)3 * cfg->out_height * cfg->out_width * p->tensor_elem;
+    if (host) { device_out = nullptr; out_pitch = 0; }
+    else {
+        if (!device_out) return fail(LEON_ERR_INVALID, "warp regions: null device_out");
+        if ((uintptr_t)device_out & 255u) return fail(LEON_ERR_INVALID, "warp regions: device_out %p is not 256-byte aligned", device_out);
+    }
+    if (out_pitch && (out_pitch % 256 || out_pitch < region_bytes))
+        return fail(LEON_ERR_INVALID, "warp regions: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", (unsigned long long)out_pitch, region_bytes);
+    const size_t pitch = out_pitch ? (size_t)out_pitch : pad256(region_bytes);
+    const size_t ids_bytes = pad256(ids.size() * 4), upload_bytes = ids_bytes + (size_t)n * sizeof(leon::WarpRecord);
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    if (!p->regions_stream) HIP_TRY(hipStreamCreateWithFlags(&p->regions_stream, hipStreamNonBlocking));
+    if ((rc = regions_reserve(p, upload_bytes, host ? (size_t)n * pitch : 0)) != LEON_OK) return rc;
+    std::copy(ids.begin(), ids.end(), reinterpret_cast<uint32_t*>(p->regions_host));
+    std::memcpy(p->regions_host + ids_bytes, regions, (size_t)n * sizeof(leon::WarpRecord));
+    uint8_t* out = host ? p->regions_out : static_cast<uint8_t*>(device_out);
+    hipStream_t st = p->regions_stream;
+    HIP_TRY(hipMemcpyAsync(p->regions_dev, p->regions_host, upload_bytes, hipMemcpyHostToDevice, st));
+    warp_launch(p, st, reinterpret_cast<const leon::WarpRecord*>(p->regions_dev + ids_bytes), reinterpret_cast<const uint32_t*>(p->regions_dev), (int32_t)ids.size(), n, *cfg,
+                pad, out, pitch, nullptr);
+    HIP_TRY(hipGetLastError());
+    if (host) HIP_TRY(hipMemcpy2DAsync(host, region_bytes, out, pitch, region_bytes, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LEON_OK;
+}
+
+// One call of the device road: the host's refusals, the window's frame ids uploaded into the boxes scratch behind its event, one launch on
+// the caller's stream (or the regions stream and a wait).  regions_mu is held while enqueuing only.
+int warp_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_warp_config* cfg, const leon_pipeline_warp_regions_call* c)
+{
+    int rc = warp_pipeline_check(p);
+    if (rc != LEON_OK) return rc;
+    if (!cfg || !c) return fail(LEON_ERR_INVALID, "null argument");
+    std::unique_lock<std::mutex> call(p->regions_mu);
+    std::vector<uint32_t> ids;
+    if ((rc = regions_window_ids(p, window, &ids)) != LEON_OK) return rc;
+    uint32_t pad = 0;
+    const int32_t n = c->n;
+    if ((rc = warp_config_check(p->vinfo.frame_width, p->vinfo.frame_height, (int32_t)ids.size(), n, cfg, &pad)) != LEON_OK) return rc;
+    if (c->reserved0 || c->reserved[0] || c->reserved[1]) return fail(LEON_ERR_INVALID, "warp regions: a reserved word of the call is not 0");
+    if (!c->regions) return fail(LEON_ERR_INVALID, "warp regions: null regions");
+    if ((uintptr_t)c->regions & 3u) return fail(LEON_ERR_INVALID, "warp regions: regions %p is not 4-byte aligned", (const void*)c->regions);
+    if ((uintptr_t)c->device_status & 3u) return fail(LEON_ERR_INVALID, "warp regions: device_status %p is not 4-byte aligned", (void*)c->device_status);
+    if (!c->device_out) return fail(LEON_ERR_INVALID, "warp regions: null device_out");
+    if ((uintptr_t)c->device_out & 255u) return fail(LEON_ERR_INVALID, "warp regions: device_out %p is not 256-byte aligned", c->device_out);
+    const size_t region_bytes = (size_t)3 * cfg->out_height * cfg->out_width * p->tensor_elem;
+    if (c->out_pitch_bytes && (c->out_pitch_bytes % 256 || c->out_pitch_bytes < region_bytes))
+        return fail(LEON_ERR_INVALID, "warp regions: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", (unsigned long long)c->out_pitch_bytes,
+                    region_bytes);
+    const uint64_t pitch = c->out_pitch_bytes ? c->out_pitch_bytes : (uint64_t)pad256(region_bytes);
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    hipStream_t st = static_cast<hipStream_t>(c->stream);
+    if (!st) {
+        if (!p->regions_stream) HIP_TRY(hipStreamCreateWithFlags(&p->regions_stream, hipStreamNonBlocking));
+        st = p->regions_stream;
+    }
+    if (!p->boxes_done) HIP_TRY(hipEventCreateWithFlags(&p->boxes_done, hipEventDisableTiming));
+    if ((rc = boxes_reserve(p, pad256(ids.size() * 4))) != LEON_OK) return rc;
+    uint32_t* ids_host = nullptr;
+    if ((rc = boxes_ids_stage(p, ids, &ids_host)) != LEON_OK) return rc;
+    const unsigned e = (p->boxes_ids_next - 1) % leon_pipeline::kBoxesStaging;
+    // from here on the stream holds work: the event is recorded whatever happens, so that the scratch stays covered
+    if (p->boxes_busy) HIP_TRY(hipStreamWaitEvent(st, p->boxes_done, 0));
+    uint32_t* d_ids = reinterpret_cast<uint32_t*>(p->boxes_dev);
+    hipError_t he = hipMemcpyAsync(d_ids, ids_host, ids.size() * 4, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && (he = hipEventRecord(p->boxes_ids_done[e], st)) == hipSuccess) p->boxes_ids_busy[e] = true;
+    if (he == hipSuccess) {
+        warp_launch(p, st, reinterpret_cast<const leon::WarpRecord*>(c->regions), d_ids, (int32_t)ids.size(), n, *cfg, pad, static_cast<uint8_t*>(c->device_out), pitch,
+                    c->device_status);
         he = hipGetLastError();
     }
     if (hipEventRecord(p->boxes_done, st) == hipSuccess) p->boxes_busy = true;
@@ -2715,6 +2905,58 @@ int leon_pipeline_resample_regions_device_fit(leon_pipeline* p, int64_t window, 
                                               const leon_pipeline_regions_device* call, int32_t* device_rects)
 {
     return resample_regions_device(p, window, cfg, fit, call, device_rects);
+}
+
+int leon_pipeline_warp_regions_check(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_warp_region* regions, int32_t n,
+                                     const leon_pipeline_warp_config* cfg, int32_t* bad)
+{
+    return warp_regions_check(frame_width, frame_height, n_frames, regions, n, cfg, bad, nullptr);
+}
+
+int32_t leon_pipeline_warp_region_status(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_warp_region* region,
+                                         const leon_pipeline_warp_config* cfg)
+{
+    if (!region || !cfg) return fail(LEON_ERR_INVALID, "null argument");
+    const int rc = warp_config_check(frame_width, frame_height, n_frames, 1, cfg, nullptr);
+    int32_t g;
+    return rc != LEON_OK ? rc : leon::warp_record_status(warp_record(*region), n_frames, &g);
+}
+
+int leon_pipeline_warp_from_matrix(const double A[6], int32_t m[6])
+{
+    return warp_quantise(A, m);
+}
+
+int leon_pipeline_warp_from_rotated_box(double cx, double cy, double w, double h, double angle_degrees, int32_t out_width, int32_t out_height, int32_t m[6])
+{
+    if (out_width < 1 || out_height < 1) return fail(LEON_ERR_INVALID, "warp: an out size of %d x %d", out_width, out_height);
+    if (!std::isfinite(angle_degrees)) return fail(LEON_ERR_INVALID, "warp: the angle is not finite");
+    const double rad = angle_degrees * (3.14159265358979323846 / 180.0), cs = std::cos(rad), sn = std::sin(rad);
+    const double ow = out_width, oh = out_height;
+    double A[6];
+    A[0] = w / ow * cs; A[1] = -h / oh * sn;
+    A[3] = w / ow * sn; A[4] = h / oh * cs;
+    A[2] = cx - (A[0] * (ow / 2) + A[1] * (oh / 2));
+    A[5] = cy - (A[3] * (ow / 2) + A[4] * (oh / 2));
+    return warp_quantise(A, m);
+}
+
+int leon_pipeline_warp_regions(leon_pipeline* p, int64_t window, const leon_pipeline_warp_region* regions, int32_t n, const leon_pipeline_warp_config* cfg,
+                               void* device_out, uint64_t out_pitch_bytes)
+{
+    return warp_regions(p, window, regions, n, cfg, device_out, out_pitch_bytes, nullptr);
+}
+
+int leon_pipeline_read_warp_regions(leon_pipeline* p, int64_t window, const leon_pipeline_warp_region* regions, int32_t n, const leon_pipeline_warp_config* cfg,
+                                    void* host)
+{
+    if (!host) return fail(LEON_ERR_INVALID, "null argument");
+    return warp_regions(p, window, regions, n, cfg, nullptr, 0, host);
+}
+
+int leon_pipeline_warp_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_warp_config* cfg, const leon_pipeline_warp_regions_call* call)
+{
+    return warp_regions_device(p, window, cfg, call);
 }
 
 int leon_pipeline_resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,

@@ -50,6 +50,9 @@
  *                                  (default) or 'bicubic'.  fit: 'letterbox' keeps every box's aspect ratio inside h x w -- centred, or
  *                                  with anchor: 'top_left' at the top left -- and fills the rest with padValue [r, g, b] through the
  *                                  element table (leon_pipeline_read_regions_fit); without fit, anchor and padValue the boxes are stretched
+ *   p.readWarpRegions(window, regions, {size: [h, w], padValue}) -> Buffer like readRegions': regions = [[frameIndex, [a00, a01, tx, a10,
+ *                                  a11, ty]], ...], the Q16 affine map from output to frame coordinates of a rotated box or an aligned
+ *                                  crop (leon_pipeline_read_warp_regions); positions outside the frame read padValue [r, g, b]
  *   p.releaseWindow(window); p.stats(); p.destroy();
  * Open GOPs (closed_gop = 0) need no option: their leading B pictures predict from the GOP before; where that GOP is not decoded (start,
  * seek target, broken_link) they are not delivered and the GOP's frames start at its I picture's displayIndex (include/leon_pipeline.h).
@@ -174,6 +177,19 @@ class LeonPipeline extends EventEmitter {
     if (!Array.isArray(pad) || pad.length !== 3 || !pad.every(Number.isInteger)) throw new TypeError('padValue: [r, g, b]');
     if (!Number.isInteger(fit) || !Number.isInteger(anchor)) throw new TypeError('fit, anchor: a name or an integer');
     return this._p.readRegions(window, boxes, size[0], size[1], filter, fit, anchor, pad[0], pad[1], pad[2]);
+  }
+  // regions: [[frameIndex, [a00, a01, tx, a10, a11, ty]], ...], Q16 integers: rotated boxes and affine crops sampled into opts.size [h, w]
+  readWarpRegions(window, regions, opts) {
+    opts = opts || {};
+    const size = opts.size;
+    if (!Array.isArray(size) || size.length !== 2 || !size.every(Number.isInteger)) throw new TypeError('size: [height, width]');
+    if (!Array.isArray(regions) || !regions.every((r) => Array.isArray(r) && r.length === 2 && Number.isInteger(r[0]) && Array.isArray(r[1]) && r[1].length === 6 &&
+        r[1].every(Number.isInteger))) {
+      throw new TypeError('regions: [[frameIndex, [a00, a01, tx, a10, a11, ty]], ...] (Q16 integers)');
+    }
+    const pad = opts.padValue === undefined ? [0, 0, 0] : opts.padValue;
+    if (!Array.isArray(pad) || pad.length !== 3 || !pad.every(Number.isInteger)) throw new TypeError('padValue: [r, g, b]');
+    return this._p.readWarpRegions(window, Int32Array.from(regions.flat(2)), size[0], size[1], pad[0], pad[1], pad[2]);
   }
   releaseWindow(window) { this._p.releaseWindow(window); }
   stats() { return this._p.stats(); }

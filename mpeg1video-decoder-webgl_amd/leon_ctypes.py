@@ -43,6 +43,8 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_resample_regions_device", "leon_pipeline_region_status", "leon_pipeline_resize_weights_device",
     "leon_pipeline_region_fit_rect", "leon_pipeline_regions_fit_check", "leon_pipeline_region_fit_status",
     "leon_pipeline_resample_regions_fit", "leon_pipeline_read_regions_fit", "leon_pipeline_resample_regions_device_fit",
+    "leon_pipeline_warp_regions_check", "leon_pipeline_warp_region_status", "leon_pipeline_warp_from_matrix", "leon_pipeline_warp_from_rotated_box",
+    "leon_pipeline_warp_regions", "leon_pipeline_read_warp_regions", "leon_pipeline_warp_regions_device",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -342,6 +344,20 @@ def _regions_fit(fit, anchor, pad_value):
 # LEON_REGION_*: the status word of a region whose box lies in device memory (0: resampled; otherwise skipped, and why)
 REGION_OK, REGION_RESERVED, REGION_FRAME, REGION_BOX, REGION_RATIO_X, REGION_RATIO_Y, REGION_TAPS = range(7)
 REGIONS_SCRATCH_DEFAULT = 256 << 20          # LEON_REGIONS_SCRATCH_DEFAULT
+REGION_SCALE, REGION_OFFSET = 7, 8           # LEON_REGION_SCALE, LEON_REGION_OFFSET: a warp record's two own
+
+
+class PipelineWarpRegion(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("m", C.c_int32 * 6), ("reserved", C.c_int32)]
+
+
+class PipelineWarpConfig(C.Structure):
+    _fields_ = [("out_width", C.c_int32), ("out_height", C.c_int32), ("pad", C.c_int32 * 3), ("reserved", C.c_int32 * 3)]
+
+
+class PipelineWarpRegionsCall(C.Structure):
+    _fields_ = [("regions", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("device_out", C.c_void_p), ("out_pitch_bytes", C.c_uint64),
+                ("device_status", C.c_void_p), ("stream", C.c_void_p), ("reserved", C.c_uint64 * 2)]
 
 
 class PipelineTensorShape(C.Structure):
@@ -475,6 +491,16 @@ def load():
         lib.leon_pipeline_region_status.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineRegion), C.POINTER(PipelineRegionsConfig)]
         lib.leon_pipeline_region_status.restype = C.c_int32
         lib.leon_pipeline_resize_weights_device.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_warp_regions"):
+        P = C.POINTER
+        lib.leon_pipeline_warp_regions_check.argtypes = [C.c_int32, C.c_int32, C.c_int32, P(PipelineWarpRegion), C.c_int32, P(PipelineWarpConfig), P(C.c_int32)]
+        lib.leon_pipeline_warp_region_status.argtypes = [C.c_int32, C.c_int32, C.c_int32, P(PipelineWarpRegion), P(PipelineWarpConfig)]
+        lib.leon_pipeline_warp_region_status.restype = C.c_int32
+        lib.leon_pipeline_warp_from_matrix.argtypes = [P(C.c_double), P(C.c_int32)]
+        lib.leon_pipeline_warp_from_rotated_box.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, P(C.c_int32)]
+        lib.leon_pipeline_warp_regions.argtypes = [C.c_void_p, C.c_int64, P(PipelineWarpRegion), C.c_int32, P(PipelineWarpConfig), C.c_void_p, C.c_uint64]
+        lib.leon_pipeline_read_warp_regions.argtypes = [C.c_void_p, C.c_int64, P(PipelineWarpRegion), C.c_int32, P(PipelineWarpConfig), C.c_void_p]
+        lib.leon_pipeline_warp_regions_device.argtypes = [C.c_void_p, C.c_int64, P(PipelineWarpConfig), P(PipelineWarpRegionsCall)]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -526,6 +552,104 @@ def region_status(frame_width, frame_height, n_frames, region, size, filter="tri
     No device.  LeonError for a size or filter the library refuses."""
     arr, _, cfg = _regions_args([region], size, filter)
     st = load().leon_pipeline_region_status(int(frame_width), int(frame_height), int(n_frames), arr, C.byref(cfg))
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return st
+
+
+def warp_rgb(rgb, m, size, pad=(0, 0, 0)):
+    """The definition of leon_pipeline_warp_regions in numpy integers (include/leon_pipeline.h), written from the header's text: rgb
+    [H, W, 3] uint8 -- the CPU twin's colours of the frame, the fill row of an odd height included -- sampled along the Q16 map
+    m = (a00, a01, tx, a10, a11, ty) into size = (out_height, out_width) -> uint8 [oh, ow, 3]; positions outside the frame read pad.
+    Raises ValueError for a matrix the library refuses (REGION_SCALE, REGION_OFFSET)."""
+    rgb = np.asarray(rgb)
+    H, W = rgb.shape[:2]
+    oh, ow = int(size[0]), int(size[1])
+    a00, a01, tx, a10, a11, ty = (int(v) for v in m)
+    s2 = max(a00 * a00 + a10 * a10, a01 * a01 + a11 * a11)
+    g = next((k for k in range(3) if s2 <= ((1 << (16 + k)) + 1) ** 2), None)
+    if g is None:
+        raise ValueError("warp_rgb: the matrix reduces by more than 4")
+    if max(abs(tx), abs(ty)) > 1 << 29:
+        raise ValueError("warp_rgb: an offset above 2^29")
+    S = 1 << g
+    # the frame inside a border of the pad value: position (x, y) is padded[y + 1, x + 1], everything further out is the border too
+    padded = np.empty((H + 2, W + 2, 3), dtype=np.int64)
+    padded[:] = np.asarray(pad, dtype=np.int64)
+    padded[1:-1, 1:-1] = rgb[..., :3]
+
+    def p(x, y):
+        return padded[np.clip(y + 1, 0, H + 1), np.clip(x + 1, 0, W + 1)]
+    ox = np.arange(ow, dtype=np.int64)[None, :]
+    oy = np.arange(oh, dtype=np.int64)[:, None]
+    acc = np.zeros((oh, ow, 3), dtype=np.int64)
+    for j in range(S):
+        for i in range(S):
+            NX = a00 * (2 * S * ox + 2 * i + 1) + a01 * (2 * S * oy + 2 * j + 1) + 2 * S * (tx - 32768)
+            NY = a10 * (2 * S * ox + 2 * i + 1) + a11 * (2 * S * oy + 2 * j + 1) + 2 * S * (ty - 32768)
+            qx = ((NX >> (g + 1)) + 128) >> 8
+            qy = ((NY >> (g + 1)) + 128) >> 8
+            x0, fx, y0, fy = qx >> 8, (qx & 255)[..., None], qy >> 8, (qy & 255)[..., None]
+            acc += (256 - fx) * (256 - fy) * p(x0, y0) + fx * (256 - fy) * p(x0 + 1, y0) + (256 - fx) * fy * p(x0, y0 + 1) + fx * fy * p(x0 + 1, y0 + 1)
+    return ((acc + (1 << (15 + 2 * g))) >> (16 + 2 * g)).astype(np.uint8)
+
+
+def warp_matrix(A):
+    """leon_pipeline_warp_from_matrix: the Q16 words of A = (a00, a01, tx, a10, a11, ty) (or a 2 x 3 array), floor(v * 65536 + 0.5)"""
+    a = (C.c_double * 6)(*[float(v) for v in np.asarray(A, dtype=np.float64).ravel()])
+    m = (C.c_int32 * 6)()
+    _chk(load().leon_pipeline_warp_from_matrix(a, m))
+    return tuple(m)
+
+
+def warp_matrix_rotated_box(cx, cy, w, h, angle_degrees, size):
+    """leon_pipeline_warp_from_rotated_box: the Q16 words that fill size = (out_height, out_width) with the box of w x h frame pixels
+    centred at (cx, cy) and rotated by angle_degrees"""
+    m = (C.c_int32 * 6)()
+    _chk(load().leon_pipeline_warp_from_rotated_box(float(cx), float(cy), float(w), float(h), float(angle_degrees), int(size[1]), int(size[0]), m))
+    return tuple(m)
+
+
+def _warp_args(regions, size, pad_value):
+    """(PipelineWarpRegion array, n, PipelineWarpConfig) of a list of (frame_index, m) -- or PipelineWarpRegion structs -- and
+    or one int32 array [n, 8] of records -- and size = (out_height, out_width) -- or a PipelineWarpConfig"""
+    if isinstance(regions, np.ndarray):          # [n, 8] records: no Python loop over the regions
+        full = np.ascontiguousarray(regions, dtype=np.int32).reshape(-1, 8)
+        return (PipelineWarpRegion * max(1, len(full))).from_buffer_copy(full.tobytes() or bytes(32)), len(full), _warp_config(size, pad_value)
+    regions = list(regions)
+    arr = (PipelineWarpRegion * max(1, len(regions)))()
+    for i, r in enumerate(regions):
+        arr[i] = r if isinstance(r, PipelineWarpRegion) else PipelineWarpRegion(int(r[0]), (C.c_int32 * 6)(*[int(v) for v in r[1]]), 0)
+    return arr, len(regions), _warp_config(size, pad_value)
+
+
+def _warp_config(size, pad_value):
+    if isinstance(size, PipelineWarpConfig):
+        return size
+    cfg = PipelineWarpConfig(int(size[1]), int(size[0]))
+    if pad_value is not None:
+        r, g, b = pad_value
+        cfg.pad[0], cfg.pad[1], cfg.pad[2] = int(r), int(g), int(b)
+    return cfg
+
+
+def warp_regions_check(frame_width, frame_height, n_frames, regions, size, pad_value=None):
+    """leon_pipeline_warp_regions_check: what Pipeline.warp_regions would refuse of these regions (a list of (frame_index, m)), without
+    a device.  Returns None when they are accepted; raises LeonError otherwise, its `bad` the index of the first offending region."""
+    arr, n, cfg = _warp_args(regions, size, pad_value)
+    bad = C.c_int32(-2)
+    rc = load().leon_pipeline_warp_regions_check(int(frame_width), int(frame_height), int(n_frames), arr, n, C.byref(cfg), C.byref(bad))
+    if rc != OK:
+        e = LeonError(rc, load().leon_last_error().decode("utf-8", "replace"))
+        e.bad = bad.value
+        raise e
+
+
+def warp_region_status(frame_width, frame_height, n_frames, region, size, pad_value=None):
+    """leon_pipeline_warp_region_status: the REGION_* word Pipeline.warp_regions_device writes for region = (frame_index, m) (or a
+    PipelineWarpRegion).  No device."""
+    arr, _, cfg = _warp_args([region], size, pad_value)
+    st = load().leon_pipeline_warp_region_status(int(frame_width), int(frame_height), int(n_frames), arr, C.byref(cfg))
     if st < 0:
         raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
     return st
@@ -1153,6 +1277,73 @@ class Pipeline:
         else:
             _chk(self.lib.leon_pipeline_read_regions_fit(self.h, int(window), arr, n, C.byref(cfg), C.byref(f), out.ctypes.data))
         return out[:n]
+
+    def warp_regions(self, window, regions, size, pad_value=None, out=None, pitch=None):
+        """leon_pipeline_warp_regions: regions = [(frame_index, m), ...], m the six Q16 words of warp_matrix / warp_matrix_rotated_box,
+        of the delivered, not yet released `window` sampled along their affine maps into size = (h, w) -> a torch view [N, 3, h, w]
+        ("hwc": [N, h, w, 3]) as resample_regions builds it; out and pitch as there.  Positions outside the frame read pad_value =
+        (r, g, b) through the element table.  Synchronous.  Raises LeonError where the library refuses; nothing is written then."""
+        import torch
+        if not self.info.tensor_dtype:
+            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        arr, n, cfg = _warp_args(regions, size, pad_value)
+        nbytes, dflt = self.region_bytes((cfg.out_height, cfg.out_width))
+        step = dflt if pitch is None else int(pitch)
+        dev = self.device_id
+        if out is None:
+            out = torch.empty(max(1, n) * max(step, 1), dtype=torch.uint8, device="cuda:%d" % dev)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < (n - 1) * step + nbytes:
+            raise ValueError("out: a contiguous uint8 tensor of at least %d bytes" % ((n - 1) * step + nbytes))
+        torch.cuda.current_stream(dev).synchronize()          # (the library writes on a stream of its own: resample_regions)
+        _chk(self.lib.leon_pipeline_warp_regions(self.h, int(window), arr, n, C.byref(cfg), out.data_ptr(), 0 if pitch is None else step))
+        shape, strides = self._region_dims((cfg.out_height, cfg.out_width))
+        return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out)
+
+    def read_warp_regions(self, window, regions, size, pad_value=None):
+        """leon_pipeline_read_warp_regions: the same regions as a host array [N, 3, h, w] ("hwc": [N, h, w, 3]), packed, as read_regions"""
+        if not self.info.tensor_dtype:
+            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        arr, n, cfg = _warp_args(regions, size, pad_value)
+        out = np.empty((max(1, n),) + self._region_dims((cfg.out_height, cfg.out_width))[0], dtype=self._tensor_np_dtype())
+        _chk(self.lib.leon_pipeline_read_warp_regions(self.h, int(window), arr, n, C.byref(cfg), out.ctypes.data))
+        return out[:n]
+
+    def warp_regions_device(self, window, records, size, pad_value=None, out=None, pitch=None, status=None, stream=None):
+        """leon_pipeline_warp_regions_device: the same batch from records that lie in DEVICE memory -- a contiguous CUDA int32 torch
+        tensor [N, 8]: frame, a00, a01, tx, a10, a11, ty (Q16), 0 -- queued on `stream` (a torch.cuda.Stream; None: torch's current
+        stream) with resample_regions_device's ordering: NO host synchronisation.  Returns (batch, status): status an int32 tensor [N]
+        on the device, REGION_* per record -- 0: written; otherwise the region was skipped and its bytes of `out` are untouched."""
+        import torch
+        if not self.info.tensor_dtype:
+            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        dev = self.device_id
+        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.dtype == torch.int32 and records.dim() == 2 and records.shape[1] == 8
+                and records.is_contiguous()):
+            raise ValueError("records: a contiguous CUDA int32 tensor [N, 8]")
+        for name, t in (("records", records), ("out", out), ("status", status)):
+            if t is not None and (not t.is_cuda or t.device.index != dev):
+                raise ValueError("%s: on %s, the pipeline's device is cuda:%d" % (name, t.device, dev))
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        n = int(records.shape[0])
+        cfg = _warp_config(size, pad_value)
+        nbytes, dflt = self.region_bytes((cfg.out_height, cfg.out_width))
+        step = dflt if pitch is None else int(pitch)
+        with torch.cuda.stream(stream):
+            if out is None:
+                out = torch.empty(max(1, n) * max(step, 1), dtype=torch.uint8, device="cuda:%d" % dev)
+            elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < (n - 1) * step + nbytes:
+                raise ValueError("out: a contiguous uint8 tensor of at least %d bytes" % ((n - 1) * step + nbytes))
+            if status is None:
+                status = torch.empty(max(1, n), dtype=torch.int32, device="cuda:%d" % dev)
+            elif status.dtype != torch.int32 or not status.is_contiguous() or status.numel() < n:
+                raise ValueError("status: a contiguous int32 tensor of at least %d words" % n)
+        handle = int(stream.cuda_stream)
+        if not handle:
+            stream.synchronize()
+        call = PipelineWarpRegionsCall(records.data_ptr() if n else None, n, 0, out.data_ptr(), 0 if pitch is None else step, status.data_ptr(), handle or None)
+        _chk(self.lib.leon_pipeline_warp_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        shape, strides = self._region_dims((cfg.out_height, cfg.out_width))
+        return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out), status[:n]
 
     def _tensor_at(self, ptr, shape, strides, device_id=None, owner=None):
         import torch

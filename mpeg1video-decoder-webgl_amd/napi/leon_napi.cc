@@ -644,6 +644,49 @@ napi_value PipeReadRegions(napi_env env, napi_callback_info info)
     return rc == LEON_OK ? buf : throw_leon(env, rc);
 }
 
+// p.readWarpRegions(window, records, outHeight, outWidth, padR, padG, padB) -> Buffer of n * region bytes, packed:
+// leon_pipeline_read_warp_regions.  records: an Int32Array of n x [frame index, a00, a01, tx, a10, a11, ty] (Q16).
+napi_value PipeReadWarpRegions(napi_env env, napi_callback_info info)
+{
+    size_t argc = 7;
+    napi_value argv[7];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    leon_pipeline_warp_config cfg{};
+    napi_typedarray_type tt;
+    size_t len = 0, off = 0;
+    void* words = nullptr;
+    napi_value ab;
+    bool is_ta = false;
+    if (argc < 7 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta ||
+        napi_get_typedarray_info(env, argv[1], &tt, &len, &words, &ab, &off) != napi_ok || tt != napi_int32_array || len % 7 != 0 ||
+        napi_get_value_int32(env, argv[2], &cfg.out_height) != napi_ok || napi_get_value_int32(env, argv[3], &cfg.out_width) != napi_ok ||
+        napi_get_value_int32(env, argv[4], &cfg.pad[0]) != napi_ok || napi_get_value_int32(env, argv[5], &cfg.pad[1]) != napi_ok ||
+        napi_get_value_int32(env, argv[6], &cfg.pad[2]) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "readWarpRegions(window, Int32Array of [frame, a00, a01, tx, a10, a11, ty] per region, outHeight, outWidth, padR, padG, padB)");
+        return nullptr;
+    }
+    if (!h->info.tensor_dtype) {
+        napi_throw_error(env, nullptr, "readWarpRegions: the pipeline has no tensor output (opts.output)");
+        return nullptr;
+    }
+    const size_t n = len / 7;
+    std::vector<leon_pipeline_warp_region> regions(n ? n : 1);
+    const int32_t* b = static_cast<const int32_t*>(words);
+    for (size_t i = 0; i < n; i++)
+        regions[i] = leon_pipeline_warp_region{b[7 * i], {b[7 * i + 1], b[7 * i + 2], b[7 * i + 3], b[7 * i + 4], b[7 * i + 5], b[7 * i + 6]}, 0};
+    const int32_t oh = cfg.out_height, ow = cfg.out_width;
+    // (a size the library refuses allocates nothing here)
+    const bool sized = oh >= 1 && oh <= 4096 && ow >= 1 && ow <= 4096 && n >= 1 && n <= 65535;
+    const size_t bytes = sized ? n * 3 * (size_t)oh * (size_t)ow * (size_t)h->info.tensor_element_bytes : 0;
+    napi_value buf;
+    void* data = nullptr;
+    NAPI_OK(napi_create_buffer(env, bytes ? bytes : 1, &data, &buf));
+    const int rc = leon_pipeline_read_warp_regions(h->p, w, regions.data(), (int32_t)std::min<size_t>(n, 65536), &cfg, data);
+    return rc == LEON_OK ? buf : throw_leon(env, rc);
+}
+
 // opts[name] as three floats (an array of numbers); absent: zeros
 bool get_f32x3(napi_env env, napi_value opts, const char* name, float* out)
 {
@@ -904,7 +947,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readRegions", PipeReadRegions}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));

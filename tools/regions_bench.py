@@ -10,9 +10,12 @@ leon_pipeline_resample_regions_device too (k_box_tables + k_boxes per chunk; enq
 paths wrote the same bytes.  --fit letterbox times the SAME seeded boxes letterboxed into --size as well (leon_pipeline_regions_fit:
 k_fitted, and k_fit_tables on the device path), in the same process, a stretched and a letterboxed call alternating; the boxes whose
 height the frame clips are the ones that get pad.  With --device-boxes it also checks that both paths wrote the same letterboxed bytes.
+--warp times leon_pipeline_warp_regions and leon_pipeline_warp_regions_device (k_warp) in the same process on the same seeded boxes'
+centres and frames: every region a box of --scale times --size, rotated by --angle degrees about its centre (parts of it may leave
+the frame and read the pad), and checks that both paths wrote the same bytes.
 
   python tools/regions_bench.py [--regions 4096] [--size 224 224] [--calls 5] [--window 128] [--filter triangle] [--device-boxes]
-                                [--fit letterbox [--anchor centre|top_left] [--pad-value R G B]]"""
+                                [--fit letterbox [--anchor centre|top_left] [--pad-value R G B]] [--warp [--angle A] [--scale S]]"""
 import argparse
 import json
 import os
@@ -41,6 +44,9 @@ def main():
     ap.add_argument("--fit", choices=["stretch", "letterbox"], default="stretch", help="letterbox: the same boxes letterboxed too, alternating with the stretched calls")
     ap.add_argument("--anchor", choices=["centre", "top_left"], default="centre")
     ap.add_argument("--pad-value", type=int, nargs=3, default=[114, 114, 114], metavar=("R", "G", "B"))
+    ap.add_argument("--warp", action="store_true", help="also time the warp calls: boxes of --scale x --size about the same centres, rotated by --angle")
+    ap.add_argument("--angle", type=float, default=0.0, help="--warp: degrees")
+    ap.add_argument("--scale", type=float, default=1.0, help="--warp: frame pixels per output pixel, at most 4")
     a = ap.parse_args()
     fit = dict(fit="letterbox", anchor=a.anchor, pad_value=tuple(a.pad_value)) if a.fit == "letterbox" else None
     import numpy as np
@@ -115,12 +121,45 @@ def main():
                     p.resample_regions_device(window, dev_boxes, (oh, ow), a.filter, out=fbuf2, status=status, stream=st, **fit)
                     st.synchronize()
                     fit_dev_times.append(1e3 * (time.perf_counter() - t))
+        warp = None
+        if a.warp:
+            # leon_pipeline_warp_from_rotated_box's expressions for every region at once
+            cs, sn = np.cos(np.deg2rad(a.angle)), np.sin(np.deg2rad(a.angle))
+            A = np.array([a.scale * cs, -a.scale * sn, 0.0, a.scale * sn, a.scale * cs, 0.0])
+            cx, cy = x + w / 2.0, y + h / 2.0
+            rec = np.zeros((a.regions, 8), dtype=np.int32)
+            rec[:, 0] = boxes[:, 0]
+            rec[:, 1:7] = np.floor(A * 65536.0 + 0.5)
+            rec[:, 3] = np.floor((cx - (A[0] * ow / 2.0 + A[1] * oh / 2.0)) * 65536.0 + 0.5)
+            rec[:, 6] = np.floor((cy - (A[3] * ow / 2.0 + A[4] * oh / 2.0)) * 65536.0 + 0.5)
+            pad = tuple(a.pad_value)
+            wbuf, wbuf2 = torch.empty_like(buf), torch.empty_like(buf)
+            p.warp_regions(window, rec, (oh, ow), pad, out=wbuf)          # scratch reaches its high-water mark
+            st = torch.cuda.Stream()
+            with torch.cuda.stream(st):
+                dev_rec = torch.from_numpy(rec).cuda()
+                wstatus = torch.empty(a.regions, dtype=torch.int32, device="cuda:0")
+                p.warp_regions_device(window, dev_rec, (oh, ow), pad, out=wbuf2, status=wstatus)
+            st.synchronize()
+            warp = dict(angle=a.angle, scale=a.scale, device_equals_host=bool(torch.equal(wbuf, wbuf2)) and not bool(wstatus.any()), call_ms=[], device_call_ms=[],
+                        device_enqueue_ms=[])
+            for _ in range(a.calls):
+                t = time.perf_counter()
+                p.warp_regions(window, rec, (oh, ow), pad, out=wbuf)
+                warp["call_ms"].append(1e3 * (time.perf_counter() - t))
+                t = time.perf_counter()
+                p.warp_regions_device(window, dev_rec, (oh, ow), pad, out=wbuf2, status=wstatus, stream=st)
+                warp["device_enqueue_ms"].append(1e3 * (time.perf_counter() - t))
+                st.synchronize()
+                warp["device_call_ms"].append(1e3 * (time.perf_counter() - t))
+            warp["call_ms_mean"] = sum(warp["call_ms"]) / a.calls
+            warp["device_call_ms_mean"] = sum(warp["device_call_ms"]) / a.calls
         requested = int((w * h).sum() * 3 // 2)
         with lock:
             out.update(frames=n_frames, call_ms=times, regions_check_ms=check_ms, requested_bytes=requested, written_bytes=a.regions * nbytes,
                        mean_ratio_x=float((w / ow).mean()), mean_ratio_y=float((h / oh).mean()), device_call_ms=dev_times, device_enqueue_ms=dev_enqueue,
                        device_equals_host=same, fit=a.fit, fit_call_ms=fit_times or None, fit_device_call_ms=fit_dev_times or None,
-                       fit_device_equals_host=fit_same, fit_regions_with_pad=padded)
+                       fit_device_equals_host=fit_same, fit_regions_with_pad=padded, warp=warp)
     pipe = L.Pipeline(data, parser_threads=16, gops_per_window=a.window, windows_in_flight=2, loop=a.window * a.windows // 2, gpu_parser=True, output="tensor",
                       tensor_dtype=a.tensor_dtype, tensor_layout=a.tensor_layout, tensor_size=(oh, ow), tensor_filter=a.filter, on_window=on_window)
     try:
