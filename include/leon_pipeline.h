@@ -455,7 +455,7 @@ int leon_pipeline_read_regions(leon_pipeline* p, int64_t window, const leon_pipe
  * of the filter's worst case for the out size, 4 * (2 * ow + ow * T + 2 * oh + oh * T) bytes with T = 33 (triangle) or 65 (bicubic);
  * the limit bounds a chunk's descriptors and slots, beside which the allocation holds the window's frame ids (4 bytes a frame), each of
  * the three parts rounded up to 256 bytes, and is never smaller than 1 MiB --
- * one k_box_tables and one k_boxes<element bytes, layout, filter> launch per chunk, in stream order over the same memory: the scratch is
+ * one k_box_tables and one k_regions<element bytes, layout, filter> launch per chunk, in stream order over the same memory: the scratch is
  * bounded whatever n is (no 4 GiB rule here).  It belongs to the pipeline and grows to its high-water mark.  Every call records an event
  * behind its last launch and the next call's stream waits for that event on the device before its first, so calls on different
  * streams never share the scratch at once; growing it, and leon_pipeline_destroy, wait for the event on the host.  Concurrent calls are
@@ -515,7 +515,7 @@ int32_t leon_pipeline_region_status(int32_t frame_width, int32_t frame_height, i
  * meant).
  * Refused with LEON_ERR_INVALID: another mode or anchor, a pad value outside 0 .. 255, a non-zero reserved word, a non-zero anchor or
  * pad under LEON_REGIONS_FIT_STRETCH.  fit NULL or all zero is the call without a fit: the same tensors from the same kernels
- * (k_regions / k_boxes), the rectangle of every region (0, 0, cw, ch). */
+ * (k_regions on both roads), the rectangle of every region (0, 0, cw, ch). */
 #define LEON_REGIONS_FIT_STRETCH      0
 #define LEON_REGIONS_FIT_LETTERBOX    1
 #define LEON_REGIONS_ANCHOR_CENTRE    0

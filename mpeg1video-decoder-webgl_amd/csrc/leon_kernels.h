@@ -1972,7 +1972,7 @@ __device__ __forceinline__ int32_t resample_mad(int32_t w, uint32_t sample, int3
 // In a canvas (`C`: ImageIsTensor or CanvasGeom) only the store addresses move: the tiles are numbered from the image's origin, a
 // tile row still stores the bytes of [g0, g1) and nothing else, its row stride and plane size are the canvas's.
 // Where a workgroup's frame and tensor lie (`W`) is asked once, behind the table loads.  RingFrame: frame_ids[blockIdx.z] of the
-// pipeline's rings (k_resample, k_letterbox).  RegionFrame: the two addresses k_regions has read from its region's descriptor.
+// pipeline's rings (k_resample, k_letterbox).  RegionFrame: the two addresses k_regions / k_fitted made from the region's descriptor.
 struct FramePair {
     const uint8_t* src;
     uint8_t* dst;
@@ -2181,13 +2181,14 @@ __global__ __launch_bounds__(kRgbaBlock) void k_resample(const uint8_t* __restri
 // constants a region has of its own -- the source frame, the destination, the tables of its box with their row lengths -- and a
 // workgroup reads it from the region's descriptor (one address per workgroup: scalar loads), then runs resample_body.  Each region's
 // tables are laid out as plan_resize lays out a pipeline's, `rt_base` int32 words into the call's table buffer.
+// One family for both roads: the host writes descriptors whose status is 0, k_box_tables one of kRegion*.
 struct RegionDesc {
     uint32_t frame_id;                   // index into the planes ring
     uint32_t rt_base;                    // int32 offset of the region's first_x in the table buffer
     uint32_t off_cx, off_wx, off_fy, off_cy, off_wy;          // as ResampleGeom's, from rt_base
     int32_t taps_x, taps_y;              // row lengths of this region's weight tables (taps_x odd)
     uint32_t dst_lo, dst_hi;             // byte offset of the region's tensor in the caller's buffer: index * pitch
-    int32_t status;                      // 0 on the host path; k_box_tables: kRegion* (non-zero: k_boxes leaves the region alone)
+    int32_t status;                      // 0 on the host road; k_box_tables: kRegion* (non-zero: the region's workgroups leave at once)
     int32_t iw, ih, ix, iy;              // k_fitted only: the region's image, iw x ih at (ix, iy) of its tensor (0 where the image is the tensor)
 };                                       // 64 bytes
 template <int EB, int LAYOUT, class F>
@@ -2196,6 +2197,7 @@ __global__ __launch_bounds__(kRgbaBlock) void k_regions(const uint8_t* __restric
                                                         ResampleGeom G)
 {
     const RegionDesc& d = descs[blockIdx.z];
+    if (d.status != kRegionOk) return;   // a refused region stores nothing anywhere
     G.taps_x = d.taps_x; G.taps_y = d.taps_y;
     G.off_cx = d.off_cx; G.off_wx = d.off_wx; G.off_fy = d.off_fy; G.off_cy = d.off_cy; G.off_wy = d.off_wy;
     const RegionFrame where{FramePair{planes_ring + (size_t)d.frame_id * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi), out + join64(d.dst_lo, d.dst_hi)}};
@@ -2204,8 +2206,8 @@ __global__ __launch_bounds__(kRgbaBlock) void k_regions(const uint8_t* __restric
 
 // ---- regions whose boxes lie in device memory (leon_pipeline.h, leon_pipeline_resample_regions_device) -------------------
 // Behind a detector that ran on the GPU nothing about a box is known on the host.  Per chunk of regions two launches in stream order
-// over one scratch: k_box_tables judges each region and writes its descriptor and tables, k_boxes<EB, LAYOUT, F> is k_regions behind
-// the descriptor's status word.
+// over one scratch: k_box_tables judges each region and writes its descriptor and tables, k_regions<EB, LAYOUT, F> runs behind the
+// descriptor's status word.
 // k_box_tables: one workgroup per region.  The region's record is one address per workgroup (scalar loads); its status is
 // region_axis_status and the rows' tap counts, which the workgroup reduces first (a lane takes every 256th output sample of both
 // axes; two LDS words) -- the row length of a table is the largest count of its rows and has to be known before a weight is stored.
@@ -2214,7 +2216,7 @@ __global__ __launch_bounds__(kRgbaBlock) void k_regions(const uint8_t* __restric
 // for the out size, so no prefix sum and nothing read back).  A lane builds whole rows: the sum in index order first, then the
 // weights from the same expressions once more (leon_resize_row.h; no array of doubles per lane).  fp64 throughout, a division per tap
 // and another per weight, a row's words stored by one lane: measured, 4096 regions of 224 x 224 (triangle, ratio 1 .. 8) take 0.09 -
-// 0.16 ms, a hundredth of the k_boxes launch behind it.
+// 0.16 ms, a hundredth of the k_regions launch behind it.
 struct BoxRecord {                       // = leon_pipeline_region
     int32_t frame, x, y, width, height, reserved[3];
 };
@@ -2357,19 +2359,6 @@ __global__ __launch_bounds__(kRgbaBlock) void k_axis_tables(const AxisRecord* __
     const size_t at = (size_t)i * (size_t)max_out;
     for (int32_t o = (int32_t)threadIdx.x; o < a.out_size; o += kRgbaBlock)
         box_axis_row(A, o, first + at, count + at, weights + (at + (size_t)o) * (size_t)max_taps, max_taps);
-}
-// k_regions behind the status test: a refused region stores nothing anywhere
-template <int EB, int LAYOUT, class F>
-__global__ __launch_bounds__(kRgbaBlock) void k_boxes(const uint8_t* __restrict__ planes_ring, uint8_t* __restrict__ out, const RegionDesc* __restrict__ descs,
-                                                      const uint32_t* __restrict__ table, const Tables* __restrict__ T, const int32_t* __restrict__ tabs,
-                                                      ResampleGeom G)
-{
-    const RegionDesc& d = descs[blockIdx.z];
-    if (d.status != kRegionOk) return;
-    G.taps_x = d.taps_x; G.taps_y = d.taps_y;
-    G.off_cx = d.off_cx; G.off_wx = d.off_wx; G.off_fy = d.off_fy; G.off_cy = d.off_cy; G.off_wy = d.off_wy;
-    const RegionFrame where{FramePair{planes_ring + (size_t)d.frame_id * join64(G.ring.planes_pitch_lo, G.ring.planes_pitch_hi), out + join64(d.dst_lo, d.dst_hi)}};
-    resample_body<EB, LAYOUT, F>(where, table, T, tabs + d.rt_base, G, ImageIsTensor{});
 }
 
 // ---- the resampled image in a padded canvas (leon_pipeline.h, leon_pipeline_tensor_canvas) ------------------------------

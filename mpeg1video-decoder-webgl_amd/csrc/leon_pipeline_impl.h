@@ -741,6 +741,19 @@ int resize_footprint_check(const int32_t* t, const leon::ResampleGeom& G, int32_
     return LEON_OK;
 }
 
+// The tables of an image ow x oh in one buffer: first_x | count_x | Wx | first_y | count_y | Wy, rows of taps_x and taps_y words (zero
+// behind count[o]).  Fills G's row lengths and off_* and returns the int32 words of the whole; box_tables_body is the device's statement.
+size_t resize_tables_layout(int32_t ow, int32_t oh, int32_t taps_x, int32_t taps_y, leon::ResampleGeom* G)
+{
+    G->taps_x = taps_x; G->taps_y = taps_y;
+    G->off_cx = (uint32_t)ow;
+    G->off_wx = G->off_cx + (uint32_t)ow;
+    G->off_fy = G->off_wx + (uint32_t)ow * (uint32_t)taps_x;
+    G->off_cy = G->off_fy + (uint32_t)oh;
+    G->off_wy = G->off_cy + (uint32_t)oh;
+    return (size_t)G->off_wy + (size_t)oh * (size_t)taps_y;
+}
+
 // What create makes of the resize settings: the geometry in force, the table buffer and k_resample's constants
 int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
 {
@@ -765,13 +778,7 @@ int plan_resize(leon_pipeline* p, const leon_pipeline_tensor_resize* rz)
     // rows of Wx are an odd number of entries long (zero behind count[o]): the horizontal pass's lanes are output columns and read
     // Wx[o][k] for one k together -- 32 entries a row (ratio 16) would put them all on one LDS bank, 18 (1080p -> 224) on every other
     // (bicubic: up to 65, odd as well)
-    G.taps_x = g.taps_x | 1; G.taps_y = g.taps_y;
-    G.off_cx = (uint32_t)g.width;
-    G.off_wx = G.off_cx + (uint32_t)g.width;
-    G.off_fy = G.off_wx + (uint32_t)g.width * (uint32_t)G.taps_x;
-    G.off_cy = G.off_fy + (uint32_t)g.height;
-    G.off_wy = G.off_cy + (uint32_t)g.height;
-    p->resize_tabs.assign((size_t)G.off_wy + (size_t)g.height * g.taps_y, 0);
+    p->resize_tabs.assign(resize_tables_layout(g.width, g.height, g.taps_x | 1, g.taps_y, &G), 0);
     int32_t* t = p->resize_tabs.data();
     if ((rc = resize_axis_build("width", fw, g.crop_x, g.crop_width, g.width, rz->filter, t, t + G.off_cx, t + G.off_wx, G.taps_x, nullptr)) != LEON_OK) return rc;
     if ((rc = resize_axis_build("height", fh, g.crop_y, g.crop_height, g.height, rz->filter, t + G.off_fy, t + G.off_cy, t + G.off_wy, g.taps_y, nullptr)) != LEON_OK) return rc;
@@ -1436,34 +1443,25 @@ int regions_check(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_
     return LEON_OK;
 }
 
-// the call's scratch, grown and never shrunk (regions_mu held; the regions stream is idle between calls)
+// one buffer of a call's scratch, grown to half again what is asked and never shrunk
+template <class T> int regions_grow(T** buf, size_t* cap_now, size_t bytes, bool pinned, const char* what)
+{
+    if (bytes <= *cap_now) return LEON_OK;
+    const size_t cap = std::max(bytes + bytes / 2, (size_t)1 << 20);
+    void* m = nullptr;
+    if ((pinned ? hipHostMalloc(&m, cap, hipHostMallocDefault) : big_alloc(&m, cap, kBigCaller)) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes %s", cap, what); }
+    if (*buf) (void)(pinned ? hipHostFree(*buf) : big_free(*buf));
+    *buf = static_cast<T*>(m);
+    *cap_now = cap;
+    return LEON_OK;
+}
+// the host roads' scratch (regions_mu held; the regions stream is idle between calls)
 int regions_reserve(leon_pipeline* p, size_t upload_bytes, size_t out_bytes)
 {
-    if (upload_bytes > p->regions_host_cap) {
-        const size_t cap = std::max(upload_bytes + upload_bytes / 2, (size_t)1 << 20);
-        char* h = nullptr;
-        if (hipHostMalloc((void**)&h, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of pinned staging", cap); }
-        if (p->regions_host) hipHostFree(p->regions_host);
-        p->regions_host = h;
-        p->regions_host_cap = cap;
-    }
-    if (upload_bytes > p->regions_dev_cap) {
-        const size_t cap = std::max(upload_bytes + upload_bytes / 2, (size_t)1 << 20);
-        char* dv = nullptr;
-        if (big_alloc((void**)&dv, cap, kBigCaller) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of device scratch", cap); }
-        if (p->regions_dev) big_free(p->regions_dev);
-        p->regions_dev = dv;
-        p->regions_dev_cap = cap;
-    }
-    if (out_bytes > p->regions_out_cap) {
-        const size_t cap = std::max(out_bytes + out_bytes / 2, (size_t)1 << 20);
-        uint8_t* dv = nullptr;
-        if (big_alloc((void**)&dv, cap, kBigCaller) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes for the tensors", cap); }
-        if (p->regions_out) big_free(p->regions_out);
-        p->regions_out = dv;
-        p->regions_out_cap = cap;
-    }
-    return LEON_OK;
+    int rc;
+    if ((rc = regions_grow(&p->regions_host, &p->regions_host_cap, upload_bytes, true, "of pinned staging")) != LEON_OK) return rc;
+    if ((rc = regions_grow(&p->regions_dev, &p->regions_dev_cap, upload_bytes, false, "of device scratch")) != LEON_OK) return rc;
+    return regions_grow(&p->regions_out, &p->regions_out_cap, out_bytes, false, "for the tensors");
 }
 
 // the ring ids of a delivered window's frames: p->mu is held for the look-up and the copy only (the notify thread and release_window need it)
@@ -1480,128 +1478,156 @@ int regions_window_ids(leon_pipeline* p, int64_t window, std::vector<uint32_t>* 
     return LEON_OK;
 }
 
-// One call: refusals, the regions' descriptors and tables into pinned staging, one upload, one launch, the wait -- all on the
-// pipeline's regions stream.  device_out NULL with `host`: into the pooled scratch at the default pitch, then packed to the host.
-int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
-                     const leon_pipeline_regions_fit* fit_settings, void* device_out, uint64_t out_pitch, void* host)
+// ---- what the four roads share (stretch / fit and warp, each from host records and from device records) --------------------------
+// the pipeline of a call: one with tensors, of an element size and layout the kernel tables list (create admits no other)
+int regions_pipeline_check(const leon_pipeline* p)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
-    RegionsFit fit;
-    int frc = regions_fit_check(fit_settings, &fit);
-    if (frc != LEON_OK) return frc;
     if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR) || !p->d_tensor || !p->d_planes)
         return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
-    std::lock_guard<std::mutex> call(p->regions_mu);
-    std::vector<uint32_t> ids;
-    int rc = regions_window_ids(p, window, &ids);
-    if (rc != LEON_OK) return rc;
-    std::vector<RegionTaps> taps;
-    const int32_t fw = p->vinfo.frame_width, fh = p->vinfo.frame_height;
-    rc = regions_check(fw, fh, (int32_t)ids.size(), regions, n, cfg, fit, nullptr, &taps);
-    if (rc != LEON_OK) return rc;
-    const int32_t ow = cfg->out_width, oh = cfg->out_height, filter = cfg->filter;
-    const size_t region_bytes = (size_t)3 * oh * ow * p->tensor_elem;
-    if (host) { device_out = nullptr; out_pitch = 0; }
-    else {
-        if (!device_out) return fail(LEON_ERR_INVALID, "regions: null device_out");
-        if ((uintptr_t)device_out & 255u) return fail(LEON_ERR_INVALID, "regions: device_out %p is not 256-byte aligned", device_out);
-    }
-    if (out_pitch && (out_pitch % 256 || out_pitch < region_bytes))
-        return fail(LEON_ERR_INVALID, "regions: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", (unsigned long long)out_pitch, region_bytes);
-    const size_t pitch = out_pitch ? (size_t)out_pitch : pad256(region_bytes);
     const int eb = (int)p->tensor_elem, layout = p->tensor_layout;
-    const bool listed = (eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc);
-    const RegionsKernel kr = listed ? kRegionsKernels[filter].k[eb >> 1][layout] : nullptr;
-    const FittedKernel kf = listed ? kFittedKernels[filter].k[eb >> 1][layout] : nullptr;
-    if (!kr || !kf) return fail(LEON_ERR_INVALID, "regions: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
+    if (!((eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc)))
+        return fail(LEON_ERR_INVALID, "regions: no kernel for %d-byte elements, layout %d", eb, layout);
+    return LEON_OK;
+}
+// ... and its kernel of a family, by filter (the config checks admit the two that have kernels), element bytes and layout
+template <class T> auto regions_kernel(const T (&family)[4], const leon_pipeline* p, int32_t filter) { return family[filter].k[p->tensor_elem >> 1][p->tensor_layout]; }
 
-    // [descriptors | tables]: a region's tables as plan_resize lays out a pipeline's, rows of its own tap counts -- and, letterboxed,
-    // of its own image size
-    const size_t desc_bytes = pad256((size_t)n * sizeof(leon::RegionDesc));
-    size_t words = 0;
-    for (int32_t i = 0; i < n; i++) {
-        const leon::FitRect image = region_image(regions[i], *cfg, fit);
-        words += 2 * (size_t)image.ow + (size_t)image.ow * (size_t)(taps[(size_t)i].x | 1) + 2 * (size_t)image.oh + (size_t)image.oh * (size_t)taps[(size_t)i].y;
-    }
-    if (words >= ((size_t)1 << 32)) return fail(LEON_ERR_INVALID, "regions: the tables of %d regions take %zu bytes (4 GiB a call at most)", n, words * 4);
-    const size_t upload_bytes = desc_bytes + words * 4;
+// the caller's buffer; *pitch: the bytes from one region's tensor to the next
+int regions_out_check(const char* who, const void* device_out, uint64_t out_pitch, size_t region_bytes, uint64_t* pitch)
+{
+    if (!device_out) return fail(LEON_ERR_INVALID, "%s: null device_out", who);
+    if ((uintptr_t)device_out & 255u) return fail(LEON_ERR_INVALID, "%s: device_out %p is not 256-byte aligned", who, device_out);
+    if (out_pitch && (out_pitch % 256 || out_pitch < region_bytes))
+        return fail(LEON_ERR_INVALID, "%s: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", who, (unsigned long long)out_pitch, region_bytes);
+    *pitch = out_pitch ? out_pitch : (uint64_t)pad256(region_bytes);
+    return LEON_OK;
+}
+
+// the stream a call enqueues on: the caller's, or (NULL) the pipeline's regions stream, made at first use
+int regions_call_stream(leon_pipeline* p, void* caller_stream, hipStream_t* st)
+{
     HIP_TRY(hipSetDevice(p->cfg.device_id));
-    if (!p->regions_stream) HIP_TRY(hipStreamCreateWithFlags(&p->regions_stream, hipStreamNonBlocking));
-    if ((rc = regions_reserve(p, upload_bytes, host ? (size_t)n * pitch : 0)) != LEON_OK) return rc;
-    leon::RegionDesc* descs = reinterpret_cast<leon::RegionDesc*>(p->regions_host);
-    int32_t* tabs = reinterpret_cast<int32_t*>(p->regions_host + desc_bytes);
-    leon::ResampleGeom G{};
-    G.fw = fw; G.fh = fh; G.ow = ow; G.oh = oh;
-    size_t at = 0;
-    for (int32_t i = 0; i < n; i++) {
-        const leon_pipeline_region& r = regions[i];
-        const leon::FitRect image = region_image(r, *cfg, fit);
-        const int32_t iw = image.ow, ih = image.oh;
-        leon::ResampleGeom R = G;
-        R.ow = iw; R.oh = ih;
-        R.taps_x = taps[(size_t)i].x | 1; R.taps_y = taps[(size_t)i].y;          // (odd rows of Wx: plan_resize says why)
-        R.off_cx = (uint32_t)iw;
-        R.off_wx = R.off_cx + (uint32_t)iw;
-        R.off_fy = R.off_wx + (uint32_t)iw * (uint32_t)R.taps_x;
-        R.off_cy = R.off_fy + (uint32_t)ih;
-        R.off_wy = R.off_cy + (uint32_t)ih;
-        int32_t* t = tabs + at;
-        if ((rc = resize_axis_build("width", fw, r.x, r.width, iw, filter, t, t + R.off_cx, t + R.off_wx, R.taps_x, nullptr)) != LEON_OK ||
-            (rc = resize_axis_build("height", fh, r.y, r.height, ih, filter, t + R.off_fy, t + R.off_cy, t + R.off_wy, R.taps_y, nullptr)) != LEON_OK ||
-            (rc = resize_footprint_check(t, R, filter)) != LEON_OK) {
-            const std::string why = g_err;
-            return fail(rc, "region %d: %s", i, why.c_str());
-        }
-        leon::RegionDesc d{};
-        d.frame_id = ids[(size_t)r.frame];
-        d.rt_base = (uint32_t)at;
-        d.off_cx = R.off_cx; d.off_wx = R.off_wx; d.off_fy = R.off_fy; d.off_cy = R.off_cy; d.off_wy = R.off_wy;
-        d.taps_x = R.taps_x; d.taps_y = R.taps_y;
-        const uint64_t dst = (uint64_t)i * pitch;
-        d.dst_lo = (uint32_t)(dst & 0xffffffffu); d.dst_hi = (uint32_t)(dst >> 32);
-        if (fit.letterbox) { d.iw = iw; d.ih = ih; d.ix = image.x; d.iy = image.y; }
-        descs[i] = d;
-        at += (size_t)R.off_wy + (size_t)ih * (size_t)R.taps_y;
-    }
+    if (!caller_stream && !p->regions_stream) HIP_TRY(hipStreamCreateWithFlags(&p->regions_stream, hipStreamNonBlocking));
+    *st = caller_stream ? static_cast<hipStream_t>(caller_stream) : p->regions_stream;
+    return LEON_OK;
+}
+
+// The tail of a host road, all on the regions stream `st`: the staging uploaded, the road's launch, the tensors packed to `host` when
+// they went into the pooled scratch, the wait.  launch(out) enqueues on `st` and returns nothing: its error is asked here.
+template <class Launch>
+int regions_host_run(leon_pipeline* p, hipStream_t st, size_t upload_bytes, void* host, void* device_out, size_t pitch, size_t region_bytes, int32_t n, Launch launch)
+{
     uint8_t* out = host ? p->regions_out : static_cast<uint8_t*>(device_out);
-    hipStream_t st = p->regions_stream;
     HIP_TRY(hipMemcpyAsync(p->regions_dev, p->regions_host, upload_bytes, hipMemcpyHostToDevice, st));
-    G.ring = ring_geom(p);
-    const unsigned gx = (unsigned)((ow + leon::kResTileX - 1) / leon::kResTileX), gy = (unsigned)((oh + leon::kResTileY - 1) / leon::kResTileY);
-    const unsigned gy_fit = gy + fitted_pad_rows(region_bytes, gx);
-    if (fit.letterbox && gy_fit > 65535u) return fail(LEON_ERR_INVALID, "regions fit: %u workgroup rows", gy_fit);
-    const leon::RegionDesc* d_descs = reinterpret_cast<const leon::RegionDesc*>(p->regions_dev);
-    for (size_t first = 0; first < (size_t)n; first += 65535) {          // (blockIdx.z; one launch: n <= 65535)
-        const dim3 grid(gx, fit.letterbox ? gy_fit : gy, (unsigned)std::min<size_t>(65535, (size_t)n - first)), block(leon::kRgbaBlock);
-        if (fit.letterbox)
-            hipLaunchKernelGGL(kf, grid, block, 0, st, (const uint8_t*)p->d_planes, out, d_descs + first, (const uint32_t*)p->d_tensor_table,
-                               (const leon::Tables*)p->dec->d_tables, reinterpret_cast<const int32_t*>(p->regions_dev + desc_bytes), G, fit.pad);
-        else
-            hipLaunchKernelGGL(kr, grid, block, 0, st, (const uint8_t*)p->d_planes, out, d_descs + first, (const uint32_t*)p->d_tensor_table,
-                               (const leon::Tables*)p->dec->d_tables, reinterpret_cast<const int32_t*>(p->regions_dev + desc_bytes), G);
-    }
+    launch(out);
     HIP_TRY(hipGetLastError());
     if (host) HIP_TRY(hipMemcpy2DAsync(host, region_bytes, out, pitch, region_bytes, (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return LEON_OK;
 }
 
+// the grid of m regions: the out size's tiles and, letterboxed, the pad's rows behind them
+dim3 regions_grid(int32_t ow, int32_t oh, size_t region_bytes, bool letterbox, unsigned m)
+{
+    const unsigned gx = (unsigned)((ow + leon::kResTileX - 1) / leon::kResTileX), gy = (unsigned)((oh + leon::kResTileY - 1) / leon::kResTileY);
+    return dim3(gx, letterbox ? gy + fitted_pad_rows(region_bytes, gx) : gy, m);
+}
+// the launch both roads share: descriptors and the tables they point into, in device memory -- k_regions, letterboxed k_fitted
+void regions_launch(leon_pipeline* p, hipStream_t st, const RegionsFit& fit, int32_t filter, const leon::ResampleGeom& G, dim3 grid, uint8_t* out,
+                    const leon::RegionDesc* d_descs, const int32_t* d_tabs)
+{
+    const dim3 block(leon::kRgbaBlock);
+    if (fit.letterbox)
+        hipLaunchKernelGGL(regions_kernel(kFittedKernels, p, filter), grid, block, 0, st, (const uint8_t*)p->d_planes, out, d_descs, (const uint32_t*)p->d_tensor_table,
+                           (const leon::Tables*)p->dec->d_tables, d_tabs, G, fit.pad);
+    else
+        hipLaunchKernelGGL(regions_kernel(kRegionsKernels, p, filter), grid, block, 0, st, (const uint8_t*)p->d_planes, out, d_descs, (const uint32_t*)p->d_tensor_table,
+                           (const leon::Tables*)p->dec->d_tables, d_tabs, G);
+}
+
+// One call: refusals, the regions' descriptors and tables into pinned staging, then regions_host_run.  device_out NULL with `host`:
+// into the pooled scratch at the default pitch, then packed to the host.
+int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_region* regions, int32_t n, const leon_pipeline_regions_config* cfg,
+                     const leon_pipeline_regions_fit* fit_settings, void* device_out, uint64_t out_pitch, void* host)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    RegionsFit fit;
+    int rc = regions_fit_check(fit_settings, &fit);
+    if (rc != LEON_OK || (rc = regions_pipeline_check(p)) != LEON_OK) return rc;
+    std::lock_guard<std::mutex> call(p->regions_mu);
+    std::vector<uint32_t> ids;
+    if ((rc = regions_window_ids(p, window, &ids)) != LEON_OK) return rc;
+    std::vector<RegionTaps> taps;
+    const int32_t fw = p->vinfo.frame_width, fh = p->vinfo.frame_height;
+    if ((rc = regions_check(fw, fh, (int32_t)ids.size(), regions, n, cfg, fit, nullptr, &taps)) != LEON_OK) return rc;
+    const int32_t ow = cfg->out_width, oh = cfg->out_height, filter = cfg->filter;
+    const size_t region_bytes = (size_t)3 * oh * ow * p->tensor_elem;
+    uint64_t pitch = pad256(region_bytes);
+    if (!host && (rc = regions_out_check("regions", device_out, out_pitch, region_bytes, &pitch)) != LEON_OK) return rc;
+
+    // [descriptors | tables]: a region's tables as plan_resize lays out a pipeline's, rows of its own tap counts -- and, letterboxed,
+    // of its own image size
+    const size_t desc_bytes = pad256((size_t)n * sizeof(leon::RegionDesc));
+    leon::ResampleGeom G{};
+    G.fw = fw; G.fh = fh; G.ow = ow; G.oh = oh;
+    G.ring = ring_geom(p);
+    size_t words = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const leon::FitRect image = region_image(regions[i], *cfg, fit);
+        leon::ResampleGeom R;
+        words += resize_tables_layout(image.ow, image.oh, taps[(size_t)i].x | 1, taps[(size_t)i].y, &R);          // (odd rows of Wx: plan_resize says why)
+    }
+    if (words >= ((size_t)1 << 32)) return fail(LEON_ERR_INVALID, "regions: the tables of %d regions take %zu bytes (4 GiB a call at most)", n, words * 4);
+    const size_t upload_bytes = desc_bytes + words * 4;
+    hipStream_t st;
+    if ((rc = regions_call_stream(p, nullptr, &st)) != LEON_OK || (rc = regions_reserve(p, upload_bytes, host ? (size_t)n * pitch : 0)) != LEON_OK) return rc;
+    leon::RegionDesc* descs = reinterpret_cast<leon::RegionDesc*>(p->regions_host);
+    int32_t* tabs = reinterpret_cast<int32_t*>(p->regions_host + desc_bytes);
+    size_t at = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const leon_pipeline_region& r = regions[i];
+        const leon::FitRect image = region_image(r, *cfg, fit);
+        leon::ResampleGeom R = G;
+        R.ow = image.ow; R.oh = image.oh;
+        const size_t region_words = resize_tables_layout(image.ow, image.oh, taps[(size_t)i].x | 1, taps[(size_t)i].y, &R);
+        int32_t* t = tabs + at;
+        if ((rc = resize_axis_build("width", fw, r.x, r.width, image.ow, filter, t, t + R.off_cx, t + R.off_wx, R.taps_x, nullptr)) != LEON_OK ||
+            (rc = resize_axis_build("height", fh, r.y, r.height, image.oh, filter, t + R.off_fy, t + R.off_cy, t + R.off_wy, R.taps_y, nullptr)) != LEON_OK ||
+            (rc = resize_footprint_check(t, R, filter)) != LEON_OK) {
+            const std::string why = g_err;
+            return fail(rc, "region %d: %s", i, why.c_str());
+        }
+        leon::RegionDesc d{};          // (status 0: kRegionOk)
+        d.frame_id = ids[(size_t)r.frame];
+        d.rt_base = (uint32_t)at;
+        d.off_cx = R.off_cx; d.off_wx = R.off_wx; d.off_fy = R.off_fy; d.off_cy = R.off_cy; d.off_wy = R.off_wy;
+        d.taps_x = R.taps_x; d.taps_y = R.taps_y;
+        const uint64_t dst = (uint64_t)i * pitch;
+        d.dst_lo = (uint32_t)(dst & 0xffffffffu); d.dst_hi = (uint32_t)(dst >> 32);
+        if (fit.letterbox) { d.iw = image.ow; d.ih = image.oh; d.ix = image.x; d.iy = image.y; }
+        descs[i] = d;
+        at += region_words;
+    }
+    const dim3 grid = regions_grid(ow, oh, region_bytes, fit.letterbox, (unsigned)n);          // (blockIdx.z; one launch: n <= 65535)
+    if (grid.y > 65535u) return fail(LEON_ERR_INVALID, "regions fit: %u workgroup rows", grid.y);
+    return regions_host_run(p, st, upload_bytes, host, device_out, (size_t)pitch, region_bytes, n, [&](uint8_t* out) {
+        regions_launch(p, st, fit, filter, G, grid, out, reinterpret_cast<const leon::RegionDesc*>(p->regions_dev), reinterpret_cast<const int32_t*>(p->regions_dev + desc_bytes));
+    });
+}
+
 // ---- regions whose boxes lie in device memory (leon_pipeline_resample_regions_device) -----------------------------------
-template <class F> constexpr RegionsKernelsOfFilter kBoxesKernelsOfFilter = {{{leon::k_boxes<1, leon::kLayoutChw, F>, leon::k_boxes<1, leon::kLayoutHwc, F>},
-                                                                              {leon::k_boxes<2, leon::kLayoutChw, F>, leon::k_boxes<2, leon::kLayoutHwc, F>},
-                                                                              {leon::k_boxes<4, leon::kLayoutChw, F>, leon::k_boxes<4, leon::kLayoutHwc, F>}}};
-constexpr RegionsKernelsOfFilter kBoxesKernels[4] = {kBoxesKernelsOfFilter<leon::ResTriangle>, {}, {}, kBoxesKernelsOfFilter<leon::ResCubic>};
 static_assert(sizeof(leon::BoxRecord) == sizeof(leon_pipeline_region) && sizeof(leon_pipeline_regions_device) == 64, "include/leon_pipeline.h states the sizes");
 static_assert(leon::kRegionOk == LEON_REGION_OK && leon::kRegionReserved == LEON_REGION_RESERVED && leon::kRegionFrame == LEON_REGION_FRAME &&
               leon::kRegionBox == LEON_REGION_BOX && leon::kRegionRatioX == LEON_REGION_RATIO_X && leon::kRegionRatioY == LEON_REGION_RATIO_Y &&
               leon::kRegionTaps == LEON_REGION_TAPS, "the kernels' codes are the header's");
 static_assert(leon::kResizeMaxTapsTriangle == LEON_RESIZE_MAX_TAPS && leon::kResizeMaxTapsCubic == LEON_RESIZE_MAX_TAPS_BICUBIC, "one limit");
 
-// int32 words of a region's table slot: the filter's worst case for the out size (rows of Wx are an odd number of words: both maxima are odd)
+// int32 words of a region's table slot: the layout at the filter's worst case for the out size (rows of Wx are an odd number of words: both maxima are odd)
 size_t boxes_slot_words(int32_t ow, int32_t oh, int32_t filter)
 {
-    const size_t t = (size_t)resize_filter_max_taps(filter);
-    return 2 * (size_t)ow + (size_t)ow * t + 2 * (size_t)oh + (size_t)oh * t;
+    leon::ResampleGeom worst;
+    return resize_tables_layout(ow, oh, resize_filter_max_taps(filter), resize_filter_max_taps(filter), &worst);
 }
 
 // The CPU twin of k_box_tables' judgement: the same functions of leon_resize_row.h in the same order
@@ -1657,66 +1683,83 @@ int boxes_ids_stage(leon_pipeline* p, const std::vector<uint32_t>& ids, uint32_t
     return LEON_OK;
 }
 
-// One call: the host's refusals, the window's frame ids uploaded, then per chunk k_box_tables and k_boxes on the caller's stream (or the
-// pipeline's regions stream and a wait).  regions_mu is held while enqueuing only.
+// what the two device roads' call structs share (leon_pipeline_regions_device, leon_pipeline_warp_regions_call); *pitch as regions_out_check's
+int boxes_call_check(const char* who, const void* regions, bool reserved_set, const int32_t* device_status, const void* device_out, uint64_t out_pitch,
+                     size_t region_bytes, uint64_t* pitch)
+{
+    if (reserved_set) return fail(LEON_ERR_INVALID, "%s: a reserved word of the call is not 0", who);
+    if (!regions) return fail(LEON_ERR_INVALID, "%s: null regions", who);
+    if ((uintptr_t)regions & 3u) return fail(LEON_ERR_INVALID, "%s: regions %p is not 4-byte aligned", who, regions);
+    if ((uintptr_t)device_status & 3u) return fail(LEON_ERR_INVALID, "%s: device_status %p is not 4-byte aligned", who, (const void*)device_status);
+    return regions_out_check(who, device_out, out_pitch, region_bytes, pitch);
+}
+
+// The bracket of a device road's enqueue on `st`, regions_mu held.  boxes_begin: the scratch (boxes_dev) at `scratch_bytes` or more, `st`
+// behind the call before's use of it (boxes_done), the window's frame ids uploaded to its start (*d_ids) with the staging entry's event
+// recorded behind the upload.  Once it returns LEON_OK the stream holds work and the road goes on to boxes_end whatever *he says: it
+// enqueues its kernels while *he is hipSuccess and folds hipGetLastError() into it.
+int boxes_begin(leon_pipeline* p, hipStream_t st, const std::vector<uint32_t>& ids, size_t scratch_bytes, uint32_t** d_ids, hipError_t* he)
+{
+    int rc;
+    if (!p->boxes_done) HIP_TRY(hipEventCreateWithFlags(&p->boxes_done, hipEventDisableTiming));
+    if ((rc = boxes_reserve(p, scratch_bytes)) != LEON_OK) return rc;
+    uint32_t* ids_host = nullptr;
+    if ((rc = boxes_ids_stage(p, ids, &ids_host)) != LEON_OK) return rc;
+    const unsigned e = (p->boxes_ids_next - 1) % leon_pipeline::kBoxesStaging;
+    if (p->boxes_busy) HIP_TRY(hipStreamWaitEvent(st, p->boxes_done, 0));
+    *d_ids = reinterpret_cast<uint32_t*>(p->boxes_dev);
+    *he = hipMemcpyAsync(*d_ids, ids_host, ids.size() * 4, hipMemcpyHostToDevice, st);
+    if (*he == hipSuccess && (*he = hipEventRecord(p->boxes_ids_done[e], st)) == hipSuccess) p->boxes_ids_busy[e] = true;
+    return LEON_OK;
+}
+// boxes_end: boxes_done recorded whatever happened, so that the scratch stays covered; the lock dropped (regions_mu is held while
+// enqueuing only); then the road's error, and the wait where the caller gave no stream
+int boxes_end(leon_pipeline* p, hipStream_t st, hipError_t he, std::unique_lock<std::mutex>& call, bool waits)
+{
+    if (hipEventRecord(p->boxes_done, st) == hipSuccess) p->boxes_busy = true;
+    else if (he == hipSuccess) he = hipGetLastError();
+    call.unlock();
+    HIP_TRY(he);
+    if (waits) HIP_TRY(hipStreamSynchronize(st));
+    return LEON_OK;
+}
+
+// One call: the host's refusals, then inside the bracket per chunk k_box_tables and k_regions (letterboxed: k_fit_tables and k_fitted) on the
+// caller's stream (or the pipeline's regions stream and a wait)
 int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_regions_config* cfg, const leon_pipeline_regions_fit* fit_settings,
                             const leon_pipeline_regions_device* c, int32_t* device_rects)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
     if (!cfg || !c) return fail(LEON_ERR_INVALID, "null argument");
     RegionsFit fit;
-    const int frc = regions_fit_check(fit_settings, &fit);
-    if (frc != LEON_OK) return frc;
+    int rc = regions_fit_check(fit_settings, &fit);
+    if (rc != LEON_OK) return rc;
     if (device_rects && !fit.letterbox) return fail(LEON_ERR_INVALID, "regions: device_rects without LEON_REGIONS_FIT_LETTERBOX (every region's rectangle is its tensor)");
     if ((uintptr_t)device_rects & 3u) return fail(LEON_ERR_INVALID, "regions: device_rects %p is not 4-byte aligned", (void*)device_rects);
-    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR) || !p->d_tensor || !p->d_planes)
-        return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    if ((rc = regions_pipeline_check(p)) != LEON_OK) return rc;
     std::unique_lock<std::mutex> call(p->regions_mu);
     std::vector<uint32_t> ids;
-    int rc = regions_window_ids(p, window, &ids);
-    if (rc != LEON_OK) return rc;
+    if ((rc = regions_window_ids(p, window, &ids)) != LEON_OK) return rc;
     const int32_t fw = p->vinfo.frame_width, fh = p->vinfo.frame_height, n = c->n;
     if ((rc = regions_config_check(fw, fh, (int32_t)ids.size(), n, cfg)) != LEON_OK) return rc;
-    if (c->reserved0 || c->reserved[0]) return fail(LEON_ERR_INVALID, "regions: a reserved word of the call is not 0");
-    if (!c->regions) return fail(LEON_ERR_INVALID, "regions: null regions");
-    if ((uintptr_t)c->regions & 3u) return fail(LEON_ERR_INVALID, "regions: regions %p is not 4-byte aligned", (const void*)c->regions);
-    if ((uintptr_t)c->device_status & 3u) return fail(LEON_ERR_INVALID, "regions: device_status %p is not 4-byte aligned", (void*)c->device_status);
-    if (!c->device_out) return fail(LEON_ERR_INVALID, "regions: null device_out");
-    if ((uintptr_t)c->device_out & 255u) return fail(LEON_ERR_INVALID, "regions: device_out %p is not 256-byte aligned", c->device_out);
     const int32_t ow = cfg->out_width, oh = cfg->out_height, filter = cfg->filter;
     const size_t region_bytes = (size_t)3 * oh * ow * p->tensor_elem;
-    if (c->out_pitch_bytes && (c->out_pitch_bytes % 256 || c->out_pitch_bytes < region_bytes))
-        return fail(LEON_ERR_INVALID, "regions: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", (unsigned long long)c->out_pitch_bytes, region_bytes);
-    const uint64_t pitch = c->out_pitch_bytes ? c->out_pitch_bytes : (uint64_t)pad256(region_bytes);
-    const int eb = (int)p->tensor_elem, layout = p->tensor_layout;
-    const bool listed = (eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc);
-    const RegionsKernel kb = listed ? kBoxesKernels[filter].k[eb >> 1][layout] : nullptr;
-    const FittedKernel kf = listed ? kFittedKernels[filter].k[eb >> 1][layout] : nullptr;
-    if (!kb || !kf) return fail(LEON_ERR_INVALID, "regions: no kernel for %d-byte elements, layout %d, filter %d", eb, layout, filter);
+    uint64_t pitch;
+    if ((rc = boxes_call_check("regions", c->regions, c->reserved0 || c->reserved[0], c->device_status, c->device_out, c->out_pitch_bytes, region_bytes, &pitch)) != LEON_OK)
+        return rc;
     // as many regions a chunk as fit the limit (and 32 bits of table words, which rt_base counts)
     const size_t slot_words = boxes_slot_words(ow, oh, filter), per_region = slot_words * 4 + sizeof(leon::RegionDesc);
     const uint64_t limit = c->scratch_limit_bytes ? c->scratch_limit_bytes : LEON_REGIONS_SCRATCH_DEFAULT;
     if (limit < per_region) return fail(LEON_ERR_INVALID, "regions: scratch_limit_bytes %llu is below one region's %zu bytes", (unsigned long long)limit, per_region);
     const size_t chunk = (size_t)std::min<uint64_t>({(uint64_t)n, limit / per_region, (((uint64_t)1 << 32) - 1) / slot_words});
     const size_t ids_bytes = pad256(ids.size() * 4), desc_bytes = pad256(chunk * sizeof(leon::RegionDesc));
-    HIP_TRY(hipSetDevice(p->cfg.device_id));
-    hipStream_t st = static_cast<hipStream_t>(c->stream);
-    if (!st) {
-        if (!p->regions_stream) HIP_TRY(hipStreamCreateWithFlags(&p->regions_stream, hipStreamNonBlocking));
-        st = p->regions_stream;
-    }
-    if (!p->boxes_done) HIP_TRY(hipEventCreateWithFlags(&p->boxes_done, hipEventDisableTiming));
-    if ((rc = boxes_reserve(p, ids_bytes + desc_bytes + chunk * slot_words * 4)) != LEON_OK) return rc;
-    uint32_t* ids_host = nullptr;
-    if ((rc = boxes_ids_stage(p, ids, &ids_host)) != LEON_OK) return rc;
-    const unsigned e = (p->boxes_ids_next - 1) % leon_pipeline::kBoxesStaging;
-    // from here on the stream holds work: the event is recorded whatever happens, so that the scratch stays covered
-    if (p->boxes_busy) HIP_TRY(hipStreamWaitEvent(st, p->boxes_done, 0));
-    uint32_t* d_ids = reinterpret_cast<uint32_t*>(p->boxes_dev);
+    hipStream_t st;
+    uint32_t* d_ids = nullptr;
+    hipError_t he = hipSuccess;
+    if ((rc = regions_call_stream(p, c->stream, &st)) != LEON_OK || (rc = boxes_begin(p, st, ids, ids_bytes + desc_bytes + chunk * slot_words * 4, &d_ids, &he)) != LEON_OK)
+        return rc;
     leon::RegionDesc* d_descs = reinterpret_cast<leon::RegionDesc*>(p->boxes_dev + ids_bytes);
     int32_t* d_tabs = reinterpret_cast<int32_t*>(p->boxes_dev + ids_bytes + desc_bytes);
-    hipError_t he = hipMemcpyAsync(d_ids, ids_host, ids.size() * 4, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && (he = hipEventRecord(p->boxes_ids_done[e], st)) == hipSuccess) p->boxes_ids_busy[e] = true;
     leon::ResampleGeom G{};
     G.fw = fw; G.fh = fh; G.ow = ow; G.oh = oh;
     G.ring = ring_geom(p);
@@ -1725,31 +1768,20 @@ int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipelin
     B.n_frames = (int32_t)ids.size(); B.cubic = filter == LEON_RESIZE_BICUBIC;
     B.slot_words = (uint32_t)slot_words;
     B.pitch_lo = (uint32_t)(pitch & 0xffffffffu); B.pitch_hi = (uint32_t)(pitch >> 32);
-    const unsigned gx = (unsigned)((ow + leon::kResTileX - 1) / leon::kResTileX), gy = (unsigned)((oh + leon::kResTileY - 1) / leon::kResTileY);
-    const unsigned gy_fit = gy + fitted_pad_rows(region_bytes, gx);          // (at most 512 tile rows and 96 pad rows: inside 65535)
     const leon::BoxRecord* boxes = reinterpret_cast<const leon::BoxRecord*>(c->regions);
     for (size_t first = 0; he == hipSuccess && first < (size_t)n; first += chunk) {
-        const unsigned m = (unsigned)std::min(chunk, (size_t)n - first);          // (blockIdx.z of k_boxes: m <= n <= 65535)
+        const unsigned m = (unsigned)std::min(chunk, (size_t)n - first);          // (blockIdx.z: m <= n <= 65535; at most 512 tile rows and 96 pad rows)
         B.first = (uint32_t)first;
         int32_t* status = c->device_status ? c->device_status + first : nullptr;
-        if (fit.letterbox) {
+        if (fit.letterbox)
             hipLaunchKernelGGL(leon::k_fit_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, (const uint32_t*)d_ids, d_descs, d_tabs, status,
                                device_rects ? device_rects + first * 4 : nullptr, fit.top_left ? 1 : 0, B);
-            hipLaunchKernelGGL(kf, dim3(gx, gy_fit, m), dim3(leon::kRgbaBlock), 0, st, (const uint8_t*)p->d_planes, static_cast<uint8_t*>(c->device_out), (const leon::RegionDesc*)d_descs,
-                               (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)d_tabs, G, fit.pad);
-        } else {
+        else
             hipLaunchKernelGGL(leon::k_box_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, (const uint32_t*)d_ids, d_descs, d_tabs, status, B);
-            hipLaunchKernelGGL(kb, dim3(gx, gy, m), dim3(leon::kRgbaBlock), 0, st, (const uint8_t*)p->d_planes, static_cast<uint8_t*>(c->device_out), (const leon::RegionDesc*)d_descs,
-                               (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, (const int32_t*)d_tabs, G);
-        }
+        regions_launch(p, st, fit, filter, G, regions_grid(ow, oh, region_bytes, fit.letterbox, m), static_cast<uint8_t*>(c->device_out), d_descs, d_tabs);
         he = hipGetLastError();
     }
-    if (hipEventRecord(p->boxes_done, st) == hipSuccess) p->boxes_busy = true;
-    else if (he == hipSuccess) he = hipGetLastError();
-    call.unlock();
-    HIP_TRY(he);
-    if (!c->stream) HIP_TRY(hipStreamSynchronize(st));
-    return LEON_OK;
+    return boxes_end(p, st, he, call, !c->stream);
 }
 
 // ---- rotated boxes and affine crops (leon_pipeline_warp_regions) ---------------------------------------------------------------
@@ -1831,22 +1863,12 @@ void warp_launch(leon_pipeline* p, hipStream_t st, const leon::WarpRecord* d_rec
     hipLaunchKernelGGL(kWarpKernels[p->tensor_elem >> 1][p->tensor_layout], dim3(gx, gy, (unsigned)n), dim3(leon::kRgbaBlock), 0, st, (const uint8_t*)p->d_planes, out, d_recs,
                        d_ids, d_status, (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, C);
 }
-int warp_pipeline_check(const leon_pipeline* p)
-{
-    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
-    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR) || !p->d_tensor || !p->d_planes)
-        return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
-    const int eb = (int)p->tensor_elem, layout = p->tensor_layout;
-    if (!((eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc)))
-        return fail(LEON_ERR_INVALID, "warp regions: no kernel for %d-byte elements, layout %d", eb, layout);
-    return LEON_OK;
-}
 
-// One call of the host road: refusals, [frame ids | records] through the regions staging, one upload, one launch, the wait
+// One call of the host road: refusals, [frame ids | records] into the regions staging, then regions_host_run
 int warp_regions(leon_pipeline* p, int64_t window, const leon_pipeline_warp_region* regions, int32_t n, const leon_pipeline_warp_config* cfg, void* device_out,
                  uint64_t out_pitch, void* host)
 {
-    int rc = warp_pipeline_check(p);
+    int rc = regions_pipeline_check(p);
     if (rc != LEON_OK) return rc;
     std::lock_guard<std::mutex> call(p->regions_mu);
     std::vector<uint32_t> ids;
@@ -1854,36 +1876,24 @@ int warp_regions(leon_pipeline* p, int64_t window, const leon_pipeline_warp_regi
     uint32_t pad = 0;
     if ((rc = warp_regions_check(p->vinfo.frame_width, p->vinfo.frame_height, (int32_t)ids.size(), regions, n, cfg, nullptr, &pad)) != LEON_OK) return rc;
     const size_t region_bytes = (size_t)3 * cfg->out_height * cfg->out_width * p->tensor_elem;
-    if (host) { device_out = nullptr; out_pitch = 0; }
-    else {
-        if (!device_out) return fail(LEON_ERR_INVALID, "warp regions: null device_out");
-        if ((uintptr_t)device_out & 255u) return fail(LEON_ERR_INVALID, "warp regions: device_out %p is not 256-byte aligned", device_out);
-    }
-    if (out_pitch && (out_pitch % 256 || out_pitch < region_bytes))
-        return fail(LEON_ERR_INVALID, "warp regions: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", (unsigned long long)out_pitch, region_bytes);
-    const size_t pitch = out_pitch ? (size_t)out_pitch : pad256(region_bytes);
+    uint64_t pitch = pad256(region_bytes);
+    if (!host && (rc = regions_out_check("warp regions", device_out, out_pitch, region_bytes, &pitch)) != LEON_OK) return rc;
     const size_t ids_bytes = pad256(ids.size() * 4), upload_bytes = ids_bytes + (size_t)n * sizeof(leon::WarpRecord);
-    HIP_TRY(hipSetDevice(p->cfg.device_id));
-    if (!p->regions_stream) HIP_TRY(hipStreamCreateWithFlags(&p->regions_stream, hipStreamNonBlocking));
-    if ((rc = regions_reserve(p, upload_bytes, host ? (size_t)n * pitch : 0)) != LEON_OK) return rc;
+    hipStream_t st;
+    if ((rc = regions_call_stream(p, nullptr, &st)) != LEON_OK || (rc = regions_reserve(p, upload_bytes, host ? (size_t)n * pitch : 0)) != LEON_OK) return rc;
     std::copy(ids.begin(), ids.end(), reinterpret_cast<uint32_t*>(p->regions_host));
     std::memcpy(p->regions_host + ids_bytes, regions, (size_t)n * sizeof(leon::WarpRecord));
-    uint8_t* out = host ? p->regions_out : static_cast<uint8_t*>(device_out);
-    hipStream_t st = p->regions_stream;
-    HIP_TRY(hipMemcpyAsync(p->regions_dev, p->regions_host, upload_bytes, hipMemcpyHostToDevice, st));
-    warp_launch(p, st, reinterpret_cast<const leon::WarpRecord*>(p->regions_dev + ids_bytes), reinterpret_cast<const uint32_t*>(p->regions_dev), (int32_t)ids.size(), n, *cfg,
-                pad, out, pitch, nullptr);
-    HIP_TRY(hipGetLastError());
-    if (host) HIP_TRY(hipMemcpy2DAsync(host, region_bytes, out, pitch, region_bytes, (size_t)n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return LEON_OK;
+    return regions_host_run(p, st, upload_bytes, host, device_out, (size_t)pitch, region_bytes, n, [&](uint8_t* out) {
+        warp_launch(p, st, reinterpret_cast<const leon::WarpRecord*>(p->regions_dev + ids_bytes), reinterpret_cast<const uint32_t*>(p->regions_dev), (int32_t)ids.size(), n, *cfg,
+                    pad, out, pitch, nullptr);
+    });
 }
 
-// One call of the device road: the host's refusals, the window's frame ids uploaded into the boxes scratch behind its event, one launch on
-// the caller's stream (or the regions stream and a wait).  regions_mu is held while enqueuing only.
+// One call of the device road: the host's refusals, then inside the boxes bracket (the frame ids are all of the scratch it needs) one launch
+// on the caller's stream (or the regions stream and a wait)
 int warp_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_warp_config* cfg, const leon_pipeline_warp_regions_call* c)
 {
-    int rc = warp_pipeline_check(p);
+    int rc = regions_pipeline_check(p);
     if (rc != LEON_OK) return rc;
     if (!cfg || !c) return fail(LEON_ERR_INVALID, "null argument");
     std::unique_lock<std::mutex> call(p->regions_mu);
@@ -1892,44 +1902,21 @@ int warp_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_wa
     uint32_t pad = 0;
     const int32_t n = c->n;
     if ((rc = warp_config_check(p->vinfo.frame_width, p->vinfo.frame_height, (int32_t)ids.size(), n, cfg, &pad)) != LEON_OK) return rc;
-    if (c->reserved0 || c->reserved[0] || c->reserved[1]) return fail(LEON_ERR_INVALID, "warp regions: a reserved word of the call is not 0");
-    if (!c->regions) return fail(LEON_ERR_INVALID, "warp regions: null regions");
-    if ((uintptr_t)c->regions & 3u) return fail(LEON_ERR_INVALID, "warp regions: regions %p is not 4-byte aligned", (const void*)c->regions);
-    if ((uintptr_t)c->device_status & 3u) return fail(LEON_ERR_INVALID, "warp regions: device_status %p is not 4-byte aligned", (void*)c->device_status);
-    if (!c->device_out) return fail(LEON_ERR_INVALID, "warp regions: null device_out");
-    if ((uintptr_t)c->device_out & 255u) return fail(LEON_ERR_INVALID, "warp regions: device_out %p is not 256-byte aligned", c->device_out);
     const size_t region_bytes = (size_t)3 * cfg->out_height * cfg->out_width * p->tensor_elem;
-    if (c->out_pitch_bytes && (c->out_pitch_bytes % 256 || c->out_pitch_bytes < region_bytes))
-        return fail(LEON_ERR_INVALID, "warp regions: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", (unsigned long long)c->out_pitch_bytes,
-                    region_bytes);
-    const uint64_t pitch = c->out_pitch_bytes ? c->out_pitch_bytes : (uint64_t)pad256(region_bytes);
-    HIP_TRY(hipSetDevice(p->cfg.device_id));
-    hipStream_t st = static_cast<hipStream_t>(c->stream);
-    if (!st) {
-        if (!p->regions_stream) HIP_TRY(hipStreamCreateWithFlags(&p->regions_stream, hipStreamNonBlocking));
-        st = p->regions_stream;
-    }
-    if (!p->boxes_done) HIP_TRY(hipEventCreateWithFlags(&p->boxes_done, hipEventDisableTiming));
-    if ((rc = boxes_reserve(p, pad256(ids.size() * 4))) != LEON_OK) return rc;
-    uint32_t* ids_host = nullptr;
-    if ((rc = boxes_ids_stage(p, ids, &ids_host)) != LEON_OK) return rc;
-    const unsigned e = (p->boxes_ids_next - 1) % leon_pipeline::kBoxesStaging;
-    // from here on the stream holds work: the event is recorded whatever happens, so that the scratch stays covered
-    if (p->boxes_busy) HIP_TRY(hipStreamWaitEvent(st, p->boxes_done, 0));
-    uint32_t* d_ids = reinterpret_cast<uint32_t*>(p->boxes_dev);
-    hipError_t he = hipMemcpyAsync(d_ids, ids_host, ids.size() * 4, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && (he = hipEventRecord(p->boxes_ids_done[e], st)) == hipSuccess) p->boxes_ids_busy[e] = true;
+    uint64_t pitch;
+    if ((rc = boxes_call_check("warp regions", c->regions, c->reserved0 || c->reserved[0] || c->reserved[1], c->device_status, c->device_out, c->out_pitch_bytes, region_bytes,
+                               &pitch)) != LEON_OK)
+        return rc;
+    hipStream_t st;
+    uint32_t* d_ids = nullptr;
+    hipError_t he = hipSuccess;
+    if ((rc = regions_call_stream(p, c->stream, &st)) != LEON_OK || (rc = boxes_begin(p, st, ids, pad256(ids.size() * 4), &d_ids, &he)) != LEON_OK) return rc;
     if (he == hipSuccess) {
         warp_launch(p, st, reinterpret_cast<const leon::WarpRecord*>(c->regions), d_ids, (int32_t)ids.size(), n, *cfg, pad, static_cast<uint8_t*>(c->device_out), pitch,
                     c->device_status);
         he = hipGetLastError();
     }
-    if (hipEventRecord(p->boxes_done, st) == hipSuccess) p->boxes_busy = true;
-    else if (he == hipSuccess) he = hipGetLastError();
-    call.unlock();
-    HIP_TRY(he);
-    if (!c->stream) HIP_TRY(hipStreamSynchronize(st));
-    return LEON_OK;
+    return boxes_end(p, st, he, call, !c->stream);
 }
 
 // The device's rows of a batch of single axes, copied back (leon_pipeline_resize_weights_device): memory of its own, the null stream

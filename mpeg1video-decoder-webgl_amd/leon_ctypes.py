@@ -1170,6 +1170,43 @@ class Pipeline:
             return (h, w, 3), (3 * w * e, 3 * e, e)
         return (3, h, w), (h * w * e, w * e, e)
 
+    def _need_tensors(self):
+        if not self.info.tensor_dtype:
+            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+
+    def _regions_out(self, out, n, size, pitch, dev):
+        """(out, step): the caller's uint8 buffer, checked, or one allocated for n regions of `size` every `step` = pitch bytes (None: the default)"""
+        import torch
+        nbytes, dflt = self.region_bytes(size)
+        step = dflt if pitch is None else int(pitch)
+        if out is None:
+            out = torch.empty(max(1, n) * max(step, 1), dtype=torch.uint8, device="cuda:%d" % dev)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < (n - 1) * step + nbytes:
+            raise ValueError("out: a contiguous uint8 tensor of at least %d bytes" % ((n - 1) * step + nbytes))
+        return out, step
+
+    def _regions_status(self, status, n, dev):
+        """the caller's int32 status tensor, checked, or one allocated for n regions"""
+        import torch
+        if status is None:
+            return torch.empty(max(1, n), dtype=torch.int32, device="cuda:%d" % dev)
+        if status.dtype != torch.int32 or not status.is_contiguous() or status.numel() < n:
+            raise ValueError("status: a contiguous int32 tensor of at least %d words" % n)
+        return status
+
+    @staticmethod
+    def _stream_handle(stream):
+        """the handle the library queues on; torch's legacy default stream has none: waited for here, and the call then waits for its work"""
+        handle = int(stream.cuda_stream)
+        if not handle:
+            stream.synchronize()
+        return handle or None
+
+    def _regions_batch(self, out, n, size, step, dev):
+        """the view [N, 3, h, w] ("hwc": [N, h, w, 3]) over `out`, regions `step` bytes apart"""
+        shape, strides = self._region_dims(size)
+        return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out)
+
     def resample_regions(self, window, regions, size, filter="triangle", out=None, pitch=None, device_id=None, fit=None, anchor=None, pad_value=None):
         """leon_pipeline_resample_regions: regions = [(frame_index, x, y, w, h), ...] of the delivered, not yet released `window`
         (frame["_i"] is the index) resampled to size = (h, w) -> a torch view [N, 3, h, w] ("hwc": [N, h, w, 3]) of the pipeline's
@@ -1181,16 +1218,10 @@ class Pipeline:
         anchor="top_left" -- and the rest is pad_value = (r, g, b) through the element table (leon_pipeline_regions_fit;
         region_fit_rect says where the image lies).  Without the three keywords the call is the one it always was."""
         import torch
-        if not self.info.tensor_dtype:
-            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        self._need_tensors()
         arr, n, cfg = _regions_args(regions, size, filter)
-        nbytes, dflt = self.region_bytes(size)
-        step = dflt if pitch is None else int(pitch)
         dev = self.device_id if device_id is None else device_id
-        if out is None:
-            out = torch.empty(max(1, n) * max(step, 1), dtype=torch.uint8, device="cuda:%d" % dev)
-        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < (n - 1) * step + nbytes:
-            raise ValueError("out: a contiguous uint8 tensor of at least %d bytes" % ((n - 1) * step + nbytes))
+        out, step = self._regions_out(out, n, size, pitch, dev)
         # the library writes on a stream of its own: what torch has queued for this memory (a fill, an earlier owner's kernels) goes first
         torch.cuda.current_stream(dev).synchronize()
         f = _regions_fit(fit, anchor, pad_value)
@@ -1198,8 +1229,7 @@ class Pipeline:
             _chk(self.lib.leon_pipeline_resample_regions(self.h, int(window), arr, n, C.byref(cfg), out.data_ptr(), 0 if pitch is None else step))
         else:
             _chk(self.lib.leon_pipeline_resample_regions_fit(self.h, int(window), arr, n, C.byref(cfg), C.byref(f), out.data_ptr(), 0 if pitch is None else step))
-        shape, strides = self._region_dims(size)
-        return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out)
+        return self._regions_batch(out, n, size, step, dev)
 
     def resample_regions_device(self, window, boxes, size, filter="triangle", out=None, pitch=None, status=None, stream=None, scratch_limit=None,
                                 fit=None, anchor=None, pad_value=None, rects=None):
@@ -1217,8 +1247,7 @@ class Pipeline:
         then returns (batch, status, rects), rects[i] = (x, y, width, height) of region i's image for every status-0 region, the
         others' words untouched."""
         import torch
-        if not self.info.tensor_dtype:
-            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        self._need_tensors()
         dev = self.device_id
         if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda and boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] in (5, 8)):
             raise ValueError("boxes: a CUDA int32 tensor [N, 8] (records) or [N, 5] (frame, x, y, w, h)")
@@ -1231,44 +1260,31 @@ class Pipeline:
         stream = torch.cuda.current_stream(dev) if stream is None else stream
         n = int(boxes.shape[0])
         cfg = size if isinstance(size, PipelineRegionsConfig) else PipelineRegionsConfig(int(size[1]), int(size[0]), _resize_filter_code(filter))
-        nbytes, dflt = self.region_bytes((cfg.out_height, cfg.out_width))
-        step = dflt if pitch is None else int(pitch)
         with torch.cuda.stream(stream):
             if boxes.shape[1] == 5:
                 boxes = torch.nn.functional.pad(boxes, (0, 3))
             elif not boxes.is_contiguous():
                 raise ValueError("boxes: [N, 8] records must be contiguous")
-            if out is None:
-                out = torch.empty(max(1, n) * max(step, 1), dtype=torch.uint8, device="cuda:%d" % dev)
-            elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < (n - 1) * step + nbytes:
-                raise ValueError("out: a contiguous uint8 tensor of at least %d bytes" % ((n - 1) * step + nbytes))
-            if status is None:
-                status = torch.empty(max(1, n), dtype=torch.int32, device="cuda:%d" % dev)
-            elif status.dtype != torch.int32 or not status.is_contiguous() or status.numel() < n:
-                raise ValueError("status: a contiguous int32 tensor of at least %d words" % n)
+            out, step = self._regions_out(out, n, (cfg.out_height, cfg.out_width), pitch, dev)
+            status = self._regions_status(status, n, dev)
             if want_rects and rects is None:
                 rects = torch.empty((max(1, n), 4), dtype=torch.int32, device="cuda:%d" % dev)
             elif want_rects and (rects.dtype != torch.int32 or not rects.is_contiguous() or rects.numel() < 4 * n):
                 raise ValueError("rects: a contiguous int32 tensor of at least %d words" % (4 * n))
-        handle = int(stream.cuda_stream)
-        if not handle:
-            stream.synchronize()
-        call = PipelineRegionsDevice(boxes.data_ptr() if n else None, n, 0, out.data_ptr(), 0 if pitch is None else step, status.data_ptr(), handle or None,
+        call = PipelineRegionsDevice(boxes.data_ptr() if n else None, n, 0, out.data_ptr(), 0 if pitch is None else step, status.data_ptr(), self._stream_handle(stream),
                                      0 if scratch_limit is None else int(scratch_limit))
         f = _regions_fit(fit, anchor, pad_value)
         if f is None and not want_rects:
             _chk(self.lib.leon_pipeline_resample_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
         else:
             _chk(self.lib.leon_pipeline_resample_regions_device_fit(self.h, int(window), C.byref(cfg), _fit_ref(f), C.byref(call), rects.data_ptr() if want_rects else None))
-        shape, strides = self._region_dims((cfg.out_height, cfg.out_width))
-        batch = self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out)
+        batch = self._regions_batch(out, n, (cfg.out_height, cfg.out_width), step, dev)
         return (batch, status[:n], rects.view(-1)[:4 * n].view(n, 4)) if want_rects else (batch, status[:n])
 
     def read_regions(self, window, regions, size, filter="triangle", fit=None, anchor=None, pad_value=None):
         """leon_pipeline_read_regions: the same regions as a host array [N, 3, h, w] ("hwc": [N, h, w, 3]), packed: float16 / float32 /
         uint8, bfloat16 as uint16 bit patterns like read_tensor; fit, anchor, pad_value as resample_regions"""
-        if not self.info.tensor_dtype:
-            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        self._need_tensors()
         arr, n, cfg = _regions_args(regions, size, filter)
         out = np.empty((max(1, n),) + self._region_dims(size)[0], dtype=self._tensor_np_dtype())
         f = _regions_fit(fit, anchor, pad_value)
@@ -1284,25 +1300,17 @@ class Pipeline:
         ("hwc": [N, h, w, 3]) as resample_regions builds it; out and pitch as there.  Positions outside the frame read pad_value =
         (r, g, b) through the element table.  Synchronous.  Raises LeonError where the library refuses; nothing is written then."""
         import torch
-        if not self.info.tensor_dtype:
-            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        self._need_tensors()
         arr, n, cfg = _warp_args(regions, size, pad_value)
-        nbytes, dflt = self.region_bytes((cfg.out_height, cfg.out_width))
-        step = dflt if pitch is None else int(pitch)
         dev = self.device_id
-        if out is None:
-            out = torch.empty(max(1, n) * max(step, 1), dtype=torch.uint8, device="cuda:%d" % dev)
-        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < (n - 1) * step + nbytes:
-            raise ValueError("out: a contiguous uint8 tensor of at least %d bytes" % ((n - 1) * step + nbytes))
+        out, step = self._regions_out(out, n, (cfg.out_height, cfg.out_width), pitch, dev)
         torch.cuda.current_stream(dev).synchronize()          # (the library writes on a stream of its own: resample_regions)
         _chk(self.lib.leon_pipeline_warp_regions(self.h, int(window), arr, n, C.byref(cfg), out.data_ptr(), 0 if pitch is None else step))
-        shape, strides = self._region_dims((cfg.out_height, cfg.out_width))
-        return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out)
+        return self._regions_batch(out, n, (cfg.out_height, cfg.out_width), step, dev)
 
     def read_warp_regions(self, window, regions, size, pad_value=None):
         """leon_pipeline_read_warp_regions: the same regions as a host array [N, 3, h, w] ("hwc": [N, h, w, 3]), packed, as read_regions"""
-        if not self.info.tensor_dtype:
-            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        self._need_tensors()
         arr, n, cfg = _warp_args(regions, size, pad_value)
         out = np.empty((max(1, n),) + self._region_dims((cfg.out_height, cfg.out_width))[0], dtype=self._tensor_np_dtype())
         _chk(self.lib.leon_pipeline_read_warp_regions(self.h, int(window), arr, n, C.byref(cfg), out.ctypes.data))
@@ -1314,8 +1322,7 @@ class Pipeline:
         stream) with resample_regions_device's ordering: NO host synchronisation.  Returns (batch, status): status an int32 tensor [N]
         on the device, REGION_* per record -- 0: written; otherwise the region was skipped and its bytes of `out` are untouched."""
         import torch
-        if not self.info.tensor_dtype:
-            raise LeonError(ERR_INVALID, "the pipeline has no tensor output (Pipeline output)")
+        self._need_tensors()
         dev = self.device_id
         if not (isinstance(records, torch.Tensor) and records.is_cuda and records.dtype == torch.int32 and records.dim() == 2 and records.shape[1] == 8
                 and records.is_contiguous()):
@@ -1326,24 +1333,12 @@ class Pipeline:
         stream = torch.cuda.current_stream(dev) if stream is None else stream
         n = int(records.shape[0])
         cfg = _warp_config(size, pad_value)
-        nbytes, dflt = self.region_bytes((cfg.out_height, cfg.out_width))
-        step = dflt if pitch is None else int(pitch)
         with torch.cuda.stream(stream):
-            if out is None:
-                out = torch.empty(max(1, n) * max(step, 1), dtype=torch.uint8, device="cuda:%d" % dev)
-            elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < (n - 1) * step + nbytes:
-                raise ValueError("out: a contiguous uint8 tensor of at least %d bytes" % ((n - 1) * step + nbytes))
-            if status is None:
-                status = torch.empty(max(1, n), dtype=torch.int32, device="cuda:%d" % dev)
-            elif status.dtype != torch.int32 or not status.is_contiguous() or status.numel() < n:
-                raise ValueError("status: a contiguous int32 tensor of at least %d words" % n)
-        handle = int(stream.cuda_stream)
-        if not handle:
-            stream.synchronize()
-        call = PipelineWarpRegionsCall(records.data_ptr() if n else None, n, 0, out.data_ptr(), 0 if pitch is None else step, status.data_ptr(), handle or None)
+            out, step = self._regions_out(out, n, (cfg.out_height, cfg.out_width), pitch, dev)
+            status = self._regions_status(status, n, dev)
+        call = PipelineWarpRegionsCall(records.data_ptr() if n else None, n, 0, out.data_ptr(), 0 if pitch is None else step, status.data_ptr(), self._stream_handle(stream))
         _chk(self.lib.leon_pipeline_warp_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
-        shape, strides = self._region_dims((cfg.out_height, cfg.out_width))
-        return self._tensor_at(out.data_ptr(), (n,) + shape, (step,) + strides, dev, owner=out), status[:n]
+        return self._regions_batch(out, n, (cfg.out_height, cfg.out_width), step, dev), status[:n]
 
     def _tensor_at(self, ptr, shape, strides, device_id=None, owner=None):
         import torch

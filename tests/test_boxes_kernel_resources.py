@@ -1,6 +1,7 @@
-"""CPU: the kernels of leon_pipeline_resample_regions_device.  k_boxes<element bytes, layout, filter> -- k_regions behind a status test --
-exists in exactly its twelve instantiations, spills nothing and uses exactly the LDS of the matching k_resample (it is resample_body
-behind a descriptor read).  k_box_tables, which builds the regions' tables in doubles, spills nothing either (no array of doubles per
+"""CPU: the kernels of leon_pipeline_resample_regions_device.  The road launches k_regions<element bytes, layout, filter>, the host
+road's family, whose first statement is the status test: there is no k_boxes family any more, and k_regions still exists in exactly its
+twelve instantiations, spills nothing and uses exactly the LDS of the matching k_resample (it is resample_body behind a descriptor
+read).  k_box_tables, which builds the regions' tables in doubles, spills nothing either (no array of doubles per
 lane) and has a reduction's LDS only.  Their names carry none of the other families' (the resource tests count families by substring),
 and those still count what they counted.  From hipcc -Rpass-analysis (tools/kernel_resources.py), no GPU needed."""
 import os
@@ -18,8 +19,9 @@ def family(name):
     return {n: v for n, v in report().items() if name in n}
 
 
-def test_twelve_boxes_kernels_with_the_lds_of_their_k_resample():
-    ks, rs = family("k_boxes"), family("k_resample")
+def test_no_boxes_kernels_and_twelve_regions_kernels_with_the_lds_of_their_k_resample():
+    assert not family("k_boxes"), sorted(family("k_boxes"))
+    ks, rs = family("k_regions"), family("k_resample")
     assert len(ks) == 12, sorted(ks)
     for combo in COMBOS:
         for filt in FILTERS:
@@ -42,5 +44,5 @@ def test_the_table_kernels():
 
 def test_the_other_tensor_kernels_are_still_theirs():
     assert [len(family(f)) for f in OTHERS] == [12, 12, 12, 6]
-    for mine in ("k_boxes", "k_box_tables", "k_axis_tables"):
+    for mine in ("k_box_tables", "k_axis_tables"):
         assert not any(other in n for n in family(mine) for other in OTHERS)

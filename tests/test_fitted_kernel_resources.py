@@ -9,7 +9,7 @@ import pytest
 
 from test_regions_kernel_resources import COMBOS, FILTERS, report          # (one compilation for the resource modules: report() is cached there)
 
-OTHERS = ("k_regions", "k_resample", "k_letterbox", "k_tensor", "k_boxes", "k_box_tables", "k_axis_tables")
+OTHERS = ("k_regions", "k_resample", "k_letterbox", "k_tensor", "k_box_tables", "k_axis_tables")
 
 pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 
@@ -40,7 +40,7 @@ def test_the_fit_table_kernel():
 
 
 def test_the_other_families_are_still_theirs():
-    assert [len(family(f)) for f in OTHERS] == [12, 12, 12, 6, 12, 1, 1]
+    assert [len(family(f)) for f in OTHERS] == [12, 12, 12, 6, 1, 1]
     for mine in ("k_fitted", "k_fit_tables"):
         assert family(mine) and not any(other in n for n in family(mine) for other in OTHERS)
     assert not any("k_fitted" in n for n in family("k_fit_tables"))

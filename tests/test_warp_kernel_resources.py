@@ -7,7 +7,7 @@ import pytest
 
 from test_regions_kernel_resources import COMBOS, report          # (one compilation for the resource modules: report() is cached there)
 
-OTHERS = ("k_regions", "k_resample", "k_letterbox", "k_tensor", "k_boxes", "k_box_tables", "k_axis_tables", "k_fitted", "k_fit_tables")
+OTHERS = ("k_regions", "k_resample", "k_letterbox", "k_tensor", "k_box_tables", "k_axis_tables", "k_fitted", "k_fit_tables")
 
 pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 
@@ -27,6 +27,6 @@ def test_six_warp_kernels_without_scratch_inside_64k_of_lds():
 
 
 def test_the_other_families_are_still_theirs():
-    assert [len(family(f)) for f in OTHERS] == [12, 12, 12, 6, 12, 1, 1, 12, 1]
+    assert [len(family(f)) for f in OTHERS] == [12, 12, 12, 6, 1, 1, 12, 1]
     assert not any(other in n for n in family("k_warp") for other in OTHERS)
     assert not any("k_warp" in n for f in OTHERS for n in family(f))

@@ -7,8 +7,9 @@ e.g. OTHER_TREE = a `git worktree` of the parent commit.
 Prints the kernels that are identical, differ, are new and are gone; --show prints a unified diff of the normalised instructions
 and descriptors of every kernel whose name contains KERNEL.  --rename pairs a kernel that was renamed, or whose template arguments
 changed: OLD is its (mangled) name in OTHER_TREE, NEW its name here, both spelled out by the user (`c++filt` shows what a
-name says); it is then compared with its predecessor instead of showing as gone + new.  Exit status 1 when a kernel both trees
-have differs in either."""
+name says); it is then compared with its predecessor instead of showing as gone + new.  A rename onto a name that OTHER_TREE has
+too wins: that kernel of OTHER_TREE's is compared with nothing and shows as gone.  Exit status 1 when a kernel both trees have differs
+in either."""
 import argparse
 import difflib
 import os
@@ -54,6 +55,15 @@ def kernels(tree):
             return parse(s)
 
 
+def rename(a, renamed):
+    """(OTHER_TREE's kernels under this tree's names, the names of those a rename displaced): a renamed kernel takes its new name
+    whichever kernel had it there"""
+    out = {renamed[k]: v for k, v in a.items() if k in renamed}
+    displaced = sorted(k for k in a if k not in renamed and k in out)
+    out.update((k, v) for k, v in a.items() if k not in renamed and k not in out)
+    return out, displaced
+
+
 def main(argv):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("other_tree")
@@ -64,13 +74,15 @@ def main(argv):
     show = args.show
     renamed = dict(r.split("=", 1) for r in args.rename)
     a, b = kernels(args.other_tree), kernels(args.this_tree)
-    a = {renamed.get(k, k): v for k, v in a.items()}
+    n_there = len(a)
+    a, displaced = rename(a, renamed)
+    gone = sorted(set(a) - set(b)) + displaced
     both = sorted(k for k in a if k in b)
     differ = [k for k in both if a[k][0] != b[k][0]]
     desc_differ = [k for k in both if a[k][1] != b[k][1]]
     print("%d kernels there, %d here: %d identical, %d differ, %d descriptor differs, %d new, %d gone" % (
-        len(a), len(b), sum(1 for k in both if a[k] == b[k]), len(differ), len(desc_differ), len(set(b) - set(a)), len(set(a) - set(b))))
-    for what, names in (("differs", differ), ("descriptor differs", desc_differ), ("new", sorted(set(b) - set(a))), ("gone", sorted(set(a) - set(b)))):
+        n_there, len(b), sum(1 for k in both if a[k] == b[k]), len(differ), len(desc_differ), len(set(b) - set(a)), len(gone)))
+    for what, names in (("differs", differ), ("descriptor differs", desc_differ), ("new", sorted(set(b) - set(a))), ("gone", gone)):
         for k in names:
             print("  %s: %s" % (what, k))
     if show is not None:

@@ -6,7 +6,7 @@ can be timed without a device (leon_pipeline_regions_check: one of the two passe
 boxes' Y, Cb and Cr samples) and writes, and the copy rate of the same process.  The kernel's own time comes from running this under
 `rocprofv3 --kernel-trace --stats -- python tools/regions_bench.py ...` (k_regions, and k_resample of the pipeline's own --tensor-size
 tensors for comparison: one launch per window of --window GOPs).  --device-boxes times the same boxes through
-leon_pipeline_resample_regions_device too (k_box_tables + k_boxes per chunk; enqueue -> stream synchronisation) and checks that both
+leon_pipeline_resample_regions_device too (k_box_tables + k_regions per chunk -- a trace then holds k_regions launches of both roads; enqueue -> stream synchronisation) and checks that both
 paths wrote the same bytes.  --fit letterbox times the SAME seeded boxes letterboxed into --size as well (leon_pipeline_regions_fit:
 k_fitted, and k_fit_tables on the device path), in the same process, a stretched and a letterboxed call alternating; the boxes whose
 height the frame clips are the ones that get pad.  With --device-boxes it also checks that both paths wrote the same letterboxed bytes.
