@@ -66,6 +66,10 @@ LEON_HD inline int32_t warp_q(int64_t N, int32_t g)
 // and their bilinear neighbours, aligned to 8 columns and even rows, staged at a row pitch of width + 1 dwords (odd: a rotation by
 // 90 degrees walks down a column, and an even pitch would put a wave's 32 lanes on one or two banks).
 static constexpr int kWarpStagePx = 8192;                     // dwords of the stage
+// Of the five levels only 0 and 1 are reachable: with column norms of at most 2^18 + 1 the largest level-1 bound of any record the
+// judgement lets through is (80 + 1) * 74 = 5994 dwords, so levels 2 to 4 have never run on a device and k_warp's row loop takes one
+// trip.  tests/test_warp_sweep_structure.py (test_no_legal_record_takes_a_level_above_1) pins that number: raising kWarpMaxLog2 or
+// shrinking the stage makes it fail before untested pieces start to run.
 static constexpr int kWarpLevels = 5;
 LEON_HD inline int32_t warp_piece_w(int32_t level) { return level < 1 ? 32 : level < 3 ? 16 : 8; }          // 32 16 16 8 8
 LEON_HD inline int32_t warp_piece_h(int32_t level) { return level < 2 ? 8 : level < 4 ? 4 : 2; }            //  8  8  4 4 2

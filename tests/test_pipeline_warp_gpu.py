@@ -67,20 +67,34 @@ def want_regions(L, name, rgba, keys, regs, size, dtype, layout, scale=None, bia
     return np.ascontiguousarray(np.stack(out))
 
 
-def check_stream(L, streams, name, dtype, layout, sizes=None, **kw):
+def assert_named_regions(got, want, names, layout, what):
+    """assert_regions, and on a mismatch the name of the first differing region's record and the output pixel: a failure points at a
+    family of tests/warp_structure.py, not at an index"""
+    if got.shape == want.shape and not np.array_equal(got, want):
+        bad = np.argwhere(got != want)
+        i, a, b, c = (int(v) for v in bad[0])
+        (oy, ox, ch) = (a, b, c) if layout == "hwc" else (b, c, a)
+        differing = sorted({int(v) for v in bad[:, 0]})
+        what = "%s: first in record %r at output pixel (x %d, y %d) channel %d; differing records %s" % (what, names[i], ox, oy, ch, [names[k] for k in differing[:10]])
+    assert_regions(got, want, what)
+
+
+def check_stream(L, streams, name, dtype, layout, sizes=None, regions=None, **kw):
+    """regions: (named records, regions) as W.matrices and W.regions are, the default"""
     data, rgba = streams(name)
     sizes = sizes or W.SIZES[name]
+    named, regions = regions or (W.matrices, W.regions)
     got = {}
 
     def on_frames(p, window, keys, frames):
         got["keys"] = keys
         for size in sizes:
-            got[size] = bits(p.read_warp_regions(window, W.regions(W.frame_wh(name), size, len(frames)), size, W.PAD))
+            got[size] = bits(p.read_warp_regions(window, regions(W.frame_wh(name), size, len(frames)), size, W.PAD))
     run(L, data, dtype, layout, on_frames, **kw).close()
     for size in sizes:
-        regs = W.regions(W.frame_wh(name), size, 9)
+        regs = regions(W.frame_wh(name), size, 9)
         want = want_regions(L, name, rgba, got["keys"], regs, size, dtype, layout, kw.get("tensor_scale"), kw.get("tensor_bias"))
-        assert_regions(got[size], want, "%s %s %s %s (regions: %s)" % (name, size, dtype, layout, [n for n, _ in W.matrices(W.frame_wh(name), size)]))
+        assert_named_regions(got[size], want, [n for n, _ in named(W.frame_wh(name), size)], layout, "%s %s %s %s" % (name, size, dtype, layout))
     return [got[size] for size in sizes]
 
 

@@ -54,24 +54,7 @@ def test_outside_edges_and_the_fill_row(name, size):
 def test_every_tap_lies_in_its_piece_box_and_every_box_fits(name, size):
     wh = W.frame_wh(name)
     for mname, m in W.matrices(wh, size):
-        g = W.supersample(m)
-        S = 1 << g
-        for t in W.tile_facts(wh, m, size):
-            pw, ph = W.piece_size(t["level"])
-            for p in t["pieces"]:
-                sx0, sx1, sy0, sy1 = p["box"]
-                assert p["dwords"] <= W.STAGE_PX and (sx1 - sx0) % 8 == 0 and sx0 % 8 == 0 and sy0 % 2 == 0 and (sy1 - sy0) % 2 == 0, (mname, p)
-                assert sx1 - sx0 <= W.span_bound(m[0], m[1], g, pw, ph, 8) and sy1 - sy0 <= W.span_bound(m[3], m[4], g, pw, ph, 2), (mname, p)
-                ox = np.arange(p["at"][0], p["at"][0] + p["size"][0], dtype=np.int64)[None, :, None, None]
-                oy = np.arange(p["at"][1], p["at"][1] + p["size"][1], dtype=np.int64)[:, None, None, None]
-                i = np.arange(S, dtype=np.int64)[None, None, None, :]
-                j = np.arange(S, dtype=np.int64)[None, None, :, None]
-                x0 = W.q(W.numerator(m[0], m[1], m[2], g, ox, oy, i, j), g) >> 8
-                y0 = W.q(W.numerator(m[3], m[4], m[5], g, ox, oy, i, j), g) >> 8
-                assert sx0 <= x0.min() and x0.max() + 1 < sx1 and sy0 <= y0.min() and y0.max() + 1 < sy1, (mname, p)
-                # what a lane adds to the piece's first numerator stays far inside 32 bits
-                rel = W.numerator(m[0], m[1], m[2], g, ox, oy, i, j) - (sx0 << (17 + g))
-                assert np.abs(rel).max() < 1 << 28, (mname, p)
+        W.assert_record_facts(wh, mname, m, size)
 
 
 def test_the_smallest_piece_fits_whatever_the_matrix():
