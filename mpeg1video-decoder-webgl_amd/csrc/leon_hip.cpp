@@ -293,7 +293,8 @@ void upload_tables(leon_decoder* d)
 // the I launch 0.382-0.384 ms at 5 workgroups per CU, **0.352 at 6**, 0.359 at 7
 // -- 6 it is (20 KB + 6 KB).  P (the two-tile kernel: kOccupancyPadPairP) is the same at 5 and 6.
 constexpr size_t kOccupancyPadI = 6144, kOccupancyPadP = 11776, kOccupancyPadB = 0;
-// the two-tile kernels (dense P / B display, 26.25 KB per workgroup = six per CU): P back to five, B as the registers allow
+// the two-tile kernel (dense P display, 26.25 KB per workgroup = six per CU): back to five.  (Dense B display: the three-tile
+// layout's static array, 25.75 KB, six per CU -- at five its launch is 1.5 % slower, 0.917 against 0.902-0.907 ms.)
 constexpr size_t kOccupancyPadPairP = 1024;
 
 int n_groups_of(const Geom& G) { return 2 * G.tasksY + 2 * G.tasksC + (G.alpha ? 2 * G.tasksY : 0); }
@@ -433,6 +434,7 @@ constexpr ReconEntriesOfOut kReconKernels[4] = {kReconEntriesOfOut<kOutSlots>, k
 constexpr size_t recon_lds_bytes(int out, int type, bool sparse, bool alpha)
 {
     if (out == kOutSlots) return (size_t)kWavesPerWG * kLdsPerWave;
+    if (out == kOutRgba && front3_task(type, sparse, alpha)) return 0;      // one static array (kSfBytes): six workgroups per CU
     const size_t pad = pair_task(type, sparse, alpha) ? (type == LEON_PIC_P ? kOccupancyPadPairP : 0)
                      : !sparse && !alpha ? (type == LEON_PIC_I ? kOccupancyPadI : type == LEON_PIC_P ? kOccupancyPadP : kOccupancyPadB) : 0;
     return (size_t)kWavesPerWG * display_strip_bytes(type, sparse, alpha) + pad;
@@ -441,7 +443,7 @@ constexpr size_t recon_lds_bytes(int out, int type, bool sparse, bool alpha)
 static_assert(recon_lds_bytes(kOutSlots, 1, false, false) == 9728 && recon_lds_bytes(kOutSlots, 3, true, true) == 9728, "k_recon");
 static_assert(recon_lds_bytes(kOutRgba, 1, false, false) == 21504 && recon_lds_bytes(kOutRgba, 1, true, false) == 15360, "I display");
 static_assert(recon_lds_bytes(kOutRgba, 2, false, false) == 22784 && recon_lds_bytes(kOutRgba, 2, true, false) == 15360, "P display");
-static_assert(recon_lds_bytes(kOutRgba, 3, false, false) == 21760 && recon_lds_bytes(kOutRgba, 3, true, false) == 15360, "B display");
+static_assert(recon_lds_bytes(kOutRgba, 3, false, false) == 0 && kSfBytes == 26368 && kSfBytes <= 160 * 1024 / 6 && recon_lds_bytes(kOutRgba, 3, true, false) == 15360, "B display");
 static_assert(recon_lds_bytes(kOutRgba, 1, false, true) == 19456 && recon_lds_bytes(kOutRgba, 1, true, true) == 19456 && recon_lds_bytes(kOutRgba, 2, false, true) == 19456
               && recon_lds_bytes(kOutRgba, 2, true, true) == 19456 && recon_lds_bytes(kOutRgba, 3, false, true) == 19456 && recon_lds_bytes(kOutRgba, 3, true, true) == 19456, "yuva display");
 static_assert(recon_lds_bytes(kOutBoth, 3, true, false) == recon_lds_bytes(kOutRgba, 3, true, false), "k_recon_display_out: as k_recon_display");

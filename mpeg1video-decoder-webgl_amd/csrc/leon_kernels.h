@@ -135,7 +135,7 @@ static constexpr int kLdsPerWaveDisplayAlpha = kLdsPerWaveDisplay + 1024;   // y
 // tile lies behind the wave's strip
 // The wave's strip, two layouts:
 //   0 (all kernels but the next): [tile 2048 | tables 192 + carried vectors 64 | column ids / Y park 512 | stash 1024 (| A park)]
-//   1 (dense P / B display, two tiles): [tile L 2048 | carried vectors 64 | column ids 256 | stash 1024 | tile R 2048] = 5440 bytes:
+//   1 (dense P display -- and dense B until it went to the three-tile layout 2 below --, two tiles): [tile L 2048 | carried vectors 64 | column ids 256 | stash 1024 | tile R 2048] = 5440 bytes:
 //     4 waves + the conversion tables = 26.25 KB, SIX workgroups per CU (with layout 0 plus a second tile: 28 KB, five -- and the B
 //     kernel loses 7 % at five).  What went: the wave's LDS copy of the quantiser tables (the column pass reads its two 8-byte columns
 //     from the picture's QTables in memory: 256 bytes that every wave of the launch reads, L1 hits), and the Y park, which now lies in
@@ -146,10 +146,34 @@ template <> struct Lay<1> { static constexpr int carry = kLdsTile, slots = kLdsT
                             static constexpr bool tables_in_lds = false, park_in_tile = true; };
 static constexpr int kLdsPerWaveDisplayPair = Lay<1>::tile_r + kLdsTile;      // 5440
 static constexpr int kOffTileR = Lay<1>::tile_r;
-// the two luma parts of a display task share one front (recon_luma_pair) on layout 1: dense P and B pictures without alpha
+// the luma parts of a display task do not run a front each: dense P and B pictures without alpha (P: the two share recon_luma_pair's on
+// layout 1; B: front3_task below)
 constexpr bool pair_task(int type, bool sparse, bool alpha) { return !sparse && !alpha && type != 1; }
+// dense B display tasks run ONE front for all three parts (layout 2, display_task_front3) instead of the chroma part's and the luma
+// pair's.  P stays as it is: the same task measured 1 % SLOWER there (0.473-0.483 against 0.469-0.478 ms per launch, one box,
+// alternating, at six and at five workgroups per CU) -- its waves wait for memory, not for issue slots (0.70 of the time a vector
+// instruction in flight, B 0.92), and the second barrier costs it more than 100 of 1451 instructions bring.
+constexpr bool front3_task(int type, bool sparse, bool alpha) { return pair_task(type, sparse, alpha) && type == 3; }
 // a display wave's strip in bytes: what the kernels step by and what the host launches with
 constexpr int display_strip_bytes(int type, bool sparse, bool alpha) { return alpha ? kLdsPerWaveDisplayAlpha : (pair_task(type, sparse, alpha) ? kLdsPerWaveDisplayPair : kLdsPerWaveDisplay); }
+// dense B display tasks (front3_task) with ONE front for the chroma part and both luma parts (recon_task, FRONT3): three tiles at once.  The
+// workgroup's LDS is one static array in blocks, every address a compile-time constant plus a multiple of the wave's number:
+//   [tiles L, R 4096 x4 | C first KB x4 | column ids 384 x4 | C second KB x4 | carried vectors 64 x4] = 26368 bytes, SIX workgroups per CU.
+// The chroma tile lies in two pieces (Cb rows in the first KB, Cr rows kSfCHalf behind them).  The chroma samples park in the first KB
+// (Cb | Cr, 512 bytes each: what `stash` was), each half behind its row pass.  Once every wave's chroma part is through (barrier 1 of
+// display_task_front3) the ids and the second KBs are dead, and the conversion tables (kLdsLut) take their place: the Y table over the last
+// KB of the ids block, the 4 KB of chroma tables over the four second KBs, contiguous behind it.
+static constexpr int kSfIdsPerWave = 3 * 128;
+static constexpr int kSfC0 = kWavesPerWG * 2 * kLdsTile;                 // 16384
+static constexpr int kSfIds = kSfC0 + kWavesPerWG * kLdsHalf;            // 20480
+static constexpr int kSfC1 = kSfIds + kWavesPerWG * kSfIdsPerWave;       // 22016
+static constexpr int kSfCarry = kSfC1 + kWavesPerWG * kLdsHalf;          // 26112
+static constexpr int kSfBytes = kSfCarry + kWavesPerWG * 64;             // 26368
+static constexpr int kSfCHalf = kSfC1 - kSfC0;                           // from a wave's Cb rows to its Cr rows
+static constexpr int kSfLut = kSfCarry - kLdsLut;                        // 20992
+static_assert(kSfLut >= kSfIds && kSfLut + 1024 == kSfC1 && kSfC1 % 16 == 0, "the tables overlay the ids and the second KBs exactly");
+static_assert(6 * kSfBytes <= 160 * 1024, "six workgroups per CU");
+template <> struct Lay<2> { static constexpr bool tables_in_lds = false, park_in_tile = true; };
 // cache policy bits of the frames' stores (1 sc0, 2 nt, 16 sc1).  nt: the GPU never reads a frame again, and written through the
 // caches like everything else it pushes the reference planes out -- round 4, one box, alternating: 5.944 -> 5.818 ms per step (I -5 %,
 // P -3.6 %, mixed B -1.2 %); sc0 / sc1: nothing.  (Round 2 measured nt on ALL stores: -4 %, the planes are read again.)
@@ -714,12 +738,12 @@ __device__ __forceinline__ void display_half(const PicDesc& pd, const Geom& G, c
 // ---- stage 2 as functions: the liveness scan of a tile and the column pass over a list of live columns ------------------------
 // A column id: tile << 7 | half << 6 | c << 3 | b.  scan_tile: lane (c = hi3, b = lo3) looks at its own column of each half of
 // `tile`; the live lanes queue up behind the n_before ids that are in the list already.  Returns the new length.
-__device__ __forceinline__ uint32_t scan_tile(const char* tile, char* ids, int lane, uint32_t tag, uint32_t n_before, uint64_t (&live)[2])
+__device__ __forceinline__ uint32_t scan_tile(const char* tile, char* ids, int lane, uint32_t tag, uint32_t n_before, uint64_t (&live)[2], int half_step = kLdsHalf)
 {
     const int hi3 = lane >> 3, lo3 = lane & 7;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-        const char* cp = tile + h * kLdsHalf + lo3 * 16 + hi3 * 2;
+        const char* cp = tile + h * half_step + lo3 * 16 + hi3 * 2;
         uint32_t o = 0;
 #pragma unroll
         for (int i = 0; i < 8; i++) o |= *reinterpret_cast<const uint16_t*>(cp + i * 128);
@@ -739,9 +763,16 @@ __device__ __forceinline__ uint32_t scan_tile(const char* tile, char* ids, int l
 // round 4 the two-tile layout, which has no room for the tables in LDS, read them from memory inside this loop: two loads and an
 // `s_waitcnt vmcnt(0)` per round -- and loads return in order: the chroma part's wait for its tables was a wait for the REFERENCE
 // rows it had requested just before, whose flight the column pass was meant to cover.)
-template <bool PAIR, bool TLDS = true>
+// Three tiles (FRONT3 tasks): the list holds the chroma tile's columns first (n_c of them), then the left luma tile's (up to n_cl),
+// then the right one's; ids carry no tile bits -- a column's tile follows from its place in the list.
+struct ThreeTiles {
+    uint32_t c_off;              // from tile0 to the chroma tile's first KB (its second: + kSfCHalf); tile0 / tile0 + tile_step are the luma tiles
+    uint32_t n_c, n_cl;
+    uint32_t flags;              // MbCarry::flags of the chroma part: lane m holds macroblock m of the task
+};
+template <bool PAIR, bool TLDS = true, bool THREE = false>
 __device__ __forceinline__ void column_pass(char* tile0, uint32_t tile_step, const char* ids, const char* qtab, uint32_t n_cols, int qia0, int qia1, int lane,
-                                            uint32_t qreg = 0u)
+                                            uint32_t qreg = 0u, const ThreeTiles& t3 = ThreeTiles())
 {
     // the clamp bounds live in registers (v_med3 takes no literals on gfx950, and the compiler would
     // otherwise re-materialise them in front of every use): one scalar, one vector -- a VOP3
@@ -756,10 +787,22 @@ __device__ __forceinline__ void column_pass(char* tile0, uint32_t tile_step, con
         id = act ? id : 0u;                               // idle lanes redo column 0 and write nothing
         char* colp = tile0 + ((id & 0x47u) << 4) + ((id >> 2) & 14u);
         if constexpr (PAIR) colp += (id >> 7) * tile_step;
+        int bq;
+        if constexpr (THREE) {
+            const bool in_c = k < t3.n_c, in_r = k >= t3.n_cl;
+            // (the half bit of a chroma id steps kSfCHalf, not kLdsHalf)
+            uint32_t off = in_c ? t3.c_off + (id & 64u) * (uint32_t)((kSfCHalf - kLdsHalf) / 64) : (in_r ? tile_step : 0u);
+            off += ((id & 0x47u) << 4) + ((id >> 2) & 14u);
+            // idle lanes redo the column of lane 0 (the first of the round: always live) and write nothing
+            colp = tile0 + (act ? off : (uint32_t)__builtin_amdgcn_readfirstlane((int)off));
+            // chroma block b: macroblock b; luma block b: macroblock b >> 1 of its side
+            const uint32_t b = id & 7u, m = in_c ? b : (b >> 1) + (in_r ? 4u : 0u);
+            bq = __builtin_amdgcn_ds_bpermute((int)(m << 2), (int)t3.flags) & 0x11f;
+        }
         int X[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) X[i] = *reinterpret_cast<const short*>(colp + i * 128);
-        int bq = __builtin_amdgcn_ds_bpermute((int)((id & 7u) << 2), qia0);      // lane b holds block b's macroblock
+        if constexpr (!THREE) bq = __builtin_amdgcn_ds_bpermute((int)((id & 7u) << 2), qia0);      // lane b holds block b's macroblock
         if constexpr (PAIR) {
             const int bq1 = __builtin_amdgcn_ds_bpermute((int)((id & 7u) << 2), qia1);
             bq = (id & 128u) ? bq1 : bq;
@@ -830,7 +873,7 @@ static constexpr int kCarryNone = 0, kCarryLeave = 1, kCarryTake = 2;
 // their front, recon_luma_pair): the part's coefficients are in TaskArgs::tile and have been through the column pass already;
 // TaskArgs::live says which of its columns were live.
 template <int TYPE_, bool SPARSE_> struct PlainLuma {               // a task of k_recon, on its own: luma, or the A plane of a yuva picture (TaskArgs{true})
-    static constexpr int TYPE = TYPE_, AMODE = kAlphaNone, CARRY = kCarryNone, LAYOUT = 0, OUT = kOutRgba; static constexpr bool SPARSE = SPARSE_, CHROMA = false, DISPLAY = false, BACK = false;
+    static constexpr int TYPE = TYPE_, AMODE = kAlphaNone, CARRY = kCarryNone, LAYOUT = 0, OUT = kOutRgba; static constexpr bool SPARSE = SPARSE_, CHROMA = false, DISPLAY = false, BACK = false, FRONT3 = false;
 };
 template <int TYPE, bool SPARSE> struct PlainChroma : PlainLuma<TYPE, SPARSE> { static constexpr bool CHROMA = true; };
 // the parts of a display task (display_task), in the order they run
@@ -842,7 +885,10 @@ template <int TYPE, bool SPARSE, int OUT_> struct DisplayLuma : PlainLuma<TYPE, 
 };
 template <int TYPE, bool SPARSE, int OUT> struct YuvaAPart : DisplayLuma<TYPE, SPARSE, OUT> { static constexpr int AMODE = kAlphaPark; };
 template <int TYPE, bool SPARSE, int OUT> struct YuvaYPart : DisplayLuma<TYPE, SPARSE, OUT> { static constexpr int AMODE = kAlphaTake; };
-template <int TYPE, int OUT> struct PairBackHalf : DisplayLuma<TYPE, false, OUT> { static constexpr int LAYOUT = 1; static constexpr bool BACK = true; };
+template <int TYPE, int OUT, int LAYOUT_ = 1> struct PairBackHalf : DisplayLuma<TYPE, false, OUT> { static constexpr int LAYOUT = LAYOUT_; static constexpr bool BACK = true; };
+// FRONT3 (front3_task: dense B display tasks, layout 2): the chroma part requests the coefficient rows of the task's three tiles, scans them into
+// one list of live columns and runs ONE column pass over it; the luma parts are back halves (TaskArgs::live_lr: their live columns)
+template <int TYPE> struct Front3Chroma : DisplayChroma<TYPE, false, 2, kOutRgba> { static constexpr bool FRONT3 = true; };
 
 struct TaskArgs {                // what only a few callers of recon_task set
     // a luma-shaped task of k_recon reconstructs the A plane of a yuva picture (wave-uniform; a display task's A part is one by
@@ -852,6 +898,12 @@ struct TaskArgs {                // what only a few callers of recon_task set
     char* tile = nullptr;        // BACK: the part's tile
     uint64_t live[2] = {0, 0};   // BACK: its live columns, per half
     uint32_t qreg = 0u;          // layout 1: the quantiser tables, dword i in lane i (column_pass)
+    // layout 2: the wave's places in the workgroup's array besides its luma tiles (`lds`: left, + kLdsTile: right)
+    char* carry = nullptr;       // the task's vectors, 64 bytes
+    char* ids = nullptr;         // FRONT3: the column ids, kSfIdsPerWave bytes
+    bool has_right = false;      // FRONT3: the task has a right luma part
+    uint64_t (*live_lr)[2] = nullptr;      // FRONT3: the live columns of the left and the right luma tile come back here
+    bool lut_barrier = false;    // BACK: the task's first conversion is this part's -- the workgroup's barrier in front of the tables stands here
 };
 
 // stage 2: column pass over the LIVE columns of both halves
@@ -875,9 +927,14 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
 {
     constexpr int TYPE = V::TYPE, AMODE = V::AMODE, CARRY = V::CARRY, LAYOUT = V::LAYOUT, OUT = V::OUT;
     constexpr bool CHROMA = V::CHROMA, SPARSE = V::SPARSE, DISPLAY = V::DISPLAY, BACK = V::BACK;
-    static_assert(!BACK || (LAYOUT == 1 && CARRY == kCarryTake), "a back half runs on the two-tile layout behind the chroma part");
+    constexpr bool FRONT3 = V::FRONT3;
+    static_assert(!BACK || (LAYOUT != 0 && CARRY == kCarryTake), "a back half runs on the two- and three-tile layouts behind the chroma part");
+    static_assert(FRONT3 == (LAYOUT == 2 && CHROMA), "the chroma part of the three-tile layout runs the front");
     const bool alpha = AMODE == kAlphaPark || args.alpha;
-    char* const tile = BACK ? args.tile : lds;
+    // FRONT3: the chroma tile's first KB (args.tile), its second kSfCHalf behind it
+    char* const tile = BACK || FRONT3 ? args.tile : lds;
+    constexpr int tile_half = FRONT3 ? kSfCHalf : kLdsHalf;
+    char* const carryp = LAYOUT == 2 ? args.carry : lds + Lay<LAYOUT == 2 ? 1 : LAYOUT>::carry;
     const int W = CHROMA ? G.cw >> 1 : G.cw;
     const int H = CHROMA ? G.ch >> 1 : G.ch;
     const int bw = W >> 3;
@@ -926,8 +983,24 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
         // the previous task of this wave may still be reading the tile
         wait_lds_all();
         __builtin_amdgcn_wave_barrier();
+        if constexpr (FRONT3) {
+            coef_rows_to_lds(pd.coef[1], tile, coef_voff, 0u);
+            coef_rows_to_lds(pd.coef[2], tile + kSfCHalf, coef_voff, 0u);
+            // the luma parts' rows: lane (r = hi3, b = lo3) as above, 16 block columns per chroma group, the lower block row 8 W samples on
+            const uint32_t row_off = (uint32_t)__mul24(16 * Rt + hi3, G.cw);
+            const int Ql = 16 * g + lo3, Qr = Ql + 8;
+            const uint32_t vl = (2u * (row_off + (uint32_t)(8 * Ql))) | (Ql < (G.cw >> 3) ? 0u : kOobBit);
+            coef_rows_to_lds(pd.coef[0], lds, vl, 0u);
+            coef_rows_to_lds(pd.coef[0], lds + kLdsHalf, vl, 16u * (uint32_t)G.cw);
+            if (args.has_right) {
+                const uint32_t vr = (2u * (row_off + (uint32_t)(8 * Qr))) | (Qr < (G.cw >> 3) ? 0u : kOobBit);
+                coef_rows_to_lds(pd.coef[0], lds + kLdsTile, vr, 0u);
+                coef_rows_to_lds(pd.coef[0], lds + kLdsTile + kLdsHalf, vr, 16u * (uint32_t)G.cw);
+            }
+        } else {
         coef_rows_to_lds(pd.coef[CHROMA ? 1 : (alpha ? 3 : 0)], lds, coef_voff, 0u);
         coef_rows_to_lds(pd.coef[CHROMA ? 2 : (alpha ? 3 : 0)], lds + kLdsHalf, coef_voff, 2u * half_step);
+        }
     }
     const uint32_t mb = (uint32_t)(CHROMA ? Rt * G.mbw + Qs : Rt * G.mbw + (Qs >> 1));
     uint32_t mf = 0, mk = 0, flags;
@@ -937,8 +1010,8 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
         flags = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)carry.flags);
         // the vectors wait in LDS (the 64 bytes behind the staged tables: kOffCarry) -- carried in registers like the
         // flags, the three words went to scratch memory in the B kernel (12 bytes per lane: +6 % HBM traffic per launch)
-        if (TYPE != 1) mf = *reinterpret_cast<const uint32_t*>(lds + Lay<LAYOUT>::carry + src);
-        if (TYPE == 3) mk = *reinterpret_cast<const uint32_t*>(lds + Lay<LAYOUT>::carry + 32 + src);
+        if (TYPE != 1) mf = *reinterpret_cast<const uint32_t*>(carryp + src);
+        if (TYPE == 3) mk = *reinterpret_cast<const uint32_t*>(carryp + 32 + src);
     } else {
         flags = (uint32_t)(ldg<uint8_t>(gptr(pd.qscale), mb) & 31) | (ldg<uint8_t>(gptr(pd.intra), mb) != 0 ? 256u : 0u);   // I pictures honour the intra map too (COL_3)
         if (TYPE != 1) {
@@ -951,10 +1024,13 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
         }
         if constexpr (CARRY == kCarryLeave) {       // lane i < 8 holds macroblock i of the task (and so does every lane i + 8 k)
             carry.flags = flags;
-            if (TYPE != 1) *reinterpret_cast<uint32_t*>(lds + Lay<LAYOUT>::carry + ((lane & 7) << 2)) = mf;
-            if (TYPE == 3) *reinterpret_cast<uint32_t*>(lds + Lay<LAYOUT>::carry + 32 + ((lane & 7) << 2)) = mk;
+            if (TYPE != 1) *reinterpret_cast<uint32_t*>(carryp + ((lane & 7) << 2)) = mf;
+            if (TYPE == 3) *reinterpret_cast<uint32_t*>(carryp + 32 + ((lane & 7) << 2)) = mk;
         }
     }
+    // FRONT3: the quantiser tables, dword i of the 256 bytes in lane i, requested behind the maps and landed with them
+    uint32_t qreg = args.qreg;
+    if constexpr (FRONT3) qreg = ldg<uint32_t>(gptr(pd.qt), (uint32_t)lane * 4u);
     const int q = (int)(flags & 31u);
     const bool ia = (flags & 256u) != 0u;
     const int x0 = 8 * Qs;
@@ -1019,6 +1095,10 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
         }
     }
 
+    // B: the wave started at priority 3 (k_recon_display) and drops to 0 now that everything its front waits for is requested -- young
+    // waves first: their loads are on the way while the older ones compute.  (One box, ms per mixed B launch: 0.919-0.922 here, 0.936-0.938
+    // in front of the wait for the coefficient rows, 0.939-0.944 behind the chroma part, where the two-front task had it.)
+    if constexpr (FRONT3 && TYPE == 3) __builtin_amdgcn_s_setprio(0);
     // ---- stage 1: the tile [half][r][b][c] ---------------------------------------------------------
     // dense: the rows are there (LDS-direct loads, waited for above); sparse: clear the tile and scatter both runs
     if constexpr (SPARSE) {
@@ -1042,7 +1122,17 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
     wave_sync();
 
     uint64_t live[2] = {args.live[0], args.live[1]};
-    if constexpr (!BACK) column_front<LAYOUT>(pd, lds, tile, lane, qia, args.qreg, live);
+    if constexpr (FRONT3) {
+        // one list, one pass: the chroma tile's live columns, then the left and the right luma tile's
+        ThreeTiles t3{(uint32_t)(tile - lds), 0u, 0u, carry.flags};
+        t3.n_c = scan_tile(tile, args.ids, lane, 0u, 0u, live, kSfCHalf);
+        t3.n_cl = scan_tile(lds, args.ids, lane, 0u, t3.n_c, args.live_lr[0]);
+        uint32_t n_cols = t3.n_cl;
+        if (args.has_right) n_cols = scan_tile(lds + kLdsTile, args.ids, lane, 0u, n_cols, args.live_lr[1]);
+        wave_sync();
+        column_pass<false, false, true>(lds, (uint32_t)kLdsTile, args.ids, nullptr, n_cols, 0, 0, lane, qreg, t3);
+        wave_sync();
+    } else if constexpr (!BACK) column_front<LAYOUT>(pd, lds, tile, lane, qia, qreg, live);
 
 #pragma unroll
     for (int half = 0; half < 2; half++) {
@@ -1060,7 +1150,7 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
             // (exact products, the conversion truncates).  Columns that are dead in every block of the half give
             // zero inputs (wave-uniform): lane (c, b) of the liveness mask -> byte c
             const int cols_live = 8 - (__builtin_clzll(colbits | 1ull) >> 3);
-            const v4u wv = *reinterpret_cast<const v4u*>(tile + half * kLdsHalf + hi3 * 128 + lo3 * 16);
+            const v4u wv = *reinterpret_cast<const v4u*>(tile + half * tile_half + hi3 * 128 + lo3 * 16);
             const v2f k25 = {2.5f, 2.5f};
             const v2f a = v2f{(float)(short)(wv.x & 0xffffu), (float)((int)wv.x >> 16)} * k25;
             const int Y0 = (int)a.x + 128, Y1 = (int)a.y;                           // "+128" of (t+128)/256
@@ -1140,6 +1230,10 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
                 // no display stage: nothing is parked for a conversion
             } else if constexpr (CHROMA) {
                 // park the samples for the luma parts: [plane = half][row hi3][8 bytes of macroblock lo3]
+                if constexpr (FRONT3) {      // the stash is the tile's first KB, whose row pass (stage 3) must have read it out
+                    wait_lds_all();
+                    __builtin_amdgcn_wave_barrier();
+                }
                 *reinterpret_cast<v2u*>(dsp.stash + half * 512 + hi3 * 64 + lo3 * 8) = o;
             } else if constexpr (AMODE == kAlphaPark) {
                 // yuva, A part: the samples wait for the Y part of the same macroblocks
@@ -1155,6 +1249,14 @@ __device__ __forceinline__ void recon_task(const PicDesc& pd, const Geom& G, int
         }
         if constexpr (DISPLAY && !CHROMA && AMODE != kAlphaPark && OUT != kOutYcbcr) {
             wave_sync();
+            if constexpr (LAYOUT == 2) {
+                // the conversion tables lie where every wave's column ids and Cr rows were: the chunks this wave requested (behind
+                // barrier 1, in front of this part's reference rows) have landed, and then every wave's have
+                if (args.lut_barrier && half == 0) {
+                    wait_vmem_all();
+                    __syncthreads();
+                }
+            }
             display_half<AMODE>(pd, G, dsp, Lay<LAYOUT>::park_in_tile ? tile + half * kLdsHalf : lds + kOffYpark, half, Rt, g, hi3, lo3);
             // the next half parks its rows in the same place
             wave_sync();
@@ -1189,10 +1291,6 @@ __device__ __forceinline__ void recon_luma_pair(const PicDesc& pd, const Geom& G
         coef_rows_to_lds(pd.coef[0], tileR, voff, 0u);
         coef_rows_to_lds(pd.coef[0], tileR + kLdsHalf, voff, 16u * (uint32_t)W);
     }
-    // B: the wave started at priority 3 (k_recon_display) and drops to 0 now that its luma coefficient loads are out -- young waves
-    // first: their loads are on the way while the older ones compute.  One box, alternating, ms per mixed B launch: 1.027-1.031
-    // without, 0.992-0.993 with; the step 5.83-5.85 -> 5.73-5.75 ms.  Other drop points and other picture types: no better or slower.
-    if (TYPE == 3) __builtin_amdgcn_s_setprio(0);
     // quantiser scale | intra << 8 of the macroblock of block b of either part, in lane b (the chroma part's lanes hold the task's
     // eight macroblocks: lane m, macroblock m)
     const int qiaL = __builtin_amdgcn_ds_bpermute((lo3 >> 1) << 2, (int)carry.flags) & 0x11f;
@@ -1354,13 +1452,66 @@ __device__ __forceinline__ bool display_task(const PicDesc* __restrict__ descs, 
     return true;
 }
 
+// A dense B display task with one front (front3_task; layout 2, see kSfBytes): the chroma part runs the front for all three tiles and its own back
+// half; barrier 1 -- every wave of the workgroup is through with its column ids and its Cr rows; the wave requests its chunks of the
+// conversion tables into their place and goes on with the left luma part, which meets the others at barrier 2 in front of its first
+// table lookup (recon_task, lut_barrier); the right part.  A wave without a task takes part in both barriers and loads its chunks.
+// The compiler does not order LDS reads behind an LDS-direct load: each wave waits for its own chunks itself (wait_vmem_all in front of
+// barrier 2; the left part's reference rows were requested behind them and are needed before that, so the wait finds the chunks landed).
+template <int TYPE>
+__device__ __forceinline__ void display_task_front3(const PicDesc* __restrict__ descs, const Geom& G, int pic, int t, char* sf, int wave, int lane, const Tables* __restrict__ T)
+{
+    const bool live = t < G.tasks_per_pic && pic < G.n_pics;
+    const PicDesc& pd = descs[live ? pic : 0];
+    const int Rt = div_inv(t, G.inv_gC), gc = t - Rt * G.gC;
+    char* const lds = sf + wave * (2 * kLdsTile);
+    char* const c0 = sf + kSfC0 + wave * kLdsHalf;
+    const bool has_right = 2 * gc + 1 < G.gY;
+    Display dsp{c0, 0, nullptr, sf + kSfLut, nullptr, nullptr};
+    MbCarry carry{};
+    uint64_t live_lr[2][2] = {{0, 0}, {0, 0}};
+    TaskArgs front{};
+    front.tile = c0;
+    front.carry = sf + kSfCarry + wave * 64;
+    front.ids = sf + kSfIds + wave * kSfIdsPerWave;
+    front.has_right = has_right;
+    front.live_lr = live_lr;
+    if (live) recon_task<Front3Chroma<TYPE>>(pd, G, Rt, gc, lds, lane, dsp, carry, front);
+    if (TYPE == 3) __builtin_amdgcn_s_setprio(0);      // (a wave without a task drops here; the others have, in their front)
+    wait_lds_all();
+    __syncthreads();            // barrier 1
+    const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc((void*)T->rgba_lut, 0, kLdsLut, 0x00020000);
+    for (int c = wave; c < kLdsLut / 1024; c += kWavesPerWG)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (__attribute__((address_space(3))) void*)(sf + kSfLut + c * 1024), 16, (int)(lane * 16u), c * 1024, 0, 0);
+    if (!live) {
+        wait_vmem_all();
+        __syncthreads();        // barrier 2
+        return;
+    }
+    TaskArgs part{};
+    part.tile = lds;
+    part.live[0] = live_lr[0][0]; part.live[1] = live_lr[0][1];
+    part.carry = front.carry;
+    part.lut_barrier = true;
+    dsp.side = 0;
+    recon_task<PairBackHalf<TYPE, kOutRgba, 2>>(pd, G, Rt, 2 * gc, lds, lane, dsp, carry, part);
+    if (has_right) {
+        part.tile = lds + kLdsTile;
+        part.live[0] = live_lr[1][0]; part.live[1] = live_lr[1][1];
+        part.lut_barrier = false;
+        dsp.side = 1;
+        recon_task<PairBackHalf<TYPE, kOutRgba, 2>>(pd, G, Rt, 2 * gc + 1, lds, lane, dsp, carry, part);
+    }
+}
+
 template <int TYPE, bool SPARSE, bool ALPHA = false>
 __global__ __launch_bounds__(kReconMaxThreads) __attribute__((amdgpu_waves_per_eu(TYPE == 3 && !ALPHA ? 7 : 4)))
 void k_recon_display(const PicDesc* __restrict__ descs, Geom G,
                                                                     const Tables* __restrict__ T)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // B waves start at priority 3 and drop to 0 in recon_luma_pair.  (The dense, non-alpha kernel only: in the pipeline's sparse
+    // B waves start at priority 3 and drop to 0 in their front (recon_task, FRONT3: one box, alternating, ms per mixed B launch of the
+    // two-front task: 1.027-1.031 without priorities, 0.992-0.993 with; other picture types: no better or slower).  (The dense, non-alpha kernel only: in the pipeline's sparse
     // launches a raised priority takes issue slots from the parser kernels beside them -- 175-177 k against 181-182 k pictures/s end to end)
     if (TYPE == 3 && !SPARSE && !ALPHA) __builtin_amdgcn_s_setprio(3);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1368,6 +1519,11 @@ void k_recon_display(const PicDesc* __restrict__ descs, Geom G,
     const int wg = xcd_remap(blockIdx.x, G.n_wg);
     int pic, twg;
     pic_of_wg<TYPE>(G, wg, pic, twg);
+    if constexpr (front3_task(TYPE, SPARSE, ALPHA)) {
+        // one static array: every LDS address of the task is a compile-time constant plus a multiple of the wave's number
+        __shared__ __attribute__((aligned(16))) char sf_s[kSfBytes];
+        display_task_front3<TYPE>(descs, G, pic, twg * kWavesPerWG + wave, sf_s, wave, lane0, T);
+    } else {
     const int wpw = (int)(blockDim.x >> 6);
     // the conversion tables: 5 KB per workgroup, requested before anything else and needed only after the
     // chroma part -- the barrier in display_task finds them long landed.  Straight into LDS, 1 KB per instruction (lane i's 16
@@ -1388,6 +1544,7 @@ void k_recon_display(const PicDesc* __restrict__ descs, Geom G,
     // works on the next: 5.89-5.92 ms per step with two against 5.90-5.95 with one, worse with three and five, and 10-20 registers more
     // for the loop -- not kept.)
     display_task<TYPE, SPARSE, ALPHA>(descs, G, pic, twg * wpw + wave, lds, lane0, reinterpret_cast<const char*>(lut_s), true);
+    }
 }
 
 
