@@ -3,6 +3,7 @@
 // There is no CPU path in this library: without a device every call fails.
 #include "leon_kernels.h"
 #include "leon_rgba_lut.h"
+#include "leon_owned.h"
 #include "../../include/leon.h"
 
 #include <hip/hip_runtime.h>
@@ -64,12 +65,47 @@ const uint8_t kPremultiplier[64] = {
     32, 44, 42, 38, 32, 25, 17,  9, 25, 35, 33, 30, 25, 20, 14,  7,
     17, 24, 23, 20, 17, 14,  9,  5,  9, 12, 12, 10,  9,  7,  5,  2};
 
+// How the host owns what it gets from the runtime (leon_owned.h): the policies are defined beside big_alloc, below.
+// Device memory goes through big_alloc(kind, asked) / big_free -- kind 0: an ordinary allocation -- pinned memory through
+// hipHostMalloc / hipHostFree, events and streams through their create and destroy calls.
+struct DeviceMem {
+    static constexpr bool kHostAddressable = false;
+    static void* get(size_t bytes, int kind = 0, bool asked = false);
+    static void give(void* p);
+};
+struct PinnedMem {
+    static constexpr bool kHostAddressable = true;
+    static void* get(size_t bytes);
+    static void give(void* p);
+};
+struct EventTraits {
+    using type = hipEvent_t;
+    static hipEvent_t create(unsigned flags = hipEventDefault);
+    static void destroy(hipEvent_t e);
+};
+struct StreamTraits {
+    using type = hipStream_t;
+    static hipStream_t create(unsigned flags);
+    static hipStream_t create(unsigned flags, int priority);
+    static void destroy(hipStream_t s);
+};
+template <class T = char> using DevBuf = leon_owned::Buffer<DeviceMem, T>;
+template <class T = char> using PinnedBuf = leon_owned::Buffer<PinnedMem, T>;
+template <class T> using Mirror = leon_owned::Mirror<PinnedMem, DeviceMem, T>;       // host(): pinned, dev(): its device twin
+using Event = leon_owned::Handle<EventTraits>;
+using Stream = leon_owned::Handle<StreamTraits>;
+using leon_owned::Grow;
+using leon_owned::cap_for;
+
+// LEON_ERR_HIP / LEON_ERR_NOMEM with the runtime's last error as text: a resource the runtime refused
+int refused(int code, const char* what);
+
 struct TimedLaunch {
-    hipEvent_t a, b;
-    int kind;
-    int pic_type;      // reconstruction launches: LEON_PIC_I/P/B, else 0
-    double bytes;
-    uint64_t mbs;
+    Event a, b;
+    int kind = 0;
+    int pic_type = 0;  // reconstruction launches: LEON_PIC_I/P/B, else 0
+    double bytes = 0;
+    uint64_t mbs = 0;
 };
 
 // SURVEY.md 8d / BASELINE.md section 2: algorithmic bytes per macroblock -- priced by what the
@@ -143,10 +179,10 @@ AnyPic any_of(const leon_sparse_picture& q)
 // kOutSlots nothing (k_recon), kOutRgba (k_recon_display), kOutYcbcr the frame's planes, kOutBoth (k_recon_display_out)
 constexpr int kClasses = 12;
 
-struct Staging {                 // device copy of one host-submitted picture
-    char* base = nullptr;
-    char* host = nullptr;        // pinned mirror: the caller's arrays are gathered here, then ONE async copy
-    hipEvent_t done = nullptr;
+struct Staging {                 // device copy of one host-submitted picture: all three made together, at the entry's first use
+    DevBuf<> base;
+    PinnedBuf<> host;            // pinned mirror: the caller's arrays are gathered here, then ONE async copy
+    Event done;
     bool busy = false;
 };
 
@@ -154,7 +190,7 @@ struct Staging {                 // device copy of one host-submitted picture
 
 struct leon_batch {
     // descriptors sorted by launch class (class_of); a batch of leon_picture holds classes 0 .. 5 only
-    PicDesc* d_descs = nullptr;
+    DevBuf<PicDesc> d_descs;
     int n = 0;
     int count[kClasses] = {};
     std::vector<int32_t> out_slots;
@@ -166,101 +202,88 @@ struct leon_batch {
 struct leon_decoder {
     leon_config cfg{};
     int dev = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    // display conversion overlapped with reconstruction (leon_set_overlap_convert)
+    // (streams and events stand in front of the buffers their work touches: members go in reverse order, the buffers first)
+    Stream stream;               // the decoder's own, or leon_config.stream borrowed
+    // display conversion overlapped with reconstruction (leon_set_overlap_convert): stream, events and conv_pending are made together
     bool overlap_convert = false;
-    hipStream_t conv_stream = nullptr;
-    hipEvent_t ev_recon_done = nullptr;   // recorded on `stream`, waited on by conv_stream
-    hipEvent_t ev_conv_done = nullptr;    // recorded on conv_stream after each conversion
+    Stream conv_stream;
+    Event ev_recon_done;                  // recorded on `stream`, waited on by conv_stream
+    Event ev_conv_done;                   // recorded on conv_stream after each conversion
     std::vector<uint8_t> conv_pending;    // per slot: a conversion may still be reading it
     Geom geom{};
     size_t plane_bytes = 0;      // cw*ch*3/2
     size_t slot_stride = 0;      // padded
-    uint8_t* d_slots = nullptr;
+    DevBuf<uint8_t> d_slots;     // a contiguous ring goes back to the process's pool, never to the driver (big_alloc)
     std::vector<uint8_t> inuse;
     // batch independence check (check_batch): which picture of the current batch writes a slot
     std::vector<uint32_t> writer_epoch;
     std::vector<int32_t> writer_of;
     uint32_t epoch = 0;
     Tables h_tables{};
-    Tables* d_tables = nullptr;       // matrix set 0 (leon_set_quant_matrices) + the conversion tables
+    DevBuf<Tables> d_tables;          // matrix set 0 (leon_set_quant_matrices) + the conversion tables
     uint8_t qm[128];
     // matrix sets 1 .. kMaxQSets - 1 (leon_add_quant_matrices): the sequences of a stream whose headers carry other
     // matrices than the first (decoders/jsv.js:540-558); a picture names its set (leon_picture.qm_set)
     static constexpr int kMaxQSets = 256;
-    QTables* d_qsets = nullptr;       // [kMaxQSets], entry 0 unused
-    QTables* h_qsets = nullptr;       // pinned mirror: the source of the asynchronous uploads stays valid
+    Mirror<QTables> qset_tabs;        // [kMaxQSets], entry 0 unused; the pinned side: the source of the asynchronous uploads stays valid
     std::vector<std::array<uint8_t, 128>> qsets;      // [0] unused; the matrices of set i, for the lookup
     // host-submit staging ring
     static constexpr int kStages = 4;
     Staging stages[kStages];
     size_t stage_bytes = 0;
     int next_stage = 0;
-    PicDesc* d_desc_ring = nullptr;   // kDescRing descriptors for ad-hoc submits
-    PicDesc* h_desc_pinned = nullptr;
+    Mirror<PicDesc> desc_ring;        // kDescRing descriptors for ad-hoc submits
     // beside each descriptor of the ring: the frame-planes record of a picture with YCbCr output (FrameOut::frames); allocated
     // with the first such batch
-    uint8_t** d_frames_ring = nullptr;
-    uint8_t** h_frames_pinned = nullptr;
+    Mirror<uint8_t*> frames_ring;
     FrameOut frame_out{};             // the frames' plane layout (frames = null), planes_layout()
     // k_planes_crop: the batch's source slots and destinations
-    int32_t* d_crop_slots = nullptr;
-    int32_t* h_crop_slots = nullptr;
-    uint8_t** d_crop_frames = nullptr;
-    uint8_t** h_crop_frames = nullptr;
+    Mirror<int32_t> crop_slots;       // (made together with crop_frames)
+    Mirror<uint8_t*> crop_frames;
     int crop_head = 0;
     // A lap of the ring is 65536 pictures; a range is reused only after the launches that read it have finished -- not by
     // waiting for the STREAM at the wrap (the pipeline lost five windows' time, 45 ms, every 65536 pictures that way) but
     // for the event recorded behind the last launch of that range, a lap ago: long since signalled.
     static constexpr int kDescRing = 65536;
     static constexpr int kDescEventEvery = 2048;       // descriptors per event
-    struct DescUse { int begin, end; hipEvent_t ev; };
+    struct DescUse { int begin, end; Event ev; };
     std::deque<DescUse> desc_uses;                      // in the order they were recorded
-    std::vector<hipEvent_t> desc_ev_pool;
+    std::vector<Event> desc_ev_pool;
     int desc_head = 0, desc_open_begin = 0, desc_open_end = 0;      // [open_begin, open_end): committed, no event behind it yet
     // rgba
-    int32_t* d_slot_ids = nullptr;
-    int32_t* h_slot_ids = nullptr;
+    Mirror<int32_t> slot_ids;
     static constexpr int kSlotIdRing = 8192;
     int slot_id_head = 0;
-    uint8_t* d_rgba_tmp = nullptr;
+    DevBuf<uint8_t> d_rgba_tmp;
     // timing
     bool timing = false;
     std::vector<TimedLaunch> timed;
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<Event> ev_pool;
 };
 
 namespace {
 
-// nullptr (and the thread's error text) when the runtime cannot give out another event
-hipEvent_t get_event(leon_decoder* d)
+// an event of `pool`, or a new one; empty (and the thread's error text) when the runtime cannot give out another
+Event get_event(std::vector<Event>& pool, unsigned flags = hipEventDefault)
 {
-    if (!d->ev_pool.empty()) {
-        hipEvent_t e = d->ev_pool.back();
-        d->ev_pool.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    hipError_t rc = hipEventCreate(&e);
-    if (rc != hipSuccess) {
-        fail(LEON_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(rc));
-        return nullptr;
-    }
+    Event e;
+    if (!pool.empty()) {
+        e = std::move(pool.back());
+        pool.pop_back();
+    } else if (!e.create(flags)) refused(LEON_ERR_HIP, "hipEventCreate");
     return e;
 }
 
 // both events of a timed launch, or LEON_ERR_HIP with nothing leaked
-int get_event_pair(leon_decoder* d, hipEvent_t& a, hipEvent_t& b)
+int get_event_pair(leon_decoder* d, Event& a, Event& b)
 {
-    a = get_event(d);
-    if (!a) return LEON_ERR_HIP;
-    b = get_event(d);
-    if (!b) {
-        d->ev_pool.push_back(a);
-        a = nullptr;
+    Event first = get_event(d->ev_pool), second = get_event(d->ev_pool);
+    if (!first || !second) {
+        if (first) d->ev_pool.push_back(std::move(first));
         return LEON_ERR_HIP;
     }
+    a = std::move(first);
+    b = std::move(second);
     return LEON_OK;
 }
 
@@ -390,7 +413,7 @@ void fill_desc(const leon_decoder* d, const AnyPic& a, PicDesc& o)
     o.rgba = (uint8_t*)p.rgba_out;
     o.no_planes = p.rgba_out || a.planes_out ? p.no_planes : 0;
     o.pad_ = 0;
-    o.qt = p.qm_set > 0 ? d->d_qsets + p.qm_set : &d->d_tables->q;
+    o.qt = p.qm_set > 0 ? &d->qset_tabs.dev()[p.qm_set] : &d->d_tables->q;
 }
 
 // a submit that overwrites a slot still being converted on the second stream waits for it
@@ -466,7 +489,7 @@ int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, 
     if (wgs > 0x7fffffffLL || wgs * G.wg_per_pic >= (1LL << 32))
         return fail(LEON_ERR_INVALID, "batch of %d pictures is too large for one launch; split it", n);
     G.n_wg = (int)wgs;
-    TimedLaunch tl{};
+    TimedLaunch tl;
     if (d->timing) {
         if (get_event_pair(d, tl.a, tl.b) != LEON_OK) return LEON_ERR_HIP;
         tl.kind = 0;
@@ -493,7 +516,7 @@ int launch_recon_type(leon_decoder* d, int type, const PicDesc* d_descs, int n, 
     HIP_TRY(hipGetLastError());
     if (d->timing) {
         HIP_TRY(hipEventRecord(tl.b, d->stream));
-        d->timed.push_back(tl);
+        d->timed.push_back(std::move(tl));
     }
     return LEON_OK;
 }
@@ -661,15 +684,48 @@ hipError_t big_free(void* p)
     return hipFree(p);
 }
 
+// The policies of the owning types (leon_owned.h).  What the destroy calls return is dropped here and nowhere else: there is
+// nobody to tell, and the owner has made sure that nothing in flight uses what goes (big_free).
+void* DeviceMem::get(size_t bytes, int kind, bool asked)
+{
+    void* p = nullptr;
+    return big_alloc(&p, bytes, kind, nullptr, asked) == hipSuccess ? p : nullptr;
+}
+void DeviceMem::give(void* p) { (void)big_free(p); }
+void* PinnedMem::get(size_t bytes)
+{
+    void* p = nullptr;
+    return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+}
+void PinnedMem::give(void* p) { (void)hipHostFree(p); }
+hipEvent_t EventTraits::create(unsigned flags)
+{
+    hipEvent_t e = nullptr;
+    return hipEventCreateWithFlags(&e, flags) == hipSuccess ? e : nullptr;
+}
+void EventTraits::destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+hipStream_t StreamTraits::create(unsigned flags)
+{
+    hipStream_t s = nullptr;
+    return hipStreamCreateWithFlags(&s, flags) == hipSuccess ? s : nullptr;
+}
+hipStream_t StreamTraits::create(unsigned flags, int priority)
+{
+    hipStream_t s = nullptr;
+    return hipStreamCreateWithPriority(&s, flags, priority) == hipSuccess ? s : nullptr;
+}
+void StreamTraits::destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
+
+int refused(int code, const char* what) { return fail(code, "%s: %s", what, hipGetErrorString(hipGetLastError())); }
+
 // an event behind everything committed so far
 int close_desc_range(leon_decoder* d)
 {
     if (d->desc_open_end == d->desc_open_begin) return LEON_OK;
-    hipEvent_t ev = nullptr;
-    if (!d->desc_ev_pool.empty()) { ev = d->desc_ev_pool.back(); d->desc_ev_pool.pop_back(); }
-    else HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    Event ev = get_event(d->desc_ev_pool, hipEventDisableTiming);
+    if (!ev) return LEON_ERR_HIP;
     HIP_TRY(hipEventRecord(ev, d->stream));
-    d->desc_uses.push_back(leon_decoder::DescUse{d->desc_open_begin, d->desc_open_end, ev});
+    d->desc_uses.push_back(leon_decoder::DescUse{d->desc_open_begin, d->desc_open_end, std::move(ev)});
     d->desc_open_begin = d->desc_open_end;
     return LEON_OK;
 }
@@ -679,10 +735,10 @@ int reserve_descs(leon_decoder* d, int n, int& at)
 {
     if (n > leon_decoder::kDescRing) return fail(LEON_ERR_INVALID, "batch of %d pictures exceeds %d; use leon_batch_create", n, leon_decoder::kDescRing);
     auto retire = [&](void) -> int {
-        leon_decoder::DescUse u = d->desc_uses.front();
+        leon_decoder::DescUse u = std::move(d->desc_uses.front());
         d->desc_uses.pop_front();
         HIP_TRY(hipEventSynchronize(u.ev));
-        d->desc_ev_pool.push_back(u.ev);
+        d->desc_ev_pool.push_back(std::move(u.ev));
         return LEON_OK;
     };
     if (d->desc_head + n > leon_decoder::kDescRing) {                 // wrap: the tail stays unused this lap
@@ -750,13 +806,10 @@ int leon_create(const leon_config* cfg, leon_decoder** out)
     d->cfg = *cfg;
     d->dev = cfg->device_id;
     if (cfg->stream) {
-        d->stream = (hipStream_t)cfg->stream;
-    } else {
-        if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete d;
-            return fail(LEON_ERR_HIP, "hipStreamCreate failed");
-        }
-        d->own_stream = true;
+        d->stream.borrow((hipStream_t)cfg->stream);
+    } else if (!d->stream.create(hipStreamNonBlocking)) {
+        delete d;
+        return fail(LEON_ERR_HIP, "hipStreamCreate failed");
     }
     Geom& G = d->geom;
     G.cw = cfg->coded_width;
@@ -785,17 +838,15 @@ int leon_create(const leon_config* cfg, leon_decoder** out)
         leon_destroy(d);
         return fail(LEON_ERR_NOMEM, "%s", msg.c_str());
     };
-    if (big_alloc((void**)&d->d_slots, d->slot_stride * (size_t)cfg->n_slots + 256, kBigSlots, nullptr, cfg->contiguous_slots == 1) != hipSuccess) return bail("slot ring");
+    if (!d->d_slots.alloc(d->slot_stride * (size_t)cfg->n_slots + 256, kBigSlots, cfg->contiguous_slots == 1)) return bail("slot ring");
     if (hipMemsetAsync(d->d_slots, 0, d->slot_stride * (size_t)cfg->n_slots + 256, d->stream) != hipSuccess) return bail("slot memset");
-    if (hipMalloc(&d->d_tables, sizeof(Tables)) != hipSuccess) return bail("tables");
+    if (!d->d_tables.alloc(sizeof(Tables))) return bail("tables");
     memcpy(d->qm, kDefaultIntra, 64);
     memset(d->qm + 64, 16, 64);
     upload_tables(d);
     if (hipMemcpyAsync(d->d_tables, &d->h_tables, sizeof(Tables), hipMemcpyHostToDevice, d->stream) != hipSuccess) return bail("tables upload");
-    if (hipMalloc(&d->d_desc_ring, sizeof(PicDesc) * leon_decoder::kDescRing) != hipSuccess) return bail("descriptor ring");
-    if (hipHostMalloc((void**)&d->h_desc_pinned, sizeof(PicDesc) * leon_decoder::kDescRing) != hipSuccess) return bail("pinned descriptors");
-    if (hipMalloc(&d->d_slot_ids, sizeof(int32_t) * leon_decoder::kSlotIdRing) != hipSuccess) return bail("slot id ring");
-    if (hipHostMalloc((void**)&d->h_slot_ids, sizeof(int32_t) * leon_decoder::kSlotIdRing) != hipSuccess) return bail("pinned slot ids");
+    if (!d->desc_ring.alloc(leon_decoder::kDescRing)) return bail("descriptor ring");
+    if (!d->slot_ids.alloc(leon_decoder::kSlotIdRing)) return bail("slot id ring");
     // staging for host-memory pictures: coef planes (2 bytes/sample) + 5 byte maps + 2 vector maps
     const size_t n_groups = (size_t)n_groups_of(d->geom);
     // coefficients: dense planes (2 B each) or, at worst, one 4-byte entry each plus the group offsets
@@ -814,40 +865,7 @@ void leon_destroy(leon_decoder* d)
     // device is not something to lean on -- and not promised for memory from hipExtMallocWithFlags)
     if (d->stream) hipStreamSynchronize(d->stream);
     if (d->conv_stream) hipStreamSynchronize(d->conv_stream);
-    for (auto& t : d->timed) {
-        hipEventDestroy(t.a);
-        hipEventDestroy(t.b);
-    }
-    for (auto e : d->ev_pool) hipEventDestroy(e);
-    for (auto& u : d->desc_uses) hipEventDestroy(u.ev);
-    for (auto e : d->desc_ev_pool) hipEventDestroy(e);
-    for (auto& s : d->stages) {
-        if (s.base) hipFree(s.base);
-        if (s.host) hipHostFree(s.host);
-        if (s.done) hipEventDestroy(s.done);
-    }
-    if (d->d_slots) big_free(d->d_slots);          // a contiguous ring goes back to the process's pool, never to the driver (big_alloc)
-    if (d->d_tables) hipFree(d->d_tables);
-    if (d->d_qsets) hipFree(d->d_qsets);
-    if (d->h_qsets) hipHostFree(d->h_qsets);
-    if (d->d_desc_ring) hipFree(d->d_desc_ring);
-    if (d->h_desc_pinned) hipHostFree(d->h_desc_pinned);
-    if (d->d_frames_ring) hipFree(d->d_frames_ring);
-    if (d->h_frames_pinned) hipHostFree(d->h_frames_pinned);
-    if (d->d_crop_slots) hipFree(d->d_crop_slots);
-    if (d->h_crop_slots) hipHostFree(d->h_crop_slots);
-    if (d->d_crop_frames) hipFree(d->d_crop_frames);
-    if (d->h_crop_frames) hipHostFree(d->h_crop_frames);
-    if (d->d_slot_ids) hipFree(d->d_slot_ids);
-    if (d->h_slot_ids) hipHostFree(d->h_slot_ids);
-    if (d->d_rgba_tmp) hipFree(d->d_rgba_tmp);
-    if (d->conv_stream) {
-        hipStreamDestroy(d->conv_stream);
-        hipEventDestroy(d->ev_recon_done);
-        hipEventDestroy(d->ev_conv_done);
-    }
-    if (d->own_stream && d->stream) hipStreamDestroy(d->stream);
-    delete d;
+    delete d;      // the members give back what they own: buffers and events first, the streams last (the order of declaration, reversed)
 }
 
 int leon_set_quant_matrices(leon_decoder* d, const uint8_t* intra64, const uint8_t* non_intra64)
@@ -874,21 +892,16 @@ int leon_add_quant_matrices(leon_decoder* d, const uint8_t* intra64, const uint8
     if (non_intra64) memcpy(m.data() + 64, non_intra64, 64); else memset(m.data() + 64, 16, 64);
     for (size_t i = 1; i < d->qsets.size(); i++)
         if (d->qsets[i] == m) { *set = (int32_t)i; return LEON_OK; }
-    if (!d->d_qsets) {       // both buffers or neither: a decoder never holds d_qsets without h_qsets
-        QTables *dq = nullptr, *hq = nullptr;
-        HIP_TRY(hipMalloc(&dq, sizeof(QTables) * leon_decoder::kMaxQSets));
-        const hipError_t e = hipHostMalloc((void**)&hq, sizeof(QTables) * leon_decoder::kMaxQSets);
-        if (e != hipSuccess) { hipFree(dq); return fail(LEON_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)); }
-        d->d_qsets = dq;
-        d->h_qsets = hq;
+    if (!d->qset_tabs) {
+        if (!d->qset_tabs.alloc(leon_decoder::kMaxQSets)) return refused(LEON_ERR_HIP, "matrix sets");
         d->qsets.assign(1, std::array<uint8_t, 128>{});
     }
     if ((int)d->qsets.size() >= leon_decoder::kMaxQSets)
         return fail(LEON_ERR_INVALID, "a decoder holds at most %d different sets of quantiser matrices", leon_decoder::kMaxQSets - 1);
     const size_t id = d->qsets.size();
-    fill_qtables(d->h_qsets[id], m.data());
+    fill_qtables(d->qset_tabs.host()[id], m.data());
     // a set is written once and never changed: the upload is ordered in front of the launches that name it by the stream
-    HIP_TRY(hipMemcpyAsync(d->d_qsets + id, d->h_qsets + id, sizeof(QTables), hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->qset_tabs.dev() + id, d->qset_tabs.host() + id, sizeof(QTables), hipMemcpyHostToDevice, d->stream));
     d->qsets.push_back(m);
     *set = (int32_t)id;
     return LEON_OK;
@@ -944,14 +957,14 @@ int submit_picture_any(leon_decoder* d, const AnyPic& pic)
     Staging& s = d->stages[d->next_stage];
     d->next_stage = (d->next_stage + 1) % leon_decoder::kStages;
     if (!s.base) {
-        HIP_TRY(hipMalloc(&s.base, d->stage_bytes));
-        HIP_TRY(hipHostMalloc((void**)&s.host, d->stage_bytes, hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+        Staging made;
+        if (!made.base.alloc(d->stage_bytes) || !made.host.alloc(d->stage_bytes) || !made.done.create(hipEventDisableTiming)) return refused(LEON_ERR_HIP, "staging entry");
+        s = std::move(made);
     }
     if (s.busy) HIP_TRY(hipEventSynchronize(s.done));
     const size_t ny = (size_t)G.cw * G.ch, nc = ny >> 2, mbs = (size_t)G.mbw * G.mbh;
     const MapLayout M = map_layout(mbs, n_groups);
-    char* p = s.base;
+    char* p = s.base.get();
     AnyPic dp = pic;
     // The pieces are gathered into the pinned mirror with plain memcpy and cross PCIe in one
     // asynchronous copy: the caller gets its arrays (and its thread) back after the gather, where
@@ -983,16 +996,16 @@ int submit_picture_any(leon_decoder* d, const AnyPic& pic)
     int at = 0;
     rc = reserve_descs(d, 1, at);
     if (rc != LEON_OK) return rc;
-    fill_desc(d, dp, d->h_desc_pinned[at]);
+    fill_desc(d, dp, d->desc_ring.host()[at]);
     rc = guard_pending_conversions(d, &dp.p.out_slot, 1);
     if (rc != LEON_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(d->d_desc_ring + at, d->h_desc_pinned + at, sizeof(PicDesc), hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->desc_ring.dev() + at, d->desc_ring.host() + at, sizeof(PicDesc), hipMemcpyHostToDevice, d->stream));
     double bytes = 0;
     if (d->timing) {
         rc = algo_bytes_of(d, pic.p, false, bytes);
         if (rc != LEON_OK) return rc;
     }
-    rc = launch_recon_type(d, type, d->d_desc_ring + at, 1, bytes, pic.sparse, pic.n_entries, pic.p.rgba_out ? kOutRgba : kOutSlots);
+    rc = launch_recon_type(d, type, d->desc_ring.dev() + at, 1, bytes, pic.sparse, pic.n_entries, pic.p.rgba_out ? kOutRgba : kOutSlots);
     if (rc != LEON_OK) return rc;
     rc = commit_descs(d, at, 1);
     if (rc != LEON_OK) return rc;
@@ -1047,11 +1060,7 @@ int submit_batch_any(leon_decoder* d, const AnyPic* pics, int n, int mem)
     bool any_frames = false;
     for (int i = 0; i < n; i++) any_frames = any_frames || pics[i].planes_out;
     if (any_frames && mem != LEON_MEM_DEVICE) return fail(LEON_ERR_INVALID, "frame planes output needs device-resident pictures");
-    if (any_frames && !d->d_frames_ring) {
-        if (hipMalloc(&d->d_frames_ring, sizeof(uint8_t*) * leon_decoder::kDescRing) != hipSuccess ||
-            hipHostMalloc((void**)&d->h_frames_pinned, sizeof(uint8_t*) * leon_decoder::kDescRing) != hipSuccess)
-            return fail(LEON_ERR_NOMEM, "frame-planes descriptor ring");
-    }
+    if (any_frames && !d->frames_ring && !d->frames_ring.alloc(leon_decoder::kDescRing)) return fail(LEON_ERR_NOMEM, "frame-planes descriptor ring");
     if (mem == LEON_MEM_HOST) {
         for (int i = 0; i < n; i++) {
             rc = submit_picture_any(d, pics[i]);
@@ -1070,7 +1079,7 @@ int submit_batch_any(leon_decoder* d, const AnyPic* pics, int n, int mem)
     }
     int count[kClasses];
     uint64_t entries[kClasses];
-    sorted_descs(d, pics, n, d->h_desc_pinned + at, count, entries, any_frames ? d->h_frames_pinned + at : nullptr);
+    sorted_descs(d, pics, n, d->desc_ring.host() + at, count, entries, any_frames ? d->frames_ring.host() + at : nullptr);
     double bytes[kClasses] = {};
     if (d->timing)   // a measurement mode: the maps are read back to price the launches
         for (int i = 0; i < n; i++) {
@@ -1079,9 +1088,9 @@ int submit_batch_any(leon_decoder* d, const AnyPic* pics, int n, int mem)
             if (rc != LEON_OK) return rc;
             bytes[class_of(pics[i])] += b;
         }
-    HIP_TRY(hipMemcpyAsync(d->d_desc_ring + at, d->h_desc_pinned + at, sizeof(PicDesc) * n, hipMemcpyHostToDevice, d->stream));
-    if (any_frames) HIP_TRY(hipMemcpyAsync(d->d_frames_ring + at, d->h_frames_pinned + at, sizeof(uint8_t*) * n, hipMemcpyHostToDevice, d->stream));
-    rc = launch_recon(d, d->d_desc_ring + at, count, bytes, pics[0].sparse, entries, any_frames ? d->d_frames_ring + at : nullptr);
+    HIP_TRY(hipMemcpyAsync(d->desc_ring.dev() + at, d->desc_ring.host() + at, sizeof(PicDesc) * n, hipMemcpyHostToDevice, d->stream));
+    if (any_frames) HIP_TRY(hipMemcpyAsync(d->frames_ring.dev() + at, d->frames_ring.host() + at, sizeof(uint8_t*) * n, hipMemcpyHostToDevice, d->stream));
+    rc = launch_recon(d, d->desc_ring.dev() + at, count, bytes, pics[0].sparse, entries, any_frames ? d->frames_ring.dev() + at : nullptr);
     if (rc != LEON_OK) return rc;
     return commit_descs(d, at, n);
 }
@@ -1109,13 +1118,12 @@ int batch_create_any(leon_decoder* d, const AnyPic* pics, int n, leon_batch** ou
     }
     b->out_slots.resize(n);
     for (int i = 0; i < n; i++) b->out_slots[i] = pics[i].p.out_slot;
-    if (hipMalloc(&b->d_descs, sizeof(PicDesc) * n) != hipSuccess) {
+    if (!b->d_descs.alloc(sizeof(PicDesc) * n)) {
         delete b;
         return fail(LEON_ERR_NOMEM, "descriptor allocation failed");
     }
     hipError_t e = hipMemcpy(b->d_descs, h.data(), sizeof(PicDesc) * n, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        hipFree(b->d_descs);
         delete b;
         return fail(LEON_ERR_HIP, "descriptor upload: %s", hipGetErrorString(e));
     }
@@ -1133,10 +1141,12 @@ int crop_planes_batch(leon_decoder* d, const int32_t* slots, uint8_t* const* fra
         if (slots[i] < 0 || slots[i] >= d->cfg.n_slots) return fail(LEON_ERR_INVALID, "slot %d", slots[i]);
         if (!frames[i] || ((size_t)frames[i] & 255)) return fail(LEON_ERR_INVALID, "frame planes must be 256-byte aligned");
     }
-    if (!d->d_crop_slots) {
-        if (hipMalloc(&d->d_crop_slots, sizeof(int32_t) * kRing) != hipSuccess || hipHostMalloc((void**)&d->h_crop_slots, sizeof(int32_t) * kRing) != hipSuccess ||
-            hipMalloc(&d->d_crop_frames, sizeof(uint8_t*) * kRing) != hipSuccess || hipHostMalloc((void**)&d->h_crop_frames, sizeof(uint8_t*) * kRing) != hipSuccess)
-            return fail(LEON_ERR_NOMEM, "planes crop ring");
+    if (!d->crop_slots) {
+        Mirror<int32_t> cs;
+        Mirror<uint8_t*> cf;
+        if (!cs.alloc(kRing) || !cf.alloc(kRing)) return fail(LEON_ERR_NOMEM, "planes crop ring");
+        d->crop_slots = std::move(cs);
+        d->crop_frames = std::move(cf);
     }
     if (d->crop_head + n > kRing) {                 // a lap: what the ring's launches read has been read
         HIP_TRY(hipStreamSynchronize(d->stream));
@@ -1144,12 +1154,12 @@ int crop_planes_batch(leon_decoder* d, const int32_t* slots, uint8_t* const* fra
     }
     const int at = d->crop_head;
     d->crop_head += n;
-    memcpy(d->h_crop_slots + at, slots, sizeof(int32_t) * n);
-    memcpy(d->h_crop_frames + at, frames, sizeof(uint8_t*) * n);
-    HIP_TRY(hipMemcpyAsync(d->d_crop_slots + at, d->h_crop_slots + at, sizeof(int32_t) * n, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->d_crop_frames + at, d->h_crop_frames + at, sizeof(uint8_t*) * n, hipMemcpyHostToDevice, d->stream));
+    memcpy(d->crop_slots.host() + at, slots, sizeof(int32_t) * n);
+    memcpy(d->crop_frames.host() + at, frames, sizeof(uint8_t*) * n);
+    HIP_TRY(hipMemcpyAsync(d->crop_slots.dev() + at, d->crop_slots.host() + at, sizeof(int32_t) * n, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->crop_frames.dev() + at, d->crop_frames.host() + at, sizeof(uint8_t*) * n, hipMemcpyHostToDevice, d->stream));
     FrameOut fo = d->frame_out;
-    fo.frames = d->d_crop_frames + at;
+    fo.frames = d->crop_frames.dev() + at;
     CropGeom G{};
     G.cw = d->cfg.coded_width; G.ch = d->cfg.coded_height;
     G.fw = d->cfg.frame_width; G.fh = d->cfg.frame_height;
@@ -1161,7 +1171,7 @@ int crop_planes_batch(leon_decoder* d, const int32_t* slots, uint8_t* const* fra
     const size_t pieces = std::max((size_t)(G.fw + 15) / 16 * (size_t)G.fh, (size_t)(G.cwid + 7) / 8 * (size_t)fo.chroma_height);
     if (pieces == 0) return LEON_OK;
     hipLaunchKernelGGL(k_planes_crop, dim3((unsigned)((pieces + kRgbaBlock - 1) / kRgbaBlock), G.alpha ? 4 : 3, n), dim3(kRgbaBlock), 0, d->stream,
-                       d->d_slots, d->d_crop_slots + at, fo, G);
+                       d->d_slots, d->crop_slots.dev() + at, fo, G);
     HIP_TRY(hipGetLastError());
     return LEON_OK;
 }
@@ -1224,7 +1234,6 @@ void leon_batch_destroy(leon_decoder* d, leon_batch* b)
         hipSetDevice(d->dev);
         hipStreamSynchronize(d->stream);
     }
-    if (b->d_descs) hipFree(b->d_descs);
     delete b;
 }
 
@@ -1243,14 +1252,14 @@ int leon_convert_rgba_batch(leon_decoder* d, const int32_t* slots, int32_t n, vo
     }
     int at = d->slot_id_head;
     d->slot_id_head += n;
-    memcpy(d->h_slot_ids + at, slots, sizeof(int32_t) * n);
+    memcpy(d->slot_ids.host() + at, slots, sizeof(int32_t) * n);
     hipStream_t cs = d->stream;
     if (d->overlap_convert) {      // second stream, ordered behind the reconstruction submitted so far
         cs = d->conv_stream;
         HIP_TRY(hipEventRecord(d->ev_recon_done, d->stream));
         HIP_TRY(hipStreamWaitEvent(cs, d->ev_recon_done, 0));
     }
-    HIP_TRY(hipMemcpyAsync(d->d_slot_ids + at, d->h_slot_ids + at, sizeof(int32_t) * n, hipMemcpyHostToDevice, cs));
+    HIP_TRY(hipMemcpyAsync(d->slot_ids.dev() + at, d->slot_ids.host() + at, sizeof(int32_t) * n, hipMemcpyHostToDevice, cs));
     RgbaGeom G{};
     G.cw = d->cfg.coded_width;
     G.ch = d->cfg.coded_height;
@@ -1266,7 +1275,7 @@ int leon_convert_rgba_batch(leon_decoder* d, const int32_t* slots, int32_t n, vo
         const uint32_t c4 = (uint32_t)G.fw >> 2;
         G.inv_cols4 = c4 <= 1 ? 0u : (uint32_t)(((1ull << 32) + c4 - 1) / c4);
     }
-    TimedLaunch tl{};
+    TimedLaunch tl;
     if (d->timing) {
         if (get_event_pair(d, tl.a, tl.b) != LEON_OK) return LEON_ERR_HIP;
         tl.kind = 1;
@@ -1285,13 +1294,13 @@ int leon_convert_rgba_batch(leon_decoder* d, const int32_t* slots, int32_t n, vo
         const bool twin4_exact = c4 * c4 * (uint64_t)G.rows < (1ull << 32);
         if (G.cols > 0 && G.rows > 0 && (G.fw & 3) == 0 && ((size_t)rgba_device & 15) == 0 && twin4_exact)
             hipLaunchKernelGGL(k_rgba_twin4, dim3(((unsigned)(G.fw / 4) * (unsigned)G.rows + kRgbaBlock - 1) / kRgbaBlock, 1, n), dim3(kRgbaBlock), 0, cs,
-                               d->d_slots, d->d_slot_ids + at, (uint8_t*)rgba_device, G);
+                               d->d_slots, d->slot_ids.dev() + at, (uint8_t*)rgba_device, G);
         else if (G.cols > 0 && G.rows > 0)
             hipLaunchKernelGGL(k_rgba_twin, dim3((G.cols + kRgbaBlock - 1) / kRgbaBlock, G.rows, n), dim3(kRgbaBlock), 0, cs,
-                               d->d_slots, d->d_slot_ids + at, (uint8_t*)rgba_device, G);
+                               d->d_slots, d->slot_ids.dev() + at, (uint8_t*)rgba_device, G);
     } else {
         hipLaunchKernelGGL(k_rgba_gl, dim3((G.fw + kRgbaBlock - 1) / kRgbaBlock, G.fh, n), dim3(kRgbaBlock), 0, cs,
-                           d->d_slots, d->d_slot_ids + at, (uint8_t*)rgba_device, G);
+                           d->d_slots, d->slot_ids.dev() + at, (uint8_t*)rgba_device, G);
     }
     if (d->geom.alpha) {
         // yuva: A bytes from the fourth plane, over what the conversion wrote (the CPU twin's quad loop covers
@@ -1299,12 +1308,12 @@ int leon_convert_rgba_batch(leon_decoder* d, const int32_t* slots, int32_t n, vo
         const int cover_w = flavour == LEON_RGB_CPU_TWIN ? (G.fw >> 1) * 2 : G.fw, cover_h = flavour == LEON_RGB_CPU_TWIN ? (G.fh >> 1) * 2 : G.fh;
         if (cover_w > 0 && cover_h > 0)
             hipLaunchKernelGGL(k_rgba_alpha, dim3((cover_w / 2 + kRgbaBlock - 1) / kRgbaBlock, cover_h, n), dim3(kRgbaBlock), 0, cs,
-                               d->d_slots, d->d_slot_ids + at, (uint8_t*)rgba_device, G, cover_w, cover_h);
+                               d->d_slots, d->slot_ids.dev() + at, (uint8_t*)rgba_device, G, cover_w, cover_h);
     }
     HIP_TRY(hipGetLastError());
     if (d->timing) {
         HIP_TRY(hipEventRecord(tl.b, cs));
-        d->timed.push_back(tl);
+        d->timed.push_back(std::move(tl));
     }
     if (d->overlap_convert) {
         HIP_TRY(hipEventRecord(d->ev_conv_done, cs));
@@ -1319,7 +1328,7 @@ int leon_convert_rgba(leon_decoder* d, int32_t slot, void* rgba, int32_t dst_mem
     if (dst_mem == LEON_MEM_DEVICE) return leon_convert_rgba_batch(d, &slot, 1, rgba, flavour);
     HIP_TRY(hipSetDevice(d->dev));
     size_t bytes = (size_t)d->cfg.frame_width * d->cfg.frame_height * 4;
-    if (!d->d_rgba_tmp) HIP_TRY(hipMalloc(&d->d_rgba_tmp, bytes));
+    if (!d->d_rgba_tmp && !d->d_rgba_tmp.alloc(bytes)) return refused(LEON_ERR_HIP, "hipMalloc");
     const bool ov = d->overlap_convert;
     d->overlap_convert = false;                 // host destination: plain in-order path
     int rc = leon_convert_rgba_batch(d, &slot, 1, d->d_rgba_tmp, flavour);
@@ -1403,10 +1412,14 @@ int leon_set_overlap_convert(leon_decoder* d, int32_t on)
     if (!d) return fail(LEON_ERR_INVALID, "null decoder");
     HIP_TRY(hipSetDevice(d->dev));
     if (on && !d->conv_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&d->conv_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&d->ev_recon_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&d->ev_conv_done, hipEventDisableTiming));
+        Stream cs;
+        Event recon_done, conv_done;
+        if (!cs.create(hipStreamNonBlocking) || !recon_done.create(hipEventDisableTiming) || !conv_done.create(hipEventDisableTiming))
+            return refused(LEON_ERR_HIP, "conversion stream and its events");
         d->conv_pending.assign(d->cfg.n_slots, 0);
+        d->conv_stream = std::move(cs);
+        d->ev_recon_done = std::move(recon_done);
+        d->ev_conv_done = std::move(conv_done);
     }
     if (!on && d->conv_stream) HIP_TRY(hipStreamSynchronize(d->conv_stream));
     d->overlap_convert = on != 0;
@@ -1422,9 +1435,9 @@ int leon_timing_enable(leon_decoder* d, int32_t on)
         // timed region
         HIP_TRY(hipSetDevice(d->dev));
         while (d->ev_pool.size() < 4096) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreate(&e));
-            d->ev_pool.push_back(e);
+            Event e;
+            if (!e.create()) return refused(LEON_ERR_HIP, "hipEventCreate");
+            d->ev_pool.push_back(std::move(e));
         }
     }
     return LEON_OK;
@@ -1437,8 +1450,8 @@ int leon_timing_reset(leon_decoder* d)
     HIP_TRY(hipStreamSynchronize(d->stream));
     if (d->conv_stream) HIP_TRY(hipStreamSynchronize(d->conv_stream));
     for (auto& t : d->timed) {
-        d->ev_pool.push_back(t.a);
-        d->ev_pool.push_back(t.b);
+        d->ev_pool.push_back(std::move(t.a));
+        d->ev_pool.push_back(std::move(t.b));
     }
     d->timed.clear();
     return LEON_OK;
@@ -1526,16 +1539,12 @@ int leon_measure_copy_bandwidth(leon_decoder* d, size_t bytes, int32_t iters, do
     if (!d || !gbps || bytes < 4096 || iters < 1) return fail(LEON_ERR_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(d->dev));
     bytes &= ~(size_t)4095;
-    uint4 *src = nullptr, *dst = nullptr;
-    if (big_alloc((void**)&src, bytes, kBigCaller) != hipSuccess) return fail(LEON_ERR_NOMEM, "copy source");      // allocated like the buffers it is the yardstick for
-    if (big_alloc((void**)&dst, bytes, kBigCaller) != hipSuccess) {
-        big_free(src);
-        return fail(LEON_ERR_NOMEM, "copy destination");
-    }
+    DevBuf<uint4> src, dst;
+    if (!src.alloc(bytes, kBigCaller)) return fail(LEON_ERR_NOMEM, "copy source");      // allocated like the buffers it is the yardstick for
+    if (!dst.alloc(bytes, kBigCaller)) return fail(LEON_ERR_NOMEM, "copy destination");
+    Event a, b;
+    if (!a.create() || !b.create()) return refused(LEON_ERR_HIP, "hipEventCreate");
     hipMemsetAsync(src, 0x5a, bytes, d->stream);
-    hipEvent_t a, b;
-    hipEventCreate(&a);
-    hipEventCreate(&b);
     size_t n = bytes / 16;
     unsigned grid = (unsigned)((n + kRgbaBlock - 1) / kRgbaBlock);
     hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(kRgbaBlock), 0, d->stream, src, dst, n);   // warm-up
@@ -1545,12 +1554,9 @@ int leon_measure_copy_bandwidth(leon_decoder* d, size_t bytes, int32_t iters, do
     hipError_t e = hipStreamSynchronize(d->stream);
     float ms = 0;
     hipEventElapsedTime(&ms, a, b);
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    // the stream is idle; contiguous buffers return to the pool (the next call, or a decoder's ring, takes them) -- the
-    // yardstick frees nothing the copy kernel wrote in front of the pipelines bench.py runs afterwards
-    big_free(src);
-    big_free(dst);
+    // the stream is idle when src and dst go (every way out of here lies behind the wait); contiguous buffers return to the pool
+    // (the next call, or a decoder's ring, takes them) -- the yardstick frees nothing the copy kernel wrote in front of the
+    // pipelines bench.py runs afterwards
     if (e != hipSuccess) return fail(LEON_ERR_HIP, "copy kernel: %s", hipGetErrorString(e));
     *gbps = 2.0 * (double)bytes * iters / (ms * 1e-3) / 1e9;
     return LEON_OK;
@@ -1562,11 +1568,12 @@ int leon_measure_stream_bandwidth(leon_decoder* d, size_t bytes, int32_t iters, 
         return fail(LEON_ERR_INVALID, "bad argument (0..2 read streams, 0..2 write streams, not both 0)");
     HIP_TRY(hipSetDevice(d->dev));
     bytes &= ~(size_t)4095;
-    uint4* buf[4] = {nullptr, nullptr, nullptr, nullptr};       // s0 s1 d0 d1
+    DevBuf<uint4> buf[4];       // s0 s1 d0 d1
     const bool want[4] = {reads >= 1, reads >= 2, true, writes >= 2};      // d0 always: the read-only kernel names it
-    auto release = [&] { for (uint4*& b : buf) { if (b) big_free(b); b = nullptr; } };
     for (int k = 0; k < 4; k++)
-        if (want[k] && big_alloc((void**)&buf[k], bytes, kBigCaller) != hipSuccess) { release(); return fail(LEON_ERR_NOMEM, "stream buffer %d", k); }
+        if (want[k] && !buf[k].alloc(bytes, kBigCaller)) return fail(LEON_ERR_NOMEM, "stream buffer %d", k);
+    Event a, b;
+    if (!a.create() || !b.create()) return refused(LEON_ERR_HIP, "hipEventCreate");
     for (int k = 0; k < 2; k++) if (buf[k]) hipMemsetAsync(buf[k], 0x5a, bytes, d->stream);
     const size_t n = bytes / 16;
     const dim3 grid((unsigned)((n + kRgbaBlock - 1) / kRgbaBlock)), block(kRgbaBlock);
@@ -1582,19 +1589,13 @@ int leon_measure_stream_bandwidth(leon_decoder* d, size_t bytes, int32_t iters, 
         default: hipLaunchKernelGGL((k_stream16<2, 2>), grid, block, 0, d->stream, buf[0], buf[1], buf[2], buf[3], n); break;
         }
     };
-    hipEvent_t a, b;
-    hipEventCreate(&a);
-    hipEventCreate(&b);
     launch();                                   // warm-up
     hipEventRecord(a, d->stream);
     for (int i = 0; i < iters; i++) launch();
     hipEventRecord(b, d->stream);
     const hipError_t e = hipStreamSynchronize(d->stream);
     float ms = 0;
-    hipEventElapsedTime(&ms, a, b);
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    release();                                  // the stream is idle; pooled buffers stay with the process (big_alloc)
+    hipEventElapsedTime(&ms, a, b);             // the stream is idle when the buffers go; pooled ones stay with the process (big_alloc)
     if (e != hipSuccess) return fail(LEON_ERR_HIP, "stream kernel: %s", hipGetErrorString(e));
     *gbps = (double)(reads + writes) * (double)bytes * iters / (ms * 1e-3) / 1e9;
     return LEON_OK;

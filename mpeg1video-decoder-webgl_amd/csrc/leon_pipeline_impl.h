@@ -29,10 +29,9 @@ struct PipePic {                 // one parsed picture: offsets of its arrays in
 };
 
 struct Arena {                   // pinned host buffer + its device twin, one GOP at a time
-    char* host = nullptr;
-    char* dev = nullptr;
-    size_t cap = 0, host_cap = 0, used = 0;      // cap: of the device twin
-    bool host_owned = true, dev_owned = true;    // false: a piece of the pipeline's slabs (gpu_parser), not to be freed
+    PinnedBuf<> host;            // each its own allocation, or a borrowed piece of the pipeline's slabs (gpu_parser) until a GOP outgrows it
+    DevBuf<> dev;
+    size_t used = 0;
 };
 
 // One position of the pipeline: the one leon_pipeline_create starts at, then one per leon_pipeline_seek.  The parser and
@@ -80,17 +79,14 @@ struct PipeWindow {
     std::vector<leon_pipeline_frame> frames;
     std::vector<uint8_t*> tensors;       // output TENSOR: frames[i]'s tensor
     std::vector<uint32_t> frame_ids;     // ... and its index in the ring entry's lanes (what k_tensor finds planes and tensor by)
-    hipEvent_t done = nullptr;
+    Event done;
     int status = LEON_OK;
     uint32_t n_vpics = 0;        // gpu_parser: error words of the window's pictures are in the ring entry's h_err
 };
 
 struct VlcRing {                 // gpu_parser: per ring entry, the window's slice / picture descriptors
-    char* h = nullptr;           // pinned: [VlcSlice x n][VlcPic x m]
-    char* d = nullptr;           // device: the same + [slice_words x n][error x m]
-    size_t cap = 0;
-    uint32_t* h_err = nullptr;   // pinned copy of the error words
-    size_t err_cap = 0;
+    Mirror<char> desc;           // pinned: [VlcSlice x n][VlcPic x m]; device: the same + [slice_words x n][error x m]
+    PinnedBuf<uint32_t> h_err;   // pinned copy of the error words
 };
 
 constexpr size_t kNone = (size_t)-1;
@@ -130,25 +126,29 @@ struct leon_pipeline {
     uint64_t last_run = 0;       // PipeRun::id, 0: nothing remembered
     uint64_t last_gop = 0;       // the run's GOP the remembered anchor closes
     int last_anchor = -1;        // its slot, -1: none
-    hipStream_t copy_stream = nullptr;
-    uint8_t* d_rgba = nullptr;                        // R ring entries of W * max_pics frames (output RGBA)
-    uint8_t* d_planes = nullptr;                      // the same for the frames' planes records (output YCbCr, and what the tensors are made from)
+    // (the streams stand in front of the buffers their work touches: members go in reverse order, the buffers first)
+    Stream copy_stream;
+    // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
+    // window n + 2, on a second stream: a parse launch lasts as long as its longest slice (one lane, symbol after symbol) and
+    // leaves three quarters of the issue slots idle; two of them side by side take little longer than one.
+    Stream vlc_stream[2];
+    DevBuf<uint8_t> d_rgba;                           // R ring entries of W * max_pics frames (output RGBA)
+    DevBuf<uint8_t> d_planes;                         // the same for the frames' planes records (output YCbCr, and what the tensors are made from)
     // output TENSOR: the ring of [3][fh][fw] tensors (tensor_pitch apart), the element table T (host, device), and per ring entry
     // the frame indices of its window for k_tensor (pinned, device)
-    uint8_t* d_tensor = nullptr;
+    DevBuf<uint8_t> d_tensor;
     int tensor_dtype = 0, tensor_layout = 0;          // LEON_TENSOR_*, LEON_TENSOR_LAYOUT_* (which k_tensor / k_resample: by element bytes and layout)
     size_t tensor_elem = 0, tensor_bytes = 0, tensor_pitch = 0;
     std::vector<uint8_t> tensor_table;
-    uint32_t* d_tensor_table = nullptr;
-    uint32_t* h_tensor_ids = nullptr;
-    uint32_t* d_tensor_ids = nullptr;
+    DevBuf<uint32_t> d_tensor_table;
+    Mirror<uint32_t> tensor_ids;
     // ... resampled to a model's input size (leon_pipeline_tensor_resize; geom.resized = 0: the full-size tensor, k_tensor): the
     // tables of both axes as k_resample reads them -- first_x, count_x, Wx, first_y, count_y, Wy in one int32 buffer
     leon_pipeline_tensor_geometry tensor_geom{};
     std::vector<int32_t> resize_tabs;
     leon::ResampleGeom resample_geom{};
     int32_t resize_filter = LEON_RESIZE_TRIANGLE;      // LEON_RESIZE_*: which k_resample
-    int32_t* d_resize_tabs = nullptr;
+    DevBuf<int32_t> d_resize_tabs;
     // ... placed in a padded canvas (leon_pipeline_tensor_canvas; canvas_on = 0: the tensor is the image): what get_tensor_canvas
     // reports and k_letterbox's constants.  tensor_geom.width / height are the canvas's then, resample_geom.ow / oh the image's.
     leon_pipeline_tensor_canvas tensor_canvas{};
@@ -157,33 +157,26 @@ struct leon_pipeline {
     // leon_pipeline_resample_regions: a stream of its own (non-blocking, made at first use) and the scratch of a call -- pinned staging
     // and its device twin for [descriptors | tables], read_regions' device tensors -- grown to the high-water mark, all under regions_mu
     std::mutex regions_mu;
-    hipStream_t regions_stream = nullptr;
-    char* regions_host = nullptr;
-    char* regions_dev = nullptr;
-    uint8_t* regions_out = nullptr;
-    size_t regions_host_cap = 0, regions_dev_cap = 0, regions_out_cap = 0;
+    Stream regions_stream;
+    PinnedBuf<> regions_host;
+    DevBuf<> regions_dev;
+    DevBuf<uint8_t> regions_out;
     // leon_pipeline_resample_regions_device (regions_mu too): the scratch of a chunk [frame ids | descriptors | table slots], the event
     // behind the last call's last launch -- the next call's stream waits for it on the device, growing the scratch and destroy on the
     // host -- and a small ring of pinned staging for the frame ids, each entry with the event behind its upload
     static constexpr int kBoxesStaging = 4;
-    char* boxes_dev = nullptr;
-    size_t boxes_dev_cap = 0;
-    hipEvent_t boxes_done = nullptr;
+    Event boxes_done;
+    DevBuf<> boxes_dev;
     bool boxes_busy = false;
-    uint32_t* boxes_ids_host[kBoxesStaging] = {};
-    size_t boxes_ids_cap[kBoxesStaging] = {};
-    hipEvent_t boxes_ids_done[kBoxesStaging] = {};
+    Event boxes_ids_done[kBoxesStaging];
+    PinnedBuf<uint32_t> boxes_ids_host[kBoxesStaging];
     bool boxes_ids_busy[kBoxesStaging] = {};
     unsigned boxes_ids_next = 0;
     bool gpu_parser = false;
-    // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
-    // window n + 2, on a second stream: a parse launch lasts as long as its longest slice (one lane, symbol after symbol) and
-    // leaves three quarters of the issue slots idle; two of them side by side take little longer than one.
-    hipStream_t vlc_stream[2] = {nullptr, nullptr};
-    leon::VlcTables* d_vlc_tables = nullptr;
+    DevBuf<leon::VlcTables> d_vlc_tables;
     leon::VlcGeom vgeom{};
-    char* slab_host = nullptr;        // gpu_parser: the arenas' memory, one allocation each (pinned host, device)
-    char* slab_dev = nullptr;
+    PinnedBuf<> slab_host;            // gpu_parser: the arenas' memory, one allocation each (pinned host, device): both or neither
+    DevBuf<> slab_dev;
     size_t vlc_index_lds = 0;         // dynamic LDS of k_vlc_index: the group counters of one picture + its scan
     std::vector<VlcRing> vlc_ring;
 
@@ -233,26 +226,9 @@ void pipe_fail(leon_pipeline* p, int code, const std::string& msg)
 // arena is copied as it is; the GPU parser uploads the stream bytes only and keeps everything else on the device)
 bool arena_reserve(Arena* a, size_t host_need, size_t dev_need)
 {
-    if (host_need > a->host_cap) {
-        const size_t cap = std::max(host_need + host_need / 2, (size_t)4 << 20);
-        char* h = nullptr;
-        if (hipHostMalloc((void**)&h, cap, hipHostMallocDefault) != hipSuccess) return false;
-        if (a->used) memcpy(h, a->host, std::min(a->used, a->host_cap));
-        if (a->host && a->host_owned) hipHostFree(a->host);
-        a->host = h;
-        a->host_cap = cap;
-        a->host_owned = true;
-    }
-    if (dev_need > a->cap) {
-        const size_t cap = std::max(dev_need + dev_need / 2, (size_t)8 << 20);
-        char* dv = nullptr;
-        if (big_alloc((void**)&dv, cap, kBigArenas) != hipSuccess) return false;
-        if (a->dev && a->dev_owned) big_free(a->dev);        // only ever grown while the arena is being filled: nothing in flight reads it
-        a->dev = dv;
-        a->cap = cap;
-        a->dev_owned = true;
-    }
-    return true;
+    // (the device twin is only ever grown while the arena is being filled: nothing in flight reads it)
+    return a->host.reserve(host_need, cap_for(host_need, Grow::Half, (size_t)4 << 20), a->used) &&
+           a->dev.reserve(dev_need, cap_for(dev_need, Grow::Half, (size_t)8 << 20), 0, kBigArenas);
 }
 
 // The pipeline takes the picture size from the stream's FIRST sequence header (leon_create).  Every key-map entry starts
@@ -930,26 +906,14 @@ int launch_gpu_parser(leon_pipeline* p, PipeWindow* w)
     VlcRing& R = p->vlc_ring[(size_t)w->ring];
     const size_t desc_bytes = pad256(n_slices * sizeof(leon::VlcSlice)) + pad256(n_pics * sizeof(leon::VlcPic)) + pad256(w->jobs.size() * sizeof(leon::VlcClear));
     const size_t dev_bytes = desc_bytes + pad256(n_slices * sizeof(leon::VlcSliceOut)) + pad256(n_pics * 4);
-    if (dev_bytes > R.cap) {                     // the ring entry is ours: its previous window has been released
-        if (R.h) hipHostFree(R.h);
-        if (R.d) hipFree(R.d);
-        R.h = R.d = nullptr;
-        R.cap = dev_bytes + dev_bytes / 2;
-        if (hipHostMalloc((void**)&R.h, R.cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&R.d, R.cap) != hipSuccess) {
-            R.cap = 0;
-            return fail(LEON_ERR_NOMEM, "descriptor ring of the GPU parser");
-        }
-    }
-    if (n_pics > R.err_cap) {
-        if (R.h_err) hipHostFree(R.h_err);
-        R.err_cap = n_pics + n_pics / 2;
-        if (hipHostMalloc((void**)&R.h_err, R.err_cap * 4, hipHostMallocDefault) != hipSuccess) { R.err_cap = 0; R.h_err = nullptr; return fail(LEON_ERR_NOMEM, "error words of the GPU parser"); }
-    }
-    leon::VlcSlice* hs = (leon::VlcSlice*)R.h;
-    leon::VlcPic* hp = (leon::VlcPic*)(R.h + pad256(n_slices * sizeof(leon::VlcSlice)));
-    leon::VlcSliceOut* d_words = (leon::VlcSliceOut*)(R.d + desc_bytes);      // what k_vlc_parse leaves per slice for the two kernels behind it
-    uint32_t* d_err = (uint32_t*)(R.d + desc_bytes + pad256(n_slices * sizeof(leon::VlcSliceOut)));
-    leon::VlcClear* hc = (leon::VlcClear*)(R.h + pad256(n_slices * sizeof(leon::VlcSlice)) + pad256(n_pics * sizeof(leon::VlcPic)));
+    // (the ring entry is ours: its previous window has been released)
+    if (!R.desc.reserve(dev_bytes, cap_for(dev_bytes, Grow::Half))) return fail(LEON_ERR_NOMEM, "descriptor ring of the GPU parser");
+    if (!R.h_err.reserve(n_pics * 4, cap_for(n_pics, Grow::Half) * 4)) return fail(LEON_ERR_NOMEM, "error words of the GPU parser");
+    leon::VlcSlice* hs = (leon::VlcSlice*)R.desc.host();
+    leon::VlcPic* hp = (leon::VlcPic*)(R.desc.host() + pad256(n_slices * sizeof(leon::VlcSlice)));
+    leon::VlcSliceOut* d_words = (leon::VlcSliceOut*)(R.desc.dev() + desc_bytes);      // what k_vlc_parse leaves per slice for the two kernels behind it
+    uint32_t* d_err = (uint32_t*)(R.desc.dev() + desc_bytes + pad256(n_slices * sizeof(leon::VlcSliceOut)));
+    leon::VlcClear* hc = (leon::VlcClear*)(R.desc.host() + pad256(n_slices * sizeof(leon::VlcSlice)) + pad256(n_pics * sizeof(leon::VlcPic)));
     size_t pi = 0, ci = 0;
     // Slice order of the launch: picture by picture, the I pictures first, then P, then B -- the 64 lanes of a wave
     // then hold slices of ONE picture type (in coded order most waves straddled two pictures of different types, and
@@ -989,12 +953,12 @@ int launch_gpu_parser(leon_pipeline* p, PipeWindow* w)
                     si++;
                 }
             }
-    HIP_TRY(hipMemcpyAsync(R.d, R.h, desc_bytes, hipMemcpyHostToDevice, vs));
+    HIP_TRY(hipMemcpyAsync(R.desc.dev(), R.desc.host(), desc_bytes, hipMemcpyHostToDevice, vs));
     HIP_TRY(hipMemsetAsync(d_err, 0, n_pics * 4, vs));
-    const leon::VlcClear* dc = (const leon::VlcClear*)(R.d + pad256(n_slices * sizeof(leon::VlcSlice)) + pad256(n_pics * sizeof(leon::VlcPic)));
+    const leon::VlcClear* dc = (const leon::VlcClear*)(R.desc.dev() + pad256(n_slices * sizeof(leon::VlcSlice)) + pad256(n_pics * sizeof(leon::VlcPic)));
     hipLaunchKernelGGL(leon::k_vlc_clear, dim3(32, (unsigned)w->jobs.size()), dim3(256), 0, vs, dc);
-    const leon::VlcSlice* ds = (const leon::VlcSlice*)R.d;
-    const leon::VlcPic* dp = (const leon::VlcPic*)(R.d + pad256(n_slices * sizeof(leon::VlcSlice)));
+    const leon::VlcSlice* ds = (const leon::VlcSlice*)R.desc.dev();
+    const leon::VlcPic* dp = (const leon::VlcPic*)(R.desc.dev() + pad256(n_slices * sizeof(leon::VlcSlice)));
     const int blocks = (int)((n_slices + 255) / 256);
     hipLaunchKernelGGL(leon::k_vlc_parse, dim3(blocks), dim3(256), 4 * leon::kVlcRingDwords * 64 * 4, vs, ds, d_words, (int)n_slices, dp, d_err, p->vgeom, p->d_vlc_tables);
     hipLaunchKernelGGL(leon::k_vlc_index, dim3((unsigned)n_pics), dim3(leon::kVlcIndexThreads), p->vlc_index_lds, vs, ds, d_words, dp, d_err, p->vgeom);
@@ -1129,22 +1093,22 @@ int upload_and_chain(leon_pipeline* p, PipeWindow* w, bool serial, bool poison)
             p->st_upload += up;
         }
     }
-    hipEvent_t ready = get_event(d);            // what the decoder's stream waits for: the upload, or the parser kernels
+    Event ready = get_event(d->ev_pool);        // what the decoder's stream waits for: the upload, or the parser kernels
     if (!ready) return LEON_ERR_HIP;
     HIP_TRY(hipEventRecord(ready, p->copy_stream));
     if (serial) HIP_TRY(hipStreamSynchronize(p->copy_stream));
     if (p->gpu_parser) {
         hipStream_t vs = p->vlc_stream[vlc_stream_of(w->id)];
         HIP_TRY(hipStreamWaitEvent(vs, ready, 0));
-        d->ev_pool.push_back(ready);
+        d->ev_pool.push_back(std::move(ready));
         const int rc = launch_gpu_parser(p, w);
         if (rc != LEON_OK) return rc;
         if (serial) HIP_TRY(hipStreamSynchronize(vs));
-        if (!(ready = get_event(d))) return LEON_ERR_HIP;
+        if (!(ready = get_event(d->ev_pool))) return LEON_ERR_HIP;
         HIP_TRY(hipEventRecord(ready, vs));
     }
     HIP_TRY(hipStreamWaitEvent(d->stream, ready, 0));
-    d->ev_pool.push_back(ready);
+    d->ev_pool.push_back(std::move(ready));
     return LEON_OK;
 }
 
@@ -1289,8 +1253,8 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
     const size_t n = w->frame_ids.size();
     if (!p->d_tensor || !n) return LEON_OK;
     const size_t entry = (size_t)p->W * p->max_pics;
-    uint32_t* h = p->h_tensor_ids + (size_t)w->ring * entry;       // the ring entry is this window's: its previous launch has finished
-    uint32_t* dv = p->d_tensor_ids + (size_t)w->ring * entry;
+    uint32_t* h = p->tensor_ids.host() + (size_t)w->ring * entry;       // the ring entry is this window's: its previous launch has finished
+    uint32_t* dv = p->tensor_ids.dev() + (size_t)w->ring * entry;
     for (size_t i = 0; i < n; i++) h[i] = (uint32_t)((size_t)w->ring * entry) + w->frame_ids[i];
     HIP_TRY(hipMemcpyAsync(dv, h, n * 4, hipMemcpyHostToDevice, p->dec->stream));
     const bool resized = p->tensor_geom.resized != 0;
@@ -1443,25 +1407,16 @@ int regions_check(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_
     return LEON_OK;
 }
 
-// one buffer of a call's scratch, grown to half again what is asked and never shrunk
-template <class T> int regions_grow(T** buf, size_t* cap_now, size_t bytes, bool pinned, const char* what)
-{
-    if (bytes <= *cap_now) return LEON_OK;
-    const size_t cap = std::max(bytes + bytes / 2, (size_t)1 << 20);
-    void* m = nullptr;
-    if ((pinned ? hipHostMalloc(&m, cap, hipHostMallocDefault) : big_alloc(&m, cap, kBigCaller)) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes %s", cap, what); }
-    if (*buf) (void)(pinned ? hipHostFree(*buf) : big_free(*buf));
-    *buf = static_cast<T*>(m);
-    *cap_now = cap;
-    return LEON_OK;
-}
-// the host roads' scratch (regions_mu held; the regions stream is idle between calls)
+// the host roads' scratch (regions_mu held; the regions stream is idle between calls): each buffer grown to half again what is
+// asked and never shrunk
 int regions_reserve(leon_pipeline* p, size_t upload_bytes, size_t out_bytes)
 {
-    int rc;
-    if ((rc = regions_grow(&p->regions_host, &p->regions_host_cap, upload_bytes, true, "of pinned staging")) != LEON_OK) return rc;
-    if ((rc = regions_grow(&p->regions_dev, &p->regions_dev_cap, upload_bytes, false, "of device scratch")) != LEON_OK) return rc;
-    return regions_grow(&p->regions_out, &p->regions_out_cap, out_bytes, false, "for the tensors");
+    const auto cap = [](size_t bytes) { return cap_for(bytes, Grow::Half, (size_t)1 << 20); };
+    const auto no = [](size_t bytes, const char* what) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes %s", bytes, what); };
+    if (!p->regions_host.reserve(upload_bytes, cap(upload_bytes))) return no(cap(upload_bytes), "of pinned staging");
+    if (!p->regions_dev.reserve(upload_bytes, cap(upload_bytes), 0, kBigCaller)) return no(cap(upload_bytes), "of device scratch");
+    if (!p->regions_out.reserve(out_bytes, cap(out_bytes), 0, kBigCaller)) return no(cap(out_bytes), "for the tensors");
+    return LEON_OK;
 }
 
 // the ring ids of a delivered window's frames: p->mu is held for the look-up and the copy only (the notify thread and release_window need it)
@@ -1508,8 +1463,8 @@ int regions_out_check(const char* who, const void* device_out, uint64_t out_pitc
 int regions_call_stream(leon_pipeline* p, void* caller_stream, hipStream_t* st)
 {
     HIP_TRY(hipSetDevice(p->cfg.device_id));
-    if (!caller_stream && !p->regions_stream) HIP_TRY(hipStreamCreateWithFlags(&p->regions_stream, hipStreamNonBlocking));
-    *st = caller_stream ? static_cast<hipStream_t>(caller_stream) : p->regions_stream;
+    if (!caller_stream && !p->regions_stream && !p->regions_stream.create(hipStreamNonBlocking)) return refused(LEON_ERR_HIP, "regions stream");
+    *st = caller_stream ? static_cast<hipStream_t>(caller_stream) : p->regions_stream.get();
     return LEON_OK;
 }
 
@@ -1518,7 +1473,7 @@ int regions_call_stream(leon_pipeline* p, void* caller_stream, hipStream_t* st)
 template <class Launch>
 int regions_host_run(leon_pipeline* p, hipStream_t st, size_t upload_bytes, void* host, void* device_out, size_t pitch, size_t region_bytes, int32_t n, Launch launch)
 {
-    uint8_t* out = host ? p->regions_out : static_cast<uint8_t*>(device_out);
+    uint8_t* out = host ? p->regions_out.get() : static_cast<uint8_t*>(device_out);
     HIP_TRY(hipMemcpyAsync(p->regions_dev, p->regions_host, upload_bytes, hipMemcpyHostToDevice, st));
     launch(out);
     HIP_TRY(hipGetLastError());
@@ -1582,7 +1537,7 @@ int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_regio
     const size_t upload_bytes = desc_bytes + words * 4;
     hipStream_t st;
     if ((rc = regions_call_stream(p, nullptr, &st)) != LEON_OK || (rc = regions_reserve(p, upload_bytes, host ? (size_t)n * pitch : 0)) != LEON_OK) return rc;
-    leon::RegionDesc* descs = reinterpret_cast<leon::RegionDesc*>(p->regions_host);
+    leon::RegionDesc* descs = reinterpret_cast<leon::RegionDesc*>(p->regions_host.get());
     int32_t* tabs = reinterpret_cast<int32_t*>(p->regions_host + desc_bytes);
     size_t at = 0;
     for (int32_t i = 0; i < n; i++) {
@@ -1612,7 +1567,7 @@ int resample_regions(leon_pipeline* p, int64_t window, const leon_pipeline_regio
     const dim3 grid = regions_grid(ow, oh, region_bytes, fit.letterbox, (unsigned)n);          // (blockIdx.z; one launch: n <= 65535)
     if (grid.y > 65535u) return fail(LEON_ERR_INVALID, "regions fit: %u workgroup rows", grid.y);
     return regions_host_run(p, st, upload_bytes, host, device_out, (size_t)pitch, region_bytes, n, [&](uint8_t* out) {
-        regions_launch(p, st, fit, filter, G, grid, out, reinterpret_cast<const leon::RegionDesc*>(p->regions_dev), reinterpret_cast<const int32_t*>(p->regions_dev + desc_bytes));
+        regions_launch(p, st, fit, filter, G, grid, out, reinterpret_cast<const leon::RegionDesc*>(p->regions_dev.get()), reinterpret_cast<const int32_t*>(p->regions_dev + desc_bytes));
     });
 }
 
@@ -1652,14 +1607,10 @@ int32_t region_status(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipel
 // the chunk's scratch, grown and never shrunk (regions_mu held): nothing of an earlier call may still run in the old one
 int boxes_reserve(leon_pipeline* p, size_t bytes)
 {
-    if (bytes <= p->boxes_dev_cap) return LEON_OK;
+    if (bytes <= p->boxes_dev.bytes()) return LEON_OK;
     if (p->boxes_busy) { HIP_TRY(hipEventSynchronize(p->boxes_done)); p->boxes_busy = false; }
-    const size_t cap = std::max(bytes, (size_t)1 << 20);
-    char* dv = nullptr;
-    if (big_alloc((void**)&dv, cap, kBigCaller) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of device scratch", cap); }
-    if (p->boxes_dev) big_free(p->boxes_dev);
-    p->boxes_dev = dv;
-    p->boxes_dev_cap = cap;
+    const size_t cap = cap_for(bytes, Grow::Exact, (size_t)1 << 20);
+    if (!p->boxes_dev.reserve(bytes, cap, 0, kBigCaller)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of device scratch", cap); }
     return LEON_OK;
 }
 
@@ -1669,16 +1620,10 @@ int boxes_ids_stage(leon_pipeline* p, const std::vector<uint32_t>& ids, uint32_t
 {
     const unsigned e = p->boxes_ids_next++ % leon_pipeline::kBoxesStaging;
     if (p->boxes_ids_busy[e]) { HIP_TRY(hipEventSynchronize(p->boxes_ids_done[e])); p->boxes_ids_busy[e] = false; }
-    if (!p->boxes_ids_done[e]) HIP_TRY(hipEventCreateWithFlags(&p->boxes_ids_done[e], hipEventDisableTiming));
-    if (ids.size() > p->boxes_ids_cap[e]) {
-        const size_t cap = std::max(ids.size() * 2, (size_t)1024);
-        uint32_t* h = nullptr;
-        if (hipHostMalloc((void**)&h, cap * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of pinned staging", cap * 4); }
-        if (p->boxes_ids_host[e]) hipHostFree(p->boxes_ids_host[e]);
-        p->boxes_ids_host[e] = h;
-        p->boxes_ids_cap[e] = cap;
-    }
-    std::copy(ids.begin(), ids.end(), p->boxes_ids_host[e]);
+    if (!p->boxes_ids_done[e] && !p->boxes_ids_done[e].create(hipEventDisableTiming)) return refused(LEON_ERR_HIP, "hipEventCreate");
+    const size_t cap = cap_for(ids.size(), Grow::Twice, 1024) * 4;
+    if (!p->boxes_ids_host[e].reserve(ids.size() * 4, cap)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "regions: %zu bytes of pinned staging", cap); }
+    std::copy(ids.begin(), ids.end(), p->boxes_ids_host[e].get());
     *host = p->boxes_ids_host[e];
     return LEON_OK;
 }
@@ -1701,13 +1646,13 @@ int boxes_call_check(const char* who, const void* regions, bool reserved_set, co
 int boxes_begin(leon_pipeline* p, hipStream_t st, const std::vector<uint32_t>& ids, size_t scratch_bytes, uint32_t** d_ids, hipError_t* he)
 {
     int rc;
-    if (!p->boxes_done) HIP_TRY(hipEventCreateWithFlags(&p->boxes_done, hipEventDisableTiming));
+    if (!p->boxes_done && !p->boxes_done.create(hipEventDisableTiming)) return refused(LEON_ERR_HIP, "hipEventCreate");
     if ((rc = boxes_reserve(p, scratch_bytes)) != LEON_OK) return rc;
     uint32_t* ids_host = nullptr;
     if ((rc = boxes_ids_stage(p, ids, &ids_host)) != LEON_OK) return rc;
     const unsigned e = (p->boxes_ids_next - 1) % leon_pipeline::kBoxesStaging;
     if (p->boxes_busy) HIP_TRY(hipStreamWaitEvent(st, p->boxes_done, 0));
-    *d_ids = reinterpret_cast<uint32_t*>(p->boxes_dev);
+    *d_ids = reinterpret_cast<uint32_t*>(p->boxes_dev.get());
     *he = hipMemcpyAsync(*d_ids, ids_host, ids.size() * 4, hipMemcpyHostToDevice, st);
     if (*he == hipSuccess && (*he = hipEventRecord(p->boxes_ids_done[e], st)) == hipSuccess) p->boxes_ids_busy[e] = true;
     return LEON_OK;
@@ -1881,10 +1826,10 @@ int warp_regions(leon_pipeline* p, int64_t window, const leon_pipeline_warp_regi
     const size_t ids_bytes = pad256(ids.size() * 4), upload_bytes = ids_bytes + (size_t)n * sizeof(leon::WarpRecord);
     hipStream_t st;
     if ((rc = regions_call_stream(p, nullptr, &st)) != LEON_OK || (rc = regions_reserve(p, upload_bytes, host ? (size_t)n * pitch : 0)) != LEON_OK) return rc;
-    std::copy(ids.begin(), ids.end(), reinterpret_cast<uint32_t*>(p->regions_host));
+    std::copy(ids.begin(), ids.end(), reinterpret_cast<uint32_t*>(p->regions_host.get()));
     std::memcpy(p->regions_host + ids_bytes, regions, (size_t)n * sizeof(leon::WarpRecord));
     return regions_host_run(p, st, upload_bytes, host, device_out, (size_t)pitch, region_bytes, n, [&](uint8_t* out) {
-        warp_launch(p, st, reinterpret_cast<const leon::WarpRecord*>(p->regions_dev + ids_bytes), reinterpret_cast<const uint32_t*>(p->regions_dev), (int32_t)ids.size(), n, *cfg,
+        warp_launch(p, st, reinterpret_cast<const leon::WarpRecord*>(p->regions_dev + ids_bytes), reinterpret_cast<const uint32_t*>(p->regions_dev.get()), (int32_t)ids.size(), n, *cfg,
                     pad, out, pitch, nullptr);
     });
 }
@@ -1936,8 +1881,8 @@ int resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes
     static_assert(sizeof(leon::AxisRecord) == 16, "four words an axis");
     const size_t rows = (size_t)n_axes * (size_t)max_out, words = (size_t)n_axes * 4 + 2 * rows + rows * (size_t)max_taps + (size_t)n_axes;
     HIP_TRY(hipSetDevice(device_id));
-    int32_t* d = nullptr;
-    if (hipMalloc((void**)&d, words * 4) != hipSuccess) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "resize: %zu bytes of device memory", words * 4); }
+    DevBuf<int32_t> d;
+    if (!d.alloc(words * 4)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "resize: %zu bytes of device memory", words * 4); }
     int32_t *d_first = d + (size_t)n_axes * 4, *d_count = d_first + rows, *d_weights = d_count + rows, *d_status = d_weights + rows * (size_t)max_taps;
     // the caller's arrays go up and come back whole: what the kernel does not write stays as the caller had it
     hipError_t he = hipMemcpy(d, axes, (size_t)n_axes * 16, hipMemcpyHostToDevice);
@@ -1945,7 +1890,7 @@ int resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes
     if (he == hipSuccess) he = hipMemcpy(d_count, count, rows * 4, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(d_weights, weights, rows * (size_t)max_taps * 4, hipMemcpyHostToDevice);
     if (he == hipSuccess) {
-        hipLaunchKernelGGL(leon::k_axis_tables, dim3((unsigned)n_axes), dim3(leon::kRgbaBlock), 0, nullptr, reinterpret_cast<const leon::AxisRecord*>(d), d_first, d_count,
+        hipLaunchKernelGGL(leon::k_axis_tables, dim3((unsigned)n_axes), dim3(leon::kRgbaBlock), 0, nullptr, reinterpret_cast<const leon::AxisRecord*>(d.get()), d_first, d_count,
                            d_weights, d_status, filter == LEON_RESIZE_BICUBIC ? 1 : 0, max_taps, max_out);
         he = hipGetLastError();
     }
@@ -1953,8 +1898,7 @@ int resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes
     if (he == hipSuccess) he = hipMemcpy(count, d_count, rows * 4, hipMemcpyDeviceToHost);
     if (he == hipSuccess) he = hipMemcpy(weights, d_weights, rows * (size_t)max_taps * 4, hipMemcpyDeviceToHost);
     if (he == hipSuccess) he = hipMemcpy(status, d_status, (size_t)n_axes * 4, hipMemcpyDeviceToHost);
-    hipFree(d);
-    HIP_TRY(he);
+    HIP_TRY(he);      // (the copies above waited: nothing in flight reads d when it goes)
     return LEON_OK;
 }
 
@@ -2061,7 +2005,7 @@ void submit_loop(leon_pipeline* p)
         for (GopJob* j : w->jobs)
             if (j->status != LEON_OK && rc == LEON_OK) { rc = j->status; msg = j->err; }
         if (rc == LEON_OK) {
-            if (hipEventCreateWithFlags(&w->done, hipEventDisableTiming) != hipSuccess) { rc = LEON_ERR_HIP; msg = "hipEventCreate failed"; }
+            if (!w->done.create(hipEventDisableTiming)) { rc = LEON_ERR_HIP; msg = "hipEventCreate failed"; }
             else {
                 const auto t = Clock::now();
                 rc = submit_window(p, w);
@@ -2104,7 +2048,6 @@ void release_window_locked(leon_pipeline* p, PipeWindow* w)
         delete j;
     }
     p->ring_owner[w->ring] = -1;
-    if (w->done) hipEventDestroy(w->done);
     delete w;
 }
 
@@ -2438,10 +2381,10 @@ int hip_fail(int code, const std::string& what)
 }
 
 // one output ring: R entries of W * max_pics frames of `frame` bytes
-int alloc_ring(leon_pipeline* p, uint8_t** ring, size_t frame, const char* name)
+int alloc_ring(leon_pipeline* p, DevBuf<uint8_t>* ring, size_t frame, const char* name)
 {
     const size_t bytes = (size_t)p->R * p->W * p->max_pics * frame;
-    if (big_alloc((void**)ring, bytes, kBigRgbaRing) == hipSuccess) return LEON_OK;
+    if (ring->alloc(bytes, kBigRgbaRing)) return LEON_OK;
     return hip_fail(LEON_ERR_NOMEM, std::string(name) + " ring of " + std::to_string(bytes >> 20) + " MiB (windows_in_flight " + std::to_string(p->R) +
                                         " x gops_per_window " + std::to_string(p->W) + " x max_gop_pictures " + std::to_string(p->max_pics) + " x " +
                                         std::to_string(frame) + " bytes per frame)");
@@ -2463,19 +2406,17 @@ int allocate_pipeline(leon_pipeline* p)
     int rc = leon_create(&dc, &p->dec);
     if (rc == LEON_OK) rc = leon_set_quant_matrices(p->dec, p->vinfo.intra_qm, p->vinfo.non_intra_qm);
     if (rc != LEON_OK) return rc;
-    if (hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking) != hipSuccess) return hip_fail(LEON_ERR_HIP, "copy stream");
+    if (!p->copy_stream.create(hipStreamNonBlocking)) return hip_fail(LEON_ERR_HIP, "copy stream");
     // (the tensors are made from the frames' planes: TENSOR runs the YCbCr road inside whether or not the planes are handed out)
     if ((p->output & (LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR)) && (rc = alloc_ring(p, &p->d_planes, p->planes_bytes, "planes")) != LEON_OK) return rc;
     if (p->output & LEON_PIPELINE_OUTPUT_TENSOR) {
         if ((rc = alloc_ring(p, &p->d_tensor, p->tensor_pitch, "tensor")) != LEON_OK) return rc;
-        const size_t ids = (size_t)p->R * p->W * p->max_pics * 4;
-        if (hipMalloc((void**)&p->d_tensor_table, p->tensor_table.size()) != hipSuccess || hipMalloc((void**)&p->d_tensor_ids, ids) != hipSuccess ||
-            hipHostMalloc((void**)&p->h_tensor_ids, ids, hipHostMallocDefault) != hipSuccess)
-            return hip_fail(LEON_ERR_NOMEM, "tensor table and frame index ring");
+        const size_t ids = (size_t)p->R * p->W * p->max_pics;
+        if (!p->d_tensor_table.alloc(p->tensor_table.size()) || !p->tensor_ids.alloc(ids)) return hip_fail(LEON_ERR_NOMEM, "tensor table and frame index ring");
         if (hipMemcpy(p->d_tensor_table, p->tensor_table.data(), p->tensor_table.size(), hipMemcpyHostToDevice) != hipSuccess) return hip_fail(LEON_ERR_HIP, "tensor table");
         if (p->tensor_geom.resized) {
             const size_t tb = p->resize_tabs.size() * 4;
-            if (hipMalloc((void**)&p->d_resize_tabs, tb) != hipSuccess) return hip_fail(LEON_ERR_NOMEM, "resize tables");
+            if (!p->d_resize_tabs.alloc(tb)) return hip_fail(LEON_ERR_NOMEM, "resize tables");
             if (hipMemcpy(p->d_resize_tabs, p->resize_tabs.data(), tb, hipMemcpyHostToDevice) != hipSuccess) return hip_fail(LEON_ERR_HIP, "resize tables");
         }
     }
@@ -2492,9 +2433,9 @@ int allocate_pipeline(leon_pipeline* p)
         // stream priority: a freed slot goes to a waiting parser workgroup first.
         int prio_lo = 0, prio_hi = 0;
         hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        for (hipStream_t& vs : p->vlc_stream)
-            if (hipStreamCreateWithPriority(&vs, hipStreamNonBlocking, prio_hi) != hipSuccess) return hip_fail(LEON_ERR_HIP, "parser stream");
-        if (hipMalloc((void**)&p->d_vlc_tables, sizeof(leon::VlcTables)) != hipSuccess) return hip_fail(LEON_ERR_NOMEM, "GPU parser tables");
+        for (Stream& vs : p->vlc_stream)
+            if (!vs.create(hipStreamNonBlocking, prio_hi)) return hip_fail(LEON_ERR_HIP, "parser stream");
+        if (!p->d_vlc_tables.alloc(sizeof(leon::VlcTables))) return hip_fail(LEON_ERR_NOMEM, "GPU parser tables");
         if (hipMemcpy(p->d_vlc_tables, t.data(), sizeof(leon::VlcTables), hipMemcpyHostToDevice) != hipSuccess) return hip_fail(LEON_ERR_HIP, "GPU parser tables");
         if (p->vlc_index_lds > kMaxVlcIndexLds)
             return hip_fail(LEON_ERR_INVALID, "picture too large for the GPU parser (its group counters do not fit in LDS): use LEON_PIPELINE_PARSER_HOST or LEON_PIPELINE_PARSER_DEFAULT");
@@ -2524,18 +2465,17 @@ int allocate_pipeline(leon_pipeline* p)
                                  (size_t)p->max_pics * (vlc_pic_bytes(p).total + MapLayout::entries_pad(kVlcMinEntries)) + 65535) / 65536 * 65536;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)n_arenas * dev_each < free_b / 2 && !getenv("LEON_DEBUG_NO_SLABS")) {
-            if (big_alloc((void**)&p->slab_dev, (size_t)n_arenas * dev_each, kBigArenas) == hipSuccess &&
-                hipHostMalloc((void**)&p->slab_host, (size_t)n_arenas * host_each, hipHostMallocDefault) == hipSuccess) {
+            DevBuf<> dev;
+            PinnedBuf<> host;
+            if (dev.alloc((size_t)n_arenas * dev_each, kBigArenas) && host.alloc((size_t)n_arenas * host_each)) {
+                p->slab_dev = std::move(dev);
+                p->slab_host = std::move(host);
                 for (int i = 0; i < n_arenas; i++) {
                     Arena* a = p->all_arenas[(size_t)i];
-                    a->dev = p->slab_dev + (size_t)i * dev_each; a->cap = dev_each; a->dev_owned = false;
-                    a->host = p->slab_host + (size_t)i * host_each; a->host_cap = host_each; a->host_owned = false;
+                    a->dev.borrow(p->slab_dev + (size_t)i * dev_each, dev_each);
+                    a->host.borrow(p->slab_host + (size_t)i * host_each, host_each);
                 }
-            } else {
-                if (p->slab_dev) big_free(p->slab_dev);
-                p->slab_dev = nullptr;
-                (void)hipGetLastError();
-            }
+            } else (void)hipGetLastError();
         }
     }
     return LEON_OK;
@@ -2987,13 +2927,7 @@ void leon_pipeline_destroy(leon_pipeline* p)
         for (auto& kv : p->parsed) delete kv.second;
         p->parsed.clear();
     }
-    for (Arena* a : p->all_arenas) {
-        if (a->host && a->host_owned) hipHostFree(a->host);
-        if (a->dev && a->dev_owned) big_free(a->dev);
-        delete a;
-    }
-    if (p->slab_host) hipHostFree(p->slab_host);
-    if (p->slab_dev) big_free(p->slab_dev);
+    for (Arena* a : p->all_arenas) delete a;
     if (getenv("LEON_DEBUG_PIPE_TIMING"))      // where the submit thread's time went (LEON_DEBUG_PIPE_TIMING=1)
         fprintf(stderr, "leon pipeline: %llu windows; per window on the submit thread: %.2f ms waiting for a ring entry, %.2f ms waiting for the window's GOPs "
                         "(parser threads), %.2f ms in submit_window\n", (unsigned long long)p->windows_submitted,
@@ -3005,34 +2939,9 @@ void leon_pipeline_destroy(leon_pipeline* p)
         for (size_t i = 0; i < p->st_window_done.size() && i < 64; i++) fprintf(stderr, " %.1f", p->st_window_done[i] * 1e3);
         fprintf(stderr, "\n");
     }
-    for (VlcRing& r : p->vlc_ring) {
-        if (r.h) hipHostFree(r.h);
-        if (r.d) hipFree(r.d);
-        if (r.h_err) hipHostFree(r.h_err);
-    }
-    if (p->d_vlc_tables) hipFree(p->d_vlc_tables);
-    for (hipStream_t vs : p->vlc_stream)
-        if (vs) hipStreamDestroy(vs);
-    if (p->d_rgba) big_free(p->d_rgba);
-    if (p->d_planes) big_free(p->d_planes);
-    if (p->d_tensor) big_free(p->d_tensor);
-    if (p->d_tensor_table) hipFree(p->d_tensor_table);
-    if (p->d_tensor_ids) hipFree(p->d_tensor_ids);
-    if (p->d_resize_tabs) hipFree(p->d_resize_tabs);
-    if (p->h_tensor_ids) hipHostFree(p->h_tensor_ids);
-    if (p->regions_host) hipHostFree(p->regions_host);
-    if (p->regions_dev) big_free(p->regions_dev);
-    if (p->regions_out) big_free(p->regions_out);
-    if (p->boxes_dev) big_free(p->boxes_dev);
-    if (p->boxes_done) hipEventDestroy(p->boxes_done);
-    for (int e = 0; e < leon_pipeline::kBoxesStaging; e++) {
-        if (p->boxes_ids_host[e]) hipHostFree(p->boxes_ids_host[e]);
-        if (p->boxes_ids_done[e]) hipEventDestroy(p->boxes_ids_done[e]);
-    }
-    if (p->regions_stream) hipStreamDestroy(p->regions_stream);
-    if (p->copy_stream) hipStreamDestroy(p->copy_stream);
-    if (p->dec) leon_destroy(p->dec);
-    delete p;
+    leon_decoder* const dec = p->dec;
+    delete p;      // the members give back what the pipeline owns: buffers and events first, the streams last (the order of declaration, reversed)
+    if (dec) leon_destroy(dec);
 }
 
 }  // extern "C"
