@@ -3,14 +3,12 @@
 #include "../../include/leon_pipeline.h"
 #include "../../include/leon_vlc.h"
 #include "leon_vlc_gpu.h"
+#include "leon_pipe_flow.h"
 
 #include <atomic>
 #include <sys/stat.h>
 #include <chrono>
-#include <condition_variable>
-#include <deque>
 #include <cmath>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -34,16 +32,7 @@ struct Arena {                   // pinned host buffer + its device twin, one GO
     size_t used = 0;
 };
 
-// One position of the pipeline: the one leon_pipeline_create starts at, then one per leon_pipeline_seek.  The parser and
-// submit threads work for the current run (leon_pipeline::run) only; what they hold of an earlier one is dropped.
-struct PipeRun {
-    uint64_t id = 0;             // counts the runs of the process (make_run): what was remembered of a run is recognised by it
-    std::vector<uint32_t> mine;  // key-map ids the run decodes, in order (this shard's, from the entry it starts with)
-    uint32_t first_key = 0;      // the key-map entry it starts with
-    uint64_t total_gops = 0;     // mine.size() * loop
-    int64_t total_windows = 0;
-    double exact_ms = -1;        // LEON_PIPELINE_SEEK_EXACT: the first GOP's frames start at the one on screen at this time; < 0: all
-};
+using leon_flow::PipeRun;
 
 struct GopJob {
     std::shared_ptr<const PipeRun> run;      // the run it was parsed for
@@ -75,7 +64,7 @@ struct PipeWindow {
     std::shared_ptr<const PipeRun> run;
     int64_t id = 0;
     int ring = 0;
-    std::vector<GopJob*> jobs;
+    std::vector<std::unique_ptr<GopJob>> jobs;
     std::vector<leon_pipeline_frame> frames;
     std::vector<uint8_t*> tensors;       // output TENSOR: frames[i]'s tensor
     std::vector<uint32_t> frame_ids;     // ... and its index in the ring entry's lanes (what k_tensor finds planes and tensor by)
@@ -89,6 +78,8 @@ struct VlcRing {                 // gpu_parser: per ring entry, the window's sli
     PinnedBuf<uint32_t> h_err;   // pinned copy of the error words
 };
 
+using PipeFlow = leon_flow::Flow<GopJob, PipeWindow>;       // the thread protocol: leon_pipe_flow.h
+
 constexpr size_t kNone = (size_t)-1;
 
 }  // namespace
@@ -98,7 +89,6 @@ struct leon_pipeline {
     leon_pipeline_info info{};
     const uint8_t* stream = nullptr;
     size_t bytes = 0;
-    size_t valid = 0;            // how much of the stream has arrived (leon_pipeline_feed); under mu
     leon_pipeline_callback cb = nullptr;
     void* user = nullptr;
     leon_vlc_info vinfo{};
@@ -106,7 +96,6 @@ struct leon_pipeline {
     std::vector<uint32_t> shard_gops;                 // key-map ids this pipeline may decode (all, or g % shard_count == shard_index)
     bool has_keymap = false;
     int W = 32, R = 2, K = 1, max_pics = 16;
-    std::vector<double> st_window_done;                      // LEON_DEBUG_PIPE_TIMING: when each window completed (seconds from the start)
     uint64_t st_wait_ring_ns = 0, st_wait_scan_ns = 0;       // submit thread: waiting for a ring entry / for the window's GOPs to be parsed
     std::string capture_dir;     // LEON_DEBUG_CAPTURE=<dir> at create: everything a window's launches read and wrote goes to files (capture_*)
     bool unfused = false;        // frame_width % 8 != 0, or the GL flavour: planes for every picture, one display conversion launch per picture
@@ -180,47 +169,23 @@ struct leon_pipeline {
     size_t vlc_index_lds = 0;         // dynamic LDS of k_vlc_index: the group counters of one picture + its scan
     std::vector<VlcRing> vlc_ring;
 
-    std::mutex mu;
-    std::condition_variable cv;
-    // the current run and how far it is; a seek replaces the run and starts these over (under mu)
-    std::shared_ptr<const PipeRun> run, ended_run;    // ended_run: the last run whose 'ended' callback has returned
-    uint64_t next_gop = 0;                            // next GOP of the run for a parser thread
-    int64_t run_submitted = 0, run_done = 0;          // windows of the run submitted / delivered
-    bool run_ended = false;                           // its 'ended' callback is out
-    int64_t next_window = 0;                          // window ids count on across runs
-    bool in_callback = false;                         // the notify thread is inside the callback
-    std::map<uint64_t, GopJob*> parsed;               // waiting for the submit thread (GOP of the current run -> job)
-    std::deque<Arena*> free_arenas;
-    std::deque<PipeWindow*> to_notify;
-    std::vector<int64_t> ring_owner;                  // window id holding a ring entry, -1 free
-    std::map<int64_t, PipeWindow*> delivered;         // waiting for release
-    int64_t windows_submitted = 0, windows_done = 0;      // over all runs
-    bool stop = false, finished = false, quiet = false, submit_exited = false;
-    int status = LEON_OK;
-    std::string err;
+    // The jobs, the windows and everything the threads wait for.  It stands behind the streams and in front of the arenas: members
+    // go in reverse order, so the arenas (all_arenas; the flow holds them as tickets and never looks inside) go first, then what is
+    // left of the windows with their events (leon_pipeline_destroy has emptied the flow by then), the streams last.
+    PipeFlow flow;
 
     std::vector<std::thread> parsers;
     std::thread submitter, notifier;
-    std::vector<Arena*> all_arenas;
+    std::vector<std::unique_ptr<Arena>> all_arenas;
 
     // stats
     Clock::time_point t0;
     std::atomic<uint64_t> st_pictures{0}, st_gops{0}, st_entries{0}, st_parse_ns{0}, st_upload{0}, st_submit_ns{0};
-    double st_seconds = 0;
 };
 
 namespace {
 
-void pipe_fail(leon_pipeline* p, int code, const std::string& msg)
-{
-    std::lock_guard<std::mutex> lk(p->mu);
-    if (p->status == LEON_OK) {
-        p->status = code;
-        p->err = msg;
-    }
-    p->stop = true;
-    p->cv.notify_all();
-}
+void pipe_fail(leon_pipeline* p, int code, const std::string& msg) { p->flow.fail(code, msg); }
 
 // host_need bytes of pinned memory and dev_need bytes of its device twin (equal for a GOP parsed on the host: the
 // arena is copied as it is; the GPU parser uploads the stream bytes only and keeps everything else on the device)
@@ -825,39 +790,17 @@ void parser_main(leon_pipeline* p)
 {
     hipSetDevice(p->cfg.device_id);
     for (;;) {
-        Arena* a = nullptr;
-        uint64_t g;
-        std::shared_ptr<const PipeRun> run;
-        {
-            std::unique_lock<std::mutex> lk(p->mu);
-            // an arena is the ticket to parse ahead: there are W * (R + 1) of them; once every GOP of the run is taken
-            // the thread waits for a seek
-            p->cv.wait(lk, [&] { return p->stop || (!p->free_arenas.empty() && p->next_gop < p->run->total_gops); });
-            if (p->stop) return;
-            run = p->run;
-            g = p->next_gop++;
-            a = p->free_arenas.front();
-            p->free_arenas.pop_front();
-        }
-        GopJob* job = new GopJob();
-        job->run = run;
-        job->gop = g;
-        job->arena = a;
+        std::unique_ptr<GopJob> owned = p->flow.take_gop();
+        if (!owned) return;
+        const std::shared_ptr<const PipeRun> run = owned->run;
+        const uint64_t g = owned->gop;
         const uint32_t key = run->mine[g % run->mine.size()];
-        bool dropped = false;
-        {   // a stream that is still arriving (leon_pipeline_create_partial): the GOP's bytes must be there -- the
-            // decoder of the reference stalls the same way when its buffer runs dry (features/bitreader.js:135-189)
-            const uint64_t need = p->shard_end[key];
-            std::unique_lock<std::mutex> lk(p->mu);
-            p->cv.wait(lk, [&] { return p->stop || p->valid >= need || p->run != run; });
-            if (p->stop) { p->free_arenas.push_back(a); delete job; return; }
-            if (p->run != run) {         // seeked away from while waiting
-                p->free_arenas.push_back(a);
-                delete job;
-                dropped = true;
-            }
-        }
-        if (dropped) { p->cv.notify_all(); continue; }
+        // a stream that is still arriving (leon_pipeline_create_partial): the GOP's bytes must be there -- the decoder of the
+        // reference stalls the same way when its buffer runs dry (features/bitreader.js:135-189)
+        const PipeFlow::Bytes bytes = p->flow.await_bytes(owned, p->shard_end[key]);
+        if (bytes == PipeFlow::Bytes::Stop) return;
+        if (bytes == PipeFlow::Bytes::Replaced) continue;
+        GopJob* const job = owned.get();
         {
             const uint8_t* b = p->stream + p->shard_begin[key];
             if (b[0] != 0 || b[1] != 0 || b[2] != 1) {
@@ -878,15 +821,7 @@ void parser_main(leon_pipeline* p)
         }
         if (job->status == LEON_OK && g == 0 && run->exact_ms >= 0) trim_to_target(p, job, run->exact_ms);
         p->st_parse_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t).count();
-        {
-            std::lock_guard<std::mutex> lk(p->mu);
-            if (p->run == run) p->parsed[g] = job;
-            else {                       // a GOP of a run seeked away from
-                p->free_arenas.push_back(job->arena);
-                delete job;
-            }
-        }
-        p->cv.notify_all();
+        p->flow.hand_parsed(std::move(owned));
     }
 }
 
@@ -900,7 +835,7 @@ int launch_gpu_parser(leon_pipeline* p, PipeWindow* w)
 {
     hipStream_t vs = p->vlc_stream[vlc_stream_of(w->id)];
     size_t n_slices = 0, n_pics = 0;
-    for (GopJob* job : w->jobs) { n_slices += job->slices.size(); n_pics += job->vpics.size(); }
+    for (const auto& job : w->jobs) { n_slices += job->slices.size(); n_pics += job->vpics.size(); }
     w->n_vpics = (uint32_t)n_pics;
     if (!n_slices || !n_pics) return LEON_OK;
     VlcRing& R = p->vlc_ring[(size_t)w->ring];
@@ -923,7 +858,7 @@ int launch_gpu_parser(leon_pipeline* p, PipeWindow* w)
     struct PicRun { const leon::VlcSlice* first; uint32_t n, pic; int type; };
     std::vector<PicRun> runs;
     runs.reserve(n_pics);
-    for (GopJob* job : w->jobs) {
+    for (const auto& job : w->jobs) {
         // what the kernels count in and report through starts at zero (regions are multiples of 256 bytes)
         hc[ci].ptr = (uint4*)(job->arena->dev + job->zero_begin);
         hc[ci].n16 = job->zero_bytes / 16;
@@ -1027,7 +962,7 @@ int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::ve
     int prev_last = -1, lv_prev_last = -1;       // the lane before's last anchor and its level
     *uses_carry = false;
     for (size_t j = 0; j < w->jobs.size(); j++) {
-        const GopJob* job = w->jobs[j];
+        const GopJob* job = w->jobs[j].get();
         int older = -1, newer = -1, lv_older = -1, lv_newer = -1, n_anchor = 0;      // anchor slots (0..2 of the lane) and their levels
         int n_b = 0;
         for (const PipePic& m : job->pics) {
@@ -1085,7 +1020,7 @@ int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::ve
 int upload_and_chain(leon_pipeline* p, PipeWindow* w, bool serial, bool poison)
 {
     leon_decoder* d = p->dec;
-    for (GopJob* job : w->jobs) {
+    for (const auto& job : w->jobs) {
         const size_t up = p->gpu_parser ? job->upload_bytes : job->arena->used;
         if (poison && p->gpu_parser && job->arena->used > up) HIP_TRY(hipMemsetAsync(job->arena->dev + up, 0xCD, job->arena->used - up, p->copy_stream));
         if (up) {
@@ -1183,7 +1118,7 @@ void list_frames(leon_pipeline* p, PipeWindow* w)
     w->tensors.clear();
     w->frame_ids.clear();
     for (size_t j = 0; j < w->jobs.size(); j++) {
-        const GopJob* job = w->jobs[j];
+        const GopJob* job = w->jobs[j].get();
         // by temporal reference: a GOP cut short by the encoder may skip display positions
         std::vector<const PipePic*> by_disp((size_t)p->max_pics, nullptr);
         for (const PipePic& m : job->pics) by_disp[(size_t)m.tref] = &m;
@@ -1419,17 +1354,18 @@ int regions_reserve(leon_pipeline* p, size_t upload_bytes, size_t out_bytes)
     return LEON_OK;
 }
 
-// the ring ids of a delivered window's frames: p->mu is held for the look-up and the copy only (the notify thread and release_window need it)
+// the ring ids of a delivered window's frames
 int regions_window_ids(leon_pipeline* p, int64_t window, std::vector<uint32_t>* ids)
 {
-    std::lock_guard<std::mutex> lk(p->mu);
-    auto it = p->delivered.find(window);
-    if (it == p->delivered.end()) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-    const PipeWindow* w = it->second;
-    if (w->status != LEON_OK) return fail(LEON_ERR_INVALID, "window %lld was delivered with an error (status %d)", (long long)window, w->status);
-    const uint32_t base = (uint32_t)((size_t)w->ring * p->W * p->max_pics);
-    ids->reserve(w->frame_ids.size());
-    for (uint32_t id : w->frame_ids) ids->push_back(base + id);
+    int status = LEON_OK;
+    const bool out = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        if ((status = w.status) != LEON_OK) return;
+        const uint32_t base = (uint32_t)((size_t)w.ring * p->W * p->max_pics);
+        ids->reserve(w.frame_ids.size());
+        for (uint32_t id : w.frame_ids) ids->push_back(base + id);
+    });
+    if (!out) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (status != LEON_OK) return fail(LEON_ERR_INVALID, "window %lld was delivered with an error (status %d)", (long long)window, status);
     return LEON_OK;
 }
 
@@ -1957,52 +1893,14 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
 void submit_loop(leon_pipeline* p)
 {
     for (;;) {
-        PipeWindow* w = new PipeWindow();
         const auto t_begin = Clock::now();
         auto t_ring = t_begin, t_scanned = t_begin;
-        {
-            std::unique_lock<std::mutex> lk(p->mu);
-            // a window of the current run to submit (once the run is all submitted the thread waits for a seek), a free entry
-            // of the RGBA ring, then every GOP of the window parsed.  A seek in between: the ring entry goes back, and the
-            // window is taken from the new run.
-            for (;;) {
-                p->cv.wait(lk, [&] {
-                    if (p->stop) return true;
-                    if (p->run_submitted >= p->run->total_windows) return false;
-                    for (int r = 0; r < p->R; r++)
-                        if (p->ring_owner[r] < 0) return true;
-                    return false;
-                });
-                if (p->stop) { delete w; return; }
-                t_ring = Clock::now();
-                w->run = p->run;
-                w->id = p->next_window++;
-                for (int r = 0; r < p->R; r++)
-                    if (p->ring_owner[r] < 0) { w->ring = r; p->ring_owner[r] = w->id; break; }
-                const uint64_t g0 = (uint64_t)p->run_submitted * p->W, g1 = std::min<uint64_t>(g0 + p->W, w->run->total_gops);
-                p->cv.wait(lk, [&] {
-                    if (p->stop || p->run != w->run) return true;
-                    for (uint64_t g = g0; g < g1; g++)
-                        if (!p->parsed.count(g)) return false;
-                    return true;
-                });
-                if (p->stop) { delete w; return; }
-                if (p->run != w->run) {
-                    p->ring_owner[w->ring] = -1;
-                    continue;
-                }
-                t_scanned = Clock::now();
-                for (uint64_t g = g0; g < g1; g++) {
-                    w->jobs.push_back(p->parsed[g]);
-                    p->parsed.erase(g);
-                }
-                p->run_submitted++;
-                break;
-            }
-        }
+        std::unique_ptr<PipeWindow> owned = p->flow.take_window(&t_ring, &t_scanned);
+        if (!owned) return;
+        PipeWindow* const w = owned.get();
         int rc = LEON_OK;
         std::string msg;
-        for (GopJob* j : w->jobs)
+        for (const auto& j : w->jobs)
             if (j->status != LEON_OK && rc == LEON_OK) { rc = j->status; msg = j->err; }
         if (rc == LEON_OK) {
             if (!w->done.create(hipEventDisableTiming)) { rc = LEON_ERR_HIP; msg = "hipEventCreate failed"; }
@@ -2014,18 +1912,13 @@ void submit_loop(leon_pipeline* p)
             }
         }
         w->status = rc;
-        {   // where the submit thread's time goes, per window (LEON_PIPE_TRACE=1 prints it when the pipeline is destroyed)
+        {   // where the submit thread's time goes, per window (LEON_DEBUG_PIPE_TIMING=1 prints it when the pipeline is destroyed)
             const auto ns = [](Clock::time_point a, Clock::time_point b) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count(); };
             p->st_wait_ring_ns += ns(t_begin, t_ring);
             p->st_wait_scan_ns += ns(t_ring, t_scanned);
         }
         if (rc != LEON_OK) pipe_fail(p, rc, msg);
-        {   // (a window of a run seeked away from meanwhile goes the same way: the notify thread drains it)
-            std::lock_guard<std::mutex> lk(p->mu);
-            p->to_notify.push_back(w);
-            p->windows_submitted++;
-        }
-        p->cv.notify_all();
+        p->flow.submitted(std::move(owned));
         if (rc != LEON_OK) return;
     }
 }
@@ -2034,71 +1927,26 @@ void submit_main(leon_pipeline* p)
 {
     hipSetDevice(p->cfg.device_id);
     submit_loop(p);
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        p->submit_exited = true;
-    }
-    p->cv.notify_all();
-}
-
-void release_window_locked(leon_pipeline* p, PipeWindow* w)
-{
-    for (GopJob* j : w->jobs) {
-        p->free_arenas.push_back(j->arena);
-        delete j;
-    }
-    p->ring_owner[w->ring] = -1;
-    delete w;
+    p->flow.submit_exited();
 }
 
 void notify_main(leon_pipeline* p)
 {
     hipSetDevice(p->cfg.device_id);
     for (;;) {
-        PipeWindow* w = nullptr;
-        std::shared_ptr<const PipeRun> ended;
-        bool quiet;
-        {
-            std::unique_lock<std::mutex> lk(p->mu);
-            p->cv.wait(lk, [&] {
-                return !p->to_notify.empty() || p->submit_exited ||
-                       (!p->stop && !p->run_ended && p->run_done == p->run->total_windows);
-            });
-            if (!p->to_notify.empty()) {
-                w = p->to_notify.front();
-                p->to_notify.pop_front();
-            } else if (p->submit_exited) break;
-            else {      // every window of the run delivered: its 'ended'; the thread stays for the next seek
-                p->run_ended = true;
-                p->in_callback = true;
-                ended = p->run;
-            }
-            quiet = p->quiet;
-        }
-        if (ended) {
-            if (p->cb && !quiet) p->cb(p->user, -1, nullptr, 0, LEON_OK);
-            {
-                std::lock_guard<std::mutex> lk(p->mu);
-                p->in_callback = false;
-                p->ended_run = ended;
-            }
-            p->cv.notify_all();
+        PipeFlow::Event ev = p->flow.next_event();
+        if (ev.exit()) break;
+        if (ev.ended) {
+            if (p->cb && !ev.quiet) p->cb(p->user, -1, nullptr, 0, LEON_OK);
+            p->flow.ended_returned(ev.ended);
             continue;
         }
+        std::unique_ptr<PipeWindow>& w = ev.window;
         if (w->status == LEON_OK && hipEventSynchronize(w->done) != hipSuccess) {
             w->status = LEON_ERR_HIP;
             pipe_fail(p, LEON_ERR_HIP, std::string("window ") + std::to_string(w->id) + ": " + hipGetErrorString(hipGetLastError()));
         }
-        {   // a window of a run seeked away from: drained -- its launches have finished (the event above), its ring entry,
-            // arenas and descriptor ring entry go back -- and never delivered.  Once a window is past this point a seek
-            // waits for its callback to return (in_callback).
-            std::lock_guard<std::mutex> lk(p->mu);
-            if (w->run != p->run && w->status == LEON_OK) {
-                release_window_locked(p, w);
-                w = nullptr;
-            } else p->in_callback = true;
-        }
-        if (!w) { p->cv.notify_all(); continue; }
+        if (!p->flow.keep_or_retire(w)) continue;
         if (w->status == LEON_OK && p->gpu_parser && w->n_vpics) {          // the GPU parser's verdict on every picture of the window
             const uint32_t* e = p->vlc_ring[(size_t)w->ring].h_err;
             for (uint32_t k = 0; k < w->n_vpics; k++)
@@ -2117,37 +1965,17 @@ void notify_main(leon_pipeline* p)
         const int64_t id = w->id;
         const int st = w->status;
         const std::shared_ptr<const PipeRun> run = w->run;
-        {
-            std::lock_guard<std::mutex> lk(p->mu);
-            p->delivered[id] = w;
-            p->st_seconds = std::chrono::duration<double>(Clock::now() - p->t0).count();
-            if (p->st_window_done.size() < 4096) p->st_window_done.push_back(p->st_seconds);
-            quiet = p->quiet;
-        }
+        bool quiet = false;
+        const PipeWindow* out = p->flow.deliver(std::move(w), std::chrono::duration<double>(Clock::now() - p->t0).count(), &quiet);
         // frames are handed over outside the lock: the callback may release the window at once
-        if (p->cb && !quiet) p->cb(p->user, id, st == LEON_OK ? w->frames.data() : nullptr, st == LEON_OK ? (int32_t)w->frames.size() : 0, st);
+        if (p->cb && !quiet) p->cb(p->user, id, st == LEON_OK ? out->frames.data() : nullptr, st == LEON_OK ? (int32_t)out->frames.size() : 0, st);
         else leon_pipeline_release_window(p, id);
-        {
-            std::lock_guard<std::mutex> lk(p->mu);
-            p->windows_done++;
-            if (run == p->run) p->run_done++;
-            p->in_callback = false;
-        }
-        p->cv.notify_all();
-    }
-    bool quiet;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        quiet = p->quiet;
+        p->flow.callback_returned(run);
     }
     // 'ended' (or the error that stopped the run) BEFORE leon_pipeline_wait returns: a host that waits and then
     // looks at what its callback recorded must find the end recorded
-    if (p->cb && !quiet) p->cb(p->user, -1, nullptr, 0, p->status);
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        p->finished = true;
-    }
-    p->cv.notify_all();
+    if (p->cb && !p->flow.quiet()) p->cb(p->user, -1, nullptr, 0, p->flow.status());
+    p->flow.finish();
 }
 
 // The run that starts at `seconds`: the key-map entry the front end's own seek finds (leon_vlc_seek, decoders/jsv.js
@@ -2190,7 +2018,6 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
     p->cfg = *cfg;
     p->stream = stream;
     p->bytes = bytes;
-    p->valid = valid_bytes;
     if (const char* cd = getenv("LEON_DEBUG_CAPTURE")) p->capture_dir = cd;
     if (n_keys > 0) {
         for (int g = 0; g < n_keys; g++) {
@@ -2214,8 +2041,9 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
     p->has_keymap = n_keys > 0;
     for (uint32_t g = si; g < p->shard_begin.size(); g += sc) p->shard_gops.push_back(g);
     p->W = cfg->gops_per_window > 0 ? cfg->gops_per_window : 32;
-    p->run = make_run(p, st, cfg->start_seconds, loops);
-    const PipeRun& run = *p->run;
+    const std::shared_ptr<const PipeRun> first_run = make_run(p, st, cfg->start_seconds, loops);
+    p->flow.begin(first_run, valid_bytes);
+    const PipeRun& run = *first_run;
     p->info.first_gop = run.first_key;
     if (run.mine.empty()) return fail(LEON_ERR_INVALID, "shard %u of %u gets no GOP: the stream has %zu", si, sc, p->shard_begin.size());
     if ((uint64_t)p->W > run.total_gops) p->W = (int)run.total_gops;      // (one window either way: run.total_windows stands)
@@ -2421,7 +2249,6 @@ int allocate_pipeline(leon_pipeline* p)
         }
     }
     if ((p->output & LEON_PIPELINE_OUTPUT_RGBA) && (rc = alloc_ring(p, &p->d_rgba, p->frame_bytes, "RGBA")) != LEON_OK) return rc;
-    p->ring_owner.assign((size_t)p->R, -1);
     if (p->gpu_parser) {
         std::vector<leon_vlc_gpu_tables> src(1);
         std::vector<leon::VlcTables> t(1);
@@ -2445,11 +2272,12 @@ int allocate_pipeline(leon_pipeline* p)
         p->vlc_ring.resize((size_t)p->R);
     }
     const int n_arenas = p->W * (p->R + 1);
+    std::vector<Arena*> tickets;
     for (int i = 0; i < n_arenas; i++) {
-        Arena* a = new Arena();
-        p->all_arenas.push_back(a);
-        p->free_arenas.push_back(a);
+        p->all_arenas.push_back(std::make_unique<Arena>());
+        tickets.push_back(p->all_arenas.back().get());
     }
+    p->flow.equip(p->W, p->R, tickets);
     if (p->gpu_parser) {
         // The arenas of the GPU parser come out of two slabs allocated HERE, sized for the largest GOP shard of the key
         // map by the bounds scan_gop_for_gpu sizes a GOP's arena with: vlc_entry_bound over the whole shard (32 / 3 bytes of
@@ -2471,7 +2299,7 @@ int allocate_pipeline(leon_pipeline* p)
                 p->slab_dev = std::move(dev);
                 p->slab_host = std::move(host);
                 for (int i = 0; i < n_arenas; i++) {
-                    Arena* a = p->all_arenas[(size_t)i];
+                    Arena* a = p->all_arenas[(size_t)i].get();
                     a->dev.borrow(p->slab_dev + (size_t)i * dev_each, dev_each);
                     a->host.borrow(p->slab_host + (size_t)i * host_each, host_each);
                 }
@@ -2507,11 +2335,7 @@ int leon_pipeline_feed(leon_pipeline* p, size_t valid_bytes)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
     if (valid_bytes > p->bytes) return fail(LEON_ERR_INVALID, "%zu bytes fed, the stream has %zu", valid_bytes, p->bytes);
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (valid_bytes > p->valid) p->valid = valid_bytes;
-    }
-    p->cv.notify_all();
+    p->flow.feed(valid_bytes);
     return LEON_OK;
 }
 
@@ -2611,31 +2435,25 @@ int leon_pipeline_create_tensor_canvas(const leon_pipeline_config* cfg, const le
 int leon_pipeline_get_info(leon_pipeline* p, leon_pipeline_info* out)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(p->mu);
     *out = p->info;
+    const std::shared_ptr<const PipeRun> run = p->flow.run();       // these two change with the run (leon_pipeline_seek)
+    out->first_gop = run->first_key;
+    out->shard_gops = (uint32_t)run->mine.size();
     return LEON_OK;
 }
 
 int leon_pipeline_release_window(leon_pipeline* p, int64_t window)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        auto it = p->delivered.find(window);
-        if (it == p->delivered.end()) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-        release_window_locked(p, it->second);
-        p->delivered.erase(it);
-    }
-    p->cv.notify_all();
+    if (!p->flow.release(window)) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
     return LEON_OK;
 }
 
 int leon_pipeline_wait(leon_pipeline* p)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
-    std::unique_lock<std::mutex> lk(p->mu);
-    p->cv.wait(lk, [&] { return p->finished || p->ended_run == p->run; });      // the current run
-    if (p->status != LEON_OK) return fail(p->status, "%s", p->err.c_str());
+    const int status = p->flow.wait_run();
+    if (status != LEON_OK) return fail(status, "%s", p->flow.error());
     return LEON_OK;
 }
 
@@ -2646,10 +2464,7 @@ int leon_pipeline_seek(leon_pipeline* p, double seconds, int32_t mode, int64_t* 
     if (!std::isfinite(seconds)) return fail(LEON_ERR_INVALID, "seek to a time that is not finite");
     if (p->cfg.loop > 1) return fail(LEON_ERR_INVALID, "a pipeline that loops over the stream (loop = %d, benchmarking) does not seek", p->cfg.loop);
     if (std::this_thread::get_id() == p->notifier.get_id()) return fail(LEON_ERR_INVALID, "leon_pipeline_seek from inside the pipeline's callback");
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (p->status != LEON_OK) return fail(LEON_ERR_INVALID, "the pipeline has failed: %s", p->err.c_str());
-    }
+    if (p->flow.status() != LEON_OK) return fail(LEON_ERR_INVALID, "the pipeline has failed: %s", p->flow.error());
     // the key map through a view of the pipeline's own bytes: nothing is copied, and a partial stream may be seeked
     // past what has arrived (the parser threads wait for leon_pipeline_feed, as after create)
     leon_vlc_stream* st = nullptr;
@@ -2659,36 +2474,19 @@ int leon_pipeline_seek(leon_pipeline* p, double seconds, int32_t mode, int64_t* 
     if (st) leon_vlc_close(st);
     // EXACT: the shard that owns the entry trims its first GOP (trim_to_target); the others decode from their next GOP on
     if (mode == LEON_PIPELINE_SEEK_EXACT && !run->mine.empty() && run->mine[0] == run->first_key) run->exact_ms = std::max(seconds, 0.0) * 1000.0;
-    std::unique_lock<std::mutex> lk(p->mu);
-    if (p->status != LEON_OK) return fail(LEON_ERR_INVALID, "the pipeline has failed: %s", p->err.c_str());
-    p->run = run;
-    p->next_gop = 0;
-    p->run_submitted = p->run_done = 0;
-    p->run_ended = false;
-    *first_window = p->next_window;
-    // what was parsed for the old position goes back; GOPs still on the parser threads are dropped when they are done,
-    // windows submitted and not delivered are drained by the notify thread (notify_main), held windows stay held
-    for (auto& kv : p->parsed) {
-        p->free_arenas.push_back(kv.second->arena);
-        delete kv.second;
-    }
-    p->parsed.clear();
-    p->info.first_gop = run->first_key;
-    p->info.shard_gops = (uint32_t)run->mine.size();
-    p->cv.notify_all();
-    p->cv.wait(lk, [&] { return !p->in_callback; });      // a callback under way returns first
+    if (!p->flow.seek(run, first_window)) return fail(LEON_ERR_INVALID, "the pipeline has failed: %s", p->flow.error());
     return LEON_OK;
 }
 
 int leon_pipeline_get_stats(leon_pipeline* p, leon_pipeline_stats* out)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(p->mu);
+    const PipeFlow::Counts c = p->flow.counts();
     out->pictures = p->st_pictures;
     out->gops = p->st_gops;
-    out->windows = (uint64_t)p->windows_done;
+    out->windows = (uint64_t)c.windows_done;
     out->stream_bytes = p->bytes;
-    out->seconds = p->st_seconds;
+    out->seconds = c.seconds;
     out->parse_seconds_sum = (double)p->st_parse_ns.load() * 1e-9;
     out->upload_bytes = (double)p->st_upload.load();
     out->entries = p->st_entries;
@@ -2723,12 +2521,14 @@ int leon_pipeline_window_tensors(leon_pipeline* p, int64_t window, void** out, i
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
     if (!p->d_tensor) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
-    std::lock_guard<std::mutex> lk(p->mu);
-    auto it = p->delivered.find(window);
-    if (it == p->delivered.end()) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-    const PipeWindow* w = it->second;
-    if (n < 0 || (size_t)n != w->tensors.size()) return fail(LEON_ERR_INVALID, "window %lld has %zu tensors, not %d", (long long)window, w->tensors.size(), n);
-    for (size_t i = 0; i < w->tensors.size(); i++) out[i] = w->tensors[i];
+    size_t has = 0;
+    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        has = w.tensors.size();
+        if (n >= 0 && (size_t)n == has)
+            for (size_t i = 0; i < has; i++) out[i] = w.tensors[i];
+    });
+    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (n < 0 || (size_t)n != has) return fail(LEON_ERR_INVALID, "window %lld has %zu tensors, not %d", (long long)window, has, n);
     return LEON_OK;
 }
 
@@ -2737,13 +2537,11 @@ int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, v
     if (!p || !host) return fail(LEON_ERR_INVALID, "null argument");
     if (!p->d_tensor) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
     const uint8_t* src = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        auto it = p->delivered.find(window);
-        if (it == p->delivered.end()) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-        if (index < 0 || (size_t)index >= it->second->tensors.size()) return fail(LEON_ERR_INVALID, "window %lld has no frame %d", (long long)window, index);
-        src = it->second->tensors[(size_t)index];
-    }
+    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        if (index >= 0 && (size_t)index < w.tensors.size()) src = w.tensors[(size_t)index];
+    });
+    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (!src) return fail(LEON_ERR_INVALID, "window %lld has no frame %d", (long long)window, index);
     HIP_TRY(hipSetDevice(p->cfg.device_id));
     HIP_TRY(hipMemcpy(host, src, p->tensor_bytes, hipMemcpyDeviceToHost));
     return LEON_OK;
@@ -2895,19 +2693,13 @@ int leon_pipeline_resize_weights_device(int32_t device_id, int32_t n_axes, const
 const char* leon_pipeline_error(leon_pipeline* p)
 {
     if (!p) return "";
-    std::lock_guard<std::mutex> lk(p->mu);
-    return p->err.c_str();
+    return p->flow.error();
 }
 
 void leon_pipeline_destroy(leon_pipeline* p)
 {
     if (!p) return;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        p->stop = true;
-        p->quiet = true;           // no callbacks while tearing down
-    }
-    p->cv.notify_all();
+    p->flow.stop_quiet();      // no callbacks while tearing down
     for (auto& t : p->parsers) if (t.joinable()) t.join();
     if (p->submitter.joinable()) p->submitter.join();
     if (p->notifier.joinable()) p->notifier.join();      // drains what was submitted, releasing instead of delivering
@@ -2920,23 +2712,18 @@ void leon_pipeline_destroy(leon_pipeline* p)
     for (hipStream_t vs : p->vlc_stream)
         if (vs) hipStreamSynchronize(vs);
     if (p->dec) leon_sync(p->dec);
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        for (auto& kv : p->delivered) release_window_locked(p, kv.second);
-        p->delivered.clear();
-        for (auto& kv : p->parsed) delete kv.second;
-        p->parsed.clear();
-    }
-    for (Arena* a : p->all_arenas) delete a;
+    p->flow.tear_down();       // delivered windows released, their events destroyed in front of the streams
+    const int64_t submitted = p->flow.counts().windows_submitted;
     if (getenv("LEON_DEBUG_PIPE_TIMING"))      // where the submit thread's time went (LEON_DEBUG_PIPE_TIMING=1)
         fprintf(stderr, "leon pipeline: %llu windows; per window on the submit thread: %.2f ms waiting for a ring entry, %.2f ms waiting for the window's GOPs "
-                        "(parser threads), %.2f ms in submit_window\n", (unsigned long long)p->windows_submitted,
-                p->windows_submitted ? (double)p->st_wait_ring_ns / 1e6 / (double)p->windows_submitted : 0.0,
-                p->windows_submitted ? (double)p->st_wait_scan_ns / 1e6 / (double)p->windows_submitted : 0.0,
-                p->windows_submitted ? (double)p->st_submit_ns.load() / 1e6 / (double)p->windows_submitted : 0.0);
-    if (getenv("LEON_DEBUG_PIPE_TIMING") && !p->st_window_done.empty()) {
+                        "(parser threads), %.2f ms in submit_window\n", (unsigned long long)submitted,
+                submitted ? (double)p->st_wait_ring_ns / 1e6 / (double)submitted : 0.0,
+                submitted ? (double)p->st_wait_scan_ns / 1e6 / (double)submitted : 0.0,
+                submitted ? (double)p->st_submit_ns.load() / 1e6 / (double)submitted : 0.0);
+    const std::vector<double> window_done = p->flow.window_done();
+    if (getenv("LEON_DEBUG_PIPE_TIMING") && !window_done.empty()) {
         fprintf(stderr, "leon pipeline: windows completed at (ms):");
-        for (size_t i = 0; i < p->st_window_done.size() && i < 64; i++) fprintf(stderr, " %.1f", p->st_window_done[i] * 1e3);
+        for (size_t i = 0; i < window_done.size() && i < 64; i++) fprintf(stderr, " %.1f", window_done[i] * 1e3);
         fprintf(stderr, "\n");
     }
     leon_decoder* const dec = p->dec;
