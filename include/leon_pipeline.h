@@ -61,6 +61,9 @@ typedef struct leon_pipeline leon_pipeline;
 /* Bit 4, not 2 or 3: create goes on refusing output = 4 and 8 (tests/test_pipeline_planes_gpu.py::test_refusals).  Written as a
  * shift: the decimal defines of this family are the RGBA / YCBCR pair tests/test_pipeline_planes_abi.py compares with its binding. */
 #define LEON_PIPELINE_OUTPUT_TENSOR (1 << 4)
+/* Bit 5: 4 and 8 stay refused as above, and so does every other unknown bit (-1 among them).  Only beside RGBA, YCBCR or TENSOR: a
+ * pipeline that parses and reconstructs nothing is a later step, so the bit on its own (output = 32) is refused at create. */
+#define LEON_PIPELINE_OUTPUT_MOTION (1 << 5)
 
 /* element type of the tensor output (leon_pipeline_tensor_config.dtype) */
 #define LEON_TENSOR_F16  1
@@ -112,7 +115,7 @@ typedef struct leon_pipeline_config {
      *     Takes the unfused road: every picture writes its planes, one k_rgba_gl launch per picture.  Not with yuva streams. */
     int32_t display_flavour;
     /* What a frame carries, a bit set (0 = LEON_PIPELINE_OUTPUT_RGBA, what every caller got before the field existed; other bits
-     * are refused at create):
+     * are refused at create; LEON_PIPELINE_OUTPUT_TENSOR and LEON_PIPELINE_OUTPUT_MOTION are described further down):
      *   LEON_PIPELINE_OUTPUT_RGBA   frame.rgba, RGBA8 in the display flavour above
      *   LEON_PIPELINE_OUTPUT_YCBCR  frame.y / cb / cr (+ a for yuva streams): the decoded YCbCr 4:2:0 planes, cropped to the frame --
      *                               the reference's own frame event, this['go']('frame', {'ybr': [Y, Cb, Cr], 'ts': ts})
@@ -266,6 +269,52 @@ typedef struct leon_pipeline_tensor_canvas {
     int32_t reserved[7];                 /* must be 0 */
 } leon_pipeline_tensor_canvas;           /* 64 bytes */
 
+/* LEON_PIPELINE_OUTPUT_MOTION: what the stream says about motion, per delivered frame -- the block-motion field a compressed-domain
+ * model reads, the vectors that carry a detector's boxes from an anchor across the B pictures between, what `-flags2 +export_mvs` gives.
+ * A delivered frame of a picture of type t gets one MOTION RECORD.  Its macroblocks are in raster order of the CODED picture:
+ * mbw = coded_width / 16, mbh = coded_height / 16, mbs = mbw * mbh.  For macroblock k, with the picture's maps as include/leon.h
+ * defines them (integers only):
+ *     I picture:  info = 4;  mv = (0, 0, 0, 0)
+ *     P picture:  intra = repadd[k] >= 128
+ *                 info  = intra ? 4 : 1
+ *                 mv    = intra ? 0 : (mv_fwd[2k], mv_fwd[2k+1], 0, 0)
+ *     B picture:  intra = repadd[k] >= 128;  d = intra ? 0 : (mb_dir[k] & 3)
+ *                 info  = intra ? 4 : d
+ *                 mv    = (d&1 ? mv_fwd[2k] : 0, d&1 ? mv_fwd[2k+1] : 0,
+ *                          d&2 ? mv_bwd[2k] : 0, d&2 ? mv_bwd[2k+1] : 0)
+ * info bits: 1 forward, 2 backward, 4 intra; the other bits are 0.  Vectors are in half-pel luma units as the maps hold them (full_pel
+ * vectors are already doubled); positive means right / down, from the macroblock to where it reads in the reference.
+ * This is exactly the stream-carried part of the maps: the maps also hold parser state -- the entry of a direction a B macroblock does
+ * not use holds the predictor, a skipped macroblock keeps the intra flag of the picture before -- which the record leaves out, so two
+ * sets of maps that agree in what the stream carries give the same record, whichever parser wrote them.  The `intra` map is not used.
+ * The record in memory, the same on the device and on the host (pad256 = rounding up to 256):
+ *     mv       int16 [mbs][4]   fwd_h, fwd_v, bwd_h, bwd_v      at 0
+ *     info     uint8 [mbs]                                      at info_offset    = pad256(8 * mbs)
+ *     summary  uint32[8]                                        at summary_offset = info_offset + pad256(mbs)
+ *     record_bytes = summary_offset + 32;   record_pitch = pad256(record_bytes)
+ * Summary words, over the RECORD's values: [0] macroblocks with info & 1, [1] with info & 2, [2] with info & 4, [3] macroblocks with any
+ * non-zero vector word, [4..7] the sums of |fwd_h|, |fwd_v|, |bwd_h|, |bwd_v|.  A vector word is at most 2048 in magnitude (f_code 7,
+ * full_pel doubled) and a picture has at most 256 x 256 macroblocks: a sum is at most 2^27 and fits its word with room.
+ * The bytes between the parts, and up to the pitch, are unspecified.  Every specified byte of every delivered frame's record is
+ * written by its window's launch (k_motion: one launch per window on the decoder's stream behind the reconstruction, one workgroup per
+ * frame), every window; nothing relies on an earlier clear.  A window delivered with an error has unspecified records.  Pictures that
+ * are not delivered (dropped leading B pictures, what an EXACT seek trims) have no record. */
+/* (a struct tag only, no typedef: the host call that fills it has the same name, so it is written `struct leon_pipeline_motion_layout`) */
+struct leon_pipeline_motion_layout {
+    int32_t  mb_width, mb_height, mbs;
+    int32_t  reserved0;                 /* 0 */
+    uint64_t info_offset, summary_offset, record_bytes, record_pitch;
+    uint64_t reserved[2];               /* 0 */
+};                                      /* 64 bytes */
+
+typedef struct leon_pipeline_motion_frame {
+    void*    record;        /* DEVICE pointer, 256-byte aligned, valid until release_window */
+    uint64_t fwd_gop;       /* GOP id of the forward reference (an open GOP's leading B pictures: the GOP before) */
+    int32_t  fwd_display;   /* display_index of the picture the forward vectors point into; -1: none (I pictures) */
+    int32_t  bwd_display;   /* the same for backward vectors, always in the frame's own GOP; -1: none (I, P) */
+    int32_t  reserved[2];
+} leon_pipeline_motion_frame;           /* 32 bytes */
+
 typedef void (*leon_pipeline_callback)(void* user, int64_t window, const leon_pipeline_frame* frames, int32_t n_frames, int32_t status);
 
 typedef struct leon_pipeline_info {
@@ -387,6 +436,21 @@ int leon_pipeline_window_tensors(leon_pipeline* p, int64_t window, void** out, i
 /* copy the tensor of frame `index` of such a window to host memory, packed (tensor_frame_bytes: [3][height][width] of the geometry, or
  * [height][width][3] with LEON_TENSOR_LAYOUT_HWC) */
 int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, void* host);
+/* host only, no device: the record's layout for a picture of mb_width x mb_height macroblocks; refuses sizes outside 1 .. 256 */
+int leon_pipeline_motion_layout(int32_t mb_width, int32_t mb_height, struct leon_pipeline_motion_layout* out);
+/* host only: the definition above on the CPU (the per-macroblock text the kernel compiles too, csrc/leon_motion.h), from a picture's
+ * maps in host memory into a buffer of record_bytes.  Unspecified bytes are left alone.  Maps the type does not have may be NULL
+ * (I: all four; P: mb_dir and mv_bwd); refuses another type, a size outside 1 .. 256, a missing map, a null record */
+int leon_pipeline_motion_record(int32_t type, int32_t mb_width, int32_t mb_height, const uint8_t* repadd, const uint8_t* mb_dir,
+                                const int16_t* mv_fwd, const int16_t* mv_bwd, void* record);
+/* the layout of this pipeline's records; LEON_ERR_INVALID for a pipeline without LEON_PIPELINE_OUTPUT_MOTION */
+int leon_pipeline_get_motion_layout(leon_pipeline* p, struct leon_pipeline_motion_layout* out);
+/* the motion records of a delivered, not yet released window: out[i] belongs to frames[i], n = the window's n_frames.  May be called
+ * from inside the callback.  The references are the ones the picture's launch predicted from: a closed GOP's leading B picture names
+ * its I picture for both.  LEON_ERR_INVALID for a pipeline without the bit, a window that is not out for delivery, another n */
+int leon_pipeline_window_motion(leon_pipeline* p, int64_t window, leon_pipeline_motion_frame* out, int32_t n);
+/* copy the record of frame `index` of such a window to host memory, packed: mv [mbs][4], info [mbs], summary [8]; each may be NULL */
+int leon_pipeline_read_motion(leon_pipeline* p, int64_t window, int32_t index, int16_t* mv, uint8_t* info, uint32_t* summary);
 
 /* Regions of delivered frames as a tensor batch: what runs behind a detector.  The detector's boxes are cut out of the FULL-RESOLUTION
  * frames of a delivered window and resampled to a second-stage model's input size, any number of them in one call, into memory of the

@@ -39,6 +39,7 @@
 #include <stdint.h>
 #include "leon_resize_row.h"
 #include "leon_warp.h"
+#include "leon_motion.h"
 
 
 namespace leon {
@@ -2891,6 +2892,89 @@ __global__ __launch_bounds__(kRgbaBlock) void k_warp(const uint8_t* __restrict__
     const uint64_t dst_off = (uint64_t)blockIdx.z * join64(c.pitch_lo, c.pitch_hi);
     warp_store<EB, LAYOUT>(px, o < nox && sub < noy, tab_s, reinterpret_cast<char*>(stage_s), out + dst_off, ox0, oy0, nox, noy, o, sub, (uint32_t)c.ow,
                            (uint32_t)c.ow * (uint32_t)c.oh);
+}
+
+// ---- output MOTION: a frame's motion record (include/leon_pipeline.h, LEON_PIPELINE_OUTPUT_MOTION) ------------------------------
+// One launch per window behind its reconstruction levels: blockIdx.y = the delivered frame, one workgroup of 256 lanes a frame, walking
+// the picture's macroblocks in a strided loop, four consecutive macroblocks per lane and trip -- a dword of repadd and of mb_dir,
+// 16 bytes of each vector map in, two 16-byte stores of vectors and a dword of info out.  The maps are padded to 256 bytes in the arenas
+// (MapLayout) and the record's parts to 256 (leon_motion.h), so the last trip's lanes address whole dwords inside both; what they
+// write behind macroblock mbs - 1 lies in the record's unspecified bytes, and only the summary's counting asks which macroblocks exist.
+// The per-macroblock expression is the host's text (leon_motion.h).  The summary is summed per lane, across the wave by shuffles,
+// across the four waves through LDS; lane 0 stores its eight words: every specified byte of the record is written by this launch,
+// nothing is cleared beforehand and nothing is added to atomically.
+struct MotionDesc {
+    const uint8_t* repadd;       // the picture's maps in its GOP's device arena; null where the type has none
+    const uint8_t* mb_dir;
+    const uint32_t* mv_fwd;      // a macroblock's (h, v) as one dword
+    const uint32_t* mv_bwd;
+    int32_t type;                // LEON_PIC_*
+    uint32_t frame;              // the frame's index in the motion ring (frame_addr)
+    uint32_t reserved[2];
+};
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(kRgbaBlock) void k_motion(const MotionDesc* __restrict__ descs, uint8_t* __restrict__ ring, MotionLayout G)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t part_s[kRgbaBlock / 64][8];
+    const MotionDesc* __restrict__ D = descs + blockIdx.y;
+    const int32_t type = D->type;
+    const uint8_t* __restrict__ repadd = D->repadd;
+    const uint8_t* __restrict__ mb_dir = D->mb_dir;
+    const uint32_t* __restrict__ mv_fwd = D->mv_fwd;
+    const uint32_t* __restrict__ mv_bwd = D->mv_bwd;
+    uint8_t* __restrict__ rec = ring + (size_t)D->frame * G.record_pitch;
+    const uint32_t mbs = G.mbs;
+    uint32_t s[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    for (uint32_t k0 = 4u * threadIdx.x; k0 < mbs; k0 += 4u * kRgbaBlock) {
+        uint32_t ra = 0u, di = 0u;
+        uint4 f = uint4{0u, 0u, 0u, 0u}, b = uint4{0u, 0u, 0u, 0u};
+        if (type != 1) {
+            ra = *reinterpret_cast<const uint32_t*>(repadd + k0);
+            f = *reinterpret_cast<const uint4*>(mv_fwd + k0);
+        }
+        if (type == 3) {
+            di = *reinterpret_cast<const uint32_t*>(mb_dir + k0);
+            b = *reinterpret_cast<const uint4*>(mv_bwd + k0);
+        }
+        const uint32_t fi[4] = {f.x, f.y, f.z, f.w}, bi[4] = {b.x, b.y, b.z, b.w};
+        uint32_t of[4], ob[4], info4 = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t info = motion_mb(type, (ra >> (8 * i)) & 255u, (di >> (8 * i)) & 255u, fi[i], bi[i], &of[i], &ob[i]);
+            info4 |= info << (8 * i);
+            if (k0 + (uint32_t)i < mbs) motion_count(info, of[i], ob[i], s);
+        }
+        uint4* mv = reinterpret_cast<uint4*>(rec + (size_t)k0 * 8u);
+        mv[0] = uint4{of[0], ob[0], of[1], ob[1]};
+        mv[1] = uint4{of[2], ob[2], of[3], ob[3]};
+        *reinterpret_cast<uint32_t*>(rec + G.info_offset + k0) = info4;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) s[i] = wave_sum(s[i]);
+    if ((threadIdx.x & 63u) == 0u) {
+        uint4* ps = reinterpret_cast<uint4*>(part_s[threadIdx.x >> 6]);
+        ps[0] = uint4{s[0], s[1], s[2], s[3]};
+        ps[1] = uint4{s[4], s[5], s[6], s[7]};
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint4 lo = uint4{0u, 0u, 0u, 0u}, hi = lo;
+#pragma unroll
+        for (int w = 0; w < kRgbaBlock / 64; w++) {
+            const uint4 a = reinterpret_cast<const uint4*>(part_s[w])[0], c = reinterpret_cast<const uint4*>(part_s[w])[1];
+            lo.x += a.x; lo.y += a.y; lo.z += a.z; lo.w += a.w;
+            hi.x += c.x; hi.y += c.y; hi.z += c.z; hi.w += c.w;
+        }
+        uint4* sm = reinterpret_cast<uint4*>(rec + G.summary_offset);
+        sm[0] = lo;
+        sm[1] = hi;
+    }
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

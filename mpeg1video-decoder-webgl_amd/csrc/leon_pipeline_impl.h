@@ -68,6 +68,8 @@ struct PipeWindow {
     std::vector<leon_pipeline_frame> frames;
     std::vector<uint8_t*> tensors;       // output TENSOR: frames[i]'s tensor
     std::vector<uint32_t> frame_ids;     // ... and its index in the ring entry's lanes (what k_tensor finds planes and tensor by)
+    std::vector<leon_pipeline_motion_frame> motion;      // output MOTION: frames[i]'s record and references
+    std::vector<leon::MotionDesc> motion_descs;          // ... and what k_motion makes the record from
     Event done;
     int status = LEON_OK;
     uint32_t n_vpics = 0;        // gpu_parser: error words of the window's pictures are in the ring entry's h_err
@@ -115,6 +117,7 @@ struct leon_pipeline {
     uint64_t last_run = 0;       // PipeRun::id, 0: nothing remembered
     uint64_t last_gop = 0;       // the run's GOP the remembered anchor closes
     int last_anchor = -1;        // its slot, -1: none
+    int last_anchor_tref = -1;   // its display index (what the motion records of the next window's leading B pictures name)
     // (the streams stand in front of the buffers their work touches: members go in reverse order, the buffers first)
     Stream copy_stream;
     // The parser kernels of window n + 1 run beside the reconstruction of window n -- and beside the parser kernels of
@@ -131,6 +134,11 @@ struct leon_pipeline {
     std::vector<uint8_t> tensor_table;
     DevBuf<uint32_t> d_tensor_table;
     Mirror<uint32_t> tensor_ids;
+    // output MOTION: the ring of motion records (motion_lay.record_pitch apart, addressed by the frame's index like its planes and
+    // tensor), and per ring entry the descriptors of its window's frames for k_motion (pinned, device)
+    DevBuf<uint8_t> d_motion;
+    leon::MotionLayout motion_lay{};
+    Mirror<leon::MotionDesc> motion_descs;
     // ... resampled to a model's input size (leon_pipeline_tensor_resize; geom.resized = 0: the full-size tensor, k_tensor): the
     // tables of both axes as k_resample reads them -- first_x, count_x, Wx, first_y, count_y, Wy in one int32 buffer
     leon_pipeline_tensor_geometry tensor_geom{};
@@ -918,7 +926,8 @@ void capture_file(const std::string& path, const void* dev, size_t bytes)
 }
 
 // a picture of a level: the lane of its GOP in the window, the slots it writes and predicts from
-struct LevelPic { size_t lane; const PipePic* pic; int fwd, bwd, out; };
+// (fwd_tref, bwd_tref: the display indices of the pictures in those slots, -1: none; fwd_before: the forward one is of the GOP before)
+struct LevelPic { size_t lane; const PipePic* pic; int fwd, bwd, out; int fwd_tref = -1, bwd_tref = -1; bool fwd_before = false; };
 
 // after a level, the decoder's stream idle: the planes its pictures wrote and predicted from, a line each in the index
 // (the first level begins the index with the geometry)
@@ -956,15 +965,18 @@ int capture_level(const leon_pipeline* p, const PipeWindow* w, const std::string
 // B pictures of an open GOP wait for the lane before's last anchor, level 4 behind an IBBP-12, while the lane's own fourth anchor
 // would replace the I picture, their backward reference, at level 3.  So the I picture of such a GOP is written to the lane's HOLD
 // slot (behind the carry slot, one per lane), which nothing else of the window writes; its other anchors rotate as before.
-int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::vector<LevelPic>>& levels, int carry, bool* uses_carry, int* last_anchor)
+int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::vector<LevelPic>>& levels, int carry, bool* uses_carry, int* last_anchor,
+                int* last_anchor_tref)
 {
     const int per_lane = 3 + (p->unfused ? p->max_pics : 0);
     int prev_last = -1, lv_prev_last = -1;       // the lane before's last anchor and its level
+    int tr_prev_last = p->last_anchor_tref;      // ... and its display index (lane 0: the carried anchor's)
     *uses_carry = false;
     for (size_t j = 0; j < w->jobs.size(); j++) {
         const GopJob* job = w->jobs[j].get();
         int older = -1, newer = -1, lv_older = -1, lv_newer = -1, n_anchor = 0;      // anchor slots (0..2 of the lane) and their levels
         int n_b = 0;
+        int tr_older = -1, tr_newer = -1;        // the anchors' display indices
         for (const PipePic& m : job->pics) {
             LevelPic it{j, &m, -1, -1, -1};
             int lv = 0;
@@ -973,6 +985,7 @@ int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::ve
             } else if (m.type == LEON_PIC_P) {
                 if (newer < 0) return fail(LEON_ERR_INVALID, "GOP %llu: a P picture without a preceding anchor", (unsigned long long)job->gop);
                 it.fwd = newer;
+                it.fwd_tref = tr_newer;
                 lv = lv_newer + 1;
                 it.out = (int)(per_lane * j) + n_anchor % 3;
             } else {
@@ -983,11 +996,15 @@ int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::ve
                     return fail(LEON_ERR_INVALID, "GOP %llu is open (closed_gop = 0) and its leading B pictures may predict from the GOP before it: "
                                                   "GOP shards must be closed", (unsigned long long)job->key_gop);
                 it.bwd = newer;
+                it.bwd_tref = tr_newer;
                 if (older >= 0 || !job->open_gop) {
                     it.fwd = older >= 0 ? older : newer;
+                    it.fwd_tref = older >= 0 ? tr_older : tr_newer;
                     lv = std::max(lv_newer, lv_older) + 1;
                 } else {
                     it.fwd = j ? prev_last : carry;
+                    it.fwd_tref = tr_prev_last;
+                    it.fwd_before = true;
                     if (it.fwd < 0) return fail(LEON_ERR_INVALID, "GOP %llu is open and the last anchor of the GOP before it is not at hand", (unsigned long long)job->key_gop);
                     if (!j) *uses_carry = true;
                     lv = std::max(lv_newer, j ? lv_prev_last : -1) + 1;
@@ -995,8 +1012,8 @@ int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::ve
                 if (p->unfused) it.out = (int)(per_lane * j) + 3 + n_b++ % p->max_pics;
             }
             if (m.type != LEON_PIC_B) {
-                older = newer; lv_older = lv_newer;
-                newer = it.out; lv_newer = lv;
+                older = newer; lv_older = lv_newer; tr_older = tr_newer;
+                newer = it.out; lv_newer = lv; tr_newer = m.tref;
                 n_anchor++;
             }
             if ((size_t)lv >= levels.size()) levels.resize((size_t)lv + 1);
@@ -1009,9 +1026,10 @@ int plan_levels(const leon_pipeline* p, const PipeWindow* w, std::vector<std::ve
             if (seen[(size_t)m.tref]) return fail(LEON_ERR_INVALID, "GOP %llu: two pictures with temporal reference %d", (unsigned long long)job->key_gop, m.tref);
             seen[(size_t)m.tref] = 1;
         }
-        prev_last = newer; lv_prev_last = lv_newer;
+        prev_last = newer; lv_prev_last = lv_newer; tr_prev_last = tr_newer;
     }
     *last_anchor = prev_last;
+    *last_anchor_tref = tr_prev_last;
     return LEON_OK;
 }
 
@@ -1112,11 +1130,20 @@ int launch_level(leon_pipeline* p, const PipeWindow* w, const std::vector<LevelP
 }
 
 // the window's frames in display order, GOP-major
-void list_frames(leon_pipeline* p, PipeWindow* w)
+void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<LevelPic>>& levels)
 {
     w->frames.clear();
     w->tensors.clear();
     w->frame_ids.clear();
+    w->motion.clear();
+    w->motion_descs.clear();
+    // output MOTION: what plan_levels gave each picture's launch to predict from, by lane and display index
+    std::vector<const LevelPic*> planned;
+    if (p->d_motion) {
+        planned.assign(w->jobs.size() * (size_t)p->max_pics, nullptr);
+        for (const auto& lvl : levels)
+            for (const LevelPic& it : lvl) planned[it.lane * (size_t)p->max_pics + (size_t)it.pic->tref] = &it;
+    }
     for (size_t j = 0; j < w->jobs.size(); j++) {
         const GopJob* job = w->jobs[j].get();
         // by temporal reference: a GOP cut short by the encoder may skip display positions
@@ -1140,6 +1167,26 @@ void list_frames(leon_pipeline* p, PipeWindow* w)
                 f.cb = a.planes + p->planes_geom.cb_off;
                 f.cr = a.planes + p->planes_geom.cr_off;
                 f.a = p->vinfo.has_alpha == 1 ? a.planes + p->planes_geom.a_off : nullptr;
+            }
+            if (p->d_motion) {
+                const PipePic& m = *by_disp[k];
+                const LevelPic* it = planned[j * (size_t)p->max_pics + k];
+                const char* base = job->arena->dev;
+                auto ptr = [&](size_t off) -> const void* { return off == kNone ? nullptr : (const void*)(base + off); };
+                leon_pipeline_motion_frame mf{};
+                mf.record = p->d_motion + a.index * p->motion_lay.record_pitch;
+                mf.fwd_gop = it && it->fwd_before ? job->key_gop - 1 : job->key_gop;
+                mf.fwd_display = it ? it->fwd_tref : -1;
+                mf.bwd_display = it ? it->bwd_tref : -1;
+                w->motion.push_back(mf);
+                leon::MotionDesc d{};
+                d.type = m.type;
+                d.frame = (uint32_t)a.index;
+                d.repadd = (const uint8_t*)ptr(m.type != LEON_PIC_I ? m.repadd : kNone);
+                d.mv_fwd = (const uint32_t*)ptr(m.type != LEON_PIC_I ? m.mv_fwd : kNone);
+                d.mb_dir = (const uint8_t*)ptr(m.type == LEON_PIC_B ? m.mb_dir : kNone);
+                d.mv_bwd = (const uint32_t*)ptr(m.type == LEON_PIC_B ? m.mv_bwd : kNone);
+                w->motion_descs.push_back(d);
             }
             w->frames.push_back(f);
         }
@@ -1235,6 +1282,73 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
                                 (const uint32_t*)p->d_tensor_table, (const leon::Tables*)p->dec->d_tables, G);
     }
     HIP_TRY(hipGetLastError());
+    return LEON_OK;
+}
+
+// output MOTION: the window's frames -> their motion records, one launch on the decoder's stream behind the last level and in front of
+// the window's event (at most 65535 frames per launch: blockIdx.y), while the maps are still in the GOPs' arenas.  The descriptors are
+// staged in the ring entry's part of the mirror and go up with one copy.
+static_assert(sizeof(leon::MotionDesc) == 48, "a descriptor is 12 dwords");
+static_assert(sizeof(leon_pipeline_motion_frame) == 32 && sizeof(struct leon_pipeline_motion_layout) == 64, "include/leon_pipeline.h states the sizes");
+int launch_motion(leon_pipeline* p, const PipeWindow* w)
+{
+    const size_t n = w->motion_descs.size();
+    if (!p->d_motion || !n) return LEON_OK;
+    const size_t entry = (size_t)p->W * p->max_pics;
+    leon::MotionDesc* h = p->motion_descs.host() + (size_t)w->ring * entry;      // the ring entry is this window's: its previous launch has finished
+    leon::MotionDesc* dv = p->motion_descs.dev() + (size_t)w->ring * entry;
+    for (size_t i = 0; i < n; i++) {
+        const leon::MotionDesc& d = w->motion_descs[i];
+        if ((d.type != LEON_PIC_I && (!d.repadd || !d.mv_fwd)) || (d.type == LEON_PIC_B && (!d.mb_dir || !d.mv_bwd)))
+            return fail(LEON_ERR_INVALID, "motion: frame %zu of window %lld (type %d) lacks a map", i, (long long)w->id, d.type);
+        h[i] = d;
+    }
+    HIP_TRY(hipMemcpyAsync(dv, h, n * sizeof(leon::MotionDesc), hipMemcpyHostToDevice, p->dec->stream));
+    for (size_t at = 0; at < n; at += 65535) {
+        const dim3 grid(1, (unsigned)std::min<size_t>(65535, n - at)), block(leon::kRgbaBlock);
+        hipLaunchKernelGGL(leon::k_motion, grid, block, 0, p->dec->stream, (const leon::MotionDesc*)(dv + at), (uint8_t*)p->d_motion, p->motion_lay);
+    }
+    HIP_TRY(hipGetLastError());
+    return LEON_OK;
+}
+
+// the definition on the CPU: the same per-macroblock text (leon_motion.h), the specified bytes of one record
+int motion_record_host(int32_t type, int32_t mbw, int32_t mbh, const uint8_t* repadd, const uint8_t* mb_dir, const int16_t* mv_fwd, const int16_t* mv_bwd,
+                       void* record)
+{
+    if (!record) return fail(LEON_ERR_INVALID, "null argument");
+    if (type != LEON_PIC_I && type != LEON_PIC_P && type != LEON_PIC_B) return fail(LEON_ERR_INVALID, "motion record: picture type %d", type);
+    if (mbw < 1 || mbw > leon::kMotionMaxMb || mbh < 1 || mbh > leon::kMotionMaxMb)
+        return fail(LEON_ERR_INVALID, "motion record: %d x %d macroblocks (1 .. %d each)", mbw, mbh, leon::kMotionMaxMb);
+    if ((type != LEON_PIC_I && (!repadd || !mv_fwd)) || (type == LEON_PIC_B && (!mb_dir || !mv_bwd)))
+        return fail(LEON_ERR_INVALID, "motion record: a picture of type %d without one of its maps", type);
+    const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+    uint8_t* rec = static_cast<uint8_t*>(record);
+    uint32_t s[8] = {};
+    for (uint32_t k = 0; k < L.mbs; k++) {
+        uint32_t f = 0, b = 0, of, ob;
+        if (type != LEON_PIC_I) memcpy(&f, mv_fwd + 2 * (size_t)k, 4);
+        if (type == LEON_PIC_B) memcpy(&b, mv_bwd + 2 * (size_t)k, 4);
+        const uint32_t info = leon::motion_mb(type, type != LEON_PIC_I ? repadd[k] : 0u, type == LEON_PIC_B ? mb_dir[k] : 0u, f, b, &of, &ob);
+        leon::motion_count(info, of, ob, s);
+        memcpy(rec + 8 * (size_t)k, &of, 4);
+        memcpy(rec + 8 * (size_t)k + 4, &ob, 4);
+        rec[L.info_offset + k] = (uint8_t)info;
+    }
+    memcpy(rec + L.summary_offset, s, 32);
+    return LEON_OK;
+}
+
+int motion_layout_host(int32_t mbw, int32_t mbh, struct leon_pipeline_motion_layout* out)
+{
+    if (!out) return fail(LEON_ERR_INVALID, "null argument");
+    if (mbw < 1 || mbw > leon::kMotionMaxMb || mbh < 1 || mbh > leon::kMotionMaxMb)
+        return fail(LEON_ERR_INVALID, "motion layout: %d x %d macroblocks (1 .. %d each)", mbw, mbh, leon::kMotionMaxMb);
+    const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+    memset(out, 0, sizeof(*out));
+    out->mb_width = mbw; out->mb_height = mbh; out->mbs = (int32_t)L.mbs;
+    out->info_offset = L.info_offset; out->summary_offset = L.summary_offset;
+    out->record_bytes = L.record_bytes; out->record_pitch = L.record_pitch;
     return LEON_OK;
 }
 
@@ -1853,8 +1967,9 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
     // the window before's last anchor, if this window follows it directly in one run
     const bool follows = p->last_anchor >= 0 && p->last_run == w->run->id && !w->jobs.empty() && p->last_gop + 1 == w->jobs[0]->gop;
     bool uses_carry = false;
-    int last_anchor = -1;
-    int rc = plan_levels(p, w, levels, follows ? p->carry_slot : -1, &uses_carry, &last_anchor);
+    int last_anchor = -1, last_anchor_tref = -1;
+    if (!follows) p->last_anchor_tref = -1;
+    int rc = plan_levels(p, w, levels, follows ? p->carry_slot : -1, &uses_carry, &last_anchor, &last_anchor_tref);
     if (rc == LEON_OK) rc = upload_and_chain(p, w, serial, poison);
     if (rc == LEON_OK) rc = register_qsets(p, w, qset);
     if (rc != LEON_OK) return rc;
@@ -1883,8 +1998,10 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
     p->last_run = w->run->id;
     p->last_gop = w->jobs.empty() ? 0 : w->jobs.back()->gop;
     p->last_anchor = last_anchor;
-    list_frames(p, w);
+    p->last_anchor_tref = last_anchor_tref;
+    list_frames(p, w, levels);
     if ((rc = launch_tensors(p, w)) != LEON_OK) return rc;
+    if ((rc = launch_motion(p, w)) != LEON_OK) return rc;
     if (serial) HIP_TRY(hipStreamSynchronize(p->dec->stream));
     HIP_TRY(hipEventRecord(w->done, p->dec->stream));
     return LEON_OK;
@@ -2095,7 +2212,10 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
     // writes its planes, and one leon_convert_rgba per picture (the generic k_rgba_twin) fills the window's frames.
     // The GL flavour (the reference's live display arithmetic, fp32) exists as a launch of its own only: the same road.
     if (cfg->display_flavour != LEON_RGB_CPU_TWIN && cfg->display_flavour != LEON_RGB_GL) return fail(LEON_ERR_INVALID, "display_flavour %d", cfg->display_flavour);
-    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR)) return fail(LEON_ERR_INVALID, "output %d", cfg->output);
+    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR | LEON_PIPELINE_OUTPUT_MOTION))
+        return fail(LEON_ERR_INVALID, "output %d", cfg->output);
+    if (cfg->output == LEON_PIPELINE_OUTPUT_MOTION)
+        return fail(LEON_ERR_INVALID, "output %d: LEON_PIPELINE_OUTPUT_MOTION needs RGBA, YCBCR or TENSOR beside it (a pipeline that only parses is not built)", cfg->output);
     if (cfg->output & LEON_PIPELINE_OUTPUT_TENSOR) {
         // the tensor is defined through the CPU twin's RGBA, whose index drifts over an odd width (k_rgba_twin): refused, as yuva is
         if (p->vinfo.frame_width & 1) return fail(LEON_ERR_INVALID, "the tensor output needs an even frame_width (it is %d)", p->vinfo.frame_width);
@@ -2137,6 +2257,11 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
     if (p->unfused && p->vinfo.has_alpha == 1)
         return fail(LEON_ERR_INVALID, "a yuva stream needs frame_width %% 8 == 0 (it is %d) and the CPU-twin display flavour in the pipeline", p->vinfo.frame_width);
     p->maps = map_layout((size_t)p->vinfo.mb_width * p->vinfo.mb_height, (size_t)p->vinfo.n_groups);
+    if (p->output & LEON_PIPELINE_OUTPUT_MOTION) {
+        if (p->vinfo.mb_width < 1 || p->vinfo.mb_width > leon::kMotionMaxMb || p->vinfo.mb_height < 1 || p->vinfo.mb_height > leon::kMotionMaxMb)
+            return fail(LEON_ERR_INVALID, "motion output: %d x %d macroblocks (1 .. %d each)", p->vinfo.mb_width, p->vinfo.mb_height, leon::kMotionMaxMb);
+        p->motion_lay = leon::motion_layout((uint32_t)p->vinfo.mb_width, (uint32_t)p->vinfo.mb_height);
+    }
     // the GPU parser's geometry; it writes a picture's maps at the offsets of the layout the arenas give them
     p->vgeom.mbw = p->vinfo.mb_width; p->vgeom.mbh = p->vinfo.mb_height;
     p->vgeom.gy = p->vinfo.groups_y; p->vgeom.gc = p->vinfo.groups_c;
@@ -2249,6 +2374,10 @@ int allocate_pipeline(leon_pipeline* p)
         }
     }
     if ((p->output & LEON_PIPELINE_OUTPUT_RGBA) && (rc = alloc_ring(p, &p->d_rgba, p->frame_bytes, "RGBA")) != LEON_OK) return rc;
+    if (p->output & LEON_PIPELINE_OUTPUT_MOTION) {
+        if ((rc = alloc_ring(p, &p->d_motion, p->motion_lay.record_pitch, "motion")) != LEON_OK) return rc;
+        if (!p->motion_descs.alloc((size_t)p->R * p->W * p->max_pics)) return hip_fail(LEON_ERR_NOMEM, "motion descriptor ring");
+    }
     if (p->gpu_parser) {
         std::vector<leon_vlc_gpu_tables> src(1);
         std::vector<leon::VlcTables> t(1);
@@ -2544,6 +2673,57 @@ int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, v
     if (!src) return fail(LEON_ERR_INVALID, "window %lld has no frame %d", (long long)window, index);
     HIP_TRY(hipSetDevice(p->cfg.device_id));
     HIP_TRY(hipMemcpy(host, src, p->tensor_bytes, hipMemcpyDeviceToHost));
+    return LEON_OK;
+}
+
+int leon_pipeline_motion_layout(int32_t mb_width, int32_t mb_height, struct leon_pipeline_motion_layout* out)
+{
+    return motion_layout_host(mb_width, mb_height, out);
+}
+
+int leon_pipeline_motion_record(int32_t type, int32_t mb_width, int32_t mb_height, const uint8_t* repadd, const uint8_t* mb_dir,
+                                const int16_t* mv_fwd, const int16_t* mv_bwd, void* record)
+{
+    return motion_record_host(type, mb_width, mb_height, repadd, mb_dir, mv_fwd, mv_bwd, record);
+}
+
+int leon_pipeline_get_motion_layout(leon_pipeline* p, struct leon_pipeline_motion_layout* out)
+{
+    if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    if (!p->d_motion) return fail(LEON_ERR_INVALID, "the pipeline has no motion output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_MOTION)");
+    return motion_layout_host(p->vinfo.mb_width, p->vinfo.mb_height, out);
+}
+
+int leon_pipeline_window_motion(leon_pipeline* p, int64_t window, leon_pipeline_motion_frame* out, int32_t n)
+{
+    if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    if (!p->d_motion) return fail(LEON_ERR_INVALID, "the pipeline has no motion output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_MOTION)");
+    size_t has = 0;
+    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        has = w.motion.size();
+        if (n >= 0 && (size_t)n == has)
+            for (size_t i = 0; i < has; i++) out[i] = w.motion[i];
+    });
+    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (n < 0 || (size_t)n != has) return fail(LEON_ERR_INVALID, "window %lld has %zu motion records, not %d", (long long)window, has, n);
+    return LEON_OK;
+}
+
+int leon_pipeline_read_motion(leon_pipeline* p, int64_t window, int32_t index, int16_t* mv, uint8_t* info, uint32_t* summary)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null argument");
+    if (!p->d_motion) return fail(LEON_ERR_INVALID, "the pipeline has no motion output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_MOTION)");
+    const uint8_t* src = nullptr;
+    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        if (index >= 0 && (size_t)index < w.motion.size()) src = static_cast<const uint8_t*>(w.motion[(size_t)index].record);
+    });
+    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (!src) return fail(LEON_ERR_INVALID, "window %lld has no frame %d", (long long)window, index);
+    const leon::MotionLayout& L = p->motion_lay;
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    if (mv) HIP_TRY(hipMemcpy(mv, src, (size_t)L.mbs * 8, hipMemcpyDeviceToHost));
+    if (info) HIP_TRY(hipMemcpy(info, src + L.info_offset, L.mbs, hipMemcpyDeviceToHost));
+    if (summary) HIP_TRY(hipMemcpy(summary, src + L.summary_offset, 32, hipMemcpyDeviceToHost));
     return LEON_OK;
 }
 

@@ -43,6 +43,11 @@
  *                                  image rectangle tensorImageX, tensorImageY, tensorImageWidth, tensorImageHeight.
  *                                  opts.tensorLetterbox [h, w]: tensorSize, tensorCanvas and tensorOrigin derived from the crop box or the
  *                                  frame with the aspect ratio kept (LeonPipeline.letterbox = leon_pipeline_letterbox)
+ *   p.readMotion(window, index) -> {mv: Int16Array [mbs][4] (fwd_h, fwd_v, bwd_h, bwd_v in half-pel luma units), info: Uint8Array [mbs] (bits: 1
+ *                                  forward, 2 backward, 4 intra), summary: Uint32Array [8], fwdGop, fwdDisplay, bwdDisplay (the pictures the
+ *                                  vectors point into, -1: none), mbWidth, mbHeight}: the frame's motion record, macroblocks in raster order of
+ *                                  the coded picture, with opts.motion true beside any output (include/leon_pipeline.h
+ *                                  LEON_PIPELINE_OUTPUT_MOTION); read only, until the window is released
  *   p.readRegions(window, regions, {size: [h, w], filter}) -> Buffer of n * 3 * h * w elements, packed: regions = [[frameIndex, x, y,
  *                                  width, height], ...], boxes of the window's FULL-RESOLUTION frames (a detector's boxes) each resampled to
  *                                  h x w with the pipeline's element type, table and layout (leon_pipeline_read_regions) -- any tensor
@@ -77,6 +82,7 @@ class LeonPipeline extends EventEmitter {
       if (!(output in outputs)) throw new TypeError("output: 'rgba', 'ycbcr', 'both', 'tensor', 'rgba+tensor', 'ycbcr+tensor' or 'all'");
       output = outputs[output];
     }
+    if (opts.motion) output = (output || outputs.rgba) | 32;          // LEON_PIPELINE_OUTPUT_MOTION beside whatever output resolves to
     let tensorDtype = opts.tensorDtype === undefined ? 0 : opts.tensorDtype;
     if (typeof tensorDtype === 'string') {
       if (!(tensorDtype in dtypes)) throw new TypeError("tensorDtype: 'float16', 'bfloat16', 'float32' or 'uint8'");
@@ -147,6 +153,7 @@ class LeonPipeline extends EventEmitter {
   readFrame(window, index) { return this._p.readFrame(window, index); }
   readPlanes(window, index) { return this._p.readPlanes(window, index); }
   readTensor(window, index) { return this._p.readTensor(window, index); }
+  readMotion(window, index) { return this._p.readMotion(window, index); }
   // regions: [[frameIndex, x, y, width, height], ...] of a delivered window's full-resolution frames, resampled to opts.size [h, w]
   readRegions(window, regions, opts) {
     opts = opts || {};

@@ -45,6 +45,8 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_resample_regions_fit", "leon_pipeline_read_regions_fit", "leon_pipeline_resample_regions_device_fit",
     "leon_pipeline_warp_regions_check", "leon_pipeline_warp_region_status", "leon_pipeline_warp_from_matrix", "leon_pipeline_warp_from_rotated_box",
     "leon_pipeline_warp_regions", "leon_pipeline_read_warp_regions", "leon_pipeline_warp_regions_device",
+    "leon_pipeline_motion_layout", "leon_pipeline_motion_record", "leon_pipeline_get_motion_layout", "leon_pipeline_window_motion",
+    "leon_pipeline_read_motion",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -54,6 +56,9 @@ PIPELINE_OUTPUT_TENSOR = 16
 PIPELINE_TENSOR_OUTPUTS = {"tensor": PIPELINE_OUTPUT_TENSOR, "rgba+tensor": PIPELINE_OUTPUT_RGBA | PIPELINE_OUTPUT_TENSOR,
                            "ycbcr+tensor": PIPELINE_OUTPUT_YCBCR | PIPELINE_OUTPUT_TENSOR,
                            "all": PIPELINE_OUTPUT_RGBA | PIPELINE_OUTPUT_YCBCR | PIPELINE_OUTPUT_TENSOR}
+# the motion output (LEON_PIPELINE_OUTPUT_MOTION): Pipeline(motion=True) ORs it into whatever output= resolves to
+PIPELINE_OUTPUT_MOTION = 32
+MOTION_FWD, MOTION_BWD, MOTION_INTRA = 1, 2, 4      # the bits of a motion record's info bytes
 TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 1, 2, 3       # LEON_TENSOR_*
 TENSOR_DTYPES = {"float16": TENSOR_F16, "bfloat16": TENSOR_BF16, "float32": TENSOR_F32}
 TENSOR_U8 = 8                                       # LEON_TENSOR_U8 ("uint8"): the element is the 8-bit colour value
@@ -365,6 +370,15 @@ class PipelineTensorShape(C.Structure):
                 ("width", C.c_int32), ("stride_c", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64)]
 
 
+class PipelineMotionLayout(C.Structure):
+    _fields_ = [("mb_width", C.c_int32), ("mb_height", C.c_int32), ("mbs", C.c_int32), ("reserved0", C.c_int32), ("info_offset", C.c_uint64),
+                ("summary_offset", C.c_uint64), ("record_bytes", C.c_uint64), ("record_pitch", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+class PipelineMotionFrame(C.Structure):
+    _fields_ = [("record", C.c_void_p), ("fwd_gop", C.c_uint64), ("fwd_display", C.c_int32), ("bwd_display", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class PipelineFrame(C.Structure):
     _fields_ = [("gop", C.c_uint64), ("display_index", C.c_int32), ("type", C.c_int32), ("ts_ms", C.c_double),
                 ("rgba", C.c_void_p), ("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("a", C.c_void_p)]
@@ -501,6 +515,12 @@ def load():
         lib.leon_pipeline_warp_regions.argtypes = [C.c_void_p, C.c_int64, P(PipelineWarpRegion), C.c_int32, P(PipelineWarpConfig), C.c_void_p, C.c_uint64]
         lib.leon_pipeline_read_warp_regions.argtypes = [C.c_void_p, C.c_int64, P(PipelineWarpRegion), C.c_int32, P(PipelineWarpConfig), C.c_void_p]
         lib.leon_pipeline_warp_regions_device.argtypes = [C.c_void_p, C.c_int64, P(PipelineWarpConfig), P(PipelineWarpRegionsCall)]
+    if hasattr(lib, "leon_pipeline_window_motion"):
+        lib.leon_pipeline_motion_layout.argtypes = [C.c_int32, C.c_int32, C.POINTER(PipelineMotionLayout)]
+        lib.leon_pipeline_motion_record.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_get_motion_layout.argtypes = [C.c_void_p, C.POINTER(PipelineMotionLayout)]
+        lib.leon_pipeline_window_motion.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineMotionFrame), C.c_int32]
+        lib.leon_pipeline_read_motion.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -555,6 +575,58 @@ def region_status(frame_width, frame_height, n_frames, region, size, filter="tri
     if st < 0:
         raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
     return st
+
+
+def motion_layout(mbw, mbh):
+    """leon_pipeline_motion_layout: where the parts of a motion record of mbw x mbh macroblocks lie (PipelineMotionLayout), no device"""
+    out = PipelineMotionLayout()
+    _chk(load().leon_pipeline_motion_layout(int(mbw), int(mbh), C.byref(out)))
+    return out
+
+
+def _motion_parts(buf, lay):
+    """(mv [mbh, mbw, 4] int16, info [mbh, mbw] uint8, summary [8] uint32): copies of the specified parts of a record buffer"""
+    mbs = lay.mbs
+    mv = buf[:8 * mbs].view(np.int16).reshape(lay.mb_height, lay.mb_width, 4).copy()
+    info = buf[lay.info_offset:lay.info_offset + mbs].reshape(lay.mb_height, lay.mb_width).copy()
+    summary = buf[lay.summary_offset:lay.summary_offset + 32].view(np.uint32).copy()
+    return mv, info, summary
+
+
+def motion_record(type, mbw, mbh, repadd=None, mb_dir=None, mv_fwd=None, mv_bwd=None, fill=None):
+    """leon_pipeline_motion_record: the library's CPU evaluation of a picture's motion record from its maps (as leon_vlc_ctypes.Stream
+    gives them; those the type does not have may be None) -> (mv [mbh, mbw, 4] int16, info [mbh, mbw] uint8, summary [8] uint32).
+    fill: the byte the record buffer holds beforehand -- the call then returns (mv, info, summary, buffer), the whole record_bytes
+    buffer as the library left it (its unspecified bytes still hold the fill)."""
+    lay = motion_layout(mbw, mbh)
+    buf = np.full(lay.record_bytes, 0 if fill is None else int(fill), dtype=np.uint8)
+    keep = [None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in ((repadd, np.uint8), (mb_dir, np.uint8), (mv_fwd, np.int16), (mv_bwd, np.int16))]
+    _chk(load().leon_pipeline_motion_record(int(type), int(mbw), int(mbh), *[None if a is None else a.ctypes.data for a in keep], buf.ctypes.data))
+    parts = _motion_parts(buf, lay)
+    return parts if fill is None else parts + (buf,)
+
+
+def motion_from_maps(type, mbw, mbh, repadd=None, mb_dir=None, mv_fwd=None, mv_bwd=None):
+    """The definition of a frame's motion record (include/leon_pipeline.h, LEON_PIPELINE_OUTPUT_MOTION) in numpy, written from the
+    header's text and independent of the C code: a picture's maps -> (mv [mbh, mbw, 4] int16, info [mbh, mbw] uint8, summary [8] uint32).
+    The `intra` map plays no part; an unused direction's vector reads as zero."""
+    mbs = int(mbw) * int(mbh)
+    mv = np.zeros((mbs, 4), dtype=np.int16)
+    if type == 1:
+        info = np.full(mbs, 4, dtype=np.uint8)
+    else:
+        intra = np.asarray(repadd).reshape(-1)[:mbs].astype(np.int64) >= 128
+        d = np.where(intra, 0, 1 if type == 2 else np.asarray(mb_dir).reshape(-1)[:mbs].astype(np.int64) & 3)
+        info = np.where(intra, 4, d).astype(np.uint8)
+        fwd = np.asarray(mv_fwd, dtype=np.int16).reshape(-1)[:2 * mbs].reshape(mbs, 2)
+        mv[:, 0:2] = np.where((d & 1)[:, None] != 0, fwd, 0)
+        if type == 3:
+            bwd = np.asarray(mv_bwd, dtype=np.int16).reshape(-1)[:2 * mbs].reshape(mbs, 2)
+            mv[:, 2:4] = np.where((d & 2)[:, None] != 0, bwd, 0)
+    a = np.abs(mv.astype(np.int64))
+    summary = np.array([int(((info & 1) != 0).sum()), int(((info & 2) != 0).sum()), int(((info & 4) != 0).sum()), int(mv.any(axis=1).sum()),
+                        int(a[:, 0].sum()), int(a[:, 1].sum()), int(a[:, 2].sum()), int(a[:, 3].sum())], dtype=np.uint32)
+    return mv.reshape(int(mbh), int(mbw), 4), info.reshape(int(mbh), int(mbw)), summary
 
 
 def warp_rgb(rgb, m, size, pad=(0, 0, 0)):
@@ -931,8 +1003,8 @@ class _Frames:
     """the frames of a delivered window as a read-only sequence of dicts, made when asked for (a 128-GOP window has 1536 of
     them; a callback that looks at a dozen should not pay for the rest on the pipeline's notify thread)"""
 
-    def __init__(self, frames, n, pipe, window=-1, tensors=None):
-        self._f, self._n, self._pipe, self._window, self._tensors = frames, n, pipe, window, tensors
+    def __init__(self, frames, n, pipe, window=-1, tensors=None, motion=None):
+        self._f, self._n, self._pipe, self._window, self._tensors, self._motion = frames, n, pipe, window, tensors, motion
 
     def __len__(self):
         return self._n
@@ -945,7 +1017,9 @@ class _Frames:
         if not 0 <= i < self._n:
             raise IndexError(i)
         f = self._f[i]
-        return {"gop": int(f.gop), "display_index": f.display_index, "type": f.type, "ts_ms": f.ts_ms, "rgba": f.rgba,
+        m = self._motion[i] if self._motion is not None else None
+        return {"motion": None if m is None else {"record": m.record, "fwd_gop": int(m.fwd_gop), "fwd_display": m.fwd_display, "bwd_display": m.bwd_display},
+                "gop": int(f.gop), "display_index": f.display_index, "type": f.type, "ts_ms": f.ts_ms, "rgba": f.rgba,
                 "y": f.y, "cb": f.cb, "cr": f.cr, "a": f.a, "tensor": self._tensors[i] if self._tensors is not None else None,
                 "_i": i, "_window": self._window, "_frames": self._f, "_pipe": self._pipe}
 
@@ -985,12 +1059,16 @@ class Pipeline:
     device batch of the pipeline's element type and table, element = table[c][resize_rgb(rgb of that frame, (x, y, w, h), size, filter)];
     the pipeline's own tensor_size / crop / canvas play no part.  Until the window is released, from the callback or (for a window held
     by returning False) from any thread; read_regions(...) gives the same as a host array.  resample_regions_device(window, boxes, ...)
-    takes the boxes from a CUDA tensor and only enqueues, on torch's current stream: no host wait between a detector and its classifier."""
+    takes the boxes from a CUDA tensor and only enqueues, on torch's current stream: no host wait between a detector and its classifier.
+    motion=True (beside any output): every frame carries its motion record -- per macroblock of the coded picture the forward and backward
+    vectors and an info byte (MOTION_FWD / MOTION_BWD / MOTION_INTRA), and a summary of eight words: motion_from_maps states it.
+    frame["motion"] = {"record": device address, "fwd_gop", "fwd_display", "bwd_display": which pictures the vectors point into (-1: none)};
+    read_motion(window, i) copies frame i's record to the host, motion_view(window, i) wraps it in place; motion_layout has the offsets."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
                  output="rgba", tensor_dtype="float16", tensor_scale=None, tensor_bias=None, tensor_size=None, tensor_crop=None, tensor_filter=RESIZE_TRIANGLE,
-                 tensor_layout="chw", tensor_canvas=None, tensor_origin=None, tensor_pad_value=None, tensor_letterbox=None):
+                 tensor_layout="chw", tensor_canvas=None, tensor_origin=None, tensor_pad_value=None, tensor_letterbox=None, motion=False):
         self.lib = load()
         if tensor_letterbox is not None:
             if tensor_size is not None or tensor_canvas is not None or tensor_origin is not None:
@@ -1007,6 +1085,8 @@ class Pipeline:
         self.device_id = device_id
         # a name of PIPELINE_OUTPUTS, or the raw bit set (anything the library does not know is refused by create)
         out_bits = (PIPELINE_OUTPUTS.get(output) or PIPELINE_TENSOR_OUTPUTS[output]) if isinstance(output, str) else int(output)
+        if motion:
+            out_bits = (out_bits or PIPELINE_OUTPUT_RGBA) | PIPELINE_OUTPUT_MOTION
         tcfg = None
         if out_bits > 0 and out_bits & PIPELINE_OUTPUT_TENSOR:
             tcfg = PipelineTensorConfig(_tensor_dtype_code(tensor_dtype), (C.c_float * 3)(*([0, 0, 0] if tensor_scale is None else tensor_scale)),
@@ -1039,7 +1119,10 @@ class Pipeline:
         import threading
         ready = threading.Event()          # set once self.h exists: decoding starts inside leon_pipeline_create
 
+        self._window_n = {}        # frames of the windows that are out for delivery (motion_view asks window_motion for exactly that many)
+
         def _release(window):
+            self._window_n.pop(window, None)
             rc = self.lib.leon_pipeline_release_window(self.h, window)
             if rc != OK and self.error is None:
                 self.error = LeonError(rc, "leon_pipeline_release_window(%d): %s" % (window, self.lib.leon_last_error().decode()))
@@ -1057,6 +1140,7 @@ class Pipeline:
                     return
                 self.windows += 1
                 self.frames += n
+                self._window_n[window] = n
                 keep = None
                 if self._on_window is not None:
                     # `_pipe`: a callback may read frames through the dicts alone (read_frame(f) below), without the
@@ -1066,7 +1150,12 @@ class Pipeline:
                         tensors = (C.c_void_p * n)()
                         if self.lib.leon_pipeline_window_tensors(self.h, window, tensors, n) != OK:
                             raise LeonError(ERR_INVALID, self.lib.leon_last_error().decode())
-                    fl = _Frames(frames, n, self, window, tensors)
+                    motion = None
+                    if self.info.output & PIPELINE_OUTPUT_MOTION and n:          # the window's motion records and references, one call
+                        motion = (PipelineMotionFrame * n)()
+                        if self.lib.leon_pipeline_window_motion(self.h, window, motion, n) != OK:
+                            raise LeonError(ERR_INVALID, self.lib.leon_last_error().decode())
+                    fl = _Frames(frames, n, self, window, tensors, motion)
                     keep = self._on_window(window, fl)
                 if keep is not False:
                     _release(window)
@@ -1119,8 +1208,57 @@ class Pipeline:
             canvas = PipelineTensorCanvas()
             rc = self.lib.leon_pipeline_get_tensor_canvas(self.h, C.byref(canvas))
             self.tensor_canvas_geometry = canvas
+        self.motion_layout = None
+        if rc == OK and info.output & PIPELINE_OUTPUT_MOTION:
+            lay = PipelineMotionLayout()
+            rc = self.lib.leon_pipeline_get_motion_layout(self.h, C.byref(lay))
+            self.motion_layout = lay
         ready.set()
         _chk(rc)
+
+    def _need_motion(self):
+        if self.motion_layout is None:
+            raise LeonError(ERR_INVALID, "the pipeline has no motion output (Pipeline motion=True)")
+
+    def window_motion(self, window, n):
+        """leon_pipeline_window_motion: the n motion frames (PipelineMotionFrame array) of a delivered, not yet released window"""
+        out = (PipelineMotionFrame * max(1, int(n)))()
+        _chk(self.lib.leon_pipeline_window_motion(self.h, int(window), out, int(n)))
+        return out
+
+    def read_motion(self, window, index):
+        """the motion record of frame `index` of a delivered, not yet released window as host arrays:
+        (mv [mbh, mbw, 4] int16, info [mbh, mbw] uint8, summary [8] uint32)"""
+        lay = self.motion_layout
+        mbw, mbh = (lay.mb_width, lay.mb_height) if lay is not None else (1, 1)      # (without the output the library refuses below)
+        mv = np.empty((mbh, mbw, 4), dtype=np.int16)
+        info = np.empty((mbh, mbw), dtype=np.uint8)
+        summary = np.empty(8, dtype=np.uint32)
+        _chk(self.lib.leon_pipeline_read_motion(self.h, int(window), int(index), mv.ctypes.data, info.ctypes.data, summary.ctypes.data))
+        return mv, info, summary
+
+    def motion_view(self, window, index, device_id=None):
+        """the same three parts where they lie, as torch views of device memory (int16 [mbh, mbw, 4], uint8 [mbh, mbw], int32 [8]: torch
+        has no uint32 arithmetic, the words are below 2^31), without copying: valid until the window is released"""
+        import torch
+        self._need_motion()
+        lay = self.motion_layout
+        n = self._window_n.get(int(window))
+        if n is None:
+            raise LeonError(ERR_INVALID, "window %d is not out for delivery" % int(window))
+        frames = self.window_motion(window, n)
+        ptr = frames[int(index)].record
+        dev = "cuda:%d" % (self.device_id if device_id is None else device_id)
+
+        def view(at, shape, typestr, strides):
+            class _View:
+                pass
+            v = _View()
+            v.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr) + int(at), False), "strides": strides, "version": 2}
+            return torch.as_tensor(v, device=dev)
+        return (view(0, (lay.mb_height, lay.mb_width, 4), "<i2", (lay.mb_width * 8, 8, 2)),
+                view(lay.info_offset, (lay.mb_height, lay.mb_width), "|u1", (lay.mb_width, 1)),
+                view(lay.summary_offset, (8,), "<i4", (4,)))
 
     def read_frame(self, frame):
         out = np.empty((self.info.frame_height, self.info.frame_width, 4), dtype=np.uint8)
@@ -1399,6 +1537,7 @@ class Pipeline:
         _chk(self.lib.leon_pipeline_feed(self.h, int(valid_bytes)))
 
     def release_window(self, window):
+        self._window_n.pop(window, None)
         _chk(self.lib.leon_pipeline_release_window(self.h, window))
 
     def seek(self, seconds, exact=False, mode=None):

@@ -594,6 +594,60 @@ napi_value PipeReadTensor(napi_env env, napi_callback_info info)
     return rc == LEON_OK ? ta : throw_leon(env, rc);
 }
 
+// p.readMotion(window, i) -> {mv: Int16Array [mbs][4], info: Uint8Array [mbs], summary: Uint32Array [8], fwdGop, fwdDisplay, bwdDisplay,
+// mbWidth, mbHeight}: one frame's motion record (opts.motion; include/leon_pipeline.h LEON_PIPELINE_OUTPUT_MOTION), copied to the host
+napi_value PipeReadMotion(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    int32_t i = -1;
+    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "readMotion(window, index)");
+        return nullptr;
+    }
+    struct leon_pipeline_motion_layout lay;
+    int rc = leon_pipeline_get_motion_layout(h->p, &lay);
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    size_t n = 0;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        auto it = h->out.find(w);
+        if (it != h->out.end()) n = it->second.size();
+    }
+    if (i < 0 || (size_t)i >= n) {
+        napi_throw_error(env, nullptr, "readMotion: no such frame in a delivered window");
+        return nullptr;
+    }
+    std::vector<leon_pipeline_motion_frame> refs(n);
+    if ((rc = leon_pipeline_window_motion(h->p, w, refs.data(), (int32_t)n)) != LEON_OK) return throw_leon(env, rc);
+    napi_value o, ab[3], ta[3];
+    void* data[3] = {nullptr, nullptr, nullptr};
+    const size_t mbs = (size_t)lay.mbs;
+    NAPI_OK(napi_create_object(env, &o));
+    NAPI_OK(napi_create_arraybuffer(env, mbs * 8, &data[0], &ab[0]));
+    NAPI_OK(napi_create_typedarray(env, napi_int16_array, mbs * 4, ab[0], 0, &ta[0]));
+    NAPI_OK(napi_create_arraybuffer(env, mbs, &data[1], &ab[1]));
+    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, mbs, ab[1], 0, &ta[1]));
+    NAPI_OK(napi_create_arraybuffer(env, 32, &data[2], &ab[2]));
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, 8, ab[2], 0, &ta[2]));
+    if ((rc = leon_pipeline_read_motion(h->p, w, i, (int16_t*)data[0], (uint8_t*)data[1], (uint32_t*)data[2])) != LEON_OK) return throw_leon(env, rc);
+    NAPI_OK(napi_set_named_property(env, o, "mv", ta[0]));
+    NAPI_OK(napi_set_named_property(env, o, "info", ta[1]));
+    NAPI_OK(napi_set_named_property(env, o, "summary", ta[2]));
+    const leon_pipeline_motion_frame& m = refs[(size_t)i];
+    const struct { const char* name; double v; } nums[] = {{"fwdGop", (double)m.fwd_gop}, {"fwdDisplay", (double)m.fwd_display}, {"bwdDisplay", (double)m.bwd_display},
+                                                           {"mbWidth", (double)lay.mb_width}, {"mbHeight", (double)lay.mb_height}};
+    for (const auto& kv : nums) {
+        napi_value v;
+        NAPI_OK(napi_create_double(env, kv.v, &v));
+        NAPI_OK(napi_set_named_property(env, o, kv.name, v));
+    }
+    return o;
+}
+
 // p.readRegions(window, boxes, outHeight, outWidth, filter) -> Buffer of n * region bytes (3 * outHeight * outWidth elements of the
 // pipeline's element type and layout each, packed): leon_pipeline_read_regions.  boxes: an Int32Array of n x [frame index, x, y, width, height].
 // Five numbers more -- fit mode, anchor, pad r, g, b (leon_pipeline_regions_fit) -- make it leon_pipeline_read_regions_fit.
@@ -947,7 +1001,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));
