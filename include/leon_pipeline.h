@@ -684,6 +684,93 @@ int leon_pipeline_read_warp_regions(leon_pipeline* p, int64_t window, const leon
                                     const leon_pipeline_warp_config* cfg, void* host);
 int leon_pipeline_warp_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_warp_config* cfg,
                                       const leon_pipeline_warp_regions_call* call);
+/* Boxes carried along the stream's motion vectors: a detector runs on an anchor, and its boxes follow the motion records
+ * (LEON_PIPELINE_OUTPUT_MOTION) to the other pictures of the GOP, on the device, between the detector and resample_regions_device.
+ * One HOP carries a box between two delivered frames of one window that are joined by a prediction.  Integers only.
+ * Records.  The input record is 32 bytes, the layout of leon_pipeline_region with its first reserved word in use
+ * (leon_pipeline_carry_region below: frame, the box, target, two reserved words that must be 0).  The output record is a
+ * leon_pipeline_region with frame = target, the moved box and all three reserved words 0: it can be handed to resample_regions_device
+ * as it is, and, once the caller has written a new target into word 5, to the next hop.
+ * References inside a window.  For window frame i, fwd[i] is the index of the window frame whose (gop, display_index) equals
+ * (motion[i].fwd_gop, motion[i].fwd_display); -1 when fwd_display is -1 or when no delivered frame of this window is that picture (an
+ * open GOP's predecessor in an earlier window, an anchor that an EXACT seek reconstructed but did not deliver).  bwd[i] is the same
+ * with (frames[i].gop, motion[i].bwd_display).
+ * Which record votes, and in which sense.  With S = frame and T = target:
+ *     S == T                                  : the box is returned as it is, votes all 0 (status 0)
+ *     else M = T, sense = -1, D = (fwd[T] == S ? 1 : 0) | (bwd[T] == S ? 2 : 0)        if that D != 0
+ *     else M = S, sense = +1, D = (fwd[S] == T ? 1 : 0) | (bwd[S] == T ? 2 : 0)        if that D != 0
+ *     else status LEON_REGION_NO_REFERENCE
+ * D = 3 happens: a closed GOP's leading B picture names its I picture for both directions.  A vector points from a macroblock of M
+ * to where it reads in the reference: an object at p in the reference is at p - v/2 in M (sense -1: from the reference to the picture
+ * that predicts from it), an object at p in M came from p + v/2 in the reference (sense +1).
+ * Votes.  Macroblock (i, j) of M's record covers frame pixels [16i, 16i+16) x [16j, 16j+16); its weight is the pixel area it shares
+ * with the box (x, y, w, h),
+ *     a = (min(x+w, 16i+16) - max(x, 16i)) * (min(y+h, 16j+16) - max(y, 16j))          1 .. 256
+ * over i = x>>4 .. (x+w-1)>>4 and the same range for j (a box inside the frame never leaves the coded grid).  For each direction
+ * bit b of D, a macroblock with info & b adds a to A, a * mv_h(b) to SH and a * mv_v(b) to SV: a bidirectional macroblock under
+ * D = 3 votes twice.  Macroblocks with info & 4 add a to I.  All sums are int64 (2^16 macroblocks, weight 2^8, |int16| up to 2^15,
+ * two directions: 2^40).
+ * The moved box.
+ *     dh = A ? floor((sense * SH + A) / (2 * A)) : 0          half-pel -> pixels, to nearest, ties up; FLOOR division, also for negatives
+ *     dv likewise with SV
+ *     x' = clamp(x + dh, 0, frame_width - w),  y' = clamp(y + dv, 0, frame_height - h);  w, h unchanged
+ *     votes[4] = { A, I, dh, dv }                              dh, dv before the clamp; A <= 2wh and I <= wh fit int32
+ * Order of judgement, regions_check's, one text for host and device (csrc/leon_carry.h): LEON_REGION_RESERVED, LEON_REGION_FRAME
+ * (either frame or target outside the window), LEON_REGION_BOX (empty, or leaves the frame), LEON_REGION_NO_REFERENCE.  A record
+ * whose status is not 0 has not one byte of its output record or votes written.
+ * ON BOTH ROADS A RECORD'S FAULT IS A STATUS WORD, NEVER AN ERROR OF THE CALL -- the host roads of the other families refuse the
+ * whole call instead.  A pair of frames with no prediction between them is a property of the stream and the seek, not a caller's bug.
+ * One launch per call (k_carry: a 64-lane wave per record, four records per workgroup); the window's table (ring id, fwd, bwd per
+ * frame) is the scratch it needs. */
+#define LEON_REGION_NO_REFERENCE 9   /* carry regions only: no prediction joins frame and target inside the window */
+typedef struct leon_pipeline_carry_region {
+    int32_t frame;                 /* the frame the box is on (index into the window's frames[]) */
+    int32_t x, y, width, height;   /* the box, frame pixels; non-empty, inside the frame */
+    int32_t target;                /* the frame to carry it to */
+    int32_t reserved[2];           /* must be 0 */
+} leon_pipeline_carry_region;      /* 32 bytes */
+typedef struct leon_pipeline_carry_regions_call {
+    const leon_pipeline_carry_region* regions;   /* DEVICE memory, n records, 4-byte aligned */
+    int32_t  n;                            /* 1 .. 65535 */
+    int32_t  reserved0;                    /* must be 0 */
+    leon_pipeline_region* device_out;      /* DEVICE memory, n records, 4-byte aligned */
+    int32_t* device_votes;                 /* DEVICE memory, n x 4 words {A, I, dh, dv}, 4-byte aligned, may be NULL */
+    int32_t* device_status;                /* DEVICE memory, n words, may be NULL */
+    void*    stream;                       /* hipStream_t of the caller's; NULL: the pipeline's regions stream, and the call waits */
+    uint64_t reserved[2];                  /* must be 0 */
+} leon_pipeline_carry_regions_call;        /* 64 bytes */
+/* host only: the resolution rule above for the n_frames frames of a window and their motion frames (leon_pipeline_window_motion) */
+int leon_pipeline_carry_refs(const leon_pipeline_frame* frames, const leon_pipeline_motion_frame* motion, int32_t n_frames,
+                             int32_t* fwd, int32_t* bwd);
+/* host only: the definition on the CPU (the text the kernel compiles too) for one record, from motion records in host memory laid out
+ * as leon_pipeline_motion_layout(mb_width, mb_height) says: records[i] is window frame i's, NULL allowed for frames that are not M.
+ * Returns the record's status word (>= 0; out and votes, 8 and 4 words, are written exactly when it is 0; votes may be NULL), or
+ * LEON_ERR_INVALID (negative) for a null argument, a grid outside 1 .. 256, a frame larger than the grid or below 1, n_frames < 0, a
+ * NULL record where M's is needed. */
+int32_t leon_pipeline_carry_record(int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                                   const int32_t* fwd, const int32_t* bwd, const void* const* records, const leon_pipeline_carry_region* rec,
+                                   leon_pipeline_region* out, int32_t* votes);
+/* what the pipeline resolved for a delivered, not yet released window (n = its n_frames); LEON_ERR_INVALID as leon_pipeline_window_motion */
+int leon_pipeline_get_carry_refs(leon_pipeline* p, int64_t window, int32_t* fwd, int32_t* bwd, int32_t n);
+/* Records in DEVICE memory: the call ONLY ENQUEUES on the caller's stream (stream NULL: the regions stream, and the call waits), with
+ * leon_pipeline_warp_regions_device's ordering rules and its scratch event, word for word.  It needs the MOTION bit only, not TENSOR.
+ * Refused (LEON_ERR_INVALID, nothing enqueued): a pipeline without the MOTION bit, a window that is not out for delivery or was
+ * delivered with an error, a null call, `regions` or `device_out`, a pointer that is not 4-byte aligned, n outside 1 .. 65535, a
+ * non-zero reserved word of the call. */
+int leon_pipeline_carry_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_carry_regions_call* call);
+/* Records in host memory, results to host memory, synchronous: the device road between an upload and three copies.  out (n records),
+ * votes (n x 4 words, may be NULL) and status (n words, may be NULL) go up and come back whole, so a refused record's words stay as
+ * the caller had them.  The call-level refusals are the device road's. */
+int leon_pipeline_carry_regions(leon_pipeline* p, int64_t window, const leon_pipeline_carry_region* regions, int32_t n,
+                                leon_pipeline_region* out, int32_t* votes, int32_t* status);
+/* A diagnostic in the manner of leon_pipeline_resize_weights_device: k_carry on motion records the CALLER supplies (host memory,
+ * records_host[i] of window frame i, laid out as leon_pipeline_motion_layout says; NULL for frames whose record no region of the call
+ * votes with), with memory of its own on device_id's null stream, synchronous; regions, out, votes (may be NULL) and status (may be
+ * NULL) in host memory, going up and coming back whole.  Refused (LEON_ERR_INVALID): what leon_pipeline_carry_record refuses, n
+ * outside 1 .. 65535, a fwd or bwd entry outside -1 .. n_frames - 1. */
+int leon_pipeline_carry_device(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                               const int32_t* fwd, const int32_t* bwd, const void* const* records_host, const leon_pipeline_carry_region* regions,
+                               int32_t n, leon_pipeline_region* out, int32_t* votes, int32_t* status);
 /* A diagnostic: the DEVICE's evaluation of the tables of n_axes single axes, copied back, to be compared word for word with
  * leon_pipeline_resize_weights (pixels would hide a weight that is one unit off).  axes = n_axes x {in_size, crop_start, crop_size,
  * out_size}; with max_out the largest out_size of the batch, axis a's tables lie at a fixed pitch: first[a * max_out + o],

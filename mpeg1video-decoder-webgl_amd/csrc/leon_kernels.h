@@ -40,6 +40,7 @@
 #include "leon_resize_row.h"
 #include "leon_warp.h"
 #include "leon_motion.h"
+#include "leon_carry.h"
 
 
 namespace leon {
@@ -2975,6 +2976,78 @@ __global__ __launch_bounds__(kRgbaBlock) void k_motion(const MotionDesc* __restr
         sm[0] = lo;
         sm[1] = hi;
     }
+}
+
+// ---- carry: a box along the motion vectors between two delivered frames (include/leon_pipeline.h, leon_pipeline_carry_regions) -----
+// One 64-lane wave per record, four records per workgroup; the waves of a workgroup share nothing.  A wave judges its record (every lane
+// the same words), picks the motion record M that votes (leon_carry.h), and its lanes stride over the macroblocks the box covers: per
+// lane and trip 8 bytes of mv[k] and one byte of info[k], the weight from the box, 64-bit partial sums in registers.  The sums cross
+// the wave by shuffles, two 32-bit halves each; lane 0 finishes and stores.  No LDS, no atomics, no barrier; idle waves of the last
+// workgroup and waves whose record is refused leave at once, a refused record with its status word alone.
+// M's record lies at ring + frames[M].ring * record_pitch, where k_motion wrote it.  A box inside the frame lies inside the coded
+// grid (fw <= 16 * mbw, fh <= 16 * mbh: the callers see to it), so every macroblock index is below mbs.
+struct CarryCall {
+    int32_t fw, fh;                      // the frame
+    int32_t mbw;                         // macroblocks a row of the coded picture
+    int32_t n_frames, n;                 // frames of the window, records of the call
+    uint32_t info_offset, record_pitch;  // MotionLayout's
+    uint32_t reserved;
+};
+struct __attribute__((aligned(4))) CarryWords4 { int32_t w[4]; };          // 16 bytes at a 4-byte aligned address
+
+__device__ __forceinline__ int64_t wave_sum64(int64_t v)
+{
+    uint32_t lo = (uint32_t)(uint64_t)v, hi = (uint32_t)((uint64_t)v >> 32);
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t olo = (uint32_t)__shfl_xor((int)lo, m, 64), ohi = (uint32_t)__shfl_xor((int)hi, m, 64);
+        const uint64_t sum = (((uint64_t)hi << 32) | lo) + (((uint64_t)ohi << 32) | olo);
+        lo = (uint32_t)sum; hi = (uint32_t)(sum >> 32);
+    }
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__global__ __launch_bounds__(kRgbaBlock) void k_carry(const CarryRecord* __restrict__ recs, const CarryFrame* __restrict__ frames,
+                                                       const uint8_t* __restrict__ ring, int32_t* __restrict__ out, int32_t* __restrict__ votes,
+                                                       int32_t* __restrict__ status, CarryCall c)
+{
+    const uint32_t lane = threadIdx.x & 63u, i = blockIdx.x * (uint32_t)(kRgbaBlock / 64) + (threadIdx.x >> 6);
+    if (i >= (uint32_t)c.n) return;
+    const CarryRecord r = recs[i];
+    int32_t st = carry_record_status(r, c.fw, c.fh, c.n_frames), m = 0, sense = 1, d = 0;
+    if (st == kRegionOk) {
+        const CarryFrame fs = frames[r.frame], ft = frames[r.target];
+        st = carry_pick(r.frame, r.target, ft.fwd, ft.bwd, fs.fwd, fs.bwd, &m, &sense, &d);
+    }
+    if (st != kRegionOk) {
+        if (lane == 0 && status) status[i] = st;
+        return;
+    }
+    CarrySums s{0, 0, 0, 0};
+    if (d) {
+        const uint8_t* __restrict__ rec = ring + (size_t)frames[m].ring * c.record_pitch;
+        const int32_t i0 = r.x >> 4, j0 = r.y >> 4;
+        const uint32_t cols = (uint32_t)(((r.x + r.width - 1) >> 4) - i0 + 1), rows = (uint32_t)(((r.y + r.height - 1) >> 4) - j0 + 1);
+        for (uint32_t k = lane; k < cols * rows; k += 64u) {
+            const uint32_t jj = k / cols, ii = k - jj * cols;
+            const int32_t mi = i0 + (int32_t)ii, mj = j0 + (int32_t)jj;
+            const uint32_t mb = (uint32_t)mj * (uint32_t)c.mbw + (uint32_t)mi;
+            const uint2 mv = *reinterpret_cast<const uint2*>(rec + (size_t)mb * 8u);
+            const uint32_t info = rec[c.info_offset + mb];
+            carry_vote(d, info, mv.x, mv.y, carry_weight(r.x, r.y, r.width, r.height, mi, mj), &s);
+        }
+        s.A = wave_sum64(s.A);
+        s.I = wave_sum64(s.I);
+        s.SH = wave_sum64(s.SH);
+        s.SV = wave_sum64(s.SV);
+    }
+    if (lane != 0) return;
+    int32_t o[8], v[4];
+    carry_finish(r, c.fw, c.fh, sense, s, o, v);
+    CarryWords4* po = reinterpret_cast<CarryWords4*>(out + (size_t)i * 8u);
+    po[0] = CarryWords4{{o[0], o[1], o[2], o[3]}};
+    po[1] = CarryWords4{{o[4], o[5], o[6], o[7]}};
+    if (votes) *reinterpret_cast<CarryWords4*>(votes + (size_t)i * 4u) = CarryWords4{{v[0], v[1], v[2], v[3]}};
+    if (status) status[i] = kRegionOk;
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

@@ -70,6 +70,7 @@ struct PipeWindow {
     std::vector<uint32_t> frame_ids;     // ... and its index in the ring entry's lanes (what k_tensor finds planes and tensor by)
     std::vector<leon_pipeline_motion_frame> motion;      // output MOTION: frames[i]'s record and references
     std::vector<leon::MotionDesc> motion_descs;          // ... and what k_motion makes the record from
+    std::vector<uint32_t> carry_table;                   // ... and per frame a leon::CarryFrame (ring id, fwd, bwd, 0): what k_carry reads
     Event done;
     int status = LEON_OK;
     uint32_t n_vpics = 0;        // gpu_parser: error words of the window's pictures are in the ring entry's h_err
@@ -1129,6 +1130,25 @@ int launch_level(leon_pipeline* p, const PipeWindow* w, const std::vector<LevelP
     return crop_planes_batch(d, crop_slots.data(), crop_frames.data(), (int)crop_slots.size());
 }
 
+// carry: which window frames a frame's vectors point into (include/leon_pipeline.h, "References inside a window"): the frames sorted
+// by (gop, display_index) once, every reference looked up in them
+void carry_refs_host(const leon_pipeline_frame* frames, const leon_pipeline_motion_frame* motion, int32_t n, int32_t* fwd, int32_t* bwd)
+{
+    std::vector<int32_t> order((size_t)n);
+    for (int32_t i = 0; i < n; i++) order[(size_t)i] = i;
+    const auto key_less = [&](uint64_t ga, int32_t da, uint64_t gb, int32_t db) { return ga != gb ? ga < gb : da < db; };
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key_less(frames[a].gop, frames[a].display_index, frames[b].gop, frames[b].display_index); });
+    const auto find = [&](uint64_t gop, int32_t display) -> int32_t {
+        if (display < 0) return -1;
+        const auto it = std::lower_bound(order.begin(), order.end(), 0, [&](int32_t a, int32_t) { return key_less(frames[a].gop, frames[a].display_index, gop, display); });
+        return it != order.end() && frames[*it].gop == gop && frames[*it].display_index == display ? *it : -1;
+    };
+    for (int32_t i = 0; i < n; i++) {
+        fwd[i] = find(motion[i].fwd_gop, motion[i].fwd_display);
+        bwd[i] = find(frames[i].gop, motion[i].bwd_display);
+    }
+}
+
 // the window's frames in display order, GOP-major
 void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<LevelPic>>& levels)
 {
@@ -1193,6 +1213,17 @@ void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<
         p->st_pictures += job->pics.size();
     }
     p->st_gops += w->jobs.size();
+    w->carry_table.clear();
+    if (p->d_motion && !w->frames.empty()) {
+        const size_t n = w->frames.size();
+        std::vector<int32_t> fwd(n), bwd(n);
+        carry_refs_host(w->frames.data(), w->motion.data(), (int32_t)n, fwd.data(), bwd.data());
+        w->carry_table.resize(4 * n);
+        for (size_t i = 0; i < n; i++) {
+            const leon::CarryFrame f{w->motion_descs[i].frame, fwd[i], bwd[i], 0u};
+            std::memcpy(&w->carry_table[4 * i], &f, sizeof(f));
+        }
+    }
 }
 
 // output TENSOR: the window's frames -> their tensors, one launch on the decoder's stream behind the last level (at most 65535 frames
@@ -1912,6 +1943,197 @@ int warp_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_wa
         he = hipGetLastError();
     }
     return boxes_end(p, st, he, call, !c->stream);
+}
+
+// ---- boxes carried along the motion vectors (leon_pipeline_carry_regions) -------------------------------------------------------
+static_assert(sizeof(leon_pipeline_carry_region) == 32 && sizeof(leon_pipeline_carry_regions_call) == 64 && sizeof(leon::CarryRecord) == sizeof(leon_pipeline_carry_region) &&
+              sizeof(leon::CarryFrame) == 16, "include/leon_pipeline.h states the sizes");
+static_assert(leon::kRegionNoReference == LEON_REGION_NO_REFERENCE, "the kernel's code is the header's");
+
+// the geometry a carry call may have: a coded grid of 1 .. 256 macroblocks an axis and a frame inside it
+int carry_geometry_check(int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames)
+{
+    if (mbw < 1 || mbw > leon::kMotionMaxMb || mbh < 1 || mbh > leon::kMotionMaxMb)
+        return fail(LEON_ERR_INVALID, "carry: %d x %d macroblocks (1 .. %d each)", mbw, mbh, leon::kMotionMaxMb);
+    if (fw < 1 || fw > 16 * mbw || fh < 1 || fh > 16 * mbh) return fail(LEON_ERR_INVALID, "carry: a frame of %d x %d in a grid of %d x %d macroblocks", fw, fh, mbw, mbh);
+    if (n_frames < 0) return fail(LEON_ERR_INVALID, "carry: %d frames", n_frames);
+    return LEON_OK;
+}
+
+// the launch every road shares: records, the window's table and the motion ring in device memory; ceil(n / 4) workgroups
+void carry_launch(hipStream_t st, const leon::CarryRecord* d_recs, const leon::CarryFrame* d_frames, const uint8_t* d_ring, int32_t fw, int32_t fh, int32_t mbw,
+                  const leon::MotionLayout& lay, int32_t n_frames, int32_t n, int32_t* d_out, int32_t* d_votes, int32_t* d_status)
+{
+    leon::CarryCall C{};
+    C.fw = fw; C.fh = fh; C.mbw = mbw;
+    C.n_frames = n_frames; C.n = n;
+    C.info_offset = lay.info_offset; C.record_pitch = lay.record_pitch;
+    const unsigned per = leon::kRgbaBlock / 64;
+    hipLaunchKernelGGL(leon::k_carry, dim3(((unsigned)n + per - 1) / per), dim3(leon::kRgbaBlock), 0, st, d_recs, d_frames, d_ring, d_out, d_votes, d_status, C);
+}
+
+// the window's table (regions_window_ids' refusals)
+int carry_window_table(leon_pipeline* p, int64_t window, std::vector<uint32_t>* table)
+{
+    int status = LEON_OK;
+    const bool out = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        if ((status = w.status) == LEON_OK) *table = w.carry_table;
+    });
+    if (!out) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (status != LEON_OK) return fail(LEON_ERR_INVALID, "window %lld was delivered with an error (status %d)", (long long)window, status);
+    return LEON_OK;
+}
+
+int carry_pipeline_check(const leon_pipeline* p)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    if (!p->d_motion) return fail(LEON_ERR_INVALID, "the pipeline has no motion output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_MOTION)");
+    return LEON_OK;
+}
+
+// One call of the device road: the host's refusals, then inside the boxes bracket (the window's table is all of the scratch it needs)
+// one launch on the caller's stream (or the regions stream and a wait)
+int carry_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_carry_regions_call* c)
+{
+    int rc = carry_pipeline_check(p);
+    if (rc != LEON_OK) return rc;
+    if (!c) return fail(LEON_ERR_INVALID, "null argument");
+    std::unique_lock<std::mutex> call(p->regions_mu);
+    std::vector<uint32_t> table;
+    if ((rc = carry_window_table(p, window, &table)) != LEON_OK) return rc;
+    const int32_t n = c->n;
+    if (c->reserved0 || c->reserved[0] || c->reserved[1]) return fail(LEON_ERR_INVALID, "carry regions: a reserved word of the call is not 0");
+    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "carry regions: %d regions (a call takes 1 .. 65535)", n);
+    if (!c->regions) return fail(LEON_ERR_INVALID, "carry regions: null regions");
+    if (!c->device_out) return fail(LEON_ERR_INVALID, "carry regions: null device_out");
+    if (((uintptr_t)c->regions | (uintptr_t)c->device_out | (uintptr_t)c->device_votes | (uintptr_t)c->device_status) & 3u)
+        return fail(LEON_ERR_INVALID, "carry regions: regions %p, device_out %p, device_votes %p, device_status %p: not all 4-byte aligned", (const void*)c->regions,
+                    (void*)c->device_out, (void*)c->device_votes, (void*)c->device_status);
+    hipStream_t st;
+    uint32_t* d_table = nullptr;
+    hipError_t he = hipSuccess;
+    if ((rc = regions_call_stream(p, c->stream, &st)) != LEON_OK || (rc = boxes_begin(p, st, table, pad256(std::max<size_t>(table.size(), 1) * 4), &d_table, &he)) != LEON_OK) return rc;
+    if (he == hipSuccess) {
+        carry_launch(st, reinterpret_cast<const leon::CarryRecord*>(c->regions), reinterpret_cast<const leon::CarryFrame*>(d_table), p->d_motion, p->vinfo.frame_width,
+                     p->vinfo.frame_height, p->vinfo.mb_width, p->motion_lay, (int32_t)(table.size() / 4), n, reinterpret_cast<int32_t*>(c->device_out), c->device_votes,
+                     c->device_status);
+        he = hipGetLastError();
+    }
+    return boxes_end(p, st, he, call, !c->stream);
+}
+
+// records, results: one device allocation [records | out | votes | status]; what the caller has in out, votes and status goes up first,
+// so that the words the kernel leaves alone come back as they were
+struct CarryHostBufs {
+    DevBuf<int32_t> d;
+    int32_t *recs = nullptr, *out = nullptr, *votes = nullptr, *status = nullptr;
+};
+int carry_host_up(CarryHostBufs* b, size_t extra_bytes, const leon_pipeline_carry_region* regions, int32_t n, const leon_pipeline_region* out, const int32_t* votes,
+                  const int32_t* status, char** extra)
+{
+    const size_t words = (size_t)n * (8 + 8 + 4 + 1), bytes = pad256(words * 4);
+    if (!b->d.alloc(bytes + extra_bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "carry: %zu bytes of device memory", bytes + extra_bytes); }
+    b->recs = b->d; b->out = b->recs + (size_t)n * 8; b->votes = b->out + (size_t)n * 8; b->status = b->votes + (size_t)n * 4;
+    if (extra) *extra = reinterpret_cast<char*>(b->d.get()) + bytes;
+    HIP_TRY(hipMemcpy(b->recs, regions, (size_t)n * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->out, out, (size_t)n * 32, hipMemcpyHostToDevice));
+    if (votes) HIP_TRY(hipMemcpy(b->votes, votes, (size_t)n * 16, hipMemcpyHostToDevice));
+    if (status) HIP_TRY(hipMemcpy(b->status, status, (size_t)n * 4, hipMemcpyHostToDevice));
+    return LEON_OK;
+}
+int carry_host_down(const CarryHostBufs& b, int32_t n, leon_pipeline_region* out, int32_t* votes, int32_t* status)
+{
+    HIP_TRY(hipMemcpy(out, b.out, (size_t)n * 32, hipMemcpyDeviceToHost));
+    if (votes) HIP_TRY(hipMemcpy(votes, b.votes, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (status) HIP_TRY(hipMemcpy(status, b.status, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return LEON_OK;
+}
+
+// One call of the host road: the device road on the regions stream between an upload and three copies
+int carry_regions(leon_pipeline* p, int64_t window, const leon_pipeline_carry_region* regions, int32_t n, leon_pipeline_region* out, int32_t* votes, int32_t* status)
+{
+    int rc = carry_pipeline_check(p);
+    if (rc != LEON_OK) return rc;
+    if (!regions || !out) return fail(LEON_ERR_INVALID, "carry regions: null %s", regions ? "out" : "regions");
+    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "carry regions: %d regions (a call takes 1 .. 65535)", n);
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    CarryHostBufs b;
+    if ((rc = carry_host_up(&b, 0, regions, n, out, votes, status, nullptr)) != LEON_OK) return rc;
+    leon_pipeline_carry_regions_call c{};
+    c.regions = reinterpret_cast<const leon_pipeline_carry_region*>(b.recs);
+    c.n = n;
+    c.device_out = reinterpret_cast<leon_pipeline_region*>(b.out);
+    c.device_votes = votes ? b.votes : nullptr;
+    c.device_status = status ? b.status : nullptr;
+    if ((rc = carry_regions_device(p, window, &c)) != LEON_OK) return rc;      // (stream NULL: it has waited)
+    return carry_host_down(b, n, out, votes, status);
+}
+
+// the definition on the CPU: the same text (leon_carry.h) over a record in host memory; the status word, or a negative error
+int32_t carry_record_host(int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames, const int32_t* fwd, const int32_t* bwd, const void* const* records,
+                          const leon_pipeline_carry_region* rec, leon_pipeline_region* out, int32_t* votes, bool dry)
+{
+    if (!fwd || !bwd || !records || !rec || (!dry && !out)) return fail(LEON_ERR_INVALID, "null argument");
+    const int rc = carry_geometry_check(fw, fh, mbw, mbh, n_frames);
+    if (rc != LEON_OK) return rc;
+    const leon::CarryRecord& r = reinterpret_cast<const leon::CarryRecord&>(*rec);
+    int32_t st = leon::carry_record_status(r, fw, fh, n_frames), m = 0, sense = 1, d = 0;
+    if (st != leon::kRegionOk) return st;
+    if ((st = leon::carry_pick(r.frame, r.target, fwd[r.target], bwd[r.target], fwd[r.frame], bwd[r.frame], &m, &sense, &d)) != leon::kRegionOk) return st;
+    leon::CarrySums s{0, 0, 0, 0};
+    if (d) {
+        const uint8_t* record = static_cast<const uint8_t*>(records[m]);
+        if (!record) return fail(LEON_ERR_INVALID, "carry: frame %d votes (frame %d to %d) and has no record", m, r.frame, r.target);
+        if (dry) return leon::kRegionOk;
+        const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+        for (int32_t j = r.y >> 4; j <= (r.y + r.height - 1) >> 4; j++)
+            for (int32_t i = r.x >> 4; i <= (r.x + r.width - 1) >> 4; i++) {
+                const size_t mb = (size_t)j * (size_t)mbw + (size_t)i;
+                uint32_t f, b;
+                memcpy(&f, record + 8 * mb, 4);
+                memcpy(&b, record + 8 * mb + 4, 4);
+                leon::carry_vote(d, record[L.info_offset + mb], f, b, leon::carry_weight(r.x, r.y, r.width, r.height, i, j), &s);
+            }
+    }
+    if (dry) return leon::kRegionOk;
+    int32_t o[8], v[4];
+    leon::carry_finish(r, fw, fh, sense, s, o, v);
+    memcpy(out, o, 32);
+    if (votes) memcpy(votes, v, 16);
+    return leon::kRegionOk;
+}
+
+// k_carry on records the caller supplies (leon_pipeline_carry_device): memory of its own, the null stream
+int carry_device(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames, const int32_t* fwd, const int32_t* bwd,
+                 const void* const* records, const leon_pipeline_carry_region* regions, int32_t n, leon_pipeline_region* out, int32_t* votes, int32_t* status)
+{
+    if (!fwd || !bwd || !records || !regions || !out) return fail(LEON_ERR_INVALID, "null argument");
+    int rc = carry_geometry_check(fw, fh, mbw, mbh, n_frames);
+    if (rc != LEON_OK) return rc;
+    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "carry regions: %d regions (a call takes 1 .. 65535)", n);
+    for (int32_t i = 0; i < n_frames; i++)
+        if (fwd[i] < -1 || fwd[i] >= n_frames || bwd[i] < -1 || bwd[i] >= n_frames)
+            return fail(LEON_ERR_INVALID, "carry: frame %d points into frames %d and %d of %d", i, fwd[i], bwd[i], n_frames);
+    for (int32_t i = 0; i < n; i++)          // a record that votes must be there: the judgement alone, nothing summed
+        if (carry_record_host(fw, fh, mbw, mbh, n_frames, fwd, bwd, records, regions + i, nullptr, nullptr, true) < 0) return LEON_ERR_INVALID;
+    const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+    // [table | ring]: a frame without a record gets no slot, its ring id stays 0 and nothing of the call reads it
+    std::vector<leon::CarryFrame> table((size_t)n_frames);
+    uint32_t slots = 0;
+    for (int32_t i = 0; i < n_frames; i++) table[(size_t)i] = leon::CarryFrame{records[i] ? slots++ : 0u, fwd[i], bwd[i], 0u};
+    const size_t table_bytes = pad256(table.size() * sizeof(leon::CarryFrame));
+    HIP_TRY(hipSetDevice(device_id));
+    CarryHostBufs b;
+    char* extra = nullptr;
+    if ((rc = carry_host_up(&b, table_bytes + (size_t)std::max<uint32_t>(slots, 1) * L.record_pitch, regions, n, out, votes, status, &extra)) != LEON_OK) return rc;
+    uint8_t* d_ring = reinterpret_cast<uint8_t*>(extra + table_bytes);
+    if (!table.empty()) HIP_TRY(hipMemcpy(extra, table.data(), table.size() * sizeof(leon::CarryFrame), hipMemcpyHostToDevice));
+    for (int32_t i = 0; i < n_frames; i++)
+        if (records[i]) HIP_TRY(hipMemcpy(d_ring + (size_t)table[(size_t)i].ring * L.record_pitch, records[i], L.record_bytes, hipMemcpyHostToDevice));
+    carry_launch(nullptr, reinterpret_cast<const leon::CarryRecord*>(b.recs), reinterpret_cast<const leon::CarryFrame*>(extra), d_ring, fw, fh, mbw, L, n_frames, n, b.out,
+                 votes ? b.votes : nullptr, status ? b.status : nullptr);
+    HIP_TRY(hipGetLastError());
+    return carry_host_down(b, n, out, votes, status);      // (the copies wait: nothing in flight reads the buffer when it goes)
 }
 
 // The device's rows of a batch of single axes, copied back (leon_pipeline_resize_weights_device): memory of its own, the null stream
@@ -2862,6 +3084,55 @@ int leon_pipeline_read_warp_regions(leon_pipeline* p, int64_t window, const leon
 int leon_pipeline_warp_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_warp_config* cfg, const leon_pipeline_warp_regions_call* call)
 {
     return warp_regions_device(p, window, cfg, call);
+}
+
+int leon_pipeline_carry_refs(const leon_pipeline_frame* frames, const leon_pipeline_motion_frame* motion, int32_t n_frames, int32_t* fwd, int32_t* bwd)
+{
+    if (n_frames < 0 || (n_frames && (!frames || !motion || !fwd || !bwd))) return fail(LEON_ERR_INVALID, n_frames < 0 ? "carry refs: a negative frame count" : "null argument");
+    carry_refs_host(frames, motion, n_frames, fwd, bwd);
+    return LEON_OK;
+}
+
+int32_t leon_pipeline_carry_record(int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames, const int32_t* fwd, const int32_t* bwd,
+                                   const void* const* records, const leon_pipeline_carry_region* rec, leon_pipeline_region* out, int32_t* votes)
+{
+    return carry_record_host(frame_width, frame_height, mb_width, mb_height, n_frames, fwd, bwd, records, rec, out, votes, false);
+}
+
+int leon_pipeline_get_carry_refs(leon_pipeline* p, int64_t window, int32_t* fwd, int32_t* bwd, int32_t n)
+{
+    if (!p || !fwd || !bwd) return fail(LEON_ERR_INVALID, "null argument");
+    if (!p->d_motion) return fail(LEON_ERR_INVALID, "the pipeline has no motion output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_MOTION)");
+    size_t has = 0;
+    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        has = w.carry_table.size() / 4;
+        if (n >= 0 && (size_t)n == has)
+            for (size_t i = 0; i < has; i++) {
+                fwd[i] = (int32_t)w.carry_table[4 * i + 1];
+                bwd[i] = (int32_t)w.carry_table[4 * i + 2];
+            }
+    });
+    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (n < 0 || (size_t)n != has) return fail(LEON_ERR_INVALID, "window %lld has %zu frames, not %d", (long long)window, has, n);
+    return LEON_OK;
+}
+
+int leon_pipeline_carry_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_carry_regions_call* call)
+{
+    return carry_regions_device(p, window, call);
+}
+
+int leon_pipeline_carry_regions(leon_pipeline* p, int64_t window, const leon_pipeline_carry_region* regions, int32_t n, leon_pipeline_region* out, int32_t* votes,
+                                int32_t* status)
+{
+    return carry_regions(p, window, regions, n, out, votes, status);
+}
+
+int leon_pipeline_carry_device(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames, const int32_t* fwd,
+                               const int32_t* bwd, const void* const* records_host, const leon_pipeline_carry_region* regions, int32_t n, leon_pipeline_region* out,
+                               int32_t* votes, int32_t* status)
+{
+    return carry_device(device_id, frame_width, frame_height, mb_width, mb_height, n_frames, fwd, bwd, records_host, regions, n, out, votes, status);
 }
 
 int leon_pipeline_resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,

@@ -58,6 +58,11 @@
  *   p.readWarpRegions(window, regions, {size: [h, w], padValue}) -> Buffer like readRegions': regions = [[frameIndex, [a00, a01, tx, a10,
  *                                  a11, ty]], ...], the Q16 affine map from output to frame coordinates of a rotated box or an aligned
  *                                  crop (leon_pipeline_read_warp_regions); positions outside the frame read padValue [r, g, b]
+ *   p.carryRegions(window, records) -> {out: Int32Array [n][8], votes: Int32Array [n][4] (A, I, dh, dv), status: Int32Array [n]}: records =
+ *                                  [[frameIndex, x, y, width, height, targetFrameIndex], ...], boxes carried along the motion vectors
+ *                                  between two frames of the window that a prediction joins (leon_pipeline_carry_regions, opts.motion);
+ *                                  out[i] = [target, x', y', width, height, 0, 0, 0] where status[i] is 0, a region record for
+ *                                  readRegions; a record's fault is its status word (9: no prediction joins the two frames), not a throw
  *   p.releaseWindow(window); p.stats(); p.destroy();
  * Open GOPs (closed_gop = 0) need no option: their leading B pictures predict from the GOP before; where that GOP is not decoded (start,
  * seek target, broken_link) they are not delivered and the GOP's frames start at its I picture's displayIndex (include/leon_pipeline.h).
@@ -197,6 +202,13 @@ class LeonPipeline extends EventEmitter {
     const pad = opts.padValue === undefined ? [0, 0, 0] : opts.padValue;
     if (!Array.isArray(pad) || pad.length !== 3 || !pad.every(Number.isInteger)) throw new TypeError('padValue: [r, g, b]');
     return this._p.readWarpRegions(window, Int32Array.from(regions.flat(2)), size[0], size[1], pad[0], pad[1], pad[2]);
+  }
+  // records: [[frameIndex, x, y, width, height, targetFrameIndex], ...]: one hop each along the window's motion records
+  carryRegions(window, records) {
+    if (!Array.isArray(records) || !records.every((r) => Array.isArray(r) && r.length === 6 && r.every(Number.isInteger))) {
+      throw new TypeError('records: [[frameIndex, x, y, width, height, targetFrameIndex], ...]');
+    }
+    return this._p.carryRegions(window, Int32Array.from(records.flat()));
   }
   releaseWindow(window) { this._p.releaseWindow(window); }
   stats() { return this._p.stats(); }

@@ -47,6 +47,8 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_warp_regions", "leon_pipeline_read_warp_regions", "leon_pipeline_warp_regions_device",
     "leon_pipeline_motion_layout", "leon_pipeline_motion_record", "leon_pipeline_get_motion_layout", "leon_pipeline_window_motion",
     "leon_pipeline_read_motion",
+    "leon_pipeline_carry_refs", "leon_pipeline_carry_record", "leon_pipeline_get_carry_refs", "leon_pipeline_carry_regions_device",
+    "leon_pipeline_carry_regions", "leon_pipeline_carry_device",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -350,6 +352,7 @@ def _regions_fit(fit, anchor, pad_value):
 REGION_OK, REGION_RESERVED, REGION_FRAME, REGION_BOX, REGION_RATIO_X, REGION_RATIO_Y, REGION_TAPS = range(7)
 REGIONS_SCRATCH_DEFAULT = 256 << 20          # LEON_REGIONS_SCRATCH_DEFAULT
 REGION_SCALE, REGION_OFFSET = 7, 8           # LEON_REGION_SCALE, LEON_REGION_OFFSET: a warp record's two own
+REGION_NO_REFERENCE = 9                      # LEON_REGION_NO_REFERENCE: a carry record's own
 
 
 class PipelineWarpRegion(C.Structure):
@@ -362,6 +365,16 @@ class PipelineWarpConfig(C.Structure):
 
 class PipelineWarpRegionsCall(C.Structure):
     _fields_ = [("regions", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("device_out", C.c_void_p), ("out_pitch_bytes", C.c_uint64),
+                ("device_status", C.c_void_p), ("stream", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class PipelineCarryRegion(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("target", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class PipelineCarryRegionsCall(C.Structure):
+    _fields_ = [("regions", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("device_out", C.c_void_p), ("device_votes", C.c_void_p),
                 ("device_status", C.c_void_p), ("stream", C.c_void_p), ("reserved", C.c_uint64 * 2)]
 
 
@@ -521,6 +534,17 @@ def load():
         lib.leon_pipeline_get_motion_layout.argtypes = [C.c_void_p, C.POINTER(PipelineMotionLayout)]
         lib.leon_pipeline_window_motion.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineMotionFrame), C.c_int32]
         lib.leon_pipeline_read_motion.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_carry_regions"):
+        P = C.POINTER
+        lib.leon_pipeline_carry_refs.argtypes = [P(PipelineFrame), P(PipelineMotionFrame), C.c_int32, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_carry_record.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, P(C.c_void_p), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
+        lib.leon_pipeline_carry_record.restype = C.c_int32
+        lib.leon_pipeline_get_carry_refs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]
+        lib.leon_pipeline_carry_regions_device.argtypes = [C.c_void_p, C.c_int64, P(PipelineCarryRegionsCall)]
+        lib.leon_pipeline_carry_regions.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_carry_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, P(C.c_void_p), C.c_void_p,
+                                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -627,6 +651,153 @@ def motion_from_maps(type, mbw, mbh, repadd=None, mb_dir=None, mv_fwd=None, mv_b
     summary = np.array([int(((info & 1) != 0).sum()), int(((info & 2) != 0).sum()), int(((info & 4) != 0).sum()), int(mv.any(axis=1).sum()),
                         int(a[:, 0].sum()), int(a[:, 1].sum()), int(a[:, 2].sum()), int(a[:, 3].sum())], dtype=np.uint32)
     return mv.reshape(int(mbh), int(mbw), 4), info.reshape(int(mbh), int(mbw)), summary
+
+
+def _floor_div(a, b):
+    return a // b          # Python's integer division floors, also for negatives
+
+
+def carry_box(frame_width, frame_height, n_frames, fwd, bwd, records, rec):
+    """The definition of one hop of leon_pipeline_carry_regions (include/leon_pipeline.h) in Python integers, written from the header's
+    text and independent of the C code.  fwd, bwd: what carry_refs gives; records[i] = (mv [mbh, mbw, 4] int16, info [mbh, mbw] uint8) of
+    window frame i (as read_motion gives them; None where no record is at hand); rec = the 8 words (frame, x, y, w, h, target, 0, 0).
+    Returns (status, out, votes): out the 8 words of the moved region and votes [A, I, dh, dv] as lists of Python integers, both None
+    where status is not 0."""
+    S, x, y, w, h, T, r0, r1 = [int(v) for v in rec]
+    fw, fh, n = int(frame_width), int(frame_height), int(n_frames)
+    if r0 or r1:
+        return REGION_RESERVED, None, None
+    if not (0 <= S < n and 0 <= T < n):
+        return REGION_FRAME, None, None
+    if w < 1 or h < 1 or x < 0 or y < 0 or x + w > fw or y + h > fh:
+        return REGION_BOX, None, None
+    if S == T:
+        return REGION_OK, [T, x, y, w, h, 0, 0, 0], [0, 0, 0, 0]
+    D = (1 if int(fwd[T]) == S else 0) | (2 if int(bwd[T]) == S else 0)
+    M, sense = T, -1
+    if not D:
+        D = (1 if int(fwd[S]) == T else 0) | (2 if int(bwd[S]) == T else 0)
+        M, sense = S, 1
+    if not D:
+        return REGION_NO_REFERENCE, None, None
+    mv, info = records[M][0], records[M][1]
+    A = I = SH = SV = 0
+    for j in range(y >> 4, ((y + h - 1) >> 4) + 1):
+        for i in range(x >> 4, ((x + w - 1) >> 4) + 1):
+            a = (min(x + w, 16 * i + 16) - max(x, 16 * i)) * (min(y + h, 16 * j + 16) - max(y, 16 * j))
+            f = int(info[j][i])
+            for b, k in ((1, 0), (2, 2)):
+                if D & b and f & b:
+                    A += a
+                    SH += a * int(mv[j][i][k])
+                    SV += a * int(mv[j][i][k + 1])
+            if f & 4:
+                I += a
+    dh = _floor_div(sense * SH + A, 2 * A) if A else 0
+    dv = _floor_div(sense * SV + A, 2 * A) if A else 0
+    return REGION_OK, [T, min(max(x + dh, 0), fw - w), min(max(y + dv, 0), fh - h), w, h, 0, 0, 0], [A, I, dh, dv]
+
+
+def carry_refs(frames, motion):
+    """leon_pipeline_carry_refs: (fwd, bwd), int32 arrays -- for each frame of a window the index of the window frame its forward and its
+    backward vectors point into, -1: none.  frames: [(gop, display_index), ...] (or dicts with those keys); motion: [(fwd_gop,
+    fwd_display, bwd_display), ...] (or the frames' "motion" dicts).  No device."""
+    n = len(frames)
+    fa, ma = (PipelineFrame * max(1, n))(), (PipelineMotionFrame * max(1, n))()
+    for i, (f, m) in enumerate(zip(frames, motion)):
+        fa[i].gop, fa[i].display_index = (f["gop"], f["display_index"]) if isinstance(f, dict) else (f[0], f[1])
+        ma[i].fwd_gop, ma[i].fwd_display, ma[i].bwd_display = (m["fwd_gop"], m["fwd_display"], m["bwd_display"]) if isinstance(m, dict) else m
+    fwd, bwd = np.full(max(1, n), -2, dtype=np.int32), np.full(max(1, n), -2, dtype=np.int32)
+    _chk(load().leon_pipeline_carry_refs(fa, ma, n, fwd.ctypes.data, bwd.ctypes.data))
+    return fwd[:n], bwd[:n]
+
+
+def _carry_records(records, mbw, mbh):
+    """(pointer array, the buffers it points into) of records[i] = (mv, info) or None, each laid out as motion_layout says"""
+    lay = motion_layout(mbw, mbh)
+    ptrs, keep = (C.c_void_p * max(1, len(records)))(), []
+    for i, r in enumerate(records):
+        if r is None:
+            continue
+        buf = np.zeros(lay.record_bytes, dtype=np.uint8)
+        buf[:8 * lay.mbs] = np.ascontiguousarray(r[0], dtype=np.int16).reshape(-1).view(np.uint8)
+        buf[lay.info_offset:lay.info_offset + lay.mbs] = np.ascontiguousarray(r[1], dtype=np.uint8).reshape(-1)
+        keep.append(buf)
+        ptrs[i] = buf.ctypes.data
+    return ptrs, keep
+
+
+def _carry_regions_array(regions):
+    """[n, 8] int32 of a list of (frame, x, y, w, h, target[, r0, r1]) or an integer array [n, 6] / [n, 8]"""
+    a = np.asarray(regions, dtype=np.int64).reshape(len(regions), -1) if len(regions) else np.zeros((0, 8), dtype=np.int64)
+    full = np.zeros((len(a), 8), dtype=np.int32)
+    full[:, :a.shape[1]] = a
+    return full
+
+
+def carry_record(frame_width, frame_height, mbw, mbh, n_frames, fwd, bwd, records, rec, fill=0):
+    """leon_pipeline_carry_record: the library's CPU evaluation of one hop; arguments as carry_box's.  Returns (status, out [8], votes [4])
+    as int32 arrays that hold `fill` where the library wrote nothing; LeonError where it refuses the call."""
+    ptrs, keep = _carry_records(records, mbw, mbh)
+    f, b = np.ascontiguousarray(fwd, dtype=np.int32), np.ascontiguousarray(bwd, dtype=np.int32)
+    r = _carry_regions_array([rec])
+    out, votes = np.full(8, fill, dtype=np.int32), np.full(4, fill, dtype=np.int32)
+    st = load().leon_pipeline_carry_record(int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), f.ctypes.data, b.ctypes.data, ptrs, r.ctypes.data,
+                                           out.ctypes.data, votes.ctypes.data)
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return st, out, votes
+
+
+def carry_device(frame_width, frame_height, mbw, mbh, n_frames, fwd, bwd, records, regions, device_id=0, fill=-1, n=None):
+    """leon_pipeline_carry_device: k_carry on motion records the caller supplies (as carry_box's), regions = [(frame, x, y, w, h,
+    target), ...] -> (out [m, 8], votes [m, 4], status [m]) int32 arrays pre-filled with `fill`: a refused record keeps it in out and
+    votes.  n: the count handed to the library when it is to differ from m = len(regions) (smaller: what lies behind keeps the fill)."""
+    ptrs, keep = _carry_records(records, mbw, mbh)
+    f, b = np.ascontiguousarray(fwd, dtype=np.int32), np.ascontiguousarray(bwd, dtype=np.int32)
+    r = _carry_regions_array(regions)
+    m = max(1, len(r))
+    out, votes, status = np.full((m, 8), fill, dtype=np.int32), np.full((m, 4), fill, dtype=np.int32), np.full(m, fill, dtype=np.int32)
+    _chk(load().leon_pipeline_carry_device(int(device_id), int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), f.ctypes.data, b.ctypes.data, ptrs,
+                                           r.ctypes.data if len(r) else None, len(r) if n is None else int(n), out.ctypes.data, votes.ctypes.data, status.ctypes.data))
+    return out[:len(r)], votes[:len(r)], status[:len(r)]
+
+
+def carry_plan(refs, frames, src):
+    """The hops that carry boxes from window frame `src` to every delivered frame of its GOP in the window: (levels, unreachable) --
+    levels = [[(from_index, to_index), ...], ...], every level's sources are `src` or targets of an earlier level; unreachable = the
+    frames of the GOP no chain of predictions inside the window reaches.  refs = (fwd, bwd) of carry_refs; frames = the window's frames
+    as dicts (or (gop, display_index, type) tuples).  Anchors (I and P pictures) go along the forward chain in both senses, level by
+    level; then every B picture goes from the nearer of its carried references (display distance; a tie: the forward one).  Host only."""
+    fwd, bwd = [int(v) for v in refs[0]], [int(v) for v in refs[1]]
+    info = [(f["gop"], f["display_index"], f["type"]) if isinstance(f, dict) else (int(f[0]), int(f[1]), int(f[2])) for f in frames]
+    src = int(src)
+    group = [i for i in range(len(info)) if info[i][0] == info[src][0]]
+    anchors = [i for i in group if info[i][2] != PIC_B]
+    carried, levels, front = {src}, [], [src]
+    while front:
+        hops = []
+        for u in front:
+            near = [fwd[u]] + ([bwd[u]] if info[u][2] == PIC_B else []) + [a for a in anchors if fwd[a] == u]
+            for a in near:
+                if a in anchors and a not in carried:
+                    carried.add(a)
+                    hops.append((u, a))
+        if hops:
+            levels.append(hops)
+        front = [a for _, a in hops]
+    hops, unreachable = [], [a for a in anchors if a not in carried]
+    for b in group:
+        if info[b][2] != PIC_B or b in carried:
+            continue
+        cands = [r for r in dict.fromkeys((fwd[b], bwd[b])) if r in carried]
+        if not cands:
+            unreachable.append(b)
+            continue
+        hops.append((min(cands, key=lambda r: abs(info[r][1] - info[b][1])), b))
+    if hops:
+        levels.append(hops)
+    return levels, sorted(unreachable)
 
 
 def warp_rgb(rgb, m, size, pad=(0, 0, 0)):
@@ -1063,7 +1234,11 @@ class Pipeline:
     motion=True (beside any output): every frame carries its motion record -- per macroblock of the coded picture the forward and backward
     vectors and an info byte (MOTION_FWD / MOTION_BWD / MOTION_INTRA), and a summary of eight words: motion_from_maps states it.
     frame["motion"] = {"record": device address, "fwd_gop", "fwd_display", "bwd_display": which pictures the vectors point into (-1: none)};
-    read_motion(window, i) copies frame i's record to the host, motion_view(window, i) wraps it in place; motion_layout has the offsets."""
+    read_motion(window, i) copies frame i's record to the host, motion_view(window, i) wraps it in place; motion_layout has the offsets.
+    Carrying boxes (motion=True): carry_regions_device(window, records) moves boxes from one frame of the window to another along those
+    vectors, on the device and on torch's current stream (carry_box states one hop; carry_regions is the same from host records);
+    carry_regions_gop(window, boxes, src) carries a detector's boxes on frame `src` to every frame of its GOP, ready for
+    resample_regions_device."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
@@ -1120,9 +1295,11 @@ class Pipeline:
         ready = threading.Event()          # set once self.h exists: decoding starts inside leon_pipeline_create
 
         self._window_n = {}        # frames of the windows that are out for delivery (motion_view asks window_motion for exactly that many)
+        self._window_gops = {}
 
         def _release(window):
             self._window_n.pop(window, None)
+            self._window_gops.pop(window, None)
             rc = self.lib.leon_pipeline_release_window(self.h, window)
             if rc != OK and self.error is None:
                 self.error = LeonError(rc, "leon_pipeline_release_window(%d): %s" % (window, self.lib.leon_last_error().decode()))
@@ -1141,6 +1318,8 @@ class Pipeline:
                 self.windows += 1
                 self.frames += n
                 self._window_n[window] = n
+                if self.info.output & PIPELINE_OUTPUT_MOTION and n:          # what carry_regions_gop plans with: the frames' gop, display_index, type
+                    self._window_gops[window] = C.string_at(frames, n * C.sizeof(PipelineFrame))          # (one copy; read when asked for)
                 keep = None
                 if self._on_window is not None:
                     # `_pipe`: a callback may read frames through the dicts alone (read_frame(f) below), without the
@@ -1259,6 +1438,106 @@ class Pipeline:
         return (view(0, (lay.mb_height, lay.mb_width, 4), "<i2", (lay.mb_width * 8, 8, 2)),
                 view(lay.info_offset, (lay.mb_height, lay.mb_width), "|u1", (lay.mb_width, 1)),
                 view(lay.summary_offset, (8,), "<i4", (4,)))
+
+    def carry_refs(self, window):
+        """leon_pipeline_get_carry_refs: (fwd, bwd) int32 arrays -- for each frame of a delivered, not yet released window the index of
+        the window frame its forward and backward vectors point into (-1: none in this window), as the pipeline resolved them"""
+        self._need_motion()
+        n = self._window_n.get(int(window))
+        if n is None:
+            raise LeonError(ERR_INVALID, "window %d is not out for delivery" % int(window))
+        fwd, bwd = np.empty(max(1, n), dtype=np.int32), np.empty(max(1, n), dtype=np.int32)
+        _chk(self.lib.leon_pipeline_get_carry_refs(self.h, int(window), fwd.ctypes.data, bwd.ctypes.data, n))
+        return fwd[:n], bwd[:n]
+
+    def carry_regions(self, window, records, fill=0):
+        """leon_pipeline_carry_regions: records = [(frame, x, y, w, h, target), ...] in host memory, one hop each along the window's
+        motion records (carry_box states it) -> (out [n, 8], votes [n, 4], status [n]) int32 host arrays; out[i] is a region record
+        (target, x', y', w, h, 0, 0, 0) for resample_regions, votes[i] = (A, I, dh, dv).  A record's fault is its status word
+        (REGION_*, REGION_NO_REFERENCE: no prediction joins the two frames), never a LeonError; its out and votes keep `fill`.  Synchronous."""
+        r = _carry_regions_array(records)
+        m = max(1, len(r))
+        out, votes, status = np.full((m, 8), fill, dtype=np.int32), np.full((m, 4), fill, dtype=np.int32), np.full(m, fill, dtype=np.int32)
+        _chk(self.lib.leon_pipeline_carry_regions(self.h, int(window), r.ctypes.data if len(r) else None, len(r), out.ctypes.data, votes.ctypes.data, status.ctypes.data))
+        return out[:len(r)], votes[:len(r)], status[:len(r)]
+
+    def carry_regions_device(self, window, records, out=None, votes=None, status=None, stream=None):
+        """leon_pipeline_carry_regions_device: the same hops from records that lie in DEVICE memory -- a contiguous CUDA int32 torch
+        tensor [N, 8]: frame, x, y, w, h, target, 0, 0 -- queued on `stream` (a torch.cuda.Stream; None: torch's current stream) with
+        warp_regions_device's ordering: NO host synchronisation.  Returns (out [N, 8], votes [N, 4], status [N]) int32 tensors on the
+        device (the caller's, or ones the method allocates, not initialised): out[i] and votes[i] are written exactly where status[i]
+        is 0.  out can go to resample_regions_device as it is, and -- a new target written into column 5 -- to the next hop."""
+        import torch
+        self._need_motion()
+        dev = self.device_id
+        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.dtype == torch.int32 and records.dim() == 2 and records.shape[1] == 8
+                and records.is_contiguous()):
+            raise ValueError("records: a contiguous CUDA int32 tensor [N, 8]")
+        n = int(records.shape[0])
+        for name, t, words in (("records", records, 8 * n), ("out", out, 8 * n), ("votes", votes, 4 * n), ("status", status, n)):
+            if t is None:
+                continue
+            if not t.is_cuda or t.device.index != dev:
+                raise ValueError("%s: on %s, the pipeline's device is cuda:%d" % (name, t.device, dev))
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < words:
+                raise ValueError("%s: a contiguous int32 tensor of at least %d words" % (name, words))
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(stream):
+            out = torch.empty((max(1, n), 8), dtype=torch.int32, device="cuda:%d" % dev) if out is None else out
+            votes = torch.empty((max(1, n), 4), dtype=torch.int32, device="cuda:%d" % dev) if votes is None else votes
+            status = torch.empty(max(1, n), dtype=torch.int32, device="cuda:%d" % dev) if status is None else status
+        call = PipelineCarryRegionsCall(records.data_ptr() if n else None, n, 0, out.data_ptr(), votes.data_ptr(), status.data_ptr(), self._stream_handle(stream))
+        _chk(self.lib.leon_pipeline_carry_regions_device(self.h, int(window), C.byref(call)))
+        return out.view(-1)[:8 * n].view(n, 8), votes.view(-1)[:4 * n].view(n, 4), status.view(-1)[:n]
+
+    def carry_regions_gop(self, window, boxes, src, frames=None):
+        """Boxes on window frame `src` carried to every delivered frame of its GOP in the window: boxes = a CUDA int32 tensor [N, 4]
+        (x, y, w, h).  One carry_regions_device call per level of carry_plan on torch's current stream, each level's inputs gathered from
+        the level before by torch indexing: nothing waits for the device.  Returns (records [F, N, 8], votes [F, N, 4], status
+        [F, N]) over all F frames of the window, zero-filled beforehand: records[f] are region records on frame f for
+        resample_regions_device, and a hop that failed -- or followed one that did -- reads as an empty box there (status REGION_BOX
+        downstream of it).  Frames of another GOP, and frames carry_plan cannot reach, have status REGION_NO_REFERENCE.
+        frames: the window's frames when the pipeline did not see them delivered (dicts, or (gop, display_index, type))."""
+        import torch
+        self._need_motion()
+        dev = "cuda:%d" % self.device_id
+        if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda and boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] == 4):
+            raise ValueError("boxes: a CUDA int32 tensor [N, 4] (x, y, w, h)")
+        if frames is None:
+            raw = self._window_gops.get(int(window))
+            if raw is None:
+                raise LeonError(ERR_INVALID, "window %d is not out for delivery" % int(window))
+            fa = np.frombuffer(raw, dtype=np.dtype([("gop", "<u8"), ("display_index", "<i4"), ("type", "<i4"), ("rest", "V48")]))
+            info = list(zip(fa["gop"].tolist(), fa["display_index"].tolist(), fa["type"].tolist()))
+        else:
+            info = list(frames)
+        levels, _ = carry_plan(self.carry_refs(window), info, src)
+        F, N = len(info), int(boxes.shape[0])
+        records = torch.zeros((F, N, 8), dtype=torch.int32, device=dev)
+        votes = torch.zeros((F, N, 4), dtype=torch.int32, device=dev)
+        status = torch.full((F, N), REGION_NO_REFERENCE, dtype=torch.int32, device=dev)
+        records[src, :, 0] = int(src)
+        records[src, :, 1:5] = boxes
+        status[src] = REGION_OK
+        per = max(1, 65535 // max(1, N))          # hops a call takes: 65535 records at the most
+        flat = [h for hops in levels for h in hops]
+        ends = torch.tensor([[h[0] for h in flat], [h[1] for h in flat]] if flat else [[], []], dtype=torch.int64, device=dev)          # (one upload for all levels)
+        ends32, first = ends.to(torch.int32), 0
+        for hops in levels:
+            for at in range(first, first + len(hops), per):
+                stop = min(at + per, first + len(hops))
+                frm, to = ends[0, at:stop], ends[1, at:stop]
+                rec = records[frm]          # (a copy; a source whose own hop failed is all zeros: an empty box on its frame)
+                rec[:, :, 0] = ends32[0, at:stop, None]
+                rec[:, :, 5] = ends32[1, at:stop, None]
+                out = torch.zeros_like(rec)
+                vot = torch.zeros((stop - at, N, 4), dtype=torch.int32, device=dev)
+                sta = torch.zeros((stop - at, N), dtype=torch.int32, device=dev)
+                if N:
+                    self.carry_regions_device(window, rec.view(-1, 8), out=out.view(-1, 8), votes=vot.view(-1, 4), status=sta.view(-1))
+                records[to], votes[to], status[to] = out, vot, sta
+            first += len(hops)
+        return records, votes, status
 
     def read_frame(self, frame):
         out = np.empty((self.info.frame_height, self.info.frame_width, 4), dtype=np.uint8)

@@ -741,6 +741,48 @@ napi_value PipeReadWarpRegions(napi_env env, napi_callback_info info)
     return rc == LEON_OK ? buf : throw_leon(env, rc);
 }
 
+// p.carryRegions(window, records) -> {out: Int32Array [n][8] (leon_pipeline_region records: frame = target, the moved box, three zeros),
+// votes: Int32Array [n][4] (A, I, dh, dv), status: Int32Array [n] (LEON_REGION_*; not 0: the record's words of out and votes are 0)}:
+// leon_pipeline_carry_regions (opts.motion).  records: an Int32Array of n x [frame index, x, y, width, height, target frame index].
+napi_value PipeCarryRegions(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    napi_typedarray_type tt;
+    size_t len = 0, off = 0;
+    void* words = nullptr;
+    napi_value ab;
+    bool is_ta = false;
+    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta ||
+        napi_get_typedarray_info(env, argv[1], &tt, &len, &words, &ab, &off) != napi_ok || tt != napi_int32_array || len % 6 != 0) {
+        napi_throw_type_error(env, nullptr, "carryRegions(window, Int32Array of [frame, x, y, width, height, target] per record)");
+        return nullptr;
+    }
+    const size_t n = len / 6, m = n >= 1 && n <= 65535 ? n : 1;          // (a count the library refuses allocates nothing to speak of here)
+    std::vector<leon_pipeline_carry_region> regions(m);
+    const int32_t* b = static_cast<const int32_t*>(words);
+    for (size_t i = 0; i < n && i < m; i++)
+        regions[i] = leon_pipeline_carry_region{b[6 * i], b[6 * i + 1], b[6 * i + 2], b[6 * i + 3], b[6 * i + 4], b[6 * i + 5], {0, 0}};
+    napi_value o, abs[3], ta[3];
+    void* data[3] = {nullptr, nullptr, nullptr};
+    const size_t per[3] = {8, 4, 1};
+    NAPI_OK(napi_create_object(env, &o));
+    for (int k = 0; k < 3; k++) {          // (a new ArrayBuffer is zero-filled: what a refused record keeps)
+        NAPI_OK(napi_create_arraybuffer(env, m * per[k] * 4, &data[k], &abs[k]));
+        NAPI_OK(napi_create_typedarray(env, napi_int32_array, m * per[k], abs[k], 0, &ta[k]));
+    }
+    const int rc = leon_pipeline_carry_regions(h->p, w, regions.data(), (int32_t)std::min<size_t>(n, 65536), static_cast<leon_pipeline_region*>(data[0]),
+                                               static_cast<int32_t*>(data[1]), static_cast<int32_t*>(data[2]));
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    NAPI_OK(napi_set_named_property(env, o, "out", ta[0]));
+    NAPI_OK(napi_set_named_property(env, o, "votes", ta[1]));
+    NAPI_OK(napi_set_named_property(env, o, "status", ta[2]));
+    return o;
+}
+
 // opts[name] as three floats (an array of numbers); absent: zeros
 bool get_f32x3(napi_env env, napi_value opts, const char* name, float* out)
 {
@@ -1001,7 +1043,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));
