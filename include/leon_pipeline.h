@@ -771,6 +771,109 @@ int leon_pipeline_carry_regions(leon_pipeline* p, int64_t window, const leon_pip
 int leon_pipeline_carry_device(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
                                const int32_t* fwd, const int32_t* bwd, const void* const* records_host, const leon_pipeline_carry_region* regions,
                                int32_t n, leon_pipeline_region* out, int32_t* votes, int32_t* status);
+/* Dense maps propagated along the stream's motion vectors: the models beside a detector give a label mask, keypoint heatmaps or a
+ * feature map, not boxes.  The network runs on the anchors, and its output is warped to the P and B pictures along the motion records
+ * (LEON_PIPELINE_OUTPUT_MOTION), on the device.  The dense counterpart of the carry family above.  Integers only, and NO arithmetic
+ * on a map's elements: they are opaque bytes, so uint8 labels, fp16 heatmaps and fp32 features are all exact.
+ * Maps.  A map lies over the FRAME (not the coded picture) at `stride` s = 1, 2, 4, 8 or 16 frame pixels a cell:
+ *     mw = ceil(frame_width / s), mh = ceil(frame_height / s)
+ * It has `planes` planes (1 .. 4096), each [mh][mw], of elements of `elem_bytes` e = 1, 2 or 4.  The caller's buffer `maps` holds
+ * n_slots maps (1 .. 65535) at slot_pitch_bytes, a multiple of 4 that is at least planes * mh * mw * e; a contiguous tensor
+ * [n_slots][planes][mh][mw] is the normal case.  maps_bytes is what the caller vouches for; it is at least n_slots * slot_pitch_bytes.
+ * A HOP writes the map of window frame `target` T from the maps of the pictures T predicts from: a GATHER THROUGH T'S OWN MOTION
+ * RECORD.  That is the one direction in which a block-motion field defines every output cell exactly once; there is no scatter and no
+ * sense +1.  The record is 32 bytes (leon_pipeline_propagate_hop below): target, dst_slot, fwd_slot, bwd_slot and four reserved words
+ * that must be 0.  fwd_slot / bwd_slot hold the maps of the pictures T's forward and backward vectors point into, -1: not supplied.
+ * THE CALLER VOUCHES FOR WHICH PICTURE A SLOT HOLDS; the kernel needs T's record alone, so a map kept from an earlier window serves an
+ * open GOP's leading B pictures.
+ * Per cell (cx, cy) of T, with info and mv of macroblock k = ((cy * s) >> 4) * mb_width + ((cx * s) >> 4) of T's record:
+ *     info & 1 and fwd_slot >= 0            : forward:  source = the fwd slot, v = (fwd_h, fwd_v), via = 1
+ *     else info & 2 and bwd_slot >= 0       : backward: source = the bwd slot, v = (bwd_h, bwd_v), via = 2
+ *     else                                  : via = 0, and every plane of the cell gets `fill` (its low e bytes)
+ * A bidirectional macroblock takes the forward map when both are supplied: no averaging, elements are opaque.  Where via != 0,
+ *     dx = (v_h + s) >> (1 + log2 s)   = floor((v_h + s) / (2 s))    half-pel luma units to cells, to nearest, ties up; floor also
+ *     dy likewise with v_v                                            below zero (the shift is arithmetic)
+ *     sx = clamp(cx + dx, 0, mw - 1),  sy = clamp(cy + dy, 0, mh - 1)
+ *     dst[pl][cy][cx] = src[pl][sy][sx]                               for every plane pl
+ * via[cy][cx], one byte a cell, goes to an optional output [n][mh][mw] (record i's map at i * mh * mw).  Every cell of every plane of
+ * dst_slot and every byte of the record's via map are written; an I picture as target is all fill, status 0.
+ * Order of judgement: LEON_REGION_RESERVED, LEON_REGION_FRAME (target outside the window), LEON_REGION_SLOT (dst_slot outside
+ * 0 .. n_slots - 1, a source outside -1 .. n_slots - 1, or dst_slot equal to a supplied source).  A refused record has not one byte
+ * of its slot or via map written.  As in the carry family A RECORD'S FAULT IS A STATUS WORD ON BOTH ROADS, NEVER AN ERROR OF THE CALL.
+ * Records of one call must not name another record's dst_slot, as destination or as source (chain the levels of a GOP in calls of
+ * their own: leon_ctypes.propagate_plan).  This is not checked; the result is unspecified, but every address stays in bounds.
+ * One launch per call (k_propagate; one text for host and device: csrc/leon_propagate.h).  No load touches a byte outside
+ * [maps, maps + maps_bytes), no store falls outside dst_slot's planes * mh * mw * e bytes.
+ * NOT in this definition: averaging of bidirectional macroblocks, intra cells filled from the co-located source cell, chroma-style
+ * scaling of the vectors, interpolation between cells. */
+#define LEON_REGION_SLOT 10          /* propagate records only: a slot outside the buffer, or the destination among the sources */
+typedef struct leon_pipeline_propagate_hop {
+    int32_t target;                /* the frame whose map is written (index into the window's frames[]) */
+    int32_t dst_slot;              /* the map that is written */
+    int32_t fwd_slot, bwd_slot;    /* the maps of the pictures T's forward / backward vectors point into; -1: not supplied */
+    int32_t reserved[4];           /* must be 0 */
+} leon_pipeline_propagate_hop;     /* 32 bytes */
+typedef struct leon_pipeline_propagate_config {
+    int32_t  stride;               /* 1, 2, 4, 8, 16 */
+    int32_t  planes;               /* 1 .. 4096 */
+    int32_t  elem_bytes;           /* 1, 2, 4 */
+    int32_t  n_slots;              /* 1 .. 65535 */
+    uint32_t fill;                 /* its low elem_bytes bytes fill the cells with via 0 */
+    int32_t  reserved0;            /* must be 0 */
+    uint64_t slot_pitch_bytes;     /* a multiple of 4, at least planes * mh * mw * elem_bytes */
+    uint64_t maps_bytes;           /* what the caller vouches for behind `maps`: at least n_slots * slot_pitch_bytes */
+} leon_pipeline_propagate_config;  /* 40 bytes */
+/* (a struct tag only, as leon_pipeline_motion_layout: the host call that fills it has the same name) */
+struct leon_pipeline_propagate_layout {
+    int32_t  mw, mh;               /* cells of a map */
+    int32_t  planes_per_group;     /* planes one lane of k_propagate loops over (grid y = ceil(planes / planes_per_group)) */
+    int32_t  fast_path;            /* 1: a work unit is a destination dword (mw * e and (16 / s) * e multiples of 4), 0: a cell */
+    uint64_t plane_bytes;          /* mh * mw * elem_bytes */
+    uint64_t slot_bytes;           /* planes * plane_bytes: the least slot_pitch_bytes (always a multiple of 4 on the fast path) */
+};                                 /* 32 bytes */
+typedef struct leon_pipeline_propagate_maps_call {
+    const leon_pipeline_propagate_hop* hops;   /* DEVICE memory, n records, 4-byte aligned */
+    int32_t  n;                            /* 1 .. 65535 */
+    int32_t  reserved0;                    /* must be 0 */
+    void*    maps;                         /* DEVICE memory, cfg->maps_bytes bytes, 4-byte aligned; written in place */
+    uint8_t* device_via;                   /* DEVICE memory, n x mh x mw bytes, 4-byte aligned, may be NULL */
+    int32_t* device_status;                /* DEVICE memory, n words, may be NULL */
+    void*    stream;                       /* hipStream_t of the caller's; NULL: the pipeline's regions stream, and the call waits */
+    uint64_t reserved[2];                  /* must be 0 */
+} leon_pipeline_propagate_maps_call;       /* 64 bytes */
+/* host only: the sizes of a map.  LEON_ERR_INVALID: a null `out`, a frame outside 1 .. 4096 an axis, a stride, plane count or element
+ * size outside the above. */
+int leon_pipeline_propagate_layout(int32_t frame_width, int32_t frame_height, int32_t stride, int32_t planes, int32_t elem_bytes,
+                                   struct leon_pipeline_propagate_layout* out);
+/* host only: the definition on the CPU (the text the kernel compiles too) for one record, everything in host memory: records[i] is
+ * window frame i's motion record laid out as leon_pipeline_motion_layout(mb_width, mb_height) says (only records[target] is read),
+ * maps the buffer of cfg->maps_bytes bytes, via this record's [mh][mw] bytes (may be NULL).  Returns the record's status word (>= 0;
+ * the slot and via are written exactly when it is 0), or LEON_ERR_INVALID (negative) for a null argument, a grid outside 1 .. 256, a
+ * frame larger than the grid or below 1, n_frames < 0, a cfg the device road refuses, maps not 4-byte aligned, a NULL record of the
+ * target's. */
+int32_t leon_pipeline_propagate_record(int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                                       const void* const* records, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hop,
+                                       void* maps, uint8_t* via);
+/* Everything in DEVICE memory: the call ONLY ENQUEUES on the caller's stream (stream NULL: the regions stream, and the call waits),
+ * with leon_pipeline_carry_regions_device's ordering rules and scratch, word for word.  It needs the MOTION bit only.
+ * Refused (LEON_ERR_INVALID, nothing enqueued): what leon_pipeline_carry_regions_device refuses (no MOTION bit, a window that is not
+ * out for delivery or was delivered with an error, a null call, `hops` or `maps`, a pointer that is not 4-byte aligned, n outside
+ * 1 .. 65535, a non-zero reserved word of the call), a null cfg, a stride, element size, plane count, n_slots or slot_pitch_bytes
+ * outside the above, maps_bytes below n_slots * slot_pitch_bytes, a non-zero reserved word of cfg. */
+int leon_pipeline_propagate_maps_device(leon_pipeline* p, int64_t window, const leon_pipeline_propagate_config* cfg,
+                                        const leon_pipeline_propagate_maps_call* call);
+/* Records and maps in host memory, synchronous: the device road between an upload and the copies back.  maps (cfg->maps_bytes bytes),
+ * via (n x mh x mw bytes, may be NULL) and status (n words, may be NULL) go up and come back whole, so bytes the kernel leaves alone
+ * stay the caller's.  The call-level refusals are the device road's. */
+int leon_pipeline_propagate_maps(leon_pipeline* p, int64_t window, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hops,
+                                 int32_t n, void* maps, uint8_t* via, int32_t* status);
+/* A diagnostic in the manner of leon_pipeline_carry_device: k_propagate on motion records the CALLER supplies (host memory,
+ * records_host[i] of window frame i; NULL for frames no hop of the call targets), with memory of its own on device_id's null stream,
+ * synchronous; hops, maps, via (may be NULL) and status (may be NULL) in host memory, going up and coming back whole.  Refused
+ * (LEON_ERR_INVALID): what leon_pipeline_propagate_record refuses, n outside 1 .. 65535, a valid hop whose target has no record. */
+int leon_pipeline_propagate_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                                   const void* const* records_host, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hops,
+                                   int32_t n, void* maps, uint8_t* via, int32_t* status);
 /* A diagnostic: the DEVICE's evaluation of the tables of n_axes single axes, copied back, to be compared word for word with
  * leon_pipeline_resize_weights (pixels would hide a weight that is one unit off).  axes = n_axes x {in_size, crop_start, crop_size,
  * out_size}; with max_out the largest out_size of the batch, axis a's tables lie at a fixed pitch: first[a * max_out + o],

@@ -41,6 +41,7 @@
 #include "leon_warp.h"
 #include "leon_motion.h"
 #include "leon_carry.h"
+#include "leon_propagate.h"
 
 
 namespace leon {
@@ -3048,6 +3049,39 @@ __global__ __launch_bounds__(kRgbaBlock) void k_carry(const CarryRecord* __restr
     po[1] = CarryWords4{{o[4], o[5], o[6], o[7]}};
     if (votes) *reinterpret_cast<CarryWords4*>(votes + (size_t)i * 4u) = CarryWords4{{v[0], v[1], v[2], v[3]}};
     if (status) status[i] = kRegionOk;
+}
+
+// ---- propagate: a dense map along the motion vectors, a gather through the target's record (include/leon_pipeline.h,
+// leon_pipeline_propagate_maps) ----
+// One launch per call: blockIdx.z the hop record, blockIdx.y a group of c.g.group planes, blockIdx.x x 256 lanes over one plane's work
+// units (leon_propagate.h: a destination dword on the fast path, a cell otherwise -- chosen per call, so uniform over the grid).  A lane
+// works out its macroblock, pick and source address once and loops over its group's planes: maps with few cells and many planes get
+// their parallelism from y.  Consecutive lanes store consecutive dwords (cells); the source of a unit the clamp leaves alone is two
+// aligned dwords funnelled by v_alignbyte, as the reconstruction kernels' reference fetch.  via is written by plane group 0 alone, the
+// status word by one lane of the hop.  No LDS, no atomics, no barrier, no scratch; lanes of a refused record leave at once.
+// T's record lies at ring + frames[T].ring * record_pitch, where k_motion wrote it.  A cell of the frame lies inside the coded grid
+// (fw <= 16 * mbw, fh <= 16 * mbh: the callers see to it), so every macroblock index is below mbs.
+struct PropagateCall {
+    PropagateGeom g;
+    size_t slot_pitch, maps_bytes;       // the caller's buffer: n_slots maps at slot_pitch, maps_bytes in all
+    int32_t n_frames, n_slots;           // frames of the window, maps of the buffer
+    uint32_t fill;
+    uint32_t info_offset, record_pitch;  // MotionLayout's
+    uint32_t reserved;
+};
+
+__global__ __launch_bounds__(kRgbaBlock) void k_propagate(const PropagateHop* __restrict__ hops, const CarryFrame* __restrict__ frames,
+                                                           const uint8_t* __restrict__ ring, uint8_t* maps, uint8_t* __restrict__ via,
+                                                           int32_t* __restrict__ status, PropagateCall c)
+{
+    const uint32_t i = blockIdx.z, u = blockIdx.x * (uint32_t)kRgbaBlock + threadIdx.x;
+    const PropagateHop h = hops[i];
+    const int32_t st = propagate_hop_status(h, c.n_frames, c.n_slots);
+    if (status && u == 0 && blockIdx.y == 0) status[i] = st;
+    if (st != kRegionOk || u >= c.g.units) return;
+    const int32_t p0 = (int32_t)blockIdx.y * c.g.group, p1 = p0 + c.g.group < c.g.planes ? p0 + c.g.group : c.g.planes;
+    uint8_t* v = via && blockIdx.y == 0 ? via + (size_t)i * (size_t)c.g.mh * (size_t)c.g.mw : nullptr;
+    propagate_unit(c.g, ring + (size_t)frames[h.target].ring * c.record_pitch, c.info_offset, maps, c.maps_bytes, c.slot_pitch, h, c.fill, v, u, p0, p1);
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

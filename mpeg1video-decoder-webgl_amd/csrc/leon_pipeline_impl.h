@@ -2136,6 +2136,197 @@ int carry_device(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32_t
     return carry_host_down(b, n, out, votes, status);      // (the copies wait: nothing in flight reads the buffer when it goes)
 }
 
+// ---- dense maps propagated along the motion vectors (leon_pipeline_propagate_maps) ------------------------------------------------
+static_assert(sizeof(leon_pipeline_propagate_hop) == 32 && sizeof(leon_pipeline_propagate_config) == 40 && sizeof(struct leon_pipeline_propagate_layout) == 32 &&
+              sizeof(leon_pipeline_propagate_maps_call) == 64 && sizeof(leon::PropagateHop) == sizeof(leon_pipeline_propagate_hop), "include/leon_pipeline.h states the sizes");
+static_assert(leon::kRegionSlot == LEON_REGION_SLOT, "the kernel's code is the header's");
+
+// what a call's maps may be: the geometry (leon_propagate.h) and the caller's buffer around it
+int propagate_config_check(int32_t fw, int32_t fh, int32_t mbw, const leon_pipeline_propagate_config* cfg, leon::PropagateGeom* g)
+{
+    if (!cfg) return fail(LEON_ERR_INVALID, "propagate: null cfg");
+    if (cfg->reserved0) return fail(LEON_ERR_INVALID, "propagate: a reserved word of cfg is not 0");
+    if (!leon::propagate_geometry(fw, fh, mbw, cfg->stride, cfg->planes, cfg->elem_bytes, g))
+        return fail(LEON_ERR_INVALID, "propagate: stride %d (1, 2, 4, 8, 16), %d planes (1 .. %d), elem_bytes %d (1, 2, 4)", cfg->stride, cfg->planes, leon::kPropagateMaxPlanes,
+                    cfg->elem_bytes);
+    if (cfg->n_slots < 1 || cfg->n_slots > leon::kPropagateMaxSlots) return fail(LEON_ERR_INVALID, "propagate: %d slots (1 .. %d)", cfg->n_slots, leon::kPropagateMaxSlots);
+    const uint64_t slot_bytes = (uint64_t)g->planes * g->plane_bytes;
+    if (cfg->slot_pitch_bytes % 4 || cfg->slot_pitch_bytes < slot_bytes)
+        return fail(LEON_ERR_INVALID, "propagate: slot_pitch_bytes %llu (a multiple of 4 not below the map's %llu bytes)", (unsigned long long)cfg->slot_pitch_bytes,
+                    (unsigned long long)slot_bytes);
+    if (cfg->maps_bytes / (uint64_t)cfg->n_slots < cfg->slot_pitch_bytes)
+        return fail(LEON_ERR_INVALID, "propagate: maps_bytes %llu is below %d slots of %llu bytes", (unsigned long long)cfg->maps_bytes, cfg->n_slots,
+                    (unsigned long long)cfg->slot_pitch_bytes);
+    return LEON_OK;
+}
+
+// the launch every road shares: hops, the window's table, the motion ring and the maps in device memory
+void propagate_launch(hipStream_t st, const leon::PropagateHop* d_hops, const leon::CarryFrame* d_frames, const uint8_t* d_ring, const leon::PropagateGeom& g,
+                      const leon::MotionLayout& lay, int32_t n_frames, const leon_pipeline_propagate_config& cfg, int32_t n, uint8_t* d_maps, uint8_t* d_via, int32_t* d_status)
+{
+    leon::PropagateCall C{};
+    C.g = g;
+    C.slot_pitch = (size_t)cfg.slot_pitch_bytes; C.maps_bytes = (size_t)cfg.maps_bytes;
+    C.n_frames = n_frames; C.n_slots = cfg.n_slots;
+    C.fill = cfg.fill;
+    C.info_offset = lay.info_offset; C.record_pitch = lay.record_pitch;
+    const dim3 grid((g.units + leon::kRgbaBlock - 1) / leon::kRgbaBlock, (unsigned)((g.planes + g.group - 1) / g.group), (unsigned)n);
+    hipLaunchKernelGGL(leon::k_propagate, grid, dim3(leon::kRgbaBlock), 0, st, d_hops, d_frames, d_ring, d_maps, d_via, d_status, C);
+}
+
+// One call of the device road: the host's refusals, then inside the boxes bracket (the window's table is all of the scratch it needs)
+// one launch on the caller's stream (or the regions stream and a wait)
+int propagate_maps_device(leon_pipeline* p, int64_t window, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_maps_call* c)
+{
+    int rc = carry_pipeline_check(p);
+    if (rc != LEON_OK) return rc;
+    if (!c) return fail(LEON_ERR_INVALID, "null argument");
+    std::unique_lock<std::mutex> call(p->regions_mu);
+    std::vector<uint32_t> table;
+    if ((rc = carry_window_table(p, window, &table)) != LEON_OK) return rc;
+    const int32_t n = c->n;
+    if (c->reserved0 || c->reserved[0] || c->reserved[1]) return fail(LEON_ERR_INVALID, "propagate maps: a reserved word of the call is not 0");
+    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "propagate maps: %d hops (a call takes 1 .. 65535)", n);
+    if (!c->hops) return fail(LEON_ERR_INVALID, "propagate maps: null hops");
+    if (!c->maps) return fail(LEON_ERR_INVALID, "propagate maps: null maps");
+    if (((uintptr_t)c->hops | (uintptr_t)c->maps | (uintptr_t)c->device_via | (uintptr_t)c->device_status) & 3u)
+        return fail(LEON_ERR_INVALID, "propagate maps: hops %p, maps %p, device_via %p, device_status %p: not all 4-byte aligned", (const void*)c->hops, c->maps,
+                    (void*)c->device_via, (void*)c->device_status);
+    leon::PropagateGeom g;
+    if ((rc = propagate_config_check(p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width, cfg, &g)) != LEON_OK) return rc;
+    hipStream_t st;
+    uint32_t* d_table = nullptr;
+    hipError_t he = hipSuccess;
+    if ((rc = regions_call_stream(p, c->stream, &st)) != LEON_OK || (rc = boxes_begin(p, st, table, pad256(std::max<size_t>(table.size(), 1) * 4), &d_table, &he)) != LEON_OK) return rc;
+    if (he == hipSuccess) {
+        propagate_launch(st, reinterpret_cast<const leon::PropagateHop*>(c->hops), reinterpret_cast<const leon::CarryFrame*>(d_table), p->d_motion, g, p->motion_lay,
+                         (int32_t)(table.size() / 4), *cfg, n, static_cast<uint8_t*>(c->maps), c->device_via, c->device_status);
+        he = hipGetLastError();
+    }
+    return boxes_end(p, st, he, call, !c->stream);
+}
+
+// hops, results and maps of a host road: one device allocation [hops | status | via | maps | extra]; what the caller has in maps, via
+// and status goes up first, so that the bytes the kernel leaves alone come back as they were
+struct PropagateHostBufs {
+    DevBuf<uint8_t> d;
+    uint8_t *hops = nullptr, *status = nullptr, *via = nullptr, *maps = nullptr;
+    size_t via_bytes = 0;
+};
+int propagate_host_up(PropagateHostBufs* b, size_t extra_bytes, const leon::PropagateGeom& g, const leon_pipeline_propagate_config& cfg, const leon_pipeline_propagate_hop* hops,
+                      int32_t n, const void* maps, const uint8_t* via, const int32_t* status, uint8_t** extra)
+{
+    b->via_bytes = (size_t)n * (size_t)g.mh * (size_t)g.mw;
+    const size_t hops_bytes = pad256((size_t)n * 32), status_bytes = pad256((size_t)n * 4), via_bytes = pad256(b->via_bytes), maps_bytes = pad256((size_t)cfg.maps_bytes);
+    const size_t bytes = hops_bytes + status_bytes + via_bytes + maps_bytes + extra_bytes;
+    if (!b->d.alloc(bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "propagate: %zu bytes of device memory", bytes); }
+    b->hops = b->d; b->status = b->hops + hops_bytes; b->via = b->status + status_bytes; b->maps = b->via + via_bytes;
+    if (extra) *extra = b->maps + maps_bytes;
+    HIP_TRY(hipMemcpy(b->hops, hops, (size_t)n * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->maps, maps, (size_t)cfg.maps_bytes, hipMemcpyHostToDevice));
+    if (via) HIP_TRY(hipMemcpy(b->via, via, b->via_bytes, hipMemcpyHostToDevice));
+    if (status) HIP_TRY(hipMemcpy(b->status, status, (size_t)n * 4, hipMemcpyHostToDevice));
+    return LEON_OK;
+}
+int propagate_host_down(const PropagateHostBufs& b, const leon_pipeline_propagate_config& cfg, int32_t n, void* maps, uint8_t* via, int32_t* status)
+{
+    HIP_TRY(hipMemcpy(maps, b.maps, (size_t)cfg.maps_bytes, hipMemcpyDeviceToHost));
+    if (via) HIP_TRY(hipMemcpy(via, b.via, b.via_bytes, hipMemcpyDeviceToHost));
+    if (status) HIP_TRY(hipMemcpy(status, b.status, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return LEON_OK;
+}
+
+// One call of the host road: the device road on the regions stream between an upload and the copies back
+int propagate_maps(leon_pipeline* p, int64_t window, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hops, int32_t n, void* maps, uint8_t* via,
+                   int32_t* status)
+{
+    int rc = carry_pipeline_check(p);
+    if (rc != LEON_OK) return rc;
+    if (!hops || !maps) return fail(LEON_ERR_INVALID, "propagate maps: null %s", hops ? "maps" : "hops");
+    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "propagate maps: %d hops (a call takes 1 .. 65535)", n);
+    leon::PropagateGeom g;
+    if ((rc = propagate_config_check(p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width, cfg, &g)) != LEON_OK) return rc;
+    {          // the window's refusals before anything is allocated or uploaded (the device road judges it again under the same lock)
+        std::unique_lock<std::mutex> call(p->regions_mu);
+        std::vector<uint32_t> table;
+        if ((rc = carry_window_table(p, window, &table)) != LEON_OK) return rc;
+    }
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    PropagateHostBufs b;
+    if ((rc = propagate_host_up(&b, 0, g, *cfg, hops, n, maps, via, status, nullptr)) != LEON_OK) return rc;
+    leon_pipeline_propagate_maps_call c{};
+    c.hops = reinterpret_cast<const leon_pipeline_propagate_hop*>(b.hops);
+    c.n = n;
+    c.maps = b.maps;
+    c.device_via = via ? b.via : nullptr;
+    c.device_status = status ? reinterpret_cast<int32_t*>(b.status) : nullptr;
+    if ((rc = propagate_maps_device(p, window, cfg, &c)) != LEON_OK) return rc;      // (stream NULL: it has waited)
+    return propagate_host_down(b, *cfg, n, maps, via, status);
+}
+
+// what the CPU road and the diagnostic refuse of their geometry
+int propagate_host_check(int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames, const void* const* records, const leon_pipeline_propagate_config* cfg,
+                         const void* hops, const void* maps, leon::PropagateGeom* g)
+{
+    if (!records || !cfg || !hops || !maps) return fail(LEON_ERR_INVALID, "null argument");
+    int rc = carry_geometry_check(fw, fh, mbw, mbh, n_frames);
+    if (rc != LEON_OK || (rc = propagate_config_check(fw, fh, mbw, cfg, g)) != LEON_OK) return rc;
+    if ((uintptr_t)maps & 3u) return fail(LEON_ERR_INVALID, "propagate: maps %p is not 4-byte aligned", maps);
+    return LEON_OK;
+}
+
+// the definition on the CPU: the same text (leon_propagate.h), every unit of every plane; the status word, or a negative error
+int32_t propagate_record_host(int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames, const void* const* records, const leon_pipeline_propagate_config* cfg,
+                              const leon_pipeline_propagate_hop* hop, void* maps, uint8_t* via)
+{
+    leon::PropagateGeom g;
+    const int rc = propagate_host_check(fw, fh, mbw, mbh, n_frames, records, cfg, hop, maps, &g);
+    if (rc != LEON_OK) return rc;
+    const leon::PropagateHop& h = reinterpret_cast<const leon::PropagateHop&>(*hop);
+    const int32_t st = leon::propagate_hop_status(h, n_frames, cfg->n_slots);
+    if (st != leon::kRegionOk) return st;
+    const uint8_t* record = static_cast<const uint8_t*>(records[h.target]);
+    if (!record) return fail(LEON_ERR_INVALID, "propagate: frame %d is the target and has no record", h.target);
+    if ((uintptr_t)record & 3u) return fail(LEON_ERR_INVALID, "propagate: record %p is not 4-byte aligned", (const void*)record);
+    const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+    for (uint32_t u = 0; u < g.units; u++)
+        leon::propagate_unit(g, record, L.info_offset, static_cast<uint8_t*>(maps), (size_t)cfg->maps_bytes, (size_t)cfg->slot_pitch_bytes, h, cfg->fill, via, u, 0, g.planes);
+    return leon::kRegionOk;
+}
+
+// k_propagate on records the caller supplies (leon_pipeline_propagate_kernel): memory of its own, the null stream
+int propagate_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames, const void* const* records,
+                     const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hops, int32_t n, void* maps, uint8_t* via, int32_t* status)
+{
+    leon::PropagateGeom g;
+    int rc = propagate_host_check(fw, fh, mbw, mbh, n_frames, records, cfg, hops, maps, &g);
+    if (rc != LEON_OK) return rc;
+    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "propagate maps: %d hops (a call takes 1 .. 65535)", n);
+    for (int32_t i = 0; i < n; i++) {          // a record that is read must be there
+        const leon::PropagateHop& h = reinterpret_cast<const leon::PropagateHop&>(hops[i]);
+        if (leon::propagate_hop_status(h, n_frames, cfg->n_slots) == leon::kRegionOk && !records[h.target])
+            return fail(LEON_ERR_INVALID, "propagate: frame %d is the target of hop %d and has no record", h.target, i);
+    }
+    const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+    // [table | ring]: a frame without a record gets no slot, its ring id stays 0 and nothing of the call reads it
+    std::vector<leon::CarryFrame> table((size_t)n_frames);
+    uint32_t slots = 0;
+    for (int32_t i = 0; i < n_frames; i++) table[(size_t)i] = leon::CarryFrame{records[i] ? slots++ : 0u, -1, -1, 0u};
+    const size_t table_bytes = pad256(std::max<size_t>(table.size(), 1) * sizeof(leon::CarryFrame));
+    HIP_TRY(hipSetDevice(device_id));
+    PropagateHostBufs b;
+    uint8_t* extra = nullptr;
+    if ((rc = propagate_host_up(&b, table_bytes + (size_t)std::max<uint32_t>(slots, 1) * L.record_pitch, g, *cfg, hops, n, maps, via, status, &extra)) != LEON_OK) return rc;
+    uint8_t* d_ring = extra + table_bytes;
+    if (!table.empty()) HIP_TRY(hipMemcpy(extra, table.data(), table.size() * sizeof(leon::CarryFrame), hipMemcpyHostToDevice));
+    for (int32_t i = 0; i < n_frames; i++)
+        if (records[i]) HIP_TRY(hipMemcpy(d_ring + (size_t)table[(size_t)i].ring * L.record_pitch, records[i], L.record_bytes, hipMemcpyHostToDevice));
+    propagate_launch(nullptr, reinterpret_cast<const leon::PropagateHop*>(b.hops), reinterpret_cast<const leon::CarryFrame*>(extra), d_ring, g, L, n_frames, *cfg, n, b.maps,
+                     via ? b.via : nullptr, status ? reinterpret_cast<int32_t*>(b.status) : nullptr);
+    HIP_TRY(hipGetLastError());
+    return propagate_host_down(b, *cfg, n, maps, via, status);      // (the copies wait: nothing in flight reads the buffer when it goes)
+}
+
 // The device's rows of a batch of single axes, copied back (leon_pipeline_resize_weights_device): memory of its own, the null stream
 int resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,
                           int32_t* weights, int32_t* status)
@@ -3133,6 +3324,44 @@ int leon_pipeline_carry_device(int32_t device_id, int32_t frame_width, int32_t f
                                int32_t* votes, int32_t* status)
 {
     return carry_device(device_id, frame_width, frame_height, mb_width, mb_height, n_frames, fwd, bwd, records_host, regions, n, out, votes, status);
+}
+
+int leon_pipeline_propagate_layout(int32_t frame_width, int32_t frame_height, int32_t stride, int32_t planes, int32_t elem_bytes, struct leon_pipeline_propagate_layout* out)
+{
+    if (!out) return fail(LEON_ERR_INVALID, "null argument");
+    if (frame_width < 1 || frame_width > 16 * leon::kMotionMaxMb || frame_height < 1 || frame_height > 16 * leon::kMotionMaxMb)
+        return fail(LEON_ERR_INVALID, "propagate: a frame of %d x %d (1 .. %d each)", frame_width, frame_height, 16 * leon::kMotionMaxMb);
+    leon::PropagateGeom g;
+    if (!leon::propagate_geometry(frame_width, frame_height, (frame_width + 15) / 16, stride, planes, elem_bytes, &g))
+        return fail(LEON_ERR_INVALID, "propagate: stride %d (1, 2, 4, 8, 16), %d planes (1 .. %d), elem_bytes %d (1, 2, 4)", stride, planes, leon::kPropagateMaxPlanes, elem_bytes);
+    out->mw = g.mw; out->mh = g.mh;
+    out->planes_per_group = g.group; out->fast_path = g.fast;
+    out->plane_bytes = g.plane_bytes; out->slot_bytes = (uint64_t)g.planes * g.plane_bytes;
+    return LEON_OK;
+}
+
+int32_t leon_pipeline_propagate_record(int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames, const void* const* records,
+                                       const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hop, void* maps, uint8_t* via)
+{
+    return propagate_record_host(frame_width, frame_height, mb_width, mb_height, n_frames, records, cfg, hop, maps, via);
+}
+
+int leon_pipeline_propagate_maps_device(leon_pipeline* p, int64_t window, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_maps_call* call)
+{
+    return propagate_maps_device(p, window, cfg, call);
+}
+
+int leon_pipeline_propagate_maps(leon_pipeline* p, int64_t window, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hops, int32_t n, void* maps,
+                                 uint8_t* via, int32_t* status)
+{
+    return propagate_maps(p, window, cfg, hops, n, maps, via, status);
+}
+
+int leon_pipeline_propagate_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                                   const void* const* records_host, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hops, int32_t n, void* maps,
+                                   uint8_t* via, int32_t* status)
+{
+    return propagate_kernel(device_id, frame_width, frame_height, mb_width, mb_height, n_frames, records_host, cfg, hops, n, maps, via, status);
 }
 
 int leon_pipeline_resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,

@@ -63,6 +63,17 @@
  *                                  between two frames of the window that a prediction joins (leon_pipeline_carry_regions, opts.motion);
  *                                  out[i] = [target, x', y', width, height, 0, 0, 0] where status[i] is 0, a region record for
  *                                  readRegions; a record's fault is its status word (9: no prediction joins the two frames), not a throw
+ *   p.propagateMaps(window, maps, hops, {stride, planes, elemBytes, fill}) -> {via: Uint8Array [n][mh][mw] (0 fill, 1 forward, 2 backward),
+ *                                  status: Int32Array [n]}: dense maps (masks, heatmaps, features) propagated along the motion vectors
+ *                                  (leon_pipeline_propagate_maps, opts.motion).  maps = a Buffer / Uint8Array over [slots][planes][mh][mw]
+ *                                  elements of elemBytes (1, 2, 4) bytes, mw = ceil(frameWidth / stride), mh likewise, WRITTEN IN
+ *                                  PLACE; hops = [[targetFrameIndex, dstSlot, fwdSlot, bwdSlot], ...]: each writes maps[dstSlot], the
+ *                                  map of frame target, as a gather through that frame's motion record from the maps of the pictures
+ *                                  it predicts from (-1: not supplied); cells with neither get fill.  A hop's fault is its status word
+ *                                  (10: a slot outside the buffer, or the destination among the sources), not a throw.  The maps lie
+ *                                  back to back, and the library takes slots a multiple of 4 bytes apart only: planes * mh * mw *
+ *                                  elemBytes must be a multiple of 4 (a 61 x 45 uint8 mask of one plane is refused with a throw; give
+ *                                  it a second plane, or 2-byte elements)
  *   p.releaseWindow(window); p.stats(); p.destroy();
  * Open GOPs (closed_gop = 0) need no option: their leading B pictures predict from the GOP before; where that GOP is not decoded (start,
  * seek target, broken_link) they are not delivered and the GOP's frames start at its I picture's displayIndex (include/leon_pipeline.h).
@@ -209,6 +220,16 @@ class LeonPipeline extends EventEmitter {
       throw new TypeError('records: [[frameIndex, x, y, width, height, targetFrameIndex], ...]');
     }
     return this._p.carryRegions(window, Int32Array.from(records.flat()));
+  }
+  // hops: [[targetFrameIndex, dstSlot, fwdSlot, bwdSlot], ...]: each a gather through the target's motion record; maps is written in place
+  propagateMaps(window, maps, hops, opts = {}) {
+    if (!(maps instanceof Uint8Array)) throw new TypeError('maps: a Buffer or Uint8Array over [slots][planes][mh][mw]');
+    if (!Array.isArray(hops) || !hops.every((r) => Array.isArray(r) && r.length === 4 && r.every(Number.isInteger))) {
+      throw new TypeError('hops: [[targetFrameIndex, dstSlot, fwdSlot, bwdSlot], ...]');
+    }
+    const { stride = 1, planes = 1, elemBytes = 1, fill = 0 } = opts;
+    if (![stride, planes, elemBytes, fill].every(Number.isInteger)) throw new TypeError('opts: {stride, planes, elemBytes, fill} are integers');
+    return this._p.propagateMaps(window, maps, Int32Array.from(hops.flat()), stride, planes, elemBytes, fill >>> 0);
   }
   releaseWindow(window) { this._p.releaseWindow(window); }
   stats() { return this._p.stats(); }

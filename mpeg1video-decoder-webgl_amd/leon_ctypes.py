@@ -49,6 +49,8 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_read_motion",
     "leon_pipeline_carry_refs", "leon_pipeline_carry_record", "leon_pipeline_get_carry_refs", "leon_pipeline_carry_regions_device",
     "leon_pipeline_carry_regions", "leon_pipeline_carry_device",
+    "leon_pipeline_propagate_layout", "leon_pipeline_propagate_record", "leon_pipeline_propagate_maps_device", "leon_pipeline_propagate_maps",
+    "leon_pipeline_propagate_kernel",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -353,6 +355,7 @@ REGION_OK, REGION_RESERVED, REGION_FRAME, REGION_BOX, REGION_RATIO_X, REGION_RAT
 REGIONS_SCRATCH_DEFAULT = 256 << 20          # LEON_REGIONS_SCRATCH_DEFAULT
 REGION_SCALE, REGION_OFFSET = 7, 8           # LEON_REGION_SCALE, LEON_REGION_OFFSET: a warp record's two own
 REGION_NO_REFERENCE = 9                      # LEON_REGION_NO_REFERENCE: a carry record's own
+REGION_SLOT = 10                             # LEON_REGION_SLOT: a propagate record's own
 
 
 class PipelineWarpRegion(C.Structure):
@@ -376,6 +379,24 @@ class PipelineCarryRegion(C.Structure):
 class PipelineCarryRegionsCall(C.Structure):
     _fields_ = [("regions", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("device_out", C.c_void_p), ("device_votes", C.c_void_p),
                 ("device_status", C.c_void_p), ("stream", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class PipelinePropagateHop(C.Structure):
+    _fields_ = [("target", C.c_int32), ("dst_slot", C.c_int32), ("fwd_slot", C.c_int32), ("bwd_slot", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class PipelinePropagateConfig(C.Structure):
+    _fields_ = [("stride", C.c_int32), ("planes", C.c_int32), ("elem_bytes", C.c_int32), ("n_slots", C.c_int32), ("fill", C.c_uint32), ("reserved0", C.c_int32),
+                ("slot_pitch_bytes", C.c_uint64), ("maps_bytes", C.c_uint64)]
+
+
+class PipelinePropagateLayout(C.Structure):
+    _fields_ = [("mw", C.c_int32), ("mh", C.c_int32), ("planes_per_group", C.c_int32), ("fast_path", C.c_int32), ("plane_bytes", C.c_uint64), ("slot_bytes", C.c_uint64)]
+
+
+class PipelinePropagateMapsCall(C.Structure):
+    _fields_ = [("hops", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("maps", C.c_void_p), ("device_via", C.c_void_p), ("device_status", C.c_void_p),
+                ("stream", C.c_void_p), ("reserved", C.c_uint64 * 2)]
 
 
 class PipelineTensorShape(C.Structure):
@@ -545,6 +566,16 @@ def load():
         lib.leon_pipeline_carry_regions.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.leon_pipeline_carry_device.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, P(C.c_void_p), C.c_void_p,
                                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_propagate_maps"):
+        P = C.POINTER
+        lib.leon_pipeline_propagate_layout.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(PipelinePropagateLayout)]
+        lib.leon_pipeline_propagate_record.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(PipelinePropagateConfig), C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
+        lib.leon_pipeline_propagate_record.restype = C.c_int32
+        lib.leon_pipeline_propagate_maps_device.argtypes = [C.c_void_p, C.c_int64, P(PipelinePropagateConfig), P(PipelinePropagateMapsCall)]
+        lib.leon_pipeline_propagate_maps.argtypes = [C.c_void_p, C.c_int64, P(PipelinePropagateConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_propagate_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(PipelinePropagateConfig), C.c_void_p,
+                                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -798,6 +829,137 @@ def carry_plan(refs, frames, src):
     if hops:
         levels.append(hops)
     return levels, sorted(unreachable)
+
+
+def propagate_map(frame_width, frame_height, n_frames, records, hop, stride, maps, fill=0):
+    """The definition of one hop of leon_pipeline_propagate_maps (include/leon_pipeline.h) in numpy integers, written from the header's
+    text and independent of the C code.  records[i] = (mv [mbh, mbw, 4] int16, info [mbh, mbw] uint8) of window frame i (None where no
+    record is at hand); hop = the 8 words (target, dst_slot, fwd_slot, bwd_slot, 0, 0, 0, 0) (or the first four); maps = an array
+    [S, P, mh, mw] of a 1-, 2- or 4-byte dtype, WRITTEN IN PLACE (maps[dst_slot]) where the status is 0.  Returns (status, via): via
+    [mh, mw] uint8, None where status is not 0."""
+    hop = [int(v) for v in hop] + [0] * (8 - len(hop))
+    T, dst, fs, bs = hop[:4]
+    fw, fh, s = int(frame_width), int(frame_height), int(stride)
+    S, P, mh, mw = maps.shape
+    e = maps.dtype.itemsize
+    if s not in (1, 2, 4, 8, 16) or e not in (1, 2, 4) or (mh, mw) != (-(-fh // s), -(-fw // s)):
+        raise ValueError("propagate_map: stride %d, %d-byte elements, maps of %d x %d cells over a frame of %d x %d" % (s, e, mw, mh, fw, fh))
+    if any(hop[4:]):
+        return REGION_RESERVED, None
+    if not 0 <= T < int(n_frames):
+        return REGION_FRAME, None
+    if not (0 <= dst < S and -1 <= fs < S and -1 <= bs < S) or dst == fs or dst == bs:
+        return REGION_SLOT, None
+    mv, info = np.asarray(records[T][0]).astype(np.int64), np.asarray(records[T][1]).astype(np.int64)
+    cy, cx = np.mgrid[0:mh, 0:mw]
+    kj, ki = (cy * s) >> 4, (cx * s) >> 4
+    f, v = info[kj, ki], mv[kj, ki]
+    use_f = ((f & 1) != 0) & (fs >= 0)
+    use_b = ~use_f & ((f & 2) != 0) & (bs >= 0)
+    dx = np.where(use_f, v[..., 0], v[..., 2]) + s
+    dy = np.where(use_f, v[..., 1], v[..., 3]) + s
+    sx = np.clip(cx + dx // (2 * s), 0, mw - 1)          # (numpy's integer division floors, also for negatives)
+    sy = np.clip(cy + dy // (2 * s), 0, mh - 1)
+    out = np.empty((P, mh, mw), dtype=maps.dtype)
+    out[:] = np.array([int(fill) & 0xffffffff], dtype="<u4").view(np.uint8)[:e].view(maps.dtype)[0]
+    if fs >= 0:
+        out[:, use_f] = maps[fs][:, sy[use_f], sx[use_f]]
+    if bs >= 0:
+        out[:, use_b] = maps[bs][:, sy[use_b], sx[use_b]]
+    maps[dst] = out
+    return REGION_OK, (use_f * 1 + use_b * 2).astype(np.uint8)
+
+
+def propagate_layout(frame_width, frame_height, stride, planes, elem_bytes):
+    """leon_pipeline_propagate_layout: the sizes of a map over a frame (PipelinePropagateLayout: mw, mh, planes_per_group, fast_path,
+    plane_bytes, slot_bytes), no device"""
+    out = PipelinePropagateLayout()
+    _chk(load().leon_pipeline_propagate_layout(int(frame_width), int(frame_height), int(stride), int(planes), int(elem_bytes), C.byref(out)))
+    return out
+
+
+def _propagate_hops_array(hops):
+    """[n, 8] int32 of a list of (target, dst_slot, fwd_slot, bwd_slot[, four reserved words]) or an integer array [n, 4] / [n, 8]"""
+    a = np.asarray(hops, dtype=np.int64).reshape(len(hops), -1) if len(hops) else np.zeros((0, 8), dtype=np.int64)
+    full = np.zeros((len(a), 8), dtype=np.int32)
+    full[:, :a.shape[1]] = a
+    return full
+
+
+def _propagate_config(maps, stride, fill, over=None):
+    """PipelinePropagateConfig of a numpy array [S, P, mh, mw] whose slots may lie further apart than a map (strides[0]); `over`
+    replaces fields (the refusals' tests)"""
+    S, P, mh, mw = maps.shape
+    e = maps.dtype.itemsize
+    if maps.strides[1:] != (mh * mw * e, mw * e, e):
+        raise ValueError("maps: the planes of a slot are contiguous")
+    cfg = PipelinePropagateConfig(int(stride), P, e, S, int(fill) & 0xffffffff, 0, maps.strides[0], S * maps.strides[0])
+    for k, v in (over or {}).items():
+        setattr(cfg, k, v)
+    return cfg
+
+
+def propagate_record(frame_width, frame_height, mbw, mbh, n_frames, records, hop, stride, maps, fill=0, via_fill=0, **over):
+    """leon_pipeline_propagate_record: the library's CPU evaluation of one hop; arguments as propagate_map's, maps written in place.
+    Returns (status, via [mh, mw] uint8 that holds `via_fill` where the library wrote nothing); LeonError where it refuses the call."""
+    ptrs, keep = _carry_records(records, mbw, mbh)
+    h = _propagate_hops_array([hop])
+    via = np.full(maps.shape[2:], via_fill, dtype=np.uint8)
+    cfg = _propagate_config(maps, stride, fill, over)
+    st = load().leon_pipeline_propagate_record(int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), ptrs, C.byref(cfg), h.ctypes.data, maps.ctypes.data,
+                                               via.ctypes.data)
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return st, via
+
+
+def propagate_kernel(frame_width, frame_height, mbw, mbh, n_frames, records, hops, stride, maps, fill=0, via=True, device_id=0, via_fill=0, status_fill=-1, n=None, **over):
+    """leon_pipeline_propagate_kernel: k_propagate on motion records the caller supplies (as propagate_map's), hops = [(target,
+    dst_slot, fwd_slot, bwd_slot), ...], maps [S, P, mh, mw] written in place -> (via [m, mh, mw] uint8 pre-filled with `via_fill`, or
+    None with via=False, status [m] int32 pre-filled with `status_fill`).  n: the count handed to the library when it is to differ
+    from m = len(hops)."""
+    ptrs, keep = _carry_records(records, mbw, mbh)
+    h = _propagate_hops_array(hops)
+    m = max(1, len(h))
+    v = np.full((m,) + maps.shape[2:], via_fill, dtype=np.uint8) if via else None
+    status = np.full(m, status_fill, dtype=np.int32)
+    cfg = _propagate_config(maps, stride, fill, over)
+    _chk(load().leon_pipeline_propagate_kernel(int(device_id), int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), ptrs, C.byref(cfg),
+                                               h.ctypes.data if len(h) else None, len(h) if n is None else int(n), maps.ctypes.data, v.ctypes.data if via else None,
+                                               status.ctypes.data))
+    return (v[:len(h)] if via else None), status[:len(h)]
+
+
+def propagate_plan(refs, frames, src):
+    """The hops that propagate a map from window frame `src` to every delivered frame of its GOP in the window that a chain of
+    predictions reaches: (levels, unreachable) -- levels = [[(target, fwd_ref, bwd_ref), ...], ...] with window frame indices, -1
+    for a reference that is not reachable; every level's references are `src` or targets of an earlier level.  First the set of
+    reachable frames is closed (T is reachable when fwd[T] or bwd[T] is), then level(T) = 1 + max(level of its reachable
+    references): a B picture waits for both anchors.  A hop is a gather through the TARGET's record, so nothing goes from a picture
+    back to its reference: from a P picture the GOP's earlier anchors are out of reach.  refs = (fwd, bwd) of carry_refs; frames =
+    the window's frames as dicts (or (gop, display_index, type) tuples).  Host only."""
+    fwd, bwd = [int(v) for v in refs[0]], [int(v) for v in refs[1]]
+    gops = [f["gop"] if isinstance(f, dict) else int(f[0]) for f in frames]
+    src = int(src)
+    group = [i for i in range(len(gops)) if gops[i] == gops[src]]
+    level, grew = {src: 0}, True
+    reach = {src}
+    while grew:
+        grew = False
+        for t in group:
+            if t not in reach and (fwd[t] in reach or bwd[t] in reach):
+                reach.add(t)
+                grew = True
+
+    def level_of(t):
+        if t not in level:
+            level[t] = 1 + max(level_of(r) for r in (fwd[t], bwd[t]) if r in reach)
+        return level[t]
+    levels = {}
+    for t in group:
+        if t in reach and t != src:
+            levels.setdefault(level_of(t), []).append((t, fwd[t] if fwd[t] in reach else -1, bwd[t] if bwd[t] in reach else -1))
+    return [levels[k] for k in sorted(levels)], [t for t in group if t not in reach]
 
 
 def warp_rgb(rgb, m, size, pad=(0, 0, 0)):
@@ -1238,7 +1400,11 @@ class Pipeline:
     Carrying boxes (motion=True): carry_regions_device(window, records) moves boxes from one frame of the window to another along those
     vectors, on the device and on torch's current stream (carry_box states one hop; carry_regions is the same from host records);
     carry_regions_gop(window, boxes, src) carries a detector's boxes on frame `src` to every frame of its GOP, ready for
-    resample_regions_device."""
+    resample_regions_device.
+    Propagating dense maps (motion=True): propagate_maps_device(window, maps, hops, stride) writes the map of a frame -- a mask, heatmaps,
+    features at 1, 2, 4, 8 or 16 frame pixels a cell -- as a gather from the maps of the pictures it predicts from, through its own motion
+    record, on the device (propagate_map states one hop; propagate_maps is the same from host arrays); propagate_maps_gop(window, map,
+    src, stride) takes a network's output on frame `src` to every frame of its GOP."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
@@ -1538,6 +1704,138 @@ class Pipeline:
                 records[to], votes[to], status[to] = out, vot, sta
             first += len(hops)
         return records, votes, status
+
+    def _propagate_check(self, maps, stride):
+        lay = propagate_layout(self.info.frame_width, self.info.frame_height, stride, maps.shape[1] if len(maps.shape) == 4 else 0, self._elem_bytes(maps))
+        if len(maps.shape) != 4 or tuple(maps.shape[2:]) != (lay.mh, lay.mw):
+            raise ValueError("maps: [S, P, %d, %d] at stride %d, not %s" % (lay.mh, lay.mw, int(stride), tuple(maps.shape)))
+        return lay
+
+    @staticmethod
+    def _elem_bytes(maps):
+        return maps.dtype.itemsize if isinstance(maps, np.ndarray) else maps.element_size()
+
+    def propagate_maps(self, window, maps, hops, stride, fill=0, via_fill=0):
+        """leon_pipeline_propagate_maps: maps = a numpy array [S, P, mh, mw] of a 1-, 2- or 4-byte dtype in host memory, WRITTEN IN PLACE;
+        hops = [(target, dst_slot, fwd_slot, bwd_slot), ...]: each writes maps[dst_slot], the map of window frame `target`, as a gather
+        through the target's motion record from maps[fwd_slot] / maps[bwd_slot] (-1: not supplied) -- propagate_map states it.
+        Returns (via [n, mh, mw] uint8, status [n] int32); a record's fault is its status word (REGION_*, REGION_SLOT), never a
+        LeonError, and its slot and via map keep what they held (`via_fill`).  Synchronous."""
+        self._need_motion()
+        self._propagate_check(maps, stride)
+        h = _propagate_hops_array(hops)
+        m = max(1, len(h))
+        via, status = np.full((m,) + maps.shape[2:], via_fill, dtype=np.uint8), np.zeros(m, dtype=np.int32)
+        cfg = _propagate_config(maps, stride, fill)
+        _chk(self.lib.leon_pipeline_propagate_maps(self.h, int(window), C.byref(cfg), h.ctypes.data if len(h) else None, len(h), maps.ctypes.data, via.ctypes.data,
+                                                   status.ctypes.data))
+        return via[:len(h)], status[:len(h)]
+
+    def propagate_maps_device(self, window, maps, hops, stride, fill=0, via=None, status=None, stream=None):
+        """leon_pipeline_propagate_maps_device: the same hops with everything in DEVICE memory -- maps a contiguous CUDA tensor
+        [S, P, mh, mw] of any 1-, 2- or 4-byte dtype (its slots may lie further apart than a map, stride(0); a map's bytes, or that
+        stride's, are a multiple of 4), written in place; hops a contiguous CUDA int32 tensor [N, 8]: target, dst_slot,
+        fwd_slot, bwd_slot, 0, 0, 0, 0 -- queued on `stream` (a torch.cuda.Stream; None: torch's current stream) with
+        carry_regions_device's ordering: NO host synchronisation.  Returns (via [N, mh, mw] uint8, status [N] int32) on the device
+        (the caller's, or ones the method allocates, not initialised): a slot and its via map are written exactly where status is 0.
+        Hops of one call must not name another hop's dst_slot: chain the levels of propagate_plan in calls of their own."""
+        import torch
+        self._need_motion()
+        dev = self.device_id
+        if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dim() == 4 and maps[0].is_contiguous() and maps.element_size() in (1, 2, 4)
+                and (maps.shape[0] == 1 or maps.stride(0) >= maps[0].numel())):
+            raise ValueError("maps: a CUDA tensor [S, P, mh, mw] of a 1-, 2- or 4-byte dtype, contiguous (or with its slots further apart: stride(0))")
+        if not (isinstance(hops, torch.Tensor) and hops.is_cuda and hops.dtype == torch.int32 and hops.dim() == 2 and hops.shape[1] == 8 and hops.is_contiguous()):
+            raise ValueError("hops: a contiguous CUDA int32 tensor [N, 8]")
+        lay = self._propagate_check(maps, stride)
+        n, cells = int(hops.shape[0]), lay.mh * lay.mw
+        for name, t, dtype, count in (("maps", maps, maps.dtype, 0), ("hops", hops, torch.int32, 0), ("via", via, torch.uint8, n * cells), ("status", status, torch.int32, n)):
+            if t is None:
+                continue
+            if not t.is_cuda or t.device.index != dev:
+                raise ValueError("%s: on %s, the pipeline's device is cuda:%d" % (name, t.device, dev))
+            if t.dtype != dtype or (t is not maps and not t.is_contiguous()) or t.numel() < count:
+                raise ValueError("%s: a contiguous %s tensor of at least %d elements" % (name, dtype, count))
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(stream):
+            via = torch.empty((max(1, n), lay.mh, lay.mw), dtype=torch.uint8, device="cuda:%d" % dev) if via is None else via
+            status = torch.empty(max(1, n), dtype=torch.int32, device="cuda:%d" % dev) if status is None else status
+        S, P, e = int(maps.shape[0]), int(maps.shape[1]), maps.element_size()
+        pitch = (maps.stride(0) if S > 1 else P * cells) * e          # (the library refuses one that is no multiple of 4: pad the slots apart)
+        cfg = PipelinePropagateConfig(int(stride), P, e, S, int(fill) & 0xffffffff, 0, pitch, S * pitch)
+        call = PipelinePropagateMapsCall(hops.data_ptr() if n else None, n, 0, maps.data_ptr(), via.data_ptr(), status.data_ptr(), self._stream_handle(stream))
+        _chk(self.lib.leon_pipeline_propagate_maps_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        return via.view(-1)[:n * cells].view(n, lay.mh, lay.mw), status.view(-1)[:n]
+
+    def _window_keys(self, window, frames=None):
+        """(gop, display_index, type) of the frames of a window that is out for delivery"""
+        if frames is not None:
+            return [(f["gop"], f["display_index"], f["type"]) if isinstance(f, dict) else tuple(int(v) for v in f[:3]) for f in frames]
+        raw = self._window_gops.get(int(window))
+        if raw is None:
+            raise LeonError(ERR_INVALID, "window %d is not out for delivery" % int(window))
+        fa = np.frombuffer(raw, dtype=np.dtype([("gop", "<u8"), ("display_index", "<i4"), ("type", "<i4"), ("rest", "V48")]))
+        return list(zip(fa["gop"].tolist(), fa["display_index"].tolist(), fa["type"].tolist()))
+
+    def gop_frames(self, window, src, frames=None):
+        """the window frames of `src`'s GOP, in the window's order: what the rows of propagate_maps_gop's results stand for"""
+        keys = self._window_keys(window, frames)
+        return [i for i, k in enumerate(keys) if k[0] == keys[int(src)][0]]
+
+    def propagate_maps_gop(self, window, map, src, stride, fill=0, frames=None):
+        """A map on window frame `src` propagated to every delivered frame of its GOP in the window: map = a CUDA tensor [P, mh, mw] of a
+        1-, 2- or 4-byte dtype (a mask, heatmaps, features).  One propagate_maps_device call per level of propagate_plan on torch's
+        current stream; all levels' hop records go up in one upload from pinned memory in front of the first launch, queued like the launches: nothing
+        waits for the device.
+        Returns (maps [F, P, mh, mw], via [F, mh, mw] uint8, status [F] int32) over the F frames gop_frames(window, src) lists: `src`'s
+        row is a copy of `map` with via 3; a frame no chain of predictions reaches from `src` is all fill, via 0, status
+        REGION_NO_REFERENCE.  frames: the window's frames when the pipeline did not see them delivered."""
+        import torch
+        self._need_motion()
+        dev = "cuda:%d" % self.device_id
+        if not (isinstance(map, torch.Tensor) and map.is_cuda and map.dim() == 3 and map.element_size() in (1, 2, 4)):
+            raise ValueError("map: a CUDA tensor [P, mh, mw] of a 1-, 2- or 4-byte dtype")
+        keys = self._window_keys(window, frames)
+        src = int(src)
+        group = [i for i, k in enumerate(keys) if k[0] == keys[src][0]]
+        slot = {f: i for i, f in enumerate(group)}
+        levels, unreachable = propagate_plan(self.carry_refs(window), keys, src)
+        F, e = len(group), map.element_size()
+        per = int(map.numel())
+        pitch = (per * e + 3) // 4 * 4 // e          # elements from slot to slot: a map's bytes rounded up to a multiple of 4
+        maps = torch.empty((F, pitch), dtype=map.dtype, device=dev)[:, :per].view((F,) + tuple(map.shape))          # (contiguous where per * e is one)
+        self._propagate_check(maps, stride)
+        via = torch.zeros((F,) + tuple(map.shape[1:]), dtype=torch.uint8, device=dev)
+        status = torch.zeros(F, dtype=torch.int32, device=dev)
+        maps[slot[src]] = map
+        via[slot[src]] = 3
+        if unreachable:          # (fills by value: nothing goes up)
+            word = int(np.array([int(fill) & 0xffffffff], dtype="<u4").view(np.uint8)[:e].view({1: np.uint8, 2: np.int16, 4: np.int32}[e])[0])
+            bits = maps.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[e])          # (the same element size: the strides stay)
+            for u in unreachable:
+                bits[slot[u]].fill_(word)
+                status[slot[u]].fill_(REGION_NO_REFERENCE)
+        flat = [(t, slot[t], slot.get(f, -1), slot.get(b, -1), 0, 0, 0, 0) for hops in levels for (t, f, b) in hops]
+        if not flat:
+            return maps, via, status
+        hops_dev = torch.tensor(flat, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)          # (one upload for all levels, from pinned memory: queued, not waited for)
+        rows = hops_dev[:, 1].to(torch.int64)
+        status_hops = torch.empty(len(flat), dtype=torch.int32, device=dev)
+        cells = int(map.shape[1]) * int(map.shape[2])
+        starts, total = [], 0          # each level's via maps start on a 4-byte boundary of one buffer
+        for hops in levels:
+            starts.append(total)
+            total += (len(hops) * cells + 3) // 4 * 4
+        via_hops = torch.empty(total, dtype=torch.uint8, device=dev)
+        first = 0
+        for hops, at in zip(levels, starts):
+            stop = first + len(hops)
+            v = via_hops[at:at + len(hops) * cells]
+            self.propagate_maps_device(window, maps, hops_dev[first:stop], stride, fill=fill, via=v, status=status_hops[first:stop])
+            via[rows[first:stop]] = v.view((len(hops),) + tuple(map.shape[1:]))
+            first = stop
+        status[rows] = status_hops
+        return maps, via, status
 
     def read_frame(self, frame):
         out = np.empty((self.info.frame_height, self.info.frame_width, 4), dtype=np.uint8)

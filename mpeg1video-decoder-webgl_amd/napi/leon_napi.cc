@@ -783,6 +783,64 @@ napi_value PipeCarryRegions(napi_env env, napi_callback_info info)
     return o;
 }
 
+// p.propagateMaps(window, maps, hops, stride, planes, elemBytes, fill) -> {via: Uint8Array [n][mh][mw] (0 fill, 1 forward, 2 backward),
+// status: Int32Array [n] (LEON_REGION_*; not 0: the record's slot and via map are left as they were, via zero)}:
+// leon_pipeline_propagate_maps (opts.motion).  maps: a Uint8Array over the bytes of [slots][planes][mh][mw], contiguous, WRITTEN IN
+// PLACE; hops: an Int32Array of n x [target frame index, dst slot, fwd slot, bwd slot].  The slot pitch is the map's size, so a map
+// whose bytes are no multiple of 4 is refused by the library (js/leon_pipeline.js says so).
+napi_value PipePropagateMaps(napi_env env, napi_callback_info info)
+{
+    size_t argc = 7;
+    napi_value argv[7];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    napi_typedarray_type tm, th;
+    size_t mlen = 0, hlen = 0, off = 0;
+    void *maps = nullptr, *words = nullptr;
+    napi_value ab;
+    bool is_m = false, is_h = false;
+    int32_t stride = 0, planes = 0, elem = 0;
+    uint32_t fill = 0;
+    if (argc < 7 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_m) != napi_ok || !is_m ||
+        napi_get_typedarray_info(env, argv[1], &tm, &mlen, &maps, &ab, &off) != napi_ok || tm != napi_uint8_array ||
+        napi_is_typedarray(env, argv[2], &is_h) != napi_ok || !is_h || napi_get_typedarray_info(env, argv[2], &th, &hlen, &words, &ab, &off) != napi_ok ||
+        th != napi_int32_array || hlen % 4 != 0 || napi_get_value_int32(env, argv[3], &stride) != napi_ok || napi_get_value_int32(env, argv[4], &planes) != napi_ok ||
+        napi_get_value_int32(env, argv[5], &elem) != napi_ok || napi_get_value_uint32(env, argv[6], &fill) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "propagateMaps(window, Uint8Array maps, Int32Array of [target, dst, fwd, bwd] per hop, stride, planes, elemBytes, fill)");
+        return nullptr;
+    }
+    struct leon_pipeline_propagate_layout lay;
+    int rc = leon_pipeline_propagate_layout(h->info.frame_width, h->info.frame_height, stride, planes, elem, &lay);
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    if (!lay.slot_bytes || mlen % lay.slot_bytes != 0 || mlen / lay.slot_bytes < 1) {
+        napi_throw_type_error(env, nullptr, "propagateMaps: maps is not a whole number of maps of planes * mh * mw * elemBytes bytes");
+        return nullptr;
+    }
+    const size_t n = hlen / 4, m = n >= 1 && n <= 65535 ? n : 1;          // (a count the library refuses allocates nothing to speak of here)
+    std::vector<leon_pipeline_propagate_hop> hops(m);
+    const int32_t* b = static_cast<const int32_t*>(words);
+    for (size_t i = 0; i < n && i < m; i++) hops[i] = leon_pipeline_propagate_hop{b[4 * i], b[4 * i + 1], b[4 * i + 2], b[4 * i + 3], {0, 0, 0, 0}};
+    leon_pipeline_propagate_config cfg{};
+    cfg.stride = stride; cfg.planes = planes; cfg.elem_bytes = elem;
+    cfg.n_slots = (int32_t)std::min<size_t>(mlen / lay.slot_bytes, 65536);
+    cfg.fill = fill;
+    cfg.slot_pitch_bytes = lay.slot_bytes; cfg.maps_bytes = mlen;
+    napi_value o, abs[2], ta[2];
+    void* data[2] = {nullptr, nullptr};
+    const size_t cells = (size_t)lay.mh * (size_t)lay.mw;
+    NAPI_OK(napi_create_object(env, &o));          // (a new ArrayBuffer is zero-filled: what a refused record keeps)
+    NAPI_OK(napi_create_arraybuffer(env, m * cells, &data[0], &abs[0]));
+    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, m * cells, abs[0], 0, &ta[0]));
+    NAPI_OK(napi_create_arraybuffer(env, m * 4, &data[1], &abs[1]));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, m, abs[1], 0, &ta[1]));
+    rc = leon_pipeline_propagate_maps(h->p, w, &cfg, hops.data(), (int32_t)std::min<size_t>(n, 65536), maps, static_cast<uint8_t*>(data[0]), static_cast<int32_t*>(data[1]));
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    NAPI_OK(napi_set_named_property(env, o, "via", ta[0]));
+    NAPI_OK(napi_set_named_property(env, o, "status", ta[1]));
+    return o;
+}
+
 // opts[name] as three floats (an array of numbers); absent: zeros
 bool get_f32x3(napi_env env, napi_value opts, const char* name, float* out)
 {
@@ -1043,7 +1101,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));

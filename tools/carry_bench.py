@@ -10,7 +10,15 @@ seeded boxes of up to --max-box pixels a side lie on the first GOP's I picture:
   host         read_motion of the P picture's record, then carry_box for the same N records
 Prints one JSON line.
 
-  python tools/carry_bench.py [--boxes 4096] [--reps 20] [--max-box 256] [--host-boxes N]"""
+--maps: dense maps instead (leon_pipeline_propagate_maps; k_propagate): a map on the first GOP's I picture propagated to the GOP's 12
+frames by propagate_maps_gop, for three shapes -- a uint8 label mask [1, 1080, 1920] at stride 1, fp16 heatmaps [17, 270, 480] at
+stride 4, fp16 features [256, 68, 120] at stride 16 -- from the enqueue to the synchronisation of the stream; the bytes the hops
+read and write a second beside the rate of a device-to-device copy of as many bytes measured in the same run; and the road a user
+had before: motion_view, a per-cell index grid built with torch ops and a gather, hop by hop in the same order, whose result is
+compared with the kernel's byte for byte.  Prints one JSON line.
+
+  python tools/carry_bench.py [--boxes 4096] [--reps 20] [--max-box 256] [--host-boxes N]
+  python tools/carry_bench.py --maps [--reps 20]"""
 import argparse
 import json
 import os
@@ -23,8 +31,103 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "mpeg1video-decoder-webgl_amd"), os.path.join(ROOT, "tools")]
 
 
+MAP_SHAPES = [("uint8 mask", 1, "uint8", 1), ("fp16 heatmaps", 4, "float16", 17), ("fp16 features", 16, "float16", 256)]          # name, stride, dtype, planes
+
+
+def torch_hop(torch, pipe, window, t, src_f, src_b, s, fill_value):
+    """one hop with torch ops alone: the target's record in place (motion_view), a per-cell index grid, a gather per direction"""
+    mv, info, _ = pipe.motion_view(window, t)
+    planes, mh, mw = (src_f if src_f is not None else src_b).shape
+    dev = mv.device
+    cy, cx = torch.meshgrid(torch.arange(mh, device=dev), torch.arange(mw, device=dev), indexing="ij")
+    kj, ki = (cy * s) >> 4, (cx * s) >> 4
+    f, v = info[kj, ki].to(torch.int32), mv[kj, ki].to(torch.int32)
+    use_f = ((f & 1) != 0) if src_f is not None else torch.zeros_like(f, dtype=torch.bool)
+    use_b = ~use_f & ((f & 2) != 0) if src_b is not None else torch.zeros_like(use_f)
+    vh, vv = torch.where(use_f, v[..., 0], v[..., 2]), torch.where(use_f, v[..., 1], v[..., 3])
+    sx = (cx + torch.div(vh + s, 2 * s, rounding_mode="floor")).clamp(0, mw - 1)
+    sy = (cy + torch.div(vv + s, 2 * s, rounding_mode="floor")).clamp(0, mh - 1)
+    at = (sy * mw + sx).reshape(-1)
+    out = torch.full((planes, mh * mw), fill_value, dtype=(src_f if src_f is not None else src_b).dtype, device=dev)
+    if src_f is not None:
+        out = torch.where(use_f.reshape(1, -1), src_f.reshape(planes, -1)[:, at], out)
+    if src_b is not None:
+        out = torch.where(use_b.reshape(1, -1), src_b.reshape(planes, -1)[:, at], out)
+    return out.reshape(planes, mh, mw)
+
+
+def maps_bench(a, pipe, window, frames):
+    import torch
+    import leon_ctypes as L
+    fw, fh = pipe.info.frame_width, pipe.info.frame_height
+    src = [i for i, f in enumerate(frames) if f["type"] == L.PIC_I][0]
+    rows = pipe.gop_frames(window, src)
+    levels, unreachable = L.propagate_plan(pipe.carry_refs(window), frames, src)
+    hops = sum(len(x) for x in levels)
+    med = statistics.median
+    result = {"bench": "propagate", "frame": [fw, fh], "window_frames": len(frames), "gop_frames": len(rows), "gop_levels": len(levels), "gop_hops": hops,
+              "gop_unreachable": len(unreachable), "reps": a.reps, "shapes": []}
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        for name, s, dtype, planes in MAP_SHAPES:
+            lay = L.propagate_layout(fw, fh, s, planes, 1 if dtype == "uint8" else 2)
+            bits = torch.uint8 if dtype == "uint8" else torch.int16
+            g = torch.Generator(device="cuda").manual_seed(s)
+            m = torch.randint(0, 256 if dtype == "uint8" else 32767, (planes, lay.mh, lay.mw), generator=g, device="cuda", dtype=bits)
+            m = m if dtype == "uint8" else m.view(torch.float16)
+            gop_us, enqueue_us = [], []
+            for i in range(a.reps + 2):          # (the first two: the scratch, the stream and torch's allocator warm up)
+                st.synchronize()
+                t0 = time.perf_counter()
+                maps, via, status = pipe.propagate_maps_gop(window, m, src, s, fill=0)
+                t1 = time.perf_counter()
+                st.synchronize()
+                t2 = time.perf_counter()
+                if i >= 2:
+                    gop_us.append((t2 - t0) * 1e6)
+                    enqueue_us.append((t1 - t0) * 1e6)
+            # the bytes the hops move: every hop reads a map's worth of source cells and the record, writes a map and its via bytes
+            moved = hops * (2 * lay.slot_bytes + lay.mh * lay.mw)
+            a_, b_ = torch.empty(hops * lay.slot_bytes, dtype=torch.uint8, device="cuda"), torch.empty(hops * lay.slot_bytes, dtype=torch.uint8, device="cuda")
+            copy_us = []
+            for i in range(a.reps + 2):
+                st.synchronize()
+                t0 = time.perf_counter()
+                b_.copy_(a_)
+                st.synchronize()
+                if i >= 2:
+                    copy_us.append((time.perf_counter() - t0) * 1e6)
+            # the road there was, in the levels' order, and its result against the kernel's
+            slot = {f: i for i, f in enumerate(rows)}
+            mb = m.view(bits)
+            torch_us = []
+            for i in range(min(a.reps, 5) + 1):
+                st.synchronize()
+                t0 = time.perf_counter()
+                ref = {src: mb}
+                for level in levels:
+                    for t, f, b in level:
+                        ref[t] = torch_hop(torch, pipe, window, t, ref.get(f) if f >= 0 else None, ref.get(b) if b >= 0 else None, s, 0)
+                st.synchronize()
+                if i >= 1:
+                    torch_us.append((time.perf_counter() - t0) * 1e6)
+            got = maps.view(bits)
+            same = all(torch.equal(got[slot[t]], ref[t]) for t in ref)
+            if not same or int((status != 0).sum().item()) != 0:
+                raise RuntimeError("%s: the kernel and the torch road disagree" % name)
+            result["shapes"].append({"name": name, "shape": [planes, lay.mh, lay.mw], "stride": s, "dtype": dtype, "fast_path": lay.fast_path,
+                                     "planes_per_group": lay.planes_per_group, "slot_bytes": lay.slot_bytes,
+                                     "gop_us": round(med(gop_us), 1), "gop_min_us": round(min(gop_us), 1), "gop_enqueue_us": round(med(enqueue_us), 1),
+                                     "bytes_moved": moved, "gop_gb_per_s": round(moved / med(gop_us) / 1e3, 1),
+                                     "copy_us": round(med(copy_us), 1), "copy_gb_per_s": round(2 * hops * lay.slot_bytes / med(copy_us) / 1e3, 1),
+                                     "torch_road_us": round(med(torch_us), 1), "kernel_equals_torch_road": True,
+                                     "cells_moved": int((via[[slot[t] for t in ref if t != src]] != 0).sum().item())})
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--maps", action="store_true", help="dense maps (k_propagate) instead of boxes")
     ap.add_argument("--boxes", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--max-box", type=int, default=256)
@@ -48,6 +151,11 @@ def main():
         if not delivered.wait(300):
             raise RuntimeError("no window was delivered: %s" % (pipe.error,))
         window, frames = held["window"], held["frames"]
+        if a.maps:
+            maps_bench(a, pipe, window, frames)
+            pipe.release_window(window)
+            pipe.wait()
+            return
         fw, fh, n = pipe.info.frame_width, pipe.info.frame_height, len(frames)
         src = [i for i, f in enumerate(frames) if f["type"] == L.PIC_I][0]
         fwd, bwd = pipe.carry_refs(window)
