@@ -443,6 +443,33 @@ int leon_pipeline_motion_layout(int32_t mb_width, int32_t mb_height, struct leon
  * (I: all four; P: mb_dir and mv_bwd); refuses another type, a size outside 1 .. 256, a missing map, a null record */
 int leon_pipeline_motion_record(int32_t type, int32_t mb_width, int32_t mb_height, const uint8_t* repadd, const uint8_t* mb_dir,
                                 const int16_t* mv_fwd, const int16_t* mv_bwd, void* record);
+/* A diagnostic in the manner of leon_pipeline_carry_device: k_motion on maps the CALLER supplies, with memory of its own on device_id's
+ * null stream, synchronous, everything in host memory.  pictures[i] is a picture of mb_width x mb_height macroblocks: its type and its
+ * maps as leon_pipeline_motion_record takes them (those the type does not have are not read and may be NULL).  On the device every map
+ * lies in a piece of its own, padded to a multiple of 256 bytes as the pipeline's arenas pad it (a byte a macroblock: pad256(mbs); a
+ * vector map: pad256(4 * mbs)), every padding byte = pad_byte.  Frame i is a record of pictures[frames[i].picture], written to
+ * ring + frames[i].ring * record_pitch; several frames may name one picture, no two one record.  `ring` is ring_frames * record_pitch
+ * bytes (leon_pipeline_motion_layout), goes up and comes back whole: every byte the kernel leaves alone is still the caller's.  The
+ * frames go through the pipeline's own launch, more than 65535 of them in more than one.
+ * Refused (LEON_ERR_INVALID, nothing launched, `ring` untouched): a null pictures, frames or ring, a size outside 1 .. 256, n_pictures
+ * or ring_frames outside 1 .. LEON_MOTION_KERNEL_MAX_FRAMES, n_frames outside 1 .. ring_frames, pad_byte outside 0 .. 255, a type
+ * outside LEON_PIC_I / _P / _B, a non-zero reserved word, a missing map of a type that has it, a picture index outside
+ * 0 .. n_pictures - 1, a ring index outside 0 .. ring_frames - 1, two frames with one ring index. */
+#define LEON_MOTION_KERNEL_MAX_FRAMES (1 << 20)
+typedef struct leon_pipeline_motion_picture {
+    int32_t type;               /* LEON_PIC_I / _P / _B */
+    int32_t reserved0;          /* 0 */
+    const uint8_t* repadd;      /* [mbs]; P, B */
+    const uint8_t* mb_dir;      /* [mbs]; B */
+    const int16_t* mv_fwd;      /* [mbs][2]; P, B */
+    const int16_t* mv_bwd;      /* [mbs][2]; B */
+} leon_pipeline_motion_picture;         /* 40 bytes */
+typedef struct leon_pipeline_motion_kernel_frame {
+    int32_t picture;            /* index into pictures */
+    int32_t ring;               /* index of the frame's record in the ring */
+} leon_pipeline_motion_kernel_frame;    /* 8 bytes */
+int leon_pipeline_motion_kernel(int32_t device_id, int32_t mb_width, int32_t mb_height, const leon_pipeline_motion_picture* pictures, int32_t n_pictures,
+                                const leon_pipeline_motion_kernel_frame* frames, int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring);
 /* the layout of this pipeline's records; LEON_ERR_INVALID for a pipeline without LEON_PIPELINE_OUTPUT_MOTION */
 int leon_pipeline_get_motion_layout(leon_pipeline* p, struct leon_pipeline_motion_layout* out);
 /* the motion records of a delivered, not yet released window: out[i] belongs to frames[i], n = the window's n_frames.  May be called

@@ -1321,6 +1321,16 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
 // staged in the ring entry's part of the mirror and go up with one copy.
 static_assert(sizeof(leon::MotionDesc) == 48, "a descriptor is 12 dwords");
 static_assert(sizeof(leon_pipeline_motion_frame) == 32 && sizeof(struct leon_pipeline_motion_layout) == 64, "include/leon_pipeline.h states the sizes");
+// k_motion over n descriptors in device memory, frame i of them in workgroup i: the one place that cuts them into launches
+// (launch_motion for a window, motion_kernel for a caller's maps)
+void motion_launch(const leon::MotionDesc* descs, size_t n, uint8_t* ring, const leon::MotionLayout& lay, hipStream_t stream)
+{
+    for (size_t at = 0; at < n; at += 65535) {
+        const dim3 grid(1, (unsigned)std::min<size_t>(65535, n - at)), block(leon::kRgbaBlock);
+        hipLaunchKernelGGL(leon::k_motion, grid, block, 0, stream, descs + at, ring, lay);
+    }
+}
+
 int launch_motion(leon_pipeline* p, const PipeWindow* w)
 {
     const size_t n = w->motion_descs.size();
@@ -1335,10 +1345,7 @@ int launch_motion(leon_pipeline* p, const PipeWindow* w)
         h[i] = d;
     }
     HIP_TRY(hipMemcpyAsync(dv, h, n * sizeof(leon::MotionDesc), hipMemcpyHostToDevice, p->dec->stream));
-    for (size_t at = 0; at < n; at += 65535) {
-        const dim3 grid(1, (unsigned)std::min<size_t>(65535, n - at)), block(leon::kRgbaBlock);
-        hipLaunchKernelGGL(leon::k_motion, grid, block, 0, p->dec->stream, (const leon::MotionDesc*)(dv + at), (uint8_t*)p->d_motion, p->motion_lay);
-    }
+    motion_launch(dv, n, p->d_motion, p->motion_lay, p->dec->stream);
     HIP_TRY(hipGetLastError());
     return LEON_OK;
 }
@@ -1367,6 +1374,86 @@ int motion_record_host(int32_t type, int32_t mbw, int32_t mbh, const uint8_t* re
         rec[L.info_offset + k] = (uint8_t)info;
     }
     memcpy(rec + L.summary_offset, s, 32);
+    return LEON_OK;
+}
+
+// k_motion on maps the caller supplies (leon_pipeline_motion_kernel): memory of its own, the null stream.  One device allocation
+// [descriptors | maps | ring]: every map of every picture in a piece of its own, padded as MapLayout pads it (mpad, vpad) with
+// pad_byte; the caller's ring goes up and comes back whole.
+static_assert(sizeof(leon_pipeline_motion_picture) == 40 && sizeof(leon_pipeline_motion_kernel_frame) == 8, "include/leon_pipeline.h states the sizes");
+int motion_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipeline_motion_picture* pics, int32_t n_pics, const leon_pipeline_motion_kernel_frame* frames,
+                  int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring)
+{
+    if (!pics || !frames || !ring) return fail(LEON_ERR_INVALID, "null argument");
+    if (mbw < 1 || mbw > leon::kMotionMaxMb || mbh < 1 || mbh > leon::kMotionMaxMb)
+        return fail(LEON_ERR_INVALID, "motion kernel: %d x %d macroblocks (1 .. %d each)", mbw, mbh, leon::kMotionMaxMb);
+    if (n_pics < 1 || n_pics > LEON_MOTION_KERNEL_MAX_FRAMES) return fail(LEON_ERR_INVALID, "motion kernel: %d pictures (1 .. %d)", n_pics, LEON_MOTION_KERNEL_MAX_FRAMES);
+    if (ring_frames < 1 || ring_frames > LEON_MOTION_KERNEL_MAX_FRAMES)
+        return fail(LEON_ERR_INVALID, "motion kernel: a ring of %d records (1 .. %d)", ring_frames, LEON_MOTION_KERNEL_MAX_FRAMES);
+    if (n_frames < 1 || n_frames > ring_frames) return fail(LEON_ERR_INVALID, "motion kernel: %d frames (1 .. the ring's %d records)", n_frames, ring_frames);
+    if (pad_byte < 0 || pad_byte > 255) return fail(LEON_ERR_INVALID, "motion kernel: pad_byte %d (0 .. 255)", pad_byte);
+    const MapLayout M = map_layout((size_t)mbw * (size_t)mbh, 0);
+    size_t maps_bytes = 0;
+    for (int32_t i = 0; i < n_pics; i++) {
+        const leon_pipeline_motion_picture& q = pics[i];
+        if (q.type != LEON_PIC_I && q.type != LEON_PIC_P && q.type != LEON_PIC_B) return fail(LEON_ERR_INVALID, "motion kernel: picture %d has type %d", i, q.type);
+        if (q.reserved0) return fail(LEON_ERR_INVALID, "motion kernel: a reserved word of picture %d is not 0", i);
+        if ((q.type != LEON_PIC_I && (!q.repadd || !q.mv_fwd)) || (q.type == LEON_PIC_B && (!q.mb_dir || !q.mv_bwd)))
+            return fail(LEON_ERR_INVALID, "motion kernel: picture %d (type %d) lacks a map", i, q.type);
+        maps_bytes += q.type == LEON_PIC_I ? 0 : (q.type == LEON_PIC_P ? 1 : 2) * (M.mpad + M.vpad);
+    }
+    {
+        std::vector<bool> named((size_t)ring_frames, false);
+        for (int32_t i = 0; i < n_frames; i++) {
+            const leon_pipeline_motion_kernel_frame& f = frames[i];
+            if (f.picture < 0 || f.picture >= n_pics) return fail(LEON_ERR_INVALID, "motion kernel: frame %d names picture %d of %d", i, f.picture, n_pics);
+            if (f.ring < 0 || f.ring >= ring_frames) return fail(LEON_ERR_INVALID, "motion kernel: frame %d names record %d of a ring of %d", i, f.ring, ring_frames);
+            if (named[(size_t)f.ring]) return fail(LEON_ERR_INVALID, "motion kernel: frame %d names record %d, which an earlier frame names", i, f.ring);
+            named[(size_t)f.ring] = true;
+        }
+    }
+    const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+    const size_t descs_bytes = pad256((size_t)n_frames * sizeof(leon::MotionDesc)), ring_bytes = (size_t)ring_frames * L.record_pitch;
+    const size_t bytes = descs_bytes + maps_bytes + ring_bytes;
+    HIP_TRY(hipSetDevice(device_id));
+    DevBuf<uint8_t> d;
+    if (!d.alloc(bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "motion kernel: %zu bytes of device memory", bytes); }
+    uint8_t *d_maps = d + descs_bytes, *d_ring = d_maps + maps_bytes;
+    // the maps as the device will hold them, staged on the host: the pad byte everywhere, then each map into its piece
+    std::vector<uint8_t> maps(maps_bytes, (uint8_t)pad_byte);
+    std::vector<leon::MotionDesc> pic_descs((size_t)n_pics);
+    size_t at = 0;
+    auto place = [&](const void* src, size_t n, size_t padded) {
+        memcpy(maps.data() + at, src, n);
+        const uint8_t* dev = d_maps + at;
+        at += padded;
+        return dev;
+    };
+    for (int32_t i = 0; i < n_pics; i++) {
+        const leon_pipeline_motion_picture& q = pics[i];
+        leon::MotionDesc& D = pic_descs[(size_t)i];
+        D = leon::MotionDesc{};
+        D.type = q.type;
+        if (q.type != LEON_PIC_I) {
+            D.repadd = place(q.repadd, M.mbs, M.mpad);
+            D.mv_fwd = reinterpret_cast<const uint32_t*>(place(q.mv_fwd, M.mbs * 4, M.vpad));
+        }
+        if (q.type == LEON_PIC_B) {
+            D.mb_dir = place(q.mb_dir, M.mbs, M.mpad);
+            D.mv_bwd = reinterpret_cast<const uint32_t*>(place(q.mv_bwd, M.mbs * 4, M.vpad));
+        }
+    }
+    std::vector<leon::MotionDesc> descs((size_t)n_frames);
+    for (int32_t i = 0; i < n_frames; i++) {
+        descs[(size_t)i] = pic_descs[(size_t)frames[i].picture];
+        descs[(size_t)i].frame = (uint32_t)frames[i].ring;
+    }
+    HIP_TRY(hipMemcpy(d, descs.data(), descs.size() * sizeof(leon::MotionDesc), hipMemcpyHostToDevice));
+    if (maps_bytes) HIP_TRY(hipMemcpy(d_maps, maps.data(), maps_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ring, ring, ring_bytes, hipMemcpyHostToDevice));
+    motion_launch(reinterpret_cast<const leon::MotionDesc*>(d.get()), (size_t)n_frames, d_ring, L, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(ring, d_ring, ring_bytes, hipMemcpyDeviceToHost));      // (the copy waits: nothing in flight reads d when it goes)
     return LEON_OK;
 }
 
@@ -3098,6 +3185,12 @@ int leon_pipeline_motion_record(int32_t type, int32_t mb_width, int32_t mb_heigh
                                 const int16_t* mv_fwd, const int16_t* mv_bwd, void* record)
 {
     return motion_record_host(type, mb_width, mb_height, repadd, mb_dir, mv_fwd, mv_bwd, record);
+}
+
+int leon_pipeline_motion_kernel(int32_t device_id, int32_t mb_width, int32_t mb_height, const leon_pipeline_motion_picture* pictures, int32_t n_pictures,
+                                const leon_pipeline_motion_kernel_frame* frames, int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring)
+{
+    return motion_kernel(device_id, mb_width, mb_height, pictures, n_pictures, frames, n_frames, ring_frames, pad_byte, ring);
 }
 
 int leon_pipeline_get_motion_layout(leon_pipeline* p, struct leon_pipeline_motion_layout* out)

@@ -46,7 +46,7 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_warp_regions_check", "leon_pipeline_warp_region_status", "leon_pipeline_warp_from_matrix", "leon_pipeline_warp_from_rotated_box",
     "leon_pipeline_warp_regions", "leon_pipeline_read_warp_regions", "leon_pipeline_warp_regions_device",
     "leon_pipeline_motion_layout", "leon_pipeline_motion_record", "leon_pipeline_get_motion_layout", "leon_pipeline_window_motion",
-    "leon_pipeline_read_motion",
+    "leon_pipeline_read_motion", "leon_pipeline_motion_kernel",
     "leon_pipeline_carry_refs", "leon_pipeline_carry_record", "leon_pipeline_get_carry_refs", "leon_pipeline_carry_regions_device",
     "leon_pipeline_carry_regions", "leon_pipeline_carry_device",
     "leon_pipeline_propagate_layout", "leon_pipeline_propagate_record", "leon_pipeline_propagate_maps_device", "leon_pipeline_propagate_maps",
@@ -413,6 +413,10 @@ class PipelineMotionFrame(C.Structure):
     _fields_ = [("record", C.c_void_p), ("fwd_gop", C.c_uint64), ("fwd_display", C.c_int32), ("bwd_display", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class PipelineMotionPicture(C.Structure):
+    _fields_ = [("type", C.c_int32), ("reserved0", C.c_int32), ("repadd", C.c_void_p), ("mb_dir", C.c_void_p), ("mv_fwd", C.c_void_p), ("mv_bwd", C.c_void_p)]
+
+
 class PipelineFrame(C.Structure):
     _fields_ = [("gop", C.c_uint64), ("display_index", C.c_int32), ("type", C.c_int32), ("ts_ms", C.c_double),
                 ("rgba", C.c_void_p), ("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("a", C.c_void_p)]
@@ -555,6 +559,8 @@ def load():
         lib.leon_pipeline_get_motion_layout.argtypes = [C.c_void_p, C.POINTER(PipelineMotionLayout)]
         lib.leon_pipeline_window_motion.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PipelineMotionFrame), C.c_int32]
         lib.leon_pipeline_read_motion.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_motion_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineMotionPicture), C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_void_p]
     if hasattr(lib, "leon_pipeline_carry_regions"):
         P = C.POINTER
         lib.leon_pipeline_carry_refs.argtypes = [P(PipelineFrame), P(PipelineMotionFrame), C.c_int32, C.c_void_p, C.c_void_p]
@@ -682,6 +688,31 @@ def motion_from_maps(type, mbw, mbh, repadd=None, mb_dir=None, mv_fwd=None, mv_b
     summary = np.array([int(((info & 1) != 0).sum()), int(((info & 2) != 0).sum()), int(((info & 4) != 0).sum()), int(mv.any(axis=1).sum()),
                         int(a[:, 0].sum()), int(a[:, 1].sum()), int(a[:, 2].sum()), int(a[:, 3].sum())], dtype=np.uint32)
     return mv.reshape(int(mbh), int(mbw), 4), info.reshape(int(mbh), int(mbw)), summary
+
+
+def motion_kernel(mbw, mbh, pictures, frames, ring_frames=None, pad_byte=0, fill=0xA5, ring=None, device_id=0, n_pictures=None, n_frames=None):
+    """leon_pipeline_motion_kernel: k_motion on maps the caller supplies.  pictures = [(type, repadd, mb_dir, mv_fwd, mv_bwd), ...] (maps
+    as motion_record takes them, None where the type has none); frames = [(picture, ring index), ...] or an integer array [n, 2];
+    every map's padding on the device holds pad_byte.  Returns the ring, uint8 [ring_frames, record_pitch], as it came back: it went
+    up holding `fill` in every byte -- or is the caller's `ring` (a contiguous uint8 array), written in place.  pictures, frames None:
+    a null pointer; n_pictures, n_frames: the counts handed to the library when they are to differ from the lists' lengths."""
+    if ring is None:
+        ring = np.full((int(ring_frames), int(motion_layout(mbw, mbh).record_pitch)), int(fill), dtype=np.uint8)
+    assert ring.dtype == np.uint8 and ring.flags.c_contiguous and ring.flags.writeable
+    keep, pics = [], None
+    if pictures is not None:
+        pics = (PipelineMotionPicture * max(1, len(pictures)))()
+        for i, (t, *maps) in enumerate(pictures):
+            q = pics[i]
+            arrs = [None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in zip(maps, (np.uint8, np.uint8, np.int16, np.int16))]
+            keep.append(arrs)
+            q.type = int(t)
+            q.repadd, q.mb_dir, q.mv_fwd, q.mv_bwd = [None if a is None else a.ctypes.data for a in arrs]
+    fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32).reshape(-1, 2)
+    _chk(load().leon_pipeline_motion_kernel(int(device_id), int(mbw), int(mbh), pics, (0 if pictures is None else len(pictures)) if n_pictures is None else int(n_pictures),
+                                            None if fr is None or not len(fr) else fr.ctypes.data, (0 if fr is None else len(fr)) if n_frames is None else int(n_frames),
+                                            len(ring) if ring_frames is None else int(ring_frames), int(pad_byte), ring.ctypes.data))
+    return ring
 
 
 def _floor_div(a, b):

@@ -52,12 +52,13 @@ def same(a, b):
 def test_symbols_and_struct_sizes():
     lib = L.load()
     for n in ("leon_pipeline_motion_layout", "leon_pipeline_motion_record", "leon_pipeline_get_motion_layout", "leon_pipeline_window_motion",
-              "leon_pipeline_read_motion"):
+              "leon_pipeline_read_motion", "leon_pipeline_motion_kernel"):
         assert hasattr(lib, n) and n in L.PIPELINE_SYMBOLS
     assert L.PIPELINE_OUTPUT_MOTION == 1 << 5
     assert C.sizeof(L.PipelineMotionFrame) == 32 and L.PipelineMotionFrame.fwd_gop.offset == 8 and L.PipelineMotionFrame.fwd_display.offset == 16
     assert L.PipelineMotionFrame.bwd_display.offset == 20
     assert C.sizeof(L.PipelineMotionLayout) == 64
+    assert C.sizeof(L.PipelineMotionPicture) == 40 and L.PipelineMotionPicture.repadd.offset == 8 and L.PipelineMotionPicture.mv_bwd.offset == 32
 
 
 def test_structs_have_the_size_the_c_compiler_gives_them(tmp_path):
@@ -65,11 +66,12 @@ def test_structs_have_the_size_the_c_compiler_gives_them(tmp_path):
     import subprocess
     from helpers import ROOT
     src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include "leon_pipeline.h"\nint main(void){printf("%zu %zu %d\\n", sizeof(leon_pipeline_motion_frame), '
-                   'sizeof(struct leon_pipeline_motion_layout), LEON_PIPELINE_OUTPUT_MOTION);return 0;}\n')
+    src.write_text('#include <stdio.h>\n#include "leon_pipeline.h"\nint main(void){printf("%zu %zu %d %zu %zu\\n", sizeof(leon_pipeline_motion_frame), '
+                   'sizeof(struct leon_pipeline_motion_layout), LEON_PIPELINE_OUTPUT_MOTION, sizeof(leon_pipeline_motion_picture), '
+                   'sizeof(leon_pipeline_motion_kernel_frame));return 0;}\n')
     exe = tmp_path / "sizes"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    assert subprocess.check_output([str(exe)], text=True).split() == ["32", "64", "32"]
+    assert subprocess.check_output([str(exe)], text=True).split() == ["32", "64", "32", "40", "8"]
 
 
 @pytest.mark.parametrize("mbw,mbh", [(6, 4), (37, 2), (13, 7), (22, 15), (1, 1), (256, 256)])
