@@ -1316,6 +1316,22 @@ int launch_tensors(leon_pipeline* p, const PipeWindow* w)
     return LEON_OK;
 }
 
+// ---- the refusals that several motion and region calls state, each under the caller's own prefix ----------------------------------------
+int record_count_check(const char* who, const char* noun, int32_t n)
+{
+    return n < 1 || n > 65535 ? fail(LEON_ERR_INVALID, "%s: %d %s (a call takes 1 .. 65535)", who, n, noun) : LEON_OK;
+}
+int mb_grid_check(const char* who, int32_t mbw, int32_t mbh)
+{
+    if (mbw >= 1 && mbw <= leon::kMotionMaxMb && mbh >= 1 && mbh <= leon::kMotionMaxMb) return LEON_OK;
+    return fail(LEON_ERR_INVALID, "%s: %d x %d macroblocks (1 .. %d each)", who, mbw, mbh, leon::kMotionMaxMb);
+}
+// a picture of `type` has the maps k_motion reads of it
+bool motion_maps_present(int32_t type, const void* repadd, const void* mb_dir, const void* mv_fwd, const void* mv_bwd)
+{
+    return (type == LEON_PIC_I || (repadd && mv_fwd)) && (type != LEON_PIC_B || (mb_dir && mv_bwd));
+}
+
 // output MOTION: the window's frames -> their motion records, one launch on the decoder's stream behind the last level and in front of
 // the window's event (at most 65535 frames per launch: blockIdx.y), while the maps are still in the GOPs' arenas.  The descriptors are
 // staged in the ring entry's part of the mirror and go up with one copy.
@@ -1340,7 +1356,7 @@ int launch_motion(leon_pipeline* p, const PipeWindow* w)
     leon::MotionDesc* dv = p->motion_descs.dev() + (size_t)w->ring * entry;
     for (size_t i = 0; i < n; i++) {
         const leon::MotionDesc& d = w->motion_descs[i];
-        if ((d.type != LEON_PIC_I && (!d.repadd || !d.mv_fwd)) || (d.type == LEON_PIC_B && (!d.mb_dir || !d.mv_bwd)))
+        if (!motion_maps_present(d.type, d.repadd, d.mb_dir, d.mv_fwd, d.mv_bwd))
             return fail(LEON_ERR_INVALID, "motion: frame %zu of window %lld (type %d) lacks a map", i, (long long)w->id, d.type);
         h[i] = d;
     }
@@ -1356,9 +1372,8 @@ int motion_record_host(int32_t type, int32_t mbw, int32_t mbh, const uint8_t* re
 {
     if (!record) return fail(LEON_ERR_INVALID, "null argument");
     if (type != LEON_PIC_I && type != LEON_PIC_P && type != LEON_PIC_B) return fail(LEON_ERR_INVALID, "motion record: picture type %d", type);
-    if (mbw < 1 || mbw > leon::kMotionMaxMb || mbh < 1 || mbh > leon::kMotionMaxMb)
-        return fail(LEON_ERR_INVALID, "motion record: %d x %d macroblocks (1 .. %d each)", mbw, mbh, leon::kMotionMaxMb);
-    if ((type != LEON_PIC_I && (!repadd || !mv_fwd)) || (type == LEON_PIC_B && (!mb_dir || !mv_bwd)))
+    if (const int rc = mb_grid_check("motion record", mbw, mbh); rc != LEON_OK) return rc;
+    if (!motion_maps_present(type, repadd, mb_dir, mv_fwd, mv_bwd))
         return fail(LEON_ERR_INVALID, "motion record: a picture of type %d without one of its maps", type);
     const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
     uint8_t* rec = static_cast<uint8_t*>(record);
@@ -1385,8 +1400,7 @@ int motion_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipeli
                   int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring)
 {
     if (!pics || !frames || !ring) return fail(LEON_ERR_INVALID, "null argument");
-    if (mbw < 1 || mbw > leon::kMotionMaxMb || mbh < 1 || mbh > leon::kMotionMaxMb)
-        return fail(LEON_ERR_INVALID, "motion kernel: %d x %d macroblocks (1 .. %d each)", mbw, mbh, leon::kMotionMaxMb);
+    if (const int rc = mb_grid_check("motion kernel", mbw, mbh); rc != LEON_OK) return rc;
     if (n_pics < 1 || n_pics > LEON_MOTION_KERNEL_MAX_FRAMES) return fail(LEON_ERR_INVALID, "motion kernel: %d pictures (1 .. %d)", n_pics, LEON_MOTION_KERNEL_MAX_FRAMES);
     if (ring_frames < 1 || ring_frames > LEON_MOTION_KERNEL_MAX_FRAMES)
         return fail(LEON_ERR_INVALID, "motion kernel: a ring of %d records (1 .. %d)", ring_frames, LEON_MOTION_KERNEL_MAX_FRAMES);
@@ -1398,7 +1412,7 @@ int motion_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipeli
         const leon_pipeline_motion_picture& q = pics[i];
         if (q.type != LEON_PIC_I && q.type != LEON_PIC_P && q.type != LEON_PIC_B) return fail(LEON_ERR_INVALID, "motion kernel: picture %d has type %d", i, q.type);
         if (q.reserved0) return fail(LEON_ERR_INVALID, "motion kernel: a reserved word of picture %d is not 0", i);
-        if ((q.type != LEON_PIC_I && (!q.repadd || !q.mv_fwd)) || (q.type == LEON_PIC_B && (!q.mb_dir || !q.mv_bwd)))
+        if (!motion_maps_present(q.type, q.repadd, q.mb_dir, q.mv_fwd, q.mv_bwd))
             return fail(LEON_ERR_INVALID, "motion kernel: picture %d (type %d) lacks a map", i, q.type);
         maps_bytes += q.type == LEON_PIC_I ? 0 : (q.type == LEON_PIC_P ? 1 : 2) * (M.mpad + M.vpad);
     }
@@ -1460,8 +1474,7 @@ int motion_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipeli
 int motion_layout_host(int32_t mbw, int32_t mbh, struct leon_pipeline_motion_layout* out)
 {
     if (!out) return fail(LEON_ERR_INVALID, "null argument");
-    if (mbw < 1 || mbw > leon::kMotionMaxMb || mbh < 1 || mbh > leon::kMotionMaxMb)
-        return fail(LEON_ERR_INVALID, "motion layout: %d x %d macroblocks (1 .. %d each)", mbw, mbh, leon::kMotionMaxMb);
+    if (const int rc = mb_grid_check("motion layout", mbw, mbh); rc != LEON_OK) return rc;
     const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
     memset(out, 0, sizeof(*out));
     out->mb_width = mbw; out->mb_height = mbh; out->mbs = (int32_t)L.mbs;
@@ -1506,8 +1519,7 @@ int regions_config_check(int32_t fw, int32_t fh, int32_t n_frames, int32_t n, co
     if (cfg->out_height < 1 || cfg->out_height > 4096) return fail(LEON_ERR_INVALID, "regions config: out_height %d is outside 1 .. 4096", cfg->out_height);
     if (!resize_filter_max_taps(cfg->filter)) return fail(LEON_ERR_INVALID, "regions config: filter %d (LEON_RESIZE_TRIANGLE and LEON_RESIZE_BICUBIC are the filters)", cfg->filter);
     if (fw < 1 || fh < 1 || n_frames < 0) return fail(LEON_ERR_INVALID, "regions: %d frames of %d x %d", n_frames, fw, fh);
-    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "regions: %d regions (a call takes 1 .. 65535)", n);
-    return LEON_OK;
+    return record_count_check("regions", "regions", n);
 }
 
 // The fit of a call as the kernels take it (leon_pipeline_regions_fit); every refusal of the settings is in regions_fit_check
@@ -1586,19 +1598,31 @@ int regions_reserve(leon_pipeline* p, size_t upload_bytes, size_t out_bytes)
     return LEON_OK;
 }
 
-// the ring ids of a delivered window's frames
-int regions_window_ids(leon_pipeline* p, int64_t window, std::vector<uint32_t>* ids)
+// fn(w) on a window that is out for delivery and was delivered whole: the one lookup of the region, carry and propagate calls
+template <class Fn>
+int window_delivered(leon_pipeline* p, int64_t window, Fn fn)
 {
     int status = LEON_OK;
     const bool out = p->flow.with_delivered(window, [&](const PipeWindow& w) {
-        if ((status = w.status) != LEON_OK) return;
-        const uint32_t base = (uint32_t)((size_t)w.ring * p->W * p->max_pics);
-        ids->reserve(w.frame_ids.size());
-        for (uint32_t id : w.frame_ids) ids->push_back(base + id);
+        if ((status = w.status) == LEON_OK) fn(w);
     });
     if (!out) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
     if (status != LEON_OK) return fail(LEON_ERR_INVALID, "window %lld was delivered with an error (status %d)", (long long)window, status);
     return LEON_OK;
+}
+// the ring ids of a delivered window's frames
+int regions_window_ids(leon_pipeline* p, int64_t window, std::vector<uint32_t>* ids)
+{
+    return window_delivered(p, window, [&](const PipeWindow& w) {
+        const uint32_t base = (uint32_t)((size_t)w.ring * p->W * p->max_pics);
+        ids->reserve(w.frame_ids.size());
+        for (uint32_t id : w.frame_ids) ids->push_back(base + id);
+    });
+}
+// ... and its table of ring ids and references, as k_carry and k_propagate take it
+int carry_window_table(leon_pipeline* p, int64_t window, std::vector<uint32_t>* table)
+{
+    return window_delivered(p, window, [&](const PipeWindow& w) { *table = w.carry_table; });
 }
 
 // ---- what the four roads share (stretch / fit and warp, each from host records and from device records) --------------------------
@@ -1807,33 +1831,36 @@ int boxes_call_check(const char* who, const void* regions, bool reserved_set, co
     return regions_out_check(who, device_out, out_pitch, region_bytes, pitch);
 }
 
-// The bracket of a device road's enqueue on `st`, regions_mu held.  boxes_begin: the scratch (boxes_dev) at `scratch_bytes` or more, `st`
-// behind the call before's use of it (boxes_done), the window's frame ids uploaded to its start (*d_ids) with the staging entry's event
-// recorded behind the upload.  Once it returns LEON_OK the stream holds work and the road goes on to boxes_end whatever *he says: it
-// enqueues its kernels while *he is hipSuccess and folds hipGetLastError() into it.
-int boxes_begin(leon_pipeline* p, hipStream_t st, const std::vector<uint32_t>& ids, size_t scratch_bytes, uint32_t** d_ids, hipError_t* he)
+// The bracket of a device road's enqueue, regions_mu held in `call`: on the caller's stream, or (NULL) on the regions stream with a wait at
+// the end.  The scratch (boxes_dev) at `scratch_bytes` or more, the stream behind the call before's use of it (boxes_done), `table` -- the
+// window's frame ids, or its carry table -- uploaded to the scratch's start with the staging entry's event recorded behind the upload; then
+// launch(st, d_table), which only enqueues, while nothing has failed, and the runtime's last error folded in.  From the upload on the stream
+// holds work, so whatever failed since, boxes_done is recorded to keep the scratch covered; the lock is dropped (regions_mu is held while
+// enqueuing only); then the road's error, and the wait.
+template <class Launch>
+int boxes_run(leon_pipeline* p, void* caller_stream, std::unique_lock<std::mutex>& call, const std::vector<uint32_t>& table, size_t scratch_bytes, Launch launch)
 {
     int rc;
+    hipStream_t st;
+    if ((rc = regions_call_stream(p, caller_stream, &st)) != LEON_OK) return rc;
     if (!p->boxes_done && !p->boxes_done.create(hipEventDisableTiming)) return refused(LEON_ERR_HIP, "hipEventCreate");
     if ((rc = boxes_reserve(p, scratch_bytes)) != LEON_OK) return rc;
-    uint32_t* ids_host = nullptr;
-    if ((rc = boxes_ids_stage(p, ids, &ids_host)) != LEON_OK) return rc;
+    uint32_t* table_host = nullptr;
+    if ((rc = boxes_ids_stage(p, table, &table_host)) != LEON_OK) return rc;
     const unsigned e = (p->boxes_ids_next - 1) % leon_pipeline::kBoxesStaging;
     if (p->boxes_busy) HIP_TRY(hipStreamWaitEvent(st, p->boxes_done, 0));
-    *d_ids = reinterpret_cast<uint32_t*>(p->boxes_dev.get());
-    *he = hipMemcpyAsync(*d_ids, ids_host, ids.size() * 4, hipMemcpyHostToDevice, st);
-    if (*he == hipSuccess && (*he = hipEventRecord(p->boxes_ids_done[e], st)) == hipSuccess) p->boxes_ids_busy[e] = true;
-    return LEON_OK;
-}
-// boxes_end: boxes_done recorded whatever happened, so that the scratch stays covered; the lock dropped (regions_mu is held while
-// enqueuing only); then the road's error, and the wait where the caller gave no stream
-int boxes_end(leon_pipeline* p, hipStream_t st, hipError_t he, std::unique_lock<std::mutex>& call, bool waits)
-{
+    uint32_t* d_table = reinterpret_cast<uint32_t*>(p->boxes_dev.get());
+    hipError_t he = hipMemcpyAsync(d_table, table_host, table.size() * 4, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && (he = hipEventRecord(p->boxes_ids_done[e], st)) == hipSuccess) p->boxes_ids_busy[e] = true;
+    if (he == hipSuccess) {
+        launch(st, d_table);
+        he = hipGetLastError();
+    }
     if (hipEventRecord(p->boxes_done, st) == hipSuccess) p->boxes_busy = true;
     else if (he == hipSuccess) he = hipGetLastError();
     call.unlock();
     HIP_TRY(he);
-    if (waits) HIP_TRY(hipStreamSynchronize(st));
+    if (!caller_stream) HIP_TRY(hipStreamSynchronize(st));
     return LEON_OK;
 }
 
@@ -1866,13 +1893,6 @@ int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipelin
     if (limit < per_region) return fail(LEON_ERR_INVALID, "regions: scratch_limit_bytes %llu is below one region's %zu bytes", (unsigned long long)limit, per_region);
     const size_t chunk = (size_t)std::min<uint64_t>({(uint64_t)n, limit / per_region, (((uint64_t)1 << 32) - 1) / slot_words});
     const size_t ids_bytes = pad256(ids.size() * 4), desc_bytes = pad256(chunk * sizeof(leon::RegionDesc));
-    hipStream_t st;
-    uint32_t* d_ids = nullptr;
-    hipError_t he = hipSuccess;
-    if ((rc = regions_call_stream(p, c->stream, &st)) != LEON_OK || (rc = boxes_begin(p, st, ids, ids_bytes + desc_bytes + chunk * slot_words * 4, &d_ids, &he)) != LEON_OK)
-        return rc;
-    leon::RegionDesc* d_descs = reinterpret_cast<leon::RegionDesc*>(p->boxes_dev + ids_bytes);
-    int32_t* d_tabs = reinterpret_cast<int32_t*>(p->boxes_dev + ids_bytes + desc_bytes);
     leon::ResampleGeom G{};
     G.fw = fw; G.fh = fh; G.ow = ow; G.oh = oh;
     G.ring = ring_geom(p);
@@ -1882,19 +1902,23 @@ int resample_regions_device(leon_pipeline* p, int64_t window, const leon_pipelin
     B.slot_words = (uint32_t)slot_words;
     B.pitch_lo = (uint32_t)(pitch & 0xffffffffu); B.pitch_hi = (uint32_t)(pitch >> 32);
     const leon::BoxRecord* boxes = reinterpret_cast<const leon::BoxRecord*>(c->regions);
-    for (size_t first = 0; he == hipSuccess && first < (size_t)n; first += chunk) {
-        const unsigned m = (unsigned)std::min(chunk, (size_t)n - first);          // (blockIdx.z: m <= n <= 65535; at most 512 tile rows and 96 pad rows)
-        B.first = (uint32_t)first;
-        int32_t* status = c->device_status ? c->device_status + first : nullptr;
-        if (fit.letterbox)
-            hipLaunchKernelGGL(leon::k_fit_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, (const uint32_t*)d_ids, d_descs, d_tabs, status,
-                               device_rects ? device_rects + first * 4 : nullptr, fit.top_left ? 1 : 0, B);
-        else
-            hipLaunchKernelGGL(leon::k_box_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, (const uint32_t*)d_ids, d_descs, d_tabs, status, B);
-        regions_launch(p, st, fit, filter, G, regions_grid(ow, oh, region_bytes, fit.letterbox, m), static_cast<uint8_t*>(c->device_out), d_descs, d_tabs);
-        he = hipGetLastError();
-    }
-    return boxes_end(p, st, he, call, !c->stream);
+    // the scratch: [frame ids | a chunk's descriptors | its tables]; the chunks in turn, none behind one whose launch failed
+    return boxes_run(p, c->stream, call, ids, ids_bytes + desc_bytes + chunk * slot_words * 4, [&](hipStream_t st, uint32_t* d_ids) {
+        leon::RegionDesc* d_descs = reinterpret_cast<leon::RegionDesc*>(p->boxes_dev + ids_bytes);
+        int32_t* d_tabs = reinterpret_cast<int32_t*>(p->boxes_dev + ids_bytes + desc_bytes);
+        for (size_t first = 0; first < (size_t)n; first += chunk) {
+            const unsigned m = (unsigned)std::min(chunk, (size_t)n - first);          // (blockIdx.z: m <= n <= 65535; at most 512 tile rows and 96 pad rows)
+            B.first = (uint32_t)first;
+            int32_t* status = c->device_status ? c->device_status + first : nullptr;
+            if (fit.letterbox)
+                hipLaunchKernelGGL(leon::k_fit_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, (const uint32_t*)d_ids, d_descs, d_tabs, status,
+                                   device_rects ? device_rects + first * 4 : nullptr, fit.top_left ? 1 : 0, B);
+            else
+                hipLaunchKernelGGL(leon::k_box_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, (const uint32_t*)d_ids, d_descs, d_tabs, status, B);
+            regions_launch(p, st, fit, filter, G, regions_grid(ow, oh, region_bytes, fit.letterbox, m), static_cast<uint8_t*>(c->device_out), d_descs, d_tabs);
+            if (hipPeekAtLastError() != hipSuccess) break;          // (boxes_run asks for it)
+        }
+    });
 }
 
 // ---- rotated boxes and affine crops (leon_pipeline_warp_regions) ---------------------------------------------------------------
@@ -1917,7 +1941,7 @@ int warp_config_check(int32_t fw, int32_t fh, int32_t n_frames, int32_t n, const
     for (int i = 0; i < 3; i++)
         if (cfg->pad[i] < 0 || cfg->pad[i] > 255) return fail(LEON_ERR_INVALID, "warp config: pad value %d is %d, outside 0 .. 255", i, cfg->pad[i]);
     if (fw < 1 || fh < 1 || n_frames < 0) return fail(LEON_ERR_INVALID, "warp regions: %d frames of %d x %d", n_frames, fw, fh);
-    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "warp regions: %d regions (a call takes 1 .. 65535)", n);
+    if (const int rc = record_count_check("warp regions", "regions", n); rc != LEON_OK) return rc;
     if (pad) *pad = (uint32_t)cfg->pad[0] | ((uint32_t)cfg->pad[1] << 8) | ((uint32_t)cfg->pad[2] << 16);
     return LEON_OK;
 }
@@ -2020,16 +2044,10 @@ int warp_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_wa
     if ((rc = boxes_call_check("warp regions", c->regions, c->reserved0 || c->reserved[0] || c->reserved[1], c->device_status, c->device_out, c->out_pitch_bytes, region_bytes,
                                &pitch)) != LEON_OK)
         return rc;
-    hipStream_t st;
-    uint32_t* d_ids = nullptr;
-    hipError_t he = hipSuccess;
-    if ((rc = regions_call_stream(p, c->stream, &st)) != LEON_OK || (rc = boxes_begin(p, st, ids, pad256(ids.size() * 4), &d_ids, &he)) != LEON_OK) return rc;
-    if (he == hipSuccess) {
+    return boxes_run(p, c->stream, call, ids, pad256(ids.size() * 4), [&](hipStream_t st, uint32_t* d_ids) {
         warp_launch(p, st, reinterpret_cast<const leon::WarpRecord*>(c->regions), d_ids, (int32_t)ids.size(), n, *cfg, pad, static_cast<uint8_t*>(c->device_out), pitch,
                     c->device_status);
-        he = hipGetLastError();
-    }
-    return boxes_end(p, st, he, call, !c->stream);
+    });
 }
 
 // ---- boxes carried along the motion vectors (leon_pipeline_carry_regions) -------------------------------------------------------
@@ -2040,8 +2058,7 @@ static_assert(leon::kRegionNoReference == LEON_REGION_NO_REFERENCE, "the kernel'
 // the geometry a carry call may have: a coded grid of 1 .. 256 macroblocks an axis and a frame inside it
 int carry_geometry_check(int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames)
 {
-    if (mbw < 1 || mbw > leon::kMotionMaxMb || mbh < 1 || mbh > leon::kMotionMaxMb)
-        return fail(LEON_ERR_INVALID, "carry: %d x %d macroblocks (1 .. %d each)", mbw, mbh, leon::kMotionMaxMb);
+    if (const int rc = mb_grid_check("carry", mbw, mbh); rc != LEON_OK) return rc;
     if (fw < 1 || fw > 16 * mbw || fh < 1 || fh > 16 * mbh) return fail(LEON_ERR_INVALID, "carry: a frame of %d x %d in a grid of %d x %d macroblocks", fw, fh, mbw, mbh);
     if (n_frames < 0) return fail(LEON_ERR_INVALID, "carry: %d frames", n_frames);
     return LEON_OK;
@@ -2057,18 +2074,6 @@ void carry_launch(hipStream_t st, const leon::CarryRecord* d_recs, const leon::C
     C.info_offset = lay.info_offset; C.record_pitch = lay.record_pitch;
     const unsigned per = leon::kRgbaBlock / 64;
     hipLaunchKernelGGL(leon::k_carry, dim3(((unsigned)n + per - 1) / per), dim3(leon::kRgbaBlock), 0, st, d_recs, d_frames, d_ring, d_out, d_votes, d_status, C);
-}
-
-// the window's table (regions_window_ids' refusals)
-int carry_window_table(leon_pipeline* p, int64_t window, std::vector<uint32_t>* table)
-{
-    int status = LEON_OK;
-    const bool out = p->flow.with_delivered(window, [&](const PipeWindow& w) {
-        if ((status = w.status) == LEON_OK) *table = w.carry_table;
-    });
-    if (!out) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-    if (status != LEON_OK) return fail(LEON_ERR_INVALID, "window %lld was delivered with an error (status %d)", (long long)window, status);
-    return LEON_OK;
 }
 
 int carry_pipeline_check(const leon_pipeline* p)
@@ -2090,23 +2095,17 @@ int carry_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_c
     if ((rc = carry_window_table(p, window, &table)) != LEON_OK) return rc;
     const int32_t n = c->n;
     if (c->reserved0 || c->reserved[0] || c->reserved[1]) return fail(LEON_ERR_INVALID, "carry regions: a reserved word of the call is not 0");
-    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "carry regions: %d regions (a call takes 1 .. 65535)", n);
+    if ((rc = record_count_check("carry regions", "regions", n)) != LEON_OK) return rc;
     if (!c->regions) return fail(LEON_ERR_INVALID, "carry regions: null regions");
     if (!c->device_out) return fail(LEON_ERR_INVALID, "carry regions: null device_out");
     if (((uintptr_t)c->regions | (uintptr_t)c->device_out | (uintptr_t)c->device_votes | (uintptr_t)c->device_status) & 3u)
         return fail(LEON_ERR_INVALID, "carry regions: regions %p, device_out %p, device_votes %p, device_status %p: not all 4-byte aligned", (const void*)c->regions,
                     (void*)c->device_out, (void*)c->device_votes, (void*)c->device_status);
-    hipStream_t st;
-    uint32_t* d_table = nullptr;
-    hipError_t he = hipSuccess;
-    if ((rc = regions_call_stream(p, c->stream, &st)) != LEON_OK || (rc = boxes_begin(p, st, table, pad256(std::max<size_t>(table.size(), 1) * 4), &d_table, &he)) != LEON_OK) return rc;
-    if (he == hipSuccess) {
+    return boxes_run(p, c->stream, call, table, pad256(std::max<size_t>(table.size(), 1) * 4), [&](hipStream_t st, uint32_t* d_table) {
         carry_launch(st, reinterpret_cast<const leon::CarryRecord*>(c->regions), reinterpret_cast<const leon::CarryFrame*>(d_table), p->d_motion, p->vinfo.frame_width,
                      p->vinfo.frame_height, p->vinfo.mb_width, p->motion_lay, (int32_t)(table.size() / 4), n, reinterpret_cast<int32_t*>(c->device_out), c->device_votes,
                      c->device_status);
-        he = hipGetLastError();
-    }
-    return boxes_end(p, st, he, call, !c->stream);
+    });
 }
 
 // records, results: one device allocation [records | out | votes | status]; what the caller has in out, votes and status goes up first,
@@ -2142,7 +2141,7 @@ int carry_regions(leon_pipeline* p, int64_t window, const leon_pipeline_carry_re
     int rc = carry_pipeline_check(p);
     if (rc != LEON_OK) return rc;
     if (!regions || !out) return fail(LEON_ERR_INVALID, "carry regions: null %s", regions ? "out" : "regions");
-    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "carry regions: %d regions (a call takes 1 .. 65535)", n);
+    if ((rc = record_count_check("carry regions", "regions", n)) != LEON_OK) return rc;
     HIP_TRY(hipSetDevice(p->cfg.device_id));
     CarryHostBufs b;
     if ((rc = carry_host_up(&b, 0, regions, n, out, votes, status, nullptr)) != LEON_OK) return rc;
@@ -2197,7 +2196,7 @@ int carry_device(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32_t
     if (!fwd || !bwd || !records || !regions || !out) return fail(LEON_ERR_INVALID, "null argument");
     int rc = carry_geometry_check(fw, fh, mbw, mbh, n_frames);
     if (rc != LEON_OK) return rc;
-    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "carry regions: %d regions (a call takes 1 .. 65535)", n);
+    if ((rc = record_count_check("carry regions", "regions", n)) != LEON_OK) return rc;
     for (int32_t i = 0; i < n_frames; i++)
         if (fwd[i] < -1 || fwd[i] >= n_frames || bwd[i] < -1 || bwd[i] >= n_frames)
             return fail(LEON_ERR_INVALID, "carry: frame %d points into frames %d and %d of %d", i, fwd[i], bwd[i], n_frames);
@@ -2273,7 +2272,7 @@ int propagate_maps_device(leon_pipeline* p, int64_t window, const leon_pipeline_
     if ((rc = carry_window_table(p, window, &table)) != LEON_OK) return rc;
     const int32_t n = c->n;
     if (c->reserved0 || c->reserved[0] || c->reserved[1]) return fail(LEON_ERR_INVALID, "propagate maps: a reserved word of the call is not 0");
-    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "propagate maps: %d hops (a call takes 1 .. 65535)", n);
+    if ((rc = record_count_check("propagate maps", "hops", n)) != LEON_OK) return rc;
     if (!c->hops) return fail(LEON_ERR_INVALID, "propagate maps: null hops");
     if (!c->maps) return fail(LEON_ERR_INVALID, "propagate maps: null maps");
     if (((uintptr_t)c->hops | (uintptr_t)c->maps | (uintptr_t)c->device_via | (uintptr_t)c->device_status) & 3u)
@@ -2281,16 +2280,10 @@ int propagate_maps_device(leon_pipeline* p, int64_t window, const leon_pipeline_
                     (void*)c->device_via, (void*)c->device_status);
     leon::PropagateGeom g;
     if ((rc = propagate_config_check(p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width, cfg, &g)) != LEON_OK) return rc;
-    hipStream_t st;
-    uint32_t* d_table = nullptr;
-    hipError_t he = hipSuccess;
-    if ((rc = regions_call_stream(p, c->stream, &st)) != LEON_OK || (rc = boxes_begin(p, st, table, pad256(std::max<size_t>(table.size(), 1) * 4), &d_table, &he)) != LEON_OK) return rc;
-    if (he == hipSuccess) {
+    return boxes_run(p, c->stream, call, table, pad256(std::max<size_t>(table.size(), 1) * 4), [&](hipStream_t st, uint32_t* d_table) {
         propagate_launch(st, reinterpret_cast<const leon::PropagateHop*>(c->hops), reinterpret_cast<const leon::CarryFrame*>(d_table), p->d_motion, g, p->motion_lay,
                          (int32_t)(table.size() / 4), *cfg, n, static_cast<uint8_t*>(c->maps), c->device_via, c->device_status);
-        he = hipGetLastError();
-    }
-    return boxes_end(p, st, he, call, !c->stream);
+    });
 }
 
 // hops, results and maps of a host road: one device allocation [hops | status | via | maps | extra]; what the caller has in maps, via
@@ -2330,7 +2323,7 @@ int propagate_maps(leon_pipeline* p, int64_t window, const leon_pipeline_propaga
     int rc = carry_pipeline_check(p);
     if (rc != LEON_OK) return rc;
     if (!hops || !maps) return fail(LEON_ERR_INVALID, "propagate maps: null %s", hops ? "maps" : "hops");
-    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "propagate maps: %d hops (a call takes 1 .. 65535)", n);
+    if ((rc = record_count_check("propagate maps", "hops", n)) != LEON_OK) return rc;
     leon::PropagateGeom g;
     if ((rc = propagate_config_check(p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width, cfg, &g)) != LEON_OK) return rc;
     {          // the window's refusals before anything is allocated or uploaded (the device road judges it again under the same lock)
@@ -2388,7 +2381,7 @@ int propagate_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int
     leon::PropagateGeom g;
     int rc = propagate_host_check(fw, fh, mbw, mbh, n_frames, records, cfg, hops, maps, &g);
     if (rc != LEON_OK) return rc;
-    if (n < 1 || n > 65535) return fail(LEON_ERR_INVALID, "propagate maps: %d hops (a call takes 1 .. 65535)", n);
+    if ((rc = record_count_check("propagate maps", "hops", n)) != LEON_OK) return rc;
     for (int32_t i = 0; i < n; i++) {          // a record that is read must be there
         const leon::PropagateHop& h = reinterpret_cast<const leon::PropagateHop&>(hops[i]);
         if (leon::propagate_hop_status(h, n_frames, cfg->n_slots) == leon::kRegionOk && !records[h.target])
@@ -2758,8 +2751,7 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
         return fail(LEON_ERR_INVALID, "a yuva stream needs frame_width %% 8 == 0 (it is %d) and the CPU-twin display flavour in the pipeline", p->vinfo.frame_width);
     p->maps = map_layout((size_t)p->vinfo.mb_width * p->vinfo.mb_height, (size_t)p->vinfo.n_groups);
     if (p->output & LEON_PIPELINE_OUTPUT_MOTION) {
-        if (p->vinfo.mb_width < 1 || p->vinfo.mb_width > leon::kMotionMaxMb || p->vinfo.mb_height < 1 || p->vinfo.mb_height > leon::kMotionMaxMb)
-            return fail(LEON_ERR_INVALID, "motion output: %d x %d macroblocks (1 .. %d each)", p->vinfo.mb_width, p->vinfo.mb_height, leon::kMotionMaxMb);
+        if (const int mrc = mb_grid_check("motion output", p->vinfo.mb_width, p->vinfo.mb_height); mrc != LEON_OK) return mrc;
         p->motion_lay = leon::motion_layout((uint32_t)p->vinfo.mb_width, (uint32_t)p->vinfo.mb_height);
     }
     // the GPU parser's geometry; it writes a picture's maps at the offsets of the layout the arenas give them

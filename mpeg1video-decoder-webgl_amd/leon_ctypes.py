@@ -789,10 +789,11 @@ def _carry_records(records, mbw, mbh):
     return ptrs, keep
 
 
-def _carry_regions_array(regions):
-    """[n, 8] int32 of a list of (frame, x, y, w, h, target[, r0, r1]) or an integer array [n, 6] / [n, 8]"""
-    a = np.asarray(regions, dtype=np.int64).reshape(len(regions), -1) if len(regions) else np.zeros((0, 8), dtype=np.int64)
-    full = np.zeros((len(a), 8), dtype=np.int32)
+def _records_array(rows, words=8):
+    """[n, words] int32 of a list of records that may leave their last (reserved) words out, or of an integer array: carry regions
+    (frame, x, y, w, h, target[, r0, r1]), propagate hops (target, dst_slot, fwd_slot, bwd_slot[, four reserved words])"""
+    a = np.asarray(rows, dtype=np.int64).reshape(len(rows), -1) if len(rows) else np.zeros((0, words), dtype=np.int64)
+    full = np.zeros((len(a), words), dtype=np.int32)
     full[:, :a.shape[1]] = a
     return full
 
@@ -802,7 +803,7 @@ def carry_record(frame_width, frame_height, mbw, mbh, n_frames, fwd, bwd, record
     as int32 arrays that hold `fill` where the library wrote nothing; LeonError where it refuses the call."""
     ptrs, keep = _carry_records(records, mbw, mbh)
     f, b = np.ascontiguousarray(fwd, dtype=np.int32), np.ascontiguousarray(bwd, dtype=np.int32)
-    r = _carry_regions_array([rec])
+    r = _records_array([rec])
     out, votes = np.full(8, fill, dtype=np.int32), np.full(4, fill, dtype=np.int32)
     st = load().leon_pipeline_carry_record(int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), f.ctypes.data, b.ctypes.data, ptrs, r.ctypes.data,
                                            out.ctypes.data, votes.ctypes.data)
@@ -817,7 +818,7 @@ def carry_device(frame_width, frame_height, mbw, mbh, n_frames, fwd, bwd, record
     votes.  n: the count handed to the library when it is to differ from m = len(regions) (smaller: what lies behind keeps the fill)."""
     ptrs, keep = _carry_records(records, mbw, mbh)
     f, b = np.ascontiguousarray(fwd, dtype=np.int32), np.ascontiguousarray(bwd, dtype=np.int32)
-    r = _carry_regions_array(regions)
+    r = _records_array(regions)
     m = max(1, len(r))
     out, votes, status = np.full((m, 8), fill, dtype=np.int32), np.full((m, 4), fill, dtype=np.int32), np.full(m, fill, dtype=np.int32)
     _chk(load().leon_pipeline_carry_device(int(device_id), int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), f.ctypes.data, b.ctypes.data, ptrs,
@@ -909,14 +910,6 @@ def propagate_layout(frame_width, frame_height, stride, planes, elem_bytes):
     return out
 
 
-def _propagate_hops_array(hops):
-    """[n, 8] int32 of a list of (target, dst_slot, fwd_slot, bwd_slot[, four reserved words]) or an integer array [n, 4] / [n, 8]"""
-    a = np.asarray(hops, dtype=np.int64).reshape(len(hops), -1) if len(hops) else np.zeros((0, 8), dtype=np.int64)
-    full = np.zeros((len(a), 8), dtype=np.int32)
-    full[:, :a.shape[1]] = a
-    return full
-
-
 def _propagate_config(maps, stride, fill, over=None):
     """PipelinePropagateConfig of a numpy array [S, P, mh, mw] whose slots may lie further apart than a map (strides[0]); `over`
     replaces fields (the refusals' tests)"""
@@ -930,11 +923,16 @@ def _propagate_config(maps, stride, fill, over=None):
     return cfg
 
 
+def _fill_element(fill, elem_bytes):
+    """the fill word as an element of elem_bytes bytes, a signed integer: its low bytes (propagate_map states the same)"""
+    return int(np.array([int(fill) & 0xffffffff], dtype="<u4").view(np.uint8)[:elem_bytes].view({1: np.uint8, 2: np.int16, 4: np.int32}[elem_bytes])[0])
+
+
 def propagate_record(frame_width, frame_height, mbw, mbh, n_frames, records, hop, stride, maps, fill=0, via_fill=0, **over):
     """leon_pipeline_propagate_record: the library's CPU evaluation of one hop; arguments as propagate_map's, maps written in place.
     Returns (status, via [mh, mw] uint8 that holds `via_fill` where the library wrote nothing); LeonError where it refuses the call."""
     ptrs, keep = _carry_records(records, mbw, mbh)
-    h = _propagate_hops_array([hop])
+    h = _records_array([hop])
     via = np.full(maps.shape[2:], via_fill, dtype=np.uint8)
     cfg = _propagate_config(maps, stride, fill, over)
     st = load().leon_pipeline_propagate_record(int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), ptrs, C.byref(cfg), h.ctypes.data, maps.ctypes.data,
@@ -950,7 +948,7 @@ def propagate_kernel(frame_width, frame_height, mbw, mbh, n_frames, records, hop
     None with via=False, status [m] int32 pre-filled with `status_fill`).  n: the count handed to the library when it is to differ
     from m = len(hops)."""
     ptrs, keep = _carry_records(records, mbw, mbh)
-    h = _propagate_hops_array(hops)
+    h = _records_array(hops)
     m = max(1, len(h))
     v = np.full((m,) + maps.shape[2:], via_fill, dtype=np.uint8) if via else None
     status = np.full(m, status_fill, dtype=np.int32)
@@ -1391,6 +1389,24 @@ class _Frames:
         return (self[i] for i in range(self._n))
 
 
+def _device_tensor_check(name, t, dtype, count, dev, words=False, strided=False):
+    """what a device road asks of a tensor argument (None: not supplied): on the pipeline's device and, with a dtype, of that dtype,
+    contiguous (strided: left to the caller) and of at least `count` elements (words: the text of the int32 arrays)"""
+    if t is None:
+        return
+    if not t.is_cuda or t.device.index != dev:
+        raise ValueError("%s: on %s, the pipeline's device is cuda:%d" % (name, t.device, dev))
+    if dtype is not None and (t.dtype != dtype or not (strided or t.is_contiguous()) or t.numel() < count):
+        raise ValueError("%s: a contiguous %s tensor of at least %d %s" % ((name, "int32", count, "words") if words else (name, dtype, count, "elements")))
+
+
+def _empty_where_none(stream, dev, wanted):
+    """wanted = [(tensor or None, shape, dtype), ...] -> the tensors, those that were None allocated on `stream` (not initialised)"""
+    import torch
+    with torch.cuda.stream(stream):
+        return [torch.empty(shape, dtype=dtype, device="cuda:%d" % dev) if t is None else t for t, shape, dtype in wanted]
+
+
 class Pipeline:
     """leon_pipeline_* (include/leon_pipeline.h): stream bytes in, RGBA frames in device memory out.
     on_window(window_id, frames) runs on the pipeline's notify thread with a list of dicts
@@ -1652,7 +1668,7 @@ class Pipeline:
         motion records (carry_box states it) -> (out [n, 8], votes [n, 4], status [n]) int32 host arrays; out[i] is a region record
         (target, x', y', w, h, 0, 0, 0) for resample_regions, votes[i] = (A, I, dh, dv).  A record's fault is its status word
         (REGION_*, REGION_NO_REFERENCE: no prediction joins the two frames), never a LeonError; its out and votes keep `fill`.  Synchronous."""
-        r = _carry_regions_array(records)
+        r = _records_array(records)
         m = max(1, len(r))
         out, votes, status = np.full((m, 8), fill, dtype=np.int32), np.full((m, 4), fill, dtype=np.int32), np.full(m, fill, dtype=np.int32)
         _chk(self.lib.leon_pipeline_carry_regions(self.h, int(window), r.ctypes.data if len(r) else None, len(r), out.ctypes.data, votes.ctypes.data, status.ctypes.data))
@@ -1672,17 +1688,9 @@ class Pipeline:
             raise ValueError("records: a contiguous CUDA int32 tensor [N, 8]")
         n = int(records.shape[0])
         for name, t, words in (("records", records, 8 * n), ("out", out, 8 * n), ("votes", votes, 4 * n), ("status", status, n)):
-            if t is None:
-                continue
-            if not t.is_cuda or t.device.index != dev:
-                raise ValueError("%s: on %s, the pipeline's device is cuda:%d" % (name, t.device, dev))
-            if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < words:
-                raise ValueError("%s: a contiguous int32 tensor of at least %d words" % (name, words))
+            _device_tensor_check(name, t, torch.int32, words, dev, words=True)
         stream = torch.cuda.current_stream(dev) if stream is None else stream
-        with torch.cuda.stream(stream):
-            out = torch.empty((max(1, n), 8), dtype=torch.int32, device="cuda:%d" % dev) if out is None else out
-            votes = torch.empty((max(1, n), 4), dtype=torch.int32, device="cuda:%d" % dev) if votes is None else votes
-            status = torch.empty(max(1, n), dtype=torch.int32, device="cuda:%d" % dev) if status is None else status
+        out, votes, status = _empty_where_none(stream, dev, [(out, (max(1, n), 8), torch.int32), (votes, (max(1, n), 4), torch.int32), (status, max(1, n), torch.int32)])
         call = PipelineCarryRegionsCall(records.data_ptr() if n else None, n, 0, out.data_ptr(), votes.data_ptr(), status.data_ptr(), self._stream_handle(stream))
         _chk(self.lib.leon_pipeline_carry_regions_device(self.h, int(window), C.byref(call)))
         return out.view(-1)[:8 * n].view(n, 8), votes.view(-1)[:4 * n].view(n, 4), status.view(-1)[:n]
@@ -1700,14 +1708,7 @@ class Pipeline:
         dev = "cuda:%d" % self.device_id
         if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda and boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] == 4):
             raise ValueError("boxes: a CUDA int32 tensor [N, 4] (x, y, w, h)")
-        if frames is None:
-            raw = self._window_gops.get(int(window))
-            if raw is None:
-                raise LeonError(ERR_INVALID, "window %d is not out for delivery" % int(window))
-            fa = np.frombuffer(raw, dtype=np.dtype([("gop", "<u8"), ("display_index", "<i4"), ("type", "<i4"), ("rest", "V48")]))
-            info = list(zip(fa["gop"].tolist(), fa["display_index"].tolist(), fa["type"].tolist()))
-        else:
-            info = list(frames)
+        info = self._window_keys(window, frames)
         levels, _ = carry_plan(self.carry_refs(window), info, src)
         F, N = len(info), int(boxes.shape[0])
         records = torch.zeros((F, N, 8), dtype=torch.int32, device=dev)
@@ -1754,7 +1755,7 @@ class Pipeline:
         LeonError, and its slot and via map keep what they held (`via_fill`).  Synchronous."""
         self._need_motion()
         self._propagate_check(maps, stride)
-        h = _propagate_hops_array(hops)
+        h = _records_array(hops)
         m = max(1, len(h))
         via, status = np.full((m,) + maps.shape[2:], via_fill, dtype=np.uint8), np.zeros(m, dtype=np.int32)
         cfg = _propagate_config(maps, stride, fill)
@@ -1781,16 +1782,9 @@ class Pipeline:
         lay = self._propagate_check(maps, stride)
         n, cells = int(hops.shape[0]), lay.mh * lay.mw
         for name, t, dtype, count in (("maps", maps, maps.dtype, 0), ("hops", hops, torch.int32, 0), ("via", via, torch.uint8, n * cells), ("status", status, torch.int32, n)):
-            if t is None:
-                continue
-            if not t.is_cuda or t.device.index != dev:
-                raise ValueError("%s: on %s, the pipeline's device is cuda:%d" % (name, t.device, dev))
-            if t.dtype != dtype or (t is not maps and not t.is_contiguous()) or t.numel() < count:
-                raise ValueError("%s: a contiguous %s tensor of at least %d elements" % (name, dtype, count))
+            _device_tensor_check(name, t, dtype, count, dev, strided=t is maps)
         stream = torch.cuda.current_stream(dev) if stream is None else stream
-        with torch.cuda.stream(stream):
-            via = torch.empty((max(1, n), lay.mh, lay.mw), dtype=torch.uint8, device="cuda:%d" % dev) if via is None else via
-            status = torch.empty(max(1, n), dtype=torch.int32, device="cuda:%d" % dev) if status is None else status
+        via, status = _empty_where_none(stream, dev, [(via, (max(1, n), lay.mh, lay.mw), torch.uint8), (status, max(1, n), torch.int32)])
         S, P, e = int(maps.shape[0]), int(maps.shape[1]), maps.element_size()
         pitch = (maps.stride(0) if S > 1 else P * cells) * e          # (the library refuses one that is no multiple of 4: pad the slots apart)
         cfg = PipelinePropagateConfig(int(stride), P, e, S, int(fill) & 0xffffffff, 0, pitch, S * pitch)
@@ -1841,7 +1835,7 @@ class Pipeline:
         maps[slot[src]] = map
         via[slot[src]] = 3
         if unreachable:          # (fills by value: nothing goes up)
-            word = int(np.array([int(fill) & 0xffffffff], dtype="<u4").view(np.uint8)[:e].view({1: np.uint8, 2: np.int16, 4: np.int32}[e])[0])
+            word = _fill_element(fill, e)
             bits = maps.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[e])          # (the same element size: the strides stay)
             for u in unreachable:
                 bits[slot[u]].fill_(word)
@@ -2001,8 +1995,7 @@ class Pipeline:
         if rects is True:
             rects = None
         for name, t in (("boxes", boxes), ("out", out), ("status", status), ("rects", rects)):
-            if t is not None and (not t.is_cuda or t.device.index != dev):
-                raise ValueError("%s: on %s, the pipeline's device is cuda:%d" % (name, t.device, dev))
+            _device_tensor_check(name, t, None, 0, dev)
         stream = torch.cuda.current_stream(dev) if stream is None else stream
         n = int(boxes.shape[0])
         cfg = size if isinstance(size, PipelineRegionsConfig) else PipelineRegionsConfig(int(size[1]), int(size[0]), _resize_filter_code(filter))
@@ -2013,10 +2006,9 @@ class Pipeline:
                 raise ValueError("boxes: [N, 8] records must be contiguous")
             out, step = self._regions_out(out, n, (cfg.out_height, cfg.out_width), pitch, dev)
             status = self._regions_status(status, n, dev)
-            if want_rects and rects is None:
-                rects = torch.empty((max(1, n), 4), dtype=torch.int32, device="cuda:%d" % dev)
-            elif want_rects and (rects.dtype != torch.int32 or not rects.is_contiguous() or rects.numel() < 4 * n):
-                raise ValueError("rects: a contiguous int32 tensor of at least %d words" % (4 * n))
+            if want_rects:
+                _device_tensor_check("rects", rects, torch.int32, 4 * n, dev, words=True)
+                rects, = _empty_where_none(stream, dev, [(rects, (max(1, n), 4), torch.int32)])
         call = PipelineRegionsDevice(boxes.data_ptr() if n else None, n, 0, out.data_ptr(), 0 if pitch is None else step, status.data_ptr(), self._stream_handle(stream),
                                      0 if scratch_limit is None else int(scratch_limit))
         f = _regions_fit(fit, anchor, pad_value)
@@ -2074,8 +2066,7 @@ class Pipeline:
                 and records.is_contiguous()):
             raise ValueError("records: a contiguous CUDA int32 tensor [N, 8]")
         for name, t in (("records", records), ("out", out), ("status", status)):
-            if t is not None and (not t.is_cuda or t.device.index != dev):
-                raise ValueError("%s: on %s, the pipeline's device is cuda:%d" % (name, t.device, dev))
+            _device_tensor_check(name, t, None, 0, dev)
         stream = torch.cuda.current_stream(dev) if stream is None else stream
         n = int(records.shape[0])
         cfg = _warp_config(size, pad_value)
