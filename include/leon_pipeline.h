@@ -64,6 +64,9 @@ typedef struct leon_pipeline leon_pipeline;
 /* Bit 5: 4 and 8 stay refused as above, and so does every other unknown bit (-1 among them).  Only beside RGBA, YCBCR or TENSOR: a
  * pipeline that parses and reconstructs nothing is a later step, so the bit on its own (output = 32) is refused at create. */
 #define LEON_PIPELINE_OUTPUT_MOTION (1 << 5)
+/* Bit 7, not 6: create goes on refusing output = 64 | 1 (tests/test_pipeline_motion_gpu.py::test_refusals), as it does every other
+ * unknown bit.  Only beside RGBA, YCBCR or TENSOR, like MOTION and independent of it: on its own (output = 128) it is refused at create. */
+#define LEON_PIPELINE_OUTPUT_ACTIVITY (1 << 7)
 
 /* element type of the tensor output (leon_pipeline_tensor_config.dtype) */
 #define LEON_TENSOR_F16  1
@@ -315,6 +318,45 @@ typedef struct leon_pipeline_motion_frame {
     int32_t  reserved[2];
 } leon_pipeline_motion_frame;           /* 32 bytes */
 
+/* LEON_PIPELINE_OUTPUT_ACTIVITY: how much the stream coded on top of each prediction, per delivered frame -- where a carried box or a
+ * propagated map stops being trustworthy, what a "run the detector again here" gate reads, the residual branch of a compressed-domain
+ * model.  A delivered frame gets one ACTIVITY RECORD, made from the picture's sparse group lists and its qscale map as
+ * include/leon_vlc.h defines them (integers only).  Geometry: mbw = coded_width / 16, mbh = coded_height / 16, mbs = mbw * mbh,
+ * groups_y = ceil(mbw / 4), groups_c = ceil(mbw / 8), n_y = 2 * mbh * groups_y, n_c = mbh * groups_c.  Only the n_y + 2 * n_c groups
+ * of Y, Cb and Cr are read (grp_off[0 .. n_y + 2 n_c]); the A groups of a yuva stream are not.
+ * An entry e of group G:  level = (int16)(e & 0xffff), a = |level| (0 .. 32768); an entry with level == 0 counts nothing (one front
+ * end writes such entries, the other does not: the record is the same).  b = (e >> 20) & 7 is its block in the group, r = (e >> 23) & 7
+ * its row and c = (e >> 17) & 7 its column in the block; it is DC when r == 0 and c == 0.  Its macroblock (mx, my) and block j:
+ *     luma, block row R, group g   G = R * groups_y + g               mx = 4 g + (b >> 1)   my = R >> 1   j = 2 (R & 1) + (b & 1)
+ *     Cb,   block row R, group g   G = n_y + R * groups_c + g         mx = 8 g + b          my = R        j = 4
+ *     Cr,   block row R, group g   G = n_y + n_c + R * groups_c + g   mx = 8 g + b          my = R        j = 5
+ * An entry whose mx >= mbw counts nothing.  Per macroblock k = my * mbw + mx, over its entries with level != 0:
+ *     ac_count  the number of entries that are not DC          ac_mag  the sum of a over those entries
+ *     dc_mag    the sum of a over the DC entries                blocks  bit j set when block j has at least one such entry (the
+ *                                                                       effective coded block pattern)
+ * The three sums are taken exactly and then each saturated at 65535.  qscale = blocks ? qscale_map[k] : 0: the map keeps stale parser
+ * state at macroblocks that code nothing, which the record does not show.  DC is kept apart because an intra macroblock's DC entry is
+ * in the 0 .. 255 predictor domain (leon_vlc.h), a sample level and not a correction; the motion record's info, or the picture type,
+ * tells the two apart.
+ * The record in memory, the same on the device and on the host, little endian (pad256 = rounding up to 256):
+ *     cell     [mbs] of 8 bytes: uint16 ac_count, uint16 ac_mag, uint16 dc_mag, uint8 blocks, uint8 qscale     at 0
+ *     summary  uint32[8]                                                              at summary_offset = pad256(8 * mbs)
+ *     record_bytes = summary_offset + 32;   record_pitch = pad256(record_bytes)
+ * Summary words, over the RECORD's values: [0] macroblocks with blocks != 0, [1] the sum of ac_count, [2] of ac_mag, [3] of dc_mag,
+ * [4] the maximum of ac_mag, [5] the sum of qscale, [6] of popcount(blocks), [7] 0.  A picture has at most 256 x 256 macroblocks and
+ * every word fits: the largest, [2], is at most 65536 * 65535 < 2^32.
+ * The bytes between the parts, and up to the pitch, are unspecified.  Every specified byte of every delivered frame's record is
+ * written by its window's launches (k_activity and k_activity_summary, one launch each per window on the decoder's stream behind the
+ * reconstruction), every window; nothing relies on an earlier clear.  A window delivered with an error has unspecified records.
+ * Pictures that are not delivered (dropped leading B pictures, what an EXACT seek trims) have no record. */
+/* (a struct tag only, as leon_pipeline_motion_layout) */
+struct leon_pipeline_activity_layout {
+    int32_t  mb_width, mb_height, mbs;
+    int32_t  reserved0;                 /* 0 */
+    uint64_t summary_offset, record_bytes, record_pitch;
+    uint64_t reserved[3];               /* 0 */
+};                                      /* 64 bytes */
+
 typedef void (*leon_pipeline_callback)(void* user, int64_t window, const leon_pipeline_frame* frames, int32_t n_frames, int32_t status);
 
 typedef struct leon_pipeline_info {
@@ -478,6 +520,44 @@ int leon_pipeline_get_motion_layout(leon_pipeline* p, struct leon_pipeline_motio
 int leon_pipeline_window_motion(leon_pipeline* p, int64_t window, leon_pipeline_motion_frame* out, int32_t n);
 /* copy the record of frame `index` of such a window to host memory, packed: mv [mbs][4], info [mbs], summary [8]; each may be NULL */
 int leon_pipeline_read_motion(leon_pipeline* p, int64_t window, int32_t index, int16_t* mv, uint8_t* info, uint32_t* summary);
+
+/* The ACTIVITY family, shaped like the MOTION one. */
+/* host only, no device: the record's layout for a picture of mb_width x mb_height macroblocks; refuses sizes outside 1 .. 256 */
+int leon_pipeline_activity_layout(int32_t mb_width, int32_t mb_height, struct leon_pipeline_activity_layout* out);
+/* host only: the definition above on the CPU (the per-entry and per-macroblock text the kernels compile too, csrc/leon_activity.h),
+ * from a picture's lists and qscale map in host memory into a buffer of record_bytes.  grp_off has n_y + 2 n_c + 1 values at least,
+ * entries n_entries (NULL only with n_entries = 0), qscale mbs.  Unspecified bytes are left alone.  Refused, the record untouched: a
+ * size outside 1 .. 256, a null grp_off, qscale or record, null entries with n_entries > 0, a grp_off that decreases anywhere in
+ * 0 .. n_y + 2 n_c, a grp_off[n_y + 2 n_c] above n_entries */
+int leon_pipeline_activity_record(int32_t mb_width, int32_t mb_height, const uint32_t* grp_off, const uint32_t* entries, uint32_t n_entries,
+                                  const uint8_t* qscale, void* record);
+/* A diagnostic in the manner of leon_pipeline_motion_kernel: k_activity and k_activity_summary on lists the CALLER supplies, with
+ * memory of its own on device_id's null stream, synchronous, everything in host memory.  pictures[i] is a picture of mb_width x
+ * mb_height macroblocks as leon_pipeline_activity_record takes it; n_entries is its list's CAPACITY, which the kernel clamps every
+ * offset to.  On the device every array lies in a piece of its own, padded as the pipeline's arenas pad it (grp_off: pad256(4 (n_y +
+ * 2 n_c + 1)), entries: pad256(4 n_entries + 4), qscale: pad256(mbs)), every padding byte = pad_byte.  Frames, ring and the launch are
+ * leon_pipeline_motion_kernel's: frame i is a record of pictures[frames[i].picture] at ring + frames[i].ring * record_pitch
+ * (leon_pipeline_activity_layout), the ring goes up and comes back whole, more than 65535 frames go in more than one launch.
+ * Refused (LEON_ERR_INVALID, nothing launched, `ring` untouched): what leon_pipeline_motion_kernel refuses of sizes, counts, pad_byte,
+ * indices and null arguments, a non-zero reserved word, and what leon_pipeline_activity_record refuses of a picture (a grp_off that is
+ * not monotonic, a grp_off[last] above n_entries among them), n_entries above 2^30. */
+typedef struct leon_pipeline_activity_picture {
+    const uint32_t* grp_off;    /* [n_y + 2 n_c + 1] */
+    const uint32_t* entries;    /* [n_entries] */
+    const uint8_t* qscale;      /* [mbs] */
+    uint32_t n_entries;
+    int32_t reserved0;          /* 0 */
+} leon_pipeline_activity_picture;       /* 32 bytes */
+int leon_pipeline_activity_kernel(int32_t device_id, int32_t mb_width, int32_t mb_height, const leon_pipeline_activity_picture* pictures, int32_t n_pictures,
+                                  const leon_pipeline_motion_kernel_frame* frames, int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring);
+/* the layout of this pipeline's records; LEON_ERR_INVALID for a pipeline without LEON_PIPELINE_OUTPUT_ACTIVITY */
+int leon_pipeline_get_activity_layout(leon_pipeline* p, struct leon_pipeline_activity_layout* out);
+/* the activity records of a delivered, not yet released window: out[i] is the DEVICE pointer (256-byte aligned, valid until
+ * release_window) of frames[i]'s record, n = the window's n_frames.  May be called from inside the callback.  LEON_ERR_INVALID for a
+ * pipeline without the bit, a window that is not out for delivery, another n */
+int leon_pipeline_window_activity(leon_pipeline* p, int64_t window, void** out, int32_t n);
+/* copy the record of frame `index` of such a window to host memory, packed: cells [mbs] of 8 bytes, summary [8]; each may be NULL */
+int leon_pipeline_read_activity(leon_pipeline* p, int64_t window, int32_t index, void* cells, uint32_t* summary);
 
 /* Regions of delivered frames as a tensor batch: what runs behind a detector.  The detector's boxes are cut out of the FULL-RESOLUTION
  * frames of a delivered window and resampled to a second-stage model's input size, any number of them in one call, into memory of the

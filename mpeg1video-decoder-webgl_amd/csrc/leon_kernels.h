@@ -40,6 +40,7 @@
 #include "leon_resize_row.h"
 #include "leon_warp.h"
 #include "leon_motion.h"
+#include "leon_activity.h"
 #include "leon_carry.h"
 #include "leon_propagate.h"
 
@@ -2974,6 +2975,145 @@ __global__ __launch_bounds__(kRgbaBlock) void k_motion(const MotionDesc* __restr
             hi.x += c.x; hi.y += c.y; hi.z += c.z; hi.w += c.w;
         }
         uint4* sm = reinterpret_cast<uint4*>(rec + G.summary_offset);
+        sm[0] = lo;
+        sm[1] = hi;
+    }
+}
+
+// ---- output ACTIVITY: a frame's activity record (include/leon_pipeline.h, LEON_PIPELINE_OUTPUT_ACTIVITY) ------------------------
+// Two launches per window behind its reconstruction levels, blockIdx.y = the delivered frame in both.
+// k_activity: a task is the 8 macroblocks under one chroma group c of one macroblock row my -- Cb and Cr group c of block row my, luma
+// groups 2c and 2c + 1 (where the row has it) of block rows 2 my and 2 my + 1, six lists at most.  One 64-lane wave per task, four
+// tasks per workgroup; the waves share nothing but the two barriers.  The wave's lanes stride over each list's entries, a dword each
+// (a list starts at any entry, so nothing wider is aligned), and add what an entry counts (leon_activity.h, the host's text) to the
+// task's bins in LDS -- all six lists' offsets are asked for at once and then every list's first 64 entries, before anything is counted:
+// a list of the 1080p benchmark stream holds 13 entries on average and 2 % hold more than 64, so a task waits for memory three times
+// (descriptor, offsets, entries) and not thirteen --: per macroblock and sum eight 64-bit words, lane l into word l & 7, so that the run of entries one block
+// contributes spreads over eight addresses and no sum can wrap whatever a list holds.  The block bits travel as one 48-bit mask per lane,
+// OR-ed into LDS once.  Lanes 0 .. 7 then add a macroblock's eight words each, saturate, read its qscale and store its 8 bytes: every
+// cell is written once, by the task that owns it.  Both offsets of a list are clamped to the list's capacity (activity_span) before
+// an entry is addressed.  LDS: 4 waves x (3 sums x 8 macroblocks x 8 words x 8 bytes + 8) = 6176 bytes.
+// k_activity_summary: the eight summary words of a frame from its cells, one workgroup per frame, k_motion's reduction (shuffles, the
+// four waves through LDS, lane 0 stores).  A second kernel and not the last workgroup of the first: the cells of a frame come from
+// workgroups on every XCD, whose L2s are not coherent inside a launch, and a "last one reduces" hand-off needs a counter that somebody
+// clears -- which the record's rule (nothing cleared beforehand, nothing added to atomically in global memory) rules out.  The launch
+// boundary orders the cells at no cost, and the cells of a window are still in L2 when they are read again.  LDS: 128 bytes.
+struct ActivityDesc {
+    const uint32_t* grp_off;     // the picture's group offsets, entry list and qscale map in its GOP's device arena
+    const uint32_t* entries;
+    const uint8_t* qscale;
+    uint32_t n_entries;          // the list's capacity: no entry at or behind it is read
+    uint32_t frame;              // the frame's index in the activity ring (frame_addr)
+};
+constexpr int kActivityWaves = kRgbaBlock / 64, kActivitySpread = 8;
+
+__global__ __launch_bounds__(kRgbaBlock) void k_activity(const ActivityDesc* __restrict__ descs, uint8_t* __restrict__ ring, ActivityGeom G, ActivityLayout L)
+{
+    __shared__ unsigned long long bins_s[kActivityWaves][3][8][kActivitySpread];      // [wave][ac_count, ac_mag, dc_mag][macroblock][lane & 7]
+    __shared__ unsigned long long seen_s[kActivityWaves];                             // bit 6 m + j: block j of macroblock m codes something
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    const uint32_t task = blockIdx.x * (uint32_t)kActivityWaves + wave;
+    const bool live = task < G.tasks;
+    unsigned long long* const bins = &bins_s[wave][0][0][0];
+    for (uint32_t i = lane; i < 3u * 8u * (uint32_t)kActivitySpread; i += 64u) bins[i] = 0ull;
+    if (lane == 0u) seen_s[wave] = 0ull;
+    __syncthreads();
+    const ActivityDesc* __restrict__ D = descs + blockIdx.y;
+    const uint32_t my = live ? task / G.groups_c : 0u, c = live ? task - my * G.groups_c : 0u;
+    // lanes 0 .. 7 own a macroblock each; its qscale is needed last and asked for first, so that it travels beside the lists
+    const uint32_t mx = 8u * c + lane, k = my * G.mbw + mx;
+    const bool owns = live && lane < 8u && mx < G.mbw;
+    const uint32_t qscale = owns ? D->qscale[k] : 0u;
+    if (live) {
+        const uint32_t* __restrict__ grp_off = D->grp_off;
+        const uint32_t* __restrict__ entries = D->entries;
+        const uint32_t cap = D->n_entries;
+        // the six lists: luma (2 my, 2c), (2 my, 2c + 1), (2 my + 1, 2c), (2 my + 1, 2c + 1), Cb, Cr.  All their offsets are asked for
+        // first and then every list's first 64 entries, before anything is counted: a list is seldom longer, and six loads in
+        // flight wait once where a list after the other waits twelve times (offsets, then entries, each a trip to memory).
+        uint32_t begin[6], end[6], first[6];
+#pragma unroll
+        for (uint32_t part = 0; part < 6u; part++) {
+            const uint32_t plane = part < 4u ? 0u : part - 3u;
+            const uint32_t R = plane == 0u ? 2u * my + (part >> 1) : my, g = plane == 0u ? 2u * c + (part & 1u) : c;
+            const uint32_t gid = plane == 0u ? R * G.groups_y + g : G.n_y + (plane - 1u) * G.n_c + R * G.groups_c + g;
+            begin[part] = end[part] = 0u;
+            if (plane != 0u || g < G.groups_y) activity_span(grp_off[gid], grp_off[gid + 1u], cap, &begin[part], &end[part]);
+        }
+#pragma unroll
+        for (uint32_t part = 0; part < 6u; part++) first[part] = begin[part] + lane < end[part] ? entries[begin[part] + lane] : 0u;      // (level 0 counts nothing)
+        unsigned long long seen = 0ull;
+        auto count = [&](uint32_t e, uint32_t plane, uint32_t R, uint32_t g) {
+            const uint32_t a = activity_abs(e);
+            uint32_t emx, emy, j;
+            activity_place(plane, R, g, activity_b(e), &emx, &emy, &j);
+            if (a == 0u || emx >= G.mbw) return;
+            const uint32_t m = (emx - 8u * c) & 7u, at = m * (uint32_t)kActivitySpread + (lane & 7u);
+            if (activity_is_dc(e)) {
+                atomicAdd(&bins[2u * 8u * kActivitySpread + at], (unsigned long long)a);
+            } else {
+                atomicAdd(&bins[at], 1ull);
+                atomicAdd(&bins[8u * kActivitySpread + at], (unsigned long long)a);
+            }
+            seen |= 1ull << (6u * m + j);
+        };
+#pragma unroll
+        for (uint32_t part = 0; part < 6u; part++) {
+            const uint32_t plane = part < 4u ? 0u : part - 3u;
+            const uint32_t R = plane == 0u ? 2u * my + (part >> 1) : my, g = plane == 0u ? 2u * c + (part & 1u) : c;
+            count(first[part], plane, R, g);
+            for (uint32_t i = begin[part] + 64u + lane; i < end[part]; i += 64u) count(entries[i], plane, R, g);
+        }
+        if (seen) atomicOr(&seen_s[wave], seen);
+    }
+    __syncthreads();
+    if (owns) {
+        unsigned long long sum[3] = {0ull, 0ull, 0ull};
+#pragma unroll
+        for (int f = 0; f < 3; f++)
+#pragma unroll
+            for (int r = 0; r < kActivitySpread; r++) sum[f] += bins_s[wave][f][lane][r];
+        uint32_t lo, hi;
+        activity_cell(sum[0], sum[1], sum[2], (uint32_t)(seen_s[wave] >> (6u * lane)) & 63u, qscale, &lo, &hi);
+        *reinterpret_cast<uint2*>(ring + (size_t)D->frame * L.record_pitch + 8u * (size_t)k) = uint2{lo, hi};
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_max(uint32_t v)
+{
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kRgbaBlock) void k_activity_summary(const ActivityDesc* __restrict__ descs, uint8_t* ring, ActivityLayout L)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t part_s[kRgbaBlock / 64][8];
+    uint8_t* rec = ring + (size_t)descs[blockIdx.y].frame * L.record_pitch;
+    uint32_t s[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    for (uint32_t k = threadIdx.x; k < L.mbs; k += kRgbaBlock) {
+        const uint2 cell = reinterpret_cast<const uint2*>(rec)[k];
+        activity_count(cell.x, cell.y, s);
+    }
+#pragma unroll
+    for (int i = 0; i < 7; i++) s[i] = i == 4 ? wave_max(s[i]) : wave_sum(s[i]);
+    if ((threadIdx.x & 63u) == 0u) {
+        uint4* ps = reinterpret_cast<uint4*>(part_s[threadIdx.x >> 6]);
+        ps[0] = uint4{s[0], s[1], s[2], s[3]};
+        ps[1] = uint4{s[4], s[5], s[6], 0u};
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint4 lo = uint4{0u, 0u, 0u, 0u}, hi = lo;
+#pragma unroll
+        for (int w = 0; w < kRgbaBlock / 64; w++) {
+            const uint4 a = reinterpret_cast<const uint4*>(part_s[w])[0], c = reinterpret_cast<const uint4*>(part_s[w])[1];
+            lo.x += a.x; lo.y += a.y; lo.z += a.z; lo.w += a.w;
+            hi.x = c.x > hi.x ? c.x : hi.x; hi.y += c.y; hi.z += c.z;
+        }
+        uint4* sm = reinterpret_cast<uint4*>(rec + L.summary_offset);
         sm[0] = lo;
         sm[1] = hi;
     }

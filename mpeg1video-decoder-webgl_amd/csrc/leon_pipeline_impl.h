@@ -71,6 +71,8 @@ struct PipeWindow {
     std::vector<leon_pipeline_motion_frame> motion;      // output MOTION: frames[i]'s record and references
     std::vector<leon::MotionDesc> motion_descs;          // ... and what k_motion makes the record from
     std::vector<uint32_t> carry_table;                   // ... and per frame a leon::CarryFrame (ring id, fwd, bwd, 0): what k_carry reads
+    std::vector<void*> activity;                         // output ACTIVITY: frames[i]'s record
+    std::vector<leon::ActivityDesc> activity_descs;      // ... and what k_activity makes the record from
     Event done;
     int status = LEON_OK;
     uint32_t n_vpics = 0;        // gpu_parser: error words of the window's pictures are in the ring entry's h_err
@@ -140,6 +142,11 @@ struct leon_pipeline {
     DevBuf<uint8_t> d_motion;
     leon::MotionLayout motion_lay{};
     Mirror<leon::MotionDesc> motion_descs;
+    // output ACTIVITY: the same for the activity records (activity_lay.record_pitch apart) and k_activity's descriptors
+    DevBuf<uint8_t> d_activity;
+    leon::ActivityLayout activity_lay{};
+    leon::ActivityGeom activity_geom{};
+    Mirror<leon::ActivityDesc> activity_descs;
     // ... resampled to a model's input size (leon_pipeline_tensor_resize; geom.resized = 0: the full-size tensor, k_tensor): the
     // tables of both axes as k_resample reads them -- first_x, count_x, Wx, first_y, count_y, Wy in one int32 buffer
     leon_pipeline_tensor_geometry tensor_geom{};
@@ -1157,6 +1164,8 @@ void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<
     w->frame_ids.clear();
     w->motion.clear();
     w->motion_descs.clear();
+    w->activity.clear();
+    w->activity_descs.clear();
     // output MOTION: what plan_levels gave each picture's launch to predict from, by lane and display index
     std::vector<const LevelPic*> planned;
     if (p->d_motion) {
@@ -1207,6 +1216,19 @@ void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<
                 d.mb_dir = (const uint8_t*)ptr(m.type == LEON_PIC_B ? m.mb_dir : kNone);
                 d.mv_bwd = (const uint32_t*)ptr(m.type == LEON_PIC_B ? m.mv_bwd : kNone);
                 w->motion_descs.push_back(d);
+            }
+            if (p->d_activity) {
+                const PipePic& m = *by_disp[k];
+                const char* base = job->arena->dev;
+                auto ptr = [&](size_t off) -> const void* { return off == kNone ? nullptr : (const void*)(base + off); };
+                w->activity.push_back(p->d_activity + a.index * p->activity_lay.record_pitch);
+                leon::ActivityDesc d{};
+                d.grp_off = (const uint32_t*)ptr(m.grp_off);
+                d.entries = (const uint32_t*)ptr(m.entries);
+                d.qscale = (const uint8_t*)ptr(m.qscale);
+                d.n_entries = m.n_entries;
+                d.frame = (uint32_t)a.index;
+                w->activity_descs.push_back(d);
             }
             w->frames.push_back(f);
         }
@@ -1396,16 +1418,34 @@ int motion_record_host(int32_t type, int32_t mbw, int32_t mbh, const uint8_t* re
 // [descriptors | maps | ring]: every map of every picture in a piece of its own, padded as MapLayout pads it (mpad, vpad) with
 // pad_byte; the caller's ring goes up and comes back whole.
 static_assert(sizeof(leon_pipeline_motion_picture) == 40 && sizeof(leon_pipeline_motion_kernel_frame) == 8, "include/leon_pipeline.h states the sizes");
+// what the diagnostics that run a record kernel on a caller's pictures (motion_kernel, activity_kernel) refuse of their counts and frames
+int kernel_counts_check(const char* who, int32_t n_pics, int32_t n_frames, int32_t ring_frames, int32_t pad_byte)
+{
+    if (n_pics < 1 || n_pics > LEON_MOTION_KERNEL_MAX_FRAMES) return fail(LEON_ERR_INVALID, "%s: %d pictures (1 .. %d)", who, n_pics, LEON_MOTION_KERNEL_MAX_FRAMES);
+    if (ring_frames < 1 || ring_frames > LEON_MOTION_KERNEL_MAX_FRAMES)
+        return fail(LEON_ERR_INVALID, "%s: a ring of %d records (1 .. %d)", who, ring_frames, LEON_MOTION_KERNEL_MAX_FRAMES);
+    if (n_frames < 1 || n_frames > ring_frames) return fail(LEON_ERR_INVALID, "%s: %d frames (1 .. the ring's %d records)", who, n_frames, ring_frames);
+    if (pad_byte < 0 || pad_byte > 255) return fail(LEON_ERR_INVALID, "%s: pad_byte %d (0 .. 255)", who, pad_byte);
+    return LEON_OK;
+}
+int kernel_frames_check(const char* who, int32_t n_pics, const leon_pipeline_motion_kernel_frame* frames, int32_t n_frames, int32_t ring_frames)
+{
+    std::vector<bool> named((size_t)ring_frames, false);
+    for (int32_t i = 0; i < n_frames; i++) {
+        const leon_pipeline_motion_kernel_frame& f = frames[i];
+        if (f.picture < 0 || f.picture >= n_pics) return fail(LEON_ERR_INVALID, "%s: frame %d names picture %d of %d", who, i, f.picture, n_pics);
+        if (f.ring < 0 || f.ring >= ring_frames) return fail(LEON_ERR_INVALID, "%s: frame %d names record %d of a ring of %d", who, i, f.ring, ring_frames);
+        if (named[(size_t)f.ring]) return fail(LEON_ERR_INVALID, "%s: frame %d names record %d, which an earlier frame names", who, i, f.ring);
+        named[(size_t)f.ring] = true;
+    }
+    return LEON_OK;
+}
 int motion_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipeline_motion_picture* pics, int32_t n_pics, const leon_pipeline_motion_kernel_frame* frames,
                   int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring)
 {
     if (!pics || !frames || !ring) return fail(LEON_ERR_INVALID, "null argument");
     if (const int rc = mb_grid_check("motion kernel", mbw, mbh); rc != LEON_OK) return rc;
-    if (n_pics < 1 || n_pics > LEON_MOTION_KERNEL_MAX_FRAMES) return fail(LEON_ERR_INVALID, "motion kernel: %d pictures (1 .. %d)", n_pics, LEON_MOTION_KERNEL_MAX_FRAMES);
-    if (ring_frames < 1 || ring_frames > LEON_MOTION_KERNEL_MAX_FRAMES)
-        return fail(LEON_ERR_INVALID, "motion kernel: a ring of %d records (1 .. %d)", ring_frames, LEON_MOTION_KERNEL_MAX_FRAMES);
-    if (n_frames < 1 || n_frames > ring_frames) return fail(LEON_ERR_INVALID, "motion kernel: %d frames (1 .. the ring's %d records)", n_frames, ring_frames);
-    if (pad_byte < 0 || pad_byte > 255) return fail(LEON_ERR_INVALID, "motion kernel: pad_byte %d (0 .. 255)", pad_byte);
+    if (const int rc = kernel_counts_check("motion kernel", n_pics, n_frames, ring_frames, pad_byte); rc != LEON_OK) return rc;
     const MapLayout M = map_layout((size_t)mbw * (size_t)mbh, 0);
     size_t maps_bytes = 0;
     for (int32_t i = 0; i < n_pics; i++) {
@@ -1416,16 +1456,7 @@ int motion_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipeli
             return fail(LEON_ERR_INVALID, "motion kernel: picture %d (type %d) lacks a map", i, q.type);
         maps_bytes += q.type == LEON_PIC_I ? 0 : (q.type == LEON_PIC_P ? 1 : 2) * (M.mpad + M.vpad);
     }
-    {
-        std::vector<bool> named((size_t)ring_frames, false);
-        for (int32_t i = 0; i < n_frames; i++) {
-            const leon_pipeline_motion_kernel_frame& f = frames[i];
-            if (f.picture < 0 || f.picture >= n_pics) return fail(LEON_ERR_INVALID, "motion kernel: frame %d names picture %d of %d", i, f.picture, n_pics);
-            if (f.ring < 0 || f.ring >= ring_frames) return fail(LEON_ERR_INVALID, "motion kernel: frame %d names record %d of a ring of %d", i, f.ring, ring_frames);
-            if (named[(size_t)f.ring]) return fail(LEON_ERR_INVALID, "motion kernel: frame %d names record %d, which an earlier frame names", i, f.ring);
-            named[(size_t)f.ring] = true;
-        }
-    }
+    if (const int rc = kernel_frames_check("motion kernel", n_pics, frames, n_frames, ring_frames); rc != LEON_OK) return rc;
     const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
     const size_t descs_bytes = pad256((size_t)n_frames * sizeof(leon::MotionDesc)), ring_bytes = (size_t)ring_frames * L.record_pitch;
     const size_t bytes = descs_bytes + maps_bytes + ring_bytes;
@@ -1480,6 +1511,167 @@ int motion_layout_host(int32_t mbw, int32_t mbh, struct leon_pipeline_motion_lay
     out->mb_width = mbw; out->mb_height = mbh; out->mbs = (int32_t)L.mbs;
     out->info_offset = L.info_offset; out->summary_offset = L.summary_offset;
     out->record_bytes = L.record_bytes; out->record_pitch = L.record_pitch;
+    return LEON_OK;
+}
+
+// output ACTIVITY: the window's frames -> their activity records, k_activity and k_activity_summary on the decoder's stream behind the
+// last level and in front of the window's event, while the lists are still in the GOPs' arenas.  The descriptors go up as k_motion's do.
+static_assert(sizeof(leon::ActivityDesc) == 32, "a descriptor is 8 dwords");
+static_assert(sizeof(struct leon_pipeline_activity_layout) == 64 && sizeof(leon_pipeline_activity_picture) == 32, "include/leon_pipeline.h states the sizes");
+static_assert(sizeof(leon::ActivityGeom) == 32 && sizeof(leon::ActivityLayout) == 16, "kernel arguments");
+static_assert(leon::kActivityMaxMb == leon::kMotionMaxMb, "mb_grid_check states one bound");
+// both kernels over n descriptors in device memory, frame i of them in workgroup row i: the one place that cuts them into launches
+// (launch_activity for a window, activity_kernel for a caller's lists)
+void activity_launch(const leon::ActivityDesc* descs, size_t n, uint8_t* ring, const leon::ActivityGeom& geom, const leon::ActivityLayout& lay, hipStream_t stream)
+{
+    const unsigned task_blocks = (geom.tasks + leon::kActivityWaves - 1) / leon::kActivityWaves;
+    for (size_t at = 0; at < n; at += 65535) {
+        const unsigned frames = (unsigned)std::min<size_t>(65535, n - at);
+        hipLaunchKernelGGL(leon::k_activity, dim3(task_blocks, frames), dim3(leon::kRgbaBlock), 0, stream, descs + at, ring, geom, lay);
+        hipLaunchKernelGGL(leon::k_activity_summary, dim3(1, frames), dim3(leon::kRgbaBlock), 0, stream, descs + at, ring, lay);
+    }
+}
+
+int launch_activity(leon_pipeline* p, const PipeWindow* w)
+{
+    const size_t n = w->activity_descs.size();
+    if (!p->d_activity || !n) return LEON_OK;
+    const size_t entry = (size_t)p->W * p->max_pics;
+    leon::ActivityDesc* h = p->activity_descs.host() + (size_t)w->ring * entry;      // the ring entry is this window's: its previous launch has finished
+    leon::ActivityDesc* dv = p->activity_descs.dev() + (size_t)w->ring * entry;
+    for (size_t i = 0; i < n; i++) {
+        const leon::ActivityDesc& d = w->activity_descs[i];
+        if (!d.grp_off || !d.entries || !d.qscale) return fail(LEON_ERR_INVALID, "activity: frame %zu of window %lld lacks its lists or its qscale map", i, (long long)w->id);
+        h[i] = d;
+    }
+    HIP_TRY(hipMemcpyAsync(dv, h, n * sizeof(leon::ActivityDesc), hipMemcpyHostToDevice, p->dec->stream));
+    activity_launch(dv, n, p->d_activity, p->activity_geom, p->activity_lay, p->dec->stream);
+    HIP_TRY(hipGetLastError());
+    return LEON_OK;
+}
+
+// what the host calls refuse of a picture's lists: they walk them without a clamp
+int activity_lists_check(const char* who, const leon::ActivityGeom& G, const uint32_t* grp_off, const uint32_t* entries, uint32_t n_entries, const uint8_t* qscale)
+{
+    if (!grp_off || !qscale || (!entries && n_entries)) return fail(LEON_ERR_INVALID, "%s: null argument", who);
+    const uint32_t n_groups = G.n_y + 2u * G.n_c;
+    for (uint32_t g = 0; g < n_groups; g++)
+        if (grp_off[g + 1] < grp_off[g]) return fail(LEON_ERR_INVALID, "%s: grp_off decreases at group %u (%u after %u)", who, g, grp_off[g + 1], grp_off[g]);
+    if (grp_off[n_groups] > n_entries) return fail(LEON_ERR_INVALID, "%s: grp_off ends at %u, the list has %u entries", who, grp_off[n_groups], n_entries);
+    return LEON_OK;
+}
+
+// the definition on the CPU: the same per-entry and per-macroblock text (leon_activity.h), the specified bytes of one record
+int activity_record_host(int32_t mbw, int32_t mbh, const uint32_t* grp_off, const uint32_t* entries, uint32_t n_entries, const uint8_t* qscale, void* record)
+{
+    if (!record) return fail(LEON_ERR_INVALID, "null argument");
+    if (const int rc = mb_grid_check("activity record", mbw, mbh); rc != LEON_OK) return rc;
+    const leon::ActivityGeom G = leon::activity_geom((uint32_t)mbw, (uint32_t)mbh);
+    if (const int rc = activity_lists_check("activity record", G, grp_off, entries, n_entries, qscale); rc != LEON_OK) return rc;
+    const leon::ActivityLayout L = leon::activity_layout((uint32_t)mbw, (uint32_t)mbh);
+    std::vector<uint64_t> sums(3 * (size_t)L.mbs, 0);          // [ac_count | ac_mag | dc_mag][mbs]
+    std::vector<uint8_t> blocks(L.mbs, 0);
+    for (uint32_t plane = 0; plane < 3u; plane++) {
+        const uint32_t rows = plane == 0u ? 2u * G.mbh : G.mbh, groups = plane == 0u ? G.groups_y : G.groups_c;
+        const uint32_t first = plane == 0u ? 0u : G.n_y + (plane - 1u) * G.n_c;
+        for (uint32_t R = 0; R < rows; R++)
+            for (uint32_t g = 0; g < groups; g++) {
+                const uint32_t gid = first + R * groups + g;
+                uint32_t begin, end;
+                leon::activity_span(grp_off[gid], grp_off[gid + 1], n_entries, &begin, &end);
+                for (uint32_t i = begin; i < end; i++) {
+                    const uint32_t e = entries[i], a = leon::activity_abs(e);
+                    uint32_t mx, my, j;
+                    leon::activity_place(plane, R, g, leon::activity_b(e), &mx, &my, &j);
+                    if (a == 0u || mx >= G.mbw) continue;
+                    const size_t k = (size_t)my * G.mbw + mx;
+                    if (leon::activity_is_dc(e)) sums[2 * (size_t)L.mbs + k] += a;
+                    else { sums[k] += 1; sums[(size_t)L.mbs + k] += a; }
+                    blocks[k] |= (uint8_t)(1u << j);
+                }
+            }
+    }
+    uint8_t* rec = static_cast<uint8_t*>(record);
+    uint32_t s[8] = {};
+    for (size_t k = 0; k < L.mbs; k++) {
+        uint32_t cell[2];
+        leon::activity_cell(sums[k], sums[(size_t)L.mbs + k], sums[2 * (size_t)L.mbs + k], blocks[k], qscale[k], &cell[0], &cell[1]);
+        leon::activity_count(cell[0], cell[1], s);
+        memcpy(rec + 8 * k, cell, 8);
+    }
+    memcpy(rec + L.summary_offset, s, 32);
+    return LEON_OK;
+}
+
+int activity_layout_host(int32_t mbw, int32_t mbh, struct leon_pipeline_activity_layout* out)
+{
+    if (!out) return fail(LEON_ERR_INVALID, "null argument");
+    if (const int rc = mb_grid_check("activity layout", mbw, mbh); rc != LEON_OK) return rc;
+    const leon::ActivityLayout L = leon::activity_layout((uint32_t)mbw, (uint32_t)mbh);
+    memset(out, 0, sizeof(*out));
+    out->mb_width = mbw; out->mb_height = mbh; out->mbs = (int32_t)L.mbs;
+    out->summary_offset = L.summary_offset; out->record_bytes = L.record_bytes; out->record_pitch = L.record_pitch;
+    return LEON_OK;
+}
+
+// both kernels on lists the caller supplies (leon_pipeline_activity_kernel): memory of its own, the null stream.  One device allocation
+// [descriptors | lists | ring]: every array of every picture in a piece of its own, padded as MapLayout pads it (gpad, entries_pad,
+// mpad) with pad_byte; the caller's ring goes up and comes back whole.
+int activity_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipeline_activity_picture* pics, int32_t n_pics, const leon_pipeline_motion_kernel_frame* frames,
+                    int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring)
+{
+    if (!pics || !frames || !ring) return fail(LEON_ERR_INVALID, "null argument");
+    if (const int rc = mb_grid_check("activity kernel", mbw, mbh); rc != LEON_OK) return rc;
+    if (const int rc = kernel_counts_check("activity kernel", n_pics, n_frames, ring_frames, pad_byte); rc != LEON_OK) return rc;
+    const leon::ActivityGeom G = leon::activity_geom((uint32_t)mbw, (uint32_t)mbh);
+    const size_t n_off = (size_t)G.n_y + 2 * (size_t)G.n_c + 1;
+    const MapLayout M = map_layout((size_t)mbw * (size_t)mbh, n_off - 1);
+    size_t lists_bytes = 0;
+    for (int32_t i = 0; i < n_pics; i++) {
+        const leon_pipeline_activity_picture& q = pics[i];
+        if (q.reserved0) return fail(LEON_ERR_INVALID, "activity kernel: a reserved word of picture %d is not 0", i);
+        if (q.n_entries > (1u << 30)) return fail(LEON_ERR_INVALID, "activity kernel: picture %d has %u entries (at most 2^30)", i, q.n_entries);
+        if (const int rc = activity_lists_check("activity kernel", G, q.grp_off, q.entries, q.n_entries, q.qscale); rc != LEON_OK) return rc;
+        lists_bytes += M.gpad + MapLayout::entries_pad(q.n_entries) + M.mpad;
+    }
+    if (const int rc = kernel_frames_check("activity kernel", n_pics, frames, n_frames, ring_frames); rc != LEON_OK) return rc;
+    const leon::ActivityLayout L = leon::activity_layout((uint32_t)mbw, (uint32_t)mbh);
+    const size_t descs_bytes = pad256((size_t)n_frames * sizeof(leon::ActivityDesc)), ring_bytes = (size_t)ring_frames * L.record_pitch;
+    const size_t bytes = descs_bytes + lists_bytes + ring_bytes;
+    HIP_TRY(hipSetDevice(device_id));
+    DevBuf<uint8_t> d;
+    if (!d.alloc(bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "activity kernel: %zu bytes of device memory", bytes); }
+    uint8_t *d_lists = d + descs_bytes, *d_ring = d_lists + lists_bytes;
+    // the lists as the device will hold them, staged on the host: the pad byte everywhere, then each array into its piece
+    std::vector<uint8_t> lists(lists_bytes, (uint8_t)pad_byte);
+    std::vector<leon::ActivityDesc> pic_descs((size_t)n_pics);
+    size_t at = 0;
+    auto place = [&](const void* src, size_t n, size_t padded) {
+        if (n) memcpy(lists.data() + at, src, n);
+        const uint8_t* dev = d_lists + at;
+        at += padded;
+        return dev;
+    };
+    for (int32_t i = 0; i < n_pics; i++) {
+        const leon_pipeline_activity_picture& q = pics[i];
+        leon::ActivityDesc& D = pic_descs[(size_t)i];
+        D = leon::ActivityDesc{};
+        D.grp_off = reinterpret_cast<const uint32_t*>(place(q.grp_off, n_off * 4, M.gpad));
+        D.entries = reinterpret_cast<const uint32_t*>(place(q.entries, (size_t)q.n_entries * 4, MapLayout::entries_pad(q.n_entries)));
+        D.qscale = place(q.qscale, M.mbs, M.mpad);
+        D.n_entries = q.n_entries;
+    }
+    std::vector<leon::ActivityDesc> descs((size_t)n_frames);
+    for (int32_t i = 0; i < n_frames; i++) {
+        descs[(size_t)i] = pic_descs[(size_t)frames[i].picture];
+        descs[(size_t)i].frame = (uint32_t)frames[i].ring;
+    }
+    HIP_TRY(hipMemcpy(d, descs.data(), descs.size() * sizeof(leon::ActivityDesc), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_lists, lists.data(), lists_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ring, ring, ring_bytes, hipMemcpyHostToDevice));
+    activity_launch(reinterpret_cast<const leon::ActivityDesc*>(d.get()), (size_t)n_frames, d_ring, G, L, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(ring, d_ring, ring_bytes, hipMemcpyDeviceToHost));      // (the copy waits: nothing in flight reads d when it goes)
     return LEON_OK;
 }
 
@@ -2495,6 +2687,7 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
     list_frames(p, w, levels);
     if ((rc = launch_tensors(p, w)) != LEON_OK) return rc;
     if ((rc = launch_motion(p, w)) != LEON_OK) return rc;
+    if ((rc = launch_activity(p, w)) != LEON_OK) return rc;
     if (serial) HIP_TRY(hipStreamSynchronize(p->dec->stream));
     HIP_TRY(hipEventRecord(w->done, p->dec->stream));
     return LEON_OK;
@@ -2705,10 +2898,10 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
     // writes its planes, and one leon_convert_rgba per picture (the generic k_rgba_twin) fills the window's frames.
     // The GL flavour (the reference's live display arithmetic, fp32) exists as a launch of its own only: the same road.
     if (cfg->display_flavour != LEON_RGB_CPU_TWIN && cfg->display_flavour != LEON_RGB_GL) return fail(LEON_ERR_INVALID, "display_flavour %d", cfg->display_flavour);
-    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR | LEON_PIPELINE_OUTPUT_MOTION))
+    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR | LEON_PIPELINE_OUTPUT_MOTION | LEON_PIPELINE_OUTPUT_ACTIVITY))
         return fail(LEON_ERR_INVALID, "output %d", cfg->output);
-    if (cfg->output == LEON_PIPELINE_OUTPUT_MOTION)
-        return fail(LEON_ERR_INVALID, "output %d: LEON_PIPELINE_OUTPUT_MOTION needs RGBA, YCBCR or TENSOR beside it (a pipeline that only parses is not built)", cfg->output);
+    if (cfg->output && !(cfg->output & (LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR)))
+        return fail(LEON_ERR_INVALID, "output %d: LEON_PIPELINE_OUTPUT_MOTION and _ACTIVITY need RGBA, YCBCR or TENSOR beside them (a pipeline that only parses is not built)", cfg->output);
     if (cfg->output & LEON_PIPELINE_OUTPUT_TENSOR) {
         // the tensor is defined through the CPU twin's RGBA, whose index drifts over an odd width (k_rgba_twin): refused, as yuva is
         if (p->vinfo.frame_width & 1) return fail(LEON_ERR_INVALID, "the tensor output needs an even frame_width (it is %d)", p->vinfo.frame_width);
@@ -2753,6 +2946,13 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
     if (p->output & LEON_PIPELINE_OUTPUT_MOTION) {
         if (const int mrc = mb_grid_check("motion output", p->vinfo.mb_width, p->vinfo.mb_height); mrc != LEON_OK) return mrc;
         p->motion_lay = leon::motion_layout((uint32_t)p->vinfo.mb_width, (uint32_t)p->vinfo.mb_height);
+    }
+    if (p->output & LEON_PIPELINE_OUTPUT_ACTIVITY) {
+        if (const int arc = mb_grid_check("activity output", p->vinfo.mb_width, p->vinfo.mb_height); arc != LEON_OK) return arc;
+        p->activity_lay = leon::activity_layout((uint32_t)p->vinfo.mb_width, (uint32_t)p->vinfo.mb_height);
+        p->activity_geom = leon::activity_geom((uint32_t)p->vinfo.mb_width, (uint32_t)p->vinfo.mb_height);
+        if ((int32_t)p->activity_geom.groups_y != p->vinfo.groups_y || (int32_t)p->activity_geom.groups_c != p->vinfo.groups_c)
+            return fail(LEON_ERR_INVALID, "activity output: the stream's groups (%d, %d) are not those of %d macroblocks a row", p->vinfo.groups_y, p->vinfo.groups_c, p->vinfo.mb_width);
     }
     // the GPU parser's geometry; it writes a picture's maps at the offsets of the layout the arenas give them
     p->vgeom.mbw = p->vinfo.mb_width; p->vgeom.mbh = p->vinfo.mb_height;
@@ -2869,6 +3069,10 @@ int allocate_pipeline(leon_pipeline* p)
     if (p->output & LEON_PIPELINE_OUTPUT_MOTION) {
         if ((rc = alloc_ring(p, &p->d_motion, p->motion_lay.record_pitch, "motion")) != LEON_OK) return rc;
         if (!p->motion_descs.alloc((size_t)p->R * p->W * p->max_pics)) return hip_fail(LEON_ERR_NOMEM, "motion descriptor ring");
+    }
+    if (p->output & LEON_PIPELINE_OUTPUT_ACTIVITY) {
+        if ((rc = alloc_ring(p, &p->d_activity, p->activity_lay.record_pitch, "activity")) != LEON_OK) return rc;
+        if (!p->activity_descs.alloc((size_t)p->R * p->W * p->max_pics)) return hip_fail(LEON_ERR_NOMEM, "activity descriptor ring");
     }
     if (p->gpu_parser) {
         std::vector<leon_vlc_gpu_tables> src(1);
@@ -3224,6 +3428,66 @@ int leon_pipeline_read_motion(leon_pipeline* p, int64_t window, int32_t index, i
     if (summary) HIP_TRY(hipMemcpy(summary, src + L.summary_offset, 32, hipMemcpyDeviceToHost));
     return LEON_OK;
 }
+
+int leon_pipeline_activity_layout(int32_t mb_width, int32_t mb_height, struct leon_pipeline_activity_layout* out)
+{
+    return activity_layout_host(mb_width, mb_height, out);
+}
+
+int leon_pipeline_activity_record(int32_t mb_width, int32_t mb_height, const uint32_t* grp_off, const uint32_t* entries, uint32_t n_entries,
+                                  const uint8_t* qscale, void* record)
+{
+    return activity_record_host(mb_width, mb_height, grp_off, entries, n_entries, qscale, record);
+}
+
+int leon_pipeline_activity_kernel(int32_t device_id, int32_t mb_width, int32_t mb_height, const leon_pipeline_activity_picture* pictures, int32_t n_pictures,
+                                  const leon_pipeline_motion_kernel_frame* frames, int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring)
+{
+    return activity_kernel(device_id, mb_width, mb_height, pictures, n_pictures, frames, n_frames, ring_frames, pad_byte, ring);
+}
+
+#define LEON_NEED_ACTIVITY(p) \
+    if (!(p)->d_activity) return fail(LEON_ERR_INVALID, "the pipeline has no activity output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_ACTIVITY)")
+
+int leon_pipeline_get_activity_layout(leon_pipeline* p, struct leon_pipeline_activity_layout* out)
+{
+    if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    LEON_NEED_ACTIVITY(p);
+    return activity_layout_host(p->vinfo.mb_width, p->vinfo.mb_height, out);
+}
+
+int leon_pipeline_window_activity(leon_pipeline* p, int64_t window, void** out, int32_t n)
+{
+    if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    LEON_NEED_ACTIVITY(p);
+    size_t has = 0;
+    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        has = w.activity.size();
+        if (n >= 0 && (size_t)n == has)
+            for (size_t i = 0; i < has; i++) out[i] = w.activity[i];
+    });
+    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (n < 0 || (size_t)n != has) return fail(LEON_ERR_INVALID, "window %lld has %zu activity records, not %d", (long long)window, has, n);
+    return LEON_OK;
+}
+
+int leon_pipeline_read_activity(leon_pipeline* p, int64_t window, int32_t index, void* cells, uint32_t* summary)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null argument");
+    LEON_NEED_ACTIVITY(p);
+    const uint8_t* src = nullptr;
+    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        if (index >= 0 && (size_t)index < w.activity.size()) src = static_cast<const uint8_t*>(w.activity[(size_t)index]);
+    });
+    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (!src) return fail(LEON_ERR_INVALID, "window %lld has no frame %d", (long long)window, index);
+    const leon::ActivityLayout& L = p->activity_lay;
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    if (cells) HIP_TRY(hipMemcpy(cells, src, (size_t)L.mbs * 8, hipMemcpyDeviceToHost));
+    if (summary) HIP_TRY(hipMemcpy(summary, src + L.summary_offset, 32, hipMemcpyDeviceToHost));
+    return LEON_OK;
+}
+#undef LEON_NEED_ACTIVITY
 
 int leon_pipeline_regions_check(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* regions, int32_t n,
                                 const leon_pipeline_regions_config* cfg, int32_t* bad)

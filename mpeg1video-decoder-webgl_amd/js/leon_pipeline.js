@@ -48,6 +48,11 @@
  *                                  vectors point into, -1: none), mbWidth, mbHeight}: the frame's motion record, macroblocks in raster order of
  *                                  the coded picture, with opts.motion true beside any output (include/leon_pipeline.h
  *                                  LEON_PIPELINE_OUTPUT_MOTION); read only, until the window is released
+ *   p.readActivity(window, index) -> {acCount, acMag, dcMag: Uint16Array [mbs], blocks, qscale: Uint8Array [mbs], summary: Uint32Array [8],
+ *                                  mbWidth, mbHeight}: the frame's activity record -- per macroblock how much the stream coded on top of its
+ *                                  prediction (non-DC entries, the sum of their magnitudes, the DC magnitudes, the coded block bits, the
+ *                                  quantiser scale where something is coded), with opts.activity true beside any output (include/leon_pipeline.h
+ *                                  LEON_PIPELINE_OUTPUT_ACTIVITY); until the window is released
  *   p.readRegions(window, regions, {size: [h, w], filter}) -> Buffer of n * 3 * h * w elements, packed: regions = [[frameIndex, x, y,
  *                                  width, height], ...], boxes of the window's FULL-RESOLUTION frames (a detector's boxes) each resampled to
  *                                  h x w with the pipeline's element type, table and layout (leon_pipeline_read_regions) -- any tensor
@@ -99,6 +104,7 @@ class LeonPipeline extends EventEmitter {
       output = outputs[output];
     }
     if (opts.motion) output = (output || outputs.rgba) | 32;          // LEON_PIPELINE_OUTPUT_MOTION beside whatever output resolves to
+    if (opts.activity) output = (output || outputs.rgba) | 128;       // LEON_PIPELINE_OUTPUT_ACTIVITY likewise
     let tensorDtype = opts.tensorDtype === undefined ? 0 : opts.tensorDtype;
     if (typeof tensorDtype === 'string') {
       if (!(tensorDtype in dtypes)) throw new TypeError("tensorDtype: 'float16', 'bfloat16', 'float32' or 'uint8'");
@@ -170,6 +176,21 @@ class LeonPipeline extends EventEmitter {
   readPlanes(window, index) { return this._p.readPlanes(window, index); }
   readTensor(window, index) { return this._p.readTensor(window, index); }
   readMotion(window, index) { return this._p.readMotion(window, index); }
+  // the addon hands the cells over as they lie, 8 bytes a macroblock; the fields as typed arrays of their own
+  readActivity(window, index) {
+    const r = this._p.readActivity(window, index), mbs = r.mbWidth * r.mbHeight;
+    const v = new DataView(r.cells.buffer, r.cells.byteOffset, 8 * mbs);
+    const out = { acCount: new Uint16Array(mbs), acMag: new Uint16Array(mbs), dcMag: new Uint16Array(mbs), blocks: new Uint8Array(mbs),
+      qscale: new Uint8Array(mbs), summary: r.summary, mbWidth: r.mbWidth, mbHeight: r.mbHeight };
+    for (let k = 0; k < mbs; k++) {
+      out.acCount[k] = v.getUint16(8 * k, true);
+      out.acMag[k] = v.getUint16(8 * k + 2, true);
+      out.dcMag[k] = v.getUint16(8 * k + 4, true);
+      out.blocks[k] = v.getUint8(8 * k + 6);
+      out.qscale[k] = v.getUint8(8 * k + 7);
+    }
+    return out;
+  }
   // regions: [[frameIndex, x, y, width, height], ...] of a delivered window's full-resolution frames, resampled to opts.size [h, w]
   readRegions(window, regions, opts) {
     opts = opts || {};

@@ -47,6 +47,8 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_warp_regions", "leon_pipeline_read_warp_regions", "leon_pipeline_warp_regions_device",
     "leon_pipeline_motion_layout", "leon_pipeline_motion_record", "leon_pipeline_get_motion_layout", "leon_pipeline_window_motion",
     "leon_pipeline_read_motion", "leon_pipeline_motion_kernel",
+    "leon_pipeline_activity_layout", "leon_pipeline_activity_record", "leon_pipeline_activity_kernel", "leon_pipeline_get_activity_layout",
+    "leon_pipeline_window_activity", "leon_pipeline_read_activity",
     "leon_pipeline_carry_refs", "leon_pipeline_carry_record", "leon_pipeline_get_carry_refs", "leon_pipeline_carry_regions_device",
     "leon_pipeline_carry_regions", "leon_pipeline_carry_device",
     "leon_pipeline_propagate_layout", "leon_pipeline_propagate_record", "leon_pipeline_propagate_maps_device", "leon_pipeline_propagate_maps",
@@ -63,6 +65,9 @@ PIPELINE_TENSOR_OUTPUTS = {"tensor": PIPELINE_OUTPUT_TENSOR, "rgba+tensor": PIPE
 # the motion output (LEON_PIPELINE_OUTPUT_MOTION): Pipeline(motion=True) ORs it into whatever output= resolves to
 PIPELINE_OUTPUT_MOTION = 32
 MOTION_FWD, MOTION_BWD, MOTION_INTRA = 1, 2, 4      # the bits of a motion record's info bytes
+# the activity output (LEON_PIPELINE_OUTPUT_ACTIVITY, bit 7): Pipeline(activity=True) ORs it in the same way; a record's cell
+PIPELINE_OUTPUT_ACTIVITY = 128
+ACTIVITY_CELL = np.dtype([("ac_count", "<u2"), ("ac_mag", "<u2"), ("dc_mag", "<u2"), ("blocks", "u1"), ("qscale", "u1")])
 TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 1, 2, 3       # LEON_TENSOR_*
 TENSOR_DTYPES = {"float16": TENSOR_F16, "bfloat16": TENSOR_BF16, "float32": TENSOR_F32}
 TENSOR_U8 = 8                                       # LEON_TENSOR_U8 ("uint8"): the element is the 8-bit colour value
@@ -417,6 +422,15 @@ class PipelineMotionPicture(C.Structure):
     _fields_ = [("type", C.c_int32), ("reserved0", C.c_int32), ("repadd", C.c_void_p), ("mb_dir", C.c_void_p), ("mv_fwd", C.c_void_p), ("mv_bwd", C.c_void_p)]
 
 
+class PipelineActivityLayout(C.Structure):
+    _fields_ = [("mb_width", C.c_int32), ("mb_height", C.c_int32), ("mbs", C.c_int32), ("reserved0", C.c_int32), ("summary_offset", C.c_uint64),
+                ("record_bytes", C.c_uint64), ("record_pitch", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class PipelineActivityPicture(C.Structure):
+    _fields_ = [("grp_off", C.c_void_p), ("entries", C.c_void_p), ("qscale", C.c_void_p), ("n_entries", C.c_uint32), ("reserved0", C.c_int32)]
+
+
 class PipelineFrame(C.Structure):
     _fields_ = [("gop", C.c_uint64), ("display_index", C.c_int32), ("type", C.c_int32), ("ts_ms", C.c_double),
                 ("rgba", C.c_void_p), ("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("a", C.c_void_p)]
@@ -561,6 +575,14 @@ def load():
         lib.leon_pipeline_read_motion.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.leon_pipeline_motion_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineMotionPicture), C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                                     C.c_int32, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_window_activity"):
+        lib.leon_pipeline_activity_layout.argtypes = [C.c_int32, C.c_int32, C.POINTER(PipelineActivityLayout)]
+        lib.leon_pipeline_activity_record.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_activity_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineActivityPicture), C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                      C.c_int32, C.c_void_p]
+        lib.leon_pipeline_get_activity_layout.argtypes = [C.c_void_p, C.POINTER(PipelineActivityLayout)]
+        lib.leon_pipeline_window_activity.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int32]
+        lib.leon_pipeline_read_activity.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     if hasattr(lib, "leon_pipeline_carry_regions"):
         P = C.POINTER
         lib.leon_pipeline_carry_refs.argtypes = [P(PipelineFrame), P(PipelineMotionFrame), C.c_int32, C.c_void_p, C.c_void_p]
@@ -712,6 +734,108 @@ def motion_kernel(mbw, mbh, pictures, frames, ring_frames=None, pad_byte=0, fill
     _chk(load().leon_pipeline_motion_kernel(int(device_id), int(mbw), int(mbh), pics, (0 if pictures is None else len(pictures)) if n_pictures is None else int(n_pictures),
                                             None if fr is None or not len(fr) else fr.ctypes.data, (0 if fr is None else len(fr)) if n_frames is None else int(n_frames),
                                             len(ring) if ring_frames is None else int(ring_frames), int(pad_byte), ring.ctypes.data))
+    return ring
+
+
+def activity_layout(mbw, mbh):
+    """leon_pipeline_activity_layout: where the parts of an activity record of mbw x mbh macroblocks lie (PipelineActivityLayout), no device"""
+    out = PipelineActivityLayout()
+    _chk(load().leon_pipeline_activity_layout(int(mbw), int(mbh), C.byref(out)))
+    return out
+
+
+def activity_groups(mbw, mbh):
+    """(groups_y, groups_c, n_y, n_c) of a picture of mbw x mbh macroblocks (include/leon_vlc.h); an activity record reads groups 0 .. n_y + 2 n_c - 1"""
+    gy, gc = -(-int(mbw) // 4), -(-int(mbw) // 8)
+    return gy, gc, 2 * int(mbh) * gy, int(mbh) * gc
+
+
+def _activity_parts(buf, lay):
+    """(cells [mbh, mbw] of ACTIVITY_CELL, summary [8] uint32): copies of the specified parts of a record buffer"""
+    cells = buf[:8 * lay.mbs].view(ACTIVITY_CELL).reshape(lay.mb_height, lay.mb_width).copy()
+    return cells, buf[lay.summary_offset:lay.summary_offset + 32].view(np.uint32).copy()
+
+
+def _activity_arrays(grp_off, entries, qscale):
+    return (None if grp_off is None else np.ascontiguousarray(grp_off, dtype=np.uint32), None if entries is None else np.ascontiguousarray(entries, dtype=np.uint32),
+            None if qscale is None else np.ascontiguousarray(qscale, dtype=np.uint8))
+
+
+def activity_record(mbw, mbh, grp_off, entries, qscale, n_entries=None, fill=None, record=True):
+    """leon_pipeline_activity_record: the library's CPU evaluation of a picture's activity record from its group lists (as
+    leon_vlc_ctypes.Stream gives them) and its qscale map -> (cells [mbh, mbw] of ACTIVITY_CELL, summary [8] uint32).  n_entries: the
+    count handed to the library when it is to differ from len(entries).  fill: the byte the record buffer holds beforehand -- the call
+    then returns (cells, summary, buffer), the whole record_bytes buffer as the library left it.  record=False: a null record."""
+    lay = activity_layout(mbw, mbh) if 1 <= int(mbw) <= 256 and 1 <= int(mbh) <= 256 else None
+    buf = np.full(lay.record_bytes if lay else 64, 0 if fill is None else int(fill), dtype=np.uint8)
+    keep = _activity_arrays(grp_off, entries, qscale)
+    n = (0 if keep[1] is None else keep[1].size) if n_entries is None else int(n_entries)
+    try:
+        _chk(load().leon_pipeline_activity_record(int(mbw), int(mbh), None if keep[0] is None else keep[0].ctypes.data, None if keep[1] is None or not keep[1].size else keep[1].ctypes.data,
+                                                  n, None if keep[2] is None else keep[2].ctypes.data, buf.ctypes.data if record else None))
+    except LeonError as e:
+        e.buffer = buf          # (a refusal leaves it as it was: tests look)
+        raise
+    parts = _activity_parts(buf, lay)
+    return parts if fill is None else parts + (buf,)
+
+
+def activity_from_lists(mbw, mbh, grp_off, entries, qscale):
+    """The definition of a frame's activity record (include/leon_pipeline.h, LEON_PIPELINE_OUTPUT_ACTIVITY) in numpy, written from the
+    header's text and independent of the C code: a picture's group lists and qscale map -> (cells [mbh, mbw] of ACTIVITY_CELL, summary [8]
+    uint32).  grp_off is non-decreasing; only the groups of Y, Cb and Cr are read."""
+    mbw, mbh = int(mbw), int(mbh)
+    mbs = mbw * mbh
+    gy, gc, n_y, n_c = activity_groups(mbw, mbh)
+    n = n_y + 2 * n_c
+    off = np.asarray(grp_off).reshape(-1)[:n + 1].astype(np.int64)
+    e = np.asarray(entries, dtype=np.uint32).reshape(-1)[off[0]:off[n]].astype(np.int64)
+    gid = np.repeat(np.arange(n, dtype=np.int64), np.diff(off))
+    a = np.abs((e & 0xffff).astype(np.uint16).view(np.int16).astype(np.int64))
+    b, dc = (e >> 20) & 7, (((e >> 23) & 7) == 0) & (((e >> 17) & 7) == 0)
+    luma, cr = gid < n_y, gid >= n_y + n_c
+    q = np.where(luma, gid, gid - n_y - np.where(cr, n_c, 0))
+    R, g = q // np.where(luma, gy, gc), q % np.where(luma, gy, gc)
+    mx = np.where(luma, 4 * g + (b >> 1), 8 * g + b)
+    my = np.where(luma, R >> 1, R)
+    j = np.where(luma, 2 * (R & 1) + (b & 1), 4 + cr)
+    keep = (a != 0) & (mx < mbw)
+    k = (my * mbw + mx)[keep]
+    a, dc, j = a[keep], dc[keep], j[keep]
+    # exact: ac_count, ac_mag, dc_mag (a float64 sum of integers is exact below 2^53)
+    sums = np.stack([np.bincount(k[~dc], minlength=mbs), np.bincount(k[~dc], weights=a[~dc], minlength=mbs).astype(np.int64),
+                     np.bincount(k[dc], weights=a[dc], minlength=mbs).astype(np.int64)])
+    blocks = sum((np.bincount(k[j == i], minlength=mbs) > 0).astype(np.int64) << i for i in range(6))
+    sat = np.minimum(sums, 65535)
+    cells = np.zeros(mbs, dtype=ACTIVITY_CELL)
+    cells["ac_count"], cells["ac_mag"], cells["dc_mag"], cells["blocks"] = sat[0], sat[1], sat[2], blocks
+    cells["qscale"] = np.where(blocks != 0, np.asarray(qscale, dtype=np.uint8).reshape(-1)[:mbs], 0)
+    pop = sum((blocks >> i) & 1 for i in range(6))
+    summary = np.array([int((blocks != 0).sum()), int(sat[0].sum()), int(sat[1].sum()), int(sat[2].sum()), int(sat[1].max()), int(cells["qscale"].astype(np.int64).sum()),
+                        int(pop.sum()), 0], dtype=np.uint32)
+    return cells.reshape(mbh, mbw), summary
+
+
+def activity_kernel(mbw, mbh, pictures, frames, ring_frames=None, pad_byte=0, fill=0xA5, ring=None, device_id=0, n_pictures=None, n_frames=None):
+    """leon_pipeline_activity_kernel: k_activity and k_activity_summary on lists the caller supplies.  pictures = [(grp_off, entries, qscale)
+    or (grp_off, entries, qscale, n_entries), ...] (n_entries: the capacity handed over, len(entries) by default); frames, the ring and
+    the rest as motion_kernel's.  Returns the ring, uint8 [ring_frames, record_pitch], as it came back."""
+    if ring is None:
+        ring = np.full((int(ring_frames), int(activity_layout(mbw, mbh).record_pitch)), int(fill), dtype=np.uint8)
+    assert ring.dtype == np.uint8 and ring.flags.c_contiguous and ring.flags.writeable
+    keep, pics = [], None
+    if pictures is not None:
+        pics = (PipelineActivityPicture * max(1, len(pictures)))()
+        for i, pic in enumerate(pictures):
+            arrs = _activity_arrays(*pic[:3])
+            keep.append(arrs)
+            q = pics[i]
+            q.grp_off, q.entries, q.qscale = [None if a is None or not a.size else a.ctypes.data for a in arrs]
+            q.n_entries = int(pic[3]) if len(pic) > 3 else (0 if arrs[1] is None else arrs[1].size)
+    fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32).reshape(-1, 2)
+    _chk(load().leon_pipeline_activity_kernel(int(device_id), int(mbw), int(mbh), pics, (0 if pictures is None else len(pictures)) if n_pictures is None else int(n_pictures),
+                                              None if fr is None or not len(fr) else fr.ctypes.data, (0 if fr is None else len(fr)) if n_frames is None else int(n_frames),
+                                              len(ring) if ring_frames is None else int(ring_frames), int(pad_byte), ring.ctypes.data))
     return ring
 
 
@@ -1365,8 +1489,8 @@ class _Frames:
     """the frames of a delivered window as a read-only sequence of dicts, made when asked for (a 128-GOP window has 1536 of
     them; a callback that looks at a dozen should not pay for the rest on the pipeline's notify thread)"""
 
-    def __init__(self, frames, n, pipe, window=-1, tensors=None, motion=None):
-        self._f, self._n, self._pipe, self._window, self._tensors, self._motion = frames, n, pipe, window, tensors, motion
+    def __init__(self, frames, n, pipe, window=-1, tensors=None, motion=None, activity=None):
+        self._f, self._n, self._pipe, self._window, self._tensors, self._motion, self._activity = frames, n, pipe, window, tensors, motion, activity
 
     def __len__(self):
         return self._n
@@ -1383,6 +1507,7 @@ class _Frames:
         return {"motion": None if m is None else {"record": m.record, "fwd_gop": int(m.fwd_gop), "fwd_display": m.fwd_display, "bwd_display": m.bwd_display},
                 "gop": int(f.gop), "display_index": f.display_index, "type": f.type, "ts_ms": f.ts_ms, "rgba": f.rgba,
                 "y": f.y, "cb": f.cb, "cr": f.cr, "a": f.a, "tensor": self._tensors[i] if self._tensors is not None else None,
+                "activity": self._activity[i] if self._activity is not None else None,
                 "_i": i, "_window": self._window, "_frames": self._f, "_pipe": self._pipe}
 
     def __iter__(self):
@@ -1444,6 +1569,10 @@ class Pipeline:
     vectors and an info byte (MOTION_FWD / MOTION_BWD / MOTION_INTRA), and a summary of eight words: motion_from_maps states it.
     frame["motion"] = {"record": device address, "fwd_gop", "fwd_display", "bwd_display": which pictures the vectors point into (-1: none)};
     read_motion(window, i) copies frame i's record to the host, motion_view(window, i) wraps it in place; motion_layout has the offsets.
+    activity=True (beside any output, with or without motion): every frame carries its activity record -- per macroblock how much the
+    stream coded on top of the prediction (ACTIVITY_CELL: ac_count, ac_mag, dc_mag, blocks, qscale) and a summary of eight words:
+    activity_from_lists states it.  frame["activity"] = the record's device address; read_activity(window, i) copies it to the host,
+    activity_view(window, i) wraps it in place; activity_layout has the offsets.
     Carrying boxes (motion=True): carry_regions_device(window, records) moves boxes from one frame of the window to another along those
     vectors, on the device and on torch's current stream (carry_box states one hop; carry_regions is the same from host records);
     carry_regions_gop(window, boxes, src) carries a detector's boxes on frame `src` to every frame of its GOP, ready for
@@ -1456,7 +1585,7 @@ class Pipeline:
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
                  output="rgba", tensor_dtype="float16", tensor_scale=None, tensor_bias=None, tensor_size=None, tensor_crop=None, tensor_filter=RESIZE_TRIANGLE,
-                 tensor_layout="chw", tensor_canvas=None, tensor_origin=None, tensor_pad_value=None, tensor_letterbox=None, motion=False):
+                 tensor_layout="chw", tensor_canvas=None, tensor_origin=None, tensor_pad_value=None, tensor_letterbox=None, motion=False, activity=False):
         self.lib = load()
         if tensor_letterbox is not None:
             if tensor_size is not None or tensor_canvas is not None or tensor_origin is not None:
@@ -1475,6 +1604,8 @@ class Pipeline:
         out_bits = (PIPELINE_OUTPUTS.get(output) or PIPELINE_TENSOR_OUTPUTS[output]) if isinstance(output, str) else int(output)
         if motion:
             out_bits = (out_bits or PIPELINE_OUTPUT_RGBA) | PIPELINE_OUTPUT_MOTION
+        if activity:
+            out_bits = (out_bits or PIPELINE_OUTPUT_RGBA) | PIPELINE_OUTPUT_ACTIVITY
         tcfg = None
         if out_bits > 0 and out_bits & PIPELINE_OUTPUT_TENSOR:
             tcfg = PipelineTensorConfig(_tensor_dtype_code(tensor_dtype), (C.c_float * 3)(*([0, 0, 0] if tensor_scale is None else tensor_scale)),
@@ -1547,7 +1678,12 @@ class Pipeline:
                         motion = (PipelineMotionFrame * n)()
                         if self.lib.leon_pipeline_window_motion(self.h, window, motion, n) != OK:
                             raise LeonError(ERR_INVALID, self.lib.leon_last_error().decode())
-                    fl = _Frames(frames, n, self, window, tensors, motion)
+                    activity = None
+                    if self.info.output & PIPELINE_OUTPUT_ACTIVITY and n:        # ... and its activity records
+                        activity = (C.c_void_p * n)()
+                        if self.lib.leon_pipeline_window_activity(self.h, window, activity, n) != OK:
+                            raise LeonError(ERR_INVALID, self.lib.leon_last_error().decode())
+                    fl = _Frames(frames, n, self, window, tensors, motion, activity)
                     keep = self._on_window(window, fl)
                 if keep is not False:
                     _release(window)
@@ -1605,6 +1741,11 @@ class Pipeline:
             lay = PipelineMotionLayout()
             rc = self.lib.leon_pipeline_get_motion_layout(self.h, C.byref(lay))
             self.motion_layout = lay
+        self.activity_layout = None
+        if rc == OK and info.output & PIPELINE_OUTPUT_ACTIVITY:
+            lay = PipelineActivityLayout()
+            rc = self.lib.leon_pipeline_get_activity_layout(self.h, C.byref(lay))
+            self.activity_layout = lay
         ready.set()
         _chk(rc)
 
@@ -1650,6 +1791,46 @@ class Pipeline:
             return torch.as_tensor(v, device=dev)
         return (view(0, (lay.mb_height, lay.mb_width, 4), "<i2", (lay.mb_width * 8, 8, 2)),
                 view(lay.info_offset, (lay.mb_height, lay.mb_width), "|u1", (lay.mb_width, 1)),
+                view(lay.summary_offset, (8,), "<i4", (4,)))
+
+    def window_activity(self, window, n):
+        """leon_pipeline_window_activity: the device addresses of the n activity records of a delivered, not yet released window"""
+        out = (C.c_void_p * max(1, int(n)))()
+        _chk(self.lib.leon_pipeline_window_activity(self.h, int(window), out, int(n)))
+        return out
+
+    def read_activity(self, window, index):
+        """the activity record of frame `index` of a delivered, not yet released window as host arrays:
+        (cells [mbh, mbw] of ACTIVITY_CELL, summary [8] uint32)"""
+        lay = self.activity_layout
+        mbw, mbh = (lay.mb_width, lay.mb_height) if lay is not None else (1, 1)      # (without the output the library refuses below)
+        cells = np.empty((mbh, mbw), dtype=ACTIVITY_CELL)
+        summary = np.empty(8, dtype=np.uint32)
+        _chk(self.lib.leon_pipeline_read_activity(self.h, int(window), int(index), cells.ctypes.data, summary.ctypes.data))
+        return cells, summary
+
+    def activity_view(self, window, index, device_id=None):
+        """the same record where it lies, as torch views of device memory, without copying: (words int16 [mbh, mbw, 4] -- ac_count, ac_mag,
+        dc_mag and blocks | qscale << 8 as their 16 bits, torch has no uint16 arithmetic --, bytes uint8 [mbh, mbw, 8] over the same
+        cells, summary int32 [8], the 32 bits of each word); valid until the window is released"""
+        import torch
+        lay = self.activity_layout
+        if lay is None:
+            raise LeonError(ERR_INVALID, "the pipeline has no activity output (Pipeline activity=True)")
+        n = self._window_n.get(int(window))
+        if n is None:
+            raise LeonError(ERR_INVALID, "window %d is not out for delivery" % int(window))
+        ptr = self.window_activity(window, n)[int(index)]
+        dev = "cuda:%d" % (self.device_id if device_id is None else device_id)
+
+        def view(at, shape, typestr, strides):
+            class _View:
+                pass
+            v = _View()
+            v.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr) + int(at), False), "strides": strides, "version": 2}
+            return torch.as_tensor(v, device=dev)
+        return (view(0, (lay.mb_height, lay.mb_width, 4), "<i2", (lay.mb_width * 8, 8, 2)),
+                view(0, (lay.mb_height, lay.mb_width, 8), "|u1", (lay.mb_width * 8, 8, 1)),
                 view(lay.summary_offset, (8,), "<i4", (4,)))
 
     def carry_refs(self, window):

@@ -648,6 +648,44 @@ napi_value PipeReadMotion(napi_env env, napi_callback_info info)
     return o;
 }
 
+// p.readActivity(window, i) -> {cells: Uint8Array [mbs][8] (per macroblock uint16 ac_count, ac_mag, dc_mag little endian, uint8 blocks, qscale),
+// summary: Uint32Array [8], mbWidth, mbHeight}: one frame's activity record (opts.activity; include/leon_pipeline.h
+// LEON_PIPELINE_OUTPUT_ACTIVITY), copied to the host; js/leon_pipeline.js splits the cells into typed arrays
+napi_value PipeReadActivity(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    int32_t i = -1;
+    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "readActivity(window, index)");
+        return nullptr;
+    }
+    struct leon_pipeline_activity_layout lay;
+    int rc = leon_pipeline_get_activity_layout(h->p, &lay);
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    napi_value o, ab[2], ta[2];
+    void* data[2] = {nullptr, nullptr};
+    const size_t mbs = (size_t)lay.mbs;
+    NAPI_OK(napi_create_object(env, &o));
+    NAPI_OK(napi_create_arraybuffer(env, mbs * 8, &data[0], &ab[0]));
+    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, mbs * 8, ab[0], 0, &ta[0]));
+    NAPI_OK(napi_create_arraybuffer(env, 32, &data[1], &ab[1]));
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, 8, ab[1], 0, &ta[1]));
+    if ((rc = leon_pipeline_read_activity(h->p, w, i, data[0], (uint32_t*)data[1])) != LEON_OK) return throw_leon(env, rc);
+    NAPI_OK(napi_set_named_property(env, o, "cells", ta[0]));
+    NAPI_OK(napi_set_named_property(env, o, "summary", ta[1]));
+    const struct { const char* name; double v; } nums[] = {{"mbWidth", (double)lay.mb_width}, {"mbHeight", (double)lay.mb_height}};
+    for (const auto& kv : nums) {
+        napi_value v;
+        NAPI_OK(napi_create_double(env, kv.v, &v));
+        NAPI_OK(napi_set_named_property(env, o, kv.name, v));
+    }
+    return o;
+}
+
 // p.readRegions(window, boxes, outHeight, outWidth, filter) -> Buffer of n * region bytes (3 * outHeight * outWidth elements of the
 // pipeline's element type and layout each, packed): leon_pipeline_read_regions.  boxes: an Int32Array of n x [frame index, x, y, width, height].
 // Five numbers more -- fit mode, anchor, pad r, g, b (leon_pipeline_regions_fit) -- make it leon_pipeline_read_regions_fit.
@@ -1101,7 +1139,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readActivity", PipeReadActivity}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));
