@@ -71,7 +71,7 @@ struct PipeWindow {
     std::vector<leon_pipeline_motion_frame> motion;      // output MOTION: frames[i]'s record and references
     std::vector<leon::MotionDesc> motion_descs;          // ... and what k_motion makes the record from
     std::vector<uint32_t> carry_table;                   // ... and per frame a leon::CarryFrame (ring id, fwd, bwd, 0): what k_carry reads
-    std::vector<void*> activity;                         // output ACTIVITY: frames[i]'s record
+    std::vector<uint8_t*> activity;                      // output ACTIVITY: frames[i]'s record
     std::vector<leon::ActivityDesc> activity_descs;      // ... and what k_activity makes the record from
     Event done;
     int status = LEON_OK;
@@ -84,6 +84,17 @@ struct VlcRing {                 // gpu_parser: per ring entry, the window's sli
 };
 
 using PipeFlow = leon_flow::Flow<GopJob, PipeWindow>;       // the thread protocol: leon_pipe_flow.h
+
+// A record output (MOTION, ACTIVITY): one record per frame in a device ring, `pitch` apart and addressed by the frame's index like its
+// planes and tensor, written by a kernel on the decoder's stream behind the last level from one descriptor per frame; per ring entry
+// the descriptors of its window's frames (pinned, device).  The window's own list of them is a PipeWindow vector (launch_records).
+template <class Desc>
+struct RecordOutput {
+    DevBuf<uint8_t> ring;
+    size_t pitch = 0;
+    Mirror<Desc> descs;
+    uint8_t* record(size_t frame) const { return ring + frame * pitch; }
+};
 
 constexpr size_t kNone = (size_t)-1;
 
@@ -137,16 +148,12 @@ struct leon_pipeline {
     std::vector<uint8_t> tensor_table;
     DevBuf<uint32_t> d_tensor_table;
     Mirror<uint32_t> tensor_ids;
-    // output MOTION: the ring of motion records (motion_lay.record_pitch apart, addressed by the frame's index like its planes and
-    // tensor), and per ring entry the descriptors of its window's frames for k_motion (pinned, device)
-    DevBuf<uint8_t> d_motion;
+    // outputs MOTION and ACTIVITY (RecordOutput), and what k_motion and k_activity take of the picture's grid
+    RecordOutput<leon::MotionDesc> motion;
     leon::MotionLayout motion_lay{};
-    Mirror<leon::MotionDesc> motion_descs;
-    // output ACTIVITY: the same for the activity records (activity_lay.record_pitch apart) and k_activity's descriptors
-    DevBuf<uint8_t> d_activity;
+    RecordOutput<leon::ActivityDesc> activity;
     leon::ActivityLayout activity_lay{};
     leon::ActivityGeom activity_geom{};
-    Mirror<leon::ActivityDesc> activity_descs;
     // ... resampled to a model's input size (leon_pipeline_tensor_resize; geom.resized = 0: the full-size tensor, k_tensor): the
     // tables of both axes as k_resample reads them -- first_x, count_x, Wx, first_y, count_y, Wy in one int32 buffer
     leon_pipeline_tensor_geometry tensor_geom{};
@@ -1168,7 +1175,7 @@ void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<
     w->activity_descs.clear();
     // output MOTION: what plan_levels gave each picture's launch to predict from, by lane and display index
     std::vector<const LevelPic*> planned;
-    if (p->d_motion) {
+    if (p->motion.ring) {
         planned.assign(w->jobs.size() * (size_t)p->max_pics, nullptr);
         for (const auto& lvl : levels)
             for (const LevelPic& it : lvl) planned[it.lane * (size_t)p->max_pics + (size_t)it.pic->tref] = &it;
@@ -1197,13 +1204,13 @@ void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<
                 f.cr = a.planes + p->planes_geom.cr_off;
                 f.a = p->vinfo.has_alpha == 1 ? a.planes + p->planes_geom.a_off : nullptr;
             }
-            if (p->d_motion) {
-                const PipePic& m = *by_disp[k];
+            const PipePic& m = *by_disp[k];
+            const char* base = job->arena->dev;
+            auto ptr = [&](size_t off) -> const void* { return off == kNone ? nullptr : (const void*)(base + off); };
+            if (p->motion.ring) {
                 const LevelPic* it = planned[j * (size_t)p->max_pics + k];
-                const char* base = job->arena->dev;
-                auto ptr = [&](size_t off) -> const void* { return off == kNone ? nullptr : (const void*)(base + off); };
                 leon_pipeline_motion_frame mf{};
-                mf.record = p->d_motion + a.index * p->motion_lay.record_pitch;
+                mf.record = p->motion.record(a.index);
                 mf.fwd_gop = it && it->fwd_before ? job->key_gop - 1 : job->key_gop;
                 mf.fwd_display = it ? it->fwd_tref : -1;
                 mf.bwd_display = it ? it->bwd_tref : -1;
@@ -1217,11 +1224,8 @@ void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<
                 d.mv_bwd = (const uint32_t*)ptr(m.type == LEON_PIC_B ? m.mv_bwd : kNone);
                 w->motion_descs.push_back(d);
             }
-            if (p->d_activity) {
-                const PipePic& m = *by_disp[k];
-                const char* base = job->arena->dev;
-                auto ptr = [&](size_t off) -> const void* { return off == kNone ? nullptr : (const void*)(base + off); };
-                w->activity.push_back(p->d_activity + a.index * p->activity_lay.record_pitch);
+            if (p->activity.ring) {
+                w->activity.push_back(p->activity.record(a.index));
                 leon::ActivityDesc d{};
                 d.grp_off = (const uint32_t*)ptr(m.grp_off);
                 d.entries = (const uint32_t*)ptr(m.entries);
@@ -1236,7 +1240,7 @@ void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<
     }
     p->st_gops += w->jobs.size();
     w->carry_table.clear();
-    if (p->d_motion && !w->frames.empty()) {
+    if (p->motion.ring && !w->frames.empty()) {
         const size_t n = w->frames.size();
         std::vector<int32_t> fwd(n), bwd(n);
         carry_refs_host(w->frames.data(), w->motion.data(), (int32_t)n, fwd.data(), bwd.data());
@@ -1343,6 +1347,36 @@ int record_count_check(const char* who, const char* noun, int32_t n)
 {
     return n < 1 || n > 65535 ? fail(LEON_ERR_INVALID, "%s: %d %s (a call takes 1 .. 65535)", who, n, noun) : LEON_OK;
 }
+int no_output(const char* name, const char* flag)          // a call for an output the pipeline was made without: its lower-case name, its flag's
+{
+    return fail(LEON_ERR_INVALID, "the pipeline has no %s output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_%s)", name, flag);
+}
+// The n per-frame items of a delivered window -- `items`: which PipeWindow vector; `noun`: what the count message calls them -- for the
+// window_* calls, and frame `index`'s item alone for the read_* calls.  Not through window_delivered: a window delivered with an error
+// still answers these.
+template <class T, class Out>
+int window_items(leon_pipeline* p, int64_t window, std::vector<T> PipeWindow::*items, const char* noun, Out* out, int32_t n)
+{
+    size_t has = 0;
+    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        has = (w.*items).size();
+        if (n >= 0 && (size_t)n == has) std::copy((w.*items).begin(), (w.*items).end(), out);
+    });
+    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (n < 0 || (size_t)n != has) return fail(LEON_ERR_INVALID, "window %lld has %zu %s, not %d", (long long)window, has, noun, n);
+    return LEON_OK;
+}
+template <class T>
+int window_item(leon_pipeline* p, int64_t window, int32_t index, std::vector<T> PipeWindow::*items, T* out)
+{
+    bool has = false;
+    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
+        if ((has = index >= 0 && (size_t)index < (w.*items).size())) *out = (w.*items)[(size_t)index];
+    });
+    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
+    if (!has) return fail(LEON_ERR_INVALID, "window %lld has no frame %d", (long long)window, index);
+    return LEON_OK;
+}
 int mb_grid_check(const char* who, int32_t mbw, int32_t mbh)
 {
     if (mbw >= 1 && mbw <= leon::kMotionMaxMb && mbh >= 1 && mbh <= leon::kMotionMaxMb) return LEON_OK;
@@ -1369,23 +1403,31 @@ void motion_launch(const leon::MotionDesc* descs, size_t n, uint8_t* ring, const
     }
 }
 
-int launch_motion(leon_pipeline* p, const PipeWindow* w)
+// A window's records: its descriptors, each checked (`check(i, d)`: LEON_OK or the refusal it states), staged in the ring entry's part
+// of the mirror, up with one copy on the decoder's stream, then `launch(device descriptors, n)`
+template <class Desc, class Check, class Launch>
+int launch_records(leon_pipeline* p, const PipeWindow* w, const RecordOutput<Desc>& out, const std::vector<Desc>& descs, Check check, Launch launch)
 {
-    const size_t n = w->motion_descs.size();
-    if (!p->d_motion || !n) return LEON_OK;
-    const size_t entry = (size_t)p->W * p->max_pics;
-    leon::MotionDesc* h = p->motion_descs.host() + (size_t)w->ring * entry;      // the ring entry is this window's: its previous launch has finished
-    leon::MotionDesc* dv = p->motion_descs.dev() + (size_t)w->ring * entry;
+    const size_t n = descs.size();
+    if (!out.ring || !n) return LEON_OK;
+    const size_t at = (size_t)w->ring * p->W * p->max_pics;      // the ring entry is this window's: its previous launch has finished
+    Desc *h = out.descs.host() + at, *dv = out.descs.dev() + at;
     for (size_t i = 0; i < n; i++) {
-        const leon::MotionDesc& d = w->motion_descs[i];
-        if (!motion_maps_present(d.type, d.repadd, d.mb_dir, d.mv_fwd, d.mv_bwd))
-            return fail(LEON_ERR_INVALID, "motion: frame %zu of window %lld (type %d) lacks a map", i, (long long)w->id, d.type);
-        h[i] = d;
+        if (const int rc = check(i, descs[i]); rc != LEON_OK) return rc;
+        h[i] = descs[i];
     }
-    HIP_TRY(hipMemcpyAsync(dv, h, n * sizeof(leon::MotionDesc), hipMemcpyHostToDevice, p->dec->stream));
-    motion_launch(dv, n, p->d_motion, p->motion_lay, p->dec->stream);
+    HIP_TRY(hipMemcpyAsync(dv, h, n * sizeof(Desc), hipMemcpyHostToDevice, p->dec->stream));
+    launch(dv, n);
     HIP_TRY(hipGetLastError());
     return LEON_OK;
+}
+
+int launch_motion(leon_pipeline* p, const PipeWindow* w)
+{
+    return launch_records(p, w, p->motion, w->motion_descs, [&](size_t i, const leon::MotionDesc& d) {
+        if (motion_maps_present(d.type, d.repadd, d.mb_dir, d.mv_fwd, d.mv_bwd)) return (int)LEON_OK;
+        return fail(LEON_ERR_INVALID, "motion: frame %zu of window %lld (type %d) lacks a map", i, (long long)w->id, d.type);
+    }, [&](const leon::MotionDesc* dv, size_t n) { motion_launch(dv, n, p->motion.ring, p->motion_lay, p->dec->stream); });
 }
 
 // the definition on the CPU: the same per-macroblock text (leon_motion.h), the specified bytes of one record
@@ -1414,9 +1456,6 @@ int motion_record_host(int32_t type, int32_t mbw, int32_t mbh, const uint8_t* re
     return LEON_OK;
 }
 
-// k_motion on maps the caller supplies (leon_pipeline_motion_kernel): memory of its own, the null stream.  One device allocation
-// [descriptors | maps | ring]: every map of every picture in a piece of its own, padded as MapLayout pads it (mpad, vpad) with
-// pad_byte; the caller's ring goes up and comes back whole.
 static_assert(sizeof(leon_pipeline_motion_picture) == 40 && sizeof(leon_pipeline_motion_kernel_frame) == 8, "include/leon_pipeline.h states the sizes");
 // what the diagnostics that run a record kernel on a caller's pictures (motion_kernel, activity_kernel) refuse of their counts and frames
 int kernel_counts_check(const char* who, int32_t n_pics, int32_t n_frames, int32_t ring_frames, int32_t pad_byte)
@@ -1440,66 +1479,84 @@ int kernel_frames_check(const char* who, int32_t n_pics, const leon_pipeline_mot
     }
     return LEON_OK;
 }
-int motion_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipeline_motion_picture* pics, int32_t n_pics, const leon_pipeline_motion_kernel_frame* frames,
-                  int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring)
+// A record kernel on a caller's pictures (motion_kernel, activity_kernel): memory of its own, the null stream.  One device allocation
+// [descriptors | payload | ring]: every array of every picture in a piece of its own, padded with pad_byte; the caller's ring of
+// records `pitch` apart goes up and comes back whole.  `sized(i, picture, &bytes)` refuses picture i or gives the bytes its pieces
+// take; `fill(picture, place)` makes its descriptor, `place(src, n, padded)` copying n bytes into the next piece of `padded` and
+// returning where the device will hold it; `launch(descriptors, n_frames, ring)`.  Nothing touches the device before every refusal.
+template <class Desc, class Pic, class Sized, class Fill, class Launch>
+int record_kernel(const char* who, int32_t device_id, int32_t mbw, int32_t mbh, const Pic* pics, int32_t n_pics, const leon_pipeline_motion_kernel_frame* frames,
+                  int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring, size_t pitch, Sized sized, Fill fill, Launch launch)
 {
     if (!pics || !frames || !ring) return fail(LEON_ERR_INVALID, "null argument");
-    if (const int rc = mb_grid_check("motion kernel", mbw, mbh); rc != LEON_OK) return rc;
-    if (const int rc = kernel_counts_check("motion kernel", n_pics, n_frames, ring_frames, pad_byte); rc != LEON_OK) return rc;
-    const MapLayout M = map_layout((size_t)mbw * (size_t)mbh, 0);
-    size_t maps_bytes = 0;
+    if (const int rc = mb_grid_check(who, mbw, mbh); rc != LEON_OK) return rc;
+    if (const int rc = kernel_counts_check(who, n_pics, n_frames, ring_frames, pad_byte); rc != LEON_OK) return rc;
+    size_t payload_bytes = 0;
     for (int32_t i = 0; i < n_pics; i++) {
-        const leon_pipeline_motion_picture& q = pics[i];
-        if (q.type != LEON_PIC_I && q.type != LEON_PIC_P && q.type != LEON_PIC_B) return fail(LEON_ERR_INVALID, "motion kernel: picture %d has type %d", i, q.type);
-        if (q.reserved0) return fail(LEON_ERR_INVALID, "motion kernel: a reserved word of picture %d is not 0", i);
-        if (!motion_maps_present(q.type, q.repadd, q.mb_dir, q.mv_fwd, q.mv_bwd))
-            return fail(LEON_ERR_INVALID, "motion kernel: picture %d (type %d) lacks a map", i, q.type);
-        maps_bytes += q.type == LEON_PIC_I ? 0 : (q.type == LEON_PIC_P ? 1 : 2) * (M.mpad + M.vpad);
+        size_t b = 0;
+        if (const int rc = sized(i, pics[i], &b); rc != LEON_OK) return rc;
+        payload_bytes += b;
     }
-    if (const int rc = kernel_frames_check("motion kernel", n_pics, frames, n_frames, ring_frames); rc != LEON_OK) return rc;
-    const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
-    const size_t descs_bytes = pad256((size_t)n_frames * sizeof(leon::MotionDesc)), ring_bytes = (size_t)ring_frames * L.record_pitch;
-    const size_t bytes = descs_bytes + maps_bytes + ring_bytes;
+    if (const int rc = kernel_frames_check(who, n_pics, frames, n_frames, ring_frames); rc != LEON_OK) return rc;
+    const size_t descs_bytes = pad256((size_t)n_frames * sizeof(Desc)), ring_bytes = (size_t)ring_frames * pitch;
+    const size_t bytes = descs_bytes + payload_bytes + ring_bytes;
     HIP_TRY(hipSetDevice(device_id));
     DevBuf<uint8_t> d;
-    if (!d.alloc(bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "motion kernel: %zu bytes of device memory", bytes); }
-    uint8_t *d_maps = d + descs_bytes, *d_ring = d_maps + maps_bytes;
-    // the maps as the device will hold them, staged on the host: the pad byte everywhere, then each map into its piece
-    std::vector<uint8_t> maps(maps_bytes, (uint8_t)pad_byte);
-    std::vector<leon::MotionDesc> pic_descs((size_t)n_pics);
+    if (!d.alloc(bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "%s: %zu bytes of device memory", who, bytes); }
+    uint8_t *d_payload = d + descs_bytes, *d_ring = d_payload + payload_bytes;
+    // the payload as the device will hold it, staged on the host: the pad byte everywhere, then each array into its piece
+    std::vector<uint8_t> payload(payload_bytes, (uint8_t)pad_byte);
     size_t at = 0;
     auto place = [&](const void* src, size_t n, size_t padded) {
-        memcpy(maps.data() + at, src, n);
-        const uint8_t* dev = d_maps + at;
+        if (n) memcpy(payload.data() + at, src, n);          // (a picture's empty list may be null)
+        const uint8_t* dev = d_payload + at;
         at += padded;
         return dev;
     };
-    for (int32_t i = 0; i < n_pics; i++) {
-        const leon_pipeline_motion_picture& q = pics[i];
-        leon::MotionDesc& D = pic_descs[(size_t)i];
-        D = leon::MotionDesc{};
-        D.type = q.type;
-        if (q.type != LEON_PIC_I) {
-            D.repadd = place(q.repadd, M.mbs, M.mpad);
-            D.mv_fwd = reinterpret_cast<const uint32_t*>(place(q.mv_fwd, M.mbs * 4, M.vpad));
-        }
-        if (q.type == LEON_PIC_B) {
-            D.mb_dir = place(q.mb_dir, M.mbs, M.mpad);
-            D.mv_bwd = reinterpret_cast<const uint32_t*>(place(q.mv_bwd, M.mbs * 4, M.vpad));
-        }
-    }
-    std::vector<leon::MotionDesc> descs((size_t)n_frames);
+    std::vector<Desc> pic_descs((size_t)n_pics), descs((size_t)n_frames);
+    for (int32_t i = 0; i < n_pics; i++) pic_descs[(size_t)i] = fill(pics[i], place);
     for (int32_t i = 0; i < n_frames; i++) {
         descs[(size_t)i] = pic_descs[(size_t)frames[i].picture];
         descs[(size_t)i].frame = (uint32_t)frames[i].ring;
     }
-    HIP_TRY(hipMemcpy(d, descs.data(), descs.size() * sizeof(leon::MotionDesc), hipMemcpyHostToDevice));
-    if (maps_bytes) HIP_TRY(hipMemcpy(d_maps, maps.data(), maps_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d, descs.data(), descs.size() * sizeof(Desc), hipMemcpyHostToDevice));
+    if (payload_bytes) HIP_TRY(hipMemcpy(d_payload, payload.data(), payload_bytes, hipMemcpyHostToDevice));      // (I pictures alone have none)
     HIP_TRY(hipMemcpy(d_ring, ring, ring_bytes, hipMemcpyHostToDevice));
-    motion_launch(reinterpret_cast<const leon::MotionDesc*>(d.get()), (size_t)n_frames, d_ring, L, nullptr);
+    launch(reinterpret_cast<const Desc*>(d.get()), (size_t)n_frames, d_ring);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(ring, d_ring, ring_bytes, hipMemcpyDeviceToHost));      // (the copy waits: nothing in flight reads d when it goes)
     return LEON_OK;
+}
+
+// k_motion on maps the caller supplies (leon_pipeline_motion_kernel): every map padded as MapLayout pads it (mpad, vpad)
+int motion_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipeline_motion_picture* pics, int32_t n_pics, const leon_pipeline_motion_kernel_frame* frames,
+                  int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring)
+{
+    const MapLayout M = map_layout((size_t)mbw * (size_t)mbh, 0);
+    const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+    return record_kernel<leon::MotionDesc>("motion kernel", device_id, mbw, mbh, pics, n_pics, frames, n_frames, ring_frames, pad_byte, ring, L.record_pitch,
+        [&](int32_t i, const leon_pipeline_motion_picture& q, size_t* bytes) {
+            if (q.type != LEON_PIC_I && q.type != LEON_PIC_P && q.type != LEON_PIC_B) return fail(LEON_ERR_INVALID, "motion kernel: picture %d has type %d", i, q.type);
+            if (q.reserved0) return fail(LEON_ERR_INVALID, "motion kernel: a reserved word of picture %d is not 0", i);
+            if (!motion_maps_present(q.type, q.repadd, q.mb_dir, q.mv_fwd, q.mv_bwd))
+                return fail(LEON_ERR_INVALID, "motion kernel: picture %d (type %d) lacks a map", i, q.type);
+            *bytes = q.type == LEON_PIC_I ? 0 : (q.type == LEON_PIC_P ? 1 : 2) * (M.mpad + M.vpad);
+            return (int)LEON_OK;
+        },
+        [&](const leon_pipeline_motion_picture& q, auto& place) {
+            leon::MotionDesc D{};
+            D.type = q.type;
+            if (q.type != LEON_PIC_I) {
+                D.repadd = place(q.repadd, M.mbs, M.mpad);
+                D.mv_fwd = reinterpret_cast<const uint32_t*>(place(q.mv_fwd, M.mbs * 4, M.vpad));
+            }
+            if (q.type == LEON_PIC_B) {
+                D.mb_dir = place(q.mb_dir, M.mbs, M.mpad);
+                D.mv_bwd = reinterpret_cast<const uint32_t*>(place(q.mv_bwd, M.mbs * 4, M.vpad));
+            }
+            return D;
+        },
+        [&](const leon::MotionDesc* descs, size_t n, uint8_t* d_ring) { motion_launch(descs, n, d_ring, L, nullptr); });
 }
 
 int motion_layout_host(int32_t mbw, int32_t mbh, struct leon_pipeline_motion_layout* out)
@@ -1534,20 +1591,10 @@ void activity_launch(const leon::ActivityDesc* descs, size_t n, uint8_t* ring, c
 
 int launch_activity(leon_pipeline* p, const PipeWindow* w)
 {
-    const size_t n = w->activity_descs.size();
-    if (!p->d_activity || !n) return LEON_OK;
-    const size_t entry = (size_t)p->W * p->max_pics;
-    leon::ActivityDesc* h = p->activity_descs.host() + (size_t)w->ring * entry;      // the ring entry is this window's: its previous launch has finished
-    leon::ActivityDesc* dv = p->activity_descs.dev() + (size_t)w->ring * entry;
-    for (size_t i = 0; i < n; i++) {
-        const leon::ActivityDesc& d = w->activity_descs[i];
-        if (!d.grp_off || !d.entries || !d.qscale) return fail(LEON_ERR_INVALID, "activity: frame %zu of window %lld lacks its lists or its qscale map", i, (long long)w->id);
-        h[i] = d;
-    }
-    HIP_TRY(hipMemcpyAsync(dv, h, n * sizeof(leon::ActivityDesc), hipMemcpyHostToDevice, p->dec->stream));
-    activity_launch(dv, n, p->d_activity, p->activity_geom, p->activity_lay, p->dec->stream);
-    HIP_TRY(hipGetLastError());
-    return LEON_OK;
+    return launch_records(p, w, p->activity, w->activity_descs, [&](size_t i, const leon::ActivityDesc& d) {
+        if (d.grp_off && d.entries && d.qscale) return (int)LEON_OK;
+        return fail(LEON_ERR_INVALID, "activity: frame %zu of window %lld lacks its lists or its qscale map", i, (long long)w->id);
+    }, [&](const leon::ActivityDesc* dv, size_t n) { activity_launch(dv, n, p->activity.ring, p->activity_geom, p->activity_lay, p->dec->stream); });
 }
 
 // what the host calls refuse of a picture's lists: they walk them without a clamp
@@ -1614,65 +1661,31 @@ int activity_layout_host(int32_t mbw, int32_t mbh, struct leon_pipeline_activity
     return LEON_OK;
 }
 
-// both kernels on lists the caller supplies (leon_pipeline_activity_kernel): memory of its own, the null stream.  One device allocation
-// [descriptors | lists | ring]: every array of every picture in a piece of its own, padded as MapLayout pads it (gpad, entries_pad,
-// mpad) with pad_byte; the caller's ring goes up and comes back whole.
+// both kernels on lists the caller supplies (leon_pipeline_activity_kernel): every array padded as MapLayout pads it (gpad,
+// entries_pad, mpad)
 int activity_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipeline_activity_picture* pics, int32_t n_pics, const leon_pipeline_motion_kernel_frame* frames,
                     int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring)
 {
-    if (!pics || !frames || !ring) return fail(LEON_ERR_INVALID, "null argument");
-    if (const int rc = mb_grid_check("activity kernel", mbw, mbh); rc != LEON_OK) return rc;
-    if (const int rc = kernel_counts_check("activity kernel", n_pics, n_frames, ring_frames, pad_byte); rc != LEON_OK) return rc;
     const leon::ActivityGeom G = leon::activity_geom((uint32_t)mbw, (uint32_t)mbh);
     const size_t n_off = (size_t)G.n_y + 2 * (size_t)G.n_c + 1;
     const MapLayout M = map_layout((size_t)mbw * (size_t)mbh, n_off - 1);
-    size_t lists_bytes = 0;
-    for (int32_t i = 0; i < n_pics; i++) {
-        const leon_pipeline_activity_picture& q = pics[i];
-        if (q.reserved0) return fail(LEON_ERR_INVALID, "activity kernel: a reserved word of picture %d is not 0", i);
-        if (q.n_entries > (1u << 30)) return fail(LEON_ERR_INVALID, "activity kernel: picture %d has %u entries (at most 2^30)", i, q.n_entries);
-        if (const int rc = activity_lists_check("activity kernel", G, q.grp_off, q.entries, q.n_entries, q.qscale); rc != LEON_OK) return rc;
-        lists_bytes += M.gpad + MapLayout::entries_pad(q.n_entries) + M.mpad;
-    }
-    if (const int rc = kernel_frames_check("activity kernel", n_pics, frames, n_frames, ring_frames); rc != LEON_OK) return rc;
     const leon::ActivityLayout L = leon::activity_layout((uint32_t)mbw, (uint32_t)mbh);
-    const size_t descs_bytes = pad256((size_t)n_frames * sizeof(leon::ActivityDesc)), ring_bytes = (size_t)ring_frames * L.record_pitch;
-    const size_t bytes = descs_bytes + lists_bytes + ring_bytes;
-    HIP_TRY(hipSetDevice(device_id));
-    DevBuf<uint8_t> d;
-    if (!d.alloc(bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "activity kernel: %zu bytes of device memory", bytes); }
-    uint8_t *d_lists = d + descs_bytes, *d_ring = d_lists + lists_bytes;
-    // the lists as the device will hold them, staged on the host: the pad byte everywhere, then each array into its piece
-    std::vector<uint8_t> lists(lists_bytes, (uint8_t)pad_byte);
-    std::vector<leon::ActivityDesc> pic_descs((size_t)n_pics);
-    size_t at = 0;
-    auto place = [&](const void* src, size_t n, size_t padded) {
-        if (n) memcpy(lists.data() + at, src, n);
-        const uint8_t* dev = d_lists + at;
-        at += padded;
-        return dev;
-    };
-    for (int32_t i = 0; i < n_pics; i++) {
-        const leon_pipeline_activity_picture& q = pics[i];
-        leon::ActivityDesc& D = pic_descs[(size_t)i];
-        D = leon::ActivityDesc{};
-        D.grp_off = reinterpret_cast<const uint32_t*>(place(q.grp_off, n_off * 4, M.gpad));
-        D.entries = reinterpret_cast<const uint32_t*>(place(q.entries, (size_t)q.n_entries * 4, MapLayout::entries_pad(q.n_entries)));
-        D.qscale = place(q.qscale, M.mbs, M.mpad);
-        D.n_entries = q.n_entries;
-    }
-    std::vector<leon::ActivityDesc> descs((size_t)n_frames);
-    for (int32_t i = 0; i < n_frames; i++) {
-        descs[(size_t)i] = pic_descs[(size_t)frames[i].picture];
-        descs[(size_t)i].frame = (uint32_t)frames[i].ring;
-    }
-    HIP_TRY(hipMemcpy(d, descs.data(), descs.size() * sizeof(leon::ActivityDesc), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_lists, lists.data(), lists_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ring, ring, ring_bytes, hipMemcpyHostToDevice));
-    activity_launch(reinterpret_cast<const leon::ActivityDesc*>(d.get()), (size_t)n_frames, d_ring, G, L, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(ring, d_ring, ring_bytes, hipMemcpyDeviceToHost));      // (the copy waits: nothing in flight reads d when it goes)
-    return LEON_OK;
+    return record_kernel<leon::ActivityDesc>("activity kernel", device_id, mbw, mbh, pics, n_pics, frames, n_frames, ring_frames, pad_byte, ring, L.record_pitch,
+        [&](int32_t i, const leon_pipeline_activity_picture& q, size_t* bytes) {
+            if (q.reserved0) return fail(LEON_ERR_INVALID, "activity kernel: a reserved word of picture %d is not 0", i);
+            if (q.n_entries > (1u << 30)) return fail(LEON_ERR_INVALID, "activity kernel: picture %d has %u entries (at most 2^30)", i, q.n_entries);
+            *bytes = M.gpad + MapLayout::entries_pad(q.n_entries) + M.mpad;
+            return activity_lists_check("activity kernel", G, q.grp_off, q.entries, q.n_entries, q.qscale);
+        },
+        [&](const leon_pipeline_activity_picture& q, auto& place) {
+            leon::ActivityDesc D{};
+            D.grp_off = reinterpret_cast<const uint32_t*>(place(q.grp_off, n_off * 4, M.gpad));
+            D.entries = reinterpret_cast<const uint32_t*>(place(q.entries, (size_t)q.n_entries * 4, MapLayout::entries_pad(q.n_entries)));
+            D.qscale = place(q.qscale, M.mbs, M.mpad);
+            D.n_entries = q.n_entries;
+            return D;
+        },
+        [&](const leon::ActivityDesc* descs, size_t n, uint8_t* d_ring) { activity_launch(descs, n, d_ring, G, L, nullptr); });
 }
 
 // ---- regions of delivered frames as a tensor batch (leon_pipeline_resample_regions) ------------------------------------
@@ -1823,7 +1836,7 @@ int regions_pipeline_check(const leon_pipeline* p)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
     if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR) || !p->d_tensor || !p->d_planes)
-        return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+        return no_output("tensor", "TENSOR");
     const int eb = (int)p->tensor_elem, layout = p->tensor_layout;
     if (!((eb == 1 || eb == 2 || eb == 4) && (layout == leon::kLayoutChw || layout == leon::kLayoutHwc)))
         return fail(LEON_ERR_INVALID, "regions: no kernel for %d-byte elements, layout %d", eb, layout);
@@ -2271,7 +2284,7 @@ void carry_launch(hipStream_t st, const leon::CarryRecord* d_recs, const leon::C
 int carry_pipeline_check(const leon_pipeline* p)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
-    if (!p->d_motion) return fail(LEON_ERR_INVALID, "the pipeline has no motion output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_MOTION)");
+    if (!p->motion.ring) return no_output("motion", "MOTION");
     return LEON_OK;
 }
 
@@ -2294,7 +2307,7 @@ int carry_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_c
         return fail(LEON_ERR_INVALID, "carry regions: regions %p, device_out %p, device_votes %p, device_status %p: not all 4-byte aligned", (const void*)c->regions,
                     (void*)c->device_out, (void*)c->device_votes, (void*)c->device_status);
     return boxes_run(p, c->stream, call, table, pad256(std::max<size_t>(table.size(), 1) * 4), [&](hipStream_t st, uint32_t* d_table) {
-        carry_launch(st, reinterpret_cast<const leon::CarryRecord*>(c->regions), reinterpret_cast<const leon::CarryFrame*>(d_table), p->d_motion, p->vinfo.frame_width,
+        carry_launch(st, reinterpret_cast<const leon::CarryRecord*>(c->regions), reinterpret_cast<const leon::CarryFrame*>(d_table), p->motion.ring, p->vinfo.frame_width,
                      p->vinfo.frame_height, p->vinfo.mb_width, p->motion_lay, (int32_t)(table.size() / 4), n, reinterpret_cast<int32_t*>(c->device_out), c->device_votes,
                      c->device_status);
     });
@@ -2473,7 +2486,7 @@ int propagate_maps_device(leon_pipeline* p, int64_t window, const leon_pipeline_
     leon::PropagateGeom g;
     if ((rc = propagate_config_check(p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width, cfg, &g)) != LEON_OK) return rc;
     return boxes_run(p, c->stream, call, table, pad256(std::max<size_t>(table.size(), 1) * 4), [&](hipStream_t st, uint32_t* d_table) {
-        propagate_launch(st, reinterpret_cast<const leon::PropagateHop*>(c->hops), reinterpret_cast<const leon::CarryFrame*>(d_table), p->d_motion, g, p->motion_lay,
+        propagate_launch(st, reinterpret_cast<const leon::PropagateHop*>(c->hops), reinterpret_cast<const leon::CarryFrame*>(d_table), p->motion.ring, g, p->motion_lay,
                          (int32_t)(table.size() / 4), *cfg, n, static_cast<uint8_t*>(c->maps), c->device_via, c->device_status);
     });
 }
@@ -2946,10 +2959,12 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
     if (p->output & LEON_PIPELINE_OUTPUT_MOTION) {
         if (const int mrc = mb_grid_check("motion output", p->vinfo.mb_width, p->vinfo.mb_height); mrc != LEON_OK) return mrc;
         p->motion_lay = leon::motion_layout((uint32_t)p->vinfo.mb_width, (uint32_t)p->vinfo.mb_height);
+        p->motion.pitch = p->motion_lay.record_pitch;
     }
     if (p->output & LEON_PIPELINE_OUTPUT_ACTIVITY) {
         if (const int arc = mb_grid_check("activity output", p->vinfo.mb_width, p->vinfo.mb_height); arc != LEON_OK) return arc;
         p->activity_lay = leon::activity_layout((uint32_t)p->vinfo.mb_width, (uint32_t)p->vinfo.mb_height);
+        p->activity.pitch = p->activity_lay.record_pitch;
         p->activity_geom = leon::activity_geom((uint32_t)p->vinfo.mb_width, (uint32_t)p->vinfo.mb_height);
         if ((int32_t)p->activity_geom.groups_y != p->vinfo.groups_y || (int32_t)p->activity_geom.groups_c != p->vinfo.groups_c)
             return fail(LEON_ERR_INVALID, "activity output: the stream's groups (%d, %d) are not those of %d macroblocks a row", p->vinfo.groups_y, p->vinfo.groups_c, p->vinfo.mb_width);
@@ -3066,14 +3081,12 @@ int allocate_pipeline(leon_pipeline* p)
         }
     }
     if ((p->output & LEON_PIPELINE_OUTPUT_RGBA) && (rc = alloc_ring(p, &p->d_rgba, p->frame_bytes, "RGBA")) != LEON_OK) return rc;
-    if (p->output & LEON_PIPELINE_OUTPUT_MOTION) {
-        if ((rc = alloc_ring(p, &p->d_motion, p->motion_lay.record_pitch, "motion")) != LEON_OK) return rc;
-        if (!p->motion_descs.alloc((size_t)p->R * p->W * p->max_pics)) return hip_fail(LEON_ERR_NOMEM, "motion descriptor ring");
-    }
-    if (p->output & LEON_PIPELINE_OUTPUT_ACTIVITY) {
-        if ((rc = alloc_ring(p, &p->d_activity, p->activity_lay.record_pitch, "activity")) != LEON_OK) return rc;
-        if (!p->activity_descs.alloc((size_t)p->R * p->W * p->max_pics)) return hip_fail(LEON_ERR_NOMEM, "activity descriptor ring");
-    }
+    const auto alloc_records = [&](auto& out, const char* name) {          // a record output's ring (out.pitch: plan_pipeline) and its descriptor mirror
+        if (const int rrc = alloc_ring(p, &out.ring, out.pitch, name); rrc != LEON_OK) return rrc;
+        return out.descs.alloc((size_t)p->R * p->W * p->max_pics) ? (int)LEON_OK : hip_fail(LEON_ERR_NOMEM, std::string(name) + " descriptor ring");
+    };
+    if ((p->output & LEON_PIPELINE_OUTPUT_MOTION) && (rc = alloc_records(p->motion, "motion")) != LEON_OK) return rc;
+    if ((p->output & LEON_PIPELINE_OUTPUT_ACTIVITY) && (rc = alloc_records(p->activity, "activity")) != LEON_OK) return rc;
     if (p->gpu_parser) {
         std::vector<leon_vlc_gpu_tables> src(1);
         std::vector<leon::VlcTables> t(1);
@@ -3180,7 +3193,7 @@ int leon_pipeline_resize_weights(int32_t in_size, int32_t crop_start, int32_t cr
 int leon_pipeline_get_tensor_geometry(leon_pipeline* p, leon_pipeline_tensor_geometry* out)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
-    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR)) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR)) return no_output("tensor", "TENSOR");
     *out = p->tensor_geom;
     return LEON_OK;
 }
@@ -3194,7 +3207,7 @@ int leon_pipeline_create_tensor_resized(const leon_pipeline_config* cfg, const l
 int leon_pipeline_get_tensor_shape(leon_pipeline* p, leon_pipeline_tensor_shape* out)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
-    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR)) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR)) return no_output("tensor", "TENSOR");
     const int64_t h = p->tensor_geom.height, w = p->tensor_geom.width;
     const bool hwc = p->tensor_layout == LEON_TENSOR_LAYOUT_HWC;
     *out = leon_pipeline_tensor_shape{p->tensor_dtype, (int32_t)p->tensor_elem, p->tensor_layout, 3, (int32_t)h, (int32_t)w, hwc ? 1 : h * w, hwc ? 3 * w : w, hwc ? 3 : 1};
@@ -3211,7 +3224,7 @@ int leon_pipeline_create_tensor_format(const leon_pipeline_config* cfg, const le
 int leon_pipeline_get_tensor_canvas(leon_pipeline* p, leon_pipeline_tensor_canvas* out)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
-    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR)) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
+    if (!(p->output & LEON_PIPELINE_OUTPUT_TENSOR)) return no_output("tensor", "TENSOR");
     *out = p->tensor_canvas;
     return LEON_OK;
 }
@@ -3345,28 +3358,16 @@ int leon_pipeline_read_frame_planes(leon_pipeline* p, const leon_pipeline_frame*
 int leon_pipeline_window_tensors(leon_pipeline* p, int64_t window, void** out, int32_t n)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
-    if (!p->d_tensor) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
-    size_t has = 0;
-    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
-        has = w.tensors.size();
-        if (n >= 0 && (size_t)n == has)
-            for (size_t i = 0; i < has; i++) out[i] = w.tensors[i];
-    });
-    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-    if (n < 0 || (size_t)n != has) return fail(LEON_ERR_INVALID, "window %lld has %zu tensors, not %d", (long long)window, has, n);
-    return LEON_OK;
+    if (!p->d_tensor) return no_output("tensor", "TENSOR");
+    return window_items(p, window, &PipeWindow::tensors, "tensors", out, n);
 }
 
 int leon_pipeline_read_tensor(leon_pipeline* p, int64_t window, int32_t index, void* host)
 {
     if (!p || !host) return fail(LEON_ERR_INVALID, "null argument");
-    if (!p->d_tensor) return fail(LEON_ERR_INVALID, "the pipeline has no tensor output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_TENSOR)");
-    const uint8_t* src = nullptr;
-    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
-        if (index >= 0 && (size_t)index < w.tensors.size()) src = w.tensors[(size_t)index];
-    });
-    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-    if (!src) return fail(LEON_ERR_INVALID, "window %lld has no frame %d", (long long)window, index);
+    if (!p->d_tensor) return no_output("tensor", "TENSOR");
+    uint8_t* src = nullptr;
+    if (const int rc = window_item(p, window, index, &PipeWindow::tensors, &src); rc != LEON_OK) return rc;
     HIP_TRY(hipSetDevice(p->cfg.device_id));
     HIP_TRY(hipMemcpy(host, src, p->tensor_bytes, hipMemcpyDeviceToHost));
     return LEON_OK;
@@ -3392,35 +3393,24 @@ int leon_pipeline_motion_kernel(int32_t device_id, int32_t mb_width, int32_t mb_
 int leon_pipeline_get_motion_layout(leon_pipeline* p, struct leon_pipeline_motion_layout* out)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
-    if (!p->d_motion) return fail(LEON_ERR_INVALID, "the pipeline has no motion output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_MOTION)");
+    if (!p->motion.ring) return no_output("motion", "MOTION");
     return motion_layout_host(p->vinfo.mb_width, p->vinfo.mb_height, out);
 }
 
 int leon_pipeline_window_motion(leon_pipeline* p, int64_t window, leon_pipeline_motion_frame* out, int32_t n)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
-    if (!p->d_motion) return fail(LEON_ERR_INVALID, "the pipeline has no motion output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_MOTION)");
-    size_t has = 0;
-    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
-        has = w.motion.size();
-        if (n >= 0 && (size_t)n == has)
-            for (size_t i = 0; i < has; i++) out[i] = w.motion[i];
-    });
-    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-    if (n < 0 || (size_t)n != has) return fail(LEON_ERR_INVALID, "window %lld has %zu motion records, not %d", (long long)window, has, n);
-    return LEON_OK;
+    if (!p->motion.ring) return no_output("motion", "MOTION");
+    return window_items(p, window, &PipeWindow::motion, "motion records", out, n);
 }
 
 int leon_pipeline_read_motion(leon_pipeline* p, int64_t window, int32_t index, int16_t* mv, uint8_t* info, uint32_t* summary)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null argument");
-    if (!p->d_motion) return fail(LEON_ERR_INVALID, "the pipeline has no motion output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_MOTION)");
-    const uint8_t* src = nullptr;
-    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
-        if (index >= 0 && (size_t)index < w.motion.size()) src = static_cast<const uint8_t*>(w.motion[(size_t)index].record);
-    });
-    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-    if (!src) return fail(LEON_ERR_INVALID, "window %lld has no frame %d", (long long)window, index);
+    if (!p->motion.ring) return no_output("motion", "MOTION");
+    leon_pipeline_motion_frame f{};
+    if (const int rc = window_item(p, window, index, &PipeWindow::motion, &f); rc != LEON_OK) return rc;
+    const uint8_t* src = static_cast<const uint8_t*>(f.record);
     const leon::MotionLayout& L = p->motion_lay;
     HIP_TRY(hipSetDevice(p->cfg.device_id));
     if (mv) HIP_TRY(hipMemcpy(mv, src, (size_t)L.mbs * 8, hipMemcpyDeviceToHost));
@@ -3446,48 +3436,32 @@ int leon_pipeline_activity_kernel(int32_t device_id, int32_t mb_width, int32_t m
     return activity_kernel(device_id, mb_width, mb_height, pictures, n_pictures, frames, n_frames, ring_frames, pad_byte, ring);
 }
 
-#define LEON_NEED_ACTIVITY(p) \
-    if (!(p)->d_activity) return fail(LEON_ERR_INVALID, "the pipeline has no activity output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_ACTIVITY)")
-
 int leon_pipeline_get_activity_layout(leon_pipeline* p, struct leon_pipeline_activity_layout* out)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
-    LEON_NEED_ACTIVITY(p);
+    if (!p->activity.ring) return no_output("activity", "ACTIVITY");
     return activity_layout_host(p->vinfo.mb_width, p->vinfo.mb_height, out);
 }
 
 int leon_pipeline_window_activity(leon_pipeline* p, int64_t window, void** out, int32_t n)
 {
     if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
-    LEON_NEED_ACTIVITY(p);
-    size_t has = 0;
-    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
-        has = w.activity.size();
-        if (n >= 0 && (size_t)n == has)
-            for (size_t i = 0; i < has; i++) out[i] = w.activity[i];
-    });
-    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-    if (n < 0 || (size_t)n != has) return fail(LEON_ERR_INVALID, "window %lld has %zu activity records, not %d", (long long)window, has, n);
-    return LEON_OK;
+    if (!p->activity.ring) return no_output("activity", "ACTIVITY");
+    return window_items(p, window, &PipeWindow::activity, "activity records", out, n);
 }
 
 int leon_pipeline_read_activity(leon_pipeline* p, int64_t window, int32_t index, void* cells, uint32_t* summary)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null argument");
-    LEON_NEED_ACTIVITY(p);
-    const uint8_t* src = nullptr;
-    const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
-        if (index >= 0 && (size_t)index < w.activity.size()) src = static_cast<const uint8_t*>(w.activity[(size_t)index]);
-    });
-    if (!delivered) return fail(LEON_ERR_INVALID, "window %lld is not out for delivery", (long long)window);
-    if (!src) return fail(LEON_ERR_INVALID, "window %lld has no frame %d", (long long)window, index);
+    if (!p->activity.ring) return no_output("activity", "ACTIVITY");
+    uint8_t* src = nullptr;
+    if (const int rc = window_item(p, window, index, &PipeWindow::activity, &src); rc != LEON_OK) return rc;
     const leon::ActivityLayout& L = p->activity_lay;
     HIP_TRY(hipSetDevice(p->cfg.device_id));
     if (cells) HIP_TRY(hipMemcpy(cells, src, (size_t)L.mbs * 8, hipMemcpyDeviceToHost));
     if (summary) HIP_TRY(hipMemcpy(summary, src + L.summary_offset, 32, hipMemcpyDeviceToHost));
     return LEON_OK;
 }
-#undef LEON_NEED_ACTIVITY
 
 int leon_pipeline_regions_check(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_region* regions, int32_t n,
                                 const leon_pipeline_regions_config* cfg, int32_t* bad)
@@ -3642,7 +3616,7 @@ int32_t leon_pipeline_carry_record(int32_t frame_width, int32_t frame_height, in
 int leon_pipeline_get_carry_refs(leon_pipeline* p, int64_t window, int32_t* fwd, int32_t* bwd, int32_t n)
 {
     if (!p || !fwd || !bwd) return fail(LEON_ERR_INVALID, "null argument");
-    if (!p->d_motion) return fail(LEON_ERR_INVALID, "the pipeline has no motion output (leon_pipeline_config.output without LEON_PIPELINE_OUTPUT_MOTION)");
+    if (!p->motion.ring) return no_output("motion", "MOTION");
     size_t has = 0;
     const bool delivered = p->flow.with_delivered(window, [&](const PipeWindow& w) {
         has = w.carry_table.size() / 4;

@@ -718,22 +718,30 @@ def motion_kernel(mbw, mbh, pictures, frames, ring_frames=None, pad_byte=0, fill
     every map's padding on the device holds pad_byte.  Returns the ring, uint8 [ring_frames, record_pitch], as it came back: it went
     up holding `fill` in every byte -- or is the caller's `ring` (a contiguous uint8 array), written in place.  pictures, frames None:
     a null pointer; n_pictures, n_frames: the counts handed to the library when they are to differ from the lists' lengths."""
+    def one(q, pic):
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in zip(pic[1:], (np.uint8, np.uint8, np.int16, np.int16))]
+        q.type = int(pic[0])
+        q.repadd, q.mb_dir, q.mv_fwd, q.mv_bwd = [None if a is None else a.ctypes.data for a in arrs]
+        return arrs
+    return _record_kernel("leon_pipeline_motion_kernel", motion_layout, PipelineMotionPicture, one, mbw, mbh, pictures, frames, ring_frames, pad_byte, fill, ring, device_id,
+                          n_pictures, n_frames)
+
+
+def _record_kernel(symbol, layout_fn, struct, one, mbw, mbh, pictures, frames, ring_frames, pad_byte, fill, ring, device_id, n_pictures, n_frames):
+    """what motion_kernel and activity_kernel share: the ring made where the caller has none, the pictures as an array of `struct`,
+    each filled by one(structure, picture) -> the arrays it points into (kept until the call returns), the frames as int32 [n, 2], the
+    counts the lists' lengths unless the caller says otherwise, the call `symbol`"""
     if ring is None:
-        ring = np.full((int(ring_frames), int(motion_layout(mbw, mbh).record_pitch)), int(fill), dtype=np.uint8)
+        ring = np.full((int(ring_frames), int(layout_fn(mbw, mbh).record_pitch)), int(fill), dtype=np.uint8)
     assert ring.dtype == np.uint8 and ring.flags.c_contiguous and ring.flags.writeable
     keep, pics = [], None
     if pictures is not None:
-        pics = (PipelineMotionPicture * max(1, len(pictures)))()
-        for i, (t, *maps) in enumerate(pictures):
-            q = pics[i]
-            arrs = [None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in zip(maps, (np.uint8, np.uint8, np.int16, np.int16))]
-            keep.append(arrs)
-            q.type = int(t)
-            q.repadd, q.mb_dir, q.mv_fwd, q.mv_bwd = [None if a is None else a.ctypes.data for a in arrs]
+        pics = (struct * max(1, len(pictures)))()
+        keep.extend(one(pics[i], pic) for i, pic in enumerate(pictures))
     fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32).reshape(-1, 2)
-    _chk(load().leon_pipeline_motion_kernel(int(device_id), int(mbw), int(mbh), pics, (0 if pictures is None else len(pictures)) if n_pictures is None else int(n_pictures),
-                                            None if fr is None or not len(fr) else fr.ctypes.data, (0 if fr is None else len(fr)) if n_frames is None else int(n_frames),
-                                            len(ring) if ring_frames is None else int(ring_frames), int(pad_byte), ring.ctypes.data))
+    _chk(getattr(load(), symbol)(int(device_id), int(mbw), int(mbh), pics, (0 if pictures is None else len(pictures)) if n_pictures is None else int(n_pictures),
+                                 None if fr is None or not len(fr) else fr.ctypes.data, (0 if fr is None else len(fr)) if n_frames is None else int(n_frames),
+                                 len(ring) if ring_frames is None else int(ring_frames), int(pad_byte), ring.ctypes.data))
     return ring
 
 
@@ -820,23 +828,13 @@ def activity_kernel(mbw, mbh, pictures, frames, ring_frames=None, pad_byte=0, fi
     """leon_pipeline_activity_kernel: k_activity and k_activity_summary on lists the caller supplies.  pictures = [(grp_off, entries, qscale)
     or (grp_off, entries, qscale, n_entries), ...] (n_entries: the capacity handed over, len(entries) by default); frames, the ring and
     the rest as motion_kernel's.  Returns the ring, uint8 [ring_frames, record_pitch], as it came back."""
-    if ring is None:
-        ring = np.full((int(ring_frames), int(activity_layout(mbw, mbh).record_pitch)), int(fill), dtype=np.uint8)
-    assert ring.dtype == np.uint8 and ring.flags.c_contiguous and ring.flags.writeable
-    keep, pics = [], None
-    if pictures is not None:
-        pics = (PipelineActivityPicture * max(1, len(pictures)))()
-        for i, pic in enumerate(pictures):
-            arrs = _activity_arrays(*pic[:3])
-            keep.append(arrs)
-            q = pics[i]
-            q.grp_off, q.entries, q.qscale = [None if a is None or not a.size else a.ctypes.data for a in arrs]
-            q.n_entries = int(pic[3]) if len(pic) > 3 else (0 if arrs[1] is None else arrs[1].size)
-    fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32).reshape(-1, 2)
-    _chk(load().leon_pipeline_activity_kernel(int(device_id), int(mbw), int(mbh), pics, (0 if pictures is None else len(pictures)) if n_pictures is None else int(n_pictures),
-                                              None if fr is None or not len(fr) else fr.ctypes.data, (0 if fr is None else len(fr)) if n_frames is None else int(n_frames),
-                                              len(ring) if ring_frames is None else int(ring_frames), int(pad_byte), ring.ctypes.data))
-    return ring
+    def one(q, pic):
+        arrs = _activity_arrays(*pic[:3])
+        q.grp_off, q.entries, q.qscale = [None if a is None or not a.size else a.ctypes.data for a in arrs]
+        q.n_entries = int(pic[3]) if len(pic) > 3 else (0 if arrs[1] is None else arrs[1].size)
+        return arrs
+    return _record_kernel("leon_pipeline_activity_kernel", activity_layout, PipelineActivityPicture, one, mbw, mbh, pictures, frames, ring_frames, pad_byte, fill, ring,
+                          device_id, n_pictures, n_frames)
 
 
 def _floor_div(a, b):
@@ -1525,6 +1523,12 @@ def _device_tensor_check(name, t, dtype, count, dev, words=False, strided=False)
         raise ValueError("%s: a contiguous %s tensor of at least %d %s" % ((name, "int32", count, "words") if words else (name, dtype, count, "elements")))
 
 
+def _need_output(layout, name):          # the layout of a Pipeline's record output ("motion", "activity"), or the refusal of one made without it
+    if layout is None:
+        raise LeonError(ERR_INVALID, "the pipeline has no %s output (Pipeline %s=True)" % (name, name))
+    return layout
+
+
 def _empty_where_none(stream, dev, wanted):
     """wanted = [(tensor or None, shape, dtype), ...] -> the tensors, those that were None allocated on `stream` (not initialised)"""
     import torch
@@ -1749,9 +1753,12 @@ class Pipeline:
         ready.set()
         _chk(rc)
 
-    def _need_motion(self):
-        if self.motion_layout is None:
-            raise LeonError(ERR_INVALID, "the pipeline has no motion output (Pipeline motion=True)")
+    def _delivered_n(self, window):
+        """the number of frames of a window that is out for delivery"""
+        n = self._window_n.get(int(window))
+        if n is None:
+            raise LeonError(ERR_INVALID, "window %d is not out for delivery" % int(window))
+        return n
 
     def window_motion(self, window, n):
         """leon_pipeline_window_motion: the n motion frames (PipelineMotionFrame array) of a delivered, not yet released window"""
@@ -1773,25 +1780,12 @@ class Pipeline:
     def motion_view(self, window, index, device_id=None):
         """the same three parts where they lie, as torch views of device memory (int16 [mbh, mbw, 4], uint8 [mbh, mbw], int32 [8]: torch
         has no uint32 arithmetic, the words are below 2^31), without copying: valid until the window is released"""
-        import torch
-        self._need_motion()
-        lay = self.motion_layout
-        n = self._window_n.get(int(window))
-        if n is None:
-            raise LeonError(ERR_INVALID, "window %d is not out for delivery" % int(window))
-        frames = self.window_motion(window, n)
-        ptr = frames[int(index)].record
-        dev = "cuda:%d" % (self.device_id if device_id is None else device_id)
-
-        def view(at, shape, typestr, strides):
-            class _View:
-                pass
-            v = _View()
-            v.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr) + int(at), False), "strides": strides, "version": 2}
-            return torch.as_tensor(v, device=dev)
-        return (view(0, (lay.mb_height, lay.mb_width, 4), "<i2", (lay.mb_width * 8, 8, 2)),
-                view(lay.info_offset, (lay.mb_height, lay.mb_width), "|u1", (lay.mb_width, 1)),
-                view(lay.summary_offset, (8,), "<i4", (4,)))
+        lay = _need_output(self.motion_layout, "motion")
+        ptr = self.window_motion(window, self._delivered_n(window))[int(index)].record
+        dev = self.device_id if device_id is None else device_id
+        return (_cuda_view(ptr, (lay.mb_height, lay.mb_width, 4), "<i2", (lay.mb_width * 8, 8, 2), dev),
+                _cuda_view(ptr + lay.info_offset, (lay.mb_height, lay.mb_width), "|u1", (lay.mb_width, 1), dev),
+                _cuda_view(ptr + lay.summary_offset, (8,), "<i4", (4,), dev))
 
     def window_activity(self, window, n):
         """leon_pipeline_window_activity: the device addresses of the n activity records of a delivered, not yet released window"""
@@ -1813,33 +1807,18 @@ class Pipeline:
         """the same record where it lies, as torch views of device memory, without copying: (words int16 [mbh, mbw, 4] -- ac_count, ac_mag,
         dc_mag and blocks | qscale << 8 as their 16 bits, torch has no uint16 arithmetic --, bytes uint8 [mbh, mbw, 8] over the same
         cells, summary int32 [8], the 32 bits of each word); valid until the window is released"""
-        import torch
-        lay = self.activity_layout
-        if lay is None:
-            raise LeonError(ERR_INVALID, "the pipeline has no activity output (Pipeline activity=True)")
-        n = self._window_n.get(int(window))
-        if n is None:
-            raise LeonError(ERR_INVALID, "window %d is not out for delivery" % int(window))
-        ptr = self.window_activity(window, n)[int(index)]
-        dev = "cuda:%d" % (self.device_id if device_id is None else device_id)
-
-        def view(at, shape, typestr, strides):
-            class _View:
-                pass
-            v = _View()
-            v.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr) + int(at), False), "strides": strides, "version": 2}
-            return torch.as_tensor(v, device=dev)
-        return (view(0, (lay.mb_height, lay.mb_width, 4), "<i2", (lay.mb_width * 8, 8, 2)),
-                view(0, (lay.mb_height, lay.mb_width, 8), "|u1", (lay.mb_width * 8, 8, 1)),
-                view(lay.summary_offset, (8,), "<i4", (4,)))
+        lay = _need_output(self.activity_layout, "activity")
+        ptr = self.window_activity(window, self._delivered_n(window))[int(index)]
+        dev = self.device_id if device_id is None else device_id
+        return (_cuda_view(ptr, (lay.mb_height, lay.mb_width, 4), "<i2", (lay.mb_width * 8, 8, 2), dev),
+                _cuda_view(ptr, (lay.mb_height, lay.mb_width, 8), "|u1", (lay.mb_width * 8, 8, 1), dev),
+                _cuda_view(ptr + lay.summary_offset, (8,), "<i4", (4,), dev))
 
     def carry_refs(self, window):
         """leon_pipeline_get_carry_refs: (fwd, bwd) int32 arrays -- for each frame of a delivered, not yet released window the index of
         the window frame its forward and backward vectors point into (-1: none in this window), as the pipeline resolved them"""
-        self._need_motion()
-        n = self._window_n.get(int(window))
-        if n is None:
-            raise LeonError(ERR_INVALID, "window %d is not out for delivery" % int(window))
+        _need_output(self.motion_layout, "motion")
+        n = self._delivered_n(window)
         fwd, bwd = np.empty(max(1, n), dtype=np.int32), np.empty(max(1, n), dtype=np.int32)
         _chk(self.lib.leon_pipeline_get_carry_refs(self.h, int(window), fwd.ctypes.data, bwd.ctypes.data, n))
         return fwd[:n], bwd[:n]
@@ -1862,7 +1841,7 @@ class Pipeline:
         device (the caller's, or ones the method allocates, not initialised): out[i] and votes[i] are written exactly where status[i]
         is 0.  out can go to resample_regions_device as it is, and -- a new target written into column 5 -- to the next hop."""
         import torch
-        self._need_motion()
+        _need_output(self.motion_layout, "motion")
         dev = self.device_id
         if not (isinstance(records, torch.Tensor) and records.is_cuda and records.dtype == torch.int32 and records.dim() == 2 and records.shape[1] == 8
                 and records.is_contiguous()):
@@ -1885,7 +1864,7 @@ class Pipeline:
         downstream of it).  Frames of another GOP, and frames carry_plan cannot reach, have status REGION_NO_REFERENCE.
         frames: the window's frames when the pipeline did not see them delivered (dicts, or (gop, display_index, type))."""
         import torch
-        self._need_motion()
+        _need_output(self.motion_layout, "motion")
         dev = "cuda:%d" % self.device_id
         if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda and boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] == 4):
             raise ValueError("boxes: a CUDA int32 tensor [N, 4] (x, y, w, h)")
@@ -1934,7 +1913,7 @@ class Pipeline:
         through the target's motion record from maps[fwd_slot] / maps[bwd_slot] (-1: not supplied) -- propagate_map states it.
         Returns (via [n, mh, mw] uint8, status [n] int32); a record's fault is its status word (REGION_*, REGION_SLOT), never a
         LeonError, and its slot and via map keep what they held (`via_fill`).  Synchronous."""
-        self._need_motion()
+        _need_output(self.motion_layout, "motion")
         self._propagate_check(maps, stride)
         h = _records_array(hops)
         m = max(1, len(h))
@@ -1953,7 +1932,7 @@ class Pipeline:
         (the caller's, or ones the method allocates, not initialised): a slot and its via map are written exactly where status is 0.
         Hops of one call must not name another hop's dst_slot: chain the levels of propagate_plan in calls of their own."""
         import torch
-        self._need_motion()
+        _need_output(self.motion_layout, "motion")
         dev = self.device_id
         if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dim() == 4 and maps[0].is_contiguous() and maps.element_size() in (1, 2, 4)
                 and (maps.shape[0] == 1 or maps.stride(0) >= maps[0].numel())):
@@ -1997,7 +1976,7 @@ class Pipeline:
         row is a copy of `map` with via 3; a frame no chain of predictions reaches from `src` is all fill, via 0, status
         REGION_NO_REFERENCE.  frames: the window's frames when the pipeline did not see them delivered."""
         import torch
-        self._need_motion()
+        _need_output(self.motion_layout, "motion")
         dev = "cuda:%d" % self.device_id
         if not (isinstance(map, torch.Tensor) and map.is_cuda and map.dim() == 3 and map.element_size() in (1, 2, 4)):
             raise ValueError("map: a CUDA tensor [P, mh, mw] of a 1-, 2- or 4-byte dtype")
@@ -2261,14 +2240,8 @@ class Pipeline:
     def _tensor_at(self, ptr, shape, strides, device_id=None, owner=None):
         import torch
         dt = self.info.tensor_dtype
-
-        class _View:
-            pass
-        v = _View()
-        v.owner = owner          # torch.as_tensor keeps this object alive, and with it the memory's owner
-        v.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": {TENSOR_F32: "<f4", TENSOR_F16: "<f2", TENSOR_BF16: "<i2", TENSOR_U8: "|u1"}[dt],
-                                      "data": (int(ptr), False), "strides": tuple(int(x) for x in strides), "version": 2}
-        t = torch.as_tensor(v, device="cuda:%d" % (self.device_id if device_id is None else device_id))
+        t = _cuda_view(ptr, shape, {TENSOR_F32: "<f4", TENSOR_F16: "<f2", TENSOR_BF16: "<i2", TENSOR_U8: "|u1"}[dt], strides,
+                       self.device_id if device_id is None else device_id, owner)
         return t.view(torch.bfloat16) if dt == TENSOR_BF16 else t
 
     def tensor_view(self, frame, device_id=None):
@@ -2367,6 +2340,19 @@ def pool_stats():
     held, used, seg = C.c_uint64(), C.c_uint64(), C.c_int32()
     _chk(load().leon_device_pool_stats(C.byref(held), C.byref(used), C.byref(seg)))
     return {"held_bytes": held.value, "in_use_bytes": used.value, "segments": seg.value}
+
+
+def _cuda_view(ptr, shape, typestr, strides, device_id, owner=None):
+    """device memory at `ptr` as a torch tensor of `shape` and `typestr` with byte `strides`, without copying (Pipeline.motion_view,
+    activity_view and the tensor views).  owner: an object the tensor keeps alive, and with it the memory"""
+    import torch
+
+    class _View:
+        pass
+    v = _View()
+    v.owner = owner          # torch.as_tensor keeps this object alive
+    v.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "strides": tuple(int(x) for x in strides), "version": 2}
+    return torch.as_tensor(v, device="cuda:%d" % device_id)
 
 
 def device_view(ptr, nbytes, device_id=0):

@@ -12,7 +12,8 @@ import functools
 
 import numpy as np
 
-SENTINEL = 0xA5                  # what a ring holds before the launch
+from record_cases import SENTINEL, permutation  # noqa: F401  (K.SENTINEL, K.permutation in the tests)
+
 WIDTHS = (1, 4, 5, 8, 9, 12, 13, 37)
 HEIGHTS = (1, 2, 3)
 SHAPES = [(w, h) for w in WIDTHS for h in HEIGHTS]
@@ -90,15 +91,6 @@ def named():
 def expected(L, case):
     mbw, mbh, (grp_off, entries, qscale) = case
     return L.activity_from_lists(mbw, mbh, grp_off, entries, qscale)
-
-
-def permutation(n_frames, ring_frames, seed):
-    """ring indices of n_frames frames in a ring of ring_frames > n_frames records: distinct, and not the identity"""
-    assert ring_frames > n_frames
-    ring = np.random.default_rng([seed, n_frames, ring_frames]).permutation(ring_frames)[:n_frames]
-    if np.array_equal(ring, np.arange(n_frames)):
-        ring = ring[::-1].copy() if n_frames > 1 else np.array([ring_frames - 1])
-    return ring.astype(np.int32)
 
 
 def assert_record(buf, lay, want, what="", sentinel=SENTINEL):

@@ -7,9 +7,10 @@ macroblocks, a wave 256.  SHAPES are (mbw, mbh) chosen by mbs = mbw * mbh; both 
 factoring is replaced by the nearest one that has it, with the same mbs % 4 and on the same side of the boundary it stands at."""
 import numpy as np
 
+from record_cases import SENTINEL, permutation  # noqa: F401  (K.SENTINEL, K.permutation in the tests)
+
 LANES, PER_LANE = 256, 4
 TRIP = LANES * PER_LANE          # macroblocks per trip of the loop
-SENTINEL = 0xA5                  # what a ring holds before the launch
 
 SHAPES = [
     (1, 1), (2, 1), (3, 1), (4, 1), (5, 1),      # 1 .. 5: lanes 0 and 1 of one wave
@@ -91,15 +92,6 @@ def expected(L, mbw, mbh, type, m):
 def picture(type, m):
     """a picture as leon_ctypes.motion_kernel takes it"""
     return (type,) + tuple(m)
-
-
-def permutation(n_frames, ring_frames, seed):
-    """ring indices of n_frames frames in a ring of ring_frames > n_frames records: distinct, and not the identity"""
-    assert ring_frames > n_frames
-    ring = np.random.default_rng([seed, n_frames, ring_frames]).permutation(ring_frames)[:n_frames]
-    if np.array_equal(ring, np.arange(n_frames)):
-        ring = ring[::-1].copy() if n_frames > 1 else np.array([ring_frames - 1])
-    return ring.astype(np.int32)
 
 
 def without_tail_group(ring, lay):

@@ -11,17 +11,12 @@ import numpy as np
 import pytest
 
 import activity_cases as K
+import record_cases
+from record_cases import L  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 NAMES = sorted(K.named())
-
-
-@pytest.fixture(scope="module")
-def L():
-    import leon_ctypes
-    leon_ctypes.load()
-    return leon_ctypes
 
 
 @functools.lru_cache(maxsize=None)
@@ -30,13 +25,8 @@ def want(name):
     return K.expected(L_, K.named()[name])
 
 
-def run(L, mbw, mbh, pictures, wants, frame_pictures, extra=2, pad_byte=0xFF, what=""):
-    n = len(frame_pictures)
-    frames = np.stack([np.asarray(frame_pictures, dtype=np.int32), K.permutation(n, n + extra, 5)], axis=1)
-    assert frames[:, 1].max() > 0
-    ring = L.activity_kernel(mbw, mbh, pictures, frames, ring_frames=n + extra, pad_byte=pad_byte, fill=K.SENTINEL)
-    K.assert_ring(ring, L.activity_layout(mbw, mbh), frames, wants, "%s, padding 0x%02X" % (what or "%d x %d" % (mbw, mbh), pad_byte))
-    return ring
+def run(L, *case, **kw):
+    return record_cases.run(L.activity_kernel, L.activity_layout, K.assert_ring, *case, **kw)
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -15,17 +15,12 @@ import numpy as np
 import pytest
 
 import motion_cases as K
+import record_cases
+from record_cases import L  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 IDS = ["%dx%d" % s for s in K.SHAPES]
-
-
-@pytest.fixture(scope="module")
-def L():
-    import leon_ctypes
-    leon_ctypes.load()
-    return leon_ctypes
 
 
 @functools.lru_cache(maxsize=None)
@@ -36,12 +31,8 @@ def shape_case(mbw, mbh):
     return [K.picture(t, m) for t, m in zip((1, 2, 3), ms)], [K.expected(L_, mbw, mbh, t, m) for t, m in zip((1, 2, 3), ms)]
 
 
-def run(L, mbw, mbh, pictures, want, frame_pictures, extra=2, pad_byte=0xFF, what=""):
-    n = len(frame_pictures)
-    frames = np.stack([np.asarray(frame_pictures, dtype=np.int32), K.permutation(n, n + extra, 5)], axis=1)
-    ring = L.motion_kernel(mbw, mbh, pictures, frames, ring_frames=n + extra, pad_byte=pad_byte, fill=K.SENTINEL)
-    K.assert_ring(ring, L.motion_layout(mbw, mbh), frames, want, "%s, padding 0x%02X" % (what or "%d x %d" % (mbw, mbh), pad_byte))
-    return ring
+def run(L, *case, **kw):
+    return record_cases.run(L.motion_kernel, L.motion_layout, K.assert_ring, *case, **kw)
 
 
 @pytest.mark.parametrize("mbw,mbh", K.SHAPES, ids=IDS)
