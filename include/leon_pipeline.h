@@ -981,6 +981,77 @@ int leon_pipeline_propagate_maps(leon_pipeline* p, int64_t window, const leon_pi
 int leon_pipeline_propagate_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
                                    const void* const* records_host, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hops,
                                    int32_t n, void* maps, uint8_t* via, int32_t* status);
+/* Boxes gauged: what a frame's motion record (LEON_PIPELINE_OUTPUT_MOTION) and activity record (LEON_PIPELINE_OUTPUT_ACTIVITY) say
+ * under each box, on the device -- what a "run the detector again here" gate reads of a box that the carry family moved.  Integers only.
+ * Records.  A record is a leon_pipeline_region (frame, the box, three reserved words that must be 0): exactly what
+ * leon_pipeline_carry_regions_device writes, so its output goes in as it is.  Judged in regions_check's order, one text for host and
+ * device (csrc/leon_gauge.h): LEON_REGION_RESERVED (a non-zero reserved word), LEON_REGION_FRAME (frame outside the window),
+ * LEON_REGION_BOX (empty, or leaves the frame: the carry family's expression).  As in the carry and propagate families A RECORD'S FAULT
+ * IS A STATUS WORD ON BOTH ROADS, NEVER AN ERROR OF THE CALL: the boxes come from k_carry, whose refused records hold unspecified bytes.
+ * A record whose status is not 0 has not one byte of its statistics written.
+ * Cover and weight, the carry family's: macroblocks (i, j) over i = x>>4 .. (x+w-1)>>4 and the same range for j, each with the pixel
+ * area a it shares with the box, 1 .. 256 (the formula under "Votes" above).
+ * Sources.  cfg->sources is a bit set of the call: LEON_GAUGE_MOTION (1) the frame's motion record, LEON_GAUGE_ACTIVITY (2) its
+ * activity record.  The words of a source that was not asked for are written as 0.
+ * Statistics: 16 int64 words (128 bytes) a record.  With cell = the macroblock's activity cell and info, mv = its motion entry:
+ *     [0]        the sum of a: equals w * h for every accepted box; always written
+ *     [1]        the sum of a over cells with blocks != 0                                             (activity)
+ *     [2 .. 6]   the sums of a * ac_count, a * ac_mag, a * dc_mag, a * qscale, a * popcount(blocks)   (activity)
+ *     [7]        the maximum of ac_mag over the cover, unweighted                                     (activity)
+ *     [8 .. 10]  the sums of a over macroblocks with info & 1, info & 2, info & 4                     (motion)
+ *     [11]       the sum of a over macroblocks with any non-zero vector word                          (motion)
+ *     [12 .. 15] the sums of a * |fwd_h|, a * |fwd_v|, a * |bwd_h|, a * |bwd_v|                       (motion)
+ * Bounds.  The sum of a is at most 4096^2 = 2^24; a value is at most 65535, a vector's magnitude at most 32768: the largest word is
+ * below 2^41 (and every word below 2^53, exact in a double).
+ * Two identities.  Word 0 = w * h.  For a frame whose size is its coded size (a multiple of 16 an axis), the whole-frame box gives
+ * 256 x the records' own summary words: activity summary [0], [1], [2], [3], [5], [6] in words 1, 2, 3, 4, 5, 6, activity summary [4]
+ * itself in word 7, motion summary [0 .. 7] in words 8 .. 15.
+ * One launch per call (k_gauge: a 64-lane wave per record, four records per workgroup); the window's table of ring ids is the
+ * scratch it needs.  Nothing is launched on the decoder's stream. */
+#define LEON_GAUGE_MOTION   1
+#define LEON_GAUGE_ACTIVITY 2
+typedef struct leon_pipeline_gauge_config {
+    int32_t sources;                       /* LEON_GAUGE_* bits, 1 .. 3 */
+    int32_t reserved[7];                   /* must be 0 */
+} leon_pipeline_gauge_config;              /* 32 bytes */
+typedef struct leon_pipeline_gauge_regions_call {
+    const leon_pipeline_region* regions;   /* DEVICE memory, n records, 4-byte aligned */
+    int32_t  n;                            /* 1 .. 65535 */
+    int32_t  reserved0;                    /* must be 0 */
+    int64_t* device_stats;                 /* DEVICE memory, n x 16 words, 8-byte aligned */
+    int32_t* device_status;                /* DEVICE memory, n words, 4-byte aligned, may be NULL */
+    void*    stream;                       /* hipStream_t of the caller's; NULL: the pipeline's regions stream, and the call waits */
+    uint64_t reserved[3];                  /* must be 0 */
+} leon_pipeline_gauge_regions_call;        /* 64 bytes */
+/* host only: the definition on the CPU (the text the kernel compiles too) for one record, from records in host memory laid out as
+ * leon_pipeline_motion_layout / leon_pipeline_activity_layout (mb_width, mb_height) say: motion_records[i] and activity_records[i]
+ * are window frame i's; an array the sources do not ask for may be NULL, and so may the entries of frames other than rec->frame.
+ * Returns the record's status word (>= 0; stats, 16 words, is written exactly when it is 0), or LEON_ERR_INVALID (negative) for a null
+ * argument, a grid outside 1 .. 256, a frame larger than the grid or below 1, n_frames < 0, sources outside 1 .. 3, a non-zero
+ * reserved word of cfg, a NULL record where the frame's is needed. */
+int32_t leon_pipeline_gauge_record(int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                                   const void* const* motion_records, const void* const* activity_records, const leon_pipeline_gauge_config* cfg,
+                                   const leon_pipeline_region* rec, int64_t* stats);
+/* Records in DEVICE memory: the call ONLY ENQUEUES on the caller's stream (stream NULL: the regions stream, and the call waits), with
+ * leon_pipeline_carry_regions_device's ordering rules and its scratch event, word for word.  Refused (LEON_ERR_INVALID, nothing
+ * enqueued): a null cfg or call, sources outside 1 .. 3, a source whose output the pipeline was created without, a window that is not
+ * out for delivery or was delivered with an error, a null `regions` or `device_stats`, regions or device_status not 4-byte aligned,
+ * device_stats not 8-byte aligned, n outside 1 .. 65535, a non-zero reserved word of cfg or of the call. */
+int leon_pipeline_gauge_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_gauge_config* cfg,
+                                       const leon_pipeline_gauge_regions_call* call);
+/* Records in host memory, results to host memory, synchronous: the device road between an upload and the copies back.  stats
+ * (n x 16 words) and status (n words, may be NULL) go up and come back whole, so a refused record's words stay as the caller had them.
+ * The call-level refusals are the device road's. */
+int leon_pipeline_gauge_regions(leon_pipeline* p, int64_t window, const leon_pipeline_gauge_config* cfg, const leon_pipeline_region* regions,
+                                int32_t n, int64_t* stats, int32_t* status);
+/* A diagnostic in the manner of leon_pipeline_carry_device: k_gauge on records the CALLER supplies (host memory, as
+ * leon_pipeline_gauge_record takes them; NULL for frames no valid record of the call names), with memory of its own on device_id's
+ * null stream, synchronous; regions, stats and status (may be NULL) in host memory, going up and coming back whole.  Refused
+ * (LEON_ERR_INVALID): what leon_pipeline_gauge_record refuses, n outside 1 .. 65535, a valid record that names a frame without the
+ * record it needs. */
+int leon_pipeline_gauge_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                               const void* const* motion_records_host, const void* const* activity_records_host, const leon_pipeline_gauge_config* cfg,
+                               const leon_pipeline_region* regions, int32_t n, int64_t* stats, int32_t* status);
 /* A diagnostic: the DEVICE's evaluation of the tables of n_axes single axes, copied back, to be compared word for word with
  * leon_pipeline_resize_weights (pixels would hide a weight that is one unit off).  axes = n_axes x {in_size, crop_start, crop_size,
  * out_size}; with max_out the largest out_size of the batch, axis a's tables lie at a fixed pitch: first[a * max_out + o],

@@ -43,6 +43,7 @@
 #include "leon_activity.h"
 #include "leon_carry.h"
 #include "leon_propagate.h"
+#include "leon_gauge.h"
 
 
 namespace leon {
@@ -3222,6 +3223,78 @@ __global__ __launch_bounds__(kRgbaBlock) void k_propagate(const PropagateHop* __
     const int32_t p0 = (int32_t)blockIdx.y * c.g.group, p1 = p0 + c.g.group < c.g.planes ? p0 + c.g.group : c.g.planes;
     uint8_t* v = via && blockIdx.y == 0 ? via + (size_t)i * (size_t)c.g.mh * (size_t)c.g.mw : nullptr;
     propagate_unit(c.g, ring + (size_t)frames[h.target].ring * c.record_pitch, c.info_offset, maps, c.maps_bytes, c.slot_pitch, h, c.fill, v, u, p0, p1);
+}
+
+// ---- gauge: the statistics of a frame's motion and activity records under a box (include/leon_pipeline.h, leon_pipeline_gauge_regions) --
+// k_carry's shape: one 64-lane wave per record, four records per workgroup, the waves of a workgroup share nothing.  A wave judges its
+// record (leon_gauge.h; every lane the same words) and its lanes stride over the macroblocks the box covers: per lane and trip the 8
+// bytes of the activity cell, the 8 bytes of mv[k] and one byte of info[k] -- whichever the call's sources ask for, a choice that is
+// uniform over the grid --, the weight from the box, 64-bit partial sums in registers.  The sums of the sources asked for and the
+// maximum cross the wave by shuffles; lane 0 finishes and stores 16 words.  No LDS, no atomics, no barrier; idle waves of the last
+// workgroup and waves whose record is refused leave at once, a refused record with its status word alone.
+// Frame f's records lie at motion + frames[f].ring * motion_pitch and activity + frames[f].ring * activity_pitch, where k_motion and
+// k_activity wrote them (a ring the call does not read may be null).  A box inside the frame lies inside the coded grid
+// (fw <= 16 * mbw, fh <= 16 * mbh: the callers see to it), so every macroblock index is below mbs.
+struct GaugeCall {
+    int32_t fw, fh;                      // the frame
+    int32_t mbw;                         // macroblocks a row of the coded picture
+    int32_t n_frames, n;                 // frames of the window, records of the call
+    int32_t sources;                     // kGaugeMotion | kGaugeActivity
+    uint32_t info_offset, motion_pitch;  // MotionLayout's
+    uint32_t activity_pitch;             // ActivityLayout's
+    uint32_t reserved;
+};
+struct __attribute__((aligned(8))) GaugeWords2 { int64_t w[2]; };          // 16 bytes at an 8-byte aligned address
+
+__global__ __launch_bounds__(kRgbaBlock) void k_gauge(const GaugeRecord* __restrict__ recs, const CarryFrame* __restrict__ frames,
+                                                       const uint8_t* __restrict__ motion, const uint8_t* __restrict__ activity,
+                                                       int64_t* __restrict__ stats, int32_t* __restrict__ status, GaugeCall c)
+{
+    const uint32_t lane = threadIdx.x & 63u, i = blockIdx.x * (uint32_t)(kRgbaBlock / 64) + (threadIdx.x >> 6);
+    if (i >= (uint32_t)c.n) return;
+    const GaugeRecord r = recs[i];
+    const int32_t st = gauge_record_status(r, c.fw, c.fh, c.n_frames);
+    if (st != kRegionOk) {
+        if (lane == 0 && status) status[i] = st;
+        return;
+    }
+    const bool act = (c.sources & kGaugeActivity) != 0, mot = (c.sources & kGaugeMotion) != 0;
+    const uint32_t ring = frames[r.frame].ring;
+    const uint8_t* __restrict__ mrec = motion + (mot ? (size_t)ring * c.motion_pitch : 0);
+    const uint8_t* __restrict__ arec = activity + (act ? (size_t)ring * c.activity_pitch : 0);
+    GaugeSums s{};
+    const int32_t i0 = r.x >> 4, j0 = r.y >> 4;
+    const uint32_t cols = (uint32_t)(((r.x + r.width - 1) >> 4) - i0 + 1), rows = (uint32_t)(((r.y + r.height - 1) >> 4) - j0 + 1);
+    for (uint32_t k = lane; k < cols * rows; k += 64u) {
+        const uint32_t jj = k / cols, ii = k - jj * cols;
+        const int32_t mi = i0 + (int32_t)ii, mj = j0 + (int32_t)jj;
+        const uint32_t mb = (uint32_t)mj * (uint32_t)c.mbw + (uint32_t)mi;
+        uint2 cell = uint2{0u, 0u}, mv = uint2{0u, 0u};
+        uint32_t info = 0u;
+        if (act) cell = *reinterpret_cast<const uint2*>(arec + (size_t)mb * 8u);
+        if (mot) {
+            mv = *reinterpret_cast<const uint2*>(mrec + (size_t)mb * 8u);
+            info = mrec[c.info_offset + mb];
+        }
+        gauge_cell(c.sources, carry_weight(r.x, r.y, r.width, r.height, mi, mj), cell.x, cell.y, info, mv.x, mv.y, &s);
+    }
+    s.w[0] = wave_sum64(s.w[0]);
+    if (act) {
+#pragma unroll
+        for (int k = 1; k < 7; k++) s.w[k] = wave_sum64(s.w[k]);
+        s.w[7] = (int64_t)wave_max((uint32_t)s.w[7]);
+    }
+    if (mot) {
+#pragma unroll
+        for (int k = 8; k < kGaugeWords; k++) s.w[k] = wave_sum64(s.w[k]);
+    }
+    if (lane != 0) return;
+    int64_t o[kGaugeWords];
+    gauge_finish(c.sources, s, o);
+    GaugeWords2* po = reinterpret_cast<GaugeWords2*>(stats + (size_t)i * kGaugeWords);
+#pragma unroll
+    for (int k = 0; k < kGaugeWords / 2; k++) po[k] = GaugeWords2{{o[2 * k], o[2 * k + 1]}};
+    if (status) status[i] = kRegionOk;
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

@@ -1240,13 +1240,15 @@ void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<
     }
     p->st_gops += w->jobs.size();
     w->carry_table.clear();
-    if (p->motion.ring && !w->frames.empty()) {
+    // the table of either record output: both rings are indexed by the frame's own index, so one ring id serves both; without MOTION
+    // there are no references (-1), and the carry and propagate calls refuse such a pipeline before they look at the table
+    if ((p->motion.ring || p->activity.ring) && !w->frames.empty()) {
         const size_t n = w->frames.size();
-        std::vector<int32_t> fwd(n), bwd(n);
-        carry_refs_host(w->frames.data(), w->motion.data(), (int32_t)n, fwd.data(), bwd.data());
+        std::vector<int32_t> fwd(n, -1), bwd(n, -1);
+        if (p->motion.ring) carry_refs_host(w->frames.data(), w->motion.data(), (int32_t)n, fwd.data(), bwd.data());
         w->carry_table.resize(4 * n);
         for (size_t i = 0; i < n; i++) {
-            const leon::CarryFrame f{w->motion_descs[i].frame, fwd[i], bwd[i], 0u};
+            const leon::CarryFrame f{p->motion.ring ? w->motion_descs[i].frame : w->activity_descs[i].frame, fwd[i], bwd[i], 0u};
             std::memcpy(&w->carry_table[4 * i], &f, sizeof(f));
         }
     }
@@ -2425,6 +2427,185 @@ int carry_device(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32_t
                  votes ? b.votes : nullptr, status ? b.status : nullptr);
     HIP_TRY(hipGetLastError());
     return carry_host_down(b, n, out, votes, status);      // (the copies wait: nothing in flight reads the buffer when it goes)
+}
+
+// ---- boxes gauged: a frame's motion and activity records under each box (leon_pipeline_gauge_regions) ------------------------------
+static_assert(sizeof(leon_pipeline_gauge_config) == 32 && sizeof(leon_pipeline_gauge_regions_call) == 64 && sizeof(leon::GaugeRecord) == sizeof(leon_pipeline_region) &&
+              sizeof(leon::GaugeCall) == 40, "include/leon_pipeline.h states the sizes");
+static_assert(leon::kGaugeMotion == LEON_GAUGE_MOTION && leon::kGaugeActivity == LEON_GAUGE_ACTIVITY, "the kernel's bits are the header's");
+
+int gauge_config_check(const leon_pipeline_gauge_config* cfg)
+{
+    if (!cfg) return fail(LEON_ERR_INVALID, "null argument");
+    if (cfg->sources < 1 || cfg->sources > (LEON_GAUGE_MOTION | LEON_GAUGE_ACTIVITY))
+        return fail(LEON_ERR_INVALID, "gauge regions: sources %d (LEON_GAUGE_MOTION | LEON_GAUGE_ACTIVITY: 1 .. 3)", cfg->sources);
+    for (int32_t v : cfg->reserved)
+        if (v) return fail(LEON_ERR_INVALID, "gauge regions: a reserved word of the config is not 0");
+    return LEON_OK;
+}
+
+// the launch every road shares: records, the window's table and the two rings in device memory (a ring the sources do not ask for is
+// not read); ceil(n / 4) workgroups
+void gauge_launch(hipStream_t st, const leon::GaugeRecord* d_recs, const leon::CarryFrame* d_frames, const uint8_t* d_motion, const uint8_t* d_activity, int32_t fw,
+                  int32_t fh, int32_t mbw, const leon::MotionLayout& ml, const leon::ActivityLayout& al, int32_t n_frames, int32_t sources, int32_t n, int64_t* d_stats,
+                  int32_t* d_status)
+{
+    leon::GaugeCall C{};
+    C.fw = fw; C.fh = fh; C.mbw = mbw;
+    C.n_frames = n_frames; C.n = n; C.sources = sources;
+    C.info_offset = ml.info_offset; C.motion_pitch = ml.record_pitch; C.activity_pitch = al.record_pitch;
+    const unsigned per = leon::kRgbaBlock / 64;
+    hipLaunchKernelGGL(leon::k_gauge, dim3(((unsigned)n + per - 1) / per), dim3(leon::kRgbaBlock), 0, st, d_recs, d_frames, d_motion, d_activity, d_stats, d_status, C);
+}
+
+// One call of the device road: the host's refusals, then inside the boxes bracket (the window's table is all of the scratch it needs)
+// one launch on the caller's stream (or the regions stream and a wait)
+int gauge_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_gauge_config* cfg, const leon_pipeline_gauge_regions_call* c)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = gauge_config_check(cfg);
+    if (rc != LEON_OK) return rc;
+    if ((cfg->sources & LEON_GAUGE_MOTION) && !p->motion.ring) return no_output("motion", "MOTION");
+    if ((cfg->sources & LEON_GAUGE_ACTIVITY) && !p->activity.ring) return no_output("activity", "ACTIVITY");
+    if (!c) return fail(LEON_ERR_INVALID, "null argument");
+    std::unique_lock<std::mutex> call(p->regions_mu);
+    std::vector<uint32_t> table;
+    if ((rc = carry_window_table(p, window, &table)) != LEON_OK) return rc;
+    const int32_t n = c->n;
+    if (c->reserved0 || c->reserved[0] || c->reserved[1] || c->reserved[2]) return fail(LEON_ERR_INVALID, "gauge regions: a reserved word of the call is not 0");
+    if ((rc = record_count_check("gauge regions", "regions", n)) != LEON_OK) return rc;
+    if (!c->regions) return fail(LEON_ERR_INVALID, "gauge regions: null regions");
+    if (!c->device_stats) return fail(LEON_ERR_INVALID, "gauge regions: null device_stats");
+    if (((uintptr_t)c->regions | (uintptr_t)c->device_status) & 3u)
+        return fail(LEON_ERR_INVALID, "gauge regions: regions %p, device_status %p: not both 4-byte aligned", (const void*)c->regions, (void*)c->device_status);
+    if ((uintptr_t)c->device_stats & 7u) return fail(LEON_ERR_INVALID, "gauge regions: device_stats %p is not 8-byte aligned", (void*)c->device_stats);
+    const int32_t sources = cfg->sources;
+    return boxes_run(p, c->stream, call, table, pad256(std::max<size_t>(table.size(), 1) * 4), [&](hipStream_t st, uint32_t* d_table) {
+        gauge_launch(st, reinterpret_cast<const leon::GaugeRecord*>(c->regions), reinterpret_cast<const leon::CarryFrame*>(d_table), p->motion.ring, p->activity.ring,
+                     p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width, p->motion_lay, p->activity_lay, (int32_t)(table.size() / 4), sources, n, c->device_stats,
+                     c->device_status);
+    });
+}
+
+// records, results: one device allocation [stats | records | status]; what the caller has in stats and status goes up first, so that
+// the words the kernel leaves alone come back as they were
+struct GaugeHostBufs {
+    DevBuf<int64_t> d;
+    int64_t* stats = nullptr;
+    int32_t *recs = nullptr, *status = nullptr;
+};
+int gauge_host_up(GaugeHostBufs* b, size_t extra_bytes, const leon_pipeline_region* regions, int32_t n, const int64_t* stats, const int32_t* status, char** extra)
+{
+    const size_t bytes = pad256((size_t)n * (8 * leon::kGaugeWords + 32 + 4));
+    if (!b->d.alloc(bytes + extra_bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "gauge: %zu bytes of device memory", bytes + extra_bytes); }
+    b->stats = b->d; b->recs = reinterpret_cast<int32_t*>(b->stats + (size_t)n * leon::kGaugeWords); b->status = b->recs + (size_t)n * 8;
+    if (extra) *extra = reinterpret_cast<char*>(b->d.get()) + bytes;
+    HIP_TRY(hipMemcpy(b->recs, regions, (size_t)n * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->stats, stats, (size_t)n * 8 * leon::kGaugeWords, hipMemcpyHostToDevice));
+    if (status) HIP_TRY(hipMemcpy(b->status, status, (size_t)n * 4, hipMemcpyHostToDevice));
+    return LEON_OK;
+}
+int gauge_host_down(const GaugeHostBufs& b, int32_t n, int64_t* stats, int32_t* status)
+{
+    HIP_TRY(hipMemcpy(stats, b.stats, (size_t)n * 8 * leon::kGaugeWords, hipMemcpyDeviceToHost));
+    if (status) HIP_TRY(hipMemcpy(status, b.status, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return LEON_OK;
+}
+
+// One call of the host road: the device road on the regions stream between an upload and two copies
+int gauge_regions(leon_pipeline* p, int64_t window, const leon_pipeline_gauge_config* cfg, const leon_pipeline_region* regions, int32_t n, int64_t* stats, int32_t* status)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = gauge_config_check(cfg);
+    if (rc != LEON_OK) return rc;
+    if (!regions || !stats) return fail(LEON_ERR_INVALID, "gauge regions: null %s", regions ? "stats" : "regions");
+    if ((rc = record_count_check("gauge regions", "regions", n)) != LEON_OK) return rc;
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    GaugeHostBufs b;
+    if ((rc = gauge_host_up(&b, 0, regions, n, stats, status, nullptr)) != LEON_OK) return rc;
+    leon_pipeline_gauge_regions_call c{};
+    c.regions = reinterpret_cast<const leon_pipeline_region*>(b.recs);
+    c.n = n;
+    c.device_stats = b.stats;
+    c.device_status = status ? b.status : nullptr;
+    if ((rc = gauge_regions_device(p, window, cfg, &c)) != LEON_OK) return rc;      // (stream NULL: it has waited)
+    return gauge_host_down(b, n, stats, status);
+}
+
+// the definition on the CPU: the same text (leon_gauge.h) over records in host memory; the status word, or a negative error
+int32_t gauge_record_host(int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames, const void* const* motion_records, const void* const* activity_records,
+                          const leon_pipeline_gauge_config* cfg, const leon_pipeline_region* rec, int64_t* stats, bool dry)
+{
+    int rc = gauge_config_check(cfg);
+    if (rc != LEON_OK) return rc;
+    const bool mot = (cfg->sources & LEON_GAUGE_MOTION) != 0, act = (cfg->sources & LEON_GAUGE_ACTIVITY) != 0;
+    if (!rec || (!dry && !stats) || (mot && !motion_records) || (act && !activity_records)) return fail(LEON_ERR_INVALID, "null argument");
+    if ((rc = carry_geometry_check(fw, fh, mbw, mbh, n_frames)) != LEON_OK) return rc;
+    const leon::GaugeRecord& r = reinterpret_cast<const leon::GaugeRecord&>(*rec);
+    const int32_t st = leon::gauge_record_status(r, fw, fh, n_frames);
+    if (st != leon::kRegionOk) return st;
+    const uint8_t* mrec = mot ? static_cast<const uint8_t*>(motion_records[r.frame]) : nullptr;
+    const uint8_t* arec = act ? static_cast<const uint8_t*>(activity_records[r.frame]) : nullptr;
+    if ((mot && !mrec) || (act && !arec)) return fail(LEON_ERR_INVALID, "gauge: frame %d has no %s record", r.frame, mot && !mrec ? "motion" : "activity");
+    if (dry) return leon::kRegionOk;
+    const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+    leon::GaugeSums s{};
+    for (int32_t j = r.y >> 4; j <= (r.y + r.height - 1) >> 4; j++)
+        for (int32_t i = r.x >> 4; i <= (r.x + r.width - 1) >> 4; i++) {
+            const size_t mb = (size_t)j * (size_t)mbw + (size_t)i;
+            uint32_t lo = 0, hi = 0, f = 0, b = 0, info = 0;
+            if (act) {
+                memcpy(&lo, arec + 8 * mb, 4);
+                memcpy(&hi, arec + 8 * mb + 4, 4);
+            }
+            if (mot) {
+                memcpy(&f, mrec + 8 * mb, 4);
+                memcpy(&b, mrec + 8 * mb + 4, 4);
+                info = mrec[L.info_offset + mb];
+            }
+            leon::gauge_cell(cfg->sources, leon::carry_weight(r.x, r.y, r.width, r.height, i, j), lo, hi, info, f, b, &s);
+        }
+    int64_t o[leon::kGaugeWords];
+    leon::gauge_finish(cfg->sources, s, o);
+    memcpy(stats, o, sizeof(o));
+    return leon::kRegionOk;
+}
+
+// k_gauge on records the caller supplies (leon_pipeline_gauge_kernel): memory of its own, the null stream
+int gauge_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames, const void* const* motion_records,
+                 const void* const* activity_records, const leon_pipeline_gauge_config* cfg, const leon_pipeline_region* regions, int32_t n, int64_t* stats, int32_t* status)
+{
+    int rc = gauge_config_check(cfg);
+    if (rc != LEON_OK) return rc;
+    if (!regions || !stats) return fail(LEON_ERR_INVALID, "null argument");
+    if ((rc = record_count_check("gauge regions", "regions", n)) != LEON_OK) return rc;
+    for (int32_t i = 0; i < n; i++)          // a record a valid region names must be there: the judgement alone, nothing summed
+        if (gauge_record_host(fw, fh, mbw, mbh, n_frames, motion_records, activity_records, cfg, regions + i, nullptr, true) < 0) return LEON_ERR_INVALID;
+    const bool mot = (cfg->sources & LEON_GAUGE_MOTION) != 0, act = (cfg->sources & LEON_GAUGE_ACTIVITY) != 0;
+    const leon::MotionLayout ML = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+    const leon::ActivityLayout AL = leon::activity_layout((uint32_t)mbw, (uint32_t)mbh);
+    // [table | motion ring | activity ring]: a frame with a record of either kind gets a slot in both rings, as the pipeline's rings
+    // share an index; a frame without gets none, its ring id stays 0 and nothing of the call reads it
+    std::vector<leon::CarryFrame> table((size_t)n_frames);
+    uint32_t slots = 0;
+    for (int32_t i = 0; i < n_frames; i++) table[(size_t)i] = leon::CarryFrame{(mot && motion_records[i]) || (act && activity_records[i]) ? slots++ : 0u, -1, -1, 0u};
+    const size_t table_bytes = pad256(std::max<size_t>(table.size(), 1) * sizeof(leon::CarryFrame));
+    const size_t motion_bytes = mot ? (size_t)std::max<uint32_t>(slots, 1) * ML.record_pitch : 0, activity_bytes = act ? (size_t)std::max<uint32_t>(slots, 1) * AL.record_pitch : 0;
+    HIP_TRY(hipSetDevice(device_id));
+    GaugeHostBufs b;
+    char* extra = nullptr;
+    if ((rc = gauge_host_up(&b, table_bytes + motion_bytes + activity_bytes, regions, n, stats, status, &extra)) != LEON_OK) return rc;
+    uint8_t* d_motion = reinterpret_cast<uint8_t*>(extra + table_bytes);
+    uint8_t* d_activity = d_motion + motion_bytes;
+    if (!table.empty()) HIP_TRY(hipMemcpy(extra, table.data(), table.size() * sizeof(leon::CarryFrame), hipMemcpyHostToDevice));
+    for (int32_t i = 0; i < n_frames; i++) {
+        if (mot && motion_records[i]) HIP_TRY(hipMemcpy(d_motion + (size_t)table[(size_t)i].ring * ML.record_pitch, motion_records[i], ML.record_bytes, hipMemcpyHostToDevice));
+        if (act && activity_records[i]) HIP_TRY(hipMemcpy(d_activity + (size_t)table[(size_t)i].ring * AL.record_pitch, activity_records[i], AL.record_bytes, hipMemcpyHostToDevice));
+    }
+    gauge_launch(nullptr, reinterpret_cast<const leon::GaugeRecord*>(b.recs), reinterpret_cast<const leon::CarryFrame*>(extra), mot ? d_motion : nullptr,
+                 act ? d_activity : nullptr, fw, fh, mbw, ML, AL, n_frames, cfg->sources, n, b.stats, status ? b.status : nullptr);
+    HIP_TRY(hipGetLastError());
+    return gauge_host_down(b, n, stats, status);      // (the copies wait: nothing in flight reads the buffer when it goes)
 }
 
 // ---- dense maps propagated along the motion vectors (leon_pipeline_propagate_maps) ------------------------------------------------
@@ -3647,6 +3828,30 @@ int leon_pipeline_carry_device(int32_t device_id, int32_t frame_width, int32_t f
                                int32_t* votes, int32_t* status)
 {
     return carry_device(device_id, frame_width, frame_height, mb_width, mb_height, n_frames, fwd, bwd, records_host, regions, n, out, votes, status);
+}
+
+int32_t leon_pipeline_gauge_record(int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames, const void* const* motion_records,
+                                   const void* const* activity_records, const leon_pipeline_gauge_config* cfg, const leon_pipeline_region* rec, int64_t* stats)
+{
+    return gauge_record_host(frame_width, frame_height, mb_width, mb_height, n_frames, motion_records, activity_records, cfg, rec, stats, false);
+}
+
+int leon_pipeline_gauge_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_gauge_config* cfg, const leon_pipeline_gauge_regions_call* call)
+{
+    return gauge_regions_device(p, window, cfg, call);
+}
+
+int leon_pipeline_gauge_regions(leon_pipeline* p, int64_t window, const leon_pipeline_gauge_config* cfg, const leon_pipeline_region* regions, int32_t n, int64_t* stats,
+                                int32_t* status)
+{
+    return gauge_regions(p, window, cfg, regions, n, stats, status);
+}
+
+int leon_pipeline_gauge_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                               const void* const* motion_records_host, const void* const* activity_records_host, const leon_pipeline_gauge_config* cfg,
+                               const leon_pipeline_region* regions, int32_t n, int64_t* stats, int32_t* status)
+{
+    return gauge_kernel(device_id, frame_width, frame_height, mb_width, mb_height, n_frames, motion_records_host, activity_records_host, cfg, regions, n, stats, status);
 }
 
 int leon_pipeline_propagate_layout(int32_t frame_width, int32_t frame_height, int32_t stride, int32_t planes, int32_t elem_bytes, struct leon_pipeline_propagate_layout* out)

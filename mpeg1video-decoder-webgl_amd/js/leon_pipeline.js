@@ -68,6 +68,11 @@
  *                                  between two frames of the window that a prediction joins (leon_pipeline_carry_regions, opts.motion);
  *                                  out[i] = [target, x', y', width, height, 0, 0, 0] where status[i] is 0, a region record for
  *                                  readRegions; a record's fault is its status word (9: no prediction joins the two frames), not a throw
+ *   p.gaugeRegions(window, regions, {sources}) -> {stats: Float64Array [n][16], status: Int32Array [n]}: regions = [[frameIndex, x, y, width,
+ *                                  height], ...], per box the area-weighted sums over the macroblocks under it of its frame's motion record
+ *                                  (sources 1: words 8 .. 15), its activity record (sources 2: words 1 .. 7) or both (3; the default: every
+ *                                  record output the pipeline has); word 0 is the box's area (leon_pipeline_gauge_regions).  Every word is
+ *                                  below 2^53, so the numbers are exact; a record's fault is its status word, not a throw
  *   p.propagateMaps(window, maps, hops, {stride, planes, elemBytes, fill}) -> {via: Uint8Array [n][mh][mw] (0 fill, 1 forward, 2 backward),
  *                                  status: Int32Array [n]}: dense maps (masks, heatmaps, features) propagated along the motion vectors
  *                                  (leon_pipeline_propagate_maps, opts.motion).  maps = a Buffer / Uint8Array over [slots][planes][mh][mw]
@@ -105,6 +110,7 @@ class LeonPipeline extends EventEmitter {
     }
     if (opts.motion) output = (output || outputs.rgba) | 32;          // LEON_PIPELINE_OUTPUT_MOTION beside whatever output resolves to
     if (opts.activity) output = (output || outputs.rgba) | 128;       // LEON_PIPELINE_OUTPUT_ACTIVITY likewise
+    this._gaugeSources = (opts.motion ? 1 : 0) | (opts.activity ? 2 : 0);          // what gaugeRegions reads without opts.sources: every record output there is
     let tensorDtype = opts.tensorDtype === undefined ? 0 : opts.tensorDtype;
     if (typeof tensorDtype === 'string') {
       if (!(tensorDtype in dtypes)) throw new TypeError("tensorDtype: 'float16', 'bfloat16', 'float32' or 'uint8'");
@@ -241,6 +247,15 @@ class LeonPipeline extends EventEmitter {
       throw new TypeError('records: [[frameIndex, x, y, width, height, targetFrameIndex], ...]');
     }
     return this._p.carryRegions(window, Int32Array.from(records.flat()));
+  }
+  // regions: [[frameIndex, x, y, width, height], ...]: the motion and activity records of each box's frame summed under the box
+  gaugeRegions(window, regions, opts = {}) {
+    if (!Array.isArray(regions) || !regions.every((r) => Array.isArray(r) && r.length === 5 && r.every(Number.isInteger))) {
+      throw new TypeError('regions: [[frameIndex, x, y, width, height], ...]');
+    }
+    const sources = opts.sources === undefined ? this._gaugeSources : opts.sources;
+    if (!Number.isInteger(sources)) throw new TypeError('sources: 1 (motion), 2 (activity) or 3');
+    return this._p.gaugeRegions(window, Int32Array.from(regions.flat()), sources);
   }
   // hops: [[targetFrameIndex, dstSlot, fwdSlot, bwdSlot], ...]: each a gather through the target's motion record; maps is written in place
   propagateMaps(window, maps, hops, opts = {}) {

@@ -53,6 +53,7 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_carry_regions", "leon_pipeline_carry_device",
     "leon_pipeline_propagate_layout", "leon_pipeline_propagate_record", "leon_pipeline_propagate_maps_device", "leon_pipeline_propagate_maps",
     "leon_pipeline_propagate_kernel",
+    "leon_pipeline_gauge_record", "leon_pipeline_gauge_regions_device", "leon_pipeline_gauge_regions", "leon_pipeline_gauge_kernel",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -361,6 +362,8 @@ REGIONS_SCRATCH_DEFAULT = 256 << 20          # LEON_REGIONS_SCRATCH_DEFAULT
 REGION_SCALE, REGION_OFFSET = 7, 8           # LEON_REGION_SCALE, LEON_REGION_OFFSET: a warp record's two own
 REGION_NO_REFERENCE = 9                      # LEON_REGION_NO_REFERENCE: a carry record's own
 REGION_SLOT = 10                             # LEON_REGION_SLOT: a propagate record's own
+GAUGE_MOTION, GAUGE_ACTIVITY = 1, 2          # LEON_GAUGE_*: the bits of a gauge call's sources
+GAUGE_WORDS = 16                             # int64 words of a gauged record's statistics
 
 
 class PipelineWarpRegion(C.Structure):
@@ -384,6 +387,15 @@ class PipelineCarryRegion(C.Structure):
 class PipelineCarryRegionsCall(C.Structure):
     _fields_ = [("regions", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("device_out", C.c_void_p), ("device_votes", C.c_void_p),
                 ("device_status", C.c_void_p), ("stream", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class PipelineGaugeConfig(C.Structure):
+    _fields_ = [("sources", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class PipelineGaugeRegionsCall(C.Structure):
+    _fields_ = [("regions", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("device_stats", C.c_void_p), ("device_status", C.c_void_p), ("stream", C.c_void_p),
+                ("reserved", C.c_uint64 * 3)]
 
 
 class PipelinePropagateHop(C.Structure):
@@ -604,6 +616,15 @@ def load():
         lib.leon_pipeline_propagate_maps.argtypes = [C.c_void_p, C.c_int64, P(PipelinePropagateConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.leon_pipeline_propagate_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(PipelinePropagateConfig), C.c_void_p,
                                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_gauge_regions"):
+        P = C.POINTER
+        lib.leon_pipeline_gauge_record.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineGaugeConfig), C.c_void_p,
+                                                   C.c_void_p]
+        lib.leon_pipeline_gauge_record.restype = C.c_int32
+        lib.leon_pipeline_gauge_regions_device.argtypes = [C.c_void_p, C.c_int64, P(PipelineGaugeConfig), P(PipelineGaugeRegionsCall)]
+        lib.leon_pipeline_gauge_regions.argtypes = [C.c_void_p, C.c_int64, P(PipelineGaugeConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_gauge_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineGaugeConfig),
+                                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -946,6 +967,97 @@ def carry_device(frame_width, frame_height, mbw, mbh, n_frames, fwd, bwd, record
     _chk(load().leon_pipeline_carry_device(int(device_id), int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), f.ctypes.data, b.ctypes.data, ptrs,
                                            r.ctypes.data if len(r) else None, len(r) if n is None else int(n), out.ctypes.data, votes.ctypes.data, status.ctypes.data))
     return out[:len(r)], votes[:len(r)], status[:len(r)]
+
+
+def gauge_box(frame_width, frame_height, n_frames, motion, activity, rec, sources=GAUGE_MOTION | GAUGE_ACTIVITY):
+    """The definition of one record of leon_pipeline_gauge_regions (include/leon_pipeline.h) in Python integers, written from the
+    header's text and independent of the C code.  motion[i] = (mv [mbh, mbw, 4] int16, info [mbh, mbw] uint8) and activity[i] = cells
+    [mbh, mbw] of ACTIVITY_CELL of window frame i (as read_motion and read_activity give them; a list the sources do not ask for may be
+    None); rec = the 8 words (frame, x, y, w, h, 0, 0, 0).  Returns (status, stats): the 16 words as a list of Python integers, None
+    where status is not 0."""
+    f, x, y, w, h, r0, r1, r2 = [int(v) for v in rec]
+    fw, fh, n, sources = int(frame_width), int(frame_height), int(n_frames), int(sources)
+    if r0 or r1 or r2:
+        return REGION_RESERVED, None
+    if not 0 <= f < n:
+        return REGION_FRAME, None
+    if w < 1 or h < 1 or x < 0 or y < 0 or x + w > fw or y + h > fh:
+        return REGION_BOX, None
+    s = [0] * GAUGE_WORDS
+    for j in range(y >> 4, ((y + h - 1) >> 4) + 1):
+        for i in range(x >> 4, ((x + w - 1) >> 4) + 1):
+            a = (min(x + w, 16 * i + 16) - max(x, 16 * i)) * (min(y + h, 16 * j + 16) - max(y, 16 * j))
+            s[0] += a
+            if sources & GAUGE_ACTIVITY:
+                cell = activity[f][j][i]
+                blocks, ac_mag = int(cell["blocks"]), int(cell["ac_mag"])
+                s[1] += a if blocks else 0
+                s[2] += a * int(cell["ac_count"])
+                s[3] += a * ac_mag
+                s[4] += a * int(cell["dc_mag"])
+                s[5] += a * int(cell["qscale"])
+                s[6] += a * bin(blocks).count("1")
+                s[7] = max(s[7], ac_mag)
+            if sources & GAUGE_MOTION:
+                mv, info = [int(v) for v in motion[f][0][j][i]], int(motion[f][1][j][i])
+                s[8] += a if info & 1 else 0
+                s[9] += a if info & 2 else 0
+                s[10] += a if info & 4 else 0
+                s[11] += a if any(mv) else 0
+                for k in range(4):
+                    s[12 + k] += a * abs(mv[k])
+    return REGION_OK, s
+
+
+def _gauge_records(motion, activity, mbw, mbh, n_frames):
+    """(motion pointer array or None, activity pointer array or None, the buffers they point into): motion[i] = (mv, info) or None laid
+    out as motion_layout says, activity[i] = cells or None as activity_layout says, each buffer exactly record_bytes long"""
+    keep = []
+    mp = None
+    if motion is not None:
+        mp, k = _carry_records(list(motion) + [None] * (int(n_frames) - len(motion)), mbw, mbh)
+        keep += k
+    ap = None
+    if activity is not None:
+        lay = activity_layout(mbw, mbh)
+        ap = (C.c_void_p * max(1, int(n_frames), len(activity)))()
+        for i, cells in enumerate(activity):
+            if cells is None:
+                continue
+            buf = np.zeros(lay.record_bytes, dtype=np.uint8)
+            buf[:8 * lay.mbs] = np.ascontiguousarray(cells, dtype=ACTIVITY_CELL).reshape(-1).view(np.uint8)
+            keep.append(buf)
+            ap[i] = buf.ctypes.data
+    return mp, ap, keep
+
+
+def gauge_record(frame_width, frame_height, mbw, mbh, n_frames, motion, activity, rec, sources=GAUGE_MOTION | GAUGE_ACTIVITY, fill=0, cfg=None):
+    """leon_pipeline_gauge_record: the library's CPU evaluation of one record; arguments as gauge_box's.  Returns (status, stats [16]
+    int64) with `fill` where the library wrote nothing; LeonError where it refuses the call.  cfg: a PipelineGaugeConfig in place of
+    sources."""
+    mp, ap, keep = _gauge_records(motion, activity, mbw, mbh, n_frames)
+    r = _records_array([rec])
+    stats = np.full(GAUGE_WORDS, fill, dtype=np.int64)
+    cfg = PipelineGaugeConfig(int(sources)) if cfg is None else cfg
+    st = load().leon_pipeline_gauge_record(int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), mp, ap, C.byref(cfg), r.ctypes.data, stats.ctypes.data)
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return st, stats
+
+
+def gauge_kernel(frame_width, frame_height, mbw, mbh, n_frames, motion, activity, regions, sources=GAUGE_MOTION | GAUGE_ACTIVITY, device_id=0, fill=-1, n=None,
+                 cfg=None):
+    """leon_pipeline_gauge_kernel: k_gauge on records the caller supplies (as gauge_box's), regions = [(frame, x, y, w, h), ...] ->
+    (stats [m, 16] int64, status [m] int32) pre-filled with `fill`: a refused record keeps it in its statistics.  n: the count handed
+    to the library when it is to differ from m = len(regions) (smaller: what lies behind keeps the fill)."""
+    mp, ap, keep = _gauge_records(motion, activity, mbw, mbh, n_frames)
+    r = _records_array(regions)
+    m = max(1, len(r))
+    stats, status = np.full((m, GAUGE_WORDS), fill, dtype=np.int64), np.full(m, fill, dtype=np.int32)
+    cfg = PipelineGaugeConfig(int(sources)) if cfg is None else cfg
+    _chk(load().leon_pipeline_gauge_kernel(int(device_id), int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), mp, ap, C.byref(cfg),
+                                           r.ctypes.data if len(r) else None, len(r) if n is None else int(n), stats.ctypes.data, status.ctypes.data))
+    return stats[:len(r)], status[:len(r)]
 
 
 def carry_plan(refs, frames, src):
@@ -1579,6 +1691,8 @@ class Pipeline:
     activity_view(window, i) wraps it in place; activity_layout has the offsets.
     Carrying boxes (motion=True): carry_regions_device(window, records) moves boxes from one frame of the window to another along those
     vectors, on the device and on torch's current stream (carry_box states one hop; carry_regions is the same from host records);
+    gauge_regions_device(window, records) returns per box the area-weighted sums of the frame's motion and activity records under it
+    (gauge_box states them; gauge_regions is the same from host records): carry_regions_gop's records go in as they are.
     carry_regions_gop(window, boxes, src) carries a detector's boxes on frame `src` to every frame of its GOP, ready for
     resample_regions_device.
     Propagating dense maps (motion=True): propagate_maps_device(window, maps, hops, stride) writes the map of a frame -- a mask, heatmaps,
@@ -1896,6 +2010,47 @@ class Pipeline:
                 records[to], votes[to], status[to] = out, vot, sta
             first += len(hops)
         return records, votes, status
+
+    def _gauge_sources(self, sources):
+        """the sources of a gauge call: None = every record output the pipeline has"""
+        if sources is not None:
+            return int(sources)
+        return (GAUGE_MOTION if self.motion_layout is not None else 0) | (GAUGE_ACTIVITY if self.activity_layout is not None else 0)
+
+    def gauge_regions(self, window, regions, sources=None, fill=0):
+        """leon_pipeline_gauge_regions: regions = [(frame, x, y, w, h), ...] in host memory -> (stats [n, 16] int64, status [n] int32)
+        host arrays: per box the area-weighted sums over the macroblocks under it of that frame's motion record (GAUGE_MOTION, words
+        8 .. 15), its activity record (GAUGE_ACTIVITY, words 1 .. 7) or both (gauge_box states them); sources=None: every record output
+        the pipeline has.  A record's fault is its status word (REGION_*), never a LeonError; its statistics keep `fill`.  Synchronous."""
+        r = _records_array(regions)
+        m = max(1, len(r))
+        stats, status = np.full((m, GAUGE_WORDS), fill, dtype=np.int64), np.full(m, fill, dtype=np.int32)
+        cfg = PipelineGaugeConfig(self._gauge_sources(sources))
+        _chk(self.lib.leon_pipeline_gauge_regions(self.h, int(window), C.byref(cfg), r.ctypes.data if len(r) else None, len(r), stats.ctypes.data, status.ctypes.data))
+        return stats[:len(r)], status[:len(r)]
+
+    def gauge_regions_device(self, window, records, sources=None, stats=None, status=None, stream=None):
+        """leon_pipeline_gauge_regions_device: the same from records that lie in DEVICE memory -- a contiguous CUDA int32 torch tensor
+        [N, 8] (frame, x, y, w, h, 0, 0, 0), or [F, N, 8] as carry_regions_gop returns it, read as [F * N, 8] -- queued on `stream` (a
+        torch.cuda.Stream; None: torch's current stream) with carry_regions_device's ordering: NO host synchronisation.  Returns (stats
+        [N, 16] int64, status [N] int32) on the device (the caller's, or ones the method allocates, not initialised): stats[i] is
+        written exactly where status[i] is 0."""
+        import torch
+        dev = self.device_id
+        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.dtype == torch.int32 and records.dim() in (2, 3) and records.shape[-1] == 8
+                and records.is_contiguous()):
+            raise ValueError("records: a contiguous CUDA int32 tensor [N, 8] or [F, N, 8]")
+        records = records.view(-1, 8)
+        n = int(records.shape[0])
+        _device_tensor_check("records", records, torch.int32, 8 * n, dev, words=True)
+        _device_tensor_check("stats", stats, torch.int64, GAUGE_WORDS * n, dev)
+        _device_tensor_check("status", status, torch.int32, n, dev, words=True)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        stats, status = _empty_where_none(stream, dev, [(stats, (max(1, n), GAUGE_WORDS), torch.int64), (status, max(1, n), torch.int32)])
+        cfg = PipelineGaugeConfig(self._gauge_sources(sources))
+        call = PipelineGaugeRegionsCall(records.data_ptr() if n else None, n, 0, stats.data_ptr(), status.data_ptr(), self._stream_handle(stream))
+        _chk(self.lib.leon_pipeline_gauge_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        return stats.view(-1)[:GAUGE_WORDS * n].view(n, GAUGE_WORDS), status.view(-1)[:n]
 
     def _propagate_check(self, maps, stride):
         lay = propagate_layout(self.info.frame_width, self.info.frame_height, stride, maps.shape[1] if len(maps.shape) == 4 else 0, self._elem_bytes(maps))

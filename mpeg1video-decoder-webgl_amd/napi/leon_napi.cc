@@ -821,6 +821,52 @@ napi_value PipeCarryRegions(napi_env env, napi_callback_info info)
     return o;
 }
 
+// p.gaugeRegions(window, regions, sources) -> {stats: Float64Array [n][16] (every word is below 2^53, so a double holds it exactly),
+// status: Int32Array [n] (LEON_REGION_*; not 0: the record's words of stats are 0)}: leon_pipeline_gauge_regions (opts.motion and / or
+// opts.activity).  regions: an Int32Array of n x [frame index, x, y, width, height]; sources: LEON_GAUGE_* bits.
+napi_value PipeGaugeRegions(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    int32_t sources = 0;
+    napi_typedarray_type tt;
+    size_t len = 0, off = 0;
+    void* words = nullptr;
+    napi_value ab;
+    bool is_ta = false;
+    if (argc < 3 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta ||
+        napi_get_typedarray_info(env, argv[1], &tt, &len, &words, &ab, &off) != napi_ok || tt != napi_int32_array || len % 5 != 0 ||
+        napi_get_value_int32(env, argv[2], &sources) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "gaugeRegions(window, Int32Array of [frame, x, y, width, height] per record, sources)");
+        return nullptr;
+    }
+    const size_t n = len / 5, m = n >= 1 && n <= 65535 ? n : 1;          // (a count the library refuses allocates nothing to speak of here)
+    std::vector<leon_pipeline_region> regions(m);
+    const int32_t* b = static_cast<const int32_t*>(words);
+    for (size_t i = 0; i < n && i < m; i++) regions[i] = leon_pipeline_region{b[5 * i], b[5 * i + 1], b[5 * i + 2], b[5 * i + 3], b[5 * i + 4], {0, 0, 0}};
+    std::vector<int64_t> stats(m * 16, 0);          // (zeros: what a refused record keeps)
+    napi_value o, abs[2], ta[2];
+    void* data[2] = {nullptr, nullptr};
+    NAPI_OK(napi_create_object(env, &o));
+    NAPI_OK(napi_create_arraybuffer(env, m * 16 * 8, &data[0], &abs[0]));
+    NAPI_OK(napi_create_typedarray(env, napi_float64_array, m * 16, abs[0], 0, &ta[0]));
+    NAPI_OK(napi_create_arraybuffer(env, m * 4, &data[1], &abs[1]));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, m, abs[1], 0, &ta[1]));
+    leon_pipeline_gauge_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.sources = sources;
+    const int rc = leon_pipeline_gauge_regions(h->p, w, &cfg, regions.data(), (int32_t)std::min<size_t>(n, 65536), stats.data(), static_cast<int32_t*>(data[1]));
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    double* d = static_cast<double*>(data[0]);
+    for (size_t i = 0; i < m * 16; i++) d[i] = (double)stats[i];
+    NAPI_OK(napi_set_named_property(env, o, "stats", ta[0]));
+    NAPI_OK(napi_set_named_property(env, o, "status", ta[1]));
+    return o;
+}
+
 // p.propagateMaps(window, maps, hops, stride, planes, elemBytes, fill) -> {via: Uint8Array [n][mh][mw] (0 fill, 1 forward, 2 backward),
 // status: Int32Array [n] (LEON_REGION_*; not 0: the record's slot and via map are left as they were, via zero)}:
 // leon_pipeline_propagate_maps (opts.motion).  maps: a Uint8Array over the bytes of [slots][planes][mh][mw], contiguous, WRITTEN IN
@@ -1139,7 +1185,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readActivity", PipeReadActivity}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readActivity", PipeReadActivity}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"gaugeRegions", PipeGaugeRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));

@@ -10,6 +10,11 @@ seeded boxes of up to --max-box pixels a side lie on the first GOP's I picture:
   host         read_motion of the P picture's record, then carry_box for the same N records
 Prints one JSON line.
 
+--gauge: in the same job, the boxes the single hop moved (its output records, on the P picture) go through gauge_regions_device
+(leon_pipeline_gauge_regions; k_gauge) for sources 1 (motion), 2 (activity) and 3 (both): the time of one call beside the single hop's
+on the same boxes, and the first --gauge-check records against gauge_box on the records read back.  The pipeline then runs with
+activity=True as well.
+
 --maps: dense maps instead (leon_pipeline_propagate_maps; k_propagate): a map on the first GOP's I picture propagated to the GOP's 12
 frames by propagate_maps_gop, for three shapes -- a uint8 label mask [1, 1080, 1920] at stride 1, fp16 heatmaps [17, 270, 480] at
 stride 4, fp16 features [256, 68, 120] at stride 16 -- from the enqueue to the synchronisation of the stream; the bytes the hops
@@ -17,7 +22,7 @@ read and write a second beside the rate of a device-to-device copy of as many by
 had before: motion_view, a per-cell index grid built with torch ops and a gather, hop by hop in the same order, whose result is
 compared with the kernel's byte for byte.  Prints one JSON line.
 
-  python tools/carry_bench.py [--boxes 4096] [--reps 20] [--max-box 256] [--host-boxes N]
+  python tools/carry_bench.py [--boxes 4096] [--reps 20] [--max-box 256] [--host-boxes N] [--gauge [--gauge-check 64]]
   python tools/carry_bench.py --maps [--reps 20]"""
 import argparse
 import json
@@ -128,6 +133,8 @@ def maps_bench(a, pipe, window, frames):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--maps", action="store_true", help="dense maps (k_propagate) instead of boxes")
+    ap.add_argument("--gauge", action="store_true", help="the carried boxes through k_gauge in the same job, sources 1, 2 and 3")
+    ap.add_argument("--gauge-check", type=int, default=64, help="records of each gauge call compared with gauge_box")
     ap.add_argument("--boxes", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--max-box", type=int, default=256)
@@ -146,7 +153,7 @@ def main():
         held["window"], held["frames"] = window, list(frames)
         delivered.set()
         return False
-    pipe = L.Pipeline(data, on_window=on_window, motion=True, gops_per_window=stream_1080p.VARIED_GOPS, gpu_parser=True, parser_threads=16)
+    pipe = L.Pipeline(data, on_window=on_window, motion=True, activity=a.gauge, gops_per_window=stream_1080p.VARIED_GOPS, gpu_parser=True, parser_threads=16)
     try:
         if not delivered.wait(300):
             raise RuntimeError("no window was delivered: %s" % (pipe.error,))
@@ -194,6 +201,34 @@ def main():
                 if i >= 2:
                     gop_us.append((t2 - t0) * 1e6)
                     gop_enqueue_us.append((t1 - t0) * 1e6)
+            gauge = None
+            if a.gauge:          # the moved boxes, on the P picture, under its two records
+                gauge = {}
+                stats = torch.empty((a.boxes, L.GAUGE_WORDS), dtype=torch.int64, device="cuda")
+                gstatus = torch.empty((a.boxes,), dtype=torch.int32, device="cuda")
+                moved_to = out.clone()
+                g_motion, g_cells = pipe.read_motion(window, tgt)[:2], pipe.read_activity(window, tgt)[0]
+                g_m, g_a = [None] * n, [None] * n
+                g_m[tgt], g_a[tgt] = g_motion, g_cells
+                for sources in (1, 2, 3):
+                    us, enq = [], []
+                    for i in range(a.reps + 2):
+                        st.synchronize()
+                        t0 = time.perf_counter()
+                        pipe.gauge_regions_device(window, moved_to, sources=sources, stats=stats, status=gstatus)
+                        t1 = time.perf_counter()
+                        st.synchronize()
+                        t2 = time.perf_counter()
+                        if i >= 2:
+                            us.append((t2 - t0) * 1e6)
+                            enq.append((t1 - t0) * 1e6)
+                    h_stats, h_status, h_rec = stats.cpu().numpy(), gstatus.cpu().numpy(), moved_to.cpu().numpy()
+                    for k in range(min(a.boxes, a.gauge_check)):
+                        s_, w_ = L.gauge_box(fw, fh, n, g_m, g_a, h_rec[k], sources)
+                        if s_ != h_status[k] or (s_ == 0 and w_ != h_stats[k].tolist()):
+                            raise RuntimeError("sources %d: the device and gauge_box disagree in record %d" % (sources, k))
+                    gauge["sources_%d" % sources] = {"us": round(statistics.median(us), 1), "min_us": round(min(us), 1), "enqueue_us": round(statistics.median(enq), 1),
+                                                     "records_ok": int((h_status == 0).sum()), "checked": min(a.boxes, a.gauge_check)}
             gop_frames = [i for i, f in enumerate(frames) if f["gop"] == frames[src]["gop"]]
             gop_ok = int((g_status[gop_frames] == 0).sum().item())
         levels, unreachable = L.carry_plan((fwd, bwd), frames, src)
@@ -218,7 +253,7 @@ def main():
                           "gop_us": round(med(gop_us), 1), "gop_min_us": round(min(gop_us), 1), "gop_enqueue_us": round(med(gop_enqueue_us), 1),
                           "host_boxes": m, "host_read_motion_us": round((t1 - t0) * 1e6, 1), "host_carry_box_us": round((t2 - t1) * 1e6, 1),
                           "host_us_per_4096": round(((t1 - t0) + (t2 - t1) * a.boxes / max(1, m)) * 1e6, 1), "device_equals_host": True,
-                          "moved": int((hop[1][:, 2:] != 0).any(axis=1).sum())}))
+                          "moved": int((hop[1][:, 2:] != 0).any(axis=1).sum()), **({"gauge": gauge} if gauge is not None else {})}))
         pipe.release_window(window)
         pipe.wait()
     finally:
