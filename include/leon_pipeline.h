@@ -67,6 +67,10 @@ typedef struct leon_pipeline leon_pipeline;
 /* Bit 7, not 6: create goes on refusing output = 64 | 1 (tests/test_pipeline_motion_gpu.py::test_refusals), as it does every other
  * unknown bit.  Only beside RGBA, YCBCR or TENSOR, like MOTION and independent of it: on its own (output = 128) it is refused at create. */
 #define LEON_PIPELINE_OUTPUT_ACTIVITY (1 << 7)
+/* Bit 9, not 6 or 8: create goes on refusing 64 and 256 (tests/test_pipeline_motion_gpu.py, tests/test_pipeline_activity_gpu.py::
+ * test_refusals).  Only beside RGBA, YCBCR or TENSOR and independent of MOTION and ACTIVITY: alone, or with only those two, it is
+ * refused at create like them. */
+#define LEON_PIPELINE_OUTPUT_RESIDUAL (1 << 9)
 
 /* element type of the tensor output (leon_pipeline_tensor_config.dtype) */
 #define LEON_TENSOR_F16  1
@@ -357,6 +361,43 @@ struct leon_pipeline_activity_layout {
     uint64_t reserved[3];               /* 0 */
 };                                      /* 64 bytes */
 
+/* LEON_PIPELINE_OUTPUT_RESIDUAL: the decoded residual picture of each delivered frame -- the correction the stream adds to its own
+ * prediction, sample by sample: the third modality of a compressed-domain model beside the I-picture pixels and the motion vectors.
+ * It is neither frame - reference (motion compensation lies between them) nor a function of the activity cells.
+ * For every delivered frame and every plane Y, Cb, Cr of the CODED picture (coded_width x coded_height, chroma half each), element
+ * (y, x) is
+ *     res(y, x) = (t + 128) / 256          (C division, truncating toward zero)
+ * taken before any prediction is added and before any clamp, t being the output of the reference's two-pass integer IDCT of the
+ * dequantised levels (integers only once pass 1 has run), with the picture's qscale and intra maps and the quantiser matrices of its
+ * sequence: exactly what lo_pass1_plane followed by lo_pass2_residual_plane of the oracle give for the picture's dense coefficient
+ * planes.  Stored as int16, saturated to -32768 .. 32767.  Nobody has proven a bound on the value; a CPU probe with the oracle (4000
+ * random 16x16 planes, all levels +-32768, +-2047 or +-255 and sparse extremes, qscale 1 and 31, intra and non-intra) found
+ * -3016 .. 3084, so the saturation is a guard and not a tested case (a saturating pack costs no more than a plain one).
+ * Consequences: a block without coefficients is all 0.  An intra macroblock's "residual" is its sample levels (the motion record's
+ * info & 4 says which macroblocks those are).  Every picture type obeys planes = clamp(prediction + res, 0, 255), with prediction 0
+ * where nothing is predicted.  The truncation holds for I pictures too, where the planes' clamp hides it: the record shows negative
+ * values.
+ * Only the n_y + 2 n_c groups of Y, Cb and Cr are read (a yuva stream's A groups are not part of the record), as in ACTIVITY.  An
+ * entry with level 0 contributes nothing.  An entry of a block at or behind the plane's block width (a partly filled last group) is
+ * not shown.
+ * The record in memory (pad64, pad256 = rounding up):
+ *     [ Y: coded_height rows | Cb: coded_height / 2 rows | Cr: coded_height / 2 rows ]   int16, little endian
+ *     luma_stride = pad64(coded_width), chroma_stride = pad64(coded_width / 2)   ELEMENTS a row
+ *     cb_offset = pad256(2 * luma_stride * coded_height), cr_offset = cb_offset + pad256(2 * chroma_stride * coded_height / 2)   bytes
+ *     record_bytes = cr_offset + 2 * chroma_stride * coded_height / 2;   record_pitch = pad256(record_bytes)
+ * The pad columns behind coded_width (coded_width / 2 for chroma) are unspecified, and so are the bytes up to the pitch; no byte outside
+ * record_bytes is ever written.  Every specified element of every delivered frame's record is written by its window's launch
+ * (k_residual, on the decoder's stream behind the reconstruction), every window; nothing is cleared beforehand and nothing is added to
+ * atomically.  A frame of frame_width x frame_height is the top-left frame_height x frame_width of the record, as the planes output
+ * crops.  A window delivered with an error has unspecified records; pictures that are not delivered have none. */
+/* (a struct tag only, as leon_pipeline_activity_layout) */
+struct leon_pipeline_residual_layout {
+    int32_t  coded_width, coded_height;
+    int32_t  luma_stride, chroma_stride;        /* elements */
+    uint64_t cb_offset, cr_offset, record_bytes, record_pitch;   /* bytes */
+    uint64_t reserved[2];               /* 0 */
+};                                      /* 64 bytes */
+
 typedef void (*leon_pipeline_callback)(void* user, int64_t window, const leon_pipeline_frame* frames, int32_t n_frames, int32_t status);
 
 typedef struct leon_pipeline_info {
@@ -558,6 +599,44 @@ int leon_pipeline_get_activity_layout(leon_pipeline* p, struct leon_pipeline_act
 int leon_pipeline_window_activity(leon_pipeline* p, int64_t window, void** out, int32_t n);
 /* copy the record of frame `index` of such a window to host memory, packed: cells [mbs] of 8 bytes, summary [8]; each may be NULL */
 int leon_pipeline_read_activity(leon_pipeline* p, int64_t window, int32_t index, void* cells, uint32_t* summary);
+
+/* The RESIDUAL family, shaped like the ACTIVITY one.  There is no host restatement of the arithmetic in the library: its definition on
+ * the CPU is the oracle. */
+/* host only, no device: the record's layout for a coded picture; refuses (`out` untouched) a null `out`, a size that is not a multiple
+ * of 16 and a size outside 1 .. 256 macroblocks an axis */
+int leon_pipeline_residual_layout(int32_t coded_width, int32_t coded_height, struct leon_pipeline_residual_layout* out);
+/* A diagnostic in the manner of leon_pipeline_activity_kernel: k_residual on lists, maps and matrices the CALLER supplies, with memory
+ * of its own on device_id's null stream, synchronous, everything in host memory.  pictures[i] is a coded picture of coded_width x
+ * coded_height: grp_off, entries and n_entries (the list's CAPACITY) as leon_pipeline_activity_record takes them, the qscale and
+ * intra maps, 128 bytes of quantiser matrices (intra, then non-intra, natural order) and the 64-byte premultiplier; the kernel's
+ * tables are built from them by the function the decoder uses.  Padding, frames, ring and the launch chunks are
+ * leon_pipeline_activity_kernel's (the intra map padded like qscale, the tables in 256 bytes of their own); record_pitch is
+ * leon_pipeline_residual_layout's.
+ * Refused (LEON_ERR_INVALID, nothing launched, `ring` untouched): what leon_pipeline_residual_layout refuses of the size, what
+ * leon_pipeline_activity_kernel refuses of counts, pad_byte, indices, null arguments, a reserved word and a picture's lists, a null
+ * intra, matrices or premultiplier, n_entries above 2^29. */
+typedef struct leon_pipeline_residual_picture {
+    const uint32_t* grp_off;    /* [n_y + 2 n_c + 1] */
+    const uint32_t* entries;    /* [n_entries] */
+    const uint8_t* qscale;      /* [mbs] */
+    const uint8_t* intra;       /* [mbs] */
+    const uint8_t* matrices;    /* [128] */
+    const uint8_t* premultiplier;       /* [64] */
+    uint32_t n_entries;
+    int32_t reserved0;          /* 0 */
+} leon_pipeline_residual_picture;       /* 56 bytes */
+int leon_pipeline_residual_kernel(int32_t device_id, int32_t coded_width, int32_t coded_height, const leon_pipeline_residual_picture* pictures,
+                                  int32_t n_pictures, const leon_pipeline_motion_kernel_frame* frames, int32_t n_frames, int32_t ring_frames,
+                                  int32_t pad_byte, void* ring);
+/* the layout of this pipeline's records; LEON_ERR_INVALID for a pipeline without LEON_PIPELINE_OUTPUT_RESIDUAL */
+int leon_pipeline_get_residual_layout(leon_pipeline* p, struct leon_pipeline_residual_layout* out);
+/* the residual records of a delivered, not yet released window: out[i] is the DEVICE pointer (256-byte aligned, valid until
+ * release_window) of frames[i]'s record, n = the window's n_frames.  May be called from inside the callback.  LEON_ERR_INVALID for a
+ * pipeline without the bit, a window that is not out for delivery, another n */
+int leon_pipeline_window_residual(leon_pipeline* p, int64_t window, void** out, int32_t n);
+/* copy the record of frame `index` of such a window to host memory, packed (no row padding): y [coded_height][coded_width], cb and cr
+ * [coded_height / 2][coded_width / 2] int16; each may be NULL */
+int leon_pipeline_read_residual(leon_pipeline* p, int64_t window, int32_t index, int16_t* y, int16_t* cb, int16_t* cr);
 
 /* Regions of delivered frames as a tensor batch: what runs behind a detector.  The detector's boxes are cut out of the FULL-RESOLUTION
  * frames of a delivered window and resampled to a second-stage model's input size, any number of them in one call, into memory of the

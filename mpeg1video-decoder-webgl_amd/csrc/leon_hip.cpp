@@ -287,14 +287,14 @@ int get_event_pair(leon_decoder* d, Event& a, Event& b)
     return LEON_OK;
 }
 
-void fill_qtables(QTables& q, const uint8_t* qm128)
+void fill_qtables(QTables& q, const uint8_t* qm128, const uint8_t* pm64 = kPremultiplier)
 {
     memset(&q, 0, sizeof q);
     for (int c = 0; c < 8; c++)
         for (int i = 0; i < 8; i++) {
             q.qmT[0][c][i] = qm128[i * 8 + c];
             q.qmT[1][c][i] = qm128[64 + i * 8 + c];
-            q.pmT[c][i] = kPremultiplier[i * 8 + c];
+            q.pmT[c][i] = pm64[i * 8 + c];
         }
 }
 

@@ -41,6 +41,7 @@
 #include "leon_warp.h"
 #include "leon_motion.h"
 #include "leon_activity.h"
+#include "leon_residual.h"
 #include "leon_carry.h"
 #include "leon_propagate.h"
 #include "leon_gauge.h"
@@ -3117,6 +3118,132 @@ __global__ __launch_bounds__(kRgbaBlock) void k_activity_summary(const ActivityD
         uint4* sm = reinterpret_cast<uint4*>(rec + L.summary_offset);
         sm[0] = lo;
         sm[1] = hi;
+    }
+}
+
+// ---- output RESIDUAL: a frame's residual record (include/leon_pipeline.h, LEON_PIPELINE_OUTPUT_RESIDUAL) -------------------------
+// One launch per window behind its reconstruction levels, blockIdx.y = the delivered frame.  A task is k_recon's (leon_residual.h): two
+// block groups that share their macroblocks; one 64-lane wave per task, four per workgroup, a private LDS strip in layout 0 per wave, no
+// talk between waves.  It is the sparse, non-display road of recon_task up to and including its row pass -- the same helpers, called,
+// not copied: both groups' offsets, each run's first 64 entries through a buffer resource of exactly n_entries dwords (count clamped to
+// 512, tile offset masked with 1022: a malformed list gives a wrong record and no access outside the list or the tile), the qscale and
+// intra bytes, clear and scatter, scan_tile and column_pass on the live columns, the row pass with its shortcuts by live columns -- and
+// then, in place of the prediction, truncation toward zero for EVERY picture type (k_recon may leave it out for I pictures because its
+// clamp hides negative values; the record shows them), a saturating pack to int16 (v_cvt_pk_i16_i32) and one 16-byte store per lane and
+// half: the 8 lanes of a row write 128 contiguous bytes of one record row.  A half without a live column stores zeros without a row
+// pass.  Every specified element is written by exactly one lane of one task; lanes of blocks at or behind the plane's block width
+// store nothing (residual_store).
+struct ResidualDesc {
+    const uint32_t* grp_off;     // the picture's group offsets, entry list and maps in its GOP's device arena
+    const uint32_t* entries;
+    const uint8_t* qscale;
+    const uint8_t* intra;
+    const QTables* qt;           // the matrices of the picture's sequence (PicDesc::qt)
+    uint32_t n_entries;          // the list's capacity: no entry at or behind it is read
+    uint32_t frame;              // the frame's index in the residual ring
+};
+
+__global__ __launch_bounds__(kRgbaBlock) void k_residual(const ResidualDesc* __restrict__ descs, uint8_t* __restrict__ ring, ResidualGeom G, ResidualLayout L)
+{
+    __shared__ __attribute__((aligned(16))) char smem[kWavesPerWG * kLdsPerWave];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const uint32_t t = blockIdx.x * (uint32_t)kWavesPerWG + (uint32_t)wave;
+    if (t >= G.tasks) return;                         // (waves share no barrier)
+    char* lds = smem + wave * kLdsPerWave;
+    const ResidualDesc& D = descs[blockIdx.y];
+    stage_tables(D.qt, lds, lane);
+    const ResidualTask T = residual_task(G, t);
+    const int hi3 = lane >> 3, lo3 = lane & 7;
+    // both runs' first 64 entries (one dword per lane), longer runs loop below; indices past the list read 0, whatever grp_off says
+    const __amdgpu_buffer_rsrc_t ent_rs = __builtin_amdgcn_make_buffer_rsrc((void*)D.entries, 0, (int)(D.n_entries * 4u), 0x00020000);
+    const LEON_GLOBAL uint32_t* go = gptr(D.grp_off);
+    uint32_t ent_first[2], ent_start[2], ent_count[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const uint32_t s0 = go[T.gid[h]], e0 = go[T.gid[h] + 1u];
+        ent_start[h] = s0;
+        ent_count[h] = e0 > s0 ? min(e0 - s0, 512u) : 0u;      // a group holds at most 8*64 coefficients
+        ent_first[h] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(
+            ent_rs, (int)(((s0 + (uint32_t)lane) * 4u) | ((uint32_t)lane < ent_count[h] ? 0u : kOobBit)), 0, kAuxStreamOnce);
+    }
+    // quantiser scale and intra flag of this lane's block (lane b: block b's macroblock), for the lanes of the column pass to fetch
+    const uint32_t bw = residual_block_width(L, T.chroma);
+    const uint32_t Qb = 8u * T.g + (uint32_t)lo3, Qs = Qb < bw ? Qb : bw - 1u;
+    const uint32_t mb = T.Rt * G.mbw + (T.chroma ? Qs : Qs >> 1);
+    const int qia = (int)(ldg<uint8_t>(gptr(D.qscale), mb) & 31) | (ldg<uint8_t>(gptr(D.intra), mb) != 0 ? 256 : 0);
+
+    *reinterpret_cast<v4i*>(lds + lane * 16) = v4i{0, 0, 0, 0};
+    *reinterpret_cast<v4i*>(lds + kLdsHalf + lane * 16) = v4i{0, 0, 0, 0};
+    wave_sync();
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        uint32_t e = ent_first[h];
+        // (an entry with level 0 writes nothing: it may name a cell another entry of the list fills)
+        if ((e & 0xffffu) != 0u) *reinterpret_cast<short*>(lds + h * kLdsHalf + ((e >> 16) & 1022u)) = (short)e;
+#pragma unroll 1
+        for (uint32_t k = 64u; k < ent_count[h]; k += 64u) {     // wave-uniform, rare
+            const uint32_t idx = k + (uint32_t)lane;
+            e = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(
+                ent_rs, (int)(((ent_start[h] + idx) * 4u) | (idx < ent_count[h] ? 0u : kOobBit)), 0, kAuxStreamOnce);
+            if ((e & 0xffffu) != 0u) *reinterpret_cast<short*>(lds + h * kLdsHalf + ((e >> 16) & 1022u)) = (short)e;
+        }
+    }
+    // the staged tables (an LDS-direct load the compiler does not order LDS reads behind) and the maps have landed
+    wait_vmem_all();
+    wave_sync();
+    uint64_t live[2];
+    const uint32_t n_cols = scan_tile(lds, lds + Lay<0>::slots, lane, 0u, 0u, live);
+    wave_sync();
+    column_pass<false, true>(lds, 0u, lds + Lay<0>::slots, lds + kOffQtab, n_cols, qia, qia, lane);
+    wave_sync();
+
+    uint8_t* const rec = ring + (size_t)D.frame * L.record_pitch;
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        int r[8];
+        const uint64_t colbits = live[half];
+        if (colbits == 0) {
+#pragma unroll
+            for (int m = 0; m < 8; m++) r[m] = 0;
+        } else {
+            // recon_task's row pass: lane (n = hi3, b = lo3), row n of block b, eight int16 w; trunc(5w/2) == trunc(w * 2.5f)
+            const int cols_live = 8 - (__builtin_clzll(colbits | 1ull) >> 3);
+            const v4u wv = *reinterpret_cast<const v4u*>(lds + half * kLdsHalf + hi3 * 128 + lo3 * 16);
+            const v2f k25 = {2.5f, 2.5f};
+            const v2f a = v2f{(float)(short)(wv.x & 0xffffu), (float)((int)wv.x >> 16)} * k25;
+            const int Y0 = (int)a.x + 128, Y1 = (int)a.y;                           // "+128" of (t+128)/256
+            if (cols_live <= 2) {
+                butterfly8_lo2(Y0, Y1, r);
+            } else {
+                const v2f bb = v2f{(float)(short)(wv.y & 0xffffu), (float)((int)wv.y >> 16)} * k25;
+                if (cols_live <= 4) {
+                    butterfly8_lo4(Y0, Y1, (int)bb.x, (int)bb.y, r);
+                } else {
+                    const v2f cc = v2f{(float)(short)(wv.z & 0xffffu), (float)((int)wv.z >> 16)} * k25;
+                    const v2f dd = v2f{(float)(short)(wv.w & 0xffffu), (float)((int)wv.w >> 16)} * k25;
+                    const int Y[8] = {Y0, Y1, (int)bb.x, (int)bb.y, (int)cc.x, (int)cc.y, (int)dd.x, (int)dd.y};
+                    butterfly8(Y, r);
+                }
+            }
+            // t / 256 truncating toward zero, every picture type
+#pragma unroll
+            for (int m = 0; m < 8; m++) {
+                r[m] += (r[m] >> 31) & 255;
+                r[m] >>= 8;
+            }
+        }
+        // saturated to int16: a guard, no stream and no probe has reached it
+        typedef short v2s __attribute__((ext_vector_type(2)));
+        v4u out;
+        {
+            const v2s p0 = __builtin_amdgcn_cvt_pk_i16(r[0], r[1]), p1 = __builtin_amdgcn_cvt_pk_i16(r[2], r[3]);
+            const v2s p2 = __builtin_amdgcn_cvt_pk_i16(r[4], r[5]), p3 = __builtin_amdgcn_cvt_pk_i16(r[6], r[7]);
+            out.x = __builtin_bit_cast(uint32_t, p0); out.y = __builtin_bit_cast(uint32_t, p1);
+            out.z = __builtin_bit_cast(uint32_t, p2); out.w = __builtin_bit_cast(uint32_t, p3);
+        }
+        uint32_t off;
+        if (residual_store(L, T, (uint32_t)half, (uint32_t)lane, &off)) __builtin_nontemporal_store(out, reinterpret_cast<LEON_GLOBAL v4u*>(gptr_mut(rec) + off));
     }
 }
 

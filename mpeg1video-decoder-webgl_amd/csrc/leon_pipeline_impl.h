@@ -73,6 +73,8 @@ struct PipeWindow {
     std::vector<uint32_t> carry_table;                   // ... and per frame a leon::CarryFrame (ring id, fwd, bwd, 0): what k_carry reads
     std::vector<uint8_t*> activity;                      // output ACTIVITY: frames[i]'s record
     std::vector<leon::ActivityDesc> activity_descs;      // ... and what k_activity makes the record from
+    std::vector<uint8_t*> residual;                      // output RESIDUAL: frames[i]'s record
+    std::vector<leon::ResidualDesc> residual_descs;      // ... and what k_residual makes the record from
     Event done;
     int status = LEON_OK;
     uint32_t n_vpics = 0;        // gpu_parser: error words of the window's pictures are in the ring entry's h_err
@@ -154,6 +156,9 @@ struct leon_pipeline {
     RecordOutput<leon::ActivityDesc> activity;
     leon::ActivityLayout activity_lay{};
     leon::ActivityGeom activity_geom{};
+    RecordOutput<leon::ResidualDesc> residual;
+    leon::ResidualLayout residual_lay{};
+    leon::ResidualGeom residual_geom{};
     // ... resampled to a model's input size (leon_pipeline_tensor_resize; geom.resized = 0: the full-size tensor, k_tensor): the
     // tables of both axes as k_resample reads them -- first_x, count_x, Wx, first_y, count_y, Wy in one int32 buffer
     leon_pipeline_tensor_geometry tensor_geom{};
@@ -1164,7 +1169,7 @@ void carry_refs_host(const leon_pipeline_frame* frames, const leon_pipeline_moti
 }
 
 // the window's frames in display order, GOP-major
-void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<LevelPic>>& levels)
+void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<LevelPic>>& levels, const std::vector<std::vector<int32_t>>& qset)
 {
     w->frames.clear();
     w->tensors.clear();
@@ -1173,6 +1178,8 @@ void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<
     w->motion_descs.clear();
     w->activity.clear();
     w->activity_descs.clear();
+    w->residual.clear();
+    w->residual_descs.clear();
     // output MOTION: what plan_levels gave each picture's launch to predict from, by lane and display index
     std::vector<const LevelPic*> planned;
     if (p->motion.ring) {
@@ -1233,6 +1240,20 @@ void list_frames(leon_pipeline* p, PipeWindow* w, const std::vector<std::vector<
                 d.n_entries = m.n_entries;
                 d.frame = (uint32_t)a.index;
                 w->activity_descs.push_back(d);
+            }
+            if (p->residual.ring) {
+                w->residual.push_back(p->residual.record(a.index));
+                leon::ResidualDesc d{};
+                d.grp_off = (const uint32_t*)ptr(m.grp_off);
+                d.entries = (const uint32_t*)ptr(m.entries);
+                d.qscale = (const uint8_t*)ptr(m.qscale);
+                d.intra = (const uint8_t*)ptr(m.intra);
+                // the matrices its reconstruction launch was given (launch_level, fill_desc)
+                const int32_t set = m.qm >= 0 ? qset[j][(size_t)m.qm] : 0;
+                d.qt = set > 0 ? &p->dec->qset_tabs.dev()[set] : &p->dec->d_tables->q;
+                d.n_entries = m.n_entries;
+                d.frame = (uint32_t)a.index;
+                w->residual_descs.push_back(d);
             }
             w->frames.push_back(f);
         }
@@ -1688,6 +1709,86 @@ int activity_kernel(int32_t device_id, int32_t mbw, int32_t mbh, const leon_pipe
             return D;
         },
         [&](const leon::ActivityDesc* descs, size_t n, uint8_t* d_ring) { activity_launch(descs, n, d_ring, G, L, nullptr); });
+}
+
+// output RESIDUAL: the window's frames -> their residual records, k_residual on the decoder's stream behind k_activity and in front of
+// the window's event, while the lists and maps are still in the GOPs' arenas.  The descriptors go up as k_motion's do.
+static_assert(sizeof(leon::ResidualDesc) == 48, "a descriptor is 12 dwords");
+static_assert(sizeof(struct leon_pipeline_residual_layout) == 64 && sizeof(leon_pipeline_residual_picture) == 56, "include/leon_pipeline.h states the sizes");
+static_assert(sizeof(leon::ResidualGeom) == 32 && sizeof(leon::ResidualLayout) == 32, "kernel arguments");
+// k_residual over n descriptors in device memory, frame i of them in workgroup row i: the one place that cuts them into launches
+// (launch_residual for a window, residual_kernel for a caller's lists)
+void residual_launch(const leon::ResidualDesc* descs, size_t n, uint8_t* ring, const leon::ResidualGeom& geom, const leon::ResidualLayout& lay, hipStream_t stream)
+{
+    const unsigned task_blocks = (geom.tasks + leon::kWavesPerWG - 1) / leon::kWavesPerWG;
+    for (size_t at = 0; at < n; at += 65535) {
+        const unsigned frames = (unsigned)std::min<size_t>(65535, n - at);
+        hipLaunchKernelGGL(leon::k_residual, dim3(task_blocks, frames), dim3(leon::kRgbaBlock), 0, stream, descs + at, ring, geom, lay);
+    }
+}
+
+int launch_residual(leon_pipeline* p, const PipeWindow* w)
+{
+    return launch_records(p, w, p->residual, w->residual_descs, [&](size_t i, const leon::ResidualDesc& d) {
+        if (d.grp_off && d.entries && d.qscale && d.intra && d.qt) return (int)LEON_OK;
+        return fail(LEON_ERR_INVALID, "residual: frame %zu of window %lld lacks its lists or a map", i, (long long)w->id);
+    }, [&](const leon::ResidualDesc* dv, size_t n) { residual_launch(dv, n, p->residual.ring, p->residual_geom, p->residual_lay, p->dec->stream); });
+}
+
+// ACTIVITY's size rules on a coded size
+int residual_size_check(const char* who, int32_t cw, int32_t ch)
+{
+    if (cw < 16 || ch < 16 || (cw & 15) || (ch & 15)) return fail(LEON_ERR_INVALID, "%s: a coded size of %d x %d (multiples of 16)", who, cw, ch);
+    return mb_grid_check(who, cw / 16, ch / 16);
+}
+
+int residual_layout_host(int32_t cw, int32_t ch, struct leon_pipeline_residual_layout* out)
+{
+    if (!out) return fail(LEON_ERR_INVALID, "null argument");
+    if (const int rc = residual_size_check("residual layout", cw, ch); rc != LEON_OK) return rc;
+    const leon::ResidualLayout L = leon::residual_layout((uint32_t)cw, (uint32_t)ch);
+    memset(out, 0, sizeof(*out));
+    out->coded_width = cw; out->coded_height = ch;
+    out->luma_stride = (int32_t)L.luma_stride; out->chroma_stride = (int32_t)L.chroma_stride;
+    out->cb_offset = L.cb_offset; out->cr_offset = L.cr_offset;
+    out->record_bytes = L.record_bytes; out->record_pitch = L.record_pitch;
+    return LEON_OK;
+}
+
+// k_residual on lists, maps and matrices the caller supplies (leon_pipeline_residual_kernel): every array padded as activity_kernel
+// pads it, the intra map like qscale, the picture's QTables (fill_qtables: what the decoder builds its own with) in 256 bytes
+int residual_kernel(int32_t device_id, int32_t cw, int32_t ch, const leon_pipeline_residual_picture* pics, int32_t n_pics, const leon_pipeline_motion_kernel_frame* frames,
+                    int32_t n_frames, int32_t ring_frames, int32_t pad_byte, void* ring)
+{
+    if (const int rc = residual_size_check("residual kernel", cw, ch); rc != LEON_OK) return rc;
+    const int32_t mbw = cw / 16, mbh = ch / 16;
+    const leon::ResidualGeom G = leon::residual_geom((uint32_t)mbw, (uint32_t)mbh);
+    const leon::ActivityGeom AG = leon::activity_geom((uint32_t)mbw, (uint32_t)mbh);
+    const size_t n_off = (size_t)G.n_y + 2 * (size_t)G.n_c + 1;
+    const MapLayout M = map_layout((size_t)mbw * (size_t)mbh, n_off - 1);
+    const leon::ResidualLayout L = leon::residual_layout((uint32_t)cw, (uint32_t)ch);
+    static_assert(sizeof(QTables) == 256, "a picture's tables take one padded piece");
+    return record_kernel<leon::ResidualDesc>("residual kernel", device_id, mbw, mbh, pics, n_pics, frames, n_frames, ring_frames, pad_byte, ring, L.record_pitch,
+        [&](int32_t i, const leon_pipeline_residual_picture& q, size_t* bytes) {
+            if (q.reserved0) return fail(LEON_ERR_INVALID, "residual kernel: a reserved word of picture %d is not 0", i);
+            if (q.n_entries > (1u << 29)) return fail(LEON_ERR_INVALID, "residual kernel: picture %d has %u entries (at most 2^29)", i, q.n_entries);
+            if (!q.intra || !q.matrices || !q.premultiplier) return fail(LEON_ERR_INVALID, "residual kernel: picture %d lacks its intra map, matrices or premultiplier", i);
+            *bytes = M.gpad + MapLayout::entries_pad(q.n_entries) + 2 * M.mpad + sizeof(QTables);
+            return activity_lists_check("residual kernel", AG, q.grp_off, q.entries, q.n_entries, q.qscale);
+        },
+        [&](const leon_pipeline_residual_picture& q, auto& place) {
+            leon::ResidualDesc D{};
+            D.grp_off = reinterpret_cast<const uint32_t*>(place(q.grp_off, n_off * 4, M.gpad));
+            D.entries = reinterpret_cast<const uint32_t*>(place(q.entries, (size_t)q.n_entries * 4, MapLayout::entries_pad(q.n_entries)));
+            D.qscale = place(q.qscale, M.mbs, M.mpad);
+            D.intra = place(q.intra, M.mbs, M.mpad);
+            QTables qt;
+            fill_qtables(qt, q.matrices, q.premultiplier);
+            D.qt = reinterpret_cast<const QTables*>(place(&qt, sizeof(qt), sizeof(qt)));
+            D.n_entries = q.n_entries;
+            return D;
+        },
+        [&](const leon::ResidualDesc* descs, size_t n, uint8_t* d_ring) { residual_launch(descs, n, d_ring, G, L, nullptr); });
 }
 
 // ---- regions of delivered frames as a tensor batch (leon_pipeline_resample_regions) ------------------------------------
@@ -2878,10 +2979,11 @@ int submit_window(leon_pipeline* p, PipeWindow* w)
     p->last_gop = w->jobs.empty() ? 0 : w->jobs.back()->gop;
     p->last_anchor = last_anchor;
     p->last_anchor_tref = last_anchor_tref;
-    list_frames(p, w, levels);
+    list_frames(p, w, levels, qset);
     if ((rc = launch_tensors(p, w)) != LEON_OK) return rc;
     if ((rc = launch_motion(p, w)) != LEON_OK) return rc;
     if ((rc = launch_activity(p, w)) != LEON_OK) return rc;
+    if ((rc = launch_residual(p, w)) != LEON_OK) return rc;
     if (serial) HIP_TRY(hipStreamSynchronize(p->dec->stream));
     HIP_TRY(hipEventRecord(w->done, p->dec->stream));
     return LEON_OK;
@@ -3092,10 +3194,11 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
     // writes its planes, and one leon_convert_rgba per picture (the generic k_rgba_twin) fills the window's frames.
     // The GL flavour (the reference's live display arithmetic, fp32) exists as a launch of its own only: the same road.
     if (cfg->display_flavour != LEON_RGB_CPU_TWIN && cfg->display_flavour != LEON_RGB_GL) return fail(LEON_ERR_INVALID, "display_flavour %d", cfg->display_flavour);
-    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR | LEON_PIPELINE_OUTPUT_MOTION | LEON_PIPELINE_OUTPUT_ACTIVITY))
+    if (cfg->output & ~(LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR | LEON_PIPELINE_OUTPUT_MOTION | LEON_PIPELINE_OUTPUT_ACTIVITY |
+                        LEON_PIPELINE_OUTPUT_RESIDUAL))
         return fail(LEON_ERR_INVALID, "output %d", cfg->output);
     if (cfg->output && !(cfg->output & (LEON_PIPELINE_OUTPUT_RGBA | LEON_PIPELINE_OUTPUT_YCBCR | LEON_PIPELINE_OUTPUT_TENSOR)))
-        return fail(LEON_ERR_INVALID, "output %d: LEON_PIPELINE_OUTPUT_MOTION and _ACTIVITY need RGBA, YCBCR or TENSOR beside them (a pipeline that only parses is not built)", cfg->output);
+        return fail(LEON_ERR_INVALID, "output %d: LEON_PIPELINE_OUTPUT_MOTION, _ACTIVITY and _RESIDUAL need RGBA, YCBCR or TENSOR beside them (a pipeline that only parses is not built)", cfg->output);
     if (cfg->output & LEON_PIPELINE_OUTPUT_TENSOR) {
         // the tensor is defined through the CPU twin's RGBA, whose index drifts over an odd width (k_rgba_twin): refused, as yuva is
         if (p->vinfo.frame_width & 1) return fail(LEON_ERR_INVALID, "the tensor output needs an even frame_width (it is %d)", p->vinfo.frame_width);
@@ -3149,6 +3252,16 @@ int plan_pipeline(leon_pipeline* p, const leon_pipeline_config* cfg, const leon_
         p->activity_geom = leon::activity_geom((uint32_t)p->vinfo.mb_width, (uint32_t)p->vinfo.mb_height);
         if ((int32_t)p->activity_geom.groups_y != p->vinfo.groups_y || (int32_t)p->activity_geom.groups_c != p->vinfo.groups_c)
             return fail(LEON_ERR_INVALID, "activity output: the stream's groups (%d, %d) are not those of %d macroblocks a row", p->vinfo.groups_y, p->vinfo.groups_c, p->vinfo.mb_width);
+    }
+    if (p->output & LEON_PIPELINE_OUTPUT_RESIDUAL) {
+        if (const int rrc = mb_grid_check("residual output", p->vinfo.mb_width, p->vinfo.mb_height); rrc != LEON_OK) return rrc;
+        p->residual_lay = leon::residual_layout((uint32_t)p->vinfo.coded_width, (uint32_t)p->vinfo.coded_height);
+        p->residual.pitch = p->residual_lay.record_pitch;
+        p->residual_geom = leon::residual_geom((uint32_t)p->vinfo.mb_width, (uint32_t)p->vinfo.mb_height);
+        if (p->vinfo.coded_width != 16 * p->vinfo.mb_width || p->vinfo.coded_height != 16 * p->vinfo.mb_height ||
+            (int32_t)p->residual_geom.groups_y != p->vinfo.groups_y || (int32_t)p->residual_geom.groups_c != p->vinfo.groups_c)
+            return fail(LEON_ERR_INVALID, "residual output: the stream's coded size %d x %d and groups (%d, %d) are not those of %d x %d macroblocks", p->vinfo.coded_width,
+                        p->vinfo.coded_height, p->vinfo.groups_y, p->vinfo.groups_c, p->vinfo.mb_width, p->vinfo.mb_height);
     }
     // the GPU parser's geometry; it writes a picture's maps at the offsets of the layout the arenas give them
     p->vgeom.mbw = p->vinfo.mb_width; p->vgeom.mbh = p->vinfo.mb_height;
@@ -3268,6 +3381,7 @@ int allocate_pipeline(leon_pipeline* p)
     };
     if ((p->output & LEON_PIPELINE_OUTPUT_MOTION) && (rc = alloc_records(p->motion, "motion")) != LEON_OK) return rc;
     if ((p->output & LEON_PIPELINE_OUTPUT_ACTIVITY) && (rc = alloc_records(p->activity, "activity")) != LEON_OK) return rc;
+    if ((p->output & LEON_PIPELINE_OUTPUT_RESIDUAL) && (rc = alloc_records(p->residual, "residual")) != LEON_OK) return rc;
     if (p->gpu_parser) {
         std::vector<leon_vlc_gpu_tables> src(1);
         std::vector<leon::VlcTables> t(1);
@@ -3641,6 +3755,47 @@ int leon_pipeline_read_activity(leon_pipeline* p, int64_t window, int32_t index,
     HIP_TRY(hipSetDevice(p->cfg.device_id));
     if (cells) HIP_TRY(hipMemcpy(cells, src, (size_t)L.mbs * 8, hipMemcpyDeviceToHost));
     if (summary) HIP_TRY(hipMemcpy(summary, src + L.summary_offset, 32, hipMemcpyDeviceToHost));
+    return LEON_OK;
+}
+
+int leon_pipeline_residual_layout(int32_t coded_width, int32_t coded_height, struct leon_pipeline_residual_layout* out)
+{
+    return residual_layout_host(coded_width, coded_height, out);
+}
+
+int leon_pipeline_residual_kernel(int32_t device_id, int32_t coded_width, int32_t coded_height, const leon_pipeline_residual_picture* pictures,
+                                  int32_t n_pictures, const leon_pipeline_motion_kernel_frame* frames, int32_t n_frames, int32_t ring_frames,
+                                  int32_t pad_byte, void* ring)
+{
+    return residual_kernel(device_id, coded_width, coded_height, pictures, n_pictures, frames, n_frames, ring_frames, pad_byte, ring);
+}
+
+int leon_pipeline_get_residual_layout(leon_pipeline* p, struct leon_pipeline_residual_layout* out)
+{
+    if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    if (!p->residual.ring) return no_output("residual", "RESIDUAL");
+    return residual_layout_host(p->vinfo.coded_width, p->vinfo.coded_height, out);
+}
+
+int leon_pipeline_window_residual(leon_pipeline* p, int64_t window, void** out, int32_t n)
+{
+    if (!p || !out) return fail(LEON_ERR_INVALID, "null argument");
+    if (!p->residual.ring) return no_output("residual", "RESIDUAL");
+    return window_items(p, window, &PipeWindow::residual, "residual records", out, n);
+}
+
+int leon_pipeline_read_residual(leon_pipeline* p, int64_t window, int32_t index, int16_t* y, int16_t* cb, int16_t* cr)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null argument");
+    if (!p->residual.ring) return no_output("residual", "RESIDUAL");
+    uint8_t* src = nullptr;
+    if (const int rc = window_item(p, window, index, &PipeWindow::residual, &src); rc != LEON_OK) return rc;
+    const leon::ResidualLayout& L = p->residual_lay;
+    HIP_TRY(hipSetDevice(p->cfg.device_id));
+    const size_t w = L.cw, h = L.ch;
+    if (y) HIP_TRY(hipMemcpy2D(y, 2 * w, src, 2 * (size_t)L.luma_stride, 2 * w, h, hipMemcpyDeviceToHost));
+    if (cb) HIP_TRY(hipMemcpy2D(cb, w, src + L.cb_offset, 2 * (size_t)L.chroma_stride, w, h / 2, hipMemcpyDeviceToHost));
+    if (cr) HIP_TRY(hipMemcpy2D(cr, w, src + L.cr_offset, 2 * (size_t)L.chroma_stride, w, h / 2, hipMemcpyDeviceToHost));
     return LEON_OK;
 }
 

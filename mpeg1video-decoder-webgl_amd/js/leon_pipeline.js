@@ -53,6 +53,11 @@
  *                                  prediction (non-DC entries, the sum of their magnitudes, the DC magnitudes, the coded block bits, the
  *                                  quantiser scale where something is coded), with opts.activity true beside any output (include/leon_pipeline.h
  *                                  LEON_PIPELINE_OUTPUT_ACTIVITY); until the window is released
+ *   p.readResidual(window, index) -> {y: Int16Array [codedHeight][codedWidth], cb, cr: Int16Array [codedHeight / 2][codedWidth / 2],
+ *                                  codedWidth, codedHeight}: the frame's residual record -- what the stream's coefficients decode to before
+ *                                  any prediction is added and before any clamp, for the coded picture (the frame is its top-left corner),
+ *                                  with opts.residual true beside any output (include/leon_pipeline.h LEON_PIPELINE_OUTPUT_RESIDUAL);
+ *                                  until the window is released
  *   p.readRegions(window, regions, {size: [h, w], filter}) -> Buffer of n * 3 * h * w elements, packed: regions = [[frameIndex, x, y,
  *                                  width, height], ...], boxes of the window's FULL-RESOLUTION frames (a detector's boxes) each resampled to
  *                                  h x w with the pipeline's element type, table and layout (leon_pipeline_read_regions) -- any tensor
@@ -110,6 +115,7 @@ class LeonPipeline extends EventEmitter {
     }
     if (opts.motion) output = (output || outputs.rgba) | 32;          // LEON_PIPELINE_OUTPUT_MOTION beside whatever output resolves to
     if (opts.activity) output = (output || outputs.rgba) | 128;       // LEON_PIPELINE_OUTPUT_ACTIVITY likewise
+    if (opts.residual) output = (output || outputs.rgba) | 512;       // LEON_PIPELINE_OUTPUT_RESIDUAL likewise
     this._gaugeSources = (opts.motion ? 1 : 0) | (opts.activity ? 2 : 0);          // what gaugeRegions reads without opts.sources: every record output there is
     let tensorDtype = opts.tensorDtype === undefined ? 0 : opts.tensorDtype;
     if (typeof tensorDtype === 'string') {
@@ -182,6 +188,7 @@ class LeonPipeline extends EventEmitter {
   readPlanes(window, index) { return this._p.readPlanes(window, index); }
   readTensor(window, index) { return this._p.readTensor(window, index); }
   readMotion(window, index) { return this._p.readMotion(window, index); }
+  readResidual(window, index) { return this._p.readResidual(window, index); }
   // the addon hands the cells over as they lie, 8 bytes a macroblock; the fields as typed arrays of their own
   readActivity(window, index) {
     const r = this._p.readActivity(window, index), mbs = r.mbWidth * r.mbHeight;

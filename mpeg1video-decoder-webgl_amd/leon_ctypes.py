@@ -49,6 +49,8 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_read_motion", "leon_pipeline_motion_kernel",
     "leon_pipeline_activity_layout", "leon_pipeline_activity_record", "leon_pipeline_activity_kernel", "leon_pipeline_get_activity_layout",
     "leon_pipeline_window_activity", "leon_pipeline_read_activity",
+    "leon_pipeline_residual_layout", "leon_pipeline_residual_kernel", "leon_pipeline_get_residual_layout", "leon_pipeline_window_residual",
+    "leon_pipeline_read_residual",
     "leon_pipeline_carry_refs", "leon_pipeline_carry_record", "leon_pipeline_get_carry_refs", "leon_pipeline_carry_regions_device",
     "leon_pipeline_carry_regions", "leon_pipeline_carry_device",
     "leon_pipeline_propagate_layout", "leon_pipeline_propagate_record", "leon_pipeline_propagate_maps_device", "leon_pipeline_propagate_maps",
@@ -69,6 +71,8 @@ MOTION_FWD, MOTION_BWD, MOTION_INTRA = 1, 2, 4      # the bits of a motion recor
 # the activity output (LEON_PIPELINE_OUTPUT_ACTIVITY, bit 7): Pipeline(activity=True) ORs it in the same way; a record's cell
 PIPELINE_OUTPUT_ACTIVITY = 128
 ACTIVITY_CELL = np.dtype([("ac_count", "<u2"), ("ac_mag", "<u2"), ("dc_mag", "<u2"), ("blocks", "u1"), ("qscale", "u1")])
+# the residual output (LEON_PIPELINE_OUTPUT_RESIDUAL, bit 9): Pipeline(residual=True) ORs it in the same way
+PIPELINE_OUTPUT_RESIDUAL = 512
 TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 1, 2, 3       # LEON_TENSOR_*
 TENSOR_DTYPES = {"float16": TENSOR_F16, "bfloat16": TENSOR_BF16, "float32": TENSOR_F32}
 TENSOR_U8 = 8                                       # LEON_TENSOR_U8 ("uint8"): the element is the 8-bit colour value
@@ -443,6 +447,16 @@ class PipelineActivityPicture(C.Structure):
     _fields_ = [("grp_off", C.c_void_p), ("entries", C.c_void_p), ("qscale", C.c_void_p), ("n_entries", C.c_uint32), ("reserved0", C.c_int32)]
 
 
+class PipelineResidualLayout(C.Structure):
+    _fields_ = [("coded_width", C.c_int32), ("coded_height", C.c_int32), ("luma_stride", C.c_int32), ("chroma_stride", C.c_int32), ("cb_offset", C.c_uint64),
+                ("cr_offset", C.c_uint64), ("record_bytes", C.c_uint64), ("record_pitch", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+class PipelineResidualPicture(C.Structure):
+    _fields_ = [("grp_off", C.c_void_p), ("entries", C.c_void_p), ("qscale", C.c_void_p), ("intra", C.c_void_p), ("matrices", C.c_void_p),
+                ("premultiplier", C.c_void_p), ("n_entries", C.c_uint32), ("reserved0", C.c_int32)]
+
+
 class PipelineFrame(C.Structure):
     _fields_ = [("gop", C.c_uint64), ("display_index", C.c_int32), ("type", C.c_int32), ("ts_ms", C.c_double),
                 ("rgba", C.c_void_p), ("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("a", C.c_void_p)]
@@ -595,6 +609,13 @@ def load():
         lib.leon_pipeline_get_activity_layout.argtypes = [C.c_void_p, C.POINTER(PipelineActivityLayout)]
         lib.leon_pipeline_window_activity.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int32]
         lib.leon_pipeline_read_activity.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_window_residual"):
+        lib.leon_pipeline_residual_layout.argtypes = [C.c_int32, C.c_int32, C.POINTER(PipelineResidualLayout)]
+        lib.leon_pipeline_residual_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PipelineResidualPicture), C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                      C.c_int32, C.c_void_p]
+        lib.leon_pipeline_get_residual_layout.argtypes = [C.c_void_p, C.POINTER(PipelineResidualLayout)]
+        lib.leon_pipeline_window_residual.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int32]
+        lib.leon_pipeline_read_residual.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(lib, "leon_pipeline_carry_regions"):
         P = C.POINTER
         lib.leon_pipeline_carry_refs.argtypes = [P(PipelineFrame), P(PipelineMotionFrame), C.c_int32, C.c_void_p, C.c_void_p]
@@ -855,6 +876,39 @@ def activity_kernel(mbw, mbh, pictures, frames, ring_frames=None, pad_byte=0, fi
         q.n_entries = int(pic[3]) if len(pic) > 3 else (0 if arrs[1] is None else arrs[1].size)
         return arrs
     return _record_kernel("leon_pipeline_activity_kernel", activity_layout, PipelineActivityPicture, one, mbw, mbh, pictures, frames, ring_frames, pad_byte, fill, ring,
+                          device_id, n_pictures, n_frames)
+
+
+def residual_layout(cw, ch):
+    """leon_pipeline_residual_layout: where the planes of a residual record of a coded picture of cw x ch lie (PipelineResidualLayout), no device"""
+    out = PipelineResidualLayout()
+    _chk(load().leon_pipeline_residual_layout(int(cw), int(ch), C.byref(out)))
+    return out
+
+
+def residual_planes(buf, lay, pads=False):
+    """a record buffer (uint8, at least record_bytes) -> (y [ch, cw], cb, cr [ch / 2, cw / 2]) int16, copies of the specified elements;
+    pads=True: the whole rows instead, pad columns included ([ch, luma_stride], [ch / 2, chroma_stride] twice)"""
+    cw, ch, ls, cs = lay.coded_width, lay.coded_height, lay.luma_stride, lay.chroma_stride
+    y = buf[:2 * ls * ch].view("<i2").reshape(ch, ls)
+    cb = buf[lay.cb_offset:lay.cb_offset + 2 * cs * (ch // 2)].view("<i2").reshape(ch // 2, cs)
+    cr = buf[lay.cr_offset:lay.cr_offset + 2 * cs * (ch // 2)].view("<i2").reshape(ch // 2, cs)
+    if pads:
+        return y.copy(), cb.copy(), cr.copy()
+    return y[:, :cw].copy(), cb[:, :cw // 2].copy(), cr[:, :cw // 2].copy()
+
+
+def residual_kernel(cw, ch, pictures, frames, ring_frames=None, pad_byte=0, fill=0xA5, ring=None, device_id=0, n_pictures=None, n_frames=None):
+    """leon_pipeline_residual_kernel: k_residual on lists, maps and matrices the caller supplies.  pictures = [(grp_off, entries, qscale, intra,
+    matrices [128], premultiplier [64]) or the same with n_entries behind them, ...] (n_entries: the capacity handed over, len(entries) by
+    default); frames, the ring and the rest as activity_kernel's.  Returns the ring, uint8 [ring_frames, record_pitch], as it came back
+    (residual_planes takes a record of it apart)."""
+    def one(q, pic):
+        arrs = _activity_arrays(*pic[:3]) + tuple(None if a is None else np.ascontiguousarray(a, dtype=np.uint8) for a in pic[3:6])
+        q.grp_off, q.entries, q.qscale, q.intra, q.matrices, q.premultiplier = [None if a is None or not a.size else a.ctypes.data for a in arrs]
+        q.n_entries = int(pic[6]) if len(pic) > 6 else (0 if arrs[1] is None else arrs[1].size)
+        return arrs
+    return _record_kernel("leon_pipeline_residual_kernel", residual_layout, PipelineResidualPicture, one, cw, ch, pictures, frames, ring_frames, pad_byte, fill, ring,
                           device_id, n_pictures, n_frames)
 
 
@@ -1599,8 +1653,9 @@ class _Frames:
     """the frames of a delivered window as a read-only sequence of dicts, made when asked for (a 128-GOP window has 1536 of
     them; a callback that looks at a dozen should not pay for the rest on the pipeline's notify thread)"""
 
-    def __init__(self, frames, n, pipe, window=-1, tensors=None, motion=None, activity=None):
+    def __init__(self, frames, n, pipe, window=-1, tensors=None, motion=None, activity=None, residual=None):
         self._f, self._n, self._pipe, self._window, self._tensors, self._motion, self._activity = frames, n, pipe, window, tensors, motion, activity
+        self._residual = residual
 
     def __len__(self):
         return self._n
@@ -1618,6 +1673,7 @@ class _Frames:
                 "gop": int(f.gop), "display_index": f.display_index, "type": f.type, "ts_ms": f.ts_ms, "rgba": f.rgba,
                 "y": f.y, "cb": f.cb, "cr": f.cr, "a": f.a, "tensor": self._tensors[i] if self._tensors is not None else None,
                 "activity": self._activity[i] if self._activity is not None else None,
+                "residual": self._residual[i] if self._residual is not None else None,
                 "_i": i, "_window": self._window, "_frames": self._f, "_pipe": self._pipe}
 
     def __iter__(self):
@@ -1635,7 +1691,7 @@ def _device_tensor_check(name, t, dtype, count, dev, words=False, strided=False)
         raise ValueError("%s: a contiguous %s tensor of at least %d %s" % ((name, "int32", count, "words") if words else (name, dtype, count, "elements")))
 
 
-def _need_output(layout, name):          # the layout of a Pipeline's record output ("motion", "activity"), or the refusal of one made without it
+def _need_output(layout, name):          # the layout of a Pipeline's record output ("motion", "activity", "residual"), or the refusal of one made without it
     if layout is None:
         raise LeonError(ERR_INVALID, "the pipeline has no %s output (Pipeline %s=True)" % (name, name))
     return layout
@@ -1689,6 +1745,10 @@ class Pipeline:
     stream coded on top of the prediction (ACTIVITY_CELL: ac_count, ac_mag, dc_mag, blocks, qscale) and a summary of eight words:
     activity_from_lists states it.  frame["activity"] = the record's device address; read_activity(window, i) copies it to the host,
     activity_view(window, i) wraps it in place; activity_layout has the offsets.
+    residual=True (beside any output, independent of the two above): every frame carries its residual record -- the int16 planes Y, Cb, Cr
+    of the coded picture that the stream's coefficients decode to before any prediction is added and before any clamp (the oracle's
+    pass 1 and residual pass 2 state it).  frame["residual"] = the record's device address; read_residual(window, i) copies the three
+    planes to the host, residual_view(window, i) wraps them in place; residual_layout has strides and offsets.
     Carrying boxes (motion=True): carry_regions_device(window, records) moves boxes from one frame of the window to another along those
     vectors, on the device and on torch's current stream (carry_box states one hop; carry_regions is the same from host records);
     gauge_regions_device(window, records) returns per box the area-weighted sums of the frame's motion and activity records under it
@@ -1703,7 +1763,8 @@ class Pipeline:
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
                  output="rgba", tensor_dtype="float16", tensor_scale=None, tensor_bias=None, tensor_size=None, tensor_crop=None, tensor_filter=RESIZE_TRIANGLE,
-                 tensor_layout="chw", tensor_canvas=None, tensor_origin=None, tensor_pad_value=None, tensor_letterbox=None, motion=False, activity=False):
+                 tensor_layout="chw", tensor_canvas=None, tensor_origin=None, tensor_pad_value=None, tensor_letterbox=None, motion=False, activity=False,
+                 residual=False):
         self.lib = load()
         if tensor_letterbox is not None:
             if tensor_size is not None or tensor_canvas is not None or tensor_origin is not None:
@@ -1724,6 +1785,8 @@ class Pipeline:
             out_bits = (out_bits or PIPELINE_OUTPUT_RGBA) | PIPELINE_OUTPUT_MOTION
         if activity:
             out_bits = (out_bits or PIPELINE_OUTPUT_RGBA) | PIPELINE_OUTPUT_ACTIVITY
+        if residual:
+            out_bits = (out_bits or PIPELINE_OUTPUT_RGBA) | PIPELINE_OUTPUT_RESIDUAL
         tcfg = None
         if out_bits > 0 and out_bits & PIPELINE_OUTPUT_TENSOR:
             tcfg = PipelineTensorConfig(_tensor_dtype_code(tensor_dtype), (C.c_float * 3)(*([0, 0, 0] if tensor_scale is None else tensor_scale)),
@@ -1801,7 +1864,12 @@ class Pipeline:
                         activity = (C.c_void_p * n)()
                         if self.lib.leon_pipeline_window_activity(self.h, window, activity, n) != OK:
                             raise LeonError(ERR_INVALID, self.lib.leon_last_error().decode())
-                    fl = _Frames(frames, n, self, window, tensors, motion, activity)
+                    residual = None
+                    if self.info.output & PIPELINE_OUTPUT_RESIDUAL and n:        # ... and its residual records
+                        residual = (C.c_void_p * n)()
+                        if self.lib.leon_pipeline_window_residual(self.h, window, residual, n) != OK:
+                            raise LeonError(ERR_INVALID, self.lib.leon_last_error().decode())
+                    fl = _Frames(frames, n, self, window, tensors, motion, activity, residual)
                     keep = self._on_window(window, fl)
                 if keep is not False:
                     _release(window)
@@ -1864,6 +1932,11 @@ class Pipeline:
             lay = PipelineActivityLayout()
             rc = self.lib.leon_pipeline_get_activity_layout(self.h, C.byref(lay))
             self.activity_layout = lay
+        self.residual_layout = None
+        if rc == OK and info.output & PIPELINE_OUTPUT_RESIDUAL:
+            lay = PipelineResidualLayout()
+            rc = self.lib.leon_pipeline_get_residual_layout(self.h, C.byref(lay))
+            self.residual_layout = lay
         ready.set()
         _chk(rc)
 
@@ -1927,6 +2000,32 @@ class Pipeline:
         return (_cuda_view(ptr, (lay.mb_height, lay.mb_width, 4), "<i2", (lay.mb_width * 8, 8, 2), dev),
                 _cuda_view(ptr, (lay.mb_height, lay.mb_width, 8), "|u1", (lay.mb_width * 8, 8, 1), dev),
                 _cuda_view(ptr + lay.summary_offset, (8,), "<i4", (4,), dev))
+
+    def window_residual(self, window, n):
+        """leon_pipeline_window_residual: the device addresses of the n residual records of a delivered, not yet released window"""
+        out = (C.c_void_p * max(1, int(n)))()
+        _chk(self.lib.leon_pipeline_window_residual(self.h, int(window), out, int(n)))
+        return out
+
+    def read_residual(self, window, index):
+        """the residual record of frame `index` of a delivered, not yet released window as host arrays, cropped to the coded size:
+        (y [ch, cw], cb [ch / 2, cw / 2], cr [ch / 2, cw / 2]) int16"""
+        lay = self.residual_layout
+        cw, ch = (lay.coded_width, lay.coded_height) if lay is not None else (16, 16)      # (without the output the library refuses below)
+        y, cb, cr = np.empty((ch, cw), dtype=np.int16), np.empty((ch // 2, cw // 2), dtype=np.int16), np.empty((ch // 2, cw // 2), dtype=np.int16)
+        _chk(self.lib.leon_pipeline_read_residual(self.h, int(window), int(index), y.ctypes.data, cb.ctypes.data, cr.ctypes.data))
+        return y, cb, cr
+
+    def residual_view(self, window, index, device_id=None):
+        """the same three planes where they lie, as strided torch views of device memory (int16 [ch, cw], [ch / 2, cw / 2] twice), without
+        copying: valid until the window is released"""
+        lay = _need_output(self.residual_layout, "residual")
+        ptr = self.window_residual(window, self._delivered_n(window))[int(index)]
+        dev = self.device_id if device_id is None else device_id
+        cw, ch = lay.coded_width, lay.coded_height
+        return (_cuda_view(ptr, (ch, cw), "<i2", (2 * lay.luma_stride, 2), dev),
+                _cuda_view(ptr + lay.cb_offset, (ch // 2, cw // 2), "<i2", (2 * lay.chroma_stride, 2), dev),
+                _cuda_view(ptr + lay.cr_offset, (ch // 2, cw // 2), "<i2", (2 * lay.chroma_stride, 2), dev))
 
     def carry_refs(self, window):
         """leon_pipeline_get_carry_refs: (fwd, bwd) int32 arrays -- for each frame of a delivered, not yet released window the index of

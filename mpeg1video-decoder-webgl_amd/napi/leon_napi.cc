@@ -686,6 +686,45 @@ napi_value PipeReadActivity(napi_env env, napi_callback_info info)
     return o;
 }
 
+// p.readResidual(window, i) -> {y: Int16Array [codedHeight][codedWidth], cb, cr: Int16Array [codedHeight / 2][codedWidth / 2], codedWidth,
+// codedHeight}: one frame's residual record (opts.residual; include/leon_pipeline.h LEON_PIPELINE_OUTPUT_RESIDUAL), copied to the host, packed
+napi_value PipeReadResidual(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2;
+    napi_value argv[2];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    int32_t i = -1;
+    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "readResidual(window, index)");
+        return nullptr;
+    }
+    struct leon_pipeline_residual_layout lay;
+    int rc = leon_pipeline_get_residual_layout(h->p, &lay);
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    napi_value o, ab[3], ta[3];
+    void* data[3] = {nullptr, nullptr, nullptr};
+    const size_t luma = (size_t)lay.coded_width * (size_t)lay.coded_height;
+    NAPI_OK(napi_create_object(env, &o));
+    for (int k = 0; k < 3; k++) {
+        const size_t n = k == 0 ? luma : luma / 4;
+        NAPI_OK(napi_create_arraybuffer(env, n * 2, &data[k], &ab[k]));
+        NAPI_OK(napi_create_typedarray(env, napi_int16_array, n, ab[k], 0, &ta[k]));
+    }
+    if ((rc = leon_pipeline_read_residual(h->p, w, i, (int16_t*)data[0], (int16_t*)data[1], (int16_t*)data[2])) != LEON_OK) return throw_leon(env, rc);
+    NAPI_OK(napi_set_named_property(env, o, "y", ta[0]));
+    NAPI_OK(napi_set_named_property(env, o, "cb", ta[1]));
+    NAPI_OK(napi_set_named_property(env, o, "cr", ta[2]));
+    const struct { const char* name; double v; } nums[] = {{"codedWidth", (double)lay.coded_width}, {"codedHeight", (double)lay.coded_height}};
+    for (const auto& kv : nums) {
+        napi_value v;
+        NAPI_OK(napi_create_double(env, kv.v, &v));
+        NAPI_OK(napi_set_named_property(env, o, kv.name, v));
+    }
+    return o;
+}
+
 // p.readRegions(window, boxes, outHeight, outWidth, filter) -> Buffer of n * region bytes (3 * outHeight * outWidth elements of the
 // pipeline's element type and layout each, packed): leon_pipeline_read_regions.  boxes: an Int32Array of n x [frame index, x, y, width, height].
 // Five numbers more -- fit mode, anchor, pad r, g, b (leon_pipeline_regions_fit) -- make it leon_pipeline_read_regions_fit.
@@ -1185,7 +1224,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readActivity", PipeReadActivity}, {"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"gaugeRegions", PipeGaugeRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readActivity", PipeReadActivity}, {"readResidual", PipeReadResidual},{"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"gaugeRegions", PipeGaugeRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));

@@ -56,6 +56,7 @@ def main():
     ap.add_argument("--motion", action="store_true", help="every frame carries its motion record too (LEON_PIPELINE_OUTPUT_MOTION: k_motion, one launch per window)")
     ap.add_argument("--activity", action="store_true", help="every frame carries its activity record too (LEON_PIPELINE_OUTPUT_ACTIVITY: k_activity and k_activity_summary, "
                                                             "one launch each per window)")
+    ap.add_argument("--residual", action="store_true", help="every frame carries its residual record too (LEON_PIPELINE_OUTPUT_RESIDUAL: k_residual, one launch per window)")
     ap.add_argument("--varied", action="store_true", help="the 16-GOP stream with 16 different contents (tools/stream_1080p.py) instead of --gops GOPs")
     ap.add_argument("--open-gops", action="store_true", help="with --varied: the same recipe written with open GOPs (closed_gop = 0), the leading B pictures "
                                                              "predicting forward (from the GOP before) and bidirectionally")
@@ -141,7 +142,7 @@ def main():
     t0 = time.perf_counter()
     pipe = L.Pipeline(data, parser_threads=a.threads, gops_per_window=a.window, windows_in_flight=a.inflight, loop=a.loop, gpu_parser=a.gpu_parser,
                       output=a.output, tensor_dtype=a.tensor_dtype, tensor_size=a.tensor_size, tensor_crop=a.tensor_crop, tensor_layout=a.tensor_layout, tensor_filter=a.tensor_filter,
-                      tensor_canvas=a.tensor_canvas, tensor_letterbox=a.tensor_letterbox, tensor_pad_value=a.tensor_pad_value, on_window=on_window, motion=a.motion, activity=a.activity)
+                      tensor_canvas=a.tensor_canvas, tensor_letterbox=a.tensor_letterbox, tensor_pad_value=a.tensor_pad_value, on_window=on_window, motion=a.motion, activity=a.activity, residual=a.residual)
     free1 = free_device_bytes()
     pool = L.pool_stats()
     pipe.wait()
@@ -155,7 +156,8 @@ def main():
                   % (pipe.info.frame_width, pipe.info.frame_height, {"rgba": "RGBA", "ycbcr": "YCbCr planes", "both": "RGBA + YCbCr planes", "tensor": "tensors", "rgba+tensor": "RGBA + tensors",
                      "ycbcr+tensor": "YCbCr planes + tensors", "all": "RGBA + YCbCr planes + tensors"}[a.output]),
         "output": a.output, "motion": a.motion, "motion_record_bytes": pipe.motion_layout.record_bytes if pipe.motion_layout is not None else None,
-        "activity": a.activity, "activity_record_bytes": pipe.activity_layout.record_bytes if pipe.activity_layout is not None else None, "tensor_dtype": a.tensor_dtype if pipe.info.tensor_dtype else None, "tensor_layout": a.tensor_layout if pipe.info.tensor_dtype else None,
+        "activity": a.activity, "activity_record_bytes": pipe.activity_layout.record_bytes if pipe.activity_layout is not None else None,
+        "residual": a.residual, "residual_record_bytes": pipe.residual_layout.record_bytes if pipe.residual_layout is not None else None, "tensor_dtype": a.tensor_dtype if pipe.info.tensor_dtype else None, "tensor_layout": a.tensor_layout if pipe.info.tensor_dtype else None,
         "tensor_frame_bytes": pipe.info.tensor_frame_bytes, "tensor_size": a.tensor_size, "tensor_crop": a.tensor_crop, "tensor_filter": a.tensor_filter if (a.tensor_size or a.tensor_letterbox) else None,
         "tensor_canvas": [canvas.height, canvas.width] if canvas else None, "tensor_image": [canvas.x, canvas.y, canvas.image_width, canvas.image_height] if canvas else None,
         "tensor_pad_value": list(canvas.pad) if canvas else None, "host_resize": a.host_resize, "windows_in_flight": a.inflight,
