@@ -1502,6 +1502,61 @@ int kernel_frames_check(const char* who, int32_t n_pics, const leon_pipeline_mot
     }
     return LEON_OK;
 }
+// The pieces of one device allocation that a synchronous call makes for itself (the host roads, the diagnostics on a caller's records,
+// resize_weights_device): `src` goes up if there is one, `dst` is brought back if there is one, `bytes` of either.  A piece without
+// a source holds what the allocation happens to hold; where a caller's array is both, the words the kernel leaves alone come back
+// as they were.  Every piece lies on a 256-byte boundary and takes 256 bytes at the least, so one of no bytes (no frames, no slots)
+// still has an address of its own that nothing reads.  alloc() lays them out and allocates, after which at() gives the device
+// address of piece i; up() and down() copy on the null stream, and down()'s copies wait: nothing in flight reads the allocation when
+// it goes.
+struct Piece { const void* src; void* dst; size_t bytes; };
+class Pieces {
+public:
+    int alloc(const char* who, std::initializer_list<Piece> pieces)
+    {
+        pieces_ = pieces;
+        size_t bytes = 0;
+        for (const Piece& q : pieces_) bytes += pad256(std::max<size_t>(q.bytes, 1));
+        if (!d_.alloc(bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "%s: %zu bytes of device memory", who, bytes); }
+        uint8_t* at = d_;
+        for (const Piece& q : pieces_) {
+            at_.push_back(at);
+            at += pad256(std::max<size_t>(q.bytes, 1));
+        }
+        return LEON_OK;
+    }
+    template <class T = uint8_t> T* at(size_t i) const { return reinterpret_cast<T*>(at_[i]); }
+    int up() const
+    {
+        for (size_t i = 0; i < pieces_.size(); i++)
+            if (pieces_[i].src && pieces_[i].bytes) HIP_TRY(hipMemcpy(at_[i], pieces_[i].src, pieces_[i].bytes, hipMemcpyHostToDevice));
+        return LEON_OK;
+    }
+    int down() const
+    {
+        for (size_t i = 0; i < pieces_.size(); i++)
+            if (pieces_[i].dst && pieces_[i].bytes) HIP_TRY(hipMemcpy(pieces_[i].dst, at_[i], pieces_[i].bytes, hipMemcpyDeviceToHost));
+        return LEON_OK;
+    }
+
+private:
+    DevBuf<uint8_t> d_;
+    std::vector<Piece> pieces_;
+    std::vector<uint8_t*> at_;
+};
+// One such call whose sources are complete before the allocation: the pieces up, run(pieces) -- which enqueues on the null stream, or
+// is a device road that has waited -- the runtime's last error, the pieces down.  Nothing touches the device before it.
+template <class Run>
+int pieces_run(int32_t device_id, const char* who, std::initializer_list<Piece> pieces, Run run)
+{
+    HIP_TRY(hipSetDevice(device_id));
+    Pieces s;
+    int rc;
+    if ((rc = s.alloc(who, pieces)) != LEON_OK || (rc = s.up()) != LEON_OK || (rc = run(s)) != LEON_OK) return rc;
+    HIP_TRY(hipGetLastError());
+    return s.down();
+}
+
 // A record kernel on a caller's pictures (motion_kernel, activity_kernel): memory of its own, the null stream.  One device allocation
 // [descriptors | payload | ring]: every array of every picture in a piece of its own, padded with pad_byte; the caller's ring of
 // records `pitch` apart goes up and comes back whole.  `sized(i, picture, &bytes)` refuses picture i or gives the bytes its pieces
@@ -1521,14 +1576,15 @@ int record_kernel(const char* who, int32_t device_id, int32_t mbw, int32_t mbh, 
         payload_bytes += b;
     }
     if (const int rc = kernel_frames_check(who, n_pics, frames, n_frames, ring_frames); rc != LEON_OK) return rc;
-    const size_t descs_bytes = pad256((size_t)n_frames * sizeof(Desc)), ring_bytes = (size_t)ring_frames * pitch;
-    const size_t bytes = descs_bytes + payload_bytes + ring_bytes;
-    HIP_TRY(hipSetDevice(device_id));
-    DevBuf<uint8_t> d;
-    if (!d.alloc(bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "%s: %zu bytes of device memory", who, bytes); }
-    uint8_t *d_payload = d + descs_bytes, *d_ring = d_payload + payload_bytes;
     // the payload as the device will hold it, staged on the host: the pad byte everywhere, then each array into its piece
     std::vector<uint8_t> payload(payload_bytes, (uint8_t)pad_byte);
+    std::vector<Desc> pic_descs((size_t)n_pics), descs((size_t)n_frames);
+    HIP_TRY(hipSetDevice(device_id));
+    Pieces s;
+    if (const int rc = s.alloc(who, {{descs.data(), nullptr, descs.size() * sizeof(Desc)}, {payload.data(), nullptr, payload_bytes},      // (I pictures alone have no payload)
+                                     {ring, ring, (size_t)ring_frames * pitch}}); rc != LEON_OK)
+        return rc;
+    const uint8_t* d_payload = s.at(1);
     size_t at = 0;
     auto place = [&](const void* src, size_t n, size_t padded) {
         if (n) memcpy(payload.data() + at, src, n);          // (a picture's empty list may be null)
@@ -1536,19 +1592,15 @@ int record_kernel(const char* who, int32_t device_id, int32_t mbw, int32_t mbh, 
         at += padded;
         return dev;
     };
-    std::vector<Desc> pic_descs((size_t)n_pics), descs((size_t)n_frames);
     for (int32_t i = 0; i < n_pics; i++) pic_descs[(size_t)i] = fill(pics[i], place);
     for (int32_t i = 0; i < n_frames; i++) {
         descs[(size_t)i] = pic_descs[(size_t)frames[i].picture];
         descs[(size_t)i].frame = (uint32_t)frames[i].ring;
     }
-    HIP_TRY(hipMemcpy(d, descs.data(), descs.size() * sizeof(Desc), hipMemcpyHostToDevice));
-    if (payload_bytes) HIP_TRY(hipMemcpy(d_payload, payload.data(), payload_bytes, hipMemcpyHostToDevice));      // (I pictures alone have none)
-    HIP_TRY(hipMemcpy(d_ring, ring, ring_bytes, hipMemcpyHostToDevice));
-    launch(reinterpret_cast<const Desc*>(d.get()), (size_t)n_frames, d_ring);
+    if (const int rc = s.up(); rc != LEON_OK) return rc;
+    launch(s.at<const Desc>(0), (size_t)n_frames, s.at(2));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(ring, d_ring, ring_bytes, hipMemcpyDeviceToHost));      // (the copy waits: nothing in flight reads d when it goes)
-    return LEON_OK;
+    return s.down();
 }
 
 // k_motion on maps the caller supplies (leon_pipeline_motion_kernel): every map padded as MapLayout pads it (mpad, vpad)
@@ -2391,76 +2443,92 @@ int carry_pipeline_check(const leon_pipeline* p)
     return LEON_OK;
 }
 
-// One call of the device road: the host's refusals, then inside the boxes bracket (the window's table is all of the scratch it needs)
-// one launch on the caller's stream (or the regions stream and a wait)
-int carry_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_carry_regions_call* c)
+// The head of the device roads that read the record rings through the window's table (carry, gauge, propagate), after the family's
+// judgement of its pipeline: regions_mu, the table, what every such call refuses alike under its prefix `who` -- a reserved word, the
+// count of its `noun` -- then the family's own (`checks()`: null pointers, alignment, propagate's config), then inside the boxes
+// bracket (the table is all of the scratch it needs) `launch(st, frames, n_frames)` on the caller's stream (or the regions stream and a
+// wait)
+template <class Checks, class Launch>
+int table_road(leon_pipeline* p, int64_t window, void* stream, const char* who, const char* noun, int32_t n, bool reserved_set, Checks checks, Launch launch)
 {
-    int rc = carry_pipeline_check(p);
-    if (rc != LEON_OK) return rc;
-    if (!c) return fail(LEON_ERR_INVALID, "null argument");
     std::unique_lock<std::mutex> call(p->regions_mu);
     std::vector<uint32_t> table;
-    if ((rc = carry_window_table(p, window, &table)) != LEON_OK) return rc;
-    const int32_t n = c->n;
-    if (c->reserved0 || c->reserved[0] || c->reserved[1]) return fail(LEON_ERR_INVALID, "carry regions: a reserved word of the call is not 0");
-    if ((rc = record_count_check("carry regions", "regions", n)) != LEON_OK) return rc;
-    if (!c->regions) return fail(LEON_ERR_INVALID, "carry regions: null regions");
-    if (!c->device_out) return fail(LEON_ERR_INVALID, "carry regions: null device_out");
-    if (((uintptr_t)c->regions | (uintptr_t)c->device_out | (uintptr_t)c->device_votes | (uintptr_t)c->device_status) & 3u)
-        return fail(LEON_ERR_INVALID, "carry regions: regions %p, device_out %p, device_votes %p, device_status %p: not all 4-byte aligned", (const void*)c->regions,
-                    (void*)c->device_out, (void*)c->device_votes, (void*)c->device_status);
-    return boxes_run(p, c->stream, call, table, pad256(std::max<size_t>(table.size(), 1) * 4), [&](hipStream_t st, uint32_t* d_table) {
-        carry_launch(st, reinterpret_cast<const leon::CarryRecord*>(c->regions), reinterpret_cast<const leon::CarryFrame*>(d_table), p->motion.ring, p->vinfo.frame_width,
-                     p->vinfo.frame_height, p->vinfo.mb_width, p->motion_lay, (int32_t)(table.size() / 4), n, reinterpret_cast<int32_t*>(c->device_out), c->device_votes,
-                     c->device_status);
+    int rc = carry_window_table(p, window, &table);
+    if (rc != LEON_OK) return rc;
+    if (reserved_set) return fail(LEON_ERR_INVALID, "%s: a reserved word of the call is not 0", who);
+    if ((rc = record_count_check(who, noun, n)) != LEON_OK || (rc = checks()) != LEON_OK) return rc;
+    return boxes_run(p, stream, call, table, pad256(std::max<size_t>(table.size(), 1) * 4), [&](hipStream_t st, uint32_t* d_table) {
+        launch(st, reinterpret_cast<const leon::CarryFrame*>(d_table), (int32_t)(table.size() / 4));
+    });
+}
+// Their host roads, after the family's argument checks: the window's refusals before anything is allocated or uploaded (the device
+// road judges it again under the same lock), then between the pieces going up and coming back `device(pieces)`: the device road with
+// stream NULL, which has waited when it returns
+template <class Device>
+int table_host_road(leon_pipeline* p, int64_t window, const char* who, std::initializer_list<Piece> pieces, Device device)
+{
+    {
+        std::unique_lock<std::mutex> call(p->regions_mu);
+        std::vector<uint32_t> table;
+        if (const int rc = carry_window_table(p, window, &table); rc != LEON_OK) return rc;
+    }
+    return pieces_run(p->cfg.device_id, who, pieces, device);
+}
+// Their diagnostics' window: the table -- a frame that `has(i)` a record gets the next slot of the ring(s), a frame without gets none:
+// its ring id stays 0 and nothing of the call reads it; fwd, bwd: null where the family reads no references -- and a ring of `slots`
+// records `pitch` apart staged on the host as record_kernel stages its payload, frame i's record at its slot, to go up as one piece
+// (records null: a ring the call does not read, of no bytes)
+template <class Has>
+std::vector<leon::CarryFrame> kernel_table(int32_t n_frames, const int32_t* fwd, const int32_t* bwd, Has has, uint32_t* slots)
+{
+    std::vector<leon::CarryFrame> table((size_t)n_frames);
+    *slots = 0;
+    for (size_t i = 0; i < table.size(); i++) table[i] = leon::CarryFrame{has(i) ? (*slots)++ : 0u, fwd ? fwd[i] : -1, bwd ? bwd[i] : -1, 0u};
+    return table;
+}
+std::vector<uint8_t> kernel_ring(const std::vector<leon::CarryFrame>& table, uint32_t slots, const void* const* records, size_t record_bytes, size_t pitch)
+{
+    std::vector<uint8_t> ring(records ? (size_t)slots * pitch : 0);
+    for (size_t i = 0; records && i < table.size(); i++)
+        if (records[i]) memcpy(ring.data() + (size_t)table[i].ring * pitch, records[i], record_bytes);
+    return ring;
+}
+
+// One call of the device road: the host's refusals, then one launch
+int carry_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_carry_regions_call* c)
+{
+    if (const int rc = carry_pipeline_check(p); rc != LEON_OK) return rc;
+    if (!c) return fail(LEON_ERR_INVALID, "null argument");
+    return table_road(p, window, c->stream, "carry regions", "regions", c->n, c->reserved0 || c->reserved[0] || c->reserved[1], [&] {
+        if (!c->regions) return fail(LEON_ERR_INVALID, "carry regions: null regions");
+        if (!c->device_out) return fail(LEON_ERR_INVALID, "carry regions: null device_out");
+        if (((uintptr_t)c->regions | (uintptr_t)c->device_out | (uintptr_t)c->device_votes | (uintptr_t)c->device_status) & 3u)
+            return fail(LEON_ERR_INVALID, "carry regions: regions %p, device_out %p, device_votes %p, device_status %p: not all 4-byte aligned", (const void*)c->regions,
+                        (void*)c->device_out, (void*)c->device_votes, (void*)c->device_status);
+        return (int)LEON_OK;
+    }, [&](hipStream_t st, const leon::CarryFrame* d_frames, int32_t n_frames) {
+        carry_launch(st, reinterpret_cast<const leon::CarryRecord*>(c->regions), d_frames, p->motion.ring, p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width,
+                     p->motion_lay, n_frames, c->n, reinterpret_cast<int32_t*>(c->device_out), c->device_votes, c->device_status);
     });
 }
 
-// records, results: one device allocation [records | out | votes | status]; what the caller has in out, votes and status goes up first,
-// so that the words the kernel leaves alone come back as they were
-struct CarryHostBufs {
-    DevBuf<int32_t> d;
-    int32_t *recs = nullptr, *out = nullptr, *votes = nullptr, *status = nullptr;
-};
-int carry_host_up(CarryHostBufs* b, size_t extra_bytes, const leon_pipeline_carry_region* regions, int32_t n, const leon_pipeline_region* out, const int32_t* votes,
-                  const int32_t* status, char** extra)
-{
-    const size_t words = (size_t)n * (8 + 8 + 4 + 1), bytes = pad256(words * 4);
-    if (!b->d.alloc(bytes + extra_bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "carry: %zu bytes of device memory", bytes + extra_bytes); }
-    b->recs = b->d; b->out = b->recs + (size_t)n * 8; b->votes = b->out + (size_t)n * 8; b->status = b->votes + (size_t)n * 4;
-    if (extra) *extra = reinterpret_cast<char*>(b->d.get()) + bytes;
-    HIP_TRY(hipMemcpy(b->recs, regions, (size_t)n * 32, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->out, out, (size_t)n * 32, hipMemcpyHostToDevice));
-    if (votes) HIP_TRY(hipMemcpy(b->votes, votes, (size_t)n * 16, hipMemcpyHostToDevice));
-    if (status) HIP_TRY(hipMemcpy(b->status, status, (size_t)n * 4, hipMemcpyHostToDevice));
-    return LEON_OK;
-}
-int carry_host_down(const CarryHostBufs& b, int32_t n, leon_pipeline_region* out, int32_t* votes, int32_t* status)
-{
-    HIP_TRY(hipMemcpy(out, b.out, (size_t)n * 32, hipMemcpyDeviceToHost));
-    if (votes) HIP_TRY(hipMemcpy(votes, b.votes, (size_t)n * 16, hipMemcpyDeviceToHost));
-    if (status) HIP_TRY(hipMemcpy(status, b.status, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return LEON_OK;
-}
-
-// One call of the host road: the device road on the regions stream between an upload and three copies
+// One call of the host road: [records | out | votes | status], what the caller has in out, votes and status going up first
 int carry_regions(leon_pipeline* p, int64_t window, const leon_pipeline_carry_region* regions, int32_t n, leon_pipeline_region* out, int32_t* votes, int32_t* status)
 {
     int rc = carry_pipeline_check(p);
     if (rc != LEON_OK) return rc;
     if (!regions || !out) return fail(LEON_ERR_INVALID, "carry regions: null %s", regions ? "out" : "regions");
     if ((rc = record_count_check("carry regions", "regions", n)) != LEON_OK) return rc;
-    HIP_TRY(hipSetDevice(p->cfg.device_id));
-    CarryHostBufs b;
-    if ((rc = carry_host_up(&b, 0, regions, n, out, votes, status, nullptr)) != LEON_OK) return rc;
-    leon_pipeline_carry_regions_call c{};
-    c.regions = reinterpret_cast<const leon_pipeline_carry_region*>(b.recs);
-    c.n = n;
-    c.device_out = reinterpret_cast<leon_pipeline_region*>(b.out);
-    c.device_votes = votes ? b.votes : nullptr;
-    c.device_status = status ? b.status : nullptr;
-    if ((rc = carry_regions_device(p, window, &c)) != LEON_OK) return rc;      // (stream NULL: it has waited)
-    return carry_host_down(b, n, out, votes, status);
+    return table_host_road(p, window, "carry", {{regions, nullptr, (size_t)n * 32}, {out, out, (size_t)n * 32}, {votes, votes, (size_t)n * 16}, {status, status, (size_t)n * 4}},
+                           [&](const Pieces& s) {
+        leon_pipeline_carry_regions_call c{};
+        c.regions = s.at<const leon_pipeline_carry_region>(0);
+        c.n = n;
+        c.device_out = s.at<leon_pipeline_region>(1);
+        c.device_votes = votes ? s.at<int32_t>(2) : nullptr;
+        c.device_status = status ? s.at<int32_t>(3) : nullptr;
+        return carry_regions_device(p, window, &c);
+    });
 }
 
 // the definition on the CPU: the same text (leon_carry.h) over a record in host memory; the status word, or a negative error
@@ -2511,23 +2579,15 @@ int carry_device(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32_t
     for (int32_t i = 0; i < n; i++)          // a record that votes must be there: the judgement alone, nothing summed
         if (carry_record_host(fw, fh, mbw, mbh, n_frames, fwd, bwd, records, regions + i, nullptr, nullptr, true) < 0) return LEON_ERR_INVALID;
     const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
-    // [table | ring]: a frame without a record gets no slot, its ring id stays 0 and nothing of the call reads it
-    std::vector<leon::CarryFrame> table((size_t)n_frames);
-    uint32_t slots = 0;
-    for (int32_t i = 0; i < n_frames; i++) table[(size_t)i] = leon::CarryFrame{records[i] ? slots++ : 0u, fwd[i], bwd[i], 0u};
-    const size_t table_bytes = pad256(table.size() * sizeof(leon::CarryFrame));
-    HIP_TRY(hipSetDevice(device_id));
-    CarryHostBufs b;
-    char* extra = nullptr;
-    if ((rc = carry_host_up(&b, table_bytes + (size_t)std::max<uint32_t>(slots, 1) * L.record_pitch, regions, n, out, votes, status, &extra)) != LEON_OK) return rc;
-    uint8_t* d_ring = reinterpret_cast<uint8_t*>(extra + table_bytes);
-    if (!table.empty()) HIP_TRY(hipMemcpy(extra, table.data(), table.size() * sizeof(leon::CarryFrame), hipMemcpyHostToDevice));
-    for (int32_t i = 0; i < n_frames; i++)
-        if (records[i]) HIP_TRY(hipMemcpy(d_ring + (size_t)table[(size_t)i].ring * L.record_pitch, records[i], L.record_bytes, hipMemcpyHostToDevice));
-    carry_launch(nullptr, reinterpret_cast<const leon::CarryRecord*>(b.recs), reinterpret_cast<const leon::CarryFrame*>(extra), d_ring, fw, fh, mbw, L, n_frames, n, b.out,
-                 votes ? b.votes : nullptr, status ? b.status : nullptr);
-    HIP_TRY(hipGetLastError());
-    return carry_host_down(b, n, out, votes, status);      // (the copies wait: nothing in flight reads the buffer when it goes)
+    uint32_t slots;
+    const std::vector<leon::CarryFrame> table = kernel_table(n_frames, fwd, bwd, [&](size_t i) { return records[i] != nullptr; }, &slots);
+    const std::vector<uint8_t> ring = kernel_ring(table, slots, records, L.record_bytes, L.record_pitch);
+    return pieces_run(device_id, "carry", {{regions, nullptr, (size_t)n * 32}, {out, out, (size_t)n * 32}, {votes, votes, (size_t)n * 16}, {status, status, (size_t)n * 4},
+                                           {table.data(), nullptr, table.size() * sizeof(leon::CarryFrame)}, {ring.data(), nullptr, ring.size()}}, [&](const Pieces& s) {
+        carry_launch(nullptr, s.at<const leon::CarryRecord>(0), s.at<const leon::CarryFrame>(4), s.at(5), fw, fh, mbw, L, n_frames, n, s.at<int32_t>(1),
+                     votes ? s.at<int32_t>(2) : nullptr, status ? s.at<int32_t>(3) : nullptr);
+        return (int)LEON_OK;
+    });
 }
 
 // ---- boxes gauged: a frame's motion and activity records under each box (leon_pipeline_gauge_regions) ------------------------------
@@ -2559,78 +2619,52 @@ void gauge_launch(hipStream_t st, const leon::GaugeRecord* d_recs, const leon::C
     hipLaunchKernelGGL(leon::k_gauge, dim3(((unsigned)n + per - 1) / per), dim3(leon::kRgbaBlock), 0, st, d_recs, d_frames, d_motion, d_activity, d_stats, d_status, C);
 }
 
-// One call of the device road: the host's refusals, then inside the boxes bracket (the window's table is all of the scratch it needs)
-// one launch on the caller's stream (or the regions stream and a wait)
+// the record outputs a call's sources ask for are the pipeline's
+int gauge_outputs_check(const leon_pipeline* p, int32_t sources)
+{
+    if ((sources & LEON_GAUGE_MOTION) && !p->motion.ring) return no_output("motion", "MOTION");
+    if ((sources & LEON_GAUGE_ACTIVITY) && !p->activity.ring) return no_output("activity", "ACTIVITY");
+    return LEON_OK;
+}
+
+// One call of the device road: the host's refusals (the config's before the window's), then one launch
 int gauge_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_gauge_config* cfg, const leon_pipeline_gauge_regions_call* c)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
     int rc = gauge_config_check(cfg);
-    if (rc != LEON_OK) return rc;
-    if ((cfg->sources & LEON_GAUGE_MOTION) && !p->motion.ring) return no_output("motion", "MOTION");
-    if ((cfg->sources & LEON_GAUGE_ACTIVITY) && !p->activity.ring) return no_output("activity", "ACTIVITY");
+    if (rc != LEON_OK || (rc = gauge_outputs_check(p, cfg->sources)) != LEON_OK) return rc;
     if (!c) return fail(LEON_ERR_INVALID, "null argument");
-    std::unique_lock<std::mutex> call(p->regions_mu);
-    std::vector<uint32_t> table;
-    if ((rc = carry_window_table(p, window, &table)) != LEON_OK) return rc;
-    const int32_t n = c->n;
-    if (c->reserved0 || c->reserved[0] || c->reserved[1] || c->reserved[2]) return fail(LEON_ERR_INVALID, "gauge regions: a reserved word of the call is not 0");
-    if ((rc = record_count_check("gauge regions", "regions", n)) != LEON_OK) return rc;
-    if (!c->regions) return fail(LEON_ERR_INVALID, "gauge regions: null regions");
-    if (!c->device_stats) return fail(LEON_ERR_INVALID, "gauge regions: null device_stats");
-    if (((uintptr_t)c->regions | (uintptr_t)c->device_status) & 3u)
-        return fail(LEON_ERR_INVALID, "gauge regions: regions %p, device_status %p: not both 4-byte aligned", (const void*)c->regions, (void*)c->device_status);
-    if ((uintptr_t)c->device_stats & 7u) return fail(LEON_ERR_INVALID, "gauge regions: device_stats %p is not 8-byte aligned", (void*)c->device_stats);
-    const int32_t sources = cfg->sources;
-    return boxes_run(p, c->stream, call, table, pad256(std::max<size_t>(table.size(), 1) * 4), [&](hipStream_t st, uint32_t* d_table) {
-        gauge_launch(st, reinterpret_cast<const leon::GaugeRecord*>(c->regions), reinterpret_cast<const leon::CarryFrame*>(d_table), p->motion.ring, p->activity.ring,
-                     p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width, p->motion_lay, p->activity_lay, (int32_t)(table.size() / 4), sources, n, c->device_stats,
-                     c->device_status);
+    return table_road(p, window, c->stream, "gauge regions", "regions", c->n, c->reserved0 || c->reserved[0] || c->reserved[1] || c->reserved[2], [&] {
+        if (!c->regions) return fail(LEON_ERR_INVALID, "gauge regions: null regions");
+        if (!c->device_stats) return fail(LEON_ERR_INVALID, "gauge regions: null device_stats");
+        if (((uintptr_t)c->regions | (uintptr_t)c->device_status) & 3u)
+            return fail(LEON_ERR_INVALID, "gauge regions: regions %p, device_status %p: not both 4-byte aligned", (const void*)c->regions, (void*)c->device_status);
+        if ((uintptr_t)c->device_stats & 7u) return fail(LEON_ERR_INVALID, "gauge regions: device_stats %p is not 8-byte aligned", (void*)c->device_stats);
+        return (int)LEON_OK;
+    }, [&](hipStream_t st, const leon::CarryFrame* d_frames, int32_t n_frames) {
+        gauge_launch(st, reinterpret_cast<const leon::GaugeRecord*>(c->regions), d_frames, p->motion.ring, p->activity.ring, p->vinfo.frame_width, p->vinfo.frame_height,
+                     p->vinfo.mb_width, p->motion_lay, p->activity_lay, n_frames, cfg->sources, c->n, c->device_stats, c->device_status);
     });
 }
 
-// records, results: one device allocation [stats | records | status]; what the caller has in stats and status goes up first, so that
-// the words the kernel leaves alone come back as they were
-struct GaugeHostBufs {
-    DevBuf<int64_t> d;
-    int64_t* stats = nullptr;
-    int32_t *recs = nullptr, *status = nullptr;
-};
-int gauge_host_up(GaugeHostBufs* b, size_t extra_bytes, const leon_pipeline_region* regions, int32_t n, const int64_t* stats, const int32_t* status, char** extra)
-{
-    const size_t bytes = pad256((size_t)n * (8 * leon::kGaugeWords + 32 + 4));
-    if (!b->d.alloc(bytes + extra_bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "gauge: %zu bytes of device memory", bytes + extra_bytes); }
-    b->stats = b->d; b->recs = reinterpret_cast<int32_t*>(b->stats + (size_t)n * leon::kGaugeWords); b->status = b->recs + (size_t)n * 8;
-    if (extra) *extra = reinterpret_cast<char*>(b->d.get()) + bytes;
-    HIP_TRY(hipMemcpy(b->recs, regions, (size_t)n * 32, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->stats, stats, (size_t)n * 8 * leon::kGaugeWords, hipMemcpyHostToDevice));
-    if (status) HIP_TRY(hipMemcpy(b->status, status, (size_t)n * 4, hipMemcpyHostToDevice));
-    return LEON_OK;
-}
-int gauge_host_down(const GaugeHostBufs& b, int32_t n, int64_t* stats, int32_t* status)
-{
-    HIP_TRY(hipMemcpy(stats, b.stats, (size_t)n * 8 * leon::kGaugeWords, hipMemcpyDeviceToHost));
-    if (status) HIP_TRY(hipMemcpy(status, b.status, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return LEON_OK;
-}
-
-// One call of the host road: the device road on the regions stream between an upload and two copies
+// One call of the host road: [stats | records | status], what the caller has in stats and status going up first.  The outputs are
+// judged here as well, behind the count and in front of the window: the order in which a caller of this road meets the refusals.
 int gauge_regions(leon_pipeline* p, int64_t window, const leon_pipeline_gauge_config* cfg, const leon_pipeline_region* regions, int32_t n, int64_t* stats, int32_t* status)
 {
     if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
     int rc = gauge_config_check(cfg);
     if (rc != LEON_OK) return rc;
     if (!regions || !stats) return fail(LEON_ERR_INVALID, "gauge regions: null %s", regions ? "stats" : "regions");
-    if ((rc = record_count_check("gauge regions", "regions", n)) != LEON_OK) return rc;
-    HIP_TRY(hipSetDevice(p->cfg.device_id));
-    GaugeHostBufs b;
-    if ((rc = gauge_host_up(&b, 0, regions, n, stats, status, nullptr)) != LEON_OK) return rc;
-    leon_pipeline_gauge_regions_call c{};
-    c.regions = reinterpret_cast<const leon_pipeline_region*>(b.recs);
-    c.n = n;
-    c.device_stats = b.stats;
-    c.device_status = status ? b.status : nullptr;
-    if ((rc = gauge_regions_device(p, window, cfg, &c)) != LEON_OK) return rc;      // (stream NULL: it has waited)
-    return gauge_host_down(b, n, stats, status);
+    if ((rc = record_count_check("gauge regions", "regions", n)) != LEON_OK || (rc = gauge_outputs_check(p, cfg->sources)) != LEON_OK) return rc;
+    return table_host_road(p, window, "gauge", {{stats, stats, (size_t)n * 8 * leon::kGaugeWords}, {regions, nullptr, (size_t)n * 32}, {status, status, (size_t)n * 4}},
+                           [&](const Pieces& s) {
+        leon_pipeline_gauge_regions_call c{};
+        c.regions = s.at<const leon_pipeline_region>(1);
+        c.n = n;
+        c.device_stats = s.at<int64_t>(0);
+        c.device_status = status ? s.at<int32_t>(2) : nullptr;
+        return gauge_regions_device(p, window, cfg, &c);
+    });
 }
 
 // the definition on the CPU: the same text (leon_gauge.h) over records in host memory; the status word, or a negative error
@@ -2685,28 +2719,19 @@ int gauge_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32_t
     const bool mot = (cfg->sources & LEON_GAUGE_MOTION) != 0, act = (cfg->sources & LEON_GAUGE_ACTIVITY) != 0;
     const leon::MotionLayout ML = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
     const leon::ActivityLayout AL = leon::activity_layout((uint32_t)mbw, (uint32_t)mbh);
-    // [table | motion ring | activity ring]: a frame with a record of either kind gets a slot in both rings, as the pipeline's rings
-    // share an index; a frame without gets none, its ring id stays 0 and nothing of the call reads it
-    std::vector<leon::CarryFrame> table((size_t)n_frames);
-    uint32_t slots = 0;
-    for (int32_t i = 0; i < n_frames; i++) table[(size_t)i] = leon::CarryFrame{(mot && motion_records[i]) || (act && activity_records[i]) ? slots++ : 0u, -1, -1, 0u};
-    const size_t table_bytes = pad256(std::max<size_t>(table.size(), 1) * sizeof(leon::CarryFrame));
-    const size_t motion_bytes = mot ? (size_t)std::max<uint32_t>(slots, 1) * ML.record_pitch : 0, activity_bytes = act ? (size_t)std::max<uint32_t>(slots, 1) * AL.record_pitch : 0;
-    HIP_TRY(hipSetDevice(device_id));
-    GaugeHostBufs b;
-    char* extra = nullptr;
-    if ((rc = gauge_host_up(&b, table_bytes + motion_bytes + activity_bytes, regions, n, stats, status, &extra)) != LEON_OK) return rc;
-    uint8_t* d_motion = reinterpret_cast<uint8_t*>(extra + table_bytes);
-    uint8_t* d_activity = d_motion + motion_bytes;
-    if (!table.empty()) HIP_TRY(hipMemcpy(extra, table.data(), table.size() * sizeof(leon::CarryFrame), hipMemcpyHostToDevice));
-    for (int32_t i = 0; i < n_frames; i++) {
-        if (mot && motion_records[i]) HIP_TRY(hipMemcpy(d_motion + (size_t)table[(size_t)i].ring * ML.record_pitch, motion_records[i], ML.record_bytes, hipMemcpyHostToDevice));
-        if (act && activity_records[i]) HIP_TRY(hipMemcpy(d_activity + (size_t)table[(size_t)i].ring * AL.record_pitch, activity_records[i], AL.record_bytes, hipMemcpyHostToDevice));
-    }
-    gauge_launch(nullptr, reinterpret_cast<const leon::GaugeRecord*>(b.recs), reinterpret_cast<const leon::CarryFrame*>(extra), mot ? d_motion : nullptr,
-                 act ? d_activity : nullptr, fw, fh, mbw, ML, AL, n_frames, cfg->sources, n, b.stats, status ? b.status : nullptr);
-    HIP_TRY(hipGetLastError());
-    return gauge_host_down(b, n, stats, status);      // (the copies wait: nothing in flight reads the buffer when it goes)
+    // a frame with a record of either kind gets a slot in both rings, as the pipeline's rings share an index
+    uint32_t slots;
+    const std::vector<leon::CarryFrame> table =
+        kernel_table(n_frames, nullptr, nullptr, [&](size_t i) { return (mot && motion_records[i]) || (act && activity_records[i]); }, &slots);
+    const std::vector<uint8_t> motion = kernel_ring(table, slots, mot ? motion_records : nullptr, ML.record_bytes, ML.record_pitch);
+    const std::vector<uint8_t> activity = kernel_ring(table, slots, act ? activity_records : nullptr, AL.record_bytes, AL.record_pitch);
+    return pieces_run(device_id, "gauge", {{stats, stats, (size_t)n * 8 * leon::kGaugeWords}, {regions, nullptr, (size_t)n * 32}, {status, status, (size_t)n * 4},
+                                           {table.data(), nullptr, table.size() * sizeof(leon::CarryFrame)}, {motion.data(), nullptr, motion.size()},
+                                           {activity.data(), nullptr, activity.size()}}, [&](const Pieces& s) {
+        gauge_launch(nullptr, s.at<const leon::GaugeRecord>(1), s.at<const leon::CarryFrame>(3), mot ? s.at(4) : nullptr, act ? s.at(5) : nullptr, fw, fh, mbw, ML, AL, n_frames,
+                     cfg->sources, n, s.at<int64_t>(0), status ? s.at<int32_t>(2) : nullptr);
+        return (int)LEON_OK;
+    });
 }
 
 // ---- dense maps propagated along the motion vectors (leon_pipeline_propagate_maps) ------------------------------------------------
@@ -2747,63 +2772,26 @@ void propagate_launch(hipStream_t st, const leon::PropagateHop* d_hops, const le
     hipLaunchKernelGGL(leon::k_propagate, grid, dim3(leon::kRgbaBlock), 0, st, d_hops, d_frames, d_ring, d_maps, d_via, d_status, C);
 }
 
-// One call of the device road: the host's refusals, then inside the boxes bracket (the window's table is all of the scratch it needs)
-// one launch on the caller's stream (or the regions stream and a wait)
+// One call of the device road: the host's refusals (the config's behind the alignment's), then one launch
 int propagate_maps_device(leon_pipeline* p, int64_t window, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_maps_call* c)
 {
-    int rc = carry_pipeline_check(p);
-    if (rc != LEON_OK) return rc;
+    if (const int rc = carry_pipeline_check(p); rc != LEON_OK) return rc;
     if (!c) return fail(LEON_ERR_INVALID, "null argument");
-    std::unique_lock<std::mutex> call(p->regions_mu);
-    std::vector<uint32_t> table;
-    if ((rc = carry_window_table(p, window, &table)) != LEON_OK) return rc;
-    const int32_t n = c->n;
-    if (c->reserved0 || c->reserved[0] || c->reserved[1]) return fail(LEON_ERR_INVALID, "propagate maps: a reserved word of the call is not 0");
-    if ((rc = record_count_check("propagate maps", "hops", n)) != LEON_OK) return rc;
-    if (!c->hops) return fail(LEON_ERR_INVALID, "propagate maps: null hops");
-    if (!c->maps) return fail(LEON_ERR_INVALID, "propagate maps: null maps");
-    if (((uintptr_t)c->hops | (uintptr_t)c->maps | (uintptr_t)c->device_via | (uintptr_t)c->device_status) & 3u)
-        return fail(LEON_ERR_INVALID, "propagate maps: hops %p, maps %p, device_via %p, device_status %p: not all 4-byte aligned", (const void*)c->hops, c->maps,
-                    (void*)c->device_via, (void*)c->device_status);
     leon::PropagateGeom g;
-    if ((rc = propagate_config_check(p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width, cfg, &g)) != LEON_OK) return rc;
-    return boxes_run(p, c->stream, call, table, pad256(std::max<size_t>(table.size(), 1) * 4), [&](hipStream_t st, uint32_t* d_table) {
-        propagate_launch(st, reinterpret_cast<const leon::PropagateHop*>(c->hops), reinterpret_cast<const leon::CarryFrame*>(d_table), p->motion.ring, g, p->motion_lay,
-                         (int32_t)(table.size() / 4), *cfg, n, static_cast<uint8_t*>(c->maps), c->device_via, c->device_status);
+    return table_road(p, window, c->stream, "propagate maps", "hops", c->n, c->reserved0 || c->reserved[0] || c->reserved[1], [&] {
+        if (!c->hops) return fail(LEON_ERR_INVALID, "propagate maps: null hops");
+        if (!c->maps) return fail(LEON_ERR_INVALID, "propagate maps: null maps");
+        if (((uintptr_t)c->hops | (uintptr_t)c->maps | (uintptr_t)c->device_via | (uintptr_t)c->device_status) & 3u)
+            return fail(LEON_ERR_INVALID, "propagate maps: hops %p, maps %p, device_via %p, device_status %p: not all 4-byte aligned", (const void*)c->hops, c->maps,
+                        (void*)c->device_via, (void*)c->device_status);
+        return propagate_config_check(p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width, cfg, &g);
+    }, [&](hipStream_t st, const leon::CarryFrame* d_frames, int32_t n_frames) {
+        propagate_launch(st, reinterpret_cast<const leon::PropagateHop*>(c->hops), d_frames, p->motion.ring, g, p->motion_lay, n_frames, *cfg, c->n,
+                         static_cast<uint8_t*>(c->maps), c->device_via, c->device_status);
     });
 }
 
-// hops, results and maps of a host road: one device allocation [hops | status | via | maps | extra]; what the caller has in maps, via
-// and status goes up first, so that the bytes the kernel leaves alone come back as they were
-struct PropagateHostBufs {
-    DevBuf<uint8_t> d;
-    uint8_t *hops = nullptr, *status = nullptr, *via = nullptr, *maps = nullptr;
-    size_t via_bytes = 0;
-};
-int propagate_host_up(PropagateHostBufs* b, size_t extra_bytes, const leon::PropagateGeom& g, const leon_pipeline_propagate_config& cfg, const leon_pipeline_propagate_hop* hops,
-                      int32_t n, const void* maps, const uint8_t* via, const int32_t* status, uint8_t** extra)
-{
-    b->via_bytes = (size_t)n * (size_t)g.mh * (size_t)g.mw;
-    const size_t hops_bytes = pad256((size_t)n * 32), status_bytes = pad256((size_t)n * 4), via_bytes = pad256(b->via_bytes), maps_bytes = pad256((size_t)cfg.maps_bytes);
-    const size_t bytes = hops_bytes + status_bytes + via_bytes + maps_bytes + extra_bytes;
-    if (!b->d.alloc(bytes)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "propagate: %zu bytes of device memory", bytes); }
-    b->hops = b->d; b->status = b->hops + hops_bytes; b->via = b->status + status_bytes; b->maps = b->via + via_bytes;
-    if (extra) *extra = b->maps + maps_bytes;
-    HIP_TRY(hipMemcpy(b->hops, hops, (size_t)n * 32, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->maps, maps, (size_t)cfg.maps_bytes, hipMemcpyHostToDevice));
-    if (via) HIP_TRY(hipMemcpy(b->via, via, b->via_bytes, hipMemcpyHostToDevice));
-    if (status) HIP_TRY(hipMemcpy(b->status, status, (size_t)n * 4, hipMemcpyHostToDevice));
-    return LEON_OK;
-}
-int propagate_host_down(const PropagateHostBufs& b, const leon_pipeline_propagate_config& cfg, int32_t n, void* maps, uint8_t* via, int32_t* status)
-{
-    HIP_TRY(hipMemcpy(maps, b.maps, (size_t)cfg.maps_bytes, hipMemcpyDeviceToHost));
-    if (via) HIP_TRY(hipMemcpy(via, b.via, b.via_bytes, hipMemcpyDeviceToHost));
-    if (status) HIP_TRY(hipMemcpy(status, b.status, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return LEON_OK;
-}
-
-// One call of the host road: the device road on the regions stream between an upload and the copies back
+// One call of the host road: [hops | status | via | maps], the maps and what the caller has in via and status going up first
 int propagate_maps(leon_pipeline* p, int64_t window, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hops, int32_t n, void* maps, uint8_t* via,
                    int32_t* status)
 {
@@ -2813,22 +2801,17 @@ int propagate_maps(leon_pipeline* p, int64_t window, const leon_pipeline_propaga
     if ((rc = record_count_check("propagate maps", "hops", n)) != LEON_OK) return rc;
     leon::PropagateGeom g;
     if ((rc = propagate_config_check(p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width, cfg, &g)) != LEON_OK) return rc;
-    {          // the window's refusals before anything is allocated or uploaded (the device road judges it again under the same lock)
-        std::unique_lock<std::mutex> call(p->regions_mu);
-        std::vector<uint32_t> table;
-        if ((rc = carry_window_table(p, window, &table)) != LEON_OK) return rc;
-    }
-    HIP_TRY(hipSetDevice(p->cfg.device_id));
-    PropagateHostBufs b;
-    if ((rc = propagate_host_up(&b, 0, g, *cfg, hops, n, maps, via, status, nullptr)) != LEON_OK) return rc;
-    leon_pipeline_propagate_maps_call c{};
-    c.hops = reinterpret_cast<const leon_pipeline_propagate_hop*>(b.hops);
-    c.n = n;
-    c.maps = b.maps;
-    c.device_via = via ? b.via : nullptr;
-    c.device_status = status ? reinterpret_cast<int32_t*>(b.status) : nullptr;
-    if ((rc = propagate_maps_device(p, window, cfg, &c)) != LEON_OK) return rc;      // (stream NULL: it has waited)
-    return propagate_host_down(b, *cfg, n, maps, via, status);
+    const size_t via_bytes = (size_t)n * (size_t)g.mh * (size_t)g.mw;
+    return table_host_road(p, window, "propagate", {{hops, nullptr, (size_t)n * 32}, {status, status, (size_t)n * 4}, {via, via, via_bytes}, {maps, maps, (size_t)cfg->maps_bytes}},
+                           [&](const Pieces& s) {
+        leon_pipeline_propagate_maps_call c{};
+        c.hops = s.at<const leon_pipeline_propagate_hop>(0);
+        c.n = n;
+        c.maps = s.at(3);
+        c.device_via = via ? s.at(2) : nullptr;
+        c.device_status = status ? s.at<int32_t>(1) : nullptr;
+        return propagate_maps_device(p, window, cfg, &c);
+    });
 }
 
 // what the CPU road and the diagnostic refuse of their geometry
@@ -2875,23 +2858,16 @@ int propagate_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int
             return fail(LEON_ERR_INVALID, "propagate: frame %d is the target of hop %d and has no record", h.target, i);
     }
     const leon::MotionLayout L = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
-    // [table | ring]: a frame without a record gets no slot, its ring id stays 0 and nothing of the call reads it
-    std::vector<leon::CarryFrame> table((size_t)n_frames);
-    uint32_t slots = 0;
-    for (int32_t i = 0; i < n_frames; i++) table[(size_t)i] = leon::CarryFrame{records[i] ? slots++ : 0u, -1, -1, 0u};
-    const size_t table_bytes = pad256(std::max<size_t>(table.size(), 1) * sizeof(leon::CarryFrame));
-    HIP_TRY(hipSetDevice(device_id));
-    PropagateHostBufs b;
-    uint8_t* extra = nullptr;
-    if ((rc = propagate_host_up(&b, table_bytes + (size_t)std::max<uint32_t>(slots, 1) * L.record_pitch, g, *cfg, hops, n, maps, via, status, &extra)) != LEON_OK) return rc;
-    uint8_t* d_ring = extra + table_bytes;
-    if (!table.empty()) HIP_TRY(hipMemcpy(extra, table.data(), table.size() * sizeof(leon::CarryFrame), hipMemcpyHostToDevice));
-    for (int32_t i = 0; i < n_frames; i++)
-        if (records[i]) HIP_TRY(hipMemcpy(d_ring + (size_t)table[(size_t)i].ring * L.record_pitch, records[i], L.record_bytes, hipMemcpyHostToDevice));
-    propagate_launch(nullptr, reinterpret_cast<const leon::PropagateHop*>(b.hops), reinterpret_cast<const leon::CarryFrame*>(extra), d_ring, g, L, n_frames, *cfg, n, b.maps,
-                     via ? b.via : nullptr, status ? reinterpret_cast<int32_t*>(b.status) : nullptr);
-    HIP_TRY(hipGetLastError());
-    return propagate_host_down(b, *cfg, n, maps, via, status);      // (the copies wait: nothing in flight reads the buffer when it goes)
+    uint32_t slots;
+    const std::vector<leon::CarryFrame> table = kernel_table(n_frames, nullptr, nullptr, [&](size_t i) { return records[i] != nullptr; }, &slots);
+    const std::vector<uint8_t> ring = kernel_ring(table, slots, records, L.record_bytes, L.record_pitch);
+    const size_t via_bytes = (size_t)n * (size_t)g.mh * (size_t)g.mw;
+    return pieces_run(device_id, "propagate", {{hops, nullptr, (size_t)n * 32}, {status, status, (size_t)n * 4}, {via, via, via_bytes}, {maps, maps, (size_t)cfg->maps_bytes},
+                                               {table.data(), nullptr, table.size() * sizeof(leon::CarryFrame)}, {ring.data(), nullptr, ring.size()}}, [&](const Pieces& s) {
+        propagate_launch(nullptr, s.at<const leon::PropagateHop>(0), s.at<const leon::CarryFrame>(4), s.at(5), g, L, n_frames, *cfg, n, s.at(3), via ? s.at(2) : nullptr,
+                         status ? s.at<int32_t>(1) : nullptr);
+        return (int)LEON_OK;
+    });
 }
 
 // The device's rows of a batch of single axes, copied back (leon_pipeline_resize_weights_device): memory of its own, the null stream
@@ -2909,27 +2885,15 @@ int resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes
         max_out = std::max(max_out, axes[4 * a + 3]);
     }
     static_assert(sizeof(leon::AxisRecord) == 16, "four words an axis");
-    const size_t rows = (size_t)n_axes * (size_t)max_out, words = (size_t)n_axes * 4 + 2 * rows + rows * (size_t)max_taps + (size_t)n_axes;
-    HIP_TRY(hipSetDevice(device_id));
-    DevBuf<int32_t> d;
-    if (!d.alloc(words * 4)) { (void)hipGetLastError(); return fail(LEON_ERR_NOMEM, "resize: %zu bytes of device memory", words * 4); }
-    int32_t *d_first = d + (size_t)n_axes * 4, *d_count = d_first + rows, *d_weights = d_count + rows, *d_status = d_weights + rows * (size_t)max_taps;
-    // the caller's arrays go up and come back whole: what the kernel does not write stays as the caller had it
-    hipError_t he = hipMemcpy(d, axes, (size_t)n_axes * 16, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d_first, first, rows * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d_count, count, rows * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d_weights, weights, rows * (size_t)max_taps * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(leon::k_axis_tables, dim3((unsigned)n_axes), dim3(leon::kRgbaBlock), 0, nullptr, reinterpret_cast<const leon::AxisRecord*>(d.get()), d_first, d_count,
-                           d_weights, d_status, filter == LEON_RESIZE_BICUBIC ? 1 : 0, max_taps, max_out);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpy(first, d_first, rows * 4, hipMemcpyDeviceToHost);
-    if (he == hipSuccess) he = hipMemcpy(count, d_count, rows * 4, hipMemcpyDeviceToHost);
-    if (he == hipSuccess) he = hipMemcpy(weights, d_weights, rows * (size_t)max_taps * 4, hipMemcpyDeviceToHost);
-    if (he == hipSuccess) he = hipMemcpy(status, d_status, (size_t)n_axes * 4, hipMemcpyDeviceToHost);
-    HIP_TRY(he);      // (the copies above waited: nothing in flight reads d when it goes)
-    return LEON_OK;
+    const size_t rows = (size_t)n_axes * (size_t)max_out;
+    // [axes | first | count | weights | status]: the caller's rows go up and come back whole, so what the kernel does not write stays as
+    // the caller had it
+    return pieces_run(device_id, "resize", {{axes, nullptr, (size_t)n_axes * 16}, {first, first, rows * 4}, {count, count, rows * 4},
+                                            {weights, weights, rows * (size_t)max_taps * 4}, {nullptr, status, (size_t)n_axes * 4}}, [&](const Pieces& s) {
+        hipLaunchKernelGGL(leon::k_axis_tables, dim3((unsigned)n_axes), dim3(leon::kRgbaBlock), 0, nullptr, s.at<const leon::AxisRecord>(0), s.at<int32_t>(1), s.at<int32_t>(2),
+                           s.at<int32_t>(3), s.at<int32_t>(4), filter == LEON_RESIZE_BICUBIC ? 1 : 0, max_taps, max_out);
+        return (int)LEON_OK;
+    });
 }
 
 // one window: its levels planned, its arenas uploaded (and parsed on the GPU), its levels launched, its frames listed

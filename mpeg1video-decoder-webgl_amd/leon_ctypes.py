@@ -995,6 +995,18 @@ def _records_array(rows, words=8):
     return full
 
 
+def _result_arrays(n, *specs):
+    """the host arrays a call writes its n results into, one per (row shape, fill, dtype): pre-filled, of one row at the least (an address); sliced to n by the caller"""
+    return [np.full((max(1, n),) + tuple(row), fill, dtype=dtype) for row, fill, dtype in specs]
+
+
+def _device_records_check(name, t, stacked=False):
+    """records (or hops) of a device road: a contiguous CUDA int32 torch tensor [N, 8] -- stacked: or [F, N, 8]"""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() in (2, 2 + stacked) and t.shape[-1] == 8 and t.is_contiguous()):
+        raise ValueError("%s: a contiguous CUDA int32 tensor [N, 8]%s" % (name, " or [F, N, 8]" if stacked else ""))
+
+
 def carry_record(frame_width, frame_height, mbw, mbh, n_frames, fwd, bwd, records, rec, fill=0):
     """leon_pipeline_carry_record: the library's CPU evaluation of one hop; arguments as carry_box's.  Returns (status, out [8], votes [4])
     as int32 arrays that hold `fill` where the library wrote nothing; LeonError where it refuses the call."""
@@ -1016,8 +1028,7 @@ def carry_device(frame_width, frame_height, mbw, mbh, n_frames, fwd, bwd, record
     ptrs, keep = _carry_records(records, mbw, mbh)
     f, b = np.ascontiguousarray(fwd, dtype=np.int32), np.ascontiguousarray(bwd, dtype=np.int32)
     r = _records_array(regions)
-    m = max(1, len(r))
-    out, votes, status = np.full((m, 8), fill, dtype=np.int32), np.full((m, 4), fill, dtype=np.int32), np.full(m, fill, dtype=np.int32)
+    out, votes, status = _result_arrays(len(r), ((8,), fill, np.int32), ((4,), fill, np.int32), ((), fill, np.int32))
     _chk(load().leon_pipeline_carry_device(int(device_id), int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), f.ctypes.data, b.ctypes.data, ptrs,
                                            r.ctypes.data if len(r) else None, len(r) if n is None else int(n), out.ctypes.data, votes.ctypes.data, status.ctypes.data))
     return out[:len(r)], votes[:len(r)], status[:len(r)]
@@ -1106,8 +1117,7 @@ def gauge_kernel(frame_width, frame_height, mbw, mbh, n_frames, motion, activity
     to the library when it is to differ from m = len(regions) (smaller: what lies behind keeps the fill)."""
     mp, ap, keep = _gauge_records(motion, activity, mbw, mbh, n_frames)
     r = _records_array(regions)
-    m = max(1, len(r))
-    stats, status = np.full((m, GAUGE_WORDS), fill, dtype=np.int64), np.full(m, fill, dtype=np.int32)
+    stats, status = _result_arrays(len(r), ((GAUGE_WORDS,), fill, np.int64), ((), fill, np.int32))
     cfg = PipelineGaugeConfig(int(sources)) if cfg is None else cfg
     _chk(load().leon_pipeline_gauge_kernel(int(device_id), int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), mp, ap, C.byref(cfg),
                                            r.ctypes.data if len(r) else None, len(r) if n is None else int(n), stats.ctypes.data, status.ctypes.data))
@@ -1237,9 +1247,7 @@ def propagate_kernel(frame_width, frame_height, mbw, mbh, n_frames, records, hop
     from m = len(hops)."""
     ptrs, keep = _carry_records(records, mbw, mbh)
     h = _records_array(hops)
-    m = max(1, len(h))
-    v = np.full((m,) + maps.shape[2:], via_fill, dtype=np.uint8) if via else None
-    status = np.full(m, status_fill, dtype=np.int32)
+    v, status = _result_arrays(len(h), (maps.shape[2:], via_fill, np.uint8), ((), status_fill, np.int32))
     cfg = _propagate_config(maps, stride, fill, over)
     _chk(load().leon_pipeline_propagate_kernel(int(device_id), int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), ptrs, C.byref(cfg),
                                                h.ctypes.data if len(h) else None, len(h) if n is None else int(n), maps.ctypes.data, v.ctypes.data if via else None,
@@ -2042,8 +2050,7 @@ class Pipeline:
         (target, x', y', w, h, 0, 0, 0) for resample_regions, votes[i] = (A, I, dh, dv).  A record's fault is its status word
         (REGION_*, REGION_NO_REFERENCE: no prediction joins the two frames), never a LeonError; its out and votes keep `fill`.  Synchronous."""
         r = _records_array(records)
-        m = max(1, len(r))
-        out, votes, status = np.full((m, 8), fill, dtype=np.int32), np.full((m, 4), fill, dtype=np.int32), np.full(m, fill, dtype=np.int32)
+        out, votes, status = _result_arrays(len(r), ((8,), fill, np.int32), ((4,), fill, np.int32), ((), fill, np.int32))
         _chk(self.lib.leon_pipeline_carry_regions(self.h, int(window), r.ctypes.data if len(r) else None, len(r), out.ctypes.data, votes.ctypes.data, status.ctypes.data))
         return out[:len(r)], votes[:len(r)], status[:len(r)]
 
@@ -2056,9 +2063,7 @@ class Pipeline:
         import torch
         _need_output(self.motion_layout, "motion")
         dev = self.device_id
-        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.dtype == torch.int32 and records.dim() == 2 and records.shape[1] == 8
-                and records.is_contiguous()):
-            raise ValueError("records: a contiguous CUDA int32 tensor [N, 8]")
+        _device_records_check("records", records)
         n = int(records.shape[0])
         for name, t, words in (("records", records, 8 * n), ("out", out, 8 * n), ("votes", votes, 4 * n), ("status", status, n)):
             _device_tensor_check(name, t, torch.int32, words, dev, words=True)
@@ -2122,8 +2127,7 @@ class Pipeline:
         8 .. 15), its activity record (GAUGE_ACTIVITY, words 1 .. 7) or both (gauge_box states them); sources=None: every record output
         the pipeline has.  A record's fault is its status word (REGION_*), never a LeonError; its statistics keep `fill`.  Synchronous."""
         r = _records_array(regions)
-        m = max(1, len(r))
-        stats, status = np.full((m, GAUGE_WORDS), fill, dtype=np.int64), np.full(m, fill, dtype=np.int32)
+        stats, status = _result_arrays(len(r), ((GAUGE_WORDS,), fill, np.int64), ((), fill, np.int32))
         cfg = PipelineGaugeConfig(self._gauge_sources(sources))
         _chk(self.lib.leon_pipeline_gauge_regions(self.h, int(window), C.byref(cfg), r.ctypes.data if len(r) else None, len(r), stats.ctypes.data, status.ctypes.data))
         return stats[:len(r)], status[:len(r)]
@@ -2136,9 +2140,7 @@ class Pipeline:
         written exactly where status[i] is 0."""
         import torch
         dev = self.device_id
-        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.dtype == torch.int32 and records.dim() in (2, 3) and records.shape[-1] == 8
-                and records.is_contiguous()):
-            raise ValueError("records: a contiguous CUDA int32 tensor [N, 8] or [F, N, 8]")
+        _device_records_check("records", records, stacked=True)
         records = records.view(-1, 8)
         n = int(records.shape[0])
         _device_tensor_check("records", records, torch.int32, 8 * n, dev, words=True)
@@ -2170,8 +2172,7 @@ class Pipeline:
         _need_output(self.motion_layout, "motion")
         self._propagate_check(maps, stride)
         h = _records_array(hops)
-        m = max(1, len(h))
-        via, status = np.full((m,) + maps.shape[2:], via_fill, dtype=np.uint8), np.zeros(m, dtype=np.int32)
+        via, status = _result_arrays(len(h), (maps.shape[2:], via_fill, np.uint8), ((), 0, np.int32))
         cfg = _propagate_config(maps, stride, fill)
         _chk(self.lib.leon_pipeline_propagate_maps(self.h, int(window), C.byref(cfg), h.ctypes.data if len(h) else None, len(h), maps.ctypes.data, via.ctypes.data,
                                                    status.ctypes.data))
@@ -2191,8 +2192,7 @@ class Pipeline:
         if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dim() == 4 and maps[0].is_contiguous() and maps.element_size() in (1, 2, 4)
                 and (maps.shape[0] == 1 or maps.stride(0) >= maps[0].numel())):
             raise ValueError("maps: a CUDA tensor [S, P, mh, mw] of a 1-, 2- or 4-byte dtype, contiguous (or with its slots further apart: stride(0))")
-        if not (isinstance(hops, torch.Tensor) and hops.is_cuda and hops.dtype == torch.int32 and hops.dim() == 2 and hops.shape[1] == 8 and hops.is_contiguous()):
-            raise ValueError("hops: a contiguous CUDA int32 tensor [N, 8]")
+        _device_records_check("hops", hops)
         lay = self._propagate_check(maps, stride)
         n, cells = int(hops.shape[0]), lay.mh * lay.mw
         for name, t, dtype, count in (("maps", maps, maps.dtype, 0), ("hops", hops, torch.int32, 0), ("via", via, torch.uint8, n * cells), ("status", status, torch.int32, n)):
@@ -2476,9 +2476,7 @@ class Pipeline:
         import torch
         self._need_tensors()
         dev = self.device_id
-        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.dtype == torch.int32 and records.dim() == 2 and records.shape[1] == 8
-                and records.is_contiguous()):
-            raise ValueError("records: a contiguous CUDA int32 tensor [N, 8]")
+        _device_records_check("records", records)
         for name, t in (("records", records), ("out", out), ("status", status)):
             _device_tensor_check(name, t, None, 0, dev)
         stream = torch.cuda.current_stream(dev) if stream is None else stream

@@ -130,6 +130,36 @@ def test_sums_near_2_to_the_40(L):
     assert out[0].tolist() == [2, 0, 0, 4096, 4096, 0, 0, 0] and out[2].tolist() == [2, 2, 2, 4094, 4094, 0, 0, 0]
 
 
+def test_a_window_of_no_frames(L):
+    """n_frames = 0 is a call the header admits: every record names a frame that is not there, and nothing of the window is read"""
+    out, votes, status = L.carry_device(FW, FH, MBW, MBH, 0, K.FWD, K.BWD, K.window(MBW, MBH, 41), [(0, 1, 1, 8, 8, 1), (1, 1, 1, 8, 8, 0)], fill=FILL)
+    assert status.tolist() == [L.REGION_FRAME] * 2 and (out == FILL).all() and (votes == FILL).all()
+
+
+def test_only_the_record_that_votes_is_there(L):
+    """one macroblock, and a window whose other frames have no record: the ring has one slot, which is not the frame's index"""
+    records = [None, K.uniform(1, 1, (6, -4, 0, 0), 1), None]
+    out, votes, status = run(L, 16, 16, 1, 1, records, [(0, 2, 3, 9, 8, 1), (1, 2, 3, 9, 8, 0), (0, 0, 0, 16, 16, 1)], what="one record")
+    assert (status == 0).all() and (votes[:, 2:] != 0).all()
+
+
+@pytest.mark.parametrize("votes,status", [(False, True), (True, False), (False, False)])
+def test_without_the_optional_outputs(L, votes, status):
+    """votes and status may be NULL, through the library itself: what is asked for is what the call with everything gives"""
+    records, regions = K.window(MBW, MBH, 43), K.pairs(BOXES["8 x 9 macroblocks"]) + [(3, 1, 1, 8, 8, 1)]
+    want = L.carry_device(FW, FH, MBW, MBH, K.N_FRAMES, K.FWD, K.BWD, records, regions, fill=FILL)
+    assert (want[2][:-1] == 0).all() and want[2][-1] == L.REGION_FRAME
+    ptrs, keep = L._carry_records(records, MBW, MBH)
+    f, b, r = np.array(K.FWD, dtype=np.int32), np.array(K.BWD, dtype=np.int32), L._records_array(regions)
+    got = [np.full_like(w, FILL) for w in want]
+    rc = L.load().leon_pipeline_carry_device(0, FW, FH, MBW, MBH, K.N_FRAMES, f.ctypes.data, b.ctypes.data, ptrs, r.ctypes.data, len(r), got[0].ctypes.data,
+                                             got[1].ctypes.data if votes else None, got[2].ctypes.data if status else None)
+    assert rc == L.OK, L.load().leon_last_error()
+    assert np.array_equal(got[0], want[0])
+    assert np.array_equal(got[1], want[1]) if votes else (got[1] == FILL).all()
+    assert np.array_equal(got[2], want[2]) if status else (got[2] == FILL).all()
+
+
 def test_call_refusals(L):
     records = K.window(MBW, MBH, 39)
     for kw in (dict(n=0), dict(n=65536)):

@@ -123,6 +123,37 @@ def test_refused_records_between_valid_ones(L, sources):
     G.assert_not_vacuous(want[0], want[1], sources, "refused between valid")
 
 
+@pytest.mark.parametrize("sources", G.SOURCES)
+def test_a_window_of_no_frames(L, sources):
+    """n_frames = 0 is a call the header admits: every record names a frame that is not there, and nothing of the window is read"""
+    motion, activity = G.window(6, 4, 41)
+    stats, status = L.gauge_kernel(96, 64, 6, 4, 0, motion, activity, [(0, 1, 1, 8, 8), (1, 1, 1, 8, 8)], sources=sources, fill=FILL)
+    assert status.tolist() == [L.REGION_FRAME] * 2 and (stats == FILL).all()
+
+
+@pytest.mark.parametrize("sources", G.SOURCES)
+def test_only_the_records_that_are_read_are_there(L, sources):
+    """one macroblock, and a window whose other frames have no record: each ring has one slot, which is not the frame's index"""
+    motion, activity = G.window(1, 1, 43)
+    (stats, status), want = run(L, 16, 16, 1, 1, [None, motion[1], None], [None, activity[1], None], [(1, 0, 0, 16, 16), (1, 3, 4, 5, 6)], sources, what="one record")
+    assert (status == 0).all() and stats[:, 0].tolist() == [256, 30]
+
+
+@pytest.mark.parametrize("sources", G.SOURCES)
+def test_without_a_status(L, sources):
+    """status may be NULL, through the library itself: the statistics are those of the call with it"""
+    fw, fh, mbw, mbh = 224, 160, 14, 10
+    motion, activity = G.window(mbw, mbh, 45)
+    regions = G.on_every_frame(common_boxes(fw, fh)) + [(3, 1, 1, 8, 8)]
+    want, want_status = L.gauge_kernel(fw, fh, mbw, mbh, G.N_FRAMES, motion, activity, regions, sources=sources, fill=FILL)
+    assert (want_status[:-1] == 0).all() and want_status[-1] == L.REGION_FRAME
+    mp, ap, keep = L._gauge_records(motion, activity, mbw, mbh, G.N_FRAMES)
+    r, stats, cfg = L._records_array(regions), np.full_like(want, FILL), L.PipelineGaugeConfig(sources)
+    rc = L.load().leon_pipeline_gauge_kernel(0, fw, fh, mbw, mbh, G.N_FRAMES, mp, ap, L.C.byref(cfg), r.ctypes.data, len(r), stats.ctypes.data, None)
+    assert rc == L.OK, L.load().leon_last_error()
+    assert np.array_equal(stats, want)
+
+
 def test_call_refusals(L):
     fw, fh, mbw, mbh = 224, 160, 14, 10
     motion, activity = G.window(mbw, mbh, 39)

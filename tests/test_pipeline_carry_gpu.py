@@ -312,6 +312,27 @@ def test_boxes_from_a_torch_op_carried_and_resampled_on_one_stream(L):
     assert batch.shape == want.shape and np.array_equal(batch.view(np.uint16), want.view(np.uint16))
 
 
+def test_the_host_road_without_votes_and_status_and_on_a_window_that_is_not_out(L):
+    data = ibbp_stream(96, 64, [6], 47)
+
+    def work(pipe, window, frames):
+        n = len(frames)
+        r = L._records_array([(s, 9, 5, 70, 50, t) for s in range(n) for t in range(n)] + [(n, 1, 1, 8, 8, 0)])
+        want, _, status = pipe.carry_regions(window, r, fill=FILL)
+        assert (status == 0).any() and status[-1] == L.REGION_FRAME
+        out, votes, st = np.full_like(want, FILL), np.full((len(r), 4), FILL, np.int32), np.full(len(r), FILL, np.int32)
+        assert pipe.lib.leon_pipeline_carry_regions(pipe.h, window, r.ctypes.data, len(r), out.ctypes.data, None, None) == L.OK, pipe.lib.leon_last_error()
+        assert np.array_equal(out, want)
+        # a window that is not out for delivery: refused before anything is allocated or uploaded, the caller's arrays as they were
+        out[:] = FILL
+        assert pipe.lib.leon_pipeline_carry_regions(pipe.h, window + 7, r.ctypes.data, len(r), out.ctypes.data, votes.ctypes.data, st.ctypes.data) == L.ERR_INVALID
+        assert pipe.lib.leon_last_error() == b"window %d is not out for delivery" % (window + 7)
+        assert (out == FILL).all() and (votes == FILL).all() and (st == FILL).all()
+        return True
+    got = run_windows(L, data, work, gops_per_window=1, gpu_parser=True)
+    assert got and all(got.values())
+
+
 def test_the_call_is_refused_as_a_whole(L):
     import torch
     data = ibbp_stream(96, 64, [6], 47)

@@ -219,6 +219,27 @@ def test_carry_regions_gop_into_gauge_on_one_stream(L):
     G.assert_not_vacuous(*want, 3, "carried boxes")
 
 
+def test_the_host_road_without_a_status_and_on_a_window_that_is_not_out(L):
+    data = ibbp_stream(96, 64, [6], 47)
+
+    def work(pipe, window, frames):
+        n, cfg = len(frames), L.PipelineGaugeConfig(3)
+        r = L._records_array([(s, 9, 5, 70, 50) for s in range(n)] + [(n, 1, 1, 8, 8)])
+        want, status = pipe.gauge_regions(window, r, fill=FILL)
+        assert (status[:-1] == 0).all() and status[-1] == L.REGION_FRAME
+        stats, st = np.full_like(want, FILL), np.full(len(r), FILL, np.int32)
+        assert pipe.lib.leon_pipeline_gauge_regions(pipe.h, window, C.byref(cfg), r.ctypes.data, len(r), stats.ctypes.data, None) == L.OK, pipe.lib.leon_last_error()
+        assert np.array_equal(stats, want)
+        # a window that is not out for delivery: refused before anything is allocated or uploaded, the caller's arrays as they were
+        stats[:] = FILL
+        assert pipe.lib.leon_pipeline_gauge_regions(pipe.h, window + 7, C.byref(cfg), r.ctypes.data, len(r), stats.ctypes.data, st.ctypes.data) == L.ERR_INVALID
+        assert pipe.lib.leon_last_error() == b"window %d is not out for delivery" % (window + 7)
+        assert (stats == FILL).all() and (st == FILL).all()
+        return True
+    got = run_windows(L, data, work, gops_per_window=1, gpu_parser=True)
+    assert got and all(got.values())
+
+
 def test_the_call_is_refused_as_a_whole(L):
     import torch
     data = ibbp_stream(96, 64, [6], 47)

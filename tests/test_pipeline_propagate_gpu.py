@@ -260,6 +260,29 @@ def test_a_mask_from_a_torch_op_propagated_and_read_on_one_stream(L):
     assert np.array_equal(counts, np.stack([(want[0] == label).sum(axis=(1, 2, 3)) for label in list(range(21)) + [255]])) and (counts.sum(axis=0) == 32 * 48).all()
 
 
+def test_the_host_road_without_via_and_status_and_on_a_window_that_is_not_out(L):
+    data = ibbp_stream(96, 64, [6], 47)
+
+    def work(pipe, window, frames):
+        n, s = len(frames), 4
+        maps = M.rand_maps(np.random.default_rng(7), 2 + n, 2, 96, 64, s, 2)
+        h = L._records_array([(t, 2 + t, 0, 1) for t in range(n)] + [(n, 2, 0, 1)])
+        want = maps.copy()
+        via, status = pipe.propagate_maps(window, want, h, s, fill=0x3C00)
+        assert (status[:-1] == 0).all() and status[-1] == L.REGION_FRAME and not np.array_equal(want, maps)
+        got, cfg = maps.copy(), L._propagate_config(maps, s, 0x3C00)
+        assert pipe.lib.leon_pipeline_propagate_maps(pipe.h, window, C.byref(cfg), h.ctypes.data, len(h), got.ctypes.data, None, None) == L.OK, pipe.lib.leon_last_error()
+        assert np.array_equal(got, want)
+        # a window that is not out for delivery: refused before anything is allocated or uploaded, the caller's arrays as they were
+        got, v, st = maps.copy(), np.full_like(via, M.VIA_FILL), np.full(len(h), -55, np.int32)
+        assert pipe.lib.leon_pipeline_propagate_maps(pipe.h, window + 7, C.byref(cfg), h.ctypes.data, len(h), got.ctypes.data, v.ctypes.data, st.ctypes.data) == L.ERR_INVALID
+        assert pipe.lib.leon_last_error() == b"window %d is not out for delivery" % (window + 7)
+        assert np.array_equal(got, maps) and (v == M.VIA_FILL).all() and (st == -55).all()
+        return True
+    got = run_windows(L, data, work, gops_per_window=1, gpu_parser=True)
+    assert got and all(got.values())
+
+
 def test_the_call_is_refused_as_a_whole(L):
     import torch
     data = ibbp_stream(96, 64, [6], 47)

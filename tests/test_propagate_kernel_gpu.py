@@ -123,6 +123,43 @@ def test_a_pitch_larger_than_the_map(L, gap):
         run(L, fw, fh, window(4, 3, s, 90), HOPS, s, maps, gap=gap, what="gap %d, %d x %d, s %d, e %d" % (gap, fw, fh, s, e))
 
 
+def test_a_window_of_no_frames(L):
+    """n_frames = 0 is a call the header admits: every hop names a target that is not there, and nothing of the window is read"""
+    fw, fh, s = 64, 48, 2
+    maps = M.rand_maps(np.random.default_rng(5), 10, 2, fw, fh, s, 2)
+    before = maps.copy()
+    via, status = L.propagate_kernel(fw, fh, 4, 3, 0, window(4, 3, s, 96), HOPS[:2], s, maps, via_fill=M.VIA_FILL)
+    assert status.tolist() == [L.REGION_FRAME] * 2 and (via == M.VIA_FILL).all() and np.array_equal(maps, before)
+
+
+def test_only_the_record_that_is_read_is_there(L):
+    """one macroblock, and a window whose other frames have no record: the ring has one slot, which is not the target's index"""
+    for s, e in ((1, 1), (4, 2), (16, 4)):
+        maps = M.rand_maps(np.random.default_rng(s), 4, 3, 16, 16, s, e)
+        want = run(L, 16, 16, [None, K.uniform(1, 1, (2 * s, -2 * s, -4 * s, 2 * s), 3), None], [(1, 3, 0, 2)], s, maps, what="one record, s %d, e %d" % (s, e))
+        assert want[2].tolist() == [0] and not np.array_equal(want[0][3], maps[3])
+
+
+@pytest.mark.parametrize("via,status", [(False, True), (True, False), (False, False)])
+def test_without_the_optional_outputs(L, via, status):
+    """via and status may be NULL, through the library itself: what is asked for is what the call with everything gives"""
+    fw, fh, s = 64, 48, 2
+    records, hops = window(4, 3, s, 97), HOPS + [(6, 9, 0, 1)]
+    maps = M.rand_maps(np.random.default_rng(6), 10, 3, fw, fh, s, 2)
+    want_maps = maps.copy()
+    want_via, want_status = L.propagate_kernel(fw, fh, 4, 3, len(records), records, hops, s, want_maps, via_fill=M.VIA_FILL, status_fill=-77)
+    assert (want_status[:-1] == 0).all() and want_status[-1] == L.REGION_FRAME
+    ptrs, keep = L._carry_records(records, 4, 3)
+    h, cfg = L._records_array(hops), L._propagate_config(maps, s, 0)
+    got_via, got_status = np.full_like(want_via, M.VIA_FILL), np.full_like(want_status, -77)
+    rc = L.load().leon_pipeline_propagate_kernel(0, fw, fh, 4, 3, len(records), ptrs, L.C.byref(cfg), h.ctypes.data, len(h), maps.ctypes.data,
+                                                 got_via.ctypes.data if via else None, got_status.ctypes.data if status else None)
+    assert rc == L.OK, L.load().leon_last_error()
+    assert np.array_equal(maps, want_maps)
+    assert np.array_equal(got_via, want_via) if via else (got_via == M.VIA_FILL).all()
+    assert np.array_equal(got_status, want_status) if status else (got_status == -77).all()
+
+
 def test_call_refusals(L):
     fw, fh, s = 64, 48, 2
     records = window(4, 3, s, 95)
