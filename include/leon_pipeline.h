@@ -1131,6 +1131,89 @@ int leon_pipeline_gauge_regions(leon_pipeline* p, int64_t window, const leon_pip
 int leon_pipeline_gauge_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
                                const void* const* motion_records_host, const void* const* activity_records_host, const leon_pipeline_gauge_config* cfg,
                                const leon_pipeline_region* regions, int32_t n, int64_t* stats, int32_t* status);
+/* Boxes proposed: WHERE a frame's motion record (LEON_PIPELINE_OUTPUT_MOTION) and activity record (LEON_PIPELINE_OUTPUT_ACTIVITY) say
+ * that something moved or was coded anew, as leon_pipeline_region rows on the device -- what the resample, warp, carry and gauge calls
+ * take as they are, so that a detector or a resample runs only there and no record visits the host.  Integers only; one text for host
+ * and device (csrc/leon_propose.h).
+ * Requests.  A request is a window frame index f.  With the coded grid mbw x mbh, the frame fw x fh and the config cfg:
+ * 1. Hot cells.  Macroblock (i, j) is hot iff 16 i < fw, 16 j < fh and at least one term holds:
+ *     motion    cfg.sources & LEON_PROPOSE_MOTION, and max(|fwd_h|, |fwd_v|, |bwd_h|, |bwd_v|) >= cfg.mv_min, the entries the frame's
+ *               motion record's, |-32768| = 32768; mv_min 1 .. 32768
+ *     intra     cfg.sources & LEON_PROPOSE_MOTION, cfg.flags & LEON_PROPOSE_INTRA, and info & 4 (on an I picture: the whole frame)
+ *     activity  cfg.sources & LEON_PROPOSE_ACTIVITY, and the cell's ac_mag >= cfg.ac_min; ac_min 1 .. 65535
+ *    A cell of the grid that lies wholly outside the frame is never hot (the grid may be larger than ceil(frame / 16)).
+ * 2. Components: the connected components of the hot cells under cfg.connectivity -- 4: edge neighbours, 8: edge and corner
+ *    neighbours; neighbours by (i, j), never by raster index (the last cell of a row and the first of the next are none).  A component's
+ *    `first` is the smallest raster index j * mbw + i among its cells, its `cells` their number, 1 .. 65536.
+ * 3. Selection and order.  The components with cells >= cfg.min_cells (1 .. 65536), in ascending order of `first`.  count is their
+ *    number, NOT capped: the caller sees an overflow.  The first K = cfg.max_boxes (1 .. 1024) of them are written.
+ * 4. Box.  With i0 .. i1 and j0 .. j1 the extent of the component's cells: x = 16 i0, y = 16 j0, w = min(16 (i1 + 1), fw) - x,
+ *    h = min(16 (j1 + 1), fh) - y: always a box regions_check accepts.
+ * 5. Outputs per request: regions[K] = {f, x, y, w, h, 0, 0, 0}; info[K][2] = {cells, first}; count; status.  Rows min(count, K) ..
+ *    K - 1 are written as {f, 0, 0, 0, 0, 0, 0, 0} with info {0, -1}: a [n, K, 8] result goes into the gauge and resample calls as it
+ *    is and the unused rows come back as LEON_REGION_BOX.  Every byte of an accepted request's outputs is written by every call.
+ * 6. Status.  LEON_REGION_FRAME: f outside the window; nothing else is judged.  As in the carry, propagate and gauge families A
+ *    REQUEST'S FAULT IS A STATUS WORD ON BOTH ROADS, NEVER AN ERROR OF THE CALL; a refused request has not one byte of its regions,
+ *    info or count written.
+ * One launch per call (k_propose: a workgroup per request; labels of 16 bits a cell, two bit masks and the rows in LDS: 2.25 bytes a
+ * cell of the grid and 8 a row, 155680 bytes at 256 x 256 and K = 1024); the window's table of ring ids is the scratch it needs.
+ * Nothing is launched on the decoder's stream. */
+#define LEON_PROPOSE_MOTION   1
+#define LEON_PROPOSE_ACTIVITY 2
+#define LEON_PROPOSE_INTRA    1           /* flags: an intra macroblock is hot (needs LEON_PROPOSE_MOTION) */
+typedef struct leon_pipeline_propose_config {
+    int32_t sources;                       /* LEON_PROPOSE_MOTION | LEON_PROPOSE_ACTIVITY, 1 .. 3 */
+    int32_t flags;                         /* 0 or LEON_PROPOSE_INTRA */
+    int32_t mv_min;                        /* 1 .. 32768 with the motion source, 0 without */
+    int32_t ac_min;                        /* 1 .. 65535 with the activity source, 0 without */
+    int32_t connectivity;                  /* 4 or 8 */
+    int32_t min_cells;                     /* 1 .. 65536 */
+    int32_t max_boxes;                     /* K, 1 .. 1024 */
+    int32_t reserved;                      /* must be 0 */
+} leon_pipeline_propose_config;            /* 32 bytes */
+typedef struct leon_pipeline_propose_regions_call {
+    const int32_t* frames;                 /* DEVICE memory, n requests, 4-byte aligned */
+    int32_t  n;                            /* 1 .. 65535 */
+    int32_t  reserved0;                    /* must be 0 */
+    leon_pipeline_region* device_regions;  /* DEVICE memory, n x K records, 4-byte aligned */
+    int32_t* device_info;                  /* DEVICE memory, n x K x 2 words, 4-byte aligned, may be NULL */
+    int32_t* device_count;                 /* DEVICE memory, n words, 4-byte aligned */
+    int32_t* device_status;                /* DEVICE memory, n words, 4-byte aligned, may be NULL */
+    void*    stream;                       /* hipStream_t of the caller's; NULL: the pipeline's regions stream, and the call waits */
+    uint64_t reserved[1];                  /* must be 0 */
+} leon_pipeline_propose_regions_call;      /* 64 bytes */
+/* host only: the definition on the CPU for one request, from records in host memory laid out as leon_pipeline_motion_layout /
+ * leon_pipeline_activity_layout (mb_width, mb_height) say: motion_records[i] and activity_records[i] are window frame i's; an array
+ * the sources do not ask for may be NULL, and so may the entries of frames other than `frame`.  The components are found by a flood
+ * fill that shares no text with the kernel's search.  Returns the request's status word (>= 0; regions (K records), info (K x 2 words,
+ * may be NULL) and *count are written exactly when it is 0), or LEON_ERR_INVALID (negative) for a null argument, a grid outside
+ * 1 .. 256, a frame larger than the grid or below 1, n_frames < 0, what the config refuses (below), a NULL record where the frame's
+ * is needed. */
+int32_t leon_pipeline_propose_record(int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                                     const void* const* motion_records, const void* const* activity_records, const leon_pipeline_propose_config* cfg,
+                                     int32_t frame, leon_pipeline_region* regions, int32_t* info, int32_t* count);
+/* Requests in DEVICE memory: the call ONLY ENQUEUES on the caller's stream (stream NULL: the regions stream, and the call waits), with
+ * leon_pipeline_carry_regions_device's ordering rules and its scratch event, word for word.  Refused (LEON_ERR_INVALID, nothing
+ * enqueued), in this order: a null cfg, sources outside 1 .. 3, LEON_PROPOSE_INTRA without the motion source or another bit in flags,
+ * mv_min or ac_min outside its range for a source asked for or not 0 for one that is not, connectivity not 4 or 8, min_cells outside
+ * 1 .. 65536, max_boxes outside 1 .. 1024, a non-zero reserved word of cfg; a source whose output the pipeline was created without;
+ * a null call; a window that is not out for delivery or was delivered with an error; a non-zero reserved word of the call; n outside
+ * 1 .. 65535; a null `frames`, `device_regions` or `device_count`; a pointer that is not 4-byte aligned. */
+int leon_pipeline_propose_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_propose_config* cfg,
+                                         const leon_pipeline_propose_regions_call* call);
+/* Requests in host memory, results to host memory, synchronous: the device road between an upload and the copies back.  regions
+ * (n x K records), info (n x K x 2 words, may be NULL), count (n words) and status (n words, may be NULL) go up and come back whole,
+ * so a refused request's words stay as the caller had them.  The call-level refusals are the device road's. */
+int leon_pipeline_propose_regions(leon_pipeline* p, int64_t window, const leon_pipeline_propose_config* cfg, const int32_t* frames, int32_t n,
+                                  leon_pipeline_region* regions, int32_t* info, int32_t* count, int32_t* status);
+/* A diagnostic in the manner of leon_pipeline_gauge_kernel: k_propose on records the CALLER supplies (host memory, as
+ * leon_pipeline_propose_record takes them; NULL for frames no valid request of the call names), with memory of its own on device_id's
+ * null stream, synchronous; frames, regions, info (may be NULL), count and status (may be NULL) in host memory, the outputs going up
+ * and coming back whole.  Refused (LEON_ERR_INVALID): what leon_pipeline_propose_record refuses, n outside 1 .. 65535, a valid
+ * request that names a frame without the record it needs. */
+int leon_pipeline_propose_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                                 const void* const* motion_records_host, const void* const* activity_records_host, const leon_pipeline_propose_config* cfg,
+                                 const int32_t* frames, int32_t n, leon_pipeline_region* regions, int32_t* info, int32_t* count, int32_t* status);
 /* A diagnostic: the DEVICE's evaluation of the tables of n_axes single axes, copied back, to be compared word for word with
  * leon_pipeline_resize_weights (pixels would hide a weight that is one unit off).  axes = n_axes x {in_size, crop_start, crop_size,
  * out_size}; with max_out the largest out_size of the batch, axis a's tables lie at a fixed pitch: first[a * max_out + o],

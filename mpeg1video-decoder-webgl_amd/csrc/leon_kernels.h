@@ -45,6 +45,7 @@
 #include "leon_carry.h"
 #include "leon_propagate.h"
 #include "leon_gauge.h"
+#include "leon_propose.h"
 
 
 namespace leon {
@@ -3422,6 +3423,225 @@ __global__ __launch_bounds__(kRgbaBlock) void k_gauge(const GaugeRecord* __restr
 #pragma unroll
     for (int k = 0; k < kGaugeWords / 2; k++) po[k] = GaugeWords2{{o[2 * k], o[2 * k + 1]}};
     if (status) status[i] = kRegionOk;
+}
+
+// ---- propose: boxes of the connected components of a frame's hot macroblocks (include/leon_pipeline.h, leon_pipeline_propose_regions) --
+// One workgroup of 8 waves per request, everything between the records and the rows in LDS (leon_propose.h, ProposeLds: 16-bit
+// labels, two bit masks, two dwords a row).  The steps, a barrier between each two:
+//   1  the hot mask: a lane a cell, 8 + 1 + 8 bytes of the frame's records -- whichever the sources ask for --, a wave's ballot is two words;
+//   2  every hot cell points to the first cell of its run in its row (bit arithmetic on the mask: a row is joined at depth 1);
+//   3  union with the row above, by smallest index: the larger root is hung under the smaller with a 16-bit minimum (a compare-and-swap
+//      on the label's dword), and whoever finds a root taken goes on with what it pointed to.  Labels only ever fall and a label never
+//      exceeds its cell, so the root of a component is its smallest cell -- its `first` -- whatever the order of the waves;
+//   4  every hot cell points to its root;
+//   5  the root mask (ballot); a root's own slot, which said nothing but "root", becomes 0;
+//   6  every other hot cell adds 1 to its root's slot: cells - 1, at most 65535, never a carry into the neighbouring label;
+//   7  the roots with cells >= min_cells are counted, a thread a piece of the root mask, and the counts scanned by shuffles;
+//   8  in raster order -- the order of `first` -- the selected roots take rows 0, 1, ...: the first K write {first, cells - 1} and
+//      their own cell as the extent and keep the row in their slot, every other root keeps 0xffff;
+//   9  every other hot cell of a component with a row widens the row's extent (three 8-bit maxima in a dword, compare-and-swap only
+//      when a field grows);
+//  10  the K rows go out, boxes first and filler behind, with count and status.
+// A refused request leaves with its status word alone.  Every index into LDS is below ProposeLds's sizes for mbs = mbw * mbh and
+// K = max_boxes, which the launch passes as dynamic LDS; every macroblock index is below mbs.
+struct ProposeCall {
+    ProposeConfig cfg;
+    int32_t fw, fh, mbw, mbh;            // the frame, the coded grid
+    int32_t n_frames, n;                 // frames of the window, requests of the call
+    uint32_t info_offset, motion_pitch;  // MotionLayout's
+    uint32_t activity_pitch;             // ActivityLayout's
+    uint32_t reserved;
+};
+
+__device__ __forceinline__ uint32_t propose_get(const volatile uint32_t* lab, uint32_t c) { return (lab[c >> 1] >> ((c & 1u) << 4)) & 0xffffu; }
+__device__ __forceinline__ void propose_put(volatile uint32_t* lab, uint32_t c, uint32_t v) { reinterpret_cast<volatile uint16_t*>(lab)[c] = (uint16_t)v; }
+__device__ __forceinline__ uint32_t propose_find(const volatile uint32_t* lab, uint32_t c)
+{
+    for (uint32_t l = propose_get(lab, c); l != c; l = propose_get(lab, c)) c = l;
+    return c;
+}
+// label a = min(label a, b); what stood there
+__device__ __forceinline__ uint32_t propose_min(uint32_t* lab, uint32_t a, uint32_t b)
+{
+    uint32_t* const p = lab + (a >> 1);
+    const uint32_t sh = (a & 1u) << 4;
+    uint32_t w = *(volatile uint32_t*)p;
+    for (;;) {
+        const uint32_t cur = (w >> sh) & 0xffffu;
+        if (cur <= b) return cur;
+        const uint32_t got = atomicCAS(p, w, (w & ~(0xffffu << sh)) | (b << sh));
+        if (got == w) return cur;
+        w = got;
+    }
+}
+__device__ __forceinline__ void propose_union(uint32_t* lab, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = propose_find(lab, a);
+        b = propose_find(lab, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }
+        const uint32_t old = propose_min(lab, a, b);
+        if (old == a) return;
+        a = old;            // a was a root no longer: what it pointed to has to meet b as well
+    }
+}
+
+__global__ __launch_bounds__(kProposeThreads) void k_propose(const int32_t* __restrict__ requests, const CarryFrame* __restrict__ frames,
+                                                             const uint8_t* __restrict__ motion, const uint8_t* __restrict__ activity,
+                                                             int32_t* __restrict__ regions, int32_t* __restrict__ info, int32_t* __restrict__ count,
+                                                             int32_t* __restrict__ status, ProposeCall c)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_propose[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6, q = blockIdx.x;
+    const int32_t f = requests[q];
+    if (propose_request_status(f, c.n_frames) != kRegionOk) {
+        if (tid == 0 && status) status[q] = kRegionFrame;
+        return;
+    }
+    const uint32_t mbw = (uint32_t)c.mbw, mbs = mbw * (uint32_t)c.mbh, K = (uint32_t)c.cfg.max_boxes;
+    const ProposeLds L = propose_lds(mbs, K);
+    uint32_t* const lab = s_propose;
+    uint32_t* const hot = s_propose + L.hot;
+    uint32_t* const root = s_propose + L.root;
+    uint32_t* const rows = s_propose + L.rows;
+    uint32_t* const scan = s_propose + L.scan;
+    const uint32_t padded = 32u * L.mask_words;
+    const bool act = (c.cfg.sources & kProposeActivity) != 0, mot = (c.cfg.sources & kProposeMotion) != 0;
+    const uint32_t ring = frames[f].ring;
+    const uint8_t* __restrict__ mrec = motion + (mot ? (size_t)ring * c.motion_pitch : 0);
+    const uint8_t* __restrict__ arec = activity + (act ? (size_t)ring * c.activity_pitch : 0);
+
+    for (uint32_t k = tid; k < padded; k += kProposeThreads) {                              // 1
+        bool h = false;
+        if (k < mbs) {
+            const uint32_t j = k / mbw, i = k - j * mbw;
+            uint2 mv = uint2{0u, 0u};
+            uint32_t lo = 0u, nf = 0u;
+            if (act) lo = *reinterpret_cast<const uint32_t*>(arec + (size_t)k * 8u);
+            if (mot) {
+                mv = *reinterpret_cast<const uint2*>(mrec + (size_t)k * 8u);
+                nf = mrec[c.info_offset + k];
+            }
+            h = propose_hot(c.cfg, c.fw, c.fh, (int32_t)i, (int32_t)j, lo, nf, mv.x, mv.y);
+        }
+        const uint64_t b = __ballot(h);
+        if (lane == 0) {
+            hot[k >> 5] = (uint32_t)b;
+            hot[(k >> 5) + 1u] = (uint32_t)(b >> 32);
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = tid; k < mbs; k += kProposeThreads)                                   // 2
+        if (propose_bit(hot, k)) propose_put(lab, k, propose_run_start(hot, k, k - k % mbw));
+    __syncthreads();
+    const bool corners = c.cfg.connectivity == 8;
+    for (uint32_t k = tid + mbw; k < mbs; k += kProposeThreads) {                           // 3
+        if (!propose_bit(hot, k)) continue;
+        const uint32_t i = k % mbw, up = k - mbw;
+        const bool left = i > 0u && propose_bit(hot, k - 1u);
+        if (propose_bit(hot, up)) {
+            // (the left neighbour joins the two runs where it and the cell above it are hot)
+            if (!(left && propose_bit(hot, up - 1u))) propose_union(lab, k, up);
+        } else if (corners) {
+            // (the cell above is cold: a corner neighbour is a run of its own above; where the left / right neighbour is hot, that
+            // corner is the cell above IT)
+            if (i > 0u && !left && propose_bit(hot, up - 1u)) propose_union(lab, k, up - 1u);
+            if (i + 1u < mbw && !propose_bit(hot, k + 1u) && propose_bit(hot, up + 1u)) propose_union(lab, k, up + 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = tid; k < mbs; k += kProposeThreads)                                   // 4
+        if (propose_bit(hot, k)) propose_put(lab, k, propose_find(lab, k));
+    __syncthreads();
+    for (uint32_t k = tid; k < padded; k += kProposeThreads) {                              // 5
+        const bool r = k < mbs && propose_bit(hot, k) && propose_get(lab, k) == k;
+        const uint64_t b = __ballot(r);
+        if (lane == 0) {
+            root[k >> 5] = (uint32_t)b;
+            root[(k >> 5) + 1u] = (uint32_t)(b >> 32);
+        }
+        if (r) propose_put(lab, k, 0u);
+    }
+    __syncthreads();
+    for (uint32_t k = tid; k < mbs; k += kProposeThreads)                                   // 6
+        if (propose_bit(hot, k) && !propose_bit(root, k)) {
+            const uint32_t r = propose_get(lab, k);
+            atomicAdd(lab + (r >> 1), 1u << ((r & 1u) << 4));
+        }
+    __syncthreads();
+    const uint32_t per = (L.mask_words + kProposeThreads - 1u) / kProposeThreads;           // 7
+    const uint32_t w0 = min(tid * per, L.mask_words), w1 = min(w0 + per, L.mask_words), least = (uint32_t)c.cfg.min_cells;
+    uint32_t sum = 0u;
+    for (uint32_t w = w0; w < w1; w++)
+        for (uint32_t m = root[w]; m; m &= m - 1u) sum += propose_get(lab, (w << 5) + (uint32_t)__builtin_ctz(m)) + 1u >= least ? 1u : 0u;
+    uint32_t incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t v = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += v;
+    }
+    if (lane == 63u) scan[wv] = incl;
+    __syncthreads();
+    uint32_t run = incl - sum, total = 0u;                                                  // 8
+    for (uint32_t w = 0; w < (uint32_t)kProposeThreads / 64u; w++) {
+        run += w < wv ? scan[w] : 0u;
+        total += scan[w];
+    }
+    for (uint32_t w = w0; w < w1; w++)
+        for (uint32_t m = root[w]; m; m &= m - 1u) {
+            const uint32_t r = (w << 5) + (uint32_t)__builtin_ctz(m), less = propose_get(lab, r);
+            uint32_t row = 0xffffu;
+            if (less + 1u >= least) {
+                if (run < K) {
+                    row = run;
+                    rows[2u * row] = r | (less << 16);
+                    rows[2u * row + 1u] = propose_extent(r % mbw, r / mbw);
+                }
+                run++;
+            }
+            propose_put(lab, r, row);
+        }
+    __syncthreads();
+    for (uint32_t k = tid; k < mbs; k += kProposeThreads)                                   // 9
+        if (propose_bit(hot, k) && !propose_bit(root, k)) {
+            const uint32_t row = propose_get(lab, propose_get(lab, k));
+            if (row == 0xffffu) continue;
+            const uint32_t e = propose_extent(k % mbw, k / mbw);
+            uint32_t* const p = rows + 2u * row + 1u;
+            uint32_t w = *(volatile uint32_t*)p;
+            for (;;) {
+                const uint32_t joined = propose_extent_join(w, e);
+                if (joined == w) break;
+                const uint32_t got = atomicCAS(p, w, joined);
+                if (got == w) break;
+                w = got;
+            }
+        }
+    __syncthreads();
+    const uint32_t written = total < K ? total : K;                                         // 10
+    for (uint32_t k = tid; k < K; k += kProposeThreads) {
+        int32_t o[8], nf[2];
+        if (k < written) {
+            const uint32_t a = rows[2u * k], e = rows[2u * k + 1u], first = a & 0xffffu;
+            propose_box(f, c.fw, c.fh, (int32_t)(255u - (e & 255u)), (int32_t)((e >> 8) & 255u), (int32_t)(first / mbw), (int32_t)((e >> 16) & 255u), o);
+            nf[0] = (int32_t)(a >> 16) + 1;
+            nf[1] = (int32_t)first;
+        } else {
+            propose_filler(f, o, nf);
+        }
+        int32_t* const po = regions + ((size_t)q * K + k) * 8u;
+#pragma unroll
+        for (int u = 0; u < 8; u++) po[u] = o[u];
+        if (info) {
+            info[((size_t)q * K + k) * 2u] = nf[0];
+            info[((size_t)q * K + k) * 2u + 1u] = nf[1];
+        }
+    }
+    if (tid == 0) {
+        count[q] = (int32_t)total;
+        if (status) status[q] = kRegionOk;
+    }
 }
 
 // ---- measured HBM roofline -----------------------------------------------------------

@@ -2734,6 +2734,150 @@ int gauge_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32_t
     });
 }
 
+// ---- boxes proposed: the components of a frame's hot macroblocks as region records (leon_pipeline_propose_regions) -----------------
+static_assert(sizeof(leon_pipeline_propose_config) == 32 && sizeof(leon_pipeline_propose_regions_call) == 64 && sizeof(leon::ProposeConfig) == 32 &&
+              sizeof(leon::ProposeCall) == 72, "include/leon_pipeline.h states the sizes");
+static_assert(leon::kProposeMotion == LEON_PROPOSE_MOTION && leon::kProposeActivity == LEON_PROPOSE_ACTIVITY && leon::kProposeIntra == LEON_PROPOSE_INTRA,
+              "the kernel's bits are the header's");
+static_assert(LEON_PROPOSE_MOTION == LEON_GAUGE_MOTION && LEON_PROPOSE_ACTIVITY == LEON_GAUGE_ACTIVITY, "one judgement of the outputs a call's sources need (gauge_outputs_check)");
+// a CU's LDS holds the largest request: every grid up to 256 x 256 with every K up to 1024
+static_assert(leon::propose_lds(leon::kProposeMaxCells, leon::kProposeMaxBoxes).bytes == 155680 && 155680 <= 160 * 1024, "include/leon_pipeline.h states the LDS");
+
+int propose_config_check(const leon_pipeline_propose_config* cfg)
+{
+    if (!cfg) return fail(LEON_ERR_INVALID, "null argument");
+    if (cfg->sources < 1 || cfg->sources > (LEON_PROPOSE_MOTION | LEON_PROPOSE_ACTIVITY))
+        return fail(LEON_ERR_INVALID, "propose regions: sources %d (LEON_PROPOSE_MOTION | LEON_PROPOSE_ACTIVITY: 1 .. 3)", cfg->sources);
+    const bool mot = (cfg->sources & LEON_PROPOSE_MOTION) != 0, act = (cfg->sources & LEON_PROPOSE_ACTIVITY) != 0;
+    if ((cfg->flags & ~LEON_PROPOSE_INTRA) || (cfg->flags && !mot))
+        return fail(LEON_ERR_INVALID, "propose regions: flags %d (LEON_PROPOSE_INTRA, with LEON_PROPOSE_MOTION only)", cfg->flags);
+    if (mot ? cfg->mv_min < 1 || cfg->mv_min > 32768 : cfg->mv_min != 0)
+        return fail(LEON_ERR_INVALID, "propose regions: mv_min %d (1 .. 32768 with the motion source, 0 without)", cfg->mv_min);
+    if (act ? cfg->ac_min < 1 || cfg->ac_min > 65535 : cfg->ac_min != 0)
+        return fail(LEON_ERR_INVALID, "propose regions: ac_min %d (1 .. 65535 with the activity source, 0 without)", cfg->ac_min);
+    if (cfg->connectivity != 4 && cfg->connectivity != 8) return fail(LEON_ERR_INVALID, "propose regions: connectivity %d (4 or 8)", cfg->connectivity);
+    if (cfg->min_cells < 1 || cfg->min_cells > leon::kProposeMaxCells) return fail(LEON_ERR_INVALID, "propose regions: min_cells %d (1 .. 65536)", cfg->min_cells);
+    if (cfg->max_boxes < 1 || cfg->max_boxes > leon::kProposeMaxBoxes) return fail(LEON_ERR_INVALID, "propose regions: max_boxes %d (1 .. 1024)", cfg->max_boxes);
+    if (cfg->reserved) return fail(LEON_ERR_INVALID, "propose regions: a reserved word of the config is not 0");
+    return LEON_OK;
+}
+
+// the launch every road shares: requests, the window's table and the two rings in device memory (a ring the sources do not ask for is
+// not read); a workgroup a request, its LDS as leon_propose.h lays it out for this grid and K -- above 48 KiB the kernel is told so
+int propose_launch(hipStream_t st, const int32_t* d_requests, const leon::CarryFrame* d_frames, const uint8_t* d_motion, const uint8_t* d_activity, int32_t fw, int32_t fh,
+                   int32_t mbw, int32_t mbh, const leon::MotionLayout& ml, const leon::ActivityLayout& al, int32_t n_frames, const leon_pipeline_propose_config& cfg, int32_t n,
+                   int32_t* d_regions, int32_t* d_info, int32_t* d_count, int32_t* d_status)
+{
+    leon::ProposeCall C{};
+    memcpy(&C.cfg, &cfg, sizeof(C.cfg));
+    C.fw = fw; C.fh = fh; C.mbw = mbw; C.mbh = mbh;
+    C.n_frames = n_frames; C.n = n;
+    C.info_offset = ml.info_offset; C.motion_pitch = ml.record_pitch; C.activity_pitch = al.record_pitch;
+    const uint32_t lds = leon::propose_lds((uint32_t)mbw * (uint32_t)mbh, (uint32_t)cfg.max_boxes).bytes;
+    if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)leon::k_propose, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(leon::k_propose, dim3((unsigned)n), dim3(leon::kProposeThreads), lds, st, d_requests, d_frames, d_motion, d_activity, d_regions, d_info, d_count,
+                       d_status, C);
+    return LEON_OK;
+}
+
+// One call of the device road: the host's refusals (the config's before the window's), then one launch
+int propose_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_propose_config* cfg, const leon_pipeline_propose_regions_call* c)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = propose_config_check(cfg);
+    if (rc != LEON_OK || (rc = gauge_outputs_check(p, cfg->sources)) != LEON_OK) return rc;
+    if (!c) return fail(LEON_ERR_INVALID, "null argument");
+    int launched = LEON_OK;
+    rc = table_road(p, window, c->stream, "propose regions", "frames", c->n, c->reserved0 || c->reserved[0], [&] {
+        if (!c->frames) return fail(LEON_ERR_INVALID, "propose regions: null frames");
+        if (!c->device_regions) return fail(LEON_ERR_INVALID, "propose regions: null device_regions");
+        if (!c->device_count) return fail(LEON_ERR_INVALID, "propose regions: null device_count");
+        if (((uintptr_t)c->frames | (uintptr_t)c->device_regions | (uintptr_t)c->device_info | (uintptr_t)c->device_count | (uintptr_t)c->device_status) & 3u)
+            return fail(LEON_ERR_INVALID, "propose regions: frames %p, device_regions %p, device_info %p, device_count %p, device_status %p: not all 4-byte aligned",
+                        (const void*)c->frames, (void*)c->device_regions, (void*)c->device_info, (void*)c->device_count, (void*)c->device_status);
+        return (int)LEON_OK;
+    }, [&](hipStream_t st, const leon::CarryFrame* d_frames, int32_t n_frames) {
+        launched = propose_launch(st, c->frames, d_frames, p->motion.ring, p->activity.ring, p->vinfo.frame_width, p->vinfo.frame_height, p->vinfo.mb_width,
+                                  p->vinfo.mb_height, p->motion_lay, p->activity_lay, n_frames, *cfg, c->n, reinterpret_cast<int32_t*>(c->device_regions), c->device_info,
+                                  c->device_count, c->device_status);
+    });
+    return rc != LEON_OK ? rc : launched;
+}
+
+// One call of the host road: [regions | info | count | status | requests], what the caller has in the outputs going up first.  The
+// outputs are judged here as well, behind the count and in front of the window, as the gauge family's host road does.
+int propose_regions(leon_pipeline* p, int64_t window, const leon_pipeline_propose_config* cfg, const int32_t* frames, int32_t n, leon_pipeline_region* regions, int32_t* info,
+                    int32_t* count, int32_t* status)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = propose_config_check(cfg);
+    if (rc != LEON_OK) return rc;
+    if (!frames || !regions || !count) return fail(LEON_ERR_INVALID, "propose regions: null %s", !frames ? "frames" : !regions ? "regions" : "count");
+    if ((rc = record_count_check("propose regions", "frames", n)) != LEON_OK || (rc = gauge_outputs_check(p, cfg->sources)) != LEON_OK) return rc;
+    const size_t rows = (size_t)n * (size_t)cfg->max_boxes;
+    return table_host_road(p, window, "propose", {{regions, regions, rows * 32}, {info, info, rows * 8}, {count, count, (size_t)n * 4}, {status, status, (size_t)n * 4},
+                                                  {frames, nullptr, (size_t)n * 4}}, [&](const Pieces& s) {
+        leon_pipeline_propose_regions_call c{};
+        c.frames = s.at<const int32_t>(4);
+        c.n = n;
+        c.device_regions = s.at<leon_pipeline_region>(0);
+        c.device_info = info ? s.at<int32_t>(1) : nullptr;
+        c.device_count = s.at<int32_t>(2);
+        c.device_status = status ? s.at<int32_t>(3) : nullptr;
+        return propose_regions_device(p, window, cfg, &c);
+    });
+}
+
+// the definition on the CPU: the checks, then leon_propose.h's host text (propose_request_host: a flood fill, nothing of the kernel's
+// search) over records in host memory; the status word, or a negative error
+int32_t propose_record_host(int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames, const void* const* motion_records, const void* const* activity_records,
+                            const leon_pipeline_propose_config* cfg, int32_t frame, leon_pipeline_region* regions, int32_t* info, int32_t* count, bool dry)
+{
+    int rc = propose_config_check(cfg);
+    if (rc != LEON_OK) return rc;
+    const bool mot = (cfg->sources & LEON_PROPOSE_MOTION) != 0, act = (cfg->sources & LEON_PROPOSE_ACTIVITY) != 0;
+    if ((!dry && (!regions || !count)) || (mot && !motion_records) || (act && !activity_records)) return fail(LEON_ERR_INVALID, "null argument");
+    if ((rc = carry_geometry_check(fw, fh, mbw, mbh, n_frames)) != LEON_OK) return rc;
+    const int32_t st = leon::propose_request_status(frame, n_frames);
+    if (st != leon::kRegionOk) return st;
+    const uint8_t* mrec = mot ? static_cast<const uint8_t*>(motion_records[frame]) : nullptr;
+    const uint8_t* arec = act ? static_cast<const uint8_t*>(activity_records[frame]) : nullptr;
+    if ((mot && !mrec) || (act && !arec)) return fail(LEON_ERR_INVALID, "propose: frame %d has no %s record", frame, mot && !mrec ? "motion" : "activity");
+    if (dry) return leon::kRegionOk;
+    leon::ProposeConfig C;
+    memcpy(&C, cfg, sizeof(C));
+    leon::propose_request_host(C, fw, fh, mbw, mbh, mrec, arec, frame, reinterpret_cast<int32_t*>(regions), info, count);
+    return leon::kRegionOk;
+}
+
+// k_propose on records the caller supplies (leon_pipeline_propose_kernel): memory of its own, the null stream
+int propose_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32_t mbh, int32_t n_frames, const void* const* motion_records,
+                   const void* const* activity_records, const leon_pipeline_propose_config* cfg, const int32_t* frames, int32_t n, leon_pipeline_region* regions, int32_t* info,
+                   int32_t* count, int32_t* status)
+{
+    int rc = propose_config_check(cfg);
+    if (rc != LEON_OK) return rc;
+    if (!frames || !regions || !count) return fail(LEON_ERR_INVALID, "null argument");
+    if ((rc = record_count_check("propose regions", "frames", n)) != LEON_OK) return rc;
+    for (int32_t i = 0; i < n; i++)          // a record a valid request names must be there: the judgement alone, nothing searched
+        if (propose_record_host(fw, fh, mbw, mbh, n_frames, motion_records, activity_records, cfg, frames[i], nullptr, nullptr, nullptr, true) < 0) return LEON_ERR_INVALID;
+    const bool mot = (cfg->sources & LEON_PROPOSE_MOTION) != 0, act = (cfg->sources & LEON_PROPOSE_ACTIVITY) != 0;
+    const leon::MotionLayout ML = leon::motion_layout((uint32_t)mbw, (uint32_t)mbh);
+    const leon::ActivityLayout AL = leon::activity_layout((uint32_t)mbw, (uint32_t)mbh);
+    uint32_t slots;
+    const std::vector<leon::CarryFrame> table =
+        kernel_table(n_frames, nullptr, nullptr, [&](size_t i) { return (mot && motion_records[i]) || (act && activity_records[i]); }, &slots);
+    const std::vector<uint8_t> motion = kernel_ring(table, slots, mot ? motion_records : nullptr, ML.record_bytes, ML.record_pitch);
+    const std::vector<uint8_t> activity = kernel_ring(table, slots, act ? activity_records : nullptr, AL.record_bytes, AL.record_pitch);
+    const size_t rows = (size_t)n * (size_t)cfg->max_boxes;
+    return pieces_run(device_id, "propose", {{regions, regions, rows * 32}, {info, info, rows * 8}, {count, count, (size_t)n * 4}, {status, status, (size_t)n * 4},
+                                             {frames, nullptr, (size_t)n * 4}, {table.data(), nullptr, table.size() * sizeof(leon::CarryFrame)},
+                                             {motion.data(), nullptr, motion.size()}, {activity.data(), nullptr, activity.size()}}, [&](const Pieces& s) {
+        return propose_launch(nullptr, s.at<const int32_t>(4), s.at<const leon::CarryFrame>(5), mot ? s.at(6) : nullptr, act ? s.at(7) : nullptr, fw, fh, mbw, mbh, ML, AL,
+                              n_frames, *cfg, n, s.at<int32_t>(0), info ? s.at<int32_t>(1) : nullptr, s.at<int32_t>(2), status ? s.at<int32_t>(3) : nullptr);
+    });
+}
+
 // ---- dense maps propagated along the motion vectors (leon_pipeline_propagate_maps) ------------------------------------------------
 static_assert(sizeof(leon_pipeline_propagate_hop) == 32 && sizeof(leon_pipeline_propagate_config) == 40 && sizeof(struct leon_pipeline_propagate_layout) == 32 &&
               sizeof(leon_pipeline_propagate_maps_call) == 64 && sizeof(leon::PropagateHop) == sizeof(leon_pipeline_propagate_hop), "include/leon_pipeline.h states the sizes");
@@ -3971,6 +4115,32 @@ int leon_pipeline_gauge_kernel(int32_t device_id, int32_t frame_width, int32_t f
                                const leon_pipeline_region* regions, int32_t n, int64_t* stats, int32_t* status)
 {
     return gauge_kernel(device_id, frame_width, frame_height, mb_width, mb_height, n_frames, motion_records_host, activity_records_host, cfg, regions, n, stats, status);
+}
+
+int32_t leon_pipeline_propose_record(int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames, const void* const* motion_records,
+                                     const void* const* activity_records, const leon_pipeline_propose_config* cfg, int32_t frame, leon_pipeline_region* regions, int32_t* info,
+                                     int32_t* count)
+{
+    return propose_record_host(frame_width, frame_height, mb_width, mb_height, n_frames, motion_records, activity_records, cfg, frame, regions, info, count, false);
+}
+
+int leon_pipeline_propose_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_propose_config* cfg, const leon_pipeline_propose_regions_call* call)
+{
+    return propose_regions_device(p, window, cfg, call);
+}
+
+int leon_pipeline_propose_regions(leon_pipeline* p, int64_t window, const leon_pipeline_propose_config* cfg, const int32_t* frames, int32_t n, leon_pipeline_region* regions,
+                                  int32_t* info, int32_t* count, int32_t* status)
+{
+    return propose_regions(p, window, cfg, frames, n, regions, info, count, status);
+}
+
+int leon_pipeline_propose_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
+                                 const void* const* motion_records_host, const void* const* activity_records_host, const leon_pipeline_propose_config* cfg,
+                                 const int32_t* frames, int32_t n, leon_pipeline_region* regions, int32_t* info, int32_t* count, int32_t* status)
+{
+    return propose_kernel(device_id, frame_width, frame_height, mb_width, mb_height, n_frames, motion_records_host, activity_records_host, cfg, frames, n, regions, info, count,
+                          status);
 }
 
 int leon_pipeline_propagate_layout(int32_t frame_width, int32_t frame_height, int32_t stride, int32_t planes, int32_t elem_bytes, struct leon_pipeline_propagate_layout* out)

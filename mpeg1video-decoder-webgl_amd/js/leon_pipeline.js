@@ -78,6 +78,15 @@
  *                                  (sources 1: words 8 .. 15), its activity record (sources 2: words 1 .. 7) or both (3; the default: every
  *                                  record output the pipeline has); word 0 is the box's area (leon_pipeline_gauge_regions).  Every word is
  *                                  below 2^53, so the numbers are exact; a record's fault is its status word, not a throw
+ *   p.proposeRegions(window, frames, {maxBoxes, mvMin, acMin, intra, connectivity, minCells, sources}) -> {regions: Int32Array [n][K][8],
+ *                                  count: Int32Array [n], info: Int32Array [n][K][2] (cells, first), status: Int32Array [n]}: frames =
+ *                                  [frameIndex, ...]; per frame the boxes of the connected components (connectivity 8 or 4) of its hot
+ *                                  macroblocks -- a vector of mvMin half-pels or more, intra where `intra`, an ac_mag of acMin or more --
+ *                                  with minCells cells or more, in raster order of their first cell (leon_pipeline_propose_regions);
+ *                                  regions[i][k] = [frameIndex, x, y, width, height, 0, 0, 0] for k < min(count[i], K = maxBoxes, default
+ *                                  16), a region record for readRegions and gaugeRegions, and an empty box behind; count is not capped.
+ *                                  sources (1 motion, 2 activity, 3): by default every record output the pipeline has, each with its
+ *                                  threshold; a request's fault is its status word, not a throw
  *   p.propagateMaps(window, maps, hops, {stride, planes, elemBytes, fill}) -> {via: Uint8Array [n][mh][mw] (0 fill, 1 forward, 2 backward),
  *                                  status: Int32Array [n]}: dense maps (masks, heatmaps, features) propagated along the motion vectors
  *                                  (leon_pipeline_propagate_maps, opts.motion).  maps = a Buffer / Uint8Array over [slots][planes][mh][mw]
@@ -263,6 +272,17 @@ class LeonPipeline extends EventEmitter {
     const sources = opts.sources === undefined ? this._gaugeSources : opts.sources;
     if (!Number.isInteger(sources)) throw new TypeError('sources: 1 (motion), 2 (activity) or 3');
     return this._p.gaugeRegions(window, Int32Array.from(regions.flat()), sources);
+  }
+  // frames: [frameIndex, ...]: the boxes of what each frame's motion and activity records say moved or was coded anew
+  proposeRegions(window, frames, opts = {}) {
+    if (!Array.isArray(frames) || !frames.every(Number.isInteger)) throw new TypeError('frames: [frameIndex, ...]');
+    const sources = opts.sources === undefined ? this._gaugeSources : opts.sources;
+    const words = [sources, opts.intra ? 1 : 0, (sources & 1) ? opts.mvMin : 0, (sources & 2) ? opts.acMin : 0,
+      opts.connectivity === undefined ? 8 : opts.connectivity, opts.minCells === undefined ? 1 : opts.minCells, opts.maxBoxes === undefined ? 16 : opts.maxBoxes, 0];
+    if (!words.every(Number.isInteger)) {
+      throw new TypeError('sources: 1 (motion), 2 (activity) or 3; mvMin with motion, acMin with activity; connectivity, minCells, maxBoxes: integers');
+    }
+    return this._p.proposeRegions(window, Int32Array.from(frames), Int32Array.from(words));
   }
   // hops: [[targetFrameIndex, dstSlot, fwdSlot, bwdSlot], ...]: each a gather through the target's motion record; maps is written in place
   propagateMaps(window, maps, hops, opts = {}) {

@@ -56,6 +56,7 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_propagate_layout", "leon_pipeline_propagate_record", "leon_pipeline_propagate_maps_device", "leon_pipeline_propagate_maps",
     "leon_pipeline_propagate_kernel",
     "leon_pipeline_gauge_record", "leon_pipeline_gauge_regions_device", "leon_pipeline_gauge_regions", "leon_pipeline_gauge_kernel",
+    "leon_pipeline_propose_record", "leon_pipeline_propose_regions_device", "leon_pipeline_propose_regions", "leon_pipeline_propose_kernel",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -368,6 +369,9 @@ REGION_NO_REFERENCE = 9                      # LEON_REGION_NO_REFERENCE: a carry
 REGION_SLOT = 10                             # LEON_REGION_SLOT: a propagate record's own
 GAUGE_MOTION, GAUGE_ACTIVITY = 1, 2          # LEON_GAUGE_*: the bits of a gauge call's sources
 GAUGE_WORDS = 16                             # int64 words of a gauged record's statistics
+PROPOSE_MOTION, PROPOSE_ACTIVITY = 1, 2      # LEON_PROPOSE_*: the bits of a propose call's sources
+PROPOSE_INTRA = 1                            # LEON_PROPOSE_INTRA: the bit of its flags
+PROPOSE_MAX_BOXES, PROPOSE_MAX_CELLS = 1024, 65536
 
 
 class PipelineWarpRegion(C.Structure):
@@ -400,6 +404,16 @@ class PipelineGaugeConfig(C.Structure):
 class PipelineGaugeRegionsCall(C.Structure):
     _fields_ = [("regions", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("device_stats", C.c_void_p), ("device_status", C.c_void_p), ("stream", C.c_void_p),
                 ("reserved", C.c_uint64 * 3)]
+
+
+class PipelineProposeConfig(C.Structure):
+    _fields_ = [("sources", C.c_int32), ("flags", C.c_int32), ("mv_min", C.c_int32), ("ac_min", C.c_int32), ("connectivity", C.c_int32), ("min_cells", C.c_int32),
+                ("max_boxes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PipelineProposeRegionsCall(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("device_regions", C.c_void_p), ("device_info", C.c_void_p),
+                ("device_count", C.c_void_p), ("device_status", C.c_void_p), ("stream", C.c_void_p), ("reserved", C.c_uint64 * 1)]
 
 
 class PipelinePropagateHop(C.Structure):
@@ -646,6 +660,15 @@ def load():
         lib.leon_pipeline_gauge_regions.argtypes = [C.c_void_p, C.c_int64, P(PipelineGaugeConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         lib.leon_pipeline_gauge_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineGaugeConfig),
                                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_propose_regions"):
+        P = C.POINTER
+        lib.leon_pipeline_propose_record.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineProposeConfig), C.c_int32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_propose_record.restype = C.c_int32
+        lib.leon_pipeline_propose_regions_device.argtypes = [C.c_void_p, C.c_int64, P(PipelineProposeConfig), P(PipelineProposeRegionsCall)]
+        lib.leon_pipeline_propose_regions.argtypes = [C.c_void_p, C.c_int64, P(PipelineProposeConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_propose_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineProposeConfig),
+                                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -1122,6 +1145,103 @@ def gauge_kernel(frame_width, frame_height, mbw, mbh, n_frames, motion, activity
     _chk(load().leon_pipeline_gauge_kernel(int(device_id), int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), mp, ap, C.byref(cfg),
                                            r.ctypes.data if len(r) else None, len(r) if n is None else int(n), stats.ctypes.data, status.ctypes.data))
     return stats[:len(r)], status[:len(r)]
+
+
+def _propose_config(sources, max_boxes, mv_min, ac_min, intra, connectivity, min_cells):
+    """the config of a propose call; sources None: the sources a threshold is given for.  A threshold that is None goes down as 0."""
+    if sources is None:
+        sources = (PROPOSE_MOTION if mv_min is not None else 0) | (PROPOSE_ACTIVITY if ac_min is not None else 0)
+    return PipelineProposeConfig(int(sources), PROPOSE_INTRA if intra else 0, int(mv_min or 0), int(ac_min or 0), int(connectivity), int(min_cells), int(max_boxes), 0)
+
+
+def propose_boxes(frame_width, frame_height, n_frames, motion, activity, frame, max_boxes=16, mv_min=None, ac_min=None, intra=False, connectivity=8, min_cells=1,
+                  sources=None):
+    """The definition of one request of leon_pipeline_propose_regions (include/leon_pipeline.h), written from the header's text and
+    independent of the C code: thresholds on the arrays, then a breadth-first fill in Python integers.  motion[i] = (mv [mbh, mbw, 4]
+    int16, info [mbh, mbw] uint8) and activity[i] = cells [mbh, mbw] of ACTIVITY_CELL of window frame i (as read_motion and
+    read_activity give them; a list the sources do not ask for may be None).  sources None: the sources a threshold is given for.
+    Returns (status, regions, info, count): K rows of 8 words, K rows of [cells, first] (lists of Python integers) and the number of
+    selected components, not capped; (REGION_FRAME, None, None, None) for a frame outside the window."""
+    fw, fh, f, K = int(frame_width), int(frame_height), int(frame), int(max_boxes)
+    if sources is None:
+        sources = (PROPOSE_MOTION if mv_min is not None else 0) | (PROPOSE_ACTIVITY if ac_min is not None else 0)
+    if not 0 <= f < int(n_frames):
+        return REGION_FRAME, None, None, None
+    hot = None
+    if sources & PROPOSE_MOTION:
+        mv, info = np.asarray(motion[f][0]).astype(np.int64), np.asarray(motion[f][1])
+        hot = np.abs(mv).max(axis=2) >= int(mv_min)
+        if intra:
+            hot |= (info & 4) != 0
+    if sources & PROPOSE_ACTIVITY:
+        a = np.asarray(activity[f])["ac_mag"].astype(np.int64) >= int(ac_min)
+        hot = a if hot is None else hot | a
+    mbh, mbw = hot.shape
+    hot = hot & (16 * np.arange(mbw)[None, :] < fw) & (16 * np.arange(mbh)[:, None] < fh)
+    todo = [[bool(v) for v in row] for row in hot]
+    steps = [(-1, 0), (1, 0), (0, -1), (0, 1)] + ([(-1, -1), (1, -1), (-1, 1), (1, 1)] if int(connectivity) == 8 else [])
+    regions, infos, count = [], [], 0
+    for j0 in range(mbh):
+        for i in range(mbw):
+            if not todo[j0][i]:
+                continue
+            todo[j0][i] = False
+            queue, at, lo, hi, j1 = [(i, j0)], 0, i, i, j0
+            while at < len(queue):
+                ci, cj = queue[at]
+                at += 1
+                lo, hi, j1 = min(lo, ci), max(hi, ci), max(j1, cj)
+                for di, dj in steps:
+                    ni, nj = ci + di, cj + dj
+                    if 0 <= ni < mbw and 0 <= nj < mbh and todo[nj][ni]:
+                        todo[nj][ni] = False
+                        queue.append((ni, nj))
+            if len(queue) < int(min_cells):
+                continue
+            if count < K:
+                x, y = 16 * lo, 16 * j0
+                regions.append([f, x, y, min(16 * (hi + 1), fw) - x, min(16 * (j1 + 1), fh) - y, 0, 0, 0])
+                infos.append([len(queue), j0 * mbw + i])
+            count += 1
+    while len(regions) < K:
+        regions.append([f, 0, 0, 0, 0, 0, 0, 0])
+        infos.append([0, -1])
+    return REGION_OK, regions, infos, count
+
+
+def propose_record(frame_width, frame_height, mbw, mbh, n_frames, motion, activity, frame, max_boxes=16, mv_min=None, ac_min=None, intra=False, connectivity=8,
+                   min_cells=1, sources=None, fill=-1, cfg=None):
+    """leon_pipeline_propose_record: the library's CPU evaluation of one request; arguments as propose_boxes's.  Returns (status,
+    regions [K, 8] int32, info [K, 2] int32, count) with `fill` where the library wrote nothing; LeonError where it refuses the call.
+    cfg: a PipelineProposeConfig in place of the keywords."""
+    mp, ap, keep = _gauge_records(motion, activity, mbw, mbh, n_frames)
+    cfg = _propose_config(sources, max_boxes, mv_min, ac_min, intra, connectivity, min_cells) if cfg is None else cfg
+    K = max(1, min(int(cfg.max_boxes), PROPOSE_MAX_BOXES))
+    regions, info, count = np.full((K, 8), fill, dtype=np.int32), np.full((K, 2), fill, dtype=np.int32), np.full(1, fill, dtype=np.int32)
+    st = load().leon_pipeline_propose_record(int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), mp, ap, C.byref(cfg), int(frame), regions.ctypes.data,
+                                             info.ctypes.data, count.ctypes.data)
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return st, regions, info, int(count[0])
+
+
+def propose_kernel(frame_width, frame_height, mbw, mbh, n_frames, motion, activity, frames, max_boxes=16, mv_min=None, ac_min=None, intra=False, connectivity=8,
+                   min_cells=1, sources=None, device_id=0, fill=-1, n=None, cfg=None, with_info=True, with_status=True):
+    """leon_pipeline_propose_kernel: k_propose on records the caller supplies (as propose_boxes's), frames = the requests -> (regions
+    [m, K, 8], info [m, K, 2], count [m], status [m]) int32, pre-filled with `fill`: a refused request keeps it in its rows and its
+    count.  n: the count handed to the library when it is to differ from m = len(frames) (smaller: what lies behind keeps the fill);
+    with_info / with_status False: NULL goes down in their place and they come back as the fill."""
+    mp, ap, keep = _gauge_records(motion, activity, mbw, mbh, n_frames)
+    cfg = _propose_config(sources, max_boxes, mv_min, ac_min, intra, connectivity, min_cells) if cfg is None else cfg
+    K = max(1, min(int(cfg.max_boxes), PROPOSE_MAX_BOXES))
+    fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+    m = max(1, len(fr))
+    regions, info = np.full((m, K, 8), fill, dtype=np.int32), np.full((m, K, 2), fill, dtype=np.int32)
+    count, status = np.full(m, fill, dtype=np.int32), np.full(m, fill, dtype=np.int32)
+    _chk(load().leon_pipeline_propose_kernel(int(device_id), int(frame_width), int(frame_height), int(mbw), int(mbh), int(n_frames), mp, ap, C.byref(cfg),
+                                             fr.ctypes.data if len(fr) else None, len(fr) if n is None else int(n), regions.ctypes.data,
+                                             info.ctypes.data if with_info else None, count.ctypes.data, status.ctypes.data if with_status else None))
+    return regions[:len(fr)], info[:len(fr)], count[:len(fr)], status[:len(fr)]
 
 
 def carry_plan(refs, frames, src):
@@ -1761,6 +1881,9 @@ class Pipeline:
     vectors, on the device and on torch's current stream (carry_box states one hop; carry_regions is the same from host records);
     gauge_regions_device(window, records) returns per box the area-weighted sums of the frame's motion and activity records under it
     (gauge_box states them; gauge_regions is the same from host records): carry_regions_gop's records go in as they are.
+    Proposing boxes (motion=True and / or activity=True): propose_regions_device(window) turns every frame's records into region records on
+    the device -- the boxes of the connected components of the macroblocks that moved, are intra or were coded anew (propose_boxes states
+    them; propose_regions is the same to host arrays) -- which go into gauge_regions_device and resample_regions_device as they are.
     carry_regions_gop(window, boxes, src) carries a detector's boxes on frame `src` to every frame of its GOP, ready for
     resample_regions_device.
     Propagating dense maps (motion=True): propagate_maps_device(window, maps, hops, stride) writes the map of a frame -- a mask, heatmaps,
@@ -2152,6 +2275,58 @@ class Pipeline:
         call = PipelineGaugeRegionsCall(records.data_ptr() if n else None, n, 0, stats.data_ptr(), status.data_ptr(), self._stream_handle(stream))
         _chk(self.lib.leon_pipeline_gauge_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
         return stats.view(-1)[:GAUGE_WORDS * n].view(n, GAUGE_WORDS), status.view(-1)[:n]
+
+    def _propose_config(self, max_boxes, mv_min, ac_min, intra, connectivity, min_cells, sources):
+        """the config of a propose call: sources None = every record output the pipeline has, each with its threshold"""
+        if sources is None:
+            sources = (PROPOSE_MOTION if self.motion_layout is not None else 0) | (PROPOSE_ACTIVITY if self.activity_layout is not None else 0)
+            if (sources & PROPOSE_MOTION and mv_min is None) or (sources & PROPOSE_ACTIVITY and ac_min is None):
+                raise ValueError("propose regions: sources=None reads every record output the pipeline has: give %s" %
+                                 ("mv_min" if sources & PROPOSE_MOTION and mv_min is None else "ac_min"))
+            mv_min, ac_min = (mv_min if sources & PROPOSE_MOTION else None), (ac_min if sources & PROPOSE_ACTIVITY else None)
+        return _propose_config(sources, max_boxes, mv_min, ac_min, intra, connectivity, min_cells)
+
+    def propose_regions(self, window, frames=None, max_boxes=16, mv_min=None, ac_min=None, intra=False, connectivity=8, min_cells=1, sources=None, fill=-1):
+        """leon_pipeline_propose_regions: frames = window frame indices in host memory (None: every frame of the window) -> (regions
+        [F, K, 8], count [F], info [F, K, 2], status [F]) int32 host arrays: per frame the boxes of the connected components of its hot
+        macroblocks -- a vector of mv_min half-pels or more (PROPOSE_MOTION), intra where `intra`, an ac_mag of ac_min or more
+        (PROPOSE_ACTIVITY) -- in raster order of their first cell (propose_boxes states them); count is not capped at K = max_boxes.
+        sources=None: every record output the pipeline has, with a threshold required for each.  A request's fault is its status word
+        (REGION_FRAME), never a LeonError; its rows and count keep `fill`.  Synchronous."""
+        cfg = self._propose_config(max_boxes, mv_min, ac_min, intra, connectivity, min_cells, sources)
+        fr = np.arange(self._delivered_n(window), dtype=np.int32) if frames is None else np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        m, K = max(1, len(fr)), max(1, min(int(cfg.max_boxes), PROPOSE_MAX_BOXES))
+        regions, info = np.full((m, K, 8), fill, dtype=np.int32), np.full((m, K, 2), fill, dtype=np.int32)
+        count, status = np.full(m, fill, dtype=np.int32), np.full(m, fill, dtype=np.int32)
+        _chk(self.lib.leon_pipeline_propose_regions(self.h, int(window), C.byref(cfg), fr.ctypes.data if len(fr) else None, len(fr), regions.ctypes.data, info.ctypes.data,
+                                                    count.ctypes.data, status.ctypes.data))
+        return regions[:len(fr)], count[:len(fr)], info[:len(fr)], status[:len(fr)]
+
+    def propose_regions_device(self, window, frames=None, max_boxes=16, mv_min=None, ac_min=None, intra=False, connectivity=8, min_cells=1, sources=None, stream=None):
+        """leon_pipeline_propose_regions_device: the same with everything in DEVICE memory -- frames: a contiguous CUDA int32 torch
+        tensor [F] of window frame indices (None: every frame of the window) -- queued on `stream` (a torch.cuda.Stream; None: torch's
+        current stream) with carry_regions_device's ordering: NO host synchronisation.  Returns (regions [F, K, 8], count [F], info
+        [F, K, 2], status [F]) int32 CUDA tensors: regions goes into gauge_regions_device / resample_regions_device as it is (the rows
+        behind count come back as REGION_BOX); a request whose status is not 0 has nothing of its rows and count written."""
+        import torch
+        dev = self.device_id
+        cfg = self._propose_config(max_boxes, mv_min, ac_min, intra, connectivity, min_cells, sources)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        if frames is None:
+            n = self._delivered_n(window)
+            with torch.cuda.stream(stream):
+                frames = torch.arange(n, dtype=torch.int32, device="cuda:%d" % dev)
+        if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.int32 and frames.dim() == 1 and frames.is_contiguous()):
+            raise ValueError("frames: a contiguous CUDA int32 tensor [F]")
+        n = int(frames.shape[0])
+        _device_tensor_check("frames", frames, torch.int32, n, dev, words=True)
+        m, K = max(1, n), max(1, min(int(cfg.max_boxes), PROPOSE_MAX_BOXES))
+        regions, count, info, status = _empty_where_none(stream, dev, [(None, (m, K, 8), torch.int32), (None, m, torch.int32), (None, (m, K, 2), torch.int32),
+                                                                       (None, m, torch.int32)])
+        call = PipelineProposeRegionsCall(frames.data_ptr() if n else None, n, 0, regions.data_ptr(), info.data_ptr(), count.data_ptr(), status.data_ptr(),
+                                          self._stream_handle(stream))
+        _chk(self.lib.leon_pipeline_propose_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        return regions[:n], count[:n], info[:n], status[:n]
 
     def _propagate_check(self, maps, stride):
         lay = propagate_layout(self.info.frame_width, self.info.frame_height, stride, maps.shape[1] if len(maps.shape) == 4 else 0, self._elem_bytes(maps))

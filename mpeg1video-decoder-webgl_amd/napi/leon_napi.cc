@@ -906,6 +906,48 @@ napi_value PipeGaugeRegions(napi_env env, napi_callback_info info)
     return o;
 }
 
+// p.proposeRegions(window, frames, config) -> {regions: Int32Array [n][K][8], count: Int32Array [n], info: Int32Array [n][K][2],
+// status: Int32Array [n] (LEON_REGION_*; not 0: the request's rows and count are 0)}: leon_pipeline_propose_regions (opts.motion and / or
+// opts.activity).  frames: an Int32Array of n window frame indices; config: an Int32Array of the 8 words of leon_pipeline_propose_config.
+napi_value PipeProposeRegions(napi_env env, napi_callback_info info)
+{
+    size_t argc = 3;
+    napi_value argv[3];
+    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
+    if (!h) return nullptr;
+    int64_t w = -1;
+    napi_typedarray_type tt[2];
+    size_t len[2] = {0, 0}, off = 0;
+    void* words[2] = {nullptr, nullptr};
+    napi_value ab;
+    bool is_ta[2] = {false, false};
+    if (argc < 3 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta[0]) != napi_ok || !is_ta[0] ||
+        napi_is_typedarray(env, argv[2], &is_ta[1]) != napi_ok || !is_ta[1] || napi_get_typedarray_info(env, argv[1], &tt[0], &len[0], &words[0], &ab, &off) != napi_ok ||
+        napi_get_typedarray_info(env, argv[2], &tt[1], &len[1], &words[1], &ab, &off) != napi_ok || tt[0] != napi_int32_array || tt[1] != napi_int32_array || len[1] != 8) {
+        napi_throw_type_error(env, nullptr, "proposeRegions(window, Int32Array of frame indices, Int32Array of the config's 8 words)");
+        return nullptr;
+    }
+    leon_pipeline_propose_config cfg;
+    memcpy(&cfg, words[1], sizeof cfg);
+    const size_t n = len[0], m = n >= 1 && n <= 65535 ? n : 1;          // (a count or a K the library refuses allocates nothing to speak of here)
+    const size_t K = cfg.max_boxes >= 1 && cfg.max_boxes <= 1024 ? (size_t)cfg.max_boxes : 1;
+    const size_t elems[4] = {m * K * 8, m, m * K * 2, m};
+    const char* names[4] = {"regions", "count", "info", "status"};
+    napi_value o, abs[4], ta[4];
+    void* data[4] = {nullptr, nullptr, nullptr, nullptr};
+    NAPI_OK(napi_create_object(env, &o));
+    for (int i = 0; i < 4; i++) {
+        NAPI_OK(napi_create_arraybuffer(env, elems[i] * 4, &data[i], &abs[i]));          // (zeros: what a refused request keeps)
+        NAPI_OK(napi_create_typedarray(env, napi_int32_array, elems[i], abs[i], 0, &ta[i]));
+    }
+    const int rc = leon_pipeline_propose_regions(h->p, w, &cfg, static_cast<const int32_t*>(words[0]), (int32_t)std::min<size_t>(n, 65536),
+                                                 static_cast<leon_pipeline_region*>(data[0]), static_cast<int32_t*>(data[2]), static_cast<int32_t*>(data[1]),
+                                                 static_cast<int32_t*>(data[3]));
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    for (int i = 0; i < 4; i++) NAPI_OK(napi_set_named_property(env, o, names[i], ta[i]));
+    return o;
+}
+
 // p.propagateMaps(window, maps, hops, stride, planes, elemBytes, fill) -> {via: Uint8Array [n][mh][mw] (0 fill, 1 forward, 2 backward),
 // status: Int32Array [n] (LEON_REGION_*; not 0: the record's slot and via map are left as they were, via zero)}:
 // leon_pipeline_propagate_maps (opts.motion).  maps: a Uint8Array over the bytes of [slots][planes][mh][mw], contiguous, WRITTEN IN
@@ -1224,7 +1266,7 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
     const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readActivity", PipeReadActivity}, {"readResidual", PipeReadResidual},{"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"gaugeRegions", PipeGaugeRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
+        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readActivity", PipeReadActivity}, {"readResidual", PipeReadResidual},{"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"gaugeRegions", PipeGaugeRegions}, {"proposeRegions", PipeProposeRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
     for (auto& m : methods) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));

@@ -22,8 +22,15 @@ read and write a second beside the rate of a device-to-device copy of as many by
 had before: motion_view, a per-cell index grid built with torch ops and a gather, hop by hop in the same order, whose result is
 compared with the kernel's byte for byte.  Prints one JSON line.
 
+--propose: boxes proposed instead (leon_pipeline_propose_regions; k_propose): one propose_regions_device call over EVERY frame of the
+window with both sources (--mv-min, --ac-min, K = --max-boxes, connectivity 8), from the enqueue to the synchronisation of the
+stream; the first --propose-check frames against propose_boxes on the records read back; then the [F, K, 8] result as it is into
+gauge_regions_device in the same job (word 0 = w * h for the first count rows, REGION_BOX behind).  The bytes the kernel must read --
+F x (8 + 1 + 8) x the macroblocks of a frame -- are set against the time.  Prints one JSON line.
+
   python tools/carry_bench.py [--boxes 4096] [--reps 20] [--max-box 256] [--host-boxes N] [--gauge [--gauge-check 64]]
-  python tools/carry_bench.py --maps [--reps 20]"""
+  python tools/carry_bench.py --maps [--reps 20]
+  python tools/carry_bench.py --propose [--reps 20] [--mv-min 2] [--ac-min 256] [--max-boxes 16] [--propose-check 8]"""
 import argparse
 import json
 import os
@@ -130,11 +137,61 @@ def maps_bench(a, pipe, window, frames):
     print(json.dumps(result))
 
 
+def propose_bench(a, pipe, window, frames):
+    import numpy as np
+    import torch
+    import leon_ctypes as L
+    fw, fh, n = pipe.info.frame_width, pipe.info.frame_height, len(frames)
+    kw = dict(max_boxes=a.max_boxes, mv_min=a.mv_min, ac_min=a.ac_min, connectivity=8)
+    st = torch.cuda.Stream()
+    us, enq = [], []
+    with torch.cuda.stream(st):
+        d_frames = torch.arange(n, dtype=torch.int32, device="cuda")
+        for i in range(a.reps + 2):
+            st.synchronize()
+            t0 = time.perf_counter()
+            regions, count, info, status = pipe.propose_regions_device(window, d_frames, **kw)
+            t1 = time.perf_counter()
+            st.synchronize()
+            t2 = time.perf_counter()
+            if i >= 2:
+                us.append((t2 - t0) * 1e6)
+                enq.append((t1 - t0) * 1e6)
+        stats, gstatus = pipe.gauge_regions_device(window, regions)
+    st.synchronize()
+    h_regions, h_count, h_info, h_status = regions.cpu().numpy(), count.cpu().numpy(), info.cpu().numpy(), status.cpu().numpy()
+    checked = min(n, a.propose_check)
+    motion, activity = [None] * n, [None] * n
+    for f in range(checked):
+        motion[f], activity[f] = pipe.read_motion(window, f)[:2], pipe.read_activity(window, f)[0]
+        s_, r_, i_, c_ = L.propose_boxes(fw, fh, n, motion, activity, f, **kw)
+        if s_ != h_status[f] or c_ != h_count[f] or r_ != h_regions[f].tolist() or i_ != h_info[f].tolist():
+            raise RuntimeError("the device and propose_boxes disagree in frame %d" % f)
+    if (h_status != 0).any():
+        raise RuntimeError("a frame of the window was refused")
+    used = (np.arange(a.max_boxes)[None, :] < h_count[:, None]).reshape(-1)
+    rows, h_stats, h_gstatus = h_regions.reshape(-1, 8), stats.cpu().numpy(), gstatus.cpu().numpy()
+    if not ((h_gstatus[used] == 0).all() and (h_gstatus[~used] == L.REGION_BOX).all() and (h_stats[used, 0] == rows[used, 3].astype(np.int64) * rows[used, 4]).all()):
+        raise RuntimeError("gauge_regions_device on the proposed rows: word 0 or the status words are not what the rows say")
+    mbs = pipe.motion_layout.mb_width * pipe.motion_layout.mb_height
+    med = statistics.median(us)
+    print(json.dumps({"propose": {"frames": n, "macroblocks": mbs, "config": kw, "us": round(med, 1), "min_us": round(min(us), 1), "enqueue_us": round(statistics.median(enq), 1),
+                                  "reps": a.reps, "bytes_read": n * 17 * mbs, "read_GBps_of_the_call": round(n * 17 * mbs / med / 1e3, 1),
+                                  "boxes": int(np.minimum(h_count, a.max_boxes).sum()), "components": int(h_count.sum()), "frames_over_K": int((h_count > a.max_boxes).sum()),
+                                  "largest_count": int(h_count.max()), "hot_cells_in_boxes": int(h_info[..., 0].sum()), "checked_frames": checked,
+                                  "gauged_rows_ok": int(used.sum()), "gauged_rows_region_box": int((~used).sum())}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--maps", action="store_true", help="dense maps (k_propagate) instead of boxes")
     ap.add_argument("--gauge", action="store_true", help="the carried boxes through k_gauge in the same job, sources 1, 2 and 3")
     ap.add_argument("--gauge-check", type=int, default=64, help="records of each gauge call compared with gauge_box")
+    ap.add_argument("--propose", action="store_true", help="boxes proposed from the records of every frame (k_propose) instead of boxes carried")
+    ap.add_argument("--mv-min", type=int, default=2)
+    ap.add_argument("--ac-min", type=int, default=256)
+    ap.add_argument("--max-boxes", type=int, default=16)
+    ap.add_argument("--propose-check", type=int, default=8, help="frames compared with propose_boxes")
     ap.add_argument("--boxes", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--max-box", type=int, default=256)
@@ -153,13 +210,13 @@ def main():
         held["window"], held["frames"] = window, list(frames)
         delivered.set()
         return False
-    pipe = L.Pipeline(data, on_window=on_window, motion=True, activity=a.gauge, gops_per_window=stream_1080p.VARIED_GOPS, gpu_parser=True, parser_threads=16)
+    pipe = L.Pipeline(data, on_window=on_window, motion=True, activity=a.gauge or a.propose, gops_per_window=stream_1080p.VARIED_GOPS, gpu_parser=True, parser_threads=16)
     try:
         if not delivered.wait(300):
             raise RuntimeError("no window was delivered: %s" % (pipe.error,))
         window, frames = held["window"], held["frames"]
-        if a.maps:
-            maps_bench(a, pipe, window, frames)
+        if a.maps or a.propose:
+            (maps_bench if a.maps else propose_bench)(a, pipe, window, frames)
             pipe.release_window(window)
             pipe.wait()
             return
