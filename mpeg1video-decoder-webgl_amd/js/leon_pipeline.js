@@ -105,6 +105,30 @@
 const path = require('path');
 const EventEmitter = require('events');
 
+// an option that is a name of `table` or already its integer (anything else goes on as it is, for the addon or the caller to refuse); absent: 0
+function named(value, table, text) {
+  if (value === undefined) return 0;
+  if (typeof value === 'string') {
+    if (!(value in table)) throw new TypeError(text);
+    return table[value];
+  }
+  return value;
+}
+// v: n integers (n undefined: any number of them), or TypeError(text); an undefined v is `absent` where one is given
+function ints(v, n, text, absent) {
+  if (v === undefined && absent) return absent;
+  if (!Array.isArray(v) || (n !== undefined && v.length !== n) || !v.every(Number.isInteger)) throw new TypeError(text);
+  return v;
+}
+// a record list [[k integers], ...] as the Int32Array the addon takes, or TypeError(text)
+function rows(value, k, text) {
+  if (!Array.isArray(value) || !value.every((r) => Array.isArray(r) && r.length === k && r.every(Number.isInteger))) throw new TypeError(text);
+  return Int32Array.from(value.flat());
+}
+const OUTPUTS = { rgba: 1, ycbcr: 2, both: 3, tensor: 16, 'rgba+tensor': 17, 'ycbcr+tensor': 18, all: 19 };
+const FILTERS = { triangle: 0, bicubic: 3 };
+const REGIONS = 'regions: [[frameIndex, x, y, width, height], ...]';
+
 class LeonPipeline extends EventEmitter {
   constructor(stream, opts) {
     super();
@@ -113,48 +137,24 @@ class LeonPipeline extends EventEmitter {
     if (!Buffer.isBuffer(stream)) stream = Buffer.from(stream.buffer, stream.byteOffset, stream.byteLength);
     this.autoRelease = opts.autoRelease !== false;
     this.ended = false;
-    const outputs = { rgba: 1, ycbcr: 2, both: 3, tensor: 16, 'rgba+tensor': 17, 'ycbcr+tensor': 18, all: 19 };
-    const dtypes = { float16: 1, bfloat16: 2, float32: 3, uint8: 8 };
-    const layouts = { chw: 0, hwc: 1 };
-    const filters = { triangle: 0, bicubic: 3 };
-    let output = opts.output === undefined ? 0 : opts.output;
-    if (typeof output === 'string') {
-      if (!(output in outputs)) throw new TypeError("output: 'rgba', 'ycbcr', 'both', 'tensor', 'rgba+tensor', 'ycbcr+tensor' or 'all'");
-      output = outputs[output];
-    }
-    if (opts.motion) output = (output || outputs.rgba) | 32;          // LEON_PIPELINE_OUTPUT_MOTION beside whatever output resolves to
-    if (opts.activity) output = (output || outputs.rgba) | 128;       // LEON_PIPELINE_OUTPUT_ACTIVITY likewise
-    if (opts.residual) output = (output || outputs.rgba) | 512;       // LEON_PIPELINE_OUTPUT_RESIDUAL likewise
+    let output = named(opts.output, OUTPUTS, "output: 'rgba', 'ycbcr', 'both', 'tensor', 'rgba+tensor', 'ycbcr+tensor' or 'all'");
+    if (opts.motion) output = (output || OUTPUTS.rgba) | 32;          // LEON_PIPELINE_OUTPUT_MOTION beside whatever output resolves to
+    if (opts.activity) output = (output || OUTPUTS.rgba) | 128;       // LEON_PIPELINE_OUTPUT_ACTIVITY likewise
+    if (opts.residual) output = (output || OUTPUTS.rgba) | 512;       // LEON_PIPELINE_OUTPUT_RESIDUAL likewise
     this._gaugeSources = (opts.motion ? 1 : 0) | (opts.activity ? 2 : 0);          // what gaugeRegions reads without opts.sources: every record output there is
-    let tensorDtype = opts.tensorDtype === undefined ? 0 : opts.tensorDtype;
-    if (typeof tensorDtype === 'string') {
-      if (!(tensorDtype in dtypes)) throw new TypeError("tensorDtype: 'float16', 'bfloat16', 'float32' or 'uint8'");
-      tensorDtype = dtypes[tensorDtype];
-    }
-    let tensorLayout = opts.tensorLayout === undefined ? 0 : opts.tensorLayout;
-    if (typeof tensorLayout === 'string') {
-      if (!(tensorLayout in layouts)) throw new TypeError("tensorLayout: 'chw' or 'hwc'");
-      tensorLayout = layouts[tensorLayout];
-    }
-    let tensorFilter = opts.tensorFilter === undefined ? 0 : opts.tensorFilter;
-    if (typeof tensorFilter === 'string') {
-      if (!(tensorFilter in filters)) throw new TypeError("tensorFilter: 'triangle' or 'bicubic'");
-      tensorFilter = filters[tensorFilter];
-    }
+    const tensorDtype = named(opts.tensorDtype, { float16: 1, bfloat16: 2, float32: 3, uint8: 8 }, "tensorDtype: 'float16', 'bfloat16', 'float32' or 'uint8'");
+    const tensorLayout = named(opts.tensorLayout, { chw: 0, hwc: 1 }, "tensorLayout: 'chw' or 'hwc'");
+    const tensorFilter = named(opts.tensorFilter, FILTERS, "tensorFilter: 'triangle' or 'bicubic'");
     // tensorSize [h, w] (, tensorCrop [x, y, w, h] in frame pixels): the tensors resampled on the device to a model's input size
-    const ints = (v, n, what) => {
-      if (v === undefined || v === null) return new Array(n).fill(0);
-      if (!Array.isArray(v) || v.length !== n || !v.every(Number.isInteger)) throw new TypeError(what);
-      return v;
-    };
-    const [tensorOutHeight, tensorOutWidth] = ints(opts.tensorSize, 2, 'tensorSize: [height, width]');
-    const [tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight] = ints(opts.tensorCrop, 4, 'tensorCrop: [x, y, width, height]');
+    const list = (v, n, text) => ints(v === null ? undefined : v, n, text, new Array(n).fill(0));          // (absent or null: zeros)
+    const [tensorOutHeight, tensorOutWidth] = list(opts.tensorSize, 2, 'tensorSize: [height, width]');
+    const [tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight] = list(opts.tensorCrop, 4, 'tensorCrop: [x, y, width, height]');
     const resize = { tensorOutHeight, tensorOutWidth, tensorCropX, tensorCropY, tensorCropWidth, tensorCropHeight, tensorFilter };
     // tensorCanvas [h, w], tensorOrigin [x, y], tensorPadValue [r, g, b]: the image in a padded canvas; tensorLetterbox [h, w] derives them
-    const [tensorCanvasHeight, tensorCanvasWidth] = ints(opts.tensorCanvas, 2, 'tensorCanvas: [height, width]');
-    const [tensorOriginX, tensorOriginY] = ints(opts.tensorOrigin, 2, 'tensorOrigin: [x, y]');
-    const [tensorPadR, tensorPadG, tensorPadB] = ints(opts.tensorPadValue, 3, 'tensorPadValue: [r, g, b]');
-    const [tensorLetterboxHeight, tensorLetterboxWidth] = ints(opts.tensorLetterbox, 2, 'tensorLetterbox: [height, width]');
+    const [tensorCanvasHeight, tensorCanvasWidth] = list(opts.tensorCanvas, 2, 'tensorCanvas: [height, width]');
+    const [tensorOriginX, tensorOriginY] = list(opts.tensorOrigin, 2, 'tensorOrigin: [x, y]');
+    const [tensorPadR, tensorPadG, tensorPadB] = list(opts.tensorPadValue, 3, 'tensorPadValue: [r, g, b]');
+    const [tensorLetterboxHeight, tensorLetterboxWidth] = list(opts.tensorLetterbox, 2, 'tensorLetterbox: [height, width]');
     const tensorOriginSet = opts.tensorOrigin === undefined || opts.tensorOrigin === null ? 0 : 1;
     Object.assign(resize, { tensorCanvasHeight, tensorCanvasWidth, tensorOriginX, tensorOriginY, tensorOriginSet, tensorPadR, tensorPadG, tensorPadB,
       tensorLetterboxHeight, tensorLetterboxWidth });
@@ -216,83 +216,53 @@ class LeonPipeline extends EventEmitter {
   // regions: [[frameIndex, x, y, width, height], ...] of a delivered window's full-resolution frames, resampled to opts.size [h, w]
   readRegions(window, regions, opts) {
     opts = opts || {};
-    const filters = { triangle: 0, bicubic: 3 };
-    let filter = opts.filter === undefined ? 0 : opts.filter;
-    if (typeof filter === 'string') {
-      if (!(filter in filters)) throw new TypeError("filter: 'triangle' or 'bicubic'");
-      filter = filters[filter];
-    }
-    const size = opts.size;
-    if (!Array.isArray(size) || size.length !== 2 || !size.every(Number.isInteger)) throw new TypeError('size: [height, width]');
-    if (!Array.isArray(regions) || !regions.every((r) => Array.isArray(r) && r.length === 5 && r.every(Number.isInteger))) {
-      throw new TypeError('regions: [[frameIndex, x, y, width, height], ...]');
-    }
-    const boxes = Int32Array.from(regions.flat());
+    const filter = named(opts.filter, FILTERS, "filter: 'triangle' or 'bicubic'");
+    const size = ints(opts.size, 2, 'size: [height, width]');
+    const boxes = rows(regions, 5, REGIONS);
     if (opts.fit === undefined && opts.anchor === undefined && opts.padValue === undefined) return this._p.readRegions(window, boxes, size[0], size[1], filter);
-    const fits = { stretch: 0, letterbox: 1 }, anchors = { centre: 0, center: 0, top_left: 1 };
-    let fit = opts.fit === undefined ? 0 : opts.fit, anchor = opts.anchor === undefined ? 0 : opts.anchor;
-    if (typeof fit === 'string') {
-      if (!(fit in fits)) throw new TypeError("fit: 'stretch' or 'letterbox'");
-      fit = fits[fit];
-    }
-    if (typeof anchor === 'string') {
-      if (!(anchor in anchors)) throw new TypeError("anchor: 'centre' or 'top_left'");
-      anchor = anchors[anchor];
-    }
-    const pad = opts.padValue === undefined ? [0, 0, 0] : opts.padValue;
-    if (!Array.isArray(pad) || pad.length !== 3 || !pad.every(Number.isInteger)) throw new TypeError('padValue: [r, g, b]');
+    const fit = named(opts.fit, { stretch: 0, letterbox: 1 }, "fit: 'stretch' or 'letterbox'");
+    const anchor = named(opts.anchor, { centre: 0, center: 0, top_left: 1 }, "anchor: 'centre' or 'top_left'");
+    const pad = ints(opts.padValue, 3, 'padValue: [r, g, b]', [0, 0, 0]);
     if (!Number.isInteger(fit) || !Number.isInteger(anchor)) throw new TypeError('fit, anchor: a name or an integer');
     return this._p.readRegions(window, boxes, size[0], size[1], filter, fit, anchor, pad[0], pad[1], pad[2]);
   }
   // regions: [[frameIndex, [a00, a01, tx, a10, a11, ty]], ...], Q16 integers: rotated boxes and affine crops sampled into opts.size [h, w]
   readWarpRegions(window, regions, opts) {
     opts = opts || {};
-    const size = opts.size;
-    if (!Array.isArray(size) || size.length !== 2 || !size.every(Number.isInteger)) throw new TypeError('size: [height, width]');
-    if (!Array.isArray(regions) || !regions.every((r) => Array.isArray(r) && r.length === 2 && Number.isInteger(r[0]) && Array.isArray(r[1]) && r[1].length === 6 &&
-        r[1].every(Number.isInteger))) {
-      throw new TypeError('regions: [[frameIndex, [a00, a01, tx, a10, a11, ty]], ...] (Q16 integers)');
-    }
-    const pad = opts.padValue === undefined ? [0, 0, 0] : opts.padValue;
-    if (!Array.isArray(pad) || pad.length !== 3 || !pad.every(Number.isInteger)) throw new TypeError('padValue: [r, g, b]');
-    return this._p.readWarpRegions(window, Int32Array.from(regions.flat(2)), size[0], size[1], pad[0], pad[1], pad[2]);
+    const size = ints(opts.size, 2, 'size: [height, width]');
+    const text = 'regions: [[frameIndex, [a00, a01, tx, a10, a11, ty]], ...] (Q16 integers)';
+    if (!Array.isArray(regions) || !regions.every((r) => Array.isArray(r) && r.length === 2 && Array.isArray(r[1]))) throw new TypeError(text);
+    const words = rows(regions.map((r) => [r[0]].concat(r[1])), 7, text);          // (the addon's record: the index and the matrix, 7 words)
+    const pad = ints(opts.padValue, 3, 'padValue: [r, g, b]', [0, 0, 0]);
+    return this._p.readWarpRegions(window, words, size[0], size[1], pad[0], pad[1], pad[2]);
   }
   // records: [[frameIndex, x, y, width, height, targetFrameIndex], ...]: one hop each along the window's motion records
   carryRegions(window, records) {
-    if (!Array.isArray(records) || !records.every((r) => Array.isArray(r) && r.length === 6 && r.every(Number.isInteger))) {
-      throw new TypeError('records: [[frameIndex, x, y, width, height, targetFrameIndex], ...]');
-    }
-    return this._p.carryRegions(window, Int32Array.from(records.flat()));
+    return this._p.carryRegions(window, rows(records, 6, 'records: [[frameIndex, x, y, width, height, targetFrameIndex], ...]'));
   }
   // regions: [[frameIndex, x, y, width, height], ...]: the motion and activity records of each box's frame summed under the box
   gaugeRegions(window, regions, opts = {}) {
-    if (!Array.isArray(regions) || !regions.every((r) => Array.isArray(r) && r.length === 5 && r.every(Number.isInteger))) {
-      throw new TypeError('regions: [[frameIndex, x, y, width, height], ...]');
-    }
+    const boxes = rows(regions, 5, REGIONS);
     const sources = opts.sources === undefined ? this._gaugeSources : opts.sources;
     if (!Number.isInteger(sources)) throw new TypeError('sources: 1 (motion), 2 (activity) or 3');
-    return this._p.gaugeRegions(window, Int32Array.from(regions.flat()), sources);
+    return this._p.gaugeRegions(window, boxes, sources);
   }
   // frames: [frameIndex, ...]: the boxes of what each frame's motion and activity records say moved or was coded anew
   proposeRegions(window, frames, opts = {}) {
-    if (!Array.isArray(frames) || !frames.every(Number.isInteger)) throw new TypeError('frames: [frameIndex, ...]');
+    ints(frames, undefined, 'frames: [frameIndex, ...]');
     const sources = opts.sources === undefined ? this._gaugeSources : opts.sources;
-    const words = [sources, opts.intra ? 1 : 0, (sources & 1) ? opts.mvMin : 0, (sources & 2) ? opts.acMin : 0,
-      opts.connectivity === undefined ? 8 : opts.connectivity, opts.minCells === undefined ? 1 : opts.minCells, opts.maxBoxes === undefined ? 16 : opts.maxBoxes, 0];
-    if (!words.every(Number.isInteger)) {
-      throw new TypeError('sources: 1 (motion), 2 (activity) or 3; mvMin with motion, acMin with activity; connectivity, minCells, maxBoxes: integers');
-    }
+    const words = ints([sources, opts.intra ? 1 : 0, (sources & 1) ? opts.mvMin : 0, (sources & 2) ? opts.acMin : 0, opts.connectivity === undefined ? 8 : opts.connectivity,
+      opts.minCells === undefined ? 1 : opts.minCells, opts.maxBoxes === undefined ? 16 : opts.maxBoxes, 0], 8,
+    'sources: 1 (motion), 2 (activity) or 3; mvMin with motion, acMin with activity; connectivity, minCells, maxBoxes: integers');
     return this._p.proposeRegions(window, Int32Array.from(frames), Int32Array.from(words));
   }
   // hops: [[targetFrameIndex, dstSlot, fwdSlot, bwdSlot], ...]: each a gather through the target's motion record; maps is written in place
   propagateMaps(window, maps, hops, opts = {}) {
     if (!(maps instanceof Uint8Array)) throw new TypeError('maps: a Buffer or Uint8Array over [slots][planes][mh][mw]');
-    if (!Array.isArray(hops) || !hops.every((r) => Array.isArray(r) && r.length === 4 && r.every(Number.isInteger))) {
-      throw new TypeError('hops: [[targetFrameIndex, dstSlot, fwdSlot, bwdSlot], ...]');
-    }
+    const words = rows(hops, 4, 'hops: [[targetFrameIndex, dstSlot, fwdSlot, bwdSlot], ...]');
     const { stride = 1, planes = 1, elemBytes = 1, fill = 0 } = opts;
-    if (![stride, planes, elemBytes, fill].every(Number.isInteger)) throw new TypeError('opts: {stride, planes, elemBytes, fill} are integers');
-    return this._p.propagateMaps(window, maps, Int32Array.from(hops.flat()), stride, planes, elemBytes, fill >>> 0);
+    ints([stride, planes, elemBytes, fill], 4, 'opts: {stride, planes, elemBytes, fill} are integers');
+    return this._p.propagateMaps(window, maps, words, stride, planes, elemBytes, fill >>> 0);
   }
   releaseWindow(window) { this._p.releaseWindow(window); }
   stats() { return this._p.stats(); }

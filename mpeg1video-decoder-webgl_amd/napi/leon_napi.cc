@@ -11,6 +11,11 @@
 //   h.submitSparse({type, outSlot, refFwdSlot, refBwdSlot, grpOff, entries, nEntries, qscale, intra,
 //                   repadd, mvFwd, mvBwd, mbDir});             // the same through the sparse boundary
 //   h.convertRGBA(slot, flavour) -> Uint8Array; h.readPlanes(slot) -> {y, cb, cr}; h.sync(); h.destroy();
+//
+// Every method is the same few steps, and each step is written once below: the argument reader (Args / Call<H>: the receiver's
+// handle, typed getters, one usage text thrown as a TypeError), the makers of what goes back (make_array, make_object, set_numbers)
+// and, for a pipeline, the delivered-frame lookup, the record-count rule, the region batch's size and the tensor-output requirement.
+// DESIGN.md ("The Node addon") adds a method in five lines; tests/node_*_pins*.js pin every refusal's class and text.
 #include <node_api.h>
 #include <cstdint>
 #include <cstdio>
@@ -19,16 +24,40 @@
 #include "../../include/leon_pipeline.h"
 #include "../../include/leon_vlc.h"
 #include <algorithm>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <vector>
 
 namespace {
 
+// the decoder handle of create()
 struct Handle {
     leon_decoder* d;
     leon_config cfg;
 };
+
+// the pipeline handle of createPipeline() ("the native pipeline" below)
+struct PipeHandle {
+    leon_pipeline* p = nullptr;
+    napi_threadsafe_function tsfn = nullptr;
+    napi_ref stream_ref = nullptr;          // keeps the stream's Buffer alive: the pipeline reads it in place
+    std::mutex mu;
+    std::map<int64_t, std::vector<leon_pipeline_frame>> out;   // delivered, not yet released
+    leon_pipeline_info info{};
+    leon_pipeline_tensor_geometry tensor_geom{};      // all 0 without tensor output
+    leon_pipeline_tensor_shape tensor_shape{};        // the same
+    leon_pipeline_tensor_canvas tensor_canvas{};      // the same
+    int64_t last_window = -1;               // notify thread, under mu
+    int64_t floor = 0;                      // JavaScript thread: the first window of the latest seek
+    bool seeked = false;
+};
+
+// a handle lives until its destroy(); what a method of a dead one throws unless it says otherwise
+bool live(const Handle* h) { return h->d != nullptr; }
+bool live(const PipeHandle* h) { return h->p != nullptr; }
+const char* dead_text(const Handle*) { return "leon: decoder handle is destroyed or invalid"; }
+const char* dead_text(const PipeHandle*) { return "pipeline is destroyed"; }
 
 #define NAPI_OK(call)                                                      \
     do {                                                                   \
@@ -46,54 +75,206 @@ napi_value throw_leon(napi_env env, int rc)
     return nullptr;
 }
 
+// ---- the argument reader ---------------------------------------------------------------------------------
+// The arguments of one call.  A getter that does not find what it asks for notes it; bad() then throws the call's usage text as a
+// TypeError, once, whichever getter it was.  Arguments that were not passed are undefined, which no getter takes, so "too few
+// arguments" needs no test of its own.
+struct Args {
+    napi_env env;
+    const char* usage;
+    size_t argc = 10;
+    napi_value argv[10] = {};
+    napi_value self = nullptr;
+    bool failed = false, thrown = false;
+
+    Args(napi_env env, napi_callback_info info, const char* usage) : env(env), usage(usage)
+    {
+        if (napi_get_cb_info(env, info, &argc, argv, &self, nullptr) != napi_ok) {
+            napi_throw_error(env, nullptr, "N-API call failed: napi_get_cb_info");
+            thrown = true;
+        }
+    }
+    // true: the call is refused -- something has been thrown already, or a getter failed or `also` holds and the usage text is thrown now
+    bool bad(bool also = false)
+    {
+        if (!thrown && (failed || also)) {
+            napi_throw_type_error(env, nullptr, usage);
+            thrown = true;
+        }
+        return thrown;
+    }
+    bool absent(size_t k) const          // undefined or null
+    {
+        napi_valuetype t = napi_undefined;
+        napi_typeof(env, argv[k], &t);
+        return t == napi_undefined || t == napi_null;
+    }
+    int64_t i64(size_t k) { int64_t v = -1; failed |= napi_get_value_int64(env, argv[k], &v) != napi_ok; return v; }
+    int32_t i32(size_t k) { int32_t v = -1; failed |= napi_get_value_int32(env, argv[k], &v) != napi_ok; return v; }
+    uint32_t u32(size_t k) { uint32_t v = 0; failed |= napi_get_value_uint32(env, argv[k], &v) != napi_ok; return v; }
+    double f64(size_t k) { double v = 0; failed |= napi_get_value_double(env, argv[k], &v) != napi_ok; return v; }
+    // (with a default: whatever is no number, or no boolean, counts as not given)
+    int32_t i32(size_t k, int32_t dflt) { napi_get_value_int32(env, argv[k], &dflt); return dflt; }
+    bool flag(size_t k, bool dflt) { napi_get_value_bool(env, argv[k], &dflt); return dflt; }
+    // v as a typed array of `kind`: its storage and its element count
+    static bool typed(napi_env env, napi_value v, napi_typedarray_type kind, void** data, size_t* len)
+    {
+        bool is_ta = false;
+        napi_typedarray_type t;
+        return napi_is_typedarray(env, v, &is_ta) == napi_ok && is_ta && napi_get_typedarray_info(env, v, &t, len, data, nullptr, nullptr) == napi_ok && t == kind;
+    }
+    void* array(size_t k, napi_typedarray_type kind, size_t* len)
+    {
+        void* data = nullptr;
+        if (typed(env, argv[k], kind, &data, len)) return data;
+        failed = true;
+        *len = 0;
+        return nullptr;
+    }
+    // an Int32Array of rows of `words` words: the words and the number of rows
+    const int32_t* rows(size_t k, size_t words, size_t* n)
+    {
+        size_t len = 0;
+        const int32_t* b = static_cast<const int32_t*>(array(k, napi_int32_array, &len));
+        failed |= len % words != 0;
+        *n = len / words;
+        return b;
+    }
+};
+
+// ... of a method: h is the receiver's live handle.  A dead or missing handle throws `dead` before any argument is looked at; with
+// dead == nullptr an absent handle is fine and h is nullptr (destroy).
+template <class H>
+struct Call : Args {
+    H* h = nullptr;
+
+    Call(napi_env env, napi_callback_info info, const char* usage, const char* dead = dead_text(static_cast<const H*>(nullptr))) : Args(env, info, usage)
+    {
+        H* got = nullptr;
+        if (thrown) return;
+        if (napi_unwrap(env, self, (void**)&got) == napi_ok && got && live(got)) {
+            h = got;
+        } else if (dead) {
+            napi_throw_error(env, nullptr, dead);
+            thrown = true;
+        }
+    }
+};
+
+// ---- what goes back ---------------------------------------------------------------------------------------
+// a new typed array of n elements of `kind` (a new ArrayBuffer is zero-filled: what a refused record keeps); *data: its storage
+napi_status make_array(napi_env env, napi_typedarray_type kind, size_t n, void** data, napi_value* out)
+{
+    static const size_t bytes[] = {1, 1, 1, 2, 2, 4, 4, 4, 8};          // napi_int8_array .. napi_float64_array
+    napi_value ab;
+    const napi_status s = napi_create_arraybuffer(env, n * bytes[kind], data, &ab);
+    return s != napi_ok ? s : napi_create_typedarray(env, kind, n, ab, 0, out);
+}
+
+struct Prop { const char* name; napi_value v; };
+struct Num { const char* name; double v; };
+
+napi_status set_props(napi_env env, napi_value o, std::initializer_list<Prop> props)
+{
+    for (const Prop& p : props) {
+        const napi_status s = napi_set_named_property(env, o, p.name, p.v);
+        if (s != napi_ok) return s;
+    }
+    return napi_ok;
+}
+
+napi_status make_object(napi_env env, std::initializer_list<Prop> props, napi_value* o)
+{
+    const napi_status s = napi_create_object(env, o);
+    return s != napi_ok ? s : set_props(env, *o, props);
+}
+
+napi_status set_numbers(napi_env env, napi_value o, std::initializer_list<Num> nums)
+{
+    for (const Num& n : nums) {
+        napi_value v;
+        napi_status s = napi_create_double(env, n.v, &v);
+        if (s == napi_ok) s = napi_set_named_property(env, o, n.name, v);
+        if (s != napi_ok) return s;
+    }
+    return napi_ok;
+}
+
+struct Method { const char* name; napi_callback fn; };
+
+napi_status define_methods(napi_env env, napi_value obj, std::initializer_list<Method> table)
+{
+    for (const Method& m : table) {
+        napi_value fn;
+        napi_status s = napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn);
+        if (s == napi_ok) s = napi_set_named_property(env, obj, m.name, fn);
+        if (s != napi_ok) return s;
+    }
+    return napi_ok;
+}
+
+// ---- options: properties of an object ------------------------------------------------------------------------
+// obj[key]: 1 and the value in *v; 0 absent (no such property, undefined or null); -1 it cannot be read
+int get_prop(napi_env env, napi_value obj, const char* key, napi_value* v)
+{
+    bool has = false;
+    napi_valuetype t = napi_undefined;
+    if (napi_has_named_property(env, obj, key, &has) != napi_ok || !has) return 0;
+    if (napi_get_named_property(env, obj, key, v) != napi_ok) return -1;
+    napi_typeof(env, *v, &t);
+    return t == napi_undefined || t == napi_null ? 0 : 1;
+}
+
 bool get_i32(napi_env env, napi_value obj, const char* key, int32_t* out, int32_t dflt)
 {
     napi_value v;
-    bool has = false;
     *out = dflt;
-    if (napi_has_named_property(env, obj, key, &has) != napi_ok || !has) return true;
-    if (napi_get_named_property(env, obj, key, &v) != napi_ok) return false;
-    napi_valuetype t;
-    napi_typeof(env, v, &t);
-    if (t == napi_undefined || t == napi_null) return true;
-    return napi_get_value_int32(env, v, out) == napi_ok;
+    const int got = get_prop(env, obj, key, &v);
+    return got == 0 || (got > 0 && napi_get_value_int32(env, v, out) == napi_ok);
 }
 
 // typed array property -> pointer (nullptr when absent/null); checks the element count
 bool get_array(napi_env env, napi_value obj, const char* key, napi_typedarray_type want, size_t min_len, const void** out)
 {
-    *out = nullptr;
     napi_value v;
-    bool has = false;
-    if (napi_has_named_property(env, obj, key, &has) != napi_ok || !has) return true;
-    if (napi_get_named_property(env, obj, key, &v) != napi_ok) return false;
-    napi_valuetype t;
-    napi_typeof(env, v, &t);
-    if (t == napi_undefined || t == napi_null) return true;
-    bool is_ta = false;
-    napi_is_typedarray(env, v, &is_ta);
-    if (!is_ta) return false;
-    napi_typedarray_type type;
-    size_t len;
-    void* data;
-    if (napi_get_typedarray_info(env, v, &type, &len, &data, nullptr, nullptr) != napi_ok) return false;
-    if (type != want || len < min_len) return false;
+    void* data = nullptr;
+    size_t len = 0;
+    *out = nullptr;
+    const int got = get_prop(env, obj, key, &v);
+    if (got == 0) return true;
+    if (got < 0 || !Args::typed(env, v, want, &data, &len) || len < min_len) return false;
     *out = data;
     return true;
 }
 
-Handle* unwrap(napi_env env, napi_callback_info info, size_t* argc, napi_value* argv)
+// opts[name] as a double: 1 a number, in *out; 0 absent (or not to be read); -1 something else
+int get_f64(napi_env env, napi_value opts, const char* name, double* out)
 {
-    napi_value self;
-    if (napi_get_cb_info(env, info, argc, argv, &self, nullptr) != napi_ok) return nullptr;
-    Handle* h = nullptr;
-    if (napi_unwrap(env, self, (void**)&h) != napi_ok || !h || !h->d) {
-        napi_throw_error(env, nullptr, "leon: decoder handle is destroyed or invalid");
-        return nullptr;
-    }
-    return h;
+    napi_value v;
+    if (get_prop(env, opts, name, &v) <= 0) return 0;
+    return napi_get_value_double(env, v, out) == napi_ok ? 1 : -1;
 }
 
+// opts[name] as three floats (an array of numbers); absent: zeros
+bool get_f32x3(napi_env env, napi_value opts, const char* name, float* out)
+{
+    napi_value v, e;
+    bool is_arr = false;
+    uint32_t n = 0;
+    const int got = get_prop(env, opts, name, &v);
+    if (got <= 0) return got == 0;
+    if (napi_is_array(env, v, &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, v, &n) != napi_ok || n != 3) return false;
+    for (uint32_t k = 0; k < 3; k++) {
+        double d = 0;
+        if (napi_get_element(env, v, k, &e) != napi_ok || napi_get_value_double(env, e, &d) != napi_ok) return false;
+        out[k] = (float)d;
+    }
+    return true;
+}
+
+struct IntOpt { const char* name; int32_t* field; int32_t dflt; };
+
+// ---- the decoder handle -------------------------------------------------------------------------------------
 void finalize(napi_env, void* data, void*)
 {
     Handle* h = (Handle*)data;
@@ -103,35 +284,25 @@ void finalize(napi_env, void* data, void*)
 
 napi_value SetQuantMatrices(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    Handle* h = unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
+    Call<Handle> a(env, info, "setQuantMatrices: Uint8Array(64) expected");
+    if (a.bad()) return nullptr;
     const uint8_t* m[2] = {nullptr, nullptr};
-    for (size_t i = 0; i < argc && i < 2; i++) {
-        napi_valuetype t;
-        napi_typeof(env, argv[i], &t);
-        if (t == napi_undefined || t == napi_null) continue;
-        napi_typedarray_type type;
-        size_t len;
-        void* data;
-        if (napi_get_typedarray_info(env, argv[i], &type, &len, &data, nullptr, nullptr) != napi_ok || type != napi_uint8_array || len < 64) {
-            napi_throw_type_error(env, nullptr, "setQuantMatrices: Uint8Array(64) expected");
-            return nullptr;
-        }
-        m[i] = (const uint8_t*)data;
+    for (size_t i = 0; i < 2; i++) {
+        size_t len = 0;
+        if (a.absent(i)) continue;
+        m[i] = static_cast<const uint8_t*>(a.array(i, napi_uint8_array, &len));
+        if (a.bad(len < 64)) return nullptr;
     }
-    int rc = leon_set_quant_matrices(h->d, m[0], m[1]);
+    int rc = leon_set_quant_matrices(a.h->d, m[0], m[1]);
     return rc == LEON_OK ? nullptr : throw_leon(env, rc);
 }
 
 napi_value AcquireSlot(napi_env env, napi_callback_info info)
 {
-    size_t argc = 0;
-    Handle* h = unwrap(env, info, &argc, nullptr);
-    if (!h) return nullptr;
+    Call<Handle> a(env, info, nullptr);
+    if (a.bad()) return nullptr;
     int32_t slot = -1;
-    int rc = leon_acquire_slot(h->d, &slot);
+    int rc = leon_acquire_slot(a.h->d, &slot);
     if (rc != LEON_OK) return throw_leon(env, rc);          // "no free render buffers"
     napi_value v;
     NAPI_OK(napi_create_int32(env, slot, &v));
@@ -140,39 +311,27 @@ napi_value AcquireSlot(napi_env env, napi_callback_info info)
 
 napi_value ReleaseSlot(napi_env env, napi_callback_info info)
 {
-    size_t argc = 1;
-    napi_value argv[1];
-    Handle* h = unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int32_t slot = -1;
-    if (argc < 1 || napi_get_value_int32(env, argv[0], &slot) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "releaseSlot(slot)");
-        return nullptr;
-    }
-    int rc = leon_release_slot(h->d, slot);
+    Call<Handle> a(env, info, "releaseSlot(slot)");
+    const int32_t slot = a.i32(0);
+    if (a.bad()) return nullptr;
+    int rc = leon_release_slot(a.h->d, slot);
     return rc == LEON_OK ? nullptr : throw_leon(env, rc);
 }
 
 napi_value FreeDecodedSlots(napi_env env, napi_callback_info info)
 {
-    size_t argc = 0;
-    Handle* h = unwrap(env, info, &argc, nullptr);
-    if (!h) return nullptr;
-    int rc = leon_free_decoded_slots(h->d);
+    Call<Handle> a(env, info, nullptr);
+    if (a.bad()) return nullptr;
+    int rc = leon_free_decoded_slots(a.h->d);
     return rc == LEON_OK ? nullptr : throw_leon(env, rc);
 }
 
 napi_value SubmitPicture(napi_env env, napi_callback_info info)
 {
-    size_t argc = 1;
-    napi_value argv[1];
-    Handle* h = unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    if (argc < 1) {
-        napi_throw_type_error(env, nullptr, "submitPicture(picture)");
-        return nullptr;
-    }
-    napi_value p = argv[0];
+    Call<Handle> a(env, info, "submitPicture(picture)");
+    if (a.bad(a.argc < 1)) return nullptr;
+    Handle* h = a.h;
+    napi_value p = a.argv[0];
     leon_picture pic;
     memset(&pic, 0, sizeof pic);
     size_t ny = (size_t)h->cfg.coded_width * h->cfg.coded_height, nc = ny / 4;
@@ -201,15 +360,10 @@ napi_value SubmitPicture(napi_env env, napi_callback_info info)
 // leon_vlc_napi's nextPicture() returns goes in unchanged
 napi_value SubmitSparse(napi_env env, napi_callback_info info)
 {
-    size_t argc = 1;
-    napi_value argv[1];
-    Handle* h = unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    if (argc < 1) {
-        napi_throw_type_error(env, nullptr, "submitSparse(picture)");
-        return nullptr;
-    }
-    napi_value p = argv[0];
+    Call<Handle> a(env, info, "submitSparse(picture)");
+    if (a.bad(a.argc < 1)) return nullptr;
+    Handle* h = a.h;
+    napi_value p = a.argv[0];
     leon_sparse_picture pic;
     memset(&pic, 0, sizeof pic);
     const int mbw = h->cfg.coded_width / 16, mbh = h->cfg.coded_height / 16;
@@ -236,104 +390,73 @@ napi_value SubmitSparse(napi_env env, napi_callback_info info)
     return rc == LEON_OK ? nullptr : throw_leon(env, rc);
 }
 
-napi_value make_u8(napi_env env, size_t bytes, uint8_t** data)
-{
-    napi_value ab, ta;
-    if (napi_create_arraybuffer(env, bytes, (void**)data, &ab) != napi_ok) return nullptr;
-    if (napi_create_typedarray(env, napi_uint8_array, bytes, ab, 0, &ta) != napi_ok) return nullptr;
-    return ta;
-}
-
 napi_value ConvertRGBA(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    Handle* h = unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int32_t slot = -1, flavour = 0;
-    if (argc < 1 || napi_get_value_int32(env, argv[0], &slot) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "convertRGBA(slot[, flavour])");
-        return nullptr;
-    }
-    if (argc > 1) napi_get_value_int32(env, argv[1], &flavour);
-    uint8_t* data = nullptr;
-    napi_value ta = make_u8(env, (size_t)h->cfg.frame_width * h->cfg.frame_height * 4, &data);
-    if (!ta) return nullptr;
-    int rc = leon_convert_rgba(h->d, slot, data, LEON_MEM_HOST, flavour);
+    Call<Handle> a(env, info, "convertRGBA(slot[, flavour])");
+    const int32_t slot = a.i32(0), flavour = a.i32(1, 0);
+    if (a.bad()) return nullptr;
+    void* data = nullptr;
+    napi_value ta;
+    NAPI_OK(make_array(env, napi_uint8_array, (size_t)a.h->cfg.frame_width * a.h->cfg.frame_height * 4, &data, &ta));
+    int rc = leon_convert_rgba(a.h->d, slot, data, LEON_MEM_HOST, flavour);
     return rc == LEON_OK ? ta : throw_leon(env, rc);
 }
 
 napi_value ReadPlanes(napi_env env, napi_callback_info info)
 {
-    size_t argc = 1;
-    napi_value argv[1];
-    Handle* h = unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int32_t slot = -1;
-    if (argc < 1 || napi_get_value_int32(env, argv[0], &slot) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "readPlanes(slot)");
-        return nullptr;
-    }
+    Call<Handle> a(env, info, "readPlanes(slot)");
+    const int32_t slot = a.i32(0);
+    if (a.bad()) return nullptr;
+    Handle* h = a.h;
     size_t ny = (size_t)h->cfg.coded_width * h->cfg.coded_height, nc = ny / 4;
-    uint8_t *y, *cb, *cr;
-    napi_value ty = make_u8(env, ny, &y), tcb = make_u8(env, nc, &cb), tcr = make_u8(env, nc, &cr);
-    if (!ty || !tcb || !tcr) return nullptr;
-    int rc = leon_read_planes(h->d, slot, y, cb, cr);
+    void *y, *cb, *cr;
+    napi_value ty, tcb, tcr, o;
+    NAPI_OK(make_array(env, napi_uint8_array, ny, &y, &ty));
+    NAPI_OK(make_array(env, napi_uint8_array, nc, &cb, &tcb));
+    NAPI_OK(make_array(env, napi_uint8_array, nc, &cr, &tcr));
+    int rc = leon_read_planes(h->d, slot, (uint8_t*)y, (uint8_t*)cb, (uint8_t*)cr);
     if (rc != LEON_OK) return throw_leon(env, rc);
-    napi_value o;
-    NAPI_OK(napi_create_object(env, &o));
-    napi_set_named_property(env, o, "y", ty);
-    napi_set_named_property(env, o, "cb", tcb);
-    napi_set_named_property(env, o, "cr", tcr);
+    NAPI_OK(make_object(env, {{"y", ty}, {"cb", tcb}, {"cr", tcr}}, &o));
     if (h->cfg.alpha) {                       // yuva: the fourth plane of the slot
-        uint8_t* a;
-        napi_value ta = make_u8(env, ny, &a);
-        if (!ta) return nullptr;
-        rc = leon_read_alpha_plane(h->d, slot, a);
+        void* al;
+        napi_value ta;
+        NAPI_OK(make_array(env, napi_uint8_array, ny, &al, &ta));
+        rc = leon_read_alpha_plane(h->d, slot, (uint8_t*)al);
         if (rc != LEON_OK) return throw_leon(env, rc);
-        napi_set_named_property(env, o, "a", ta);
+        NAPI_OK(set_props(env, o, {{"a", ta}}));
     }
     return o;
 }
 
 napi_value Sync(napi_env env, napi_callback_info info)
 {
-    size_t argc = 0;
-    Handle* h = unwrap(env, info, &argc, nullptr);
-    if (!h) return nullptr;
-    int rc = leon_sync(h->d);
+    Call<Handle> a(env, info, nullptr);
+    if (a.bad()) return nullptr;
+    int rc = leon_sync(a.h->d);
     return rc == LEON_OK ? nullptr : throw_leon(env, rc);
 }
 
 napi_value Destroy(napi_env env, napi_callback_info info)
 {
-    size_t argc = 0;
-    napi_value self;
-    napi_get_cb_info(env, info, &argc, nullptr, &self, nullptr);
-    Handle* h = nullptr;
-    if (napi_unwrap(env, self, (void**)&h) == napi_ok && h && h->d) {
-        leon_destroy(h->d);
-        h->d = nullptr;
+    Call<Handle> a(env, info, nullptr, nullptr);
+    if (a.h) {
+        leon_destroy(a.h->d);
+        a.h->d = nullptr;
     }
     return nullptr;
 }
 
 napi_value Create(napi_env env, napi_callback_info info)
 {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    if (argc < 1) {
-        napi_throw_type_error(env, nullptr, "create({codedWidth, codedHeight, ...})");
-        return nullptr;
-    }
+    Args a(env, info, "create({codedWidth, codedHeight, ...})");
+    if (a.bad(a.argc < 1)) return nullptr;
     Handle* h = new Handle();
     memset(&h->cfg, 0, sizeof h->cfg);
     h->d = nullptr;
-    bool ok = get_i32(env, argv[0], "codedWidth", &h->cfg.coded_width, 0) && get_i32(env, argv[0], "codedHeight", &h->cfg.coded_height, 0) &&
-              get_i32(env, argv[0], "frameWidth", &h->cfg.frame_width, 0) && get_i32(env, argv[0], "frameHeight", &h->cfg.frame_height, 0) &&
-              get_i32(env, argv[0], "nSlots", &h->cfg.n_slots, 13) && get_i32(env, argv[0], "deviceId", &h->cfg.device_id, 0) &&
-              get_i32(env, argv[0], "alpha", &h->cfg.alpha, 0);
+    bool ok = true;
+    for (const IntOpt& o : {IntOpt{"codedWidth", &h->cfg.coded_width, 0}, {"codedHeight", &h->cfg.coded_height, 0}, {"frameWidth", &h->cfg.frame_width, 0},
+                            {"frameHeight", &h->cfg.frame_height, 0}, {"nSlots", &h->cfg.n_slots, 13}, {"deviceId", &h->cfg.device_id, 0}, {"alpha", &h->cfg.alpha, 0}})
+        ok = ok && get_i32(env, a.argv[0], o.name, o.field, o.dflt);
     if (!ok) {
         delete h;
         napi_throw_type_error(env, nullptr, "create: integer fields expected");
@@ -349,15 +472,9 @@ napi_value Create(napi_env env, napi_callback_info info)
     napi_value obj;
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, finalize, nullptr, nullptr));
-    const struct { const char* name; napi_callback fn; } methods[] = {
-        {"setQuantMatrices", SetQuantMatrices}, {"acquireSlot", AcquireSlot}, {"releaseSlot", ReleaseSlot},
-        {"freeDecodedSlots", FreeDecodedSlots}, {"submitPicture", SubmitPicture}, {"submitSparse", SubmitSparse}, {"convertRGBA", ConvertRGBA},
-        {"readPlanes", ReadPlanes}, {"sync", Sync}, {"destroy", Destroy}};
-    for (auto& m : methods) {
-        napi_value fn;
-        NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));
-        NAPI_OK(napi_set_named_property(env, obj, m.name, fn));
-    }
+    NAPI_OK(define_methods(env, obj, {{"setQuantMatrices", SetQuantMatrices}, {"acquireSlot", AcquireSlot}, {"releaseSlot", ReleaseSlot}, {"freeDecodedSlots", FreeDecodedSlots},
+                                      {"submitPicture", SubmitPicture}, {"submitSparse", SubmitSparse}, {"convertRGBA", ConvertRGBA}, {"readPlanes", ReadPlanes}, {"sync", Sync},
+                                      {"destroy", Destroy}}));
     return obj;
 }
 
@@ -381,21 +498,6 @@ struct PipeMsg {
     int64_t last_window;        // 'ended': the last window delivered before it (which position it ends)
     int32_t status;
     std::vector<leon_pipeline_frame> frames;
-};
-
-struct PipeHandle {
-    leon_pipeline* p = nullptr;
-    napi_threadsafe_function tsfn = nullptr;
-    napi_ref stream_ref = nullptr;          // keeps the stream's Buffer alive: the pipeline reads it in place
-    std::mutex mu;
-    std::map<int64_t, std::vector<leon_pipeline_frame>> out;   // delivered, not yet released
-    leon_pipeline_info info{};
-    leon_pipeline_tensor_geometry tensor_geom{};      // all 0 without tensor output
-    leon_pipeline_tensor_shape tensor_shape{};        // the same
-    leon_pipeline_tensor_canvas tensor_canvas{};      // the same
-    int64_t last_window = -1;               // notify thread, under mu
-    int64_t floor = 0;                      // JavaScript thread: the first window of the latest seek
-    bool seeked = false;
 };
 
 void pipe_native_cb(void* user, int64_t window, const leon_pipeline_frame* frames, int32_t n, int32_t status)
@@ -442,12 +544,10 @@ void pipe_call_js(napi_env env, napi_value js_cb, void* ctx, void* data)
         napi_create_int64(env, m->window, &argv[0]);
         napi_create_array_with_length(env, m->frames.size(), &argv[1]);
         for (size_t i = 0; i < m->frames.size(); i++) {
-            napi_value o, v;
+            const leon_pipeline_frame& f = m->frames[i];
+            napi_value o;
             napi_create_object(env, &o);
-            napi_create_double(env, (double)m->frames[i].gop, &v); napi_set_named_property(env, o, "gop", v);
-            napi_create_int32(env, m->frames[i].display_index, &v); napi_set_named_property(env, o, "displayIndex", v);
-            napi_create_int32(env, m->frames[i].type, &v); napi_set_named_property(env, o, "type", v);
-            napi_create_double(env, m->frames[i].ts_ms, &v); napi_set_named_property(env, o, "ts", v);
+            set_numbers(env, o, {{"gop", (double)f.gop}, {"displayIndex", (double)f.display_index}, {"type", (double)f.type}, {"ts", f.ts_ms}});
             napi_set_element(env, argv[1], (uint32_t)i, o);
         }
         napi_create_int32(env, m->status, &argv[2]);
@@ -457,73 +557,97 @@ void pipe_call_js(napi_env env, napi_value js_cb, void* ctx, void* data)
     delete m;
 }
 
-void pipe_finalize(napi_env env, void* data, void*)
+// the end of a PipeHandle that no JavaScript object owns (yet, or any more), in this order: the pipeline, the threadsafe function (a
+// live one keeps the event loop alive), the stream's reference, the handle
+void pipe_release(napi_env env, PipeHandle* h)
 {
-    PipeHandle* h = (PipeHandle*)data;
     if (h->p) leon_pipeline_destroy(h->p);
     if (h->tsfn) napi_release_threadsafe_function(h->tsfn, napi_tsfn_abort);
     if (h->stream_ref) napi_delete_reference(env, h->stream_ref);
     delete h;
 }
 
-PipeHandle* pipe_unwrap(napi_env env, napi_callback_info info, size_t* argc, napi_value* argv)
+void pipe_finalize(napi_env env, void* data, void*) { pipe_release(env, (PipeHandle*)data); }
+
+// owns the handle from `new` until napi_wrap has it: every way out of CreatePipeline before that releases it
+struct PipeGuard {
+    napi_env env;
+    PipeHandle* h;
+    ~PipeGuard() { if (h) pipe_release(env, h); }
+};
+
+// The delivered window w, under h->mu: its frame count, and its frame i in *f where f is given.  No such window, or no frame i in
+// it: `text` is thrown (as a RangeError where `range`) and false comes back.
+bool delivered(napi_env env, PipeHandle* h, int64_t w, int32_t i, leon_pipeline_frame* f, size_t* n, bool range, const char* text)
 {
-    napi_value self;
-    if (napi_get_cb_info(env, info, argc, argv, &self, nullptr) != napi_ok) return nullptr;
-    PipeHandle* h = nullptr;
-    if (napi_unwrap(env, self, (void**)&h) != napi_ok || !h || !h->p) {
-        napi_throw_error(env, nullptr, "pipeline is destroyed");
-        return nullptr;
+    std::lock_guard<std::mutex> lk(h->mu);
+    auto it = h->out.find(w);
+    *n = it == h->out.end() ? 0 : it->second.size();
+    if (i < 0 || (size_t)i >= *n) {
+        if (range) napi_throw_range_error(env, nullptr, text);
+        else napi_throw_error(env, nullptr, text);
+        return false;
     }
-    return h;
+    if (f) *f = it->second[(size_t)i];
+    return true;
+}
+
+// The record-count rule of the calls that take n records.  The library takes 1 .. 65535 (`ok`) and refuses the rest by its own
+// text, so that n is handed on: as `count`, clamped to a value an int32 holds and the library still refuses.  `rows` is what the
+// result arrays and the record vector are sized for: n where the library takes it, else one row -- a count it refuses allocates
+// nothing to speak of here.
+struct Count { bool ok; size_t rows; int32_t count; };
+
+Count record_count(size_t n)
+{
+    const bool ok = n >= 1 && n <= 65535;
+    return Count{ok, ok ? n : 1, (int32_t)std::min<size_t>(n, 65536)};
+}
+
+// a Buffer for a batch of n regions of oh x ow in the pipeline's element type (one byte where the library refuses the size or
+// the count: that allocates nothing here)
+napi_status region_batch(napi_env env, const PipeHandle* h, size_t n, int32_t oh, int32_t ow, void** data, napi_value* buf)
+{
+    const bool sized = oh >= 1 && oh <= 4096 && ow >= 1 && ow <= 4096 && record_count(n).ok;
+    const size_t bytes = sized ? n * 3 * (size_t)oh * (size_t)ow * (size_t)h->info.tensor_element_bytes : 0;
+    return napi_create_buffer(env, bytes ? bytes : 1, data, buf);
+}
+
+bool has_tensor_output(napi_env env, const PipeHandle* h, const char* method)
+{
+    if (h->info.tensor_dtype) return true;
+    char msg[120];
+    snprintf(msg, sizeof msg, "%s: the pipeline has no tensor output (opts.output)", method);
+    napi_throw_error(env, nullptr, msg);
+    return false;
 }
 
 napi_value PipeRelease(napi_env env, napi_callback_info info)
 {
-    size_t argc = 1;
-    napi_value argv[1];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    if (argc < 1 || napi_get_value_int64(env, argv[0], &w) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "releaseWindow(window)");
-        return nullptr;
-    }
+    Call<PipeHandle> a(env, info, "releaseWindow(window)");
+    const int64_t w = a.i64(0);
+    if (a.bad()) return nullptr;
     {
-        std::lock_guard<std::mutex> lk(h->mu);
-        h->out.erase(w);
+        std::lock_guard<std::mutex> lk(a.h->mu);
+        a.h->out.erase(w);
     }
-    int rc = leon_pipeline_release_window(h->p, w);
+    int rc = leon_pipeline_release_window(a.h->p, w);
     return rc == LEON_OK ? nullptr : throw_leon(env, rc);
 }
 
 napi_value PipeReadFrame(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    int32_t i = -1;
-    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "readFrame(window, index)");
-        return nullptr;
-    }
+    Call<PipeHandle> a(env, info, "readFrame(window, index)");
+    const int64_t w = a.i64(0);
+    const int32_t i = a.i32(1);
+    if (a.bad()) return nullptr;
+    PipeHandle* h = a.h;
     leon_pipeline_frame f{};
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        auto it = h->out.find(w);
-        if (it == h->out.end() || i < 0 || (size_t)i >= it->second.size()) {
-            napi_throw_range_error(env, nullptr, "readFrame: no such frame (window released?)");
-            return nullptr;
-        }
-        f = it->second[(size_t)i];
-    }
-    const size_t bytes = (size_t)h->info.frame_width * h->info.frame_height * 4;
-    napi_value ab, ta;
+    size_t n;
+    if (!delivered(env, h, w, i, &f, &n, true, "readFrame: no such frame (window released?)")) return nullptr;
+    napi_value ta;
     void* data = nullptr;
-    NAPI_OK(napi_create_arraybuffer(env, bytes, &data, &ab));
-    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, bytes, ab, 0, &ta));
+    NAPI_OK(make_array(env, napi_uint8_array, (size_t)h->info.frame_width * h->info.frame_height * 4, &data, &ta));
     int rc = leon_pipeline_read_frame(h->p, &f, (uint8_t*)data);
     return rc == LEON_OK ? ta : throw_leon(env, rc);
 }
@@ -531,36 +655,23 @@ napi_value PipeReadFrame(napi_env env, napi_callback_info info)
 // p.readPlanes(window, i) -> {y, cb, cr[, a]}: packed Uint8Arrays of one frame's YCbCr planes (output 'ycbcr' / 'both')
 napi_value PipeReadPlanes(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    int32_t i = -1;
-    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "readPlanes(window, index)");
-        return nullptr;
-    }
+    Call<PipeHandle> a(env, info, "readPlanes(window, index)");
+    const int64_t w = a.i64(0);
+    const int32_t i = a.i32(1);
+    if (a.bad()) return nullptr;
+    PipeHandle* h = a.h;
     leon_pipeline_frame f{};
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        auto it = h->out.find(w);
-        if (it == h->out.end() || i < 0 || (size_t)i >= it->second.size()) {
-            napi_throw_range_error(env, nullptr, "readPlanes: no such frame (window released?)");
-            return nullptr;
-        }
-        f = it->second[(size_t)i];
-    }
+    size_t n;
+    if (!delivered(env, h, w, i, &f, &n, true, "readPlanes: no such frame (window released?)")) return nullptr;
     const size_t ybytes = (size_t)h->info.frame_width * h->info.frame_height, cbytes = (size_t)h->info.chroma_width * h->info.chroma_height;
     const char* names[4] = {"y", "cb", "cr", "a"};
     const size_t sizes[4] = {ybytes, cbytes, cbytes, ybytes};
     void* data[4] = {nullptr, nullptr, nullptr, nullptr};
-    napi_value o, ab, ta;
+    napi_value o, ta;
     NAPI_OK(napi_create_object(env, &o));
     for (int k = 0; k < (f.a ? 4 : 3); k++) {
-        NAPI_OK(napi_create_arraybuffer(env, sizes[k], &data[k], &ab));
-        NAPI_OK(napi_create_typedarray(env, napi_uint8_array, sizes[k], ab, 0, &ta));
-        NAPI_OK(napi_set_named_property(env, o, names[k], ta));
+        NAPI_OK(make_array(env, napi_uint8_array, sizes[k], &data[k], &ta));
+        NAPI_OK(set_props(env, o, {{names[k], ta}}));
     }
     int rc = leon_pipeline_read_frame_planes(h->p, &f, (uint8_t*)data[0], (uint8_t*)data[1], (uint8_t*)data[2], (uint8_t*)data[3]);
     return rc == LEON_OK ? o : throw_leon(env, rc);
@@ -571,26 +682,15 @@ napi_value PipeReadPlanes(napi_env env, napi_callback_info info)
 // one frame's tensor (output 'tensor' ...)
 napi_value PipeReadTensor(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    int32_t i = -1;
-    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "readTensor(window, index)");
-        return nullptr;
-    }
-    if (!h->info.tensor_dtype) {
-        napi_throw_error(env, nullptr, "readTensor: the pipeline has no tensor output (opts.output)");
-        return nullptr;
-    }
-    const size_t bytes = (size_t)h->info.tensor_frame_bytes, eb = (size_t)h->info.tensor_element_bytes;
-    napi_value ab, ta;
+    Call<PipeHandle> a(env, info, "readTensor(window, index)");
+    const int64_t w = a.i64(0);
+    const int32_t i = a.i32(1);
+    if (a.bad() || !has_tensor_output(env, a.h, "readTensor")) return nullptr;
+    const size_t bytes = (size_t)a.h->info.tensor_frame_bytes, eb = (size_t)a.h->info.tensor_element_bytes;
+    napi_value ta;
     void* data = nullptr;
-    NAPI_OK(napi_create_arraybuffer(env, bytes, &data, &ab));
-    NAPI_OK(napi_create_typedarray(env, eb == 4 ? napi_float32_array : (eb == 1 ? napi_uint8_array : napi_uint16_array), bytes / eb, ab, 0, &ta));
-    int rc = leon_pipeline_read_tensor(h->p, w, i, data);
+    NAPI_OK(make_array(env, eb == 4 ? napi_float32_array : (eb == 1 ? napi_uint8_array : napi_uint16_array), bytes / eb, &data, &ta));
+    int rc = leon_pipeline_read_tensor(a.h->p, w, i, data);
     return rc == LEON_OK ? ta : throw_leon(env, rc);
 }
 
@@ -598,53 +698,29 @@ napi_value PipeReadTensor(napi_env env, napi_callback_info info)
 // mbWidth, mbHeight}: one frame's motion record (opts.motion; include/leon_pipeline.h LEON_PIPELINE_OUTPUT_MOTION), copied to the host
 napi_value PipeReadMotion(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    int32_t i = -1;
-    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "readMotion(window, index)");
-        return nullptr;
-    }
+    Call<PipeHandle> a(env, info, "readMotion(window, index)");
+    const int64_t w = a.i64(0);
+    const int32_t i = a.i32(1);
+    if (a.bad()) return nullptr;
+    PipeHandle* h = a.h;
     struct leon_pipeline_motion_layout lay;
     int rc = leon_pipeline_get_motion_layout(h->p, &lay);
     if (rc != LEON_OK) return throw_leon(env, rc);
     size_t n = 0;
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        auto it = h->out.find(w);
-        if (it != h->out.end()) n = it->second.size();
-    }
-    if (i < 0 || (size_t)i >= n) {
-        napi_throw_error(env, nullptr, "readMotion: no such frame in a delivered window");
-        return nullptr;
-    }
+    if (!delivered(env, h, w, i, nullptr, &n, false, "readMotion: no such frame in a delivered window")) return nullptr;
     std::vector<leon_pipeline_motion_frame> refs(n);
     if ((rc = leon_pipeline_window_motion(h->p, w, refs.data(), (int32_t)n)) != LEON_OK) return throw_leon(env, rc);
-    napi_value o, ab[3], ta[3];
-    void* data[3] = {nullptr, nullptr, nullptr};
+    napi_value o, mv, mbinfo, summary;
+    void *mv_data, *info_data, *summary_data;
     const size_t mbs = (size_t)lay.mbs;
-    NAPI_OK(napi_create_object(env, &o));
-    NAPI_OK(napi_create_arraybuffer(env, mbs * 8, &data[0], &ab[0]));
-    NAPI_OK(napi_create_typedarray(env, napi_int16_array, mbs * 4, ab[0], 0, &ta[0]));
-    NAPI_OK(napi_create_arraybuffer(env, mbs, &data[1], &ab[1]));
-    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, mbs, ab[1], 0, &ta[1]));
-    NAPI_OK(napi_create_arraybuffer(env, 32, &data[2], &ab[2]));
-    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, 8, ab[2], 0, &ta[2]));
-    if ((rc = leon_pipeline_read_motion(h->p, w, i, (int16_t*)data[0], (uint8_t*)data[1], (uint32_t*)data[2])) != LEON_OK) return throw_leon(env, rc);
-    NAPI_OK(napi_set_named_property(env, o, "mv", ta[0]));
-    NAPI_OK(napi_set_named_property(env, o, "info", ta[1]));
-    NAPI_OK(napi_set_named_property(env, o, "summary", ta[2]));
+    NAPI_OK(make_array(env, napi_int16_array, mbs * 4, &mv_data, &mv));
+    NAPI_OK(make_array(env, napi_uint8_array, mbs, &info_data, &mbinfo));
+    NAPI_OK(make_array(env, napi_uint32_array, 8, &summary_data, &summary));
+    if ((rc = leon_pipeline_read_motion(h->p, w, i, (int16_t*)mv_data, (uint8_t*)info_data, (uint32_t*)summary_data)) != LEON_OK) return throw_leon(env, rc);
     const leon_pipeline_motion_frame& m = refs[(size_t)i];
-    const struct { const char* name; double v; } nums[] = {{"fwdGop", (double)m.fwd_gop}, {"fwdDisplay", (double)m.fwd_display}, {"bwdDisplay", (double)m.bwd_display},
-                                                           {"mbWidth", (double)lay.mb_width}, {"mbHeight", (double)lay.mb_height}};
-    for (const auto& kv : nums) {
-        napi_value v;
-        NAPI_OK(napi_create_double(env, kv.v, &v));
-        NAPI_OK(napi_set_named_property(env, o, kv.name, v));
-    }
+    NAPI_OK(make_object(env, {{"mv", mv}, {"info", mbinfo}, {"summary", summary}}, &o));
+    NAPI_OK(set_numbers(env, o, {{"fwdGop", (double)m.fwd_gop}, {"fwdDisplay", (double)m.fwd_display}, {"bwdDisplay", (double)m.bwd_display},
+                                 {"mbWidth", (double)lay.mb_width}, {"mbHeight", (double)lay.mb_height}}));
     return o;
 }
 
@@ -653,36 +729,20 @@ napi_value PipeReadMotion(napi_env env, napi_callback_info info)
 // LEON_PIPELINE_OUTPUT_ACTIVITY), copied to the host; js/leon_pipeline.js splits the cells into typed arrays
 napi_value PipeReadActivity(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    int32_t i = -1;
-    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "readActivity(window, index)");
-        return nullptr;
-    }
+    Call<PipeHandle> a(env, info, "readActivity(window, index)");
+    const int64_t w = a.i64(0);
+    const int32_t i = a.i32(1);
+    if (a.bad()) return nullptr;
     struct leon_pipeline_activity_layout lay;
-    int rc = leon_pipeline_get_activity_layout(h->p, &lay);
+    int rc = leon_pipeline_get_activity_layout(a.h->p, &lay);
     if (rc != LEON_OK) return throw_leon(env, rc);
-    napi_value o, ab[2], ta[2];
-    void* data[2] = {nullptr, nullptr};
-    const size_t mbs = (size_t)lay.mbs;
-    NAPI_OK(napi_create_object(env, &o));
-    NAPI_OK(napi_create_arraybuffer(env, mbs * 8, &data[0], &ab[0]));
-    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, mbs * 8, ab[0], 0, &ta[0]));
-    NAPI_OK(napi_create_arraybuffer(env, 32, &data[1], &ab[1]));
-    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, 8, ab[1], 0, &ta[1]));
-    if ((rc = leon_pipeline_read_activity(h->p, w, i, data[0], (uint32_t*)data[1])) != LEON_OK) return throw_leon(env, rc);
-    NAPI_OK(napi_set_named_property(env, o, "cells", ta[0]));
-    NAPI_OK(napi_set_named_property(env, o, "summary", ta[1]));
-    const struct { const char* name; double v; } nums[] = {{"mbWidth", (double)lay.mb_width}, {"mbHeight", (double)lay.mb_height}};
-    for (const auto& kv : nums) {
-        napi_value v;
-        NAPI_OK(napi_create_double(env, kv.v, &v));
-        NAPI_OK(napi_set_named_property(env, o, kv.name, v));
-    }
+    napi_value o, cells, summary;
+    void *cells_data, *summary_data;
+    NAPI_OK(make_array(env, napi_uint8_array, (size_t)lay.mbs * 8, &cells_data, &cells));
+    NAPI_OK(make_array(env, napi_uint32_array, 8, &summary_data, &summary));
+    if ((rc = leon_pipeline_read_activity(a.h->p, w, i, cells_data, (uint32_t*)summary_data)) != LEON_OK) return throw_leon(env, rc);
+    NAPI_OK(make_object(env, {{"cells", cells}, {"summary", summary}}, &o));
+    NAPI_OK(set_numbers(env, o, {{"mbWidth", (double)lay.mb_width}, {"mbHeight", (double)lay.mb_height}}));
     return o;
 }
 
@@ -690,38 +750,20 @@ napi_value PipeReadActivity(napi_env env, napi_callback_info info)
 // codedHeight}: one frame's residual record (opts.residual; include/leon_pipeline.h LEON_PIPELINE_OUTPUT_RESIDUAL), copied to the host, packed
 napi_value PipeReadResidual(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    int32_t i = -1;
-    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_get_value_int32(env, argv[1], &i) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "readResidual(window, index)");
-        return nullptr;
-    }
+    Call<PipeHandle> a(env, info, "readResidual(window, index)");
+    const int64_t w = a.i64(0);
+    const int32_t i = a.i32(1);
+    if (a.bad()) return nullptr;
     struct leon_pipeline_residual_layout lay;
-    int rc = leon_pipeline_get_residual_layout(h->p, &lay);
+    int rc = leon_pipeline_get_residual_layout(a.h->p, &lay);
     if (rc != LEON_OK) return throw_leon(env, rc);
-    napi_value o, ab[3], ta[3];
+    napi_value o, ta[3];
     void* data[3] = {nullptr, nullptr, nullptr};
     const size_t luma = (size_t)lay.coded_width * (size_t)lay.coded_height;
-    NAPI_OK(napi_create_object(env, &o));
-    for (int k = 0; k < 3; k++) {
-        const size_t n = k == 0 ? luma : luma / 4;
-        NAPI_OK(napi_create_arraybuffer(env, n * 2, &data[k], &ab[k]));
-        NAPI_OK(napi_create_typedarray(env, napi_int16_array, n, ab[k], 0, &ta[k]));
-    }
-    if ((rc = leon_pipeline_read_residual(h->p, w, i, (int16_t*)data[0], (int16_t*)data[1], (int16_t*)data[2])) != LEON_OK) return throw_leon(env, rc);
-    NAPI_OK(napi_set_named_property(env, o, "y", ta[0]));
-    NAPI_OK(napi_set_named_property(env, o, "cb", ta[1]));
-    NAPI_OK(napi_set_named_property(env, o, "cr", ta[2]));
-    const struct { const char* name; double v; } nums[] = {{"codedWidth", (double)lay.coded_width}, {"codedHeight", (double)lay.coded_height}};
-    for (const auto& kv : nums) {
-        napi_value v;
-        NAPI_OK(napi_create_double(env, kv.v, &v));
-        NAPI_OK(napi_set_named_property(env, o, kv.name, v));
-    }
+    for (int k = 0; k < 3; k++) NAPI_OK(make_array(env, napi_int16_array, k == 0 ? luma : luma / 4, &data[k], &ta[k]));
+    if ((rc = leon_pipeline_read_residual(a.h->p, w, i, (int16_t*)data[0], (int16_t*)data[1], (int16_t*)data[2])) != LEON_OK) return throw_leon(env, rc);
+    NAPI_OK(make_object(env, {{"y", ta[0]}, {"cb", ta[1]}, {"cr", ta[2]}}, &o));
+    NAPI_OK(set_numbers(env, o, {{"codedWidth", (double)lay.coded_width}, {"codedHeight", (double)lay.coded_height}}));
     return o;
 }
 
@@ -730,48 +772,29 @@ napi_value PipeReadResidual(napi_env env, napi_callback_info info)
 // Five numbers more -- fit mode, anchor, pad r, g, b (leon_pipeline_regions_fit) -- make it leon_pipeline_read_regions_fit.
 napi_value PipeReadRegions(napi_env env, napi_callback_info info)
 {
-    size_t argc = 10;
-    napi_value argv[10];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    int32_t oh = 0, ow = 0, filter = 0;
-    napi_typedarray_type tt;
-    size_t len = 0, off = 0;
-    void* boxes = nullptr;
-    napi_value ab;
-    bool is_ta = false;
-    if (argc < 5 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta ||
-        napi_get_typedarray_info(env, argv[1], &tt, &len, &boxes, &ab, &off) != napi_ok || tt != napi_int32_array || len % 5 != 0 ||
-        napi_get_value_int32(env, argv[2], &oh) != napi_ok || napi_get_value_int32(env, argv[3], &ow) != napi_ok || napi_get_value_int32(env, argv[4], &filter) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "readRegions(window, Int32Array of [frame, x, y, width, height] per region, outHeight, outWidth, filter)");
-        return nullptr;
-    }
-    const bool fitted = argc > 5;
+    Call<PipeHandle> a(env, info, "readRegions(window, Int32Array of [frame, x, y, width, height] per region, outHeight, outWidth, filter)");
+    size_t n = 0;
+    const int64_t w = a.i64(0);
+    const int32_t* b = a.rows(1, 5, &n);
+    const int32_t oh = a.i32(2), ow = a.i32(3), filter = a.i32(4);
+    if (a.bad()) return nullptr;
+    const bool fitted = a.argc > 5;
     leon_pipeline_regions_fit fit{};
-    if (fitted && (argc < 10 || napi_get_value_int32(env, argv[5], &fit.mode) != napi_ok || napi_get_value_int32(env, argv[6], &fit.anchor) != napi_ok ||
-                   napi_get_value_int32(env, argv[7], &fit.pad[0]) != napi_ok || napi_get_value_int32(env, argv[8], &fit.pad[1]) != napi_ok ||
-                   napi_get_value_int32(env, argv[9], &fit.pad[2]) != napi_ok)) {
-        napi_throw_type_error(env, nullptr, "readRegions(..., filter, fitMode, anchor, padR, padG, padB)");
-        return nullptr;
+    if (fitted) {
+        a.usage = "readRegions(..., filter, fitMode, anchor, padR, padG, padB)";
+        fit.mode = a.i32(5);
+        fit.anchor = a.i32(6);
+        for (size_t k = 0; k < 3; k++) fit.pad[k] = a.i32(7 + k);
     }
-    if (!h->info.tensor_dtype) {
-        napi_throw_error(env, nullptr, "readRegions: the pipeline has no tensor output (opts.output)");
-        return nullptr;
-    }
-    const size_t n = len / 5;
+    if (a.bad() || !has_tensor_output(env, a.h, "readRegions")) return nullptr;
     std::vector<leon_pipeline_region> regions(n ? n : 1);
-    const int32_t* b = static_cast<const int32_t*>(boxes);
     for (size_t i = 0; i < n; i++) regions[i] = leon_pipeline_region{b[5 * i], b[5 * i + 1], b[5 * i + 2], b[5 * i + 3], b[5 * i + 4], {0, 0, 0}};
     const leon_pipeline_regions_config cfg{ow, oh, filter, {0, 0, 0, 0, 0}};
-    // (a size the library refuses allocates nothing here)
-    const bool sized = oh >= 1 && oh <= 4096 && ow >= 1 && ow <= 4096 && n >= 1 && n <= 65535;
-    const size_t bytes = sized ? n * 3 * (size_t)oh * (size_t)ow * (size_t)h->info.tensor_element_bytes : 0;
     napi_value buf;
     void* data = nullptr;
-    NAPI_OK(napi_create_buffer(env, bytes ? bytes : 1, &data, &buf));
-    const int32_t count = (int32_t)std::min<size_t>(n, 65536);
-    int rc = fitted ? leon_pipeline_read_regions_fit(h->p, w, regions.data(), count, &cfg, &fit, data) : leon_pipeline_read_regions(h->p, w, regions.data(), count, &cfg, data);
+    NAPI_OK(region_batch(env, a.h, n, oh, ow, &data, &buf));
+    const int32_t count = record_count(n).count;
+    int rc = fitted ? leon_pipeline_read_regions_fit(a.h->p, w, regions.data(), count, &cfg, &fit, data) : leon_pipeline_read_regions(a.h->p, w, regions.data(), count, &cfg, data);
     return rc == LEON_OK ? buf : throw_leon(env, rc);
 }
 
@@ -779,42 +802,22 @@ napi_value PipeReadRegions(napi_env env, napi_callback_info info)
 // leon_pipeline_read_warp_regions.  records: an Int32Array of n x [frame index, a00, a01, tx, a10, a11, ty] (Q16).
 napi_value PipeReadWarpRegions(napi_env env, napi_callback_info info)
 {
-    size_t argc = 7;
-    napi_value argv[7];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
+    Call<PipeHandle> a(env, info, "readWarpRegions(window, Int32Array of [frame, a00, a01, tx, a10, a11, ty] per region, outHeight, outWidth, padR, padG, padB)");
+    size_t n = 0;
     leon_pipeline_warp_config cfg{};
-    napi_typedarray_type tt;
-    size_t len = 0, off = 0;
-    void* words = nullptr;
-    napi_value ab;
-    bool is_ta = false;
-    if (argc < 7 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta ||
-        napi_get_typedarray_info(env, argv[1], &tt, &len, &words, &ab, &off) != napi_ok || tt != napi_int32_array || len % 7 != 0 ||
-        napi_get_value_int32(env, argv[2], &cfg.out_height) != napi_ok || napi_get_value_int32(env, argv[3], &cfg.out_width) != napi_ok ||
-        napi_get_value_int32(env, argv[4], &cfg.pad[0]) != napi_ok || napi_get_value_int32(env, argv[5], &cfg.pad[1]) != napi_ok ||
-        napi_get_value_int32(env, argv[6], &cfg.pad[2]) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "readWarpRegions(window, Int32Array of [frame, a00, a01, tx, a10, a11, ty] per region, outHeight, outWidth, padR, padG, padB)");
-        return nullptr;
-    }
-    if (!h->info.tensor_dtype) {
-        napi_throw_error(env, nullptr, "readWarpRegions: the pipeline has no tensor output (opts.output)");
-        return nullptr;
-    }
-    const size_t n = len / 7;
+    const int64_t w = a.i64(0);
+    const int32_t* b = a.rows(1, 7, &n);
+    cfg.out_height = a.i32(2);
+    cfg.out_width = a.i32(3);
+    for (size_t k = 0; k < 3; k++) cfg.pad[k] = a.i32(4 + k);
+    if (a.bad() || !has_tensor_output(env, a.h, "readWarpRegions")) return nullptr;
     std::vector<leon_pipeline_warp_region> regions(n ? n : 1);
-    const int32_t* b = static_cast<const int32_t*>(words);
     for (size_t i = 0; i < n; i++)
         regions[i] = leon_pipeline_warp_region{b[7 * i], {b[7 * i + 1], b[7 * i + 2], b[7 * i + 3], b[7 * i + 4], b[7 * i + 5], b[7 * i + 6]}, 0};
-    const int32_t oh = cfg.out_height, ow = cfg.out_width;
-    // (a size the library refuses allocates nothing here)
-    const bool sized = oh >= 1 && oh <= 4096 && ow >= 1 && ow <= 4096 && n >= 1 && n <= 65535;
-    const size_t bytes = sized ? n * 3 * (size_t)oh * (size_t)ow * (size_t)h->info.tensor_element_bytes : 0;
     napi_value buf;
     void* data = nullptr;
-    NAPI_OK(napi_create_buffer(env, bytes ? bytes : 1, &data, &buf));
-    const int rc = leon_pipeline_read_warp_regions(h->p, w, regions.data(), (int32_t)std::min<size_t>(n, 65536), &cfg, data);
+    NAPI_OK(region_batch(env, a.h, n, cfg.out_height, cfg.out_width, &data, &buf));
+    const int rc = leon_pipeline_read_warp_regions(a.h->p, w, regions.data(), record_count(n).count, &cfg, data);
     return rc == LEON_OK ? buf : throw_leon(env, rc);
 }
 
@@ -823,40 +826,24 @@ napi_value PipeReadWarpRegions(napi_env env, napi_callback_info info)
 // leon_pipeline_carry_regions (opts.motion).  records: an Int32Array of n x [frame index, x, y, width, height, target frame index].
 napi_value PipeCarryRegions(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    napi_typedarray_type tt;
-    size_t len = 0, off = 0;
-    void* words = nullptr;
-    napi_value ab;
-    bool is_ta = false;
-    if (argc < 2 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta ||
-        napi_get_typedarray_info(env, argv[1], &tt, &len, &words, &ab, &off) != napi_ok || tt != napi_int32_array || len % 6 != 0) {
-        napi_throw_type_error(env, nullptr, "carryRegions(window, Int32Array of [frame, x, y, width, height, target] per record)");
-        return nullptr;
-    }
-    const size_t n = len / 6, m = n >= 1 && n <= 65535 ? n : 1;          // (a count the library refuses allocates nothing to speak of here)
-    std::vector<leon_pipeline_carry_region> regions(m);
-    const int32_t* b = static_cast<const int32_t*>(words);
-    for (size_t i = 0; i < n && i < m; i++)
+    Call<PipeHandle> a(env, info, "carryRegions(window, Int32Array of [frame, x, y, width, height, target] per record)");
+    size_t n = 0;
+    const int64_t w = a.i64(0);
+    const int32_t* b = a.rows(1, 6, &n);
+    if (a.bad()) return nullptr;
+    const Count c = record_count(n);
+    std::vector<leon_pipeline_carry_region> regions(c.rows);
+    for (size_t i = 0; i < n && i < c.rows; i++)
         regions[i] = leon_pipeline_carry_region{b[6 * i], b[6 * i + 1], b[6 * i + 2], b[6 * i + 3], b[6 * i + 4], b[6 * i + 5], {0, 0}};
-    napi_value o, abs[3], ta[3];
-    void* data[3] = {nullptr, nullptr, nullptr};
-    const size_t per[3] = {8, 4, 1};
-    NAPI_OK(napi_create_object(env, &o));
-    for (int k = 0; k < 3; k++) {          // (a new ArrayBuffer is zero-filled: what a refused record keeps)
-        NAPI_OK(napi_create_arraybuffer(env, m * per[k] * 4, &data[k], &abs[k]));
-        NAPI_OK(napi_create_typedarray(env, napi_int32_array, m * per[k], abs[k], 0, &ta[k]));
-    }
-    const int rc = leon_pipeline_carry_regions(h->p, w, regions.data(), (int32_t)std::min<size_t>(n, 65536), static_cast<leon_pipeline_region*>(data[0]),
-                                               static_cast<int32_t*>(data[1]), static_cast<int32_t*>(data[2]));
+    napi_value o, out, votes, status;
+    void *out_data, *votes_data, *status_data;
+    NAPI_OK(make_array(env, napi_int32_array, c.rows * 8, &out_data, &out));
+    NAPI_OK(make_array(env, napi_int32_array, c.rows * 4, &votes_data, &votes));
+    NAPI_OK(make_array(env, napi_int32_array, c.rows, &status_data, &status));
+    const int rc = leon_pipeline_carry_regions(a.h->p, w, regions.data(), c.count, static_cast<leon_pipeline_region*>(out_data), static_cast<int32_t*>(votes_data),
+                                               static_cast<int32_t*>(status_data));
     if (rc != LEON_OK) return throw_leon(env, rc);
-    NAPI_OK(napi_set_named_property(env, o, "out", ta[0]));
-    NAPI_OK(napi_set_named_property(env, o, "votes", ta[1]));
-    NAPI_OK(napi_set_named_property(env, o, "status", ta[2]));
+    NAPI_OK(make_object(env, {{"out", out}, {"votes", votes}, {"status", status}}, &o));
     return o;
 }
 
@@ -865,44 +852,28 @@ napi_value PipeCarryRegions(napi_env env, napi_callback_info info)
 // opts.activity).  regions: an Int32Array of n x [frame index, x, y, width, height]; sources: LEON_GAUGE_* bits.
 napi_value PipeGaugeRegions(napi_env env, napi_callback_info info)
 {
-    size_t argc = 3;
-    napi_value argv[3];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    int32_t sources = 0;
-    napi_typedarray_type tt;
-    size_t len = 0, off = 0;
-    void* words = nullptr;
-    napi_value ab;
-    bool is_ta = false;
-    if (argc < 3 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta ||
-        napi_get_typedarray_info(env, argv[1], &tt, &len, &words, &ab, &off) != napi_ok || tt != napi_int32_array || len % 5 != 0 ||
-        napi_get_value_int32(env, argv[2], &sources) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "gaugeRegions(window, Int32Array of [frame, x, y, width, height] per record, sources)");
-        return nullptr;
-    }
-    const size_t n = len / 5, m = n >= 1 && n <= 65535 ? n : 1;          // (a count the library refuses allocates nothing to speak of here)
-    std::vector<leon_pipeline_region> regions(m);
-    const int32_t* b = static_cast<const int32_t*>(words);
-    for (size_t i = 0; i < n && i < m; i++) regions[i] = leon_pipeline_region{b[5 * i], b[5 * i + 1], b[5 * i + 2], b[5 * i + 3], b[5 * i + 4], {0, 0, 0}};
-    std::vector<int64_t> stats(m * 16, 0);          // (zeros: what a refused record keeps)
-    napi_value o, abs[2], ta[2];
-    void* data[2] = {nullptr, nullptr};
-    NAPI_OK(napi_create_object(env, &o));
-    NAPI_OK(napi_create_arraybuffer(env, m * 16 * 8, &data[0], &abs[0]));
-    NAPI_OK(napi_create_typedarray(env, napi_float64_array, m * 16, abs[0], 0, &ta[0]));
-    NAPI_OK(napi_create_arraybuffer(env, m * 4, &data[1], &abs[1]));
-    NAPI_OK(napi_create_typedarray(env, napi_int32_array, m, abs[1], 0, &ta[1]));
+    Call<PipeHandle> a(env, info, "gaugeRegions(window, Int32Array of [frame, x, y, width, height] per record, sources)");
+    size_t n = 0;
+    const int64_t w = a.i64(0);
+    const int32_t* b = a.rows(1, 5, &n);
+    const int32_t sources = a.i32(2);
+    if (a.bad()) return nullptr;
+    const Count c = record_count(n);
+    std::vector<leon_pipeline_region> regions(c.rows);
+    for (size_t i = 0; i < n && i < c.rows; i++) regions[i] = leon_pipeline_region{b[5 * i], b[5 * i + 1], b[5 * i + 2], b[5 * i + 3], b[5 * i + 4], {0, 0, 0}};
+    std::vector<int64_t> words(c.rows * 16, 0);          // (zeros: what a refused record keeps)
+    napi_value o, stats, status;
+    void *stats_data, *status_data;
+    NAPI_OK(make_array(env, napi_float64_array, c.rows * 16, &stats_data, &stats));
+    NAPI_OK(make_array(env, napi_int32_array, c.rows, &status_data, &status));
     leon_pipeline_gauge_config cfg;
     memset(&cfg, 0, sizeof cfg);
     cfg.sources = sources;
-    const int rc = leon_pipeline_gauge_regions(h->p, w, &cfg, regions.data(), (int32_t)std::min<size_t>(n, 65536), stats.data(), static_cast<int32_t*>(data[1]));
+    const int rc = leon_pipeline_gauge_regions(a.h->p, w, &cfg, regions.data(), c.count, words.data(), static_cast<int32_t*>(status_data));
     if (rc != LEON_OK) return throw_leon(env, rc);
-    double* d = static_cast<double*>(data[0]);
-    for (size_t i = 0; i < m * 16; i++) d[i] = (double)stats[i];
-    NAPI_OK(napi_set_named_property(env, o, "stats", ta[0]));
-    NAPI_OK(napi_set_named_property(env, o, "status", ta[1]));
+    double* d = static_cast<double*>(stats_data);
+    for (size_t i = 0; i < c.rows * 16; i++) d[i] = (double)words[i];
+    NAPI_OK(make_object(env, {{"stats", stats}, {"status", status}}, &o));
     return o;
 }
 
@@ -911,40 +882,26 @@ napi_value PipeGaugeRegions(napi_env env, napi_callback_info info)
 // opts.activity).  frames: an Int32Array of n window frame indices; config: an Int32Array of the 8 words of leon_pipeline_propose_config.
 napi_value PipeProposeRegions(napi_env env, napi_callback_info info)
 {
-    size_t argc = 3;
-    napi_value argv[3];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    napi_typedarray_type tt[2];
-    size_t len[2] = {0, 0}, off = 0;
-    void* words[2] = {nullptr, nullptr};
-    napi_value ab;
-    bool is_ta[2] = {false, false};
-    if (argc < 3 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta[0]) != napi_ok || !is_ta[0] ||
-        napi_is_typedarray(env, argv[2], &is_ta[1]) != napi_ok || !is_ta[1] || napi_get_typedarray_info(env, argv[1], &tt[0], &len[0], &words[0], &ab, &off) != napi_ok ||
-        napi_get_typedarray_info(env, argv[2], &tt[1], &len[1], &words[1], &ab, &off) != napi_ok || tt[0] != napi_int32_array || tt[1] != napi_int32_array || len[1] != 8) {
-        napi_throw_type_error(env, nullptr, "proposeRegions(window, Int32Array of frame indices, Int32Array of the config's 8 words)");
-        return nullptr;
-    }
+    Call<PipeHandle> a(env, info, "proposeRegions(window, Int32Array of frame indices, Int32Array of the config's 8 words)");
+    size_t n = 0, config_words = 0;
+    const int64_t w = a.i64(0);
+    const int32_t* frames = a.rows(1, 1, &n);
+    const void* config = a.array(2, napi_int32_array, &config_words);
+    if (a.bad(config_words != 8)) return nullptr;
     leon_pipeline_propose_config cfg;
-    memcpy(&cfg, words[1], sizeof cfg);
-    const size_t n = len[0], m = n >= 1 && n <= 65535 ? n : 1;          // (a count or a K the library refuses allocates nothing to speak of here)
+    memcpy(&cfg, config, sizeof cfg);
+    const Count c = record_count(n);          // (a K the library refuses allocates nothing to speak of either)
     const size_t K = cfg.max_boxes >= 1 && cfg.max_boxes <= 1024 ? (size_t)cfg.max_boxes : 1;
-    const size_t elems[4] = {m * K * 8, m, m * K * 2, m};
-    const char* names[4] = {"regions", "count", "info", "status"};
-    napi_value o, abs[4], ta[4];
-    void* data[4] = {nullptr, nullptr, nullptr, nullptr};
-    NAPI_OK(napi_create_object(env, &o));
-    for (int i = 0; i < 4; i++) {
-        NAPI_OK(napi_create_arraybuffer(env, elems[i] * 4, &data[i], &abs[i]));          // (zeros: what a refused request keeps)
-        NAPI_OK(napi_create_typedarray(env, napi_int32_array, elems[i], abs[i], 0, &ta[i]));
-    }
-    const int rc = leon_pipeline_propose_regions(h->p, w, &cfg, static_cast<const int32_t*>(words[0]), (int32_t)std::min<size_t>(n, 65536),
-                                                 static_cast<leon_pipeline_region*>(data[0]), static_cast<int32_t*>(data[2]), static_cast<int32_t*>(data[1]),
-                                                 static_cast<int32_t*>(data[3]));
+    napi_value o, regions, count, boxinfo, status;
+    void *regions_data, *count_data, *info_data, *status_data;
+    NAPI_OK(make_array(env, napi_int32_array, c.rows * K * 8, &regions_data, &regions));
+    NAPI_OK(make_array(env, napi_int32_array, c.rows, &count_data, &count));
+    NAPI_OK(make_array(env, napi_int32_array, c.rows * K * 2, &info_data, &boxinfo));
+    NAPI_OK(make_array(env, napi_int32_array, c.rows, &status_data, &status));
+    const int rc = leon_pipeline_propose_regions(a.h->p, w, &cfg, frames, c.count, static_cast<leon_pipeline_region*>(regions_data), static_cast<int32_t*>(info_data),
+                                                 static_cast<int32_t*>(count_data), static_cast<int32_t*>(status_data));
     if (rc != LEON_OK) return throw_leon(env, rc);
-    for (int i = 0; i < 4; i++) NAPI_OK(napi_set_named_property(env, o, names[i], ta[i]));
+    NAPI_OK(make_object(env, {{"regions", regions}, {"count", count}, {"info", boxinfo}, {"status", status}}, &o));
     return o;
 }
 
@@ -955,91 +912,55 @@ napi_value PipeProposeRegions(napi_env env, napi_callback_info info)
 // whose bytes are no multiple of 4 is refused by the library (js/leon_pipeline.js says so).
 napi_value PipePropagateMaps(napi_env env, napi_callback_info info)
 {
-    size_t argc = 7;
-    napi_value argv[7];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    int64_t w = -1;
-    napi_typedarray_type tm, th;
-    size_t mlen = 0, hlen = 0, off = 0;
-    void *maps = nullptr, *words = nullptr;
-    napi_value ab;
-    bool is_m = false, is_h = false;
-    int32_t stride = 0, planes = 0, elem = 0;
-    uint32_t fill = 0;
-    if (argc < 7 || napi_get_value_int64(env, argv[0], &w) != napi_ok || napi_is_typedarray(env, argv[1], &is_m) != napi_ok || !is_m ||
-        napi_get_typedarray_info(env, argv[1], &tm, &mlen, &maps, &ab, &off) != napi_ok || tm != napi_uint8_array ||
-        napi_is_typedarray(env, argv[2], &is_h) != napi_ok || !is_h || napi_get_typedarray_info(env, argv[2], &th, &hlen, &words, &ab, &off) != napi_ok ||
-        th != napi_int32_array || hlen % 4 != 0 || napi_get_value_int32(env, argv[3], &stride) != napi_ok || napi_get_value_int32(env, argv[4], &planes) != napi_ok ||
-        napi_get_value_int32(env, argv[5], &elem) != napi_ok || napi_get_value_uint32(env, argv[6], &fill) != napi_ok) {
-        napi_throw_type_error(env, nullptr, "propagateMaps(window, Uint8Array maps, Int32Array of [target, dst, fwd, bwd] per hop, stride, planes, elemBytes, fill)");
-        return nullptr;
-    }
+    Call<PipeHandle> a(env, info, "propagateMaps(window, Uint8Array maps, Int32Array of [target, dst, fwd, bwd] per hop, stride, planes, elemBytes, fill)");
+    size_t mlen = 0, n = 0;
+    const int64_t w = a.i64(0);
+    void* maps = a.array(1, napi_uint8_array, &mlen);
+    const int32_t* b = a.rows(2, 4, &n);
+    const int32_t stride = a.i32(3), planes = a.i32(4), elem = a.i32(5);
+    const uint32_t fill = a.u32(6);
+    if (a.bad()) return nullptr;
     struct leon_pipeline_propagate_layout lay;
-    int rc = leon_pipeline_propagate_layout(h->info.frame_width, h->info.frame_height, stride, planes, elem, &lay);
+    int rc = leon_pipeline_propagate_layout(a.h->info.frame_width, a.h->info.frame_height, stride, planes, elem, &lay);
     if (rc != LEON_OK) return throw_leon(env, rc);
     if (!lay.slot_bytes || mlen % lay.slot_bytes != 0 || mlen / lay.slot_bytes < 1) {
         napi_throw_type_error(env, nullptr, "propagateMaps: maps is not a whole number of maps of planes * mh * mw * elemBytes bytes");
         return nullptr;
     }
-    const size_t n = hlen / 4, m = n >= 1 && n <= 65535 ? n : 1;          // (a count the library refuses allocates nothing to speak of here)
-    std::vector<leon_pipeline_propagate_hop> hops(m);
-    const int32_t* b = static_cast<const int32_t*>(words);
-    for (size_t i = 0; i < n && i < m; i++) hops[i] = leon_pipeline_propagate_hop{b[4 * i], b[4 * i + 1], b[4 * i + 2], b[4 * i + 3], {0, 0, 0, 0}};
+    const Count c = record_count(n);
+    std::vector<leon_pipeline_propagate_hop> hops(c.rows);
+    for (size_t i = 0; i < n && i < c.rows; i++) hops[i] = leon_pipeline_propagate_hop{b[4 * i], b[4 * i + 1], b[4 * i + 2], b[4 * i + 3], {0, 0, 0, 0}};
     leon_pipeline_propagate_config cfg{};
     cfg.stride = stride; cfg.planes = planes; cfg.elem_bytes = elem;
-    cfg.n_slots = (int32_t)std::min<size_t>(mlen / lay.slot_bytes, 65536);
+    cfg.n_slots = record_count(mlen / lay.slot_bytes).count;
     cfg.fill = fill;
     cfg.slot_pitch_bytes = lay.slot_bytes; cfg.maps_bytes = mlen;
-    napi_value o, abs[2], ta[2];
-    void* data[2] = {nullptr, nullptr};
-    const size_t cells = (size_t)lay.mh * (size_t)lay.mw;
-    NAPI_OK(napi_create_object(env, &o));          // (a new ArrayBuffer is zero-filled: what a refused record keeps)
-    NAPI_OK(napi_create_arraybuffer(env, m * cells, &data[0], &abs[0]));
-    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, m * cells, abs[0], 0, &ta[0]));
-    NAPI_OK(napi_create_arraybuffer(env, m * 4, &data[1], &abs[1]));
-    NAPI_OK(napi_create_typedarray(env, napi_int32_array, m, abs[1], 0, &ta[1]));
-    rc = leon_pipeline_propagate_maps(h->p, w, &cfg, hops.data(), (int32_t)std::min<size_t>(n, 65536), maps, static_cast<uint8_t*>(data[0]), static_cast<int32_t*>(data[1]));
+    napi_value o, via, status;
+    void *via_data, *status_data;
+    NAPI_OK(make_array(env, napi_uint8_array, c.rows * (size_t)lay.mh * (size_t)lay.mw, &via_data, &via));
+    NAPI_OK(make_array(env, napi_int32_array, c.rows, &status_data, &status));
+    rc = leon_pipeline_propagate_maps(a.h->p, w, &cfg, hops.data(), c.count, maps, static_cast<uint8_t*>(via_data), static_cast<int32_t*>(status_data));
     if (rc != LEON_OK) return throw_leon(env, rc);
-    NAPI_OK(napi_set_named_property(env, o, "via", ta[0]));
-    NAPI_OK(napi_set_named_property(env, o, "status", ta[1]));
+    NAPI_OK(make_object(env, {{"via", via}, {"status", status}}, &o));
     return o;
-}
-
-// opts[name] as three floats (an array of numbers); absent: zeros
-bool get_f32x3(napi_env env, napi_value opts, const char* name, float* out)
-{
-    napi_value v, e;
-    bool has = false, is_arr = false;
-    if (napi_has_named_property(env, opts, name, &has) != napi_ok || !has) return true;
-    if (napi_get_named_property(env, opts, name, &v) != napi_ok) return false;
-    napi_valuetype t;
-    if (napi_typeof(env, v, &t) == napi_ok && (t == napi_undefined || t == napi_null)) return true;
-    uint32_t n = 0;
-    if (napi_is_array(env, v, &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, v, &n) != napi_ok || n != 3) return false;
-    for (uint32_t k = 0; k < 3; k++) {
-        double d = 0;
-        if (napi_get_element(env, v, k, &e) != napi_ok || napi_get_value_double(env, e, &d) != napi_ok) return false;
-        out[k] = (float)d;
-    }
-    return true;
 }
 
 napi_value PipeStats(napi_env env, napi_callback_info info)
 {
-    size_t argc = 0;
-    PipeHandle* h = pipe_unwrap(env, info, &argc, nullptr);
-    if (!h) return nullptr;
+    Call<PipeHandle> a(env, info, nullptr);
+    if (a.bad()) return nullptr;
+    PipeHandle* h = a.h;
     leon_pipeline_stats s{};
     leon_pipeline_get_stats(h->p, &s);
     napi_value o, v;
     NAPI_OK(napi_create_object(env, &o));
-    const struct { const char* k; double val; } kv[] = {
+    NAPI_OK(set_numbers(env, o, {
         {"pictures", (double)s.pictures}, {"gops", (double)s.gops}, {"windows", (double)s.windows}, {"streamBytes", (double)s.stream_bytes},
         {"seconds", s.seconds}, {"parseSecondsSum", s.parse_seconds_sum}, {"uploadBytes", s.upload_bytes}, {"entries", (double)s.entries},
         {"frameWidth", (double)h->info.frame_width}, {"frameHeight", (double)h->info.frame_height},
         {"codedWidth", (double)h->info.coded_width}, {"codedHeight", (double)h->info.coded_height},
-        {"pictureRate", h->info.picture_rate}, {"keyMapGops", (double)h->info.gops}, {"shardGops", (double)h->info.shard_gops}, {"firstGop", (double)h->info.first_gop}, {"duration", h->info.duration}, {"parserThreads", (double)h->info.parser_threads},
+        {"pictureRate", h->info.picture_rate}, {"keyMapGops", (double)h->info.gops}, {"shardGops", (double)h->info.shard_gops}, {"firstGop", (double)h->info.first_gop},
+        {"duration", h->info.duration}, {"parserThreads", (double)h->info.parser_threads},
         {"gopsPerWindow", (double)h->info.gops_per_window}, {"output", (double)h->info.output},
         {"chromaWidth", (double)h->info.chroma_width}, {"chromaHeight", (double)h->info.chroma_height},
         {"tensorDtype", (double)h->info.tensor_dtype}, {"tensorElementBytes", (double)h->info.tensor_element_bytes},
@@ -1047,30 +968,23 @@ napi_value PipeStats(napi_env env, napi_callback_info info)
         {"tensorGopPitch", (double)h->info.tensor_gop_pitch}, {"tensorWidth", (double)h->tensor_geom.width}, {"tensorHeight", (double)h->tensor_geom.height},
         // where the resampled image lies in the tensor (leon_pipeline_tensor_canvas; without a canvas: all of it)
         {"tensorImageX", (double)h->tensor_canvas.x}, {"tensorImageY", (double)h->tensor_canvas.y},
-        {"tensorImageWidth", (double)h->tensor_canvas.image_width}, {"tensorImageHeight", (double)h->tensor_canvas.image_height}};
-    for (auto& e : kv) {
-        NAPI_OK(napi_create_double(env, e.val, &v));
-        NAPI_OK(napi_set_named_property(env, o, e.k, v));
-    }
+        {"tensorImageWidth", (double)h->tensor_canvas.image_width}, {"tensorImageHeight", (double)h->tensor_canvas.image_height}}));
     if (h->info.tensor_dtype) {          // the tensors' layout by its option name
         NAPI_OK(napi_create_string_utf8(env, h->tensor_shape.layout == LEON_TENSOR_LAYOUT_HWC ? "hwc" : "chw", NAPI_AUTO_LENGTH, &v));
-        NAPI_OK(napi_set_named_property(env, o, "tensorLayout", v));
+        NAPI_OK(set_props(env, o, {{"tensorLayout", v}}));
     }
     return o;
 }
 
 napi_value PipeDestroy(napi_env env, napi_callback_info info)
 {
-    napi_value self;
-    size_t argc = 0;
-    NAPI_OK(napi_get_cb_info(env, info, &argc, nullptr, &self, nullptr));
-    PipeHandle* h = nullptr;
-    if (napi_unwrap(env, self, (void**)&h) == napi_ok && h && h->p) {
-        leon_pipeline_destroy(h->p);       // joins the notify thread: no further callbacks are queued
-        h->p = nullptr;
-        if (h->tsfn) {
-            napi_release_threadsafe_function(h->tsfn, napi_tsfn_abort);
-            h->tsfn = nullptr;
+    Call<PipeHandle> a(env, info, nullptr, nullptr);
+    if (a.h) {
+        leon_pipeline_destroy(a.h->p);       // joins the notify thread: no further callbacks are queued
+        a.h->p = nullptr;
+        if (a.h->tsfn) {
+            napi_release_threadsafe_function(a.h->tsfn, napi_tsfn_abort);
+            a.h->tsfn = nullptr;
         }
     }
     return nullptr;
@@ -1079,14 +993,11 @@ napi_value PipeDestroy(napi_env env, napi_callback_info info)
 // seek(seconds, exact) -> firstWindow
 napi_value PipeSeek(napi_env env, napi_callback_info info)
 {
-    size_t argc = 2;
-    napi_value argv[2];
-    PipeHandle* h = pipe_unwrap(env, info, &argc, argv);
-    if (!h) return nullptr;
-    double t = 0;
-    bool exact = false;
-    if (argc < 1 || napi_get_value_double(env, argv[0], &t) != napi_ok) { napi_throw_type_error(env, nullptr, "seek(seconds, exact)"); return nullptr; }
-    if (argc >= 2) napi_get_value_bool(env, argv[1], &exact);
+    Call<PipeHandle> a(env, info, "seek(seconds, exact)");
+    const double t = a.f64(0);
+    const bool exact = a.flag(1, false);
+    if (a.bad()) return nullptr;
+    PipeHandle* h = a.h;
     int64_t first = -1;
     const int rc = leon_pipeline_seek(h->p, t, exact ? LEON_PIPELINE_SEEK_EXACT : LEON_PIPELINE_SEEK_KEY, &first);
     if (rc != LEON_OK) return throw_leon(env, rc);
@@ -1102,94 +1013,68 @@ napi_value PipeSeek(napi_env env, napi_callback_info info)
 // feed(validBytes): more of the stream has arrived in the Buffer the pipeline was created on
 napi_value PipeFeed(napi_env env, napi_callback_info info)
 {
-    size_t argc = 1;
-    napi_value argv[1], self;
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, &self, nullptr));
-    PipeHandle* h = nullptr;
-    if (napi_unwrap(env, self, (void**)&h) != napi_ok || !h || !h->p) { napi_throw_error(env, nullptr, "pipeline destroyed"); return nullptr; }
-    int64_t v = -1;
-    if (argc < 1 || napi_get_value_int64(env, argv[0], &v) != napi_ok || v < 0) { napi_throw_type_error(env, nullptr, "feed(validBytes)"); return nullptr; }
-    const int rc = leon_pipeline_feed(h->p, (size_t)v);
+    Call<PipeHandle> a(env, info, "feed(validBytes)", "pipeline destroyed");
+    const int64_t v = a.i64(0);
+    if (a.bad(v < 0)) return nullptr;
+    const int rc = leon_pipeline_feed(a.h->p, (size_t)v);
     return rc == LEON_OK ? nullptr : throw_leon(env, rc);
 }
 
 napi_value CreatePipeline(napi_env env, napi_callback_info info)
 {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, "createPipeline(streamBuffer, options, callback)");
     bool is_buf = false;
-    if (argc >= 1) napi_is_buffer(env, argv[0], &is_buf);
     napi_valuetype cbt = napi_undefined;
-    if (argc >= 3) napi_typeof(env, argv[2], &cbt);
-    if (argc < 3 || !is_buf || cbt != napi_function) {
-        napi_throw_type_error(env, nullptr, "createPipeline(streamBuffer, options, callback)");
-        return nullptr;
-    }
+    napi_is_buffer(env, a.argv[0], &is_buf);
+    napi_typeof(env, a.argv[2], &cbt);
+    if (a.bad(!is_buf || cbt != napi_function)) return nullptr;
+    napi_value opts = a.argv[1];
     void* data = nullptr;
     size_t len = 0;
-    NAPI_OK(napi_get_buffer_info(env, argv[0], &data, &len));
+    NAPI_OK(napi_get_buffer_info(env, a.argv[0], &data, &len));
+    // The integer options, one table per struct of include/leon_pipeline.h (js/leon_pipeline.js maps the names of output, tensorDtype,
+    // tensorFilter and tensorLayout to LEON_PIPELINE_OUTPUT_* bits, LEON_TENSOR_*, LEON_RESIZE_* and LEON_TENSOR_LAYOUT_*, and spreads
+    // tensorSize / tensorCrop / tensorCanvas / tensorOrigin / tensorPadValue / tensorLetterbox into these): the decode itself; the
+    // tensor output's element type; the tensors resampled to a model's input size; their layout; the image placed in a padded canvas.
+    // tensorLetterbox: out size, canvas and origin from leon_pipeline_letterbox of the crop box, or of the frame (the stream's first
+    // sequence header).
     leon_pipeline_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    bool ok = get_i32(env, argv[1], "deviceId", &cfg.device_id, 0) && get_i32(env, argv[1], "parserThreads", &cfg.parser_threads, 0) &&
-              get_i32(env, argv[1], "gopsPerWindow", &cfg.gops_per_window, 0) && get_i32(env, argv[1], "windowsInFlight", &cfg.windows_in_flight, 0) &&
-              get_i32(env, argv[1], "maxGopPictures", &cfg.max_gop_pictures, 0) && get_i32(env, argv[1], "loop", &cfg.loop, 0) &&
-              get_i32(env, argv[1], "shardIndex", &cfg.shard_index, 0) && get_i32(env, argv[1], "shardCount", &cfg.shard_count, 0) &&
-              get_i32(env, argv[1], "gpuParser", &cfg.gpu_parser, 0) && get_i32(env, argv[1], "displayFlavour", &cfg.display_flavour, 0) &&
-              get_i32(env, argv[1], "output", &cfg.output, 0);      // LEON_PIPELINE_OUTPUT_* bits (js/leon_pipeline.js maps the names)
-    {   // startSeconds: begin at the key-map entry at or before this time
-        napi_value v;
-        bool has = false;
-        if (ok && napi_has_named_property(env, argv[1], "startSeconds", &has) == napi_ok && has &&
-            napi_get_named_property(env, argv[1], "startSeconds", &v) == napi_ok) {
-            napi_valuetype t;
-            napi_typeof(env, v, &t);
-            if (t == napi_number) napi_get_value_double(env, v, &cfg.start_seconds);
-        }
-    }
-    // the tensor output's settings (leon_pipeline_tensor_config): tensorDtype LEON_TENSOR_* (js/leon_pipeline.js maps the names),
-    // tensorScale / tensorBias [r, g, b]
     leon_pipeline_tensor_config tcfg;
+    leon_pipeline_tensor_resize rcfg;
+    leon_pipeline_tensor_format fcfg;
+    leon_pipeline_tensor_canvas ccfg;
+    memset(&cfg, 0, sizeof cfg);
     memset(&tcfg, 0, sizeof tcfg);
-    ok = ok && get_i32(env, argv[1], "tensorDtype", &tcfg.dtype, 0);
-    if (!ok) {
+    memset(&rcfg, 0, sizeof rcfg);
+    memset(&fcfg, 0, sizeof fcfg);
+    memset(&ccfg, 0, sizeof ccfg);
+    int32_t lb_w = 0, lb_h = 0, origin_set = 0;
+    const std::vector<IntOpt> tables[5] = {
+        {{"deviceId", &cfg.device_id, 0}, {"parserThreads", &cfg.parser_threads, 0}, {"gopsPerWindow", &cfg.gops_per_window, 0}, {"windowsInFlight", &cfg.windows_in_flight, 0},
+         {"maxGopPictures", &cfg.max_gop_pictures, 0}, {"loop", &cfg.loop, 0}, {"shardIndex", &cfg.shard_index, 0}, {"shardCount", &cfg.shard_count, 0},
+         {"gpuParser", &cfg.gpu_parser, 0}, {"displayFlavour", &cfg.display_flavour, 0}, {"output", &cfg.output, 0}},
+        {{"tensorDtype", &tcfg.dtype, 0}},
+        {{"tensorOutWidth", &rcfg.out_width, 0}, {"tensorOutHeight", &rcfg.out_height, 0}, {"tensorCropX", &rcfg.crop_x, 0}, {"tensorCropY", &rcfg.crop_y, 0},
+         {"tensorCropWidth", &rcfg.crop_width, 0}, {"tensorCropHeight", &rcfg.crop_height, 0}, {"tensorFilter", &rcfg.filter, 0}},
+        {{"tensorLayout", &fcfg.layout, 0}},
+        {{"tensorCanvasWidth", &ccfg.width, 0}, {"tensorCanvasHeight", &ccfg.height, 0}, {"tensorOriginX", &ccfg.x, 0}, {"tensorOriginY", &ccfg.y, 0},
+         {"tensorOriginSet", &origin_set, 0}, {"tensorPadR", &ccfg.pad[0], 0}, {"tensorPadG", &ccfg.pad[1], 0}, {"tensorPadB", &ccfg.pad[2], 0},
+         {"tensorLetterboxWidth", &lb_w, 0}, {"tensorLetterboxHeight", &lb_h, 0}}};
+    size_t bad_table = 5;          // the first table with an option that is no integer
+    for (size_t t = 0; t < 5; t++)
+        for (const IntOpt& o : tables[t])
+            if (!get_i32(env, opts, o.name, o.field, o.dflt) && bad_table == 5) bad_table = t;
+    // tensorScale / tensorBias [r, g, b] stand between the element type and the resize options, and so does their fault
+    const bool bad_scale = !get_f32x3(env, opts, "tensorScale", tcfg.scale) || !get_f32x3(env, opts, "tensorBias", tcfg.bias);
+    if (bad_table < 2 || (bad_table < 5 && !bad_scale)) {
         napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
         return nullptr;
     }
-    if (!get_f32x3(env, argv[1], "tensorScale", tcfg.scale) || !get_f32x3(env, argv[1], "tensorBias", tcfg.bias)) {
+    if (bad_scale) {
         napi_throw_type_error(env, nullptr, "createPipeline: tensorScale / tensorBias must be arrays of three numbers");
         return nullptr;
     }
-    // ... resampled to a model's input size (leon_pipeline_tensor_resize; js/leon_pipeline.js spreads tensorSize / tensorCrop into these and maps tensorFilter's names to LEON_RESIZE_*)
-    leon_pipeline_tensor_resize rcfg;
-    memset(&rcfg, 0, sizeof rcfg);
-    if (!(get_i32(env, argv[1], "tensorOutWidth", &rcfg.out_width, 0) && get_i32(env, argv[1], "tensorOutHeight", &rcfg.out_height, 0) &&
-          get_i32(env, argv[1], "tensorCropX", &rcfg.crop_x, 0) && get_i32(env, argv[1], "tensorCropY", &rcfg.crop_y, 0) &&
-          get_i32(env, argv[1], "tensorCropWidth", &rcfg.crop_width, 0) && get_i32(env, argv[1], "tensorCropHeight", &rcfg.crop_height, 0) &&
-          get_i32(env, argv[1], "tensorFilter", &rcfg.filter, 0))) {
-        napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
-        return nullptr;
-    }
-    // ... and their layout (leon_pipeline_tensor_format; js/leon_pipeline.js maps 'chw' / 'hwc' to LEON_TENSOR_LAYOUT_*)
-    leon_pipeline_tensor_format fcfg;
-    memset(&fcfg, 0, sizeof fcfg);
-    if (!get_i32(env, argv[1], "tensorLayout", &fcfg.layout, 0)) {
-        napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
-        return nullptr;
-    }
-    // ... placed in a padded canvas (leon_pipeline_tensor_canvas; js/leon_pipeline.js spreads tensorCanvas / tensorOrigin / tensorPadValue /
-    // tensorLetterbox into these).  tensorLetterbox: out size, canvas and origin from leon_pipeline_letterbox of the crop box, or of the
-    // frame (the stream's first sequence header)
-    leon_pipeline_tensor_canvas ccfg;
-    memset(&ccfg, 0, sizeof ccfg);
-    int32_t lb_w = 0, lb_h = 0, origin_set = 0;
-    if (!(get_i32(env, argv[1], "tensorCanvasWidth", &ccfg.width, 0) && get_i32(env, argv[1], "tensorCanvasHeight", &ccfg.height, 0) &&
-          get_i32(env, argv[1], "tensorOriginX", &ccfg.x, 0) && get_i32(env, argv[1], "tensorOriginY", &ccfg.y, 0) && get_i32(env, argv[1], "tensorOriginSet", &origin_set, 0) &&
-          get_i32(env, argv[1], "tensorPadR", &ccfg.pad[0], 0) && get_i32(env, argv[1], "tensorPadG", &ccfg.pad[1], 0) && get_i32(env, argv[1], "tensorPadB", &ccfg.pad[2], 0) &&
-          get_i32(env, argv[1], "tensorLetterboxWidth", &lb_w, 0) && get_i32(env, argv[1], "tensorLetterboxHeight", &lb_h, 0))) {
-        napi_throw_type_error(env, nullptr, "createPipeline: integer options expected");
-        return nullptr;
-    }
+    get_f64(env, opts, "startSeconds", &cfg.start_seconds);          // begin at the key-map entry at or before this time (no number: 0)
     if (lb_w || lb_h) {
         if (rcfg.out_width || rcfg.out_height || ccfg.width || ccfg.height || origin_set) {
             napi_throw_type_error(env, nullptr, "createPipeline: tensorLetterbox derives tensorSize, tensorCanvas and tensorOrigin: give it alone");
@@ -1216,46 +1101,29 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     const bool canvas = (ccfg.width | ccfg.height | ccfg.x | ccfg.y | ccfg.pad[0] | ccfg.pad[1] | ccfg.pad[2]) != 0;
     const bool resized = (rcfg.out_width | rcfg.out_height | rcfg.crop_x | rcfg.crop_y | rcfg.crop_width | rcfg.crop_height | rcfg.filter) != 0;
     const bool tensor = (cfg.output & LEON_PIPELINE_OUTPUT_TENSOR) != 0 || tcfg.dtype != 0 || resized || fcfg.layout != 0 || canvas;
-    PipeHandle* h = new PipeHandle();
+    PipeGuard guard{env, new PipeHandle()};
+    PipeHandle* h = guard.h;
     napi_value name;
     NAPI_OK(napi_create_string_utf8(env, "leon pipeline frames", NAPI_AUTO_LENGTH, &name));
-    if (napi_create_threadsafe_function(env, argv[2], nullptr, name, 0, 1, nullptr, nullptr, h, pipe_call_js, &h->tsfn) != napi_ok) {
-        delete h;
+    if (napi_create_threadsafe_function(env, a.argv[2], nullptr, name, 0, 1, nullptr, nullptr, h, pipe_call_js, &h->tsfn) != napi_ok) {
         napi_throw_error(env, nullptr, "napi_create_threadsafe_function failed");
         return nullptr;
     }
-    napi_create_reference(env, argv[0], 1, &h->stream_ref);
+    napi_create_reference(env, a.argv[0], 1, &h->stream_ref);
     // validBytes: the stream is still arriving (leon_pipeline_create_partial) -- the loader writes on into the same
     // Buffer and calls feed(validBytesNow), as addBuffer does in the reference (features/bitreader.js:332-430)
     // (a presence test and a double, not an int32 with -1 for "absent": 2 GiB and more of a stream may have arrived)
-    bool partial = false;
     double valid = 0;
-    {
-        napi_value v;
-        bool has = false;
-        if (napi_has_named_property(env, argv[1], "validBytes", &has) == napi_ok && has && napi_get_named_property(env, argv[1], "validBytes", &v) == napi_ok) {
-            napi_valuetype t;
-            if (napi_typeof(env, v, &t) == napi_ok && t != napi_undefined && t != napi_null) {
-                if (t != napi_number || napi_get_value_double(env, v, &valid) != napi_ok || !(valid >= 0) || valid > (double)len || valid != (double)(size_t)valid) {
-                    napi_release_threadsafe_function(h->tsfn, napi_tsfn_abort);
-                    napi_delete_reference(env, h->stream_ref);
-                    delete h;
-                    napi_throw_range_error(env, nullptr, "createPipeline: validBytes must be an integer between 0 and the stream's length");
-                    return nullptr;
-                }
-                partial = true;
-            }
-        }
+    const int given = get_f64(env, opts, "validBytes", &valid);
+    if (given < 0 || (given > 0 && (!(valid >= 0) || valid > (double)len || valid != (double)(size_t)valid))) {
+        napi_throw_range_error(env, nullptr, "createPipeline: validBytes must be an integer between 0 and the stream's length");
+        return nullptr;
     }
+    const bool partial = given > 0;
     int rc = tensor ? leon_pipeline_create_tensor_canvas(&cfg, &tcfg, resized ? &rcfg : nullptr, fcfg.layout ? &fcfg : nullptr, canvas ? &ccfg : nullptr, (const uint8_t*)data, len, partial ? (size_t)valid : len, pipe_native_cb, h, &h->p)
            : partial ? leon_pipeline_create_partial(&cfg, (const uint8_t*)data, len, (size_t)valid, pipe_native_cb, h, &h->p)
                      : leon_pipeline_create(&cfg, (const uint8_t*)data, len, pipe_native_cb, h, &h->p);
-    if (rc != LEON_OK) {
-        napi_release_threadsafe_function(h->tsfn, napi_tsfn_abort);
-        napi_delete_reference(env, h->stream_ref);
-        delete h;
-        return throw_leon(env, rc);
-    }
+    if (rc != LEON_OK) return throw_leon(env, rc);
     leon_pipeline_get_info(h->p, &h->info);
     if (h->info.tensor_dtype) {
         leon_pipeline_get_tensor_geometry(h->p, &h->tensor_geom);
@@ -1265,33 +1133,27 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
     napi_value obj;
     NAPI_OK(napi_create_object(env, &obj));
     NAPI_OK(napi_wrap(env, obj, h, pipe_finalize, nullptr, nullptr));
-    const struct { const char* name; napi_callback fn; } methods[] = {
-        {"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor}, {"readMotion", PipeReadMotion}, {"readActivity", PipeReadActivity}, {"readResidual", PipeReadResidual},{"readRegions", PipeReadRegions}, {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"gaugeRegions", PipeGaugeRegions}, {"proposeRegions", PipeProposeRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed}, {"seek", PipeSeek}};
-    for (auto& m : methods) {
-        napi_value fn;
-        NAPI_OK(napi_create_function(env, m.name, NAPI_AUTO_LENGTH, m.fn, nullptr, &fn));
-        NAPI_OK(napi_set_named_property(env, obj, m.name, fn));
-    }
+    guard.h = nullptr;          // the object owns it now (pipe_finalize)
+    NAPI_OK(define_methods(env, obj, {{"releaseWindow", PipeRelease}, {"readFrame", PipeReadFrame}, {"readPlanes", PipeReadPlanes}, {"readTensor", PipeReadTensor},
+                                      {"readMotion", PipeReadMotion}, {"readActivity", PipeReadActivity}, {"readResidual", PipeReadResidual}, {"readRegions", PipeReadRegions},
+                                      {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"gaugeRegions", PipeGaugeRegions},
+                                      {"proposeRegions", PipeProposeRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed},
+                                      {"seek", PipeSeek}}));
     return obj;
 }
 
 // letterbox(srcWidth, srcHeight, canvasWidth, canvasHeight) -> [outWidth, outHeight, x, y]: leon_pipeline_letterbox, no device
 napi_value Letterbox(napi_env env, napi_callback_info info)
 {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    int32_t a[4] = {0, 0, 0, 0};
-    for (size_t k = 0; k < 4; k++)
-        if (argc < 4 || napi_get_value_int32(env, argv[k], &a[k]) != napi_ok) {
-            napi_throw_type_error(env, nullptr, "letterbox(srcWidth, srcHeight, canvasWidth, canvasHeight)");
-            return nullptr;
-        }
+    Args a(env, info, "letterbox(srcWidth, srcHeight, canvasWidth, canvasHeight)");
+    int32_t s[4];
+    for (size_t k = 0; k < 4; k++) s[k] = a.i32(k);
+    if (a.bad()) return nullptr;
     leon_pipeline_tensor_resize rz;
     leon_pipeline_tensor_canvas cv;
     memset(&rz, 0, sizeof rz);
     memset(&cv, 0, sizeof cv);
-    const int rc = leon_pipeline_letterbox(a[0], a[1], a[2], a[3], &rz, &cv);
+    const int rc = leon_pipeline_letterbox(s[0], s[1], s[2], s[3], &rz, &cv);
     if (rc != LEON_OK) return throw_leon(env, rc);
     const int32_t r[4] = {rz.out_width, rz.out_height, cv.x, cv.y};
     napi_value arr, v;
@@ -1316,15 +1178,7 @@ napi_value Init(napi_env env, napi_value exports)
         napi_throw_error(env, nullptr, "leon_napi: libleon_hip.so speaks another ABI version than this addon was built for; rebuild both");
         return exports;
     }
-    napi_value fn;
-    NAPI_OK(napi_create_function(env, "create", NAPI_AUTO_LENGTH, Create, nullptr, &fn));
-    NAPI_OK(napi_set_named_property(env, exports, "create", fn));
-    NAPI_OK(napi_create_function(env, "createPipeline", NAPI_AUTO_LENGTH, CreatePipeline, nullptr, &fn));
-    NAPI_OK(napi_set_named_property(env, exports, "createPipeline", fn));
-    NAPI_OK(napi_create_function(env, "letterbox", NAPI_AUTO_LENGTH, Letterbox, nullptr, &fn));
-    NAPI_OK(napi_set_named_property(env, exports, "letterbox", fn));
-    NAPI_OK(napi_create_function(env, "abiVersion", NAPI_AUTO_LENGTH, AbiVersion, nullptr, &fn));
-    NAPI_OK(napi_set_named_property(env, exports, "abiVersion", fn));
+    NAPI_OK(define_methods(env, exports, {{"create", Create}, {"createPipeline", CreatePipeline}, {"letterbox", Letterbox}, {"abiVersion", AbiVersion}}));
     return exports;
 }
 
