@@ -1214,6 +1214,114 @@ int leon_pipeline_propose_regions(leon_pipeline* p, int64_t window, const leon_p
 int leon_pipeline_propose_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
                                  const void* const* motion_records_host, const void* const* activity_records_host, const leon_pipeline_propose_config* cfg,
                                  const int32_t* frames, int32_t n, leon_pipeline_region* regions, int32_t* info, int32_t* count, int32_t* status);
+/* Boxes compared with each other: the two steps of a detection loop that the calls above leave out -- PRUNING a set of boxes that
+ * overlap (leon_pipeline_suppress_regions: greedy suppression, what a detector's raw output and the nested boxes of
+ * leon_pipeline_propose_regions want before they are resampled or carried) and ASSOCIATING two sets (leon_pipeline_match_regions:
+ * greedy one-to-one matching, e.g. the boxes carried to the end of a GOP with the detections on the next I picture) -- on
+ * leon_pipeline_region rows in device memory, so that no box visits the host.  Integers only, everything in int64; one text for host
+ * and device (csrc/leon_overlap.h).  The calls read no record and no frame: a pipeline of any output takes them; of the window they
+ * use the frame count, of the pipeline the frame size.
+ * Rows and sets.  A set is K consecutive rows (1 .. 1024); a call has n sets (1 .. 65535): the [n, K, 8] arrays that the propose and
+ * carry calls write go in as they are.  Every row is judged as leon_pipeline_gauge_regions judges it, in that order:
+ * LEON_REGION_RESERVED (a non-zero reserved word), LEON_REGION_FRAME (frame outside the window), LEON_REGION_BOX (an empty box, or one
+ * that leaves the frame).  A refused row takes no part: it suppresses and matches nothing and none of its per-row outputs is written
+ * (the status word apart) -- the filler rows of propose and the refused rows of carry drop out by themselves.  A ROW'S FAULT IS A
+ * STATUS WORD ON BOTH ROADS, NEVER AN ERROR OF THE CALL.  The frame word is judged and otherwise ignored: overlap is a matter of pixel
+ * coordinates, so rows on different frames of the window compare like rows on one.
+ * Overlap of two accepted rows a and b: iw = min(ax + aw, bx + bw) - max(ax, bx), ih likewise, inter = max(iw, 0) * max(ih, 0);
+ *     LEON_OVERLAP_IOU    den = aw * ah + bw * bh - inter
+ *     LEON_OVERLAP_IOMIN  den = min(aw * ah, bw * bh)           (a nested box overlaps in full)
+ * The pair REACHES the threshold iff inter * 65536 >= cfg.threshold * den; threshold is Q16, 1 .. 65536, so boxes that only touch
+ * never reach it.  Frames are at most 4096 x 4096: inter <= 2^24, den <= 2^25, every product below 2^50.
+ * Suppress, per set.  Row i's score is scores[(set * K + i) * score_stride] (int32; score_stride 1 .. 8 words; scores NULL: every
+ * score 0).  The accepted rows are walked by descending score, ties by ascending row index; a row is KEPT iff no row kept before it
+ * reaches the threshold with it.  by[n][K]: -1 for a kept row, else the row index of the first kept row in walk order that reaches
+ * the threshold with it; count[n]: the kept rows; out[n][K] (may be NULL): the kept rows in walk order as {frame, x, y, w, h, 0, 0,
+ * 0}, rows count .. K - 1 eight zero words (which the sibling calls refuse as LEON_REGION_BOX: out goes into them as it is);
+ * order[n][K] (may be NULL): the input row index of each row of out, -1 behind count; status[n][K] (may be NULL).  Every byte of
+ * count, out and order is written for every set, by for every accepted row.
+ * Match, per pair of sets: set s of a ([n][ka]) against set s of b ([n][kb]), ka and kb each 1 .. 1024.  The candidates are the pairs
+ * (i, j) of accepted rows that reach the threshold, in the order of inter / den descending -- compared exactly, inter1 * den2
+ * against inter2 * den1 --, ties by the smaller i, then the smaller j; walking that order a pair is TAKEN iff neither of its rows
+ * has been.  match_a[n][ka]: j or -1; match_b[n][kb]: i or -1; overlap[n][ka]: floor(inter * 65536 / den) of the taken pair, else 0;
+ * count[n]: the pairs taken; status_a, status_b (may be NULL).  The words of a refused row are not written.
+ * One launch per call (k_suppress / k_match: a workgroup of 256 threads a set or pair, everything in LDS -- suppress: 16 bytes a row
+ * of boxes, a 64-bit key (score, index) for each of K rounded up to a power of two, sorted bitonically, two dwords a row: 32768
+ * bytes at K = 1024; match: 24 bytes a row of either set and a dword: 49156 bytes at 1024 and 1024).  k_match repeats "every free row
+ * finds its best free partner, mutual best pairs are taken", which gives the greedy result; sets of IDENTICAL boxes are its worst
+ * case, one pair a round.  Nothing is launched on the decoder's stream. */
+#define LEON_OVERLAP_IOU   0
+#define LEON_OVERLAP_IOMIN 1
+typedef struct leon_pipeline_overlap_config {
+    int32_t measure;                       /* LEON_OVERLAP_IOU or LEON_OVERLAP_IOMIN */
+    int32_t threshold;                     /* Q16, 1 .. 65536 */
+    int32_t reserved[2];                   /* must be 0 */
+} leon_pipeline_overlap_config;            /* 16 bytes */
+typedef struct leon_pipeline_suppress_regions_call {
+    const leon_pipeline_region* regions;   /* DEVICE memory, n x k records, 4-byte aligned */
+    const int32_t* scores;                 /* DEVICE memory, n x k x score_stride words, 4-byte aligned, may be NULL */
+    int32_t  n;                            /* sets, 1 .. 65535 */
+    int32_t  k;                            /* rows of a set, 1 .. 1024 */
+    int32_t  score_stride;                 /* words from one row's score to the next, 1 .. 8 (also with scores NULL) */
+    int32_t  reserved0;                    /* must be 0 */
+    leon_pipeline_region* device_out;      /* DEVICE memory, n x k records, 4-byte aligned, may be NULL */
+    int32_t* device_order;                 /* DEVICE memory, n x k words, 4-byte aligned, may be NULL */
+    int32_t* device_by;                    /* DEVICE memory, n x k words, 4-byte aligned */
+    int32_t* device_count;                 /* DEVICE memory, n words, 4-byte aligned */
+    int32_t* device_status;                /* DEVICE memory, n x k words, 4-byte aligned, may be NULL */
+    void*    stream;                       /* hipStream_t of the caller's; NULL: the pipeline's regions stream, and the call waits */
+    uint64_t reserved[2];                  /* must be 0 */
+} leon_pipeline_suppress_regions_call;     /* 96 bytes */
+typedef struct leon_pipeline_match_regions_call {
+    const leon_pipeline_region* a;         /* DEVICE memory, n x ka records, 4-byte aligned */
+    const leon_pipeline_region* b;         /* DEVICE memory, n x kb records, 4-byte aligned */
+    int32_t  n;                            /* pairs of sets, 1 .. 65535 */
+    int32_t  ka, kb;                       /* rows of a set of a and of b, each 1 .. 1024 */
+    int32_t  reserved0;                    /* must be 0 */
+    int32_t* device_match_a;               /* DEVICE memory, n x ka words, 4-byte aligned */
+    int32_t* device_match_b;               /* DEVICE memory, n x kb words, 4-byte aligned */
+    int32_t* device_overlap;               /* DEVICE memory, n x ka words, 4-byte aligned */
+    int32_t* device_count;                 /* DEVICE memory, n words, 4-byte aligned */
+    int32_t* device_status_a;              /* DEVICE memory, n x ka words, 4-byte aligned, may be NULL */
+    int32_t* device_status_b;              /* DEVICE memory, n x kb words, 4-byte aligned, may be NULL */
+    void*    stream;                       /* as above */
+    uint64_t reserved[1];                  /* must be 0 */
+} leon_pipeline_match_regions_call;        /* 96 bytes */
+/* host only: the definitions on the CPU for ONE set (pair of sets) in host memory -- a stable sort and a walk that share no text with
+ * the kernels' steps.  Return LEON_OK, or LEON_ERR_INVALID (nothing written) for, in this order: a null cfg, a measure outside 0 ..
+ * 1, a threshold outside 1 .. 65536, a non-zero reserved word of cfg; a frame outside 1 .. 4096 on an axis, n_frames < 0; k (ka, kb)
+ * outside 1 .. 1024; score_stride outside 1 .. 8; a null regions, by or count (a, b, match_a, match_b, overlap or count). */
+int32_t leon_pipeline_suppress_record(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_overlap_config* cfg,
+                                      const leon_pipeline_region* regions, int32_t k, const int32_t* scores, int32_t score_stride, leon_pipeline_region* out,
+                                      int32_t* order, int32_t* by, int32_t* count, int32_t* status);
+int32_t leon_pipeline_match_record(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* a,
+                                   int32_t ka, const leon_pipeline_region* b, int32_t kb, int32_t* match_a, int32_t* match_b, int32_t* overlap, int32_t* count,
+                                   int32_t* status_a, int32_t* status_b);
+/* Sets in DEVICE memory: the calls ONLY ENQUEUE on the caller's stream (stream NULL: the regions stream, and the call waits), with
+ * leon_pipeline_carry_regions_device's ordering rules and its scratch event, word for word.  Refused (LEON_ERR_INVALID, nothing
+ * enqueued), in this order: a null cfg, a measure outside 0 .. 1, a threshold outside 1 .. 65536, a non-zero reserved word of cfg; a
+ * null call; a window that is not out for delivery or was delivered with an error; a non-zero reserved word of the call; n outside
+ * 1 .. 65535, k (ka, kb) outside 1 .. 1024; score_stride outside 1 .. 8; a null regions, device_by or device_count (a, b,
+ * device_match_a, device_match_b, device_overlap or device_count); a pointer that is not 4-byte aligned. */
+int leon_pipeline_suppress_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_suppress_regions_call* call);
+int leon_pipeline_match_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_match_regions_call* call);
+/* Sets in host memory, results to host memory, synchronous: the device road between an upload and the copies back.  Every output
+ * goes up and comes back whole, so a refused row's words stay as the caller had them.  The call-level refusals are the device
+ * road's. */
+int leon_pipeline_suppress_regions(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* regions, int32_t n, int32_t k,
+                                   const int32_t* scores, int32_t score_stride, leon_pipeline_region* out, int32_t* order, int32_t* by, int32_t* count, int32_t* status);
+int leon_pipeline_match_regions(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* a, int32_t ka,
+                                const leon_pipeline_region* b, int32_t kb, int32_t n, int32_t* match_a, int32_t* match_b, int32_t* overlap, int32_t* count,
+                                int32_t* status_a, int32_t* status_b);
+/* Diagnostics in the manner of leon_pipeline_gauge_kernel: k_suppress / k_match on rows the CALLER supplies (host memory) for a frame
+ * size and a frame count the caller names, with memory of their own on device_id's null stream, synchronous; the outputs go up and
+ * come back whole.  Refused (LEON_ERR_INVALID): what the record calls refuse, n outside 1 .. 65535. */
+int leon_pipeline_suppress_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_overlap_config* cfg,
+                                  const leon_pipeline_region* regions, int32_t n, int32_t k, const int32_t* scores, int32_t score_stride, leon_pipeline_region* out,
+                                  int32_t* order, int32_t* by, int32_t* count, int32_t* status);
+int leon_pipeline_match_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_overlap_config* cfg,
+                               const leon_pipeline_region* a, int32_t ka, const leon_pipeline_region* b, int32_t kb, int32_t n, int32_t* match_a, int32_t* match_b,
+                               int32_t* overlap, int32_t* count, int32_t* status_a, int32_t* status_b);
 /* A diagnostic: the DEVICE's evaluation of the tables of n_axes single axes, copied back, to be compared word for word with
  * leon_pipeline_resize_weights (pixels would hide a weight that is one unit off).  axes = n_axes x {in_size, crop_start, crop_size,
  * out_size}; with max_out the largest out_size of the batch, axis a's tables lie at a fixed pitch: first[a * max_out + o],

@@ -46,6 +46,7 @@
 #include "leon_propagate.h"
 #include "leon_gauge.h"
 #include "leon_propose.h"
+#include "leon_overlap.h"
 
 
 namespace leon {

@@ -2878,6 +2878,279 @@ int propose_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int32
     });
 }
 
+// ---- boxes compared by overlap: suppression inside a set, matching of two sets (leon_pipeline_suppress_regions, _match_regions) ----
+static_assert(sizeof(leon_pipeline_overlap_config) == 16 && sizeof(leon_pipeline_suppress_regions_call) == 96 && sizeof(leon_pipeline_match_regions_call) == 96 &&
+              sizeof(leon::OverlapConfig) == 16 && sizeof(leon::OverlapCall) == 40, "include/leon_pipeline.h states the sizes");
+static_assert(leon::kOverlapIou == LEON_OVERLAP_IOU && leon::kOverlapIomin == LEON_OVERLAP_IOMIN && leon::kOverlapMaxRows == leon::kProposeMaxBoxes,
+              "the kernels' words are the header's");
+// a CU's LDS holds the largest set and the largest pair
+static_assert(leon::suppress_lds(leon::kOverlapMaxRows).bytes == 32768 && leon::match_lds(leon::kOverlapMaxRows, leon::kOverlapMaxRows).bytes == 49156 && 49156 <= 160 * 1024,
+              "include/leon_pipeline.h states the LDS");
+
+int overlap_config_check(const char* who, const leon_pipeline_overlap_config* cfg)
+{
+    if (!cfg) return fail(LEON_ERR_INVALID, "null argument");
+    if (cfg->measure != LEON_OVERLAP_IOU && cfg->measure != LEON_OVERLAP_IOMIN) return fail(LEON_ERR_INVALID, "%s: measure %d (LEON_OVERLAP_IOU 0, LEON_OVERLAP_IOMIN 1)", who, cfg->measure);
+    if (cfg->threshold < 1 || cfg->threshold > leon::kOverlapMaxThreshold) return fail(LEON_ERR_INVALID, "%s: threshold %d (Q16, 1 .. 65536)", who, cfg->threshold);
+    if (cfg->reserved[0] || cfg->reserved[1]) return fail(LEON_ERR_INVALID, "%s: a reserved word of the config is not 0", who);
+    return LEON_OK;
+}
+// the rows of a set, and a suppress call's stride
+int overlap_rows_check(const char* who, const char* noun, int32_t k)
+{
+    return k < 1 || k > leon::kOverlapMaxRows ? fail(LEON_ERR_INVALID, "%s: %s %d (a set has 1 .. 1024 rows)", who, noun, k) : LEON_OK;
+}
+int overlap_stride_check(int32_t score_stride)
+{
+    return score_stride < 1 || score_stride > leon::kOverlapMaxStride ? fail(LEON_ERR_INVALID, "suppress regions: score_stride %d (1 .. 8 words)", score_stride) : LEON_OK;
+}
+// the frame a record or diagnostic call names itself
+int overlap_geometry_check(const char* who, int32_t fw, int32_t fh, int32_t n_frames)
+{
+    if (fw < 1 || fw > leon::kOverlapMaxFrame || fh < 1 || fh > leon::kOverlapMaxFrame) return fail(LEON_ERR_INVALID, "%s: a frame of %d x %d (1 .. 4096 an axis)", who, fw, fh);
+    if (n_frames < 0) return fail(LEON_ERR_INVALID, "%s: %d frames", who, n_frames);
+    return LEON_OK;
+}
+leon::OverlapCall overlap_call(const leon_pipeline_overlap_config& cfg, int32_t fw, int32_t fh, int32_t n_frames, int32_t n, int32_t ka, int32_t kb, int32_t score_stride)
+{
+    leon::OverlapCall C{};
+    C.measure = cfg.measure; C.threshold = cfg.threshold;
+    C.fw = fw; C.fh = fh; C.n_frames = n_frames;
+    C.n = n; C.ka = ka; C.kb = kb;
+    C.score_stride = score_stride;
+    return C;
+}
+
+// the launches every road shares: a workgroup a set (pair), its LDS as leon_overlap.h lays it out for this K -- above 48 KiB the kernel
+// is told so
+int suppress_launch(hipStream_t st, const leon::OverlapCall& C, const int32_t* d_rows, const int32_t* d_scores, int32_t* d_out, int32_t* d_order, int32_t* d_by,
+                    int32_t* d_count, int32_t* d_status)
+{
+    const uint32_t lds = leon::suppress_lds((uint32_t)C.ka).bytes;
+    if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)leon::k_suppress, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(leon::k_suppress, dim3((unsigned)C.n), dim3(leon::kOverlapThreads), lds, st, d_rows, d_scores, d_out, d_order, d_by, d_count, d_status, C);
+    return LEON_OK;
+}
+int match_launch(hipStream_t st, const leon::OverlapCall& C, const int32_t* d_a, const int32_t* d_b, int32_t* d_match_a, int32_t* d_match_b, int32_t* d_overlap,
+                 int32_t* d_count, int32_t* d_status_a, int32_t* d_status_b)
+{
+    const uint32_t lds = leon::match_lds((uint32_t)C.ka, (uint32_t)C.kb).bytes;
+    if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)leon::k_match, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(leon::k_match, dim3((unsigned)C.n), dim3(leon::kOverlapThreads), lds, st, d_a, d_b, d_match_a, d_match_b, d_overlap, d_count, d_status_a, d_status_b, C);
+    return LEON_OK;
+}
+
+// the frames of a window that is out for delivery: from the window itself -- its tables are only built for the outputs that need them
+int overlap_window_frames(leon_pipeline* p, int64_t window, int32_t* n_frames)
+{
+    return window_delivered(p, window, [&](const PipeWindow& w) { *n_frames = (int32_t)w.frames.size(); });
+}
+
+// The head of both device roads: the config, the call, regions_mu, the window, the call's reserved words, then the family's own checks
+// (`checks()`: counts, null pointers, alignment), then inside the boxes bracket -- whose table is the window's frame count alone: the
+// kernels read no ring -- `launch(st, n_frames)` on the caller's stream (or the regions stream and a wait)
+template <class Call, class Checks, class Launch>
+int overlap_road(leon_pipeline* p, int64_t window, const char* who, const leon_pipeline_overlap_config* cfg, const Call* c, Checks checks, Launch launch)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = overlap_config_check(who, cfg);
+    if (rc != LEON_OK) return rc;
+    if (!c) return fail(LEON_ERR_INVALID, "null argument");
+    std::unique_lock<std::mutex> call(p->regions_mu);
+    int32_t n_frames = 0;
+    if ((rc = overlap_window_frames(p, window, &n_frames)) != LEON_OK) return rc;
+    if ((rc = checks()) != LEON_OK) return rc;
+    int launched = LEON_OK;
+    const std::vector<uint32_t> table(1, (uint32_t)n_frames);
+    rc = boxes_run(p, c->stream, call, table, pad256(4), [&](hipStream_t st, uint32_t*) { launched = launch(st, n_frames); });
+    return rc != LEON_OK ? rc : launched;
+}
+
+int suppress_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_suppress_regions_call* c)
+{
+    const char* who = "suppress regions";
+    return overlap_road(p, window, who, cfg, c, [&] {
+        if (c->reserved0 || c->reserved[0] || c->reserved[1]) return fail(LEON_ERR_INVALID, "%s: a reserved word of the call is not 0", who);
+        int rc = record_count_check(who, "sets", c->n);
+        if (rc != LEON_OK || (rc = overlap_rows_check(who, "k", c->k)) != LEON_OK || (rc = overlap_stride_check(c->score_stride)) != LEON_OK) return rc;
+        if (!c->regions || !c->device_by || !c->device_count)
+            return fail(LEON_ERR_INVALID, "%s: null %s", who, !c->regions ? "regions" : !c->device_by ? "device_by" : "device_count");
+        if (((uintptr_t)c->regions | (uintptr_t)c->scores | (uintptr_t)c->device_out | (uintptr_t)c->device_order | (uintptr_t)c->device_by | (uintptr_t)c->device_count |
+             (uintptr_t)c->device_status) & 3u)
+            return fail(LEON_ERR_INVALID, "%s: regions %p, scores %p, device_out %p, device_order %p, device_by %p, device_count %p, device_status %p: not all 4-byte aligned",
+                        who, (const void*)c->regions, (const void*)c->scores, (void*)c->device_out, (void*)c->device_order, (void*)c->device_by, (void*)c->device_count,
+                        (void*)c->device_status);
+        return (int)LEON_OK;
+    }, [&](hipStream_t st, int32_t n_frames) {
+        return suppress_launch(st, overlap_call(*cfg, p->vinfo.frame_width, p->vinfo.frame_height, n_frames, c->n, c->k, 0, c->score_stride),
+                               reinterpret_cast<const int32_t*>(c->regions), c->scores, reinterpret_cast<int32_t*>(c->device_out), c->device_order, c->device_by, c->device_count,
+                               c->device_status);
+    });
+}
+
+int match_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_match_regions_call* c)
+{
+    const char* who = "match regions";
+    return overlap_road(p, window, who, cfg, c, [&] {
+        if (c->reserved0 || c->reserved[0]) return fail(LEON_ERR_INVALID, "%s: a reserved word of the call is not 0", who);
+        int rc = record_count_check(who, "pairs of sets", c->n);
+        if (rc != LEON_OK || (rc = overlap_rows_check(who, "ka", c->ka)) != LEON_OK || (rc = overlap_rows_check(who, "kb", c->kb)) != LEON_OK) return rc;
+        if (!c->a || !c->b || !c->device_match_a || !c->device_match_b || !c->device_overlap || !c->device_count)
+            return fail(LEON_ERR_INVALID, "%s: null %s", who,
+                        !c->a ? "a" : !c->b ? "b" : !c->device_match_a ? "device_match_a" : !c->device_match_b ? "device_match_b" : !c->device_overlap ? "device_overlap" : "device_count");
+        if (((uintptr_t)c->a | (uintptr_t)c->b | (uintptr_t)c->device_match_a | (uintptr_t)c->device_match_b | (uintptr_t)c->device_overlap | (uintptr_t)c->device_count |
+             (uintptr_t)c->device_status_a | (uintptr_t)c->device_status_b) & 3u)
+            return fail(LEON_ERR_INVALID, "%s: a %p, b %p, device_match_a %p, device_match_b %p, device_overlap %p, device_count %p, device_status_a %p, device_status_b %p: "
+                        "not all 4-byte aligned", who, (const void*)c->a, (const void*)c->b, (void*)c->device_match_a, (void*)c->device_match_b, (void*)c->device_overlap,
+                        (void*)c->device_count, (void*)c->device_status_a, (void*)c->device_status_b);
+        return (int)LEON_OK;
+    }, [&](hipStream_t st, int32_t n_frames) {
+        return match_launch(st, overlap_call(*cfg, p->vinfo.frame_width, p->vinfo.frame_height, n_frames, c->n, c->ka, c->kb, 1), reinterpret_cast<const int32_t*>(c->a),
+                            reinterpret_cast<const int32_t*>(c->b), c->device_match_a, c->device_match_b, c->device_overlap, c->device_count, c->device_status_a,
+                            c->device_status_b);
+    });
+}
+
+// what the host roads, the record calls and the diagnostics judge of their own arguments, in the device road's order
+int suppress_args_check(const leon_pipeline_overlap_config* cfg, int32_t n, int32_t k, int32_t score_stride, const void* regions, const void* by, const void* count)
+{
+    const char* who = "suppress regions";
+    int rc = overlap_config_check(who, cfg);
+    if (rc != LEON_OK || (rc = record_count_check(who, "sets", n)) != LEON_OK || (rc = overlap_rows_check(who, "k", k)) != LEON_OK ||
+        (rc = overlap_stride_check(score_stride)) != LEON_OK)
+        return rc;
+    if (!regions || !by || !count) return fail(LEON_ERR_INVALID, "%s: null %s", who, !regions ? "regions" : !by ? "by" : "count");
+    return LEON_OK;
+}
+int match_args_check(const leon_pipeline_overlap_config* cfg, int32_t n, int32_t ka, int32_t kb, const void* a, const void* b, const void* match_a, const void* match_b,
+                     const void* overlap, const void* count)
+{
+    const char* who = "match regions";
+    int rc = overlap_config_check(who, cfg);
+    if (rc != LEON_OK || (rc = record_count_check(who, "pairs of sets", n)) != LEON_OK || (rc = overlap_rows_check(who, "ka", ka)) != LEON_OK ||
+        (rc = overlap_rows_check(who, "kb", kb)) != LEON_OK)
+        return rc;
+    if (!a || !b || !match_a || !match_b || !overlap || !count)
+        return fail(LEON_ERR_INVALID, "%s: null %s", who, !a ? "a" : !b ? "b" : !match_a ? "match_a" : !match_b ? "match_b" : !overlap ? "overlap" : "count");
+    return LEON_OK;
+}
+
+// the pieces of a suppress call that goes up and comes back: [out | order | by | count | status | rows | scores]
+#define LEON_SUPPRESS_PIECES {{out, out, rows * 32}, {order, order, rows * 4}, {by, by, rows * 4}, {count, count, (size_t)n * 4}, {status, status, rows * 4}, \
+                              {regions, nullptr, rows * 32}, {scores, nullptr, scores ? rows * 4 * (size_t)score_stride : 0}}
+#define LEON_MATCH_PIECES {{match_a, match_a, ra * 4}, {match_b, match_b, rb * 4}, {overlap, overlap, ra * 4}, {count, count, (size_t)n * 4}, {status_a, status_a, ra * 4}, \
+                           {status_b, status_b, rb * 4}, {a, nullptr, ra * 32}, {b, nullptr, rb * 32}}
+
+int suppress_regions(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* regions, int32_t n, int32_t k,
+                     const int32_t* scores, int32_t score_stride, leon_pipeline_region* out, int32_t* order, int32_t* by, int32_t* count, int32_t* status)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = overlap_config_check("suppress regions", cfg);
+    if (rc != LEON_OK) return rc;
+    int32_t n_frames = 0;
+    {
+        std::unique_lock<std::mutex> call(p->regions_mu);
+        if ((rc = overlap_window_frames(p, window, &n_frames)) != LEON_OK) return rc;
+    }
+    if ((rc = suppress_args_check(cfg, n, k, score_stride, regions, by, count)) != LEON_OK) return rc;
+    const size_t rows = (size_t)n * (size_t)k;
+    return pieces_run(p->cfg.device_id, "suppress", LEON_SUPPRESS_PIECES, [&](const Pieces& s) {
+        leon_pipeline_suppress_regions_call c{};
+        c.regions = s.at<const leon_pipeline_region>(5);
+        c.scores = scores ? s.at<const int32_t>(6) : nullptr;
+        c.n = n; c.k = k; c.score_stride = score_stride;
+        c.device_out = out ? s.at<leon_pipeline_region>(0) : nullptr;
+        c.device_order = order ? s.at<int32_t>(1) : nullptr;
+        c.device_by = s.at<int32_t>(2);
+        c.device_count = s.at<int32_t>(3);
+        c.device_status = status ? s.at<int32_t>(4) : nullptr;
+        return suppress_regions_device(p, window, cfg, &c);
+    });
+}
+
+int match_regions(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* a, int32_t ka, const leon_pipeline_region* b,
+                  int32_t kb, int32_t n, int32_t* match_a, int32_t* match_b, int32_t* overlap, int32_t* count, int32_t* status_a, int32_t* status_b)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = overlap_config_check("match regions", cfg);
+    if (rc != LEON_OK) return rc;
+    int32_t n_frames = 0;
+    {
+        std::unique_lock<std::mutex> call(p->regions_mu);
+        if ((rc = overlap_window_frames(p, window, &n_frames)) != LEON_OK) return rc;
+    }
+    if ((rc = match_args_check(cfg, n, ka, kb, a, b, match_a, match_b, overlap, count)) != LEON_OK) return rc;
+    const size_t ra = (size_t)n * (size_t)ka, rb = (size_t)n * (size_t)kb;
+    return pieces_run(p->cfg.device_id, "match", LEON_MATCH_PIECES, [&](const Pieces& s) {
+        leon_pipeline_match_regions_call c{};
+        c.a = s.at<const leon_pipeline_region>(6);
+        c.b = s.at<const leon_pipeline_region>(7);
+        c.n = n; c.ka = ka; c.kb = kb;
+        c.device_match_a = s.at<int32_t>(0);
+        c.device_match_b = s.at<int32_t>(1);
+        c.device_overlap = s.at<int32_t>(2);
+        c.device_count = s.at<int32_t>(3);
+        c.device_status_a = status_a ? s.at<int32_t>(4) : nullptr;
+        c.device_status_b = status_b ? s.at<int32_t>(5) : nullptr;
+        return match_regions_device(p, window, cfg, &c);
+    });
+}
+
+// the definitions on the CPU for one set (pair): the checks, then leon_overlap.h's host texts
+int32_t suppress_record_host(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* regions, int32_t k,
+                             const int32_t* scores, int32_t score_stride, leon_pipeline_region* out, int32_t* order, int32_t* by, int32_t* count, int32_t* status)
+{
+    int rc = overlap_config_check("suppress regions", cfg);
+    if (rc != LEON_OK || (rc = overlap_geometry_check("suppress regions", fw, fh, n_frames)) != LEON_OK ||
+        (rc = suppress_args_check(cfg, 1, k, score_stride, regions, by, count)) != LEON_OK)
+        return rc;
+    leon::suppress_set_host(overlap_call(*cfg, fw, fh, n_frames, 1, k, 0, score_stride), reinterpret_cast<const int32_t*>(regions), scores, reinterpret_cast<int32_t*>(out),
+                            order, by, count, status);
+    return LEON_OK;
+}
+int32_t match_record_host(int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* a, int32_t ka,
+                          const leon_pipeline_region* b, int32_t kb, int32_t* match_a, int32_t* match_b, int32_t* overlap, int32_t* count, int32_t* status_a, int32_t* status_b)
+{
+    int rc = overlap_config_check("match regions", cfg);
+    if (rc != LEON_OK || (rc = overlap_geometry_check("match regions", fw, fh, n_frames)) != LEON_OK ||
+        (rc = match_args_check(cfg, 1, ka, kb, a, b, match_a, match_b, overlap, count)) != LEON_OK)
+        return rc;
+    leon::match_set_host(overlap_call(*cfg, fw, fh, n_frames, 1, ka, kb, 1), reinterpret_cast<const int32_t*>(a), reinterpret_cast<const int32_t*>(b), match_a, match_b,
+                         overlap, count, status_a, status_b);
+    return LEON_OK;
+}
+
+// k_suppress / k_match on rows the caller supplies (leon_pipeline_suppress_kernel, _match_kernel): memory of their own, the null stream
+int suppress_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* regions, int32_t n,
+                    int32_t k, const int32_t* scores, int32_t score_stride, leon_pipeline_region* out, int32_t* order, int32_t* by, int32_t* count, int32_t* status)
+{
+    int rc = overlap_config_check("suppress regions", cfg);
+    if (rc != LEON_OK || (rc = overlap_geometry_check("suppress regions", fw, fh, n_frames)) != LEON_OK ||
+        (rc = suppress_args_check(cfg, n, k, score_stride, regions, by, count)) != LEON_OK)
+        return rc;
+    const size_t rows = (size_t)n * (size_t)k;
+    return pieces_run(device_id, "suppress", LEON_SUPPRESS_PIECES, [&](const Pieces& s) {
+        return suppress_launch(nullptr, overlap_call(*cfg, fw, fh, n_frames, n, k, 0, score_stride), s.at<const int32_t>(5), scores ? s.at<const int32_t>(6) : nullptr,
+                               out ? s.at<int32_t>(0) : nullptr, order ? s.at<int32_t>(1) : nullptr, s.at<int32_t>(2), s.at<int32_t>(3), status ? s.at<int32_t>(4) : nullptr);
+    });
+}
+int match_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t n_frames, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* a, int32_t ka,
+                 const leon_pipeline_region* b, int32_t kb, int32_t n, int32_t* match_a, int32_t* match_b, int32_t* overlap, int32_t* count, int32_t* status_a,
+                 int32_t* status_b)
+{
+    int rc = overlap_config_check("match regions", cfg);
+    if (rc != LEON_OK || (rc = overlap_geometry_check("match regions", fw, fh, n_frames)) != LEON_OK ||
+        (rc = match_args_check(cfg, n, ka, kb, a, b, match_a, match_b, overlap, count)) != LEON_OK)
+        return rc;
+    const size_t ra = (size_t)n * (size_t)ka, rb = (size_t)n * (size_t)kb;
+    return pieces_run(device_id, "match", LEON_MATCH_PIECES, [&](const Pieces& s) {
+        return match_launch(nullptr, overlap_call(*cfg, fw, fh, n_frames, n, ka, kb, 1), s.at<const int32_t>(6), s.at<const int32_t>(7), s.at<int32_t>(0), s.at<int32_t>(1),
+                            s.at<int32_t>(2), s.at<int32_t>(3), status_a ? s.at<int32_t>(4) : nullptr, status_b ? s.at<int32_t>(5) : nullptr);
+    });
+}
+#undef LEON_SUPPRESS_PIECES
+#undef LEON_MATCH_PIECES
+
 // ---- dense maps propagated along the motion vectors (leon_pipeline_propagate_maps) ------------------------------------------------
 static_assert(sizeof(leon_pipeline_propagate_hop) == 32 && sizeof(leon_pipeline_propagate_config) == 40 && sizeof(struct leon_pipeline_propagate_layout) == 32 &&
               sizeof(leon_pipeline_propagate_maps_call) == 64 && sizeof(leon::PropagateHop) == sizeof(leon_pipeline_propagate_hop), "include/leon_pipeline.h states the sizes");
@@ -4141,6 +4414,57 @@ int leon_pipeline_propose_kernel(int32_t device_id, int32_t frame_width, int32_t
 {
     return propose_kernel(device_id, frame_width, frame_height, mb_width, mb_height, n_frames, motion_records_host, activity_records_host, cfg, frames, n, regions, info, count,
                           status);
+}
+
+int32_t leon_pipeline_suppress_record(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_overlap_config* cfg,
+                                      const leon_pipeline_region* regions, int32_t k, const int32_t* scores, int32_t score_stride, leon_pipeline_region* out, int32_t* order,
+                                      int32_t* by, int32_t* count, int32_t* status)
+{
+    return suppress_record_host(frame_width, frame_height, n_frames, cfg, regions, k, scores, score_stride, out, order, by, count, status);
+}
+
+int32_t leon_pipeline_match_record(int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* a,
+                                   int32_t ka, const leon_pipeline_region* b, int32_t kb, int32_t* match_a, int32_t* match_b, int32_t* overlap, int32_t* count,
+                                   int32_t* status_a, int32_t* status_b)
+{
+    return match_record_host(frame_width, frame_height, n_frames, cfg, a, ka, b, kb, match_a, match_b, overlap, count, status_a, status_b);
+}
+
+int leon_pipeline_suppress_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_suppress_regions_call* call)
+{
+    return suppress_regions_device(p, window, cfg, call);
+}
+
+int leon_pipeline_match_regions_device(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_match_regions_call* call)
+{
+    return match_regions_device(p, window, cfg, call);
+}
+
+int leon_pipeline_suppress_regions(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* regions, int32_t n, int32_t k,
+                                   const int32_t* scores, int32_t score_stride, leon_pipeline_region* out, int32_t* order, int32_t* by, int32_t* count, int32_t* status)
+{
+    return suppress_regions(p, window, cfg, regions, n, k, scores, score_stride, out, order, by, count, status);
+}
+
+int leon_pipeline_match_regions(leon_pipeline* p, int64_t window, const leon_pipeline_overlap_config* cfg, const leon_pipeline_region* a, int32_t ka,
+                                const leon_pipeline_region* b, int32_t kb, int32_t n, int32_t* match_a, int32_t* match_b, int32_t* overlap, int32_t* count,
+                                int32_t* status_a, int32_t* status_b)
+{
+    return match_regions(p, window, cfg, a, ka, b, kb, n, match_a, match_b, overlap, count, status_a, status_b);
+}
+
+int leon_pipeline_suppress_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_overlap_config* cfg,
+                                  const leon_pipeline_region* regions, int32_t n, int32_t k, const int32_t* scores, int32_t score_stride, leon_pipeline_region* out,
+                                  int32_t* order, int32_t* by, int32_t* count, int32_t* status)
+{
+    return suppress_kernel(device_id, frame_width, frame_height, n_frames, cfg, regions, n, k, scores, score_stride, out, order, by, count, status);
+}
+
+int leon_pipeline_match_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t n_frames, const leon_pipeline_overlap_config* cfg,
+                               const leon_pipeline_region* a, int32_t ka, const leon_pipeline_region* b, int32_t kb, int32_t n, int32_t* match_a, int32_t* match_b,
+                               int32_t* overlap, int32_t* count, int32_t* status_a, int32_t* status_b)
+{
+    return match_kernel(device_id, frame_width, frame_height, n_frames, cfg, a, ka, b, kb, n, match_a, match_b, overlap, count, status_a, status_b);
 }
 
 int leon_pipeline_propagate_layout(int32_t frame_width, int32_t frame_height, int32_t stride, int32_t planes, int32_t elem_bytes, struct leon_pipeline_propagate_layout* out)

@@ -57,6 +57,8 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_propagate_kernel",
     "leon_pipeline_gauge_record", "leon_pipeline_gauge_regions_device", "leon_pipeline_gauge_regions", "leon_pipeline_gauge_kernel",
     "leon_pipeline_propose_record", "leon_pipeline_propose_regions_device", "leon_pipeline_propose_regions", "leon_pipeline_propose_kernel",
+    "leon_pipeline_suppress_record", "leon_pipeline_suppress_regions_device", "leon_pipeline_suppress_regions", "leon_pipeline_suppress_kernel",
+    "leon_pipeline_match_record", "leon_pipeline_match_regions_device", "leon_pipeline_match_regions", "leon_pipeline_match_kernel",
 ]
 PIPELINE_SEEK_KEY, PIPELINE_SEEK_EXACT = 0, 1      # leon_pipeline_seek modes
 PIPELINE_OUTPUT_RGBA, PIPELINE_OUTPUT_YCBCR = 1, 2  # leon_pipeline_config.output bits
@@ -372,6 +374,8 @@ GAUGE_WORDS = 16                             # int64 words of a gauged record's 
 PROPOSE_MOTION, PROPOSE_ACTIVITY = 1, 2      # LEON_PROPOSE_*: the bits of a propose call's sources
 PROPOSE_INTRA = 1                            # LEON_PROPOSE_INTRA: the bit of its flags
 PROPOSE_MAX_BOXES, PROPOSE_MAX_CELLS = 1024, 65536
+OVERLAP_IOU, OVERLAP_IOMIN = 0, 1            # LEON_OVERLAP_*: the measure of a suppress or match call
+OVERLAP_MAX_ROWS = 1024                      # rows of a set
 
 
 class PipelineWarpRegion(C.Structure):
@@ -414,6 +418,22 @@ class PipelineProposeConfig(C.Structure):
 class PipelineProposeRegionsCall(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("device_regions", C.c_void_p), ("device_info", C.c_void_p),
                 ("device_count", C.c_void_p), ("device_status", C.c_void_p), ("stream", C.c_void_p), ("reserved", C.c_uint64 * 1)]
+
+
+class PipelineOverlapConfig(C.Structure):
+    _fields_ = [("measure", C.c_int32), ("threshold", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class PipelineSuppressRegionsCall(C.Structure):
+    _fields_ = [("regions", C.c_void_p), ("scores", C.c_void_p), ("n", C.c_int32), ("k", C.c_int32), ("score_stride", C.c_int32), ("reserved0", C.c_int32),
+                ("device_out", C.c_void_p), ("device_order", C.c_void_p), ("device_by", C.c_void_p), ("device_count", C.c_void_p), ("device_status", C.c_void_p),
+                ("stream", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class PipelineMatchRegionsCall(C.Structure):
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("n", C.c_int32), ("ka", C.c_int32), ("kb", C.c_int32), ("reserved0", C.c_int32), ("device_match_a", C.c_void_p),
+                ("device_match_b", C.c_void_p), ("device_overlap", C.c_void_p), ("device_count", C.c_void_p), ("device_status_a", C.c_void_p),
+                ("device_status_b", C.c_void_p), ("stream", C.c_void_p), ("reserved", C.c_uint64 * 1)]
 
 
 class PipelinePropagateHop(C.Structure):
@@ -669,6 +689,18 @@ def load():
         lib.leon_pipeline_propose_regions.argtypes = [C.c_void_p, C.c_int64, P(PipelineProposeConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.leon_pipeline_propose_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineProposeConfig),
                                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_suppress_regions"):
+        P, i32, vp = C.POINTER, C.c_int32, C.c_void_p
+        lib.leon_pipeline_suppress_record.argtypes = [i32, i32, i32, P(PipelineOverlapConfig), vp, i32, vp, i32, vp, vp, vp, vp, vp]
+        lib.leon_pipeline_suppress_record.restype = i32
+        lib.leon_pipeline_match_record.argtypes = [i32, i32, i32, P(PipelineOverlapConfig), vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+        lib.leon_pipeline_match_record.restype = i32
+        lib.leon_pipeline_suppress_regions_device.argtypes = [vp, C.c_int64, P(PipelineOverlapConfig), P(PipelineSuppressRegionsCall)]
+        lib.leon_pipeline_match_regions_device.argtypes = [vp, C.c_int64, P(PipelineOverlapConfig), P(PipelineMatchRegionsCall)]
+        lib.leon_pipeline_suppress_regions.argtypes = [vp, C.c_int64, P(PipelineOverlapConfig), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+        lib.leon_pipeline_match_regions.argtypes = [vp, C.c_int64, P(PipelineOverlapConfig), vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+        lib.leon_pipeline_suppress_kernel.argtypes = [i32, i32, i32, i32, P(PipelineOverlapConfig), vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+        lib.leon_pipeline_match_kernel.argtypes = [i32, i32, i32, i32, P(PipelineOverlapConfig), vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.leon_pipeline_error.argtypes = [C.c_void_p]
     lib.leon_pipeline_error.restype = C.c_char_p
     lib.leon_pipeline_seek.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
@@ -1242,6 +1274,176 @@ def propose_kernel(frame_width, frame_height, mbw, mbh, n_frames, motion, activi
                                              fr.ctypes.data if len(fr) else None, len(fr) if n is None else int(n), regions.ctypes.data,
                                              info.ctypes.data if with_info else None, count.ctypes.data, status.ctypes.data if with_status else None))
     return regions[:len(fr)], info[:len(fr)], count[:len(fr)], status[:len(fr)]
+
+
+def _overlap_config(threshold, measure, threshold_q16=None):
+    """the config of a suppress or match call: measure "iou" / "iomin" (or the word itself), the threshold as a float converted with
+    round(threshold * 65536) unless threshold_q16 gives the Q16 word"""
+    m = {"iou": OVERLAP_IOU, "iomin": OVERLAP_IOMIN}.get(measure, measure)
+    return PipelineOverlapConfig(int(m), int(round(float(threshold) * 65536)) if threshold_q16 is None else int(threshold_q16))
+
+
+def _overlap_ok(row, fw, fh, n_frames):
+    """the status word of a row, as the gauge family judges it"""
+    f, x, y, w, h, r0, r1, r2 = (int(v) for v in row)
+    if r0 or r1 or r2:
+        return REGION_RESERVED
+    if not 0 <= f < n_frames:
+        return REGION_FRAME
+    if w < 1 or h < 1 or x < 0 or y < 0 or x + w > fw or y + h > fh:
+        return REGION_BOX
+    return REGION_OK
+
+
+def _overlap_pair(measure, a, b):
+    """(inter, den) of two rows in Python integers"""
+    iw = min(a[1] + a[3], b[1] + b[3]) - max(a[1], b[1])
+    ih = min(a[2] + a[4], b[2] + b[4]) - max(a[2], b[2])
+    inter = max(iw, 0) * max(ih, 0)
+    return inter, (min(a[3] * a[4], b[3] * b[4]) if measure == OVERLAP_IOMIN else a[3] * a[4] + b[3] * b[4] - inter)
+
+
+def suppress_boxes(frame_width, frame_height, n_frames, rows, scores=None, threshold_q16=32768, measure=OVERLAP_IOU):
+    """The definition of one set of leon_pipeline_suppress_regions (include/leon_pipeline.h), written from the header's text in Python
+    integers and independent of the C code: rows = K rows of 8 words, scores = K integers (None: all 0).  Returns (out, order, by,
+    count, status): K rows of 8 words, K input indices (-1 behind count), K words of by (None for a refused row: not written), the
+    kept rows' number and K status words."""
+    rows = [[int(v) for v in r] for r in rows]
+    K = len(rows)
+    status = [_overlap_ok(r, int(frame_width), int(frame_height), int(n_frames)) for r in rows]
+    walk = sorted((i for i in range(K) if status[i] == REGION_OK), key=lambda i: (-(int(scores[i]) if scores is not None else 0), i))
+    by, kept = [None] * K, []
+    for i in walk:
+        by[i] = -1
+        for k in kept:
+            inter, den = _overlap_pair(measure, rows[k], rows[i])
+            if inter * 65536 >= int(threshold_q16) * den:
+                by[i] = k
+                break
+        if by[i] == -1:
+            kept.append(i)
+    out = [rows[i][:5] + [0, 0, 0] for i in kept] + [[0] * 8] * (K - len(kept))
+    return out, kept + [-1] * (K - len(kept)), by, len(kept), status
+
+
+def match_boxes(frame_width, frame_height, n_frames, a, b, threshold_q16=32768, measure=OVERLAP_IOU):
+    """The definition of one pair of sets of leon_pipeline_match_regions in Python integers: a = Ka rows, b = Kb rows of 8 words.
+    Returns (match_a, match_b, overlap, count, status_a, status_b); the words of a refused row are None (not written).  The candidates
+    are sorted with exact fractions."""
+    from fractions import Fraction
+    a, b = [[int(v) for v in r] for r in a], [[int(v) for v in r] for r in b]
+    sa = [_overlap_ok(r, int(frame_width), int(frame_height), int(n_frames)) for r in a]
+    sb = [_overlap_ok(r, int(frame_width), int(frame_height), int(n_frames)) for r in b]
+    match_a, overlap = [-1 if s == REGION_OK else None for s in sa], [0 if s == REGION_OK else None for s in sa]
+    match_b = [-1 if s == REGION_OK else None for s in sb]
+    okb = [j for j in range(len(b)) if sb[j] == REGION_OK]
+    cand = []
+    for i in range(len(a)):
+        if sa[i] != REGION_OK:
+            continue
+        for j in okb:
+            if a[i][1] + a[i][3] <= b[j][1] or b[j][1] + b[j][3] <= a[i][1]:          # no common column: inter 0 reaches no threshold
+                continue
+            inter, den = _overlap_pair(measure, a[i], b[j])
+            if inter * 65536 >= int(threshold_q16) * den:
+                cand.append((-Fraction(inter, den), i, j, inter * 65536 // den))
+    cand.sort()
+    count = 0
+    for _, i, j, q in cand:
+        if match_a[i] == -1 and match_b[j] == -1:
+            match_a[i], match_b[j], overlap[i] = j, i, q
+            count += 1
+    return match_a, match_b, overlap, count, sa, sb
+
+
+def _overlap_rows(rows, name):
+    """rows [K, 8] or [n, K, 8] -> a contiguous int32 array [n, K, 8]"""
+    r = np.ascontiguousarray(rows, dtype=np.int32)
+    if r.ndim == 2:
+        r = r[None]
+    if r.ndim != 3 or r.shape[2] != 8:
+        raise ValueError("%s: [K, 8] or [n, K, 8] words" % name)
+    return r
+
+
+def _suppress_arrays(rows, scores, score_stride, fill):
+    r = _overlap_rows(rows, "regions")
+    n, K = r.shape[0], r.shape[1]
+    sc = None if scores is None else np.ascontiguousarray(scores, dtype=np.int32).reshape(-1)
+    if sc is not None and sc.size < (n * K - 1) * int(score_stride) + 1 and 1 <= int(score_stride) <= 8:
+        raise ValueError("scores: at least %d words" % ((n * K - 1) * int(score_stride) + 1))
+    if sc is not None and sc.size < n * K * max(1, int(score_stride)):         # the library reads whole strides
+        sc = np.concatenate([sc, np.zeros(n * K * max(1, int(score_stride)) - sc.size, dtype=np.int32)])
+    m, Kc = max(1, n), max(1, K)
+    outs = (np.full((m, Kc, 8), fill, dtype=np.int32), np.full((m, Kc), fill, dtype=np.int32), np.full((m, Kc), fill, dtype=np.int32), np.full(m, fill, dtype=np.int32),
+            np.full((m, Kc), fill, dtype=np.int32))
+    return r, n, K, sc, outs
+
+
+def suppress_record(frame_width, frame_height, n_frames, rows, scores=None, threshold=0.5, measure="iou", score_stride=1, threshold_q16=None, fill=-1, cfg=None, k=None,
+                    with_out=True, with_order=True, with_status=True):
+    """leon_pipeline_suppress_record: the library's CPU evaluation of one set; rows [K, 8].  Returns (out [K, 8], order [K], by [K],
+    count, status [K]) int32 with `fill` where the library wrote nothing; LeonError where it refuses the call.  cfg: a
+    PipelineOverlapConfig in place of the keywords; k: the count handed down when it is to differ from len(rows)."""
+    r, n, K, sc, (out, order, by, count, status) = _suppress_arrays(rows, scores, score_stride, fill)
+    cfg = _overlap_config(threshold, measure, threshold_q16) if cfg is None else cfg
+    st = load().leon_pipeline_suppress_record(int(frame_width), int(frame_height), int(n_frames), C.byref(cfg), r.ctypes.data if r.size else None, K if k is None else int(k),
+                                              None if sc is None else sc.ctypes.data, int(score_stride), out.ctypes.data if with_out else None,
+                                              order.ctypes.data if with_order else None, by.ctypes.data, count.ctypes.data, status.ctypes.data if with_status else None)
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return out[0], order[0], by[0], int(count[0]), status[0]
+
+
+def suppress_kernel(frame_width, frame_height, n_frames, rows, scores=None, threshold=0.5, measure="iou", score_stride=1, threshold_q16=None, device_id=0, fill=-1, n=None,
+                    cfg=None, with_out=True, with_order=True, with_status=True):
+    """leon_pipeline_suppress_kernel: k_suppress on rows the caller supplies, [n, K, 8] (or [K, 8]) -> (out [n, K, 8], order [n, K],
+    by [n, K], count [n], status [n, K]) int32, pre-filled with `fill`.  n: the set count handed to the library when it is to differ
+    (smaller: what lies behind keeps the fill); with_* False: NULL goes down in its place and it comes back as the fill."""
+    r, sets, K, sc, (out, order, by, count, status) = _suppress_arrays(rows, scores, score_stride, fill)
+    cfg = _overlap_config(threshold, measure, threshold_q16) if cfg is None else cfg
+    _chk(load().leon_pipeline_suppress_kernel(int(device_id), int(frame_width), int(frame_height), int(n_frames), C.byref(cfg), r.ctypes.data if r.size else None,
+                                              sets if n is None else int(n), K, None if sc is None else sc.ctypes.data, int(score_stride),
+                                              out.ctypes.data if with_out else None, order.ctypes.data if with_order else None, by.ctypes.data, count.ctypes.data,
+                                              status.ctypes.data if with_status else None))
+    return out, order, by, count, status
+
+
+def _match_arrays(a, b, fill):
+    ra, rb = _overlap_rows(a, "a"), _overlap_rows(b, "b")
+    if ra.shape[0] != rb.shape[0]:
+        raise ValueError("a and b: as many sets")
+    n, Ka, Kb = ra.shape[0], ra.shape[1], rb.shape[1]
+    m, A, B = max(1, n), max(1, Ka), max(1, Kb)
+    outs = (np.full((m, A), fill, dtype=np.int32), np.full((m, B), fill, dtype=np.int32), np.full((m, A), fill, dtype=np.int32), np.full(m, fill, dtype=np.int32),
+            np.full((m, A), fill, dtype=np.int32), np.full((m, B), fill, dtype=np.int32))
+    return ra, rb, n, Ka, Kb, outs
+
+
+def match_record(frame_width, frame_height, n_frames, a, b, threshold=0.5, measure="iou", threshold_q16=None, fill=-1, cfg=None, ka=None, kb=None, with_status=True):
+    """leon_pipeline_match_record: the library's CPU evaluation of one pair of sets, a [Ka, 8] and b [Kb, 8].  Returns (match_a [Ka],
+    match_b [Kb], overlap [Ka], count, status_a [Ka], status_b [Kb]) int32 with `fill` where the library wrote nothing."""
+    ra, rb, n, Ka, Kb, (ma, mb, ov, count, sa, sb) = _match_arrays(a, b, fill)
+    cfg = _overlap_config(threshold, measure, threshold_q16) if cfg is None else cfg
+    st = load().leon_pipeline_match_record(int(frame_width), int(frame_height), int(n_frames), C.byref(cfg), ra.ctypes.data if ra.size else None, Ka if ka is None else int(ka),
+                                           rb.ctypes.data if rb.size else None, Kb if kb is None else int(kb), ma.ctypes.data, mb.ctypes.data, ov.ctypes.data,
+                                           count.ctypes.data, sa.ctypes.data if with_status else None, sb.ctypes.data if with_status else None)
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return ma[0], mb[0], ov[0], int(count[0]), sa[0], sb[0]
+
+
+def match_kernel(frame_width, frame_height, n_frames, a, b, threshold=0.5, measure="iou", threshold_q16=None, device_id=0, fill=-1, n=None, cfg=None, with_status_a=True,
+                 with_status_b=True):
+    """leon_pipeline_match_kernel: k_match on rows the caller supplies, a [n, Ka, 8] and b [n, Kb, 8] -> (match_a [n, Ka], match_b
+    [n, Kb], overlap [n, Ka], count [n], status_a [n, Ka], status_b [n, Kb]) int32, pre-filled with `fill`; n and with_* as
+    suppress_kernel's."""
+    ra, rb, sets, Ka, Kb, (ma, mb, ov, count, sa, sb) = _match_arrays(a, b, fill)
+    cfg = _overlap_config(threshold, measure, threshold_q16) if cfg is None else cfg
+    _chk(load().leon_pipeline_match_kernel(int(device_id), int(frame_width), int(frame_height), int(n_frames), C.byref(cfg), ra.ctypes.data if ra.size else None, Ka,
+                                           rb.ctypes.data if rb.size else None, Kb, sets if n is None else int(n), ma.ctypes.data, mb.ctypes.data, ov.ctypes.data,
+                                           count.ctypes.data, sa.ctypes.data if with_status_a else None, sb.ctypes.data if with_status_b else None))
+    return ma, mb, ov, count, sa, sb
 
 
 def carry_plan(refs, frames, src):
@@ -1886,6 +2088,11 @@ class Pipeline:
     them; propose_regions is the same to host arrays) -- which go into gauge_regions_device and resample_regions_device as they are.
     carry_regions_gop(window, boxes, src) carries a detector's boxes on frame `src` to every frame of its GOP, ready for
     resample_regions_device.
+    Comparing boxes (any output): suppress_regions_device(window, records, scores) prunes every set of a [n, K, 8] tensor by greedy
+    suppression (suppress_boxes states it) and match_regions_device(window, a, b) pairs the rows of two such tensors one to one by
+    overlap (match_boxes states it), both on the device: what propose_regions_device and carry_regions_gop return goes in as it is,
+    and the `out` rows of a suppression go into the gauge, resample and carry calls.  suppress_regions / match_regions: the same on
+    host arrays.
     Propagating dense maps (motion=True): propagate_maps_device(window, maps, hops, stride) writes the map of a frame -- a mask, heatmaps,
     features at 1, 2, 4, 8 or 16 frame pixels a cell -- as a gather from the maps of the pictures it predicts from, through its own motion
     record, on the device (propagate_map states one hop; propagate_maps is the same from host arrays); propagate_maps_gop(window, map,
@@ -2327,6 +2534,78 @@ class Pipeline:
                                           self._stream_handle(stream))
         _chk(self.lib.leon_pipeline_propose_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
         return regions[:n], count[:n], info[:n], status[:n]
+
+    def suppress_regions(self, window, regions, scores=None, threshold=0.5, measure="iou", score_stride=1, threshold_q16=None, fill=-1):
+        """leon_pipeline_suppress_regions: regions [n, K, 8] (or [K, 8]) and scores in host memory -> (out [n, K, 8], order [n, K], by
+        [n, K], count [n], status [n, K]) int32 host arrays (suppress_boxes states them).  A row's fault is its status word, never a
+        LeonError; its `by` keeps `fill`.  Synchronous."""
+        r, n, K, sc, (out, order, by, count, status) = _suppress_arrays(regions, scores, score_stride, fill)
+        cfg = _overlap_config(threshold, measure, threshold_q16)
+        _chk(self.lib.leon_pipeline_suppress_regions(self.h, int(window), C.byref(cfg), r.ctypes.data if r.size else None, n, K, None if sc is None else sc.ctypes.data,
+                                                     int(score_stride), out.ctypes.data, order.ctypes.data, by.ctypes.data, count.ctypes.data, status.ctypes.data))
+        return out[:n], order[:n], by[:n], count[:n], status[:n]
+
+    def match_regions(self, window, a, b, threshold=0.5, measure="iou", threshold_q16=None, fill=-1):
+        """leon_pipeline_match_regions: a [n, Ka, 8] and b [n, Kb, 8] in host memory -> (match_a [n, Ka], match_b [n, Kb], overlap
+        [n, Ka], count [n], status_a, status_b) int32 host arrays (match_boxes states them).  Synchronous."""
+        ra, rb, n, Ka, Kb, (ma, mb, ov, count, sa, sb) = _match_arrays(a, b, fill)
+        cfg = _overlap_config(threshold, measure, threshold_q16)
+        _chk(self.lib.leon_pipeline_match_regions(self.h, int(window), C.byref(cfg), ra.ctypes.data if ra.size else None, Ka, rb.ctypes.data if rb.size else None, Kb, n,
+                                                  ma.ctypes.data, mb.ctypes.data, ov.ctypes.data, count.ctypes.data, sa.ctypes.data, sb.ctypes.data))
+        return ma[:n], mb[:n], ov[:n], count[:n], sa[:n], sb[:n]
+
+    @staticmethod
+    def _overlap_sets(name, t):
+        """a CUDA int32 tensor [K, 8] or [n, K, 8] of rows -> [n, K, 8]"""
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() in (2, 3) and t.shape[-1] == 8 and t.is_contiguous()):
+            raise ValueError("%s: a contiguous CUDA int32 tensor [K, 8] or [n, K, 8]" % name)
+        return t.view(1, -1, 8) if t.dim() == 2 else t
+
+    def suppress_regions_device(self, window, records, scores=None, threshold=0.5, measure="iou", score_stride=1, stream=None, threshold_q16=None):
+        """leon_pipeline_suppress_regions_device: records = a contiguous CUDA int32 tensor [n, K, 8] ([K, 8]: one set), scores = a
+        contiguous CUDA int32 tensor of n * K * score_stride words (propose's info [n, K, 2] with score_stride=2: the cells) or None,
+        queued on `stream` (None: torch's current stream) with carry_regions_device's ordering: NO host synchronisation.  Returns
+        (out [n, K, 8], order [n, K], by [n, K], count [n], status [n, K]) int32 CUDA tensors: `out` holds the kept rows in walk
+        order and zero rows behind count, and goes into gauge_regions_device / resample_regions_device / carry_regions_gop as it is;
+        `by` is written for the accepted rows only."""
+        import torch
+        dev = self.device_id
+        records = self._overlap_sets("records", records)
+        n, K = int(records.shape[0]), int(records.shape[1])
+        _device_tensor_check("records", records, torch.int32, 8 * n * K, dev, words=True)
+        _device_tensor_check("scores", scores, torch.int32, n * K * max(1, int(score_stride)), dev, words=True)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        m, Kc = max(1, n), max(1, K)
+        out, order, by, count, status = _empty_where_none(stream, dev, [(None, (m, Kc, 8), torch.int32), (None, (m, Kc), torch.int32), (None, (m, Kc), torch.int32),
+                                                                        (None, m, torch.int32), (None, (m, Kc), torch.int32)])
+        cfg = _overlap_config(threshold, measure, threshold_q16)
+        call = PipelineSuppressRegionsCall(records.data_ptr() if n * K else None, None if scores is None else scores.data_ptr(), n, K, int(score_stride), 0, out.data_ptr(),
+                                           order.data_ptr(), by.data_ptr(), count.data_ptr(), status.data_ptr(), self._stream_handle(stream))
+        _chk(self.lib.leon_pipeline_suppress_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        return out[:n], order[:n], by[:n], count[:n], status[:n]
+
+    def match_regions_device(self, window, a, b, threshold=0.5, measure="iou", stream=None, threshold_q16=None):
+        """leon_pipeline_match_regions_device: a [n, Ka, 8] and b [n, Kb, 8], contiguous CUDA int32 tensors ([K, 8]: one set), set s
+        of a against set s of b, queued like suppress_regions_device.  Returns (match_a [n, Ka], match_b [n, Kb], overlap [n, Ka],
+        count [n], status_a [n, Ka], status_b [n, Kb]) int32 CUDA tensors; the words of a refused row are not written."""
+        import torch
+        dev = self.device_id
+        a, b = self._overlap_sets("a", a), self._overlap_sets("b", b)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("a and b: as many sets")
+        n, Ka, Kb = int(a.shape[0]), int(a.shape[1]), int(b.shape[1])
+        _device_tensor_check("a", a, torch.int32, 8 * n * Ka, dev, words=True)
+        _device_tensor_check("b", b, torch.int32, 8 * n * Kb, dev, words=True)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        m, A, B = max(1, n), max(1, Ka), max(1, Kb)
+        ma, mb, ov, count, sa, sb = _empty_where_none(stream, dev, [(None, (m, A), torch.int32), (None, (m, B), torch.int32), (None, (m, A), torch.int32),
+                                                                    (None, m, torch.int32), (None, (m, A), torch.int32), (None, (m, B), torch.int32)])
+        cfg = _overlap_config(threshold, measure, threshold_q16)
+        call = PipelineMatchRegionsCall(a.data_ptr() if n * Ka else None, b.data_ptr() if n * Kb else None, n, Ka, Kb, 0, ma.data_ptr(), mb.data_ptr(), ov.data_ptr(),
+                                        count.data_ptr(), sa.data_ptr(), sb.data_ptr(), self._stream_handle(stream))
+        _chk(self.lib.leon_pipeline_match_regions_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        return ma[:n], mb[:n], ov[:n], count[:n], sa[:n], sb[:n]
 
     def _propagate_check(self, maps, stride):
         lay = propagate_layout(self.info.frame_width, self.info.frame_height, stride, maps.shape[1] if len(maps.shape) == 4 else 0, self._elem_bytes(maps))

@@ -28,9 +28,18 @@ stream; the first --propose-check frames against propose_boxes on the records re
 gauge_regions_device in the same job (word 0 = w * h for the first count rows, REGION_BOX behind).  The bytes the kernel must read --
 F x (8 + 1 + 8) x the macroblocks of a frame -- are set against the time.  Prints one JSON line.
 
+--suppress / --match: boxes compared by overlap instead (leon_pipeline_suppress_regions, leon_pipeline_match_regions; k_suppress,
+k_match): for K = 64, 256 and 1024, F sets of K seeded boxes of side 16 .. 160, one set on each of the F frames of the window, in ONE
+suppress_regions_device (IOU 0.5 and IOMIN 0.75, seeded scores) or match_regions_device (IOU 0.3, against a second seeded tensor)
+call, from the enqueue to the synchronisation of the stream; the first --overlap-check sets against suppress_boxes / match_boxes;
+beside it the same call through the host road (suppress_regions / match_regions on numpy arrays: the upload, the launch and the
+copies back -- the round trip a user had to make, with a numpy loop in place of the launch).  --match adds the worst case of the
+mutual-best rounds: ONE pair of sets of 256 and of 1024 identical boxes, a pair a round.  Both print one JSON line.
+
   python tools/carry_bench.py [--boxes 4096] [--reps 20] [--max-box 256] [--host-boxes N] [--gauge [--gauge-check 64]]
   python tools/carry_bench.py --maps [--reps 20]
-  python tools/carry_bench.py --propose [--reps 20] [--mv-min 2] [--ac-min 256] [--max-boxes 16] [--propose-check 8]"""
+  python tools/carry_bench.py --propose [--reps 20] [--mv-min 2] [--ac-min 256] [--max-boxes 16] [--propose-check 8]
+  python tools/carry_bench.py --suppress | --match [--reps 20] [--overlap-check 2]"""
 import argparse
 import json
 import os
@@ -182,6 +191,88 @@ def propose_bench(a, pipe, window, frames):
                                   "gauged_rows_ok": int(used.sum()), "gauged_rows_region_box": int((~used).sum())}}))
 
 
+def overlap_sets(np, n, k, fw, fh, seed):
+    """[n, k, 8] rows: set f on frame f, sides 16 .. 160"""
+    g = np.random.default_rng(seed)
+    w, h = g.integers(16, 161, size=(n, k)), g.integers(16, 161, size=(n, k))
+    r = np.zeros((n, k, 8), dtype=np.int32)
+    r[..., 0] = np.arange(n)[:, None]
+    r[..., 1], r[..., 2], r[..., 3], r[..., 4] = g.integers(0, fw - w + 1), g.integers(0, fh - h + 1), w, h
+    return r
+
+
+def timed(torch, st, reps, call):
+    """the median and the least of `reps` calls from the enqueue to the synchronisation of the stream, and the median enqueue, in us"""
+    us, enq = [], []
+    for i in range(reps + 2):          # (the first two: the scratch, the stream and torch's allocator warm up)
+        st.synchronize()
+        t0 = time.perf_counter()
+        out = call()
+        t1 = time.perf_counter()
+        st.synchronize()
+        t2 = time.perf_counter()
+        if i >= 2:
+            us.append((t2 - t0) * 1e6)
+            enq.append((t1 - t0) * 1e6)
+    return out, {"us": round(statistics.median(us), 1), "min_us": round(min(us), 1), "enqueue_us": round(statistics.median(enq), 1)}
+
+
+def overlap_bench(a, pipe, window, frames):
+    import numpy as np
+    import torch
+    import leon_ctypes as L
+    fw, fh, n = pipe.info.frame_width, pipe.info.frame_height, len(frames)
+    st = torch.cuda.Stream()
+    result = {"frames": n, "reps": a.reps, "K": {}}
+    with torch.cuda.stream(st):
+        for k in (64, 256, 1024):
+            rows, other = overlap_sets(np, n, k, fw, fh, k), overlap_sets(np, n, k, fw, fh, k + 1)
+            scores = np.random.default_rng(k).integers(0, 1000, size=(n, k)).astype(np.int32)
+            d_rows, d_other, d_scores = torch.tensor(rows, device="cuda"), torch.tensor(other, device="cuda"), torch.tensor(scores, device="cuda")
+            entry = {}
+            if a.suppress:
+                for name, t, measure in (("iou_0.5", 32768, L.OVERLAP_IOU), ("iomin_0.75", 49152, L.OVERLAP_IOMIN)):
+                    got, e = timed(torch, st, a.reps, lambda: pipe.suppress_regions_device(window, d_rows, d_scores, threshold_q16=t, measure=measure))
+                    out, order, by, count, status = (x.cpu().numpy() for x in got)
+                    for s_ in range(min(n, a.overlap_check)):
+                        o_, ord_, by_, c_, st_ = L.suppress_boxes(fw, fh, n, rows[s_].tolist(), scores[s_].tolist(), t, measure)
+                        if (o_, ord_, by_, c_, st_) != (out[s_].tolist(), order[s_].tolist(), by[s_].tolist(), count[s_], status[s_].tolist()):
+                            raise RuntimeError("the device and suppress_boxes disagree in set %d" % s_)
+                    t0 = time.perf_counter()
+                    host = pipe.suppress_regions(window, rows, scores, threshold_q16=t, measure=measure)
+                    e["host_road_us"] = round((time.perf_counter() - t0) * 1e6, 1)
+                    if not all(np.array_equal(h_, g_) for h_, g_ in zip(host, (out, order, by, count, status))):
+                        raise RuntimeError("the host road and the device road disagree")
+                    e.update(kept=int(count.sum()), suppressed=int((status == 0).sum() - count.sum()), checked_sets=min(n, a.overlap_check))
+                    entry[name] = e
+            if a.match:
+                got, e = timed(torch, st, a.reps, lambda: pipe.match_regions_device(window, d_rows, d_other, threshold_q16=19661))
+                ma, mb, ov, count, sa, sb = (x.cpu().numpy() for x in got)
+                for s_ in range(min(n, a.overlap_check) if k <= 256 else 0):          # (the definition sorts exact fractions: not at K = 1024)
+                    m_ = L.match_boxes(fw, fh, n, rows[s_].tolist(), other[s_].tolist(), 19661)
+                    if m_[:4] != (ma[s_].tolist(), mb[s_].tolist(), ov[s_].tolist(), count[s_]):
+                        raise RuntimeError("the device and match_boxes disagree in set %d" % s_)
+                t0 = time.perf_counter()
+                host = pipe.match_regions(window, rows, other, threshold_q16=19661)
+                e["host_road_us"] = round((time.perf_counter() - t0) * 1e6, 1)
+                if not all(np.array_equal(h_, g_) for h_, g_ in zip(host, (ma, mb, ov, count, sa, sb))):
+                    raise RuntimeError("the host road and the device road disagree")
+                e.update(pairs=int(count.sum()), checked_sets=min(n, a.overlap_check) if k <= 256 else 0)
+                entry["iou_0.3"] = e
+            result["K"][k] = entry
+        if a.match:
+            result["identical"] = {}
+            for k in (256, 1024):
+                same = np.zeros((1, k, 8), dtype=np.int32)
+                same[..., 1:5] = (100, 100, 50, 40)
+                d_same = torch.tensor(same, device="cuda")
+                got, e = timed(torch, st, max(3, a.reps // 4), lambda: pipe.match_regions_device(window, d_same, d_same, threshold_q16=65536))
+                if got[0].cpu().numpy().tolist() != [list(range(k))] or got[3].cpu().numpy().tolist() != [k]:
+                    raise RuntimeError("identical boxes: row i is not matched with row i")
+                result["identical"][k] = e
+    print(json.dumps({("suppress" if a.suppress else "match"): result}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--maps", action="store_true", help="dense maps (k_propagate) instead of boxes")
@@ -192,6 +283,9 @@ def main():
     ap.add_argument("--ac-min", type=int, default=256)
     ap.add_argument("--max-boxes", type=int, default=16)
     ap.add_argument("--propose-check", type=int, default=8, help="frames compared with propose_boxes")
+    ap.add_argument("--suppress", action="store_true", help="sets of boxes pruned by overlap (k_suppress) instead of boxes carried")
+    ap.add_argument("--match", action="store_true", help="pairs of sets of boxes matched by overlap (k_match) instead of boxes carried")
+    ap.add_argument("--overlap-check", type=int, default=2, help="sets compared with suppress_boxes / match_boxes")
     ap.add_argument("--boxes", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--max-box", type=int, default=256)
@@ -215,8 +309,8 @@ def main():
         if not delivered.wait(300):
             raise RuntimeError("no window was delivered: %s" % (pipe.error,))
         window, frames = held["window"], held["frames"]
-        if a.maps or a.propose:
-            (maps_bench if a.maps else propose_bench)(a, pipe, window, frames)
+        if a.maps or a.propose or a.suppress or a.match:
+            (maps_bench if a.maps else propose_bench if a.propose else overlap_bench)(a, pipe, window, frames)
             pipe.release_window(window)
             pipe.wait()
             return
