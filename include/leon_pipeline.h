@@ -1060,6 +1060,109 @@ int leon_pipeline_propagate_maps(leon_pipeline* p, int64_t window, const leon_pi
 int leon_pipeline_propagate_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t mb_width, int32_t mb_height, int32_t n_frames,
                                    const void* const* records_host, const leon_pipeline_propagate_config* cfg, const leon_pipeline_propagate_hop* hops,
                                    int32_t n, void* maps, uint8_t* via, int32_t* status);
+/* Motion and residual accumulated along a GOP's chain: what the compressed-domain video networks (CoViAR and its successors) read.  A
+ * P picture's vectors and residual (LEON_PIPELINE_OUTPUT_MOTION, LEON_PIPELINE_OUTPUT_RESIDUAL) are relative to the picture before it,
+ * which is itself a prediction; they mean something once they are traced back to a picture the model has seen.  For every sample of
+ * a P or B picture an accumulator says where the sample came from in the picture the chain started at and the sum of everything the
+ * stream added along that path.  The arithmetic counterpart of the propagate family above, on the device.  Integers only.
+ * Accumulator.  An accumulator lies over the CODED picture (cw x ch, as the residual record does) and consists of int16 planes chosen
+ * by `parts`:
+ *     LEON_ACCUMULATE_MOTION (1)   : AX, AY, AGE, each [ch][luma_stride]
+ *     LEON_ACCUMULATE_RESIDUAL (2) : RY [ch][luma_stride], RCb and RCr [ch / 2][chroma_stride]
+ * Strides follow leon_pipeline_residual_layout: luma_stride = pad64(cw), chroma_stride = pad64(cw / 2), in elements.  Every plane starts
+ * on a 256-byte boundary, in the order above, and absent parts take no room: with parts = 2 the three planes lie exactly as a residual
+ * record's do, at the same offsets.  The caller's buffer `slots` holds n_slots accumulators (1 .. 65535) at slot_pitch_bytes, a multiple
+ * of 4 that is at least slot_bytes.  slots_bytes is what the caller vouches for; it is at least n_slots * slot_pitch_bytes.
+ * A HOP is the propagate family's 32-byte record as it is (leon_pipeline_propagate_hop: target, dst_slot, fwd_slot, bwd_slot, four
+ * reserved words), judged as there and in the same order: LEON_REGION_RESERVED, LEON_REGION_FRAME, LEON_REGION_SLOT.  What
+ * leon_ctypes.propagate_plan makes feeds the call unchanged.  It writes the accumulator of window frame `target` T from those of the
+ * pictures T predicts from: a gather through T's own motion record.  THE CALLER VOUCHES FOR WHICH PICTURE A SLOT HOLDS.
+ * The pick, per macroblock k of T's motion record, is the propagate family's word for word: forward where info & 1 and fwd_slot >= 0
+ * (via = 1), else backward where info & 2 and bwd_slot >= 0 (via = 2), else a restart (via = 0).  via, one byte per MACROBLOCK, goes to
+ * an optional output [n][mbh][mbw].  A bidirectional macroblock takes the forward source: no averaging.
+ * A restart macroblock (via = 0): every element of every plane asked for under the macroblock is 0 -- the sample is its own origin.
+ * An I picture as target is all zero with status 0: that is how a chain's start is written (a hop with both sources -1 does the same).
+ * Luma.  For luma element (x, y) under a macroblock with vector v and source slot S:
+ *     dx = (v_h + 1) >> 1,  dy = (v_v + 1) >> 1                    the propagate rule at stride 1: arithmetic shift, ties up
+ *     sx = clamp(x + dx, 0, cw - 1),  sy = clamp(y + dy, 0, ch - 1)
+ *     AX[y][x]  = sat16(S.AX[sy][sx]  + (sx - x))                   the own term is the displacement AFTER the clamp, so
+ *     AY[y][x]  = sat16(S.AY[sy][sx]  + (sy - y))                   0 <= x + AX <= cw - 1 whenever the sources obey it (AY likewise)
+ *     AGE[y][x] = sat16(S.AGE[sy][sx] + 1)
+ *     RY[y][x]  = sat16(S.RY[sy][sx]  + res_T.Y[y][x])              res_T: T's residual record; sat16: saturation to -32768 .. 32767
+ * Chroma.  For element (x, y) of the cw / 2 x ch / 2 planes, with macroblock (y >> 3) * mb_width + (x >> 3):
+ *     dx = (v_h + 2) >> 2,  dy likewise                             the propagate rule at stride 2; the clamp is to the chroma plane
+ *     R[y][x] = sat16(S.R[sy][sx] + res_T[y][x])                    for RCb and RCr
+ * Meaning.  With O the picture reached after AGE hops, frame_T(p) ~ O(p + A_T(p)) + R_T(p); exactly so for luma where every vector
+ * on the chain is full-pel and no clamp to 0 .. 255 acted.
+ * A refused hop has not one byte of its slot or via written; A RECORD'S FAULT IS A STATUS WORD ON BOTH ROADS, NEVER AN ERROR OF THE
+ * CALL.  Pad columns behind cw (cw / 2) of a destination are unspecified.  No store falls outside the destination's slot_bytes, no
+ * load outside [slots, slots + slots_bytes).  Hops of one call must not name another hop's dst_slot, as destination or as source;
+ * this is not checked, the result is unspecified, but every address stays in bounds.  One launch per call (k_accumulate; one text for
+ * host and device: csrc/leon_accumulate.h).
+ * Outputs.  MOTION is always needed, RESIDUAL when parts & 2; a pipeline lacking one is refused as the gauge family refuses.
+ * NOT in this definition: half-pel interpolation of accumulators, averaging of both references, rebasing a restart cell against the
+ * I picture, the decoder's own chroma vector derivation. */
+#define LEON_ACCUMULATE_MOTION   1
+#define LEON_ACCUMULATE_RESIDUAL 2
+typedef struct leon_pipeline_accumulate_config {
+    int32_t  parts;                /* LEON_ACCUMULATE_MOTION | LEON_ACCUMULATE_RESIDUAL: 1 .. 3 */
+    int32_t  n_slots;              /* 1 .. 65535 */
+    int32_t  reserved[2];          /* must be 0 */
+    uint64_t slot_pitch_bytes;     /* a multiple of 4, at least the layout's slot_bytes */
+    uint64_t slots_bytes;          /* what the caller vouches for behind `slots`: at least n_slots * slot_pitch_bytes */
+} leon_pipeline_accumulate_config; /* 32 bytes */
+/* (a struct tag only, as leon_pipeline_propagate_layout: the host call that fills it has the same name) */
+struct leon_pipeline_accumulate_layout {
+    int32_t  coded_width, coded_height;
+    int32_t  parts;
+    int32_t  planes;               /* planes asked for: 3 or 6 (k_accumulate's grid y) */
+    int32_t  luma_stride, chroma_stride;   /* elements a row */
+    uint32_t ax_offset, ay_offset, age_offset, ry_offset, rcb_offset, rcr_offset;   /* bytes into a slot; 0 for an absent plane */
+    uint32_t slot_bytes;           /* the least slot_pitch_bytes */
+    uint32_t slot_pitch;           /* pad256(slot_bytes) */
+    uint32_t reserved[2];
+};                                 /* 64 bytes */
+typedef struct leon_pipeline_accumulate_call {
+    const leon_pipeline_propagate_hop* hops;   /* DEVICE memory, n records, 4-byte aligned */
+    int32_t  n;                            /* 1 .. 65535 */
+    int32_t  reserved0;                    /* must be 0 */
+    void*    slots;                        /* DEVICE memory, cfg->slots_bytes bytes, 4-byte aligned; written in place */
+    uint8_t* device_via;                   /* DEVICE memory, n x mbh x mbw bytes, may be NULL */
+    int32_t* device_status;                /* DEVICE memory, n words, 4-byte aligned, may be NULL */
+    void*    stream;                       /* hipStream_t of the caller's; NULL: the pipeline's regions stream, and the call waits */
+    uint64_t reserved[2];                  /* must be 0 */
+} leon_pipeline_accumulate_call;           /* 64 bytes */
+/* host only: where the planes of an accumulator lie.  LEON_ERR_INVALID: a null `out`, a coded size the residual layout refuses, parts
+ * outside 1 .. 3. */
+int leon_pipeline_accumulate_layout(int32_t coded_width, int32_t coded_height, int32_t parts, struct leon_pipeline_accumulate_layout* out);
+/* host only: the definition on the CPU (the text the kernel compiles too) for one hop, everything in host memory: motion_records[i] and
+ * residual_records[i] are window frame i's records laid out as leon_pipeline_motion_layout(coded_width / 16, coded_height / 16) and
+ * leon_pipeline_residual_layout say (only the target's are read; residual_records may be NULL without LEON_ACCUMULATE_RESIDUAL), slots
+ * the buffer of cfg->slots_bytes bytes, via this hop's [mbh][mbw] bytes (may be NULL).  Returns the hop's status word (>= 0; the slot and
+ * via are written exactly when it is 0), or LEON_ERR_INVALID (negative) for a null argument, a coded size or cfg the device road
+ * refuses, n_frames < 0, slots not 4-byte aligned, a missing or misaligned record of the target's. */
+int32_t leon_pipeline_accumulate_record(int32_t coded_width, int32_t coded_height, int32_t n_frames, const void* const* motion_records,
+                                        const void* const* residual_records, const leon_pipeline_accumulate_config* cfg,
+                                        const leon_pipeline_propagate_hop* hop, void* slots, uint8_t* via);
+/* Everything in DEVICE memory: the call ONLY ENQUEUES on the caller's stream (stream NULL: the regions stream, and the call waits),
+ * with leon_pipeline_propagate_maps_device's ordering rules and scratch, word for word.
+ * Refused (LEON_ERR_INVALID, nothing enqueued): a null cfg, parts outside 1 .. 3, a non-zero reserved word of cfg, a pipeline without
+ * the outputs the parts need, a window that is not out for delivery or was delivered with an error, a null call, `hops` or `slots`,
+ * hops, slots or device_status not 4-byte aligned, n outside 1 .. 65535, a non-zero reserved word of the call, n_slots or
+ * slot_pitch_bytes outside the above, slots_bytes below n_slots * slot_pitch_bytes. */
+int leon_pipeline_accumulate_device(leon_pipeline* p, int64_t window, const leon_pipeline_accumulate_config* cfg, const leon_pipeline_accumulate_call* call);
+/* Hops and accumulators in host memory, synchronous: the device road between an upload and the copies back.  slots (cfg->slots_bytes
+ * bytes), via (n x mbh x mbw bytes, may be NULL) and status (n words, may be NULL) go up and come back whole, so bytes the kernel
+ * leaves alone stay the caller's.  The call-level refusals are the device road's. */
+int leon_pipeline_accumulate(leon_pipeline* p, int64_t window, const leon_pipeline_accumulate_config* cfg, const leon_pipeline_propagate_hop* hops,
+                             int32_t n, void* slots, uint8_t* via, int32_t* status);
+/* A diagnostic in the manner of leon_pipeline_propagate_kernel: k_accumulate on motion and residual records the CALLER supplies (host
+ * memory, records of window frame i; NULL for frames no hop of the call targets), with memory of its own on device_id's null stream,
+ * synchronous; hops, slots, via (may be NULL) and status (may be NULL) in host memory, going up and coming back whole.  Refused
+ * (LEON_ERR_INVALID): what leon_pipeline_accumulate_record refuses, n outside 1 .. 65535, a valid hop whose target lacks a record. */
+int leon_pipeline_accumulate_kernel(int32_t device_id, int32_t coded_width, int32_t coded_height, int32_t n_frames, const void* const* motion_records_host,
+                                    const void* const* residual_records_host, const leon_pipeline_accumulate_config* cfg,
+                                    const leon_pipeline_propagate_hop* hops, int32_t n, void* slots, uint8_t* via, int32_t* status);
 /* Boxes gauged: what a frame's motion record (LEON_PIPELINE_OUTPUT_MOTION) and activity record (LEON_PIPELINE_OUTPUT_ACTIVITY) say
  * under each box, on the device -- what a "run the detector again here" gate reads of a box that the carry family moved.  Integers only.
  * Records.  A record is a leon_pipeline_region (frame, the box, three reserved words that must be 0): exactly what

@@ -44,6 +44,7 @@
 #include "leon_residual.h"
 #include "leon_carry.h"
 #include "leon_propagate.h"
+#include "leon_accumulate.h"
 #include "leon_gauge.h"
 #include "leon_propose.h"
 #include "leon_overlap.h"
@@ -3352,6 +3353,42 @@ __global__ __launch_bounds__(kRgbaBlock) void k_propagate(const PropagateHop* __
     const int32_t p0 = (int32_t)blockIdx.y * c.g.group, p1 = p0 + c.g.group < c.g.planes ? p0 + c.g.group : c.g.planes;
     uint8_t* v = via && blockIdx.y == 0 ? via + (size_t)i * (size_t)c.g.mh * (size_t)c.g.mw : nullptr;
     propagate_unit(c.g, ring + (size_t)frames[h.target].ring * c.record_pitch, c.info_offset, maps, c.maps_bytes, c.slot_pitch, h, c.fill, v, u, p0, p1);
+}
+
+// ---- accumulate: motion and residual summed along a GOP's chain, a gather through the target's records (include/leon_pipeline.h,
+// leon_pipeline_accumulate) ----
+// One launch per call: blockIdx.z the hop, blockIdx.y the plane among those asked for (AX AY AGE | RY RCb RCr), blockIdx.x x 256 lanes
+// over the plane's work units (leon_accumulate.h: 4 destination elements, 8 bytes, never across a macroblock).  The grid's x is sized
+// for a luma plane; lanes behind a chroma plane's units, and lanes of a refused hop, leave at once.  A lane works out its macroblock
+// and pick as k_propagate does, reads the source's 8 bytes as the aligned dwords around their 2-byte aligned address (v_alignbyte),
+// T's residual as 8 aligned bytes, adds with two packed saturating 16-bit adds and stores 8 bytes: consecutive lanes store
+// consecutive 8 bytes, a wave one 512-byte run of a row.  A unit the clamp touches goes element by element.  via (a byte a
+// macroblock) is written by plane 0 alone, by the lane of the macroblock's first unit; the status word by one lane of the hop.
+// No LDS, no atomics, no barrier, no scratch.  T's records lie at motion + frames[T].ring * motion_pitch and residual + frames[T].ring *
+// residual_pitch, where k_motion and k_residual wrote them (residual may be null where the parts do not ask for it).
+struct AccumulateCall {
+    AccumulateGeom g;
+    size_t slot_pitch, slots_bytes;      // the caller's buffer: n_slots accumulators at slot_pitch, slots_bytes in all
+    int32_t n_frames, n_slots;           // frames of the window, accumulators of the buffer
+    uint32_t info_offset, motion_pitch;  // MotionLayout's
+    uint32_t residual_pitch;             // ResidualLayout's
+    uint32_t reserved;
+};
+
+__global__ __launch_bounds__(kRgbaBlock) void k_accumulate(const PropagateHop* __restrict__ hops, const CarryFrame* __restrict__ frames,
+                                                            const uint8_t* __restrict__ motion, const uint8_t* __restrict__ residual, uint8_t* slots,
+                                                            uint8_t* __restrict__ via, int32_t* __restrict__ status, AccumulateCall c)
+{
+    const uint32_t i = blockIdx.z, u = blockIdx.x * (uint32_t)kRgbaBlock + threadIdx.x;
+    const int32_t q = (int32_t)blockIdx.y;
+    const PropagateHop h = hops[i];
+    const int32_t st = propagate_hop_status(h, c.n_frames, c.n_slots);
+    if (status && u == 0 && q == 0) status[i] = st;
+    if (st != kRegionOk || u >= accumulate_units(c.g, q)) return;
+    const uint32_t ring = frames[h.target].ring;
+    uint8_t* v = via && q == 0 ? via + (size_t)i * (size_t)c.g.mbw * (size_t)(c.g.ch >> 4) : nullptr;
+    accumulate_unit(c.g, motion + (size_t)ring * c.motion_pitch, c.info_offset, residual ? residual + (size_t)ring * c.residual_pitch : nullptr, slots, c.slots_bytes,
+                    c.slot_pitch, h, v, q, u);
 }
 
 // ---- gauge: the statistics of a frame's motion and activity records under a box (include/leon_pipeline.h, leon_pipeline_gauge_regions) --

@@ -3287,6 +3287,191 @@ int propagate_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t mbw, int
     });
 }
 
+// ---- motion and residual accumulated along a GOP's chain (leon_pipeline_accumulate) -------------------------------------------------
+static_assert(sizeof(leon_pipeline_accumulate_config) == 32 && sizeof(struct leon_pipeline_accumulate_layout) == 64 && sizeof(leon_pipeline_accumulate_call) == 64,
+              "include/leon_pipeline.h states the sizes");
+static_assert(leon::kAccumulateMotion == LEON_ACCUMULATE_MOTION && leon::kAccumulateResidual == LEON_ACCUMULATE_RESIDUAL, "the kernel's bits are the header's");
+
+// what a call's accumulators may be: the geometry (leon_accumulate.h) and the caller's buffer around it
+int accumulate_config_check(int32_t cw, int32_t ch, const leon_pipeline_accumulate_config* cfg, leon::AccumulateGeom* g)
+{
+    if (!cfg) return fail(LEON_ERR_INVALID, "accumulate: null cfg");
+    if (cfg->reserved[0] | cfg->reserved[1]) return fail(LEON_ERR_INVALID, "accumulate: a reserved word of cfg is not 0");
+    if (cfg->parts < 1 || cfg->parts > (LEON_ACCUMULATE_MOTION | LEON_ACCUMULATE_RESIDUAL))
+        return fail(LEON_ERR_INVALID, "accumulate: parts %d (LEON_ACCUMULATE_MOTION | LEON_ACCUMULATE_RESIDUAL: 1 .. 3)", cfg->parts);
+    if (const int rc = residual_size_check("accumulate", cw, ch); rc != LEON_OK) return rc;
+    leon::accumulate_geometry(cw, ch, cfg->parts, g);
+    if (cfg->n_slots < 1 || cfg->n_slots > leon::kPropagateMaxSlots) return fail(LEON_ERR_INVALID, "accumulate: %d slots (1 .. %d)", cfg->n_slots, leon::kPropagateMaxSlots);
+    if (cfg->slot_pitch_bytes % 4 || cfg->slot_pitch_bytes < g->slot_bytes)
+        return fail(LEON_ERR_INVALID, "accumulate: slot_pitch_bytes %llu (a multiple of 4 not below the accumulator's %u bytes)", (unsigned long long)cfg->slot_pitch_bytes,
+                    g->slot_bytes);
+    if (cfg->slots_bytes / (uint64_t)cfg->n_slots < cfg->slot_pitch_bytes)
+        return fail(LEON_ERR_INVALID, "accumulate: slots_bytes %llu is below %d slots of %llu bytes", (unsigned long long)cfg->slots_bytes, cfg->n_slots,
+                    (unsigned long long)cfg->slot_pitch_bytes);
+    return LEON_OK;
+}
+
+int accumulate_layout_host(int32_t cw, int32_t ch, int32_t parts, struct leon_pipeline_accumulate_layout* out)
+{
+    if (!out) return fail(LEON_ERR_INVALID, "null argument");
+    if (const int rc = residual_size_check("accumulate layout", cw, ch); rc != LEON_OK) return rc;
+    leon::AccumulateGeom g;
+    if (!leon::accumulate_geometry(cw, ch, parts, &g)) return fail(LEON_ERR_INVALID, "accumulate layout: parts %d (LEON_ACCUMULATE_MOTION | LEON_ACCUMULATE_RESIDUAL: 1 .. 3)", parts);
+    memset(out, 0, sizeof(*out));
+    out->coded_width = cw; out->coded_height = ch; out->parts = parts; out->planes = g.planes;
+    out->luma_stride = (int32_t)g.luma_stride; out->chroma_stride = (int32_t)g.chroma_stride;
+    out->ax_offset = g.off[leon::kAccAX]; out->ay_offset = g.off[leon::kAccAY]; out->age_offset = g.off[leon::kAccAGE];
+    out->ry_offset = g.off[leon::kAccRY]; out->rcb_offset = g.off[leon::kAccRCb]; out->rcr_offset = g.off[leon::kAccRCr];
+    out->slot_bytes = g.slot_bytes; out->slot_pitch = (uint32_t)pad256(g.slot_bytes);
+    return LEON_OK;
+}
+
+// the launch every road shares: hops, the window's table, the two rings (the residual ring null where the parts do not read it) and
+// the accumulators in device memory; x sized for a luma plane
+void accumulate_launch(hipStream_t st, const leon::PropagateHop* d_hops, const leon::CarryFrame* d_frames, const uint8_t* d_motion, const uint8_t* d_residual,
+                       const leon::AccumulateGeom& g, const leon::MotionLayout& ml, const leon::ResidualLayout& rl, int32_t n_frames,
+                       const leon_pipeline_accumulate_config& cfg, int32_t n, uint8_t* d_slots, uint8_t* d_via, int32_t* d_status)
+{
+    leon::AccumulateCall C{};
+    C.g = g;
+    C.slot_pitch = (size_t)cfg.slot_pitch_bytes; C.slots_bytes = (size_t)cfg.slots_bytes;
+    C.n_frames = n_frames; C.n_slots = cfg.n_slots;
+    C.info_offset = ml.info_offset; C.motion_pitch = ml.record_pitch; C.residual_pitch = rl.record_pitch;
+    const dim3 grid((g.units_luma + leon::kRgbaBlock - 1) / leon::kRgbaBlock, (unsigned)g.planes, (unsigned)n);
+    hipLaunchKernelGGL(leon::k_accumulate, grid, dim3(leon::kRgbaBlock), 0, st, d_hops, d_frames, d_motion, (cfg.parts & LEON_ACCUMULATE_RESIDUAL) ? d_residual : nullptr, d_slots,
+                       d_via, d_status, C);
+}
+
+// the record outputs a call's parts need are the pipeline's: MOTION always, RESIDUAL for its part
+int accumulate_outputs_check(const leon_pipeline* p, int32_t parts)
+{
+    if (!p->motion.ring) return no_output("motion", "MOTION");
+    if ((parts & LEON_ACCUMULATE_RESIDUAL) && !p->residual.ring) return no_output("residual", "RESIDUAL");
+    return LEON_OK;
+}
+int accumulate_parts_check(const leon_pipeline_accumulate_config* cfg)
+{
+    if (!cfg) return fail(LEON_ERR_INVALID, "accumulate: null cfg");
+    if (cfg->parts < 1 || cfg->parts > (LEON_ACCUMULATE_MOTION | LEON_ACCUMULATE_RESIDUAL))
+        return fail(LEON_ERR_INVALID, "accumulate: parts %d (LEON_ACCUMULATE_MOTION | LEON_ACCUMULATE_RESIDUAL: 1 .. 3)", cfg->parts);
+    return LEON_OK;
+}
+
+// One call of the device road: the host's refusals (the parts' and the outputs' before the window's, as gauge's), then one launch
+int accumulate_device(leon_pipeline* p, int64_t window, const leon_pipeline_accumulate_config* cfg, const leon_pipeline_accumulate_call* c)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = accumulate_parts_check(cfg);
+    if (rc != LEON_OK || (rc = accumulate_outputs_check(p, cfg->parts)) != LEON_OK) return rc;
+    if (!c) return fail(LEON_ERR_INVALID, "null argument");
+    leon::AccumulateGeom g;
+    return table_road(p, window, c->stream, "accumulate", "hops", c->n, c->reserved0 || c->reserved[0] || c->reserved[1], [&] {
+        if (!c->hops) return fail(LEON_ERR_INVALID, "accumulate: null hops");
+        if (!c->slots) return fail(LEON_ERR_INVALID, "accumulate: null slots");
+        if (((uintptr_t)c->hops | (uintptr_t)c->slots | (uintptr_t)c->device_status) & 3u)
+            return fail(LEON_ERR_INVALID, "accumulate: hops %p, slots %p, device_status %p: not all 4-byte aligned", (const void*)c->hops, c->slots, (void*)c->device_status);
+        return accumulate_config_check(p->vinfo.coded_width, p->vinfo.coded_height, cfg, &g);
+    }, [&](hipStream_t st, const leon::CarryFrame* d_frames, int32_t n_frames) {
+        accumulate_launch(st, reinterpret_cast<const leon::PropagateHop*>(c->hops), d_frames, p->motion.ring, p->residual.ring, g, p->motion_lay, p->residual_lay, n_frames, *cfg,
+                          c->n, static_cast<uint8_t*>(c->slots), c->device_via, c->device_status);
+    });
+}
+
+// One call of the host road: [hops | status | via | slots], the accumulators and what the caller has in via and status going up first
+int accumulate(leon_pipeline* p, int64_t window, const leon_pipeline_accumulate_config* cfg, const leon_pipeline_propagate_hop* hops, int32_t n, void* slots, uint8_t* via,
+               int32_t* status)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = accumulate_parts_check(cfg);
+    if (rc != LEON_OK || (rc = accumulate_outputs_check(p, cfg->parts)) != LEON_OK) return rc;
+    if (!hops || !slots) return fail(LEON_ERR_INVALID, "accumulate: null %s", hops ? "slots" : "hops");
+    if ((rc = record_count_check("accumulate", "hops", n)) != LEON_OK) return rc;
+    leon::AccumulateGeom g;
+    if ((rc = accumulate_config_check(p->vinfo.coded_width, p->vinfo.coded_height, cfg, &g)) != LEON_OK) return rc;
+    const size_t via_bytes = (size_t)n * (size_t)g.mbw * (size_t)(g.ch >> 4);
+    return table_host_road(p, window, "accumulate", {{hops, nullptr, (size_t)n * 32}, {status, status, (size_t)n * 4}, {via, via, via_bytes}, {slots, slots, (size_t)cfg->slots_bytes}},
+                           [&](const Pieces& s) {
+        leon_pipeline_accumulate_call c{};
+        c.hops = s.at<const leon_pipeline_propagate_hop>(0);
+        c.n = n;
+        c.slots = s.at(3);
+        c.device_via = via ? s.at(2) : nullptr;
+        c.device_status = status ? s.at<int32_t>(1) : nullptr;
+        return accumulate_device(p, window, cfg, &c);
+    });
+}
+
+// what the CPU road and the diagnostic refuse of their geometry
+int accumulate_host_check(int32_t cw, int32_t ch, int32_t n_frames, const void* const* motion, const void* const* residual, const leon_pipeline_accumulate_config* cfg,
+                          const void* hops, const void* slots, leon::AccumulateGeom* g)
+{
+    if (!motion || !cfg || !hops || !slots) return fail(LEON_ERR_INVALID, "null argument");
+    if (n_frames < 0) return fail(LEON_ERR_INVALID, "accumulate: %d frames", n_frames);
+    if (const int rc = accumulate_config_check(cw, ch, cfg, g); rc != LEON_OK) return rc;
+    if ((cfg->parts & LEON_ACCUMULATE_RESIDUAL) && !residual) return fail(LEON_ERR_INVALID, "accumulate: null residual records with LEON_ACCUMULATE_RESIDUAL");
+    if ((uintptr_t)slots & 3u) return fail(LEON_ERR_INVALID, "accumulate: slots %p is not 4-byte aligned", slots);
+    return LEON_OK;
+}
+// the records a valid hop reads must be there
+int accumulate_records_check(const leon::PropagateHop& h, int32_t i, int32_t parts, const void* const* motion, const void* const* residual)
+{
+    if (!motion[h.target]) return fail(LEON_ERR_INVALID, "accumulate: frame %d is the target of hop %d and has no motion record", h.target, i);
+    if ((parts & LEON_ACCUMULATE_RESIDUAL) && !residual[h.target]) return fail(LEON_ERR_INVALID, "accumulate: frame %d is the target of hop %d and has no residual record", h.target, i);
+    return LEON_OK;
+}
+
+// the definition on the CPU: the same text (leon_accumulate.h), every unit of every plane asked for; the status word, or a negative error
+int32_t accumulate_record_host(int32_t cw, int32_t ch, int32_t n_frames, const void* const* motion, const void* const* residual, const leon_pipeline_accumulate_config* cfg,
+                               const leon_pipeline_propagate_hop* hop, void* slots, uint8_t* via)
+{
+    leon::AccumulateGeom g;
+    int rc = accumulate_host_check(cw, ch, n_frames, motion, residual, cfg, hop, slots, &g);
+    if (rc != LEON_OK) return rc;
+    const leon::PropagateHop& h = reinterpret_cast<const leon::PropagateHop&>(*hop);
+    const int32_t st = leon::propagate_hop_status(h, n_frames, cfg->n_slots);
+    if (st != leon::kRegionOk) return st;
+    if ((rc = accumulate_records_check(h, 0, cfg->parts, motion, residual)) != LEON_OK) return rc;
+    const uint8_t* mrec = static_cast<const uint8_t*>(motion[h.target]);
+    const uint8_t* rrec = (cfg->parts & LEON_ACCUMULATE_RESIDUAL) ? static_cast<const uint8_t*>(residual[h.target]) : nullptr;
+    if (((uintptr_t)mrec & 3u) || ((uintptr_t)rrec & 7u)) return fail(LEON_ERR_INVALID, "accumulate: records %p (4-byte aligned), %p (8-byte aligned)", (const void*)mrec, (const void*)rrec);
+    const leon::MotionLayout L = leon::motion_layout((uint32_t)g.mbw, (uint32_t)(ch >> 4));
+    for (int32_t q = 0; q < g.planes; q++)
+        for (uint32_t u = 0; u < leon::accumulate_units(g, q); u++)
+            leon::accumulate_unit(g, mrec, L.info_offset, rrec, static_cast<uint8_t*>(slots), (size_t)cfg->slots_bytes, (size_t)cfg->slot_pitch_bytes, h, q == 0 ? via : nullptr, q, u);
+    return leon::kRegionOk;
+}
+
+// k_accumulate on records the caller supplies (leon_pipeline_accumulate_kernel): memory of its own, the null stream
+int accumulate_kernel(int32_t device_id, int32_t cw, int32_t ch, int32_t n_frames, const void* const* motion, const void* const* residual,
+                      const leon_pipeline_accumulate_config* cfg, const leon_pipeline_propagate_hop* hops, int32_t n, void* slots, uint8_t* via, int32_t* status)
+{
+    leon::AccumulateGeom g;
+    int rc = accumulate_host_check(cw, ch, n_frames, motion, residual, cfg, hops, slots, &g);
+    if (rc != LEON_OK) return rc;
+    if ((rc = record_count_check("accumulate", "hops", n)) != LEON_OK) return rc;
+    const bool res = (cfg->parts & LEON_ACCUMULATE_RESIDUAL) != 0;
+    for (int32_t i = 0; i < n; i++) {
+        const leon::PropagateHop& h = reinterpret_cast<const leon::PropagateHop&>(hops[i]);
+        if (leon::propagate_hop_status(h, n_frames, cfg->n_slots) == leon::kRegionOk && (rc = accumulate_records_check(h, i, cfg->parts, motion, residual)) != LEON_OK) return rc;
+    }
+    const int32_t mbh = ch >> 4;
+    const leon::MotionLayout ML = leon::motion_layout((uint32_t)g.mbw, (uint32_t)mbh);
+    const leon::ResidualLayout RL = leon::residual_layout((uint32_t)cw, (uint32_t)ch);
+    // a frame with a record of either kind gets a slot in both rings, as the pipeline's rings share an index
+    uint32_t ring_slots;
+    const std::vector<leon::CarryFrame> table = kernel_table(n_frames, nullptr, nullptr, [&](size_t i) { return motion[i] || (res && residual[i]); }, &ring_slots);
+    const std::vector<uint8_t> mring = kernel_ring(table, ring_slots, motion, ML.record_bytes, ML.record_pitch);
+    const std::vector<uint8_t> rring = kernel_ring(table, ring_slots, res ? residual : nullptr, RL.record_bytes, RL.record_pitch);
+    const size_t via_bytes = (size_t)n * (size_t)g.mbw * (size_t)mbh;
+    return pieces_run(device_id, "accumulate", {{hops, nullptr, (size_t)n * 32}, {status, status, (size_t)n * 4}, {via, via, via_bytes}, {slots, slots, (size_t)cfg->slots_bytes},
+                                                {table.data(), nullptr, table.size() * sizeof(leon::CarryFrame)}, {mring.data(), nullptr, mring.size()},
+                                                {rring.data(), nullptr, rring.size()}}, [&](const Pieces& s) {
+        accumulate_launch(nullptr, s.at<const leon::PropagateHop>(0), s.at<const leon::CarryFrame>(4), s.at(5), res ? s.at(6) : nullptr, g, ML, RL, n_frames, *cfg, n, s.at(3),
+                          via ? s.at(2) : nullptr, status ? s.at<int32_t>(1) : nullptr);
+        return (int)LEON_OK;
+    });
+}
+
 // The device's rows of a batch of single axes, copied back (leon_pipeline_resize_weights_device): memory of its own, the null stream
 int resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,
                           int32_t* weights, int32_t* status)
@@ -4503,6 +4688,35 @@ int leon_pipeline_propagate_kernel(int32_t device_id, int32_t frame_width, int32
                                    uint8_t* via, int32_t* status)
 {
     return propagate_kernel(device_id, frame_width, frame_height, mb_width, mb_height, n_frames, records_host, cfg, hops, n, maps, via, status);
+}
+
+int leon_pipeline_accumulate_layout(int32_t coded_width, int32_t coded_height, int32_t parts, struct leon_pipeline_accumulate_layout* out)
+{
+    return accumulate_layout_host(coded_width, coded_height, parts, out);
+}
+
+int32_t leon_pipeline_accumulate_record(int32_t coded_width, int32_t coded_height, int32_t n_frames, const void* const* motion_records, const void* const* residual_records,
+                                        const leon_pipeline_accumulate_config* cfg, const leon_pipeline_propagate_hop* hop, void* slots, uint8_t* via)
+{
+    return accumulate_record_host(coded_width, coded_height, n_frames, motion_records, residual_records, cfg, hop, slots, via);
+}
+
+int leon_pipeline_accumulate_device(leon_pipeline* p, int64_t window, const leon_pipeline_accumulate_config* cfg, const leon_pipeline_accumulate_call* call)
+{
+    return accumulate_device(p, window, cfg, call);
+}
+
+int leon_pipeline_accumulate(leon_pipeline* p, int64_t window, const leon_pipeline_accumulate_config* cfg, const leon_pipeline_propagate_hop* hops, int32_t n, void* slots,
+                             uint8_t* via, int32_t* status)
+{
+    return accumulate(p, window, cfg, hops, n, slots, via, status);
+}
+
+int leon_pipeline_accumulate_kernel(int32_t device_id, int32_t coded_width, int32_t coded_height, int32_t n_frames, const void* const* motion_records_host,
+                                    const void* const* residual_records_host, const leon_pipeline_accumulate_config* cfg, const leon_pipeline_propagate_hop* hops, int32_t n,
+                                    void* slots, uint8_t* via, int32_t* status)
+{
+    return accumulate_kernel(device_id, coded_width, coded_height, n_frames, motion_records_host, residual_records_host, cfg, hops, n, slots, via, status);
 }
 
 int leon_pipeline_resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,

@@ -98,6 +98,17 @@
  *                                  back to back, and the library takes slots a multiple of 4 bytes apart only: planes * mh * mw *
  *                                  elemBytes must be a multiple of 4 (a 61 x 45 uint8 mask of one plane is refused with a throw; give
  *                                  it a second plane, or 2-byte elements)
+ *   p.accumulate(window, hops, {parts, slots}) -> {slots: Int16Array, via: Uint8Array [n][mbh][mbw] (0 restart, 1 forward, 2 backward),
+ *                                  status: Int32Array [n], layout}: motion and residual accumulated along a chain of predictions
+ *                                  (leon_pipeline_accumulate, opts.motion; opts.residual for parts 2 and 3).  An accumulator lies over
+ *                                  the CODED picture: parts & 1 the planes AX, AY, AGE (where a sample came from in the picture the
+ *                                  chain started at, and after how many hops), parts & 2 the planes RY, RCb, RCr (the sum of the
+ *                                  residual along that path), int16, at layout.axOffset .. layout.rcrOffset bytes into a slot of
+ *                                  layout.slotBytes, rows layout.lumaStride / chromaStride elements apart.  parts: by default every part
+ *                                  the pipeline's outputs allow.  slots: an Int16Array over a whole number of accumulators, WRITTEN IN
+ *                                  PLACE and handed back, or how many to make (all zero; by default one more than the largest slot the
+ *                                  hops name).  hops = [[targetFrameIndex, dstSlot, fwdSlot, bwdSlot], ...] as propagateMaps takes them;
+ *                                  a hop with both sources -1 writes a chain's start (all zero).  A hop's fault is its status word
  *   p.releaseWindow(window); p.stats(); p.destroy();
  * Open GOPs (closed_gop = 0) need no option: their leading B pictures predict from the GOP before; where that GOP is not decoded (start,
  * seek target, broken_link) they are not delivered and the GOP's frames start at its I picture's displayIndex (include/leon_pipeline.h).
@@ -141,6 +152,7 @@ class LeonPipeline extends EventEmitter {
     if (opts.motion) output = (output || OUTPUTS.rgba) | 32;          // LEON_PIPELINE_OUTPUT_MOTION beside whatever output resolves to
     if (opts.activity) output = (output || OUTPUTS.rgba) | 128;       // LEON_PIPELINE_OUTPUT_ACTIVITY likewise
     if (opts.residual) output = (output || OUTPUTS.rgba) | 512;       // LEON_PIPELINE_OUTPUT_RESIDUAL likewise
+    this._accumulateParts = 1 | (opts.residual ? 2 : 0);          // what accumulate writes without opts.parts: every part the outputs allow
     this._gaugeSources = (opts.motion ? 1 : 0) | (opts.activity ? 2 : 0);          // what gaugeRegions reads without opts.sources: every record output there is
     const tensorDtype = named(opts.tensorDtype, { float16: 1, bfloat16: 2, float32: 3, uint8: 8 }, "tensorDtype: 'float16', 'bfloat16', 'float32' or 'uint8'");
     const tensorLayout = named(opts.tensorLayout, { chw: 0, hwc: 1 }, "tensorLayout: 'chw' or 'hwc'");
@@ -263,6 +275,16 @@ class LeonPipeline extends EventEmitter {
     const { stride = 1, planes = 1, elemBytes = 1, fill = 0 } = opts;
     ints([stride, planes, elemBytes, fill], 4, 'opts: {stride, planes, elemBytes, fill} are integers');
     return this._p.propagateMaps(window, maps, words, stride, planes, elemBytes, fill >>> 0);
+  }
+  // hops as propagateMaps takes them; opts.slots: an Int16Array of accumulators (written in place) or how many to make, all zero
+  accumulate(window, hops, opts = {}) {
+    const words = rows(hops, 4, 'hops: [[targetFrameIndex, dstSlot, fwdSlot, bwdSlot], ...]');
+    const { parts = this._accumulateParts } = opts;
+    let { slots } = opts;
+    if (slots === undefined) slots = hops.reduce((m, h) => Math.max(m, h[1], h[2], h[3]), 0) + 1;
+    if (!(slots instanceof Int16Array)) ints([slots], 1, 'opts.slots: an Int16Array over whole accumulators, or their number');
+    ints([parts], 1, 'opts.parts: 1 (motion), 2 (residual) or 3');
+    return this._p.accumulate(window, words, parts, slots);
   }
   releaseWindow(window) { this._p.releaseWindow(window); }
   stats() { return this._p.stats(); }

@@ -55,6 +55,8 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_carry_regions", "leon_pipeline_carry_device",
     "leon_pipeline_propagate_layout", "leon_pipeline_propagate_record", "leon_pipeline_propagate_maps_device", "leon_pipeline_propagate_maps",
     "leon_pipeline_propagate_kernel",
+    "leon_pipeline_accumulate_layout", "leon_pipeline_accumulate_record", "leon_pipeline_accumulate_device", "leon_pipeline_accumulate",
+    "leon_pipeline_accumulate_kernel",
     "leon_pipeline_gauge_record", "leon_pipeline_gauge_regions_device", "leon_pipeline_gauge_regions", "leon_pipeline_gauge_kernel",
     "leon_pipeline_propose_record", "leon_pipeline_propose_regions_device", "leon_pipeline_propose_regions", "leon_pipeline_propose_kernel",
     "leon_pipeline_suppress_record", "leon_pipeline_suppress_regions_device", "leon_pipeline_suppress_regions", "leon_pipeline_suppress_kernel",
@@ -370,6 +372,9 @@ REGION_SCALE, REGION_OFFSET = 7, 8           # LEON_REGION_SCALE, LEON_REGION_OF
 REGION_NO_REFERENCE = 9                      # LEON_REGION_NO_REFERENCE: a carry record's own
 REGION_SLOT = 10                             # LEON_REGION_SLOT: a propagate record's own
 GAUGE_MOTION, GAUGE_ACTIVITY = 1, 2          # LEON_GAUGE_*: the bits of a gauge call's sources
+ACCUMULATE_MOTION = 1                        # LEON_ACCUMULATE_MOTION: AX, AY, AGE
+ACCUMULATE_RESIDUAL = 2                      # LEON_ACCUMULATE_RESIDUAL: RY, RCb, RCr
+ACCUMULATE_PLANES = ("AX", "AY", "AGE", "RY", "RCb", "RCr")          # the planes of an accumulator, in their order in a slot
 GAUGE_WORDS = 16                             # int64 words of a gauged record's statistics
 PROPOSE_MOTION, PROPOSE_ACTIVITY = 1, 2      # LEON_PROPOSE_*: the bits of a propose call's sources
 PROPOSE_INTRA = 1                            # LEON_PROPOSE_INTRA: the bit of its flags
@@ -451,6 +456,21 @@ class PipelinePropagateLayout(C.Structure):
 
 class PipelinePropagateMapsCall(C.Structure):
     _fields_ = [("hops", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("maps", C.c_void_p), ("device_via", C.c_void_p), ("device_status", C.c_void_p),
+                ("stream", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class PipelineAccumulateConfig(C.Structure):
+    _fields_ = [("parts", C.c_int32), ("n_slots", C.c_int32), ("reserved", C.c_int32 * 2), ("slot_pitch_bytes", C.c_uint64), ("slots_bytes", C.c_uint64)]
+
+
+class PipelineAccumulateLayout(C.Structure):
+    _fields_ = [("coded_width", C.c_int32), ("coded_height", C.c_int32), ("parts", C.c_int32), ("planes", C.c_int32), ("luma_stride", C.c_int32), ("chroma_stride", C.c_int32),
+                ("ax_offset", C.c_uint32), ("ay_offset", C.c_uint32), ("age_offset", C.c_uint32), ("ry_offset", C.c_uint32), ("rcb_offset", C.c_uint32),
+                ("rcr_offset", C.c_uint32), ("slot_bytes", C.c_uint32), ("slot_pitch", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class PipelineAccumulateCall(C.Structure):
+    _fields_ = [("hops", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("slots", C.c_void_p), ("device_via", C.c_void_p), ("device_status", C.c_void_p),
                 ("stream", C.c_void_p), ("reserved", C.c_uint64 * 2)]
 
 
@@ -671,6 +691,16 @@ def load():
         lib.leon_pipeline_propagate_maps.argtypes = [C.c_void_p, C.c_int64, P(PipelinePropagateConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.leon_pipeline_propagate_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(PipelinePropagateConfig), C.c_void_p,
                                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_accumulate"):
+        P = C.POINTER
+        lib.leon_pipeline_accumulate_layout.argtypes = [C.c_int32, C.c_int32, C.c_int32, P(PipelineAccumulateLayout)]
+        lib.leon_pipeline_accumulate_record.argtypes = [C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineAccumulateConfig), C.c_void_p, C.c_void_p,
+                                                        C.c_void_p]
+        lib.leon_pipeline_accumulate_record.restype = C.c_int32
+        lib.leon_pipeline_accumulate_device.argtypes = [C.c_void_p, C.c_int64, P(PipelineAccumulateConfig), P(PipelineAccumulateCall)]
+        lib.leon_pipeline_accumulate.argtypes = [C.c_void_p, C.c_int64, P(PipelineAccumulateConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_accumulate_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineAccumulateConfig), C.c_void_p,
+                                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(lib, "leon_pipeline_gauge_regions"):
         P = C.POINTER
         lib.leon_pipeline_gauge_record.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineGaugeConfig), C.c_void_p,
@@ -1609,6 +1639,136 @@ def propagate_plan(refs, frames, src):
     return [levels[k] for k in sorted(levels)], [t for t in group if t not in reach]
 
 
+def accumulate_layout(cw, ch, parts=ACCUMULATE_MOTION | ACCUMULATE_RESIDUAL):
+    """leon_pipeline_accumulate_layout: where the planes of an accumulator over a coded picture of cw x ch lie (PipelineAccumulateLayout), no device"""
+    out = PipelineAccumulateLayout()
+    _chk(load().leon_pipeline_accumulate_layout(int(cw), int(ch), int(parts), C.byref(out)))
+    return out
+
+
+def accumulate_names(parts):
+    """the planes `parts` asks for, in their order in a slot"""
+    return tuple(n for i, n in enumerate(ACCUMULATE_PLANES) if int(parts) & (ACCUMULATE_MOTION if i < 3 else ACCUMULATE_RESIDUAL))
+
+
+def accumulate_views(buf, lay):
+    """a buffer of accumulators (uint8 [S, pitch], pitch at least lay.slot_bytes) -> {name: int16 view [S, h, w]} of the planes the layout
+    holds, cropped to the coded size: [S, ch, cw] for AX, AY, AGE, RY and [S, ch / 2, cw / 2] for RCb, RCr.  Views, not copies."""
+    S, pitch = buf.shape
+    cw, ch = lay.coded_width, lay.coded_height
+    out = {}
+    for name in accumulate_names(lay.parts):
+        chroma = name in ("RCb", "RCr")
+        h, w, stride = (ch // 2, cw // 2, lay.chroma_stride) if chroma else (ch, cw, lay.luma_stride)
+        off = getattr(lay, name.lower() + "_offset")
+        out[name] = np.lib.stride_tricks.as_strided(buf.reshape(-1)[off:].view("<i2"), shape=(S, h, w), strides=(pitch, 2 * stride, 2))
+    return out
+
+
+def accumulate_hop(cw, ch, n_frames, motion, residual, hop, acc):
+    """The definition of one hop of leon_pipeline_accumulate (include/leon_pipeline.h) in numpy integers, written from the header's text
+    and independent of the C code.  motion[i] = (mv [mbh, mbw, 4] int16, info [mbh, mbw] uint8), residual[i] = (y [ch, cw], cb, cr
+    [ch / 2, cw / 2]) int16 of window frame i (None where no record is at hand; residual may be None without residual planes); hop =
+    the 8 words (target, dst_slot, fwd_slot, bwd_slot, 0, 0, 0, 0) (or the first four); acc = {name: int16 array [S, h, w]} with the
+    planes of one or both parts (AX AY AGE | RY RCb RCr), WRITTEN IN PLACE (acc[name][dst_slot]) where the status is 0.  Returns
+    (status, via): via [mbh, mbw] uint8, None where the status is not 0."""
+    hop = [int(v) for v in hop] + [0] * (8 - len(hop))
+    T, dst, fs, bs = hop[:4]
+    cw, ch = int(cw), int(ch)
+    names = [n for n in ACCUMULATE_PLANES if n in acc]
+    if cw % 16 or ch % 16 or set(names) not in ({"AX", "AY", "AGE"}, {"RY", "RCb", "RCr"}, set(ACCUMULATE_PLANES)):
+        raise ValueError("accumulate_hop: a coded size of %d x %d, planes %s" % (cw, ch, names))
+    S = acc[names[0]].shape[0]
+    if any(hop[4:]):
+        return REGION_RESERVED, None
+    if not 0 <= T < int(n_frames):
+        return REGION_FRAME, None
+    if not (0 <= dst < S and -1 <= fs < S and -1 <= bs < S) or dst == fs or dst == bs:
+        return REGION_SLOT, None
+    mv, info = np.asarray(motion[T][0]).astype(np.int64), np.asarray(motion[T][1]).astype(np.int64)
+    use_f = ((info & 1) != 0) & (fs >= 0)
+    use_b = ~use_f & ((info & 2) != 0) & (bs >= 0)
+    res = dict(zip(("RY", "RCb", "RCr"), residual[T])) if "RY" in acc else {}
+    for name in names:
+        step = 2 if name in ("RCb", "RCr") else 1          # luma pixels an element: the rounding is floor((v + step) / (2 step))
+        h, w = ch // step, cw // step
+        y, x = np.mgrid[0:h, 0:w]
+        kj, ki = (y * step) >> 4, (x * step) >> 4
+        f, b, v = use_f[kj, ki], use_b[kj, ki], mv[kj, ki]
+        dx = (np.where(f, v[..., 0], v[..., 2]) + step) // (2 * step)          # (numpy's integer division floors, also for negatives)
+        dy = (np.where(f, v[..., 1], v[..., 3]) + step) // (2 * step)
+        sx, sy = np.clip(x + dx, 0, w - 1), np.clip(y + dy, 0, h - 1)
+        own = {"AX": sx - x, "AY": sy - y, "AGE": 1}.get(name)
+        if own is None:
+            own = np.asarray(res[name]).astype(np.int64)
+        plane = acc[name]
+        out = np.zeros((h, w), dtype=np.int64)
+        for use, slot in ((f, fs), (b, bs)):
+            if slot >= 0:
+                out[use] = (plane[slot].astype(np.int64)[sy, sx] + own)[use]
+        plane[dst] = np.clip(out, -32768, 32767).astype(np.int16)
+    return REGION_OK, (use_f * 1 + use_b * 2).astype(np.uint8)
+
+
+def _residual_records(residual, cw, ch):
+    """(pointer array, the buffers it points into) of residual[i] = (y, cb, cr) or None, each laid out as residual_layout says (8-byte aligned)"""
+    lay = residual_layout(cw, ch)
+    n = 0 if residual is None else len(residual)
+    ptrs, keep = (C.c_void_p * max(1, n))(), []
+    for i in range(n):
+        if residual[i] is None:
+            continue
+        buf = np.zeros(lay.record_pitch // 8, dtype=np.uint64).view(np.uint8)
+        for plane, off, stride in zip(residual[i], (0, lay.cb_offset, lay.cr_offset), (lay.luma_stride, lay.chroma_stride, lay.chroma_stride)):
+            plane = np.ascontiguousarray(plane, dtype=np.int16)
+            np.lib.stride_tricks.as_strided(buf[off:].view("<i2"), shape=plane.shape, strides=(2 * stride, 2))[...] = plane
+        keep.append(buf)
+        ptrs[i] = buf.ctypes.data
+    return ptrs, keep
+
+
+def _accumulate_config(buf, parts, over=None):
+    """PipelineAccumulateConfig of a numpy buffer uint8 [S, pitch]; `over` replaces fields (the refusals' tests)"""
+    if not (isinstance(buf, np.ndarray) and buf.dtype == np.uint8 and buf.ndim == 2 and buf.flags.c_contiguous):
+        raise ValueError("slots: a contiguous uint8 array [S, pitch]")
+    cfg = PipelineAccumulateConfig(int(parts), buf.shape[0], (C.c_int32 * 2)(0, 0), buf.shape[1], buf.shape[0] * buf.shape[1])
+    for k, v in (over or {}).items():
+        setattr(cfg, k, (C.c_int32 * 2)(*v) if k == "reserved" else v)
+    return cfg
+
+
+def accumulate_record(cw, ch, n_frames, motion, residual, hop, parts, slots, via_fill=0, **over):
+    """leon_pipeline_accumulate_record: the library's CPU evaluation of one hop; motion, residual and hop as accumulate_hop's, slots a
+    uint8 array [S, pitch] written in place (accumulate_views takes it apart).  Returns (status, via [mbh, mbw] uint8 that holds
+    `via_fill` where the library wrote nothing); LeonError where it refuses the call."""
+    mptrs, keep = _carry_records(motion, int(cw) // 16, int(ch) // 16)
+    rptrs, rkeep = _residual_records(residual, cw, ch)
+    h = _records_array([hop])
+    via = np.full((int(ch) // 16, int(cw) // 16), via_fill, dtype=np.uint8)
+    cfg = _accumulate_config(slots, parts, over)
+    st = load().leon_pipeline_accumulate_record(int(cw), int(ch), int(n_frames), mptrs, rptrs if residual is not None else None, C.byref(cfg), h.ctypes.data, slots.ctypes.data,
+                                                via.ctypes.data)
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return st, via
+
+
+def accumulate_kernel(cw, ch, n_frames, motion, residual, hops, parts, slots, via=True, status=True, device_id=0, via_fill=0, status_fill=-1, n=None, **over):
+    """leon_pipeline_accumulate_kernel: k_accumulate on records the caller supplies (as accumulate_hop's), hops = [(target, dst_slot,
+    fwd_slot, bwd_slot), ...], slots uint8 [S, pitch] written in place -> (via [m, mbh, mbw] uint8 pre-filled with `via_fill`, status [m]
+    int32 pre-filled with `status_fill`); via=False / status=False hand the library NULL, and the array comes back as it was filled.
+    n: the count handed to the library when it is to differ from m = len(hops)."""
+    mptrs, keep = _carry_records(motion, int(cw) // 16, int(ch) // 16)
+    rptrs, rkeep = _residual_records(residual, cw, ch)
+    h = _records_array(hops)
+    v, st = _result_arrays(len(h), ((int(ch) // 16, int(cw) // 16), via_fill, np.uint8), ((), status_fill, np.int32))
+    cfg = _accumulate_config(slots, parts, over)
+    _chk(load().leon_pipeline_accumulate_kernel(int(device_id), int(cw), int(ch), int(n_frames), mptrs, rptrs if residual is not None else None, C.byref(cfg),
+                                                h.ctypes.data if len(h) else None, len(h) if n is None else int(n), slots.ctypes.data, v.ctypes.data if via else None,
+                                                st.ctypes.data if status else None))
+    return v[:len(h)], st[:len(h)]
+
+
 def warp_rgb(rgb, m, size, pad=(0, 0, 0)):
     """The definition of leon_pipeline_warp_regions in numpy integers (include/leon_pipeline.h), written from the header's text: rgb
     [H, W, 3] uint8 -- the CPU twin's colours of the frame, the fill row of an odd height included -- sampled along the Q16 map
@@ -2096,7 +2256,12 @@ class Pipeline:
     Propagating dense maps (motion=True): propagate_maps_device(window, maps, hops, stride) writes the map of a frame -- a mask, heatmaps,
     features at 1, 2, 4, 8 or 16 frame pixels a cell -- as a gather from the maps of the pictures it predicts from, through its own motion
     record, on the device (propagate_map states one hop; propagate_maps is the same from host arrays); propagate_maps_gop(window, map,
-    src, stride) takes a network's output on frame `src` to every frame of its GOP."""
+    src, stride) takes a network's output on frame `src` to every frame of its GOP.
+    Accumulating motion and residual (motion=True; residual=True for the residual planes): accumulate_device(window, slots, hops, parts)
+    writes the accumulator of a frame -- per sample where it came from in the picture the chain started at (AX, AY, AGE) and the sum of
+    the residual records along that path (RY, RCb, RCr), int16 planes over the coded picture -- through its own motion record from the
+    accumulators of the pictures it predicts from (accumulate_hop states one hop; accumulate is the same from host arrays);
+    accumulate_gop(window, src) traces every frame of `src`'s GOP back to `src`: what a compressed-domain video model reads."""
 
     def __init__(self, data, device_id=0, parser_threads=0, gops_per_window=0, windows_in_flight=0, max_gop_pictures=0,
                  loop=0, on_window=None, shard_index=0, shard_count=0, start_seconds=0.0, gpu_parser=None, valid_bytes=None, display_flavour=0,
@@ -2729,6 +2894,107 @@ class Pipeline:
             first = stop
         status[rows] = status_hops
         return maps, via, status
+
+    def _accumulate_parts(self, parts):
+        """the parts of a call: None is every part the pipeline's outputs allow"""
+        _need_output(self.motion_layout, "motion")
+        if parts is None:
+            return ACCUMULATE_MOTION | (ACCUMULATE_RESIDUAL if self.residual_layout is not None else 0)
+        return int(parts)
+
+    def accumulate_layout(self, parts=None):
+        """accumulate_layout of the pipeline's coded size"""
+        return accumulate_layout(self.info.coded_width, self.info.coded_height, self._accumulate_parts(parts))
+
+    def accumulate(self, window, slots, hops, parts=None, via_fill=0):
+        """leon_pipeline_accumulate: slots = a uint8 numpy array [S, pitch] of accumulators in host memory (accumulate_layout says where
+        the planes lie, accumulate_views takes it apart), WRITTEN IN PLACE; hops = [(target, dst_slot, fwd_slot, bwd_slot), ...]: each
+        writes slot dst_slot, the accumulator of window frame `target`, as a gather through the target's motion record from the slots
+        fwd_slot / bwd_slot (-1: not supplied) plus what the hop itself adds -- accumulate_hop states it.  Returns (via [n, mbh, mbw] uint8,
+        status [n] int32); a hop's fault is its status word, never a LeonError, and its slot and via keep what they held.  Synchronous."""
+        parts = self._accumulate_parts(parts)
+        h = _records_array(hops)
+        mbw, mbh = self.info.coded_width // 16, self.info.coded_height // 16
+        via, status = _result_arrays(len(h), ((mbh, mbw), via_fill, np.uint8), ((), 0, np.int32))
+        cfg = _accumulate_config(slots, parts)
+        _chk(self.lib.leon_pipeline_accumulate(self.h, int(window), C.byref(cfg), h.ctypes.data if len(h) else None, len(h), slots.ctypes.data, via.ctypes.data,
+                                               status.ctypes.data))
+        return via[:len(h)], status[:len(h)]
+
+    def accumulate_device(self, window, slots, hops, parts=None, via=None, status=None, stream=None):
+        """leon_pipeline_accumulate_device: the same hops with everything in DEVICE memory -- slots a contiguous CUDA uint8 tensor [S, pitch]
+        (pitch a multiple of 4 not below the layout's slot_bytes), written in place; hops a contiguous
+        CUDA int32 tensor [N, 8] -- queued on `stream` (a torch.cuda.Stream; None: torch's current stream) with
+        propagate_maps_device's ordering: NO host synchronisation.  Returns (via [N, mbh, mbw] uint8, status [N] int32) on the device
+        (the caller's, or ones the method allocates, not initialised).  Hops of one call must not name another hop's dst_slot: chain
+        the levels of propagate_plan in calls of their own."""
+        import torch
+        parts = self._accumulate_parts(parts)
+        dev = self.device_id
+        if not (isinstance(slots, torch.Tensor) and slots.is_cuda and slots.dtype == torch.uint8 and slots.dim() == 2 and slots.is_contiguous()):
+            raise ValueError("slots: a contiguous CUDA uint8 tensor [S, pitch]")
+        _device_records_check("hops", hops)
+        mbw, mbh = self.info.coded_width // 16, self.info.coded_height // 16
+        n, cells = int(hops.shape[0]), mbw * mbh
+        for name, t, dtype, count in (("slots", slots, torch.uint8, 0), ("hops", hops, torch.int32, 0), ("via", via, torch.uint8, n * cells), ("status", status, torch.int32, n)):
+            _device_tensor_check(name, t, dtype, count, dev)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        via, status = _empty_where_none(stream, dev, [(via, (max(1, n), mbh, mbw), torch.uint8), (status, max(1, n), torch.int32)])
+        S, pitch = int(slots.shape[0]), int(slots.shape[1])
+        cfg = PipelineAccumulateConfig(parts, S, (C.c_int32 * 2)(0, 0), pitch, S * pitch)
+        call = PipelineAccumulateCall(hops.data_ptr() if n else None, n, 0, slots.data_ptr(), via.data_ptr(), status.data_ptr(), self._stream_handle(stream))
+        _chk(self.lib.leon_pipeline_accumulate_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        return via.view(-1)[:n * cells].view(n, mbh, mbw), status.view(-1)[:n]
+
+    def accumulate_gop(self, window, src, parts=None, frames=None):
+        """Motion and residual accumulated from window frame `src` to every delivered frame of its GOP in the window: `src` is written
+        as a restart (a hop with both sources -1: all zero), then one accumulate_device call per level of propagate_plan on torch's
+        current stream; all levels' hop records go up in one upload from pinned memory in front of the first launch, queued like the
+        launches: nothing waits for the device.  parts: None is every part the pipeline's outputs allow.
+        Returns a dict of strided int16 CUDA views over the F frames gop_frames(window, src) lists -- AX, AY, AGE, RY [F, ch, cw], RCb, RCr
+        [F, ch / 2, cw / 2], whichever the parts hold --, "via" [F, mbh, mbw] uint8 and "status" [F] int32, with "slots" (the uint8
+        [F, slot_pitch] buffer the views lie in, as accumulate_device takes it) and "layout" (accumulate_layout's).  A frame no chain of
+        predictions reaches from `src` is all zero, via 0, status REGION_NO_REFERENCE.  frames: the window's frames when the pipeline
+        did not see them delivered."""
+        import torch
+        parts = self._accumulate_parts(parts)
+        dev = "cuda:%d" % self.device_id
+        lay = accumulate_layout(self.info.coded_width, self.info.coded_height, parts)
+        keys = self._window_keys(window, frames)
+        src = int(src)
+        group = [i for i, k in enumerate(keys) if k[0] == keys[src][0]]
+        slot = {f: i for i, f in enumerate(group)}
+        levels, unreachable = propagate_plan(self.carry_refs(window), keys, src)
+        F, mbw, mbh = len(group), lay.coded_width // 16, lay.coded_height // 16
+        slots = torch.empty((F, lay.slot_pitch), dtype=torch.uint8, device=dev)
+        for u in unreachable:
+            slots[slot[u]].zero_()
+        levels = [[(src, -1, -1)]] + levels          # the chain's start: a restart
+        flat = [(t, slot[t], slot.get(f, -1), slot.get(b, -1), 0, 0, 0, 0) for hops in levels for (t, f, b) in hops]
+        hops_dev = torch.tensor(flat, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)          # (one upload for all levels, from pinned memory: queued, not waited for)
+        rows = hops_dev[:, 1].to(torch.int64)
+        via = torch.zeros((F, mbh, mbw), dtype=torch.uint8, device=dev)
+        status = torch.zeros(F, dtype=torch.int32, device=dev)
+        if unreachable:
+            status[torch.tensor([slot[u] for u in unreachable], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)] = REGION_NO_REFERENCE
+        via_hops = torch.empty((len(flat), mbh, mbw), dtype=torch.uint8, device=dev)
+        status_hops = torch.empty(len(flat), dtype=torch.int32, device=dev)
+        first = 0
+        for hops in levels:
+            stop = first + len(hops)
+            self.accumulate_device(window, slots, hops_dev[first:stop], parts, via=via_hops[first:stop], status=status_hops[first:stop])
+            first = stop
+        via[rows] = via_hops
+        status[rows] = status_hops
+        out = {"via": via, "status": status, "slots": slots, "layout": lay}
+        flat16 = slots.view(torch.int16)          # [F, slot_pitch / 2]
+        cw, ch = lay.coded_width, lay.coded_height
+        for name in accumulate_names(parts):
+            chroma = name in ("RCb", "RCr")
+            h, w, stride = (ch // 2, cw // 2, lay.chroma_stride) if chroma else (ch, cw, lay.luma_stride)
+            off = getattr(lay, name.lower() + "_offset") // 2
+            out[name] = flat16[:, off:off + h * stride].view(F, h, stride)[:, :, :w]
+        return out
 
     def read_frame(self, frame):
         out = np.empty((self.info.frame_height, self.info.frame_width, 4), dtype=np.uint8)

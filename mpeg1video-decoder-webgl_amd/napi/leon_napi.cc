@@ -945,6 +945,60 @@ napi_value PipePropagateMaps(napi_env env, napi_callback_info info)
     return o;
 }
 
+// p.accumulate(window, hops, parts, slots) -> {slots (the array handed in, WRITTEN IN PLACE), via: Uint8Array [n][mbh][mbw] (0 restart,
+// 1 forward, 2 backward), status: Int32Array [n] (LEON_REGION_*; not 0: the hop's slot is left as it was, its via zero), layout: the
+// numbers of leon_pipeline_accumulate_layout}: leon_pipeline_accumulate (opts.motion, and opts.residual for parts & 2).  hops: an
+// Int32Array of n x [target frame index, dst slot, fwd slot, bwd slot]; slots: an Int16Array over a whole number of accumulators, each
+// the layout's slotBytes (always a multiple of 256) long, or a number: that many accumulators made here, all zero.
+napi_value PipeAccumulate(napi_env env, napi_callback_info info)
+{
+    Call<PipeHandle> a(env, info, "accumulate(window, Int32Array of [target, dst, fwd, bwd] per hop, parts, Int16Array slots or their number 1 .. 65535)");
+    size_t slen = 0, n = 0;
+    const int64_t w = a.i64(0);
+    const int32_t* b = a.rows(1, 4, &n);
+    const int32_t parts = a.i32(2);
+    napi_valuetype kind = napi_undefined;
+    napi_typeof(env, a.argv[3], &kind);
+    const int32_t fresh = kind == napi_number ? a.i32(3) : 0;          // a number: that many accumulators, made here, all zero
+    napi_value held = a.argv[3];
+    void* slots = kind == napi_number ? nullptr : a.array(3, napi_int16_array, &slen);
+    if (a.bad(kind == napi_number && !record_count((size_t)(fresh < 0 ? 0 : fresh)).ok)) return nullptr;
+    struct leon_pipeline_accumulate_layout lay;
+    int rc = leon_pipeline_accumulate_layout(a.h->info.coded_width, a.h->info.coded_height, parts, &lay);
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    if (kind == napi_number) {
+        slen = (size_t)fresh * (lay.slot_bytes / 2);
+        NAPI_OK(make_array(env, napi_int16_array, slen, &slots, &held));
+    }
+    const size_t bytes = slen * 2;
+    if (!lay.slot_bytes || bytes % lay.slot_bytes != 0 || bytes / lay.slot_bytes < 1) {
+        napi_throw_type_error(env, nullptr, "accumulate: slots is not a whole number of accumulators of the layout's slotBytes");
+        return nullptr;
+    }
+    const Count c = record_count(n);
+    std::vector<leon_pipeline_propagate_hop> hops(c.rows);
+    for (size_t i = 0; i < n && i < c.rows; i++) hops[i] = leon_pipeline_propagate_hop{b[4 * i], b[4 * i + 1], b[4 * i + 2], b[4 * i + 3], {0, 0, 0, 0}};
+    leon_pipeline_accumulate_config cfg{};
+    cfg.parts = parts;
+    cfg.n_slots = record_count(bytes / lay.slot_bytes).count;
+    cfg.slot_pitch_bytes = lay.slot_bytes; cfg.slots_bytes = bytes;
+    const size_t mbs = (size_t)(lay.coded_width / 16) * (size_t)(lay.coded_height / 16);
+    napi_value o, layout, via, status;
+    void *via_data, *status_data;
+    NAPI_OK(make_array(env, napi_uint8_array, c.rows * mbs, &via_data, &via));
+    NAPI_OK(make_array(env, napi_int32_array, c.rows, &status_data, &status));
+    rc = leon_pipeline_accumulate(a.h->p, w, &cfg, hops.data(), c.count, slots, static_cast<uint8_t*>(via_data), static_cast<int32_t*>(status_data));
+    if (rc != LEON_OK) return throw_leon(env, rc);
+    NAPI_OK(napi_create_object(env, &layout));
+    NAPI_OK(set_numbers(env, layout, {{"codedWidth", (double)lay.coded_width}, {"codedHeight", (double)lay.coded_height}, {"parts", (double)lay.parts},
+                                      {"planes", (double)lay.planes}, {"lumaStride", (double)lay.luma_stride}, {"chromaStride", (double)lay.chroma_stride},
+                                      {"axOffset", (double)lay.ax_offset}, {"ayOffset", (double)lay.ay_offset}, {"ageOffset", (double)lay.age_offset},
+                                      {"ryOffset", (double)lay.ry_offset}, {"rcbOffset", (double)lay.rcb_offset}, {"rcrOffset", (double)lay.rcr_offset},
+                                      {"slotBytes", (double)lay.slot_bytes}, {"slotPitch", (double)lay.slot_pitch}}));
+    NAPI_OK(make_object(env, {{"slots", held}, {"via", via}, {"status", status}, {"layout", layout}}, &o));
+    return o;
+}
+
 napi_value PipeStats(napi_env env, napi_callback_info info)
 {
     Call<PipeHandle> a(env, info, nullptr);
@@ -1139,6 +1193,10 @@ napi_value CreatePipeline(napi_env env, napi_callback_info info)
                                       {"readWarpRegions", PipeReadWarpRegions}, {"carryRegions", PipeCarryRegions}, {"gaugeRegions", PipeGaugeRegions},
                                       {"proposeRegions", PipeProposeRegions}, {"propagateMaps", PipePropagateMaps}, {"stats", PipeStats}, {"destroy", PipeDestroy}, {"feed", PipeFeed},
                                       {"seek", PipeSeek}}));
+    // accumulate: callable like the rest, not enumerable (as a class's methods are not): Object.keys(handle) is a list callers iterate,
+    // "every method after destroy" among them, and stays what it was
+    const napi_property_descriptor accumulate = {"accumulate", nullptr, PipeAccumulate, nullptr, nullptr, nullptr, (napi_property_attributes)(napi_writable | napi_configurable), nullptr};
+    NAPI_OK(napi_define_properties(env, obj, 1, &accumulate));
     return obj;
 }
 

@@ -36,10 +36,21 @@ beside it the same call through the host road (suppress_regions / match_regions 
 copies back -- the round trip a user had to make, with a numpy loop in place of the launch).  --match adds the worst case of the
 mutual-best rounds: ONE pair of sets of 256 and of 1024 identical boxes, a pair a round.  Both print one JSON line.
 
+--accumulate: motion and residual accumulated instead (leon_pipeline_accumulate; k_accumulate): accumulate_gop from the first GOP's I
+picture to the GOP's 12 frames for parts 1 (AX AY AGE), 2 (RY RCb RCr) and 3, from the enqueue to the synchronisation of the stream;
+one level of the plan and one hop alone (one accumulate_device call each); the bytes a hop moves from the shapes -- the source planes
+read, the target's residual record read, the destination planes written -- beside a device-to-device copy that moves as many bytes,
+measured in the same run; one hop of parts 3 against accumulate_hop on the records read back; and the road a user had before for
+that hop: three propagate_maps_device calls (AX AY AGE RY at stride 1, RCb RCr at stride 2, a coordinate map to recover the clamped
+displacement) with the elementwise torch adds around them -- no saturation, restart cells not rebased: a yardstick of time alone.  Its
+first call is k_propagate at stride 1, int16, 4 planes, timed by itself as well.  The pipeline then runs with residual=True.  --parts
+names the parts timed (under a profiler one at a time: the launches of parts 1 and 2 have the same grid).
+
   python tools/carry_bench.py [--boxes 4096] [--reps 20] [--max-box 256] [--host-boxes N] [--gauge [--gauge-check 64]]
   python tools/carry_bench.py --maps [--reps 20]
   python tools/carry_bench.py --propose [--reps 20] [--mv-min 2] [--ac-min 256] [--max-boxes 16] [--propose-check 8]
-  python tools/carry_bench.py --suppress | --match [--reps 20] [--overlap-check 2]"""
+  python tools/carry_bench.py --suppress | --match [--reps 20] [--overlap-check 2]
+  python tools/carry_bench.py --accumulate [--reps 20] [--parts 1,2,3]"""
 import argparse
 import json
 import os
@@ -273,6 +284,87 @@ def overlap_bench(a, pipe, window, frames):
     print(json.dumps({("suppress" if a.suppress else "match"): result}))
 
 
+def accumulate_bench(a, pipe, window, frames):
+    import numpy as np
+    import torch
+    import leon_ctypes as L
+    fw, fh, cw, ch = pipe.info.frame_width, pipe.info.frame_height, pipe.info.coded_width, pipe.info.coded_height
+    n = len(frames)
+    src = [i for i, f in enumerate(frames) if f["type"] == L.PIC_I][0]
+    rows = pipe.gop_frames(window, src)
+    slot = {f: i for i, f in enumerate(rows)}
+    fwd, bwd = pipe.carry_refs(window)
+    levels, unreachable = L.propagate_plan((fwd, bwd), frames, src)
+    tgt = [t for t, f, b in levels[0] if frames[t]["type"] == L.PIC_P][0]
+    luma, chroma = 2 * cw * ch, 2 * (cw // 2) * (ch // 2)
+    result = {"bench": "accumulate", "frame": [fw, fh], "coded": [cw, ch], "window_frames": n, "gop_frames": len(rows), "gop_levels": len(levels) + 1,
+              "gop_hops": sum(len(x) for x in levels) + 1, "gop_unreachable": len(unreachable), "reps": a.reps, "parts": []}
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        for parts in a.parts:
+            lay = L.accumulate_layout(cw, ch, parts)
+            got, gop = timed(torch, st, a.reps, lambda: pipe.accumulate_gop(window, src, parts))
+            if int((got["status"] != 0).sum().item()) != 0:
+                raise RuntimeError("parts %d: a hop of the GOP was refused" % parts)
+            slots = got["slots"]
+            level_hops = torch.tensor([(t, slot[t], slot.get(f, -1), slot.get(b, -1), 0, 0, 0, 0) for t, f, b in levels[0]], dtype=torch.int32, device="cuda")
+            one_hop = torch.tensor([(tgt, slot[tgt], slot[src], -1, 0, 0, 0, 0)], dtype=torch.int32, device="cuda")
+            via = torch.empty((len(levels[0]), ch // 16, cw // 16), dtype=torch.uint8, device="cuda")
+            status = torch.empty(len(levels[0]), dtype=torch.int32, device="cuda")
+            _, level = timed(torch, st, a.reps, lambda: pipe.accumulate_device(window, slots, level_hops, parts, via=via, status=status))
+            _, hop = timed(torch, st, a.reps, lambda: pipe.accumulate_device(window, slots, one_hop, parts, via=via[:1], status=status[:1]))
+            # the bytes a hop moves, from the shapes: its planes read from the source and written, T's residual record read for the residual part
+            planes = (3 * luma if parts & 1 else 0) + (luma + 2 * chroma if parts & 2 else 0)
+            per_hop = 2 * planes + (luma + 2 * chroma if parts & 2 else 0)
+            a_, b_ = torch.empty(per_hop // 2, dtype=torch.uint8, device="cuda"), torch.empty(per_hop // 2, dtype=torch.uint8, device="cuda")
+            _, copy = timed(torch, st, a.reps, lambda: b_.copy_(a_))
+            result["parts"].append({"parts": parts, "slot_bytes": lay.slot_bytes, "gop": gop, "level": dict(level, hops=len(levels[0])), "hop": hop,
+                                    "hop_bytes_moved": per_hop, "hop_gb_per_s": round(per_hop / hop["us"] / 1e3, 1), "hop_min_gb_per_s": round(per_hop / hop["min_us"] / 1e3, 1),
+                                    "level_gb_per_s": round(len(levels[0]) * per_hop / level["us"] / 1e3, 1),
+                                    "copy_of_as_many_bytes": copy, "copy_gb_per_s": round(per_hop / copy["us"] / 1e3, 1),
+                                    "hop_fraction_of_copy_rate": round(copy["us"] / hop["us"], 3)})
+        # one hop of parts 3 against the definition, on the records read back
+        lay = L.accumulate_layout(cw, ch, 3)
+        got = pipe.accumulate_gop(window, src, 3)
+        st.synchronize()
+        motion, residual = [None] * n, [None] * n
+        motion[tgt], residual[tgt] = pipe.read_motion(window, tgt)[:2], pipe.read_residual(window, tgt)
+        want = np.zeros((2, lay.slot_bytes), dtype=np.uint8)
+        acc = L.accumulate_views(want, lay)
+        if L.accumulate_hop(cw, ch, n, motion, residual, (tgt, 1, 0, -1), acc)[0] != 0 or any(not np.array_equal(acc[k][1], got[k][slot[tgt]].cpu().numpy()) for k in acc):
+            raise RuntimeError("the device and accumulate_hop disagree on the hop to frame %d" % tgt)
+        result["hop_equals_accumulate_hop"] = True
+        result["moving_macroblocks_of_the_hop"] = int((motion[tgt][0] != 0).any(axis=2).sum())
+        # the road there was for that hop: three propagate calls and the adds around them (maps lie over the FRAME)
+        mh2, mw2 = (fh + 1) // 2, (fw + 1) // 2
+        m4 = torch.zeros((2, 4, fh, fw), dtype=torch.int16, device="cuda")          # AX AY AGE RY
+        m2 = torch.zeros((2, 2, mh2, mw2), dtype=torch.int16, device="cuda")        # RCb RCr
+        yy, xx = torch.meshgrid(torch.arange(fh, device="cuda", dtype=torch.int16), torch.arange(fw, device="cuda", dtype=torch.int16), indexing="ij")
+        mc = torch.stack([torch.stack([xx, yy]), torch.zeros((2, fh, fw), dtype=torch.int16, device="cuda")])
+        hop8 = torch.tensor([(tgt, 1, 0, -1, 0, 0, 0, 0)], dtype=torch.int32, device="cuda")
+        ry, rcb, rcr = pipe.residual_view(window, tgt)
+
+        def composed():
+            pipe.propagate_maps_device(window, m4, hop8, 1)
+            pipe.propagate_maps_device(window, m2, hop8, 2)
+            pipe.propagate_maps_device(window, mc, hop8, 1)
+            m4[1, 0] += mc[1, 0] - xx
+            m4[1, 1] += mc[1, 1] - yy
+            m4[1, 2] += 1
+            m4[1, 3] += ry[:fh, :fw]
+            m2[1, 0] += rcb[:mh2, :mw2]
+            m2[1, 1] += rcr[:mh2, :mw2]
+        _, road = timed(torch, st, a.reps, composed)
+        _, prop4 = timed(torch, st, a.reps, lambda: pipe.propagate_maps_device(window, m4, hop8, 1))
+        moved4 = 2 * 4 * 2 * fh * fw          # four int16 planes read and written
+        c_, d_ = torch.empty(moved4 // 2, dtype=torch.uint8, device="cuda"), torch.empty(moved4 // 2, dtype=torch.uint8, device="cuda")
+        _, copy4 = timed(torch, st, a.reps, lambda: d_.copy_(c_))
+        result["composed_road_one_hop_parts_3"] = road
+        result["propagate_stride_1_int16_4_planes"] = dict(prop4, bytes_moved=moved4, gb_per_s=round(moved4 / prop4["us"] / 1e3, 1), copy_of_as_many_bytes=copy4,
+                                                         fraction_of_copy_rate=round(copy4["us"] / prop4["us"], 3))
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--maps", action="store_true", help="dense maps (k_propagate) instead of boxes")
@@ -286,6 +378,8 @@ def main():
     ap.add_argument("--suppress", action="store_true", help="sets of boxes pruned by overlap (k_suppress) instead of boxes carried")
     ap.add_argument("--match", action="store_true", help="pairs of sets of boxes matched by overlap (k_match) instead of boxes carried")
     ap.add_argument("--overlap-check", type=int, default=2, help="sets compared with suppress_boxes / match_boxes")
+    ap.add_argument("--accumulate", action="store_true", help="motion and residual accumulated over the GOP (k_accumulate) instead of boxes carried")
+    ap.add_argument("--parts", type=lambda v: [int(x) for x in v.split(",")], default=[1, 2, 3], help="--accumulate: the parts timed, e.g. 3 alone under a profiler")
     ap.add_argument("--boxes", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--max-box", type=int, default=256)
@@ -304,13 +398,13 @@ def main():
         held["window"], held["frames"] = window, list(frames)
         delivered.set()
         return False
-    pipe = L.Pipeline(data, on_window=on_window, motion=True, activity=a.gauge or a.propose, gops_per_window=stream_1080p.VARIED_GOPS, gpu_parser=True, parser_threads=16)
+    pipe = L.Pipeline(data, on_window=on_window, motion=True, activity=a.gauge or a.propose, residual=a.accumulate, gops_per_window=stream_1080p.VARIED_GOPS, gpu_parser=True, parser_threads=16)
     try:
         if not delivered.wait(300):
             raise RuntimeError("no window was delivered: %s" % (pipe.error,))
         window, frames = held["window"], held["frames"]
-        if a.maps or a.propose or a.suppress or a.match:
-            (maps_bench if a.maps else propose_bench if a.propose else overlap_bench)(a, pipe, window, frames)
+        if a.maps or a.propose or a.suppress or a.match or a.accumulate:
+            (maps_bench if a.maps else propose_bench if a.propose else accumulate_bench if a.accumulate else overlap_bench)(a, pipe, window, frames)
             pipe.release_window(window)
             pipe.wait()
             return
