@@ -1163,6 +1163,113 @@ int leon_pipeline_accumulate(leon_pipeline* p, int64_t window, const leon_pipeli
 int leon_pipeline_accumulate_kernel(int32_t device_id, int32_t coded_width, int32_t coded_height, int32_t n_frames, const void* const* motion_records_host,
                                     const void* const* residual_records_host, const leon_pipeline_accumulate_config* cfg,
                                     const leon_pipeline_propagate_hop* hops, int32_t n, void* slots, uint8_t* via, int32_t* status);
+/* Field tensors: boxes of the record side's int16 planes -- a motion record's vectors, a residual record's planes, the accumulators
+ * above -- resampled into one [N, C, h, w] batch of a model's element type, cropped by the same box records and through the same tables
+ * as the pixel tensors of leon_pipeline_resample_regions, on the caller's stream.  What a CoViAR-style network takes as its motion
+ * input [2, 224, 224] and residual input [3, 224, 224] beside its RGB input.
+ * Field.  A field is a plane of int16 that lies over the frame at a power-of-two cell size.  Channel c of a call is described by
+ * offset_bytes (into the item, a multiple of 2), row_stride (elements, >= 0), elem_stride (1 .. 4 elements), shift (0 .. 4) and scale,
+ * bias (float).  Its value at frame pixel (x, y), 0 <= x < frame_width, 0 <= y < frame_height, is
+ *     p_c[y][x] = item[offset_bytes / 2 + (y >> shift) * row_stride + (x >> shift) * elem_stride]
+ * -- nearest-neighbour replication of the cell, as the compressed-domain models lay a macroblock's vector over its 16 x 16 pixels:
+ *     luma-sized planes (AX, AY, AGE, RY, a residual record's Y):  shift 0, elem_stride 1, row_stride the plane's stride
+ *     chroma planes:                                               shift 1, elem_stride 1, row_stride the chroma stride
+ *     a motion record's fwd_h, fwd_v, bwd_h, bwd_v:                shift 4, elem_stride 4, row_stride 4 * mb_width, offsets 0 / 2 / 4 / 6
+ * Source.  One kind per call: LEON_FIELD_SOURCE_BUFFER (0), the caller's device memory holding n_items items (1 .. 65535) at
+ * item_pitch_bytes (a multiple of 2), of which the caller vouches for source_bytes; a record's `frame` word is the item index, and the
+ * window of the call is not consulted.  LEON_FIELD_SOURCE_MOTION (1): the window frame's motion record (needs
+ * LEON_PIPELINE_OUTPUT_MOTION).  LEON_FIELD_SOURCE_RESIDUAL (2): the window frame's residual record (needs the RESIDUAL bit).  A
+ * pipeline lacking the output is refused as the gauge family refuses.  For the two record sources the pipeline roads read neither
+ * n_items, item_pitch_bytes nor source_bytes, and the call's `source` pointer must be NULL.
+ * Records.  A record is a leon_pipeline_region as it is (frame, x, y, width, height, three reserved words), the box in frame pixels,
+ * judged by leon_pipeline_regions_check's text in its order against the FRAME size: LEON_REGION_RESERVED, _FRAME (for a BUFFER source:
+ * an item index outside n_items), _BOX, _RATIO_X, _RATIO_Y, _TAPS.  What leon_pipeline_carry_regions_device and
+ * leon_pipeline_propose_regions_device write goes in unchanged for the two record sources.  A RECORD'S FAULT IS A STATUS WORD ON BOTH
+ * ROADS, NEVER AN ERROR OF THE CALL; a refused record has not one byte of its tensor written.
+ * Resampling.  The pixel road's tables, unchanged: leon_pipeline_resize_weights(frame_size, box_start, box_size, out_size,
+ * LEON_RESIZE_TRIANGLE), 22 fractional bits, for each axis; taps may leave the box, never the frame.  Exact integers:
+ *     h[y][o]  = sat16((2^21 + sum_k Wx[o][k]  * p_c[y][first_x[o] + k]) >> 22)       horizontal first; an arithmetic shift
+ *     r[oy][o] = sat16((2^21 + sum_k Wy[oy][k] * h[first_y[oy] + k][o]) >> 22)        then vertical
+ * (the sums need more than 32 bits; an implementation may split p or use 64-bit multiply-adds as long as the result is the exact
+ * integer).  For the same box and size a field tensor is aligned sample for sample with the pixel tensor leon_pipeline_resample_regions
+ * gives.
+ * Element.  out[i][c][oy][ox] = to_dtype(u), u = fl32(fl32((float)r * scale_c) + bias_c): two separately rounded binary32 operations,
+ * no contraction, then one rounding to nearest even to fp16 / bf16 (the identity for fp32).  dtype: LEON_TENSOR_F16 / _BF16 / _F32.
+ * Layout CHW, dense, C = 1 .. LEON_FIELD_MAX_CHANNELS.  Region i lies at i * out_pitch_bytes; a pitch of 0 means C * oh * ow * element
+ * bytes rounded up to 256.
+ * Refused at the call (LEON_ERR_INVALID, nothing enqueued): a non-finite scale or bias; a channel for which
+ * fl32(fl32(32768 * |scale|) + |bias|) is not finite in the element type (so every stored element is finite); C outside 1 .. 8; shift,
+ * elem_stride, row_stride or offset_bytes outside the above; out sizes outside 1 .. 4096; another filter, dtype or source; a non-zero
+ * reserved word; misaligned pointers (records and device_status 4 bytes, source 2, device_out 256; out_pitch_bytes a multiple of 256);
+ * a channel whose last element lies outside the item -- offset_bytes + 2 * (((fh - 1) >> shift) * row_stride + ((fw - 1) >> shift) *
+ * elem_stride) + 2 above item_pitch_bytes, or for the record sources above the record's bytes --; source_bytes < n_items *
+ * item_pitch_bytes.  No load falls outside the source, no store outside a valid region's tensor bytes.
+ * One text for host and device: csrc/leon_fields.h.  Per chunk of regions k_box_tables (as leon_pipeline_resample_regions_device runs
+ * it, the tables in the pipeline's bounded regions scratch) and k_fields.
+ * NOT in this definition: bicubic; uint8 elements and HWC; letterbox fit; converting a YCbCr residual to RGB differences; rescaling
+ * vectors by the resize ratio -- vectors are in half-pel FRAME units, and scale = 0.5 * out_size / box_size makes them output pixels. */
+#define LEON_FIELD_SOURCE_BUFFER   0
+#define LEON_FIELD_SOURCE_MOTION   1
+#define LEON_FIELD_SOURCE_RESIDUAL 2
+#define LEON_FIELD_MAX_CHANNELS    8
+typedef struct leon_pipeline_field_channel {
+    uint32_t offset_bytes;         /* into the item, a multiple of 2 */
+    int32_t  row_stride;           /* elements, >= 0 */
+    int32_t  elem_stride;          /* 1 .. 4 elements */
+    int32_t  shift;                /* 0 .. 4: the cell is 1 << shift frame pixels */
+    float    scale, bias;
+    int32_t  reserved[2];          /* must be 0 */
+} leon_pipeline_field_channel;     /* 32 bytes */
+typedef struct leon_pipeline_field_config {
+    int32_t  source;               /* LEON_FIELD_SOURCE_* */
+    int32_t  dtype;                /* LEON_TENSOR_F16 / _BF16 / _F32 */
+    int32_t  channels;             /* 1 .. LEON_FIELD_MAX_CHANNELS */
+    int32_t  filter;               /* LEON_RESIZE_TRIANGLE */
+    int32_t  out_width, out_height;/* 1 .. 4096 */
+    int32_t  n_items;              /* 1 .. 65535 */
+    int32_t  reserved;             /* must be 0 */
+    uint64_t item_pitch_bytes;     /* a multiple of 2 */
+    uint64_t source_bytes;         /* at least n_items * item_pitch_bytes */
+    leon_pipeline_field_channel channel[LEON_FIELD_MAX_CHANNELS];
+} leon_pipeline_field_config;      /* 304 bytes */
+typedef struct leon_pipeline_field_tensors_call {
+    const leon_pipeline_region* records;   /* DEVICE memory, n records, 4-byte aligned */
+    int32_t  n;                            /* 1 .. 65535 */
+    int32_t  reserved0;                    /* must be 0 */
+    const void* source;                    /* DEVICE memory, cfg->source_bytes bytes, 2-byte aligned; NULL for the record sources */
+    void*    device_out;                   /* DEVICE memory, 256-byte aligned, (n - 1) * pitch + a region's bytes */
+    uint64_t out_pitch_bytes;              /* 0, or a multiple of 256 not below a region's bytes */
+    int32_t* device_status;                /* DEVICE memory, n words, 4-byte aligned, may be NULL */
+    void*    stream;                       /* hipStream_t of the caller's; NULL: the pipeline's regions stream, and the call waits */
+    uint64_t reserved;                     /* must be 0 */
+} leon_pipeline_field_tensors_call;        /* 64 bytes */
+/* host only: the definition on the CPU (the text the kernel compiles too) for one record, everything in host memory.  items: n_items
+ * items at item_pitch_bytes, for every source -- a record source's items are records laid out as leon_pipeline_motion_layout(
+ * coded_width / 16, coded_height / 16) or leon_pipeline_residual_layout(coded_width, coded_height) say, at an item_pitch_bytes not
+ * below the record's bytes, which are then the channels' limit.  out: the record's dense tensor, C * oh * ow elements, aligned to its
+ * element.  Returns the record's status word (>= 0; the tensor is written exactly when it is 0), or LEON_ERR_INVALID (negative) for a
+ * null argument, a frame size outside 1 .. 4096, a coded size the record's layout refuses, or a cfg the device road refuses. */
+int32_t leon_pipeline_field_tensor_record(int32_t frame_width, int32_t frame_height, int32_t coded_width, int32_t coded_height,
+                                          const leon_pipeline_field_config* cfg, const void* items, const leon_pipeline_region* record, void* out);
+/* Everything in DEVICE memory: the call ONLY ENQUEUES on the caller's stream (stream NULL: the regions stream, and the call waits),
+ * with leon_pipeline_resample_regions_device's ordering rules and scratch; the window's records are reached through the table the
+ * carry, gauge and propagate calls read them through.  Refused (LEON_ERR_INVALID, nothing enqueued): the list above, a null cfg or
+ * call, a pipeline without the source's output, a window (record sources) that is not out for delivery or was delivered with an
+ * error, n outside 1 .. 65535, a null records or device_out, a null source with LEON_FIELD_SOURCE_BUFFER and a non-null one without. */
+int leon_pipeline_field_tensors_device(leon_pipeline* p, int64_t window, const leon_pipeline_field_config* cfg, const leon_pipeline_field_tensors_call* call);
+/* Records, source (BUFFER only; NULL otherwise), tensors and status in host memory, synchronous: the device road between an upload and
+ * the copies back.  out (n regions out_pitch_bytes apart; 0: the default pitch) and status (n words, may be NULL) go up and come back
+ * whole, so bytes the kernel leaves alone -- a refused record's tensor, the gap behind a tensor -- stay the caller's. */
+int leon_pipeline_field_tensors(leon_pipeline* p, int64_t window, const leon_pipeline_field_config* cfg, const leon_pipeline_region* records, int32_t n,
+                                const void* source, void* out, uint64_t out_pitch_bytes, int32_t* status);
+/* A diagnostic in the manner of leon_pipeline_accumulate_kernel: k_box_tables and k_fields on items the CALLER supplies (host memory,
+ * as leon_pipeline_field_tensor_record takes them), with explicit frame and coded sizes and no pipeline, memory of its own on
+ * device_id's null stream, synchronous; records, out and status (may be NULL) in host memory, going up and coming back whole.
+ * scratch_limit_bytes: the bytes of table scratch a chunk of regions may take (0: 256 MiB), so that a test can make a call of
+ * several chunks.  Refused: what leon_pipeline_field_tensor_record refuses, n outside 1 .. 65535, a limit below one region's tables. */
+int leon_pipeline_field_tensors_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t coded_width, int32_t coded_height,
+                                       const leon_pipeline_field_config* cfg, const void* items, const leon_pipeline_region* records, int32_t n, void* out,
+                                       uint64_t out_pitch_bytes, int32_t* status, uint64_t scratch_limit_bytes);
 /* Boxes gauged: what a frame's motion record (LEON_PIPELINE_OUTPUT_MOTION) and activity record (LEON_PIPELINE_OUTPUT_ACTIVITY) say
  * under each box, on the device -- what a "run the detector again here" gate reads of a box that the carry family moved.  Integers only.
  * Records.  A record is a leon_pipeline_region (frame, the box, three reserved words that must be 0): exactly what

@@ -45,6 +45,7 @@
 #include "leon_carry.h"
 #include "leon_propagate.h"
 #include "leon_accumulate.h"
+#include "leon_fields.h"
 #include "leon_gauge.h"
 #include "leon_propose.h"
 #include "leon_overlap.h"
@@ -3389,6 +3390,50 @@ __global__ __launch_bounds__(kRgbaBlock) void k_accumulate(const PropagateHop* _
     uint8_t* v = via && q == 0 ? via + (size_t)i * (size_t)c.g.mbw * (size_t)(c.g.ch >> 4) : nullptr;
     accumulate_unit(c.g, motion + (size_t)ring * c.motion_pitch, c.info_offset, residual ? residual + (size_t)ring * c.residual_pitch : nullptr, slots, c.slots_bytes,
                     c.slot_pitch, h, v, q, u);
+}
+
+// ---- fields: boxes of int16 fields -- motion vectors, residual planes, accumulators -- as a model's tensors (include/leon_pipeline.h,
+// leon_pipeline_field_tensors) ----
+// k_regions' shape behind k_box_tables: blockIdx.z the region of the chunk, blockIdx.x / y the 32 x 8 tiles of the out size.  A workgroup
+// reads the region's descriptor (one address per workgroup: scalar loads) and leaves at once on a non-zero status; otherwise it takes
+// the tile's rows of the region's tables into LDS once and then, per channel, runs leon_fields.h's three steps: the horizontal pass of
+// the frame rows the tile's vertical taps need, gathered from the field's cells (2-byte loads; lanes of neighbouring columns read
+// neighbouring or the same cells) with 64-bit multiply-adds, into LDS as int16; the vertical pass from LDS, a lane per output sample,
+// whose element goes into the packed tile at its row's place in its 16-byte line; and the rows out in whole 16-byte lines, the lines
+// at a row's ends element by element.  The item of a region is src + frame_id * item_pitch: a record of the ring through the window's
+// table, or an item of the caller's buffer through an identity table.  Static LDS 16992 bytes, no scratch.  DTYPE: LEON_TENSOR_F16 /
+// _BF16 / _F32.
+struct FieldCall {
+    FieldChannel ch[kFieldMaxChannels];
+    int32_t fw, fh, ow, oh;
+    int32_t channels, reserved;
+    size_t item_pitch;
+};
+template <int DTYPE>
+__global__ __launch_bounds__(kRgbaBlock) void k_fields(const uint8_t* __restrict__ src, uint8_t* __restrict__ out, const RegionDesc* __restrict__ descs,
+                                                       const int32_t* __restrict__ tabs, FieldCall c)
+{
+    static_assert(kFieldLanes == kRgbaBlock, "a lane per sample of the tile");
+    __shared__ FieldTile t;
+    const RegionDesc& d = descs[blockIdx.z];
+    if (d.status != kRegionOk) return;   // a refused region stores nothing anywhere
+    const int32_t* rt = tabs + d.rt_base;
+    const FieldTables T{rt, rt + d.off_cx, rt + d.off_wx, rt + d.off_fy, rt + d.off_cy, rt + d.off_wy, d.taps_x, d.taps_y};
+    const FieldTileAt a = field_tile_at(c.ow, c.oh, (int32_t)blockIdx.x, (int32_t)blockIdx.y);
+    const int32_t tid = (int32_t)threadIdx.x;
+    const uint8_t* item = src + (size_t)d.frame_id * c.item_pitch;
+    uint8_t* dst = out + join64(d.dst_lo, d.dst_hi);
+    field_step_tables(t, T, a, tid);
+    __syncthreads();
+    int32_t ry0, rows;
+    field_tile_rows(t, a, &ry0, &rows);
+    for (int32_t q = 0; q < c.channels; q++) {
+        field_step_h(t, item, c.ch[q], a, ry0, rows, tid);
+        __syncthreads();
+        field_step_v(t, c.ch[q], a, c.ow, c.oh, q, DTYPE, ry0, rows, tid);
+        __syncthreads();          // (the next channel's horizontal pass stands between this store and the next write of the packed tile)
+        field_step_store(t, dst, a, c.ow, c.oh, q, DTYPE, tid);
+    }
 }
 
 // ---- gauge: the statistics of a frame's motion and activity records under a box (include/leon_pipeline.h, leon_pipeline_gauge_regions) --

@@ -3472,6 +3472,285 @@ int accumulate_kernel(int32_t device_id, int32_t cw, int32_t ch, int32_t n_frame
     });
 }
 
+// ---- boxes of int16 fields as a model's tensors (leon_pipeline_field_tensors) ---------------------------------------------------------
+static_assert(sizeof(leon_pipeline_field_channel) == 32 && sizeof(leon_pipeline_field_config) == 304 && sizeof(leon_pipeline_field_tensors_call) == 64 &&
+              sizeof(leon::FieldChannel) == sizeof(leon_pipeline_field_channel), "include/leon_pipeline.h states the sizes");
+static_assert(leon::kFieldSourceBuffer == LEON_FIELD_SOURCE_BUFFER && leon::kFieldSourceMotion == LEON_FIELD_SOURCE_MOTION && leon::kFieldSourceResidual == LEON_FIELD_SOURCE_RESIDUAL &&
+              leon::kFieldF16 == LEON_TENSOR_F16 && leon::kFieldBF16 == LEON_TENSOR_BF16 && leon::kFieldF32 == LEON_TENSOR_F32 && leon::kFieldMaxChannels == LEON_FIELD_MAX_CHANNELS,
+              "the kernel's codes are the header's");
+static_assert(sizeof(leon::FieldTile) <= 65536, "k_fields' static LDS");
+typedef void (*FieldsKernel)(const uint8_t*, uint8_t*, const leon::RegionDesc*, const int32_t*, leon::FieldCall);
+constexpr FieldsKernel kFieldsKernels[3] = {leon::k_fields<LEON_TENSOR_F16>, leon::k_fields<LEON_TENSOR_BF16>, leon::k_fields<LEON_TENSOR_F32>};
+
+int field_source_check(const leon_pipeline_field_config* cfg)
+{
+    if (!cfg) return fail(LEON_ERR_INVALID, "field tensors: null cfg");
+    if (cfg->source < LEON_FIELD_SOURCE_BUFFER || cfg->source > LEON_FIELD_SOURCE_RESIDUAL)
+        return fail(LEON_ERR_INVALID, "field tensors: source %d (LEON_FIELD_SOURCE_BUFFER, _MOTION, _RESIDUAL: 0 .. 2)", cfg->source);
+    return LEON_OK;
+}
+// What a call's config can be refused for.  limit: the bytes of an item its channels must lie in, 0: item_pitch_bytes; items: whether
+// the item geometry is the caller's (a BUFFER source, and every source of the CPU road and the diagnostic)
+int field_config_check(int32_t fw, int32_t fh, const leon_pipeline_field_config* cfg, uint64_t limit, bool items)
+{
+    if (const int rc = field_source_check(cfg); rc != LEON_OK) return rc;
+    if (cfg->reserved) return fail(LEON_ERR_INVALID, "field tensors: the reserved word of cfg is not 0");
+    if (cfg->dtype != LEON_TENSOR_F16 && cfg->dtype != LEON_TENSOR_BF16 && cfg->dtype != LEON_TENSOR_F32)
+        return fail(LEON_ERR_INVALID, "field tensors: dtype %d (LEON_TENSOR_F16, _BF16, _F32)", cfg->dtype);
+    if (cfg->filter != LEON_RESIZE_TRIANGLE) return fail(LEON_ERR_INVALID, "field tensors: filter %d (LEON_RESIZE_TRIANGLE is the filter)", cfg->filter);
+    if (cfg->channels < 1 || cfg->channels > LEON_FIELD_MAX_CHANNELS) return fail(LEON_ERR_INVALID, "field tensors: %d channels (1 .. %d)", cfg->channels, LEON_FIELD_MAX_CHANNELS);
+    if (cfg->out_width < 1 || cfg->out_width > 4096) return fail(LEON_ERR_INVALID, "field tensors: out_width %d is outside 1 .. 4096", cfg->out_width);
+    if (cfg->out_height < 1 || cfg->out_height > 4096) return fail(LEON_ERR_INVALID, "field tensors: out_height %d is outside 1 .. 4096", cfg->out_height);
+    if (fw < 1 || fw > 4096 || fh < 1 || fh > 4096) return fail(LEON_ERR_INVALID, "field tensors: a frame of %d x %d (1 .. 4096 each)", fw, fh);
+    if (items) {
+        if (cfg->n_items < 1 || cfg->n_items > 65535) return fail(LEON_ERR_INVALID, "field tensors: %d items (1 .. 65535)", cfg->n_items);
+        if (cfg->item_pitch_bytes & 1u) return fail(LEON_ERR_INVALID, "field tensors: item_pitch_bytes %llu is not a multiple of 2", (unsigned long long)cfg->item_pitch_bytes);
+        if (limit > cfg->item_pitch_bytes)
+            return fail(LEON_ERR_INVALID, "field tensors: item_pitch_bytes %llu is below the record's %llu bytes", (unsigned long long)cfg->item_pitch_bytes, (unsigned long long)limit);
+        if (cfg->source_bytes / (uint64_t)cfg->n_items < cfg->item_pitch_bytes)
+            return fail(LEON_ERR_INVALID, "field tensors: source_bytes %llu is below %d items of %llu bytes", (unsigned long long)cfg->source_bytes, cfg->n_items,
+                        (unsigned long long)cfg->item_pitch_bytes);
+        if (!limit) limit = cfg->item_pitch_bytes;
+    }
+    for (int32_t q = 0; q < cfg->channels; q++) {
+        const leon::FieldChannel& c = reinterpret_cast<const leon::FieldChannel&>(cfg->channel[q]);
+        switch (leon::field_channel_judge(c, fw, fh, cfg->dtype, limit)) {
+        case leon::kFieldOk: break;
+        case leon::kFieldBadReserved: return fail(LEON_ERR_INVALID, "field tensors: channel %d: a reserved word is not 0", q);
+        case leon::kFieldBadShift: return fail(LEON_ERR_INVALID, "field tensors: channel %d: shift %d (0 .. %d)", q, c.shift, leon::kFieldMaxShift);
+        case leon::kFieldBadElemStride: return fail(LEON_ERR_INVALID, "field tensors: channel %d: elem_stride %d (1 .. %d)", q, c.elem_stride, leon::kFieldMaxElemStride);
+        case leon::kFieldBadRowStride: return fail(LEON_ERR_INVALID, "field tensors: channel %d: row_stride %d is negative", q, c.row_stride);
+        case leon::kFieldBadOffset: return fail(LEON_ERR_INVALID, "field tensors: channel %d: offset_bytes %u is not a multiple of 2", q, c.offset_bytes);
+        case leon::kFieldBadScale: return fail(LEON_ERR_INVALID, "field tensors: channel %d: scale %g, bias %g: not finite", q, (double)c.scale, (double)c.bias);
+        case leon::kFieldBadRange:
+            return fail(LEON_ERR_INVALID, "field tensors: channel %d: scale %g, bias %g: 32768 * |scale| + |bias| is not finite in the element type", q, (double)c.scale, (double)c.bias);
+        default:
+            return fail(LEON_ERR_INVALID, "field tensors: channel %d: its last element ends at byte %llu of an item of %llu bytes", q,
+                        (unsigned long long)leon::field_channel_end(c, fw, fh), (unsigned long long)limit);
+        }
+    }
+    return LEON_OK;
+}
+inline size_t field_region_bytes(const leon_pipeline_field_config& cfg)
+{
+    return (size_t)cfg.channels * (size_t)cfg.out_height * (size_t)cfg.out_width * (size_t)leon::field_elem_bytes(cfg.dtype);
+}
+// the bytes of a record source's record over a coded picture (0: a BUFFER source), for the roads with explicit sizes
+int field_record_bytes(const leon_pipeline_field_config* cfg, int32_t cw, int32_t ch, uint64_t* bytes)
+{
+    if (const int rc = field_source_check(cfg); rc != LEON_OK) return rc;
+    *bytes = 0;
+    if (cfg->source == LEON_FIELD_SOURCE_BUFFER) return LEON_OK;
+    if (const int rc = residual_size_check("field tensors", cw, ch); rc != LEON_OK) return rc;
+    *bytes = cfg->source == LEON_FIELD_SOURCE_MOTION ? leon::motion_layout((uint32_t)cw / 16u, (uint32_t)ch / 16u).record_bytes : leon::residual_layout((uint32_t)cw, (uint32_t)ch).record_bytes;
+    return LEON_OK;
+}
+
+// regions a chunk and the scratch behind the table: as many as fit the limit (and 32 bits of table words, which rt_base counts)
+struct FieldsPlan {
+    size_t slot_words, chunk, desc_bytes, tabs_bytes;
+};
+int fields_plan(const leon_pipeline_field_config& cfg, int32_t n, uint64_t limit, FieldsPlan* P)
+{
+    P->slot_words = boxes_slot_words(cfg.out_width, cfg.out_height, LEON_RESIZE_TRIANGLE);
+    const size_t per_region = P->slot_words * 4 + sizeof(leon::RegionDesc);
+    if (!limit) limit = LEON_REGIONS_SCRATCH_DEFAULT;
+    if (limit < per_region) return fail(LEON_ERR_INVALID, "field tensors: scratch_limit_bytes %llu is below one region's %zu bytes", (unsigned long long)limit, per_region);
+    P->chunk = (size_t)std::min<uint64_t>({(uint64_t)n, limit / per_region, (((uint64_t)1 << 32) - 1) / P->slot_words});
+    P->desc_bytes = pad256(P->chunk * sizeof(leon::RegionDesc));
+    P->tabs_bytes = P->chunk * P->slot_words * 4;
+    return LEON_OK;
+}
+// the launches every device road shares: per chunk k_box_tables, which judges the records and builds their tables, and k_fields behind
+// the descriptors' status words; none behind a chunk whose launch failed
+void fields_launch(hipStream_t st, const leon_pipeline_field_config& cfg, int32_t fw, int32_t fh, int32_t n_frames, const leon::BoxRecord* boxes, int32_t n, const uint32_t* d_ids,
+                   leon::RegionDesc* d_descs, int32_t* d_tabs, const FieldsPlan& P, const uint8_t* src, size_t item_pitch, uint8_t* out, uint64_t pitch, int32_t* d_status)
+{
+    const int32_t ow = cfg.out_width, oh = cfg.out_height;
+    leon::BoxCall B{};
+    B.fw = fw; B.fh = fh; B.ow = ow; B.oh = oh;
+    B.n_frames = n_frames; B.cubic = 0;
+    B.slot_words = (uint32_t)P.slot_words;
+    B.pitch_lo = (uint32_t)(pitch & 0xffffffffu); B.pitch_hi = (uint32_t)(pitch >> 32);
+    leon::FieldCall F{};
+    for (int32_t q = 0; q < cfg.channels; q++) F.ch[q] = reinterpret_cast<const leon::FieldChannel&>(cfg.channel[q]);
+    F.fw = fw; F.fh = fh; F.ow = ow; F.oh = oh;
+    F.channels = cfg.channels;
+    F.item_pitch = item_pitch;
+    const FieldsKernel k = kFieldsKernels[cfg.dtype - LEON_TENSOR_F16];
+    for (size_t first = 0; first < (size_t)n; first += P.chunk) {
+        const unsigned m = (unsigned)std::min(P.chunk, (size_t)n - first);          // (blockIdx.z: m <= n <= 65535; at most 512 tile rows)
+        B.first = (uint32_t)first;
+        hipLaunchKernelGGL(leon::k_box_tables, dim3(m), dim3(leon::kRgbaBlock), 0, st, boxes + first, d_ids, d_descs, d_tabs, d_status ? d_status + first : nullptr, B);
+        const dim3 grid((unsigned)((ow + leon::kFieldTileX - 1) / leon::kFieldTileX), (unsigned)((oh + leon::kFieldTileY - 1) / leon::kFieldTileY), m);
+        hipLaunchKernelGGL(k, grid, dim3(leon::kRgbaBlock), 0, st, src, out, (const leon::RegionDesc*)d_descs, (const int32_t*)d_tabs, F);
+        if (hipPeekAtLastError() != hipSuccess) break;
+    }
+}
+
+int field_outputs_check(const leon_pipeline* p, int32_t source)
+{
+    if (source == LEON_FIELD_SOURCE_MOTION && !p->motion.ring) return no_output("motion", "MOTION");
+    if (source == LEON_FIELD_SOURCE_RESIDUAL && !p->residual.ring) return no_output("residual", "RESIDUAL");
+    return LEON_OK;
+}
+// the caller's pointers of a device call; *pitch as regions_out_check's
+int field_call_check(const leon_pipeline_field_config* cfg, const leon_pipeline_field_tensors_call* c, uint64_t* pitch)
+{
+    if (const int rc = boxes_call_check("field tensors", c->records, false, c->device_status, c->device_out, c->out_pitch_bytes, field_region_bytes(*cfg), pitch); rc != LEON_OK) return rc;
+    if (cfg->source == LEON_FIELD_SOURCE_BUFFER) {
+        if (!c->source) return fail(LEON_ERR_INVALID, "field tensors: null source with LEON_FIELD_SOURCE_BUFFER");
+        if ((uintptr_t)c->source & 1u) return fail(LEON_ERR_INVALID, "field tensors: source %p is not 2-byte aligned", c->source);
+    } else if (c->source) return fail(LEON_ERR_INVALID, "field tensors: a source pointer with a record source (the window's records are the source)");
+    return LEON_OK;
+}
+
+// One call of the device road: the host's refusals (the source's and the output's before the window's, as gauge's), then inside the boxes
+// bracket the chunks' launches.  The scratch: [the table of item ids | a chunk's descriptors | its tables] -- the ids the ring slots of
+// the window's records, taken from the table the carry family reads them through, or an identity for the caller's buffer.
+int field_tensors_device(leon_pipeline* p, int64_t window, const leon_pipeline_field_config* cfg, const leon_pipeline_field_tensors_call* c)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = field_source_check(cfg);
+    if (rc != LEON_OK || (rc = field_outputs_check(p, cfg->source)) != LEON_OK) return rc;
+    if (!c) return fail(LEON_ERR_INVALID, "null argument");
+    const bool buffer = cfg->source == LEON_FIELD_SOURCE_BUFFER, motion = cfg->source == LEON_FIELD_SOURCE_MOTION;
+    std::unique_lock<std::mutex> call(p->regions_mu);
+    std::vector<uint32_t> ids;
+    if (!buffer) {
+        // the ring slots of the window's records: the first word of the rows of the table the carry, gauge and propagate calls read (a
+        // CarryFrame: ring, fwd, bwd, a spare word); a pipeline with the RESIDUAL output alone has no such table, and the slots are the
+        // ones its residual descriptors name -- the rings share the index
+        rc = window_delivered(p, window, [&](const PipeWindow& w) {
+            if (!w.carry_table.empty())
+                for (size_t i = 0; i + 3 < w.carry_table.size(); i += 4) ids.push_back(w.carry_table[i]);
+            else
+                for (const leon::ResidualDesc& d : w.residual_descs) ids.push_back(d.frame);
+        });
+        if (rc != LEON_OK) return rc;
+    }
+    if (c->reserved0 || c->reserved) return fail(LEON_ERR_INVALID, "field tensors: a reserved word of the call is not 0");
+    if ((rc = record_count_check("field tensors", "records", c->n)) != LEON_OK) return rc;
+    const int32_t fw = p->vinfo.frame_width, fh = p->vinfo.frame_height;
+    const uint64_t record_bytes = buffer ? 0 : motion ? p->motion_lay.record_bytes : p->residual_lay.record_bytes;
+    if ((rc = field_config_check(fw, fh, cfg, record_bytes, buffer)) != LEON_OK) return rc;
+    uint64_t pitch;
+    if ((rc = field_call_check(cfg, c, &pitch)) != LEON_OK) return rc;
+    if (buffer)
+        for (int32_t i = 0; i < cfg->n_items; i++) ids.push_back((uint32_t)i);
+    FieldsPlan P;
+    if ((rc = fields_plan(*cfg, c->n, 0, &P)) != LEON_OK) return rc;
+    const uint8_t* src = buffer ? static_cast<const uint8_t*>(c->source) : motion ? (const uint8_t*)p->motion.ring : (const uint8_t*)p->residual.ring;
+    const size_t item_pitch = buffer ? (size_t)cfg->item_pitch_bytes : motion ? p->motion_lay.record_pitch : p->residual_lay.record_pitch;
+    const size_t ids_bytes = pad256(std::max<size_t>(ids.size(), 1) * 4);
+    return boxes_run(p, c->stream, call, ids, ids_bytes + P.desc_bytes + P.tabs_bytes, [&](hipStream_t st, uint32_t* d_ids) {
+        fields_launch(st, *cfg, fw, fh, (int32_t)ids.size(), reinterpret_cast<const leon::BoxRecord*>(c->records), c->n, d_ids,
+                      reinterpret_cast<leon::RegionDesc*>(p->boxes_dev + ids_bytes), reinterpret_cast<int32_t*>(p->boxes_dev + ids_bytes + P.desc_bytes), P, src, item_pitch,
+                      static_cast<uint8_t*>(c->device_out), pitch, c->device_status);
+    });
+}
+
+// One call of the host road: [records | source | tensors | status], the tensors and status going up first so that what the kernel leaves
+// alone comes back as it was
+int field_tensors(leon_pipeline* p, int64_t window, const leon_pipeline_field_config* cfg, const leon_pipeline_region* records, int32_t n, const void* source, void* out,
+                  uint64_t out_pitch, int32_t* status)
+{
+    if (!p) return fail(LEON_ERR_INVALID, "null pipeline");
+    int rc = field_source_check(cfg);
+    if (rc != LEON_OK || (rc = field_outputs_check(p, cfg->source)) != LEON_OK) return rc;
+    if (!records || !out) return fail(LEON_ERR_INVALID, "field tensors: null %s", records ? "out" : "records");
+    const bool buffer = cfg->source == LEON_FIELD_SOURCE_BUFFER, motion = cfg->source == LEON_FIELD_SOURCE_MOTION;
+    if (buffer != (source != nullptr)) return fail(LEON_ERR_INVALID, "field tensors: %s", buffer ? "null source with LEON_FIELD_SOURCE_BUFFER" : "a source pointer with a record source");
+    if ((rc = record_count_check("field tensors", "records", n)) != LEON_OK) return rc;
+    const uint64_t record_bytes = buffer ? 0 : motion ? p->motion_lay.record_bytes : p->residual_lay.record_bytes;
+    if ((rc = field_config_check(p->vinfo.frame_width, p->vinfo.frame_height, cfg, record_bytes, buffer)) != LEON_OK) return rc;
+    const size_t region_bytes = field_region_bytes(*cfg);
+    if (out_pitch && (out_pitch % 256 || out_pitch < region_bytes))
+        return fail(LEON_ERR_INVALID, "field tensors: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", (unsigned long long)out_pitch, region_bytes);
+    const size_t pitch = out_pitch ? (size_t)out_pitch : pad256(region_bytes);
+    const auto device = [&](const Pieces& s) {
+        leon_pipeline_field_tensors_call c{};
+        c.records = s.at<const leon_pipeline_region>(0);
+        c.n = n;
+        c.source = buffer ? s.at(1) : nullptr;
+        c.device_out = s.at(2);
+        c.out_pitch_bytes = pitch;
+        c.device_status = status ? s.at<int32_t>(3) : nullptr;
+        return field_tensors_device(p, window, cfg, &c);
+    };
+    const std::initializer_list<Piece> pieces = {{records, nullptr, (size_t)n * 32}, {source, nullptr, buffer ? (size_t)cfg->source_bytes : 0}, {out, out, (size_t)n * pitch},
+                                                 {status, status, (size_t)n * 4}};
+    if (buffer) return pieces_run(p->cfg.device_id, "field tensors", pieces, device);
+    return table_host_road(p, window, "field tensors", pieces, device);
+}
+
+// what the CPU road and the diagnostic refuse alike: the sizes, the config with the caller's item geometry, the pointers
+int field_host_check(int32_t fw, int32_t fh, int32_t cw, int32_t ch, const leon_pipeline_field_config* cfg, const void* items, const void* records, const void* out)
+{
+    if (!cfg || !items || !records || !out) return fail(LEON_ERR_INVALID, "null argument");
+    uint64_t record_bytes;
+    int rc = field_record_bytes(cfg, cw, ch, &record_bytes);
+    if (rc != LEON_OK || (rc = field_config_check(fw, fh, cfg, record_bytes, true)) != LEON_OK) return rc;
+    if ((uintptr_t)items & 1u) return fail(LEON_ERR_INVALID, "field tensors: items %p is not 2-byte aligned", items);
+    if ((uintptr_t)records & 3u) return fail(LEON_ERR_INVALID, "field tensors: records %p is not 4-byte aligned", records);
+    return LEON_OK;
+}
+
+// the definition on the CPU: the record judged by the regions' own function, the tables by the pixel road's builder, then the plain loop
+// over every sample of every channel (leon_fields.h); the status word, or a negative error
+int32_t field_tensor_record_host(int32_t fw, int32_t fh, int32_t cw, int32_t ch, const leon_pipeline_field_config* cfg, const void* items, const leon_pipeline_region* record,
+                                 void* out)
+{
+    int rc = field_host_check(fw, fh, cw, ch, cfg, items, record, out);
+    if (rc != LEON_OK) return rc;
+    const int32_t eb = leon::field_elem_bytes(cfg->dtype), ow = cfg->out_width, oh = cfg->out_height;
+    if ((uintptr_t)out & (uintptr_t)(eb - 1)) return fail(LEON_ERR_INVALID, "field tensors: out %p is not aligned to its %d-byte elements", out, eb);
+    leon_pipeline_regions_config rcfg{};
+    rcfg.out_width = ow; rcfg.out_height = oh; rcfg.filter = LEON_RESIZE_TRIANGLE;
+    const int32_t st = region_status(fw, fh, cfg->n_items, *record, rcfg, RegionsFit{});
+    if (st != LEON_REGION_OK) return st;
+    const int32_t taps = LEON_RESIZE_MAX_TAPS;
+    std::vector<int32_t> t((size_t)(ow + oh) * (size_t)(2 + taps));
+    int32_t* tx = t.data();
+    int32_t* ty = tx + (size_t)ow * (size_t)(2 + taps);
+    if ((rc = resize_axis_build("width", fw, record->x, record->width, ow, LEON_RESIZE_TRIANGLE, tx, tx + ow, tx + 2 * ow, taps, nullptr)) != LEON_OK) return rc;
+    if ((rc = resize_axis_build("height", fh, record->y, record->height, oh, LEON_RESIZE_TRIANGLE, ty, ty + oh, ty + 2 * oh, taps, nullptr)) != LEON_OK) return rc;
+    const leon::FieldTables T{tx, tx + ow, tx + 2 * ow, ty, ty + oh, ty + 2 * oh, taps, taps};
+    const uint8_t* item = static_cast<const uint8_t*>(items) + (size_t)record->frame * (size_t)cfg->item_pitch_bytes;
+    uint8_t* o = static_cast<uint8_t*>(out);
+    for (int32_t q = 0; q < cfg->channels; q++) {
+        const leon::FieldChannel& c = reinterpret_cast<const leon::FieldChannel&>(cfg->channel[q]);
+        for (int32_t oy = 0; oy < oh; oy++)
+            for (int32_t ox = 0; ox < ow; ox++)
+                leon::field_store_elem(o + (((size_t)q * oh + oy) * ow + ox) * eb, leon::field_elem(leon::field_value(leon::field_sample(item, c, T, ox, oy), c.scale, c.bias), cfg->dtype), eb);
+    }
+    return LEON_REGION_OK;
+}
+
+// k_box_tables and k_fields on items the caller supplies (leon_pipeline_field_tensors_kernel): memory of its own, the null stream, an
+// identity table of item ids
+int field_tensors_kernel(int32_t device_id, int32_t fw, int32_t fh, int32_t cw, int32_t ch, const leon_pipeline_field_config* cfg, const void* items,
+                         const leon_pipeline_region* records, int32_t n, void* out, uint64_t out_pitch, int32_t* status, uint64_t scratch_limit)
+{
+    int rc = field_host_check(fw, fh, cw, ch, cfg, items, records, out);
+    if (rc != LEON_OK || (rc = record_count_check("field tensors", "records", n)) != LEON_OK) return rc;
+    const size_t region_bytes = field_region_bytes(*cfg);
+    if (out_pitch && (out_pitch % 256 || out_pitch < region_bytes))
+        return fail(LEON_ERR_INVALID, "field tensors: out_pitch_bytes %llu (0, or a multiple of 256 not below the region's %zu bytes)", (unsigned long long)out_pitch, region_bytes);
+    const size_t pitch = out_pitch ? (size_t)out_pitch : pad256(region_bytes);
+    FieldsPlan P;
+    if ((rc = fields_plan(*cfg, n, scratch_limit, &P)) != LEON_OK) return rc;
+    std::vector<uint32_t> ids((size_t)cfg->n_items);
+    for (size_t i = 0; i < ids.size(); i++) ids[i] = (uint32_t)i;
+    return pieces_run(device_id, "field tensors", {{records, nullptr, (size_t)n * 32}, {items, nullptr, (size_t)cfg->source_bytes}, {out, out, (size_t)n * pitch},
+                                                   {status, status, (size_t)n * 4}, {ids.data(), nullptr, ids.size() * 4}, {nullptr, nullptr, P.desc_bytes},
+                                                   {nullptr, nullptr, P.tabs_bytes}}, [&](const Pieces& s) {
+        fields_launch(nullptr, *cfg, fw, fh, cfg->n_items, s.at<const leon::BoxRecord>(0), n, s.at<const uint32_t>(4), s.at<leon::RegionDesc>(5), s.at<int32_t>(6), P, s.at(1),
+                      (size_t)cfg->item_pitch_bytes, s.at(2), pitch, status ? s.at<int32_t>(3) : nullptr);
+        return (int)LEON_OK;
+    });
+}
+
 // The device's rows of a batch of single axes, copied back (leon_pipeline_resize_weights_device): memory of its own, the null stream
 int resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,
                           int32_t* weights, int32_t* status)
@@ -4717,6 +4996,30 @@ int leon_pipeline_accumulate_kernel(int32_t device_id, int32_t coded_width, int3
                                     void* slots, uint8_t* via, int32_t* status)
 {
     return accumulate_kernel(device_id, coded_width, coded_height, n_frames, motion_records_host, residual_records_host, cfg, hops, n, slots, via, status);
+}
+
+int32_t leon_pipeline_field_tensor_record(int32_t frame_width, int32_t frame_height, int32_t coded_width, int32_t coded_height, const leon_pipeline_field_config* cfg,
+                                          const void* items, const leon_pipeline_region* record, void* out)
+{
+    return field_tensor_record_host(frame_width, frame_height, coded_width, coded_height, cfg, items, record, out);
+}
+
+int leon_pipeline_field_tensors_device(leon_pipeline* p, int64_t window, const leon_pipeline_field_config* cfg, const leon_pipeline_field_tensors_call* call)
+{
+    return field_tensors_device(p, window, cfg, call);
+}
+
+int leon_pipeline_field_tensors(leon_pipeline* p, int64_t window, const leon_pipeline_field_config* cfg, const leon_pipeline_region* records, int32_t n, const void* source,
+                                void* out, uint64_t out_pitch_bytes, int32_t* status)
+{
+    return field_tensors(p, window, cfg, records, n, source, out, out_pitch_bytes, status);
+}
+
+int leon_pipeline_field_tensors_kernel(int32_t device_id, int32_t frame_width, int32_t frame_height, int32_t coded_width, int32_t coded_height,
+                                       const leon_pipeline_field_config* cfg, const void* items, const leon_pipeline_region* records, int32_t n, void* out,
+                                       uint64_t out_pitch_bytes, int32_t* status, uint64_t scratch_limit_bytes)
+{
+    return field_tensors_kernel(device_id, frame_width, frame_height, coded_width, coded_height, cfg, items, records, n, out, out_pitch_bytes, status, scratch_limit_bytes);
 }
 
 int leon_pipeline_resize_weights_device(int32_t device_id, int32_t n_axes, const int32_t* axes, int32_t filter, int32_t max_taps, int32_t* first, int32_t* count,

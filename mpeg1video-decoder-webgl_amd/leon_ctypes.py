@@ -57,6 +57,7 @@ PIPELINE_SYMBOLS = [
     "leon_pipeline_propagate_kernel",
     "leon_pipeline_accumulate_layout", "leon_pipeline_accumulate_record", "leon_pipeline_accumulate_device", "leon_pipeline_accumulate",
     "leon_pipeline_accumulate_kernel",
+    "leon_pipeline_field_tensor_record", "leon_pipeline_field_tensors_device", "leon_pipeline_field_tensors", "leon_pipeline_field_tensors_kernel",
     "leon_pipeline_gauge_record", "leon_pipeline_gauge_regions_device", "leon_pipeline_gauge_regions", "leon_pipeline_gauge_kernel",
     "leon_pipeline_propose_record", "leon_pipeline_propose_regions_device", "leon_pipeline_propose_regions", "leon_pipeline_propose_kernel",
     "leon_pipeline_suppress_record", "leon_pipeline_suppress_regions_device", "leon_pipeline_suppress_regions", "leon_pipeline_suppress_kernel",
@@ -375,6 +376,9 @@ GAUGE_MOTION, GAUGE_ACTIVITY = 1, 2          # LEON_GAUGE_*: the bits of a gauge
 ACCUMULATE_MOTION = 1                        # LEON_ACCUMULATE_MOTION: AX, AY, AGE
 ACCUMULATE_RESIDUAL = 2                      # LEON_ACCUMULATE_RESIDUAL: RY, RCb, RCr
 ACCUMULATE_PLANES = ("AX", "AY", "AGE", "RY", "RCb", "RCr")          # the planes of an accumulator, in their order in a slot
+FIELD_SOURCE_BUFFER, FIELD_SOURCE_MOTION, FIELD_SOURCE_RESIDUAL = 0, 1, 2          # LEON_FIELD_SOURCE_*
+FIELD_SOURCES = {"buffer": FIELD_SOURCE_BUFFER, "motion": FIELD_SOURCE_MOTION, "residual": FIELD_SOURCE_RESIDUAL}
+FIELD_MAX_CHANNELS = 8                       # LEON_FIELD_MAX_CHANNELS
 GAUGE_WORDS = 16                             # int64 words of a gauged record's statistics
 PROPOSE_MOTION, PROPOSE_ACTIVITY = 1, 2      # LEON_PROPOSE_*: the bits of a propose call's sources
 PROPOSE_INTRA = 1                            # LEON_PROPOSE_INTRA: the bit of its flags
@@ -472,6 +476,21 @@ class PipelineAccumulateLayout(C.Structure):
 class PipelineAccumulateCall(C.Structure):
     _fields_ = [("hops", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("slots", C.c_void_p), ("device_via", C.c_void_p), ("device_status", C.c_void_p),
                 ("stream", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class PipelineFieldChannel(C.Structure):
+    _fields_ = [("offset_bytes", C.c_uint32), ("row_stride", C.c_int32), ("elem_stride", C.c_int32), ("shift", C.c_int32), ("scale", C.c_float), ("bias", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
+class PipelineFieldConfig(C.Structure):
+    _fields_ = [("source", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32), ("filter", C.c_int32), ("out_width", C.c_int32), ("out_height", C.c_int32),
+                ("n_items", C.c_int32), ("reserved", C.c_int32), ("item_pitch_bytes", C.c_uint64), ("source_bytes", C.c_uint64), ("channel", PipelineFieldChannel * 8)]
+
+
+class PipelineFieldTensorsCall(C.Structure):
+    _fields_ = [("records", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32), ("source", C.c_void_p), ("device_out", C.c_void_p), ("out_pitch_bytes", C.c_uint64),
+                ("device_status", C.c_void_p), ("stream", C.c_void_p), ("reserved", C.c_uint64)]
 
 
 class PipelineTensorShape(C.Structure):
@@ -701,6 +720,14 @@ def load():
         lib.leon_pipeline_accumulate.argtypes = [C.c_void_p, C.c_int64, P(PipelineAccumulateConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.leon_pipeline_accumulate_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineAccumulateConfig), C.c_void_p,
                                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "leon_pipeline_field_tensors"):
+        P = C.POINTER
+        lib.leon_pipeline_field_tensor_record.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(PipelineFieldConfig), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.leon_pipeline_field_tensor_record.restype = C.c_int32
+        lib.leon_pipeline_field_tensors_device.argtypes = [C.c_void_p, C.c_int64, P(PipelineFieldConfig), P(PipelineFieldTensorsCall)]
+        lib.leon_pipeline_field_tensors.argtypes = [C.c_void_p, C.c_int64, P(PipelineFieldConfig), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.leon_pipeline_field_tensors_kernel.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(PipelineFieldConfig), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                           C.c_uint64, C.c_void_p, C.c_uint64]
     if hasattr(lib, "leon_pipeline_gauge_regions"):
         P = C.POINTER
         lib.leon_pipeline_gauge_record.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_void_p), P(C.c_void_p), P(PipelineGaugeConfig), C.c_void_p,
@@ -1767,6 +1794,184 @@ def accumulate_kernel(cw, ch, n_frames, motion, residual, hops, parts, slots, vi
                                                 h.ctypes.data if len(h) else None, len(h) if n is None else int(n), slots.ctypes.data, v.ctypes.data if via else None,
                                                 st.ctypes.data if status else None))
     return v[:len(h)], st[:len(h)]
+
+
+FIELD_NP_DTYPES = {"float16": np.float16, "bfloat16": np.uint16, "float32": np.float32}          # bfloat16 as bit patterns, like read_tensor
+
+
+def field_channel(offset_bytes, row_stride, elem_stride=1, shift=0, scale=1.0, bias=0.0):
+    """one channel of a field tensors call: the plane's first element offset_bytes into the item, its value under frame pixel (x, y) at
+    element offset_bytes / 2 + (y >> shift) * row_stride + (x >> shift) * elem_stride; the element is fl32(fl32(r * scale) + bias)"""
+    return (int(offset_bytes), int(row_stride), int(elem_stride), int(shift), float(scale), float(bias))
+
+
+def _per_channel(v, n):
+    """a scalar for every channel, or one value a channel"""
+    v = [float(v)] * n if np.isscalar(v) else [float(x) for x in v]
+    if len(v) != n:
+        raise ValueError("%d values for %d channels" % (len(v), n))
+    return v
+
+
+MOTION_FIELDS = ("fwd_h", "fwd_v", "bwd_h", "bwd_v")          # a motion record's four interleaved words a macroblock
+
+
+def field_channels_motion(mbw, names=("fwd_h", "fwd_v"), scale=1.0, bias=0.0):
+    """channels of a motion record's vectors (motion_layout: int16 [mbs][4] at 0) over a picture mbw macroblocks wide: cells of 16 frame
+    pixels, 4 elements apart.  VECTORS ARE IN HALF-PEL FRAME UNITS: scale = 0.5 * out_size / box_size makes them output pixels (per
+    channel: the horizontal words with the widths, the vertical ones with the heights).  scale, bias: one value, or one a channel."""
+    sc, bi = _per_channel(scale, len(names)), _per_channel(bias, len(names))
+    return [field_channel(2 * MOTION_FIELDS.index(n), 4 * int(mbw), 4, 4, sc[i], bi[i]) for i, n in enumerate(names)]
+
+
+def field_channels_residual(layout, names=("Y", "Cb", "Cr"), scale=1.0, bias=0.0):
+    """channels of a residual record's planes (layout: residual_layout's): Y at the frame's size, Cb and Cr in cells of 2 frame pixels"""
+    sc, bi = _per_channel(scale, len(names)), _per_channel(bias, len(names))
+    at = {"Y": (0, layout.luma_stride, 0), "Cb": (layout.cb_offset, layout.chroma_stride, 1), "Cr": (layout.cr_offset, layout.chroma_stride, 1)}
+    return [field_channel(at[n][0], at[n][1], 1, at[n][2], sc[i], bi[i]) for i, n in enumerate(names)]
+
+
+def field_channels_accumulate(layout, names=("AX", "AY"), scale=1.0, bias=0.0):
+    """channels of an accumulator's planes (layout: accumulate_layout's; names of ACCUMULATE_PLANES the layout holds).  AX and AY are in
+    FRAME PIXELS: scale = out_size / box_size makes them output pixels."""
+    sc, bi = _per_channel(scale, len(names)), _per_channel(bias, len(names))
+    have = accumulate_names(layout.parts)
+    out = []
+    for i, n in enumerate(names):
+        if n not in have:
+            raise ValueError("the accumulator has no plane %s (parts %d)" % (n, layout.parts))
+        chroma = n in ("RCb", "RCr")
+        out.append(field_channel(getattr(layout, n.lower() + "_offset"), layout.chroma_stride if chroma else layout.luma_stride, 1, 1 if chroma else 0, sc[i], bi[i]))
+    return out
+
+
+def field_record_status(fw, fh, n_items, record, size):
+    """the status word of one record of a field tensors call (REGION_*), in Python integers from the header's text: the reserved words,
+    the frame or item index, then per axis -- x before y -- the box and the ratio"""
+    r = [int(v) for v in record] + [0] * (8 - len(record))
+    oh, ow = int(size[0]), int(size[1])
+    if any(r[5:]):
+        return REGION_RESERVED
+    if not 0 <= r[0] < int(n_items):
+        return REGION_FRAME
+    for in_size, start, length, out, ratio in ((int(fw), r[1], r[3], ow, REGION_RATIO_X), (int(fh), r[2], r[4], oh, REGION_RATIO_Y)):
+        if in_size < 1 or length < 1 or start < 0 or start > in_size or length > in_size - start:
+            return REGION_BOX
+        if length > 16 * out:
+            return ratio
+    return REGION_OK
+
+
+def _field_pass(p, first, count, weights):
+    """one pass along axis 1 of p [rows, in] int64 -> [rows, out] int64: exact integers, saturated to int16"""
+    out = np.empty((p.shape[0], len(first)), dtype=np.int64)
+    for o in range(len(first)):
+        n = int(count[o])
+        acc = p[:, first[o]:first[o] + n] @ weights[o, :n].astype(np.int64)
+        out[:, o] = np.clip((acc + (1 << (RESIZE_PRECISION - 1))) >> RESIZE_PRECISION, -32768, 32767)
+    return out
+
+
+def field_resample(item, fw, fh, box, size, channel):
+    """r of one channel: item a 1-D int16 array of the item's elements, box = (x, y, width, height) in frame pixels, size = (out_height,
+    out_width) -> int64 [out_height, out_width], each value inside int16"""
+    off, rs, es, shift = channel[:4]
+    x, y, w, h = [int(v) for v in box]
+    oh, ow = int(size[0]), int(size[1])
+    fx, nx, wx = resize_weights(fw, x, w, ow, RESIZE_TRIANGLE)
+    fy, ny, wy = resize_weights(fh, y, h, oh, RESIZE_TRIANGLE)
+    lo, hi = int(fy.min()), int((fy + ny).max())          # the rows the vertical pass taps
+    a = np.asarray(item).reshape(-1)
+    idx = off // 2 + (np.arange(lo, hi)[:, None] >> shift) * rs + (np.arange(int(fw))[None, :] >> shift) * es
+    hz = _field_pass(a[idx].astype(np.int64), fx, nx, wx)
+    return _field_pass(hz.T.copy(), fy - lo, ny, wy).T.copy()
+
+
+def field_element(r, scale, bias, dtype="float16"):
+    """the elements of r (integers): fl32(fl32(r * scale) + bias) in np.float32, two rounded operations, then one rounding to nearest
+    even into the element type -- float16 / float32 arrays, bfloat16 as uint16 bit patterns"""
+    u = (np.asarray(r).astype(np.float32) * np.float32(scale)).astype(np.float32) + np.float32(bias)
+    if dtype == "float32":
+        return u.astype(np.float32)
+    if dtype == "float16":
+        return u.astype(np.float16)
+    if dtype != "bfloat16":
+        raise ValueError("dtype %r" % (dtype,))
+    bits = np.ascontiguousarray(u, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    return ((bits + 0x7fff + ((bits >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+def field_tensor(item, fw, fh, box, size, channels, dtype="float16"):
+    """The definition of one record of leon_pipeline_field_tensors (include/leon_pipeline.h) in numpy integers and np.float32, written
+    from the header's text and independent of the C code, on the pure-Python resize_weights: item a 1-D int16 array (the item's
+    elements from its first byte on), a frame of fw x fh, box = (x, y, width, height) in frame pixels -- one field_record_status accepts
+    --, size = (out_height, out_width), channels = [field_channel(...), ...] -> [C, out_height, out_width] of FIELD_NP_DTYPES[dtype]
+    (bfloat16 as uint16 bit patterns)."""
+    return np.stack([field_element(field_resample(item, fw, fh, box, size, c), c[4], c[5], dtype) for c in channels])
+
+
+def _field_config(source, dtype, size, channels, n_items=0, item_pitch=0, source_bytes=0, over=None):
+    """PipelineFieldConfig; `over` replaces fields, "channelN" = {field: value} those of channel N (the refusals' tests)"""
+    source = FIELD_SOURCES[source] if isinstance(source, str) else int(source)
+    dtype = TENSOR_DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+    cfg = PipelineFieldConfig(source, dtype, len(channels), RESIZE_TRIANGLE, int(size[1]), int(size[0]), int(n_items), 0, int(item_pitch), int(source_bytes))
+    for i, c in enumerate(channels[:FIELD_MAX_CHANNELS]):
+        cfg.channel[i] = PipelineFieldChannel(c[0], c[1], c[2], c[3], c[4], c[5], (C.c_int32 * 2)(0, 0))
+    for k, v in (over or {}).items():
+        if k.startswith("channel") and k != "channels":
+            for f, x in v.items():
+                setattr(cfg.channel[int(k[7:])], f, (C.c_int32 * 2)(*x) if f == "reserved" else x)
+        else:
+            setattr(cfg, k, v)
+    return cfg
+
+
+def _field_items(items):
+    if not (isinstance(items, np.ndarray) and items.dtype == np.uint8 and items.ndim == 2 and items.flags.c_contiguous):
+        raise ValueError("items: a contiguous uint8 array [n_items, item_pitch]")
+    return items
+
+
+def field_tensor_record(fw, fh, cw, ch, items, record, size, channels, source="buffer", dtype="float16", fill=0, over=None):
+    """leon_pipeline_field_tensor_record: the library's CPU evaluation of one record; items a uint8 array [n_items, item_pitch].  Returns
+    (status, tensor [C, oh, ow] of FIELD_NP_DTYPES[dtype] that holds the bytes `fill` where the library wrote nothing); LeonError where it
+    refuses the call.  over: fields of the config replaced, as _field_config takes them."""
+    items = _field_items(items)
+    cfg = _field_config(source, dtype, size, channels, items.shape[0], items.shape[1], items.size, over)
+    out = np.full((len(channels), int(size[0]), int(size[1])), 0, dtype=FIELD_NP_DTYPES[dtype])
+    out.view(np.uint8)[...] = fill
+    r = _records_array([record])
+    st = load().leon_pipeline_field_tensor_record(int(fw), int(fh), int(cw), int(ch), C.byref(cfg), items.ctypes.data, r.ctypes.data, out.ctypes.data)
+    if st < 0:
+        raise LeonError(st, load().leon_last_error().decode("utf-8", "replace"))
+    return st, out
+
+
+def field_tensors_kernel(fw, fh, cw, ch, items, records, size, channels, source="buffer", dtype="float16", pitch=None, status=True, device_id=0, fill=0, status_fill=-1,
+                         scratch_limit=0, n=None, over=None):
+    """leon_pipeline_field_tensors_kernel: k_box_tables and k_fields on items the caller supplies (uint8 [n_items, item_pitch]), records =
+    [(frame, x, y, w, h), ...] -> (out uint8 [m, pitch] pre-filled with `fill`, status [m] int32 pre-filled with `status_fill`); pitch:
+    None is the default, a region's bytes rounded up to 256; status=False hands the library NULL.  field_batch takes `out` apart."""
+    items = _field_items(items)
+    cfg = _field_config(source, dtype, size, channels, items.shape[0], items.shape[1], items.size, over)
+    r = _records_array(records)
+    nbytes = len(channels) * int(size[0]) * int(size[1]) * np.dtype(FIELD_NP_DTYPES[dtype]).itemsize
+    step = -(-nbytes // 256) * 256 if pitch is None else int(pitch)
+    out = np.full((max(1, len(r)), max(step, 1)), fill, dtype=np.uint8)
+    st, = _result_arrays(len(r), ((), status_fill, np.int32))
+    _chk(load().leon_pipeline_field_tensors_kernel(int(device_id), int(fw), int(fh), int(cw), int(ch), C.byref(cfg), items.ctypes.data, r.ctypes.data if len(r) else None,
+                                                   len(r) if n is None else int(n), out.ctypes.data, 0 if pitch is None else step, st.ctypes.data if status else None,
+                                                   int(scratch_limit)))
+    return out[:len(r)], st[:len(r)]
+
+
+def field_batch(out, n_channels, size, dtype="float16"):
+    """a host buffer of field tensors, uint8 [n, pitch] -> the view [n, C, oh, ow] of FIELD_NP_DTYPES[dtype] over the tensors' bytes"""
+    dt = np.dtype(FIELD_NP_DTYPES[dtype])
+    nbytes = int(n_channels) * int(size[0]) * int(size[1]) * dt.itemsize
+    return out[:, :nbytes].view(dt).reshape(out.shape[0], int(n_channels), int(size[0]), int(size[1])) if out.shape[1] == nbytes else \
+        np.lib.stride_tricks.as_strided(out.view(dt), shape=(out.shape[0], int(n_channels), int(size[0]), int(size[1])),
+                                        strides=(out.strides[0], int(size[0]) * int(size[1]) * dt.itemsize, int(size[1]) * dt.itemsize, dt.itemsize))
 
 
 def warp_rgb(rgb, m, size, pad=(0, 0, 0)):
@@ -2995,6 +3200,93 @@ class Pipeline:
             off = getattr(lay, name.lower() + "_offset") // 2
             out[name] = flat16[:, off:off + h * stride].view(F, h, stride)[:, :, :w]
         return out
+
+    def _field_source(self, source, buffer):
+        """(source code, n_items, item_pitch, source_bytes) of a field tensors call; buffer: a uint8 array or CUDA tensor [n_items, item_pitch]"""
+        source = FIELD_SOURCES[source] if isinstance(source, str) else int(source)
+        if source == FIELD_SOURCE_MOTION:
+            _need_output(self.motion_layout, "motion")
+        if source == FIELD_SOURCE_RESIDUAL:
+            _need_output(self.residual_layout, "residual")
+        if (source == FIELD_SOURCE_BUFFER) != (buffer is not None):
+            raise ValueError("buffer: the items of source=\"buffer\", and of no other source")
+        if buffer is None:
+            return source, 0, 0, 0
+        if buffer.dtype != (np.uint8 if isinstance(buffer, np.ndarray) else __import__("torch").uint8) or len(buffer.shape) != 2:
+            raise ValueError("buffer: uint8 [n_items, item_pitch]")
+        return source, int(buffer.shape[0]), int(buffer.shape[1]), int(buffer.shape[0]) * int(buffer.shape[1])
+
+    @staticmethod
+    def _field_bytes(channels, size, dtype, pitch):
+        nbytes = len(channels) * int(size[0]) * int(size[1]) * np.dtype(FIELD_NP_DTYPES[dtype]).itemsize
+        return nbytes, (-(-nbytes // 256) * 256 if pitch is None else int(pitch))
+
+    def field_tensors_device(self, window, records, size, channels, source="buffer", buffer=None, dtype="float16", out=None, status=None, stream=None, pitch=None):
+        """leon_pipeline_field_tensors_device: boxes of int16 fields resampled into one [N, C, h, w] batch of `dtype` ("float16",
+        "bfloat16", "float32"), cropped by the same records and through the same tables as resample_regions_device's pixel tensors, so
+        the two line up sample for sample.  records: a contiguous CUDA int32 tensor [N, 8] (leon_pipeline_region records: frame, x, y, w,
+        h, 0, 0, 0) or stacked [F, N, 8], as carry_regions_gop and propose_regions_device write them; size = (h, w); channels =
+        [field_channel(...), ...] (field_channels_motion / _residual / _accumulate build them); source: "motion" / "residual" -- the
+        window frame's record -- or "buffer" with buffer = a contiguous CUDA uint8 tensor [n_items, item_pitch], a record's `frame`
+        word being the item index (the window is not consulted then).  Queued on `stream` (None: torch's current stream) with
+        resample_regions_device's ordering: NO host synchronisation.  Returns (batch [N, C, h, w] view over `out` -- a uint8 tensor,
+        256-byte aligned, regions `pitch` bytes apart (None: a region's bytes rounded up to 256), or one the method allocates, not
+        initialised --, status [N] int32: REGION_* per record; a refused record's tensor is untouched)."""
+        import torch
+        dev = self.device_id
+        src, n_items, item_pitch, source_bytes = self._field_source(source, buffer)
+        _device_records_check("records", records, stacked=True)
+        records = records.view(-1, 8)
+        n = int(records.shape[0])
+        if buffer is not None and not (isinstance(buffer, torch.Tensor) and buffer.is_contiguous()):
+            raise ValueError("buffer: a contiguous CUDA uint8 tensor [n_items, item_pitch]")
+        nbytes, step = self._field_bytes(channels, size, dtype, pitch)
+        for name, t, dt, count in (("records", records, torch.int32, 0), ("buffer", buffer, torch.uint8, 0), ("out", out, torch.uint8, (n - 1) * step + nbytes),
+                                   ("status", status, torch.int32, n)):
+            _device_tensor_check(name, t, dt, count, dev)
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        out, status = _empty_where_none(stream, dev, [(out, max(1, n) * max(step, 1), torch.uint8), (status, max(1, n), torch.int32)])
+        cfg = _field_config(src, dtype, size, channels, n_items, item_pitch, source_bytes)
+        call = PipelineFieldTensorsCall(records.data_ptr() if n else None, n, 0, buffer.data_ptr() if buffer is not None else None, out.data_ptr(), 0 if pitch is None else step,
+                                        status.data_ptr(), self._stream_handle(stream), 0)
+        _chk(self.lib.leon_pipeline_field_tensors_device(self.h, int(window), C.byref(cfg), C.byref(call)))
+        tdt = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32}[dtype]
+        oh, ow = int(size[0]), int(size[1])
+        e = nbytes // max(1, len(channels) * oh * ow)
+        batch = torch.as_strided(out.view(tdt), (n, len(channels), oh, ow), (step // e, oh * ow, ow, 1))
+        return batch, status.view(-1)[:n]
+
+    def field_tensors(self, window, records, size, channels, source="buffer", buffer=None, dtype="float16", pitch=None, fill=0, status_fill=0):
+        """leon_pipeline_field_tensors: the same call from host arrays, synchronous -- records = [(frame, x, y, w, h), ...], buffer a uint8
+        numpy array [n_items, item_pitch].  Returns (batch [N, C, h, w] of FIELD_NP_DTYPES[dtype] -- bfloat16 as uint16 bit patterns --
+        over a buffer pre-filled with the byte `fill`, which a refused record's tensor still holds, status [N] int32)."""
+        src, n_items, item_pitch, source_bytes = self._field_source(source, buffer)
+        r = _records_array(records)
+        nbytes, step = self._field_bytes(channels, size, dtype, pitch)
+        out = np.full((max(1, len(r)), max(step, 1)), fill, dtype=np.uint8)
+        st, = _result_arrays(len(r), ((), status_fill, np.int32))
+        cfg = _field_config(src, dtype, size, channels, n_items, item_pitch, source_bytes)
+        _chk(self.lib.leon_pipeline_field_tensors(self.h, int(window), C.byref(cfg), r.ctypes.data if len(r) else None, len(r),
+                                                  _field_items(buffer).ctypes.data if buffer is not None else None, out.ctypes.data, 0 if pitch is None else step, st.ctypes.data))
+        return field_batch(out[:len(r)], len(channels), size, dtype), st[:len(r)]
+
+    def motion_tensors(self, window, records, size, channels=("fwd_h", "fwd_v"), scale=1.0, bias=0.0, **kw):
+        """field_tensors_device on the window frames' motion records: the vectors named (MOTION_FIELDS) as [N, C, h, w].  Vectors are in
+        HALF-PEL FRAME units and the call does not rescale them by the resize ratio: scale = 0.5 * out_size / box_size gives output
+        pixels for boxes of one size (one value, or one a channel)."""
+        return self.field_tensors_device(window, records, size, field_channels_motion(self.info.coded_width // 16, channels, scale, bias), source="motion", **kw)
+
+    def residual_tensors(self, window, records, size, channels=("Y", "Cb", "Cr"), scale=1.0, bias=0.0, **kw):
+        """field_tensors_device on the window frames' residual records: Y, Cb, Cr (chroma replicated to the frame's size) as [N, C, h, w];
+        they stay YCbCr differences"""
+        return self.field_tensors_device(window, records, size, field_channels_residual(_need_output(self.residual_layout, "residual"), channels, scale, bias),
+                                         source="residual", **kw)
+
+    def accumulate_tensors(self, acc, records, size, names=("AX", "AY"), scale=1.0, bias=0.0, **kw):
+        """field_tensors_device on accumulate_gop's dict `acc`: the planes named as [N, C, h, w].  A record's `frame` word is the position
+        in gop_frames(window, src), the row of acc's planes.  AX and AY are in FRAME PIXELS: scale = out_size / box_size gives output
+        pixels."""
+        return self.field_tensors_device(-1, records, size, field_channels_accumulate(acc["layout"], names, scale, bias), source="buffer", buffer=acc["slots"], **kw)
 
     def read_frame(self, frame):
         out = np.empty((self.info.frame_height, self.info.frame_width, 4), dtype=np.uint8)

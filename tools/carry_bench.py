@@ -46,11 +46,21 @@ displacement) with the elementwise torch adds around them -- no saturation, rest
 first call is k_propagate at stride 1, int16, 4 planes, timed by itself as well.  The pipeline then runs with residual=True.  --parts
 names the parts timed (under a profiler one at a time: the launches of parts 1 and 2 have the same grid).
 
+--fields: boxes of the records as a model's tensors instead (leon_pipeline_field_tensors; k_box_tables and k_fields): --boxes seeded
+boxes of 16 .. --max-box pixels a side spread over the window's frames to 224 x 224 fp16, once from the motion records (2 channels:
+fwd_h, fwd_v at scale 0.5) and once from the residual records (3 channels: Y, Cb, Cr at scale 1 / 128), one call each, from the enqueue
+to the synchronisation of the stream; the bytes the call writes; the first --fields-check records against field_tensor on the records
+read back; and the road a user has today for --torch-boxes of the same boxes on the same views, box by box: the cells under the box,
+repeat_interleave to pixels, the crop, F.interpolate(mode="bilinear", antialias=True), a multiply-add and the cast -- a yardstick of
+time alone: its filter is not the pixel tensors' and its values differ.  The pipeline then runs with residual=True.  --fields-source
+names the sources timed (under a profiler one at a time: the launches have the same names).
+
   python tools/carry_bench.py [--boxes 4096] [--reps 20] [--max-box 256] [--host-boxes N] [--gauge [--gauge-check 64]]
   python tools/carry_bench.py --maps [--reps 20]
   python tools/carry_bench.py --propose [--reps 20] [--mv-min 2] [--ac-min 256] [--max-boxes 16] [--propose-check 8]
   python tools/carry_bench.py --suppress | --match [--reps 20] [--overlap-check 2]
-  python tools/carry_bench.py --accumulate [--reps 20] [--parts 1,2,3]"""
+  python tools/carry_bench.py --accumulate [--reps 20] [--parts 1,2,3]
+  python tools/carry_bench.py --fields [--boxes 4096] [--reps 20] [--max-box 256] [--torch-boxes 256] [--fields-check 4] [--fields-source motion,residual]"""
 import argparse
 import json
 import os
@@ -365,6 +375,73 @@ def accumulate_bench(a, pipe, window, frames):
     print(json.dumps(result))
 
 
+def fields_bench(a, pipe, window, frames):
+    import numpy as np
+    import torch
+    import torch.nn.functional as F
+    import leon_ctypes as L
+    fw, fh, cw, ch, n = pipe.info.frame_width, pipe.info.frame_height, pipe.info.coded_width, pipe.info.coded_height, len(frames)
+    rng = np.random.default_rng(224)
+    N, size = a.boxes, (224, 224)
+    w, h = rng.integers(16, a.max_box + 1, size=N), rng.integers(16, a.max_box + 1, size=N)
+    recs = np.zeros((N, 8), dtype=np.int32)
+    recs[:, 0] = np.arange(N) % n
+    recs[:, 1], recs[:, 2], recs[:, 3], recs[:, 4] = rng.integers(0, fw - w + 1), rng.integers(0, fh - h + 1), w, h
+    result = {"bench": "fields", "frame": [fw, fh], "coded": [cw, ch], "window_frames": n, "boxes": N, "box_side": [16, a.max_box], "size": list(size), "dtype": "float16",
+              "reps": a.reps, "sources": {}}
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        dev = torch.from_numpy(recs).cuda()
+        for source in a.fields_source:
+            C_ = 2 if source == "motion" else 3
+            scale = 0.5 if source == "motion" else 1.0 / 128
+            out = torch.empty(N * C_ * size[0] * size[1] * 2, dtype=torch.uint8, device="cuda")
+            status = torch.empty(N, dtype=torch.int32, device="cuda")
+            call = (lambda: pipe.motion_tensors(window, dev, size, scale=scale, out=out, status=status)) if source == "motion" else \
+                (lambda: pipe.residual_tensors(window, dev, size, scale=scale, out=out, status=status))
+            (batch, _), t = timed(torch, st, a.reps, call)
+            if int((status != 0).sum().item()) != 0:
+                raise RuntimeError("%s: a record was refused" % source)
+            # against the definition, on the records read back
+            for k in range(min(a.fields_check, N)):
+                f = int(recs[k, 0])
+                if source == "motion":
+                    item, chans = np.ascontiguousarray(pipe.read_motion(window, f)[0]).reshape(-1), L.field_channels_motion(cw // 16, scale=scale)
+                else:
+                    item = np.concatenate([np.ascontiguousarray(p).reshape(-1) for p in pipe.read_residual(window, f)])
+                    chans = [L.field_channel(0, cw, 1, 0, scale), L.field_channel(2 * cw * ch, cw // 2, 1, 1, scale), L.field_channel(2 * cw * ch + 2 * (cw // 2) * (ch // 2), cw // 2, 1, 1, scale)]
+                if not np.array_equal(batch[k].cpu().numpy(), L.field_tensor(item, fw, fh, recs[k, 1:5], size, chans)):
+                    raise RuntimeError("%s: record %d differs from field_tensor" % (source, k))
+            # the road a user has today, box by box on the same views
+            M = min(a.torch_boxes, N)
+            views = {}
+            for f in sorted(set(int(v) for v in recs[:M, 0])):
+                views[f] = (pipe.motion_view(window, f)[0][..., :2].permute(2, 0, 1),) if source == "motion" else pipe.residual_view(window, f)
+            res = torch.empty((M, C_) + size, dtype=torch.float16, device="cuda")
+
+            def torch_road():
+                for k in range(M):
+                    f, x, y, bw, bh = (int(v) for v in recs[k, :5])
+                    planes = []
+                    for q, v in enumerate(views[f]):
+                        s = 4 if source == "motion" else (0 if q == 0 else 1)
+                        v = v if v.dim() == 3 else v[None]
+                        cells = v[:, y >> s:((y + bh - 1) >> s) + 1, x >> s:((x + bw - 1) >> s) + 1]
+                        px = cells.repeat_interleave(1 << s, dim=1).repeat_interleave(1 << s, dim=2) if s else cells
+                        y0, x0 = y - ((y >> s) << s), x - ((x >> s) << s)
+                        planes.append(px[:, y0:y0 + bh, x0:x0 + bw])
+                    crop = torch.cat(planes).to(torch.float32)[None]
+                    res[k] = (F.interpolate(crop, size=size, mode="bilinear", antialias=True, align_corners=False)[0] * scale + 0.0).to(torch.float16)
+                return res
+            _, road = timed(torch, st, max(2, a.reps // 4), torch_road)
+            written = N * C_ * size[0] * size[1] * 2
+            result["sources"][source] = {"channels": C_, "call": t, "us_per_box": round(t["us"] / N, 3), "bytes_written": written, "write_gb_per_s": round(written / t["us"] / 1e3, 1),
+                                         "records_checked_against_field_tensor": min(a.fields_check, N),
+                                         "torch_road": dict(road, boxes=M, us_per_box=round(road["us"] / M, 2)),
+                                         "torch_road_per_box_over_call_per_box": round((road["us"] / M) / (t["us"] / N), 1)}
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--maps", action="store_true", help="dense maps (k_propagate) instead of boxes")
@@ -380,6 +457,10 @@ def main():
     ap.add_argument("--overlap-check", type=int, default=2, help="sets compared with suppress_boxes / match_boxes")
     ap.add_argument("--accumulate", action="store_true", help="motion and residual accumulated over the GOP (k_accumulate) instead of boxes carried")
     ap.add_argument("--parts", type=lambda v: [int(x) for x in v.split(",")], default=[1, 2, 3], help="--accumulate: the parts timed, e.g. 3 alone under a profiler")
+    ap.add_argument("--fields", action="store_true", help="boxes of the motion and residual records as fp16 tensors (k_fields) instead of boxes carried")
+    ap.add_argument("--torch-boxes", type=int, default=256, help="--fields: boxes of the torch yardstick")
+    ap.add_argument("--fields-check", type=int, default=4, help="--fields: records compared with field_tensor")
+    ap.add_argument("--fields-source", type=lambda v: v.split(","), default=["motion", "residual"], help="--fields: the sources timed")
     ap.add_argument("--boxes", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--max-box", type=int, default=256)
@@ -398,13 +479,13 @@ def main():
         held["window"], held["frames"] = window, list(frames)
         delivered.set()
         return False
-    pipe = L.Pipeline(data, on_window=on_window, motion=True, activity=a.gauge or a.propose, residual=a.accumulate, gops_per_window=stream_1080p.VARIED_GOPS, gpu_parser=True, parser_threads=16)
+    pipe = L.Pipeline(data, on_window=on_window, motion=True, activity=a.gauge or a.propose, residual=a.accumulate or a.fields, gops_per_window=stream_1080p.VARIED_GOPS, gpu_parser=True, parser_threads=16)
     try:
         if not delivered.wait(300):
             raise RuntimeError("no window was delivered: %s" % (pipe.error,))
         window, frames = held["window"], held["frames"]
-        if a.maps or a.propose or a.suppress or a.match or a.accumulate:
-            (maps_bench if a.maps else propose_bench if a.propose else accumulate_bench if a.accumulate else overlap_bench)(a, pipe, window, frames)
+        if a.maps or a.propose or a.suppress or a.match or a.accumulate or a.fields:
+            (maps_bench if a.maps else propose_bench if a.propose else accumulate_bench if a.accumulate else fields_bench if a.fields else overlap_bench)(a, pipe, window, frames)
             pipe.release_window(window)
             pipe.wait()
             return
